@@ -27,6 +27,10 @@ Prints ONE JSON line on rank 0: metric/value (whole-job scalar-muls/s), roofline
 algorithmic 32x32 multiply-adds per second against the chip's peak; kernel time from HIP events
 on the launch stream) and cpu_baseline (the C oracle timed on this box's host cores on a bounded
 sample of the same inputs, which doubles as a parity spot-check of the GPU output).
+
+--dump-outputs DIR: after the timed steps, the points the last timed step computed go to DIR/result.npy (float64, at
+most 64 MB: a fixed seeded sample of the rows of a larger batch; the inputs are seeded, so two builds of the library run
+with the same flags can be compared output for output).
 """
 import argparse
 import json
@@ -100,7 +104,13 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline duration (all legs together)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-clock-probe", action="store_true", help="skip the ~1 s rocm-smi clock sampling under load (N = 1)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result of the last timed step to DIR/result.npy (see dump_outputs) "
+                         "so that two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def host_cores():
@@ -155,6 +165,28 @@ def cpu_baseline(workload, inputs, gpu_out, target_s):
             "sample": "first %d of the rank-0 batch (%s), C oracle oracle/forge_ec_oracle.c (a restatement of the "
                       "reference's Rust, not rustc output), %d threads, %.1f s" % (n, workload, cores, dt),
             "parity_sample_bit_exact": ok}
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, result, suffix="", budget=DUMP_BUDGET_BYTES):
+    """Write `result` -- the (n, limbs) uint64 points of one step, as a caller of the *_dev path receives them -- to
+    out_dir/result<suffix>.npy, float64 of shape (m, 2 * limbs): every 64-bit limb as its two 32-bit halves, low half
+    first (float64 holds them exactly), and the m row indices into the batch to out_dir/result_rows<suffix>.npy
+    (float64).  m = n when both files fit in `budget` bytes, else a fixed seeded sample of the rows in ascending order:
+    the same rows for the same n from run to run."""
+    n, limbs = result.shape
+    m = min(n, max(0, budget - 4096) // (2 * limbs * 8 + 8))   # 4096: room for the two .npy headers
+    if m == n:
+        rows = np.arange(n)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, m, replace=False))
+    words = np.ascontiguousarray(result[rows], dtype="<u8").view("<u4").reshape(m, 2 * limbs)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "result%s.npy" % suffix), words.astype(np.float64))
+    np.save(os.path.join(out_dir, "result_rows%s.npy" % suffix), rows.astype(np.float64))
 
 
 def load_checker():
@@ -546,6 +578,11 @@ def main(argv=None, platform_factory=None, script=None):
     elapsed = elapsed_by_mode[modes[0]]
     # the *_dev launches only enqueue: a fault a kernel reported is visible now (the host-pointer calls check themselves)
     ctx.check()
+    if args.dump_outputs:
+        # what the last timed step wrote, copied before anything below launches again into the same buffers
+        plat.synchronize()
+        last_out = d_out[(args.steps - 1) & 1].cpu().numpy().view(np.uint64).copy()
+        dump_outputs(args.dump_outputs, last_out, "" if world == 1 else "_rank%d" % rank, DUMP_BUDGET_BYTES // world)
 
     # kernel duration from HIP events on the launch stream (separate passes, not in `value`)
     gather0 = gathers.get(modes[0])

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -91,3 +92,82 @@ def test_bench_strong_scaling_line_on_one_gpu():
         assert t["scaling"] == "strong" and t["config"]["global_batch"] == 1 << 13 == t["config"]["batch_per_gpu"]
         assert abs(t["value"] - (1 << 13) / (t["ms_per_step"] * 1e-3)) / t["value"] < 1e-6
         assert t["cpu_baseline"]["parity_sample_bit_exact"] is True
+
+
+def _dumped_points(words):
+    """result.npy's float64 32-bit halves back to the (rows, limbs) uint64 points."""
+    assert words.dtype == np.float64 and words.shape[1] % 2 == 0
+    halves = words.astype(np.uint64)
+    assert np.array_equal(halves.astype(np.float64), words) and int(halves.max(initial=0)) < 1 << 32
+    return np.ascontiguousarray(halves.astype(np.uint32)).view(np.uint64)
+
+
+def test_dump_outputs_rows_and_budget(tmp_path):
+    """dump_outputs: every row while the files fit the budget, else the same seeded sample of rows at every call, the
+    files together within the budget, and the 32-bit halves decode to the rows they came from."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    result = rng.integers(0, 1 << 64, size=(1000, 12), dtype=np.uint64, endpoint=False)
+    bench.dump_outputs(str(tmp_path / "all"), result)
+    rows = np.load(tmp_path / "all" / "result_rows.npy")
+    assert np.array_equal(rows, np.arange(1000)) and np.array_equal(_dumped_points(np.load(tmp_path / "all" / "result.npy")), result)
+    budget = 40000
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), result, budget=budget)
+        assert sum(os.path.getsize(tmp_path / name / f) for f in os.listdir(tmp_path / name)) <= budget
+    rows = np.load(tmp_path / "a" / "result_rows.npy")
+    assert 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "result_rows.npy"))
+    words = np.load(tmp_path / "a" / "result.npy")
+    assert np.array_equal(words, np.load(tmp_path / "b" / "result.npy"))
+    assert np.array_equal(_dumped_points(words), result[rows.astype(np.int64)])
+
+
+@pytest.mark.parametrize("workload", ["secp256k1-var", "ed25519-fixed", "secp256k1-double"])
+def test_dump_outputs_one_rank_rehearsal(tmp_path, workload):
+    """bench.py --dump-outputs on one rank, the oracle standing in for the kernels (tests/bench_rehearsal.py): --steps is
+    the number of timed steps, ms_per_step is in the line, and result.npy holds what the step computed from the seeded
+    inputs -- identical in a second run."""
+    sys.path.insert(0, ROOT)
+    from forge_ec_amd import synth
+    from oracle import c_oracle
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rehearsal.py"), "--gpus", "1", "--steps", "3",
+                            "--warmup", "1", "--log2-batch", "6", "--workload", workload, "--no-cpu-baseline",
+                            "--dump-outputs", str(tmp_path / run)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout + r.stderr
+        t = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert t["steps"] == 3 and t["ms_per_step"] > 0
+        assert np.array_equal(np.load(tmp_path / run / "result_rows.npy"), np.arange(64))
+        outs.append(_dumped_points(np.load(tmp_path / run / "result.npy")))
+    assert np.array_equal(outs[0], outs[1])
+    cid = {"secp256k1": 0, "p256": 1, "ed25519": 2}[workload.split("-")[0]]
+    k = synth.scalars(64, cid, 1000)
+    if workload.endswith("-var"):
+        want = c_oracle.batch_mul(cid, k, synth.points(64, cid, 1001))
+    elif workload.endswith("-fixed"):
+        want = c_oracle.batch_mul_fixed(cid, k, c_oracle.generator(cid))
+    else:
+        want = c_oracle.batch_double_mul(cid, k, synth.scalars(64, cid, 1001), synth.points(64, cid, 1002))
+    assert np.array_equal(outs[0], want)
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_match_the_oracle(tmp_path):
+    """bench.py --dump-outputs on the GPU: the dumped points of the last timed step equal the oracle's on the seeded
+    inputs, row for row."""
+    sys.path.insert(0, ROOT)
+    from forge_ec_amd import synth
+    from oracle import c_oracle
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "secp256k1-var", "--log2-batch", "13",
+                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-clock-probe",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    t = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert t["steps"] == 3 and t["ms_per_step"] > 0
+    assert np.array_equal(np.load(tmp_path / "result_rows.npy"), np.arange(1 << 13))
+    want = c_oracle.batch_mul(0, synth.scalars(1 << 13, 0, 1000), synth.points(1 << 13, 0, 1001), nthreads=8)
+    assert np.array_equal(_dumped_points(np.load(tmp_path / "result.npy")), want)
