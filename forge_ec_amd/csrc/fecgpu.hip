@@ -2052,8 +2052,11 @@ int schnorr_batch_verify(fec_ctx* ctx, int curve, const uint64_t* pk_xy, const u
   if (edw) {
     // Ed25519 (the generic batch_verify::<Ed25519, D>): the same pipeline with that curve's kernels -- multiply(G, .) by
     // the table kernel, the two variable-base products by the scheduler kernel -- one after the other on the ctx stream
-    // work area: s*a (32 n), from_affine(P) (128 n), e*P (128 n), R + e*P (128 n)
-    char* work = static_cast<char*>(scratch_for(ctx, ctx->stream, n * (32 + 3 * pb)));
+    // work area: s*a (32 n), from_affine(P) (128 n), e*P (128 n), R + e*P (128 n), then the popcount-sort area of the
+    // table kernel (n >= 2^16).  One request: scratch_for hands every request on this stream the same buffer, so the
+    // sort area must not be asked for separately while s*a lives in it.
+    const size_t ed_work = ed_fixed_work_bytes(n);
+    char* work = static_cast<char*>(scratch_for(ctx, ctx->stream, n * (32 + 3 * pb) + ed_work));
     if (!work) return FEC_E_OOM;
     u32* sa = reinterpret_cast<u32*>(work);
     u32* pp = reinterpret_cast<u32*>(work + n * 32);
@@ -2066,8 +2069,16 @@ int schnorr_batch_verify(fec_ctx* ctx, int curve, const uint64_t* pk_xy, const u
       rc = L.done();
       if (rc != FEC_OK) return rc;
     }
-    rc = launch_ed_fixed(ctx, (const u64*)sa, ctx->d_gen[FEC_ED25519], ctx->h_gen_ed, (u64*)ctx->d_buf[5], n, nullptr);   // A_i (266-268)
+    rc = ensure_ed_table(ctx, ctx->d_gen[FEC_ED25519], ctx->h_gen_ed, ctx->stream);
     if (rc != FEC_OK) return rc;
+    ensure_gen_prefix(ctx, FEC_ED25519, ctx->stream, n);
+    {
+      Launch L(ctx, nullptr, ed_work ? "k_ed_fixed_sorted (+ k_ed_pc_hist, k_ed_pc_scan, k_ed_pc_scatter)" : "k_ed_fixed_base");
+      ed_fixed_launch(sched_env(ctx), sa, reinterpret_cast<const u32*>(ctx->d_gen[FEC_ED25519]), ctx->d_ed_table,
+                      (u32*)ctx->d_buf[5], n, ed_work ? work + n * (32 + 3 * pb) : nullptr, L.s);   // A_i (266-268)
+      rc = L.done();
+      if (rc != FEC_OK) return rc;
+    }
     {
       Launch L(ctx, nullptr, "k_schnorr_pre + k_ed_fixed_base + k_ed_mul_pers x2 + k_schnorr_mid");
       const SchedEnv env = sched_env(ctx);

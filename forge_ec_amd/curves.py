@@ -312,7 +312,7 @@ class Context:
         _check(self._lib.fec_schnorr_batch_verify_secp256k1(self._h, _ptr(pk), _ptr(pi), _ptr(rr), _ptr(ri), _ptr(ss),
                                                             _ptr(aa), _ptr(ee), n, _ptr(res), _ptr(sides), _ptr(sinf)),
                "fec_schnorr_batch_verify_secp256k1")
-        return bool(res[0]), sides, sinf
+        return bool(res[0] == 1), sides, sinf
 
     def schnorr_batch_verify(self, curve, pk_xy, r_xy, s, a, e, pk_inf=None, r_inf=None):
         """schnorr::batch_verify::<C, D> (schnorr.rs:194-290) for any curve; as the secp256k1 form.  (ED25519: the release
@@ -332,7 +332,8 @@ class Context:
         sinf = np.zeros(2, dtype=np.uint8)
         _check(self._lib.fec_schnorr_batch_verify(self._h, curve, _ptr(pk), _ptr(pi), _ptr(rr), _ptr(ri), _ptr(ss), _ptr(aa),
                                                   _ptr(ee), n, _ptr(res), _ptr(sides), _ptr(sinf)), "fec_schnorr_batch_verify")
-        return bool(res[0]), sides, sinf
+        # (ED25519: 2 means the reference panics in to_affine -- not a verified batch)
+        return bool(res[0] == 1), sides, sinf
 
     def schnorr_batch_verify_ed25519(self, pk_xy, r_xy, s, a, e, pk_inf=None, r_inf=None):
         """fec_schnorr_batch_verify_ed25519: schnorr::batch_verify::<Ed25519, D> with the scalar Mul as the reference's

@@ -309,7 +309,7 @@ inline bool batch_verify(GpuContext& ctx, const std::vector<AffinePoint<FEC_SECP
                                            reinterpret_cast<const uint64_t*>(weights.data()),
                                            reinterpret_cast<const uint64_t*>(challenges.data()), n, &result,
                                            nullptr, nullptr));
-  return result != 0;
+  return result == 1;   // (2 -- the reference panics -- is not a verified batch)
 }
 }  // namespace schnorr
 

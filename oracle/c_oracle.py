@@ -74,7 +74,7 @@ def lib():
         L.fo_p256_ecdsa_verify.restype = ctypes.c_int
         L.fo_batch_p256_ecdsa_verify.argtypes = [p, p, p, p, p, p, ctypes.c_size_t, ctypes.c_int]
         L.fo_batch_p256_ecdsa_verify.restype = None
-        L.fo_ecdsa_batch_verify.argtypes = [ctypes.c_int, p, p, p, p, p, p, ctypes.c_size_t, p]
+        L.fo_ecdsa_batch_verify.argtypes = [ctypes.c_int, p, p, p, p, p, p, ctypes.c_size_t, p, ctypes.c_int]
         L.fo_ecdsa_batch_verify.restype = ctypes.c_int
         L.fo_batch_validate_point.argtypes = [ctypes.c_int, p, p, p, ctypes.c_size_t, ctypes.c_int]
         L.fo_batch_validate_point.restype = None
@@ -82,11 +82,11 @@ def lib():
         L.fo_batch_ecdh.restype = None
         L.fo_batch_ed25519_eddsa_verify.argtypes = [p, p, p, p, p, p, p, ctypes.c_size_t, ctypes.c_int]
         L.fo_batch_ed25519_eddsa_verify.restype = None
-        L.fo_secp256k1_schnorr_batch_verify.argtypes = [p, p, p, p, p, p, p, ctypes.c_size_t, p, p]
+        L.fo_secp256k1_schnorr_batch_verify.argtypes = [p, p, p, p, p, p, p, ctypes.c_size_t, p, p, ctypes.c_int]
         L.fo_secp256k1_schnorr_batch_verify.restype = ctypes.c_int
-        L.fo_p256_schnorr_batch_verify.argtypes = [p, p, p, p, p, p, p, ctypes.c_size_t, p, p]
+        L.fo_p256_schnorr_batch_verify.argtypes = [p, p, p, p, p, p, p, ctypes.c_size_t, p, p, ctypes.c_int]
         L.fo_p256_schnorr_batch_verify.restype = ctypes.c_int
-        L.fo_ed25519_schnorr_batch_verify.argtypes = [p, p, p, p, p, p, p, ctypes.c_size_t, p, p, p]
+        L.fo_ed25519_schnorr_batch_verify.argtypes = [p, p, p, p, p, p, p, ctypes.c_size_t, p, p, p, ctypes.c_int]
         L.fo_ed25519_schnorr_batch_verify.restype = ctypes.c_int
         L.fo_ed25519_scalar_mul_release.argtypes = [p, p, p]
         L.fo_ed25519_scalar_mul_release.restype = ctypes.c_int
@@ -316,16 +316,16 @@ def batch_p256_ecdsa_verify(digests, r, s, pk_xy, pk_inf=None, nthreads=1):
     return out
 
 
-def ecdsa_batch_verify(curve, digests, r, s, pk_xy, pk_inf, a):
+def ecdsa_batch_verify(curve, digests, r, s, pk_xy, pk_inf, a, nthreads=1):
     """Ecdsa::<C, D>::batch_verify (ecdsa.rs:287-391), curve 0 / 1: -> (status, detail (16,) uint64 = r_sum,
-    r_scalar_sum)."""
+    r_scalar_sum).  nthreads: threads for the per-element products (the result does not depend on it)."""
     digests = np.ascontiguousarray(np.asarray(digests, dtype=np.uint8)).reshape(-1, 32)
     r, s, pk_xy, a = _u64(r), _u64(s), _u64(pk_xy), _u64(a)
     n = digests.shape[0]
     inf = np.ascontiguousarray(np.asarray(pk_inf, dtype=np.uint8)) if pk_inf is not None else None
     detail = np.zeros(16, dtype=np.uint64)
     rc = lib().fo_ecdsa_batch_verify(curve, _ptr(digests), _ptr(r), _ptr(s), _ptr(pk_xy),
-                                     _ptr(inf) if inf is not None else None, _ptr(a), n, _ptr(detail))
+                                     _ptr(inf) if inf is not None else None, _ptr(a), n, _ptr(detail), nthreads)
     if rc < 0:
         raise ValueError("fo_ecdsa_batch_verify rc=%d" % rc)
     return rc, detail
@@ -365,7 +365,7 @@ def batch_ed25519_eddsa_verify(r_xy, r_inf, pk_xy, pk_inf, s, k, nthreads=1):
     return out
 
 
-def secp256k1_schnorr_batch_verify(pk_xy, pk_inf, r_xy, r_inf, s, a, e):
+def secp256k1_schnorr_batch_verify(pk_xy, pk_inf, r_xy, r_inf, s, a, e, nthreads=1):
     """-> (result, sides (16,) uint64, sides_inf (2,) uint8)."""
     pk_xy, r_xy, s, a, e = _u64(pk_xy), _u64(r_xy), _u64(s), _u64(a), _u64(e)
     n = s.size // 4
@@ -375,14 +375,16 @@ def secp256k1_schnorr_batch_verify(pk_xy, pk_inf, r_xy, r_inf, s, a, e):
     sinf = np.zeros(2, dtype=np.uint8)
     rc = lib().fo_secp256k1_schnorr_batch_verify(_ptr(pk_xy), _ptr(pi) if pi is not None else None, _ptr(r_xy),
                                                  _ptr(ri) if ri is not None else None, _ptr(s), _ptr(a), _ptr(e),
-                                                 n, _ptr(sides), _ptr(sinf))
+                                                 n, _ptr(sides), _ptr(sinf), nthreads)
+    if rc < 0:
+        raise MemoryError("fo_secp256k1_schnorr_batch_verify")
     return rc, sides, sinf
 
 
-def schnorr_batch_verify(curve, pk_xy, pk_inf, r_xy, r_inf, s, a, e):
+def schnorr_batch_verify(curve, pk_xy, pk_inf, r_xy, r_inf, s, a, e, nthreads=1):
     """schnorr::batch_verify::<C, D> for curve 0 (secp256k1) / 1 (P-256): -> (result, sides (16,), sides_inf (2,))."""
     if curve == SECP256K1:
-        return secp256k1_schnorr_batch_verify(pk_xy, pk_inf, r_xy, r_inf, s, a, e)
+        return secp256k1_schnorr_batch_verify(pk_xy, pk_inf, r_xy, r_inf, s, a, e, nthreads)
     if curve != P256:
         raise ValueError("schnorr batch_verify: curve 0 or 1")
     pk_xy, r_xy, s, a, e = _u64(pk_xy), _u64(r_xy), _u64(s), _u64(a), _u64(e)
@@ -393,11 +395,13 @@ def schnorr_batch_verify(curve, pk_xy, pk_inf, r_xy, r_inf, s, a, e):
     sinf = np.zeros(2, dtype=np.uint8)
     rc = lib().fo_p256_schnorr_batch_verify(_ptr(pk_xy), _ptr(pi) if pi is not None else None, _ptr(r_xy),
                                             _ptr(ri) if ri is not None else None, _ptr(s), _ptr(a), _ptr(e), n,
-                                            _ptr(sides), _ptr(sinf))
+                                            _ptr(sides), _ptr(sinf), nthreads)
+    if rc < 0:
+        raise MemoryError("fo_p256_schnorr_batch_verify")
     return rc, sides, sinf
 
 
-def ed25519_schnorr_batch_verify(pk_xy, pk_inf, r_xy, r_inf, s, a, e):
+def ed25519_schnorr_batch_verify(pk_xy, pk_inf, r_xy, r_inf, s, a, e, nthreads=1):
     """schnorr::batch_verify::<Ed25519, D> under the release profile (wrapping u128 sums in the scalar Mul):
     -> (result 0 / 1 / 2 = the reference panics in to_affine, sides (16,), sides_inf (2,), debug_build_panics 0 / 1)."""
     pk_xy, r_xy, s, a, e = _u64(pk_xy), _u64(r_xy), _u64(s), _u64(a), _u64(e)
@@ -409,7 +413,9 @@ def ed25519_schnorr_batch_verify(pk_xy, pk_inf, r_xy, r_inf, s, a, e):
     dbg = np.zeros(1, dtype=np.uint8)
     rc = lib().fo_ed25519_schnorr_batch_verify(_ptr(pk_xy), _ptr(pi) if pi is not None else None, _ptr(r_xy),
                                                _ptr(ri) if ri is not None else None, _ptr(s), _ptr(a), _ptr(e), n,
-                                               _ptr(sides), _ptr(sinf), _ptr(dbg))
+                                               _ptr(sides), _ptr(sinf), _ptr(dbg), nthreads)
+    if rc < 0:
+        raise MemoryError("fo_ed25519_schnorr_batch_verify")
     return rc, sides, sinf, int(dbg[0])
 
 

@@ -12,6 +12,7 @@
 #include "forge_ec_oracle.h"
 
 #include <pthread.h>
+#include <stdlib.h>
 #include <string.h>
 
 typedef uint64_t u64;
@@ -1284,6 +1285,30 @@ static void run_jobs(job_t proto, size_t n, int nthreads) {
   for (int t = 0; t < nthreads; ++t) pthread_join(th[t], NULL);
 }
 
+/* The same split for any per-element body: body(arg, lo, hi) over [0, n) on nthreads threads (1: inline).  The batch
+ * verifiers below compute their independent per-element products this way and keep every fold and early return
+ * sequential, so the thread count cannot change a result. */
+typedef struct { void (*body)(void*, size_t, size_t); void* arg; size_t lo, hi; } range_t;
+static void* range_worker(void* p) {
+  range_t* r = (range_t*)p;
+  r->body(r->arg, r->lo, r->hi);
+  return NULL;
+}
+static void run_ranges(void (*body)(void*, size_t, size_t), void* arg, size_t n, int nthreads) {
+  if (nthreads < 1) nthreads = 1;
+  if (nthreads > 256) nthreads = 256;
+  if ((size_t)nthreads > n) nthreads = n ? (int)n : 1;
+  pthread_t th[256];
+  range_t jobs[256];
+  for (int t = 0; t < nthreads; ++t) {
+    range_t r = {body, arg, n * (size_t)t / (size_t)nthreads, n * (size_t)(t + 1) / (size_t)nthreads};
+    jobs[t] = r;
+  }
+  if (nthreads == 1) { range_worker(&jobs[0]); return; }
+  for (int t = 0; t < nthreads; ++t) pthread_create(&th[t], NULL, range_worker, &jobs[t]);
+  for (int t = 0; t < nthreads; ++t) pthread_join(th[t], NULL);
+}
+
 void fo_batch_mul(int curve, const u64* scalars, const u64* points, u64* out, size_t n, int nthreads) {
   job_t j = {0, curve, scalars, NULL, points, out, NULL, 0, 0};
   run_jobs(j, n, nthreads);
@@ -1368,43 +1393,77 @@ static void ns_add(const u64 a[4], const u64 b[4], u64 r[4]) {            /* p25
   }
   if (carry > 0 || n_cmp(r, NS_N) >= 0) ns_sub_n_while_ge(r);             /* reduce() sees only the low 256 bits */
 }
-int fo_ecdsa_batch_verify(int curve, const unsigned char* digests, const u64* r, const u64* s, const u64* pk_xy,
-                          const uint8_t* pk_inf, const u64* a, size_t n, u64* detail) {
-  if (detail) memset(detail, 0, 16 * sizeof(u64));
-  if (curve != 0 && curve != 1) return -1;
-  if (n == 0) return 0;                                                    /* 289-291 */
-  jpt r_sum = curve == 0 ? k_identity() : n_identity();                    /* 310 */
-  for (size_t i = 0; i < n; ++i) {
-    const u64 *ri = r + 4 * i, *si = s + 4 * i, *ai = a + 4 * i;
-    if ((ri[0] | ri[1] | ri[2] | ri[3]) == 0 || (si[0] | si[1] | si[2] | si[3]) == 0) return 0;   /* 317-319 */
+/* per element i: the checks of 317-342 (st[i] = 0 passed, else 1 + the value the loop returns) and, when `products`,
+ * r1 + r2 (353-355) */
+typedef struct {
+  int curve, products;
+  const unsigned char* dg;
+  const u64 *r, *s, *pk, *a;
+  const uint8_t* pk_inf;
+  jpt* pt;
+  uint8_t* st;
+} ebv_t;
+static void ecdsa_batch_body(void* arg, size_t lo, size_t hi) {
+  const ebv_t* j = (const ebv_t*)arg;
+  const int curve = j->curve;
+  for (size_t i = lo; i < hi; ++i) {
+    const u64 *ri = j->r + 4 * i, *si = j->s + 4 * i, *ai = j->a + 4 * i;
+    const u64* pk_xy = j->pk;
+    const uint8_t* pk_inf = j->pk_inf;
+    j->st[i] = 0;
+    if ((ri[0] | ri[1] | ri[2] | ri[3]) == 0 || (si[0] | si[1] | si[2] | si[3]) == 0) { j->st[i] = 1; continue; }   /* 317-319 */
     u64 h[4], s_inv[4], u1[4], u2[4], au1[4], au2[4];
-    jpt q, r1, r2, ri_pt;
+    jpt q, r1, r2;
     if (curve == 0) {
-      if (ks_ge_n(ri) || ks_ge_n(si)) return 0;                            /* 322-327 */
-      if (!ks_from_bytes_be(digests + 32 * i, h)) return 2;                /* 334 */
-      if (!ks_inv(si, s_inv)) return 0;                                    /* 338-342 */
+      if (ks_ge_n(ri) || ks_ge_n(si)) { j->st[i] = 1; continue; }                          /* 322-327 */
+      if (!ks_from_bytes_be(j->dg + 32 * i, h)) { j->st[i] = 3; continue; }                /* 334 */
+      if (!ks_inv(si, s_inv)) { j->st[i] = 1; continue; }                                  /* 338-342 */
+      if (!j->products) continue;
       ks_mul(h, s_inv, u1); ks_mul(ri, s_inv, u2);                         /* 345-346 */
       ks_mul(ai, u1, au1); ks_mul(ai, u2, au2);                            /* 349-350 */
       jpt g = k_generator();
       q = k_identity();
       if (!(pk_inf && pk_inf[i])) { q.x = ld(pk_xy + 8 * i); q.y = ld(pk_xy + 8 * i + 4); q.z = fe_small(1); }
       r1 = k_multiply(&g, au1); r2 = k_multiply(&q, au2);                  /* 353-354 */
-      ri_pt = k_padd(&r1, &r2);                                            /* 355 */
-      r_sum = k_padd(&r_sum, &ri_pt);                                      /* 358 */
+      j->pt[i] = k_padd(&r1, &r2);                                         /* 355 */
     } else {
-      if (!(ns_ct_lt(ri, NS_N) & ns_ct_lt(si, NS_N))) return 0;
-      if (!ns_from_bytes_be(digests + 32 * i, h)) return 2;
-      if (!ns_inv(si, s_inv)) return 0;
+      if (!(ns_ct_lt(ri, NS_N) & ns_ct_lt(si, NS_N))) { j->st[i] = 1; continue; }
+      if (!ns_from_bytes_be(j->dg + 32 * i, h)) { j->st[i] = 3; continue; }
+      if (!ns_inv(si, s_inv)) { j->st[i] = 1; continue; }
+      if (!j->products) continue;
       ns_mul(h, s_inv, u1); ns_mul(ri, s_inv, u2);
       ns_mul(ai, u1, au1); ns_mul(ai, u2, au2);
       jpt g = n_generator();
       q = n_identity();
       if (!(pk_inf && pk_inf[i])) { q.x = ld(pk_xy + 8 * i); q.y = ld(pk_xy + 8 * i + 4); q.z = fe_small(1); }
       r1 = n_multiply(&g, au1); r2 = n_multiply(&q, au2);
-      ri_pt = n_padd(&r1, &r2);
-      r_sum = n_padd(&r_sum, &ri_pt);
+      j->pt[i] = n_padd(&r1, &r2);
     }
   }
+}
+/* -1: bad curve or no memory */
+int fo_ecdsa_batch_verify(int curve, const unsigned char* digests, const u64* r, const u64* s, const u64* pk_xy,
+                          const uint8_t* pk_inf, const u64* a, size_t n, u64* detail, int nthreads) {
+  if (detail) memset(detail, 0, 16 * sizeof(u64));
+  if (curve != 0 && curve != 1) return -1;
+  if (n == 0) return 0;                                                    /* 289-291 */
+  jpt* pt = (jpt*)malloc(n * sizeof(jpt));
+  uint8_t* st = (uint8_t*)malloc(n);
+  if (!pt || !st) { free(pt); free(st); return -1; }
+  /* the loop returns at the first failed check, and then no product matters: the checks of all elements first */
+  ebv_t job = {curve, 0, digests, r, s, pk_xy, a, pk_inf, pt, st};
+  run_ranges(ecdsa_batch_body, &job, n, nthreads);
+  for (size_t i = 0; i < n; ++i)
+    if (st[i]) {
+      const int ret = st[i] - 1;
+      free(pt); free(st);
+      return ret;
+    }
+  job.products = 1;
+  run_ranges(ecdsa_batch_body, &job, n, nthreads);
+  jpt r_sum = curve == 0 ? k_identity() : n_identity();                    /* 310 */
+  for (size_t i = 0; i < n; ++i) r_sum = curve == 0 ? k_padd(&r_sum, &pt[i]) : n_padd(&r_sum, &pt[i]);   /* 358 */
+  free(pt); free(st);
   u64 sum[4] = {0, 0, 0, 0}, t[4], ar[4];                                  /* 368-372 */
   for (size_t i = 0; i < n; ++i) {
     if (curve == 0) { ks_mul(a + 4 * i, r + 4 * i, ar); ks_add(sum, ar, t); }
@@ -1558,9 +1617,27 @@ int fo_ed25519_scalar_mul_release(const u64 a[4], const u64 b[4], u64 out[4]) {
 /* schnorr::batch_verify::<Ed25519, D> (schnorr.rs:194-290), release profile.  Arguments as for the two functions
  * below; 1 true, 0 false, 2 = the reference panics in to_affine (286: z.invert().unwrap() on a zero z of a point that
  * is not the identity, ed25519.rs:1805).  *debug_build_panics (optional) = 1 when some s_i * a_i wrapped a u128. */
+/* per element i: multiply(G, s_i * a_i) (and whether that Mul wrapped) and multiply(R_i + multiply(P_i, e_i), a_i) */
+typedef struct { const u64 *pk, *r, *s, *a, *e; ept *t, *arp; uint8_t* ovf; } esbv_t;
+static void ed25519_schnorr_batch_body(void* arg, size_t lo, size_t hi) {
+  const esbv_t* j = (const esbv_t*)arg;
+  ept g = e_generator();
+  for (size_t i = lo; i < hi; ++i) {
+    u64 sa[4];
+    int ovf = 0;
+    es_mul_release(j->s + 4 * i, j->a + 4 * i, sa, &ovf);
+    j->ovf[i] = (uint8_t)ovf;
+    j->t[i] = e_multiply(&g, sa);
+    ept P = e_from_affine(j->pk + 8 * i, 0);
+    ept ep = e_multiply(&P, j->e + 4 * i);
+    ept R = e_from_affine(j->r + 8 * i, 0);
+    ept rp = e_padd(&R, &ep);
+    j->arp[i] = e_multiply(&rp, j->a + 4 * i);
+  }
+}
 int fo_ed25519_schnorr_batch_verify(const u64* pk_xy, const uint8_t* pk_inf, const u64* r_xy, const uint8_t* r_inf,
                                     const u64* s, const u64* a, const u64* e, size_t n, u64* sides, uint8_t* sides_inf,
-                                    uint8_t* debug_build_panics) {
+                                    uint8_t* debug_build_panics, int nthreads) {
   if (sides) memset(sides, 0, 16 * sizeof(u64));
   if (sides_inf) sides_inf[0] = sides_inf[1] = 0;
   if (debug_build_panics) *debug_build_panics = 0;
@@ -1569,22 +1646,19 @@ int fo_ed25519_schnorr_batch_verify(const u64* pk_xy, const uint8_t* pk_inf, con
     if (pk_inf && pk_inf[i]) return 0;
     if (r_inf && r_inf[i]) return 0;
   }
-  ept g = e_generator();
+  ept* t = (ept*)malloc(n * sizeof(ept));
+  ept* arp = (ept*)malloc(n * sizeof(ept));
+  uint8_t* ovf = (uint8_t*)malloc(n);
+  if (!t || !arp || !ovf) { free(t); free(arp); free(ovf); return -1; }
+  esbv_t job = {pk_xy, r_xy, s, a, e, t, arp, ovf};
+  run_ranges(ed25519_schnorr_batch_body, &job, n, nthreads);
   ept s_g = e_identity(), r_e_p = e_identity();
-  for (size_t i = 0; i < n; ++i) {
-    u64 sa[4];
-    int ovf = 0;
-    es_mul_release(s + 4 * i, a + 4 * i, sa, &ovf);
-    if (ovf && debug_build_panics) *debug_build_panics = 1;
-    ept t = e_multiply(&g, sa);
-    s_g = e_padd(&s_g, &t);
-    ept P = e_from_affine(pk_xy + 8 * i, 0);
-    ept ep = e_multiply(&P, e + 4 * i);
-    ept R = e_from_affine(r_xy + 8 * i, 0);
-    ept rp = e_padd(&R, &ep);
-    ept arp = e_multiply(&rp, a + 4 * i);
-    r_e_p = e_padd(&r_e_p, &arp);
+  for (size_t i = 0; i < n; ++i) {                                 /* both folds in index order */
+    if (ovf[i] && debug_build_panics) *debug_build_panics = 1;
+    s_g = e_padd(&s_g, &t[i]);
+    r_e_p = e_padd(&r_e_p, &arp[i]);
   }
+  free(t); free(arp); free(ovf);
   if (!e_is_identity(&s_g) && fe_is_zero(&s_g.z)) return 2;      /* to_affine(s_g) is evaluated first */
   if (!e_is_identity(&r_e_p) && fe_is_zero(&r_e_p.z)) return 2;
   fe x1, y1, x2, y2;
@@ -1604,9 +1678,45 @@ int fo_ed25519_schnorr_batch_verify(const u64* pk_xy, const uint8_t* pk_inf, con
  *     multiply(from_affine(P_i), e_i), a_i), both folds strictly in index order from identity().
  *   - 286: to_affine(s_g).ct_eq(to_affine(r_e_p)) with AffinePoint::ct_eq (1292-1296).
  * sides (optional, 16 limbs): x,y of to_affine(s_g) then of to_affine(r_e_p); sides_inf (optional, 2). */
+/* per element i (curve 0 / 1): multiply(G, s_i * a_i) and multiply(from_affine(R_i) + multiply(from_affine(P_i), e_i), a_i) */
+typedef struct { int curve; const u64 *pk, *r, *s, *a, *e; jpt *t, *arp; } wsbv_t;
+static void weierstrass_schnorr_batch_body(void* arg, size_t lo, size_t hi) {
+  const wsbv_t* j = (const wsbv_t*)arg;
+  const int secp = j->curve == 0;
+  jpt g = secp ? k_generator() : n_generator();
+  for (size_t i = lo; i < hi; ++i) {
+    u64 sa[4];
+    if (secp) ks_mul(j->s + 4 * i, j->a + 4 * i, sa);         /* impl Mul for Scalar 2410-2456 */
+    else ns_mul(j->s + 4 * i, j->a + 4 * i, sa);
+    j->t[i] = secp ? k_multiply(&g, sa) : n_multiply(&g, sa);
+    jpt P = {ld(j->pk + 8 * i), ld(j->pk + 8 * i + 4), fe_small(1)};   /* from_affine 1365-1373 */
+    jpt ep = secp ? k_multiply(&P, j->e + 4 * i) : n_multiply(&P, j->e + 4 * i);
+    jpt R = {ld(j->r + 8 * i), ld(j->r + 8 * i + 4), fe_small(1)};
+    jpt rp = secp ? k_padd(&R, &ep) : n_padd(&R, &ep);
+    j->arp[i] = secp ? k_multiply(&rp, j->a + 4 * i) : n_multiply(&rp, j->a + 4 * i);
+  }
+}
+/* the products of weierstrass_schnorr_batch_body, then both folds from identity() strictly in index order (AddAssign
+ * 1543-1547); 0 on success, -1 without memory */
+static int weierstrass_schnorr_batch_sums(int curve, const u64* pk_xy, const u64* r_xy, const u64* s, const u64* a,
+                                          const u64* e, size_t n, int nthreads, jpt* s_g, jpt* r_e_p) {
+  jpt* t = (jpt*)malloc(n * sizeof(jpt));
+  jpt* arp = (jpt*)malloc(n * sizeof(jpt));
+  if (!t || !arp) { free(t); free(arp); return -1; }
+  wsbv_t job = {curve, pk_xy, r_xy, s, a, e, t, arp};
+  run_ranges(weierstrass_schnorr_batch_body, &job, n, nthreads);
+  *s_g = curve == 0 ? k_identity() : n_identity();
+  *r_e_p = *s_g;
+  for (size_t i = 0; i < n; ++i) {
+    *s_g = curve == 0 ? k_padd(s_g, &t[i]) : n_padd(s_g, &t[i]);
+    *r_e_p = curve == 0 ? k_padd(r_e_p, &arp[i]) : n_padd(r_e_p, &arp[i]);
+  }
+  free(t); free(arp);
+  return 0;
+}
 int fo_secp256k1_schnorr_batch_verify(const u64* pk_xy, const uint8_t* pk_inf, const u64* r_xy,
                                       const uint8_t* r_inf, const u64* s, const u64* a, const u64* e, size_t n,
-                                      u64* sides, uint8_t* sides_inf) {
+                                      u64* sides, uint8_t* sides_inf, int nthreads) {
   if (sides) memset(sides, 0, 16 * sizeof(u64));
   if (sides_inf) sides_inf[0] = sides_inf[1] = 0;
   if (n == 0) return 0;
@@ -1614,20 +1724,8 @@ int fo_secp256k1_schnorr_batch_verify(const u64* pk_xy, const uint8_t* pk_inf, c
     if (pk_inf && pk_inf[i]) return 0;
     if (r_inf && r_inf[i]) return 0;
   }
-  jpt g = k_generator();
-  jpt s_g = k_identity(), r_e_p = k_identity();
-  for (size_t i = 0; i < n; ++i) {
-    u64 sa[4];
-    ks_mul(s + 4 * i, a + 4 * i, sa);                          /* impl Mul for Scalar 2410-2456 */
-    jpt t = k_multiply(&g, sa);
-    s_g = k_padd(&s_g, &t);                                    /* AddAssign 1543-1547 */
-    jpt P = {ld(pk_xy + 8 * i), ld(pk_xy + 8 * i + 4), fe_small(1)};   /* from_affine 1365-1373 */
-    jpt ep = k_multiply(&P, e + 4 * i);
-    jpt R = {ld(r_xy + 8 * i), ld(r_xy + 8 * i + 4), fe_small(1)};
-    jpt rp = k_padd(&R, &ep);
-    jpt arp = k_multiply(&rp, a + 4 * i);
-    r_e_p = k_padd(&r_e_p, &arp);
-  }
+  jpt s_g, r_e_p;
+  if (weierstrass_schnorr_batch_sums(0, pk_xy, r_xy, s, a, e, n, nthreads, &s_g, &r_e_p) != 0) return -1;
   fe x1, y1, x2, y2;
   int i1 = k_to_affine(&s_g, &x1, &y1), i2 = k_to_affine(&r_e_p, &x2, &y2);
   if (sides) { st(sides, x1); st(sides + 4, y1); st(sides + 8, x2); st(sides + 12, y2); }
@@ -2093,7 +2191,8 @@ void fo_batch_schnorr_verify(int curve, const u64* pk_xy, const uint8_t* pk_inf,
 /* schnorr::batch_verify::<C, D> (schnorr.rs:194-290) for C = P256: the secp256k1 form above with the P-256 point and
  * scalar arithmetic (Scalar Mul p256.rs:1409-1432).  Same argument meaning, same outputs. */
 int fo_p256_schnorr_batch_verify(const u64* pk_xy, const uint8_t* pk_inf, const u64* r_xy, const uint8_t* r_inf,
-                                 const u64* s, const u64* a, const u64* e, size_t n, u64* sides, uint8_t* sides_inf) {
+                                 const u64* s, const u64* a, const u64* e, size_t n, u64* sides, uint8_t* sides_inf,
+                                 int nthreads) {
   if (sides) memset(sides, 0, 16 * sizeof(u64));
   if (sides_inf) sides_inf[0] = sides_inf[1] = 0;
   if (n == 0) return 0;
@@ -2101,20 +2200,8 @@ int fo_p256_schnorr_batch_verify(const u64* pk_xy, const uint8_t* pk_inf, const 
     if (pk_inf && pk_inf[i]) return 0;
     if (r_inf && r_inf[i]) return 0;
   }
-  jpt g = n_generator();
-  jpt s_g = n_identity(), r_e_p = n_identity();
-  for (size_t i = 0; i < n; ++i) {
-    u64 sa[4];
-    ns_mul(s + 4 * i, a + 4 * i, sa);
-    jpt t = n_multiply(&g, sa);
-    s_g = n_padd(&s_g, &t);
-    jpt P = {ld(pk_xy + 8 * i), ld(pk_xy + 8 * i + 4), fe_small(1)};
-    jpt ep = n_multiply(&P, e + 4 * i);
-    jpt R = {ld(r_xy + 8 * i), ld(r_xy + 8 * i + 4), fe_small(1)};
-    jpt rp = n_padd(&R, &ep);
-    jpt arp = n_multiply(&rp, a + 4 * i);
-    r_e_p = n_padd(&r_e_p, &arp);
-  }
+  jpt s_g, r_e_p;
+  if (weierstrass_schnorr_batch_sums(1, pk_xy, r_xy, s, a, e, n, nthreads, &s_g, &r_e_p) != 0) return -1;
   fe x1, y1, x2, y2;
   int i1 = n_to_affine(&s_g, &x1, &y1), i2 = n_to_affine(&r_e_p, &x2, &y2);
   if (sides) { st(sides, x1); st(sides + 4, y1); st(sides + 8, x2); st(sides + 12, y2); }

@@ -75,10 +75,11 @@ void fo_batch_p256_ecdsa_verify(const unsigned char* digests, const uint64_t* r,
                                 int nthreads);
 
 /* Ecdsa::<C, D>::batch_verify (ecdsa.rs:287-391), C = Secp256k1 (0) or P256 (1), digests and weights a_i given:
- * 1 true, 0 false, 2 the reference panics, -1 bad curve; detail (16 limbs or NULL) = r_sum, r_scalar_sum */
+ * 1 true, 0 false, 2 the reference panics, -1 bad curve or no memory; detail (16 limbs or NULL) = r_sum, r_scalar_sum;
+ * nthreads: threads for the per-element products (the checks and the fold stay in index order) */
 int fo_ecdsa_batch_verify(int curve, const unsigned char* digests, const uint64_t* r, const uint64_t* s,
                           const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* a, size_t n,
-                          uint64_t* detail);
+                          uint64_t* detail, int nthreads);
 
 /* Curve::validate_point: is_on_curve for secp256k1 / P-256 (their overrides), the trait default for Ed25519
  * (on the curve AND order * (8 * P) is the identity): 1 / 0 */
@@ -101,21 +102,24 @@ void fo_batch_ed25519_eddsa_verify(const uint64_t* r_xy, const uint8_t* r_inf, c
 
 /* schnorr::batch_verify::<Secp256k1, D> (forge-ec-signature/src/schnorr.rs:194-290) with the challenges
  * e_i and the random weights a_i supplied; 1 = true, 0 = false.  sides / sides_inf (optional): the
- * two affine points the reference compares at 286 */
+ * two affine points the reference compares at 286; -1 no memory.  nthreads: threads for the per-element products
+ * (the two folds stay in index order, so the result does not depend on it) */
 int fo_secp256k1_schnorr_batch_verify(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* r_xy,
                                       const uint8_t* r_inf, const uint64_t* s, const uint64_t* a,
-                                      const uint64_t* e, size_t n, uint64_t* sides, uint8_t* sides_inf);
+                                      const uint64_t* e, size_t n, uint64_t* sides, uint8_t* sides_inf,
+                                      int nthreads);
 
 /* the same for C = P256 (its own point and scalar arithmetic) */
 int fo_p256_schnorr_batch_verify(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* r_xy,
                                  const uint8_t* r_inf, const uint64_t* s, const uint64_t* a,
-                                 const uint64_t* e, size_t n, uint64_t* sides, uint8_t* sides_inf);
+                                 const uint64_t* e, size_t n, uint64_t* sides, uint8_t* sides_inf, int nthreads);
 /* the same for C = Ed25519 with the RELEASE-profile scalar Mul (ed25519.rs:1256-1376: u128 sums wrap; Cargo.toml:53-58);
  * 2 = the reference panics in to_affine; *debug_build_panics (optional) = 1 when some s_i * a_i wrapped a u128, i.e. a
  * debug build (overflow checks on) panics on these inputs */
 int fo_ed25519_schnorr_batch_verify(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* r_xy,
                                     const uint8_t* r_inf, const uint64_t* s, const uint64_t* a, const uint64_t* e,
-                                    size_t n, uint64_t* sides, uint8_t* sides_inf, uint8_t* debug_build_panics);
+                                    size_t n, uint64_t* sides, uint8_t* sides_inf, uint8_t* debug_build_panics,
+                                    int nthreads);
 /* impl Mul for Scalar (Ed25519) under the release profile: out = a * b, returns 1 when a u128 sum wrapped */
 int fo_ed25519_scalar_mul_release(const uint64_t a[4], const uint64_t b[4], uint64_t out[4]);
 /* Schnorr::<C, D>::verify per signature (schnorr.rs:90-140) from the point computation on, curve 0 / 1 / 2:
