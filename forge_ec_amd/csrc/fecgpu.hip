@@ -757,12 +757,10 @@ void ensure_gen_prefix(fec_ctx* ctx, int curve, hipStream_t s, size_t n) {
 }
 
 // Any OTHER fixed base: a table for this one launch, in the launch stream's scratch, sized to the batch -- 2^w entries
-// with w = log2(n) - 2 cost n / 2 steps to build and save n * w: from 2^16 elements on.  `front`: bytes of the scratch
-// the caller needs for itself, in front of the table.  On success `env` names the table for `base`; the scratch pointer
-// is returned through `scratch` (null: no scratch could be had -- the caller's own `front` bytes included).
-void per_call_prefix(fec_ctx* ctx, int curve, const u32* base, size_t n, hipStream_t s, size_t front, SchedEnv& env,
-                     void** scratch) {
-  *scratch = nullptr;
+// with w = log2(n) - 2 cost n / 2 steps to build and save n * w: from 2^16 elements on.  Acquires `area` -- the caller's
+// own regions, then the table (the caller's regions alone when there is no room for one).  With a table, `env` names it
+// for `base`.
+int acquire_with_prefix(fec_ctx* ctx, int curve, const u32* base, size_t n, hipStream_t s, WorkArea& area, SchedEnv& env) {
   unsigned w = 0;
   if (ctx->prefix_bits != 0 && n >= ((size_t)1 << 16)) {
     unsigned lg = 0;
@@ -771,22 +769,19 @@ void per_call_prefix(fec_ctx* ctx, int curve, const u32* base, size_t n, hipStre
     if (w > ctx->prefix_bits) w = ctx->prefix_bits;
     if (w > 22) w = 22;
   }
-  const size_t fr = (front + 255) & ~(size_t)255;
-  const size_t bytes = fr + (w ? prefix_table_bytes(curve, w) + prefix_half_bytes(curve, w) : 0);
-  if (bytes == 0) return;
-  char* p = static_cast<char*>(scratch_for(ctx, s, bytes));
-  if (!p && w) {                                                   // no room for a table: the caller's own bytes alone
-    w = 0;
-    p = front ? static_cast<char*>(scratch_for(ctx, s, fr)) : nullptr;
+  if (w) {
+    u32 *tab, *half;
+    area.add(tab, prefix_table_bytes(curve, w)).add(half, prefix_half_bytes(curve, w));
+    if (area.acquire(ctx, s) == FEC_OK) {
+      queue_prefix_levels(curve, base, ctx->d_ed_table, w, tab, half, s);
+      env.gen[curve] = base;
+      env.gen_prefix[curve] = tab;
+      env.gen_prefix_bits[curve] = w;
+      return FEC_OK;
+    }
+    area.pop(2);                                                   // no room for a table: the caller's own regions alone
   }
-  *scratch = p;
-  if (!p || w == 0) return;
-  u32* tab = reinterpret_cast<u32*>(p + fr);
-  u32* half = prefix_half_bytes(curve, w) ? reinterpret_cast<u32*>(p + fr + prefix_table_bytes(curve, w)) : nullptr;
-  queue_prefix_levels(curve, base, ctx->d_ed_table, w, tab, half, s);
-  env.gen[curve] = base;
-  env.gen_prefix[curve] = tab;
-  env.gen_prefix_bits[curve] = w;
+  return area.acquire(ctx, s);
 }
 void drop_gen_prefix(fec_ctx* ctx) {
   for (int c = 0; c < 3; ++c) {
@@ -812,59 +807,94 @@ int ensure_ed_table(fec_ctx* ctx, const u64* d_base, const u64* host_base, hipSt
   return FEC_OK;
 }
 
-int launch_ed_fixed(fec_ctx* ctx, const u64* ds, const u64* dbase, const u64* host_base, u64* dout, size_t n,
-                    void* stream) {
-  if (n == 0) return FEC_OK;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  int rc = ensure_ed_table(ctx, dbase, host_base, s);
-  if (rc != FEC_OK) return rc;
-  const bool is_gen = dbase == ctx->d_gen[FEC_ED25519];
-  if (is_gen) ensure_gen_prefix(ctx, FEC_ED25519, s, n);
-  // per-stream scratch: the batch-wide popcount sort of large batches, and behind it the prefix table of a base that is
-  // not the generator (per_call_prefix)
-  void* work = nullptr;
-  const size_t work_bytes = ed_fixed_work_bytes(n);
-  Launch L(ctx, stream, work_bytes ? "k_ed_fixed_sorted (+ k_ed_pc_hist, k_ed_pc_scan, k_ed_pc_scatter)" : "k_ed_fixed_base");
-  SchedEnv env = sched_env(ctx);
-  if (is_gen) {
-    if (work_bytes != 0 && !(work = scratch_for(ctx, s, work_bytes))) return FEC_E_OOM;
-  } else {
-    per_call_prefix(ctx, FEC_ED25519, reinterpret_cast<const u32*>(dbase), n, L.s, work_bytes, env, &work);
-    if (work_bytes != 0 && !work) return FEC_E_OOM;
-    if (work_bytes == 0) work = nullptr;   // (the scratch then holds the table alone: no sort area)
+// The setup of a composed launch that multiplies `n` scalars by the generator: the Ed25519 addend table of G (built once)
+// and the prefix table of the curve (ensure_gen_prefix).
+int prepare_generator(fec_ctx* ctx, int curve, hipStream_t s, size_t n) {
+  if (curve == FEC_ED25519) {
+    const int rc = ensure_ed_table(ctx, ctx->d_gen[FEC_ED25519], ctx->h_gen_ed, s);
+    if (rc != FEC_OK) return rc;
   }
-  ed_fixed_launch(env, reinterpret_cast<const u32*>(ds), reinterpret_cast<const u32*>(dbase), ctx->d_ed_table,
-                  reinterpret_cast<u32*>(dout), n, work, L.s);
-  return L.done();
+  ensure_gen_prefix(ctx, curve, s, n);
+  return FEC_OK;
 }
 
-int launch_mul(fec_ctx* ctx, int curve, bool fixed, const u64* ds, const u64* dp, u64* dout, size_t n,
-               void* stream) {
+// One per-curve dispatch of the kernel templates of this file: f(Secp{}), f(P256{}) or f(Ed{}).
+template <class F>
+void with_curve(int curve, F&& f) {
+  switch (curve) {
+    case FEC_SECP256K1: f(Secp{}); break;
+    case FEC_P256: f(P256{}); break;
+    default: f(Ed{}); break;
+  }
+}
+
+// multiply(base, k) with one base for the batch: secp256k1's ladder, the P-256 scheduler, the Ed25519 LDS addend-table
+// kernel (its table of `base` in ctx->d_ed_table; `sort`: its popcount-sort area, ed_fixed_work_bytes(n), or null).
+void fixed_product(const fec_ctx* ctx, const SchedEnv& env, int curve, const u32* k, const u32* base, u32* out, size_t n,
+                   void* sort, hipStream_t s) {
+  switch (curve) {
+    case FEC_SECP256K1: secp_launch_mul(env, true, k, base, out, n, s); break;
+    case FEC_P256: p256_launch_mul(env, true, k, base, out, n, s); break;
+    default: ed_fixed_launch(env, k, base, ctx->d_ed_table, out, n, sort, s); break;
+  }
+}
+// multiply(p[i], k[i]).  cu_divisor (Ed25519): the scheduler takes 1 / cu_divisor of the CUs.
+void var_product(const SchedEnv& env, int curve, const u32* k, const u32* p, u32* out, size_t n, hipStream_t s,
+                 unsigned cu_divisor = 1) {
+  switch (curve) {
+    case FEC_SECP256K1: secp_launch_mul(env, false, k, p, out, n, s); break;
+    case FEC_P256: p256_launch_mul(env, false, k, p, out, n, s); break;
+    default: ed_launch_mul(env, k, p, out, n, s, cu_divisor); break;
+  }
+}
+// The SchedEnv of the fixed-base product and of the variable-base product(s) beside it: with the fork active, the P-256
+// launches divide the CUs in proportion to their work (cu_split.hpp; var_ms: the variable-base side's cost).
+struct ProductEnvs {
+  SchedEnv fixed, var;
+};
+ProductEnvs product_envs(const fec_ctx* ctx, int curve, size_t n, bool forked, double var_ms) {
+  const SchedEnv env = sched_env(ctx);
+  ProductEnvs e{env, env};
+  if (forked && curve == FEC_P256) p256_cu_split(env, n, var_ms, e.fixed, e.var);
+  return e;
+}
+
+// out[i] = multiply(k[i], p[i]), or multiply(base, k[i]) for every i (`fixed`).  A fixed base that is the ctx's generator
+// starts from its prefix table; any other from a table of its own for this launch (acquire_with_prefix).
+// `ed_host_base` (Ed25519, fixed): the base on the host, the cache key of the addend table (null: always rebuilt).
+int launch_mul(fec_ctx* ctx, int curve, bool fixed, const u64* ds, const u64* dp, u64* dout, size_t n, void* stream,
+               const u64* ed_host_base = nullptr) {
   if (n == 0) return FEC_OK;
-  if (fixed && curve == FEC_ED25519) return launch_ed_fixed(ctx, ds, dp, nullptr, dout, n, stream);  // LDS addend table
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   const u32* s = reinterpret_cast<const u32*>(ds);
   const u32* p = reinterpret_cast<const u32*>(dp);
   u32* o = reinterpret_cast<u32*>(dout);
+  const bool ed_fixed = fixed && curve == FEC_ED25519, is_gen = fixed && dp == ctx->d_gen[curve];
+  if (ed_fixed) {   // the LDS addend table of the base
+    const int rc = ensure_ed_table(ctx, dp, ed_host_base, st);
+    if (rc != FEC_OK) return rc;
+  }
+  if (is_gen) ensure_gen_prefix(ctx, curve, st, n);
+  const size_t sort_bytes = ed_fixed ? ed_fixed_work_bytes(n) : 0;   // the batch-wide popcount sort of large batches
   const char* name = curve == FEC_SECP256K1 ? (fixed ? "k_secp_mul<fixed>" : "k_secp_mul<var>")
                      : curve == FEC_P256    ? (fixed ? "k_p256_mul_sched<fixed>" : "k_p256_mul_sched<var>")
-                                            : "k_ed_mul_pers";
-  if (fixed && dp == ctx->d_gen[curve]) ensure_gen_prefix(ctx, curve, stream ? (hipStream_t)stream : ctx->stream, n);
+                     : !fixed               ? "k_ed_mul_pers"
+                     : sort_bytes           ? "k_ed_fixed_sorted (+ k_ed_pc_hist, k_ed_pc_scan, k_ed_pc_scatter)"
+                                            : "k_ed_fixed_base";
   Launch L(ctx, stream, name);
   SchedEnv env = sched_env(ctx);
-  if (fixed && dp != ctx->d_gen[curve]) {   // a base of the caller's own: a table for this launch (per_call_prefix)
-    void* unused = nullptr;
-    per_call_prefix(ctx, curve, p, n, L.s, 0, env, &unused);
-  }
-  switch (curve) {
-    case FEC_SECP256K1: secp_launch_mul(env, fixed, s, p, o, n, L.s); break;
-    case FEC_P256: p256_launch_mul(env, fixed, s, p, o, n, L.s); break;
-    default: ed_launch_mul(env, s, p, o, n, L.s); break;
-  }
+  void* sort;
+  WorkArea area;
+  area.add(sort, sort_bytes);
+  const int rc = fixed && !is_gen ? acquire_with_prefix(ctx, curve, p, n, L.s, area, env) : area.acquire(ctx, L.s);
+  if (rc != FEC_OK) return rc;
+  if (fixed) fixed_product(ctx, env, curve, s, p, o, n, sort, L.s);
+  else var_product(env, curve, s, p, o, n, L.s);
   return L.done();
 }
 
 // A launch forked onto the ctx's second stream and joined back (events; no host blocking).  Inactive -- `s` is the
-// main stream and fork_done / join do nothing -- for large batches, when the ctx has no second stream, or when the
+// main stream and join does nothing -- for batches above `limit`, when the ctx has no second stream, or when the
 // main stream IS the second stream.
 struct SideStream {
   // Round 2 forked only up to 98304 elements (two launches side by side fill the chip: 256 CUs x 768 lanes / 2).  Measured
@@ -888,13 +918,30 @@ struct SideStream {
     s = ctx->stream2;
     active = true;
   }
-  void fork_done() { if (active) (void)hipEventRecord(ev_out, s); }
-  void join() { if (active) (void)hipStreamWaitEvent(main, ev_out, 0); }
+  void join() {   // `main` waits for everything queued on `s` so far
+    if (!active) return;
+    (void)hipEventRecord(ev_out, s);
+    (void)hipStreamWaitEvent(main, ev_out, 0);
+  }
   ~SideStream() {
     if (ev_in) (void)hipEventDestroy(ev_in);
     if (ev_out) (void)hipEventDestroy(ev_out);
   }
 };
+
+// The composition of the verifiers and of double_mul: og = multiply(G, kg) beside op = multiply(p, kp).  The fixed-base
+// product goes to the ctx's second stream up to `fork_limit` elements (the persistent kernels, one workgroup per CU,
+// each on its share of the CUs: ProductEnvs), the variable-base one to `main`, and `main` waits for both.
+void product_pair(fec_ctx* ctx, int curve, size_t n, hipStream_t main, size_t fork_limit, double var_ms, const u32* kg,
+                  u32* og, void* sort, const u32* kp, const u32* p, u32* op) {
+  SideStream side(ctx, main, n, fork_limit);
+  const ProductEnvs env = product_envs(ctx, curve, n, side.active, var_ms);
+  fixed_product(ctx, env.fixed, curve, kg, reinterpret_cast<const u32*>(ctx->d_gen[curve]), og, n, sort, side.s);
+  // (Ed25519 forks in double_mul only, up to 2^15 elements: its table kernel is short and not capped to a share of the
+  // CUs, so there the scheduler beside it takes half of them)
+  var_product(env.var, curve, kp, p, op, n, main, side.active ? 2 : 1);
+  side.join();
+}
 
 // out[i] = multiply(G, u1[i]) + multiply(q[i], u2[i])   (ecdsa.rs:254-256).
 // Composed from the single-multiplication kernels: u1*G and u2*Q into per-stream scratch (secp256k1: the
@@ -904,170 +951,125 @@ struct SideStream {
 int launch_double_mul(fec_ctx* ctx, int curve, const u64* d1, const u64* d2, const u64* dq, u64* dout,
                       size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  const u32* a = reinterpret_cast<const u32*>(d1);
-  const u32* b2 = reinterpret_cast<const u32*>(d2);
-  const u32* q = reinterpret_cast<const u32*>(dq);
-  const u32* gen = reinterpret_cast<const u32*>(ctx->d_gen[curve]);
-  u32* o = reinterpret_cast<u32*>(dout);
-  dim3 g(grid_for(n)), b(TPB);
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   const size_t pb = (size_t)plimbs(curve) * 8;
-  const size_t ed_work = curve == FEC_ED25519 ? ed_fixed_work_bytes(n) : 0;
-  char* scratch = static_cast<char*>(scratch_for(ctx, st, 2 * n * pb + ed_work));
-  if (!scratch) return FEC_E_OOM;
-  u32* ta = reinterpret_cast<u32*>(scratch);
-  u32* tb = reinterpret_cast<u32*>(scratch + n * pb);
-  if (curve == FEC_ED25519) {  // the addend table of G is built (once) before the timed sequence
-    int rc = ensure_ed_table(ctx, ctx->d_gen[FEC_ED25519], ctx->h_gen_ed, st);
-    if (rc != FEC_OK) return rc;
-  }
-  ensure_gen_prefix(ctx, curve, st, n);
+  u32 *ta, *tb;
+  void* sort;
+  WorkArea area;
+  area.add(ta, n * pb).add(tb, n * pb).add(sort, curve == FEC_ED25519 ? ed_fixed_work_bytes(n) : 0);
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, curve, st, n);   // (the addend table of G is built before the timed sequence)
+  if (rc != FEC_OK) return rc;
   Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_secp_mul x2 + k_point_op"
                         : (curve == FEC_P256 ? "k_p256_mul_sched x2 + k_point_op" : "k_ed_fixed_base + k_ed_mul_pers + k_point_op"));
-  // The fixed-base product runs on the ctx's second stream beside the variable-base one (the persistent kernels, one
-  // workgroup per CU, each on half of the CUs): see SideStream.
-  // (Ed25519: the table kernel is short and not capped to half of the CUs; side by side pays up to 2^15 elements)
-  // (fec_ctx_set_side_stream_max -- the measurement knob of tools/double_mul_small_perf.py -- moves the limit)
-  SideStream side(ctx, L.s, n, curve == FEC_ED25519 ? (size_t)1 << 15 : ctx->side_stream_max);
-  if (curve == FEC_SECP256K1) {  // the 3-waves-per-SIMD ladder twice (fixed G, then Q) beats the fused 2-wave kernel
-    secp_launch_mul(sched_env(ctx), true, a, gen, ta, n, side.s);
-    side.fork_done();
-    secp_launch_mul(sched_env(ctx), false, b2, q, tb, n, L.s);
-    side.join();
-    hipLaunchKernelGGL((k_point_op<Secp>), g, b, 0, L.s, (int)FEC_P_ADD, (const u32*)ta, (const u32*)tb, o, n);
-  } else if (curve == FEC_P256) {
-    SchedEnv ef = sched_env(ctx), ev = ef;
-    if (side.active) p256_cu_split(sched_env(ctx), n, kP256VarMs, ef, ev);   // the CUs in proportion to the two launches' work
-    p256_launch_mul(ef, true, a, gen, ta, n, side.s);
-    side.fork_done();
-    p256_launch_mul(ev, false, b2, q, tb, n, L.s);
-    side.join();
-    hipLaunchKernelGGL((k_point_op<P256>), g, b, 0, L.s, (int)FEC_P_ADD, (const u32*)ta, (const u32*)tb, o, n);
-  } else {
-    ed_fixed_launch(sched_env(ctx), a, gen, ctx->d_ed_table, ta, n, ed_work ? scratch + 2 * n * pb : nullptr, side.s);  // (ed_work != 0 only where the side stream is off)
-    side.fork_done();
-    ed_launch_mul(sched_env(ctx), b2, q, tb, n, L.s, side.active ? 2 : 1);
-    side.join();
-    hipLaunchKernelGGL((k_point_op<Ed>), g, b, 0, L.s, (int)FEC_P_ADD, (const u32*)ta, (const u32*)tb, o, n);
-  }
+  // Fork limit (see SideStream): Ed25519 pays side by side up to 2^15 elements only (its sort area is used from 2^16, where
+  // the fork is off); fec_ctx_set_side_stream_max -- the measurement knob of tools/double_mul_small_perf.py -- moves the
+  // Weierstrass curves' limit.
+  product_pair(ctx, curve, n, L.s, curve == FEC_ED25519 ? (size_t)1 << 15 : ctx->side_stream_max, kP256VarMs,
+               reinterpret_cast<const u32*>(d1), ta, sort, reinterpret_cast<const u32*>(d2), reinterpret_cast<const u32*>(dq), tb);
+  with_curve(curve, [&](auto c) {
+    using C = decltype(c);
+    hipLaunchKernelGGL((k_point_op<C>), dim3(grid_for(n)), dim3(TPB), 0, L.s, (int)FEC_P_ADD, (const u32*)ta, (const u32*)tb,
+                       reinterpret_cast<u32*>(dout), n);
+  });
   return L.done();
 }
 
 int launch_to_affine(fec_ctx* ctx, int curve, const u64* dp, u64* dxy, unsigned char* dinf, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  const u32* p = reinterpret_cast<const u32*>(dp);
-  u32* o = reinterpret_cast<u32*>(dxy);
-  dim3 g(grid_for(n)), b(TPB);
   Launch L(ctx, stream, "k_to_affine");
-  switch (curve) {
-    case FEC_SECP256K1: hipLaunchKernelGGL((k_to_affine<Secp>), g, b, 0, L.s, p, o, dinf, n); break;
-    case FEC_P256: hipLaunchKernelGGL((k_to_affine<P256>), g, b, 0, L.s, p, o, dinf, n); break;
-    default: hipLaunchKernelGGL((k_to_affine<Ed>), g, b, 0, L.s, p, o, dinf, n); break;
-  }
+  with_curve(curve, [&](auto c) {
+    using C = decltype(c);
+    hipLaunchKernelGGL((k_to_affine<C>), dim3(grid_for(n)), dim3(TPB), 0, L.s, reinterpret_cast<const u32*>(dp),
+                       reinterpret_cast<u32*>(dxy), dinf, n);
+  });
   return L.done();
 }
 
 int launch_compress(fec_ctx* ctx, int curve, const u64* dxy, const unsigned char* dinf, unsigned char* dout, size_t n,
                     void* stream) {
   if (n == 0) return FEC_OK;
-  const u32* p = reinterpret_cast<const u32*>(dxy);
-  dim3 g(grid_for(n)), b(TPB);
   Launch L(ctx, stream, "k_compress");
-  switch (curve) {
-    case FEC_SECP256K1: hipLaunchKernelGGL((k_compress<Secp>), g, b, 0, L.s, p, dinf, dout, n); break;
-    case FEC_P256: hipLaunchKernelGGL((k_compress<P256>), g, b, 0, L.s, p, dinf, dout, n); break;
-    default: hipLaunchKernelGGL((k_compress<Ed>), g, b, 0, L.s, p, dinf, dout, n); break;
-  }
+  with_curve(curve, [&](auto c) {
+    using C = decltype(c);
+    hipLaunchKernelGGL((k_compress<C>), dim3(grid_for(n)), dim3(TPB), 0, L.s, reinterpret_cast<const u32*>(dxy), dinf, dout, n);
+  });
   return L.done();
 }
 
-// Ecdsa::<C, D>::verify for secp256k1 / P-256: the pipeline of kernels_ecdsa.hip on per-stream scratch.
-// (The single-kernel secp256k1 form of round 1 measured 70.7 ms per 2^20 against 65.7 ms for this pipeline.)
+// The ECDSA work area (kernels.hpp: EcdsaWork), in one place for verify (stream scratch) and batch_verify (a staging
+// slot); a_i * r_i only for batch_verify (`weighted`).
+void ecdsa_layout(WorkArea& area, EcdsaWork& w, size_t n, bool weighted) {
+  area.add(w.u1, n * 32).add(w.u2, n * 32).add(w.q, n * 96).add(w.ta, n * 96).add(w.tb, n * 96).add(w.flags, n);
+  area.add(w.ar, weighted ? n * 32 : 0);
+}
+
+// Ecdsa::<C, D>::verify for secp256k1 / P-256: the passes of kernels_ecdsa.hip around the two products, on per-stream
+// scratch.  (The single-kernel secp256k1 form of round 1 measured 70.7 ms per 2^20 against 65.7 ms for this pipeline.)
 int launch_ecdsa_verify(fec_ctx* ctx, int curve, const unsigned char* dd, const u64* dr, const u64* ds, const u64* dpk,
                         const unsigned char* dinf, unsigned char* dstatus, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  void* work = scratch_for(ctx, st, ecdsa_work_bytes(n));
-  if (!work) return FEC_E_OOM;
-  ensure_gen_prefix(ctx, curve, st, n);
+  EcdsaWork w;
+  WorkArea area;
+  ecdsa_layout(area, w, n, false);
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, curve, st, n);
+  if (rc != FEC_OK) return rc;
   Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_ecdsa_pre + k_secp_mul x2 + k_ecdsa_finish"
                                                : "k_ecdsa_pre + k_p256_mul_sched x2 + k_ecdsa_finish");
-  ecdsa_launch(sched_env(ctx), curve, dd, reinterpret_cast<const u32*>(dr), reinterpret_cast<const u32*>(ds),
-               reinterpret_cast<const u32*>(dpk), dinf, reinterpret_cast<const u32*>(ctx->d_gen[curve]), dstatus, work, n,
-               L.s, ctx->stream2 != L.s ? ctx->stream2 : nullptr);
+  const u32* r = reinterpret_cast<const u32*>(dr);
+  ecdsa_pre_launch(curve, dd, r, reinterpret_cast<const u32*>(ds), reinterpret_cast<const u32*>(dpk), dinf, nullptr, w, n, L.s);
+  // (u2 * from_affine(public key): the affine-addend cost in the P-256 CU split)
+  product_pair(ctx, curve, n, L.s, SideStream::kSideStreamMax, kP256VarAffineMs, w.u1, w.ta, nullptr, w.u2, w.q, w.tb);
+  ecdsa_finish_launch(curve, r, w, dstatus, n, L.s);
   return L.done();
 }
 
 // Eddsa::<Ed25519, D>::verify / Ed25519::verify from the point computation on (eddsa.rs:174-211, 430-447):
-// A = from_affine(pk); s*G by the LDS addend-table kernel, k*A by the task scheduler; R + k*A, the two
-// to_affine, the difference and is_identity in one finishing pass.  Work area: A, s*G, k*A (3 x 128 B).
+// A = from_affine(pk); s*G by the LDS addend-table kernel, k*A by the task scheduler, one after the other; R + k*A, the
+// two to_affine, the difference and is_identity in one finishing pass.
 int launch_eddsa_verify(fec_ctx* ctx, const u64* dr, const unsigned char* drinf, const u64* dpk, const unsigned char* dpinf,
                         const u64* ds, const u64* dk, unsigned char* dstatus, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  const size_t ed_work = ed_fixed_work_bytes(n);
-  char* work = static_cast<char*>(scratch_for(ctx, st, n * 384 + ed_work));
-  if (!work) return FEC_E_OOM;
-  u32* a = reinterpret_cast<u32*>(work);
-  u32* sg = reinterpret_cast<u32*>(work + n * 128);
-  u32* ka = reinterpret_cast<u32*>(work + n * 256);
-  int rc = ensure_ed_table(ctx, ctx->d_gen[FEC_ED25519], ctx->h_gen_ed, st);
+  u32 *a, *sg, *ka;
+  void* sort;
+  WorkArea area;
+  area.add(a, n * 128).add(sg, n * 128).add(ka, n * 128).add(sort, ed_fixed_work_bytes(n));
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, FEC_ED25519, st, n);
   if (rc != FEC_OK) return rc;
-  ensure_gen_prefix(ctx, FEC_ED25519, st, n);
   Launch L(ctx, stream, "k_eddsa_pre + k_ed_fixed_base + k_ed_mul_pers + k_eddsa_finish");
   eddsa_pre_launch(reinterpret_cast<const u32*>(dpk), dpinf, a, n, L.s);
-  ed_fixed_launch(sched_env(ctx), reinterpret_cast<const u32*>(ds), reinterpret_cast<const u32*>(ctx->d_gen[FEC_ED25519]),
-                  ctx->d_ed_table, sg, n, ed_work ? work + n * 384 : nullptr, L.s);
-  ed_launch_mul(sched_env(ctx), reinterpret_cast<const u32*>(dk), a, ka, n, L.s);
+  product_pair(ctx, FEC_ED25519, n, L.s, 0, 0.0, reinterpret_cast<const u32*>(ds), sg, sort, reinterpret_cast<const u32*>(dk), a, ka);
   eddsa_finish_launch(sg, ka, reinterpret_cast<const u32*>(dr), drinf, dstatus, n, L.s);
   return L.done();
 }
 
 // Schnorr::<C, D>::verify per signature from the point computation on (schnorr.rs:90-140): A = from_affine(pk);
 // s*G by the curve's fixed-base kernel (forked to the second stream for the Weierstrass curves), e*A by its
-// variable-base kernel; the rest in one finishing pass.  Work area: A, s*G, e*A.
+// variable-base kernel; the rest in one finishing pass.
 int launch_schnorr_verify(fec_ctx* ctx, int curve, const u64* dpk, const unsigned char* dpinf, const u64* dr,
                           const unsigned char* drinf, const u64* ds, const u64* de, unsigned char* dstatus, size_t n,
                           void* stream) {
   if (n == 0) return FEC_OK;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   const size_t pb = (size_t)plimbs(curve) * 8;
-  const size_t ed_work = curve == FEC_ED25519 ? ed_fixed_work_bytes(n) : 0;
-  char* work = static_cast<char*>(scratch_for(ctx, st, schnorr_verify_work_bytes(curve, n) + ed_work));
-  if (!work) return FEC_E_OOM;
-  u32* a = reinterpret_cast<u32*>(work);
-  u32* sg = reinterpret_cast<u32*>(work + n * pb);
-  u32* ep = reinterpret_cast<u32*>(work + 2 * n * pb);
-  const u32* gen = reinterpret_cast<const u32*>(ctx->d_gen[curve]);
-  const u32* sc = reinterpret_cast<const u32*>(ds);
-  const u32* ec = reinterpret_cast<const u32*>(de);
-  if (curve == FEC_ED25519) {
-    int rc = ensure_ed_table(ctx, ctx->d_gen[FEC_ED25519], ctx->h_gen_ed, st);
-    if (rc != FEC_OK) return rc;
-  }
-  ensure_gen_prefix(ctx, curve, st, n);
+  u32 *a, *sg, *ep;
+  void* sort;
+  WorkArea area;
+  area.add(a, n * pb).add(sg, n * pb).add(ep, n * pb).add(sort, curve == FEC_ED25519 ? ed_fixed_work_bytes(n) : 0);
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, curve, st, n);
+  if (rc != FEC_OK) return rc;
   Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_schnorr_verify_pre + k_secp_mul x2 + k_schnorr_verify_finish"
                         : (curve == FEC_P256 ? "k_schnorr_verify_pre + k_p256_mul_sched x2 + k_schnorr_verify_finish"
                                              : "k_schnorr_verify_pre + k_ed_fixed_base + k_ed_mul_pers + k_schnorr_verify_finish"));
   schnorr_verify_pre_launch(curve, reinterpret_cast<const u32*>(dpk), dpinf, a, n, L.s);
-  if (curve == FEC_ED25519) {
-    ed_fixed_launch(sched_env(ctx), sc, gen, ctx->d_ed_table, sg, n, ed_work ? work + 3 * n * pb : nullptr, L.s);
-    ed_launch_mul(sched_env(ctx), ec, a, ep, n, L.s);
-  } else {
-    SideStream side(ctx, L.s, n);
-    if (curve == FEC_SECP256K1) {
-      secp_launch_mul(sched_env(ctx), true, sc, gen, sg, n, side.s);
-      side.fork_done();
-      secp_launch_mul(sched_env(ctx), false, ec, a, ep, n, L.s);
-    } else {
-      SchedEnv ef = sched_env(ctx), ev = ef;
-      if (side.active) p256_cu_split(sched_env(ctx), n, kP256VarAffineMs, ef, ev);   // (e * from_affine(P): affine addend)
-      p256_launch_mul(ef, true, sc, gen, sg, n, side.s);
-      side.fork_done();
-      p256_launch_mul(ev, false, ec, a, ep, n, L.s);
-    }
-    side.join();
-  }
+  // (e * from_affine(P): the affine-addend cost in the P-256 CU split)
+  product_pair(ctx, curve, n, L.s, curve == FEC_ED25519 ? 0 : SideStream::kSideStreamMax, kP256VarAffineMs,
+               reinterpret_cast<const u32*>(ds), sg, sort, reinterpret_cast<const u32*>(de), a, ep);
   schnorr_verify_finish_launch(curve, sg, ep, reinterpret_cast<const u32*>(dr), drinf, dstatus, n, L.s);
   return L.done();
 }
@@ -1075,12 +1077,11 @@ int launch_schnorr_verify(fec_ctx* ctx, int curve, const u64* dpk, const unsigne
 // Curve::validate_point per affine point (kernels_ecdsa.hip)
 int launch_validate(fec_ctx* ctx, int curve, const u64* dxy, const unsigned char* dinf, unsigned char* dok, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  void* work = nullptr;
-  if (validate_work_bytes(curve, n)) {
-    work = scratch_for(ctx, st, validate_work_bytes(curve, n));
-    if (!work) return FEC_E_OOM;
-  }
+  void* work;
+  WorkArea area;
+  area.add(work, validate_work_bytes(curve, n));
+  const int rc = area.acquire(ctx, stream ? (hipStream_t)stream : ctx->stream);
+  if (rc != FEC_OK) return rc;
   Launch L(ctx, stream, curve == FEC_ED25519 ? "k_ed_validate_pre + k_ed_mul_pers x2 + k_ed_validate_finish" : "k_validate_weierstrass");
   validate_launch(sched_env(ctx), curve, reinterpret_cast<const u32*>(dxy), dinf, dok, work, n, L.s);
   return L.done();
@@ -1090,9 +1091,11 @@ int launch_validate(fec_ctx* ctx, int curve, const u64* dxy, const unsigned char
 int launch_ecdh(fec_ctx* ctx, int curve, const u64* dsk, const u64* dpk, const unsigned char* dinf, unsigned char* dout,
                 unsigned char* dstatus, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  void* work = scratch_for(ctx, st, ecdh_work_bytes(n));
-  if (!work) return FEC_E_OOM;
+  void* work;
+  WorkArea area;
+  area.add(work, ecdh_work_bytes(n));
+  const int rc = area.acquire(ctx, stream ? (hipStream_t)stream : ctx->stream);
+  if (rc != FEC_OK) return rc;
   Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_ecdh_pre + k_secp_mul + k_ecdh_finish" : "k_ecdh_pre + k_p256_mul_sched + k_ecdh_finish");
   ecdh_launch(sched_env(ctx), curve, reinterpret_cast<const u32*>(dsk), reinterpret_cast<const u32*>(dpk), dinf, reinterpret_cast<u32*>(dout),
               dstatus, work, n, L.s);
@@ -1102,32 +1105,24 @@ int launch_ecdh(fec_ctx* ctx, int curve, const u64* dsk, const u64* dpk, const u
 int launch_field(fec_ctx* ctx, int curve, int op, const u64* da, const u64* db, u64* dout, size_t n,
                  void* stream = nullptr) {
   if (n == 0) return FEC_OK;
-  const u32* a = reinterpret_cast<const u32*>(da);
-  const u32* bb = reinterpret_cast<const u32*>(db);
-  u32* o = reinterpret_cast<u32*>(dout);
-  dim3 g(grid_for(n)), b(TPB);
   Launch L(ctx, stream, "k_field_op");
-  switch (curve) {
-    case FEC_SECP256K1: hipLaunchKernelGGL((k_field_op<Secp>), g, b, 0, L.s, op, a, bb, o, n); break;
-    case FEC_P256: hipLaunchKernelGGL((k_field_op<P256>), g, b, 0, L.s, op, a, bb, o, n); break;
-    default: hipLaunchKernelGGL((k_field_op<Ed>), g, b, 0, L.s, op, a, bb, o, n); break;
-  }
+  with_curve(curve, [&](auto c) {
+    using C = decltype(c);
+    hipLaunchKernelGGL((k_field_op<C>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, reinterpret_cast<const u32*>(da),
+                       reinterpret_cast<const u32*>(db), reinterpret_cast<u32*>(dout), n);
+  });
   return L.done();
 }
 
 int launch_point(fec_ctx* ctx, int curve, int op, const u64* dp, const u64* dq, u64* dout, size_t n,
                  void* stream = nullptr) {
   if (n == 0) return FEC_OK;
-  const u32* p = reinterpret_cast<const u32*>(dp);
-  const u32* q = reinterpret_cast<const u32*>(dq);
-  u32* o = reinterpret_cast<u32*>(dout);
-  dim3 g(grid_for(n)), b(TPB);
   Launch L(ctx, stream, "k_point_op");
-  switch (curve) {
-    case FEC_SECP256K1: hipLaunchKernelGGL((k_point_op<Secp>), g, b, 0, L.s, op, p, q, o, n); break;
-    case FEC_P256: hipLaunchKernelGGL((k_point_op<P256>), g, b, 0, L.s, op, p, q, o, n); break;
-    default: hipLaunchKernelGGL((k_point_op<Ed>), g, b, 0, L.s, op, p, q, o, n); break;
-  }
+  with_curve(curve, [&](auto c) {
+    using C = decltype(c);
+    hipLaunchKernelGGL((k_point_op<C>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, reinterpret_cast<const u32*>(dp),
+                       reinterpret_cast<const u32*>(dq), reinterpret_cast<u32*>(dout), n);
+  });
   return L.done();
 }
 
@@ -1496,12 +1491,8 @@ int fec_batch_mul_fixed_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* ds, c
   if (!ctx || !curve_ok(curve) || (n && (!ds || !dbase || !dout))) return FEC_E_ARG;
   if (!aligned16(ds) || !aligned16(dbase) || !aligned16(dout)) return FEC_E_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  if (curve == FEC_ED25519) {
-    // the ctx's own generator (fec_generator_dev) is recognised by address, so its table is built once
-    const u64* host_base = dbase == ctx->d_gen[FEC_ED25519] ? ctx->h_gen_ed : nullptr;
-    return launch_ed_fixed(ctx, ds, dbase, host_base, dout, n, stream);
-  }
-  return launch_mul(ctx, curve, true, ds, dbase, dout, n, stream);
+  // (Ed25519: the ctx's own generator (fec_generator_dev) is recognised by address, so its addend table is built once)
+  return launch_mul(ctx, curve, true, ds, dbase, dout, n, stream, dbase == ctx->d_gen[FEC_ED25519] ? ctx->h_gen_ed : nullptr);
 } FEC_ABI_CATCH_STATUS
 
 int fec_batch_double_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d1, const uint64_t* d2,
@@ -1554,9 +1545,8 @@ int fec_multi_batch_mul_fixed_dev(fec_ctx* ctx, fec_curve curve, const uint64_t*
                        [&](fec_ctx* c, size_t g, size_t lo, size_t m, uint64_t* o, void* s) {
                          // no base given: the device's own copy of the reference's generator() (and its prefix table)
                          const uint64_t* base = bases && bases[g] ? bases[g] : c->d_gen[curve];
-                         if (curve == FEC_ED25519)
-                           return launch_ed_fixed(c, scalars[g] + lo * 4, base, base == c->d_gen[FEC_ED25519] ? c->h_gen_ed : nullptr, o, m, s);
-                         return launch_mul(c, curve, true, scalars[g] + lo * 4, base, o, m, s);
+                         return launch_mul(c, curve, true, scalars[g] + lo * 4, base, o, m, s,
+                                           base == c->d_gen[FEC_ED25519] ? c->h_gen_ed : nullptr);
                        });
 } FEC_ABI_CATCH_STATUS
 
@@ -1624,8 +1614,7 @@ int fec_batch_mul_fixed(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, 
   const HostIn in[3] = {{scalars, 32, 0}, {base, 0, pb}, {nullptr, 0, 0}};
   return host_pipeline(ctx, n, in, out, pb, [&](void* a, void* b, void*, void* o, size_t cnt, void* s) {
     const u64* db = is_gen ? ctx->d_gen[curve] : (const u64*)b;
-    if (curve == FEC_ED25519) return launch_ed_fixed(ctx, (const u64*)a, db, base, (u64*)o, cnt, s);
-    return launch_mul(ctx, curve, true, (const u64*)a, db, (u64*)o, cnt, s);
+    return launch_mul(ctx, curve, true, (const u64*)a, db, (u64*)o, cnt, s, base);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -1672,13 +1661,10 @@ int fec_multi_scalar_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars,
   }
   {
     Launch L(ctx, nullptr, "k_fold_sum");
-    const u32* prod = reinterpret_cast<const u32*>(ctx->d_buf[6]);
-    u32* o = reinterpret_cast<u32*>(ctx->d_buf[7]);
-    switch (curve) {
-      case FEC_SECP256K1: hipLaunchKernelGGL((k_fold_sum<Secp>), dim3(1), dim3(64), 0, L.s, prod, o, n); break;
-      case FEC_P256: hipLaunchKernelGGL((k_fold_sum<P256>), dim3(1), dim3(64), 0, L.s, prod, o, n); break;
-      default: hipLaunchKernelGGL((k_fold_sum<Ed>), dim3(1), dim3(64), 0, L.s, prod, o, n); break;
-    }
+    with_curve(curve, [&](auto c) {
+      using C = decltype(c);
+      hipLaunchKernelGGL((k_fold_sum<C>), dim3(1), dim3(64), 0, L.s, (const u32*)ctx->d_buf[6], (u32*)ctx->d_buf[7], n);
+    });
     rc = L.done();
     if (rc != FEC_OK) return rc;
   }
@@ -1772,52 +1758,52 @@ int fec_ecdsa_batch_verify(fec_ctx* ctx, fec_curve curve, const uint8_t* digests
   unsigned char res = 0;
   uint64_t det[16];
   return drained(ctx, [&]() -> int {
-  // slots: 0 digests, 1 r, 2 s, 3 pk, 4 a, 5 pk_inf, 6 work area, 7 r_sum + detail + result
+  // slots: 0 digests, 1 r, 2 s, 3 pk, 4 a, 5 pk_inf, 6 work area (ecdsa_layout), 7 r_sum + detail + result
   const void* hin[6] = {digests, r, s, pk_xy, a, pk_inf};
   const size_t bytes[6] = {n * 32, n * 32, n * 32, n * 64, n * 32, n};
+  EcdsaWork w;
+  WorkArea area;
+  ecdsa_layout(area, w, n, true);
   int rc = FEC_OK;
   for (int i = 0; i < 6 && rc == FEC_OK; ++i)
     if (hin[i]) rc = ensure(ctx, i, bytes[i]);
-  if (rc == FEC_OK) rc = ensure(ctx, 6, ecdsa_batch_work_bytes(n));
+  if (rc == FEC_OK) rc = ensure(ctx, 6, area.bytes());
   if (rc == FEC_OK) rc = ensure(ctx, 7, 96 + 128 + 16);
   if (rc != FEC_OK) return rc;
   for (int i = 0; i < 6; ++i)
     if (hin[i] && hipMemcpyAsync(ctx->d_buf[i], hin[i], bytes[i], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
       return FEC_E_DEVICE;
-  char* work = static_cast<char*>(ctx->d_buf[6]);
+  area.place(ctx->d_buf[6]);
   char* tail = static_cast<char*>(ctx->d_buf[7]);
   {
     Launch L(ctx, nullptr, "k_ecdsa_pre");
-    ecdsa_batch_pre_launch(curve, (const unsigned char*)ctx->d_buf[0], (const u32*)ctx->d_buf[1], (const u32*)ctx->d_buf[2],
-                           (const u32*)ctx->d_buf[3], pk_inf ? (const unsigned char*)ctx->d_buf[5] : nullptr,
-                           (const u32*)ctx->d_buf[4], work, n, L.s);
+    ecdsa_pre_launch(curve, (const unsigned char*)ctx->d_buf[0], (const u32*)ctx->d_buf[1], (const u32*)ctx->d_buf[2],
+                     (const u32*)ctx->d_buf[3], pk_inf ? (const unsigned char*)ctx->d_buf[5] : nullptr, (const u32*)ctx->d_buf[4],
+                     w, n, L.s);
     rc = L.done();
     if (rc != FEC_OK) return rc;
   }
   // the loop returns at the first signature that fails a check (317-342): nothing after it is computed
-  if (hipMemcpyAsync(flags.get(), work + n * 352, n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
+  if (hipMemcpyAsync(flags.get(), w.flags, n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
   if (int rc_sync = sync_and_check(ctx, ctx->stream)) return rc_sync;
   for (size_t i = 0; i < n; ++i)
     if (flags[i] != 0) {
       *result = flags[i] == 2 ? 2 : 0;
       return FEC_OK;
     }
-  u32* ta = reinterpret_cast<u32*>(work + n * 160);
-  u32* tb = reinterpret_cast<u32*>(work + n * 256);
   ensure_gen_prefix(ctx, curve, ctx->stream, n);
   {
     Launch L(ctx, nullptr, curve == FEC_SECP256K1 ? "k_secp_mul x2 + k_point_op + k_fold_sum + k_ecdsa_batch_finish"
                                                   : "k_p256_mul_sched x2 + k_point_op + k_fold_sum + k_ecdsa_batch_finish");
-    ecdsa_batch_mul_launch(sched_env(ctx), curve, reinterpret_cast<const u32*>(ctx->d_gen[curve]), work, n, L.s, ctx->stream2);
-    const dim3 g(grid_for(n)), b(TPB);
-    if (curve == FEC_SECP256K1) {  // r_i = r1 + r2 (355), then r_sum += r_i in index order (358)
-      hipLaunchKernelGGL((k_point_op<Secp>), g, b, 0, L.s, (int)FEC_P_ADD, (const u32*)ta, (const u32*)tb, ta, n);
-      hipLaunchKernelGGL((k_fold_sum<Secp>), dim3(1), dim3(64), 0, L.s, (const u32*)ta, (u32*)tail, n);
-    } else {
-      hipLaunchKernelGGL((k_point_op<P256>), g, b, 0, L.s, (int)FEC_P_ADD, (const u32*)ta, (const u32*)tb, ta, n);
-      hipLaunchKernelGGL((k_fold_sum<P256>), dim3(1), dim3(64), 0, L.s, (const u32*)ta, (u32*)tail, n);
-    }
-    ecdsa_batch_finish_launch(curve, (const u32*)tail, work, n, (unsigned char*)(tail + 96 + 128), (u32*)(tail + 96), L.s);
+    // ta = multiply(G, a*u1), tb = multiply(Q, a*u2): at the moderate n batch_verify is meant for, one launch fills a
+    // fraction of the chip and is bound by the latency of one multiplication, so the two overlap
+    product_pair(ctx, curve, n, L.s, SideStream::kSideStreamMax, kP256VarAffineMs, w.u1, w.ta, nullptr, w.u2, w.q, w.tb);
+    with_curve(curve, [&](auto c) {   // r_i = r1 + r2 (355), then r_sum += r_i in index order (358)
+      using C = decltype(c);
+      hipLaunchKernelGGL((k_point_op<C>), dim3(grid_for(n)), dim3(TPB), 0, L.s, (int)FEC_P_ADD, (const u32*)w.ta, (const u32*)w.tb, w.ta, n);
+      hipLaunchKernelGGL((k_fold_sum<C>), dim3(1), dim3(64), 0, L.s, (const u32*)w.ta, (u32*)tail, n);
+    });
+    ecdsa_batch_finish_launch(curve, (const u32*)tail, w.ar, n, (unsigned char*)(tail + 96 + 128), (u32*)(tail + 96), L.s);
     rc = L.done();
     if (rc != FEC_OK) return rc;
   }
@@ -2011,7 +1997,7 @@ int fec_schnorr_verify(fec_ctx* ctx, fec_curve curve, const uint64_t* pk_xy, con
 } FEC_ABI_CATCH_STATUS
 
 namespace {
-// schnorr::batch_verify::<C, D> (forge-ec-signature/src/schnorr.rs:194-290) for C = Secp256k1 / P256
+// schnorr::batch_verify::<C, D> (forge-ec-signature/src/schnorr.rs:194-290) for C = Secp256k1 / P256 / Ed25519
 int schnorr_batch_verify(fec_ctx* ctx, int curve, const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* r_xy,
                          const uint8_t* r_inf, const uint64_t* s, const uint64_t* a, const uint64_t* e, size_t n,
                          uint8_t* result, uint64_t* sides_xy, uint8_t* sides_inf, uint8_t* debug_build_panics = nullptr) {
@@ -2049,94 +2035,48 @@ int schnorr_batch_verify(fec_ctx* ctx, int curve, const uint64_t* pk_xy, const u
   unsigned int* d_done = (unsigned int*)(tail + 2 * pb + 128 + 8);
   unsigned char* d_wrapped = (unsigned char*)(tail + 2 * pb + 128 + 16);   // Ed25519: some s_i * a_i wrapped a u128 sum
   if (hipMemsetAsync(tail + 2 * pb + 128, 0, 32, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
-  if (edw) {
-    // Ed25519 (the generic batch_verify::<Ed25519, D>): the same pipeline with that curve's kernels -- multiply(G, .) by
-    // the table kernel, the two variable-base products by the scheduler kernel -- one after the other on the ctx stream
-    // work area: s*a (32 n), from_affine(P) (128 n), e*P (128 n), R + e*P (128 n), then the popcount-sort area of the
-    // table kernel (n >= 2^16).  One request: scratch_for hands every request on this stream the same buffer, so the
-    // sort area must not be asked for separately while s*a lives in it.
-    const size_t ed_work = ed_fixed_work_bytes(n);
-    char* work = static_cast<char*>(scratch_for(ctx, ctx->stream, n * (32 + 3 * pb) + ed_work));
-    if (!work) return FEC_E_OOM;
-    u32* sa = reinterpret_cast<u32*>(work);
-    u32* pp = reinterpret_cast<u32*>(work + n * 32);
-    u32* ep = reinterpret_cast<u32*>(work + n * (32 + pb));
-    u32* qq = reinterpret_cast<u32*>(work + n * (32 + 2 * pb));
-    const dim3 g(grid_for(n)), b(TPB);
-    {
-      Launch L(ctx, nullptr, "k_schnorr_pre");
-      hipLaunchKernelGGL((k_schnorr_pre<Ed>), g, b, 0, L.s, (const u32*)ctx->d_buf[0], (const u32*)ctx->d_buf[2], (const u32*)ctx->d_buf[3], sa, pp, d_wrapped, n);
-      rc = L.done();
-      if (rc != FEC_OK) return rc;
-    }
-    rc = ensure_ed_table(ctx, ctx->d_gen[FEC_ED25519], ctx->h_gen_ed, ctx->stream);
+  {
+    // work area: s*a (32 n), from_affine(P), e*P, R + e*P (one point each), and the popcount-sort area of the Ed25519 table
+    // kernel (n >= 2^16)
+    u32 *sa, *pp, *ep, *qq;
+    void* sort;
+    WorkArea area;
+    area.add(sa, n * 32).add(pp, n * pb).add(ep, n * pb).add(qq, n * pb).add(sort, edw ? ed_fixed_work_bytes(n) : 0);
+    rc = area.acquire(ctx, ctx->stream);
+    if (rc == FEC_OK) rc = prepare_generator(ctx, curve, ctx->stream, n);
     if (rc != FEC_OK) return rc;
-    ensure_gen_prefix(ctx, FEC_ED25519, ctx->stream, n);
-    {
-      Launch L(ctx, nullptr, ed_work ? "k_ed_fixed_sorted (+ k_ed_pc_hist, k_ed_pc_scan, k_ed_pc_scatter)" : "k_ed_fixed_base");
-      ed_fixed_launch(sched_env(ctx), sa, reinterpret_cast<const u32*>(ctx->d_gen[FEC_ED25519]), ctx->d_ed_table,
-                      (u32*)ctx->d_buf[5], n, ed_work ? work + n * (32 + 3 * pb) : nullptr, L.s);   // A_i (266-268)
-      rc = L.done();
-      if (rc != FEC_OK) return rc;
-    }
-    {
-      Launch L(ctx, nullptr, "k_schnorr_pre + k_ed_fixed_base + k_ed_mul_pers x2 + k_schnorr_mid");
-      const SchedEnv env = sched_env(ctx);
-      ed_launch_mul(env, (const u32*)ctx->d_buf[4], pp, ep, n, L.s);                                                        // e_i P_i (276)
-      hipLaunchKernelGGL((k_schnorr_mid<Ed>), g, b, 0, L.s, (const u32*)ctx->d_buf[1], (const u32*)ep, qq, n);
-      ed_launch_mul(env, (const u32*)ctx->d_buf[3], qq, (u32*)ctx->d_buf[6], n, L.s);                                       // B_i (282)
-      rc = L.done();
-      if (rc != FEC_OK) return rc;
-    }
-  } else {
-    // work area: s*a (32 n), from_affine(P) (96 n), e*P (96 n), R + e*P (96 n)
-    char* work = static_cast<char*>(scratch_for(ctx, ctx->stream, n * 320));
-    if (!work) return FEC_E_OOM;
-    u32* sa = reinterpret_cast<u32*>(work);
-    u32* pp = reinterpret_cast<u32*>(work + n * 32);
-    u32* ep = reinterpret_cast<u32*>(work + n * 128);
-    u32* qq = reinterpret_cast<u32*>(work + n * 224);
-    const u32* gen = reinterpret_cast<const u32*>(ctx->d_gen[curve]);
-    ensure_gen_prefix(ctx, curve, ctx->stream, n);
-    const SchedEnv env = sched_env(ctx);
-    Launch L(ctx, nullptr, secp ? "k_schnorr_pre + k_secp_mul x3 + k_schnorr_mid" : "k_schnorr_pre + k_p256_mul_sched x3 + k_schnorr_mid");
+    Launch L(ctx, nullptr, secp ? "k_schnorr_pre + k_secp_mul x3 + k_schnorr_mid"
+                           : (edw ? "k_schnorr_pre + k_ed_fixed_base + k_ed_mul_pers x2 + k_schnorr_mid"
+                                  : "k_schnorr_pre + k_p256_mul_sched x3 + k_schnorr_mid"));
     const dim3 g(grid_for(n)), b(TPB);
-    auto mul = [&](bool fixed, const u32* k, const u32* p, u32* o, hipStream_t st, const SchedEnv& e) {
-      if (secp) secp_launch_mul(e, fixed, k, p, o, n, st);
-      else p256_launch_mul(e, fixed, k, p, o, n, st);
-    };
-    if (secp) hipLaunchKernelGGL((k_schnorr_pre<Secp>), g, b, 0, L.s, (const u32*)ctx->d_buf[0], (const u32*)ctx->d_buf[2], (const u32*)ctx->d_buf[3], sa, pp, (unsigned char*)nullptr, n);
-    else hipLaunchKernelGGL((k_schnorr_pre<P256>), g, b, 0, L.s, (const u32*)ctx->d_buf[0], (const u32*)ctx->d_buf[2], (const u32*)ctx->d_buf[3], sa, pp, (unsigned char*)nullptr, n);
-    // the A terms do not depend on the B chain: they run on the ctx's second stream beside it (at the moderate n
-    // this entry point is meant for, a launch fills a fraction of the chip and is bound by one ladder's latency)
-    hipEvent_t ev_pre = nullptr, ev_a = nullptr;
-    const bool side = ctx->stream2 != nullptr && hipEventCreateWithFlags(&ev_pre, hipEventDisableTiming) == hipSuccess &&
-                      hipEventCreateWithFlags(&ev_a, hipEventDisableTiming) == hipSuccess;
-    hipStream_t sa_stream = L.s;
-    if (side) {
-      (void)hipEventRecord(ev_pre, L.s);
-      (void)hipStreamWaitEvent(ctx->stream2, ev_pre, 0);
-      sa_stream = ctx->stream2;
-    }
-    // the persistent P-256 kernels: the CUs in proportion to the work on either stream (one fixed-base launch beside
-    // two variable-base ones) while they run side by side
-    SchedEnv ef = env, ev = env;
-    if (side && !secp) p256_cu_split(env, n, kP256VarAffineMs + kP256VarMs, ef, ev);
-    mul(true, sa, gen, (u32*)ctx->d_buf[5], sa_stream, ef);                              // A_i (266-268)
-    if (side) (void)hipEventRecord(ev_a, ctx->stream2);
-    mul(false, (const u32*)ctx->d_buf[4], pp, ep, L.s, ev);                              // e_i P_i (276)
-    if (secp) hipLaunchKernelGGL((k_schnorr_mid<Secp>), g, b, 0, L.s, (const u32*)ctx->d_buf[1], (const u32*)ep, qq, n);
-    else hipLaunchKernelGGL((k_schnorr_mid<P256>), g, b, 0, L.s, (const u32*)ctx->d_buf[1], (const u32*)ep, qq, n);
-    mul(false, (const u32*)ctx->d_buf[3], qq, (u32*)ctx->d_buf[6], L.s, ev);             // B_i (282)
-    if (side) (void)hipStreamWaitEvent(L.s, ev_a, 0);
+    auto d = [&](int slot) { return static_cast<const u32*>(ctx->d_buf[slot]); };
+    with_curve(curve, [&](auto c) {
+      using C = decltype(c);
+      hipLaunchKernelGGL((k_schnorr_pre<C>), g, b, 0, L.s, d(0), d(2), d(3), sa, pp, edw ? d_wrapped : (unsigned char*)nullptr, n);
+    });
+    // the A terms do not depend on the B chain: for the Weierstrass curves they run on the ctx's second stream beside it
+    // (at the moderate n this entry point is meant for, a launch fills a fraction of the chip and is bound by one ladder's
+    // latency; the P-256 CUs in proportion to one fixed-base launch beside two variable-base ones).  Ed25519 (the generic
+    // batch_verify::<Ed25519, D>): the same products one after the other on the ctx stream.
+    SideStream side(ctx, L.s, n, edw ? 0 : SideStream::kSideStreamMax);
+    const ProductEnvs env = product_envs(ctx, curve, n, side.active, kP256VarAffineMs + kP256VarMs);
+    fixed_product(ctx, env.fixed, curve, sa, reinterpret_cast<const u32*>(ctx->d_gen[curve]), (u32*)ctx->d_buf[5], n, sort,
+                  side.s);                                                                             // A_i (266-268)
+    var_product(env.var, curve, d(4), pp, ep, n, L.s);                                                 // e_i P_i (276)
+    with_curve(curve, [&](auto c) {
+      using C = decltype(c);
+      hipLaunchKernelGGL((k_schnorr_mid<C>), g, b, 0, L.s, d(1), (const u32*)ep, qq, n);
+    });
+    var_product(env.var, curve, d(3), qq, (u32*)ctx->d_buf[6], n, L.s);                                // B_i (282)
+    side.join();
     rc = L.done();
-    if (ev_pre) (void)hipEventDestroy(ev_pre);
-    if (ev_a) (void)hipEventDestroy(ev_a);
     if (rc != FEC_OK) return rc;
   }
-  if (secp) hipLaunchKernelGGL((k_schnorr_fold_compare<Secp>), dim3(2), dim3(64), 0, ctx->stream, (const u32*)ctx->d_buf[5], (const u32*)ctx->d_buf[6], d_sums, d_sides, d_flags, d_done, n);
-  else if (edw) hipLaunchKernelGGL((k_schnorr_fold_compare<Ed>), dim3(2), dim3(64), 0, ctx->stream, (const u32*)ctx->d_buf[5], (const u32*)ctx->d_buf[6], d_sums, d_sides, d_flags, d_done, n);
-  else hipLaunchKernelGGL((k_schnorr_fold_compare<P256>), dim3(2), dim3(64), 0, ctx->stream, (const u32*)ctx->d_buf[5], (const u32*)ctx->d_buf[6], d_sums, d_sides, d_flags, d_done, n);
+  with_curve(curve, [&](auto c) {
+    using C = decltype(c);
+    hipLaunchKernelGGL((k_schnorr_fold_compare<C>), dim3(2), dim3(64), 0, ctx->stream, (const u32*)ctx->d_buf[5],
+                       (const u32*)ctx->d_buf[6], d_sums, d_sides, d_flags, d_done, n);
+  });
   if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
   if (hipMemcpyAsync(flags + 4, d_wrapped, 1, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
   if (hipMemcpyAsync(flags, d_flags, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||

@@ -50,11 +50,13 @@ struct fec_ctx {
   // multi-device ctx (fec_ctx_create_multi): the shard workers; empty for a single-device ctx
   std::vector<fec_ctx*> children;
   // per-stream scratch of the composed launches (two ladders + one addition): a buffer is only ever
-  // used by launches on the stream it belongs to, so calls on different streams cannot race on it
+  // used by launches on the stream it belongs to, so calls on different streams cannot race on it.  `held`: a launcher
+  // owns it right now (host::WorkArea), and nothing else on that stream may have it.
   struct StreamScratch {
     hipStream_t stream;
     void* buf;
     size_t cap;
+    bool held;
   };
   std::vector<StreamScratch> stream_scratch;
   // ordering of launches that share ctx-owned scratch (Ed25519 addend table, canonical-mode work areas,
@@ -139,11 +141,14 @@ inline int ensure(fec_ctx* ctx, int slot, size_t bytes) {
   return FEC_OK;
 }
 
-// Device scratch of at least `bytes` dedicated to `stream` (grown on demand; growing waits for that stream).
-inline void* scratch_for(fec_ctx* ctx, hipStream_t stream, size_t bytes) {
+// Device scratch of at least `bytes` dedicated to `stream` (grown on demand; growing waits for that stream).  Only
+// WorkArea asks for it.  Null when there is no memory, or when the stream's scratch is held: it is then neither handed
+// out a second time nor regrown under its holder.
+inline fec_ctx::StreamScratch* scratch_for(fec_ctx* ctx, hipStream_t stream, size_t bytes) {
   for (auto& e : ctx->stream_scratch) {
     if (e.stream != stream) continue;
-    if (e.cap >= bytes) return e.buf;
+    if (e.held) return nullptr;
+    if (e.cap >= bytes) return &e;
     (void)hipMemsetAsync(e.buf, 0, e.cap, stream);  // cleared before it is released (it may hold u1/u2, shared points)
     (void)hipStreamSynchronize(stream);
     (void)hipFree(e.buf);
@@ -154,9 +159,9 @@ inline void* scratch_for(fec_ctx* ctx, hipStream_t stream, size_t bytes) {
       return nullptr;
     }
     e.cap = bytes + (bytes >> 2);
-    return e.buf;
+    return &e;
   }
-  fec_ctx::StreamScratch e{stream, nullptr, 0};
+  fec_ctx::StreamScratch e{stream, nullptr, 0, false};
   if (hipMalloc(&e.buf, bytes + (bytes >> 2)) != hipSuccess) {
     (void)hipGetLastError();
     return nullptr;
@@ -168,8 +173,73 @@ inline void* scratch_for(fec_ctx* ctx, hipStream_t stream, size_t bytes) {
     (void)hipFree(e.buf);
     return nullptr;
   }
-  return e.buf;
+  return &ctx->stream_scratch.back();
 }
+
+// A launcher's work area: named regions, each on a 256-byte boundary, laid out once and then either taken from the
+// launch stream's scratch in ONE request (acquire) or placed on memory the caller owns (place).  Each region's pointer is
+// set then (null for an empty region).  Acquired scratch is held until the WorkArea goes out of scope: a second
+// acquisition on that stream in the meantime fails instead of being handed the same buffer, so one launcher's regions
+// can never be written over by another's (the launcher keeps its WorkArea alive past its last enqueue that uses it).
+class WorkArea {
+ public:
+  static constexpr size_t kAlign = 256;
+  WorkArea() = default;
+  WorkArea(const WorkArea&) = delete;
+  WorkArea& operator=(const WorkArea&) = delete;
+  ~WorkArea() {
+    if (ctx_) ctx_->stream_scratch[held_].held = false;
+  }
+  template <class T>
+  WorkArea& add(T*& p, size_t bytes) {
+    p = nullptr;
+    if (count_ < kMaxRegions) regions_[count_] = Region{&p, total_, bytes, &assign<T>};
+    ++count_;
+    total_ += (bytes + kAlign - 1) & ~(kAlign - 1);
+    return *this;
+  }
+  // forget the last k regions (not after acquire / place)
+  void pop(int k) {
+    for (; k > 0 && count_ > 0 && count_ <= kMaxRegions; --k) total_ = regions_[--count_].off;
+  }
+  size_t bytes() const { return total_; }
+  void place(void* base) {
+    for (int i = 0; i < count_ && i < kMaxRegions; ++i)
+      regions_[i].set(regions_[i].slot, regions_[i].bytes ? static_cast<char*>(base) + regions_[i].off : nullptr);
+  }
+  // FEC_E_OOM: no memory; FEC_E_DEVICE: the stream's scratch is held already (no correct path nests: an internal error).
+  // An empty area takes nothing.
+  int acquire(fec_ctx* ctx, hipStream_t s) {
+    if (ctx_ || count_ > kMaxRegions) return FEC_E_DEVICE;
+    if (total_ == 0) return FEC_OK;
+    for (const auto& e : ctx->stream_scratch)
+      if (e.stream == s && e.held) return FEC_E_DEVICE;
+    fec_ctx::StreamScratch* e = scratch_for(ctx, s, total_);
+    if (!e) return FEC_E_OOM;
+    e->held = true;
+    ctx_ = ctx;
+    held_ = (size_t)(e - ctx->stream_scratch.data());
+    place(e->buf);
+    return FEC_OK;
+  }
+
+ private:
+  static constexpr int kMaxRegions = 8;
+  template <class T>
+  static void assign(void* slot, char* at) {
+    *static_cast<T**>(slot) = reinterpret_cast<T*>(at);
+  }
+  struct Region {
+    void* slot;  // the caller's T* that acquire / place sets
+    size_t off, bytes;
+    void (*set)(void*, char*);
+  };
+  Region regions_[kMaxRegions];
+  int count_ = 0;
+  size_t total_ = 0;
+  fec_ctx* ctx_ = nullptr;  // set while the scratch entry held_ is held
+  size_t held_ = 0;
+};
 
 // Calls on one ctx are serialised by the caller on the HOST, but they may name different streams while
 // sharing ctx-owned device scratch.  Every launch therefore orders itself after the previous launch of

@@ -57,21 +57,22 @@ void secp_prefix_level_launch(const u32* parent, u32* child, size_t child_entrie
 void codec_launch(int op, int curve, const void* in, const void* in2, void* out, void* out2, void* out3, size_t n,
                   hipStream_t s);
 
-// kernels_ecdsa.hip: Ecdsa::<C, D>::verify for C = Secp256k1 / P256 (ecdsa.rs:213-281): scalar pre-pass, the two
-// multiplications through the launchers above, finishing pass.  `work` holds ecdsa_work_bytes(n) bytes.
-size_t ecdsa_work_bytes(size_t n);
-void ecdsa_launch(const SchedEnv& env, int curve, const unsigned char* digests, const u32* r, const u32* s_, const u32* pk,
-                  const unsigned char* pk_inf, const u32* gen, unsigned char* status, void* work, size_t n,
-                  hipStream_t s, hipStream_t side = nullptr);   // side: a second stream for the fixed-base launch, or null
-
-// kernels_ecdsa.hip: Ecdsa::<C, D>::batch_verify (ecdsa.rs:287-391) in three parts around the point fold that
-// fecgpu.hip owns.  Work area (ecdsa_batch_work_bytes): u1 +0, u2 +32n, Q +64n, ta +160n, tb +256n, flags +352n
-// (one byte per signature: 0 go, 1 the loop returns false here, 2 it panics here), a_i * r_i after that.
-size_t ecdsa_batch_work_bytes(size_t n);
-void ecdsa_batch_pre_launch(int curve, const unsigned char* digests, const u32* r, const u32* s_, const u32* pk,
-                            const unsigned char* pk_inf, const u32* weights, void* work, size_t n, hipStream_t s);
-void ecdsa_batch_mul_launch(const SchedEnv& env, int curve, const u32* gen, void* work, size_t n, hipStream_t s, hipStream_t side);
-void ecdsa_batch_finish_launch(int curve, const u32* r_sum, const void* work, size_t n, unsigned char* result, u32* detail,
+// kernels_ecdsa.hip: Ecdsa::<C, D>::verify (ecdsa.rs:213-281) and batch_verify (287-391) for C = Secp256k1 / P256, the
+// passes around multiply(G, u1) -> ta and multiply(Q, u2) -> tb, which fecgpu.hip launches (and, for batch_verify, its
+// ordered point fold).  The work area (fecgpu.hip: ecdsa_layout): u1, u2 (8 words each), Q, ta, tb (24 words each),
+// flags (one byte per signature: 0 go, 1 the loop returns false here, 2 it panics here), a_i * r_i (8 words; batch only).
+struct EcdsaWork {
+  u32 *u1, *u2, *q, *ta, *tb;
+  unsigned char* flags;
+  u32* ar;
+};
+// scalars, flags and Q = from_affine(pk); with `weights` (batch_verify) u1, u2 times a_i and a_i * r_i into ar
+void ecdsa_pre_launch(int curve, const unsigned char* digests, const u32* r, const u32* s_, const u32* pk,
+                      const unsigned char* pk_inf, const u32* weights, const EcdsaWork& w, size_t n, hipStream_t s);
+// verify: status from ta + tb, r and the flags
+void ecdsa_finish_launch(int curve, const u32* r, const EcdsaWork& w, unsigned char* status, size_t n, hipStream_t s);
+// batch_verify: result and detail from the folded r_sum and the ordered sum of ar
+void ecdsa_batch_finish_launch(int curve, const u32* r_sum, const u32* ar, size_t n, unsigned char* result, u32* detail,
                                hipStream_t s);
 
 // kernels_ecdsa.hip: Curve::validate_point per affine point (secp256k1 / P-256: is_on_curve; Ed25519: the trait default
@@ -93,8 +94,7 @@ void eddsa_finish_launch(const u32* sg, const u32* ka, const u32* r_xy, const un
                          size_t n, hipStream_t s);
 
 // kernels_ecdsa.hip: Schnorr::<C, D>::verify per signature (schnorr.rs:90-140) around the curve's multiplications:
-// a[i] = from_affine(pk[i]); status from sg = multiply(G, s), ep = multiply(A, e), R.  Work: A, sg, ep.
-size_t schnorr_verify_work_bytes(int curve, size_t n);
+// a[i] = from_affine(pk[i]); status from sg = multiply(G, s), ep = multiply(A, e), R.
 void schnorr_verify_pre_launch(int curve, const u32* pk, const unsigned char* pk_inf, u32* a, size_t n, hipStream_t s);
 void schnorr_verify_finish_launch(int curve, const u32* sg, const u32* ep, const u32* r_xy, const unsigned char* r_inf,
                                   unsigned char* status, size_t n, hipStream_t s);

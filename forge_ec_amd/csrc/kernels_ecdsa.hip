@@ -3,7 +3,7 @@
 //   k_ecdsa_pre<E>     215-251: zero / range checks, h = Scalar::from_bytes(digest), s^-1, u1 = h * s^-1,
 //                      u2 = r * s^-1 in the curve's scalar field AS THE REFERENCE IMPLEMENTS IT, and
 //                      Q = from_affine(pk); writes u1, u2, Q and one flag byte per signature
-//   <curve>_launch_mul 254-255: multiply(G, u1) (fixed base) and multiply(Q, u2) with the curve's own kernel
+//   (fecgpu.hip)       254-255: multiply(G, u1) (fixed base) and multiply(Q, u2) with the curve's own kernel
 //   k_ecdsa_finish<E>  256-274: R = r1 + r2, identity check, to_affine, field_to_bytes -> Scalar::from_bytes,
 //                      comparison with r; writes status 1 valid / 0 invalid / 2 where the reference panics
 //                      (CtOption::unwrap on None at 239 or 271)
@@ -13,7 +13,6 @@
 #include "../../include/fecgpu.h"
 #include "ed25519.hpp"
 #include "kernels.hpp"
-#include "cu_split.hpp"
 #include "p256.hpp"
 #include "secp256k1.hpp"
 #include "staging.hpp"
@@ -67,9 +66,6 @@ struct ESecp {
   FEC_DEV static lmask to_affine(const pt& p, fe& x, fe& y) { return secp::to_affine(p, x, y); }
   FEC_DEV static fe wmul(const fe& a, const fe& b) { return secp::sc_mul(a, b); }   // impl Mul for Scalar
   FEC_DEV static fe wadd(const fe& a, const fe& b) { return secp::sc_add(a, b); }   // impl Add for Scalar
-  static void launch_mul(const SchedEnv& env, bool fixed, const u32* k, const u32* p, u32* o, size_t n, hipStream_t s, unsigned = 1) {
-    secp_launch_mul(env, fixed, k, p, o, n, s);
-  }
 };
 
 // P-256: scalar field p256.rs:875-1100, 1409-1432 (reduce_wide drops the high half of its second fold);
@@ -106,13 +102,6 @@ struct EP256 {
   FEC_DEV static lmask to_affine(const pt& p, fe& x, fe& y) { return p256::to_affine(p, x, y); }
   FEC_DEV static fe wmul(const fe& a, const fe& b) { return p256::sc_mul32(a, b); }
   FEC_DEV static fe wadd(const fe& a, const fe& b) { return p256::sc_fe(p256::sc_add(p256::sc_of(a), p256::sc_of(b))); }
-  // cu_divisor == 2: this launch runs beside its fixed- / variable-base twin on another stream (cu_split.hpp)
-  static void launch_mul(const SchedEnv& env, bool fixed, const u32* k, const u32* p, u32* o, size_t n, hipStream_t s,
-                         unsigned cu_divisor = 1) {
-    SchedEnv ef = env, ev = env;
-    if (cu_divisor == 2) p256_cu_split(env, n, kP256VarAffineMs, ef, ev);   // (u2 * from_affine(public key): affine addend)
-    p256_launch_mul(fixed ? ef : ev, fixed, k, p, o, n, s);
-  }
 };
 
 template <class E>
@@ -160,58 +149,6 @@ __global__ __launch_bounds__(TPB) void k_ecdsa_finish(const u32* __restrict__ ta
   const unsigned char st = E::finish(a, b, load8(rs + i * 8));
   const unsigned char f = flags[i];
   status[i] = f == F_FALSE ? 0 : (f == F_PANIC ? 2 : st);
-}
-
-// The fixed-base multiplication of a pair (multiply(G, u1), multiply(Q, u2)) forked onto a second stream and joined back
-// with events (no host blocking): the two launches overlap, each persistent kernel on half of the CUs.  Wins at every
-// batch size (fecgpu.hip: SideStream).  Inactive -- `s` is the main stream -- without a distinct second stream.
-struct Fork {
-  hipStream_t main, s;
-  hipEvent_t ev_in = nullptr, ev_out = nullptr;
-  bool active = false;
-  Fork(hipStream_t main_, hipStream_t side) : main(main_), s(main_) {
-    if (side == nullptr || side == main_) return;
-    if (hipEventCreateWithFlags(&ev_in, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ev_out, hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      return;
-    }
-    (void)hipEventRecord(ev_in, main);
-    (void)hipStreamWaitEvent(side, ev_in, 0);
-    s = side;
-    active = true;
-  }
-  void join() {
-    if (!active) return;
-    (void)hipEventRecord(ev_out, s);
-    (void)hipStreamWaitEvent(main, ev_out, 0);
-  }
-  ~Fork() {
-    if (ev_in) (void)hipEventDestroy(ev_in);
-    if (ev_out) (void)hipEventDestroy(ev_out);
-  }
-};
-
-template <class E>
-void run(const SchedEnv& env, const unsigned char* dd, const u32* dr, const u32* ds, const u32* dpk, const unsigned char* dinf, const u32* gen,
-         unsigned char* dstatus, void* work, size_t n, hipStream_t s, hipStream_t side) {
-  char* w = static_cast<char*>(work);
-  u32* u1 = reinterpret_cast<u32*>(w);
-  u32* u2 = reinterpret_cast<u32*>(w + n * 32);
-  u32* q = reinterpret_cast<u32*>(w + n * 64);
-  u32* ta = reinterpret_cast<u32*>(w + n * 160);
-  u32* tb = reinterpret_cast<u32*>(w + n * 256);
-  unsigned char* flags = reinterpret_cast<unsigned char*>(w + n * 352);
-  const dim3 g((unsigned)((n + TPB - 1) / TPB)), b(TPB);
-  hipLaunchKernelGGL((k_ecdsa_pre<E>), g, b, 0, s, dd, dr, ds, dpk, dinf, (const u32*)nullptr, u1, u2, q, flags,
-                     (u32*)nullptr, n);
-  {
-    Fork fork(s, side);
-    E::launch_mul(env, true, u1, gen, ta, n, fork.s, fork.active ? 2 : 1);
-    E::launch_mul(env, false, u2, q, tb, n, s, fork.active ? 2 : 1);
-    fork.join();
-  }
-  hipLaunchKernelGGL((k_ecdsa_finish<E>), g, b, 0, s, (const u32*)ta, (const u32*)tb, dr, (const unsigned char*)flags, dstatus, n);
 }
 
 // ---- Ecdsa::<C, D>::batch_verify (ecdsa.rs:287-391), the part after the ordered point fold ----
@@ -282,16 +219,17 @@ __global__ __launch_bounds__(TPB) void k_ecdh_finish(const u32* __restrict__ t, 
   store8(out + i * 8, o);
   status[i] = st;
 }
+using MulLauncher = void (*)(const SchedEnv&, bool, const u32*, const u32*, u32*, size_t, hipStream_t);
 template <class E>
-void run_ecdh(const SchedEnv& env, const u32* sk, const u32* pk, const unsigned char* pk_inf, u32* out, unsigned char* status, void* work, size_t n,
-              hipStream_t s) {
+void run_ecdh(MulLauncher mul, const SchedEnv& env, const u32* sk, const u32* pk, const unsigned char* pk_inf, u32* out,
+              unsigned char* status, void* work, size_t n, hipStream_t s) {
   char* w = static_cast<char*>(work);
   u32* q = reinterpret_cast<u32*>(w);
   u32* t = reinterpret_cast<u32*>(w + n * 96);
   unsigned char* flags = reinterpret_cast<unsigned char*>(w + n * 192);
   const dim3 g((unsigned)((n + TPB - 1) / TPB)), b(TPB);
   hipLaunchKernelGGL((k_ecdh_pre<E>), g, b, 0, s, pk, pk_inf, q, flags, n);
-  E::launch_mul(env, false, sk, q, t, n, s);
+  mul(env, false, sk, q, t, n, s);
   hipLaunchKernelGGL((k_ecdh_finish<E>), g, b, 0, s, (const u32*)t, (const unsigned char*)flags, out, status, n);
 }
 
@@ -470,7 +408,6 @@ __global__ __launch_bounds__(TPB) void k_schnorr_verify_finish(const u32* __rest
 
 }  // namespace
 
-size_t schnorr_verify_work_bytes(int curve, size_t n) { return n * 3 * (curve == FEC_ED25519 ? 128 : 96); }
 void schnorr_verify_pre_launch(int curve, const u32* pk, const unsigned char* pk_inf, u32* a, size_t n, hipStream_t s) {
   const dim3 g((unsigned)((n + TPB - 1) / TPB)), b(TPB);
   if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_schnorr_verify_pre<VSecp>), g, b, 0, s, pk, pk_inf, a, n);
@@ -492,8 +429,6 @@ void eddsa_finish_launch(const u32* sg, const u32* ka, const u32* r_xy, const un
                          size_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_eddsa_finish, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, s, sg, ka, r_xy, r_inf, status, n);
 }
-
-size_t ecdsa_work_bytes(size_t n) { return n * 353; }
 
 // Curve::validate_point.  Work (Ed25519 only): point A (128 n), scalars (32 n), products T1, T2 (128 n each), flags (n).
 size_t validate_work_bytes(int curve, size_t n) { return curve == FEC_ED25519 ? n * 417 : 0; }
@@ -523,54 +458,27 @@ void validate_launch(const SchedEnv& env, int curve, const u32* xy, const unsign
 size_t ecdh_work_bytes(size_t n) { return n * 193; }
 void ecdh_launch(const SchedEnv& env, int curve, const u32* sk, const u32* pk, const unsigned char* pk_inf, u32* out,
                  unsigned char* status, void* work, size_t n, hipStream_t s) {
-  if (curve == FEC_SECP256K1) run_ecdh<ESecp>(env, sk, pk, pk_inf, out, status, work, n, s);
-  else run_ecdh<EP256>(env, sk, pk, pk_inf, out, status, work, n, s);
+  if (curve == FEC_SECP256K1) run_ecdh<ESecp>(secp_launch_mul, env, sk, pk, pk_inf, out, status, work, n, s);
+  else run_ecdh<EP256>(p256_launch_mul, env, sk, pk, pk_inf, out, status, work, n, s);
 }
 
-// batch_verify, first half: work area as ecdsa_launch plus ar at +n*353 rounded up to 16 (n * 32 bytes).
-size_t ecdsa_batch_work_bytes(size_t n) { return ((n * 353 + 15) & ~(size_t)15) + n * 32; }
-void ecdsa_batch_pre_launch(int curve, const unsigned char* digests, const u32* r, const u32* s_, const u32* pk,
-                            const unsigned char* pk_inf, const u32* weights, void* work, size_t n, hipStream_t s) {
-  char* w = static_cast<char*>(work);
-  u32* u1 = reinterpret_cast<u32*>(w);
-  u32* u2 = reinterpret_cast<u32*>(w + n * 32);
-  u32* q = reinterpret_cast<u32*>(w + n * 64);
-  unsigned char* flags = reinterpret_cast<unsigned char*>(w + n * 352);
-  u32* ar = reinterpret_cast<u32*>(w + ((n * 353 + 15) & ~(size_t)15));
+void ecdsa_pre_launch(int curve, const unsigned char* digests, const u32* r, const u32* s_, const u32* pk,
+                      const unsigned char* pk_inf, const u32* weights, const EcdsaWork& w, size_t n, hipStream_t s) {
   const dim3 g((unsigned)((n + TPB - 1) / TPB)), b(TPB);
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_ecdsa_pre<ESecp>), g, b, 0, s, digests, r, s_, pk, pk_inf, weights, u1, u2, q, flags, ar, n);
-  else hipLaunchKernelGGL((k_ecdsa_pre<EP256>), g, b, 0, s, digests, r, s_, pk, pk_inf, weights, u1, u2, q, flags, ar, n);
+  if (curve == FEC_SECP256K1)
+    hipLaunchKernelGGL((k_ecdsa_pre<ESecp>), g, b, 0, s, digests, r, s_, pk, pk_inf, weights, w.u1, w.u2, w.q, w.flags, w.ar, n);
+  else hipLaunchKernelGGL((k_ecdsa_pre<EP256>), g, b, 0, s, digests, r, s_, pk, pk_inf, weights, w.u1, w.u2, w.q, w.flags, w.ar, n);
 }
-// second half: ta = multiply(G, a*u1), tb = multiply(Q, a*u2)
-// `side` (may be null): a second stream for the fixed-base launch -- at the moderate n batch_verify is meant for, one
-// launch fills a fraction of the chip and is bound by the latency of one multiplication, so the two overlap
-void ecdsa_batch_mul_launch(const SchedEnv& env, int curve, const u32* gen, void* work, size_t n, hipStream_t s, hipStream_t side) {
-  char* w = static_cast<char*>(work);
-  const u32* u1 = reinterpret_cast<const u32*>(w);
-  const u32* u2 = reinterpret_cast<const u32*>(w + n * 32);
-  const u32* q = reinterpret_cast<const u32*>(w + n * 64);
-  u32* ta = reinterpret_cast<u32*>(w + n * 160);
-  u32* tb = reinterpret_cast<u32*>(w + n * 256);
-  Fork fork(s, side);
-  const bool two = fork.active;
-  if (curve == FEC_SECP256K1) ESecp::launch_mul(env, true, u1, gen, ta, n, fork.s);
-  else EP256::launch_mul(env, true, u1, gen, ta, n, fork.s, two ? 2 : 1);
-  if (curve == FEC_SECP256K1) ESecp::launch_mul(env, false, u2, q, tb, n, s);
-  else EP256::launch_mul(env, false, u2, q, tb, n, s, two ? 2 : 1);
-  fork.join();
+void ecdsa_finish_launch(int curve, const u32* r, const EcdsaWork& w, unsigned char* status, size_t n, hipStream_t s) {
+  const dim3 g((unsigned)((n + TPB - 1) / TPB)), b(TPB);
+  if (curve == FEC_SECP256K1)
+    hipLaunchKernelGGL((k_ecdsa_finish<ESecp>), g, b, 0, s, (const u32*)w.ta, (const u32*)w.tb, r, (const unsigned char*)w.flags, status, n);
+  else hipLaunchKernelGGL((k_ecdsa_finish<EP256>), g, b, 0, s, (const u32*)w.ta, (const u32*)w.tb, r, (const unsigned char*)w.flags, status, n);
 }
-void ecdsa_batch_finish_launch(int curve, const u32* r_sum, const void* work, size_t n, unsigned char* result, u32* detail,
+void ecdsa_batch_finish_launch(int curve, const u32* r_sum, const u32* ar, size_t n, unsigned char* result, u32* detail,
                                hipStream_t s) {
-  const u32* ar = reinterpret_cast<const u32*>(static_cast<const char*>(work) + ((n * 353 + 15) & ~(size_t)15));
   if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_ecdsa_batch_finish<ESecp>), dim3(1), dim3(64), 0, s, r_sum, ar, n, result, detail);
   else hipLaunchKernelGGL((k_ecdsa_batch_finish<EP256>), dim3(1), dim3(64), 0, s, r_sum, ar, n, result, detail);
-}
-
-void ecdsa_launch(const SchedEnv& env, int curve, const unsigned char* digests, const u32* r, const u32* s_, const u32* pk,
-                  const unsigned char* pk_inf, const u32* gen, unsigned char* status, void* work, size_t n,
-                  hipStream_t s, hipStream_t side) {
-  if (curve == FEC_SECP256K1) run<ESecp>(env, digests, r, s_, pk, pk_inf, gen, status, work, n, s, side);
-  else run<EP256>(env, digests, r, s_, pk, pk_inf, gen, status, work, n, s, side);
 }
 
 }  // namespace fecgpu

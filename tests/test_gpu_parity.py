@@ -340,7 +340,7 @@ def test_fixed_base_prefix_table_is_invisible(oracle, curve, bits):
 @pytest.mark.parametrize("curve", CURVES)
 def test_fixed_base_of_the_callers_own_gets_a_table_per_launch(gpu_ctx, oracle, curve):
     """From 2^16 elements on a fixed base that is not the generator is multiplied from a prefix table built for that one
-    launch (fecgpu.hip: per_call_prefix; 2^14 entries here): projective base with z != 1, every element against the oracle,
+    launch (fecgpu.hip: acquire_with_prefix; 2^14 entries here): projective base with z != 1, every element against the oracle,
     and the same call again with the tables switched off."""
     import forge_ec_amd as F
     n = (1 << 16) + 37

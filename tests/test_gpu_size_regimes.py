@@ -5,12 +5,13 @@ the Ed25519 debug-build flag, ECDSA's folded sums).
 
   n >= 2^16        the Ed25519 table kernel sorts the whole batch by popcount in a work area of the launch stream's
                    scratch (ed_fixed_work_bytes); a fixed base of the caller's own gets a prefix table in that scratch
-                   behind the caller's own bytes (per_call_prefix)
+                   behind the caller's own bytes (acquire_with_prefix)
   n > 2^15         launch_double_mul stops forking the Ed25519 fixed-base product to the second stream
   n > ctx chunk    the host-pointer pipeline and multi_scalar_mul run chunks on two lanes, each with its own scratch
 
-scratch_for hands every request on one stream the same buffer, so a pipeline that holds scratch and then asks for
-more on the same stream overlays its own data; nothing below these sizes can show it.  The batches are ragged
+A stream's scratch is one buffer.  Each launcher lays out all of its regions (its own, the sort area, a per-call prefix
+table) in one WorkArea and holds that scratch until its last enqueue: a second acquisition on the same stream in the
+meantime fails with an error instead of overlaying the holder's data.  Below these sizes an overlay could not show.  The batches are ragged
 (N = 2^16 + 37) and carry the edge inputs of the small tests at both ends -- zero and all-ones scalars, single-bit
 and low-popcount runs, zero weights, identity points, infinity flags -- so that the popcount sort moves elements
 across the whole batch.

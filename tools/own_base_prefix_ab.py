@@ -1,5 +1,5 @@
 """Fixed-base multiplication by a base of the caller's own (random projective point, not the generator) with the tables
-off and on: from 2^16 elements on such a launch builds a prefix table for itself (fecgpu.hip: per_call_prefix); the kernel
+off and on: from 2^16 elements on such a launch builds a prefix table for itself (fecgpu.hip: acquire_with_prefix); the kernel
 time of each of five launches includes that build.
 
     python tools/own_base_prefix_ab.py
