@@ -1102,6 +1102,26 @@ int launch_ecdh(fec_ctx* ctx, int curve, const u64* dsk, const u64* dpk, const u
   return L.done();
 }
 
+// Ecdsa::<C, D>::sign for secp256k1 / P-256 after the hash and the nonce (ecdsa.rs:98-211): R = multiply(G, k) by the
+// curve's fixed-base kernel into the stream's scratch -- from the ctx's prefix table under launch_mul's policy (the
+// host-pointer form may build one, a *_dev call only takes one that exists) -- then k_ecdsa_sign_finish (kernels_ecdsa.hip).
+int launch_ecdsa_sign(fec_ctx* ctx, int curve, const u64* dsk, const unsigned char* dd, const u64* dk, u64* dsig,
+                      unsigned char* dstatus, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  u32* rp;
+  WorkArea area;
+  area.add(rp, n * 96);
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, curve, st, n);
+  if (rc != FEC_OK) return rc;
+  Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_secp_mul + k_ecdsa_sign_finish" : "k_p256_mul_sched + k_ecdsa_sign_finish");
+  const u32* k = reinterpret_cast<const u32*>(dk);
+  fixed_product(ctx, sched_env(ctx), curve, k, reinterpret_cast<const u32*>(ctx->d_gen[curve]), rp, n, nullptr, L.s);
+  ecdsa_sign_finish_launch(curve, rp, reinterpret_cast<const u32*>(dsk), dd, k, reinterpret_cast<u32*>(dsig), dstatus, n, L.s);
+  return L.done();
+}
+
 int launch_field(fec_ctx* ctx, int curve, int op, const u64* da, const u64* db, u64* dout, size_t n,
                  void* stream = nullptr) {
   if (n == 0) return FEC_OK;
@@ -1896,6 +1916,51 @@ int fec_batch_ecdh(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys, 
   return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
     return launch_ecdh(ctx, curve, (const u64*)d[0], (const u64*)d[1], (const unsigned char*)d[2], (unsigned char*)o[0],
                        (unsigned char*)o[1], cnt, nullptr);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_ecdsa_sign_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_digests, const uint64_t* d_k,
+                       uint64_t* d_sig, uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || (n && (!d_sk || !d_digests || !d_k || !d_sig || !d_status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
+  if (!aligned16(d_sk) || !aligned16(d_digests) || !aligned16(d_k) || !aligned16(d_sig)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_ecdsa_sign(ctx, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_ecdsa_sign(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8_t* digests, const uint64_t* k, uint64_t* sig,
+                   uint8_t* status, size_t n) try {
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
+  if (is_multi(ctx)) {
+    if (n && (!sk || !digests || !k || !sig || !status)) return FEC_E_ARG;
+    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
+      return fec_ecdsa_sign(c, curve, sk + lo * 4, digests + lo * 32, k + lo * 4, sig + lo * 8, status + lo, cnt);
+    });
+  }
+  if (!ctx || (n && (!sk || !digests || !k || !sig || !status))) return FEC_E_ARG;
+  if (n == 0) return FEC_OK;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  // Chunked like fec_batch_ecdh.  The private keys (slot 0), the nonces (slot 2) and R = k * G (the stream's scratch)
+  // sit in ctx-owned device memory while the call runs: they are cleared on EVERY way out of it, error returns included.
+  struct Wipe {
+    fec_ctx* c;
+    ~Wipe() {
+      if (c->d_buf[0]) (void)hipMemsetAsync(c->d_buf[0], 0, c->d_cap[0], c->stream);
+      if (c->d_buf[2]) (void)hipMemsetAsync(c->d_buf[2], 0, c->d_cap[2], c->stream);
+      for (auto& e : c->stream_scratch)
+        if (e.stream == c->stream && e.buf) (void)hipMemsetAsync(e.buf, 0, e.cap, c->stream);
+      (void)hipStreamSynchronize(c->stream);
+      (void)hipGetLastError();
+    }
+  } wipe{ctx};
+  const void* const in[4] = {sk, digests, k, nullptr};
+  const size_t in_stride[4] = {32, 32, 32, 0};
+  void* const outs[2] = {sig, status};
+  const size_t out_stride[2] = {64, 1};
+  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
+    return launch_ecdsa_sign(ctx, curve, (const u64*)d[0], (const unsigned char*)d[1], (const u64*)d[2], (u64*)o[0],
+                             (unsigned char*)o[1], cnt, nullptr);
   });
 } FEC_ABI_CATCH_STATUS
 

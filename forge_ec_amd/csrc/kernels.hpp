@@ -75,6 +75,11 @@ void ecdsa_finish_launch(int curve, const u32* r, const EcdsaWork& w, unsigned c
 void ecdsa_batch_finish_launch(int curve, const u32* r_sum, const u32* ar, size_t n, unsigned char* result, u32* detail,
                                hipStream_t s);
 
+// kernels_ecdsa.hip: Ecdsa::<C, D>::sign (ecdsa.rs:98-211) for C = Secp256k1 / P256 after R = multiply(G, k): rp holds R
+// (24 words per element), sig receives r then s (16 words per element), status one byte.
+void ecdsa_sign_finish_launch(int curve, const u32* rp, const u32* sk, const unsigned char* digests, const u32* k, u32* sig,
+                              unsigned char* status, size_t n, hipStream_t s);
+
 // kernels_ecdsa.hip: Curve::validate_point per affine point (secp256k1 / P-256: is_on_curve; Ed25519: the trait default
 // with its two multiplications).  `work` holds validate_work_bytes(curve, n) bytes (0 for the Weierstrass curves).
 size_t validate_work_bytes(int curve, size_t n);

@@ -7,6 +7,8 @@
 //   k_ecdsa_finish<E>  256-274: R = r1 + r2, identity check, to_affine, field_to_bytes -> Scalar::from_bytes,
 //                      comparison with r; writes status 1 valid / 0 invalid / 2 where the reference panics
 //                      (CtOption::unwrap on None at 239 or 271)
+// and Ecdsa::<C, D>::sign (98-211) with the digest and the nonce k given: multiply(G, k) is the fixed-base kernel
+// (fecgpu.hip), k_ecdsa_sign_finish<E> everything after it.
 // One signature per lane in the two small kernels; the multiplications are the measured hot-path kernels.
 #include <hip/hip_runtime.h>
 
@@ -66,6 +68,33 @@ struct ESecp {
   FEC_DEV static lmask to_affine(const pt& p, fe& x, fe& y) { return secp::to_affine(p, x, y); }
   FEC_DEV static fe wmul(const fe& a, const fe& b) { return secp::sc_mul(a, b); }   // impl Mul for Scalar
   FEC_DEV static fe wadd(const fe& a, const fe& b) { return secp::sc_add(a, b); }   // impl Add for Scalar
+  // ---- Ecdsa::sign ----
+  FEC_DEV static bool sc_invalid(const fe& a) { return lane_of(secp::sc_ge_n(a)); }  // Scalar::from_bytes (2270-2297)
+  FEC_DEV static bool sk_bad(const fe& sk) { return lane_of(fe_is_zero(sk) | secp::sc_ge_n(sk)); }  // !sk.ct_lt(&N)
+  FEC_DEV static bool lt_half(const fe& s) { return lane_of(secp::sc_ct_lt(s, secp::SC_HALF_())); }
+  FEC_DEV static fe order_minus(const fe& s) { return secp::sc_sub(secp::N_(), s); }
+  // Z^-1 (field invert, 599-632) and k^-1 (scalar invert, 2162-2195) in one loop: both are 4 x 64 steps of
+  // square-then-multiply, limbs LS -> MS and bits MS -> LS, so the two independent chains interleave step by step.
+  // Zero has no inverse in either: the field result is zero (CtOption none), the scalar one is not used.
+  FEC_DEV static void inv_pair(const fe& z, const fe& k, fe& zi, fe& ki) {
+    const u64 ez[4] = {0xFFFFFFFEFFFFFC2DULL, 0xFFFFFFFFFFFFFFFFULL, 0xFFFFFFFFFFFFFFFFULL, 0xFFFFFFFFFFFFFFFFULL};
+    const u64 ek[4] = {0xBFD25E8CD036413FULL, 0xBAAEDCE6AF48A03BULL, 0xFFFFFFFFFFFFFFFFULL, 0xFFFFFFFFFFFFFFFEULL};
+    fe rz = fe_small(1), rk = fe_small(1);
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll 1
+      for (int j = 63; j >= 0; --j) {
+        rz = secp::sqr(rz);
+        rk = secp::sc_mul(rk, rk);
+        if ((ez[i] >> j) & 1) rz = secp::mul(rz, z);   // exponent bits are uniform
+        if ((ek[i] >> j) & 1) rk = secp::sc_mul(rk, k);
+      }
+    }
+    zi = fe_select(rz, fe_zero(), fe_is_zero(z));
+    ki = rk;
+  }
+  // x of to_affine (1342-1363) from X and Z^-1: X * (Z^-1)^2; zero for the identity
+  FEC_DEV static fe affine_x(const fe& x, const fe& zi, bool ident) { return ident ? fe_zero() : secp::mul(x, secp::sqr(zi)); }
 };
 
 // P-256: scalar field p256.rs:875-1100, 1409-1432 (reduce_wide drops the high half of its second fold);
@@ -102,6 +131,35 @@ struct EP256 {
   FEC_DEV static lmask to_affine(const pt& p, fe& x, fe& y) { return p256::to_affine(p, x, y); }
   FEC_DEV static fe wmul(const fe& a, const fe& b) { return p256::sc_mul32(a, b); }
   FEC_DEV static fe wadd(const fe& a, const fe& b) { return p256::sc_fe(p256::sc_add(p256::sc_of(a), p256::sc_of(b))); }
+  // ---- Ecdsa::sign ----
+  FEC_DEV static bool sc_invalid(const fe& a) { return p256::sc_ge_n(p256::sc_of(a)); }  // Scalar::from_bytes (1041-1055)
+  // is_zero || !ct_lt(&N) with the trait-default ct_lt: top_byte(sk) <= 0xFF always holds, so only zero is rejected
+  FEC_DEV static bool sk_bad(const fe& sk) {
+    return lane_of(fe_is_zero(sk)) || !p256::sc_ct_lt_default(p256::sc_of(sk), p256::sc_of(p256::SC_N_()));
+  }
+  FEC_DEV static bool lt_half(const fe& s) { return p256::sc_ct_lt_default(p256::sc_of(s), p256::sc_of(p256::SC_HALF_())); }
+  FEC_DEV static fe order_minus(const fe& s) { return p256::sc_sub(p256::SC_N_(), s); }
+  // Z^-1 (field invert, 343-393) and k^-1 (scalar invert, 1057-1100) in one loop: both are pow over 4 x 64 exponent
+  // bits LSB first (`if bit { result *= base }; base = base.square()`), so the two chains interleave step by step.
+  FEC_DEV static void inv_pair(const fe& z, const fe& k, fe& zi, fe& ki) {
+    const u64 ez[4] = {0xFFFFFFFFFFFFFFFDULL, 0x00000000FFFFFFFFULL, 0x0000000000000000ULL, 0xFFFFFFFF00000001ULL};
+    const u64 ek[4] = {0xF3B9CAC2FC63254FULL, 0xBCE6FAADA7179E84ULL, 0xFFFFFFFFFFFFFFFFULL, 0xFFFFFFFF00000000ULL};
+    fe rz = fe_small(1), bz = z, rk = fe_small(1), bk = k;
+#pragma unroll 1
+    for (int w = 0; w < 4; ++w) {
+#pragma unroll 1
+      for (int i = 0; i < 64; ++i) {
+        if ((ez[w] >> i) & 1) rz = p256::mul(rz, bz);   // exponent bits are uniform
+        if ((ek[w] >> i) & 1) rk = p256::sc_mul32(rk, bk);
+        bz = p256::sqr(bz);
+        bk = p256::sc_mul32(bk, bk);
+      }
+    }
+    zi = fe_select(rz, fe_zero(), fe_is_zero(z));
+    ki = rk;
+  }
+  // x of to_affine (1835-1857) from X and Z^-1: X * (Z^-1)^2; zero for the identity
+  FEC_DEV static fe affine_x(const fe& x, const fe& zi, bool ident) { return ident ? fe_zero() : p256::mul(x, p256::sqr(zi)); }
 };
 
 template <class E>
@@ -185,6 +243,42 @@ __global__ __launch_bounds__(64) void k_ecdsa_batch_finish(const u32* __restrict
   result[0] = E::compare_x(p, total);
   store8(detail, p.x); store8(detail + 8, p.y); store8(detail + 16, p.z);
   store8(detail + 24, total);
+}
+
+// ---- Ecdsa::<C, D>::sign (ecdsa.rs:98-211) after the hash and the nonce, from R = multiply(G, k) on ----
+// One signature per lane; status 0 Ok, 1 Err(InvalidPrivateKey), 2 Err(InvalidScalar), 3 Err(InvalidSignature), the
+// first Err in the reference's order; sig = r then s (8 words each), (one(), one()) wherever status != 0 (sign,
+// 199-210).  Nothing derived from sk or k but the signature itself is written: k^-1, r * sk, h + r * sk and s before
+// normalize stay in registers.  No `unwrap` on this path can see None: to_affine inverts Z only after the Z == 0
+// identity test, and Div's invert(2) is Some (secp256k1.hpp / p256.hpp: SC_HALF_).
+template <class E>
+__global__ __launch_bounds__(TPB) void k_ecdsa_sign_finish(const u32* __restrict__ rp, const u32* __restrict__ sks,
+                                                           const unsigned char* __restrict__ digests,
+                                                           const u32* __restrict__ ks, u32* __restrict__ sig,
+                                                           unsigned char* __restrict__ status, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const fe sk = load8(sks + i * 8), k = load8(ks + i * 8);
+  const bool bad_sk = E::sk_bad(sk);                                                      // 101-104
+  const fe z = load8(rp + i * 24 + 16);
+  const bool ident = lane_of(fe_is_zero(z));                                              // is_identity
+  fe zi, k_inv;
+  E::inv_pair(z, k, zi, k_inv);                                                           // 111, 157
+  const fe r = E::x_value(E::affine_x(load8(rp + i * 24), zi, ident));                    // 111-121: x.to_bytes()
+  const bool bad_r = E::sc_invalid(r);                                                    // 122-129
+  const bool zero_r = lane_of(fe_is_zero(r));                                             // 131-134
+  const fe d = load8(reinterpret_cast<const u32*>(digests + i * 32));
+  fe h;
+  FEC_UNROLL for (int w = 0; w < 8; ++w) h.w[w] = __builtin_bswap32(d.w[7 - w]);        // big-endian bytes
+  const bool bad_h = E::sc_invalid(h);                                                    // 147-154
+  const bool zero_k = lane_of(fe_is_zero(k));                                             // 157-164: invert is None
+  fe s = E::wmul(k_inv, E::wadd(h, E::wmul(r, sk)));                                      // 166-169
+  const bool zero_s = lane_of(fe_is_zero(s));                                             // 172-177
+  if (!E::lt_half(s)) s = E::order_minus(s);                                              // normalize, 45-71
+  const unsigned char st = bad_sk ? 1 : bad_r ? 2 : zero_r ? 3 : bad_h ? 2 : (zero_k || zero_s) ? 3 : 0;
+  store8(sig + i * 16, st == 0 ? r : fe_small(1));
+  store8(sig + i * 16 + 8, st == 0 ? s : fe_small(1));
+  status[i] = st;
 }
 
 // ---- KeyExchange::derive_shared_secret (secp256k1.rs:1884-1904, p256.rs:2281-2302) ----
@@ -474,6 +568,12 @@ void ecdsa_finish_launch(int curve, const u32* r, const EcdsaWork& w, unsigned c
   if (curve == FEC_SECP256K1)
     hipLaunchKernelGGL((k_ecdsa_finish<ESecp>), g, b, 0, s, (const u32*)w.ta, (const u32*)w.tb, r, (const unsigned char*)w.flags, status, n);
   else hipLaunchKernelGGL((k_ecdsa_finish<EP256>), g, b, 0, s, (const u32*)w.ta, (const u32*)w.tb, r, (const unsigned char*)w.flags, status, n);
+}
+void ecdsa_sign_finish_launch(int curve, const u32* rp, const u32* sk, const unsigned char* digests, const u32* k, u32* sig,
+                              unsigned char* status, size_t n, hipStream_t s) {
+  const dim3 g((unsigned)((n + TPB - 1) / TPB)), b(TPB);
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_ecdsa_sign_finish<ESecp>), g, b, 0, s, rp, sk, digests, k, sig, status, n);
+  else hipLaunchKernelGGL((k_ecdsa_sign_finish<EP256>), g, b, 0, s, rp, sk, digests, k, sig, status, n);
 }
 void ecdsa_batch_finish_launch(int curve, const u32* r_sum, const u32* ar, size_t n, unsigned char* result, u32* detail,
                                hipStream_t s) {

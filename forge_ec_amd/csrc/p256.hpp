@@ -676,6 +676,29 @@ FEC_DEV sc sc_add(const sc& a, const sc& b) {
 // pair with self > other both leaves result clear and breaks the chain for good: the verdict is
 // top_byte(self) <= top_byte(other).  Against n (top byte 0xFF) that is true for every value.
 FEC_DEV bool sc_ct_lt_default(const sc& a, const sc& other) { return (a.l[3] >> 56) <= (other.l[3] >> 56); }
+// ---- the rest of the scalar field for Ecdsa::sign (ecdsa.rs:98-211) ----
+// Sub (1377-1408): where self < rhs (compare, 70-80), `result += n` first -- AddAssign (1466-1470) is Add (1352-1375),
+// whose reduce() takes self + n back down below n unless the sum carried out of 2^256 -- then the limb-wise
+// difference with its borrow dropped.
+FEC_DEV fe sc_sub(const fe& a, const fe& b) {
+  fe t;
+  const bool lt = lane_of(sub256(t, a, b));
+  const fe r = lt ? sc_fe(sc_add(sc_of(a), sc_of(SC_N_()))) : a;
+  fe d;
+  (void)sub256(d, r, b);
+  return d;
+}
+// half = get_order() / Scalar::from(2) in Signature::normalize (ecdsa.rs:54), i.e. Div (1196-1207): N * invert(2)
+// with the Mul above (reduce_wide, the high half of its second fold dropped) on the unreduced N.  invert(2) is Some
+// (2 is not zero), so Div's unwrap never sees None.  Not (n - 1) / 2.  With the trait-default ct_lt, s.ct_lt(&half)
+// is top_byte(s) <= 0x2C: both legs of normalize are reachable.  (tests/test_ecdsa_sign_model.py checks this
+// constant against the CPU oracle's scalar Mul and invert.)
+FEC_DEV fe SC_HALF_() {
+  fe h;
+  h.w[0] = 0xA564981Au; h.w[1] = 0xDCAFC7DEu; h.w[2] = 0x51D79C4Du; h.w[3] = 0x09839D2Eu;
+  h.w[4] = 0xEEAD368Au; h.w[5] = 0xA23E554Cu; h.w[6] = 0x3778D328u; h.w[7] = 0x2C740484u;
+  return h;
+}
 
 }  // namespace p256
 }  // namespace fecgpu

@@ -804,6 +804,25 @@ FEC_DEV fe sc_inv(const fe& a) {
   }
   return result;
 }
+// ---- the rest of the scalar field for Ecdsa::sign (ecdsa.rs:98-211) ----
+// ct_lt, the override (2323-2347): a true limb-by-limb comparison a < b
+FEC_DEV lmask sc_ct_lt(const fe& a, const fe& b) {
+  fe t;
+  return sub256(t, a, b);
+}
+// Sub for Scalar (2380-2408): the 256-bit difference; on a borrow N is added back, its carry out dropped
+FEC_DEV fe sc_sub(const fe& a, const fe& b) {
+  fe t, u;
+  const lmask borrow = sub256(t, a, b);
+  (void)add256(u, t, N_());
+  return fe_select(t, u, borrow);
+}
+// half = get_order() / Scalar::from(2) in Signature::normalize (ecdsa.rs:54), i.e. Div (2552-2564): N * invert(2)
+// with the Mul above on the unreduced N.  invert(2) is Some (2 is not zero), so Div's unwrap never sees None -- but
+// under this Mul the square-and-multiply chain of sc_inv collapses to ZERO for 2, so half = N * 0 = 0: s.ct_lt(&half)
+// is false for every s, and normalize always returns N - s.  (tests/test_ecdsa_sign_model.py checks this constant
+// against the CPU oracle's scalar Mul and invert.)
+FEC_DEV fe SC_HALF_() { return fe_zero(); }
 
 }  // namespace secp
 }  // namespace fecgpu

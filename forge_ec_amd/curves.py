@@ -216,6 +216,22 @@ class Context:
         _check(self._lib.fec_batch_ecdh(self._h, curve, _ptr(kk), _ptr(pk), _ptr(inf), _ptr(out), _ptr(st), n), "fec_batch_ecdh")
         return out, st
 
+    def ecdsa_sign(self, curve, sk, digests, k):
+        """Ecdsa::<C, D>::sign per element (ecdsa.rs:98-211) for secp256k1 / P-256 after the hash and the nonce:
+        sk (n,4), digests (n,32) uint8 (h_bytes), k (n,4) from Rfc6979::<C, D>::generate_k.  Returns (r (n,4),
+        s (n,4), status (n,) uint8): 0 Ok, 1 Err(InvalidPrivateKey), 2 Err(InvalidScalar), 3 Err(InvalidSignature);
+        r = s = one() wherever status != 0.  The reference's signatures, not standard ECDSA; not constant-time --
+        see include/fecgpu.h."""
+        kk, nn = _u64(sk, 4), _u64(k, 4)
+        d = np.ascontiguousarray(np.asarray(digests, dtype=np.uint8)).reshape(-1, 32)
+        n = kk.shape[0]
+        if not (d.shape[0] == nn.shape[0] == n):
+            raise ValueError("inputs differ in length")
+        sig = np.zeros((n, 8), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_ecdsa_sign(self._h, curve, _ptr(kk), _ptr(d), _ptr(nn), _ptr(sig), _ptr(st), n), "fec_ecdsa_sign")
+        return sig[:, :4].copy(), sig[:, 4:].copy(), st
+
     def ecdsa_batch_verify(self, curve, digests, r, s, pk_xy, pk_inf, a):
         """Ecdsa::<C, D>::batch_verify (ecdsa.rs:287-391) for secp256k1 / P-256 with the digests and the weights
         a (n,4) supplied.  Returns (result, detail): result 1 true, 0 false, 2 = the reference panics; detail
@@ -459,6 +475,9 @@ class Context:
     def batch_ecdh_dev(self, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream=None):
         _check(self._lib.fec_batch_ecdh_dev(self._h, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream),
                "fec_batch_ecdh_dev")
+
+    def ecdsa_sign_dev(self, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream=None):
+        _check(self._lib.fec_ecdsa_sign_dev(self._h, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream), "fec_ecdsa_sign_dev")
 
     def eddsa_verify_ed25519_dev(self, d_r_xy, d_r_inf, d_pk_xy, d_pk_inf, d_s, d_k, d_status, n, stream=None):
         _check(self._lib.fec_eddsa_verify_ed25519_dev(self._h, d_r_xy, d_r_inf, d_pk_xy, d_pk_inf, d_s, d_k, d_status, n,

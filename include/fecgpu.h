@@ -32,6 +32,8 @@
  *   fec_batch_validate_point   Curve::validate_point (secp256k1.rs:2722-2726, p256.rs:2187-2191, core lib.rs:905-925)
  *   fec_batch_ecdh        KeyExchange::derive_shared_secret for secp256k1 / P-256 (secp256k1.rs:1884-1904,
  *                         p256.rs:2281-2312)
+ *   fec_ecdsa_sign        Ecdsa::<C, D>::sign for secp256k1 / P-256 after the hash and the RFC 6979 nonce
+ *                         (ecdsa.rs:45-71, 98-211; scalar Sub secp256k1.rs:2380-2408, p256.rs:1377-1408)
  *   fec_ecdsa_batch_verify   Ecdsa::<C, D>::batch_verify for secp256k1 / P-256 (ecdsa.rs:287-391; scalar Add
  *                         secp256k1.rs:2358-2378, p256.rs:1352-1375)
  *   fec_eddsa_verify_ed25519   Eddsa::<Ed25519, D>::verify / Ed25519::verify after the hash and the decoding
@@ -127,7 +129,7 @@ int fec_ctx_create(fec_ctx** out, int device);
  * one GPU).  The element-wise host-pointer entry points -- fec_batch_mul, fec_batch_mul_fixed,
  * fec_batch_double_mul, fec_batch_to_affine, fec_batch_compress, fec_batch_decompress,
  * fec_batch_encode_uncompressed, fec_batch_decode_uncompressed, fec_ecdsa_verify_secp256k1,
- * fec_ecdsa_verify_p256, fec_eddsa_verify_ed25519, fec_schnorr_verify, fec_batch_ecdh, fec_batch_validate_point,
+ * fec_ecdsa_verify_p256, fec_eddsa_verify_ed25519, fec_schnorr_verify, fec_batch_ecdh, fec_ecdsa_sign, fec_batch_validate_point,
  * fec_field_op, fec_point_op (tests/test_gpu_multi_ctx.py runs every one of them sharded) -- then
  * split the batch into n_devices contiguous shards
  * [g*n/N, (g+1)*n/N), run each shard on its device from its own host thread with that device's
@@ -199,6 +201,23 @@ int fec_ecdsa_verify_p256(fec_ctx* ctx, const uint8_t* digests /* n*32 */, const
  * arithmetic the generators of all three curves FAIL this check; that is reproduced. */
 int fec_batch_validate_point(fec_ctx* ctx, fec_curve curve, const uint64_t* xy /* n*8 */, const uint8_t* inf /* n or NULL */,
                              uint8_t* ok /* n */, size_t n);
+/* Ecdsa::<C, D>::sign per element (forge-ec-signature/src/ecdsa.rs:98-211 with normalize 45-71), curve = FEC_SECP256K1
+ * or FEC_P256 (Ed25519 has no Ecdsa instance: FEC_E_UNSUPPORTED), everything after the hash and the nonce: the
+ * caller hashes (digests[i] = the 32 bytes h_bytes holds at 138-145) and draws k[i] with the reference's
+ * Rfc6979::<C, D>::generate_k(sk, msg) (forge-ec-rng/src/rfc6979.rs:40); R = multiply(G, k), r, s and normalize run
+ * on the GPU under the reference's own scalar arithmetic.
+ * status[i]: 0 Ok, 1 Err(InvalidPrivateKey), 2 Err(InvalidScalar), 3 Err(InvalidSignature) -- the first Err in the
+ * reference's order; sig[i] = r limbs then s limbs (8 per element), (1, 1) wherever status != 0, as Ecdsa::sign
+ * returns.  No unwrap on this path can see None, so there is no "the reference panics" status.
+ * (a) These are the REFERENCE's signatures, not standard ECDSA: its scalar Mul, invert, Sub and its normalize with
+ * half = n / 2 through its own Div (secp256k1: half is 0, so s is always replaced by n - s; P-256: the trait-default
+ * ct_lt, a top-byte comparison).  The reference's own sign -> verify test is #[ignore]d (ecdsa.rs:454-467); the
+ * canonical-mode calls (fecgpu_canon.h) are the standard scheme.
+ * (b) NOT constant-time: the P-256 product is a task scheduler whose work depends on the bits of k, as for
+ * fec_batch_ecdh.  SECRETS: the host-pointer form clears its device staging of sk and k and the stream scratch holding
+ * R before returning. */
+int fec_ecdsa_sign(fec_ctx* ctx, fec_curve curve, const uint64_t* sk /* n*4 */, const uint8_t* digests /* n*32 */,
+                   const uint64_t* k /* n*4 */, uint64_t* sig /* n*8 */, uint8_t* status /* n */, size_t n);
 /* KeyExchange::derive_shared_secret per element (forge-ec-curves/src/secp256k1.rs:1884-1904, p256.rs:2281-2302;
  * the pattern of forge-ec-examples/src/ecdh.rs:40-49), curve = FEC_SECP256K1 or FEC_P256 (Ed25519 implements no
  * KeyExchange: FEC_E_UNSUPPORTED).  secrets[i] = the 32 bytes of Ok(x.to_bytes()) of to_affine(multiply(
@@ -330,6 +349,9 @@ int fec_batch_validate_point_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* 
 /* d_secrets 16-byte aligned; the caller owns (and clears) every buffer */
 int fec_batch_ecdh_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_keys, const uint64_t* d_pk_xy,
                        const uint8_t* d_pk_inf, uint8_t* d_secrets, uint8_t* d_status, size_t n, void* stream);
+/* d_sk, d_digests, d_k, d_sig 16-byte aligned; the caller owns (and clears) every buffer */
+int fec_ecdsa_sign_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_digests,
+                       const uint64_t* d_k, uint64_t* d_sig, uint8_t* d_status, size_t n, void* stream);
 int fec_eddsa_verify_ed25519_dev(fec_ctx* ctx, const uint64_t* d_r_xy, const uint8_t* d_r_inf, const uint64_t* d_pk_xy,
                                  const uint8_t* d_pk_inf, const uint64_t* d_s, const uint64_t* d_k, uint8_t* d_status,
                                  size_t n, void* stream);

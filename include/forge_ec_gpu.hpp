@@ -439,6 +439,28 @@ inline Verify batch_verify(GpuContext& ctx, const std::vector<AffinePoint<C>>& p
                                inf.data(), reinterpret_cast<const uint64_t*>(weights.data()), n, &result, nullptr));
   return result == 1 ? Verify::True : (result == 2 ? Verify::ReferencePanics : Verify::False);
 }
+// Ecdsa::<C, D>::sign per element (ecdsa.rs:98-211) after the hash and the nonce: digests[i] = D::digest(msg_i) and
+// nonces[i] = Rfc6979::<C, D>::generate_k(sk_i, msg_i) (forge-ec-rng/src/rfc6979.rs:40), both drawn by the caller.
+// Every Err comes back as Signature{one, one}, as sign (199-210) returns it.  The reference's signatures, not standard
+// ECDSA, and not constant-time: see fec_ecdsa_sign in fecgpu.h.
+template <fec_curve C>
+inline std::vector<Signature<C>> sign(GpuContext& ctx, const std::vector<Scalar<C>>& sks, const std::vector<Digest>& digests,
+                                      const std::vector<Scalar<C>>& nonces) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "Ecdsa is built for secp256k1 and P-256");
+  const size_t n = sks.size();
+  if (digests.size() != n || nonces.size() != n) throw Error(FEC_E_ARG);
+  std::vector<uint64_t> sig(n * 8);
+  std::vector<uint8_t> st(n);
+  check(fec_ecdsa_sign(ctx.raw(), C, reinterpret_cast<const uint64_t*>(sks.data()), reinterpret_cast<const uint8_t*>(digests.data()),
+                       reinterpret_cast<const uint64_t*>(nonces.data()), sig.data(), st.data(), n));
+  std::vector<Signature<C>> out(n);
+  for (size_t i = 0; i < n; ++i)
+    for (int l = 0; l < 4; ++l) {
+      out[i].r.raw[l] = sig[i * 8 + l];
+      out[i].s.raw[l] = sig[i * 8 + 4 + l];
+    }
+  return out;
+}
 }  // namespace ecdsa
 
 namespace key_exchange {

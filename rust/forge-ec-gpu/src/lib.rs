@@ -45,6 +45,8 @@ extern "C" {
     fn fec_batch_validate_point_dev(ctx: *mut FecCtx, curve: c_int, d_xy: *const u64, d_inf: *const u8, d_ok: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_batch_ecdh(ctx: *mut FecCtx, curve: c_int, private_keys: *const u64, pk_xy: *const u64, pk_inf: *const u8, secrets: *mut u8, status: *mut u8, n: usize) -> c_int;
     fn fec_batch_ecdh_dev(ctx: *mut FecCtx, curve: c_int, d_private_keys: *const u64, d_pk_xy: *const u64, d_pk_inf: *const u8, d_secrets: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_ecdsa_sign(ctx: *mut FecCtx, curve: c_int, sk: *const u64, digests: *const u8, k: *const u64, sig: *mut u64, status: *mut u8, n: usize) -> c_int;
+    fn fec_ecdsa_sign_dev(ctx: *mut FecCtx, curve: c_int, d_sk: *const u64, d_digests: *const u8, d_k: *const u64, d_sig: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_ecdsa_batch_verify(ctx: *mut FecCtx, curve: c_int, digests: *const u8, r: *const u64, s: *const u64, pk_xy: *const u64, pk_inf: *const u8, a: *const u64, n: usize, result: *mut u8, detail: *mut u64) -> c_int;
     fn fec_eddsa_verify_ed25519(ctx: *mut FecCtx, r_xy: *const u64, r_inf: *const u8, pk_xy: *const u64, pk_inf: *const u8, s: *const u64, k: *const u64, status: *mut u8, n: usize) -> c_int;
     fn fec_ecdsa_verify_p256(ctx: *mut FecCtx, digests: *const u8, r: *const u64, s: *const u64, pk_xy: *const u64, pk_inf: *const u8, status: *mut u8, n: usize) -> c_int;
@@ -261,6 +263,8 @@ pub trait GpuCurve: Curve {
     const LIMBS: usize;
     /// `Scalar::to_raw()`.
     fn scalar_limbs(s: &Self::Scalar) -> [u64; 4];
+    /// `Scalar::from_raw(l)`.
+    fn scalar_from_limbs(l: [u64; 4]) -> Self::Scalar;
     /// Writes the point's raw coordinates into `out[..LIMBS]`.
     fn point_limbs(p: &Self::PointProjective, out: &mut [u64]);
     /// Rebuilds a point from `LIMBS` raw limbs (no validation, like `multiply`'s own return value).
@@ -282,6 +286,9 @@ macro_rules! impl_weierstrass {
             const LIMBS: usize = 12;
             fn scalar_limbs(s: &$m::Scalar) -> [u64; 4] {
                 s.to_raw()
+            }
+            fn scalar_from_limbs(l: [u64; 4]) -> $m::Scalar {
+                $m::Scalar::from_raw(l)
             }
             fn point_limbs(p: &$m::ProjectivePoint, out: &mut [u64]) {
                 for (i, c) in p.to_raw_coords().iter().enumerate() {
@@ -312,6 +319,9 @@ impl GpuCurve for ed25519::Ed25519 {
     const LIMBS: usize = 16;
     fn scalar_limbs(s: &ed25519::Scalar) -> [u64; 4] {
         s.to_raw()
+    }
+    fn scalar_from_limbs(l: [u64; 4]) -> ed25519::Scalar {
+        ed25519::Scalar::from_raw(l)
     }
     fn point_limbs(p: &ed25519::ExtendedPoint, out: &mut [u64]) {
         for (i, c) in p.to_raw_coords().iter().enumerate() {
@@ -555,6 +565,47 @@ pub fn batch_derive_shared_secret<C: GpuCurve>(ctx: &mut GpuContext, private_key
     }).collect())
 }
 
+/// `Ecdsa::<C, D>::sign(sks[i], msgs[i])` per element (`forge-ec-signature/src/ecdsa.rs:98-211`) for `C` = secp256k1 or
+/// P-256: the hash (`D::digest`) and the nonce (`Rfc6979::<C, D>::generate_k`, `forge-ec-rng/src/rfc6979.rs:40`) on the
+/// host, R = k * G, r, s and `normalize` on the GPU under the reference's own scalar arithmetic.  Every `Err` of
+/// `sign_internal` comes back as `Signature::new(one, one)`, as `sign` returns it (the key check of 101-104 runs
+/// before the nonce there, so no nonce is drawn for a rejected key).  The reference's signatures, not standard ECDSA,
+/// and not constant-time: see `fec_ecdsa_sign` in include/fecgpu.h.
+#[cfg(feature = "signature")]
+pub fn ecdsa_sign_batch<C, D>(ctx: &mut GpuContext, sks: &[C::Scalar], msgs: &[&[u8]]) -> Result<Vec<forge_ec_signature::ecdsa::Signature<C>>>
+where
+    C: GpuCurve,
+    D: digest::Digest + Clone + digest::core_api::BlockSizeUser,
+{
+    use forge_ec_core::{FieldElement, Scalar};
+    let n = sks.len();
+    if msgs.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let order = <C::Scalar as Scalar>::get_order();
+    let (mut kk, mut nonces, mut digests) = (vec![0u64; 4 * n], vec![0u64; 4 * n], vec![0u8; 32 * n]);
+    for i in 0..n {
+        kk[4 * i..4 * i + 4].copy_from_slice(&C::scalar_limbs(&sks[i]));
+        let h = D::digest(msgs[i]);   // h_bytes (138-145): the first 32 bytes, zero-padded
+        let m = h.len().min(32);
+        digests[32 * i..32 * i + m].copy_from_slice(&h[..m]);
+        if !bool::from(sks[i].is_zero()) && bool::from(sks[i].ct_lt(&order)) {
+            let k = forge_ec_rng::Rfc6979::<C, D>::generate_k(&sks[i], msgs[i]);
+            nonces[4 * i..4 * i + 4].copy_from_slice(&C::scalar_limbs(&k));
+        }
+    }
+    let (mut sig, mut status) = (vec![0u64; 8 * n], vec![0u8; n]);
+    // SAFETY: every buffer holds n elements of the width the header states.
+    let rc = check(unsafe { fec_ecdsa_sign(ctx.raw, C::ID, kk.as_ptr(), digests.as_ptr(), nonces.as_ptr(), sig.as_mut_ptr(), status.as_mut_ptr(), n) });
+    kk.iter_mut().chain(nonces.iter_mut()).for_each(|w| *w = 0);
+    rc?;
+    let one = <C::Scalar as FieldElement>::one();
+    Ok((0..n).map(|i| match status[i] {
+        0 => forge_ec_signature::ecdsa::Signature::new(C::scalar_from_limbs(limb4(&sig, 2 * i)), C::scalar_from_limbs(limb4(&sig, 2 * i + 1))),
+        _ => forge_ec_signature::ecdsa::Signature::new(one, one),
+    }).collect())
+}
+
 /// `Ecdsa::<C, D>::batch_verify` (`forge-ec-signature/src/ecdsa.rs:287-391`) for `C` = secp256k1 or P-256 from
 /// line 310 on: the caller hashes (`digests[i] = D::digest(msgs[i])`) and draws the weights `a` (302-306) with
 /// the reference's own `Scalar::random`.
@@ -765,6 +816,14 @@ pub mod dev {
     /// As [`batch_mul`]; the caller owns and clears every buffer.
     pub unsafe fn batch_ecdh(ctx: &mut GpuContext, curve: c_int, d_private_keys: *const u64, d_pk_xy: *const u64, d_pk_inf: *const u8, d_secrets: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
         check(fec_batch_ecdh_dev(ctx.raw, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream))
+    }
+
+    /// `fec_ecdsa_sign_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn ecdsa_sign(ctx: &mut GpuContext, curve: c_int, d_sk: *const u64, d_digests: *const u8, d_k: *const u64, d_sig: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_ecdsa_sign_dev(ctx.raw, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream))
     }
 
     /// `fec_schnorr_verify_dev`.
