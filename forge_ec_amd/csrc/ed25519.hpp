@@ -28,11 +28,15 @@ FEC_DEV fe reduce(const fe& a) {
   const u32 top = a.w[7] >> 31;
   v.w[7] &= 0x7FFFFFFFu;
   const lmask cy = add_short1(v, top * 19u);          // leaves word 0 with probability 19 / 2^32
-  if (__builtin_expect(cy != 0, 0)) carry_from<1>(v, cy);
+  if (__builtin_expect(cy != 0, 0)) {
+    FEC_RARE(ED_REDUCE_CARRY);
+    carry_from<1>(v, cy);
+  }
   // v < 2^255 + 19.  v >= p = 2^255 - 19 needs either bit 255 set again or words 1..6 all ones with
   // w7 == 0x7FFFFFFF, either way a top word >= 0x7FFFFFFF: ~2^-31 per lane, so the exact comparison sits behind a
   // wave-uniform branch.
   if (__builtin_expect(lanes_where(v.w[7] >= 0x7FFFFFFFu) != 0, 0)) {
+    FEC_RARE(ED_REDUCE_TOP);
     fe u;
     lmask t;
     FEC_ADDK256(u, v, t, 19, 0, 0, 0, 0, 0, 0, 0);  // u = v + 19 < 2^256
@@ -50,6 +54,7 @@ FEC_DEV fe add(const fe& a, const fe& b) {
   fe s;
   const lmask carry = add256(s, a, b);
   if (__builtin_expect(carry != 0, 0)) {
+    FEC_RARE(ED_ADD_CARRY);
     fe s2;
     add_word256(s2, s, word_select(0u, 19u, carry));
     s = s2;
@@ -74,7 +79,10 @@ FEC_DEV fe sub(const fe& a, const fe& b) {
       "s_mov_b64 %2, vcc"                      // last: %2 may share its registers with %4
       : "+v"(d.w[0]), "+v"(d.w[7]), "=s"(bw), "=&v"(t) : "s"(borrow) : "vcc");
 #endif
-  if (__builtin_expect(bw != 0, 0)) borrow_from<1>(d, bw);  // commutes with the toggle (both are additions mod 2^32 on word 7)
+  if (__builtin_expect(bw != 0, 0)) {
+    FEC_RARE(ED_SUB_BORROW);
+    borrow_from<1>(d, bw);
+  }  // commutes with the toggle (both are additions mod 2^32 on word 7)
   return d;
 }
 
@@ -118,7 +126,34 @@ FEC_DEV fe sqr_cxx(const fe& a) {
   return reduce_wide(t);
 }
 #ifdef FEC_HOST_EMUL
-FEC_DEV fe mul(const fe& a, const fe& b) { return mul_cxx(a, b); }
+// the exc mask of the asm Mul / self*self (tools/gen_field_asm.py ed_reduce) on the same 512-bit product: carry*19, or
+// the 19 for bit 255, carries out of word 0, or the top word ends at 0x7FFFFFFF
+FEC_DEV bool ed_exc(const u32 t[16]) {
+  u32 lo[8], hi[8], r[8];
+  for (int i = 0; i < 8; ++i) {
+    const u64 d = (u64)t[8 + i] * 38u + t[i];
+    lo[i] = (u32)d;
+    hi[i] = (u32)(d >> 32);
+  }
+  u64 c = 0;
+  for (int i = 1; i < 8; ++i) {
+    c = (u64)lo[i] + hi[i - 1] + (c >> 32);
+    r[i] = (u32)c;
+  }
+  const u32 cw = (u32)(hi[7] + (c >> 32)) * 19u;
+  u64 s = (u64)lo[0] + cw;
+  bool exc = (s >> 32) != 0;
+  s = (u64)(u32)s + (r[7] >> 31) * 19u;
+  exc |= (s >> 32) != 0;
+  return exc || (r[7] & 0x7FFFFFFFu) == 0x7FFFFFFFu;
+}
+FEC_DEV fe mul(const fe& a, const fe& b) {
+  u32 t[16];
+  mul_wide(t, a, b);
+  FEC_RARE_IF(ed_exc(t), ED_MUL_EXC);
+  return reduce_wide(t);
+}
+// (the host build never calls sqr_exact: its double() is add(self, self), whose Mul forms the same exact products)
 FEC_DEV fe sqr_exact(const fe& a) { return sqr_cxx(a); }
 #else
 // Mul / self*self as ONE hand-allocated asm statement each (tools/gen_field_asm.py), for the path on
@@ -194,10 +229,19 @@ FEC_DEV pt padd(const pt& p, const pt& q) {
   lmask opposite = fe_eq(p.x, neg(q.x)) & fe_eq(p.y, q.y);  // 1878, raw coordinates
   lmask idp = is_identity(p), idq = is_identity(q);
   if (__builtin_expect((opposite | idp | idq) != 0, 0)) {
+    FEC_RARE(ED_PADD_EARLY);
+    FEC_RARE_IF(opposite, ED_PADD_OPPOSITE);
     o = pt_select(o, identity(), opposite);
     o = pt_select(o, p, idq);
     o = pt_select(o, q, idp);
   }
+#ifdef FEC_HOST_EMUL
+  // a doubling (double() is add(self, self)): pdbl / pdbl_mem's one-word test and their x == -x leg
+  if (fe_eq(p.x, q.x) && fe_eq(p.y, q.y) && fe_eq(p.z, q.z) && fe_eq(p.t, q.t)) {
+    FEC_RARE_IF(p.x.w[0] == 0u || p.x.w[0] == 0xFFFFFFEDu - p.x.w[0], ED_PDBL_MAYBE);
+    FEC_RARE_IF(opposite, ED_PDBL_OPPOSITE);
+  }
+#endif
   return o;
 }
 
@@ -280,6 +324,7 @@ FEC_DEV pt pdbl(const pt& p) {
   lmask opposite = fe_eq(p.x, neg(p.x));
   lmask idp = is_identity(p);
   if (__builtin_expect((opposite | idp) != 0, 0)) {
+    FEC_RARE_IF(opposite, ED_PDBL_OPPOSITE);
     o = pt_select(o, identity(), opposite);
     o = pt_select(o, p, idp);
   }

@@ -34,6 +34,33 @@
 #define FEC_DEV_NOINLINE __device__ __attribute__((noinline))
 #endif
 
+// Reach counters of the rare legs (tests/rare_legs.json is their census), host emulation only: FEC_RARE(LEG) sits
+// inside a leg's branch, FEC_RARE_IF(cond, LEG) evaluates the condition of a leg whose device form is asm (or lives in
+// a kernel file) on the host form's own intermediate values.  Both expand to nothing in the device build.
+#ifdef FEC_HOST_EMUL
+#define FEC_RARE_LEGS(X)                                                                                          \
+  X(SECP_CSUB_P) X(SECP_ADD_TOP) X(SECP_ADD_CARRY) X(SECP_DBL_TOP) X(SECP_DBL_CARRY) X(SECP_SUB_BORROW)           \
+  X(SECP_PRODUCT_TOP) X(SECP_MUL_BW) X(SECP_MULK_EXC) X(SECP_MULK_BW) X(SECP_SQR_RIPPLE)                          \
+  X(SECP_SQR_FOLD_GENERAL) X(SECP_SQR_FOLD_RIPPLE) X(SECP_SQR_EXC) X(SECP_PDOUBLE_ID) X(SECP_PADD_EARLY)          \
+  X(SECP_PADD_UEQ) X(SECP_PADD_ND)                                                                                \
+  X(P256_ADD_GENERAL) X(P256_SUB_TOP) X(P256_SUB_GE) X(P256_PRODUCT_TOP) X(P256_MULK_EXC)                         \
+  X(P256_PDBL_ZLOW) X(P256_PADD_EARLY) X(P256_PADD_UEQ) X(P256_PADD_NONCANON)                                     \
+  X(ED_REDUCE_CARRY) X(ED_REDUCE_TOP) X(ED_ADD_CARRY) X(ED_SUB_BORROW) X(ED_MUL_EXC)                              \
+  X(ED_PADD_EARLY) X(ED_PADD_OPPOSITE) X(ED_PDBL_MAYBE) X(ED_PDBL_OPPOSITE)
+#define FEC_RARE_ENUM(L) FEC_RL_##L,
+#define FEC_RARE_NAME(L) #L,
+namespace fecgpu {
+enum { FEC_RARE_LEGS(FEC_RARE_ENUM) FEC_RARE_N };
+static thread_local unsigned long fec_host_rare[FEC_RARE_N];  // per thread: searches count on many
+static const char* const fec_host_rare_names[FEC_RARE_N] = {FEC_RARE_LEGS(FEC_RARE_NAME)};
+}  // namespace fecgpu
+#define FEC_RARE(L) (++::fecgpu::fec_host_rare[::fecgpu::FEC_RL_##L])
+#define FEC_RARE_IF(c, L) ((c) ? (void)FEC_RARE(L) : (void)0)
+#else
+#define FEC_RARE(L) ((void)0)
+#define FEC_RARE_IF(c, L) ((void)0)
+#endif
+
 namespace fecgpu {
 
 typedef uint32_t u32;

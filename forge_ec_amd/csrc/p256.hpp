@@ -94,8 +94,10 @@ FEC_DEV fe add(const fe& a, const fe& b) {
   const lmask noncanon = lanes_where(a.w[7] == 0xFFFFFFFFu || b.w[7] == 0xFFFFFFFFu);
   fe s;
   const lmask carry = add256(s, a, b);
-  if (__builtin_expect((noncanon | lanes_where(s.w[7] == 0xFFFFFFFFu)) != 0, 0)) add_tail_general(s, carry);
-  else add_red_masked(s, carry);
+  if (__builtin_expect((noncanon | lanes_where(s.w[7] == 0xFFFFFFFFu)) != 0, 0)) {
+    FEC_RARE(P256_ADD_GENERAL);
+    add_tail_general(s, carry);
+  } else add_red_masked(s, carry);
   return s;
 }
 // a + a through Add (the doublings of the point formulas), with one operand list (dbl256)
@@ -117,6 +119,7 @@ FEC_DEV fe dbl(const fe& a) {
 FEC_DEV fe sub(const fe& a, const fe& b) {
   lmask ge = 0;
   if (__builtin_expect(lanes_where(a.w[7] == 0xFFFFFFFFu) != 0, 0)) {
+    FEC_RARE(P256_SUB_TOP);
     fe t;
     lmask bo;
     FEC_SUBK256(t, a, bo, FEC_P256_P);
@@ -124,7 +127,10 @@ FEC_DEV fe sub(const fe& a, const fe& b) {
   }
   fe d;
   const lmask borrow = sub256(d, a, b);
-  if (__builtin_expect((ge & borrow) != 0, 0)) add_red_masked(d, uniform_mask(ge & borrow));
+  if (__builtin_expect((ge & borrow) != 0, 0)) {
+    FEC_RARE(P256_SUB_GE);
+    add_red_masked(d, uniform_mask(ge & borrow));
+  }
   return d;
 }
 
@@ -171,6 +177,7 @@ FEC_DEV fe reduce_wide(const u32 c[16]) {
     acc[i + 1] += cy;
   }
   r.w[7] = (u32)acc[7];
+  FEC_RARE_IF(r.w[7] == 0xFFFFFFFFu, P256_PRODUCT_TOP);  // csub_p_top's test on the device
   return csub_p(r);  // reduce() (701)
 }
 
@@ -249,7 +256,17 @@ FEC_DEV fe sqr(const fe& a) {
 }
 #endif
 #ifdef FEC_HOST_EMUL
-FEC_DEV fe mul_small(const fe& a, u32 k) { return mul_small_cxx(a, k); }
+// mul_small_k's exc leg on the same nine-word product: S = T_lo + c8*(2^256 - p) carries out of 2^256
+FEC_DEV fe mul_small(const fe& a, u32 k) {
+  u32 t[16];
+  mul_wide_small(t, a, k);
+  const u32 top = t[8], v3 = 0u - top, c3 = (u32)((int32_t)v3 >> 31), v6 = c3 - top, v7 = top + (u32)((int32_t)v6 >> 31);
+  const u32 adds[8] = {top, 0, 0, v3, c3, c3, v6, v7};
+  u64 c = 0;
+  for (int i = 0; i < 8; ++i) c = ((u64)t[i] + adds[i] + (c >> 32));
+  FEC_RARE_IF((k == 3 || k == 8) && (c >> 32) != 0, P256_MULK_EXC);
+  return reduce_wide(t);
+}
 #else
 FEC_DEV fe mul_small(const fe& a, u32 k) { return k == 3 ? mul_small_k<3>(a) : (k == 8 ? mul_small_k<8>(a) : mul_small_cxx(a, k)); }
 #endif
@@ -290,6 +307,8 @@ FEC_DEV pt pdouble(const pt& p) {
   r.y = sub(mul(e, sub(d, r.x)), mul_small(yyyy, 8));
   fe z3 = add(p.y, p.y);
   r.z = fe_select(mul(z3, p.z), z3, fe_eq(p.z, fe_small(1)));
+  // pdouble_in_place's one-word test z.w[0] <= 1, on a z that is neither 0 nor 1
+  FEC_RARE_IF(p.z.w[0] <= 1u && !fe_is_zero(p.z) && !fe_eq(p.z, fe_small(1)), P256_PDBL_ZLOW);
   return pt_select(r, identity(), is_identity(p));
 }
 
@@ -322,6 +341,10 @@ FEC_DEV pt padd_nodouble(const pt& p, const pt& q, lmask& need_double) {
   o = pt_select(o, p, idq);
   o = pt_select(o, q, idp);
   need_double = same & ~idp & ~idq;
+  FEC_RARE_IF(idp | idq | ueq, P256_PADD_EARLY);
+  FEC_RARE_IF(ueq & ~idp & ~idq, P256_PADD_UEQ);
+  // padd_in_place's general form for an affine addend: the running point has an all-ones top word in x or y
+  FEC_RARE_IF(fe_eq(q.z, fe_small(1)) && (p.x.w[7] == 0xFFFFFFFFu || p.y.w[7] == 0xFFFFFFFFu), P256_PADD_NONCANON);
   return o;
 }
 

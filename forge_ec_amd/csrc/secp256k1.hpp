@@ -39,7 +39,10 @@ FEC_DEV lmask maybe_ge_p(const fe& v) {
 // the same reduce where v >= p is improbable (2^-224 for a Mul/square result): the chain and the
 // select sit behind a wave-uniform branch
 FEC_DEV fe csub_p_unlikely(const fe& v) {
-  if (__builtin_expect(maybe_ge_p(v) != 0, 0)) return csub_p(v);
+  if (__builtin_expect(maybe_ge_p(v) != 0, 0)) {
+    FEC_RARE(SECP_CSUB_P);
+    return csub_p(v);
+  }
   return v;
 }
 
@@ -50,6 +53,7 @@ FEC_DEV fe add(const fe& a, const fe& b) {
   fe s;
   const lmask carry = add256(s, a, b);
   if (__builtin_expect(lanes_where(s.w[7] == 0xFFFFFFFFu) != 0, 0)) {
+    FEC_RARE(SECP_ADD_TOP);
     fe w;
     lmask ov;
     FEC_ADDK256(w, s, ov, FEC_SECP_C);  // w = s - p mod 2^256
@@ -57,7 +61,10 @@ FEC_DEV fe add(const fe& a, const fe& b) {
   }
   lmask cy;
   FEC_ADD_SHORT2(s, carry, cy, 0x3d1);
-  if (__builtin_expect(cy != 0, 0)) carry_from<2>(s, cy);
+  if (__builtin_expect(cy != 0, 0)) {
+    FEC_RARE(SECP_ADD_CARRY);
+    carry_from<2>(s, cy);
+  }
   return s;
 }
 
@@ -66,6 +73,7 @@ FEC_DEV fe dbl(const fe& a) {
   fe s;
   const lmask carry = dbl256(s, a);
   if (__builtin_expect(lanes_where(s.w[7] == 0xFFFFFFFFu) != 0, 0)) {
+    FEC_RARE(SECP_DBL_TOP);
     fe w;
     lmask ov;
     FEC_ADDK256(w, s, ov, FEC_SECP_C);  // w = s - p mod 2^256
@@ -73,7 +81,10 @@ FEC_DEV fe dbl(const fe& a) {
   }
   lmask cy;
   FEC_ADD_SHORT2(s, carry, cy, 0x3d1);
-  if (__builtin_expect(cy != 0, 0)) carry_from<2>(s, cy);
+  if (__builtin_expect(cy != 0, 0)) {
+    FEC_RARE(SECP_DBL_CARRY);
+    carry_from<2>(s, cy);
+  }
   return s;
 }
 
@@ -83,7 +94,10 @@ FEC_DEV fe sub(const fe& a, const fe& b) {
   const lmask borrow = sub256(d, a, b);
   lmask bw;
   FEC_SUB_SHORT2(d, borrow, bw, 0x3d1);
-  if (__builtin_expect(bw != 0, 0)) borrow_from<2>(d, bw);
+  if (__builtin_expect(bw != 0, 0)) {
+    FEC_RARE(SECP_SUB_BORROW);
+    borrow_from<2>(d, bw);
+  }
   return d;
 }
 
@@ -117,6 +131,7 @@ FEC_DEV fe mont_reduce(const u32 t[16]) {
   }
   add256(v, th, mm);
   sub_lohi256(v2, v, e_lo, e_hi);
+  FEC_RARE_IF(v2.w[7] == 0xFFFFFFFFu, SECP_PRODUCT_TOP);  // csub_p_top's test on the device
   return csub_p_unlikely(v2);
 }
 
@@ -136,7 +151,30 @@ FEC_DEV fe mul_cxx(const fe& a, const fe& b) {
 }
 
 #ifdef FEC_HOST_EMUL
-FEC_DEV fe mul(const fe& a, const fe& b) { return mul_cxx(a, b); }
+// The legs of the asm Mul / mul_small_k, on mont_reduce's values: V = T_hi + M - Q borrows out of word 1 when the low
+// 64 bits of T_hi + M are below Q; mul_small_k's m0 + t8 carries out of word 0 (exc), and then recomputes instead.
+FEC_DEV void mont_probe(const u32 t[16], u32& m0, u64& vlo, u64& q) {
+  u32 m[2] = {0, 0}, e_lo = 0, e_hi = 0;
+  for (int k = 0; k < 8; ++k) {
+    u32 mk = (t[k] - e_lo) * 0xD2253531u;
+    if (k < 2) m[k] = mk;
+    u64 d = (u64)mk * 977u + (((u64)e_hi << 32) | e_lo);
+    u64 e = (d >> 32) + mk;
+    e_lo = (u32)e;
+    e_hi = (u32)(e >> 32);
+  }
+  m0 = m[0];
+  vlo = ((((u64)t[9] << 32) | t[8]) + (((u64)m[1] << 32) | m[0]));
+  q = ((u64)e_hi << 32) | e_lo;
+}
+FEC_DEV fe mul(const fe& a, const fe& b) {
+  u32 t[16], m0;
+  u64 vlo, q;
+  mul_wide(t, a, b);
+  mont_probe(t, m0, vlo, q);
+  FEC_RARE_IF(vlo < q, SECP_MUL_BW);
+  return mont_reduce(t);
+}
 #else
 // v -= 2^64 on the lanes of bw: the borrow out of word 1 continued through words 2..7
 FEC_DEV fe borrow_from_word2(const fe& v, lmask bw) {
@@ -201,7 +239,16 @@ FEC_DEV fe mul_small_k(const fe& a) {
 }
 #endif
 #ifdef FEC_HOST_EMUL
-FEC_DEV fe mul_small(const fe& a, u32 k) { return mul_small_cxx(a, k); }
+FEC_DEV fe mul_small(const fe& a, u32 k) {
+  u32 t[16], m0;
+  u64 vlo, q;
+  mul_wide_small(t, a, k);
+  mont_probe(t, m0, vlo, q);
+  const bool exc = (u64)m0 + t[8] > 0xFFFFFFFFu;
+  FEC_RARE_IF(exc, SECP_MULK_EXC);
+  FEC_RARE_IF(!exc && vlo < q, SECP_MULK_BW);
+  return mont_reduce(t);
+}
 #else
 FEC_DEV fe mul_small(const fe& a, u32 k) { return k == 3 ? mul_small_k<3>(a) : (k == 8 ? mul_small_k<8>(a) : mul_small_cxx(a, k)); }
 #endif
@@ -221,7 +268,7 @@ FEC_DEV fe mul_small(const fe& a, u32 k) { return k == 3 ? mul_small_k<3>(a) : (
 // that fold step runs the reference's general rule.  Every branch is exact; none is taken on
 // random data (tests/golden/secp256k1_sqr_ripple_operands.json forces them).
 #ifdef FEC_HOST_EMUL
-static unsigned long fec_host_rare_sqr = 0;  // coverage counter for tests (host emulation only)
+static thread_local unsigned long fec_host_rare_sqr = 0;  // coverage counter for tests (host emulation only)
 FEC_DEV lmask cross_add(u32& w0, u32& w1, u32& w2, u32& w3, u32& w4, u32& w5, u32 x0, u32 x1, u32 x2, u32 x3) {
   u64 lo = ((u64)w1 << 32) | w0, hi = ((u64)w3 << 32) | w2, nx = ((u64)w5 << 32) | w4;
   u64 xl = ((u64)x1 << 32) | x0, xh = ((u64)x3 << 32) | x2;
@@ -325,6 +372,7 @@ FEC_DEV fe sqr_cxx(const fe& a) {
         if (__builtin_expect(more != 0, 0)) {
 #ifdef FEC_HOST_EMUL
           ++fec_host_rare_sqr;
+          FEC_RARE(SECP_SQR_RIPPLE);
 #endif
           FEC_UNROLL for (int k = B + 6; k < 16; k += 2) more = ripple2(w[k], w[k + 1], more);
         }
@@ -346,6 +394,7 @@ FEC_DEV fe sqr_cxx(const fe& a) {
       if (__builtin_expect(more != 0, 0)) {
 #ifdef FEC_HOST_EMUL
         ++fec_host_rare_sqr;
+        FEC_RARE(SECP_SQR_FOLD_RIPPLE);
 #endif
         more = ripple2(r[4], r[5], more);
         carry = ripple2(r[6], r[7], more);
@@ -353,17 +402,25 @@ FEC_DEV fe sqr_cxx(const fe& a) {
     } else {
 #ifdef FEC_HOST_EMUL
       ++fec_host_rare_sqr;
+      FEC_RARE(SECP_SQR_FOLD_GENERAL);
 #endif
       carry = fold_general(r, m0, m1, carry);
     }
   }
   fe o;
   FEC_UNROLL for (int i = 0; i < 8; ++i) o.w[i] = r[i];
+  FEC_RARE_IF(o.w[7] == 0xFFFFFFFFu, SECP_PRODUCT_TOP);
   return csub_p_unlikely(o);
 }
 
 #ifdef FEC_HOST_EMUL
-FEC_DEV fe sqr(const fe& a) { return sqr_cxx(a); }
+// the asm square's exc mask covers every lane on which one of sqr_cxx's cold blocks runs
+FEC_DEV fe sqr(const fe& a) {
+  const unsigned long before = fec_host_rare_sqr;
+  const fe r = sqr_cxx(a);
+  FEC_RARE_IF(fec_host_rare_sqr != before, SECP_SQR_EXC);
+  return r;
+}
 #else
 // square() as ONE hand-allocated asm statement (tools/gen_field_asm.py) for the path on which no +1
 // ripples past the limb it is added to (each continuation needs a 64-bit limb of all ones).  The
@@ -419,7 +476,10 @@ FEC_DEV pt pdouble(const pt& p) {
   fe yz = mul(p.y, p.z);
   r.z = dbl(yz);
   lmask idp = is_identity(p);
-  if (__builtin_expect(idp != 0, 0)) r = pt_select(r, identity(), idp);
+  if (__builtin_expect(idp != 0, 0)) {
+    FEC_RARE(SECP_PDOUBLE_ID);
+    r = pt_select(r, identity(), idp);
+  }
   return r;
 }
 
@@ -448,11 +508,14 @@ FEC_DEV pt padd_nodouble(const pt& p, const pt& q, lmask& need_double) {
   lmask ueq = fe_eq(u1, u2);
   need_double = 0;
   if (__builtin_expect((idp | idq | ueq) != 0, 0)) {  // early-outs: only the ladder's first steps
+    FEC_RARE(SECP_PADD_EARLY);
     lmask seq = fe_eq(s1, s2);
     o = pt_select(o, identity(), ueq & ~seq);
     o = pt_select(o, p, idq);
     o = pt_select(o, q, idp);
     need_double = ueq & seq & ~idp & ~idq;
+    FEC_RARE_IF(ueq & ~idp & ~idq, SECP_PADD_UEQ);  // padd_slots' ueq leg: u1 == u2 on two finite points
+    FEC_RARE_IF(need_double, SECP_PADD_ND);
   }
   return o;
 }

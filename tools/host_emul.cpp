@@ -6,12 +6,60 @@
 #include "../forge_ec_amd/csrc/p256.hpp"
 #include "../forge_ec_amd/csrc/ed25519.hpp"
 #include <string.h>
+#include <atomic>
+#include <mutex>
+#include <thread>
+#include <vector>
 using namespace fecgpu;
 
 static fe ld(const uint64_t* a) { fe r; for (int i = 0; i < 4; ++i) { r.w[2*i] = (u32)a[i]; r.w[2*i+1] = (u32)(a[i] >> 32); } return r; }
 static void st(uint64_t* o, const fe& a) { for (int i = 0; i < 4; ++i) o[i] = (u64)a.w[2*i] | ((u64)a.w[2*i+1] << 32); }
 
 extern "C" unsigned long he_rare_sqr_count() { return secp::fec_host_rare_sqr; }
+// the reach counters of the rare legs (limbs.hpp FEC_RARE_LEGS): their number, names and current values
+extern "C" int he_rare_leg_count() { return FEC_RARE_N; }
+extern "C" const char* he_rare_leg_name(int i) { return i >= 0 && i < FEC_RARE_N ? fec_host_rare_names[i] : nullptr; }
+extern "C" void he_rare_legs(unsigned long* out) { memcpy(out, fec_host_rare, sizeof(fec_host_rare)); }
+
+// Bounded search for operands of mul_small_k's rare legs as a multiplication's first doubling meets them:
+// which 0: mul_small(sqr(v), 3) (the doubling of a point with x = v), 1: mul_small(sqr(sqr(v)), 8) (y = v).  Candidates
+// are splitmix64 words from `seed` below p; a hit is a candidate on which the leg's reach counter moves.  Returns the
+// number of hits (the one of lowest candidate index is written to `hit`); `count` candidates are spread over `threads` threads.
+static uint64_t splitmix(uint64_t& x) {
+  uint64_t z = (x += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+extern "C" unsigned long he_search_mulk(int curve, int which, int leg, uint64_t seed, unsigned long count, int threads,
+                                        uint64_t* hit) {
+  std::atomic<unsigned long> hits{0};
+  std::mutex m;
+  unsigned long first = ~0ul;
+  std::vector<std::thread> pool;
+  for (int t = 0; t < threads; ++t)
+    pool.emplace_back([&, t] {
+      uint64_t st = seed ^ ((uint64_t)t << 48);
+      for (unsigned long i = t; i < count; i += threads) {
+        uint64_t w[4] = {splitmix(st), splitmix(st), splitmix(st), splitmix(st)};
+        w[3] &= 0x7FFFFFFFFFFFFFFFull;  // below p for both curves
+        const fe v = ld(w);
+        const unsigned long before = fec_host_rare[leg];
+        if (curve == 0) (void)(which ? secp::mul_small(secp::sqr(secp::sqr(v)), 8) : secp::mul_small(secp::sqr(v), 3));
+        else (void)(which ? p256::mul_small(p256::sqr(p256::sqr(v)), 8) : p256::mul_small(p256::sqr(v), 3));
+        if (fec_host_rare[leg] != before) {  // keep the hit of the lowest candidate index: the result is deterministic
+          ++hits;
+          std::lock_guard<std::mutex> g(m);
+          if (i < first) {
+            first = i;
+            memcpy(hit, w, sizeof(w));
+          }
+        }
+      }
+    });
+  for (auto& th : pool) th.join();
+  return hits;
+}
 extern "C" int he_field_op(int curve, int op, const uint64_t* a, const uint64_t* b, uint64_t* out) {
   fe x = ld(a), y = b ? ld(b) : fe_zero(), r;
   if (curve == 0) r = op == 0 ? secp::add(x, y) : op == 1 ? secp::sub(x, y) : op == 2 ? secp::mul(x, y) : op == 3 ? secp::sqr(x) : secp::neg(x);
