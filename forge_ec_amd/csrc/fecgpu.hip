@@ -1319,6 +1319,44 @@ inline bool is_multi(const fec_ctx* ctx) { return ctx && !ctx->children.empty();
 
 }  // namespace
 
+// Curve25519 (kernels_x25519.hip): launch helpers of the fec_x25519 / fec_curve25519_mul entry points
+namespace {
+// The host forms of the Curve25519 calls: chunked through the ctx's staging; the scalars (slot 0) and the results
+// (slot 4) are secret and cleared on every way out, error returns included.
+template <class F>
+int x25519_host(fec_ctx* ctx, size_t n, const void* in0, size_t s0, const void* in1, size_t s1, void* out, size_t so, F launch) {
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  struct Wipe {
+    fec_ctx* c;
+    ~Wipe() {
+      for (int slot : {0, 4})
+        if (c->d_buf[slot]) (void)hipMemsetAsync(c->d_buf[slot], 0, c->d_cap[slot], c->stream);
+      (void)hipStreamSynchronize(c->stream);
+      (void)hipGetLastError();
+    }
+  } wipe{ctx};
+  const void* const in[4] = {in0, in1, nullptr, nullptr};
+  const size_t in_stride[4] = {s0, s1, 0, 0};
+  void* const outs[2] = {out, nullptr};
+  const size_t out_stride[2] = {so, 0};
+  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
+    return launch((const u32*)d[0], (const u32*)d[1], (u32*)o[0], cnt, nullptr);
+  });
+}
+int launch_x25519(fec_ctx* ctx, const u32* s, const u32* u, u32* out, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_x25519");
+  x25519_launch(s, u, out, n, L.s);
+  return L.done();
+}
+int launch_curve25519_mul(fec_ctx* ctx, const u32* s, const u32* p, u32* out, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_curve25519_mul");
+  curve25519_mul_launch(s, p, out, n, L.s);
+  return L.done();
+}
+}  // namespace
+
 extern "C" {
 
 int fec_point_limbs(fec_curve curve) { return curve_ok(curve) ? plimbs(curve) : 0; }
@@ -2590,6 +2628,76 @@ int fec_ctx_device_info(fec_ctx* ctx, char* name, size_t name_len, int* compute_
   if (compute_units) *compute_units = ctx->prop.multiProcessorCount;
   if (clock_khz) *clock_khz = ctx->prop.clockRate;
   return FEC_OK;
+} FEC_ABI_CATCH_STATUS
+
+// ---- Curve25519 (kernels_x25519.hip; helpers above the extern "C" block) ----
+
+int fec_x25519_dev(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_u, uint8_t* d_out, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || (n && (!d_scalars || !d_u || !d_out))) return FEC_E_ARG;
+  if (!aligned16(d_scalars) || !aligned16(d_u) || !aligned16(d_out)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_x25519(ctx, (const u32*)d_scalars, (const u32*)d_u, (u32*)d_out, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_x25519(fec_ctx* ctx, const uint8_t* scalars, const uint8_t* u, uint8_t* out, size_t n) try {
+  if (is_multi(ctx)) {
+    if (n && (!scalars || !u || !out)) return FEC_E_ARG;
+    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
+      return fec_x25519(c, scalars + lo * 32, u + lo * 32, out + lo * 32, cnt);
+    });
+  }
+  if (!ctx || (n && (!scalars || !u || !out))) return FEC_E_ARG;
+  if (n == 0) return FEC_OK;
+  return x25519_host(ctx, n, scalars, 32, u, 32, out, 32, [&](const u32* s, const u32* q, u32* o, size_t cnt, void* st) {
+    return launch_x25519(ctx, s, q, o, cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_curve25519_mul_dev(fec_ctx* ctx, const uint64_t* d_scalars, const uint64_t* d_points, uint64_t* d_out, size_t n,
+                           void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;
+  if (!ctx || (n && (!d_scalars || !d_points || !d_out))) return FEC_E_ARG;
+  if (!aligned16(d_scalars) || !aligned16(d_points) || !aligned16(d_out)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_curve25519_mul(ctx, (const u32*)d_scalars, (const u32*)d_points, (u32*)d_out, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_curve25519_mul(fec_ctx* ctx, const uint64_t* scalars, const uint64_t* points, uint64_t* out, size_t n) try {
+  if (is_multi(ctx)) {
+    if (n && (!scalars || !points || !out)) return FEC_E_ARG;
+    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
+      return fec_curve25519_mul(c, scalars + lo * 4, points + lo * 8, out + lo * 8, cnt);
+    });
+  }
+  if (!ctx || (n && (!scalars || !points || !out))) return FEC_E_ARG;
+  if (n == 0) return FEC_OK;
+  return x25519_host(ctx, n, scalars, 32, points, 64, out, 64, [&](const u32* s, const u32* p, u32* o, size_t cnt, void* st) {
+    return launch_curve25519_mul(ctx, s, p, o, cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_curve25519_field_op(fec_ctx* ctx, fec_field_opcode op, const uint64_t* a, const uint64_t* b, uint64_t* out,
+                            size_t n) try {
+  const bool binary = op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL;
+  if (op < FEC_F_ADD || op > FEC_F_NEG || (n && (!a || !out || (binary && !b)))) return FEC_E_ARG;
+  if (is_multi(ctx)) {
+    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
+      return fec_curve25519_field_op(c, op, a + lo * 4, binary ? b + lo * 4 : nullptr, out + lo * 4, cnt);
+    });
+  }
+  if (!ctx) return FEC_E_ARG;
+  if (n == 0) return FEC_OK;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const void* const in[4] = {a, binary ? b : nullptr, nullptr, nullptr};
+  const size_t in_stride[4] = {32, 32, 0, 0};
+  void* const outs[2] = {out, nullptr};
+  const size_t out_stride[2] = {32, 0};
+  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
+    Launch L(ctx, nullptr, "k_x25519_field_op");
+    x25519_field_launch((int)op, (const u32*)d[0], (const u32*)d[1], (u32*)o[0], cnt, L.s);
+    return L.done();
+  });
 } FEC_ABI_CATCH_STATUS
 
 }  // extern "C"

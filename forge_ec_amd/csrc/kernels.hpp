@@ -80,6 +80,13 @@ void ecdsa_batch_finish_launch(int curve, const u32* r_sum, const u32* ar, size_
 void ecdsa_sign_finish_launch(int curve, const u32* rp, const u32* sk, const unsigned char* digests, const u32* k, u32* sig,
                               unsigned char* status, size_t n, hipStream_t s);
 
+// kernels_x25519.hip: the reference's Curve25519 (curve25519.rs).  x25519: 32-byte scalar and u strings in, the 32-byte
+// result out (8 words per element each); multiply: raw Scalar limbs (8 words) and ProjectivePoint X then Z (16 words)
+// in, X then Z out; field op: FEC_F_* on raw limbs (8 words per operand).
+void x25519_launch(const u32* scalars, const u32* us, u32* out, size_t n, hipStream_t s);
+void curve25519_mul_launch(const u32* scalars, const u32* points, u32* out, size_t n, hipStream_t s);
+void x25519_field_launch(int op, const u32* a, const u32* b, u32* out, size_t n, hipStream_t s);
+
 // kernels_ecdsa.hip: Curve::validate_point per affine point (secp256k1 / P-256: is_on_curve; Ed25519: the trait default
 // with its two multiplications).  `work` holds validate_work_bytes(curve, n) bytes (0 for the Weierstrass curves).
 size_t validate_work_bytes(int curve, size_t n);

@@ -404,6 +404,41 @@ class Context:
         _check(self._lib.fec_field_op(self._h, curve, op, _ptr(x), _ptr(y), _ptr(out), x.shape[0]), "fec_field_op")
         return out
 
+    def x25519(self, scalars, u):
+        """The reference's x25519(scalar, u) per element (curve25519.rs:1624-1716): scalars and u (n, 32) uint8 byte
+        strings; returns (n, 32) uint8.  Parity mode, not RFC 7748 -- see include/fecgpu.h."""
+        s = np.ascontiguousarray(np.asarray(scalars, dtype=np.uint8)).reshape(-1, 32)
+        q = np.ascontiguousarray(np.asarray(u, dtype=np.uint8)).reshape(-1, 32)
+        if s.shape != q.shape:
+            raise ValueError("inputs differ in length")
+        out = np.zeros_like(s)
+        _check(self._lib.fec_x25519(self._h, _ptr(s), _ptr(q), _ptr(out), s.shape[0]), "fec_x25519")
+        return out
+
+    def curve25519_mul(self, scalars, points):
+        """Curve25519::multiply per element (curve25519.rs:1922-1955): scalars (n, 4) raw Scalar limbs, points (n, 8)
+        ProjectivePoint X limbs then Z limbs; returns (n, 8) likewise."""
+        k, p = _u64(scalars, 4), _u64(points, 8)
+        if k.shape[0] != p.shape[0]:
+            raise ValueError("inputs differ in length")
+        out = np.zeros_like(p)
+        _check(self._lib.fec_curve25519_mul(self._h, _ptr(k), _ptr(p), _ptr(out), k.shape[0]), "fec_curve25519_mul")
+        return out
+
+    def curve25519_field_op(self, op, a, b=None):
+        """Add / Sub / Mul / square / Neg of the reference's Curve25519 field (curve25519.rs:186-336, 490-494) on raw
+        limbs (n, 4)."""
+        x = _u64(a, 4)
+        y = _u64(b, 4) if b is not None else None
+        if y is not None and y.shape != x.shape:
+            raise ValueError("operands differ in shape")
+        if y is None and op in (L.F_ADD, L.F_SUB, L.F_MUL):
+            raise ValueError("binary op needs b")
+        out = np.empty_like(x)
+        _check(self._lib.fec_curve25519_field_op(self._h, op, _ptr(x), _ptr(y), _ptr(out), x.shape[0]),
+               "fec_curve25519_field_op")
+        return out
+
     def point_op(self, curve, op, p, q=None):
         pl = L.POINT_LIMBS[curve]
         x = _u64(p, pl)
@@ -475,6 +510,12 @@ class Context:
     def batch_ecdh_dev(self, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream=None):
         _check(self._lib.fec_batch_ecdh_dev(self._h, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream),
                "fec_batch_ecdh_dev")
+
+    def x25519_dev(self, d_scalars, d_u, d_out, n, stream=None):
+        _check(self._lib.fec_x25519_dev(self._h, d_scalars, d_u, d_out, n, stream), "fec_x25519_dev")
+
+    def curve25519_mul_dev(self, d_scalars, d_points, d_out, n, stream=None):
+        _check(self._lib.fec_curve25519_mul_dev(self._h, d_scalars, d_points, d_out, n, stream), "fec_curve25519_mul_dev")
 
     def ecdsa_sign_dev(self, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream=None):
         _check(self._lib.fec_ecdsa_sign_dev(self._h, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream), "fec_ecdsa_sign_dev")

@@ -454,6 +454,29 @@ int fec_ctx_fixed_prefix_bits(fec_ctx* ctx, fec_curve curve);
  * (tools/double_mul_small_perf.py); results do not depend on it. */
 int fec_ctx_set_side_stream_max(fec_ctx* ctx, size_t elements);
 
+/* ---- Curve25519 (forge-ec-curves/src/curve25519.rs), parity mode ----
+ * The reference's own x25519 and Curve25519::multiply, bit for bit, with its field's quirks (limb-wise Add / Sub
+ * with no carry between limbs, a schoolbook Mul that drops some carries and folds by 19, its own inversion chain): NOT
+ * RFC 7748 X25519.  Not constant-time in the caller's sense: a wavefront whose elements meet a rare leg of the field
+ * arithmetic takes a longer branch.  SECRETS: the host-pointer forms clear their device staging of the scalars and of
+ * the results before returning; the _dev forms leave every buffer to the caller.  The _dev forms take 16-byte aligned
+ * buffers and return FEC_E_UNSUPPORTED on a multi-device ctx; the host forms chunk by fec_ctx_set_chunk and shard
+ * over a multi-device ctx.
+ * fec_x25519       out[i] = x25519(scalars[i], u[i]) (1624-1716); all three are 32-byte strings.
+ * fec_curve25519_mul   out[i] = Curve25519::multiply(p[i], scalar[i]) (1922-1955): scalars n*4 raw Scalar limbs,
+ *                  points / out n*8 = ProjectivePoint X limbs then Z limbs (raw, unreduced, as the reference holds them).
+ * fec_curve25519_field_op   the field's Add / Sub / Mul / square / Neg (186-336, 490-494) on raw limbs; b is read
+ *                  for ADD, SUB and MUL only. */
+int fec_x25519(fec_ctx* ctx, const uint8_t* scalars /* n*32 */, const uint8_t* u /* n*32 */, uint8_t* out /* n*32 */,
+               size_t n);
+int fec_x25519_dev(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_u, uint8_t* d_out, size_t n, void* stream);
+int fec_curve25519_mul(fec_ctx* ctx, const uint64_t* scalars /* n*4 */, const uint64_t* points /* n*8 */,
+                       uint64_t* out /* n*8 */, size_t n);
+int fec_curve25519_mul_dev(fec_ctx* ctx, const uint64_t* d_scalars, const uint64_t* d_points, uint64_t* d_out, size_t n,
+                           void* stream);
+int fec_curve25519_field_op(fec_ctx* ctx, fec_field_opcode op, const uint64_t* a /* n*4 */, const uint64_t* b /* n*4 */,
+                            uint64_t* out /* n*4 */, size_t n);
+
 /* Host-pointer batches are processed as a two-lane pipeline of `elements`-sized chunks (default
  * 2^18): copies of one chunk overlap the kernel of the other, and device staging memory is bounded
  * by two chunks for any n.  Tuning/test knob; results do not depend on it. */

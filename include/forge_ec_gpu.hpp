@@ -491,6 +491,36 @@ inline std::vector<SharedSecret> derive_shared_secret(GpuContext& ctx, const std
 }
 }  // namespace key_exchange
 
+namespace curve25519 {
+// The reference's Curve25519 (forge-ec-curves/src/curve25519.rs) in parity mode: its own field quirks and special cases,
+// not RFC 7748 X25519, and not constant-time -- see fec_x25519 in fecgpu.h.
+using Bytes = std::array<uint8_t, 32>;
+using Limbs = std::array<uint64_t, 4>;
+// ProjectivePoint { x, z } as the reference holds it (raw limbs, unreduced values included)
+struct Point {
+  Limbs x, z;
+};
+// x25519(scalars[i], u[i]) (1624-1716)
+inline std::vector<Bytes> x25519(GpuContext& ctx, const std::vector<Bytes>& scalars, const std::vector<Bytes>& u) {
+  const size_t n = scalars.size();
+  if (u.size() != n) throw Error(FEC_E_ARG);
+  std::vector<Bytes> out(n);
+  check(fec_x25519(ctx.raw(), reinterpret_cast<const uint8_t*>(scalars.data()), reinterpret_cast<const uint8_t*>(u.data()),
+                   reinterpret_cast<uint8_t*>(out.data()), n));
+  return out;
+}
+// Curve25519::multiply(points[i], scalars[i]) (1922-1955) with raw Scalar limbs
+inline std::vector<Point> multiply(GpuContext& ctx, const std::vector<Point>& points, const std::vector<Limbs>& scalars) {
+  const size_t n = points.size();
+  if (scalars.size() != n) throw Error(FEC_E_ARG);
+  static_assert(sizeof(Point) == 64 && sizeof(Limbs) == 32, "packed limbs");
+  std::vector<Point> out(n);
+  check(fec_curve25519_mul(ctx.raw(), reinterpret_cast<const uint64_t*>(scalars.data()),
+                           reinterpret_cast<const uint64_t*>(points.data()), reinterpret_cast<uint64_t*>(out.data()), n));
+  return out;
+}
+}  // namespace curve25519
+
 namespace eddsa {
 // forge_ec_signature::eddsa::Signature<Ed25519> { r: AffinePoint, s: Scalar }
 struct Signature {

@@ -9,7 +9,7 @@
 use core::ffi::{c_char, c_double, c_float, c_int, c_uint, c_void};
 
 use forge_ec_core::{Curve, Error, Result};
-use forge_ec_curves::{ed25519, p256, secp256k1};
+use forge_ec_curves::{curve25519, ed25519, p256, secp256k1};
 
 /// Opaque `fec_ctx`.
 #[repr(C)]
@@ -73,6 +73,11 @@ extern "C" {
     fn fec_schnorr_verify_dev(ctx: *mut FecCtx, curve: c_int, d_pk_xy: *const u64, d_pk_inf: *const u8, d_r_xy: *const u64, d_r_inf: *const u8, d_s: *const u64, d_e: *const u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_batch_compress_dev(ctx: *mut FecCtx, curve: c_int, d_xy: *const u64, d_inf: *const u8, d_out: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_batch_to_affine_dev(ctx: *mut FecCtx, curve: c_int, d_points: *const u64, d_xy: *mut u64, d_inf: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_x25519(ctx: *mut FecCtx, scalars: *const u8, u: *const u8, out: *mut u8, n: usize) -> c_int;
+    fn fec_x25519_dev(ctx: *mut FecCtx, d_scalars: *const u8, d_u: *const u8, d_out: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_curve25519_mul(ctx: *mut FecCtx, scalars: *const u64, points: *const u64, out: *mut u64, n: usize) -> c_int;
+    fn fec_curve25519_mul_dev(ctx: *mut FecCtx, d_scalars: *const u64, d_points: *const u64, d_out: *mut u64, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_curve25519_field_op(ctx: *mut FecCtx, op: c_int, a: *const u64, b: *const u64, out: *mut u64, n: usize) -> c_int;
     fn fec_ctx_set_chunk(ctx: *mut FecCtx, elements: usize) -> c_int;
     fn fec_ctx_set_timing(ctx: *mut FecCtx, enabled: c_int) -> c_int;
     fn fec_ctx_last_kernel_ms(ctx: *mut FecCtx, ms: *mut c_float, kernel_name: *mut *const c_char) -> c_int;
@@ -565,6 +570,38 @@ pub fn batch_derive_shared_secret<C: GpuCurve>(ctx: &mut GpuContext, private_key
     }).collect())
 }
 
+/// `curve25519::x25519(scalars[i], u[i])` per element (`forge-ec-curves/src/curve25519.rs:1624-1716`), bit for bit:
+/// the reference's own field arithmetic and special cases, not RFC 7748 X25519, and not constant-time (see
+/// `fec_x25519` in include/fecgpu.h).  The library clears its device copies of the scalars and results.
+pub fn x25519_batch(ctx: &mut GpuContext, scalars: &[[u8; 32]], u: &[[u8; 32]]) -> Result<Vec<[u8; 32]>> {
+    let n = scalars.len();
+    if u.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let mut out = vec![[0u8; 32]; n];
+    // SAFETY: [u8; 32] slices are n * 32 contiguous bytes each.
+    check(unsafe { fec_x25519(ctx.raw, scalars.as_ptr() as *const u8, u.as_ptr() as *const u8, out.as_mut_ptr() as *mut u8, n) })?;
+    Ok(out)
+}
+
+/// `Curve25519::multiply(p, k)` per element (`forge-ec-curves/src/curve25519.rs:1922-1955`).  The reference keeps the
+/// coordinates of its `ProjectivePoint` private, so points cross as `(x, z)` field elements (`FieldElement::from_raw`
+/// / `to_raw`), exactly the values the reference holds, unreduced ones included.
+pub fn curve25519_mul_batch(ctx: &mut GpuContext, points: &[(curve25519::FieldElement, curve25519::FieldElement)], scalars: &[curve25519::Scalar]) -> Result<Vec<(curve25519::FieldElement, curve25519::FieldElement)>> {
+    let n = points.len();
+    if scalars.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let mut kk: Vec<u64> = scalars.iter().flat_map(|k| k.to_raw()).collect();
+    let pts: Vec<u64> = points.iter().flat_map(|(x, z)| x.to_raw().into_iter().chain(z.to_raw())).collect();
+    let mut out = vec![0u64; 8 * n];
+    // SAFETY: kk holds n * 4 limbs, pts and out n * 8.
+    let rc = check(unsafe { fec_curve25519_mul(ctx.raw, kk.as_ptr(), pts.as_ptr(), out.as_mut_ptr(), n) });
+    kk.iter_mut().for_each(|w| *w = 0);
+    rc?;
+    Ok((0..n).map(|i| (curve25519::FieldElement::from_raw(limb4(&out, 2 * i)), curve25519::FieldElement::from_raw(limb4(&out, 2 * i + 1)))).collect())
+}
+
 /// `Ecdsa::<C, D>::sign(sks[i], msgs[i])` per element (`forge-ec-signature/src/ecdsa.rs:98-211`) for `C` = secp256k1 or
 /// P-256: the hash (`D::digest`) and the nonce (`Rfc6979::<C, D>::generate_k`, `forge-ec-rng/src/rfc6979.rs:40`) on the
 /// host, R = k * G, r, s and `normalize` on the GPU under the reference's own scalar arithmetic.  Every `Err` of
@@ -818,6 +855,22 @@ pub mod dev {
         check(fec_batch_ecdh_dev(ctx.raw, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream))
     }
 
+    /// `fec_x25519_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn x25519(ctx: &mut GpuContext, d_scalars: *const u8, d_u: *const u8, d_out: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_x25519_dev(ctx.raw, d_scalars, d_u, d_out, n, stream))
+    }
+
+    /// `fec_curve25519_mul_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn curve25519_mul(ctx: &mut GpuContext, d_scalars: *const u64, d_points: *const u64, d_out: *mut u64, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_curve25519_mul_dev(ctx.raw, d_scalars, d_points, d_out, n, stream))
+    }
+
     /// `fec_ecdsa_sign_dev`.
     ///
     /// # Safety
@@ -871,6 +924,18 @@ pub mod hooks {
         let mut out = vec![[0u64; 4]; n];
         // SAFETY: n elements of 4 limbs behind every non-null pointer.
         check(unsafe { fec_field_op(ctx.raw, curve, op, a.as_ptr().cast(), b.map_or(core::ptr::null(), |x| x.as_ptr().cast()), out.as_mut_ptr().cast(), n) })?;
+        Ok(out)
+    }
+
+    /// `fec_curve25519_field_op` on raw limbs of the reference's Curve25519 field: op 0 add, 1 sub, 2 mul, 3 square, 4 neg.
+    pub fn curve25519_field_op(ctx: &mut GpuContext, op: c_int, a: &[[u64; 4]], b: Option<&[[u64; 4]]>) -> Result<Vec<[u64; 4]>> {
+        let n = a.len();
+        if b.map_or(false, |x| x.len() != n) {
+            return Err(Error::ValidationError);
+        }
+        let mut out = vec![[0u64; 4]; n];
+        // SAFETY: n elements of 4 limbs behind every non-null pointer.
+        check(unsafe { fec_curve25519_field_op(ctx.raw, op, a.as_ptr().cast(), b.map_or(core::ptr::null(), |x| x.as_ptr().cast()), out.as_mut_ptr().cast(), n) })?;
         Ok(out)
     }
 
