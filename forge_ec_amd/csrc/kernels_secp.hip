@@ -15,6 +15,7 @@
 
 #include "../../include/fecgpu.h"
 #include "secp256k1.hpp"
+#include "secp_step.hpp"
 #include "staging.hpp"
 #include "kernels.hpp"
 
@@ -172,20 +173,22 @@ __global__ __launch_bounds__(TPB, 3) void k_secp_mul(const u32* __restrict__ sca
         const int sh = (((i >> 3) & 3) << 3) + 7 - (i & 7);
         b = (kword >> sh) & 1u;
       }
-      lmask nd;
-      secp::pt s = padd_slots(slot0, slot0 + 24 * TPB, nd);
-      if (__builtin_expect(nd != 0, 0)) {  // Add (1469-1473) returns self.double(): never on random inputs
-        secp::pt d0 = secp::pdouble(ld3(slot0, TPB));
-        s = secp::pt_select(s, d0, nd);
-      }
       // (r0, r1) = bit ? (s, d) : (d, s) with d = double(bit ? r1 : r0), the only doubling the reference keeps
       // (2669-2684): the doubling's operand sits in slot `b`, which the doubling then overwrites; the sum goes to
-      // the other slot, whose point is dead once the addition has read it
+      // the other slot, whose point is dead once the addition has read it.  Each operation runs the fast step
+      // (secp_step.hpp) and, on a wavefront where some lane meets a rare condition, the exact code below instead.
       u32* const slot_d = slot0 + b * (24u * TPB);
       u32* const slot_s = slot0 + (b ^ 1u) * (24u * TPB);
-      const secp::pt din = ld3(slot_d, TPB);
-      st3(slot_s, TPB, s);
-      st3(slot_d, TPB, secp::pdouble(din));
+      secp_step::add_step(slot0, slot0 + 24 * TPB, slot_s, [&]() {
+        lmask nd;
+        secp::pt s = padd_slots(slot0, slot0 + 24 * TPB, nd);
+        if (__builtin_expect(nd != 0, 0)) {  // Add (1469-1473) returns self.double(): never on random inputs
+          secp::pt d0 = secp::pdouble(ld3(slot0, TPB));
+          s = secp::pt_select(s, d0, nd);
+        }
+        return s;
+      });
+      secp_step::double_step(slot_d, [&]() { return secp::pdouble(ld3(slot_d, TPB)); });
     }
     if (MODE != 3) {
       const secp::pt r0 = secp::pt_select(ld3(slot0, TPB), secp::identity(), early);

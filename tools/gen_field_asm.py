@@ -108,11 +108,14 @@ def mul_wide_columns(A, B, VB, side_for_column=None, first_col_src=None):
 # operands: %0-%7 r, %8 sc (SGPR pair: the recurrence's 33rd bit), %9 bw (SGPR pair: dummy carry
 # sink, then the borrow out of word 1), %10-%17 a, %18-%25 b, %26 N0' (s), %27 977 (s)
 # ------------------------------------------------------------------------------------------------
-def secp_mul(VB):
-    A = ["%%%d" % (10 + i) for i in range(8)]
-    B = ["%%%d" % (18 + i) for i in range(8)]
+# acc=True (FEC_SECP_MUL_ACC): %9 is only the sink, %10 acc (SGPR pair, read and written: the borrow is OR-ed into it),
+# %11-%18 a, %19-%26 b, %27 N0', %28 977
+def secp_mul(VB, acc=False):
+    o = 1 if acc else 0
+    A = ["%%%d" % (10 + o + i) for i in range(8)]
+    B = ["%%%d" % (18 + o + i) for i in range(8)]
     R = ["%%%d" % i for i in range(8)]
-    SC, BW, N0P, C977 = "%8", "%9", "%26", "%27"
+    SC, BW, N0P, C977 = "%8", "%9", "%%%d" % (26 + o), "%%%d" % (27 + o)
     P, D = VB + 32, VB + 34  # P = {e_lo, 0}; D = m*977 + P
     T = [VB + 2 * k for k in range(15)] + [VB + 29]
     M = [VB + 2 * k + 1 for k in range(8)]
@@ -141,7 +144,7 @@ def secp_mul(VB):
     b.e("v_cndmask_b32_e64 %s, 0, 1, %s" % (v(P + 1), SC))
     b.e("v_sub_co_u32_e32 %s, vcc, %s, %s" % (R[0], R[0], v(P)))
     b.e("v_subb_co_u32_e32 %s, vcc, %s, %s, vcc" % (R[1], R[1], v(P + 1)))
-    b.e("s_mov_b64 %s, vcc" % BW)
+    b.e("s_or_b64 %10, %10, vcc" if acc else "s_mov_b64 %s, vcc" % BW)
     return b, list(range(VB, VB + 36))
 
 
@@ -150,8 +153,10 @@ def secp_mul(VB):
 # nine words, so V = T_hi + M - Q is M + t8 - Q.  The carry of m0 + t8 (t8 < 8) out of word 0 is an
 # exception lane (2^-29), the borrow of - Q out of word 1 the same rare continuation as in Mul.
 # operands: %0-%7 r, %8 sc, %9 bw (sink, then the borrow mask), %10 exc, %11-%18 a, %19 N0' (s), %20 977 (s)
+# acc=True (FEC_SECP_MUL3_ACC / MUL8_ACC): %9 is only the sink; exc and the borrow are both OR-ed into %10 (read and
+# written)
 # ------------------------------------------------------------------------------------------------
-def secp_mul_small(VB, K):
+def secp_mul_small(VB, K, acc=False):
     A = ["%%%d" % (11 + i) for i in range(8)]
     R = ["%%%d" % i for i in range(8)]
     SC, BW, EXC, N0P, C977 = "%8", "%9", "%10", "%19", "%20"
@@ -177,11 +182,11 @@ def secp_mul_small(VB, K):
         b.e("v_mad_u64_u32 %s, %s, %s, %s, %s" % (vp(D), BW, R[k], C977, vp(P)))
         b.e("v_addc_co_u32_e64 %s, %s, %s, %s, %s" % (v(P), SC, v(D + 1), R[k], SC))
     b.e("v_add_co_u32_e32 %s, vcc, %s, %s" % (R[0], R[0], t8))
-    b.e("s_mov_b64 %s, vcc" % EXC)
+    b.e("s_or_b64 %s, %s, vcc" % (EXC, EXC) if acc else "s_mov_b64 %s, vcc" % EXC)
     b.e("v_cndmask_b32_e64 %s, 0, 1, %s" % (v(P + 1), SC))
     b.e("v_sub_co_u32_e32 %s, vcc, %s, %s" % (R[0], R[0], v(P)))
     b.e("v_subb_co_u32_e32 %s, vcc, %s, %s, vcc" % (R[1], R[1], v(P + 1)))
-    b.e("s_mov_b64 %s, vcc" % BW)
+    b.e("s_or_b64 %s, %s, vcc" % (EXC, EXC) if acc else "s_mov_b64 %s, vcc" % BW)
     return b, list(range(VB, VB + 22))
 
 
@@ -192,8 +197,9 @@ def secp_mul_small(VB, K):
 # where one would fire are collected in the exception mask %9 and the caller recomputes those
 # wavefronts with sqr_cxx.
 # operands: %0-%7 r, %8 tmp (SGPR pair), %9 exc (SGPR pair), %10-%17 a, %18 977 (s)
+# acc=True (FEC_SECP_SQR_ACC): %9 is the caller's accumulator (read and written), not cleared first
 # ------------------------------------------------------------------------------------------------
-def secp_sqr(VB):
+def secp_sqr(VB, acc=False):
     A = ["%%%d" % (10 + i) for i in range(8)]
     R = ["%%%d" % i for i in range(8)]
     TMP, EXC, C977 = "%8", "%9", "%18"
@@ -208,7 +214,8 @@ def secp_sqr(VB):
     Z, Y = pair(), pair()  # Z = {x, 0} zero-extension pair; Y = {acc.hi, ovf}
     b = Block()
     b.e("v_mov_b32_e32 %s, 0" % v(Z + 1))
-    b.e("s_mov_b64 %s, 0" % EXC)
+    if not acc:
+        b.e("s_mov_b64 %s, 0" % EXC)
 
     def mul64(x0, x1, y0, y1, pa, pb, pc):
         """p = (x1:x0)*(y1:y0): p0 = lo(pa), p1 = lo(pb), p2 = lo(pc), p3 = hi(pc)."""
@@ -267,6 +274,31 @@ def secp_sqr(VB):
         parts = b.lines[last].split(" ", 2)
         b.lines[last] = "%s %s, %s" % (parts[0], R[i], parts[2])
     return b, list(range(VB, nxt[0]))
+
+
+# ------------------------------------------------------------------------------------------------
+# secp256k1 Add / double / Sub (secp256k1.rs:353-440) for the ladder's fast step (secp_step.hpp): the 256-bit chain and
+# the short +-c on the carry (borrow) lanes in one statement, VCC handed straight from the chain to the short add.  The
+# carry (borrow) out of word 1 -- the continuation of secp256k1.hpp's add / dbl / sub -- is OR-ed into the caller's
+# accumulator instead of being tested; so is nothing else: add's and dbl's top-word condition is the caller's (the
+# result's top word is the chain's whenever no carry left word 1).
+# operands: %0-%7 x (in place: a on entry), %8 acc (SGPR pair, read and written), %9-%10 temporaries, %11-%18 b
+# ------------------------------------------------------------------------------------------------
+def secp_addsub_acc(op):
+    X = ["%%%d" % i for i in range(8)]
+    ACC, T1, T0 = "%8", "%9", "%10"
+    Bop = X if op == "dbl" else ["%%%d" % (11 + i) for i in range(8)]
+    first, rest = ("v_sub_co_u32_e32", "v_subb_co_u32_e32") if op == "sub" else ("v_add_co_u32_e32", "v_addc_co_u32_e32")
+    b = Block()
+    b.e("%s %s, vcc, %s, %s" % (first, X[0], X[0], Bop[0]))
+    for i in range(1, 8):
+        b.e("%s %s, vcc, %s, %s, vcc" % (rest, X[i], X[i], Bop[i]))
+    b.e("v_cndmask_b32_e64 %s, 0, 1, vcc" % T1)
+    b.e("v_mul_u32_u24_e32 %s, 0x3d1, %s" % (T0, T1))
+    b.e("%s %s, vcc, %s, %s" % (first, X[0], X[0], T0))
+    b.e("%s %s, vcc, %s, %s, vcc" % (rest, X[1], X[1], T1))
+    b.e("s_or_b64 %s, %s, vcc" % (ACC, ACC))
+    return b
 
 
 def sqr_wide_columns(A, VB, sink):
@@ -546,6 +578,18 @@ def main():
     add("P256_MUL8", *p256_mul_small(P256_TOP - 24, 8))
     add("ED_MUL", *ed_mul(ED_TOP - 32))
     add("ED_SQR", *ed_sqr(ED_TOP - 46))
+    # accumulating forms for the secp256k1 ladder's fast step (secp_step.hpp): the rare conditions are OR-ed into an
+    # SGPR pair of the caller's, tested once per point operation
+    add("SECP_MUL_ACC", *secp_mul(SECP_TOP - 36, acc=True))
+    add("SECP_SQR_ACC", *secp_sqr(SECP_TOP - 34, acc=True))
+    add("SECP_MUL3_ACC", *secp_mul_small(SECP_TOP - 22, 3, acc=True))
+    add("SECP_MUL8_ACC", *secp_mul_small(SECP_TOP - 22, 8, acc=True))
+    for op in ("add", "dbl", "sub"):
+        blk = secp_addsub_acc(op)
+        name = "SECP_%s_ACC" % op.upper()
+        parts.append("#define FEC_%s_ASM \\\n" % name + blk.text().replace("\n", " \\\n") + "\n")
+        parts.append("// FEC_%s_ASM: %d instructions, no fixed block\n" % (name, len(blk.lines)))
+        report.append("%s %d" % (name, len(blk.lines)))
     with open(OUT, "w") as f:
         f.write("\n".join(parts))
     print("wrote %s (%s)" % (OUT, ", ".join(report)))

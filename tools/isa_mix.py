@@ -166,6 +166,7 @@ def main():
 
     def walk(start_pc):
         path, pc, steps, scc, first_visit = [], start_pc, 0, None, {}
+        sel, vcc = {}, None  # SGPR pairs set by s_cselect_b64 X, -1, 0 on a known SCC; VCC = EXEC & such a pair
         while steps < 400000:
             if pc in first_visit:  # the cycle closed: one iteration = the walk since the first visit
                 return path[first_visit[pc]:]
@@ -173,6 +174,13 @@ def main():
             m, ops = insts[pc]
             path.append(m)
             steps += 1
+            o = [x.strip() for x in ops.split(",")]
+            if m == "s_cselect_b64" and o[1:] == ["-1", "0"]:
+                sel[o[0]] = scc
+            elif m == "s_and_b64" and o[0] == "vcc" and "exec" in o[1:]:
+                vcc = sel.get(o[2] if o[1] == "exec" else o[1])
+            elif o and o[0] == "vcc" or m.startswith("v_cmp"):
+                vcc = None
             if m in ("s_cmp_eq_u64", "s_cmp_lg_u64") and ops.replace(" ", "").endswith(",0"):
                 scc = 1 if m == "s_cmp_eq_u64" else 0
             elif m.startswith(("s_cmp", "s_add", "s_sub", "s_and", "s_or", "s_xor", "s_lshl", "s_lshr", "s_bitcmp", "s_andn2", "s_orn2", "s_not")):
@@ -184,7 +192,9 @@ def main():
                 taken = scc == 0
             elif m == "s_cbranch_scc1":
                 taken = scc == 1
-            elif m in ("s_cbranch_vccz", "s_cbranch_execnz"):
+            elif m == "s_cbranch_vccz":
+                taken = vcc != 1  # a rare-mask test reached through s_cselect (mask == 0 -> VCC = EXEC) falls through
+            elif m == "s_cbranch_execnz":
                 taken = True
             if m.startswith("s_cbranch") and label_at.get(ops.split()[0].rstrip(",")) == start_pc:
                 taken = True  # the loop's own back edge (its condition is the trip counter)
