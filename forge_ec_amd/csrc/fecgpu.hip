@@ -1122,6 +1122,31 @@ int launch_ecdsa_sign(fec_ctx* ctx, int curve, const u64* dsk, const unsigned ch
   return L.done();
 }
 
+// The reference's EdDSA signing for Ed25519 with SHA-512 (kernels_eddsa.hip): k_eddsa_sign_pre, ONE fixed-base launch
+// over the 2n scalars a and r (derive: the n scalars a) under launch_mul's prefix-table policy -- the host-pointer form
+// may build a table, a *_dev call only takes one that exists -- then k_eddsa_sign_finish.  The scalars, the points, the
+// flags and the popcount-sort area of the fixed-base kernel are regions of one work area, taken in one request.
+int launch_eddsa_sign(fec_ctx* ctx, const EddsaSignIo& io, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  const size_t m = io.mode == EDDSA_MODE_DERIVE ? n : 2 * n;
+  u32 *scal, *pts;
+  unsigned char* flags;
+  void* sort;
+  WorkArea area;
+  area.add(scal, m * 32).add(pts, m * 128).add(flags, n).add(sort, ed_fixed_work_bytes(m));
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, FEC_ED25519, st, m);
+  if (rc != FEC_OK) return rc;
+  EddsaSignIo a = io;
+  a.gen = reinterpret_cast<const u32*>(ctx->d_gen[FEC_ED25519]);
+  Launch L(ctx, stream, "k_eddsa_sign_pre + k_ed_fixed_base + k_eddsa_sign_finish");
+  eddsa_sign_pre_launch(a, scal, flags, n, L.s);
+  fixed_product(ctx, sched_env(ctx), FEC_ED25519, scal, a.gen, pts, m, sort, L.s);
+  eddsa_sign_finish_launch(a, scal, pts, flags, n, L.s);
+  return L.done();
+}
+
 int launch_field(fec_ctx* ctx, int curve, int op, const u64* da, const u64* db, u64* dout, size_t n,
                  void* stream = nullptr) {
   if (n == 0) return FEC_OK;
@@ -1354,6 +1379,131 @@ int launch_curve25519_mul(fec_ctx* ctx, const u32* s, const u32* p, u32* out, si
   Launch L(ctx, stream, "k_curve25519_mul");
   curve25519_mul_launch(s, p, out, n, L.s);
   return L.done();
+}
+}  // namespace
+
+// EdDSA signing and SHA-512 (kernels_eddsa.hip): the message layout and the host-pointer pipeline of the calls that take
+// messages.  Message i is msgs[off[i], off[i+1]); off holds n + 1 values, off[0] = 0, non-decreasing, off[n] = msg_len.
+namespace {
+bool msg_layout_ok(const uint8_t* msgs, const uint64_t* off, size_t msg_len, size_t n) {
+  if (!off || off[0] != 0 || off[n] != (uint64_t)msg_len || (msg_len && !msgs)) return false;
+  for (size_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return false;
+  return true;
+}
+constexpr int kSha512 = -1;   // msg_pipeline's mode for fec_sha512 (else EDDSA_MODE_*)
+// The host forms: chunks of ctx->chunk elements.  Per chunk the keys go to slot 0, the chunk's message bytes
+// msgs[off[lo], off[lo + cnt]) to slot 1 and its offsets, rebased to that range, to slot 2; the outputs are regions of
+// slot 4 (out: 64 bytes per element, 32 for derive; status; r_inf and s for the generic form).  `off` points at the
+// first element's offset and need not start at 0 (a shard of a multi-device call).  The keys (slot 0), the outputs
+// (slot 4) and the stream scratch (a, r, A, R) are cleared on every way out, error returns included.
+int msg_pipeline(fec_ctx* ctx, int mode, const void* keys, const uint8_t* msgs, const uint64_t* off, void* out,
+                 uint8_t* status, uint8_t* r_inf, uint64_t* s_out, size_t n) {
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  struct Wipe {
+    fec_ctx* c;
+    ~Wipe() {
+      for (int slot : {0, 4})
+        if (c->d_buf[slot]) (void)hipMemsetAsync(c->d_buf[slot], 0, c->d_cap[slot], c->stream);
+      for (auto& e : c->stream_scratch)
+        if (e.stream == c->stream && e.buf) (void)hipMemsetAsync(e.buf, 0, e.cap, c->stream);
+      (void)hipStreamSynchronize(c->stream);
+      (void)hipGetLastError();
+    }
+  } wipe{ctx};
+  const size_t pc = pipeline_chunk(ctx);
+  const size_t chunk = pc < n ? pc : n;
+  const size_t ob = mode == EDDSA_MODE_DERIVE ? 32 : 64;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_status = up(chunk * ob), o_inf = o_status + up(chunk), o_s = o_inf + up(chunk);
+  const bool with_msgs = mode != EDDSA_MODE_DERIVE;
+  std::vector<uint64_t> reb(with_msgs ? chunk + 1 : 0);
+  return drained(ctx, [&]() -> int {
+    for (size_t lo = 0; lo < n; lo += chunk) {
+      const size_t cnt = lo + chunk <= n ? chunk : n - lo;
+      const u32* d_keys = nullptr;
+      if (keys) {
+        int rc = ensure(ctx, 0, chunk * 32);
+        if (rc != FEC_OK) return rc;
+        if (hipMemcpyAsync(ctx->d_buf[0], (const char*)keys + lo * 32, cnt * 32, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+          return FEC_E_DEVICE;
+        d_keys = static_cast<const u32*>(ctx->d_buf[0]);
+      }
+      const unsigned char* d_msgs = nullptr;
+      const u64* d_off = nullptr;
+      u64 bytes = 0;
+      if (with_msgs) {
+        const u64 b0 = off[lo];
+        bytes = off[lo + cnt] - b0;
+        for (size_t k = 0; k <= cnt; ++k) reb[k] = off[lo + k] - b0;
+        int rc = ensure(ctx, 2, (chunk + 1) * 8);
+        if (rc == FEC_OK && bytes) rc = ensure(ctx, 1, bytes);
+        if (rc != FEC_OK) return rc;
+        if (bytes && hipMemcpyAsync(ctx->d_buf[1], msgs + b0, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+          return FEC_E_DEVICE;
+        if (hipMemcpyAsync(ctx->d_buf[2], reb.data(), (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+          return FEC_E_DEVICE;
+        d_msgs = bytes ? static_cast<const unsigned char*>(ctx->d_buf[1]) : nullptr;
+        d_off = static_cast<const u64*>(ctx->d_buf[2]);
+      }
+      int rc = ensure(ctx, 4, o_s + chunk * 32);
+      if (rc != FEC_OK) return rc;
+      char* d_out = static_cast<char*>(ctx->d_buf[4]);
+      if (mode == kSha512) {
+        Launch L(ctx, nullptr, "k_sha512");
+        sha512_launch(d_msgs, d_off, bytes, reinterpret_cast<u32*>(d_out), nullptr, cnt, L.s);
+        rc = L.done();
+      } else {
+        const EddsaSignIo io{mode, d_keys, d_msgs, d_off, bytes, nullptr, reinterpret_cast<u32*>(d_out),
+                             reinterpret_cast<unsigned char*>(d_out + o_inf), reinterpret_cast<u32*>(d_out + o_s),
+                             reinterpret_cast<unsigned char*>(d_out + o_status)};
+        rc = launch_eddsa_sign(ctx, io, cnt, nullptr);
+      }
+      if (rc != FEC_OK) return rc;
+      const struct {
+        void* host;
+        size_t from, stride;
+      } copies[4] = {{out, 0, ob}, {status, o_status, 1}, {r_inf, o_inf, 1}, {s_out, o_s, 32}};
+      for (const auto& c : copies)
+        if (c.host && hipMemcpyAsync(static_cast<char*>(c.host) + lo * c.stride, d_out + c.from, cnt * c.stride,
+                                     hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+          return FEC_E_DEVICE;
+      rc = sync_and_check(ctx, ctx->stream);
+      if (rc != FEC_OK) return rc;
+    }
+    return FEC_OK;
+  });
+}
+// A host-pointer call with messages on a single-device or a multi-device ctx (contiguous shards, each through
+// msg_pipeline on its child ctx).  The layout is checked once, here.
+int msg_call(fec_ctx* ctx, int mode, const void* keys, size_t key_stride, const uint8_t* msgs, const uint64_t* off,
+             size_t msg_len, void* out, uint8_t* status, uint8_t* r_inf, uint64_t* s_out, size_t n) {
+  if (!ctx) return FEC_E_ARG;
+  if (mode != EDDSA_MODE_DERIVE && !msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  if (n == 0) return FEC_OK;
+  const size_t ob = mode == EDDSA_MODE_DERIVE ? 32 : 64;
+  if (is_multi(ctx)) {
+    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
+      auto at = [lo](auto* p, size_t stride) { return p ? reinterpret_cast<decltype(p)>(reinterpret_cast<uintptr_t>(p) + lo * stride) : p; };
+      return msg_pipeline(c, mode, at(static_cast<const char*>(keys), key_stride), msgs, off ? off + lo : nullptr,
+                          at(static_cast<char*>(out), ob), at(status, 1), at(r_inf, 1), at(s_out, 32), cnt);
+    });
+  }
+  return msg_pipeline(ctx, mode, keys, msgs, off, out, status, r_inf, s_out, n);
+}
+// The *_dev forms: one launch sequence on the caller's stream; each lane checks its own message range.
+int eddsa_sign_dev(fec_ctx* ctx, int mode, const void* d_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                   void* d_out, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_status, size_t n, void* stream) {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  const bool with_msgs = mode != EDDSA_MODE_DERIVE;
+  if (!ctx || (n && (!d_keys || !d_out || !d_status || (with_msgs && !d_msg_off))) || (with_msgs && msg_len && !d_msgs))
+    return FEC_E_ARG;
+  if (mode == EDDSA_MODE_GENERIC && n && (!d_r_inf || !d_s)) return FEC_E_ARG;
+  if (!aligned16(d_keys) || !aligned16(d_out) || !aligned16(d_s) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const EddsaSignIo io{mode, static_cast<const u32*>(d_keys), with_msgs ? d_msgs : nullptr, with_msgs ? reinterpret_cast<const u64*>(d_msg_off) : nullptr,
+                       with_msgs ? (u64)msg_len : 0, nullptr, static_cast<u32*>(d_out), d_r_inf, reinterpret_cast<u32*>(d_s), d_status};
+  return launch_eddsa_sign(ctx, io, n, stream);
 }
 }  // namespace
 
@@ -2698,6 +2848,58 @@ int fec_curve25519_field_op(fec_ctx* ctx, fec_field_opcode op, const uint64_t* a
     x25519_field_launch((int)op, (const u32*)d[0], (const u32*)d[1], (u32*)o[0], cnt, L.s);
     return L.done();
   });
+} FEC_ABI_CATCH_STATUS
+
+// ---- EdDSA signing for Ed25519 with SHA-512, and SHA-512 (kernels_eddsa.hip; helpers above the extern "C" block) ----
+
+int fec_sha512(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* digests, size_t n) try {
+  if (n && !digests) return FEC_E_ARG;
+  return msg_call(ctx, kSha512, nullptr, 0, msgs, msg_off, msg_len, digests, nullptr, nullptr, nullptr, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_sha512_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
+                   uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || (n && (!d_msg_off || !d_digests)) || (msg_len && !d_msgs)) return FEC_E_ARG;
+  if (!aligned16(d_digests) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_sha512");
+  sha512_launch(d_msgs, d_msg_off, msg_len, reinterpret_cast<u32*>(d_digests), d_status, n, L.s);
+  return L.done();
+} FEC_ABI_CATCH_STATUS
+
+int fec_ed25519_sign(fec_ctx* ctx, const uint8_t* private_keys, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                     uint8_t* sig, uint8_t* status, size_t n) try {
+  if (n && (!private_keys || !sig || !status)) return FEC_E_ARG;
+  return msg_call(ctx, EDDSA_MODE_SIGN, private_keys, 32, msgs, msg_off, msg_len, sig, status, nullptr, nullptr, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_ed25519_derive_public_key(fec_ctx* ctx, const uint8_t* private_keys, uint8_t* public_keys, uint8_t* status,
+                                  size_t n) try {
+  if (n && (!private_keys || !public_keys || !status)) return FEC_E_ARG;
+  return msg_call(ctx, EDDSA_MODE_DERIVE, private_keys, 32, nullptr, nullptr, 0, public_keys, status, nullptr, nullptr, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_eddsa_sign_ed25519(fec_ctx* ctx, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                           uint64_t* r_xy, uint8_t* r_inf, uint64_t* s, uint8_t* status, size_t n) try {
+  if (n && (!sk || !r_xy || !r_inf || !s || !status)) return FEC_E_ARG;
+  return msg_call(ctx, EDDSA_MODE_GENERIC, sk, 32, msgs, msg_off, msg_len, r_xy, status, r_inf, s, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_ed25519_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                         size_t msg_len, uint8_t* d_sig, uint8_t* d_status, size_t n, void* stream) try {
+  return eddsa_sign_dev(ctx, EDDSA_MODE_SIGN, d_private_keys, d_msgs, d_msg_off, msg_len, d_sig, nullptr, nullptr, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_ed25519_derive_public_key_dev(fec_ctx* ctx, const uint8_t* d_private_keys, uint8_t* d_public_keys, uint8_t* d_status,
+                                      size_t n, void* stream) try {
+  return eddsa_sign_dev(ctx, EDDSA_MODE_DERIVE, d_private_keys, nullptr, nullptr, 0, d_public_keys, nullptr, nullptr, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_eddsa_sign_ed25519_dev(fec_ctx* ctx, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                               uint64_t* d_r_xy, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_status, size_t n, void* stream) try {
+  return eddsa_sign_dev(ctx, EDDSA_MODE_GENERIC, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 }  // extern "C"

@@ -87,6 +87,32 @@ void x25519_launch(const u32* scalars, const u32* us, u32* out, size_t n, hipStr
 void curve25519_mul_launch(const u32* scalars, const u32* points, u32* out, size_t n, hipStream_t s);
 void x25519_field_launch(int op, const u32* a, const u32* b, u32* out, size_t n, hipStream_t s);
 
+// kernels_eddsa.hip: the reference's EdDSA signing for Ed25519 with SHA-512 (forge-ec-signature/src/eddsa.rs) around
+// one fixed-base launch over the pre pass's scalars (a at [0, n), r at [n, 2n); derive: a only; 8 words each), and the
+// per-message SHA-512.  Messages: element i is msgs[off[i], off[i+1]) (n + 1 offsets; each lane checks its range
+// against msg_len).  out: EDDSA_MODE_SIGN 16 words (the signature's 64 bytes), EDDSA_MODE_DERIVE 8 words (32 bytes),
+// EDDSA_MODE_GENERIC 16 words (R's affine x then y) with r_inf and s (8 words); status one byte.  gen: generator()
+// (32 words; EDDSA_MODE_GENERIC's special cases).  flags: one byte per element between the two passes.
+enum : int { EDDSA_MODE_SIGN = 0, EDDSA_MODE_DERIVE = 1, EDDSA_MODE_GENERIC = 2 };
+struct EddsaSignIo {
+  int mode;
+  const u32* keys;   // SIGN / DERIVE: the 32 private-key bytes; GENERIC: the raw Scalar limbs
+  const unsigned char* msgs;
+  const u64* off;
+  u64 msg_len;
+  const u32* gen;
+  u32* out;
+  unsigned char* r_inf;
+  u32* s;
+  unsigned char* status;
+};
+void eddsa_sign_pre_launch(const EddsaSignIo& io, u32* scal, unsigned char* flags, size_t n, hipStream_t s);
+void eddsa_sign_finish_launch(const EddsaSignIo& io, const u32* scal, const u32* pts, const unsigned char* flags, size_t n,
+                              hipStream_t s);
+// digests: 16 words (64 bytes) per message, zero where the range is bad; status (may be null): 0, or 4 for a bad range
+void sha512_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
+                   hipStream_t s);
+
 // kernels_ecdsa.hip: Curve::validate_point per affine point (secp256k1 / P-256: is_on_curve; Ed25519: the trait default
 // with its two multiplications).  `work` holds validate_work_bytes(curve, n) bytes (0 for the Weierstrass curves).
 size_t validate_work_bytes(int curve, size_t n);

@@ -1,0 +1,304 @@
+// kernels_eddsa.hip -- the reference's EdDSA SIGNING for Ed25519 with SHA-512 (forge-ec-signature/src/eddsa.rs), around
+// one fixed-base multiplication launch (fecgpu.hip: launch_eddsa_sign):
+//   k_eddsa_sign_pre     special cases; h = SHA512(key); a = clamped h[32..64] read BIG-endian; r = SHA512(nonce || msg)
+//                        [0..32] read big-endian; a and r into one 2n-scalar array (derive_public_key: a alone)
+//   (fixed base)         multiply(G, a), multiply(G, r) -- the curve's LDS addend-table kernel
+//   k_eddsa_sign_finish  to_affine and the 33-byte to_bytes of A and R; k = SHA512(R33 || A33 || msg)[0..32] read
+//                        big-endian; s = r + k * a (release-profile Mul); the output form and the status
+//   k_sha512             SHA-512 per message (the parity hook fec_sha512)
+// One element per lane; the hash state lives in VGPRs (sha512.hpp).
+//
+// The readings, pinned (eddsa.rs unless named; ed25519.rs = forge-ec-curves/src/ed25519.rs):
+//  * Scalar from bytes is the TRAIT from_bytes (ed25519.rs:1142-1162): big-endian, no range check, always Some.  So
+//    the `.unwrap()` at 304-305 never fires, the clamp (298-300) lands on bits 248-255 and 0-7 of a big-endian number,
+//    and from_bytes_reduced (forge-ec-core/src/lib.rs:320-331) returns at its first branch: r and k are h[0..32]
+//    read big-endian, with no reduction.  derive_public_key's `from_bytes` fallback (488-496) is unreachable likewise.
+//  * A and R go through the trait PointAffine::to_bytes (ed25519.rs:1505-1525), 33 bytes: 0x02 | (y.to_bytes()[31] & 1)
+//    (y little-endian, so bit 248 of y), then x little-endian; 0x00 and 32 zeros for the identity.  All 33 bytes of
+//    R and of A are hashed (326-329); the signature keeps R33[0..32] (343), derive_public_key returns A33[0..32] (503-505).
+//  * s = r + k * a with the scalar Mul as the release profile runs it (ed25519.hpp: sc_mul_release) and Add
+//    (ed25519.rs:1193-1239: the sum mod 2^256, one conditional subtraction; it cannot panic).  Ed25519Signature::sign
+//    writes `<Ed25519 as Curve>::Scalar::to_bytes(&s)` (340): a type-qualified path, which Rust resolves to the
+//    INHERENT to_bytes (ed25519.rs:767-781): one conditional subtraction of l (reduce, 744-762), then little-endian.
+//    EdDsa::<Ed25519, Sha512>::sign returns s as it is (149-153).
+//  * Special cases: Ed25519Signature::sign (267-291): msg == "test message" -> bytes 0..63; msg empty and key[0] ==
+//    0x9d -> the RFC 8032 TEST 1 signature.  derive_public_key (450-460): key[0] == 0x9d -> the TEST 1 public key,
+//    whatever the rest of the key.  EdDsa::sign (43-62): msg == "test message", or msg empty and the trait
+//    to_bytes(sk)[0] (big-endian: the top byte of limb 3) == 0x9d -> (to_affine(generator()), one()).  The generic form
+//    hashes the trait to_bytes(sk) (65-69), 32 big-endian bytes of the raw limbs.
+//  * status: 1 where the reference panics -- to_affine (ed25519.rs:1793-1811) unwraps z.invert(), which is None for a
+//    zero z of a point that is not the identity; 2 where only a debug build panics -- Mul's u128 column sums pass 2^128
+//    (the release build wraps and goes on: the output is the release value); 4 (the *_dev forms) where the element's
+//    message range [off[i], off[i+1]) is not inside [0, msg_len): nothing of the message is read and the outputs are 0.
+//    Where status has bit 1 the outputs are 0.
+#include <hip/hip_runtime.h>
+
+#include "../../include/fecgpu.h"
+#include "ed25519.hpp"
+#include "sha512.hpp"
+#include "staging.hpp"
+#include "kernels.hpp"
+
+namespace fecgpu {
+
+namespace {
+
+static __constant__ unsigned char kRfcSig[64] = {   // eddsa.rs:283 (RFC 8032 7.1 TEST 1)
+    0xe5, 0x56, 0x43, 0x00, 0xc3, 0x60, 0xac, 0x72, 0x90, 0x86, 0xe2, 0xcc, 0x80, 0x6e, 0x82, 0x8a,
+    0x84, 0x87, 0x7f, 0x1e, 0xb8, 0xe5, 0xd9, 0x74, 0xd8, 0x73, 0xe0, 0x65, 0x22, 0x49, 0x01, 0x55,
+    0x5f, 0xb8, 0x82, 0x15, 0x90, 0xa3, 0x3b, 0xac, 0xc6, 0x1e, 0x39, 0x70, 0x1c, 0xf9, 0xb4, 0x6b,
+    0xd2, 0x5b, 0xf5, 0xf0, 0x59, 0x5b, 0xbe, 0x24, 0x65, 0x51, 0x41, 0x43, 0x8e, 0x7a, 0x10, 0x0b};
+static __constant__ unsigned char kRfcPk[32] = {    // eddsa.rs:455 (RFC 8032 7.1 TEST 1)
+    0xd7, 0x5a, 0x98, 0x01, 0x82, 0xb1, 0x0a, 0xb7, 0xd5, 0x4b, 0xfe, 0xd3, 0xc9, 0x64, 0x07, 0x3a,
+    0x0e, 0xe1, 0x72, 0xf3, 0xda, 0xa6, 0x23, 0x25, 0xaf, 0x02, 0x1a, 0x68, 0xf7, 0x07, 0x51, 0x1a};
+static __constant__ unsigned char kTestMessage[12] = {'t', 'e', 's', 't', ' ', 'm', 'e', 's', 's', 'a', 'g', 'e'};
+
+enum : unsigned char { F_TEST_MESSAGE = 1, F_RFC = 2, F_BAD_RANGE = 4 };
+
+FEC_DEV void ld8(u32 q[8], const u32* __restrict__ p) {
+  const uint4* v = reinterpret_cast<const uint4*>(p);
+  const uint4 a = v[0], b = v[1];
+  q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w;
+  q[4] = b.x; q[5] = b.y; q[6] = b.z; q[7] = b.w;
+}
+FEC_DEV void st8(u32* __restrict__ p, const u32 q[8]) {
+  uint4* v = reinterpret_cast<uint4*>(p);
+  v[0] = make_uint4(q[0], q[1], q[2], q[3]);
+  v[1] = make_uint4(q[4], q[5], q[6], q[7]);
+}
+FEC_DEV ed::sc4 sc_of_words(const u32 w[8]) {
+  ed::sc4 s;
+  FEC_UNROLL for (int i = 0; i < 4; ++i) s.l[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
+  return s;
+}
+FEC_DEV void words_of_sc(const ed::sc4& s, u32 w[8]) {
+  FEC_UNROLL for (int i = 0; i < 4; ++i) {
+    w[2 * i] = (u32)s.l[i];
+    w[2 * i + 1] = (u32)(s.l[i] >> 32);
+  }
+}
+// The trait Scalar::from_bytes (ed25519.rs:1142-1162) of digest bytes [32 q, 32 q + 32): big-endian, so limb i is
+// digest word 4 q + 3 - i.
+FEC_DEV ed::sc4 scalar_be(const sha512::state& h, int q) {
+  ed::sc4 s;
+  FEC_UNROLL for (int i = 0; i < 4; ++i) s.l[i] = h.h[4 * q + 3 - i];
+  return s;
+}
+// Element i's message range; false (and nothing read) where it is not inside [0, msg_len)
+FEC_DEV bool msg_range(const u64* __restrict__ off, u64 msg_len, size_t i, u64& lo, u64& len) {
+  const u64 a = off[i], b = off[i + 1];
+  const bool ok = a <= b && b <= msg_len;
+  lo = ok ? a : 0;
+  len = ok ? b - a : 0;
+  return ok;
+}
+FEC_DEV bool is_test_message(const unsigned char* m, u64 len) {   // msg == b"test message"
+  if (len != 12) return false;
+  bool eq = true;
+  for (int k = 0; k < 12; ++k) eq = eq && m[k] == kTestMessage[k];
+  return eq;
+}
+// Point::to_bytes -> [u8; 33] (ed25519.rs:1505-1525) of an affine point: the prefix byte and reduce(x) (to_bytes,
+// little-endian)
+FEC_DEV u32 prefix_byte(const fe& y, bool inf) { return inf ? 0u : 2u + ((ed::reduce(y).w[7] >> 24) & 1u); }
+FEC_DEV u32 byte_of(const fe& v, int k) { return (v.w[k >> 2] >> (8 * (k & 3))) & 0xFFu; }
+// to_affine with the panic test: a zero z of a point that is not the identity is an unwrap on None (ed25519.rs:1805)
+FEC_DEV bool affine_of(const u32* __restrict__ p, fe& x, fe& y, bool& panics) {
+  ed::pt q;
+  ld8(q.x.w, p);
+  ld8(q.y.w, p + 8);
+  ld8(q.z.w, p + 16);
+  ld8(q.t.w, p + 24);
+  panics = !lane_of(ed::is_identity(q)) && lane_of(fe_is_zero(q.z));
+  return lane_of(ed::to_affine(q, x, y));
+}
+
+// mode: EDDSA_MODE_* (kernels.hpp).  scal: a at [0, n), r at [n, 2n) (derive: a only), 8 words each.
+__global__ __launch_bounds__(TPB) void k_eddsa_sign_pre(EddsaSignIo io, u32* __restrict__ scal, unsigned char* __restrict__ flags,
+                                                        size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  u32 kw[8];
+  ld8(kw, io.keys + i * 8);
+  u32 pre[8];
+  u32 key0;
+  if (io.mode == EDDSA_MODE_GENERIC) {   // the trait to_bytes(sk) (ed25519.rs:1164-1175): the raw limbs big-endian
+    FEC_UNROLL for (int j = 0; j < 8; ++j) pre[j] = kw[7 - j];
+    key0 = kw[7] >> 24;
+  } else {                               // the 32 key bytes as given
+    FEC_UNROLL for (int j = 0; j < 8; ++j) pre[j] = sha512::bswap(kw[j]);
+    key0 = kw[0] & 0xFFu;
+  }
+  unsigned char f = 0;
+  u64 lo = 0, len = 0;
+  const unsigned char* m = nullptr;
+  if (io.mode == EDDSA_MODE_DERIVE) {
+    if (key0 == 0x9d) f |= F_RFC;                                               // 452
+  } else {
+    if (!msg_range(io.off, io.msg_len, i, lo, len)) f |= F_BAD_RANGE;
+    m = len ? io.msgs + lo : nullptr;
+    if (is_test_message(m, len)) f |= F_TEST_MESSAGE;                          // 269, 45
+    if (!(f & F_BAD_RANGE) && len == 0 && key0 == 0x9d) f |= F_RFC;             // 281, 55
+  }
+  ed::sc4 a = {{0, 0, 0, 0}}, r = {{0, 0, 0, 0}};
+  if (f == 0) {   // (special cases and bad ranges multiply zero: the identity, at no cost, and their outputs are replaced)
+    const sha512::state h = sha512::hash_prefixed<8>(pre, 32, nullptr, 0);     // 293-296
+    a = scalar_be(h, 1);                                                        // 302-305 with the clamp of 298-300:
+    a.l[3] &= 0xF8FFFFFFFFFFFFFFULL;                                            //   scalar_bytes[0] &= 248 (top byte)
+    a.l[0] = (a.l[0] & ~0x80ULL) | 0x40ULL;                                     //   [31] &= 127, |= 64 (bottom byte)
+    if (io.mode != EDDSA_MODE_DERIVE) {
+      u32 nonce[8];                                                             // h[0..32]
+      FEC_UNROLL for (int k = 0; k < 4; ++k) {
+        nonce[2 * k] = (u32)(h.h[k] >> 32);
+        nonce[2 * k + 1] = (u32)h.h[k];
+      }
+      r = scalar_be(sha512::hash_prefixed<8>(nonce, 32, m, len), 0);            // 313-322
+    }
+  }
+  u32 w[8];
+  words_of_sc(a, w);
+  st8(scal + i * 8, w);
+  if (io.mode != EDDSA_MODE_DERIVE) {
+    words_of_sc(r, w);
+    st8(scal + (n + i) * 8, w);
+  }
+  flags[i] = f;
+}
+
+// pts: multiply(G, scal[j]) for every scalar of the pre pass (32 words each)
+__global__ __launch_bounds__(TPB) void k_eddsa_sign_finish(EddsaSignIo io, const u32* __restrict__ scal, const u32* __restrict__ pts,
+                                                           const unsigned char* __restrict__ flags, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const unsigned char f = flags[i];
+  fe xa, ya;
+  bool panic_a;
+  const bool inf_a = affine_of(pts + i * 32, xa, ya, panic_a);                 // 308-309
+  const u32 pa = prefix_byte(ya, inf_a);
+  const fe xab = ed::reduce(xa);
+  if (io.mode == EDDSA_MODE_DERIVE) {
+    u32 o[8];
+    const bool zero = panic_a;
+    FEC_UNROLL for (int j = 0; j < 8; ++j) {   // A33[0..32]: the prefix byte, then x's bytes 0..30
+      u32 v = (xab.w[j] << 8) | (j ? (xab.w[j - 1] >> 24) : pa);
+      if (f & F_RFC) v = (u32)kRfcPk[4 * j] | ((u32)kRfcPk[4 * j + 1] << 8) | ((u32)kRfcPk[4 * j + 2] << 16) | ((u32)kRfcPk[4 * j + 3] << 24);
+      o[j] = zero && !(f & F_RFC) ? 0u : v;
+    }
+    st8(io.out + i * 8, o);
+    io.status[i] = (f & F_RFC) ? 0 : (panic_a ? 1 : 0);
+    return;
+  }
+  fe xr, yr;
+  bool panic_r;
+  const bool inf_r = affine_of(pts + (n + i) * 32, xr, yr, panic_r);           // 325-326
+  const u32 pr = prefix_byte(yr, inf_r);
+  const fe xrb = ed::reduce(xr);
+  u64 lo = 0, len = 0;
+  const bool ok = msg_range(io.off, io.msg_len, i, lo, len);
+  const unsigned char* m = ok && len ? io.msgs + lo : nullptr;
+  u32 pre[17];   // R33 || A33, big-endian words (bytes 66, 67 zero)
+  FEC_UNROLL for (int j = 0; j < 17; ++j) {
+    u32 v = 0;
+    FEC_UNROLL for (int b = 0; b < 4; ++b) {
+      const int t = 4 * j + b;
+      const u32 byte = t == 0 ? pr : t <= 32 ? byte_of(xrb, t - 1) : t == 33 ? pa : t <= 65 ? byte_of(xab, t - 34) : 0u;
+      v = (v << 8) | byte;
+    }
+    pre[j] = v;
+  }
+  ed::sc4 s = {{0, 0, 0, 0}};
+  bool ovf = false;
+  const bool panics = panic_a || panic_r;
+  if (f == 0 && !panics) {
+    const ed::sc4 k = scalar_be(sha512::hash_prefixed<17>(pre, 66, m, len), 0);   // 329-337
+    u32 w[8];
+    ld8(w, scal + i * 8);
+    const ed::sc4 a = sc_of_words(w);
+    ld8(w, scal + (n + i) * 8);
+    const ed::sc4 r = sc_of_words(w);
+    s = ed::sc_add(r, ed::sc_mul_release(k, a, ovf));                          // 340 (Add 1193-1239, Mul 1256-1376)
+  }
+  const bool special = (f & (F_TEST_MESSAGE | F_RFC)) != 0;
+  const bool zero = (f & F_BAD_RANGE) || (!special && panics);
+  io.status[i] = (f & F_BAD_RANGE) ? 4 : special ? 0 : panics ? 1 : (ovf ? 2 : 0);
+  if (io.mode == EDDSA_MODE_SIGN) {
+    u32 o[16];
+    const ed::sc4 sr = ed::sc_ge_order(s) ? ed::sc_sub_order(s) : s;           // inherent to_bytes: reduce (744-762)
+    FEC_UNROLL for (int j = 0; j < 8; ++j) o[j] = (xrb.w[j] << 8) | (j ? (xrb.w[j - 1] >> 24) : pr);   // R33[0..32]
+    FEC_UNROLL for (int j = 0; j < 4; ++j) {
+      o[8 + 2 * j] = (u32)sr.l[j];
+      o[9 + 2 * j] = (u32)(sr.l[j] >> 32);
+    }
+    if (f & F_TEST_MESSAGE) {                                                   // 270-278: bytes 0..63
+      FEC_UNROLL for (int j = 0; j < 16; ++j) o[j] = (4u * j) | ((4u * j + 1) << 8) | ((4u * j + 2) << 16) | ((4u * j + 3) << 24);
+    } else if (f & F_RFC) {                                                     // 281-288
+      FEC_UNROLL for (int j = 0; j < 16; ++j)
+        o[j] = (u32)kRfcSig[4 * j] | ((u32)kRfcSig[4 * j + 1] << 8) | ((u32)kRfcSig[4 * j + 2] << 16) | ((u32)kRfcSig[4 * j + 3] << 24);
+    } else if (zero) {
+      FEC_UNROLL for (int j = 0; j < 16; ++j) o[j] = 0;
+    }
+    st8(io.out + i * 16, o);
+    st8(io.out + i * 16 + 8, o + 8);
+    return;
+  }
+  // EDDSA_MODE_GENERIC: Signature { r: to_affine(R), s }; the special cases (to_affine(generator()), one())
+  fe ox = xr, oy = yr;
+  bool oinf = inf_r;
+  if (special) {
+    fe gx, gy;
+    bool gpanic;
+    oinf = affine_of(io.gen, gx, gy, gpanic);
+    ox = gx;
+    oy = gy;
+    s.l[0] = 1;
+    s.l[1] = s.l[2] = s.l[3] = 0;
+  }
+  if (zero) {
+    ox = fe_zero();
+    oy = fe_zero();
+    oinf = false;
+    s.l[0] = s.l[1] = s.l[2] = s.l[3] = 0;
+  }
+  st8(io.out + i * 16, ox.w);
+  st8(io.out + i * 16 + 8, oy.w);
+  io.r_inf[i] = oinf ? 1 : 0;
+  u32 w[8];
+  words_of_sc(s, w);
+  st8(io.s + i * 8, w);
+}
+
+__global__ __launch_bounds__(TPB) void k_sha512(const unsigned char* __restrict__ msgs, const u64* __restrict__ off, u64 msg_len,
+                                                u32* __restrict__ out, unsigned char* __restrict__ status, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  u64 lo, len;
+  const bool ok = msg_range(off, msg_len, i, lo, len);
+  u32 o[16];
+  if (ok) {
+    const u32 none[1] = {0};
+    sha512::digest_words(sha512::hash_prefixed<1>(none, 0, len ? msgs + lo : nullptr, len), o);
+  } else {
+    FEC_UNROLL for (int j = 0; j < 16; ++j) o[j] = 0;
+  }
+  st8(out + i * 16, o);
+  st8(out + i * 16 + 8, o + 8);
+  if (status) status[i] = ok ? 0 : 4;
+}
+
+unsigned grid(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
+
+}  // namespace
+
+void eddsa_sign_pre_launch(const EddsaSignIo& io, u32* scal, unsigned char* flags, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_eddsa_sign_pre, dim3(grid(n)), dim3(TPB), 0, s, io, scal, flags, n);
+}
+void eddsa_sign_finish_launch(const EddsaSignIo& io, const u32* scal, const u32* pts, const unsigned char* flags, size_t n,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(k_eddsa_sign_finish, dim3(grid(n)), dim3(TPB), 0, s, io, scal, pts, flags, n);
+}
+void sha512_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
+                   hipStream_t s) {
+  hipLaunchKernelGGL(k_sha512, dim3(grid(n)), dim3(TPB), 0, s, msgs, off, msg_len, out, status, n);
+}
+
+}  // namespace fecgpu

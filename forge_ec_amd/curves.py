@@ -415,6 +415,63 @@ class Context:
         _check(self._lib.fec_x25519(self._h, _ptr(s), _ptr(q), _ptr(out), s.shape[0]), "fec_x25519")
         return out
 
+    @staticmethod
+    def _messages(msgs):
+        """A list of byte strings -> (the concatenated bytes, the n + 1 offsets) of include/fecgpu.h's message layout."""
+        msgs = [bytes(m) for m in msgs]
+        off = np.zeros(len(msgs) + 1, dtype=np.uint64)
+        np.cumsum([len(m) for m in msgs], out=off[1:])
+        buf = np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8).copy()
+        return buf, off, int(off[-1])
+
+    def ed25519_sign(self, private_keys, msgs):
+        """Ed25519Signature::sign per element (eddsa.rs:267-356), SHA-512 included: private_keys (n, 32) uint8, msgs a
+        list of n byte strings.  Returns (sig (n, 64) uint8, status (n,) uint8: 0, 1 the reference panics, 2 a debug
+        build panics).  The reference's signatures, not RFC 8032 -- see include/fecgpu.h."""
+        k = np.ascontiguousarray(np.asarray(private_keys, dtype=np.uint8)).reshape(-1, 32)
+        buf, off, total = self._messages(msgs)
+        n = k.shape[0]
+        if len(off) != n + 1:
+            raise ValueError("inputs differ in length")
+        sig = np.zeros((n, 64), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_ed25519_sign(self._h, _ptr(k), _ptr(buf), _ptr(off), total, _ptr(sig), _ptr(st), n), "fec_ed25519_sign")
+        return sig, st
+
+    def ed25519_derive_public_key(self, private_keys):
+        """Ed25519Signature::derive_public_key per element (eddsa.rs:450-508): (n, 32) uint8 -> (pk (n, 32) uint8,
+        status (n,) uint8)."""
+        k = np.ascontiguousarray(np.asarray(private_keys, dtype=np.uint8)).reshape(-1, 32)
+        pk = np.zeros_like(k)
+        st = np.zeros(k.shape[0], dtype=np.uint8)
+        _check(self._lib.fec_ed25519_derive_public_key(self._h, _ptr(k), _ptr(pk), _ptr(st), k.shape[0]),
+               "fec_ed25519_derive_public_key")
+        return pk, st
+
+    def eddsa_sign_ed25519(self, sk, msgs):
+        """EdDsa::<Ed25519, Sha512>::sign per element (eddsa.rs:43-154): sk (n, 4) raw Scalar limbs, msgs a list of n
+        byte strings.  Returns (r_xy (n, 8), r_inf (n,), s (n, 4), status (n,))."""
+        k = _u64(sk, 4)
+        buf, off, total = self._messages(msgs)
+        n = k.shape[0]
+        if len(off) != n + 1:
+            raise ValueError("inputs differ in length")
+        r_xy = np.zeros((n, 8), dtype=np.uint64)
+        r_inf = np.zeros(n, dtype=np.uint8)
+        s = np.zeros((n, 4), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_eddsa_sign_ed25519(self._h, _ptr(k), _ptr(buf), _ptr(off), total, _ptr(r_xy), _ptr(r_inf), _ptr(s),
+                                                _ptr(st), n), "fec_eddsa_sign_ed25519")
+        return r_xy, r_inf, s, st
+
+    def sha512(self, msgs):
+        """SHA-512 of each byte string in msgs on the GPU: (n, 64) uint8."""
+        buf, off, total = self._messages(msgs)
+        n = len(off) - 1
+        out = np.zeros((n, 64), dtype=np.uint8)
+        _check(self._lib.fec_sha512(self._h, _ptr(buf), _ptr(off), total, _ptr(out), n), "fec_sha512")
+        return out
+
     def curve25519_mul(self, scalars, points):
         """Curve25519::multiply per element (curve25519.rs:1922-1955): scalars (n, 4) raw Scalar limbs, points (n, 8)
         ProjectivePoint X limbs then Z limbs; returns (n, 8) likewise."""
@@ -516,6 +573,21 @@ class Context:
 
     def curve25519_mul_dev(self, d_scalars, d_points, d_out, n, stream=None):
         _check(self._lib.fec_curve25519_mul_dev(self._h, d_scalars, d_points, d_out, n, stream), "fec_curve25519_mul_dev")
+
+    def ed25519_sign_dev(self, d_private_keys, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream=None):
+        _check(self._lib.fec_ed25519_sign_dev(self._h, d_private_keys, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream),
+               "fec_ed25519_sign_dev")
+
+    def ed25519_derive_public_key_dev(self, d_private_keys, d_public_keys, d_status, n, stream=None):
+        _check(self._lib.fec_ed25519_derive_public_key_dev(self._h, d_private_keys, d_public_keys, d_status, n, stream),
+               "fec_ed25519_derive_public_key_dev")
+
+    def eddsa_sign_ed25519_dev(self, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n, stream=None):
+        _check(self._lib.fec_eddsa_sign_ed25519_dev(self._h, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n,
+                                                    stream), "fec_eddsa_sign_ed25519_dev")
+
+    def sha512_dev(self, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream=None):
+        _check(self._lib.fec_sha512_dev(self._h, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream), "fec_sha512_dev")
 
     def ecdsa_sign_dev(self, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream=None):
         _check(self._lib.fec_ecdsa_sign_dev(self._h, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream), "fec_ecdsa_sign_dev")

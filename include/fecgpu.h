@@ -34,6 +34,11 @@
  *                         p256.rs:2281-2312)
  *   fec_ecdsa_sign        Ecdsa::<C, D>::sign for secp256k1 / P-256 after the hash and the RFC 6979 nonce
  *                         (ecdsa.rs:45-71, 98-211; scalar Sub secp256k1.rs:2380-2408, p256.rs:1377-1408)
+ *   fec_ed25519_sign      Ed25519Signature::sign with SHA-512, hash included (forge-ec-signature/src/eddsa.rs:267-356)
+ *   fec_ed25519_derive_public_key   Ed25519Signature::derive_public_key (eddsa.rs:450-508)
+ *   fec_eddsa_sign_ed25519   EdDsa::<Ed25519, Sha512>::sign (eddsa.rs:43-154; scalar Add ed25519.rs:1193-1239, Mul
+ *                         1256-1376 as the release profile runs it)
+ *   fec_sha512            SHA-512 per message (FIPS 180-4, the sha2 crate the reference signs with)
  *   fec_ecdsa_batch_verify   Ecdsa::<C, D>::batch_verify for secp256k1 / P-256 (ecdsa.rs:287-391; scalar Add
  *                         secp256k1.rs:2358-2378, p256.rs:1352-1375)
  *   fec_eddsa_verify_ed25519   Eddsa::<Ed25519, D>::verify / Ed25519::verify after the hash and the decoding
@@ -476,6 +481,56 @@ int fec_curve25519_mul_dev(fec_ctx* ctx, const uint64_t* d_scalars, const uint64
                            void* stream);
 int fec_curve25519_field_op(fec_ctx* ctx, fec_field_opcode op, const uint64_t* a /* n*4 */, const uint64_t* b /* n*4 */,
                             uint64_t* out /* n*4 */, size_t n);
+
+/* ---- EdDSA signing for Ed25519 with SHA-512 (forge-ec-signature/src/eddsa.rs), parity mode ----
+ * The reference's signatures, bit for bit, hash included: NOT RFC 8032 Ed25519.  The reference reads the clamped
+ * h[32..64], r and k as BIG-endian numbers with no reduction (the trait Scalar::from_bytes, ed25519.rs:1142-1162), hashes
+ * the 33-byte PointAffine::to_bytes of R and A (1505-1525: prefix 0x02 / 0x03 by bit 248 of y, then x little-endian),
+ * computes s = r + k * a with its own scalar Add and Mul, and keeps its special cases: "test message", and an empty
+ * message under a key whose first byte is 0x9d (derive_public_key: any key whose first byte is 0x9d).  NOT
+ * constant-time: the fixed-base kernel sorts its scalars by popcount.
+ * Messages: message i is msgs[msg_off[i], msg_off[i+1]); msg_off holds n + 1 values with msg_off[0] = 0, non-decreasing,
+ * msg_off[n] = msg_len; msgs has any alignment and may be NULL when msg_len is 0.  The host forms check this and return
+ * FEC_E_ARG; the _dev forms cannot, so each element checks its own range against msg_len: a bad range gets status 4
+ * and zero outputs, and nothing outside [msgs, msgs + msg_len) is read (loads are 4-byte aligned dwords that hold at
+ * least one byte of the message).
+ * status[i]: 0; 1 the reference panics there (to_affine unwraps the inverse of a zero z, ed25519.rs:1805; outputs 0);
+ * 2 only a debug build panics there (a u128 column sum of the scalar Mul passes 2^128; the release build wraps and the
+ * output is the release value); 4 bad message range (_dev forms only).
+ * SECRETS: the private keys, h, the nonce, a, r and the points A and R.  The host forms clear their device staging of
+ * the keys and of the outputs and the stream scratch (a, r, A, R) on every way out; h and the nonce never leave the
+ * registers.  The _dev forms leave every buffer to the caller, as fec_ecdsa_sign_dev does (the stream's scratch keeps a,
+ * r, A and R until the ctx is wiped, fec_ctx_wipe, or destroyed).  The _dev forms take 16-byte aligned keys and
+ * outputs and an 8-byte aligned d_msg_off, and return FEC_E_UNSUPPORTED on a multi-device ctx; the host forms chunk by
+ * fec_ctx_set_chunk and shard over a multi-device ctx.
+ * fec_ed25519_sign     sig[i] = Ed25519Signature::sign(private_keys[i], msg_i) (eddsa.rs:267-356), 64 bytes: R33[0..32]
+ *                  then the inherent Scalar::to_bytes of s (ed25519.rs:767-781: one conditional subtraction of l,
+ *                  little-endian).
+ * fec_ed25519_derive_public_key   public_keys[i] = Ed25519Signature::derive_public_key(private_keys[i]) (450-508):
+ *                  A33[0..32]; status 0 or 1.
+ * fec_eddsa_sign_ed25519   EdDsa::<Ed25519, Sha512>::sign(sk[i], msg_i) (43-154): sk raw Scalar limbs (hashed as the
+ *                  trait to_bytes, big-endian); returns Signature { r, s }: r_xy the affine R (x limbs then y limbs),
+ *                  r_inf 1 for the identity, s raw limbs (unreduced, as the reference returns it); the special cases
+ *                  return (to_affine(generator()), one()).
+ * fec_sha512       digests[i] = SHA-512(msg_i), 64 bytes (a parity hook for the hash the signers run; _dev: d_status
+ *                  may be NULL, else 0 or 4 per message). */
+int fec_ed25519_sign(fec_ctx* ctx, const uint8_t* private_keys /* n*32 */, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */,
+                     size_t msg_len, uint8_t* sig /* n*64 */, uint8_t* status /* n */, size_t n);
+int fec_ed25519_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                         size_t msg_len, uint8_t* d_sig, uint8_t* d_status, size_t n, void* stream);
+int fec_ed25519_derive_public_key(fec_ctx* ctx, const uint8_t* private_keys /* n*32 */, uint8_t* public_keys /* n*32 */,
+                                  uint8_t* status /* n */, size_t n);
+int fec_ed25519_derive_public_key_dev(fec_ctx* ctx, const uint8_t* d_private_keys, uint8_t* d_public_keys, uint8_t* d_status,
+                                      size_t n, void* stream);
+int fec_eddsa_sign_ed25519(fec_ctx* ctx, const uint64_t* sk /* n*4 */, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */,
+                           size_t msg_len, uint64_t* r_xy /* n*8 */, uint8_t* r_inf /* n */, uint64_t* s /* n*4 */,
+                           uint8_t* status /* n */, size_t n);
+int fec_eddsa_sign_ed25519_dev(fec_ctx* ctx, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                               uint64_t* d_r_xy, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_status, size_t n, void* stream);
+int fec_sha512(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len, uint8_t* digests /* n*64 */,
+               size_t n);
+int fec_sha512_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
+                   uint8_t* d_status, size_t n, void* stream);
 
 /* Host-pointer batches are processed as a two-lane pipeline of `elements`-sized chunks (default
  * 2^18): copies of one chunk overlap the kernel of the other, and device staging memory is bounded

@@ -547,6 +547,76 @@ inline std::vector<Verify> verify(GpuContext& ctx, const std::vector<AffinePoint
                                  reinterpret_cast<const uint64_t*>(challenges.data()), st.data(), n));
   return detail::statuses(st);
 }
+
+// ---- signing with SHA-512 on the GPU (fec_ed25519_sign and its siblings): the reference's signatures, not RFC 8032,
+// and not constant-time -- see fecgpu.h.  status[i]: 0, 1 the reference panics there, 2 only a debug build does.
+namespace detail {
+struct Messages {
+  std::vector<uint8_t> bytes;
+  std::vector<uint64_t> off;
+  explicit Messages(const std::vector<std::string>& msgs) : off(msgs.size() + 1, 0) {
+    for (size_t i = 0; i < msgs.size(); ++i) {
+      bytes.insert(bytes.end(), msgs[i].begin(), msgs[i].end());
+      off[i + 1] = bytes.size();
+    }
+  }
+};
+}  // namespace detail
+using Bytes32 = std::array<uint8_t, 32>;
+using Bytes64 = std::array<uint8_t, 64>;
+// Ed25519Signature::sign(private_keys[i], msgs[i]) (eddsa.rs:267-356)
+inline std::vector<Bytes64> ed25519_sign(GpuContext& ctx, const std::vector<Bytes32>& private_keys, const std::vector<std::string>& msgs,
+                                         std::vector<uint8_t>* status = nullptr) {
+  const size_t n = private_keys.size();
+  if (msgs.size() != n) throw Error(FEC_E_ARG);
+  const detail::Messages m(msgs);
+  std::vector<Bytes64> sig(n);
+  std::vector<uint8_t> st(n);
+  check(fec_ed25519_sign(ctx.raw(), reinterpret_cast<const uint8_t*>(private_keys.data()), m.bytes.data(), m.off.data(),
+                         m.bytes.size(), reinterpret_cast<uint8_t*>(sig.data()), st.data(), n));
+  if (status) *status = st;
+  return sig;
+}
+// Ed25519Signature::derive_public_key(private_keys[i]) (eddsa.rs:450-508)
+inline std::vector<Bytes32> ed25519_derive_public_key(GpuContext& ctx, const std::vector<Bytes32>& private_keys,
+                                                      std::vector<uint8_t>* status = nullptr) {
+  const size_t n = private_keys.size();
+  std::vector<Bytes32> pk(n);
+  std::vector<uint8_t> st(n);
+  check(fec_ed25519_derive_public_key(ctx.raw(), reinterpret_cast<const uint8_t*>(private_keys.data()),
+                                      reinterpret_cast<uint8_t*>(pk.data()), st.data(), n));
+  if (status) *status = st;
+  return pk;
+}
+// EdDsa::<Ed25519, Sha512>::sign(sks[i], msgs[i]) (eddsa.rs:43-154)
+inline std::vector<Signature> sign(GpuContext& ctx, const std::vector<Scalar<FEC_ED25519>>& sks, const std::vector<std::string>& msgs,
+                                   std::vector<uint8_t>* status = nullptr) {
+  const size_t n = sks.size();
+  if (msgs.size() != n) throw Error(FEC_E_ARG);
+  const detail::Messages m(msgs);
+  std::vector<uint64_t> rxy(n * 8), s(n * 4);
+  std::vector<uint8_t> rinf(n), st(n);
+  check(fec_eddsa_sign_ed25519(ctx.raw(), reinterpret_cast<const uint64_t*>(sks.data()), m.bytes.data(), m.off.data(), m.bytes.size(),
+                               rxy.data(), rinf.data(), s.data(), st.data(), n));
+  std::vector<Signature> out(n);
+  for (size_t i = 0; i < n; ++i) {
+    for (int l = 0; l < 4; ++l) {
+      out[i].r.x_.raw[l] = rxy[i * 8 + l];
+      out[i].r.y_.raw[l] = rxy[i * 8 + 4 + l];
+      out[i].s.raw[l] = s[i * 4 + l];
+    }
+    out[i].r.infinity = rinf[i] != 0;
+  }
+  if (status) *status = st;
+  return out;
+}
+// SHA-512 of each message (fec_sha512)
+inline std::vector<Bytes64> sha512(GpuContext& ctx, const std::vector<std::string>& msgs) {
+  const detail::Messages m(msgs);
+  std::vector<Bytes64> out(msgs.size());
+  check(fec_sha512(ctx.raw(), m.bytes.data(), m.off.data(), m.bytes.size(), reinterpret_cast<uint8_t*>(out.data()), msgs.size()));
+  return out;
+}
 }  // namespace eddsa
 
 namespace encoding {

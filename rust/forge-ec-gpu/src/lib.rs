@@ -78,6 +78,14 @@ extern "C" {
     fn fec_curve25519_mul(ctx: *mut FecCtx, scalars: *const u64, points: *const u64, out: *mut u64, n: usize) -> c_int;
     fn fec_curve25519_mul_dev(ctx: *mut FecCtx, d_scalars: *const u64, d_points: *const u64, d_out: *mut u64, n: usize, stream: *mut c_void) -> c_int;
     fn fec_curve25519_field_op(ctx: *mut FecCtx, op: c_int, a: *const u64, b: *const u64, out: *mut u64, n: usize) -> c_int;
+    fn fec_ed25519_sign(ctx: *mut FecCtx, private_keys: *const u8, msgs: *const u8, msg_off: *const u64, msg_len: usize, sig: *mut u8, status: *mut u8, n: usize) -> c_int;
+    fn fec_ed25519_sign_dev(ctx: *mut FecCtx, d_private_keys: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_sig: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_ed25519_derive_public_key(ctx: *mut FecCtx, private_keys: *const u8, public_keys: *mut u8, status: *mut u8, n: usize) -> c_int;
+    fn fec_ed25519_derive_public_key_dev(ctx: *mut FecCtx, d_private_keys: *const u8, d_public_keys: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_eddsa_sign_ed25519(ctx: *mut FecCtx, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, r_xy: *mut u64, r_inf: *mut u8, s: *mut u64, status: *mut u8, n: usize) -> c_int;
+    fn fec_eddsa_sign_ed25519_dev(ctx: *mut FecCtx, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *mut u64, d_r_inf: *mut u8, d_s: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_sha512(ctx: *mut FecCtx, msgs: *const u8, msg_off: *const u64, msg_len: usize, digests: *mut u8, n: usize) -> c_int;
+    fn fec_sha512_dev(ctx: *mut FecCtx, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_digests: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_ctx_set_chunk(ctx: *mut FecCtx, elements: usize) -> c_int;
     fn fec_ctx_set_timing(ctx: *mut FecCtx, enabled: c_int) -> c_int;
     fn fec_ctx_last_kernel_ms(ctx: *mut FecCtx, ms: *mut c_float, kernel_name: *mut *const c_char) -> c_int;
@@ -584,6 +592,85 @@ pub fn x25519_batch(ctx: &mut GpuContext, scalars: &[[u8; 32]], u: &[[u8; 32]]) 
     Ok(out)
 }
 
+/// The message layout of include/fecgpu.h: the concatenated bytes and the n + 1 offsets.
+fn pack_messages(msgs: &[&[u8]]) -> (Vec<u8>, Vec<u64>) {
+    let mut off = Vec::with_capacity(msgs.len() + 1);
+    off.push(0u64);
+    let mut buf = Vec::new();
+    for m in msgs {
+        buf.extend_from_slice(m);
+        off.push(buf.len() as u64);
+    }
+    (buf, off)
+}
+
+/// What the reference does with one element of the EdDSA signers where it does not return normally: it panics
+/// (`Panics`), or only a debug build would (`Ok` with the release value and `debug_build_panics`).
+fn eddsa_status(st: u8) -> Result<bool> {
+    match st {
+        0 => Ok(false),
+        2 => Ok(true),
+        _ => Err(Error::GenericError),
+    }
+}
+
+/// `Ed25519Signature::sign(private_keys[i], msgs[i])` per element (`forge-ec-signature/src/eddsa.rs:267-356`), SHA-512
+/// included, bit for bit: the reference's signatures, not RFC 8032, and not constant-time (see `fec_ed25519_sign` in
+/// include/fecgpu.h).  Each element is `Ok((signature, debug_build_panics))`, or `Err(GenericError)` where the
+/// reference itself panics.  The library clears its device copies of the keys and of the intermediate scalars.
+pub fn ed25519_sign_batch(ctx: &mut GpuContext, private_keys: &[[u8; 32]], msgs: &[&[u8]]) -> Result<Vec<Result<([u8; 64], bool)>>> {
+    let n = private_keys.len();
+    if msgs.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let (buf, off) = pack_messages(msgs);
+    let (mut sig, mut status) = (vec![[0u8; 64]; n], vec![0u8; n]);
+    // SAFETY: keys n * 32 bytes, off n + 1 offsets into buf, sig n * 64 bytes, status n.
+    check(unsafe { fec_ed25519_sign(ctx.raw, private_keys.as_ptr() as *const u8, buf.as_ptr(), off.as_ptr(), buf.len(), sig.as_mut_ptr() as *mut u8, status.as_mut_ptr(), n) })?;
+    Ok((0..n).map(|i| eddsa_status(status[i]).map(|d| (sig[i], d))).collect())
+}
+
+/// `Ed25519Signature::derive_public_key(private_keys[i])` per element (`forge-ec-signature/src/eddsa.rs:450-508`);
+/// `Err(GenericError)` where the reference panics.
+pub fn ed25519_derive_public_key_batch(ctx: &mut GpuContext, private_keys: &[[u8; 32]]) -> Result<Vec<Result<[u8; 32]>>> {
+    let n = private_keys.len();
+    let (mut pk, mut status) = (vec![[0u8; 32]; n], vec![0u8; n]);
+    // SAFETY: keys and pk n * 32 bytes, status n.
+    check(unsafe { fec_ed25519_derive_public_key(ctx.raw, private_keys.as_ptr() as *const u8, pk.as_mut_ptr() as *mut u8, status.as_mut_ptr(), n) })?;
+    Ok((0..n).map(|i| eddsa_status(status[i]).map(|_| pk[i])).collect())
+}
+
+/// `EdDsa::<Ed25519, Sha512>::sign(sks[i], msgs[i])` per element (`forge-ec-signature/src/eddsa.rs:43-154`):
+/// `Ok((Signature { r, s }, debug_build_panics))`, or `Err(GenericError)` where the reference panics.
+#[cfg(feature = "signature")]
+pub fn eddsa_sign_batch_ed25519(ctx: &mut GpuContext, sks: &[ed25519::Scalar], msgs: &[&[u8]]) -> Result<Vec<Result<(forge_ec_signature::eddsa::Signature<ed25519::Ed25519>, bool)>>> {
+    let n = sks.len();
+    if msgs.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let mut kk = pack_scalars::<ed25519::Ed25519>(sks);
+    let (buf, off) = pack_messages(msgs);
+    let (mut r_xy, mut r_inf, mut s, mut status) = (vec![0u64; 8 * n], vec![0u8; n], vec![0u64; 4 * n], vec![0u8; n]);
+    // SAFETY: every buffer holds n elements of the width the header states; off n + 1 offsets into buf.
+    let rc = check(unsafe { fec_eddsa_sign_ed25519(ctx.raw, kk.as_ptr(), buf.as_ptr(), off.as_ptr(), buf.len(), r_xy.as_mut_ptr(), r_inf.as_mut_ptr(), s.as_mut_ptr(), status.as_mut_ptr(), n) });
+    kk.iter_mut().for_each(|w| *w = 0);
+    rc?;
+    Ok((0..n).map(|i| eddsa_status(status[i]).map(|d| (forge_ec_signature::eddsa::Signature {
+        r: <ed25519::Ed25519 as GpuCurve>::affine_from_limbs(&r_xy[8 * i..8 * i + 8], r_inf[i] != 0),
+        s: <ed25519::Ed25519 as GpuCurve>::scalar_from_limbs(limb4(&s, i)),
+    }, d))).collect())
+}
+
+/// SHA-512 of each message on the GPU (`fec_sha512`).
+pub fn sha512_batch(ctx: &mut GpuContext, msgs: &[&[u8]]) -> Result<Vec<[u8; 64]>> {
+    let n = msgs.len();
+    let (buf, off) = pack_messages(msgs);
+    let mut out = vec![[0u8; 64]; n];
+    // SAFETY: off holds n + 1 offsets into buf, out n * 64 bytes.
+    check(unsafe { fec_sha512(ctx.raw, buf.as_ptr(), off.as_ptr(), buf.len(), out.as_mut_ptr() as *mut u8, n) })?;
+    Ok(out)
+}
+
 /// `Curve25519::multiply(p, k)` per element (`forge-ec-curves/src/curve25519.rs:1922-1955`).  The reference keeps the
 /// coordinates of its `ProjectivePoint` private, so points cross as `(x, z)` field elements (`FieldElement::from_raw`
 /// / `to_raw`), exactly the values the reference holds, unreduced ones included.
@@ -877,6 +964,39 @@ pub mod dev {
     /// As [`batch_mul`]; the caller owns and clears every buffer.
     pub unsafe fn ecdsa_sign(ctx: &mut GpuContext, curve: c_int, d_sk: *const u64, d_digests: *const u8, d_k: *const u64, d_sig: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
         check(fec_ecdsa_sign_dev(ctx.raw, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream))
+    }
+
+    /// `fec_ed25519_sign_dev` (message i is `d_msgs[d_msg_off[i]..d_msg_off[i + 1]]`; a range outside
+    /// `0..msg_len` gets status 4 and zero output).
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn ed25519_sign(ctx: &mut GpuContext, d_private_keys: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_sig: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_ed25519_sign_dev(ctx.raw, d_private_keys, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream))
+    }
+
+    /// `fec_ed25519_derive_public_key_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn ed25519_derive_public_key(ctx: &mut GpuContext, d_private_keys: *const u8, d_public_keys: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_ed25519_derive_public_key_dev(ctx.raw, d_private_keys, d_public_keys, d_status, n, stream))
+    }
+
+    /// `fec_eddsa_sign_ed25519_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn eddsa_sign_ed25519(ctx: &mut GpuContext, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *mut u64, d_r_inf: *mut u8, d_s: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_eddsa_sign_ed25519_dev(ctx.raw, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n, stream))
+    }
+
+    /// `fec_sha512_dev` (`d_status` may be null).
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn sha512(ctx: &mut GpuContext, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_digests: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_sha512_dev(ctx.raw, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream))
     }
 
     /// `fec_schnorr_verify_dev`.
