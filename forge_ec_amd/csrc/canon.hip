@@ -229,13 +229,9 @@ int fec_canon_mul_base(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, u
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!scalars || !out_xy || !status))) return FEC_E_ARG;
   if (!canon_curve_ok(curve)) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {scalars, nullptr, nullptr, nullptr};
-  const size_t in_stride[4] = {32, 0, 0, 0};
-  void* const out[2] = {out_xy, status};
-  const size_t out_stride[2] = {64, 1};
-  return host_chunked(ctx, n, in, in_stride, out, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    return launch_canon_mul_base(ctx, curve, (const u64*)d[0], (u64*)o[0], (unsigned char*)o[1], cnt, nullptr);
+  const HostArray a[] = {input(scalars, 32), output(out_xy, 64), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_mul_base(c, curve, (const u64*)d[0], (u64*)d[1], (unsigned char*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -254,13 +250,9 @@ int fec_canon_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const 
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!scalars || !points_xy || !out_xy || !status))) return FEC_E_ARG;
   if (!canon_curve_ok(curve)) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {scalars, points_xy, nullptr, nullptr};
-  const size_t in_stride[4] = {32, 64, 0, 0};
-  void* const out[2] = {out_xy, status};
-  const size_t out_stride[2] = {64, 1};
-  return host_chunked(ctx, n, in, in_stride, out, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    return launch_canon_mul(ctx, curve, (const u64*)d[0], (const u64*)d[1], (u64*)o[0], (unsigned char*)o[1], cnt, nullptr);
+  const HostArray a[] = {input(scalars, 32), input(points_xy, 64), output(out_xy, 64), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_mul(c, curve, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], (unsigned char*)d[3], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -282,16 +274,11 @@ int fec_canon_double_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* u1, cons
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!u1 || !u2 || !points_xy || !out_xy || !status))) return FEC_E_ARG;
   if (!canon_curve_ok(curve)) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {u1, u2, points_xy, nullptr};
-  const size_t in_stride[4] = {32, 32, 64, 0};
-  void* const out[2] = {out_xy, status};
-  const size_t out_stride[2] = {64, 1};
-  return host_chunked(ctx, n, in, in_stride, out, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    int rc = launch_canon_mul_base(ctx, curve, (const u64*)d[0], (u64*)o[0], (unsigned char*)o[1], cnt, nullptr, false);
+  const HostArray a[] = {input(u1, 32), input(u2, 32), input(points_xy, 64), output(out_xy, 64), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    int rc = launch_canon_mul_base(c, curve, (const u64*)d[0], (u64*)d[3], (unsigned char*)d[4], m, s, false);
     if (rc != FEC_OK) return rc;
-    return launch_canon_mul(ctx, curve, (const u64*)d[1], (const u64*)d[2], (u64*)o[0], (unsigned char*)o[1], cnt, nullptr,
-                            true);
+    return launch_canon_mul(c, curve, (const u64*)d[1], (const u64*)d[2], (u64*)d[3], (unsigned char*)d[4], m, s, true);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -311,14 +298,10 @@ int fec_canon_ecdsa_verify(fec_ctx* ctx, fec_curve curve, const uint64_t* z, con
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!z || !r || !s || !pk_xy || !result))) return FEC_E_ARG;
   if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {z, r, s, pk_xy};
-  const size_t in_stride[4] = {32, 32, 32, 64};
-  void* const out[2] = {result, nullptr};
-  const size_t out_stride[2] = {1, 0};
-  return host_chunked(ctx, n, in, in_stride, out, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    return launch_canon_ecdsa_verify(ctx, curve, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
-                                     (unsigned char*)o[0], cnt, nullptr);
+  const HostArray a[] = {input(z, 32), input(r, 32), input(s, 32), input(pk_xy, 64), output(result, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
+    return launch_canon_ecdsa_verify(c, curve, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
+                                     (unsigned char*)d[4], m, st);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -335,14 +318,10 @@ int fec_canon_bip340_verify(fec_ctx* ctx, const uint64_t* pk_x, const uint64_t* 
                             const uint64_t* e, uint8_t* result, size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!pk_x || !r || !s || !e || !result))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {pk_x, r, s, e};
-  const size_t in_stride[4] = {32, 32, 32, 32};
-  void* const out[2] = {result, nullptr};
-  const size_t out_stride[2] = {1, 0};
-  return host_chunked(ctx, n, in, in_stride, out, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    return launch_canon_sig_verify(ctx, FEC_SECP256K1, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
-                                   (unsigned char*)o[0], cnt, nullptr);
+  const HostArray arr[] = {input(pk_x, 32), input(r, 32), input(s, 32), input(e, 32), output(result, 1)};
+  return host_call(ctx, n, arr, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
+    return launch_canon_sig_verify(c, FEC_SECP256K1, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
+                                   (unsigned char*)d[4], m, st);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -359,14 +338,10 @@ int fec_canon_eddsa_verify(fec_ctx* ctx, const uint64_t* a_enc, const uint64_t* 
                            const uint64_t* h, uint8_t* result, size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!a_enc || !r_enc || !s || !h || !result))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {a_enc, r_enc, s, h};
-  const size_t in_stride[4] = {32, 32, 32, 32};
-  void* const out[2] = {result, nullptr};
-  const size_t out_stride[2] = {1, 0};
-  return host_chunked(ctx, n, in, in_stride, out, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    return launch_canon_sig_verify(ctx, FEC_ED25519, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
-                                   (unsigned char*)o[0], cnt, nullptr);
+  const HostArray arr[] = {input(a_enc, 32), input(r_enc, 32), input(s, 32), input(h, 32), output(result, 1)};
+  return host_call(ctx, n, arr, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
+    return launch_canon_sig_verify(c, FEC_ED25519, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
+                                   (unsigned char*)d[4], m, st);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -375,18 +350,14 @@ int fec_canon_scalar_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || !canon_curve_ok(curve) || op < 0 || op > 1 || (n && (!a || !out))) return FEC_E_ARG;
   if (op == 0 && n && (!b || !c)) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {a, op == 0 ? b : nullptr, op == 0 ? c : nullptr, nullptr};
-  const size_t in_stride[4] = {32, 32, 32, 0};
-  void* const outs[2] = {out, nullptr};
-  const size_t out_stride[2] = {32, 0};
-  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    Launch L(ctx, nullptr, "k_canon_scalar_op");
-    dim3 g(grid_for(cnt)), blk(TPB);
+  const HostArray arr[] = {input(a, 32), input(op == 0 ? b : nullptr, 32), input(op == 0 ? c : nullptr, 32), output(out, 32)};
+  return host_call(ctx, n, arr, 1, [&](fec_ctx* cx, void* const* d, size_t, size_t m, hipStream_t s) {
+    Launch L(cx, s, "k_canon_scalar_op");
+    dim3 g(grid_for(m)), blk(TPB);
     const u32 *x = (const u32*)d[0], *y = (const u32*)d[1], *z = (const u32*)d[2];
-    if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_scalar_op<canon::NSecp>), g, blk, 0, L.s, op, x, y, z, (u32*)o[0], cnt);
-    else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_scalar_op<canon::NP256>), g, blk, 0, L.s, op, x, y, z, (u32*)o[0], cnt);
-    else hipLaunchKernelGGL((k_canon_scalar_op<canon::NEd>), g, blk, 0, L.s, op, x, y, z, (u32*)o[0], cnt);
+    if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_scalar_op<canon::NSecp>), g, blk, 0, L.s, op, x, y, z, (u32*)d[3], m);
+    else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_scalar_op<canon::NP256>), g, blk, 0, L.s, op, x, y, z, (u32*)d[3], m);
+    else hipLaunchKernelGGL((k_canon_scalar_op<canon::NEd>), g, blk, 0, L.s, op, x, y, z, (u32*)d[3], m);
     return L.done();
   });
 } FEC_ABI_CATCH_STATUS
@@ -398,15 +369,11 @@ int fec_canon_field_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a,
   if (!canon_curve_ok(curve)) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
   const bool binary = op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL;
   if (binary && n && !b) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {a, binary ? b : nullptr, nullptr, nullptr};
-  const size_t in_stride[4] = {32, 32, 0, 0};
-  void* const outs[2] = {out, nullptr};
-  const size_t out_stride[2] = {32, 0};
-  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const oo[2], size_t cnt) {
-    const size_t n = cnt;
-    void *x = d[0], *y = d[1], *o = oo[0];
-    Launch L(ctx, nullptr, "k_canon_field_op");
+  const HostArray arr[] = {input(a, 32), input(binary ? b : nullptr, 32), output(out, 32)};
+  return host_call(ctx, n, arr, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    const size_t n = m;
+    void *x = d[0], *y = d[1], *o = d[2];
+    Launch L(c, s, "k_canon_field_op");
     if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_field_op<csecp>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);
     else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_field_op<cp256>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);
     else hipLaunchKernelGGL((k_canon_field_op<ced>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);

@@ -562,6 +562,37 @@ __global__ __launch_bounds__(TPB) void k_ed_prefix_level(const u32* __restrict__
 using namespace fecgpu;
 using namespace fecgpu::host;
 
+// The shard workers of a multi-device ctx (host_ctx.hpp: sharded; multi_dev_run below).
+int fecgpu::host::multi_each(fec_ctx* ctx, const std::function<int(size_t)>& call) {
+  const size_t N = ctx->children.size();
+  if (N == 0 || N > kMaxShards) return FEC_E_ARG;
+  // fixed-size state: nothing here allocates, so the only thing that can throw is the creation of a thread, and
+  // an exception inside a worker is caught inside the worker (it would otherwise terminate the process)
+  int rc[kMaxShards];
+  std::thread workers[kMaxShards];
+  for (size_t g = 0; g < N; ++g) rc[g] = FEC_OK;
+  for (size_t g = 0; g < N; ++g) {
+    try {
+      workers[g] = std::thread([&rc, &call, g] {
+        try {
+          rc[g] = call(g);
+        } catch (const std::bad_alloc&) {
+          rc[g] = FEC_E_OOM;
+        } catch (...) {
+          rc[g] = FEC_E_DEVICE;
+        }
+      });
+    } catch (...) {  // std::system_error: the thread could not be started
+      rc[g] = FEC_E_COMM;
+    }
+  }
+  for (size_t g = 0; g < N; ++g)
+    if (workers[g].joinable()) workers[g].join();
+  for (size_t g = 0; g < N; ++g)
+    if (rc[g] != FEC_OK) return rc[g];
+  return FEC_OK;
+}
+
 namespace {
 
 // Inputs of generator() as the reference writes them.  secp256k1 (secp256k1.rs:2608-2625) pushes
@@ -1171,111 +1202,6 @@ int launch_point(fec_ctx* ctx, int curve, int op, const u64* dp, const u64* dq, 
   return L.done();
 }
 
-// Host-pointer batches run as a two-lane software pipeline over chunks of ctx->chunk elements:
-//   H2D(c) K(c) on lane c%2, then D2H(c-1) on the other lane -- so while the host waits for
-// chunk c-1's results the GPU is already running chunk c.  Copies from/to pageable caller memory
-// overlap the kernels of the other lane; device staging is bounded by two chunks however large n
-// is.  An input with stride 0 is shared by all elements (a fixed base) and copied once per lane.
-struct HostIn {
-  const void* ptr;
-  size_t stride;  // bytes per element; 0 = one shared value of `bytes` bytes
-  size_t bytes;   // only for stride == 0
-};
-template <class F>
-int host_pipeline(fec_ctx* ctx, size_t n, const HostIn (&in)[3], void* hout, size_t out_stride, F body) {
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const size_t chunk = pipeline_chunk(ctx);
-  const size_t nchunks = (n + chunk - 1) / chunk;
-  struct InPipeline {  // (SideStream: a multi-chunk pipeline keeps both streams busy by itself)
-    fec_ctx* c;
-    ~InPipeline() { c->in_multi_chunk_pipeline = false; }
-  } in_pipeline{ctx};
-  ctx->in_multi_chunk_pipeline = nchunks > 1;
-  hipStream_t lanes[2] = {ctx->stream, ctx->stream2};
-  auto copy_back = [&](size_t c) -> int {
-    const int lane = (int)(c & 1);
-    const size_t lo = c * chunk, cnt = (lo + chunk <= n ? chunk : n - lo);
-    if (hipMemcpyAsync((char*)hout + lo * out_stride, ctx->d_buf[lane * 4 + 3], cnt * out_stride,
-                       hipMemcpyDeviceToHost, lanes[lane]) != hipSuccess)
-      return FEC_E_DEVICE;
-    return FEC_OK;
-  };
-  return drained(ctx, [&]() -> int {  // (a failure half-way leaves nothing queued on the caller's arrays)
-  for (size_t c = 0; c < nchunks; ++c) {
-    const int lane = (int)(c & 1);
-    const size_t lo = c * chunk, cnt = (lo + chunk <= n ? chunk : n - lo);
-    void* d_in[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < 3; ++i) {
-      if (!in[i].ptr) continue;
-      const size_t bytes = in[i].stride ? cnt * in[i].stride : in[i].bytes;
-      int rc = ensure(ctx, lane * 4 + i, in[i].stride ? (chunk < n ? chunk : n) * in[i].stride : in[i].bytes);
-      if (rc != FEC_OK) return rc;
-      d_in[i] = ctx->d_buf[lane * 4 + i];
-      if (in[i].stride == 0 && c >= 2) continue;  // the shared value is already on this lane
-      const char* src = (const char*)in[i].ptr + (in[i].stride ? lo * in[i].stride : 0);
-      if (hipMemcpyAsync(d_in[i], src, bytes, hipMemcpyHostToDevice, lanes[lane]) != hipSuccess)
-        return FEC_E_DEVICE;
-    }
-    int rc = ensure(ctx, lane * 4 + 3, (chunk < n ? chunk : n) * out_stride);
-    if (rc != FEC_OK) return rc;
-    rc = body(d_in[0], d_in[1], d_in[2], ctx->d_buf[lane * 4 + 3], cnt, (void*)lanes[lane]);
-    if (rc != FEC_OK) return rc;
-    if (c > 0) {
-      rc = copy_back(c - 1);
-      if (rc != FEC_OK) return rc;
-    }
-  }
-  int rc = copy_back(nchunks - 1);
-  if (rc != FEC_OK) return rc;
-  return sync_and_check(ctx, ctx->stream, ctx->stream2);
-  });
-}
-
-// Multi-device ctx: one host thread per shard worker, each running `call(g)` for its child ctx.  Returns the first
-// failure in shard order.
-constexpr size_t kMaxShards = 16;  // fec_ctx_create_multi's limit
-template <class F>
-int multi_each(fec_ctx* ctx, F call) {
-  const size_t N = ctx->children.size();
-  if (N == 0 || N > kMaxShards) return FEC_E_ARG;
-  // fixed-size state: nothing here allocates, so the only thing that can throw is the creation of a thread, and
-  // an exception inside a worker is caught inside the worker (it would otherwise terminate the process)
-  int rc[kMaxShards];
-  std::thread workers[kMaxShards];
-  for (size_t g = 0; g < N; ++g) rc[g] = FEC_OK;
-  for (size_t g = 0; g < N; ++g) {
-    try {
-      workers[g] = std::thread([&rc, &call, g] {
-        try {
-          rc[g] = call(g);
-        } catch (const std::bad_alloc&) {
-          rc[g] = FEC_E_OOM;
-        } catch (...) {
-          rc[g] = FEC_E_DEVICE;
-        }
-      });
-    } catch (...) {  // std::system_error: the thread could not be started
-      rc[g] = FEC_E_COMM;
-    }
-  }
-  for (size_t g = 0; g < N; ++g)
-    if (workers[g].joinable()) workers[g].join();
-  for (size_t g = 0; g < N; ++g)
-    if (rc[g] != FEC_OK) return rc[g];
-  return FEC_OK;
-}
-// Host-pointer calls: contiguous shards [g*n/N, (g+1)*n/N), each worker calling the single-device entry point on its
-// child ctx with offset pointers.
-template <class F>
-int multi_shard(fec_ctx* ctx, size_t n, F call) {
-  const size_t N = ctx->children.size();
-  if (N == 0 || N > kMaxShards) return FEC_E_ARG;
-  return multi_each(ctx, [&](size_t g) -> int {
-    const size_t lo = n / N * g + (n % N) * g / N, hi = n / N * (g + 1) + (n % N) * (g + 1) / N;
-    return hi == lo ? (int)FEC_OK : call(ctx->children[g], lo, hi - lo);
-  });
-}
-
 // Device-RESIDENT shards (fec_multi_batch_*_dev): shard g -- counts[g] elements -- already sits in the memory of the
 // ctx's g-th device; `launch(child, g, lo, cnt, out, stream)` enqueues the kernels for elements [lo, lo + cnt) of that
 // shard.  With `gathered` (an array on the consumer-th device of the ctx) every shard's results are also copied into
@@ -1340,34 +1266,11 @@ int multi_dev_run(fec_ctx* ctx, int curve, const size_t* counts, uint64_t* const
     return rc;
   });
 }
-inline bool is_multi(const fec_ctx* ctx) { return ctx && !ctx->children.empty(); }
 
 }  // namespace
 
 // Curve25519 (kernels_x25519.hip): launch helpers of the fec_x25519 / fec_curve25519_mul entry points
 namespace {
-// The host forms of the Curve25519 calls: chunked through the ctx's staging; the scalars (slot 0) and the results
-// (slot 4) are secret and cleared on every way out, error returns included.
-template <class F>
-int x25519_host(fec_ctx* ctx, size_t n, const void* in0, size_t s0, const void* in1, size_t s1, void* out, size_t so, F launch) {
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  struct Wipe {
-    fec_ctx* c;
-    ~Wipe() {
-      for (int slot : {0, 4})
-        if (c->d_buf[slot]) (void)hipMemsetAsync(c->d_buf[slot], 0, c->d_cap[slot], c->stream);
-      (void)hipStreamSynchronize(c->stream);
-      (void)hipGetLastError();
-    }
-  } wipe{ctx};
-  const void* const in[4] = {in0, in1, nullptr, nullptr};
-  const size_t in_stride[4] = {s0, s1, 0, 0};
-  void* const outs[2] = {out, nullptr};
-  const size_t out_stride[2] = {so, 0};
-  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    return launch((const u32*)d[0], (const u32*)d[1], (u32*)o[0], cnt, nullptr);
-  });
-}
 int launch_x25519(fec_ctx* ctx, const u32* s, const u32* u, u32* out, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
   Launch L(ctx, stream, "k_x25519");
@@ -1391,105 +1294,49 @@ bool msg_layout_ok(const uint8_t* msgs, const uint64_t* off, size_t msg_len, siz
     if (off[i + 1] < off[i]) return false;
   return true;
 }
-constexpr int kSha512 = -1;   // msg_pipeline's mode for fec_sha512 (else EDDSA_MODE_*)
-// The host forms: chunks of ctx->chunk elements.  Per chunk the keys go to slot 0, the chunk's message bytes
-// msgs[off[lo], off[lo + cnt]) to slot 1 and its offsets, rebased to that range, to slot 2; the outputs are regions of
-// slot 4 (out: 64 bytes per element, 32 for derive; status; r_inf and s for the generic form).  `off` points at the
-// first element's offset and need not start at 0 (a shard of a multi-device call).  The keys (slot 0), the outputs
-// (slot 4) and the stream scratch (a, r, A, R) are cleared on every way out, error returns included.
-int msg_pipeline(fec_ctx* ctx, int mode, const void* keys, const uint8_t* msgs, const uint64_t* off, void* out,
-                 uint8_t* status, uint8_t* r_inf, uint64_t* s_out, size_t n) {
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  struct Wipe {
-    fec_ctx* c;
-    ~Wipe() {
-      for (int slot : {0, 4})
-        if (c->d_buf[slot]) (void)hipMemsetAsync(c->d_buf[slot], 0, c->d_cap[slot], c->stream);
-      for (auto& e : c->stream_scratch)
-        if (e.stream == c->stream && e.buf) (void)hipMemsetAsync(e.buf, 0, e.cap, c->stream);
-      (void)hipStreamSynchronize(c->stream);
-      (void)hipGetLastError();
-    }
-  } wipe{ctx};
-  const size_t pc = pipeline_chunk(ctx);
-  const size_t chunk = pc < n ? pc : n;
-  const size_t ob = mode == EDDSA_MODE_DERIVE ? 32 : 64;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_status = up(chunk * ob), o_inf = o_status + up(chunk), o_s = o_inf + up(chunk);
+constexpr int kSha512 = -1;   // msg_call's mode for fec_sha512 (else EDDSA_MODE_*)
+// The host forms, on a single-device or a multi-device ctx (host_ctx.hpp: sharded, chunked; one lane).  The engine stages
+// the keys and takes back the outputs (out: 64 bytes per element, 32 for derive; status; r_inf and s for the generic
+// form); the body stages the chunk's message bytes msgs[off[lo], off[lo + cnt]) into slot kStageBody and its offsets,
+// rebased to that range, into the slot after it.  Keys and outputs are secret (a digest too: its message may be), so the
+// staging and the stream scratch (a, r, A, R) are cleared on every way out.  The layout is checked once, here.
+int msg_call(fec_ctx* ctx, int mode, const void* keys, const uint8_t* msgs, const uint64_t* off, size_t msg_len, void* out,
+             uint8_t* status, uint8_t* r_inf, uint64_t* s_out, size_t n) {
+  if (!ctx) return FEC_E_ARG;
   const bool with_msgs = mode != EDDSA_MODE_DERIVE;
-  std::vector<uint64_t> reb(with_msgs ? chunk + 1 : 0);
-  return drained(ctx, [&]() -> int {
-    for (size_t lo = 0; lo < n; lo += chunk) {
-      const size_t cnt = lo + chunk <= n ? chunk : n - lo;
-      const u32* d_keys = nullptr;
-      if (keys) {
-        int rc = ensure(ctx, 0, chunk * 32);
-        if (rc != FEC_OK) return rc;
-        if (hipMemcpyAsync(ctx->d_buf[0], (const char*)keys + lo * 32, cnt * 32, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-          return FEC_E_DEVICE;
-        d_keys = static_cast<const u32*>(ctx->d_buf[0]);
-      }
+  if (with_msgs && !msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(keys, 32), ragged(with_msgs ? off : nullptr, 8), secret_output(out, with_msgs ? 64 : 32),
+                         output(status, 1), output(r_inf, 1), output(s_out, 32)};
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[6], size_t cnt, size_t) {
+    std::vector<uint64_t> reb(with_msgs ? (child->chunk < cnt ? child->chunk : cnt) + 1 : 0);
+    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
+      const u64* o = static_cast<const u64*>(d[1]);   // (host) the offsets from the chunk's first element on
       const unsigned char* d_msgs = nullptr;
       const u64* d_off = nullptr;
       u64 bytes = 0;
       if (with_msgs) {
-        const u64 b0 = off[lo];
-        bytes = off[lo + cnt] - b0;
-        for (size_t k = 0; k <= cnt; ++k) reb[k] = off[lo + k] - b0;
-        int rc = ensure(ctx, 2, (chunk + 1) * 8);
-        if (rc == FEC_OK && bytes) rc = ensure(ctx, 1, bytes);
+        bytes = o[m] - o[0];
+        for (size_t k = 0; k <= m; ++k) reb[k] = o[k] - o[0];
+        int rc = ensure(c, kStageBody + 1, reb.size() * 8);
+        if (rc == FEC_OK && bytes) rc = ensure(c, kStageBody, bytes);
         if (rc != FEC_OK) return rc;
-        if (bytes && hipMemcpyAsync(ctx->d_buf[1], msgs + b0, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        if (bytes && hipMemcpyAsync(c->d_buf[kStageBody], msgs + o[0], bytes, hipMemcpyHostToDevice, st) != hipSuccess)
           return FEC_E_DEVICE;
-        if (hipMemcpyAsync(ctx->d_buf[2], reb.data(), (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        if (hipMemcpyAsync(c->d_buf[kStageBody + 1], reb.data(), (m + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
           return FEC_E_DEVICE;
-        d_msgs = bytes ? static_cast<const unsigned char*>(ctx->d_buf[1]) : nullptr;
-        d_off = static_cast<const u64*>(ctx->d_buf[2]);
+        d_msgs = bytes ? static_cast<const unsigned char*>(c->d_buf[kStageBody]) : nullptr;
+        d_off = static_cast<const u64*>(c->d_buf[kStageBody + 1]);
       }
-      int rc = ensure(ctx, 4, o_s + chunk * 32);
-      if (rc != FEC_OK) return rc;
-      char* d_out = static_cast<char*>(ctx->d_buf[4]);
       if (mode == kSha512) {
-        Launch L(ctx, nullptr, "k_sha512");
-        sha512_launch(d_msgs, d_off, bytes, reinterpret_cast<u32*>(d_out), nullptr, cnt, L.s);
-        rc = L.done();
-      } else {
-        const EddsaSignIo io{mode, d_keys, d_msgs, d_off, bytes, nullptr, reinterpret_cast<u32*>(d_out),
-                             reinterpret_cast<unsigned char*>(d_out + o_inf), reinterpret_cast<u32*>(d_out + o_s),
-                             reinterpret_cast<unsigned char*>(d_out + o_status)};
-        rc = launch_eddsa_sign(ctx, io, cnt, nullptr);
+        Launch L(c, st, "k_sha512");
+        sha512_launch(d_msgs, d_off, bytes, static_cast<u32*>(d[2]), nullptr, m, L.s);
+        return L.done();
       }
-      if (rc != FEC_OK) return rc;
-      const struct {
-        void* host;
-        size_t from, stride;
-      } copies[4] = {{out, 0, ob}, {status, o_status, 1}, {r_inf, o_inf, 1}, {s_out, o_s, 32}};
-      for (const auto& c : copies)
-        if (c.host && hipMemcpyAsync(static_cast<char*>(c.host) + lo * c.stride, d_out + c.from, cnt * c.stride,
-                                     hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-          return FEC_E_DEVICE;
-      rc = sync_and_check(ctx, ctx->stream);
-      if (rc != FEC_OK) return rc;
-    }
-    return FEC_OK;
-  });
-}
-// A host-pointer call with messages on a single-device or a multi-device ctx (contiguous shards, each through
-// msg_pipeline on its child ctx).  The layout is checked once, here.
-int msg_call(fec_ctx* ctx, int mode, const void* keys, size_t key_stride, const uint8_t* msgs, const uint64_t* off,
-             size_t msg_len, void* out, uint8_t* status, uint8_t* r_inf, uint64_t* s_out, size_t n) {
-  if (!ctx) return FEC_E_ARG;
-  if (mode != EDDSA_MODE_DERIVE && !msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const size_t ob = mode == EDDSA_MODE_DERIVE ? 32 : 64;
-  if (is_multi(ctx)) {
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      auto at = [lo](auto* p, size_t stride) { return p ? reinterpret_cast<decltype(p)>(reinterpret_cast<uintptr_t>(p) + lo * stride) : p; };
-      return msg_pipeline(c, mode, at(static_cast<const char*>(keys), key_stride), msgs, off ? off + lo : nullptr,
-                          at(static_cast<char*>(out), ob), at(status, 1), at(r_inf, 1), at(s_out, 32), cnt);
+      const EddsaSignIo io{mode, static_cast<const u32*>(d[0]), d_msgs, d_off, bytes, nullptr, static_cast<u32*>(d[2]),
+                           static_cast<unsigned char*>(d[4]), static_cast<u32*>(d[5]), static_cast<unsigned char*>(d[3])};
+      return launch_eddsa_sign(c, io, m, st);
     });
-  }
-  return msg_pipeline(ctx, mode, keys, msgs, off, out, status, r_inf, s_out, n);
+  });
 }
 // The *_dev forms: one launch sequence on the caller's stream; each lane checks its own message range.
 int eddsa_sign_dev(fec_ctx* ctx, int mode, const void* d_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
@@ -1775,72 +1622,50 @@ int fec_multi_batch_double_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t
 
 int fec_batch_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* points,
                   uint64_t* out, size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || (n && (!scalars || !points || !out))) return FEC_E_ARG;
-    const size_t pl = (size_t)plimbs(curve);
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_mul(c, curve, scalars + lo * 4, points + lo * pl, out + lo * pl, cnt);
-    });
-  }
   if (!ctx || !curve_ok(curve) || (n && (!scalars || !points || !out))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  size_t pb = (size_t)plimbs(curve) * 8;
-  const HostIn in[3] = {{scalars, 32, 0}, {points, pb, 0}, {nullptr, 0, 0}};
-  return host_pipeline(ctx, n, in, out, pb, [&](void* a, void* b, void*, void* o, size_t cnt, void* s) {
-    return launch_mul(ctx, curve, false, (const u64*)a, (const u64*)b, (u64*)o, cnt, s);
+  const size_t pb = (size_t)plimbs(curve) * 8;
+  const HostArray a[] = {input(scalars, 32), input(points, pb), output(out, pb)};
+  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_mul(c, curve, false, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
 int fec_batch_mul_fixed(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* base,
                         uint64_t* out, size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || !base || (n && (!scalars || !out))) return FEC_E_ARG;
-    const size_t pl = (size_t)plimbs(curve);
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_mul_fixed(c, curve, scalars + lo * 4, base, out + lo * pl, cnt);
-    });
-  }
   if (!ctx || !curve_ok(curve) || !base || (n && (!scalars || !out))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  size_t pb = (size_t)plimbs(curve) * 8;
-  if (curve == FEC_ED25519) {
-    // the addend table is built once, on the ctx's first stream, before the pipeline starts
-    if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-    int rc = drained(ctx, [&]() -> int {
-      int r = ensure(ctx, 1, pb);
-      if (r != FEC_OK) return r;
-      if (hipMemcpyAsync(ctx->d_buf[1], base, pb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
-      r = ensure_ed_table(ctx, (const u64*)ctx->d_buf[1], base, ctx->stream);
-      if (r != FEC_OK) return r;
-      return hipStreamSynchronize(ctx->stream) == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+  const size_t pb = (size_t)plimbs(curve) * 8;
+  const HostArray a[] = {input(scalars, 32), shared_input(base, pb), output(out, pb)};
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[3], size_t cnt, size_t) -> int {
+    if (curve == FEC_ED25519) {
+      // the addend table is built once per device, on its ctx's first stream, before the chunks start
+      if (hipSetDevice(child->device) != hipSuccess) return FEC_E_DEVICE;
+      int rc = drained(child, [&]() -> int {
+        int r = ensure(child, kStageBody, pb);
+        if (r != FEC_OK) return r;
+        if (hipMemcpyAsync(child->d_buf[kStageBody], base, pb, hipMemcpyHostToDevice, child->stream) != hipSuccess)
+          return FEC_E_DEVICE;
+        r = ensure_ed_table(child, (const u64*)child->d_buf[kStageBody], base, child->stream);
+        if (r != FEC_OK) return r;
+        return hipStreamSynchronize(child->stream) == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+      });
+      if (rc != FEC_OK) return rc;
+    }
+    // the reference's generator() is recognised by value: the launches then name the ctx's own device copy, whose
+    // prefix table (ensure_gen_prefix) they can start from
+    const bool is_gen = std::memcmp(base, child->h_gen[curve], pb) == 0;
+    return chunked(child, cnt, sa, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+      return launch_mul(c, curve, true, (const u64*)d[0], is_gen ? c->d_gen[curve] : (const u64*)d[1], (u64*)d[2], m, s, base);
     });
-    if (rc != FEC_OK) return rc;
-  }
-  // the reference's generator() is recognised by value: the launches then name the ctx's own device copy, whose
-  // prefix table (ensure_gen_prefix) they can start from
-  const bool is_gen = std::memcmp(base, ctx->h_gen[curve], pb) == 0;
-  const HostIn in[3] = {{scalars, 32, 0}, {base, 0, pb}, {nullptr, 0, 0}};
-  return host_pipeline(ctx, n, in, out, pb, [&](void* a, void* b, void*, void* o, size_t cnt, void* s) {
-    const u64* db = is_gen ? ctx->d_gen[curve] : (const u64*)b;
-    return launch_mul(ctx, curve, true, (const u64*)a, db, (u64*)o, cnt, s, base);
   });
 } FEC_ABI_CATCH_STATUS
 
 int fec_batch_double_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* u1, const uint64_t* u2,
                          const uint64_t* q, uint64_t* out, size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || (n && (!u1 || !u2 || !q || !out))) return FEC_E_ARG;
-    const size_t pl = (size_t)plimbs(curve);
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_double_mul(c, curve, u1 + lo * 4, u2 + lo * 4, q + lo * pl, out + lo * pl, cnt);
-    });
-  }
   if (!ctx || !curve_ok(curve) || (n && (!u1 || !u2 || !q || !out))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  size_t pb = (size_t)plimbs(curve) * 8;
-  const HostIn in[3] = {{u1, 32, 0}, {u2, 32, 0}, {q, pb, 0}};
-  return host_pipeline(ctx, n, in, out, pb, [&](void* a, void* b, void* c, void* o, size_t cnt, void* s) {
-    return launch_double_mul(ctx, curve, (const u64*)a, (const u64*)b, (const u64*)c, (u64*)o, cnt, s);
+  const size_t pb = (size_t)plimbs(curve) * 8;
+  const HostArray a[] = {input(u1, 32), input(u2, 32), input(q, pb), output(out, pb)};
+  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_double_mul(c, curve, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (u64*)d[3], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -1893,35 +1718,11 @@ int ecdsa_verify_dev(fec_ctx* ctx, int curve, const uint8_t* d_digests, const ui
 
 int ecdsa_verify_host(fec_ctx* ctx, int curve, const uint8_t* digests, const uint64_t* r, const uint64_t* s,
                       const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* status, size_t n) {
-  if (is_multi(ctx)) {
-    if (n && (!digests || !r || !s || !pk_xy || !status)) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return ecdsa_verify_host(c, curve, digests + lo * 32, r + lo * 4, s + lo * 4, pk_xy + lo * 8,
-                               pk_inf ? pk_inf + lo : nullptr, status + lo, cnt);
-    });
-  }
   if (!ctx || (n && (!digests || !r || !s || !pk_xy || !status))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return drained(ctx, [&]() -> int {
-  const void* hin[5] = {digests, r, s, pk_xy, pk_inf};
-  const size_t bytes[5] = {n * 32, n * 32, n * 32, n * 64, n};
-  const int slot[5] = {0, 1, 2, 4, 5};
-  for (int i = 0; i < 5; ++i) {
-    if (!hin[i]) continue;
-    int rc = ensure(ctx, slot[i], bytes[i]);
-    if (rc != FEC_OK) return rc;
-    if (hipMemcpyAsync(ctx->d_buf[slot[i]], hin[i], bytes[i], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      return FEC_E_DEVICE;
-  }
-  int rc = ensure(ctx, 3, n);
-  if (rc != FEC_OK) return rc;
-  rc = launch_ecdsa_verify(ctx, curve, (const unsigned char*)ctx->d_buf[0], (const u64*)ctx->d_buf[1],
-                           (const u64*)ctx->d_buf[2], (const u64*)ctx->d_buf[4],
-                           pk_inf ? (const unsigned char*)ctx->d_buf[5] : nullptr, (unsigned char*)ctx->d_buf[3], n, nullptr);
-  if (rc != FEC_OK) return rc;
-  if (hipMemcpyAsync(status, ctx->d_buf[3], n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
-  return sync_and_check(ctx, ctx->stream);
+  const HostArray a[] = {input(digests, 32), input(r, 32), input(s, 32), input(pk_xy, 64), input(pk_inf, 1), output(status, 1)};
+  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
+    return launch_ecdsa_verify(c, curve, (const unsigned char*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
+                               (const unsigned char*)d[4], (unsigned char*)d[5], m, st);
   });
 }
 }  // namespace
@@ -2035,28 +1836,10 @@ int fec_batch_validate_point_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* 
 } FEC_ABI_CATCH_STATUS
 
 int fec_batch_validate_point(fec_ctx* ctx, fec_curve curve, const uint64_t* xy, const uint8_t* inf, uint8_t* ok, size_t n) try {
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  if (is_multi(ctx)) {
-    if (n && (!xy || !ok)) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_validate_point(c, curve, xy + lo * 8, inf ? inf + lo : nullptr, ok + lo, cnt);
-    });
-  }
-  if (!ctx || (n && (!xy || !ok))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return drained(ctx, [&]() -> int {
-  int rc = ensure(ctx, 0, n * 64);
-  if (rc == FEC_OK && inf) rc = ensure(ctx, 1, n);
-  if (rc == FEC_OK) rc = ensure(ctx, 2, n);
-  if (rc != FEC_OK) return rc;
-  if (hipMemcpyAsync(ctx->d_buf[0], xy, n * 64, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
-  if (inf && hipMemcpyAsync(ctx->d_buf[1], inf, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
-  rc = launch_validate(ctx, curve, (const u64*)ctx->d_buf[0], inf ? (const unsigned char*)ctx->d_buf[1] : nullptr,
-                       (unsigned char*)ctx->d_buf[2], n, nullptr);
-  if (rc != FEC_OK) return rc;
-  if (hipMemcpyAsync(ok, ctx->d_buf[2], n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
-  return sync_and_check(ctx, ctx->stream);
+  if (!ctx || !curve_ok(curve) || (n && (!xy || !ok))) return FEC_E_ARG;
+  const HostArray a[] = {input(xy, 64), input(inf, 1), output(ok, 1)};
+  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_validate(c, curve, (const u64*)d[0], (const unsigned char*)d[1], (unsigned char*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -2073,37 +1856,13 @@ int fec_batch_ecdh_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_
 int fec_batch_ecdh(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys, const uint64_t* pk_xy, const uint8_t* pk_inf,
                    uint8_t* secrets, uint8_t* status, size_t n) try {
   if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
-  if (is_multi(ctx)) {
-    if (n && (!private_keys || !pk_xy || !secrets || !status)) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_ecdh(c, curve, private_keys + lo * 4, pk_xy + lo * 8, pk_inf ? pk_inf + lo : nullptr, secrets + lo * 32,
-                            status + lo, cnt);
-    });
-  }
   if (!ctx || (n && (!private_keys || !pk_xy || !secrets || !status))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  // Chunked like the other element-wise calls (device staging bounded by one chunk).  The private keys (slot 0), the
-  // secrets (slot 4) and the shared points (the stream's scratch) sit in ctx-owned device memory while the call runs:
-  // they are cleared on EVERY way out of it, error returns included.
-  struct Wipe {
-    fec_ctx* c;
-    ~Wipe() {
-      if (c->d_buf[0]) (void)hipMemsetAsync(c->d_buf[0], 0, c->d_cap[0], c->stream);
-      if (c->d_buf[4]) (void)hipMemsetAsync(c->d_buf[4], 0, c->d_cap[4], c->stream);
-      for (auto& e : c->stream_scratch)
-        if (e.stream == c->stream && e.buf) (void)hipMemsetAsync(e.buf, 0, e.cap, c->stream);
-      (void)hipStreamSynchronize(c->stream);
-      (void)hipGetLastError();
-    }
-  } wipe{ctx};
-  const void* const in[4] = {private_keys, pk_xy, pk_inf, nullptr};
-  const size_t in_stride[4] = {32, 64, 1, 0};
-  void* const outs[2] = {secrets, status};
-  const size_t out_stride[2] = {32, 1};
-  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    return launch_ecdh(ctx, curve, (const u64*)d[0], (const u64*)d[1], (const unsigned char*)d[2], (unsigned char*)o[0],
-                       (unsigned char*)o[1], cnt, nullptr);
+  // (the shared points sit in the stream's scratch: cleared with the staging on every way out)
+  const HostArray a[] = {secret_input(private_keys, 32), input(pk_xy, 64), input(pk_inf, 1), secret_output(secrets, 32),
+                         output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_ecdh(c, curve, (const u64*)d[0], (const u64*)d[1], (const unsigned char*)d[2], (unsigned char*)d[3],
+                       (unsigned char*)d[4], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -2120,35 +1879,12 @@ int fec_ecdsa_sign_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, cons
 int fec_ecdsa_sign(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8_t* digests, const uint64_t* k, uint64_t* sig,
                    uint8_t* status, size_t n) try {
   if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
-  if (is_multi(ctx)) {
-    if (n && (!sk || !digests || !k || !sig || !status)) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_ecdsa_sign(c, curve, sk + lo * 4, digests + lo * 32, k + lo * 4, sig + lo * 8, status + lo, cnt);
-    });
-  }
   if (!ctx || (n && (!sk || !digests || !k || !sig || !status))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  // Chunked like fec_batch_ecdh.  The private keys (slot 0), the nonces (slot 2) and R = k * G (the stream's scratch)
-  // sit in ctx-owned device memory while the call runs: they are cleared on EVERY way out of it, error returns included.
-  struct Wipe {
-    fec_ctx* c;
-    ~Wipe() {
-      if (c->d_buf[0]) (void)hipMemsetAsync(c->d_buf[0], 0, c->d_cap[0], c->stream);
-      if (c->d_buf[2]) (void)hipMemsetAsync(c->d_buf[2], 0, c->d_cap[2], c->stream);
-      for (auto& e : c->stream_scratch)
-        if (e.stream == c->stream && e.buf) (void)hipMemsetAsync(e.buf, 0, e.cap, c->stream);
-      (void)hipStreamSynchronize(c->stream);
-      (void)hipGetLastError();
-    }
-  } wipe{ctx};
-  const void* const in[4] = {sk, digests, k, nullptr};
-  const size_t in_stride[4] = {32, 32, 32, 0};
-  void* const outs[2] = {sig, status};
-  const size_t out_stride[2] = {64, 1};
-  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    return launch_ecdsa_sign(ctx, curve, (const u64*)d[0], (const unsigned char*)d[1], (const u64*)d[2], (u64*)o[0],
-                             (unsigned char*)o[1], cnt, nullptr);
+  // (R = k * G sits in the stream's scratch: cleared with the staging on every way out)
+  const HostArray a[] = {secret_input(sk, 32), input(digests, 32), secret_input(k, 32), output(sig, 64), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_ecdsa_sign(c, curve, (const u64*)d[0], (const unsigned char*)d[1], (const u64*)d[2], (u64*)d[3],
+                             (unsigned char*)d[4], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -2164,35 +1900,12 @@ int fec_eddsa_verify_ed25519_dev(fec_ctx* ctx, const uint64_t* d_r_xy, const uin
 
 int fec_eddsa_verify_ed25519(fec_ctx* ctx, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy,
                              const uint8_t* pk_inf, const uint64_t* s, const uint64_t* k, uint8_t* status, size_t n) try {
-  if (is_multi(ctx)) {
-    if (n && (!r_xy || !pk_xy || !s || !k || !status)) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_eddsa_verify_ed25519(c, r_xy + lo * 8, r_inf ? r_inf + lo : nullptr, pk_xy + lo * 8,
-                                      pk_inf ? pk_inf + lo : nullptr, s + lo * 4, k + lo * 4, status + lo, cnt);
-    });
-  }
   if (!ctx || (n && (!r_xy || !pk_xy || !s || !k || !status))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return drained(ctx, [&]() -> int {
-  const void* hin[6] = {r_xy, pk_xy, s, k, r_inf, pk_inf};
-  const size_t bytes[6] = {n * 64, n * 64, n * 32, n * 32, n, n};
-  const int slot[6] = {0, 1, 2, 4, 5, 6};
-  for (int i = 0; i < 6; ++i) {
-    if (!hin[i]) continue;
-    int rc = ensure(ctx, slot[i], bytes[i]);
-    if (rc != FEC_OK) return rc;
-    if (hipMemcpyAsync(ctx->d_buf[slot[i]], hin[i], bytes[i], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      return FEC_E_DEVICE;
-  }
-  int rc = ensure(ctx, 3, n);
-  if (rc != FEC_OK) return rc;
-  rc = launch_eddsa_verify(ctx, (const u64*)ctx->d_buf[0], r_inf ? (const unsigned char*)ctx->d_buf[5] : nullptr,
-                           (const u64*)ctx->d_buf[1], pk_inf ? (const unsigned char*)ctx->d_buf[6] : nullptr,
-                           (const u64*)ctx->d_buf[2], (const u64*)ctx->d_buf[4], (unsigned char*)ctx->d_buf[3], n, nullptr);
-  if (rc != FEC_OK) return rc;
-  if (hipMemcpyAsync(status, ctx->d_buf[3], n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
-  return sync_and_check(ctx, ctx->stream);
+  const HostArray a[] = {input(r_xy, 64), input(r_inf, 1), input(pk_xy, 64), input(pk_inf, 1), input(s, 32), input(k, 32),
+                         output(status, 1)};
+  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
+    return launch_eddsa_verify(c, (const u64*)d[0], (const unsigned char*)d[1], (const u64*)d[2], (const unsigned char*)d[3],
+                               (const u64*)d[4], (const u64*)d[5], (unsigned char*)d[6], m, st);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -2208,44 +1921,12 @@ int fec_schnorr_verify_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_pk_x
 
 int fec_schnorr_verify(fec_ctx* ctx, fec_curve curve, const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* r_xy,
                        const uint8_t* r_inf, const uint64_t* s, const uint64_t* e, uint8_t* status, size_t n) try {
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  if (is_multi(ctx)) {
-    if (n && (!pk_xy || !r_xy || !s || !e || !status)) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_schnorr_verify(c, curve, pk_xy + lo * 8, pk_inf ? pk_inf + lo : nullptr, r_xy + lo * 8,
-                                r_inf ? r_inf + lo : nullptr, s + lo * 4, e + lo * 4, status + lo, cnt);
-    });
-  }
-  if (!ctx || (n && (!pk_xy || !r_xy || !s || !e || !status))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  // chunked like the other element-wise calls; slots: 0 pk, 1 r, 2 s, 4 e, 5 pk_inf, 6 r_inf, 3 status
-  const size_t pc = pipeline_chunk(ctx);
-  const size_t chunk = pc < n ? pc : n;
-  return drained(ctx, [&]() -> int {
-  for (size_t lo = 0; lo < n; lo += chunk) {
-    const size_t cnt = lo + chunk <= n ? chunk : n - lo;
-    const void* hin[6] = {pk_xy + lo * 8, r_xy + lo * 8, s + lo * 4, e + lo * 4, pk_inf ? pk_inf + lo : nullptr,
-                          r_inf ? r_inf + lo : nullptr};
-    const size_t bytes[6] = {cnt * 64, cnt * 64, cnt * 32, cnt * 32, cnt, cnt};
-    const int slot[6] = {0, 1, 2, 4, 5, 6};
-    for (int i = 0; i < 6; ++i) {
-      if (!hin[i]) continue;
-      int rc = ensure(ctx, slot[i], bytes[i]);
-      if (rc != FEC_OK) return rc;
-      if (hipMemcpyAsync(ctx->d_buf[slot[i]], hin[i], bytes[i], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return FEC_E_DEVICE;
-    }
-    int rc = ensure(ctx, 3, cnt);
-    if (rc != FEC_OK) return rc;
-    rc = launch_schnorr_verify(ctx, curve, (const u64*)ctx->d_buf[0], pk_inf ? (const unsigned char*)ctx->d_buf[5] : nullptr,
-                               (const u64*)ctx->d_buf[1], r_inf ? (const unsigned char*)ctx->d_buf[6] : nullptr,
-                               (const u64*)ctx->d_buf[2], (const u64*)ctx->d_buf[4], (unsigned char*)ctx->d_buf[3], cnt, nullptr);
-    if (rc != FEC_OK) return rc;
-    if (hipMemcpyAsync(status + lo, ctx->d_buf[3], cnt, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
-    if (int rc_sync = sync_and_check(ctx, ctx->stream)) return rc_sync;
-  }
-  return FEC_OK;
+  if (!ctx || !curve_ok(curve) || (n && (!pk_xy || !r_xy || !s || !e || !status))) return FEC_E_ARG;
+  const HostArray a[] = {input(pk_xy, 64), input(pk_inf, 1), input(r_xy, 64), input(r_inf, 1), input(s, 32), input(e, 32),
+                         output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
+    return launch_schnorr_verify(c, curve, (const u64*)d[0], (const unsigned char*)d[1], (const u64*)d[2],
+                                 (const unsigned char*)d[3], (const u64*)d[4], (const u64*)d[5], (unsigned char*)d[6], m, st);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -2377,99 +2058,42 @@ int fec_batch_compress_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_xy, 
 
 int fec_batch_compress(fec_ctx* ctx, fec_curve curve, const uint64_t* xy, const uint8_t* inf, uint8_t* out,
                        size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || (n && (!xy || !out))) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_compress(c, curve, xy + lo * 8, inf ? inf + lo : nullptr, out + lo * 33, cnt);
-    });
-  }
   if (!ctx || !curve_ok(curve) || (n && (!xy || !out))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {xy, inf, nullptr, nullptr};
-  const size_t in_stride[4] = {64, 1, 0, 0};
-  void* const outs[2] = {out, nullptr};
-  const size_t out_stride[2] = {33, 0};
-  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    return launch_compress(ctx, curve, (const u64*)d[0], (const unsigned char*)d[1], (unsigned char*)o[0], cnt, nullptr);
+  const HostArray a[] = {input(xy, 64), input(inf, 1), output(out, 33)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_compress(c, curve, (const u64*)d[0], (const unsigned char*)d[1], (unsigned char*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
-// decode entry points: in -> (xy, inf, ok).  The device writes inf and ok into one staging area
-// (inf at [0, cnt), ok at [chunk, chunk + cnt)), so host_chunked's two output slots suffice.
+// decode entry points: in (33 or 65 bytes per element) -> (xy, inf, ok)
 static int decode_host(fec_ctx* ctx, int op, fec_curve curve, const uint8_t* in, size_t in_stride, uint64_t* xy,
                        uint8_t* inf, uint8_t* ok, size_t n) {
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const size_t chunk = ctx->chunk < n ? ctx->chunk : n;
-  return drained(ctx, [&]() -> int {
-  for (size_t lo = 0; lo < n; lo += chunk) {
-    const size_t cnt = lo + chunk <= n ? chunk : n - lo;
-    int rc = ensure(ctx, 0, chunk * in_stride);
-    if (rc == FEC_OK) rc = ensure(ctx, 4, chunk * 64);
-    if (rc == FEC_OK) rc = ensure(ctx, 5, chunk * 2);
-    if (rc != FEC_OK) return rc;
-    if (hipMemcpyAsync(ctx->d_buf[0], in + lo * in_stride, cnt * in_stride, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      return FEC_E_DEVICE;
-    unsigned char* flags = (unsigned char*)ctx->d_buf[5];
-    {
-      Launch L(ctx, nullptr, op == 0 ? "k_decompress" : "k_decode_uncompressed");
-      codec_launch(op, curve, ctx->d_buf[0], nullptr, ctx->d_buf[4], flags, flags + chunk, cnt, L.s);
-      rc = L.done();
-      if (rc != FEC_OK) return rc;
-    }
-    if (hipMemcpyAsync(xy + lo * 8, ctx->d_buf[4], cnt * 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(inf + lo, flags, cnt, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(ok + lo, flags + chunk, cnt, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-      return FEC_E_DEVICE;
-    rc = sync_and_check(ctx, ctx->stream);
-    if (rc != FEC_OK) return rc;
-  }
-  return FEC_OK;
+  if (!ctx || !curve_ok(curve) || (n && (!in || !xy || !inf || !ok))) return FEC_E_ARG;
+  const HostArray a[] = {input(in, in_stride), output(xy, 64), output(inf, 1), output(ok, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    Launch L(c, s, op == 0 ? "k_decompress" : "k_decode_uncompressed");
+    codec_launch(op, curve, d[0], nullptr, d[1], (unsigned char*)d[2], (unsigned char*)d[3], m, L.s);
+    return L.done();
   });
 }
 
 int fec_batch_decompress(fec_ctx* ctx, fec_curve curve, const uint8_t* in, uint64_t* xy, uint8_t* inf, uint8_t* ok,
                          size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || (n && (!in || !xy || !inf || !ok))) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_decompress(c, curve, in + lo * 33, xy + lo * 8, inf + lo, ok + lo, cnt);
-    });
-  }
-  if (!ctx || !curve_ok(curve) || (n && (!in || !xy || !inf || !ok))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
   return decode_host(ctx, 0, curve, in, 33, xy, inf, ok, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_batch_decode_uncompressed(fec_ctx* ctx, fec_curve curve, const uint8_t* in, uint64_t* xy, uint8_t* inf,
                                   uint8_t* ok, size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || (n && (!in || !xy || !inf || !ok))) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_decode_uncompressed(c, curve, in + lo * 65, xy + lo * 8, inf + lo, ok + lo, cnt);
-    });
-  }
-  if (!ctx || !curve_ok(curve) || (n && (!in || !xy || !inf || !ok))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
   return decode_host(ctx, 1, curve, in, 65, xy, inf, ok, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_batch_encode_uncompressed(fec_ctx* ctx, fec_curve curve, const uint64_t* xy, const uint8_t* inf, uint8_t* out,
                                   size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || (n && (!xy || !out))) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_encode_uncompressed(c, curve, xy + lo * 8, inf ? inf + lo : nullptr, out + lo * 65, cnt);
-    });
-  }
   if (!ctx || !curve_ok(curve) || (n && (!xy || !out))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const void* const in[4] = {xy, inf, nullptr, nullptr};
-  const size_t in_stride[4] = {64, 1, 0, 0};
-  void* const outs[2] = {out, nullptr};
-  const size_t out_stride[2] = {65, 0};
-  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    Launch L(ctx, nullptr, "k_encode_uncompressed");
-    codec_launch(2, curve, d[0], d[1], o[0], nullptr, nullptr, cnt, L.s);
+  const HostArray a[] = {input(xy, 64), input(inf, 1), output(out, 65)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    Launch L(c, s, "k_encode_uncompressed");
+    codec_launch(2, curve, d[0], d[1], d[2], nullptr, nullptr, m, L.s);
     return L.done();
   });
 } FEC_ABI_CATCH_STATUS
@@ -2485,70 +2109,34 @@ int fec_batch_to_affine_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_poi
 
 int fec_batch_to_affine(fec_ctx* ctx, fec_curve curve, const uint64_t* points, uint64_t* xy, uint8_t* inf,
                         size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || (n && (!points || !xy || !inf))) return FEC_E_ARG;
-    const size_t pl = (size_t)plimbs(curve);
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_batch_to_affine(c, curve, points + lo * pl, xy + lo * 8, inf + lo, cnt);
-    });
-  }
   if (!ctx || !curve_ok(curve) || (n && (!points || !xy || !inf))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  size_t pb = (size_t)plimbs(curve) * 8;
-  return drained(ctx, [&]() -> int {
-  int rc = ensure(ctx, 0, n * pb);
-  if (rc == FEC_OK) rc = ensure(ctx, 3, n * 64);
-  if (rc == FEC_OK) rc = ensure(ctx, 1, n);
-  if (rc != FEC_OK) return rc;
-  if (hipMemcpyAsync(ctx->d_buf[0], points, n * pb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-    return FEC_E_DEVICE;
-  rc = launch_to_affine(ctx, curve, (const u64*)ctx->d_buf[0], (u64*)ctx->d_buf[3],
-                        (unsigned char*)ctx->d_buf[1], n, nullptr);
-  if (rc != FEC_OK) return rc;
-  if (hipMemcpyAsync(xy, ctx->d_buf[3], n * 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(inf, ctx->d_buf[1], n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-    return FEC_E_DEVICE;
-  return sync_and_check(ctx, ctx->stream);
+  const HostArray a[] = {input(points, (size_t)plimbs(curve) * 8), output(xy, 64), output(inf, 1)};
+  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_to_affine(c, curve, (const u64*)d[0], (u64*)d[1], (unsigned char*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
 int fec_field_op(fec_ctx* ctx, fec_curve curve, fec_field_opcode op, const uint64_t* a, const uint64_t* b,
                  uint64_t* out, size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || (n && (!a || !out))) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_field_op(c, curve, op, a + lo * 4, b ? b + lo * 4 : nullptr, out + lo * 4, cnt);
-    });
-  }
   if (!ctx || !curve_ok(curve) || op < FEC_F_ADD || op > FEC_F_NEG || (n && (!a || !out))) return FEC_E_ARG;
-  bool binary = op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL;
+  const bool binary = op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL;
   if (binary && n && !b) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  const HostIn in[3] = {{a, 32, 0}, {binary ? b : nullptr, 32, 0}, {nullptr, 0, 0}};
-  return host_pipeline(ctx, n, in, out, 32, [&](void* x, void* y, void*, void* o, size_t cnt, void* s) {
-    return launch_field(ctx, curve, op, (const u64*)x, (const u64*)y, (u64*)o, cnt, s);
+  const HostArray arr[] = {input(a, 32), input(binary ? b : nullptr, 32), output(out, 32)};
+  return host_call(ctx, n, arr, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_field(c, curve, op, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
 int fec_point_op(fec_ctx* ctx, fec_curve curve, fec_point_opcode op, const uint64_t* p, const uint64_t* q,
                  uint64_t* out, size_t n) try {
-  if (is_multi(ctx)) {
-    if (!curve_ok(curve) || (n && (!p || !out))) return FEC_E_ARG;
-    const size_t pl = (size_t)plimbs(curve);
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_point_op(c, curve, op, p + lo * pl, q ? q + lo * pl : nullptr, out + lo * pl, cnt);
-    });
-  }
   if (!ctx || !curve_ok(curve) || op < FEC_P_ADD || op > FEC_P_DOUBLE_TRAIT || (n && (!p || !out)))
     return FEC_E_ARG;
   if (op == FEC_P_DOUBLE_TRAIT && curve != FEC_SECP256K1) return FEC_E_UNSUPPORTED;
   if (op == FEC_P_ADD && n && !q) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  size_t pb = (size_t)plimbs(curve) * 8;
-  const HostIn in[3] = {{p, pb, 0}, {op == FEC_P_ADD ? q : nullptr, pb, 0}, {nullptr, 0, 0}};
-  return host_pipeline(ctx, n, in, out, pb, [&](void* x, void* y, void*, void* o, size_t cnt, void* s) {
-    return launch_point(ctx, curve, op, (const u64*)x, (const u64*)y, (u64*)o, cnt, s);
+  const size_t pb = (size_t)plimbs(curve) * 8;
+  const HostArray a[] = {input(p, pb), input(op == FEC_P_ADD ? q : nullptr, pb), output(out, pb)};
+  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_point(c, curve, op, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -2791,16 +2379,10 @@ int fec_x25519_dev(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_u, u
 } FEC_ABI_CATCH_STATUS
 
 int fec_x25519(fec_ctx* ctx, const uint8_t* scalars, const uint8_t* u, uint8_t* out, size_t n) try {
-  if (is_multi(ctx)) {
-    if (n && (!scalars || !u || !out)) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_x25519(c, scalars + lo * 32, u + lo * 32, out + lo * 32, cnt);
-    });
-  }
   if (!ctx || (n && (!scalars || !u || !out))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  return x25519_host(ctx, n, scalars, 32, u, 32, out, 32, [&](const u32* s, const u32* q, u32* o, size_t cnt, void* st) {
-    return launch_x25519(ctx, s, q, o, cnt, st);
+  const HostArray a[] = {secret_input(scalars, 32), input(u, 32), secret_output(out, 32)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_x25519(c, (const u32*)d[0], (const u32*)d[1], (u32*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -2814,38 +2396,21 @@ int fec_curve25519_mul_dev(fec_ctx* ctx, const uint64_t* d_scalars, const uint64
 } FEC_ABI_CATCH_STATUS
 
 int fec_curve25519_mul(fec_ctx* ctx, const uint64_t* scalars, const uint64_t* points, uint64_t* out, size_t n) try {
-  if (is_multi(ctx)) {
-    if (n && (!scalars || !points || !out)) return FEC_E_ARG;
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_curve25519_mul(c, scalars + lo * 4, points + lo * 8, out + lo * 8, cnt);
-    });
-  }
   if (!ctx || (n && (!scalars || !points || !out))) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  return x25519_host(ctx, n, scalars, 32, points, 64, out, 64, [&](const u32* s, const u32* p, u32* o, size_t cnt, void* st) {
-    return launch_curve25519_mul(ctx, s, p, o, cnt, st);
+  const HostArray a[] = {secret_input(scalars, 32), input(points, 64), secret_output(out, 64)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_curve25519_mul(c, (const u32*)d[0], (const u32*)d[1], (u32*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
 int fec_curve25519_field_op(fec_ctx* ctx, fec_field_opcode op, const uint64_t* a, const uint64_t* b, uint64_t* out,
                             size_t n) try {
   const bool binary = op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL;
-  if (op < FEC_F_ADD || op > FEC_F_NEG || (n && (!a || !out || (binary && !b)))) return FEC_E_ARG;
-  if (is_multi(ctx)) {
-    return multi_shard(ctx, n, [=](fec_ctx* c, size_t lo, size_t cnt) {
-      return fec_curve25519_field_op(c, op, a + lo * 4, binary ? b + lo * 4 : nullptr, out + lo * 4, cnt);
-    });
-  }
-  if (!ctx) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const void* const in[4] = {a, binary ? b : nullptr, nullptr, nullptr};
-  const size_t in_stride[4] = {32, 32, 0, 0};
-  void* const outs[2] = {out, nullptr};
-  const size_t out_stride[2] = {32, 0};
-  return host_chunked(ctx, n, in, in_stride, outs, out_stride, [&](void* const d[4], void* const o[2], size_t cnt) {
-    Launch L(ctx, nullptr, "k_x25519_field_op");
-    x25519_field_launch((int)op, (const u32*)d[0], (const u32*)d[1], (u32*)o[0], cnt, L.s);
+  if (!ctx || op < FEC_F_ADD || op > FEC_F_NEG || (n && (!a || !out || (binary && !b)))) return FEC_E_ARG;
+  const HostArray arr[] = {input(a, 32), input(binary ? b : nullptr, 32), output(out, 32)};
+  return host_call(ctx, n, arr, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    Launch L(c, s, "k_x25519_field_op");
+    x25519_field_launch((int)op, (const u32*)d[0], (const u32*)d[1], (u32*)d[2], m, L.s);
     return L.done();
   });
 } FEC_ABI_CATCH_STATUS
@@ -2854,7 +2419,7 @@ int fec_curve25519_field_op(fec_ctx* ctx, fec_field_opcode op, const uint64_t* a
 
 int fec_sha512(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* digests, size_t n) try {
   if (n && !digests) return FEC_E_ARG;
-  return msg_call(ctx, kSha512, nullptr, 0, msgs, msg_off, msg_len, digests, nullptr, nullptr, nullptr, n);
+  return msg_call(ctx, kSha512, nullptr, msgs, msg_off, msg_len, digests, nullptr, nullptr, nullptr, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_sha512_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
@@ -2872,19 +2437,19 @@ int fec_sha512_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_of
 int fec_ed25519_sign(fec_ctx* ctx, const uint8_t* private_keys, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                      uint8_t* sig, uint8_t* status, size_t n) try {
   if (n && (!private_keys || !sig || !status)) return FEC_E_ARG;
-  return msg_call(ctx, EDDSA_MODE_SIGN, private_keys, 32, msgs, msg_off, msg_len, sig, status, nullptr, nullptr, n);
+  return msg_call(ctx, EDDSA_MODE_SIGN, private_keys, msgs, msg_off, msg_len, sig, status, nullptr, nullptr, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_ed25519_derive_public_key(fec_ctx* ctx, const uint8_t* private_keys, uint8_t* public_keys, uint8_t* status,
                                   size_t n) try {
   if (n && (!private_keys || !public_keys || !status)) return FEC_E_ARG;
-  return msg_call(ctx, EDDSA_MODE_DERIVE, private_keys, 32, nullptr, nullptr, 0, public_keys, status, nullptr, nullptr, n);
+  return msg_call(ctx, EDDSA_MODE_DERIVE, private_keys, nullptr, nullptr, 0, public_keys, status, nullptr, nullptr, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_eddsa_sign_ed25519(fec_ctx* ctx, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                            uint64_t* r_xy, uint8_t* r_inf, uint64_t* s, uint8_t* status, size_t n) try {
   if (n && (!sk || !r_xy || !r_inf || !s || !status)) return FEC_E_ARG;
-  return msg_call(ctx, EDDSA_MODE_GENERIC, sk, 32, msgs, msg_off, msg_len, r_xy, status, r_inf, s, n);
+  return msg_call(ctx, EDDSA_MODE_GENERIC, sk, msgs, msg_off, msg_len, r_xy, status, r_inf, s, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_ed25519_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,

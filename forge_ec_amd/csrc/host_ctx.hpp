@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <vector>
 
@@ -20,8 +21,10 @@ struct fec_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timing = false, timed = false;
   const char* last_kernel = "";
-  // device staging for the host-pointer entry points: slots 0-3 serve pipeline lane 0 (and the
-  // small one-shot calls), slots 4-7 pipeline lane 1
+  // device staging for the host-pointer entry points (host::chunked): lane 0 packs a chunk's inputs into slot 0 and its
+  // outputs into slot 1 (one region per array, each on a 256-byte boundary); slots 2 and 3 are the body's own, for
+  // ragged data (the message calls: message bytes, rebased offsets); lane 1 (the second stream) uses slots 4 and 5.
+  // The calls that stage a whole batch at once (fec_multi_scalar_mul, the batch_verify calls) take slots as they need.
   void* d_buf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t d_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hipStream_t stream2 = nullptr;
@@ -77,7 +80,7 @@ struct fec_ctx {
   unsigned prefix_bits = 0;                  // wanted (FEC_FIXED_PREFIX_BITS at ctx creation, fec_ctx_set_fixed_prefix_bits)
   size_t fixed_elems[3] = {0, 0, 0};         // multiplications by the generator this ctx has been asked for, per curve
   size_t prefix_after = 0;                   // a table is built once fixed_elems reaches this (see fecgpu.hip: kPrefixAfter)
-  bool in_multi_chunk_pipeline = false;  // set by host_pipeline while it runs more than one chunk (fecgpu.hip: SideStream)
+  bool in_multi_chunk_pipeline = false;  // set by a two-lane host::chunked while it runs more than one chunk (fecgpu.hip: SideStream)
   bool in_host_call = false;             // inside a host-pointer (synchronous) entry point: host::drained
   bool prefix_explicit = false;          // the caller asked for prefix tables (fec_ctx_set_fixed_prefix_bits): any launch may build one
   unsigned prefix_budget_pct = 25;       // a table and its build scratch may take this share of the device's FREE memory
@@ -342,49 +345,156 @@ inline int drained(fec_ctx* ctx, F body) {
   return rc;
 }
 
-// Host-pointer call over chunks of ctx->chunk elements with up to four per-element inputs (slots 0-3)
-// and two per-element outputs (slots 4-5): H2D, body(d_in[4], d_out[2], count), D2H per chunk on the
-// ctx stream.  Device staging and any per-element scratch the body allocates stay bounded by one
-// chunk however large n is.  A null input / output pointer is passed through as null.
-template <class F>
-inline int host_chunked(fec_ctx* ctx, size_t n, const void* const in[4], const size_t in_stride[4], void* const out[2],
-                        const size_t out_stride[2], F body) {
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const size_t pc = pipeline_chunk(ctx);
-  const size_t chunk = pc < n ? pc : n;
-  return drained(ctx, [&]() -> int {
-  for (size_t lo = 0; lo < n; lo += chunk) {
-    const size_t cnt = lo + chunk <= n ? chunk : n - lo;
-    void* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
-    void* d_out[2] = {nullptr, nullptr};
-    for (int i = 0; i < 4; ++i) {
-      if (!in[i]) continue;
-      int rc = ensure(ctx, i, chunk * in_stride[i]);
-      if (rc != FEC_OK) return rc;
-      d_in[i] = ctx->d_buf[i];
-      if (hipMemcpyAsync(d_in[i], (const char*)in[i] + lo * in_stride[i], cnt * in_stride[i], hipMemcpyHostToDevice,
-                         ctx->stream) != hipSuccess)
-        return FEC_E_DEVICE;
+// ---- the element-wise host-pointer entry points: one engine for all of them ----
+//
+// A call names its host arrays (HostArray) and a body that enqueues the kernels of one chunk on device copies of
+// them.  Two layers compose:
+//   sharded(ctx, n, a, fn)          a multi-device ctx splits [0, n) into contiguous shards [g*n/N, (g+1)*n/N), one
+//                                   host thread per shard worker (multi_each); fn(child, a', cnt, lo) gets the arrays
+//                                   offset to the shard (a' = a + lo * stride).  A single-device ctx: fn(ctx, a, n, 0).
+//   chunked(ctx, n, a, lanes, body) chunks of ctx->chunk elements; per chunk H2D, body(ctx, d, lo, cnt, stream), D2H.
+// host_call runs both; a call whose every device must be prepared before its chunks run (fec_batch_mul_fixed) or whose
+// body keeps per-shard host state (the message calls) composes them itself.
+//
+// Staging, per lane: the chunk's inputs are packed into one buffer and its outputs into another, each array a region on
+// a 256-byte boundary (slot map: fec_ctx::d_buf), so device staging is bounded by two chunks per lane for any n.
+// lanes = 2: H2D(c) and K(c) on lane c % 2, then D2H(c - 1) -- while the host waits for chunk c - 1's results the GPU
+// already runs chunk c (the lanes are the ctx's two streams; a launcher then does not fork onto the second stream:
+// in_multi_chunk_pipeline).  lanes = 1: every chunk on the ctx stream, synchronised before the next.
+// Secrets: a call that names any secret array clears, on every way out (error returns included), all the staging it
+// used and the scratch of the streams it ran on.
+struct HostArray {
+  const void* ptr;  // null: absent (an optional array) -- reaches the body as null
+  size_t stride;    // bytes per element; 0 = shared: one value of `bytes` bytes, copied once per lane
+  size_t bytes;     // shared only
+  bool out;         // copied back after the chunk's kernels
+  bool secret;
+  bool staged;      // false: the body reads it from the host itself (ragged data), at the chunk's first element
+};
+inline HostArray input(const void* p, size_t stride) { return {p, stride, 0, false, false, true}; }
+inline HostArray secret_input(const void* p, size_t stride) { return {p, stride, 0, false, true, true}; }
+inline HostArray shared_input(const void* p, size_t bytes) { return {p, 0, bytes, false, false, true}; }
+inline HostArray output(void* p, size_t stride) { return {p, stride, 0, true, false, true}; }
+inline HostArray secret_output(void* p, size_t stride) { return {p, stride, 0, true, true, true}; }
+inline HostArray ragged(const void* p, size_t stride) { return {p, stride, 0, false, false, false}; }
+inline const void* element(const HostArray& a, size_t i) {
+  return a.ptr && a.stride ? static_cast<const char*>(a.ptr) + i * a.stride : a.ptr;
+}
+
+// Staging slots of lane L: 4L inputs, 4L + 1 outputs.  Slots 2 and 3 stay free for a lanes = 1 body that stages
+// something ragged (the message calls: message bytes, rebased offsets).
+constexpr int kStageIn = 0, kStageOut = 1, kStageBody = 2;
+
+inline bool is_multi(const fec_ctx* ctx) { return ctx && !ctx->children.empty(); }
+
+// Multi-device ctx: one host thread per shard worker, each running `call(g)` for its child ctx (fecgpu.hip).  Returns
+// the first failure in shard order.
+constexpr size_t kMaxShards = 16;  // fec_ctx_create_multi's limit
+int multi_each(fec_ctx* ctx, const std::function<int(size_t)>& call);
+
+template <size_t N, class F>
+int sharded(fec_ctx* ctx, size_t n, const HostArray (&a)[N], F fn) {
+  if (n == 0) return FEC_OK;
+  if (!is_multi(ctx)) return fn(ctx, a, n, (size_t)0);
+  const size_t D = ctx->children.size();
+  return multi_each(ctx, [&](size_t g) -> int {
+    const size_t lo = n / D * g + (n % D) * g / D, hi = n / D * (g + 1) + (n % D) * (g + 1) / D;
+    if (hi == lo) return FEC_OK;
+    HostArray s[N];
+    for (size_t i = 0; i < N; ++i) {
+      s[i] = a[i];
+      s[i].ptr = element(a[i], lo);
     }
-    for (int i = 0; i < 2; ++i) {
-      if (!out[i]) continue;
-      int rc = ensure(ctx, 4 + i, chunk * out_stride[i]);
-      if (rc != FEC_OK) return rc;
-      d_out[i] = ctx->d_buf[4 + i];
-    }
-    int rc = body(d_in, d_out, cnt);
-    if (rc != FEC_OK) return rc;
-    for (int i = 0; i < 2; ++i) {
-      if (!out[i]) continue;
-      if (hipMemcpyAsync((char*)out[i] + lo * out_stride[i], d_out[i], cnt * out_stride[i], hipMemcpyDeviceToHost,
-                         ctx->stream) != hipSuccess)
-        return FEC_E_DEVICE;
-    }
-    rc = sync_and_check(ctx, ctx->stream);
-    if (rc != FEC_OK) return rc;
-  }
-  return FEC_OK;
+    return fn(ctx->children[g], s, hi - lo, lo);
   });
+}
+
+template <size_t N, class F>
+int chunked(fec_ctx* ctx, size_t n, const HostArray (&a)[N], int lanes, F body) {
+  if (n == 0) return FEC_OK;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const size_t chunk = pipeline_chunk(ctx) < n ? pipeline_chunk(ctx) : n;
+  const size_t nchunks = (n + chunk - 1) / chunk;
+  size_t off[N], bytes[2] = {0, 0};  // region of each staged array in its lane's input / output buffer
+  bool secret = false;
+  for (size_t i = 0; i < N; ++i) {
+    if (!a[i].staged || !a[i].ptr) continue;
+    off[i] = bytes[a[i].out];
+    bytes[a[i].out] += ((a[i].stride ? chunk * a[i].stride : a[i].bytes) + 255) & ~(size_t)255;
+    secret = secret || a[i].secret;
+  }
+  hipStream_t st[2] = {ctx->stream, lanes == 2 ? ctx->stream2 : ctx->stream};
+  struct Guard {  // (runs after drained: by then nothing the call queued is still in flight on an error path)
+    fec_ctx* c;
+    const hipStream_t* st;
+    int lanes;
+    bool wipe;
+    ~Guard() {
+      c->in_multi_chunk_pipeline = false;
+      if (!wipe) return;
+      for (int l = 0; l < lanes; ++l) {
+        for (int slot = 4 * l; slot < 4 * l + 4; ++slot)
+          if (c->d_buf[slot]) (void)hipMemsetAsync(c->d_buf[slot], 0, c->d_cap[slot], st[l]);
+        for (auto& e : c->stream_scratch)
+          if (e.stream == st[l] && e.buf) (void)hipMemsetAsync(e.buf, 0, e.cap, st[l]);
+      }
+      for (int l = 0; l < lanes; ++l) (void)hipStreamSynchronize(st[l]);
+      (void)hipGetLastError();
+    }
+  } guard{ctx, st, lanes, secret};
+  ctx->in_multi_chunk_pipeline = lanes == 2 && nchunks > 1;
+  auto copy_back = [&](size_t c) -> int {
+    const int lane = lanes == 2 ? (int)(c & 1) : 0;
+    const size_t lo = c * chunk, cnt = lo + chunk <= n ? chunk : n - lo;
+    const char* base = static_cast<const char*>(ctx->d_buf[4 * lane + kStageOut]);
+    for (size_t i = 0; i < N; ++i)
+      if (a[i].staged && a[i].ptr && a[i].out &&
+          hipMemcpyAsync(const_cast<void*>(element(a[i], lo)), base + off[i], cnt * a[i].stride, hipMemcpyDeviceToHost,
+                         st[lane]) != hipSuccess)
+        return FEC_E_DEVICE;
+    return FEC_OK;
+  };
+  return drained(ctx, [&]() -> int {
+    for (size_t c = 0; c < nchunks; ++c) {
+      const int lane = lanes == 2 ? (int)(c & 1) : 0;
+      const size_t lo = c * chunk, cnt = lo + chunk <= n ? chunk : n - lo;
+      for (int dir = 0; dir < 2; ++dir)
+        if (bytes[dir]) {
+          const int rc = ensure(ctx, 4 * lane + (dir ? kStageOut : kStageIn), bytes[dir]);
+          if (rc != FEC_OK) return rc;
+        }
+      void* d[N];
+      for (size_t i = 0; i < N; ++i) {
+        if (!a[i].staged || !a[i].ptr) {
+          d[i] = const_cast<void*>(element(a[i], lo));
+          continue;
+        }
+        d[i] = static_cast<char*>(ctx->d_buf[4 * lane + (a[i].out ? kStageOut : kStageIn)]) + off[i];
+        if (a[i].out || (!a[i].stride && c >= (size_t)lanes)) continue;  // (a shared value already on this lane)
+        if (hipMemcpyAsync(d[i], element(a[i], lo), a[i].stride ? cnt * a[i].stride : a[i].bytes, hipMemcpyHostToDevice,
+                           st[lane]) != hipSuccess)
+          return FEC_E_DEVICE;
+      }
+      int rc = body(ctx, static_cast<void* const*>(d), lo, cnt, st[lane]);
+      if (rc != FEC_OK) return rc;
+      if (lanes == 1) {
+        rc = copy_back(c);
+        if (rc == FEC_OK) rc = sync_and_check(ctx, st[0]);
+      } else if (c > 0) {
+        rc = copy_back(c - 1);
+      }
+      if (rc != FEC_OK) return rc;
+    }
+    if (lanes == 1) return FEC_OK;
+    const int rc = copy_back(nchunks - 1);
+    return rc != FEC_OK ? rc : sync_and_check(ctx, st[0], st[1]);
+  });
+}
+
+// An element-wise host-pointer call: sharded over the devices of a multi-device ctx, chunked on each.
+template <size_t N, class F>
+int host_call(fec_ctx* ctx, size_t n, const HostArray (&a)[N], int lanes, F body) {
+  return sharded(ctx, n, a, [&](fec_ctx* c, const HostArray (&s)[N], size_t cnt, size_t) { return chunked(c, cnt, s, lanes, body); });
 }
 
 }  // namespace host

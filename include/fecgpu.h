@@ -138,7 +138,7 @@ int fec_ctx_create(fec_ctx** out, int device);
  * fec_field_op, fec_point_op (tests/test_gpu_multi_ctx.py runs every one of them sharded) -- then
  * split the batch into n_devices contiguous shards
  * [g*n/N, (g+1)*n/N), run each shard on its device from its own host thread with that device's
- * chunked copy/compute pipeline, and write results straight into the caller's output array: the
+ * chunked copy/compute path, and write results straight into the caller's output array: the
  * "gather" is the D2H copy of each shard, there is no device-to-device exchange.  Results are
  * identical to a single-device ctx.  Entry points that are not element-wise (fec_multi_scalar_mul,
  * fec_ecdsa_batch_verify, fec_schnorr_batch_verify*, fec_generator*, the measurement hooks)
@@ -532,9 +532,11 @@ int fec_sha512(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1
 int fec_sha512_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
                    uint8_t* d_status, size_t n, void* stream);
 
-/* Host-pointer batches are processed as a two-lane pipeline of `elements`-sized chunks (default
- * 2^18): copies of one chunk overlap the kernel of the other, and device staging memory is bounded
- * by two chunks for any n.  Tuning/test knob; results do not depend on it. */
+/* Every element-wise host-pointer entry point processes its batch in chunks of `elements` elements
+ * (default 2^18), so device staging memory is bounded by two chunks for any n.  Most run them as a
+ * two-lane pipeline in which the copies of one chunk overlap the kernels of the other; the calls that
+ * handle secrets, the codec and the canonical-mode calls run one chunk at a time.  Tuning/test knob;
+ * results do not depend on it. */
 int fec_ctx_set_chunk(fec_ctx* ctx, size_t elements);
 
 /* ---- measurement hooks ---- */
