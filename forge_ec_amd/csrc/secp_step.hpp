@@ -71,30 +71,34 @@ FEC_DEV fe mul_small(const fe& a, Rare& rr) {
   note_top(rr, r);
   return r;
 }
-// square() (634-713): secp::sqr without its exc leg and reduce
+// square() (634-713): secp::sqr without its exc leg and reduce.  The statement itself folds the five words that
+// decide its rare legs, and the result's top word, into the running maximum (tools/gen_field_asm.py, secp_sqr).
 FEC_DEV fe sqr(const fe& a, Rare& rr) {
   fe r;
   lmask tmp;
   asm(FEC_SECP_SQR_ACC_ASM
       : "=v"(r.w[0]), "=v"(r.w[1]), "=v"(r.w[2]), "=v"(r.w[3]), "=&v"(r.w[4]), "=&v"(r.w[5]), "=&v"(r.w[6]),
-        "=&v"(r.w[7]), "=&s"(tmp), "+s"(rr.m)
+        "=&v"(r.w[7]), "=&s"(tmp), "+v"(rr.top)
       : FEC_V8(a), "s"(977u)
       : FEC_SECP_SQR_ACC_CLOBBERS);
-  note_top(rr, r);
   return r;
 }
 // Add (353-393) and a + a: secp::add / secp::dbl without their top-word and carry legs
 FEC_DEV fe add(const fe& a, const fe& b, Rare& rr) {
   fe x = a;
   u32 t0, t1;
-  asm(FEC_SECP_ADD_ACC_ASM : FEC_RW8(x), "+s"(rr.m), "=&v"(t1), "=&v"(t0) : FEC_V8(b) : "vcc");
+  register lmask c asm("vcc");  // the carry (borrow) out of word 1, where the statement's last instruction leaves it
+  asm(FEC_SECP_ADD_ACC_ASM : FEC_RW8(x), "=s"(c), "=&v"(t1), "=&v"(t0) : FEC_V8(b));
+  rr.m |= c;
   note_top(rr, x);
   return x;
 }
 FEC_DEV fe dbl(const fe& a, Rare& rr) {
   fe x = a;
   u32 t0, t1;
-  asm(FEC_SECP_DBL_ACC_ASM : FEC_RW8(x), "+s"(rr.m), "=&v"(t1), "=&v"(t0) : : "vcc");
+  register lmask c asm("vcc");  // the carry (borrow) out of word 1, where the statement's last instruction leaves it
+  asm(FEC_SECP_DBL_ACC_ASM : FEC_RW8(x), "=s"(c), "=&v"(t1), "=&v"(t0));
+  rr.m |= c;
   note_top(rr, x);
   return x;
 }
@@ -102,7 +106,9 @@ FEC_DEV fe dbl(const fe& a, Rare& rr) {
 FEC_DEV fe sub(const fe& a, const fe& b, Rare& rr) {
   fe x = a;
   u32 t0, t1;
-  asm(FEC_SECP_SUB_ACC_ASM : FEC_RW8(x), "+s"(rr.m), "=&v"(t1), "=&v"(t0) : FEC_V8(b) : "vcc");
+  register lmask c asm("vcc");  // the carry (borrow) out of word 1, where the statement's last instruction leaves it
+  asm(FEC_SECP_SUB_ACC_ASM : FEC_RW8(x), "=s"(c), "=&v"(t1), "=&v"(t0) : FEC_V8(b));
+  rr.m |= c;
   return x;
 }
 

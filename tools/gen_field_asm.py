@@ -24,6 +24,7 @@ reduction); tests/test_gpu_parity.py and the host emulation (which keeps the por
 pin them against the oracle.
 """
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -74,11 +75,13 @@ def interleave(main, side):
     return out
 
 
-def mul_wide_columns(A, B, VB, side_for_column=None, first_col_src=None):
+def mul_wide_columns(A, B, VB, side_for_column=None, first_col_src=None, zero=None):
     """Product scanning of A[0..7] x B[0..7] (operand strings).  Column k accumulates in the pair
     Q_k = v[VB+2k : VB+2k+1]; C = v[VB+30 : VB+31] is the carry pair {next column's carry-in low,
     overflow count}.  Returns the instruction list; afterwards T[k] = v(VB+2k) for k <= 14 and
-    T[15] = v(VB+29).  side_for_column(k) -> instructions to interleave into column k."""
+    T[15] = v(VB+29).  side_for_column(k) -> instructions to interleave into column k.  zero = a register that holds 0
+    through every column: the capture behind a column's first product is then VOP2 too (both its sources are constants
+    otherwise, which only VOP3 encodes)."""
     C = VB + 30
     ins = ["v_mov_b32_e32 %s, 0" % v(C + 1)]
     for k in range(15):
@@ -92,7 +95,7 @@ def mul_wide_columns(A, B, VB, side_for_column=None, first_col_src=None):
                 main.append("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (vp(q), A[i], B[j], src2))
                 # carry-in < 2^32 for column 1 and the top column is bounded by the true product
                 if k >= 2 and k != 14:
-                    main.append("v_addc_co_u32_e64 %s, vcc, 0, 0, vcc" % v(C + 1))
+                    main.append(CAPTURE % (v(C + 1), zero) if zero else "v_addc_co_u32_e64 %s, vcc, 0, 0, vcc" % v(C + 1))
             else:
                 main.append("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (vp(q), A[i], B[j], vp(q)))
                 main.append(CAPTURE % (v(C + 1), v(C + 1)))
@@ -135,7 +138,7 @@ def secp_mul(VB, acc=False):
 
     b = Block()
     b.e("v_mov_b32_e32 %s, 0" % v(P + 1))
-    for s in mul_wide_columns(A, B, VB, side):
+    for s in mul_wide_columns(A, B, VB, side, zero=v(P + 1)):  # P's high half is 0 until the columns are done
         b.e(s)
     # V = T_hi + M - Q (mod 2^256), Q = {P.lo, sc}
     b.e("v_add_co_u32_e32 %s, vcc, %s, %s" % (R[0], v(T[8]), v(M[0])))
@@ -193,11 +196,22 @@ def secp_mul_small(VB, K, acc=False):
 # ------------------------------------------------------------------------------------------------
 # secp256k1 square() (secp256k1.rs:634-713), common path: see secp256k1.hpp sqr_cxx for the literal
 # restatement.  Every data-dependent continuation of the reference (a +1 that ripples past the limb it
-# is added to; the fold's general carry rule) fires only when a 64-bit limb is all ones; the lanes
-# where one would fire are collected in the exception mask %9 and the caller recomputes those
-# wavefronts with sqr_cxx.
-# operands: %0-%7 r, %8 tmp (SGPR pair), %9 exc (SGPR pair), %10-%17 a, %18 977 (s)
-# acc=True (FEC_SECP_SQR_ACC): %9 is the caller's accumulator (read and written), not cleared first
+# is added to; the fold's general carry rule) fires only when a 64-bit limb is all ones, and the scalar
+# unit is kept out of finding those lanes: the statement flags a superset of them from five words.
+#   * Cross terms: the +1 of term (i, j) goes into limb i+j+2, which no earlier term has touched (term
+#     (1, 2) finds (0, 3)'s +1 there, added in the same chain here), so a ripple out of it needs the high
+#     word of that limb AS THE LIMB SQUARES LEFT IT to be all ones: W[7], W[9], W[11], W[13].
+#   * Folds: the carries out of limb 0 (at most four) are counted and added into limb 1 once, behind the
+#     last fold -- the same limb 1 whenever it does not wrap, and it wraps (a fold ripple, or the general
+#     carry rule behind one) only if its high word W[3] was all ones before the folds.
+# The unsigned maximum of the five words is all ones on every such lane (5 * 2^-32 per lane and square on
+# random input against the ~2^-63 of the exact condition: at 2^20 points a few wavefronts per launch
+# recompute one point operation).  The one scalar instruction left per cross term is the reference's
+# carry | carry2, the first chain's carry captured straight into %8 by its closing v_addc (VOP3).
+# operands: %0-%7 r, %8 tmp (SGPR pair), %9 exc (SGPR pair, written once), %10-%17 a, %18 977 (s)
+# acc=True (FEC_SECP_SQR_ACC): %9 is the caller's running maximum of top words (VGPR, read and written):
+# the five words and the result's own top word join it, and the caller's one compare per point operation
+# finds them (secp_step.hpp)
 # ------------------------------------------------------------------------------------------------
 def secp_sqr(VB, acc=False):
     A = ["%%%d" % (10 + i) for i in range(8)]
@@ -212,10 +226,9 @@ def secp_sqr(VB, acc=False):
         return r
 
     Z, Y = pair(), pair()  # Z = {x, 0} zero-extension pair; Y = {acc.hi, ovf}
+    ZERO = v(Z + 1)
     b = Block()
-    b.e("v_mov_b32_e32 %s, 0" % v(Z + 1))
-    if not acc:
-        b.e("s_mov_b64 %s, 0" % EXC)
+    b.e("v_mov_b32_e32 %s, 0" % ZERO)
 
     def mul64(x0, x1, y0, y1, pa, pb, pc):
         """p = (x1:x0)*(y1:y0): p0 = lo(pa), p1 = lo(pb), p2 = lo(pc), p3 = hi(pc)."""
@@ -223,15 +236,25 @@ def secp_sqr(VB, acc=False):
         b.e("v_mov_b32_e32 %s, %s" % (v(Z), v(pa + 1)))
         b.e("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (vp(pb), x0, y1, vp(Z)))
         b.e("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (vp(pb), x1, y0, vp(pb)))
-        b.e("v_addc_co_u32_e64 %s, vcc, 0, 0, vcc" % v(Y + 1))
+        b.e("v_addc_co_u32_e32 %s, vcc, 0, %s, vcc" % (v(Y + 1), ZERO))  # VOP2 on the zero register
         b.e("v_mov_b32_e32 %s, %s" % (v(Y), v(pb + 1)))
         b.e("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (vp(pc), x1, y1, vp(Y)))
         return [v(pa), v(pb), v(pc), v(pc + 1)]
 
     W = [None] * 16
+    dead = []  # the high halves of the first two pairs of a limb square are dead once it is done
     for i in range(4):  # 643-649: limb squares
         pa, pb, pc = pair(), pair(), pair()
         W[4 * i:4 * i + 4] = mul64(A[2 * i], A[2 * i + 1], A[2 * i], A[2 * i + 1], pa, pb, pc)
+        dead += [pa + 1, pb + 1]
+    TOP = EXC if acc else v(dead[0])  # the maximum of the words that decide every rare leg
+    E3 = v(dead[1])                   # (0, 3)'s +1, waiting for (1, 2)'s
+    if acc:
+        b.e("v_max3_u32 %s, %s, %s, %s" % (TOP, TOP, W[7], W[9]))
+        b.e("v_max3_u32 %s, %s, %s, %s" % (TOP, TOP, W[11], W[13]))
+    else:
+        b.e("v_max3_u32 %s, %s, %s, %s" % (TOP, W[7], W[9], W[11]))
+        b.e("v_max_u32_e32 %s, %s, %s" % (TOP, TOP, W[13]))
     xa, xb, xc = pair(), pair(), pair()  # cross products reuse one set of pairs
     for i in range(4):  # 652-679: doubled cross terms
         for j in range(i + 1, 4):
@@ -242,51 +265,63 @@ def secp_sqr(VB, acc=False):
             b.e("v_alignbit_b32 %s, %s, %s, 31" % (p1, p1, p0))
             b.e("v_lshlrev_b32_e32 %s, 1, %s" % (p0, p0))
             B = 2 * (i + j)
+            # carry out of limb i+j into %8, carry2 out of limb i+j+1 (which does not take carry) into VCC
             b.e("v_add_co_u32_e32 %s, vcc, %s, %s" % (W[B], W[B], p0))
-            b.e("v_addc_co_u32_e32 %s, vcc, %s, %s, vcc" % (W[B + 1], W[B + 1], p1))
-            b.e("s_mov_b64 %s, vcc" % TMP)
+            b.e("v_addc_co_u32_e64 %s, %s, %s, %s, vcc" % (W[B + 1], TMP, W[B + 1], p1))
             b.e("v_add_co_u32_e32 %s, vcc, %s, %s" % (W[B + 2], W[B + 2], p2))
             b.e("v_addc_co_u32_e32 %s, vcc, %s, %s, vcc" % (W[B + 3], W[B + 3], p3))
             b.e("s_or_b64 vcc, vcc, %s" % TMP)
-            b.e("v_addc_co_u32_e32 %s, vcc, 0, %s, vcc" % (W[B + 4], W[B + 4]))
+            if (i, j) == (0, 3):  # limb 5 is next touched by (1, 2)'s +1: both in one chain there
+                b.e("v_cndmask_b32_e64 %s, 0, 1, vcc" % E3)
+                continue
+            b.e("v_addc_co_u32_e32 %s, vcc, %s, %s, vcc" % (W[B + 4], E3 if (i, j) == (1, 2) else "0", W[B + 4]))
             b.e("v_addc_co_u32_e32 %s, vcc, 0, %s, vcc" % (W[B + 5], W[B + 5]))
-            if B + 6 < 16:
-                b.e("s_or_b64 %s, %s, vcc" % (EXC, EXC))
-    # 681-707: every high limb folded into limb 0 with the low 64 bits of limb * 0x1000003D1
+    # 681-707: every high limb folded into limb 0 with the low 64 bits of limb * 0x1000003D1; the carries out of limb 0
+    # are counted in K and enter limb 1 behind the last fold
     F = xa
     T = xb  # scratch word
+    K = v(xc)
     for i in range(4, 8):
         h0, h1 = W[2 * i], W[2 * i + 1]
         b.e("v_mad_u64_u32 %s, vcc, %s, %s, 0" % (vp(F), h0, C977))
         b.e("v_mul_lo_u32 %s, %s, %s" % (v(T), h1, C977))
         b.e("v_add3_u32 %s, %s, %s, %s" % (v(T), v(F + 1), v(T), h0))
-        dst = R if i == 7 else W  # the last fold leaves limbs 0..1 in the output operands
+        dst = R if i == 7 else W  # the last fold leaves limb 0 in the output operands
         b.e("v_add_co_u32_e32 %s, vcc, %s, %s" % (dst[0], W[0], v(F)))
         b.e("v_addc_co_u32_e32 %s, vcc, %s, %s, vcc" % (dst[1], W[1], v(T)))
-        b.e("v_addc_co_u32_e32 %s, vcc, 0, %s, vcc" % (dst[2], W[2]))
-        b.e("v_addc_co_u32_e32 %s, vcc, 0, %s, vcc" % (dst[3], W[3]))
-        b.e("s_or_b64 %s, %s, vcc" % (EXC, EXC))
+        b.e("v_addc_co_u32_e32 %s, vcc, 0, %s, vcc" % (K, ZERO if i == 4 else K))
+    b.e("v_add_co_u32_e32 %s, vcc, %s, %s" % (R[2], W[2], K))
+    b.e("v_addc_co_u32_e32 %s, vcc, 0, %s, vcc" % (R[3], W[3]))
     # limbs 2..3 (W[4..7]) are final after the cross terms: their last writers target the output
     # operands directly (those four outputs are early-clobber in the C++ wrapper)
     for i in range(4, 8):
         last = max(n for n, l in enumerate(b.lines) if l.split()[1].rstrip(",") == W[i])
-        assert not any(W[i] in l for l in b.lines[last + 1:]), W[i]
+        assert not any(re.search(r"\b%s\b" % W[i], l) for l in b.lines[last + 1:]), W[i]
         parts = b.lines[last].split(" ", 2)
         b.lines[last] = "%s %s, %s" % (parts[0], R[i], parts[2])
+    # limb 1's high word as the cross terms left it, and (acc) the result's top word, join the maximum
+    at = next(n for n, l in enumerate(b.lines) if l.startswith("v_mul_lo_u32"))  # inside the first fold
+    if acc:
+        b.lines.insert(at, "v_max3_u32 %s, %s, %s, %s" % (TOP, TOP, W[3], R[7]))
+    else:
+        b.lines.insert(at, "v_max_u32_e32 %s, %s, %s" % (TOP, TOP, W[3]))
+        b.e("v_cmp_eq_u32_e64 %s, -1, %s" % (EXC, TOP))
     return b, list(range(VB, nxt[0]))
 
 
 # ------------------------------------------------------------------------------------------------
 # secp256k1 Add / double / Sub (secp256k1.rs:353-440) for the ladder's fast step (secp_step.hpp): the 256-bit chain and
 # the short +-c on the carry (borrow) lanes in one statement, VCC handed straight from the chain to the short add.  The
-# carry (borrow) out of word 1 -- the continuation of secp256k1.hpp's add / dbl / sub -- is OR-ed into the caller's
-# accumulator instead of being tested; so is nothing else: add's and dbl's top-word condition is the caller's (the
-# result's top word is the chain's whenever no carry left word 1).
-# operands: %0-%7 x (in place: a on entry), %8 acc (SGPR pair, read and written), %9-%10 temporaries, %11-%18 b
+# carry (borrow) out of word 1 -- the continuation of secp256k1.hpp's add / dbl / sub -- is left in VCC, which is the
+# statement's ninth output: the caller ORs it into its accumulator in C++, so the compiler places that s_or_b64 (it
+# lands between this statement and the next one, where a statement that ended in it was followed by an s_nop: the
+# hazard recogniser cannot see that the last instruction of a statement is scalar).  Nothing else is accumulated:
+# add's and dbl's top-word condition is the caller's (the result's top word is the chain's whenever no carry left word 1).
+# operands: %0-%7 x (in place: a on entry), %8 VCC (not named in the text), %9-%10 temporaries, %11-%18 b
 # ------------------------------------------------------------------------------------------------
 def secp_addsub_acc(op):
     X = ["%%%d" % i for i in range(8)]
-    ACC, T1, T0 = "%8", "%9", "%10"
+    T1, T0 = "%9", "%10"
     Bop = X if op == "dbl" else ["%%%d" % (11 + i) for i in range(8)]
     first, rest = ("v_sub_co_u32_e32", "v_subb_co_u32_e32") if op == "sub" else ("v_add_co_u32_e32", "v_addc_co_u32_e32")
     b = Block()
@@ -297,7 +332,6 @@ def secp_addsub_acc(op):
     b.e("v_mul_u32_u24_e32 %s, 0x3d1, %s" % (T0, T1))
     b.e("%s %s, vcc, %s, %s" % (first, X[0], X[0], T0))
     b.e("%s %s, vcc, %s, %s, vcc" % (rest, X[1], X[1], T1))
-    b.e("s_or_b64 %s, %s, vcc" % (ACC, ACC))
     return b
 
 
