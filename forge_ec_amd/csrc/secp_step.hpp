@@ -9,6 +9,9 @@
 //     (borrow) out of word 1;
 //   * the condition of every reduce -- a result's top word all ones (2^-32 per lane) -- is folded into the unsigned
 //     maximum of the top words: one v_max3 per two results, one compare per point operation;
+//   * carries that need a 32-bit word within a few units of 2^32 (Mul's first product of a column, the square's +1
+//     inside a limb) are not computed at all: the words that decide them join the same maximum, which is tested
+//     against RARE_WORD instead of all ones;
 //   * the point operation tests both once, at its end.  If any lane of the wavefront met any of them, the whole
 //     wavefront recomputes that operation from its LDS operands with the exact code (the caller's padd_slots +
 //     secp::pdouble), which takes every leg where it must.  Otherwise every operation above computed exactly what the
@@ -30,17 +33,33 @@ using secp::pt;
 // the rare conditions met so far in one point operation
 struct Rare {
   lmask m = 0;   // lanes on which a field operation's rare leg would run
-  u32 top = 0;   // unsigned maximum of the top words of the reduced results: all ones iff one of them is
+  u32 top = 0;   // unsigned maximum of the words that decide a rare leg by being close to 2^32 (RARE_WORD)
 };
+// One threshold for every word in Rare::top; each condition below is a subset of `word >= RARE_WORD`:
+//   * the top word of a reduced result all ones (every reduce);
+//   * Mul's a.w[0] or b.w[7] >= 2^32 - 9 (see mul());
+//   * square's W[6], W[14] all ones, W[10] >= 0xFFFFFFFE, W[3] all ones (tools/gen_field_asm.py, secp_sqr).
+// Rate on random input, 2^-28 per word and lane: an addition folds 56 words (12 Mul x 3, 4 squares x 5), a doubling
+// 37 (2 Mul x 3, 2 mul_small, 5 squares x 5, 4 Add / double), so a wavefront flags 93 * 64 * 2^-28 = 2.2e-5 steps:
+// about 93 of the 8.4 million point operations of a 2^20 launch are recomputed with the exact code.
+constexpr u32 RARE_WORD = 0xFFFFFFF0u;
 // (measured against it: note_top as `rr.m |= lanes_where(r.w[7] == 0xFFFFFFFFu)`, one v_cmp per result straight into
 // m -- 12 more VALU and 27 more SALU per step, 28.30 against 28.23 ms at 2^20 on the same box, profiles/fast_step_r05/)
 FEC_DEV void note_top(Rare& rr, const fe& r) { rr.top = rr.top > r.w[7] ? rr.top : r.w[7]; }
-FEC_DEV bool met(const Rare& rr) { return (rr.m | lanes_where(rr.top == 0xFFFFFFFFu)) != 0; }
+FEC_DEV void note_word(Rare& rr, u32 x, u32 y) {
+  const u32 m = x > y ? x : y;
+  rr.top = rr.top > m ? rr.top : m;
+}
+FEC_DEV bool met(const Rare& rr) { return (rr.m | lanes_where(rr.top >= RARE_WORD)) != 0; }
 
-// Mul (442-507): secp::mul without its borrow continuation and reduce
+// Mul (442-507): secp::mul without its borrow continuation and reduce, and without the carry out of the first product
+// of columns 2..13 of the product scanning.  That product is a.w[0] * b.w[k] (k <= 7) or a.w[k - 7] * b.w[7], added to a
+// carry-in below 9 * 2^32: it passes 2^64 only if both factors are >= 2^32 - 9.  With a.w[0] and b.w[7] below RARE_WORD
+// (= 2^32 - 16) no such carry exists, so both words join the maximum that met() tests.
 FEC_DEV fe mul(const fe& a, const fe& b, Rare& rr) {
   fe r;
   lmask sc, sink;
+  note_word(rr, a.w[0], b.w[7]);
   asm(FEC_SECP_MUL_ACC_ASM
       : "=v"(r.w[0]), "=v"(r.w[1]), "=v"(r.w[2]), "=v"(r.w[3]), "=v"(r.w[4]), "=v"(r.w[5]), "=v"(r.w[6]),
         "=v"(r.w[7]), "=&s"(sc), "=&s"(sink), "+s"(rr.m)
@@ -71,8 +90,9 @@ FEC_DEV fe mul_small(const fe& a, Rare& rr) {
   note_top(rr, r);
   return r;
 }
-// square() (634-713): secp::sqr without its exc leg and reduce.  The statement itself folds the five words that
-// decide its rare legs, and the result's top word, into the running maximum (tools/gen_field_asm.py, secp_sqr).
+// square() (634-713): secp::sqr without its exc leg and reduce, and without the +1 chains' ripple inside the limb they
+// enter.  The statement itself folds the four words that decide its rare legs (each against RARE_WORD or a weaker
+// bound), and the result's top word, into the running maximum (tools/gen_field_asm.py, secp_sqr).
 FEC_DEV fe sqr(const fe& a, Rare& rr) {
   fe r;
   lmask tmp;

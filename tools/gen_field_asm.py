@@ -75,13 +75,21 @@ def interleave(main, side):
     return out
 
 
-def mul_wide_columns(A, B, VB, side_for_column=None, first_col_src=None, zero=None):
+def mul_wide_columns(A, B, VB, side_for_column=None, first_col_src=None, zero=None, rare_first=False):
     """Product scanning of A[0..7] x B[0..7] (operand strings).  Column k accumulates in the pair
     Q_k = v[VB+2k : VB+2k+1]; C = v[VB+30 : VB+31] is the carry pair {next column's carry-in low,
     overflow count}.  Returns the instruction list; afterwards T[k] = v(VB+2k) for k <= 14 and
     T[15] = v(VB+29).  side_for_column(k) -> instructions to interleave into column k.  zero = a register that holds 0
     through every column: the capture behind a column's first product is then VOP2 too (both its sources are constants
-    otherwise, which only VOP3 encodes)."""
+    otherwise, which only VOP3 encodes).
+    rare_first (needs zero): no capture behind the first product of columns 2..13.  The carry-in C is below 9 * 2^32
+    (induction: a column sums at most eight products below 2^64 and a carry-in below 9 * 2^32, so it stays below
+    8 * 2^64 + 9 * 2^32 and hands on less than 9 * 2^32), so that product overflows only if a_i * b_j >= 2^64 - 9 * 2^32,
+    which needs both factors >= 2^32 - 9.  One of them is a_0 (columns 2..7: a_0 * b_k) or b_7 (columns 8..13:
+    a_(k-7) * b_7): with a_0 < 2^32 - 9 and b_7 < 2^32 - 9 the dropped captures all add zero.  The CALLER owns that
+    condition (secp_step.hpp).  The capture behind the column's second product then starts the overflow word from the
+    zero register, as the first one did."""
+    assert zero or not rare_first
     C = VB + 30
     ins = ["v_mov_b32_e32 %s, 0" % v(C + 1)]
     for k in range(15):
@@ -94,11 +102,11 @@ def mul_wide_columns(A, B, VB, side_for_column=None, first_col_src=None, zero=No
                 src2 = "0" if k == 0 else vp(C)
                 main.append("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (vp(q), A[i], B[j], src2))
                 # carry-in < 2^32 for column 1 and the top column is bounded by the true product
-                if k >= 2 and k != 14:
+                if k >= 2 and k != 14 and not rare_first:
                     main.append(CAPTURE % (v(C + 1), zero) if zero else "v_addc_co_u32_e64 %s, vcc, 0, 0, vcc" % v(C + 1))
             else:
                 main.append("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (vp(q), A[i], B[j], vp(q)))
-                main.append(CAPTURE % (v(C + 1), v(C + 1)))
+                main.append(CAPTURE % (v(C + 1), zero if rare_first and n == 1 and k >= 2 else v(C + 1)))
         if k != 14:
             main.append("v_mov_b32_e32 %s, %s" % (v(C), v(q + 1)))
         side = side_for_column(k) if side_for_column else []
@@ -138,7 +146,8 @@ def secp_mul(VB, acc=False):
 
     b = Block()
     b.e("v_mov_b32_e32 %s, 0" % v(P + 1))
-    for s in mul_wide_columns(A, B, VB, side, zero=v(P + 1)):  # P's high half is 0 until the columns are done
+    # P's high half is 0 until the columns are done; acc: the caller flags a_0 and b_7 near 2^32 (rare_first)
+    for s in mul_wide_columns(A, B, VB, side, zero=v(P + 1), rare_first=acc):
         b.e(s)
     # V = T_hi + M - Q (mod 2^256), Q = {P.lo, sc}
     b.e("v_add_co_u32_e32 %s, vcc, %s, %s" % (R[0], v(T[8]), v(M[0])))
@@ -209,9 +218,16 @@ def secp_mul_small(VB, K, acc=False):
 # recompute one point operation).  The one scalar instruction left per cross term is the reference's
 # carry | carry2, the first chain's carry captured straight into %8 by its closing v_addc (VOP3).
 # operands: %0-%7 r, %8 tmp (SGPR pair), %9 exc (SGPR pair, written once), %10-%17 a, %18 977 (s)
-# acc=True (FEC_SECP_SQR_ACC): %9 is the caller's running maximum of top words (VGPR, read and written):
-# the five words and the result's own top word join it, and the caller's one compare per point operation
-# finds them (secp_step.hpp)
+# acc=True (FEC_SECP_SQR_ACC): %9 is the caller's running maximum of top words (VGPR, read and written), which the
+# caller tests once per point operation against a threshold a little below all ones (secp_step.hpp: RARE_WORD).  Here
+# the +1 of a cross term stops inside the limb it enters: the v_addc that carries it from the limb's low word W[2L]
+# into its high word is not issued, and the LOW words join the maximum in place of the high ones (a ripple past the
+# limb needs the ripple inside it first).  The +1 goes into limb L = i+j+2 as the limb squares left it:
+#   * L = 3, 7 (terms (0,1), (2,3)): W[6] + 1, W[14] + 1 wrap only from all ones;
+#   * L = 5 (term (1,2), with (0,3)'s +1 in the same chain): W[10] + 2 wraps only from >= 0xFFFFFFFE;
+#   * L = 4, 6 (terms (0,2), (1,3)): W[8], W[12] are the low words of a_4^2 and a_6^2, a square is 0 or 1 mod 4, all
+#     ones is 3 mod 4: these never wrap, and need no flag.
+# So W[6], W[10], W[14] (threshold <= 0xFFFFFFFE), limb 1's W[3] and the result's own top word join the maximum.
 # ------------------------------------------------------------------------------------------------
 def secp_sqr(VB, acc=False):
     A = ["%%%d" % (10 + i) for i in range(8)]
@@ -250,8 +266,8 @@ def secp_sqr(VB, acc=False):
     TOP = EXC if acc else v(dead[0])  # the maximum of the words that decide every rare leg
     E3 = v(dead[1])                   # (0, 3)'s +1, waiting for (1, 2)'s
     if acc:
-        b.e("v_max3_u32 %s, %s, %s, %s" % (TOP, TOP, W[7], W[9]))
-        b.e("v_max3_u32 %s, %s, %s, %s" % (TOP, TOP, W[11], W[13]))
+        b.e("v_max3_u32 %s, %s, %s, %s" % (TOP, TOP, W[6], W[10]))
+        b.e("v_max_u32_e32 %s, %s, %s" % (TOP, TOP, W[14]))
     else:
         b.e("v_max3_u32 %s, %s, %s, %s" % (TOP, W[7], W[9], W[11]))
         b.e("v_max_u32_e32 %s, %s, %s" % (TOP, TOP, W[13]))
@@ -275,7 +291,8 @@ def secp_sqr(VB, acc=False):
                 b.e("v_cndmask_b32_e64 %s, 0, 1, vcc" % E3)
                 continue
             b.e("v_addc_co_u32_e32 %s, vcc, %s, %s, vcc" % (W[B + 4], E3 if (i, j) == (1, 2) else "0", W[B + 4]))
-            b.e("v_addc_co_u32_e32 %s, vcc, 0, %s, vcc" % (W[B + 5], W[B + 5]))
+            if not acc:  # acc: the caller recomputes the lanes on which W[B + 4] can wrap
+                b.e("v_addc_co_u32_e32 %s, vcc, 0, %s, vcc" % (W[B + 5], W[B + 5]))
     # 681-707: every high limb folded into limb 0 with the low 64 bits of limb * 0x1000003D1; the carries out of limb 0
     # are counted in K and enter limb 1 behind the last fold
     F = xa
