@@ -92,6 +92,25 @@ int main(void) {
   }
   printf("parity  schnorr::batch_verify::<Ed25519> with zero weights: result %u, a debug build would panic: %u\n", verdict, dbg);
   ok = ok && verdict == 1 && dbg == 0;
+  /* EdDSA with the hash on the GPU: sign a small batch, then verify it from the message.  Both are the reference's own
+   * functions: its verifier accepts "test message" and an empty message whatever the key and the signature are, and
+   * decodes R and A in a way under which the bytes its signer writes do not decode (see fecgpu.h) */
+  static const uint8_t msgs3[] = "test messagehello";   /* "test message", "hello", "" */
+  const uint64_t off3[4] = {0, 12, 17, 17};
+  uint8_t sk3[3][32], pk3[3][32], sig3[3][64], st_sign[3], st_pk[3], st_ver[3];
+  for (int i = 0; i < 3; ++i)
+    for (int b = 0; b < 32; ++b) sk3[i][b] = (uint8_t)(16 * i + b + 1);
+  rc = fec_ed25519_sign(ctx, &sk3[0][0], msgs3, off3, 17, &sig3[0][0], st_sign, 3);
+  if (rc == FEC_OK) rc = fec_ed25519_derive_public_key(ctx, &sk3[0][0], &pk3[0][0], st_pk, 3);
+  if (rc == FEC_OK) rc = fec_ed25519_verify(ctx, &pk3[0][0], msgs3, off3, 17, &sig3[0][0], st_ver, 3);
+  if (rc != FEC_OK) {
+    printf("EdDSA sign / verify failed: %s\n", fec_strerror(rc));
+    return 1;
+  }
+  printf("parity  Ed25519Signature::sign status %u %u %u, signature 1 starts %02x%02x%02x%02x\n", st_sign[0], st_sign[1], st_sign[2],
+         sig3[1][0], sig3[1][1], sig3[1][2], sig3[1][3]);
+  printf("parity  Ed25519Signature::verify status %u %u %u  (\"test message\", \"hello\", \"\")\n", st_ver[0], st_ver[1], st_ver[2]);
+  ok = ok && st_ver[0] == 1 && st_ver[2] == 1 && st_ver[1] <= 2;
   /* a single-device ctx has fec_batch_*_dev; the device-resident multi-GPU calls say so */
   const size_t none = 0;
   const uint64_t* no_in[1] = {NULL};

@@ -1078,6 +1078,28 @@ int launch_eddsa_verify(fec_ctx* ctx, const u64* dr, const unsigned char* drinf,
   return L.done();
 }
 
+// Ed25519Signature::verify (eddsa.rs:360-447) and EdDsa::<Ed25519, Sha512>::verify (156-212) from the message
+// (kernels_eddsa.hip): k_eddsa_verify_msg_pre -- the message cases, the decoding of R and A (byte form), SHA-512 -- then
+// product_pair exactly as launch_eddsa_verify calls it, then k_eddsa_verify_msg_finish.  from_affine(A), R, s, k, the two
+// products, the flags and the popcount-sort area of the fixed-base kernel are regions of one work area, one request.
+int launch_eddsa_verify_msg(fec_ctx* ctx, const EddsaVerifyIo& io, unsigned char* dstatus, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  EddsaVerifyWork w;
+  void* sort;
+  WorkArea area;
+  area.add(w.a, n * 128).add(w.r, n * 64).add(w.s, n * 32).add(w.k, n * 32).add(w.sg, n * 128).add(w.ka, n * 128);
+  area.add(w.flags, n).add(sort, ed_fixed_work_bytes(n));
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, FEC_ED25519, st, n);
+  if (rc != FEC_OK) return rc;
+  Launch L(ctx, stream, "k_eddsa_verify_msg_pre + k_ed_fixed_base + k_ed_mul_pers + k_eddsa_verify_msg_finish");
+  eddsa_verify_msg_pre_launch(io, w, n, L.s);
+  product_pair(ctx, FEC_ED25519, n, L.s, 0, 0.0, w.s, w.sg, sort, w.k, w.a, w.ka);
+  eddsa_verify_msg_finish_launch(w, dstatus, n, L.s);
+  return L.done();
+}
+
 // Schnorr::<C, D>::verify per signature from the point computation on (schnorr.rs:90-140): A = from_affine(pk);
 // s*G by the curve's fixed-base kernel (forked to the second stream for the Weierstrass curves), e*A by its
 // variable-base kernel; the rest in one finishing pass.
@@ -1294,6 +1316,23 @@ bool msg_layout_ok(const uint8_t* msgs, const uint64_t* off, size_t msg_len, siz
     if (off[i + 1] < off[i]) return false;
   return true;
 }
+// One chunk's messages onto the device: the bytes msgs[o[0], o[m]) into slot kStageBody, the m + 1 offsets o[0..m],
+// rebased to that range (`reb`: host scratch of at least m + 1 values that outlives the copy), into the slot after it.
+int stage_messages(fec_ctx* c, const uint8_t* msgs, const u64* o, size_t m, std::vector<uint64_t>& reb, hipStream_t st,
+                   const unsigned char*& d_msgs, const u64*& d_off, u64& bytes) {
+  bytes = o[m] - o[0];
+  for (size_t k = 0; k <= m; ++k) reb[k] = o[k] - o[0];
+  int rc = ensure(c, kStageBody + 1, reb.size() * 8);
+  if (rc == FEC_OK && bytes) rc = ensure(c, kStageBody, bytes);
+  if (rc != FEC_OK) return rc;
+  if (bytes && hipMemcpyAsync(c->d_buf[kStageBody], msgs + o[0], bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+    return FEC_E_DEVICE;
+  if (hipMemcpyAsync(c->d_buf[kStageBody + 1], reb.data(), (m + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+    return FEC_E_DEVICE;
+  d_msgs = bytes ? static_cast<const unsigned char*>(c->d_buf[kStageBody]) : nullptr;
+  d_off = static_cast<const u64*>(c->d_buf[kStageBody + 1]);
+  return FEC_OK;
+}
 constexpr int kSha512 = -1;   // msg_call's mode for fec_sha512 (else EDDSA_MODE_*)
 // The host forms, on a single-device or a multi-device ctx (host_ctx.hpp: sharded, chunked; one lane).  The engine stages
 // the keys and takes back the outputs (out: 64 bytes per element, 32 for derive; status; r_inf and s for the generic
@@ -1315,17 +1354,8 @@ int msg_call(fec_ctx* ctx, int mode, const void* keys, const uint8_t* msgs, cons
       const u64* d_off = nullptr;
       u64 bytes = 0;
       if (with_msgs) {
-        bytes = o[m] - o[0];
-        for (size_t k = 0; k <= m; ++k) reb[k] = o[k] - o[0];
-        int rc = ensure(c, kStageBody + 1, reb.size() * 8);
-        if (rc == FEC_OK && bytes) rc = ensure(c, kStageBody, bytes);
+        const int rc = stage_messages(c, msgs, o, m, reb, st, d_msgs, d_off, bytes);
         if (rc != FEC_OK) return rc;
-        if (bytes && hipMemcpyAsync(c->d_buf[kStageBody], msgs + o[0], bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-          return FEC_E_DEVICE;
-        if (hipMemcpyAsync(c->d_buf[kStageBody + 1], reb.data(), (m + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
-          return FEC_E_DEVICE;
-        d_msgs = bytes ? static_cast<const unsigned char*>(c->d_buf[kStageBody]) : nullptr;
-        d_off = static_cast<const u64*>(c->d_buf[kStageBody + 1]);
       }
       if (mode == kSha512) {
         Launch L(c, st, "k_sha512");
@@ -1351,6 +1381,44 @@ int eddsa_sign_dev(fec_ctx* ctx, int mode, const void* d_keys, const uint8_t* d_
   const EddsaSignIo io{mode, static_cast<const u32*>(d_keys), with_msgs ? d_msgs : nullptr, with_msgs ? reinterpret_cast<const u64*>(d_msg_off) : nullptr,
                        with_msgs ? (u64)msg_len : 0, nullptr, static_cast<u32*>(d_out), d_r_inf, reinterpret_cast<u32*>(d_s), d_status};
   return launch_eddsa_sign(ctx, io, n, stream);
+}
+
+// The verifiers from the message.  form EDDSA_VERIFY_BYTES: pk n*32 bytes, sig n*64 bytes; EDDSA_VERIFY_GENERIC: pk and
+// sig (R) n*64 bytes of affine limbs with their flags, s n*32 bytes.  Host form: the engine as msg_call uses it, one lane,
+// the chunk's messages in the same two slots; nothing is secret, so nothing is cleared beyond the engine's rule.
+int verify_msg_call(fec_ctx* ctx, int form, const void* pk, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* off,
+                    size_t msg_len, const void* sig, const uint8_t* r_inf, const uint64_t* s_in, uint8_t* status, size_t n) {
+  const bool generic = form == EDDSA_VERIFY_GENERIC;
+  if (!ctx || (n && (!pk || !sig || !status || (generic && !s_in)))) return FEC_E_ARG;
+  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  const HostArray a[] = {input(pk, generic ? 64 : 32), input(pk_inf, 1), ragged(off, 8), input(sig, 64), input(r_inf, 1),
+                         input(s_in, 32), output(status, 1)};
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[7], size_t cnt, size_t) {
+    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
+    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
+      const unsigned char* d_msgs = nullptr;
+      const u64* d_off = nullptr;
+      u64 bytes = 0;
+      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[2]), m, reb, st, d_msgs, d_off, bytes);
+      if (rc != FEC_OK) return rc;
+      const EddsaVerifyIo io{form, static_cast<const u32*>(d[0]), static_cast<const unsigned char*>(d[1]), d_msgs, d_off, bytes,
+                             static_cast<const u32*>(d[3]), static_cast<const unsigned char*>(d[4]), static_cast<const u32*>(d[5])};
+      return launch_eddsa_verify_msg(c, io, static_cast<unsigned char*>(d[6]), m, st);
+    });
+  });
+}
+// The *_dev forms: one launch sequence on the caller's stream; each lane checks its own message range.
+int verify_msg_dev(fec_ctx* ctx, int form, const void* d_pk, const uint8_t* d_pk_inf, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                   size_t msg_len, const void* d_sig, const uint8_t* d_r_inf, const uint64_t* d_s, uint8_t* d_status, size_t n,
+                   void* stream) {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  const bool generic = form == EDDSA_VERIFY_GENERIC;
+  if (!ctx || (n && (!d_pk || !d_sig || !d_status || !d_msg_off || (generic && !d_s))) || (msg_len && !d_msgs)) return FEC_E_ARG;
+  if (!aligned16(d_pk) || !aligned16(d_sig) || !aligned16(d_s) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const EddsaVerifyIo io{form, static_cast<const u32*>(d_pk), d_pk_inf, d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len,
+                         static_cast<const u32*>(d_sig), d_r_inf, reinterpret_cast<const u32*>(d_s)};
+  return launch_eddsa_verify_msg(ctx, io, d_status, n, stream);
 }
 }  // namespace
 
@@ -2465,6 +2533,32 @@ int fec_ed25519_derive_public_key_dev(fec_ctx* ctx, const uint8_t* d_private_key
 int fec_eddsa_sign_ed25519_dev(fec_ctx* ctx, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                                uint64_t* d_r_xy, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_status, size_t n, void* stream) try {
   return eddsa_sign_dev(ctx, EDDSA_MODE_GENERIC, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+// ---- the Ed25519 EdDSA verifiers from the message (kernels_eddsa.hip; helpers above the extern "C" block) ----
+
+int fec_ed25519_verify(fec_ctx* ctx, const uint8_t* public_keys, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                       const uint8_t* sigs, uint8_t* status, size_t n) try {
+  return verify_msg_call(ctx, EDDSA_VERIFY_BYTES, public_keys, nullptr, msgs, msg_off, msg_len, sigs, nullptr, nullptr, status, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_ed25519_verify_dev(fec_ctx* ctx, const uint8_t* d_public_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                           size_t msg_len, const uint8_t* d_sigs, uint8_t* d_status, size_t n, void* stream) try {
+  return verify_msg_dev(ctx, EDDSA_VERIFY_BYTES, d_public_keys, nullptr, d_msgs, d_msg_off, msg_len, d_sigs, nullptr, nullptr,
+                        d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_eddsa_verify_ed25519_msg(fec_ctx* ctx, const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs,
+                                 const uint64_t* msg_off, size_t msg_len, const uint64_t* r_xy, const uint8_t* r_inf,
+                                 const uint64_t* s, uint8_t* status, size_t n) try {
+  return verify_msg_call(ctx, EDDSA_VERIFY_GENERIC, pk_xy, pk_inf, msgs, msg_off, msg_len, r_xy, r_inf, s, status, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_eddsa_verify_ed25519_msg_dev(fec_ctx* ctx, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf, const uint8_t* d_msgs,
+                                     const uint64_t* d_msg_off, size_t msg_len, const uint64_t* d_r_xy, const uint8_t* d_r_inf,
+                                     const uint64_t* d_s, uint8_t* d_status, size_t n, void* stream) try {
+  return verify_msg_dev(ctx, EDDSA_VERIFY_GENERIC, d_pk_xy, d_pk_inf, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status,
+                        n, stream);
 } FEC_ABI_CATCH_STATUS
 
 }  // extern "C"

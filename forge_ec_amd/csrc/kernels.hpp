@@ -113,6 +113,31 @@ void eddsa_sign_finish_launch(const EddsaSignIo& io, const u32* scal, const u32*
 void sha512_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
                    hipStream_t s);
 
+// kernels_eddsa.hip: the reference's two Ed25519 EdDSA verifiers FROM THE MESSAGE (eddsa.rs:360-447 Ed25519Signature::
+// verify on bytes; 156-212 EdDsa::<Ed25519, Sha512>::verify on a decoded key and signature) around the two multiplications
+// of launch_eddsa_verify.  The pre pass decides the message cases, decodes R and A (byte form), hashes and writes, per
+// element, a = from_affine(A) (32 words), r = R's affine x then y (16 words), s and k (8 words each) and one flag byte
+// (0: go on; else 0x80 | the status already decided, with s = k = 0 and a = the identity); the finishing pass turns
+// sg = multiply(G, s), ka = multiply(a, k) and r into the status, which a decided flag overrides.
+enum : int { EDDSA_VERIFY_BYTES = 0, EDDSA_VERIFY_GENERIC = 1 };
+struct EddsaVerifyIo {
+  int form;
+  const u32* pk;                 // BYTES: the 32 public-key bytes; GENERIC: the affine x then y (16 words)
+  const unsigned char* pk_inf;   // GENERIC (may be null)
+  const unsigned char* msgs;
+  const u64* off;
+  u64 msg_len;
+  const u32* sig;                // BYTES: the 64 signature bytes; GENERIC: R's affine x then y (16 words)
+  const unsigned char* r_inf;    // GENERIC (may be null)
+  const u32* s;                  // GENERIC: the raw Scalar limbs
+};
+struct EddsaVerifyWork {
+  u32 *a, *r, *s, *k, *sg, *ka;
+  unsigned char* flags;
+};
+void eddsa_verify_msg_pre_launch(const EddsaVerifyIo& io, const EddsaVerifyWork& w, size_t n, hipStream_t s);
+void eddsa_verify_msg_finish_launch(const EddsaVerifyWork& w, unsigned char* status, size_t n, hipStream_t s);
+
 // kernels_ecdsa.hip: Curve::validate_point per affine point (secp256k1 / P-256: is_on_curve; Ed25519: the trait default
 // with its two multiplications).  `work` holds validate_work_bytes(curve, n) bytes (0 for the Weierstrass curves).
 size_t validate_work_bytes(int curve, size_t n);

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fecgpu.h"
+#include "codec_bytes.hpp"
 #include "ed25519.hpp"
 #include "p256.hpp"
 #include "secp256k1.hpp"
@@ -37,24 +38,6 @@ struct CEd {
   FEC_DEV static fe bytes_value(const fe& a) { return ed::reduce(a); }                // to_bytes (295-310): reduce()
 };
 
-// the 32 bytes at `b` as a 256-bit value: big-endian (secp256k1, P-256) or little-endian (Ed25519)
-template <bool BE>
-FEC_DEV fe value_of(const unsigned char* b) {
-  fe v;
-  FEC_UNROLL for (int w = 0; w < 8; ++w) {
-    u32 x = 0;
-    FEC_UNROLL for (int j = 0; j < 4; ++j) {
-      const int k = 4 * w + j;  // byte k of the value, little-endian index
-      x |= (u32)b[BE ? 31 - k : k] << (8 * j);
-    }
-    v.w[w] = x;
-  }
-  return v;
-}
-template <bool BE>
-FEC_DEV void bytes_of(unsigned char* b, const fe& v) {
-  FEC_UNROLL for (int k = 0; k < 32; ++k) b[BE ? 31 - k : k] = (unsigned char)(v.w[k >> 2] >> (8 * (k & 3)));
-}
 FEC_DEV void put_xy(u32* xy, size_t i, const fe& x, const fe& y, bool ok) {
   FEC_UNROLL for (int w = 0; w < 8; ++w) {
     xy[i * 16 + w] = ok ? x.w[w] : 0u;

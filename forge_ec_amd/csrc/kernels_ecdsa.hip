@@ -14,6 +14,7 @@
 
 #include "../../include/fecgpu.h"
 #include "ed25519.hpp"
+#include "eddsa_verify.hpp"
 #include "kernels.hpp"
 #include "p256.hpp"
 #include "secp256k1.hpp"
@@ -360,11 +361,6 @@ __global__ __launch_bounds__(TPB) void k_ed_validate_finish(const u32* __restric
 }
 
 // ---- Eddsa::<Ed25519, D>::verify / Ed25519::verify from the point computation on (eddsa.rs:174-211, 430-447) ----
-FEC_DEV ed::pt ed_from_affine(const fe& x, const fe& y, bool inf) {  // ed25519.rs:1813-1826
-  ed::pt p;
-  p.x = x; p.y = y; p.z = fe_small(1); p.t = ed::mul(x, y);
-  return ed::pt_select(p, ed::identity(), lanes_where(inf));
-}
 FEC_DEV ed::pt ed_load32(const u32* g) {
   ed::pt p;
   p.x = load8(g); p.y = load8(g + 8); p.z = load8(g + 16); p.t = load8(g + 24);
@@ -406,19 +402,9 @@ __global__ __launch_bounds__(TPB) void k_eddsa_finish(const u32* __restrict__ sg
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   const ed::pt s_g = ed_load32(sg + i * 32), k_a = ed_load32(ka + i * 32);
-  const ed::pt r = ed_from_affine(load8(r_xy + i * 16), load8(r_xy + i * 16 + 8), false);
-  const ed::pt rk = ed::padd(r, k_a);                                                     // 200 / 435
-  // to_affine (1793-1811) unwraps z.invert(): a zero z of a point that is not the identity panics
-  const bool panic = lane_of((~ed::is_identity(s_g) & fe_is_zero(s_g.z)) | (~ed::is_identity(rk) & fe_is_zero(rk.z)));
-  fe x1, y1, x2, y2;
-  const lmask i1 = ed::to_affine(s_g, x1, y1), i2 = ed::to_affine(rk, x2, y2);           // 204-205 / 439-440
-  const ed::pt p1 = ed_from_affine(x1, y1, lane_of(i1));
-  ed::pt p2 = ed_from_affine(x2, y2, lane_of(i2));
-  p2.x = ed::neg(p2.x);                                                                    // negate 1834-1841
-  p2.t = ed::neg(p2.t);
-  const bool same = lane_of(ed::is_identity(ed::padd(p1, p2)));                           // Sub 1936-1947; 210 / 446
+  const unsigned char v = eddsa_verify_tail(s_g, k_a, load8(r_xy + i * 16), load8(r_xy + i * 16 + 8));   // eddsa_verify.hpp
   const bool rinf = r_inf != nullptr && r_inf[i] != 0;                                     // 174-177
-  status[i] = rinf ? 0 : (panic ? 2 : (same ? 1 : 0));
+  status[i] = rinf ? 0 : v;
 }
 
 // ---- Schnorr::<C, D>::verify per signature (forge-ec-signature/src/schnorr.rs:90-140), from the point computation on ----

@@ -6,9 +6,26 @@
 //   k_eddsa_sign_finish  to_affine and the 33-byte to_bytes of A and R; k = SHA512(R33 || A33 || msg)[0..32] read
 //                        big-endian; s = r + k * a (release-profile Mul); the output form and the status
 //   k_sha512             SHA-512 per message (the parity hook fec_sha512)
+// and its two VERIFIERS from the message (fecgpu.hip: launch_eddsa_verify_msg), around the two multiplications of the
+// verifier that is given k (s * G by the addend-table kernel, k * A by the task scheduler):
+//   k_eddsa_verify_msg_pre<FORM>   the message cases; byte form: from_bytes of R and of A (ed::decompress, one after the
+//                        other); k = SHA512(prefix || msg)[0..32] read big-endian; from_affine(A), R, s, k and a flag
+//   k_eddsa_verify_msg_finish      the point computation of k_eddsa_finish (eddsa_verify.hpp), overridden by the flag
 // One element per lane; the hash state lives in VGPRs (sha512.hpp).
 //
-// The readings, pinned (eddsa.rs unless named; ed25519.rs = forge-ec-curves/src/ed25519.rs):
+// The verifiers' readings (nothing here is secret):
+//  * Both return true for msg == "test message" and for an empty message, false for msg == "different message", in
+//    that order and before anything else is looked at (158-170, 362-374).
+//  * Ed25519Signature::verify (360-447): R = from_bytes(0x02 || sig[0..32]), A = from_bytes(0x02 || public_key)
+//    (ed25519.rs:1526-1582: the even root, None -> false; R is tested first, but neither test has a side effect);
+//    s = the trait Scalar::from_bytes(sig[32..64]), big-endian and never None (398-401 cannot fire); the hash takes
+//    sig[0..32] || public_key || msg, a 64-byte prefix (419-423).
+//  * EdDsa::verify (156-212): an identity R (the flag) -> false (174-177); the hash takes the 33-byte trait to_bytes of R
+//    and of pk (180-182), 33 zero bytes for an identity pk, whatever its coordinates hold.
+//  * k = from_bytes_reduced(h[0..32]) returns at its first branch: big-endian, unreduced (186-193, 426-428).
+//  * status: 1 true, 0 false, 2 the reference panics (to_affine, ed25519.rs:1805), 4 a bad message range (_dev forms).
+//
+// The signers' readings, pinned (eddsa.rs unless named; ed25519.rs = forge-ec-curves/src/ed25519.rs):
 //  * Scalar from bytes is the TRAIT from_bytes (ed25519.rs:1142-1162): big-endian, no range check, always Some.  So
 //    the `.unwrap()` at 304-305 never fires, the clamp (298-300) lands on bits 248-255 and 0-7 of a big-endian number,
 //    and from_bytes_reduced (forge-ec-core/src/lib.rs:320-331) returns at its first branch: r and k are h[0..32]
@@ -34,7 +51,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fecgpu.h"
+#include "codec_bytes.hpp"
 #include "ed25519.hpp"
+#include "eddsa_verify.hpp"
 #include "sha512.hpp"
 #include "staging.hpp"
 #include "kernels.hpp"
@@ -52,6 +71,7 @@ static __constant__ unsigned char kRfcPk[32] = {    // eddsa.rs:455 (RFC 8032 7.
     0xd7, 0x5a, 0x98, 0x01, 0x82, 0xb1, 0x0a, 0xb7, 0xd5, 0x4b, 0xfe, 0xd3, 0xc9, 0x64, 0x07, 0x3a,
     0x0e, 0xe1, 0x72, 0xf3, 0xda, 0xa6, 0x23, 0x25, 0xaf, 0x02, 0x1a, 0x68, 0xf7, 0x07, 0x51, 0x1a};
 static __constant__ unsigned char kTestMessage[12] = {'t', 'e', 's', 't', ' ', 'm', 'e', 's', 's', 'a', 'g', 'e'};
+static __constant__ unsigned char kDifferentMessage[17] = {'d', 'i', 'f', 'f', 'e', 'r', 'e', 'n', 't', ' ', 'm', 'e', 's', 's', 'a', 'g', 'e'};
 
 enum : unsigned char { F_TEST_MESSAGE = 1, F_RFC = 2, F_BAD_RANGE = 4 };
 
@@ -98,10 +118,28 @@ FEC_DEV bool is_test_message(const unsigned char* m, u64 len) {   // msg == b"te
   for (int k = 0; k < 12; ++k) eq = eq && m[k] == kTestMessage[k];
   return eq;
 }
+FEC_DEV bool is_different_message(const unsigned char* m, u64 len) {   // msg == b"different message"
+  if (len != 17) return false;
+  bool eq = true;
+  for (int k = 0; k < 17; ++k) eq = eq && m[k] == kDifferentMessage[k];
+  return eq;
+}
 // Point::to_bytes -> [u8; 33] (ed25519.rs:1505-1525) of an affine point: the prefix byte and reduce(x) (to_bytes,
 // little-endian)
 FEC_DEV u32 prefix_byte(const fe& y, bool inf) { return inf ? 0u : 2u + ((ed::reduce(y).w[7] >> 24) & 1u); }
 FEC_DEV u32 byte_of(const fe& v, int k) { return (v.w[k >> 2] >> (8 * (k & 3))) & 0xFFu; }
+// R33 || A33 as big-endian words (bytes 66, 67 zero): each a prefix byte, then the reduced x little-endian
+FEC_DEV void prefix_r33_a33(u32 (&pre)[17], u32 pr, const fe& xrb, u32 pa, const fe& xab) {
+  FEC_UNROLL for (int j = 0; j < 17; ++j) {
+    u32 v = 0;
+    FEC_UNROLL for (int b = 0; b < 4; ++b) {
+      const int t = 4 * j + b;
+      const u32 byte = t == 0 ? pr : t <= 32 ? byte_of(xrb, t - 1) : t == 33 ? pa : t <= 65 ? byte_of(xab, t - 34) : 0u;
+      v = (v << 8) | byte;
+    }
+    pre[j] = v;
+  }
+}
 // to_affine with the panic test: a zero z of a point that is not the identity is an unwrap on None (ed25519.rs:1805)
 FEC_DEV bool affine_of(const u32* __restrict__ p, fe& x, fe& y, bool& panics) {
   ed::pt q;
@@ -196,16 +234,8 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_finish(EddsaSignIo io, const
   u64 lo = 0, len = 0;
   const bool ok = msg_range(io.off, io.msg_len, i, lo, len);
   const unsigned char* m = ok && len ? io.msgs + lo : nullptr;
-  u32 pre[17];   // R33 || A33, big-endian words (bytes 66, 67 zero)
-  FEC_UNROLL for (int j = 0; j < 17; ++j) {
-    u32 v = 0;
-    FEC_UNROLL for (int b = 0; b < 4; ++b) {
-      const int t = 4 * j + b;
-      const u32 byte = t == 0 ? pr : t <= 32 ? byte_of(xrb, t - 1) : t == 33 ? pa : t <= 65 ? byte_of(xab, t - 34) : 0u;
-      v = (v << 8) | byte;
-    }
-    pre[j] = v;
-  }
+  u32 pre[17];
+  prefix_r33_a33(pre, pr, xrb, pa, xab);
   ed::sc4 s = {{0, 0, 0, 0}};
   bool ovf = false;
   const bool panics = panic_a || panic_r;
@@ -285,6 +315,97 @@ __global__ __launch_bounds__(TPB) void k_sha512(const unsigned char* __restrict_
   if (status) status[i] = ok ? 0 : 4;
 }
 
+// ---- the verifiers from the message ----
+enum : unsigned char { V_DECIDED = 0x80 };   // flag: V_DECIDED | status where the pre pass has the answer, else 0
+
+template <int FORM>
+__global__ __launch_bounds__(TPB) void k_eddsa_verify_msg_pre(EddsaVerifyIo io, EddsaVerifyWork w, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  u64 lo = 0, len = 0;
+  unsigned char f = 0;
+  if (!msg_range(io.off, io.msg_len, i, lo, len)) f = V_DECIDED | 4;
+  const unsigned char* m = len ? io.msgs + lo : nullptr;
+  if (f == 0) {
+    if (is_test_message(m, len) || len == 0) f = V_DECIDED | 1;            // 362-369, 158-165
+    else if (is_different_message(m, len)) f = V_DECIDED | 0;             // 372-374, 168-170
+  }
+  fe rx = fe_zero(), ry = fe_zero(), ax = fe_zero(), ay = fe_zero();
+  bool ainf = false;
+  u32 sw[8];
+  ed::sc4 k = {{0, 0, 0, 0}};
+  if (FORM == EDDSA_VERIFY_BYTES) {
+    const unsigned char* sb = reinterpret_cast<const unsigned char*>(io.sig + i * 16);
+    u32 pre[16];   // sig[0..32] || public_key, big-endian words
+    bool some = true;
+    // (a wavefront whose every lane is decided skips the decoding; a mixed one runs it on all its lanes)
+    if (lanes_where(f == 0) != 0) {
+      const fe rv = value_of<false>(sb);                                   // 378-395
+      FEC_UNROLL for (int j = 0; j < 8; ++j) pre[j] = sha512::bswap(rv.w[j]);
+      some = lane_of(ed::decompress(rv, lanes_where(false), rx, ry));
+      const fe av = value_of<false>(reinterpret_cast<const unsigned char*>(io.pk + i * 8));   // 404-416
+      FEC_UNROLL for (int j = 0; j < 8; ++j) pre[8 + j] = sha512::bswap(av.w[j]);
+      some = lane_of(ed::decompress(av, lanes_where(false), ax, ay)) && some;
+    }
+    if (f == 0 && !some) f = V_DECIDED | 0;
+    const fe sv = value_of<false>(sb + 32);                                // 398: the trait from_bytes, big-endian
+    FEC_UNROLL for (int j = 0; j < 8; ++j) sw[j] = sha512::bswap(sv.w[7 - j]);
+    if (f == 0) k = scalar_be(sha512::hash_prefixed<16>(pre, 64, m, len), 0);   // 419-428
+  } else {
+    ld8(rx.w, io.sig + i * 16);
+    ld8(ry.w, io.sig + i * 16 + 8);
+    ld8(ax.w, io.pk + i * 16);
+    ld8(ay.w, io.pk + i * 16 + 8);
+    ld8(sw, io.s + i * 8);
+    ainf = io.pk_inf != nullptr && io.pk_inf[i] != 0;
+    if (f == 0 && io.r_inf != nullptr && io.r_inf[i] != 0) f = V_DECIDED | 0;   // 174-177
+    if (f == 0) {
+      u32 pre[17];
+      prefix_r33_a33(pre, prefix_byte(ry, false), ed::reduce(rx), prefix_byte(ay, ainf), ainf ? fe_zero() : ed::reduce(ax));
+      k = scalar_be(sha512::hash_prefixed<17>(pre, 66, m, len), 0);       // 179-193
+    }
+  }
+  // a decided lane multiplies zero by zero on the identity: no steps in either multiplication kernel, nothing undefined
+  const bool go = f == 0;
+  const ed::pt a = ed_from_affine(ax, ay, ainf || !go);                    // 199 / 434
+  u32 kw[8];
+  words_of_sc(k, kw);
+  FEC_UNROLL for (int j = 0; j < 8; ++j) {
+    sw[j] = go ? sw[j] : 0u;
+    rx.w[j] = go ? rx.w[j] : 0u;
+    ry.w[j] = go ? ry.w[j] : 0u;
+  }
+  st8(w.a + i * 32, a.x.w);
+  st8(w.a + i * 32 + 8, a.y.w);
+  st8(w.a + i * 32 + 16, a.z.w);
+  st8(w.a + i * 32 + 24, a.t.w);
+  st8(w.r + i * 16, rx.w);
+  st8(w.r + i * 16 + 8, ry.w);
+  st8(w.s + i * 8, sw);
+  st8(w.k + i * 8, kw);
+  w.flags[i] = f;
+}
+
+__global__ __launch_bounds__(TPB) void k_eddsa_verify_msg_finish(EddsaVerifyWork w, unsigned char* __restrict__ status, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const unsigned char f = w.flags[i];
+  ed::pt s_g, k_a;
+  ld8(s_g.x.w, w.sg + i * 32);
+  ld8(s_g.y.w, w.sg + i * 32 + 8);
+  ld8(s_g.z.w, w.sg + i * 32 + 16);
+  ld8(s_g.t.w, w.sg + i * 32 + 24);
+  ld8(k_a.x.w, w.ka + i * 32);
+  ld8(k_a.y.w, w.ka + i * 32 + 8);
+  ld8(k_a.z.w, w.ka + i * 32 + 16);
+  ld8(k_a.t.w, w.ka + i * 32 + 24);
+  fe rx, ry;
+  ld8(rx.w, w.r + i * 16);
+  ld8(ry.w, w.r + i * 16 + 8);
+  const unsigned char v = eddsa_verify_tail(s_g, k_a, rx, ry);             // 196-211 / 431-446
+  status[i] = (f & V_DECIDED) ? (unsigned char)(f & 0x7F) : v;
+}
+
 unsigned grid(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 }  // namespace
@@ -295,6 +416,15 @@ void eddsa_sign_pre_launch(const EddsaSignIo& io, u32* scal, unsigned char* flag
 void eddsa_sign_finish_launch(const EddsaSignIo& io, const u32* scal, const u32* pts, const unsigned char* flags, size_t n,
                               hipStream_t s) {
   hipLaunchKernelGGL(k_eddsa_sign_finish, dim3(grid(n)), dim3(TPB), 0, s, io, scal, pts, flags, n);
+}
+void eddsa_verify_msg_pre_launch(const EddsaVerifyIo& io, const EddsaVerifyWork& w, size_t n, hipStream_t s) {
+  if (io.form == EDDSA_VERIFY_BYTES)
+    hipLaunchKernelGGL(k_eddsa_verify_msg_pre<EDDSA_VERIFY_BYTES>, dim3(grid(n)), dim3(TPB), 0, s, io, w, n);
+  else
+    hipLaunchKernelGGL(k_eddsa_verify_msg_pre<EDDSA_VERIFY_GENERIC>, dim3(grid(n)), dim3(TPB), 0, s, io, w, n);
+}
+void eddsa_verify_msg_finish_launch(const EddsaVerifyWork& w, unsigned char* status, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_eddsa_verify_msg_finish, dim3(grid(n)), dim3(TPB), 0, s, w, status, n);
 }
 void sha512_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
                    hipStream_t s) {

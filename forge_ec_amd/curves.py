@@ -464,6 +464,40 @@ class Context:
                                                 _ptr(st), n), "fec_eddsa_sign_ed25519")
         return r_xy, r_inf, s, st
 
+    def ed25519_verify(self, public_keys, msgs, sigs):
+        """Ed25519Signature::verify per element (eddsa.rs:360-447), decoding and SHA-512 included: public_keys (n, 32)
+        uint8, msgs a list of n byte strings, sigs (n, 64) uint8.  Returns (n,) uint8: 1 true, 0 false, 2 the reference
+        panics.  The reference's verifier, not RFC 8032 -- see include/fecgpu.h."""
+        pk = np.ascontiguousarray(np.asarray(public_keys, dtype=np.uint8)).reshape(-1, 32)
+        sg = np.ascontiguousarray(np.asarray(sigs, dtype=np.uint8)).reshape(-1, 64)
+        buf, off, total = self._messages(msgs)
+        n = pk.shape[0]
+        if len(off) != n + 1 or sg.shape[0] != n:
+            raise ValueError("inputs differ in length")
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_ed25519_verify(self._h, _ptr(pk), _ptr(buf), _ptr(off), total, _ptr(sg), _ptr(st), n), "fec_ed25519_verify")
+        return st
+
+    def eddsa_verify_ed25519_msg(self, pk_xy, pk_inf, msgs, r_xy, r_inf, s):
+        """EdDsa::<Ed25519, Sha512>::verify per element (eddsa.rs:156-212), SHA-512 included: pk_xy, r_xy (n, 8) raw
+        limbs; pk_inf, r_inf (n,) uint8 or None; msgs a list of n byte strings; s (n, 4) raw Scalar limbs.  Returns
+        (n,) uint8: 1 true, 0 false, 2 the reference panics."""
+        pk, rr, ss = _u64(pk_xy, 8), _u64(r_xy, 8), _u64(s, 4)
+        buf, off, total = self._messages(msgs)
+        n = ss.shape[0]
+        if not (pk.shape[0] == rr.shape[0] == n) or len(off) != n + 1:
+            raise ValueError("inputs differ in length")
+        flags = []
+        for f in (pk_inf, r_inf):
+            a = np.ascontiguousarray(np.asarray(f, dtype=np.uint8)).reshape(-1) if f is not None else None
+            if a is not None and a.shape[0] != n:
+                raise ValueError("flags and signatures differ in length")  # the C side reads n bytes
+            flags.append(a)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_eddsa_verify_ed25519_msg(self._h, _ptr(pk), _ptr(flags[0]), _ptr(buf), _ptr(off), total, _ptr(rr),
+                                                      _ptr(flags[1]), _ptr(ss), _ptr(st), n), "fec_eddsa_verify_ed25519_msg")
+        return st
+
     def sha512(self, msgs):
         """SHA-512 of each byte string in msgs on the GPU: (n, 64) uint8."""
         buf, off, total = self._messages(msgs)
@@ -585,6 +619,15 @@ class Context:
     def eddsa_sign_ed25519_dev(self, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n, stream=None):
         _check(self._lib.fec_eddsa_sign_ed25519_dev(self._h, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n,
                                                     stream), "fec_eddsa_sign_ed25519_dev")
+
+    def ed25519_verify_dev(self, d_public_keys, d_msgs, d_msg_off, msg_len, d_sigs, d_status, n, stream=None):
+        _check(self._lib.fec_ed25519_verify_dev(self._h, d_public_keys, d_msgs, d_msg_off, msg_len, d_sigs, d_status, n, stream),
+               "fec_ed25519_verify_dev")
+
+    def eddsa_verify_ed25519_msg_dev(self, d_pk_xy, d_pk_inf, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n,
+                                     stream=None):
+        _check(self._lib.fec_eddsa_verify_ed25519_msg_dev(self._h, d_pk_xy, d_pk_inf, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf,
+                                                          d_s, d_status, n, stream), "fec_eddsa_verify_ed25519_msg_dev")
 
     def sha512_dev(self, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream=None):
         _check(self._lib.fec_sha512_dev(self._h, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream), "fec_sha512_dev")

@@ -39,6 +39,8 @@
  *   fec_eddsa_sign_ed25519   EdDsa::<Ed25519, Sha512>::sign (eddsa.rs:43-154; scalar Add ed25519.rs:1193-1239, Mul
  *                         1256-1376 as the release profile runs it)
  *   fec_sha512            SHA-512 per message (FIPS 180-4, the sha2 crate the reference signs with)
+ *   fec_ed25519_verify    Ed25519Signature::verify from the message: decoding and SHA-512 included (eddsa.rs:360-447)
+ *   fec_eddsa_verify_ed25519_msg   EdDsa::<Ed25519, Sha512>::verify from the message (eddsa.rs:156-212)
  *   fec_ecdsa_batch_verify   Ecdsa::<C, D>::batch_verify for secp256k1 / P-256 (ecdsa.rs:287-391; scalar Add
  *                         secp256k1.rs:2358-2378, p256.rs:1352-1375)
  *   fec_eddsa_verify_ed25519   Eddsa::<Ed25519, D>::verify / Ed25519::verify after the hash and the decoding
@@ -531,6 +533,50 @@ int fec_sha512(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1
                size_t n);
 int fec_sha512_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
                    uint8_t* d_status, size_t n, void* stream);
+
+/* ---- EdDSA verification for Ed25519 with SHA-512 FROM THE MESSAGE (forge-ec-signature/src/eddsa.rs), parity mode ----
+ * The reference's two verifiers, bit for bit, decoding and hash included: NOT RFC 8032 verification.  fec_eddsa_verify_ed25519
+ * above starts after the hash; these take what the reference's callers hold.  Per element, in the reference's order:
+ *   msg == "test message" -> true; an empty message -> true; msg == "different message" -> false (158-170, 362-374):
+ *   before the key or the signature is looked at, so ANY key and signature verify under the first two.
+ * fec_ed25519_verify   status[i] = Ed25519Signature::verify(public_keys[i], msg_i, sigs[i]) (360-447).
+ *   R = PointAffine::from_bytes(0x02 || sig[0..32]), None -> false (383-394); A = from_bytes(0x02 || public_key), None ->
+ *   false (404-415).  from_bytes (ed25519.rs:1526-1582) reads the 32 bytes as x, little-endian -- None as soon as a 64-bit
+ *   limb exceeds the same limb of p, whatever the higher limbs say (315-357) -- evaluates the MONTGOMERY-form right-hand
+ *   side x^3 + 0x7FFFFFDA x^2 + x, takes the reference's sqrt (359-402, both candidates) and keeps the root whose bit 248 is
+ *   clear: these are not RFC 8032's encodings of R and A.  s = the trait Scalar::from_bytes(sig[32..64]) (ed25519.rs:
+ *   1142-1162): BIG-endian, no range check, always Some, so 398-401 never return.  k = the first 32 bytes of
+ *   SHA512(sig[0..32] || public_key || msg) (419-423: the 64 bytes as given, not the 66 that the signer hashes, and
+ *   fec_ed25519_sign's sig[0..32] is R33[0..32], a prefix byte and 31 bytes of x, which is read here as an x), read big-endian and UNREDUCED: from_bytes_reduced
+ *   (forge-ec-core/src/lib.rs:320-331) returns at its first branch.  Then s * G, k * from_affine(A), from_affine(R) + k * A,
+ *   the two to_affine, the difference and is_identity (431-446).
+ * fec_eddsa_verify_ed25519_msg   status[i] = EdDsa::<Ed25519, Sha512>::verify(pk[i], msg_i, Signature { r, s }) (156-212):
+ *   pk_xy and r_xy the affine x limbs then y limbs, taken as they are (no curve check), pk_inf / r_inf 1 for the identity
+ *   (NULL: none); s raw Scalar limbs.  An identity R -> false (174-177).  k = the first 32 bytes of SHA512(to_bytes(R) ||
+ *   to_bytes(pk) || msg) with the 33-byte trait PointAffine::to_bytes (ed25519.rs:1505-1525): 0x02 | bit 248 of y, then x
+ *   little-endian (reduced); 33 zero bytes for an identity pk whatever its coordinates hold; read big-endian, unreduced.
+ *   Then the same point computation (196-211).
+ * status[i]: 1 true; 0 false; 2 the reference panics there (to_affine unwraps the inverse of a zero z, ed25519.rs:1805) --
+ * the values of fec_eddsa_verify_ed25519; 4 bad message range (_dev forms only).
+ * Messages: the layout, the alignment rules and status 4 of the signing block above -- message i is msgs[msg_off[i],
+ * msg_off[i+1]), msg_off holds n + 1 values with msg_off[0] = 0, non-decreasing, msg_off[n] = msg_len; the host forms
+ * check this and return FEC_E_ARG; in the _dev forms each element checks its own range against msg_len: a bad range gets
+ * status 4, and nothing outside [msgs, msgs + msg_len) is read.
+ * NOTHING HERE IS SECRET (public keys, messages, signatures): no staging or scratch is cleared beyond what every host
+ * call does.  NOT constant-time.  The _dev forms take 16-byte aligned keys, signatures and scalars and an 8-byte aligned
+ * d_msg_off, return FEC_E_UNSUPPORTED on a multi-device ctx and never build a fixed-base prefix table (they take one that
+ * exists); the host forms chunk by fec_ctx_set_chunk and shard over a multi-device ctx. */
+int fec_ed25519_verify(fec_ctx* ctx, const uint8_t* public_keys /* n*32 */, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */,
+                       size_t msg_len, const uint8_t* sigs /* n*64 */, uint8_t* status /* n */, size_t n);
+int fec_ed25519_verify_dev(fec_ctx* ctx, const uint8_t* d_public_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                           size_t msg_len, const uint8_t* d_sigs, uint8_t* d_status, size_t n, void* stream);
+int fec_eddsa_verify_ed25519_msg(fec_ctx* ctx, const uint64_t* pk_xy /* n*8 */, const uint8_t* pk_inf /* n or NULL */,
+                                 const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                                 const uint64_t* r_xy /* n*8 */, const uint8_t* r_inf /* n or NULL */, const uint64_t* s /* n*4 */,
+                                 uint8_t* status /* n */, size_t n);
+int fec_eddsa_verify_ed25519_msg_dev(fec_ctx* ctx, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf, const uint8_t* d_msgs,
+                                     const uint64_t* d_msg_off, size_t msg_len, const uint64_t* d_r_xy, const uint8_t* d_r_inf,
+                                     const uint64_t* d_s, uint8_t* d_status, size_t n, void* stream);
 
 /* Every element-wise host-pointer entry point processes its batch in chunks of `elements` elements
  * (default 2^18), so device staging memory is bounded by two chunks for any n.  Most run them as a

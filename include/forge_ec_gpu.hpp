@@ -610,6 +610,38 @@ inline std::vector<Signature> sign(GpuContext& ctx, const std::vector<Scalar<FEC
   if (status) *status = st;
   return out;
 }
+// ---- verification from the message (fec_ed25519_verify, fec_eddsa_verify_ed25519_msg): decoding and SHA-512 on the
+// GPU; the reference's verifiers, quirks included -- see fecgpu.h.  Nothing here is secret.
+// Ed25519Signature::verify(public_keys[i], msgs[i], signatures[i]) (eddsa.rs:360-447)
+inline std::vector<Verify> ed25519_verify(GpuContext& ctx, const std::vector<Bytes32>& public_keys, const std::vector<std::string>& msgs,
+                                                const std::vector<Bytes64>& signatures) {
+  const size_t n = public_keys.size();
+  if (msgs.size() != n || signatures.size() != n) throw Error(FEC_E_ARG);
+  const detail::Messages m(msgs);
+  std::vector<uint8_t> st(n);
+  check(fec_ed25519_verify(ctx.raw(), reinterpret_cast<const uint8_t*>(public_keys.data()), m.bytes.data(), m.off.data(), m.bytes.size(),
+                           reinterpret_cast<const uint8_t*>(signatures.data()), st.data(), n));
+  return forge_ec::detail::statuses(st);
+}
+// EdDsa::<Ed25519, Sha512>::verify(public_keys[i], msgs[i], sigs[i]) (eddsa.rs:156-212)
+inline std::vector<Verify> verify(GpuContext& ctx, const std::vector<AffinePoint<FEC_ED25519>>& public_keys,
+                                        const std::vector<std::string>& msgs, const std::vector<Signature>& sigs) {
+  const size_t n = sigs.size();
+  if (public_keys.size() != n || msgs.size() != n) throw Error(FEC_E_ARG);
+  const detail::Messages m(msgs);
+  std::vector<uint64_t> pk, rxy, s(n * 4);
+  std::vector<uint8_t> pinf, rinf, st(n);
+  std::vector<AffinePoint<FEC_ED25519>> rs(n);
+  for (size_t i = 0; i < n; ++i) {
+    rs[i] = sigs[i].r;
+    for (int l = 0; l < 4; ++l) s[i * 4 + l] = sigs[i].s.raw[l];
+  }
+  forge_ec::detail::pack_affine<FEC_ED25519>(public_keys, pk, pinf);
+  forge_ec::detail::pack_affine<FEC_ED25519>(rs, rxy, rinf);
+  check(fec_eddsa_verify_ed25519_msg(ctx.raw(), pk.data(), pinf.data(), m.bytes.data(), m.off.data(), m.bytes.size(), rxy.data(),
+                                     rinf.data(), s.data(), st.data(), n));
+  return forge_ec::detail::statuses(st);
+}
 // SHA-512 of each message (fec_sha512)
 inline std::vector<Bytes64> sha512(GpuContext& ctx, const std::vector<std::string>& msgs) {
   const detail::Messages m(msgs);

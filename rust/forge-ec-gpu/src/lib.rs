@@ -86,6 +86,10 @@ extern "C" {
     fn fec_eddsa_sign_ed25519_dev(ctx: *mut FecCtx, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *mut u64, d_r_inf: *mut u8, d_s: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_sha512(ctx: *mut FecCtx, msgs: *const u8, msg_off: *const u64, msg_len: usize, digests: *mut u8, n: usize) -> c_int;
     fn fec_sha512_dev(ctx: *mut FecCtx, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_digests: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_ed25519_verify(ctx: *mut FecCtx, public_keys: *const u8, msgs: *const u8, msg_off: *const u64, msg_len: usize, sigs: *const u8, status: *mut u8, n: usize) -> c_int;
+    fn fec_ed25519_verify_dev(ctx: *mut FecCtx, d_public_keys: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_sigs: *const u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_eddsa_verify_ed25519_msg(ctx: *mut FecCtx, pk_xy: *const u64, pk_inf: *const u8, msgs: *const u8, msg_off: *const u64, msg_len: usize, r_xy: *const u64, r_inf: *const u8, s: *const u64, status: *mut u8, n: usize) -> c_int;
+    fn fec_eddsa_verify_ed25519_msg_dev(ctx: *mut FecCtx, d_pk_xy: *const u64, d_pk_inf: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *const u64, d_r_inf: *const u8, d_s: *const u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_ctx_set_chunk(ctx: *mut FecCtx, elements: usize) -> c_int;
     fn fec_ctx_set_timing(ctx: *mut FecCtx, enabled: c_int) -> c_int;
     fn fec_ctx_last_kernel_ms(ctx: *mut FecCtx, ms: *mut c_float, kernel_name: *mut *const c_char) -> c_int;
@@ -661,6 +665,51 @@ pub fn eddsa_sign_batch_ed25519(ctx: &mut GpuContext, sks: &[ed25519::Scalar], m
     }, d))).collect())
 }
 
+fn verify_statuses(status: &[u8]) -> Vec<VerifyStatus> {
+    status.iter().map(|&v| match v { 1 => VerifyStatus::Valid, 2 => VerifyStatus::ReferencePanics, _ => VerifyStatus::Invalid }).collect()
+}
+
+/// `Ed25519Signature::verify(&public_keys[i], msgs[i], &signatures[i])` per element
+/// (`forge-ec-signature/src/eddsa.rs:360-447`), decoding and SHA-512 included, bit for bit: the reference's verifier,
+/// not RFC 8032 (see `fec_ed25519_verify` in include/fecgpu.h).  Nothing here is secret.
+pub fn ed25519_verify_batch(ctx: &mut GpuContext, public_keys: &[[u8; 32]], msgs: &[&[u8]], signatures: &[[u8; 64]]) -> Result<Vec<VerifyStatus>> {
+    let n = public_keys.len();
+    if msgs.len() != n || signatures.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let (buf, off) = pack_messages(msgs);
+    let mut status = vec![0u8; n];
+    // SAFETY: keys n * 32 bytes, off n + 1 offsets into buf, signatures n * 64 bytes, status n.
+    check(unsafe { fec_ed25519_verify(ctx.raw, public_keys.as_ptr() as *const u8, buf.as_ptr(), off.as_ptr(), buf.len(), signatures.as_ptr() as *const u8, status.as_mut_ptr(), n) })?;
+    Ok(verify_statuses(&status))
+}
+
+/// `EdDsa::<Ed25519, Sha512>::verify(&public_keys[i], msgs[i], &signatures[i])` per element
+/// (`forge-ec-signature/src/eddsa.rs:156-212`), SHA-512 included.
+#[cfg(feature = "signature")]
+pub fn eddsa_verify_msg_batch_ed25519(ctx: &mut GpuContext, public_keys: &[ed25519::AffinePoint], msgs: &[&[u8]], signatures: &[forge_ec_signature::eddsa::Signature<ed25519::Ed25519>]) -> Result<Vec<VerifyStatus>> {
+    let n = public_keys.len();
+    if msgs.len() != n || signatures.len() != n {
+        return Err(Error::ValidationError);
+    }
+    type C = ed25519::Ed25519;
+    let (buf, off) = pack_messages(msgs);
+    let (mut rxy, mut rinf, mut pxy, mut pinf, mut ss) = (vec![0u64; 8 * n], vec![0u8; n], vec![0u64; 8 * n], vec![0u8; n], vec![0u64; 4 * n]);
+    for i in 0..n {
+        let (l, f) = C::affine_limbs(&signatures[i].r);
+        rxy[8 * i..8 * i + 8].copy_from_slice(&l);
+        rinf[i] = f as u8;
+        let (l, f) = C::affine_limbs(&public_keys[i]);
+        pxy[8 * i..8 * i + 8].copy_from_slice(&l);
+        pinf[i] = f as u8;
+        ss[4 * i..4 * i + 4].copy_from_slice(&C::scalar_limbs(&signatures[i].s));
+    }
+    let mut status = vec![0u8; n];
+    // SAFETY: every buffer holds n elements of the width the header states; off n + 1 offsets into buf.
+    check(unsafe { fec_eddsa_verify_ed25519_msg(ctx.raw, pxy.as_ptr(), pinf.as_ptr(), buf.as_ptr(), off.as_ptr(), buf.len(), rxy.as_ptr(), rinf.as_ptr(), ss.as_ptr(), status.as_mut_ptr(), n) })?;
+    Ok(verify_statuses(&status))
+}
+
 /// SHA-512 of each message on the GPU (`fec_sha512`).
 pub fn sha512_batch(ctx: &mut GpuContext, msgs: &[&[u8]]) -> Result<Vec<[u8; 64]>> {
     let n = msgs.len();
@@ -989,6 +1038,22 @@ pub mod dev {
     /// As [`batch_mul`]; the caller owns and clears every buffer.
     pub unsafe fn eddsa_sign_ed25519(ctx: &mut GpuContext, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *mut u64, d_r_inf: *mut u8, d_s: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
         check(fec_eddsa_sign_ed25519_dev(ctx.raw, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n, stream))
+    }
+
+    /// `fec_ed25519_verify_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn ed25519_verify(ctx: &mut GpuContext, d_public_keys: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_sigs: *const u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_ed25519_verify_dev(ctx.raw, d_public_keys, d_msgs, d_msg_off, msg_len, d_sigs, d_status, n, stream))
+    }
+
+    /// `fec_eddsa_verify_ed25519_msg_dev` (`d_pk_inf` and `d_r_inf` may be null).
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn eddsa_verify_ed25519_msg(ctx: &mut GpuContext, d_pk_xy: *const u64, d_pk_inf: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *const u64, d_r_inf: *const u8, d_s: *const u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_eddsa_verify_ed25519_msg_dev(ctx.raw, d_pk_xy, d_pk_inf, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n, stream))
     }
 
     /// `fec_sha512_dev` (`d_status` may be null).
