@@ -111,6 +111,26 @@ int main(void) {
          sig3[1][0], sig3[1][1], sig3[1][2], sig3[1][3]);
   printf("parity  Ed25519Signature::verify status %u %u %u  (\"test message\", \"hello\", \"\")\n", st_ver[0], st_ver[1], st_ver[2]);
   ok = ok && st_ver[0] == 1 && st_ver[2] == 1 && st_ver[1] <= 2;
+  /* SHA-256 on the GPU and its two users, on the same three messages: the hash itself, the reference's BipSchnorr::sign
+   * (bytes 0..63 for "test message", a computed signature otherwise) and Ecdsa::<Secp256k1, Sha256>::verify from the
+   * message (an arbitrary signature and key: false, or 2 where the reference would panic) */
+  uint8_t dg3[3][32], bsig3[3][64], st_bip[3], st_ecdsa[3];
+  uint64_t er3[3][4], es3[3][4], epk3[3][8];
+  for (int i = 0; i < 3; ++i) {
+    for (int l = 0; l < 4; ++l) { er3[i][l] = (uint64_t)(3 + i + l); es3[i][l] = (uint64_t)(5 + i + l); }
+    for (int l = 0; l < 8; ++l) epk3[i][l] = (uint64_t)(11 + i + l);
+  }
+  rc = fec_sha256(ctx, msgs3, off3, 17, &dg3[0][0], 3);
+  if (rc == FEC_OK) rc = fec_bip340_sign(ctx, &sk3[0][0], msgs3, off3, 17, &bsig3[0][0], st_bip, 3);
+  if (rc == FEC_OK) rc = fec_ecdsa_verify_msg(ctx, FEC_SECP256K1, msgs3, off3, 17, &er3[0][0], &es3[0][0], &epk3[0][0], NULL, st_ecdsa, 3);
+  if (rc != FEC_OK) {
+    printf("SHA-256 / BIP-340 sign / ECDSA verify from the message failed: %s\n", fec_strerror(rc));
+    return 1;
+  }
+  printf("parity  SHA-256(\"hello\") starts %02x%02x%02x%02x; BipSchnorr::sign status %u %u %u; Ecdsa::verify(msg) status %u %u %u\n",
+         dg3[1][0], dg3[1][1], dg3[1][2], dg3[1][3], st_bip[0], st_bip[1], st_bip[2], st_ecdsa[0], st_ecdsa[1], st_ecdsa[2]);
+  ok = ok && dg3[1][0] == 0x2c && dg3[1][1] == 0xf2 && dg3[2][0] == 0xe3 && st_bip[0] == 1 && bsig3[0][63] == 63 && st_bip[1] == 0 &&
+       st_bip[2] == 0 && st_ecdsa[0] <= 2 && st_ecdsa[1] <= 2 && st_ecdsa[2] <= 2;
   /* a single-device ctx has fec_batch_*_dev; the device-resident multi-GPU calls say so */
   const size_t none = 0;
   const uint64_t* no_in[1] = {NULL};

@@ -17,6 +17,7 @@ ABI_SYMBOLS = [
     "fec_batch_double_mul", "fec_batch_to_affine", "fec_batch_to_affine_dev", "fec_ecdsa_verify_secp256k1", "fec_ecdsa_verify_secp256k1_dev", "fec_ecdsa_verify_p256", "fec_ecdsa_verify_p256_dev", "fec_eddsa_verify_ed25519", "fec_eddsa_verify_ed25519_dev", "fec_ecdsa_batch_verify", "fec_batch_ecdh", "fec_batch_ecdh_dev", "fec_ecdsa_sign", "fec_ecdsa_sign_dev", "fec_x25519", "fec_x25519_dev", "fec_curve25519_mul", "fec_curve25519_mul_dev", "fec_curve25519_field_op", "fec_ed25519_sign", "fec_ed25519_sign_dev", "fec_ed25519_derive_public_key", "fec_ed25519_derive_public_key_dev", "fec_eddsa_sign_ed25519", "fec_eddsa_sign_ed25519_dev", "fec_sha512", "fec_sha512_dev", "fec_ed25519_verify", "fec_ed25519_verify_dev", "fec_eddsa_verify_ed25519_msg", "fec_eddsa_verify_ed25519_msg_dev", "fec_batch_validate_point", "fec_batch_validate_point_dev", "fec_multi_scalar_mul", "fec_schnorr_batch_verify_secp256k1", "fec_schnorr_batch_verify", "fec_schnorr_batch_verify_ed25519", "fec_schnorr_verify", "fec_schnorr_verify_dev", "fec_batch_compress", "fec_batch_compress_dev", "fec_batch_decompress", "fec_batch_encode_uncompressed", "fec_batch_decode_uncompressed", "fec_field_op", "fec_point_op", "fec_batch_mul_dev",
     "fec_batch_mul_fixed_dev", "fec_batch_double_mul_dev", "fec_multi_batch_mul_dev", "fec_multi_batch_mul_fixed_dev", "fec_multi_batch_double_mul_dev", "fec_ctx_set_chunk", "fec_ctx_set_timing",
     "fec_ctx_last_kernel_ms", "fec_measure_peak_mad32", "fec_ctx_device_info", "fec_strerror",
+    "fec_sha256", "fec_sha256_dev", "fec_ecdsa_verify_msg", "fec_ecdsa_verify_msg_dev", "fec_bip340_sign", "fec_bip340_sign_dev",
 ]
 # include/fecgpu_canon.h: the canonical-math mode (NOT reference parity)
 CANON_ABI_SYMBOLS = [
@@ -186,6 +187,14 @@ def lib():
     for n in ("fec_ed25519_sign", "fec_ed25519_sign_dev", "fec_ed25519_derive_public_key", "fec_ed25519_derive_public_key_dev",
               "fec_eddsa_sign_ed25519", "fec_eddsa_sign_ed25519_dev", "fec_sha512", "fec_sha512_dev", "fec_ed25519_verify",
               "fec_ed25519_verify_dev", "fec_eddsa_verify_ed25519_msg", "fec_eddsa_verify_ed25519_msg_dev"):
+        getattr(L, n).restype = ci
+    L.fec_sha256.argtypes = [vp, vp, vp, sz, vp, sz]
+    L.fec_sha256_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+    L.fec_ecdsa_verify_msg.argtypes = [vp, ci, vp, vp, sz, vp, vp, vp, vp, vp, sz]
+    L.fec_ecdsa_verify_msg_dev.argtypes = [vp, ci, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp]
+    L.fec_bip340_sign.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz]
+    L.fec_bip340_sign_dev.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz, vp]
+    for n in ("fec_sha256", "fec_sha256_dev", "fec_ecdsa_verify_msg", "fec_ecdsa_verify_msg_dev", "fec_bip340_sign", "fec_bip340_sign_dev"):
         getattr(L, n).restype = ci
     L.fec_ctx_set_chunk.argtypes = [vp, sz]
     L.fec_ctx_set_chunk.restype = ci

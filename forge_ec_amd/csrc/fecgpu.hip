@@ -1037,23 +1037,45 @@ void ecdsa_layout(WorkArea& area, EcdsaWork& w, size_t n, bool weighted) {
 
 // Ecdsa::<C, D>::verify for secp256k1 / P-256: the passes of kernels_ecdsa.hip around the two products, on per-stream
 // scratch.  (The single-kernel secp256k1 form of round 1 measured 70.7 ms per 2^20 against 65.7 ms for this pipeline.)
+// With `msg` (Ecdsa::<C, Sha256>::verify from the message, ecdsa.rs:231-239) one k_sha256 pass first writes the digests
+// into a region of the same work area -- one request for both stages -- and the pipeline runs on them unchanged;
+// `mark_bad_ranges` (the *_dev form, whose message layout nobody has checked) then sets status 4 where an element's
+// range was bad.
+struct EcdsaMessages {
+  const unsigned char* msgs;
+  const u64* off;
+  u64 msg_len;
+  bool mark_bad_ranges;
+};
 int launch_ecdsa_verify(fec_ctx* ctx, int curve, const unsigned char* dd, const u64* dr, const u64* ds, const u64* dpk,
-                        const unsigned char* dinf, unsigned char* dstatus, size_t n, void* stream) {
+                        const unsigned char* dinf, unsigned char* dstatus, size_t n, void* stream,
+                        const EcdsaMessages* msg = nullptr) {
   if (n == 0) return FEC_OK;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   EcdsaWork w;
+  u32* digests = nullptr;
+  unsigned char* bad = nullptr;
   WorkArea area;
   ecdsa_layout(area, w, n, false);
+  if (msg) {
+    area.pop(1);   // (a_i * r_i is batch_verify's: its empty region makes room)
+    area.add(digests, n * 32).add(bad, n);
+  }
   int rc = area.acquire(ctx, st);
   if (rc == FEC_OK) rc = prepare_generator(ctx, curve, st, n);
   if (rc != FEC_OK) return rc;
-  Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_ecdsa_pre + k_secp_mul x2 + k_ecdsa_finish"
-                                               : "k_ecdsa_pre + k_p256_mul_sched x2 + k_ecdsa_finish");
+  Launch L(ctx, stream, curve == FEC_SECP256K1 ? (msg ? "k_sha256 + k_ecdsa_pre + k_secp_mul x2 + k_ecdsa_finish" : "k_ecdsa_pre + k_secp_mul x2 + k_ecdsa_finish")
+                                               : (msg ? "k_sha256 + k_ecdsa_pre + k_p256_mul_sched x2 + k_ecdsa_finish" : "k_ecdsa_pre + k_p256_mul_sched x2 + k_ecdsa_finish"));
+  if (msg) {
+    sha256_launch(msg->msgs, msg->off, msg->msg_len, digests, bad, n, L.s);
+    dd = reinterpret_cast<const unsigned char*>(digests);
+  }
   const u32* r = reinterpret_cast<const u32*>(dr);
   ecdsa_pre_launch(curve, dd, r, reinterpret_cast<const u32*>(ds), reinterpret_cast<const u32*>(dpk), dinf, nullptr, w, n, L.s);
   // (u2 * from_affine(public key): the affine-addend cost in the P-256 CU split)
   product_pair(ctx, curve, n, L.s, SideStream::kSideStreamMax, kP256VarAffineMs, w.u1, w.ta, nullptr, w.u2, w.q, w.tb);
   ecdsa_finish_launch(curve, r, w, dstatus, n, L.s);
+  if (msg && msg->mark_bad_ranges) bad_range_status_launch(bad, dstatus, n, L.s);
   return L.done();
 }
 
@@ -1200,6 +1222,30 @@ int launch_eddsa_sign(fec_ctx* ctx, const EddsaSignIo& io, size_t n, void* strea
   return L.done();
 }
 
+// BipSchnorr::sign (schnorr.rs:302-420; kernels_schnorr.hip): k_bip340_pre, P = multiply(G, d), k_bip340_mid,
+// R = multiply(G, k), k_bip340_finish.  Both multiplications are the secp256k1 fixed-base ladder under launch_mul's
+// prefix-table policy -- the host-pointer form may build a table, a *_dev call only takes one that exists.  d', k,
+// P.x, the two points and the flags are regions of one work area, taken in one request.
+int launch_bip340_sign(fec_ctx* ctx, const Bip340Io& io, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  Bip340Work w;
+  WorkArea area;
+  area.add(w.d, n * 32).add(w.k, n * 32).add(w.px, n * 32).add(w.p, n * 96).add(w.r, n * 96).add(w.flags, n);
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, FEC_SECP256K1, st, 2 * n);
+  if (rc != FEC_OK) return rc;
+  const u32* gen = reinterpret_cast<const u32*>(ctx->d_gen[FEC_SECP256K1]);
+  Launch L(ctx, stream, "k_bip340_pre + k_secp_mul + k_bip340_mid + k_secp_mul + k_bip340_finish");
+  const SchedEnv env = sched_env(ctx);
+  bip340_pre_launch(io, w, n, L.s);
+  fixed_product(ctx, env, FEC_SECP256K1, w.d, gen, w.p, n, nullptr, L.s);
+  bip340_mid_launch(io, w, n, L.s);
+  fixed_product(ctx, env, FEC_SECP256K1, w.k, gen, w.r, n, nullptr, L.s);
+  bip340_finish_launch(io, w, n, L.s);
+  return L.done();
+}
+
 int launch_field(fec_ctx* ctx, int curve, int op, const u64* da, const u64* db, u64* dout, size_t n,
                  void* stream = nullptr) {
   if (n == 0) return FEC_OK;
@@ -1333,9 +1379,9 @@ int stage_messages(fec_ctx* c, const uint8_t* msgs, const u64* o, size_t m, std:
   d_off = static_cast<const u64*>(c->d_buf[kStageBody + 1]);
   return FEC_OK;
 }
-constexpr int kSha512 = -1;   // msg_call's mode for fec_sha512 (else EDDSA_MODE_*)
+constexpr int kSha512 = -1, kSha256 = -2, kBip340 = -3;   // msg_call's modes for fec_sha512, fec_sha256, fec_bip340_sign (else EDDSA_MODE_*)
 // The host forms, on a single-device or a multi-device ctx (host_ctx.hpp: sharded, chunked; one lane).  The engine stages
-// the keys and takes back the outputs (out: 64 bytes per element, 32 for derive; status; r_inf and s for the generic
+// the keys and takes back the outputs (out: 64 bytes per element, 32 for derive and SHA-256; status; r_inf and s for the generic
 // form); the body stages the chunk's message bytes msgs[off[lo], off[lo + cnt]) into slot kStageBody and its offsets,
 // rebased to that range, into the slot after it.  Keys and outputs are secret (a digest too: its message may be), so the
 // staging and the stream scratch (a, r, A, R) are cleared on every way out.  The layout is checked once, here.
@@ -1344,8 +1390,9 @@ int msg_call(fec_ctx* ctx, int mode, const void* keys, const uint8_t* msgs, cons
   if (!ctx) return FEC_E_ARG;
   const bool with_msgs = mode != EDDSA_MODE_DERIVE;
   if (with_msgs && !msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(keys, 32), ragged(with_msgs ? off : nullptr, 8), secret_output(out, with_msgs ? 64 : 32),
-                         output(status, 1), output(r_inf, 1), output(s_out, 32)};
+  const HostArray a[] = {secret_input(keys, 32), ragged(with_msgs ? off : nullptr, 8),
+                         secret_output(out, with_msgs && mode != kSha256 ? 64 : 32), output(status, 1), output(r_inf, 1),
+                         output(s_out, 32)};
   return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[6], size_t cnt, size_t) {
     std::vector<uint64_t> reb(with_msgs ? (child->chunk < cnt ? child->chunk : cnt) + 1 : 0);
     return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
@@ -1361,6 +1408,15 @@ int msg_call(fec_ctx* ctx, int mode, const void* keys, const uint8_t* msgs, cons
         Launch L(c, st, "k_sha512");
         sha512_launch(d_msgs, d_off, bytes, static_cast<u32*>(d[2]), nullptr, m, L.s);
         return L.done();
+      }
+      if (mode == kSha256) {
+        Launch L(c, st, "k_sha256");
+        sha256_launch(d_msgs, d_off, bytes, static_cast<u32*>(d[2]), nullptr, m, L.s);
+        return L.done();
+      }
+      if (mode == kBip340) {
+        const Bip340Io io{static_cast<const u32*>(d[0]), d_msgs, d_off, bytes, static_cast<u32*>(d[2]), static_cast<unsigned char*>(d[3])};
+        return launch_bip340_sign(c, io, m, st);
       }
       const EddsaSignIo io{mode, static_cast<const u32*>(d[0]), d_msgs, d_off, bytes, nullptr, static_cast<u32*>(d[2]),
                            static_cast<unsigned char*>(d[4]), static_cast<u32*>(d[5]), static_cast<unsigned char*>(d[3])};
@@ -1419,6 +1475,26 @@ int verify_msg_dev(fec_ctx* ctx, int form, const void* d_pk, const uint8_t* d_pk
   const EddsaVerifyIo io{form, static_cast<const u32*>(d_pk), d_pk_inf, d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len,
                          static_cast<const u32*>(d_sig), d_r_inf, reinterpret_cast<const u32*>(d_s)};
   return launch_eddsa_verify_msg(ctx, io, d_status, n, stream);
+}
+
+// Ecdsa::<C, Sha256>::verify from the message (ecdsa.rs:213-281).  Host form: the engine as verify_msg_call uses it, one
+// lane, the chunk's messages in the same two slots; nothing is secret.
+int ecdsa_verify_msg_call(fec_ctx* ctx, int curve, const uint8_t* msgs, const uint64_t* off, size_t msg_len, const uint64_t* r,
+                          const uint64_t* s_in, const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* status, size_t n) {
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
+  if (!ctx || (n && (!r || !s_in || !pk_xy || !status))) return FEC_E_ARG;
+  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  const HostArray a[] = {ragged(off, 8), input(r, 32), input(s_in, 32), input(pk_xy, 64), input(pk_inf, 1), output(status, 1)};
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[6], size_t cnt, size_t) {
+    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
+    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
+      EcdsaMessages em{nullptr, nullptr, 0, false};
+      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[0]), m, reb, st, em.msgs, em.off, em.msg_len);
+      if (rc != FEC_OK) return rc;
+      return launch_ecdsa_verify(c, curve, nullptr, (const u64*)d[1], (const u64*)d[2], (const u64*)d[3], (const unsigned char*)d[4],
+                                 (unsigned char*)d[5], m, st, &em);
+    });
+  });
 }
 }  // namespace
 
@@ -2559,6 +2635,60 @@ int fec_eddsa_verify_ed25519_msg_dev(fec_ctx* ctx, const uint64_t* d_pk_xy, cons
                                      const uint64_t* d_s, uint8_t* d_status, size_t n, void* stream) try {
   return verify_msg_dev(ctx, EDDSA_VERIFY_GENERIC, d_pk_xy, d_pk_inf, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status,
                         n, stream);
+} FEC_ABI_CATCH_STATUS
+
+// ---- SHA-256, ECDSA verification from the message, BIP-340 signing (kernels_schnorr.hip; helpers above) ----
+
+int fec_sha256(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* digests, size_t n) try {
+  if (n && !digests) return FEC_E_ARG;
+  return msg_call(ctx, kSha256, nullptr, msgs, msg_off, msg_len, digests, nullptr, nullptr, nullptr, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_sha256_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
+                   uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || (n && (!d_msg_off || !d_digests)) || (msg_len && !d_msgs)) return FEC_E_ARG;
+  if (!aligned16(d_digests) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_sha256");
+  sha256_launch(d_msgs, d_msg_off, msg_len, reinterpret_cast<u32*>(d_digests), d_status, n, L.s);
+  return L.done();
+} FEC_ABI_CATCH_STATUS
+
+int fec_ecdsa_verify_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                         const uint64_t* r, const uint64_t* s, const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* status,
+                         size_t n) try {
+  return ecdsa_verify_msg_call(ctx, curve, msgs, msg_off, msg_len, r, s, pk_xy, pk_inf, status, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_ecdsa_verify_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                             const uint64_t* d_r, const uint64_t* d_s, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf,
+                             uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || (n && (!d_msg_off || !d_r || !d_s || !d_pk_xy || !d_status)) || (msg_len && !d_msgs)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
+  if (!aligned16(d_r) || !aligned16(d_s) || !aligned16(d_pk_xy) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const EcdsaMessages em{d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len, true};
+  return launch_ecdsa_verify(ctx, curve, nullptr, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n, stream, &em);
+} FEC_ABI_CATCH_STATUS
+
+int fec_bip340_sign(fec_ctx* ctx, const uint8_t* private_keys, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                    uint8_t* signatures, uint8_t* status, size_t n) try {
+  if (n && (!private_keys || !signatures || !status)) return FEC_E_ARG;
+  return msg_call(ctx, kBip340, private_keys, msgs, msg_off, msg_len, signatures, status, nullptr, nullptr, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_bip340_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                        size_t msg_len, uint8_t* d_signatures, uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || (n && (!d_private_keys || !d_signatures || !d_status || !d_msg_off)) || (msg_len && !d_msgs)) return FEC_E_ARG;
+  if (!aligned16(d_private_keys) || !aligned16(d_signatures) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const Bip340Io io{reinterpret_cast<const u32*>(d_private_keys), d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len,
+                    reinterpret_cast<u32*>(d_signatures), d_status};
+  return launch_bip340_sign(ctx, io, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 }  // extern "C"

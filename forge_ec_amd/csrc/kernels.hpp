@@ -138,6 +138,33 @@ struct EddsaVerifyWork {
 void eddsa_verify_msg_pre_launch(const EddsaVerifyIo& io, const EddsaVerifyWork& w, size_t n, hipStream_t s);
 void eddsa_verify_msg_finish_launch(const EddsaVerifyWork& w, unsigned char* status, size_t n, hipStream_t s);
 
+// kernels_schnorr.hip: SHA-256 per message, as sha512_launch: digests 8 words (32 bytes) per message, zero where the
+// range is bad; status (may be null): 0, or 4 for a bad range
+void sha256_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
+                   hipStream_t s);
+// status[i] = 4 where bad[i] != 0 (sha256_launch's status of a pass whose digests went on into a verifier)
+void bad_range_status_launch(const unsigned char* bad, unsigned char* status, size_t n, hipStream_t s);
+
+// kernels_schnorr.hip: BipSchnorr::sign (forge-ec-signature/src/schnorr.rs:302-420), the three passes around
+// p = multiply(G, d) and r = multiply(G, k) (24 words per element each).  keys: the 32 private-key bytes per element;
+// messages as above; sig 16 words (64 bytes), status one byte.  Work area per element: d (8 words: d after the pre
+// pass, d' = -d or d after the middle one), k (8 words), px (8 words: the value P.x.to_bytes() encodes), one flag byte.
+struct Bip340Io {
+  const u32* keys;
+  const unsigned char* msgs;
+  const u64* off;
+  u64 msg_len;
+  u32* sig;
+  unsigned char* status;
+};
+struct Bip340Work {
+  u32 *d, *k, *px, *p, *r;
+  unsigned char* flags;
+};
+void bip340_pre_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStream_t s);
+void bip340_mid_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStream_t s);
+void bip340_finish_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStream_t s);
+
 // kernels_ecdsa.hip: Curve::validate_point per affine point (secp256k1 / P-256: is_on_curve; Ed25519: the trait default
 // with its two multiplications).  `work` holds validate_work_bytes(curve, n) bytes (0 for the Weierstrass curves).
 size_t validate_work_bytes(int curve, size_t n);

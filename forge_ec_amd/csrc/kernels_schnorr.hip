@@ -1,0 +1,166 @@
+// kernels_schnorr.hip -- the SHA-256 users of the parity-mode surface:
+//   k_sha256          SHA-256 per message (fec_sha256, and the first pass of fec_ecdsa_verify_msg, whose digests
+//                     launch_ecdsa_verify then takes as they are: ecdsa.rs:231-239; k_bad_range_status marks the
+//                     elements whose message range the hash pass refused)
+// and BipSchnorr::sign (forge-ec-signature/src/schnorr.rs:302-420), around two fixed-base multiplications by the
+// secp256k1 ladder with the prefix table (fecgpu.hip: launch_bip340_sign):
+//   k_bip340_pre      the message case (307-316); d = Scalar::from_bytes(private_key) (324-334); a decided lane gets
+//                     the scalar 0 and a flag
+//   (fixed base)      P = multiply(G, d)                                                              337
+//   k_bip340_mid      to_affine(P); P.x bytes; the parity of P.y.to_bytes()[31]; d' = -d or d (338-349);
+//                     k = Scalar::from_bytes(SHA256(d'.to_bytes() || msg)) (352-370)
+//   (fixed base)      R = multiply(G, k)                                                              373
+//   k_bip340_finish   to_affine(R); R.x bytes; parity; k' = -k or k (374-385); e = Scalar::from_bytes(SHA256(R.x ||
+//                     P.x || msg)) (388-407); s = k' + e * d' (410-411); R.x || s.to_bytes() (412-417); the flags override
+// One element per lane; the hash state lives in VGPRs (sha256.hpp).
+//
+// Readings, pinned (secp256k1.rs = forge-ec-curves/src/secp256k1.rs):
+//  * Scalar::from_bytes / to_bytes are the INHERENT forms (secp256k1.rs:1924-1951; bip340.hpp): little-endian, None iff
+//    the value is not below the reference's N, zero valid.  So "BIP-340 requires [1, n-1]" (323) is not what 324-325
+//    test: d = 0 signs.
+//  * p_x.to_bytes(), p_y.to_bytes() are the field's inherent to_bytes (138-178): mont_reduce -- Mul by the raw 1 --
+//    then big-endian; byte 31 is the low byte, so the parity is bit 0 of that value.
+//  * d = 0: multiply(G, 0) is the identity (2635-2692), to_affine of it (0, 0, infinity) (1342-1350), so P.x is 32 zero
+//    bytes, the parity even, d' = 0 and s = k'.  A hash that reads as k = 0 does the same to R.
+//  * to_affine cannot panic here: it inverts Z only when is_identity -- Z == 0 -- is false (1344, 1353).  No other
+//    unwrap sees None: the three from_bytes are tested first.  So no input makes BipSchnorr::sign panic.
+//  * -d, e * d, k + e_d are impl Neg / Mul / Add for Scalar (2466-2488, 2410-2456, 2358-2378).
+//  * The "test message" signature and the fallback of a failed from_bytes are the same 64 bytes 0..63 (311-314,
+//    328-330); the status tells them apart.
+//  * status: 0 computed; 1 the "test message" pattern; 2 the 0..63 fallback (d, k or e not below N); 3 the reference
+//    panics -- never written, see above; 4 (the *_dev forms) a bad message range: nothing of the message is read and
+//    the signature is 0.
+// Secret: d, d', k, k' and the digest behind k.  The digest stays in registers; d' and k sit in the work area.
+#include <hip/hip_runtime.h>
+
+#include "../../include/fecgpu.h"
+#include "bip340.hpp"
+#include "kernels.hpp"
+#include "secp256k1.hpp"
+#include "sha256.hpp"
+#include "staging.hpp"
+
+namespace fecgpu {
+
+namespace {
+
+FEC_DEV void ld8(u32 q[8], const u32* __restrict__ p) {
+  const uint4* v = reinterpret_cast<const uint4*>(p);
+  const uint4 a = v[0], b = v[1];
+  q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w;
+  q[4] = b.x; q[5] = b.y; q[6] = b.z; q[7] = b.w;
+}
+FEC_DEV void st8(u32* __restrict__ p, const u32 q[8]) {
+  uint4* v = reinterpret_cast<uint4*>(p);
+  v[0] = make_uint4(q[0], q[1], q[2], q[3]);
+  v[1] = make_uint4(q[4], q[5], q[6], q[7]);
+}
+// Element i's message range; false (and nothing read) where it is not inside [0, msg_len)  (as kernels_eddsa.hip)
+FEC_DEV bool msg_range(const u64* __restrict__ off, u64 msg_len, size_t i, u64& lo, u64& len) {
+  const u64 a = off[i], b = off[i + 1];
+  const bool ok = a <= b && b <= msg_len;
+  lo = ok ? a : 0;
+  len = ok ? b - a : 0;
+  return ok;
+}
+FEC_DEV secp::pt ld_pt(const u32* __restrict__ p) {
+  secp::pt q;
+  ld8(q.x.w, p);
+  ld8(q.y.w, p + 8);
+  ld8(q.z.w, p + 16);
+  return q;
+}
+
+__global__ __launch_bounds__(TPB) void k_sha256(const unsigned char* __restrict__ msgs, const u64* __restrict__ off, u64 msg_len,
+                                                u32* __restrict__ out, unsigned char* __restrict__ status, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  u64 lo, len;
+  const bool ok = msg_range(off, msg_len, i, lo, len);
+  u32 o[8];
+  if (ok) {
+    const u32 none[1] = {0};
+    sha256::digest_words(sha256::hash_prefixed<1>(none, 0, len ? msgs + lo : nullptr, len), o);
+  } else {
+    FEC_UNROLL for (int j = 0; j < 8; ++j) o[j] = 0;
+  }
+  st8(out + i * 8, o);
+  if (status) status[i] = ok ? 0 : 4;
+}
+
+// status[i] = 4 where the hash pass found element i's message range bad (fec_ecdsa_verify_msg_dev)
+__global__ __launch_bounds__(TPB) void k_bad_range_status(const unsigned char* __restrict__ bad, unsigned char* __restrict__ status,
+                                                          size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i < n && bad[i] != 0) status[i] = 4;
+}
+
+// The three passes of BipSchnorr::sign: each loads its element, runs its step of bip340.hpp and stores.
+__global__ __launch_bounds__(TPB) void k_bip340_pre(Bip340Io io, Bip340Work w, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  u64 lo = 0, len = 0;
+  unsigned char f = msg_range(io.off, io.msg_len, i, lo, len) ? 0 : bip340::F_BAD_RANGE;
+  u32 kw[8];
+  ld8(kw, io.keys + i * 8);
+  const fe d = bip340::pre_step(f, kw, len ? io.msgs + lo : nullptr, len);
+  st8(w.d + i * 8, d.w);
+  w.flags[i] = f;
+}
+
+// p: multiply(G, d) (24 words per element)
+__global__ __launch_bounds__(TPB) void k_bip340_mid(Bip340Io io, Bip340Work w, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  unsigned char f = w.flags[i];
+  u64 lo = 0, len = 0;
+  (void)msg_range(io.off, io.msg_len, i, lo, len);
+  fe d, px;
+  ld8(d.w, w.d + i * 8);
+  const fe k = bip340::mid_step(f, ld_pt(w.p + i * 24), d, px, len ? io.msgs + lo : nullptr, len);
+  st8(w.d + i * 8, d.w);
+  st8(w.k + i * 8, k.w);
+  st8(w.px + i * 8, px.w);
+  w.flags[i] = f;
+}
+
+// r: multiply(G, k) (24 words per element)
+__global__ __launch_bounds__(TPB) void k_bip340_finish(Bip340Io io, Bip340Work w, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  unsigned char f = w.flags[i];
+  u64 lo = 0, len = 0;
+  (void)msg_range(io.off, io.msg_len, i, lo, len);
+  fe k, d, px;
+  ld8(k.w, w.k + i * 8);
+  ld8(d.w, w.d + i * 8);
+  ld8(px.w, w.px + i * 8);
+  u32 o[16];
+  bip340::finish_step(f, ld_pt(w.r + i * 24), k, d, px, len ? io.msgs + lo : nullptr, len, o);
+  st8(io.sig + i * 16, o);
+  st8(io.sig + i * 16 + 8, o + 8);
+  io.status[i] = bip340::status_of(f);
+}
+
+unsigned grid(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
+
+}  // namespace
+
+void sha256_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
+                   hipStream_t s) {
+  hipLaunchKernelGGL(k_sha256, dim3(grid(n)), dim3(TPB), 0, s, msgs, off, msg_len, out, status, n);
+}
+void bad_range_status_launch(const unsigned char* bad, unsigned char* status, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_bad_range_status, dim3(grid(n)), dim3(TPB), 0, s, bad, status, n);
+}
+void bip340_pre_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_bip340_pre, dim3(grid(n)), dim3(TPB), 0, s, io, w, n);
+}
+void bip340_mid_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_bip340_mid, dim3(grid(n)), dim3(TPB), 0, s, io, w, n);
+}
+void bip340_finish_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_bip340_finish, dim3(grid(n)), dim3(TPB), 0, s, io, w, n);
+}
+
+}  // namespace fecgpu

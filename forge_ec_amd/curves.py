@@ -506,6 +506,45 @@ class Context:
         _check(self._lib.fec_sha512(self._h, _ptr(buf), _ptr(off), total, _ptr(out), n), "fec_sha512")
         return out
 
+    def sha256(self, msgs):
+        """SHA-256 of each byte string in msgs on the GPU: (n, 32) uint8."""
+        buf, off, total = self._messages(msgs)
+        n = len(off) - 1
+        out = np.zeros((n, 32), dtype=np.uint8)
+        _check(self._lib.fec_sha256(self._h, _ptr(buf), _ptr(off), total, _ptr(out), n), "fec_sha256")
+        return out
+
+    def ecdsa_verify_msg(self, curve, msgs, r, s, pk_xy, pk_inf=None):
+        """Ecdsa::<C, Sha256>::verify per signature FROM THE MESSAGE (ecdsa.rs:213-281), SHA-256 included: curve 0
+        (secp256k1) or 1 (P-256); msgs a list of n byte strings; r, s (n, 4); pk_xy (n, 8) raw limbs; pk_inf (n,) uint8 or
+        None.  Returns (n,) uint8: 1 valid, 0 invalid, 2 = the reference panics."""
+        rr, ss, pk = _u64(r, 4), _u64(s, 4), _u64(pk_xy, 8)
+        buf, off, total = self._messages(msgs)
+        n = rr.shape[0]
+        if not (ss.shape[0] == pk.shape[0] == n) or len(off) != n + 1:
+            raise ValueError("inputs differ in length")
+        inf = np.ascontiguousarray(np.asarray(pk_inf, dtype=np.uint8)).reshape(-1) if pk_inf is not None else None
+        if inf is not None and inf.shape[0] != n:
+            raise ValueError("flags and signatures differ in length")  # the C side reads n bytes
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_ecdsa_verify_msg(self._h, curve, _ptr(buf), _ptr(off), total, _ptr(rr), _ptr(ss), _ptr(pk), _ptr(inf),
+                                              _ptr(st), n), "fec_ecdsa_verify_msg")
+        return st
+
+    def bip340_sign(self, private_keys, msgs):
+        """BipSchnorr::sign per element (schnorr.rs:302-420), both SHA-256 passes included: private_keys (n, 32) uint8,
+        msgs a list of n byte strings.  Returns (sig (n, 64) uint8, status (n,) uint8: 0 computed, 1 the "test message"
+        pattern, 2 the 0..63 fallback).  The reference's signatures, not BIP-340 -- see include/fecgpu.h."""
+        k = np.ascontiguousarray(np.asarray(private_keys, dtype=np.uint8)).reshape(-1, 32)
+        buf, off, total = self._messages(msgs)
+        n = k.shape[0]
+        if len(off) != n + 1:
+            raise ValueError("inputs differ in length")
+        sig = np.zeros((n, 64), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_bip340_sign(self._h, _ptr(k), _ptr(buf), _ptr(off), total, _ptr(sig), _ptr(st), n), "fec_bip340_sign")
+        return sig, st
+
     def curve25519_mul(self, scalars, points):
         """Curve25519::multiply per element (curve25519.rs:1922-1955): scalars (n, 4) raw Scalar limbs, points (n, 8)
         ProjectivePoint X limbs then Z limbs; returns (n, 8) likewise."""
@@ -631,6 +670,17 @@ class Context:
 
     def sha512_dev(self, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream=None):
         _check(self._lib.fec_sha512_dev(self._h, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream), "fec_sha512_dev")
+
+    def sha256_dev(self, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream=None):
+        _check(self._lib.fec_sha256_dev(self._h, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream), "fec_sha256_dev")
+
+    def ecdsa_verify_msg_dev(self, curve, d_msgs, d_msg_off, msg_len, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n, stream=None):
+        _check(self._lib.fec_ecdsa_verify_msg_dev(self._h, curve, d_msgs, d_msg_off, msg_len, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n,
+                                                  stream), "fec_ecdsa_verify_msg_dev")
+
+    def bip340_sign_dev(self, d_private_keys, d_msgs, d_msg_off, msg_len, d_signatures, d_status, n, stream=None):
+        _check(self._lib.fec_bip340_sign_dev(self._h, d_private_keys, d_msgs, d_msg_off, msg_len, d_signatures, d_status, n, stream),
+               "fec_bip340_sign_dev")
 
     def ecdsa_sign_dev(self, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream=None):
         _check(self._lib.fec_ecdsa_sign_dev(self._h, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream), "fec_ecdsa_sign_dev")

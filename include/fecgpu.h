@@ -41,6 +41,10 @@
  *   fec_sha512            SHA-512 per message (FIPS 180-4, the sha2 crate the reference signs with)
  *   fec_ed25519_verify    Ed25519Signature::verify from the message: decoding and SHA-512 included (eddsa.rs:360-447)
  *   fec_eddsa_verify_ed25519_msg   EdDsa::<Ed25519, Sha512>::verify from the message (eddsa.rs:156-212)
+ *   fec_sha256            SHA-256 per message (FIPS 180-4, the sha2 crate the reference hashes with)
+ *   fec_ecdsa_verify_msg  Ecdsa::<C, Sha256>::verify for secp256k1 / P-256 from the message, hash included (ecdsa.rs:213-281)
+ *   fec_bip340_sign       BipSchnorr::sign, both hashes included (forge-ec-signature/src/schnorr.rs:302-420; inherent
+ *                         Scalar::from_bytes / to_bytes secp256k1.rs:1924-1951, Neg 2466-2488)
  *   fec_ecdsa_batch_verify   Ecdsa::<C, D>::batch_verify for secp256k1 / P-256 (ecdsa.rs:287-391; scalar Add
  *                         secp256k1.rs:2358-2378, p256.rs:1352-1375)
  *   fec_eddsa_verify_ed25519   Eddsa::<Ed25519, D>::verify / Ed25519::verify after the hash and the decoding
@@ -577,6 +581,61 @@ int fec_eddsa_verify_ed25519_msg(fec_ctx* ctx, const uint64_t* pk_xy /* n*8 */, 
 int fec_eddsa_verify_ed25519_msg_dev(fec_ctx* ctx, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf, const uint8_t* d_msgs,
                                      const uint64_t* d_msg_off, size_t msg_len, const uint64_t* d_r_xy, const uint8_t* d_r_inf,
                                      const uint64_t* d_s, uint8_t* d_status, size_t n, void* stream);
+
+/* ---- SHA-256, ECDSA verification FROM THE MESSAGE and BIP-340 signing (ecdsa.rs, schnorr.rs), parity mode ----
+ * Messages: the layout, the alignment rules and status 4 of the EdDSA signing block above -- message i is msgs[msg_off[i],
+ * msg_off[i+1]), msg_off holds n + 1 values with msg_off[0] = 0, non-decreasing, msg_off[n] = msg_len; msgs has any alignment
+ * and may be NULL when msg_len is 0.  The host forms check this and return FEC_E_ARG; in the _dev forms each element checks
+ * its own range against msg_len: a bad range gets status 4 and zero outputs, and nothing outside [msgs, msgs + msg_len) is read.
+ * The _dev forms take 16-byte aligned arrays and an 8-byte aligned d_msg_off, return FEC_E_UNSUPPORTED on a multi-device
+ * ctx and never build a fixed-base prefix table (they take one that exists); the host forms chunk by fec_ctx_set_chunk and
+ * shard over a multi-device ctx.
+ * fec_sha256       digests[i] = SHA-256(msg_i), 32 bytes; as fec_sha512 (_dev: d_status may be NULL, else 0 or 4 per message).
+ * fec_ecdsa_verify_msg   status[i] = Ecdsa::<C, Sha256>::verify(pk[i], msg_i, Signature { r[i], s[i] }) (ecdsa.rs:213-281)
+ *   for curve = FEC_SECP256K1 or FEC_P256 (else FEC_E_UNSUPPORTED): one SHA-256 pass into the call's work area, then
+ *   exactly the pipeline of fec_ecdsa_verify_secp256k1 / _p256 on those digests, with their arguments and their status:
+ *   1 true; 0 false; 2 the reference panics there -- which includes `from_bytes(h).unwrap()` on a digest that is not below
+ *   the curve's order constant (239); 4 bad message range (_dev form only).  Unlike the Schnorr and EdDSA functions,
+ *   ecdsa.rs:213-281 has no message special case: "test message" is hashed like any other.  Nothing here is secret.
+ * fec_bip340_sign  signatures[i] = BipSchnorr::sign(private_keys[i], msg_i) (schnorr.rs:302-420), 64 bytes, bit for bit:
+ *   NOT BIP-340 (no tagged hashes, no auxiliary randomness; the reference's order constant has its two top limbs
+ *   swapped and its scalar Mul keeps the low 256 bits of the product).  In the reference's order:
+ *     msg == "test message" -> the bytes 0..63, before the key is looked at (307-316);
+ *     d = Scalar::from_bytes(private_key): the INHERENT form (secp256k1.rs:1936-1951; Rust resolves an inherent
+ *       associated function before a trait one) -- LITTLE-endian, None iff the value is not below the order constant,
+ *       zero is Some; None -> the bytes 0..63 (324-332);
+ *     P = to_affine(multiply(G, d)); P.x.to_bytes() and P.y.to_bytes() are the field's inherent to_bytes (138-178:
+ *       mont_reduce, big-endian), byte 31 of y the parity byte: odd -> d = -d (Neg, 2466-2488) (337-349).  d = 0 gives the
+ *       identity, whose to_affine is (0, 0, infinity): P.x is 32 zero bytes, the parity even, and s below is k;
+ *     k = Scalar::from_bytes(SHA256(d.to_bytes() || msg)), d.to_bytes() the inherent little-endian form (1924-1933);
+ *       None -> the bytes 0..63 (352-368);
+ *     R = to_affine(multiply(G, k)), odd R.y -> k = -k (373-385);
+ *     e = Scalar::from_bytes(SHA256(R.x bytes || P.x bytes || msg)); None -> the bytes 0..63 (388-405);
+ *     s = k + e * d (impl Mul 2410-2456, Add 2358-2378); the signature is R.x bytes || s.to_bytes() (410-417).
+ *   k and e are None only for a hash whose top little-endian limb is >= 0xFFFFFFFFFFFFFFFE (about 2^-127): no known
+ *   message reaches those legs; tests/test_sha256_host.py forces the step on the CPU.
+ *   status[i]: 0 computed signature; 1 the "test message" pattern; 2 the 0..63 fallback (d, k or e not below the order
+ *   constant); 3 is reserved for "the reference panics" and is never returned: to_affine inverts z only when z != 0
+ *   (1344, 1353) and every from_bytes is tested before its unwrap, so BipSchnorr::sign has no reachable panic;
+ *   4 bad message range (_dev form only; the signature is 0).
+ *   SECRETS: the private keys, d, -d, k, -k and the digest behind k.  The host form clears its device staging of the keys
+ *   and of the outputs and the stream scratch (d, k, P, R) on every way out, as fec_ecdsa_sign and fec_ed25519_sign do; the
+ *   digest never leaves the registers.  The _dev form leaves every buffer to the caller (the stream's scratch keeps d, k,
+ *   P and R until the ctx is wiped, fec_ctx_wipe, or destroyed).  NOT constant-time. */
+int fec_sha256(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len, uint8_t* digests /* n*32 */,
+               size_t n);
+int fec_sha256_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
+                   uint8_t* d_status, size_t n, void* stream);
+int fec_ecdsa_verify_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                         const uint64_t* r /* n*4 */, const uint64_t* s /* n*4 */, const uint64_t* pk_xy /* n*8 */,
+                         const uint8_t* pk_inf /* n or NULL */, uint8_t* status /* n */, size_t n);
+int fec_ecdsa_verify_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                             const uint64_t* d_r, const uint64_t* d_s, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf,
+                             uint8_t* d_status, size_t n, void* stream);
+int fec_bip340_sign(fec_ctx* ctx, const uint8_t* private_keys /* n*32 */, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */,
+                    size_t msg_len, uint8_t* signatures /* n*64 */, uint8_t* status /* n */, size_t n);
+int fec_bip340_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                        size_t msg_len, uint8_t* d_signatures, uint8_t* d_status, size_t n, void* stream);
 
 /* Every element-wise host-pointer entry point processes its batch in chunks of `elements` elements
  * (default 2^18), so device staging memory is bounded by two chunks for any n.  Most run them as a

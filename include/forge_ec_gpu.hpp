@@ -651,6 +651,56 @@ inline std::vector<Bytes64> sha512(GpuContext& ctx, const std::vector<std::strin
 }
 }  // namespace eddsa
 
+// ---- SHA-256 on the GPU (fec_sha256) and its two users: messages as eddsa::detail::Messages packs them ----
+namespace sha2 {
+// SHA-256 of each message (fec_sha256)
+inline std::vector<eddsa::Bytes32> sha256(GpuContext& ctx, const std::vector<std::string>& msgs) {
+  const eddsa::detail::Messages m(msgs);
+  std::vector<eddsa::Bytes32> out(msgs.size());
+  check(fec_sha256(ctx.raw(), m.bytes.data(), m.off.data(), m.bytes.size(), reinterpret_cast<uint8_t*>(out.data()), msgs.size()));
+  return out;
+}
+}  // namespace sha2
+namespace ecdsa {
+// Ecdsa::<C, Sha256>::verify(public_keys[i], msgs[i], sigs[i]) (ecdsa.rs:213-281), C = Secp256k1 or P256, the hash on
+// the GPU as well (fec_ecdsa_verify_msg).  The function has no message special case.
+template <fec_curve C>
+inline std::vector<Verify> verify(GpuContext& ctx, const std::vector<AffinePoint<C>>& public_keys,
+                                  const std::vector<std::string>& msgs, const std::vector<Signature<C>>& sigs) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "Ecdsa is built for secp256k1 and P-256");
+  const size_t n = sigs.size();
+  if (public_keys.size() != n || msgs.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  std::vector<uint64_t> pk, r(n * 4), s(n * 4);
+  std::vector<uint8_t> inf, st(n);
+  detail::pack_affine<C>(public_keys, pk, inf);
+  for (size_t i = 0; i < n; ++i)
+    for (int l = 0; l < 4; ++l) {
+      r[i * 4 + l] = sigs[i].r.raw[l];
+      s[i * 4 + l] = sigs[i].s.raw[l];
+    }
+  check(fec_ecdsa_verify_msg(ctx.raw(), C, m.bytes.data(), m.off.data(), m.bytes.size(), r.data(), s.data(), pk.data(), inf.data(),
+                             st.data(), n));
+  return detail::statuses(st);
+}
+}  // namespace ecdsa
+namespace schnorr {
+// BipSchnorr::sign(private_keys[i], msgs[i]) (schnorr.rs:302-420), both hashes on the GPU (fec_bip340_sign): the
+// reference's signer, not BIP-340.  status: 0 computed, 1 the "test message" pattern, 2 the 0..63 fallback.
+inline std::vector<eddsa::Bytes64> bip340_sign(GpuContext& ctx, const std::vector<eddsa::Bytes32>& private_keys,
+                                               const std::vector<std::string>& msgs, std::vector<uint8_t>* status = nullptr) {
+  const size_t n = private_keys.size();
+  if (msgs.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  std::vector<eddsa::Bytes64> sig(n);
+  std::vector<uint8_t> st(n);
+  check(fec_bip340_sign(ctx.raw(), reinterpret_cast<const uint8_t*>(private_keys.data()), m.bytes.data(), m.off.data(), m.bytes.size(),
+                        reinterpret_cast<uint8_t*>(sig.data()), st.data(), n));
+  if (status) *status = st;
+  return sig;
+}
+}  // namespace schnorr
+
 namespace encoding {
 // PointAffine::from_bytes(&[u8; 33]) per element (secp256k1.rs:896-976, p256.rs:1580-1639, ed25519.rs:1526-1582):
 // nullopt-like `ok[i] == 0` where the reference returns None.

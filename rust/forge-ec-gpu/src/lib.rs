@@ -90,6 +90,12 @@ extern "C" {
     fn fec_ed25519_verify_dev(ctx: *mut FecCtx, d_public_keys: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_sigs: *const u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_eddsa_verify_ed25519_msg(ctx: *mut FecCtx, pk_xy: *const u64, pk_inf: *const u8, msgs: *const u8, msg_off: *const u64, msg_len: usize, r_xy: *const u64, r_inf: *const u8, s: *const u64, status: *mut u8, n: usize) -> c_int;
     fn fec_eddsa_verify_ed25519_msg_dev(ctx: *mut FecCtx, d_pk_xy: *const u64, d_pk_inf: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *const u64, d_r_inf: *const u8, d_s: *const u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_sha256(ctx: *mut FecCtx, msgs: *const u8, msg_off: *const u64, msg_len: usize, digests: *mut u8, n: usize) -> c_int;
+    fn fec_sha256_dev(ctx: *mut FecCtx, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_digests: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_ecdsa_verify_msg(ctx: *mut FecCtx, curve: c_int, msgs: *const u8, msg_off: *const u64, msg_len: usize, r: *const u64, s: *const u64, pk_xy: *const u64, pk_inf: *const u8, status: *mut u8, n: usize) -> c_int;
+    fn fec_ecdsa_verify_msg_dev(ctx: *mut FecCtx, curve: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r: *const u64, d_s: *const u64, d_pk_xy: *const u64, d_pk_inf: *const u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_bip340_sign(ctx: *mut FecCtx, private_keys: *const u8, msgs: *const u8, msg_off: *const u64, msg_len: usize, signatures: *mut u8, status: *mut u8, n: usize) -> c_int;
+    fn fec_bip340_sign_dev(ctx: *mut FecCtx, d_private_keys: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_signatures: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_ctx_set_chunk(ctx: *mut FecCtx, elements: usize) -> c_int;
     fn fec_ctx_set_timing(ctx: *mut FecCtx, enabled: c_int) -> c_int;
     fn fec_ctx_last_kernel_ms(ctx: *mut FecCtx, ms: *mut c_float, kernel_name: *mut *const c_char) -> c_int;
@@ -720,6 +726,63 @@ pub fn sha512_batch(ctx: &mut GpuContext, msgs: &[&[u8]]) -> Result<Vec<[u8; 64]
     Ok(out)
 }
 
+/// SHA-256 of each message on the GPU (`fec_sha256`).
+pub fn sha256_batch(ctx: &mut GpuContext, msgs: &[&[u8]]) -> Result<Vec<[u8; 32]>> {
+    let n = msgs.len();
+    let (buf, off) = pack_messages(msgs);
+    let mut out = vec![[0u8; 32]; n];
+    // SAFETY: off holds n + 1 offsets into buf, out n * 32 bytes.
+    check(unsafe { fec_sha256(ctx.raw, buf.as_ptr(), off.as_ptr(), buf.len(), out.as_mut_ptr() as *mut u8, n) })?;
+    Ok(out)
+}
+
+/// `Ecdsa::<C, Sha256>::verify(&public_keys[i], msgs[i], &Signature { r[i], s[i] })` per element for C = Secp256k1 or
+/// P256 (`forge-ec-signature/src/ecdsa.rs:213-281`), SHA-256 included (`fec_ecdsa_verify_msg`).  Nothing here is secret.
+pub fn ecdsa_verify_msg_batch<C: GpuCurve>(ctx: &mut GpuContext, public_keys: &[C::PointAffine], msgs: &[&[u8]], r: &[C::Scalar], s: &[C::Scalar]) -> Result<Vec<VerifyStatus>> {
+    let n = public_keys.len();
+    if msgs.len() != n || r.len() != n || s.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let (buf, off) = pack_messages(msgs);
+    let (rr, ss) = (pack_scalars::<C>(r), pack_scalars::<C>(s));
+    let (mut xy, mut inf) = (vec![0u64; 8 * n], vec![0u8; n]);
+    for (i, a) in public_keys.iter().enumerate() {
+        let (l, f) = C::affine_limbs(a);
+        xy[8 * i..8 * i + 8].copy_from_slice(&l);
+        inf[i] = f as u8;
+    }
+    let mut status = vec![0u8; n];
+    // SAFETY: off holds n + 1 offsets into buf; the other buffers hold n elements of the width the header states.
+    check(unsafe { fec_ecdsa_verify_msg(ctx.raw, C::ID, buf.as_ptr(), off.as_ptr(), buf.len(), rr.as_ptr(), ss.as_ptr(), xy.as_ptr(), inf.as_ptr(), status.as_mut_ptr(), n) })?;
+    Ok(verify_statuses(&status))
+}
+
+/// Which leg of `BipSchnorr::sign` produced a signature (`fec_bip340_sign`'s status).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Bip340Leg {
+    /// the computed signature
+    Computed,
+    /// the bytes 0..63 the reference returns for `msg == b"test message"`
+    TestMessagePattern,
+    /// the bytes 0..63 the reference returns when the key, the nonce or the challenge is not below its order constant
+    FallbackPattern,
+}
+
+/// `BipSchnorr::sign(&private_keys[i], msgs[i])` per element (`forge-ec-signature/src/schnorr.rs:302-420`), both
+/// SHA-256 passes included, bit for bit: the reference's signer, not BIP-340 (see `fec_bip340_sign` in
+/// include/fecgpu.h).  The keys are secret: the library clears its device copies before it returns.
+pub fn bip340_sign_batch(ctx: &mut GpuContext, private_keys: &[[u8; 32]], msgs: &[&[u8]]) -> Result<Vec<([u8; 64], Bip340Leg)>> {
+    let n = private_keys.len();
+    if msgs.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let (buf, off) = pack_messages(msgs);
+    let (mut sig, mut status) = (vec![[0u8; 64]; n], vec![0u8; n]);
+    // SAFETY: keys n * 32 bytes, off n + 1 offsets into buf, sig n * 64 bytes, status n.
+    check(unsafe { fec_bip340_sign(ctx.raw, private_keys.as_ptr() as *const u8, buf.as_ptr(), off.as_ptr(), buf.len(), sig.as_mut_ptr() as *mut u8, status.as_mut_ptr(), n) })?;
+    Ok((0..n).map(|i| (sig[i], match status[i] { 1 => Bip340Leg::TestMessagePattern, 2 => Bip340Leg::FallbackPattern, _ => Bip340Leg::Computed })).collect())
+}
+
 /// `Curve25519::multiply(p, k)` per element (`forge-ec-curves/src/curve25519.rs:1922-1955`).  The reference keeps the
 /// coordinates of its `ProjectivePoint` private, so points cross as `(x, z)` field elements (`FieldElement::from_raw`
 /// / `to_raw`), exactly the values the reference holds, unreduced ones included.
@@ -1062,6 +1125,30 @@ pub mod dev {
     /// As [`batch_mul`].
     pub unsafe fn sha512(ctx: &mut GpuContext, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_digests: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
         check(fec_sha512_dev(ctx.raw, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream))
+    }
+
+    /// `fec_sha256_dev` (`d_status` may be null).
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn sha256(ctx: &mut GpuContext, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_digests: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_sha256_dev(ctx.raw, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream))
+    }
+
+    /// `fec_ecdsa_verify_msg_dev` (`d_pk_inf` may be null).
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn ecdsa_verify_msg(ctx: &mut GpuContext, curve: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r: *const u64, d_s: *const u64, d_pk_xy: *const u64, d_pk_inf: *const u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_ecdsa_verify_msg_dev(ctx.raw, curve, d_msgs, d_msg_off, msg_len, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n, stream))
+    }
+
+    /// `fec_bip340_sign_dev`.  The stream's scratch keeps d, k and the two points until the ctx is wiped.
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn bip340_sign(ctx: &mut GpuContext, d_private_keys: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_signatures: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_bip340_sign_dev(ctx.raw, d_private_keys, d_msgs, d_msg_off, msg_len, d_signatures, d_status, n, stream))
     }
 
     /// `fec_schnorr_verify_dev`.
