@@ -3,39 +3,22 @@
 // parallelism is inside one addition).  Values travel between lanes through eight-word slots of LDS owned by
 // the wavefront; a wavefront's LDS instructions execute in program order, so a read issued after another
 // lane's write (same wavefront, later instruction) returns the written data and no s_waitcnt is needed between
-// them, only compiler ordering.  secp256k1.hpp carries its own copy of these helpers (namespace secp::coop).
+// them, only compiler ordering.  All three curves' cooperative additions (secp::, p256::, ed::padd_coop) use these.
 #pragma once
 #include "limbs.hpp"
+#include "point_io.hpp"
 
 namespace fecgpu {
 namespace coopx {
 
+// a slot is 32 bytes, 16-byte aligned (the caller's array is): two ds_read_b128 / ds_write_b128
+FEC_DEV fe ld(const u32* sh, int slot) { return load_fe16(sh + slot * 8); }
+FEC_DEV void st(u32* sh, int slot, const fe& a) { store_fe16(sh + slot * 8, a); }
 #ifdef FEC_HOST_EMUL
-FEC_DEV fe ld(const u32* sh, int slot) {
-  fe a;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) a.w[i] = sh[slot * 8 + i];
-  return a;
-}
-FEC_DEV void st(u32* sh, int slot, const fe& a) {
-  FEC_UNROLL for (int i = 0; i < 8; ++i) sh[slot * 8 + i] = a.w[i];
-}
 FEC_DEV void sync() {}
 FEC_DEV int lane_id() { return 0; }
 #else
-// a slot is 32 bytes, 16-byte aligned (the caller's array is): two ds_read_b128 / ds_write_b128
-FEC_DEV fe ld(const u32* sh, int slot) {
-  const uint4* s4 = reinterpret_cast<const uint4*>(sh + slot * 8);
-  const uint4 lo = s4[0], hi = s4[1];
-  fe a;
-  a.w[0] = lo.x; a.w[1] = lo.y; a.w[2] = lo.z; a.w[3] = lo.w;
-  a.w[4] = hi.x; a.w[5] = hi.y; a.w[6] = hi.z; a.w[7] = hi.w;
-  return a;
-}
-FEC_DEV void st(u32* sh, int slot, const fe& a) {
-  uint4* s4 = reinterpret_cast<uint4*>(sh + slot * 8);
-  s4[0] = make_uint4(a.w[0], a.w[1], a.w[2], a.w[3]);
-  s4[1] = make_uint4(a.w[4], a.w[5], a.w[6], a.w[7]);
-}
+// the fences emit no instruction at wavefront scope
 FEC_DEV void sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();

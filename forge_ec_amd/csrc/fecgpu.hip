@@ -36,22 +36,13 @@ namespace fecgpu {
 struct Secp {
   static constexpr int PW = 24;  // 32-bit words per point
   using pt = secp::pt;
-  FEC_DEV static pt load(const u32* l, int stride) {
-    pt p;
-    FEC_UNROLL for (int i = 0; i < 8; ++i) {
-      p.x.w[i] = l[i * stride];
-      p.y.w[i] = l[(8 + i) * stride];
-      p.z.w[i] = l[(16 + i) * stride];
-    }
-    return p;
+  // the cooperative addition of the ordered folds (fold_coop): its LDS words, its constant slots, the addition itself
+  static constexpr int COOP_WORDS = secp::coop::WORDS;
+  static_assert(secp::coop::PX == 0 && secp::coop::QX * 8 == PW, "p's slots start the area, q's follow them");
+  FEC_DEV static void coop_constants(u32* sh) {
+    coopx::st(sh, secp::coop::ONE, fe_small(1));
   }
-  FEC_DEV static void store(u32* l, int stride, const pt& p) {
-    FEC_UNROLL for (int i = 0; i < 8; ++i) {
-      l[i * stride] = p.x.w[i];
-      l[(8 + i) * stride] = p.y.w[i];
-      l[(16 + i) * stride] = p.z.w[i];
-    }
-  }
+  FEC_DEV static pt padd_coop(u32* sh) { return secp::padd_coop(sh); }
   FEC_DEV static pt multiply(const pt& p, const u32* kw) { return secp::multiply(p, kw); }
   FEC_DEV static lmask to_affine(const pt& p, fe& x, fe& y) { return secp::to_affine(p, x, y); }
   FEC_DEV static pt identity() { return secp::identity(); }
@@ -79,22 +70,13 @@ struct Secp {
 struct P256 {
   static constexpr int PW = 24;
   using pt = p256::pt;
-  FEC_DEV static pt load(const u32* l, int stride) {
-    pt p;
-    FEC_UNROLL for (int i = 0; i < 8; ++i) {
-      p.x.w[i] = l[i * stride];
-      p.y.w[i] = l[(8 + i) * stride];
-      p.z.w[i] = l[(16 + i) * stride];
-    }
-    return p;
+  // the cooperative addition of the ordered folds (fold_coop): its LDS words, its constant slots, the addition itself
+  static constexpr int COOP_WORDS = p256::coop::WORDS;
+  static_assert(p256::coop::PX == 0 && p256::coop::QX * 8 == PW, "p's slots start the area, q's follow them");
+  FEC_DEV static void coop_constants(u32* sh) {
+    coopx::st(sh, p256::coop::ONE, fe_small(1));
   }
-  FEC_DEV static void store(u32* l, int stride, const pt& p) {
-    FEC_UNROLL for (int i = 0; i < 8; ++i) {
-      l[i * stride] = p.x.w[i];
-      l[(8 + i) * stride] = p.y.w[i];
-      l[(16 + i) * stride] = p.z.w[i];
-    }
-  }
+  FEC_DEV static pt padd_coop(u32* sh) { return p256::padd_coop(sh); }
   FEC_DEV static pt multiply(const pt& p, const u32* kw) { return p256::multiply(p, kw); }
   FEC_DEV static lmask to_affine(const pt& p, fe& x, fe& y) { return p256::to_affine(p, x, y); }
   FEC_DEV static pt identity() { return p256::identity(); }
@@ -122,24 +104,14 @@ struct P256 {
 struct Ed {
   static constexpr int PW = 32;
   using pt = ed::pt;
-  FEC_DEV static pt load(const u32* l, int stride) {
-    pt p;
-    FEC_UNROLL for (int i = 0; i < 8; ++i) {
-      p.x.w[i] = l[i * stride];
-      p.y.w[i] = l[(8 + i) * stride];
-      p.z.w[i] = l[(16 + i) * stride];
-      p.t.w[i] = l[(24 + i) * stride];
-    }
-    return p;
+  // the cooperative addition of the ordered folds (fold_coop): its LDS words, its constant slots, the addition itself
+  static constexpr int COOP_WORDS = ed::coop::WORDS;
+  static_assert(ed::coop::PX == 0 && ed::coop::QX * 8 == PW, "p's slots start the area, q's follow them");
+  FEC_DEV static void coop_constants(u32* sh) {
+    coopx::st(sh, ed::coop::ONE, fe_small(1));
+    coopx::st(sh, ed::coop::DCONST, ed::D_());
   }
-  FEC_DEV static void store(u32* l, int stride, const pt& p) {
-    FEC_UNROLL for (int i = 0; i < 8; ++i) {
-      l[i * stride] = p.x.w[i];
-      l[(8 + i) * stride] = p.y.w[i];
-      l[(16 + i) * stride] = p.z.w[i];
-      l[(24 + i) * stride] = p.t.w[i];
-    }
-  }
+  FEC_DEV static pt padd_coop(u32* sh) { return ed::padd_coop(sh); }
   FEC_DEV static pt multiply(const pt& p, const u32* kw) { return ed::multiply(p, kw); }
   FEC_DEV static lmask to_affine(const pt& p, fe& x, fe& y) { return ed::to_affine(p, x, y); }
   FEC_DEV static pt identity() { return ed::identity(); }
@@ -234,11 +206,11 @@ __global__ __launch_bounds__(TPB) void k_point_op(int op, const u32* __restrict_
   __syncthreads();
   const int e = threadIdx.x;
   if (e < valid) {
-    typename C::pt a = C::load(lds_p + e, TPB);
+    typename C::pt a = load_pt<typename C::pt>(lds_p + e, TPB);
     typename C::pt r;
     switch (op) {
       case FEC_P_ADD: {
-        typename C::pt b = C::load(lds_q + e, TPB);
+        typename C::pt b = load_pt<typename C::pt>(lds_q + e, TPB);
         r = C::padd(a, b);
         break;
       }
@@ -246,7 +218,7 @@ __global__ __launch_bounds__(TPB) void k_point_op(int op, const u32* __restrict_
       case FEC_P_NEGATE: r = C::pnegate(a); break;
       default: r = C::pdouble_trait(a); break;
     }
-    C::store(lds_p + e, TPB, r);
+    store_pt(lds_p + e, TPB, r);
   }
   __syncthreads();
   stage_out<C::PW>(out + first * C::PW, lds_p, valid);
@@ -259,72 +231,21 @@ __global__ __launch_bounds__(TPB) void k_point_op(int op, const u32* __restrict_
 // Each addition is spread over a few lanes of the wavefront (secp::padd_coop: four lanes, 6 instead of 16
 // dependent field operations; p256::padd_coop: five lanes, 5 instead of 16; ed::padd_coop: four lanes, 3
 // instead of 9) -- the same products on the same operands, so the sums are bit-identical.
-// One wavefront folds `terms` left to right from the identity with the cooperative addition.
-FEC_DEV secp::pt fold_coop_secp(const u32* __restrict__ terms, size_t n, u32* sh) {
-  using namespace secp::coop;
+// One wavefront folds `terms` left to right from the identity with the curve's cooperative addition.
+template <class C>
+FEC_DEV typename C::pt fold_coop(const u32* __restrict__ terms, size_t n, u32* sh) {
   const int lane = threadIdx.x & 63;
-  secp::pt acc = secp::identity();
-  if (lane == 0) st(sh, ONE, fe_small(1));
+  typename C::pt acc = C::identity();
+  if (lane == 0) C::coop_constants(sh);
   // term i + 1 is fetched (one word per lane) while addition i runs, so its HBM/L2 latency is hidden
-  u32 next_word = (n != 0 && lane < 24) ? terms[lane] : 0u;
+  u32 next_word = (n != 0 && lane < C::PW) ? terms[lane] : 0u;
 #pragma unroll 1
   for (size_t i = 0; i < n; ++i) {
-    if (lane == 0) {
-      st(sh, PX, acc.x);
-      st(sh, PY, acc.y);
-      st(sh, PZ, acc.z);
-    }
-    if (lane < 24) sh[QX * 8 + lane] = next_word;  // q = term i (X, Y, Z: slots QX..QZ are contiguous)
-    if (i + 1 < n && lane < 24) next_word = terms[(i + 1) * Secp::PW + lane];
-    sync();
-    acc = secp::padd_coop(sh);
-  }
-  return acc;
-}
-
-// P-256: the same fold with p256::padd_coop (five lanes, 5 instead of 16 dependent field operations)
-FEC_DEV p256::pt fold_coop_p256(const u32* __restrict__ terms, size_t n, u32* sh) {
-  using namespace p256::coop;
-  const int lane = threadIdx.x & 63;
-  p256::pt acc = p256::identity();
-  if (lane == 0) coopx::st(sh, ONE, fe_small(1));
-  u32 next_word = (n != 0 && lane < 24) ? terms[lane] : 0u;
-#pragma unroll 1
-  for (size_t i = 0; i < n; ++i) {
-    if (lane == 0) {
-      coopx::st(sh, PX, acc.x);
-      coopx::st(sh, PY, acc.y);
-      coopx::st(sh, PZ, acc.z);
-    }
-    if (lane < 24) sh[QX * 8 + lane] = next_word;  // q = term i (X, Y, Z: slots QX..QZ are contiguous)
-    if (i + 1 < n && lane < 24) next_word = terms[(i + 1) * P256::PW + lane];
+    if (lane == 0) store_pt16(sh, acc);                 // p = the running sum: slots PX.. are the first PW words
+    if (lane < C::PW) sh[C::PW + lane] = next_word;     // q = term i: slots QX.. follow them
+    if (i + 1 < n && lane < C::PW) next_word = terms[(i + 1) * C::PW + lane];
     coopx::sync();
-    acc = p256::padd_coop(sh);
-  }
-  return acc;
-}
-// Ed25519: ed::padd_coop (four lanes, 3 instead of 9 dependent field operations)
-FEC_DEV ed::pt fold_coop_ed(const u32* __restrict__ terms, size_t n, u32* sh) {
-  using namespace ed::coop;
-  const int lane = threadIdx.x & 63;
-  ed::pt acc = ed::identity();
-  if (lane == 0) {
-    coopx::st(sh, ONE, fe_small(1));
-    coopx::st(sh, DCONST, ed::D_());
-  }
-  u32 next_word = (n != 0 && lane < 32) ? terms[lane] : 0u;
-#pragma unroll 1
-  for (size_t i = 0; i < n; ++i) {
-    if (lane == 0) {
-      coopx::st(sh, PX, acc.x);
-      coopx::st(sh, PY, acc.y);
-      coopx::st(sh, PZ, acc.z);
-      coopx::st(sh, PT, acc.t);
-    }
-    if (lane < 32) sh[QX * 8 + lane] = next_word;  // q = term i (X, Y, Z, T: slots QX..QT are contiguous)
-    if (i + 1 < n && lane < 32) next_word = terms[(i + 1) * Ed::PW + lane];
-    coopx::sync();
-    acc = ed::padd_coop(sh);
+    acc = C::padd_coop(sh);
   }
   return acc;
 }
@@ -332,19 +253,9 @@ FEC_DEV ed::pt fold_coop_ed(const u32* __restrict__ terms, size_t n, u32* sh) {
 template <class C>
 __global__ __launch_bounds__(64) void k_fold_sum(const u32* __restrict__ products, u32* __restrict__ out, size_t n) {
   if (blockIdx.x != 0) return;
-  if constexpr (__is_same(typename C::pt, secp::pt)) {
-    __shared__ __attribute__((aligned(16))) u32 sh[secp::coop::WORDS];
-    secp::pt acc = fold_coop_secp(products, n, sh);
-    if (threadIdx.x == 0) C::store(out, 1, acc);
-  } else if constexpr (__is_same(typename C::pt, p256::pt)) {
-    __shared__ __attribute__((aligned(16))) u32 sh[p256::coop::WORDS];
-    p256::pt acc = fold_coop_p256(products, n, sh);
-    if (threadIdx.x == 0) C::store(out, 1, acc);
-  } else {
-    __shared__ __attribute__((aligned(16))) u32 sh[ed::coop::WORDS];
-    ed::pt acc = fold_coop_ed(products, n, sh);
-    if (threadIdx.x == 0) C::store(out, 1, acc);
-  }
+  __shared__ __attribute__((aligned(16))) u32 sh[C::COOP_WORDS];
+  const typename C::pt acc = fold_coop<C>(products, n, sh);
+  if (threadIdx.x == 0) store_pt(out, 1, acc);
 }
 
 // xy[i] = to_affine(points[i]) as (x, y); inf[i] = 1 where the point is the identity
@@ -358,7 +269,7 @@ __global__ __launch_bounds__(TPB) void k_to_affine(const u32* __restrict__ point
   __syncthreads();
   const int e = threadIdx.x;
   if (e < valid) {
-    typename C::pt p = C::load(lds_p + e, TPB);
+    typename C::pt p = load_pt<typename C::pt>(lds_p + e, TPB);
     fe x, y;
     lmask m = C::to_affine(p, x, y);
     bool mine = lane_of(m);
@@ -393,7 +304,7 @@ __global__ __launch_bounds__(TPB) void k_schnorr_pre(const u32* __restrict__ pk_
   // from_affine: the caller has rejected identities
   fe x, y;
   FEC_UNROLL for (int w = 0; w < 8; ++w) { x.w[w] = pk_xy[i * 16 + w]; y.w[w] = pk_xy[i * 16 + 8 + w]; }
-  C::store(p_out + i * C::PW, 1, C::from_affine(x, y));
+  store_pt(p_out + i * C::PW, 1, C::from_affine(x, y));
 }
 // q_i = from_affine(R_i) + ep_i   (277-279)
 template <class C>
@@ -409,7 +320,7 @@ __global__ __launch_bounds__(TPB) void k_schnorr_mid(const u32* __restrict__ r_x
   const int e = threadIdx.x;
   if (e < valid) {
     const typename C::pt r = C::from_affine(load_fe(lds_r + e, TPB), load_fe(lds_r + 8 * TPB + e, TPB));
-    C::store(lds_p + e, TPB, C::padd(r, C::load(lds_p + e, TPB)));
+    store_pt(lds_p + e, TPB, C::padd(r, load_pt<typename C::pt>(lds_p + e, TPB)));
   }
   __syncthreads();
   stage_out<C::PW>(q_out + first * C::PW, lds_p, valid);
@@ -426,16 +337,12 @@ __global__ __launch_bounds__(64) void k_schnorr_fold_compare(const u32* __restri
                                                              u32* __restrict__ sums, u32* __restrict__ out_xy,
                                                              unsigned char* __restrict__ flags,
                                                              unsigned int* __restrict__ done, size_t n) {
-  constexpr bool kSecp = __is_same(typename C::pt, secp::pt);
   constexpr bool kEd = __is_same(typename C::pt, ed::pt);
-  __shared__ __attribute__((aligned(16))) u32 sh[kSecp ? secp::coop::WORDS : (kEd ? ed::coop::WORDS : p256::coop::WORDS)];
-  const u32* terms = blockIdx.x == 0 ? terms_a : terms_b;
-  typename C::pt acc;  // the whole wavefront folds: each addition on four (secp256k1, Ed25519) / five (P-256) lanes
-  if constexpr (kSecp) acc = fold_coop_secp(terms, n, sh);
-  else if constexpr (kEd) acc = fold_coop_ed(terms, n, sh);
-  else acc = fold_coop_p256(terms, n, sh);
+  __shared__ __attribute__((aligned(16))) u32 sh[C::COOP_WORDS];
+  // the whole wavefront folds: each addition on four (secp256k1, Ed25519) / five (P-256) lanes
+  const typename C::pt acc = fold_coop<C>(blockIdx.x == 0 ? terms_a : terms_b, n, sh);
   if (threadIdx.x != 0) return;
-  C::store(sums + blockIdx.x * C::PW, 1, acc);
+  store_pt(sums + blockIdx.x * C::PW, 1, acc);
   __threadfence();
   if (atomicAdd(done, 1u) != 1u) return;  // the other fold is still running: it will finish the job
   __threadfence();
@@ -444,7 +351,7 @@ __global__ __launch_bounds__(64) void k_schnorr_fold_compare(const u32* __restri
   bool panics = false;
 #pragma unroll 1
   for (int k = 0; k < 2; ++k) {
-    typename C::pt p = C::load(sums + k * C::PW, 1);
+    typename C::pt p = load_pt<typename C::pt>(sums + k * C::PW, 1);
     fe xx, yy;
     if constexpr (kEd) {   // to_affine (1793-1811) unwraps z.invert(): a zero z of a point that is not the identity panics (1805)
       if (!lane_of(ed::is_identity(p)) && lane_of(fe_is_zero(p.z))) panics = true;
@@ -527,9 +434,9 @@ __global__ __launch_bounds__(TPB) void k_p256_prefix_level(const u32* __restrict
                                                            const u32* __restrict__ base, size_t n) {
   const size_t g = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (g >= n) return;
-  p256::pt r = p256::pdouble(P256::load(parent + (g >> 1) * 24, 1));
-  if (g & 1) r = p256::padd(r, P256::load(base, 1));
-  P256::store(child + g * 24, 1, r);
+  p256::pt r = p256::pdouble(load_pt<p256::pt>(parent + (g >> 1) * 24, 1));
+  if (g & 1) r = p256::padd(r, load_pt<p256::pt>(base, 1));
+  store_pt(child + g * 24, 1, r);
 }
 // level 0 / entry 0: the multiplication's initial state -- secp256k1 (identity, base) with identity = (0, one(), 0), one()
 // = raw 1 (secp256k1.rs:1322, 585); P-256 the identity (0, 1, 0) (p256.rs:1827); Ed25519 the identity (0, 1, 1, 0)
@@ -550,7 +457,7 @@ __global__ __launch_bounds__(TPB) void k_ed_prefix_level(const u32* __restrict__
                                                          const u32* __restrict__ addend, size_t n) {
   const size_t g = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (g >= n) return;
-  Ed::store(upper + g * 32, 1, ed::padd(Ed::load(lower + g * 32, 1), Ed::load(addend, 1)));
+  store_pt(upper + g * 32, 1, ed::padd(load_pt<ed::pt>(lower + g * 32, 1), load_pt<ed::pt>(addend, 1)));
 }
 
 }  // namespace fecgpu

@@ -1,4 +1,5 @@
-// kernels.hpp -- launchers of kernels that live in their own translation units (compiled in parallel).
+// kernels.hpp -- launchers of kernels that live in their own translation units (compiled in parallel), and the host-side
+// launch-shape rules the persistent scheduler launchers share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,6 +27,40 @@ struct SchedEnv {
   unsigned gen_prefix_bits[3] = {0, 0, 0};
 };
 enum : unsigned { FEC_DEVERR_SCHED_WATCHDOG = 1u, FEC_DEVERR_SCHED_INDEX = 2u, FEC_DEVERR_FORCED = 4u };
+
+// The launch shape of a persistent scheduler kernel: one workgroup per CU the launch may take (env.cus, or every
+// cu_divisor-th of them), each with a contiguous range of `per_wg` elements, at least 64.
+struct SchedGrid {
+  unsigned grid, per_wg;
+};
+inline SchedGrid sched_grid(const SchedEnv& env, size_t n, unsigned cu_divisor = 1) {
+  const unsigned cus = env.cus ? env.cus : 256u;
+  const unsigned cap = cu_divisor > 1 && cus >= cu_divisor ? cus / cu_divisor : cus;
+  size_t grid = (n + 63) / 64;
+  if (grid > cap) grid = cap;
+  const unsigned per_wg = (unsigned)((n + grid - 1) / grid);
+  return {(unsigned)((n + per_wg - 1) / per_wg), per_wg};
+}
+// Which instantiation a launch whose workgroups own `per_wg` elements each takes: the one with `wide` slots when those
+// elements are a little more than a whole number of `main`-element fills and a (near) whole number of `wide`-element
+// ones -- a fill of leftovers starts late and runs thinly occupied -- and only up to three fills (beyond that the refills
+// overlap and the leaner LDS image with the scalar in it wins: P-256 23.9 against 24.3 ms at 2^20).
+inline bool wide_slots_pay(unsigned per_wg, unsigned main, unsigned wide) {
+  if (per_wg <= main || per_wg > 3u * wide) return false;
+  auto waste = [per_wg](unsigned q) { return (double)(((per_wg + q - 1) / q) * q) / (double)per_wg; };
+  return waste(wide) + 0.04 < waste(main);
+}
+// The fixed-base prefix table a launch with base `base` starts from: the ctx's, when it has one for `curve` and `base`
+// IS the ctx's generator; else {null, 0}.
+struct GenPrefix {
+  const u32* prefix;
+  int wbits;
+};
+inline GenPrefix gen_prefix_for(const SchedEnv& env, int curve, const u32* base) {
+  if (base == env.gen[curve] && env.gen_prefix[curve] != nullptr && env.gen_prefix_bits[curve] > 0)
+    return {env.gen_prefix[curve], (int)env.gen_prefix_bits[curve]};
+  return {nullptr, 0};
+}
 
 // kernels_p256.hip: P-256 Curve::multiply, workgroup task scheduler.  out[i] = multiply(fixed ? points[0] : points[i], scalars[i])
 // One persistent workgroup per CU the launch may take: env.cus (two launches that run side by side get a SchedEnv each,

@@ -26,18 +26,6 @@ namespace {
 
 enum : unsigned char { F_GO = 0, F_FALSE = 1, F_PANIC = 2 };
 
-FEC_DEV fe load8(const u32* g) {
-  const uint4 a = *reinterpret_cast<const uint4*>(g), b = *reinterpret_cast<const uint4*>(g + 4);
-  fe r;
-  r.w[0] = a.x; r.w[1] = a.y; r.w[2] = a.z; r.w[3] = a.w;
-  r.w[4] = b.x; r.w[5] = b.y; r.w[6] = b.z; r.w[7] = b.w;
-  return r;
-}
-FEC_DEV void store8(u32* g, const fe& v) {
-  *reinterpret_cast<uint4*>(g) = make_uint4(v.w[0], v.w[1], v.w[2], v.w[3]);
-  *reinterpret_cast<uint4*>(g + 4) = make_uint4(v.w[4], v.w[5], v.w[6], v.w[7]);
-}
-
 // secp256k1: scalar field secp256k1.rs:1953-1969, 2162-2195, 2270-2297, 2410-2456 (its N has the two top
 // limbs swapped and its Mul keeps only the low 256 bits of the product); ct_lt overridden with a true
 // comparison against that N
@@ -173,27 +161,27 @@ __global__ __launch_bounds__(TPB) void k_ecdsa_pre(const unsigned char* __restri
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   // Scalar::from_bytes: big-endian bytes -> little-endian limbs
-  const fe d = load8(reinterpret_cast<const u32*>(digests + i * 32));
+  const fe d = load_fe16(reinterpret_cast<const u32*>(digests + i * 32));
   fe h;
   FEC_UNROLL for (int w = 0; w < 8; ++w) h.w[w] = __builtin_bswap32(d.w[7 - w]);
-  const fe r = load8(rs + i * 8), s = load8(ss + i * 8);
+  const fe r = load_fe16(rs + i * 8), s = load_fe16(ss + i * 8);
   fe a, b;
   flags[i] = E::scalars(h, r, s, a, b);
   if (weights != nullptr) {  // batch_verify (ecdsa.rs:349-350, 370): a_i * u1, a_i * u2, a_i * r_i
-    const fe w = load8(weights + i * 8);
+    const fe w = load_fe16(weights + i * 8);
     a = E::wmul(w, a);
     b = E::wmul(w, b);
-    store8(ar + i * 8, E::wmul(w, r));
+    store_fe16(ar + i * 8, E::wmul(w, r));
   }
-  store8(u1 + i * 8, a);
-  store8(u2 + i * 8, b);
+  store_fe16(u1 + i * 8, a);
+  store_fe16(u2 + i * 8, b);
   // from_affine (secp256k1.rs:1365-1373, p256.rs:1859-1867): (x, y, 1), or the identity (0, 1, 0)
   const bool inf = pk_inf != nullptr && pk_inf[i] != 0;
-  fe x = load8(pk + i * 16), y = load8(pk + i * 16 + 8), z = fe_small(1);
+  fe x = load_fe16(pk + i * 16), y = load_fe16(pk + i * 16 + 8), z = fe_small(1);
   if (inf) { x = fe_zero(); y = fe_small(1); z = fe_zero(); }
-  store8(q + i * 24, x);
-  store8(q + i * 24 + 8, y);
-  store8(q + i * 24 + 16, z);
+  store_fe16(q + i * 24, x);
+  store_fe16(q + i * 24 + 8, y);
+  store_fe16(q + i * 24 + 16, z);
 }
 
 template <class E>
@@ -202,10 +190,8 @@ __global__ __launch_bounds__(TPB) void k_ecdsa_finish(const u32* __restrict__ ta
                                                       unsigned char* __restrict__ status, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  typename E::pt a, b;
-  a.x = load8(ta + i * 24); a.y = load8(ta + i * 24 + 8); a.z = load8(ta + i * 24 + 16);
-  b.x = load8(tb + i * 24); b.y = load8(tb + i * 24 + 8); b.z = load8(tb + i * 24 + 16);
-  const unsigned char st = E::finish(a, b, load8(rs + i * 8));
+  const typename E::pt a = load_pt16<typename E::pt>(ta + i * 24), b = load_pt16<typename E::pt>(tb + i * 24);
+  const unsigned char st = E::finish(a, b, load_fe16(rs + i * 8));
   const unsigned char f = flags[i];
   status[i] = f == F_FALSE ? 0 : (f == F_PANIC ? 2 : st);
 }
@@ -224,7 +210,7 @@ __global__ __launch_bounds__(64) void k_ecdsa_batch_finish(const u32* __restrict
   for (size_t base = 0; base < n; base += 64) {
     const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
     if (lane < cnt) {
-      const fe t = load8(ar + (base + lane) * 8);
+      const fe t = load_fe16(ar + (base + lane) * 8);
       FEC_UNROLL for (int w = 0; w < 8; ++w) sh[lane * 8 + w] = t.w[w];
     }
     __syncthreads();
@@ -239,11 +225,10 @@ __global__ __launch_bounds__(64) void k_ecdsa_batch_finish(const u32* __restrict
     __syncthreads();
   }
   if (lane != 0) return;
-  typename E::pt p;
-  p.x = load8(r_sum); p.y = load8(r_sum + 8); p.z = load8(r_sum + 16);
+  const typename E::pt p = load_pt16<typename E::pt>(r_sum);
   result[0] = E::compare_x(p, total);
-  store8(detail, p.x); store8(detail + 8, p.y); store8(detail + 16, p.z);
-  store8(detail + 24, total);
+  store_pt16(detail, p);
+  store_fe16(detail + 24, total);
 }
 
 // ---- Ecdsa::<C, D>::sign (ecdsa.rs:98-211) after the hash and the nonce, from R = multiply(G, k) on ----
@@ -259,16 +244,16 @@ __global__ __launch_bounds__(TPB) void k_ecdsa_sign_finish(const u32* __restrict
                                                            unsigned char* __restrict__ status, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  const fe sk = load8(sks + i * 8), k = load8(ks + i * 8);
+  const fe sk = load_fe16(sks + i * 8), k = load_fe16(ks + i * 8);
   const bool bad_sk = E::sk_bad(sk);                                                      // 101-104
-  const fe z = load8(rp + i * 24 + 16);
+  const fe z = load_fe16(rp + i * 24 + 16);
   const bool ident = lane_of(fe_is_zero(z));                                              // is_identity
   fe zi, k_inv;
   E::inv_pair(z, k, zi, k_inv);                                                           // 111, 157
-  const fe r = E::x_value(E::affine_x(load8(rp + i * 24), zi, ident));                    // 111-121: x.to_bytes()
+  const fe r = E::x_value(E::affine_x(load_fe16(rp + i * 24), zi, ident));                    // 111-121: x.to_bytes()
   const bool bad_r = E::sc_invalid(r);                                                    // 122-129
   const bool zero_r = lane_of(fe_is_zero(r));                                             // 131-134
-  const fe d = load8(reinterpret_cast<const u32*>(digests + i * 32));
+  const fe d = load_fe16(reinterpret_cast<const u32*>(digests + i * 32));
   fe h;
   FEC_UNROLL for (int w = 0; w < 8; ++w) h.w[w] = __builtin_bswap32(d.w[7 - w]);        // big-endian bytes
   const bool bad_h = E::sc_invalid(h);                                                    // 147-154
@@ -277,8 +262,8 @@ __global__ __launch_bounds__(TPB) void k_ecdsa_sign_finish(const u32* __restrict
   const bool zero_s = lane_of(fe_is_zero(s));                                             // 172-177
   if (!E::lt_half(s)) s = E::order_minus(s);                                              // normalize, 45-71
   const unsigned char st = bad_sk ? 1 : bad_r ? 2 : zero_r ? 3 : bad_h ? 2 : (zero_k || zero_s) ? 3 : 0;
-  store8(sig + i * 16, st == 0 ? r : fe_small(1));
-  store8(sig + i * 16 + 8, st == 0 ? s : fe_small(1));
+  store_fe16(sig + i * 16, st == 0 ? r : fe_small(1));
+  store_fe16(sig + i * 16 + 8, st == 0 ? s : fe_small(1));
   status[i] = st;
 }
 
@@ -291,27 +276,26 @@ __global__ __launch_bounds__(TPB) void k_ecdh_pre(const u32* __restrict__ pk, co
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   const bool inf = pk_inf != nullptr && pk_inf[i] != 0;
-  fe x = load8(pk + i * 16), y = load8(pk + i * 16 + 8), z = fe_small(1);
+  fe x = load_fe16(pk + i * 16), y = load_fe16(pk + i * 16 + 8), z = fe_small(1);
   flags[i] = E::pk_valid(x, y, inf) ? 0 : 1;
   if (inf) { x = fe_zero(); y = fe_small(1); z = fe_zero(); }   // from_affine of the identity: (0, 1, 0)
-  store8(q + i * 24, x);
-  store8(q + i * 24 + 8, y);
-  store8(q + i * 24 + 16, z);
+  store_fe16(q + i * 24, x);
+  store_fe16(q + i * 24 + 8, y);
+  store_fe16(q + i * 24 + 16, z);
 }
 template <class E>
 __global__ __launch_bounds__(TPB) void k_ecdh_finish(const u32* __restrict__ t, const unsigned char* __restrict__ flags,
                                                      u32* __restrict__ out, unsigned char* __restrict__ status, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  typename E::pt p;
-  p.x = load8(t + i * 24); p.y = load8(t + i * 24 + 8); p.z = load8(t + i * 24 + 16);
+  const typename E::pt p = load_pt16<typename E::pt>(t + i * 24);
   fe x, y;
   const bool ident = lane_of(E::to_affine(p, x, y));
   const fe v = E::x_value(x);
   const unsigned char st = flags[i] != 0 ? 1 : (ident ? 2 : 0);
   fe o;  // big-endian bytes of the value, as eight words in memory order; zero unless Ok
   FEC_UNROLL for (int w = 0; w < 8; ++w) o.w[w] = st == 0 ? __builtin_bswap32(v.w[7 - w]) : 0u;
-  store8(out + i * 8, o);
+  store_fe16(out + i * 8, o);
   status[i] = st;
 }
 using MulLauncher = void (*)(const SchedEnv&, bool, const u32*, const u32*, u32*, size_t, hipStream_t);
@@ -336,7 +320,7 @@ __global__ __launch_bounds__(TPB) void k_validate_weierstrass(const u32* __restr
                                                               unsigned char* __restrict__ ok, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  const fe x = load8(xy + i * 16), y = load8(xy + i * 16 + 8);
+  const fe x = load_fe16(xy + i * 16), y = load_fe16(xy + i * 16 + 8);
   const bool on = CURVE == FEC_SECP256K1 ? lane_of(secp::affine_on_curve(x, y)) : lane_of(fe_eq(p256::sqr(y), p256::curve_rhs(x)));
   ok[i] = ((inf != nullptr && inf[i] != 0) || on) ? 1 : 0;
 }
@@ -355,26 +339,19 @@ __global__ __launch_bounds__(TPB) void k_ed_validate_finish(const u32* __restric
                                                             unsigned char* __restrict__ ok, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  ed::pt p;
-  p.x = load8(t + i * 32); p.y = load8(t + i * 32 + 8); p.z = load8(t + i * 32 + 16); p.t = load8(t + i * 32 + 24);
+  const ed::pt p = load_pt16<ed::pt>(t + i * 32);
   ok[i] = (flags[i] != 0 && lane_of(ed::is_identity(p))) ? 1 : 0;
 }
 
 // ---- Eddsa::<Ed25519, D>::verify / Ed25519::verify from the point computation on (eddsa.rs:174-211, 430-447) ----
-FEC_DEV ed::pt ed_load32(const u32* g) {
-  ed::pt p;
-  p.x = load8(g); p.y = load8(g + 8); p.z = load8(g + 16); p.t = load8(g + 24);
-  return p;
-}
-
 // A = from_affine(pk) as the base of multiply(A, k)
 __global__ __launch_bounds__(TPB) void k_eddsa_pre(const u32* __restrict__ pk, const unsigned char* __restrict__ pk_inf,
                                                    u32* __restrict__ a, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   const bool inf = pk_inf != nullptr && pk_inf[i] != 0;
-  const ed::pt p = ed_from_affine(load8(pk + i * 16), load8(pk + i * 16 + 8), inf);
-  store8(a + i * 32, p.x); store8(a + i * 32 + 8, p.y); store8(a + i * 32 + 16, p.z); store8(a + i * 32 + 24, p.t);
+  const ed::pt p = ed_from_affine(load_fe16(pk + i * 16), load_fe16(pk + i * 16 + 8), inf);
+  store_pt16(a + i * 32, p);
 }
 
 // PointAffine::is_on_curve (ed25519.rs:1719-1744) / PointAffine::new (1476-1498): -x^2 + y^2 == 1 + d x^2 y^2
@@ -389,10 +366,10 @@ __global__ __launch_bounds__(TPB) void k_ed_validate_pre(const u32* __restrict__
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   const bool is_inf = inf != nullptr && inf[i] != 0;
-  const fe x = load8(xy + i * 16), y = load8(xy + i * 16 + 8);
+  const fe x = load_fe16(xy + i * 16), y = load_fe16(xy + i * 16 + 8);
   flags[i] = (is_inf || lane_of(ed_affine_on_curve(x, y))) ? 1 : 0;
   const ed::pt p = ed_from_affine(x, y, is_inf);
-  store8(a + i * 32, p.x); store8(a + i * 32 + 8, p.y); store8(a + i * 32 + 16, p.z); store8(a + i * 32 + 24, p.t);
+  store_pt16(a + i * 32, p);
 }
 
 // sg = multiply(G, s), ka = multiply(A, k): R + ka, both to_affine, from_affine(..) - from_affine(..), is_identity
@@ -401,8 +378,8 @@ __global__ __launch_bounds__(TPB) void k_eddsa_finish(const u32* __restrict__ sg
                                                       unsigned char* __restrict__ status, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  const ed::pt s_g = ed_load32(sg + i * 32), k_a = ed_load32(ka + i * 32);
-  const unsigned char v = eddsa_verify_tail(s_g, k_a, load8(r_xy + i * 16), load8(r_xy + i * 16 + 8));   // eddsa_verify.hpp
+  const ed::pt s_g = load_pt16<ed::pt>(sg + i * 32), k_a = load_pt16<ed::pt>(ka + i * 32);
+  const unsigned char v = eddsa_verify_tail(s_g, k_a, load_fe16(r_xy + i * 16), load_fe16(r_xy + i * 16 + 8));   // eddsa_verify.hpp
   const bool rinf = r_inf != nullptr && r_inf[i] != 0;                                     // 174-177
   status[i] = rinf ? 0 : v;
 }
@@ -419,8 +396,6 @@ struct VSecp {
     pt p; p.x = x; p.y = y; p.z = fe_small(1);
     return inf ? secp::identity() : p;
   }
-  FEC_DEV static pt load(const u32* g) { pt p; p.x = load8(g); p.y = load8(g + 8); p.z = load8(g + 16); return p; }
-  FEC_DEV static void store(u32* g, const pt& p) { store8(g, p.x); store8(g + 8, p.y); store8(g + 16, p.z); }
   FEC_DEV static fe neg(const fe& a) { return secp::neg(a); }
   FEC_DEV static bool on_curve(const fe& x, const fe& y) { return lane_of(secp::affine_on_curve(x, y)); }
   FEC_DEV static pt padd(const pt& a, const pt& b) { return secp::padd(a, b); }
@@ -434,8 +409,6 @@ struct VP256 {
     pt p; p.x = x; p.y = y; p.z = fe_small(1);
     return inf ? p256::identity() : p;
   }
-  FEC_DEV static pt load(const u32* g) { pt p; p.x = load8(g); p.y = load8(g + 8); p.z = load8(g + 16); return p; }
-  FEC_DEV static void store(u32* g, const pt& p) { store8(g, p.x); store8(g + 8, p.y); store8(g + 16, p.z); }
   FEC_DEV static fe neg(const fe& a) { return p256::neg(a); }
   FEC_DEV static bool on_curve(const fe& x, const fe& y) { return lane_of(fe_eq(p256::sqr(y), p256::curve_rhs(x))); }
   FEC_DEV static pt padd(const pt& a, const pt& b) { return p256::padd(a, b); }
@@ -446,8 +419,6 @@ struct VEd {
   typedef ed::pt pt;
   static constexpr int PW = 32;
   FEC_DEV static pt from_affine(const fe& x, const fe& y, bool inf) { return ed_from_affine(x, y, inf); }
-  FEC_DEV static pt load(const u32* g) { return ed_load32(g); }
-  FEC_DEV static void store(u32* g, const pt& p) { store8(g, p.x); store8(g + 8, p.y); store8(g + 16, p.z); store8(g + 24, p.t); }
   FEC_DEV static fe neg(const fe& a) { return ed::neg(a); }
   FEC_DEV static bool on_curve(const fe& x, const fe& y) { return lane_of(ed_affine_on_curve(x, y)); }
   FEC_DEV static pt padd(const pt& a, const pt& b) { return ed::padd(a, b); }
@@ -462,7 +433,7 @@ __global__ __launch_bounds__(TPB) void k_schnorr_verify_pre(const u32* __restric
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   const bool inf = pk_inf != nullptr && pk_inf[i] != 0;
-  V::store(a + i * V::PW, V::from_affine(load8(pk + i * 16), load8(pk + i * 16 + 8), inf));
+  store_pt16(a + i * V::PW, V::from_affine(load_fe16(pk + i * 16), load_fe16(pk + i * 16 + 8), inf));
 }
 template <class V>
 __global__ __launch_bounds__(TPB) void k_schnorr_verify_finish(const u32* __restrict__ sg, const u32* __restrict__ ep,
@@ -471,7 +442,7 @@ __global__ __launch_bounds__(TPB) void k_schnorr_verify_finish(const u32* __rest
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   const bool rinf = r_inf != nullptr && r_inf[i] != 0;                                     // 103-105
-  const typename V::pt s_g = V::load(sg + i * V::PW), e_p = V::load(ep + i * V::PW);
+  const typename V::pt s_g = load_pt16<typename V::pt>(sg + i * V::PW), e_p = load_pt16<typename V::pt>(ep + i * V::PW);
   bool panic = V::panics(e_p);
   fe x, y;
   (void)V::to_affine(e_p, x, y);                                                           // 129: (0, 0) for the identity
@@ -481,7 +452,7 @@ __global__ __launch_bounds__(TPB) void k_schnorr_verify_finish(const u32* __rest
   panic = panic || (some && V::panics(rp));
   fe rx, ry;
   const bool ri = lane_of(V::to_affine(rp, rx, ry));                                       // 139
-  const bool same = lane_of(fe_eq(rx, load8(r_xy + i * 16)) & fe_eq(ry, load8(r_xy + i * 16 + 8)));
+  const bool same = lane_of(fe_eq(rx, load_fe16(r_xy + i * 16)) & fe_eq(ry, load_fe16(r_xy + i * 16 + 8)));
   (void)ri;                                                                                // (inf & inf): sig.r is finite here
   status[i] = rinf ? 0 : (V::panics(e_p) ? 2 : (!some ? 0 : (panic ? 2 : (same ? 1 : 0))));
 }

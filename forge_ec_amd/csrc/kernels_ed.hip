@@ -23,73 +23,19 @@ namespace fecgpu {
 
 namespace {
 
-
-FEC_DEV ed::pt ld_lds(const u32* l, int stride) {
-  ed::pt p;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) {
-    p.x.w[i] = l[i * stride];
-    p.y.w[i] = l[(8 + i) * stride];
-    p.z.w[i] = l[(16 + i) * stride];
-    p.t.w[i] = l[(24 + i) * stride];
-  }
-  return p;
-}
-FEC_DEV void st_lds(u32* l, int stride, const ed::pt& p) {
-  FEC_UNROLL for (int i = 0; i < 8; ++i) {
-    l[i * stride] = p.x.w[i];
-    l[(8 + i) * stride] = p.y.w[i];
-    l[(16 + i) * stride] = p.z.w[i];
-    l[(24 + i) * stride] = p.t.w[i];
-  }
-}
-FEC_DEV ed::pt ld_glb(const u32* g) {  // 32 consecutive words, 16-byte loads
-  const uint4* src = reinterpret_cast<const uint4*>(g);
-  uint4 v[8];
-  FEC_UNROLL for (int i = 0; i < 8; ++i) v[i] = src[i];
-  ed::pt p;
-  FEC_UNROLL for (int i = 0; i < 2; ++i) {
-    p.x.w[4 * i] = v[i].x; p.x.w[4 * i + 1] = v[i].y; p.x.w[4 * i + 2] = v[i].z; p.x.w[4 * i + 3] = v[i].w;
-    p.y.w[4 * i] = v[2 + i].x; p.y.w[4 * i + 1] = v[2 + i].y; p.y.w[4 * i + 2] = v[2 + i].z; p.y.w[4 * i + 3] = v[2 + i].w;
-    p.z.w[4 * i] = v[4 + i].x; p.z.w[4 * i + 1] = v[4 + i].y; p.z.w[4 * i + 2] = v[4 + i].z; p.z.w[4 * i + 3] = v[4 + i].w;
-    p.t.w[4 * i] = v[6 + i].x; p.t.w[4 * i + 1] = v[6 + i].y; p.t.w[4 * i + 2] = v[6 + i].z; p.t.w[4 * i + 3] = v[6 + i].w;
-  }
-  return p;
-}
-FEC_DEV void st_glb(u32* g, const ed::pt& p) {
-  uint4* dst = reinterpret_cast<uint4*>(g);
-  FEC_UNROLL for (int i = 0; i < 2; ++i) {
-    dst[i] = make_uint4(p.x.w[4 * i], p.x.w[4 * i + 1], p.x.w[4 * i + 2], p.x.w[4 * i + 3]);
-    dst[2 + i] = make_uint4(p.y.w[4 * i], p.y.w[4 * i + 1], p.y.w[4 * i + 2], p.y.w[4 * i + 3]);
-    dst[4 + i] = make_uint4(p.z.w[4 * i], p.z.w[4 * i + 1], p.z.w[4 * i + 2], p.z.w[4 * i + 3]);
-    dst[6 + i] = make_uint4(p.t.w[4 * i], p.t.w[4 * i + 1], p.t.w[4 * i + 2], p.t.w[4 * i + 3]);
-  }
-}
-
 // bit i of scalar.to_raw() of element g (2075-2079: limb i / 64, bit i % 64)
 FEC_DEV u32 scalar_bit(const u32* scalars, size_t g, int i) { return (scalars[g * 8 + (i >> 5)] >> (i & 31)) & 1u; }
 
-}  // namespace
-
-namespace {
-// a point as 32 consecutive words (x, y, z, t), word loads (any alignment the callers use)
-FEC_DEV ed::pt ld_words(const u32* g) {
-  ed::pt p;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) { p.x.w[i] = g[i]; p.y.w[i] = g[8 + i]; p.z.w[i] = g[16 + i]; p.t.w[i] = g[24 + i]; }
-  return p;
-}
-FEC_DEV void st_words(u32* g, const ed::pt& p) {
-  FEC_UNROLL for (int i = 0; i < 8; ++i) { g[i] = p.x.w[i]; g[8 + i] = p.y.w[i]; g[16 + i] = p.z.w[i]; g[24 + i] = p.t.w[i]; }
-}
 }  // namespace
 
 // table[j] = 2^j * base by the reference's own doubling chain (ed25519.rs:2089): one lane, 255
 // sequential additions; 32 words per entry, dense.  Runs once per base point.
 __global__ __launch_bounds__(64) void k_ed_build_table(const u32* __restrict__ base, u32* __restrict__ table) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  ed::pt a = ld_words(base);
+  ed::pt a = load_pt<ed::pt>(base, 1);
 #pragma unroll 1
   for (int j = 0; j < 256; ++j) {
-    st_words(table + j * 32, a);
+    store_pt(table + j * 32, 1, a);
     a = ed::padd(a, a);
   }
 }
@@ -102,20 +48,29 @@ __global__ __launch_bounds__(64) void k_ed_build_table(const u32* __restrict__ b
 // lane taking one must pass -- is_identity needs x == 0, the negation test needs p.y == q.y -- and evaluate the exact
 // masks on the plain entry (x, y, z, t: `g`, the table in global memory) inside the rare branch.
 constexpr int FT_STRIDE = 35;   // odd: lanes reading different entries spread over the LDS banks
-FEC_DEV fe ld_tab(const u32* e, int c) {
-  fe a;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) a.w[i] = e[8 * c + i];
-  return a;
+// entry e of the 32 KiB table (L2-resident) into its LDS form: y - x, y + x, z, t, x.w[0], y.w[0]
+FEC_DEV void stage_table_entry(u32* lds_t, const u32* table, int e) {
+  const ed::pt q = load_pt<ed::pt>(table + (size_t)e * 32, 1);
+  const fe ymx = ed::sub(q.y, q.x), ypx = ed::add(q.y, q.x);
+  u32* d = lds_t + e * FT_STRIDE;
+  FEC_UNROLL for (int i = 0; i < 8; ++i) {
+    d[i] = ymx.w[i];
+    d[8 + i] = ypx.w[i];
+    d[16 + i] = q.z.w[i];
+    d[24 + i] = q.t.w[i];
+  }
+  d[32] = q.x.w[0];
+  d[33] = q.y.w[0];
 }
 FEC_DEV ed::pt padd_table(const ed::pt& p, const u32* e, const u32* g) {
   using namespace ed;
   const lmask maybe = lanes_where(p.x.w[0] == 0u || e[32] == 0u || p.y.w[0] == e[33]);
   fe a, b, d;
-  d = mul(p.z, ld_tab(e, 2));
-  a = mul(sub(p.y, p.x), ld_tab(e, 0));
-  b = mul(add(p.y, p.x), ld_tab(e, 1));
+  d = mul(p.z, load_coord(e, 1, 2));
+  a = mul(sub(p.y, p.x), load_coord(e, 1, 0));
+  b = mul(add(p.y, p.x), load_coord(e, 1, 1));
   __builtin_amdgcn_sched_barrier(0);  // keep the load of q.t below the first three products (register budget)
-  fe c = mul(mul(p.t, ld_tab(e, 3)), D_());
+  fe c = mul(mul(p.t, load_coord(e, 1, 3)), D_());
   __builtin_amdgcn_sched_barrier(0);
   const fe ee = sub(b, a), f = sub(d, c), gg = add(d, c), h = add(b, a);
   pt o;
@@ -124,7 +79,7 @@ FEC_DEV ed::pt padd_table(const ed::pt& p, const u32* e, const u32* g) {
   o.t = mul(ee, h);
   o.z = mul(f, gg);
   if (__builtin_expect(maybe != 0, 0)) {  // improbable: a lane's first addition is a copy (multiply_fixed_in_place)
-    const pt q = ld_words(g);
+    const pt q = load_pt<ed::pt>(g, 1);
     const lmask opposite = fe_eq(p.x, neg(q.x)) & fe_eq(p.y, q.y);  // 1878, raw coordinates
     const lmask idp = is_identity(p), idq = is_identity(q);
     o = pt_select(o, identity(), uniform_mask(opposite));
@@ -159,7 +114,7 @@ FEC_DEV ed::pt multiply_fixed_in_place(const ed::pt& base, const u32* tab, const
     }
     const bool have = cur != 0, pre = low != 0;
     const u32* src = pre ? prefix + (size_t)low * 32u : gtab + (have ? (u32)wi * 32u + (u32)__builtin_ctz(cur) : 0u) * 32u;
-    const pt q = ld_words(src);
+    const pt q = load_pt<ed::pt>(src, 1);
     if (!pre) cur &= cur - 1;  // (0 stays 0)
     result = pt_select(result, q, lanes_where(have || pre));
   }
@@ -204,19 +159,7 @@ __global__ __launch_bounds__(TPB, 3) void k_ed_fixed_base(const u32* __restrict_
   const int e = threadIdx.x;
   stage_in<8>(lds_k, scalars + first * 8, valid);
   static_assert(TPB == 256, "one thread stages one table entry");
-  {  // entry e of the 32 KiB table (L2-resident): y - x, y + x, z, t, x.w[0], y.w[0]
-    const ed::pt q = ld_words(table + (size_t)e * 32);
-    const fe ymx = ed::sub(q.y, q.x), ypx = ed::add(q.y, q.x);
-    u32* d = lds_t + e * FT_STRIDE;
-    FEC_UNROLL for (int i = 0; i < 8; ++i) {
-      d[i] = ymx.w[i];
-      d[8 + i] = ypx.w[i];
-      d[16 + i] = q.z.w[i];
-      d[24 + i] = q.t.w[i];
-    }
-    d[32] = q.x.w[0];
-    d[33] = q.y.w[0];
-  }
+  stage_table_entry(lds_t, table, e);
   for (int v = e; v < 260; v += TPB) lds_bin[v] = 0;
   __syncthreads();
   // ---- counting sort of the workgroup's elements by popcount ----
@@ -256,12 +199,12 @@ __global__ __launch_bounds__(TPB, 3) void k_ed_fixed_base(const u32* __restrict_
   const int src = lds_perm[slot];
   ed::pt r = ed::identity();
   if (src < valid) {
-    ed::pt b = ld_words(base);
+    ed::pt b = load_pt<ed::pt>(base, 1);
     r = multiply_fixed_in_place(b, lds_t, table, lds_k + src, prefix, wbits);
   }
   __syncthreads();                      // every lane has read its last table entry
   static_assert(256 * FT_STRIDE >= 32 * TPB, "the table region holds the staged results");
-  if (src < valid) st_lds(lds_t + src, TPB, r);
+  if (src < valid) store_pt(lds_t + src, TPB, r);
   __syncthreads();
   stage_out<32>(out + first * 32, lds_t, valid);
 }
@@ -370,23 +313,11 @@ __global__ __launch_bounds__(TPB, 3) void k_ed_fixed_sorted(const u32* __restric
     lds_k[4 * TPB + e] = b.x; lds_k[5 * TPB + e] = b.y; lds_k[6 * TPB + e] = b.z; lds_k[7 * TPB + e] = b.w;
   }
   static_assert(TPB == 256 && KSTRIDE == TPB, "one thread stages one table entry; scalar columns at stride TPB");
-  {  // entry e of the table: y - x, y + x, z, t, x.w[0], y.w[0] (see padd_table)
-    const ed::pt q = ld_words(table + (size_t)e * 32);
-    const fe ymx = ed::sub(q.y, q.x), ypx = ed::add(q.y, q.x);
-    u32* d = lds_t + e * FT_STRIDE;
-    FEC_UNROLL for (int i = 0; i < 8; ++i) {
-      d[i] = ymx.w[i];
-      d[8 + i] = ypx.w[i];
-      d[16 + i] = q.z.w[i];
-      d[24 + i] = q.t.w[i];
-    }
-    d[32] = q.x.w[0];
-    d[33] = q.y.w[0];
-  }
+  stage_table_entry(lds_t, table, e);
   __syncthreads();
   if (e < valid) {
-    const ed::pt b = ld_words(base);
-    st_glb(out + g * 32, multiply_fixed_in_place(b, lds_t, table, lds_k + e, prefix, wbits));
+    const ed::pt b = load_pt<ed::pt>(base, 1);
+    store_pt16(out + g * 32, multiply_fixed_in_place(b, lds_t, table, lds_k + e, prefix, wbits));
   }
 }
 
@@ -396,19 +327,6 @@ __global__ __launch_bounds__(TPB, 3) void k_ed_fixed_sorted(const u32* __restric
 // opposite points: improbable after an element's first addition) re-read both points inside their rare branch.
 // Same products, operands and order as ed::padd / ed::pdbl.
 namespace {
-FEC_DEV fe ld_gcoord(const u32* g, int c) {
-  const uint4* s4 = reinterpret_cast<const uint4*>(g + 8 * c);
-  const uint4 lo = s4[0], hi = s4[1];
-  fe a;
-  a.w[0] = lo.x; a.w[1] = lo.y; a.w[2] = lo.z; a.w[3] = lo.w;
-  a.w[4] = hi.x; a.w[5] = hi.y; a.w[6] = hi.z; a.w[7] = hi.w;
-  return a;
-}
-FEC_DEV fe ld_lcoord(const u32* l, int stride, int c) {
-  fe a;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) a.w[i] = l[(8 * c + i) * stride];
-  return a;
-}
 // result (global) + addend (LDS)
 FEC_DEV ed::pt padd_mem(const u32* gr, const u32* la, int stride) {
   using namespace ed;
@@ -417,9 +335,9 @@ FEC_DEV ed::pt padd_mem(const u32* gr, const u32* la, int stride) {
   lmask maybe;
   fe a, b, d;
   {
-    const fe px = ld_gcoord(gr, 0), py = ld_gcoord(gr, 1), qx = ld_lcoord(la, stride, 0), qy = ld_lcoord(la, stride, 1);
+    const fe px = load_coord16(gr, 0), py = load_coord16(gr, 1), qx = load_coord(la, stride, 0), qy = load_coord(la, stride, 1);
     {
-      const fe pz = ld_gcoord(gr, 2), qz = ld_lcoord(la, stride, 2);
+      const fe pz = load_coord16(gr, 2), qz = load_coord(la, stride, 2);
       d = mul(pz, qz);
     }
     maybe = lanes_where(px.w[0] == 0u || qx.w[0] == 0u || py.w[0] == qy.w[0]);
@@ -429,7 +347,7 @@ FEC_DEV ed::pt padd_mem(const u32* gr, const u32* la, int stride) {
   __builtin_amdgcn_sched_barrier(0);
   fe c;
   {
-    const fe pt_ = ld_gcoord(gr, 3), qt = ld_lcoord(la, stride, 3);
+    const fe pt_ = load_coord16(gr, 3), qt = load_coord(la, stride, 3);
     c = mul(mul(pt_, qt), D_());
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -441,8 +359,8 @@ FEC_DEV ed::pt padd_mem(const u32* gr, const u32* la, int stride) {
   o.z = mul(f, g);
   if (__builtin_expect(maybe != 0, 0)) {  // an element's first addition (result = identity); improbable afterwards
     pt p, q;
-    p.x = ld_gcoord(gr, 0); p.y = ld_gcoord(gr, 1); p.z = ld_gcoord(gr, 2); p.t = ld_gcoord(gr, 3);
-    q.x = ld_lcoord(la, stride, 0); q.y = ld_lcoord(la, stride, 1); q.z = ld_lcoord(la, stride, 2); q.t = ld_lcoord(la, stride, 3);
+    p.x = load_coord16(gr, 0); p.y = load_coord16(gr, 1); p.z = load_coord16(gr, 2); p.t = load_coord16(gr, 3);
+    q.x = load_coord(la, stride, 0); q.y = load_coord(la, stride, 1); q.z = load_coord(la, stride, 2); q.t = load_coord(la, stride, 3);
     const lmask opposite = fe_eq(p.x, neg(q.x)) & fe_eq(p.y, q.y);  // 1878, raw coordinates
     const lmask idp = is_identity(p), idq = is_identity(q);       // 1785-1791
     o = pt_select(o, identity(), uniform_mask(opposite));
@@ -459,9 +377,9 @@ FEC_DEV ed::pt pdbl_mem(const u32* la, int stride) {
   lmask maybe;
   fe a, b, d;
   {
-    const fe x = ld_lcoord(la, stride, 0), y = ld_lcoord(la, stride, 1);
+    const fe x = load_coord(la, stride, 0), y = load_coord(la, stride, 1);
     {
-      const fe z = ld_lcoord(la, stride, 2);
+      const fe z = load_coord(la, stride, 2);
       d = sqr_exact(z);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -472,7 +390,7 @@ FEC_DEV ed::pt pdbl_mem(const u32* la, int stride) {
   __builtin_amdgcn_sched_barrier(0);
   fe c;
   {
-    const fe t = ld_lcoord(la, stride, 3);
+    const fe t = load_coord(la, stride, 3);
     c = mul(sqr_exact(t), D_());
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -484,7 +402,7 @@ FEC_DEV ed::pt pdbl_mem(const u32* la, int stride) {
   o.z = mul(f, g);
   if (__builtin_expect(maybe != 0, 0)) {
     pt p;
-    p.x = ld_lcoord(la, stride, 0); p.y = ld_lcoord(la, stride, 1); p.z = ld_lcoord(la, stride, 2); p.t = ld_lcoord(la, stride, 3);
+    p.x = load_coord(la, stride, 0); p.y = load_coord(la, stride, 1); p.z = load_coord(la, stride, 2); p.t = load_coord(la, stride, 3);
     const lmask opposite = fe_eq(p.x, neg(p.x));                 // Add's test with q = p: x == -x
     const lmask idp = is_identity(p);
     o = pt_select(o, identity(), uniform_mask(opposite));
@@ -514,7 +432,7 @@ constexpr int PS_MAIN = FEC_ED_PS;  // element slots per workgroup (12 x 64 in f
                                     // 800 -> 18.09 ms, 832 -> 17.89, 864 -> 17.20, 880 -> 16.95 / 17.46 on two boxes, 896 -> 17.49.  Round 3's sweeps with the lock (profiles/slot_sweep_r03.txt), ms and
                                     // L2-side traffic per 2^20: 1024 -> 17.87 / 27.0 GB, 960 -> 19.05, 896 -> 18.43, 864 -> 18.10, 832 -> 17.75 / 18.4 GB, 800 -> 19.95, 768 -> 19.02
 // The second instantiation, 1 024 slots: for launches whose workgroups get a little more than a whole number of
-// PS_MAIN-element fills (2^18 elements: 1 024 per workgroup, 6.6 ms against 5.0) -- see kernels_p256.hip: wide_slots_pay.
+// PS_MAIN-element fills (2^18 elements: 1 024 per workgroup, 6.6 ms against 5.0) -- see kernels.hpp: wide_slots_pay.
 constexpr int PS_WIDE = 1024;
 }  // namespace
 
@@ -551,16 +469,16 @@ __global__ __launch_bounds__(PT, 1) void k_ed_mul_pers(const u32* __restrict__ s
       const int rel = lds_fetch_add(ctl, LF_NEXT, 1);
       if (rel >= range) return LF_NXT_DEAD;
       const size_t g = lo + rel;
-      const ed::pt base = ld_glb(points + g * 32);
+      const ed::pt base = load_pt16<ed::pt>(points + g * 32);
       u32 any = 0;
       FEC_UNROLL for (int w = 0; w < 8; ++w) any |= scalars[g * 8 + w];
       if (any == 0 || lane_of(ed::is_identity(base))) {
-        st_glb(out + g * 32, ed::identity());
+        store_pt16(out + g * 32, ed::identity());
         continue;
       }
-      st_lds(lds_ad + e, PS, base);
+      store_pt(lds_ad + e, PS, base);
       lds_gid[e] = (u32)rel;
-      st_glb(out + g * 32, ed::identity());
+      store_pt16(out + g * 32, ed::identity());
       lds_step[e] = 0;
       return (scalars[g * 8] & 1u) ? LF_NXT_A : LF_NXT_D;
     }
@@ -610,7 +528,7 @@ __global__ __launch_bounds__(PT, 1) void k_ed_mul_pers(const u32* __restrict__ s
       FEC_MARK("task_add_begin");
       const ed::pt res = padd_mem(slot, lds_ad + e, PS);
       FEC_MARK("task_add_end");
-      if (live) st_glb(slot, res);
+      if (live) store_pt16(slot, res);
     }
     {
       FEC_MARK("task_double_begin");
@@ -620,7 +538,7 @@ __global__ __launch_bounds__(PT, 1) void k_ed_mul_pers(const u32* __restrict__ s
         if (step == 255) {  // (only reached through ring A: A_255 was the element's last operation)
           fin = true;
         } else {
-          st_lds(lds_ad + e, PS, d);
+          store_pt(lds_ad + e, PS, d);
           ++step;
           const u32 bit = scalar_bit(scalars, lo + gid, step);
           lds_step[e] = (unsigned short)step;
@@ -644,7 +562,7 @@ __global__ __launch_bounds__(PT, 1) void k_ed_mul_pers(const u32* __restrict__ s
     // FEC_E_LAUNCH (fecgpu.hip: sync_and_check, fec_ctx_check) instead of FEC_OK with plausible-looking points.
     ed::pt z;
     z.x = z.y = z.z = z.t = fe_zero();
-    for (int el = tid; el < range; el += PT) st_glb(out + (lo + el) * 32, z);
+    for (int el = tid; el < range; el += PT) store_pt16(out + (lo + el) * 32, z);
     if (tid == 0 && err != nullptr) {  // plain store into pinned host memory (no PCIe atomic needed: any non-zero value is the signal)
       *reinterpret_cast<volatile unsigned*>(err) = (unsigned)ec;
       __threadfence_system();
@@ -660,9 +578,9 @@ void ed_fixed_launch(const SchedEnv& env, const u32* scalars, const u32* base, c
                      hipStream_t s) {
   const unsigned grid = (unsigned)((n + TPB - 1) / TPB);
   // the generator's prefix table (multiply_fixed_in_place), when the ctx has one and `base` is the generator
-  const bool tab = base == env.gen[FEC_ED25519] && env.gen_prefix[FEC_ED25519] != nullptr && env.gen_prefix_bits[FEC_ED25519] > 0;
-  const u32* prefix = tab ? env.gen_prefix[FEC_ED25519] : nullptr;
-  const int wbits = tab ? (int)env.gen_prefix_bits[FEC_ED25519] : 0;
+  const GenPrefix gp = gen_prefix_for(env, FEC_ED25519, base);
+  const u32* prefix = gp.prefix;
+  const int wbits = gp.wbits;
   if (n < ED_SORT_MIN || work == nullptr) {  // small batch (or no work area): quartiles of each workgroup's own 256 elements
     hipLaunchKernelGGL(k_ed_fixed_base, dim3(grid), dim3(TPB), 0, s, scalars, base, table, out, n, prefix, wbits);
     return;
@@ -680,26 +598,14 @@ void ed_fixed_launch(const SchedEnv& env, const u32* scalars, const u32* base, c
 
 void ed_launch_mul(const SchedEnv& env, const u32* scalars, const u32* points, u32* out, size_t n, hipStream_t s,
                    unsigned cu_divisor) {
-  // one workgroup per CU (or per cu_divisor-th CU) of the ctx's own device, each with a contiguous range of at least
-  // 64 elements
-  const unsigned cus = env.cus ? env.cus : 256u;
-  size_t grid = (n + 63) / 64;
-  const unsigned cap = cu_divisor > 1 && cus >= cu_divisor ? cus / cu_divisor : cus;
-  if (grid > cap) grid = cap;
-  const unsigned per_wg = (unsigned)((n + grid - 1) / grid);
-  grid = (n + per_wg - 1) / per_wg;
-  // PS_WIDE when the workgroups' elements are a little more than a whole number of PS_MAIN-element fills and a (near)
-  // whole number of PS_WIDE-element ones, up to three fills (the rule of kernels_p256.hip: wide_slots_pay)
-  bool wide = false;
-  if (per_wg > (unsigned)PS_MAIN && per_wg <= 3u * PS_WIDE) {
-    auto waste = [per_wg](unsigned q) { return (double)(((per_wg + q - 1) / q) * q) / (double)per_wg; };
-    wide = waste(PS_WIDE) + 0.04 < waste(PS_MAIN);
-  }
+  const SchedGrid sg = sched_grid(env, n, cu_divisor);
+  const unsigned grid = sg.grid, per_wg = sg.per_wg;
+  const bool wide = wide_slots_pay(per_wg, PS_MAIN, PS_WIDE);
   if (wide)
-    hipLaunchKernelGGL((k_ed_mul_pers<PS_WIDE>), dim3((unsigned)grid), dim3(PT), 0, s, scalars, points, out, n, per_wg, env.err,
+    hipLaunchKernelGGL((k_ed_mul_pers<PS_WIDE>), dim3(grid), dim3(PT), 0, s, scalars, points, out, n, per_wg, env.err,
                        env.force_fault);
   else
-    hipLaunchKernelGGL((k_ed_mul_pers<PS_MAIN>), dim3((unsigned)grid), dim3(PT), 0, s, scalars, points, out, n, per_wg, env.err,
+    hipLaunchKernelGGL((k_ed_mul_pers<PS_MAIN>), dim3(grid), dim3(PT), 0, s, scalars, points, out, n, per_wg, env.err,
                        env.force_fault);
 }
 

@@ -75,17 +75,6 @@ static __constant__ unsigned char kDifferentMessage[17] = {'d', 'i', 'f', 'f', '
 
 enum : unsigned char { F_TEST_MESSAGE = 1, F_RFC = 2, F_BAD_RANGE = 4 };
 
-FEC_DEV void ld8(u32 q[8], const u32* __restrict__ p) {
-  const uint4* v = reinterpret_cast<const uint4*>(p);
-  const uint4 a = v[0], b = v[1];
-  q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w;
-  q[4] = b.x; q[5] = b.y; q[6] = b.z; q[7] = b.w;
-}
-FEC_DEV void st8(u32* __restrict__ p, const u32 q[8]) {
-  uint4* v = reinterpret_cast<uint4*>(p);
-  v[0] = make_uint4(q[0], q[1], q[2], q[3]);
-  v[1] = make_uint4(q[4], q[5], q[6], q[7]);
-}
 FEC_DEV ed::sc4 sc_of_words(const u32 w[8]) {
   ed::sc4 s;
   FEC_UNROLL for (int i = 0; i < 4; ++i) s.l[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
@@ -142,11 +131,7 @@ FEC_DEV void prefix_r33_a33(u32 (&pre)[17], u32 pr, const fe& xrb, u32 pa, const
 }
 // to_affine with the panic test: a zero z of a point that is not the identity is an unwrap on None (ed25519.rs:1805)
 FEC_DEV bool affine_of(const u32* __restrict__ p, fe& x, fe& y, bool& panics) {
-  ed::pt q;
-  ld8(q.x.w, p);
-  ld8(q.y.w, p + 8);
-  ld8(q.z.w, p + 16);
-  ld8(q.t.w, p + 24);
+  const ed::pt q = load_pt16<ed::pt>(p);
   panics = !lane_of(ed::is_identity(q)) && lane_of(fe_is_zero(q.z));
   return lane_of(ed::to_affine(q, x, y));
 }
@@ -157,7 +142,7 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_pre(EddsaSignIo io, u32* __r
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   u32 kw[8];
-  ld8(kw, io.keys + i * 8);
+  load_w8(kw, io.keys + i * 8);
   u32 pre[8];
   u32 key0;
   if (io.mode == EDDSA_MODE_GENERIC) {   // the trait to_bytes(sk) (ed25519.rs:1164-1175): the raw limbs big-endian
@@ -195,10 +180,10 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_pre(EddsaSignIo io, u32* __r
   }
   u32 w[8];
   words_of_sc(a, w);
-  st8(scal + i * 8, w);
+  store_w8(scal + i * 8, w);
   if (io.mode != EDDSA_MODE_DERIVE) {
     words_of_sc(r, w);
-    st8(scal + (n + i) * 8, w);
+    store_w8(scal + (n + i) * 8, w);
   }
   flags[i] = f;
 }
@@ -222,7 +207,7 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_finish(EddsaSignIo io, const
       if (f & F_RFC) v = (u32)kRfcPk[4 * j] | ((u32)kRfcPk[4 * j + 1] << 8) | ((u32)kRfcPk[4 * j + 2] << 16) | ((u32)kRfcPk[4 * j + 3] << 24);
       o[j] = zero && !(f & F_RFC) ? 0u : v;
     }
-    st8(io.out + i * 8, o);
+    store_w8(io.out + i * 8, o);
     io.status[i] = (f & F_RFC) ? 0 : (panic_a ? 1 : 0);
     return;
   }
@@ -242,9 +227,9 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_finish(EddsaSignIo io, const
   if (f == 0 && !panics) {
     const ed::sc4 k = scalar_be(sha512::hash_prefixed<17>(pre, 66, m, len), 0);   // 329-337
     u32 w[8];
-    ld8(w, scal + i * 8);
+    load_w8(w, scal + i * 8);
     const ed::sc4 a = sc_of_words(w);
-    ld8(w, scal + (n + i) * 8);
+    load_w8(w, scal + (n + i) * 8);
     const ed::sc4 r = sc_of_words(w);
     s = ed::sc_add(r, ed::sc_mul_release(k, a, ovf));                          // 340 (Add 1193-1239, Mul 1256-1376)
   }
@@ -267,8 +252,8 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_finish(EddsaSignIo io, const
     } else if (zero) {
       FEC_UNROLL for (int j = 0; j < 16; ++j) o[j] = 0;
     }
-    st8(io.out + i * 16, o);
-    st8(io.out + i * 16 + 8, o + 8);
+    store_w8(io.out + i * 16, o);
+    store_w8(io.out + i * 16 + 8, o + 8);
     return;
   }
   // EDDSA_MODE_GENERIC: Signature { r: to_affine(R), s }; the special cases (to_affine(generator()), one())
@@ -289,12 +274,12 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_finish(EddsaSignIo io, const
     oinf = false;
     s.l[0] = s.l[1] = s.l[2] = s.l[3] = 0;
   }
-  st8(io.out + i * 16, ox.w);
-  st8(io.out + i * 16 + 8, oy.w);
+  store_fe16(io.out + i * 16, ox);
+  store_fe16(io.out + i * 16 + 8, oy);
   io.r_inf[i] = oinf ? 1 : 0;
   u32 w[8];
   words_of_sc(s, w);
-  st8(io.s + i * 8, w);
+  store_w8(io.s + i * 8, w);
 }
 
 __global__ __launch_bounds__(TPB) void k_sha512(const unsigned char* __restrict__ msgs, const u64* __restrict__ off, u64 msg_len,
@@ -310,8 +295,8 @@ __global__ __launch_bounds__(TPB) void k_sha512(const unsigned char* __restrict_
   } else {
     FEC_UNROLL for (int j = 0; j < 16; ++j) o[j] = 0;
   }
-  st8(out + i * 16, o);
-  st8(out + i * 16 + 8, o + 8);
+  store_w8(out + i * 16, o);
+  store_w8(out + i * 16 + 8, o + 8);
   if (status) status[i] = ok ? 0 : 4;
 }
 
@@ -352,11 +337,11 @@ __global__ __launch_bounds__(TPB) void k_eddsa_verify_msg_pre(EddsaVerifyIo io, 
     FEC_UNROLL for (int j = 0; j < 8; ++j) sw[j] = sha512::bswap(sv.w[7 - j]);
     if (f == 0) k = scalar_be(sha512::hash_prefixed<16>(pre, 64, m, len), 0);   // 419-428
   } else {
-    ld8(rx.w, io.sig + i * 16);
-    ld8(ry.w, io.sig + i * 16 + 8);
-    ld8(ax.w, io.pk + i * 16);
-    ld8(ay.w, io.pk + i * 16 + 8);
-    ld8(sw, io.s + i * 8);
+    rx = load_fe16(io.sig + i * 16);
+    ry = load_fe16(io.sig + i * 16 + 8);
+    ax = load_fe16(io.pk + i * 16);
+    ay = load_fe16(io.pk + i * 16 + 8);
+    load_w8(sw, io.s + i * 8);
     ainf = io.pk_inf != nullptr && io.pk_inf[i] != 0;
     if (f == 0 && io.r_inf != nullptr && io.r_inf[i] != 0) f = V_DECIDED | 0;   // 174-177
     if (f == 0) {
@@ -375,14 +360,11 @@ __global__ __launch_bounds__(TPB) void k_eddsa_verify_msg_pre(EddsaVerifyIo io, 
     rx.w[j] = go ? rx.w[j] : 0u;
     ry.w[j] = go ? ry.w[j] : 0u;
   }
-  st8(w.a + i * 32, a.x.w);
-  st8(w.a + i * 32 + 8, a.y.w);
-  st8(w.a + i * 32 + 16, a.z.w);
-  st8(w.a + i * 32 + 24, a.t.w);
-  st8(w.r + i * 16, rx.w);
-  st8(w.r + i * 16 + 8, ry.w);
-  st8(w.s + i * 8, sw);
-  st8(w.k + i * 8, kw);
+  store_pt16(w.a + i * 32, a);
+  store_fe16(w.r + i * 16, rx);
+  store_fe16(w.r + i * 16 + 8, ry);
+  store_w8(w.s + i * 8, sw);
+  store_w8(w.k + i * 8, kw);
   w.flags[i] = f;
 }
 
@@ -390,18 +372,10 @@ __global__ __launch_bounds__(TPB) void k_eddsa_verify_msg_finish(EddsaVerifyWork
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   const unsigned char f = w.flags[i];
-  ed::pt s_g, k_a;
-  ld8(s_g.x.w, w.sg + i * 32);
-  ld8(s_g.y.w, w.sg + i * 32 + 8);
-  ld8(s_g.z.w, w.sg + i * 32 + 16);
-  ld8(s_g.t.w, w.sg + i * 32 + 24);
-  ld8(k_a.x.w, w.ka + i * 32);
-  ld8(k_a.y.w, w.ka + i * 32 + 8);
-  ld8(k_a.z.w, w.ka + i * 32 + 16);
-  ld8(k_a.t.w, w.ka + i * 32 + 24);
+  const ed::pt s_g = load_pt16<ed::pt>(w.sg + i * 32), k_a = load_pt16<ed::pt>(w.ka + i * 32);
   fe rx, ry;
-  ld8(rx.w, w.r + i * 16);
-  ld8(ry.w, w.r + i * 16 + 8);
+  rx = load_fe16(w.r + i * 16);
+  ry = load_fe16(w.r + i * 16 + 8);
   const unsigned char v = eddsa_verify_tail(s_g, k_a, rx, ry);             // 196-211 / 431-446
   status[i] = (f & V_DECIDED) ? (unsigned char)(f & 0x7F) : v;
 }

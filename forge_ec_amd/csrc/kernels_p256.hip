@@ -53,73 +53,16 @@ __device__ unsigned long long g_sched_stats[8];
 
 namespace {
 
-FEC_DEV p256::pt ld_pt(const u32* l, int stride) {
-  p256::pt p;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) {
-    p.x.w[i] = l[i * stride];
-    p.y.w[i] = l[(8 + i) * stride];
-    p.z.w[i] = l[(16 + i) * stride];
-  }
-  return p;
-}
-FEC_DEV void st_pt(u32* l, int stride, const p256::pt& p) {
-  FEC_UNROLL for (int i = 0; i < 8; ++i) {
-    l[i * stride] = p.x.w[i];
-    l[(8 + i) * stride] = p.y.w[i];
-    l[(16 + i) * stride] = p.z.w[i];
-  }
-}
 // base point of element g straight from the caller's array (24 words, 16-byte loads; L2-resident:
 // a workgroup re-reads its 48 KiB of base points about 128 times)
-FEC_DEV p256::pt ld_base(const u32* points, size_t g) {
-  const uint4* src = reinterpret_cast<const uint4*>(points + g * 24);
-  uint4 v[6];
-  FEC_UNROLL for (int i = 0; i < 6; ++i) v[i] = src[i];
-  p256::pt p;
-  FEC_UNROLL for (int i = 0; i < 2; ++i) {
-    p.x.w[4 * i] = v[i].x; p.x.w[4 * i + 1] = v[i].y; p.x.w[4 * i + 2] = v[i].z; p.x.w[4 * i + 3] = v[i].w;
-    p.y.w[4 * i] = v[2 + i].x; p.y.w[4 * i + 1] = v[2 + i].y; p.y.w[4 * i + 2] = v[2 + i].z; p.y.w[4 * i + 3] = v[2 + i].w;
-    p.z.w[4 * i] = v[4 + i].x; p.z.w[4 * i + 1] = v[4 + i].y; p.z.w[4 * i + 2] = v[4 + i].z; p.z.w[4 * i + 3] = v[4 + i].w;
-  }
-  return p;
-}
-
-// Streaming accesses (a result is written once) carry the non-temporal hint so that they do not push the base points
-// -- re-read by every addition -- out of the XCD's L2.
-typedef u32 v4u_t __attribute__((ext_vector_type(4)));
-FEC_DEV void st_stream(u32* g, u32 a, u32 b, u32 c, u32 d) {
-  v4u_t v = {a, b, c, d};
-  __builtin_nontemporal_store(v, reinterpret_cast<v4u_t*>(g));
-}
-FEC_DEV void st_out(u32* o, const p256::pt& r) {  // 24 words, 16-byte stores
-  FEC_UNROLL for (int w = 0; w < 2; ++w) {
-    st_stream(o + 4 * w, r.x.w[4 * w], r.x.w[4 * w + 1], r.x.w[4 * w + 2], r.x.w[4 * w + 3]);
-    st_stream(o + 8 + 4 * w, r.y.w[4 * w], r.y.w[4 * w + 1], r.y.w[4 * w + 2], r.y.w[4 * w + 3]);
-    st_stream(o + 16 + 4 * w, r.z.w[4 * w], r.z.w[4 * w + 1], r.z.w[4 * w + 2], r.z.w[4 * w + 3]);
-  }
-}
-
-// one coordinate (8 words) of a slot / of a base point
-FEC_DEV fe ld_coord(const u32* l, int stride, int c) {
-  fe a;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) a.w[i] = l[(8 * c + i) * stride];
-  return a;
-}
-FEC_DEV fe ld_base_coord(const u32* point, int c) {
-  const uint4* src = reinterpret_cast<const uint4*>(point + 8 * c);
-  const uint4 lo = src[0], hi = src[1];
-  fe a;
-  a.w[0] = lo.x; a.w[1] = lo.y; a.w[2] = lo.z; a.w[3] = lo.w;
-  a.w[4] = hi.x; a.w[5] = hi.y; a.w[6] = hi.z; a.w[7] = hi.w;
-  return a;
-}
+FEC_DEV p256::pt base_point(const u32* points, size_t g) { return load_pt16<p256::pt>(points + g * 24); }
 
 // p256::pdouble (1869-1912) on a slot, coordinates loaded where they are used (Y twice)
 FEC_DEV p256::pt pdouble_in_place(const u32* lp, int stride) {
   using namespace p256;
-  const fe x = ld_coord(lp, stride, 0);
+  const fe x = load_coord(lp, stride, 0);
   const fe xx = sqr(x);
-  const fe yy = sqr(ld_coord(lp, stride, 1));
+  const fe yy = sqr(load_coord(lp, stride, 1));
   const fe yyyy = sqr(yy);
   const fe xy2 = sqr(add(x, yy));
   const fe w = sub(sub(xy2, xx), yyyy);
@@ -129,7 +72,7 @@ FEC_DEV p256::pt pdouble_in_place(const u32* lp, int stride) {
   pt r;
   r.x = sub(sub(ee, d), d);
   r.y = sub(mul(e, sub(d, r.x)), mul_small(yyyy, 8));
-  const fe y = ld_coord(lp, stride, 1), z = ld_coord(lp, stride, 2);
+  const fe y = load_coord(lp, stride, 1), z = load_coord(lp, stride, 2);
   const fe z3 = dbl(y);
   r.z = mul(z3, z);
   // z.is_one() (1909: once per element, on the first doubling after the result became the base point) and the
@@ -157,16 +100,16 @@ FEC_DEV p256::pt pdouble_in_place(const u32* lp, int stride) {
 template <bool AFFINE>
 FEC_DEV p256::pt padd_body(const u32* lp, int stride, const u32* gq, const u32* lzz, int zstride) {
   using namespace p256;
-  const fe z1 = ld_coord(lp, stride, 2), z2 = AFFINE ? fe_small(1) : ld_base_coord(gq, 2);
+  const fe z1 = load_coord(lp, stride, 2), z2 = AFFINE ? fe_small(1) : load_coord16(gq, 2);
   const lmask idp = fe_is_zero(z1), idq = AFFINE ? (lmask)0 : fe_is_zero(z2);
-  const fe z1z1 = sqr(z1), z2z2 = AFFINE ? fe_small(1) : (lzz ? ld_coord(lzz, zstride, 0) : sqr(z2));
+  const fe z1z1 = sqr(z1), z2z2 = AFFINE ? fe_small(1) : (lzz ? load_coord(lzz, zstride, 0) : sqr(z2));
   const fe zs = sub(sub(sqr(add(z1, z2)), z1z1), z2z2);
-  const fe s1 = AFFINE ? ld_coord(lp, stride, 1) : mul(mul(ld_coord(lp, stride, 1), z2), z2z2);
+  const fe s1 = AFFINE ? load_coord(lp, stride, 1) : mul(mul(load_coord(lp, stride, 1), z2), z2z2);
   __builtin_amdgcn_sched_barrier(0);  // keep the loads of q's coordinates where they are used (register budget)
-  const fe s2 = mul(mul(ld_base_coord(gq, 1), z1), z1z1);
-  const fe u1 = AFFINE ? ld_coord(lp, stride, 0) : mul(ld_coord(lp, stride, 0), z2z2);
+  const fe s2 = mul(mul(load_coord16(gq, 1), z1), z1z1);
+  const fe u1 = AFFINE ? load_coord(lp, stride, 0) : mul(load_coord(lp, stride, 0), z2z2);
   __builtin_amdgcn_sched_barrier(0);
-  const fe u2 = mul(ld_base_coord(gq, 0), z1z1);
+  const fe u2 = mul(load_coord16(gq, 0), z1z1);
   const lmask ueq = fe_eq(u1, u2);
   lmask same = 0, opposite = 0;
   if (__builtin_expect(ueq != 0, 0)) {
@@ -186,8 +129,8 @@ FEC_DEV p256::pt padd_body(const u32* lp, int stride, const u32* gq, const u32* 
   o.z = z3;
   if (__builtin_expect((idp | idq | ueq) != 0, 0)) {
     pt p, q;
-    p.x = ld_coord(lp, stride, 0); p.y = ld_coord(lp, stride, 1); p.z = ld_coord(lp, stride, 2);
-    q.x = ld_base_coord(gq, 0); q.y = ld_base_coord(gq, 1); q.z = ld_base_coord(gq, 2);
+    p.x = load_coord(lp, stride, 0); p.y = load_coord(lp, stride, 1); p.z = load_coord(lp, stride, 2);
+    q.x = load_coord16(gq, 0); q.y = load_coord16(gq, 1); q.z = load_coord16(gq, 2);
     o = pt_select(o, identity(), uniform_mask(opposite));
     o = pt_select(o, p, idq);
     o = pt_select(o, q, idp);
@@ -271,10 +214,8 @@ __global__ __launch_bounds__(QT, 1) void k_p256_mul_sched(const u32* __restrict_
   asm volatile("" : "+v"(ctl));
   const unsigned ctl_addr = (unsigned)(size_t)ctl;  // LDS byte address of the control block
   if (FIXED && HOIST) {  // every lane computes the same square; one stores it
-    const fe zz = p256::sqr(ld_base_coord(points, 2));
-    if (tid == 0) {
-      FEC_UNROLL for (int w = 0; w < 8; ++w) lds_zz[w] = zz.w[w];
-    }
+    const fe zz = p256::sqr(load_coord16(points, 2));
+    if (tid == 0) store_fe(lds_zz, 1, zz);
   }
   // every slot starts in the free ring: the wavefronts' first pops are claims of 64 elements each
   lf_init<RING>(lds_lf, tid, QT, range < QS ? range : QS, force_fault ? (unsigned)FEC_DEVERR_FORCED : 0u);
@@ -312,9 +253,9 @@ __global__ __launch_bounds__(QT, 1) void k_p256_mul_sched(const u32* __restrict_
       const u32 kw[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
       int t = 0;  // top set bit of the scalar
       FEC_UNROLL for (int w = 0; w < 8; ++w) t = kw[w] ? 32 * w + 31 - __builtin_clz(kw[w]) : t;
-      const p256::pt base = ld_base(points, FIXED ? 0 : g);
+      const p256::pt base = base_point(points, FIXED ? 0 : g);
       if (t == 0) {  // scalar == 1: 255 doublings of the identity, then identity + point
-        st_out(out + g * 24, base);
+        store_pt16_nt(out + g * 24, base);
         continue;
       }
       // Fixed base with a prefix table (fecgpu.hip: ensure_gen_prefix): the result after the first wbits steps --
@@ -325,9 +266,9 @@ __global__ __launch_bounds__(QT, 1) void k_p256_mul_sched(const u32* __restrict_
       p256::pt start = base;
       if (idx != 0) {
         t = 256 - wbits;   // the slot starts at step wbits
-        start = ld_base(prefix, idx);
+        start = base_point(prefix, idx);
       }
-      st_pt(lds_st + e, QS, start);
+      store_pt(lds_st + e, QS, start);
       if (!FIXED) {
         const fe zz = p256::sqr(base.z);
         FEC_UNROLL for (int w = 0; w < 8; ++w) lds_zq[w * QS + e] = zz.w[w];
@@ -387,7 +328,7 @@ __global__ __launch_bounds__(QT, 1) void k_p256_mul_sched(const u32* __restrict_
     // (Round 2 queued the doubling and the addition separately: 381 visits of the scheduler per element instead of 254.)
     FEC_MARK("task_double_begin");
 #ifdef FEC_SCHED_STUB   // tools/microbench/sched_stats.hip: the scheduler alone (the task is a copy of the slot)
-    res = ld_pt(lds_st + e, QS);
+    res = load_pt<p256::pt>(lds_st + e, QS);
 #else
     res = pdouble_in_place(lds_st + e, QS);
 #endif
@@ -395,11 +336,11 @@ __global__ __launch_bounds__(QT, 1) void k_p256_mul_sched(const u32* __restrict_
     if (kind == LF_Q_A) {
       // the addition reads its first operand from the slot (a lane's LDS accesses stay in order); inactive lanes add
       // slot 0 and element 0 of the range: harmless, never stored
-      if (live) st_pt(lds_st + e, QS, res);
+      if (live) store_pt(lds_st + e, QS, res);
       const size_t g_el = lo + gid;
       FEC_MARK("task_add_begin");
 #ifdef FEC_SCHED_STUB
-      res = ld_pt(lds_st + e, QS);
+      res = load_pt<p256::pt>(lds_st + e, QS);
       (void)g_el;
 #else
       const bool all_affine = __builtin_amdgcn_ballot_w64(live && !(step_word & 0x8000)) == 0;
@@ -413,12 +354,12 @@ __global__ __launch_bounds__(QT, 1) void k_p256_mul_sched(const u32* __restrict_
       lds_step[e] = (unsigned short)(step | (step_word & 0x8000));
       fin = step == 256;
       if (!fin) {
-        st_pt(lds_st + e, QS, res);
+        store_pt(lds_st + e, QS, res);
         nxt = (int)step_bit(e, step);
       }
     }
     if (fin) {  // the element is done: its result goes out (16-byte stores), the slot joins the free ring
-      st_out(out + (lo + gid) * 24, res);
+      store_pt16_nt(out + (lo + gid) * 24, res);
       nxt = LF_NXT_FREE;
     }
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(oob) != 0, 0)) {
@@ -443,33 +384,15 @@ __global__ __launch_bounds__(QT, 1) void k_p256_mul_sched(const u32* __restrict_
   }
 }
 
-namespace {
-// Which instantiation a launch whose workgroups own `per_wg` elements each takes: QS_WIDE when those elements are a
-// little more than a whole number of QS_MAIN-element fills and a (near) whole number of QS_WIDE-element ones -- a fill
-// of leftovers starts late and runs thinly occupied -- and only up to three fills (beyond that the refills overlap and
-// the leaner LDS image with the scalar in it wins: 23.9 against 24.3 ms at 2^20).
-inline bool wide_slots_pay(unsigned per_wg) {
-  if (per_wg <= (unsigned)QS_MAIN || per_wg > 3u * QS_WIDE) return false;
-  auto waste = [per_wg](unsigned q) { return (double)(((per_wg + q - 1) / q) * q) / (double)per_wg; };
-  return waste(QS_WIDE) + 0.04 < waste(QS_MAIN);
-}
-}  // namespace
-
 void p256_launch_mul(const SchedEnv& env, bool fixed, const u32* scalars, const u32* points, u32* out, size_t n, hipStream_t s) {
-  // one workgroup per CU the launch may take (env.cus), each with a contiguous range of at least 64 elements
-  const unsigned cus = env.cus ? env.cus : 256u;
-  size_t grid = (n + 63) / 64;
-  if (grid > cus) grid = cus;
-  const unsigned per_wg = (unsigned)((n + grid - 1) / grid);
-  grid = (n + per_wg - 1) / per_wg;
-  const bool wide = wide_slots_pay(per_wg);
-  const dim3 g((unsigned)grid), b(QT);
+  const SchedGrid sg = sched_grid(env, n);
+  const unsigned per_wg = sg.per_wg;
+  const bool wide = wide_slots_pay(per_wg, QS_MAIN, QS_WIDE);
+  const dim3 g(sg.grid), b(QT);
   if (fixed) {
-    const bool tab = points == env.gen[FEC_P256] && env.gen_prefix[FEC_P256] != nullptr && env.gen_prefix_bits[FEC_P256] > 0;
-    const u32* pre = tab ? env.gen_prefix[FEC_P256] : (const u32*)nullptr;
-    const int wbits = tab ? (int)env.gen_prefix_bits[FEC_P256] : 0;
+    const GenPrefix gp = gen_prefix_for(env, FEC_P256, points);
     hipLaunchKernelGGL((k_p256_mul_sched<true, true, QS_FIXED>), g, b, 0, s, scalars, points, out, n, per_wg, env.err,
-                       env.force_fault, pre, wbits);
+                       env.force_fault, gp.prefix, gp.wbits);
     return;
   }
   // Variable base: z2z2 is recomputed by every addition.  Parking it in the element's (still unused) output slot was

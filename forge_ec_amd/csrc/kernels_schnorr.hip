@@ -44,17 +44,6 @@ namespace fecgpu {
 
 namespace {
 
-FEC_DEV void ld8(u32 q[8], const u32* __restrict__ p) {
-  const uint4* v = reinterpret_cast<const uint4*>(p);
-  const uint4 a = v[0], b = v[1];
-  q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w;
-  q[4] = b.x; q[5] = b.y; q[6] = b.z; q[7] = b.w;
-}
-FEC_DEV void st8(u32* __restrict__ p, const u32 q[8]) {
-  uint4* v = reinterpret_cast<uint4*>(p);
-  v[0] = make_uint4(q[0], q[1], q[2], q[3]);
-  v[1] = make_uint4(q[4], q[5], q[6], q[7]);
-}
 // Element i's message range; false (and nothing read) where it is not inside [0, msg_len)  (as kernels_eddsa.hip)
 FEC_DEV bool msg_range(const u64* __restrict__ off, u64 msg_len, size_t i, u64& lo, u64& len) {
   const u64 a = off[i], b = off[i + 1];
@@ -63,14 +52,6 @@ FEC_DEV bool msg_range(const u64* __restrict__ off, u64 msg_len, size_t i, u64& 
   len = ok ? b - a : 0;
   return ok;
 }
-FEC_DEV secp::pt ld_pt(const u32* __restrict__ p) {
-  secp::pt q;
-  ld8(q.x.w, p);
-  ld8(q.y.w, p + 8);
-  ld8(q.z.w, p + 16);
-  return q;
-}
-
 __global__ __launch_bounds__(TPB) void k_sha256(const unsigned char* __restrict__ msgs, const u64* __restrict__ off, u64 msg_len,
                                                 u32* __restrict__ out, unsigned char* __restrict__ status, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
@@ -84,7 +65,7 @@ __global__ __launch_bounds__(TPB) void k_sha256(const unsigned char* __restrict_
   } else {
     FEC_UNROLL for (int j = 0; j < 8; ++j) o[j] = 0;
   }
-  st8(out + i * 8, o);
+  store_w8(out + i * 8, o);
   if (status) status[i] = ok ? 0 : 4;
 }
 
@@ -102,9 +83,9 @@ __global__ __launch_bounds__(TPB) void k_bip340_pre(Bip340Io io, Bip340Work w, s
   u64 lo = 0, len = 0;
   unsigned char f = msg_range(io.off, io.msg_len, i, lo, len) ? 0 : bip340::F_BAD_RANGE;
   u32 kw[8];
-  ld8(kw, io.keys + i * 8);
+  load_w8(kw, io.keys + i * 8);
   const fe d = bip340::pre_step(f, kw, len ? io.msgs + lo : nullptr, len);
-  st8(w.d + i * 8, d.w);
+  store_fe16(w.d + i * 8, d);
   w.flags[i] = f;
 }
 
@@ -116,11 +97,11 @@ __global__ __launch_bounds__(TPB) void k_bip340_mid(Bip340Io io, Bip340Work w, s
   u64 lo = 0, len = 0;
   (void)msg_range(io.off, io.msg_len, i, lo, len);
   fe d, px;
-  ld8(d.w, w.d + i * 8);
-  const fe k = bip340::mid_step(f, ld_pt(w.p + i * 24), d, px, len ? io.msgs + lo : nullptr, len);
-  st8(w.d + i * 8, d.w);
-  st8(w.k + i * 8, k.w);
-  st8(w.px + i * 8, px.w);
+  d = load_fe16(w.d + i * 8);
+  const fe k = bip340::mid_step(f, load_pt16<secp::pt>(w.p + i * 24), d, px, len ? io.msgs + lo : nullptr, len);
+  store_fe16(w.d + i * 8, d);
+  store_fe16(w.k + i * 8, k);
+  store_fe16(w.px + i * 8, px);
   w.flags[i] = f;
 }
 
@@ -132,13 +113,13 @@ __global__ __launch_bounds__(TPB) void k_bip340_finish(Bip340Io io, Bip340Work w
   u64 lo = 0, len = 0;
   (void)msg_range(io.off, io.msg_len, i, lo, len);
   fe k, d, px;
-  ld8(k.w, w.k + i * 8);
-  ld8(d.w, w.d + i * 8);
-  ld8(px.w, w.px + i * 8);
+  k = load_fe16(w.k + i * 8);
+  d = load_fe16(w.d + i * 8);
+  px = load_fe16(w.px + i * 8);
   u32 o[16];
-  bip340::finish_step(f, ld_pt(w.r + i * 24), k, d, px, len ? io.msgs + lo : nullptr, len, o);
-  st8(io.sig + i * 16, o);
-  st8(io.sig + i * 16 + 8, o + 8);
+  bip340::finish_step(f, load_pt16<secp::pt>(w.r + i * 24), k, d, px, len ? io.msgs + lo : nullptr, len, o);
+  store_w8(io.sig + i * 16, o);
+  store_w8(io.sig + i * 16 + 8, o + 8);
   io.status[i] = bip340::status_of(f);
 }
 

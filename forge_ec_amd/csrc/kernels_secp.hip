@@ -23,30 +23,6 @@ namespace fecgpu {
 
 namespace {
 
-FEC_DEV secp::pt ld3(const u32* l, int stride) {
-  secp::pt p;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) {
-    p.x.w[i] = l[i * stride];
-    p.y.w[i] = l[(8 + i) * stride];
-    p.z.w[i] = l[(16 + i) * stride];
-  }
-  return p;
-}
-FEC_DEV void st3(u32* l, int stride, const secp::pt& p) {
-  FEC_UNROLL for (int i = 0; i < 8; ++i) {
-    l[i * stride] = p.x.w[i];
-    l[(8 + i) * stride] = p.y.w[i];
-    l[(16 + i) * stride] = p.z.w[i];
-  }
-}
-
-// one coordinate (c = 0, 1, 2: X, Y, Z) of a ladder point in its LDS slot
-FEC_DEV fe ldc(const u32* l, int c) {
-  fe a;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) a.w[i] = l[(8 * c + i) * TPB];
-  return a;
-}
-
 // secp::padd_nodouble (Add, 1444-1498) with both operands left in their LDS slots: every coordinate is loaded where
 // it is first used (Z twice), so that neither point is live across the sixteen products, and the early-outs
 // (identity operands: Z == 0; u1 == u2) sit behind one-word tests every lane taking one must pass, their exact masks
@@ -57,24 +33,24 @@ FEC_DEV secp::pt padd_slots(const u32* lp, const u32* lq, lmask& need_double) {
   fe z1s, z1c, z2s, z2c;
   lmask maybe;
   {
-    const fe z1 = ldc(lp, 2);
+    const fe z1 = load_coord(lp, TPB, 2);
     maybe = lanes_where(z1.w[0] == 0u);
     z1s = sqr(z1);
     z1c = mul(z1s, z1);
   }
   __builtin_amdgcn_sched_barrier(0);  // keep the loads where they are used (register budget of three waves per SIMD)
   {
-    const fe z2 = ldc(lq, 2);
+    const fe z2 = load_coord(lq, TPB, 2);
     maybe |= lanes_where(z2.w[0] == 0u);
     z2s = sqr(z2);
     z2c = mul(z2s, z2);
   }
   __builtin_amdgcn_sched_barrier(0);
-  const fe u1 = mul(ldc(lp, 0), z2s);
-  const fe u2 = mul(ldc(lq, 0), z1s);
+  const fe u1 = mul(load_coord(lp, TPB, 0), z2s);
+  const fe u2 = mul(load_coord(lq, TPB, 0), z1s);
   __builtin_amdgcn_sched_barrier(0);
-  const fe s1 = mul(ldc(lp, 1), z2c);
-  const fe s2 = mul(ldc(lq, 1), z1c);
+  const fe s1 = mul(load_coord(lp, TPB, 1), z2c);
+  const fe s2 = mul(load_coord(lq, TPB, 1), z1c);
   __builtin_amdgcn_sched_barrier(0);
   lmask ueq = 0, seq = 0;
   if (__builtin_expect(lanes_where(u1.w[0] == u2.w[0]) != 0, 0)) {
@@ -89,10 +65,10 @@ FEC_DEV secp::pt padd_slots(const u32* lp, const u32* lq, lmask& need_double) {
   pt o;
   o.x = sub(sub(sub(sqr(r), h3), u1h2), u1h2);
   o.y = sub(mul(r, sub(u1h2, o.x)), mul(s1, h3));
-  o.z = mul(mul(h, ldc(lp, 2)), ldc(lq, 2));
+  o.z = mul(mul(h, load_coord(lp, TPB, 2)), load_coord(lq, TPB, 2));
   need_double = 0;
   if (__builtin_expect((maybe | ueq) != 0, 0)) {  // early-outs: only the ladder's first steps
-    const pt p = ld3(lp, TPB), q = ld3(lq, TPB);
+    const pt p = load_pt<secp::pt>(lp, TPB), q = load_pt<secp::pt>(lq, TPB);
     const lmask idp = is_identity(p), idq = is_identity(q);
     o = pt_select(o, identity(), ueq & ~seq);
     o = pt_select(o, p, idq);
@@ -141,7 +117,7 @@ __global__ __launch_bounds__(TPB, 3) void k_secp_mul(const u32* __restrict__ sca
       FEC_UNROLL for (int i = 0; i < 8; ++i) any |= kg[i];
       early = lanes_where(any == 0);
     }
-    if (MODE == 2) early |= secp::is_identity(ld3(points, 1));   // (2636-2639: a caller's own base may be the identity)
+    if (MODE == 2) early |= secp::is_identity(load_pt<secp::pt>(points, 1));   // (2636-2639: a caller's own base may be the identity)
     if (MODE == 2 || MODE == 3) {
       // MODE 3: `prefix` is the level below, this element's parent entry is g >> 1
       const u32 idx = MODE == 3 ? (u32)(g >> 1) : __builtin_bswap32(kg[0]) >> (32 - wbits);
@@ -156,10 +132,10 @@ __global__ __launch_bounds__(TPB, 3) void k_secp_mul(const u32* __restrict__ sca
       i0 = MODE == 3 ? 0 : wbits;
       if (MODE == 3) i1 = 1;
     } else {
-      const secp::pt r1 = MODE != 0 ? ld3(points, 1) : ld3(lds + e, TPB);
+      const secp::pt r1 = MODE != 0 ? load_pt<secp::pt>(points, 1) : load_pt<secp::pt>(lds + e, TPB);
       early |= secp::is_identity(r1);
-      st3(slot0, TPB, secp::identity());
-      st3(slot0 + 24 * TPB, TPB, r1);
+      store_pt(slot0, TPB, secp::identity());
+      store_pt(slot0 + 24 * TPB, TPB, r1);
     }
     u32 kword = MODE == 3 ? 0u : kg[i0 >> 5];
 #pragma unroll 1
@@ -183,16 +159,16 @@ __global__ __launch_bounds__(TPB, 3) void k_secp_mul(const u32* __restrict__ sca
         lmask nd;
         secp::pt s = padd_slots(slot0, slot0 + 24 * TPB, nd);
         if (__builtin_expect(nd != 0, 0)) {  // Add (1469-1473) returns self.double(): never on random inputs
-          secp::pt d0 = secp::pdouble(ld3(slot0, TPB));
+          secp::pt d0 = secp::pdouble(load_pt<secp::pt>(slot0, TPB));
           s = secp::pt_select(s, d0, nd);
         }
         return s;
       });
-      secp_step::double_step(slot_d, [&]() { return secp::pdouble(ld3(slot_d, TPB)); });
+      secp_step::double_step(slot_d, [&]() { return secp::pdouble(load_pt<secp::pt>(slot_d, TPB)); });
     }
     if (MODE != 3) {
-      const secp::pt r0 = secp::pt_select(ld3(slot0, TPB), secp::identity(), early);
-      st3(slot0, TPB, r0);
+      const secp::pt r0 = secp::pt_select(load_pt<secp::pt>(slot0, TPB), secp::identity(), early);
+      store_pt(slot0, TPB, r0);
     }
   }
   __syncthreads();
@@ -202,9 +178,9 @@ __global__ __launch_bounds__(TPB, 3) void k_secp_mul(const u32* __restrict__ sca
 
 void secp_launch_mul(const SchedEnv& env, bool fixed, const u32* scalars, const u32* points, u32* out, size_t n, hipStream_t s) {
   const unsigned grid = (unsigned)((n + TPB - 1) / TPB);
-  const int w = (int)env.gen_prefix_bits[FEC_SECP256K1];
-  if (fixed && w > 0 && points == env.gen[FEC_SECP256K1] && env.gen_prefix[FEC_SECP256K1] != nullptr)
-    hipLaunchKernelGGL((k_secp_mul<2>), dim3(grid), dim3(TPB), 0, s, scalars, points, out, n, env.gen_prefix[FEC_SECP256K1], w);
+  const GenPrefix gp = fixed ? gen_prefix_for(env, FEC_SECP256K1, points) : GenPrefix{nullptr, 0};
+  if (gp.prefix != nullptr)
+    hipLaunchKernelGGL((k_secp_mul<2>), dim3(grid), dim3(TPB), 0, s, scalars, points, out, n, gp.prefix, gp.wbits);
   else if (fixed) hipLaunchKernelGGL((k_secp_mul<1>), dim3(grid), dim3(TPB), 0, s, scalars, points, out, n, (const u32*)nullptr, 0);
   else hipLaunchKernelGGL((k_secp_mul<0>), dim3(grid), dim3(TPB), 0, s, scalars, points, out, n, (const u32*)nullptr, 0);
 }

@@ -15,36 +15,15 @@
 
 namespace fecgpu {
 
-namespace {
-
-FEC_DEV void load8(u32 q[8], const u32* __restrict__ p, size_t i) {
-  const uint4* v = reinterpret_cast<const uint4*>(p + i * 8);
-  const uint4 a = v[0], b = v[1];
-  q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w;
-  q[4] = b.x; q[5] = b.y; q[6] = b.z; q[7] = b.w;
-}
-FEC_DEV void store8(u32* __restrict__ p, size_t i, const u32 q[8]) {
-  uint4* v = reinterpret_cast<uint4*>(p + i * 8);
-  v[0] = make_uint4(q[0], q[1], q[2], q[3]);
-  v[1] = make_uint4(q[4], q[5], q[6], q[7]);
-}
-FEC_DEV fe load_fe(const u32* __restrict__ p, size_t i) {
-  fe v;
-  load8(v.w, p, i);
-  return v;
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(TPB) void k_x25519(const u32* __restrict__ scalars, const u32* __restrict__ us,
                                                 u32* __restrict__ out, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   u32 s[8], q[8], r[8];
-  load8(s, scalars, i);
-  load8(q, us, i);
+  load_w8(s, scalars + i * 8);
+  load_w8(q, us + i * 8);
   x25519::x25519_words(r, s, q);
-  store8(out, i, r);
+  store_w8(out + i * 8, r);
 }
 
 __global__ __launch_bounds__(TPB) void k_curve25519_mul(const u32* __restrict__ scalars, const u32* __restrict__ points,
@@ -55,8 +34,8 @@ __global__ __launch_bounds__(TPB) void k_curve25519_mul(const u32* __restrict__ 
   lmask ident, kzero, kone, ktwo;
   {
     u32 k[8];
-    load8(k, scalars, i);
-    const fe x = load_fe(points, 2 * i), z = load_fe(points, 2 * i + 1);
+    load_w8(k, scalars + i * 8);
+    const fe x = load_fe16(points + i * 16), z = load_fe16(points + i * 16 + 8);
     const u32 khi = k[1] | k[2] | k[3] | k[4] | k[5] | k[6] | k[7];
     ident = fe_is_zero(z);                        // 1924
     kzero = lanes_where(khi == 0u && k[0] == 0u);  // 1928
@@ -71,7 +50,7 @@ __global__ __launch_bounds__(TPB) void k_curve25519_mul(const u32* __restrict__ 
   x25519::x25519_words(rb, sb, ub);
   fe rx = x25519::reduce(x25519::from_be_words(rb)), rz = fe_small(1);
   // the early exits, on the point reloaded (it is not kept live across the ladder)
-  const fe x = load_fe(points, 2 * i), z = load_fe(points, 2 * i + 1);
+  const fe x = load_fe16(points + i * 16), z = load_fe16(points + i * 16 + 8);
   const lmask two = uniform_mask(ktwo & ~ident);
   if (__builtin_expect(two != 0, 0)) {  // p.double() (1749-1780); z != 0 on these lanes
     fe dx = x, dz = z;
@@ -85,16 +64,16 @@ __global__ __launch_bounds__(TPB) void k_curve25519_mul(const u32* __restrict__ 
   const lmask idm = uniform_mask(ident | kzero);  // Self::identity() = (one, zero)
   rx = fe_select(rx, fe_small(1), idm);
   rz = fe_select(rz, fe_zero(), idm);
-  store8(out, 2 * i, rx.w);
-  store8(out, 2 * i + 1, rz.w);
+  store_fe16(out + i * 16, rx);
+  store_fe16(out + i * 16 + 8, rz);
 }
 
 __global__ __launch_bounds__(TPB) void k_x25519_field_op(int op, const u32* __restrict__ a, const u32* __restrict__ b,
                                                          u32* __restrict__ out, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  const fe x = load_fe(a, i);
-  const fe y = (op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL) ? load_fe(b, i) : fe_zero();
+  const fe x = load_fe16(a + i * 8);
+  const fe y = (op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL) ? load_fe16(b + i * 8) : fe_zero();
   fe r;
   switch (op) {
     case FEC_F_ADD: r = x25519::add(x, y); break;
@@ -103,7 +82,7 @@ __global__ __launch_bounds__(TPB) void k_x25519_field_op(int op, const u32* __re
     case FEC_F_SQR: r = x25519::sqr(x); break;
     default: r = x25519::neg(x); break;
   }
-  store8(out, i, r.w);
+  store_fe16(out + i * 8, r);
 }
 
 static unsigned grid(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }

@@ -15,6 +15,7 @@
 //  * Add / Sub / Neg (353-440, 509-539) are restated for arbitrary 256-bit operands.
 #pragma once
 #include "limbs.hpp"
+#include "coop.hpp"
 
 namespace fecgpu {
 namespace secp {
@@ -538,7 +539,7 @@ FEC_DEV pt padd(const pt& p, const pt& q) {
 // squarings form a dependency graph of depth 6 and width <= 4.  padd_coop() executes that graph level
 // by level -- the same operations on the same operands as padd_nodouble(), so the sum is bit-identical
 // -- with lanes 0..3 of the wavefront each taking one operation of the level.  Values travel between
-// lanes through 27 eight-word slots of LDS (a wavefront's LDS accesses execute in program order, so no
+// lanes through 27 eight-word slots of LDS (coop.hpp: a wavefront's LDS accesses execute in program order, so no
 // barrier is needed); the cheap field subtractions in between are done by every lane redundantly.
 //   level 1 (square)   z1s = z1^2            z2s = z2^2
 //   level 2 (Mul)      u1 = x1 z2s           u2 = x2 z1s          z1c = z1s z1      z2c = z2s z2
@@ -550,45 +551,10 @@ FEC_DEV pt padd(const pt& p, const pt& q) {
 namespace coop {
 enum { PX = 0, PY, PZ, QX, QY, QZ, Z1S, Z2S, U1, U2, Z1C, Z2C, S1, S2, H, R, H2, R2, H3, U1H2, HZ, T, S1H3, Z3, X3, DD, ONE, SLOTS };
 constexpr int WORDS = SLOTS * 8;
-#ifdef FEC_HOST_EMUL
-FEC_DEV fe ld(const u32* sh, int slot) {
-  fe a;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) a.w[i] = sh[slot * 8 + i];
-  return a;
-}
-FEC_DEV void st(u32* sh, int slot, const fe& a) {
-  FEC_UNROLL for (int i = 0; i < 8; ++i) sh[slot * 8 + i] = a.w[i];
-}
-#else
-// a slot is 32 bytes, 16-byte aligned (the caller's array is): two ds_read_b128 / ds_write_b128
-FEC_DEV fe ld(const u32* sh, int slot) {
-  const uint4* s4 = reinterpret_cast<const uint4*>(sh + slot * 8);
-  const uint4 lo = s4[0], hi = s4[1];
-  fe a;
-  a.w[0] = lo.x; a.w[1] = lo.y; a.w[2] = lo.z; a.w[3] = lo.w;
-  a.w[4] = hi.x; a.w[5] = hi.y; a.w[6] = hi.z; a.w[7] = hi.w;
-  return a;
-}
-FEC_DEV void st(u32* sh, int slot, const fe& a) {
-  uint4* s4 = reinterpret_cast<uint4*>(sh + slot * 8);
-  s4[0] = make_uint4(a.w[0], a.w[1], a.w[2], a.w[3]);
-  s4[1] = make_uint4(a.w[4], a.w[5], a.w[6], a.w[7]);
-}
-#endif
-#ifdef FEC_HOST_EMUL
-FEC_DEV void sync() {}
-FEC_DEV int lane_id() { return 0; }
-#else
-// A wavefront's LDS instructions execute in program order, so a read issued after another lane's
-// write (same wavefront, later instruction) returns the written data: no s_waitcnt is needed between
-// them, only compiler ordering (the fences emit no instruction at wavefront scope).
-FEC_DEV void sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-FEC_DEV int lane_id() { return (int)(threadIdx.x & 63); }
-#endif
+using coopx::ld;
+using coopx::st;
+using coopx::sync;
+using coopx::lane_id;
 FEC_DEV int pick(int lane, int a0, int a1, int a2, int a3) { return lane == 0 ? a0 : (lane == 1 ? a1 : (lane == 2 ? a2 : (lane == 3 ? a3 : ONE))); }
 // one level: lane l (< n) computes op(slot a_l, slot b_l) into slot o_l; the other lanes work on the constant 1
 template <bool SQR>
@@ -610,7 +576,7 @@ FEC_DEV void level(u32* sh, int n, int a0, int a1, int a2, int a3, int b0, int b
 }  // namespace coop
 
 // sh: coop::WORDS words of LDS owned by this wavefront; slots PX..QZ hold p and q on entry (written by
-// the caller, followed by coop::sync()); slot ONE holds the constant 1.  Every lane returns the sum.
+// the caller, followed by coopx::sync()); slot ONE holds the constant 1.  Every lane returns the sum.
 FEC_DEV pt padd_coop(u32* sh) {
   using namespace coop;
 #ifdef FEC_HOST_EMUL

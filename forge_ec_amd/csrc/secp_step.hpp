@@ -132,20 +132,6 @@ FEC_DEV fe sub(const fe& a, const fe& b, Rare& rr) {
   return x;
 }
 
-// a ladder point in its LDS slot: word w of the point at l[w * TPB]
-FEC_DEV fe ld(const u32* l, int c) {
-  fe a;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) a.w[i] = l[(8 * c + i) * TPB];
-  return a;
-}
-FEC_DEV void st(u32* l, const pt& p) {
-  FEC_UNROLL for (int i = 0; i < 8; ++i) {
-    l[i * TPB] = p.x.w[i];
-    l[(8 + i) * TPB] = p.y.w[i];
-    l[(16 + i) * TPB] = p.z.w[i];
-  }
-}
-
 // The up-front identity tests need one word of Z; the operation needs the whole point right after.  Without this
 // the compiler sinks the other loads below the test's branch (the fast path is their only user), and the step pays
 // two LDS round trips in a row where one does: the empty statement takes the loaded words as inputs, so all of them
@@ -153,10 +139,11 @@ FEC_DEV void st(u32* l, const pt& p) {
 FEC_DEV void in_registers(const fe& a, u32 b) { asm volatile("" : : FEC_V8(a), "v"(b)); }
 FEC_DEV void in_registers(const fe& a, const fe& b) { asm volatile("" : : FEC_V8(a), FEC_V8(b)); }
 
+// (A ladder point sits in its LDS slot: word w of the point at l[w * TPB].)
 // The addition of padd_slots (kernels_secp.hip) -- the same products on the same operands, loaded where they are used,
 // with the same sched_barrier placement -- on the common legs only.  False: some lane needs the exact code.
 FEC_DEV bool padd_fast(const u32* lp, const u32* lq, pt& o) {
-  const fe z1 = ld(lp, 2);
+  const fe z1 = load_coord(lp, TPB, 2);
   const u32 z2w0 = lq[16 * TPB];
   in_registers(z1, z2w0);
   if (__builtin_expect(lanes_where((z1.w[0] < z2w0 ? z1.w[0] : z2w0) == 0u) != 0, 0)) return false;
@@ -168,16 +155,16 @@ FEC_DEV bool padd_fast(const u32* lp, const u32* lq, pt& o) {
   }
   __builtin_amdgcn_sched_barrier(0);  // keep the loads where they are used (register budget of three waves per SIMD)
   {
-    const fe z2 = ld(lq, 2);
+    const fe z2 = load_coord(lq, TPB, 2);
     z2s = sqr(z2, rr);
     z2c = mul(z2s, z2, rr);
   }
   __builtin_amdgcn_sched_barrier(0);
-  const fe u1 = mul(ld(lp, 0), z2s, rr);
-  const fe u2 = mul(ld(lq, 0), z1s, rr);
+  const fe u1 = mul(load_coord(lp, TPB, 0), z2s, rr);
+  const fe u2 = mul(load_coord(lq, TPB, 0), z1s, rr);
   __builtin_amdgcn_sched_barrier(0);
-  const fe s1 = mul(ld(lp, 1), z2c, rr);
-  const fe s2 = mul(ld(lq, 1), z1c, rr);
+  const fe s1 = mul(load_coord(lp, TPB, 1), z2c, rr);
+  const fe s2 = mul(load_coord(lq, TPB, 1), z1c, rr);
   __builtin_amdgcn_sched_barrier(0);
   rr.m |= lanes_where(u1.w[0] == u2.w[0]);  // u1 == u2 possible: equal points or their negatives
   const fe h = sub(u2, u1, rr);
@@ -187,13 +174,13 @@ FEC_DEV bool padd_fast(const u32* lp, const u32* lq, pt& o) {
   const fe u1h2 = mul(u1, h2, rr);
   o.x = sub(sub(sub(sqr(r, rr), h3, rr), u1h2, rr), u1h2, rr);
   o.y = sub(mul(r, sub(u1h2, o.x, rr), rr), mul(s1, h3, rr), rr);
-  o.z = mul(mul(h, ld(lp, 2), rr), ld(lq, 2), rr);
+  o.z = mul(mul(h, load_coord(lp, TPB, 2), rr), load_coord(lq, TPB, 2), rr);
   return !met(rr);
 }
 
 // secp::pdouble of the point in slot l on the common legs only.  False: some lane needs the exact code.
 FEC_DEV bool pdouble_fast(const u32* l, pt& r) {
-  const pt p = {ld(l, 0), ld(l, 1), ld(l, 2)};
+  const pt p = {load_coord(l, TPB, 0), load_coord(l, TPB, 1), load_coord(l, TPB, 2)};
   in_registers(p.x, p.y);
   in_registers(p.z, 0u);
   if (__builtin_expect(lanes_where(p.z.w[0] == 0u) != 0, 0)) return false;
@@ -219,13 +206,13 @@ template <class Exact>
 FEC_DEV void add_step(const u32* lp, const u32* lq, u32* dst, Exact exact) {
   pt o;
   if (__builtin_expect(!padd_fast(lp, lq, o), 0)) o = exact();
-  st(dst, o);
+  store_pt(dst, TPB, o);
 }
 template <class Exact>
 FEC_DEV void double_step(u32* l, Exact exact) {
   pt o;
   if (__builtin_expect(!pdouble_fast(l, o), 0)) o = exact();
-  st(l, o);
+  store_pt(l, TPB, o);
 }
 
 }  // namespace secp_step

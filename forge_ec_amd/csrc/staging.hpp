@@ -1,6 +1,8 @@
-// staging.hpp -- workgroup shape and the HBM <-> LDS staging helpers shared by all kernels.
+// staging.hpp -- workgroup shape and the HBM <-> LDS staging helpers shared by all kernels (a lane's accesses to its
+// own column of the staged image: point_io.hpp).
 #pragma once
 #include "limbs.hpp"
+#include "point_io.hpp"
 
 namespace fecgpu {
 
@@ -36,14 +38,6 @@ FEC_DEV void stage_out(u32* g, const u32* lds, int valid) {
       *reinterpret_cast<uint4*>(g + (size_t)v * 4) = x;
     }
   }
-}
-FEC_DEV fe load_fe(const u32* l, int stride) {
-  fe a;
-  FEC_UNROLL for (int i = 0; i < 8; ++i) a.w[i] = l[i * stride];
-  return a;
-}
-FEC_DEV void store_fe(u32* l, int stride, const fe& a) {
-  FEC_UNROLL for (int i = 0; i < 8; ++i) l[i * stride] = a.w[i];
 }
 FEC_DEV int block_valid(size_t n) {
   size_t first = (size_t)blockIdx.x * TPB;
