@@ -131,6 +131,25 @@ int main(void) {
          dg3[1][0], dg3[1][1], dg3[1][2], dg3[1][3], st_bip[0], st_bip[1], st_bip[2], st_ecdsa[0], st_ecdsa[1], st_ecdsa[2]);
   ok = ok && dg3[1][0] == 0x2c && dg3[1][1] == 0xf2 && dg3[2][0] == 0xe3 && st_bip[0] == 1 && bsig3[0][63] == 63 && st_bip[1] == 0 &&
        st_bip[2] == 0 && st_ecdsa[0] <= 2 && st_ecdsa[1] <= 2 && st_ecdsa[2] <= 2;
+  /* Ecdsa::<P256, Sha256>::sign from the message -- key check, SHA-256 and the RFC 6979 nonce on the GPU -- equals its
+   * parts: the nonces of fec_rfc6979_k and the digests above through fec_ecdsa_sign */
+  uint64_t esk3[3][4], ek3[3][4], esig3[3][8], esig_parts3[3][8];
+  uint8_t st_k[3], st_msg[3], st_parts[3];
+  for (int i = 0; i < 3; ++i)
+    for (int l = 0; l < 4; ++l) esk3[i][l] = (uint64_t)(7 + 2 * i + l);
+  rc = fec_ecdsa_sign_msg(ctx, FEC_P256, &esk3[0][0], msgs3, off3, 17, &esig3[0][0], st_msg, 3);
+  if (rc == FEC_OK) rc = fec_rfc6979_k(ctx, FEC_P256, &esk3[0][0], msgs3, off3, 17, &ek3[0][0], st_k, 3);
+  if (rc == FEC_OK) rc = fec_ecdsa_sign(ctx, FEC_P256, &esk3[0][0], &dg3[0][0], &ek3[0][0], &esig_parts3[0][0], st_parts, 3);
+  if (rc != FEC_OK) {
+    printf("ECDSA sign from the message failed: %s\n", fec_strerror(rc));
+    return 1;
+  }
+  printf("parity  Ecdsa::<P256, Sha256>::sign(msg) status %u %u %u, r[1] limb 0 %016llx\n", st_msg[0], st_msg[1], st_msg[2],
+         (unsigned long long)esig3[1][0]);
+  for (int i = 0; i < 3; ++i) {
+    ok = ok && st_k[i] == 0 && st_msg[i] == st_parts[i];
+    for (int l = 0; l < 8; ++l) ok = ok && esig3[i][l] == esig_parts3[i][l];
+  }
   /* a single-device ctx has fec_batch_*_dev; the device-resident multi-GPU calls say so */
   const size_t none = 0;
   const uint64_t* no_in[1] = {NULL};

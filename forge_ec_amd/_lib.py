@@ -18,6 +18,7 @@ ABI_SYMBOLS = [
     "fec_batch_mul_fixed_dev", "fec_batch_double_mul_dev", "fec_multi_batch_mul_dev", "fec_multi_batch_mul_fixed_dev", "fec_multi_batch_double_mul_dev", "fec_ctx_set_chunk", "fec_ctx_set_timing",
     "fec_ctx_last_kernel_ms", "fec_measure_peak_mad32", "fec_ctx_device_info", "fec_strerror",
     "fec_sha256", "fec_sha256_dev", "fec_ecdsa_verify_msg", "fec_ecdsa_verify_msg_dev", "fec_bip340_sign", "fec_bip340_sign_dev",
+    "fec_ecdsa_sign_msg", "fec_ecdsa_sign_msg_dev", "fec_rfc6979_k", "fec_rfc6979_k_dev", "fec_debug_rfc6979_k",
 ]
 # include/fecgpu_canon.h: the canonical-math mode (NOT reference parity)
 CANON_ABI_SYMBOLS = [
@@ -195,6 +196,13 @@ def lib():
     L.fec_bip340_sign.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz]
     L.fec_bip340_sign_dev.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz, vp]
     for n in ("fec_sha256", "fec_sha256_dev", "fec_ecdsa_verify_msg", "fec_ecdsa_verify_msg_dev", "fec_bip340_sign", "fec_bip340_sign_dev"):
+        getattr(L, n).restype = ci
+    L.fec_ecdsa_sign_msg.argtypes = [vp, ci, vp, vp, vp, sz, vp, vp, sz]
+    L.fec_ecdsa_sign_msg_dev.argtypes = [vp, ci, vp, vp, vp, sz, vp, vp, sz, vp]
+    L.fec_rfc6979_k.argtypes = [vp, ci, vp, vp, vp, sz, vp, vp, sz]
+    L.fec_rfc6979_k_dev.argtypes = [vp, ci, vp, vp, vp, sz, vp, vp, sz, vp]
+    L.fec_debug_rfc6979_k.argtypes = [vp, ci, vp, vp, vp, vp, sz, vp, vp, sz]
+    for n in ("fec_ecdsa_sign_msg", "fec_ecdsa_sign_msg_dev", "fec_rfc6979_k", "fec_rfc6979_k_dev", "fec_debug_rfc6979_k"):
         getattr(L, n).restype = ci
     L.fec_ctx_set_chunk.argtypes = [vp, sz]
     L.fec_ctx_set_chunk.restype = ci

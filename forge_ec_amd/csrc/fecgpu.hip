@@ -1087,20 +1087,45 @@ int launch_ecdh(fec_ctx* ctx, int curve, const u64* dsk, const u64* dpk, const u
 // Ecdsa::<C, D>::sign for secp256k1 / P-256 after the hash and the nonce (ecdsa.rs:98-211): R = multiply(G, k) by the
 // curve's fixed-base kernel into the stream's scratch -- from the ctx's prefix table under launch_mul's policy (the
 // host-pointer form may build one, a *_dev call only takes one that exists) -- then k_ecdsa_sign_finish (kernels_ecdsa.hip).
+// With `msg` (Ecdsa::<C, Sha256>::sign from the message) one k_rfc6979 pass first (kernels_rfc6979.hip) checks the key,
+// hashes and draws the nonce: h_bytes, k and one decided byte per element are regions of the same work area -- one
+// request for every stage -- and the two stages above run on them unchanged.  k_bad_range_status then writes what that
+// pass decided: status 4 and a zero signature for a bad range (a *_dev call's layout, which nobody has checked), status 5
+// at the retry cap.
 int launch_ecdsa_sign(fec_ctx* ctx, int curve, const u64* dsk, const unsigned char* dd, const u64* dk, u64* dsig,
-                      unsigned char* dstatus, size_t n, void* stream) {
+                      unsigned char* dstatus, size_t n, void* stream, const EcdsaMessages* msg = nullptr) {
   if (n == 0) return FEC_OK;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  u32* rp;
+  u32 *rp, *nonce = nullptr, *digests = nullptr;
+  unsigned char* decided = nullptr;
   WorkArea area;
   area.add(rp, n * 96);
+  if (msg) area.add(nonce, n * 32).add(digests, n * 32).add(decided, n);
   int rc = area.acquire(ctx, st);
   if (rc == FEC_OK) rc = prepare_generator(ctx, curve, st, n);
   if (rc != FEC_OK) return rc;
-  Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_secp_mul + k_ecdsa_sign_finish" : "k_p256_mul_sched + k_ecdsa_sign_finish");
+  Launch L(ctx, stream, curve == FEC_SECP256K1 ? (msg ? "k_rfc6979 + k_secp_mul + k_ecdsa_sign_finish" : "k_secp_mul + k_ecdsa_sign_finish")
+                                               : (msg ? "k_rfc6979 + k_p256_mul_sched + k_ecdsa_sign_finish" : "k_p256_mul_sched + k_ecdsa_sign_finish"));
+  const u32* sk = reinterpret_cast<const u32*>(dsk);
   const u32* k = reinterpret_cast<const u32*>(dk);
+  if (msg) {
+    rfc6979_launch(curve, Rfc6979Io{sk, msg->msgs, msg->off, msg->msg_len, nonce, digests, decided}, rfc6979_curve_order(curve), true, n, L.s);
+    dd = reinterpret_cast<const unsigned char*>(digests);
+    k = nonce;
+  }
   fixed_product(ctx, sched_env(ctx), curve, k, reinterpret_cast<const u32*>(ctx->d_gen[curve]), rp, n, nullptr, L.s);
-  ecdsa_sign_finish_launch(curve, rp, reinterpret_cast<const u32*>(dsk), dd, k, reinterpret_cast<u32*>(dsig), dstatus, n, L.s);
+  ecdsa_sign_finish_launch(curve, rp, sk, dd, k, reinterpret_cast<u32*>(dsig), dstatus, n, L.s);
+  if (msg) bad_range_status_launch(decided, dstatus, n, L.s, reinterpret_cast<u32*>(dsig));
+  return L.done();
+}
+
+// Rfc6979::<C, Sha256>::generate_k per element (kernels_rfc6979.hip): one pass, no work area, no key check.
+int launch_rfc6979(fec_ctx* ctx, int curve, const Rfc6979Order& order, const u64* dsk, const EcdsaMessages& msg, u64* dk,
+                   unsigned char* dstatus, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_rfc6979");
+  rfc6979_launch(curve, Rfc6979Io{reinterpret_cast<const u32*>(dsk), msg.msgs, msg.off, msg.msg_len, reinterpret_cast<u32*>(dk), nullptr, dstatus},
+                 order, false, n, L.s);
   return L.done();
 }
 
@@ -1402,6 +1427,40 @@ int ecdsa_verify_msg_call(fec_ctx* ctx, int curve, const uint8_t* msgs, const ui
                                  (unsigned char*)d[5], m, st, &em);
     });
   });
+}
+
+// Ecdsa::<C, Sha256>::sign from the message (`order` null: out = the signature, 64 bytes per element) and
+// Rfc6979::<C, Sha256>::generate_k alone (out = k, 32 bytes, candidates compared with *order).  Host form: the engine as
+// msg_call uses it, one lane, the chunk's messages in the same two slots.  The keys are secret, and so is k: the staging
+// and the stream scratch (k, h1, R) are cleared on every way out.
+int ecdsa_sign_msg_call(fec_ctx* ctx, int curve, const Rfc6979Order* order, const uint64_t* sk, const uint8_t* msgs, const uint64_t* off,
+                        size_t msg_len, uint64_t* out, uint8_t* status, size_t n) {
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
+  if (!ctx || (n && (!sk || !out || !status))) return FEC_E_ARG;
+  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(sk, 32), ragged(off, 8), secret_output(out, order ? 32 : 64), output(status, 1)};
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[4], size_t cnt, size_t) {
+    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
+    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
+      EcdsaMessages em{nullptr, nullptr, 0, false};
+      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[1]), m, reb, st, em.msgs, em.off, em.msg_len);
+      if (rc != FEC_OK) return rc;
+      if (order) return launch_rfc6979(c, curve, *order, (const u64*)d[0], em, (u64*)d[2], (unsigned char*)d[3], m, st);
+      return launch_ecdsa_sign(c, curve, (const u64*)d[0], nullptr, nullptr, (u64*)d[2], (unsigned char*)d[3], m, st, &em);
+    });
+  });
+}
+// The *_dev forms of the two: one launch sequence on the caller's stream; each lane checks its own message range.
+int ecdsa_sign_msg_dev(fec_ctx* ctx, int curve, bool nonce_only, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                       size_t msg_len, uint64_t* d_out, uint8_t* d_status, size_t n, void* stream) {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || (n && (!d_sk || !d_msg_off || !d_out || !d_status)) || (msg_len && !d_msgs)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
+  if (!aligned16(d_sk) || !aligned16(d_out) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const EcdsaMessages em{d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len, true};
+  if (nonce_only) return launch_rfc6979(ctx, curve, rfc6979_curve_order(curve), d_sk, em, d_out, d_status, n, stream);
+  return launch_ecdsa_sign(ctx, curve, d_sk, nullptr, nullptr, d_out, d_status, n, stream, &em);
 }
 }  // namespace
 
@@ -2596,6 +2655,43 @@ int fec_bip340_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8
   const Bip340Io io{reinterpret_cast<const u32*>(d_private_keys), d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len,
                     reinterpret_cast<u32*>(d_signatures), d_status};
   return launch_bip340_sign(ctx, io, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+// ---- ECDSA signing from the message, RFC 6979 nonces (kernels_rfc6979.hip; helpers above) ----
+
+int fec_ecdsa_sign_msg(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                       uint64_t* sig, uint8_t* status, size_t n) try {
+  return ecdsa_sign_msg_call(ctx, curve, nullptr, sk, msgs, msg_off, msg_len, sig, status, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_ecdsa_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                           size_t msg_len, uint64_t* d_sig, uint8_t* d_status, size_t n, void* stream) try {
+  return ecdsa_sign_msg_dev(ctx, curve, false, d_sk, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                  uint64_t* k, uint8_t* status, size_t n) try {
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
+  const Rfc6979Order order = rfc6979_curve_order(curve);
+  return ecdsa_sign_msg_call(ctx, curve, &order, sk, msgs, msg_off, msg_len, k, status, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                      size_t msg_len, uint64_t* d_k, uint8_t* d_status, size_t n, void* stream) try {
+  return ecdsa_sign_msg_dev(ctx, curve, true, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+// Debug hook: fec_rfc6979_k with the caller's comparison constant instead of the curve's.  At least 2^254, so that a
+// candidate passes with probability 1/4 or more and the retry cap stays out of reach.
+int fec_debug_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* order_override, const uint64_t* sk, const uint8_t* msgs,
+                        const uint64_t* msg_off, size_t msg_len, uint64_t* k, uint8_t* status, size_t n) try {
+  if (!order_override || (order_override[3] >> 62) == 0) return FEC_E_ARG;
+  Rfc6979Order order;
+  for (int i = 0; i < 4; ++i) {
+    order.w[2 * i] = (u32)order_override[i];
+    order.w[2 * i + 1] = (u32)(order_override[i] >> 32);
+  }
+  return ecdsa_sign_msg_call(ctx, curve, &order, sk, msgs, msg_off, msg_len, k, status, n);
 } FEC_ABI_CATCH_STATUS
 
 }  // extern "C"

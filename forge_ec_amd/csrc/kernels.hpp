@@ -177,8 +177,30 @@ void eddsa_verify_msg_finish_launch(const EddsaVerifyWork& w, unsigned char* sta
 // range is bad; status (may be null): 0, or 4 for a bad range
 void sha256_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
                    hipStream_t s);
-// status[i] = 4 where bad[i] != 0 (sha256_launch's status of a pass whose digests went on into a verifier)
-void bad_range_status_launch(const unsigned char* bad, unsigned char* status, size_t n, hipStream_t s);
+// status[i] = bad[i] where bad[i] != 0: the status of a pass whose outputs went on into a verifier or a signer
+// (sha256_launch: 4; rfc6979_launch: 4 or 5).  With `sig` (16 words per element) a bad range's signature is zeroed too.
+void bad_range_status_launch(const unsigned char* bad, unsigned char* status, size_t n, hipStream_t s, u32* sig = nullptr);
+
+// kernels_rfc6979.hip: Rfc6979::<C, Sha256>::generate_k (forge-ec-rng/src/rfc6979.rs:58-181; rfc6979.hpp) per element,
+// the message's own SHA-256 included.  sk: the raw Scalar limbs (8 words); messages as above; k 8 words; h1 (may be
+// null) the 32 bytes of SHA-256(msg) as sha256_launch writes them; status (may be null) 0, 4 for a bad range, 5 for the
+// retry cap -- k and h1 are zero for both.  `order`: the constant a candidate is compared with, 8 little-endian words
+// (rfc6979_curve_order: the one the reference's Scalar::from_bytes uses).  check_key: Ecdsa::sign's key check
+// (ecdsa.rs:101-104) first; a rejected key draws no nonce: k = h1 = 0, status 0 (the signer's finishing pass reports it).
+struct Rfc6979Io {
+  const u32* sk;
+  const unsigned char* msgs;
+  const u64* off;
+  u64 msg_len;
+  u32* k;
+  u32* h1;
+  unsigned char* status;
+};
+struct Rfc6979Order {
+  u32 w[8];
+};
+Rfc6979Order rfc6979_curve_order(int curve);
+void rfc6979_launch(int curve, const Rfc6979Io& io, const Rfc6979Order& order, bool check_key, size_t n, hipStream_t s);
 
 // kernels_schnorr.hip: BipSchnorr::sign (forge-ec-signature/src/schnorr.rs:302-420), the three passes around
 // p = multiply(G, d) and r = multiply(G, k) (24 words per element each).  keys: the 32 private-key bytes per element;

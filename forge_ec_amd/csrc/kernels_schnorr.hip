@@ -1,7 +1,7 @@
 // kernels_schnorr.hip -- the SHA-256 users of the parity-mode surface:
 //   k_sha256          SHA-256 per message (fec_sha256, and the first pass of fec_ecdsa_verify_msg, whose digests
 //                     launch_ecdsa_verify then takes as they are: ecdsa.rs:231-239; k_bad_range_status marks the
-//                     elements whose message range the hash pass refused)
+//                     elements that the hash pass, or the nonce pass of kernels_rfc6979.hip, decided)
 // and BipSchnorr::sign (forge-ec-signature/src/schnorr.rs:302-420), around two fixed-base multiplications by the
 // secp256k1 ladder with the prefix table (fecgpu.hip: launch_bip340_sign):
 //   k_bip340_pre      the message case (307-316); d = Scalar::from_bytes(private_key) (324-334); a decided lane gets
@@ -69,11 +69,18 @@ __global__ __launch_bounds__(TPB) void k_sha256(const unsigned char* __restrict_
   if (status) status[i] = ok ? 0 : 4;
 }
 
-// status[i] = 4 where the hash pass found element i's message range bad (fec_ecdsa_verify_msg_dev)
+// status[i] = bad[i] where the hash pass (k_sha256: 4) or the nonce pass (k_rfc6979: 4 or 5) decided element i
+// (fec_ecdsa_verify_msg_dev, fec_ecdsa_sign_msg*); with `sig`, the signature of a bad range becomes zero
 __global__ __launch_bounds__(TPB) void k_bad_range_status(const unsigned char* __restrict__ bad, unsigned char* __restrict__ status,
-                                                          size_t n) {
+                                                          u32* __restrict__ sig, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
-  if (i < n && bad[i] != 0) status[i] = 4;
+  if (i >= n || bad[i] == 0) return;
+  status[i] = bad[i];
+  if (sig != nullptr && bad[i] == 4) {
+    const u32 zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    store_w8(sig + i * 16, zero);
+    store_w8(sig + i * 16 + 8, zero);
+  }
 }
 
 // The three passes of BipSchnorr::sign: each loads its element, runs its step of bip340.hpp and stores.
@@ -131,8 +138,8 @@ void sha256_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* 
                    hipStream_t s) {
   hipLaunchKernelGGL(k_sha256, dim3(grid(n)), dim3(TPB), 0, s, msgs, off, msg_len, out, status, n);
 }
-void bad_range_status_launch(const unsigned char* bad, unsigned char* status, size_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_bad_range_status, dim3(grid(n)), dim3(TPB), 0, s, bad, status, n);
+void bad_range_status_launch(const unsigned char* bad, unsigned char* status, size_t n, hipStream_t s, u32* sig) {
+  hipLaunchKernelGGL(k_bad_range_status, dim3(grid(n)), dim3(TPB), 0, s, bad, status, sig, n);
 }
 void bip340_pre_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_bip340_pre, dim3(grid(n)), dim3(TPB), 0, s, io, w, n);

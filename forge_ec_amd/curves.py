@@ -545,6 +545,49 @@ class Context:
         _check(self._lib.fec_bip340_sign(self._h, _ptr(k), _ptr(buf), _ptr(off), total, _ptr(sig), _ptr(st), n), "fec_bip340_sign")
         return sig, st
 
+    def ecdsa_sign_msg(self, curve, sk, msgs):
+        """Ecdsa::<C, Sha256>::sign per element FROM THE MESSAGE (ecdsa.rs:98-211), SHA-256 and the RFC 6979 nonce
+        (forge-ec-rng/src/rfc6979.rs:58-181) included: curve 0 (secp256k1) or 1 (P-256); sk (n, 4) raw limbs; msgs a list
+        of n byte strings.  Returns (r (n,4), s (n,4), status (n,) uint8) as ecdsa_sign: 0 Ok, 1 Err(InvalidPrivateKey),
+        2 Err(InvalidScalar), 3 Err(InvalidSignature), 5 the nonce loop gave up (never seen); r = s = one() wherever
+        status != 0.  The reference's signatures, not standard ECDSA; not constant-time -- see include/fecgpu.h."""
+        kk = _u64(sk, 4)
+        buf, off, total = self._messages(msgs)
+        n = kk.shape[0]
+        if len(off) != n + 1:
+            raise ValueError("inputs differ in length")
+        sig = np.zeros((n, 8), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_ecdsa_sign_msg(self._h, curve, _ptr(kk), _ptr(buf), _ptr(off), total, _ptr(sig), _ptr(st), n),
+               "fec_ecdsa_sign_msg")
+        return sig[:, :4].copy(), sig[:, 4:].copy(), st
+
+    def rfc6979_k(self, curve, sk, msgs):
+        """Rfc6979::<C, Sha256>::generate_k per element (forge-ec-rng/src/rfc6979.rs:40-181): sk (n, 4) raw limbs, hashed
+        as they are (no key check); msgs a list of n byte strings.  Returns (k (n,4), status (n,) uint8: 0, or 5 where
+        the loop gave up -- never seen).  The reference's nonces, not RFC 6979 to the letter -- see include/fecgpu.h."""
+        return self._rfc6979(curve, None, sk, msgs)
+
+    def debug_rfc6979_k(self, curve, order_override, sk, msgs):
+        """fec_debug_rfc6979_k: test hook, not part of the reference's surface -- rfc6979_k with candidates compared
+        against order_override (4 limbs, at least 2^254) instead of the curve's order constant."""
+        return self._rfc6979(curve, _u64(order_override, 4), sk, msgs)
+
+    def _rfc6979(self, curve, order, sk, msgs):
+        kk = _u64(sk, 4)
+        buf, off, total = self._messages(msgs)
+        n = kk.shape[0]
+        if len(off) != n + 1:
+            raise ValueError("inputs differ in length")
+        k = np.zeros((n, 4), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8)
+        if order is None:
+            _check(self._lib.fec_rfc6979_k(self._h, curve, _ptr(kk), _ptr(buf), _ptr(off), total, _ptr(k), _ptr(st), n), "fec_rfc6979_k")
+        else:
+            _check(self._lib.fec_debug_rfc6979_k(self._h, curve, _ptr(order), _ptr(kk), _ptr(buf), _ptr(off), total, _ptr(k), _ptr(st), n),
+                   "fec_debug_rfc6979_k")
+        return k, st
+
     def curve25519_mul(self, scalars, points):
         """Curve25519::multiply per element (curve25519.rs:1922-1955): scalars (n, 4) raw Scalar limbs, points (n, 8)
         ProjectivePoint X limbs then Z limbs; returns (n, 8) likewise."""
@@ -681,6 +724,13 @@ class Context:
     def bip340_sign_dev(self, d_private_keys, d_msgs, d_msg_off, msg_len, d_signatures, d_status, n, stream=None):
         _check(self._lib.fec_bip340_sign_dev(self._h, d_private_keys, d_msgs, d_msg_off, msg_len, d_signatures, d_status, n, stream),
                "fec_bip340_sign_dev")
+
+    def ecdsa_sign_msg_dev(self, curve, d_sk, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream=None):
+        _check(self._lib.fec_ecdsa_sign_msg_dev(self._h, curve, d_sk, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream),
+               "fec_ecdsa_sign_msg_dev")
+
+    def rfc6979_k_dev(self, curve, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream=None):
+        _check(self._lib.fec_rfc6979_k_dev(self._h, curve, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream), "fec_rfc6979_k_dev")
 
     def ecdsa_sign_dev(self, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream=None):
         _check(self._lib.fec_ecdsa_sign_dev(self._h, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream), "fec_ecdsa_sign_dev")

@@ -45,6 +45,10 @@
  *   fec_ecdsa_verify_msg  Ecdsa::<C, Sha256>::verify for secp256k1 / P-256 from the message, hash included (ecdsa.rs:213-281)
  *   fec_bip340_sign       BipSchnorr::sign, both hashes included (forge-ec-signature/src/schnorr.rs:302-420; inherent
  *                         Scalar::from_bytes / to_bytes secp256k1.rs:1924-1951, Neg 2466-2488)
+ *   fec_ecdsa_sign_msg    Ecdsa::<C, Sha256>::sign for secp256k1 / P-256 from the message: SHA-256 and the RFC 6979 nonce
+ *                         included (ecdsa.rs:98-211; forge-ec-rng/src/rfc6979.rs:58-181)
+ *   fec_rfc6979_k         Rfc6979::<C, Sha256>::generate_k for secp256k1 / P-256 (forge-ec-rng/src/rfc6979.rs:40-181; trait
+ *                         Scalar::to_bytes / from_bytes secp256k1.rs:2271-2312, p256.rs:1026-1055)
  *   fec_ecdsa_batch_verify   Ecdsa::<C, D>::batch_verify for secp256k1 / P-256 (ecdsa.rs:287-391; scalar Add
  *                         secp256k1.rs:2358-2378, p256.rs:1352-1375)
  *   fec_eddsa_verify_ed25519   Eddsa::<Ed25519, D>::verify / Ed25519::verify after the hash and the decoding
@@ -636,6 +640,47 @@ int fec_bip340_sign(fec_ctx* ctx, const uint8_t* private_keys /* n*32 */, const 
                     size_t msg_len, uint8_t* signatures /* n*64 */, uint8_t* status /* n */, size_t n);
 int fec_bip340_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                         size_t msg_len, uint8_t* d_signatures, uint8_t* d_status, size_t n, void* stream);
+
+/* ---- ECDSA signing FROM THE MESSAGE and its RFC 6979 nonces (ecdsa.rs, forge-ec-rng/src/rfc6979.rs), parity mode ----
+ * Messages, alignment, status 4, multi-device and prefix-table rules: those of the block above.  curve = FEC_SECP256K1 or
+ * FEC_P256, else FEC_E_UNSUPPORTED (Ed25519 has no Ecdsa instance).
+ * fec_rfc6979_k    k[i] = Rfc6979::<C, Sha256>::generate_k(sk[i], msg_i) (rfc6979.rs:40-181, extra_data empty), four raw
+ *   limbs.  As the reference computes it, which is not RFC 6979 to the letter:
+ *     the key bytes are the TRAIT Scalar::to_bytes of the limbs as they are -- big-endian, most significant limb first,
+ *       NOT reduced; there is no key check here (the reference has none): zero and out-of-range limbs are hashed as they are;
+ *     h1 = SHA-256(msg) is taken whole, with no bits2octets reduction;
+ *     the DRBG is HMAC-SHA-256 with V = 01.., K = 00..; K = HMAC_K(V || 00 || x || h1), V = HMAC_K(V),
+ *       K = HMAC_K(V || 01 || x || h1), V = HMAC_K(V); then V = HMAC_K(V) is the candidate;
+ *     a candidate is taken iff the TRAIT Scalar::from_bytes is Some -- big-endian, below the reference's order constant (for
+ *       secp256k1 the one whose two top limbs are swapped, secp256k1.rs:2271-2297, not the true n) -- and it is not zero;
+ *       else K = HMAC_K(V || 00), V = HMAC_K(V) and the next candidate;
+ *     no message is special: "test message" is hashed like any other.
+ *   status[i]: 0; 4 bad message range (_dev form only; k is 0); 5 the loop gave up after 128 retries (k is 0) -- below
+ *   2^-4000 under either curve's constant, so never seen: the bound only keeps any input from spinning a wavefront.
+ * fec_ecdsa_sign_msg   sig[i] = Ecdsa::<C, Sha256>::sign(sk[i], msg_i) (ecdsa.rs:98-211), r then s: the key check of 101-104
+ *   (a rejected key draws no nonce), one pass that hashes the message once -- h1 of the nonce and h_bytes of the signature
+ *   are the same 32 bytes -- and draws k as fec_rfc6979_k does, then exactly the pipeline of fec_ecdsa_sign on that digest
+ *   and nonce, with its status and its (1, 1) substitution: 0 Ok, 1 Err(InvalidPrivateKey), 2 Err(InvalidScalar),
+ *   3 Err(InvalidSignature); plus 4 bad message range (_dev form only; the signature is 0) and 5 the retry cap (the
+ *   signature is (1, 1)).  The reference's signatures, not standard ECDSA.
+ *   SECRETS: sk, k, and h1 where the message is.  The host forms clear their device staging and the stream scratch (k, h1,
+ *   R) on every way out; the _dev forms leave every buffer to the caller (the stream's scratch keeps k, h1 and R until the
+ *   ctx is wiped, fec_ctx_wipe, or destroyed).  NOT constant-time: the number of retries depends on the candidate.
+ * fec_debug_rfc6979_k  test hook, NOT part of the reference's surface: fec_rfc6979_k with candidates compared against
+ *   order_override (four limbs) instead of the curve's constant, so that a test can see elements leave the retry loop after
+ *   different numbers of rounds.  FEC_E_ARG unless order_override >= 2^254 (a candidate then passes with probability
+ *   1/4 or more, and status 5 stays out of reach).  Host form only. */
+int fec_ecdsa_sign_msg(fec_ctx* ctx, fec_curve curve, const uint64_t* sk /* n*4 */, const uint8_t* msgs,
+                       const uint64_t* msg_off /* n+1 */, size_t msg_len, uint64_t* sig /* n*8 */, uint8_t* status /* n */, size_t n);
+int fec_ecdsa_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                           size_t msg_len, uint64_t* d_sig, uint8_t* d_status, size_t n, void* stream);
+int fec_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* sk /* n*4 */, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */,
+                  size_t msg_len, uint64_t* k /* n*4 */, uint8_t* status /* n */, size_t n);
+int fec_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                      size_t msg_len, uint64_t* d_k, uint8_t* d_status, size_t n, void* stream);
+int fec_debug_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* order_override /* 4 */, const uint64_t* sk /* n*4 */,
+                        const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len, uint64_t* k /* n*4 */,
+                        uint8_t* status /* n */, size_t n);
 
 /* Every element-wise host-pointer entry point processes its batch in chunks of `elements` elements
  * (default 2^18), so device staging memory is bounded by two chunks for any n.  Most run them as a

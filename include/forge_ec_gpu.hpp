@@ -683,6 +683,48 @@ inline std::vector<Verify> verify(GpuContext& ctx, const std::vector<AffinePoint
                              st.data(), n));
   return detail::statuses(st);
 }
+// Ecdsa::<C, Sha256>::sign(sks[i], msgs[i]) (ecdsa.rs:98-211), all of it on the GPU (fec_ecdsa_sign_msg): the key check,
+// SHA-256, the RFC 6979 nonce (forge-ec-rng/src/rfc6979.rs:58-181) and the pipeline of sign above.  Every Err comes back
+// as Signature{one, one}; status (optional) as fec_ecdsa_sign's, plus 5 where the nonce loop gave up (never seen).
+template <fec_curve C>
+inline std::vector<Signature<C>> sign_msg(GpuContext& ctx, const std::vector<Scalar<C>>& sks, const std::vector<std::string>& msgs,
+                                          std::vector<uint8_t>* status = nullptr) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "Ecdsa is built for secp256k1 and P-256");
+  const size_t n = sks.size();
+  if (msgs.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  std::vector<uint64_t> sig(n * 8);
+  std::vector<uint8_t> st(n);
+  check(fec_ecdsa_sign_msg(ctx.raw(), C, reinterpret_cast<const uint64_t*>(sks.data()), m.bytes.data(), m.off.data(), m.bytes.size(),
+                           sig.data(), st.data(), n));
+  std::vector<Signature<C>> out(n);
+  for (size_t i = 0; i < n; ++i)
+    for (int l = 0; l < 4; ++l) {
+      out[i].r.raw[l] = sig[i * 8 + l];
+      out[i].s.raw[l] = sig[i * 8 + 4 + l];
+    }
+  if (status) *status = st;
+  return out;
+}
+// Rfc6979::<C, Sha256>::generate_k(sks[i], msgs[i]) (forge-ec-rng/src/rfc6979.rs:40-181) per element (fec_rfc6979_k): no
+// key check, as there.  With order_override (four limbs, at least 2^254) the test hook fec_debug_rfc6979_k, which is not
+// part of the reference's surface.  status (optional): 0, or 5 where the loop gave up (k is 0; never seen).
+template <fec_curve C>
+inline std::vector<Scalar<C>> rfc6979_k(GpuContext& ctx, const std::vector<Scalar<C>>& sks, const std::vector<std::string>& msgs,
+                                        std::vector<uint8_t>* status = nullptr, const uint64_t* order_override = nullptr) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "Ecdsa is built for secp256k1 and P-256");
+  const size_t n = sks.size();
+  if (msgs.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  std::vector<Scalar<C>> k(n);
+  std::vector<uint8_t> st(n);
+  const uint64_t* sk = reinterpret_cast<const uint64_t*>(sks.data());
+  uint64_t* out = reinterpret_cast<uint64_t*>(k.data());
+  check(order_override ? fec_debug_rfc6979_k(ctx.raw(), C, order_override, sk, m.bytes.data(), m.off.data(), m.bytes.size(), out, st.data(), n)
+                       : fec_rfc6979_k(ctx.raw(), C, sk, m.bytes.data(), m.off.data(), m.bytes.size(), out, st.data(), n));
+  if (status) *status = st;
+  return k;
+}
 }  // namespace ecdsa
 namespace schnorr {
 // BipSchnorr::sign(private_keys[i], msgs[i]) (schnorr.rs:302-420), both hashes on the GPU (fec_bip340_sign): the

@@ -96,6 +96,11 @@ extern "C" {
     fn fec_ecdsa_verify_msg_dev(ctx: *mut FecCtx, curve: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r: *const u64, d_s: *const u64, d_pk_xy: *const u64, d_pk_inf: *const u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_bip340_sign(ctx: *mut FecCtx, private_keys: *const u8, msgs: *const u8, msg_off: *const u64, msg_len: usize, signatures: *mut u8, status: *mut u8, n: usize) -> c_int;
     fn fec_bip340_sign_dev(ctx: *mut FecCtx, d_private_keys: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_signatures: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_ecdsa_sign_msg(ctx: *mut FecCtx, curve: c_int, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, sig: *mut u64, status: *mut u8, n: usize) -> c_int;
+    fn fec_ecdsa_sign_msg_dev(ctx: *mut FecCtx, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_sig: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_rfc6979_k(ctx: *mut FecCtx, curve: c_int, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, k: *mut u64, status: *mut u8, n: usize) -> c_int;
+    fn fec_rfc6979_k_dev(ctx: *mut FecCtx, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_k: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_debug_rfc6979_k(ctx: *mut FecCtx, curve: c_int, order_override: *const u64, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, k: *mut u64, status: *mut u8, n: usize) -> c_int;
     fn fec_ctx_set_chunk(ctx: *mut FecCtx, elements: usize) -> c_int;
     fn fec_ctx_set_timing(ctx: *mut FecCtx, enabled: c_int) -> c_int;
     fn fec_ctx_last_kernel_ms(ctx: *mut FecCtx, ms: *mut c_float, kernel_name: *mut *const c_char) -> c_int;
@@ -842,6 +847,67 @@ where
     }).collect())
 }
 
+/// `Ecdsa::<C, Sha256>::sign(sks[i], msgs[i])` per element, ALL of it on the GPU (`fec_ecdsa_sign_msg`): the key check,
+/// SHA-256, the nonce of `Rfc6979::<C, Sha256>::generate_k` and everything `ecdsa_sign_batch` runs there.  The host does
+/// nothing per element but pack the limbs; `ecdsa_sign_batch` stays for other digests.  Every `Err` of `sign_internal`
+/// comes back as `Signature::new(one, one)`, as `sign` returns it; so does the nonce loop's retry cap (status 5, never
+/// seen).  The reference's signatures, not standard ECDSA, and not constant-time: see include/fecgpu.h.
+#[cfg(feature = "signature")]
+pub fn ecdsa_sign_msg_batch<C: GpuCurve>(ctx: &mut GpuContext, sks: &[C::Scalar], msgs: &[&[u8]]) -> Result<Vec<forge_ec_signature::ecdsa::Signature<C>>> {
+    use forge_ec_core::FieldElement;
+    let n = sks.len();
+    if msgs.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let mut kk = pack_scalars::<C>(sks);
+    let (buf, off) = pack_messages(msgs);
+    let (mut sig, mut status) = (vec![0u64; 8 * n], vec![0u8; n]);
+    // SAFETY: kk holds n * 4 limbs, sig n * 8, status n; off holds n + 1 offsets into buf.
+    let rc = check(unsafe { fec_ecdsa_sign_msg(ctx.raw, C::ID, kk.as_ptr(), buf.as_ptr(), off.as_ptr(), buf.len(), sig.as_mut_ptr(), status.as_mut_ptr(), n) });
+    kk.iter_mut().for_each(|w| *w = 0);
+    rc?;
+    let one = <C::Scalar as FieldElement>::one();
+    Ok((0..n).map(|i| match status[i] {
+        0 => forge_ec_signature::ecdsa::Signature::new(C::scalar_from_limbs(limb4(&sig, 2 * i)), C::scalar_from_limbs(limb4(&sig, 2 * i + 1))),
+        _ => forge_ec_signature::ecdsa::Signature::new(one, one),
+    }).collect())
+}
+
+/// `Rfc6979::<C, Sha256>::generate_k(sks[i], msgs[i])` per element on the GPU (`fec_rfc6979_k`;
+/// `forge-ec-rng/src/rfc6979.rs:40-181`): no key check, as there.  `Err` where the nonce loop gave up (status 5: below
+/// 2^-4000 under either curve's constant).  The nonces are secret: the caller clears them.
+pub fn rfc6979_k_batch<C: GpuCurve>(ctx: &mut GpuContext, sks: &[C::Scalar], msgs: &[&[u8]]) -> Result<Vec<C::Scalar>> {
+    rfc6979_k_with::<C>(ctx, None, sks, msgs)
+}
+
+/// Test hook (`fec_debug_rfc6979_k`), not part of the reference's surface: `rfc6979_k_batch` with candidates compared
+/// against `order_override` (four limbs, at least 2^254) instead of the curve's order constant.
+pub fn debug_rfc6979_k_batch<C: GpuCurve>(ctx: &mut GpuContext, order_override: [u64; 4], sks: &[C::Scalar], msgs: &[&[u8]]) -> Result<Vec<C::Scalar>> {
+    rfc6979_k_with::<C>(ctx, Some(order_override), sks, msgs)
+}
+
+fn rfc6979_k_with<C: GpuCurve>(ctx: &mut GpuContext, order: Option<[u64; 4]>, sks: &[C::Scalar], msgs: &[&[u8]]) -> Result<Vec<C::Scalar>> {
+    let n = sks.len();
+    if msgs.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let mut kk = pack_scalars::<C>(sks);
+    let (buf, off) = pack_messages(msgs);
+    let (mut k, mut status) = (vec![0u64; 4 * n], vec![0u8; n]);
+    // SAFETY: kk and k hold n * 4 limbs, status n; off holds n + 1 offsets into buf; an order holds 4 limbs.
+    let rc = check(unsafe {
+        match order {
+            None => fec_rfc6979_k(ctx.raw, C::ID, kk.as_ptr(), buf.as_ptr(), off.as_ptr(), buf.len(), k.as_mut_ptr(), status.as_mut_ptr(), n),
+            Some(o) => fec_debug_rfc6979_k(ctx.raw, C::ID, o.as_ptr(), kk.as_ptr(), buf.as_ptr(), off.as_ptr(), buf.len(), k.as_mut_ptr(), status.as_mut_ptr(), n),
+        }
+    });
+    kk.iter_mut().for_each(|w| *w = 0);
+    rc?;
+    let out = if status.iter().all(|&s| s == 0) { Ok((0..n).map(|i| C::scalar_from_limbs(limb4(&k, i))).collect()) } else { Err(Error::ValidationError) };
+    k.iter_mut().for_each(|w| *w = 0);
+    out
+}
+
 /// `Ecdsa::<C, D>::batch_verify` (`forge-ec-signature/src/ecdsa.rs:287-391`) for `C` = secp256k1 or P-256 from
 /// line 310 on: the caller hashes (`digests[i] = D::digest(msgs[i])`) and draws the weights `a` (302-306) with
 /// the reference's own `Scalar::random`.
@@ -1149,6 +1215,22 @@ pub mod dev {
     /// As [`batch_mul`].
     pub unsafe fn bip340_sign(ctx: &mut GpuContext, d_private_keys: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_signatures: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
         check(fec_bip340_sign_dev(ctx.raw, d_private_keys, d_msgs, d_msg_off, msg_len, d_signatures, d_status, n, stream))
+    }
+
+    /// `fec_ecdsa_sign_msg_dev`.  The stream's scratch keeps k, h1 and R until the ctx is wiped.
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn ecdsa_sign_msg(ctx: &mut GpuContext, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_sig: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_ecdsa_sign_msg_dev(ctx.raw, curve, d_sk, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream))
+    }
+
+    /// `fec_rfc6979_k_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn rfc6979_k(ctx: &mut GpuContext, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_k: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_rfc6979_k_dev(ctx.raw, curve, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream))
     }
 
     /// `fec_schnorr_verify_dev`.
