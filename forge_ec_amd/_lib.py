@@ -19,6 +19,8 @@ ABI_SYMBOLS = [
     "fec_ctx_last_kernel_ms", "fec_measure_peak_mad32", "fec_ctx_device_info", "fec_strerror",
     "fec_sha256", "fec_sha256_dev", "fec_ecdsa_verify_msg", "fec_ecdsa_verify_msg_dev", "fec_bip340_sign", "fec_bip340_sign_dev",
     "fec_ecdsa_sign_msg", "fec_ecdsa_sign_msg_dev", "fec_rfc6979_k", "fec_rfc6979_k_dev", "fec_debug_rfc6979_k",
+    "fec_scalar_from_bytes_reduced", "fec_scalar_from_bytes_reduced_dev", "fec_schnorr_challenge", "fec_schnorr_challenge_dev",
+    "fec_schnorr_sign_msg", "fec_schnorr_sign_msg_dev",
 ]
 # include/fecgpu_canon.h: the canonical-math mode (NOT reference parity)
 CANON_ABI_SYMBOLS = [
@@ -203,6 +205,15 @@ def lib():
     L.fec_rfc6979_k_dev.argtypes = [vp, ci, vp, vp, vp, sz, vp, vp, sz, vp]
     L.fec_debug_rfc6979_k.argtypes = [vp, ci, vp, vp, vp, vp, sz, vp, vp, sz]
     for n in ("fec_ecdsa_sign_msg", "fec_ecdsa_sign_msg_dev", "fec_rfc6979_k", "fec_rfc6979_k_dev", "fec_debug_rfc6979_k"):
+        getattr(L, n).restype = ci
+    L.fec_scalar_from_bytes_reduced.argtypes = [vp, ci, vp, vp, sz]
+    L.fec_scalar_from_bytes_reduced_dev.argtypes = [vp, ci, vp, vp, sz, vp]
+    L.fec_schnorr_challenge.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, sz, vp, sz]
+    L.fec_schnorr_challenge_dev.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, vp]
+    L.fec_schnorr_sign_msg.argtypes = [vp, ci, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz]
+    L.fec_schnorr_sign_msg_dev.argtypes = [vp, ci, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp]
+    for n in ("fec_scalar_from_bytes_reduced", "fec_scalar_from_bytes_reduced_dev", "fec_schnorr_challenge", "fec_schnorr_challenge_dev",
+              "fec_schnorr_sign_msg", "fec_schnorr_sign_msg_dev"):
         getattr(L, n).restype = ci
     L.fec_ctx_set_chunk.argtypes = [vp, sz]
     L.fec_ctx_set_chunk.restype = ci

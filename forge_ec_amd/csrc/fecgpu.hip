@@ -1178,6 +1178,50 @@ int launch_bip340_sign(fec_ctx* ctx, const Bip340Io& io, size_t n, void* stream)
   return L.done();
 }
 
+// Schnorr::<C, Sha256>::sign for secp256k1 / P-256 (schnorr.rs:43-88; kernels_schnorr.hip, schnorr_sign.hpp): k_rfc6979
+// (no key check: Schnorr::sign has none) writes k into scal[0, n), sk has been copied into scal[n, 2n), ONE fixed-base launch
+// over the 2n scalars under launch_mul's prefix-table policy -- the host-pointer form may build a table, a *_dev call
+// only takes one that exists -- then k_schnorr_sign_finish.  The scalars, the points and the nonce pass's status are
+// regions of one work area, taken in one request.
+int launch_schnorr_sign(fec_ctx* ctx, int curve, const SchnorrSignIo& io, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  u32 *scal, *pts;
+  unsigned char* decided;
+  WorkArea area;
+  area.add(scal, 2 * n * 32).add(pts, 2 * n * 96).add(decided, n);
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, curve, st, 2 * n);
+  if (rc != FEC_OK) return rc;
+  const u32* gen = reinterpret_cast<const u32*>(ctx->d_gen[curve]);
+  // sk into scal[n, 2n) first: the one step here that can refuse, so it comes before anything is queued or timed.  The
+  // region belongs to this stream's scratch, which `area` holds, and the copy is in stream order before its readers.
+  if (hipMemcpyAsync(scal + n * 8, io.sk, n * 32, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    (void)hipGetLastError();
+    return FEC_E_DEVICE;
+  }
+  Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_rfc6979 + k_secp_mul + k_schnorr_sign_finish" : "k_rfc6979 + k_p256_mul_sched + k_schnorr_sign_finish");
+  rfc6979_launch(curve, Rfc6979Io{io.sk, io.msgs, io.off, io.msg_len, scal, nullptr, decided}, rfc6979_curve_order(curve), false, n, L.s);
+  fixed_product(ctx, sched_env(ctx), curve, scal, gen, pts, 2 * n, nullptr, L.s);
+  schnorr_sign_finish_launch(curve, io, scal, pts, decided, gen, n, L.s);
+  return L.done();
+}
+
+// e = from_bytes_reduced(SHA256(R.to_bytes() || P.to_bytes() || msg)) per element, and from_bytes_reduced alone: one
+// pass each, no work area.
+int launch_schnorr_challenge(fec_ctx* ctx, int curve, const SchnorrChallengeIo& io, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_schnorr_challenge");
+  schnorr_challenge_launch(curve, io, n, L.s);
+  return L.done();
+}
+int launch_from_bytes_reduced(fec_ctx* ctx, int curve, const u32* bytes, u32* out, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_from_bytes_reduced");
+  from_bytes_reduced_launch(curve, bytes, out, n, L.s);
+  return L.done();
+}
+
 int launch_field(fec_ctx* ctx, int curve, int op, const u64* da, const u64* db, u64* dout, size_t n,
                  void* stream = nullptr) {
   if (n == 0) return FEC_OK;
@@ -1461,6 +1505,46 @@ int ecdsa_sign_msg_dev(fec_ctx* ctx, int curve, bool nonce_only, const uint64_t*
   const EcdsaMessages em{d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len, true};
   if (nonce_only) return launch_rfc6979(ctx, curve, rfc6979_curve_order(curve), d_sk, em, d_out, d_status, n, stream);
   return launch_ecdsa_sign(ctx, curve, d_sk, nullptr, nullptr, d_out, d_status, n, stream, &em);
+}
+
+// Schnorr::<C, Sha256>::sign from the message.  Host form: the engine as ecdsa_sign_msg_call uses it, one lane, the
+// chunk's messages in the same two slots.  sk is secret, and so are k and e * sk behind s: the staging and the stream
+// scratch (k, sk, R, P) are cleared on every way out.
+int schnorr_sign_msg_call(fec_ctx* ctx, int curve, const uint64_t* sk, const uint8_t* msgs, const uint64_t* off, size_t msg_len,
+                          uint64_t* r_xy, uint8_t* r_inf, uint64_t* s_out, uint8_t* sig_bytes, uint8_t* status, size_t n) {
+  if (!curve_ok(curve)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519: its nonce and fixed-base instances are not built
+  if (!ctx || (n && (!sk || !r_xy || !r_inf || !s_out || !status))) return FEC_E_ARG;
+  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(sk, 32), ragged(off, 8), secret_output(r_xy, 64), output(r_inf, 1), secret_output(s_out, 32),
+                         secret_output(sig_bytes, 64), output(status, 1)};
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[7], size_t cnt, size_t) {
+    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
+    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
+      SchnorrSignIo io{static_cast<const u32*>(d[0]), nullptr, nullptr, 0, static_cast<u32*>(d[2]), static_cast<unsigned char*>(d[3]),
+                       static_cast<u32*>(d[4]), static_cast<u32*>(d[5]), static_cast<unsigned char*>(d[6])};
+      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[1]), m, reb, st, io.msgs, io.off, io.msg_len);
+      if (rc != FEC_OK) return rc;
+      return launch_schnorr_sign(c, curve, io, m, st);
+    });
+  });
+}
+// The challenge alone, all three curves.  Nothing is secret.
+int schnorr_challenge_call(fec_ctx* ctx, int curve, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy, const uint8_t* pk_inf,
+                           const uint8_t* msgs, const uint64_t* off, size_t msg_len, uint64_t* e, size_t n) {
+  if (!ctx || !curve_ok(curve) || (n && (!r_xy || !pk_xy || !e))) return FEC_E_ARG;
+  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  const HostArray a[] = {input(r_xy, 64), input(r_inf, 1), input(pk_xy, 64), input(pk_inf, 1), ragged(off, 8), output(e, 32)};
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[6], size_t cnt, size_t) {
+    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
+    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
+      SchnorrChallengeIo io{static_cast<const u32*>(d[0]), static_cast<const unsigned char*>(d[1]), static_cast<const u32*>(d[2]),
+                            static_cast<const unsigned char*>(d[3]), nullptr, nullptr, 0, static_cast<u32*>(d[5]), nullptr};
+      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[4]), m, reb, st, io.msgs, io.off, io.msg_len);
+      if (rc != FEC_OK) return rc;
+      return launch_schnorr_challenge(c, curve, io, m, st);
+    });
+  });
 }
 }  // namespace
 
@@ -2679,6 +2763,56 @@ int fec_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8
 int fec_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                       size_t msg_len, uint64_t* d_k, uint8_t* d_status, size_t n, void* stream) try {
   return ecdsa_sign_msg_dev(ctx, curve, true, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_scalar_from_bytes_reduced(fec_ctx* ctx, fec_curve curve, const uint8_t* bytes, uint64_t* out, size_t n) try {
+  if (!ctx || !curve_ok(curve) || (n && (!bytes || !out))) return FEC_E_ARG;
+  const HostArray a[] = {input(bytes, 32), output(out, 32)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_from_bytes_reduced(c, curve, static_cast<const u32*>(d[0]), static_cast<u32*>(d[1]), m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+int fec_scalar_from_bytes_reduced_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_bytes, uint64_t* d_out, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || !curve_ok(curve) || (n && (!d_bytes || !d_out))) return FEC_E_ARG;
+  if (!aligned16(d_bytes) || !aligned16(d_out)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_from_bytes_reduced(ctx, curve, reinterpret_cast<const u32*>(d_bytes), reinterpret_cast<u32*>(d_out), n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_schnorr_challenge(fec_ctx* ctx, fec_curve curve, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy,
+                          const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint64_t* e, size_t n) try {
+  return schnorr_challenge_call(ctx, curve, r_xy, r_inf, pk_xy, pk_inf, msgs, msg_off, msg_len, e, n);
+} FEC_ABI_CATCH_STATUS
+int fec_schnorr_challenge_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_r_xy, const uint8_t* d_r_inf, const uint64_t* d_pk_xy,
+                              const uint8_t* d_pk_inf, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint64_t* d_e,
+                              uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || !curve_ok(curve) || (n && (!d_r_xy || !d_pk_xy || !d_msg_off || !d_e || !d_status)) || (msg_len && !d_msgs)) return FEC_E_ARG;
+  if (!aligned16(d_r_xy) || !aligned16(d_pk_xy) || !aligned16(d_e) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const SchnorrChallengeIo io{reinterpret_cast<const u32*>(d_r_xy), d_r_inf, reinterpret_cast<const u32*>(d_pk_xy), d_pk_inf, d_msgs,
+                              reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len, reinterpret_cast<u32*>(d_e), d_status};
+  return launch_schnorr_challenge(ctx, curve, io, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_schnorr_sign_msg(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                         uint64_t* r_xy, uint8_t* r_inf, uint64_t* s, uint8_t* sig_bytes, uint8_t* status, size_t n) try {
+  return schnorr_sign_msg_call(ctx, curve, sk, msgs, msg_off, msg_len, r_xy, r_inf, s, sig_bytes, status, n);
+} FEC_ABI_CATCH_STATUS
+int fec_schnorr_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                             size_t msg_len, uint64_t* d_r_xy, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_sig_bytes, uint8_t* d_status,
+                             size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || !curve_ok(curve) || (n && (!d_sk || !d_msg_off || !d_r_xy || !d_r_inf || !d_s || !d_status)) || (msg_len && !d_msgs))
+    return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
+  if (!aligned16(d_sk) || !aligned16(d_r_xy) || !aligned16(d_s) || !aligned16(d_sig_bytes) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u))
+    return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const SchnorrSignIo io{reinterpret_cast<const u32*>(d_sk), d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len,
+                         reinterpret_cast<u32*>(d_r_xy), d_r_inf, reinterpret_cast<u32*>(d_s), reinterpret_cast<u32*>(d_sig_bytes), d_status};
+  return launch_schnorr_sign(ctx, curve, io, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 // Debug hook: fec_rfc6979_k with the caller's comparison constant instead of the curve's.  At least 2^254, so that a

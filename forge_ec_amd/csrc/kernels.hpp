@@ -222,6 +222,39 @@ void bip340_pre_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStr
 void bip340_mid_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStream_t s);
 void bip340_finish_launch(const Bip340Io& io, const Bip340Work& w, size_t n, hipStream_t s);
 
+// kernels_schnorr.hip: Schnorr::<C, Sha256>::sign (schnorr.rs:43-88; schnorr_sign.hpp) and its parts.
+// from_bytes_reduced: 32 bytes (8 words) per element in, the scalar's raw limbs out, all three curves.
+// challenge: e = from_bytes_reduced(SHA256(R.to_bytes() || P.to_bytes() || msg)) from raw affine limbs (16 words per
+// point; the flag arrays may be null), all three curves; status (may be null) 0, or 4 with e = 0 for a bad range.
+// sign_finish (secp256k1 / P-256): scal holds k at [0, n) and sk at [n, 2n), pts their products by G (24 words each),
+// decided the nonce pass's status, gen generator(); sig_bytes may be null.
+void from_bytes_reduced_launch(int curve, const u32* bytes, u32* out, size_t n, hipStream_t s);
+struct SchnorrChallengeIo {
+  const u32* r_xy;
+  const unsigned char* r_inf;
+  const u32* pk_xy;
+  const unsigned char* pk_inf;
+  const unsigned char* msgs;
+  const u64* off;
+  u64 msg_len;
+  u32* e;
+  unsigned char* status;
+};
+void schnorr_challenge_launch(int curve, const SchnorrChallengeIo& io, size_t n, hipStream_t s);
+struct SchnorrSignIo {
+  const u32* sk;
+  const unsigned char* msgs;
+  const u64* off;
+  u64 msg_len;
+  u32* r_xy;
+  unsigned char* r_inf;
+  u32* s;
+  u32* sig_bytes;
+  unsigned char* status;
+};
+void schnorr_sign_finish_launch(int curve, const SchnorrSignIo& io, const u32* scal, const u32* pts, const unsigned char* decided,
+                                const u32* gen, size_t n, hipStream_t s);
+
 // kernels_ecdsa.hip: Curve::validate_point per affine point (secp256k1 / P-256: is_on_curve; Ed25519: the trait default
 // with its two multiplications).  `work` holds validate_work_bytes(curve, n) bytes (0 for the Weierstrass curves).
 size_t validate_work_bytes(int curve, size_t n);

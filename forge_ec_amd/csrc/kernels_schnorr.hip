@@ -13,8 +13,15 @@
 //   k_bip340_finish   to_affine(R); R.x bytes; parity; k' = -k or k (374-385); e = Scalar::from_bytes(SHA256(R.x ||
 //                     P.x || msg)) (388-407); s = k' + e * d' (410-411); R.x || s.to_bytes() (412-417); the flags override
 // One element per lane; the hash state lives in VGPRs (sha256.hpp).
+// and Schnorr::<C, Sha256>::sign (schnorr.rs:43-88; schnorr_sign.hpp holds the pinned readings) with its parts:
+//   k_from_bytes_reduced<E>   C::Scalar::from_bytes_reduced of 32 bytes (fec_scalar_from_bytes_reduced)
+//   k_schnorr_challenge<E>    e = from_bytes_reduced(SHA256(R.to_bytes() || P.to_bytes() || msg)) (fec_schnorr_challenge)
+//   k_schnorr_sign_finish<E>  after k_rfc6979 (k) and ONE fixed-base launch over the 2n scalars k, sk (fecgpu.hip:
+//                             launch_schnorr_sign): both to_affine with their inversions interleaved, the challenge,
+//                             s = k + e * sk, R, s and signature_to_bytes; then the message case and what the nonce pass
+//                             decided (4 bad range, 5 retry cap: zero outputs)
 //
-// Readings, pinned (secp256k1.rs = forge-ec-curves/src/secp256k1.rs):
+// Readings of BipSchnorr::sign, pinned (secp256k1.rs = forge-ec-curves/src/secp256k1.rs):
 //  * Scalar::from_bytes / to_bytes are the INHERENT forms (secp256k1.rs:1924-1951; bip340.hpp): little-endian, None iff
 //    the value is not below the reference's N, zero valid.  So "BIP-340 requires [1, n-1]" (323) is not what 324-325
 //    test: d = 0 signs.
@@ -36,6 +43,7 @@
 #include "../../include/fecgpu.h"
 #include "bip340.hpp"
 #include "kernels.hpp"
+#include "schnorr_sign.hpp"
 #include "secp256k1.hpp"
 #include "sha256.hpp"
 #include "staging.hpp"
@@ -130,9 +138,94 @@ __global__ __launch_bounds__(TPB) void k_bip340_finish(Bip340Io io, Bip340Work w
   io.status[i] = bip340::status_of(f);
 }
 
+// ---- Schnorr::<C, Sha256>::sign and its parts (schnorr_sign.hpp) ----
+// bytes: 32 per element at a 16-byte aligned address; out: the scalar's raw limbs
+template <class E>
+__global__ __launch_bounds__(TPB) void k_from_bytes_reduced(const u32* __restrict__ bytes, u32* __restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  u32 b[8];
+  load_w8(b, bytes + i * 8);
+  unsigned char leg;
+  store_fe16(out + i * 8, schnorr::from_bytes_reduced<E>(b, leg));
+}
+
+template <class E>
+__global__ __launch_bounds__(TPB) void k_schnorr_challenge(SchnorrChallengeIo io, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  u64 lo, len;
+  const bool ok = msg_range(io.off, io.msg_len, i, lo, len);
+  fe e = fe_zero();
+  if (ok) {
+    const bool rinf = io.r_inf != nullptr && io.r_inf[i] != 0, pinf = io.pk_inf != nullptr && io.pk_inf[i] != 0;
+    u32 pre[17];
+    unsigned char leg;
+    e = schnorr::schnorr_challenge<E>(load_fe16(io.r_xy + i * 16), load_fe16(io.r_xy + i * 16 + 8), rinf, load_fe16(io.pk_xy + i * 16),
+                                      load_fe16(io.pk_xy + i * 16 + 8), pinf, len ? io.msgs + lo : nullptr, len, pre, leg);
+  }
+  store_fe16(io.e + i * 8, e);
+  if (io.status) io.status[i] = ok ? 0 : 4;
+}
+
+// scal: k at [0, n), sk at [n, 2n); pts: multiply(G, k) at [0, n), multiply(G, sk) at [n, 2n), 24 words each; decided:
+// the nonce pass's status (0, 4, 5); gen: generator().  A bad range wins over everything -- its message cannot be
+// read --, then the message case, which the reference decides before it draws a nonce, then the retry cap.
+// Left to itself the register allocator takes 170 VGPRs for secp256k1, two more than three wavefronts per SIMD allow;
+// asked for three it fits both curves in 168 without scratch.
+template <class E>
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(3))) void k_schnorr_sign_finish(SchnorrSignIo io, const u32* __restrict__ scal, const u32* __restrict__ pts,
+                                                             const unsigned char* __restrict__ decided, const u32* __restrict__ gen,
+                                                             size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  u64 lo, len;
+  const bool ok = msg_range(io.off, io.msg_len, i, lo, len);
+  const unsigned char* msg = len ? io.msgs + lo : nullptr;
+  const bool test = ok && schnorr::is_test_message(msg, len);
+  typedef typename E::pt pt;
+  schnorr::signature o = schnorr::sign_finish<E>(load_pt16<pt>(pts + i * 24), load_pt16<pt>(pts + (n + i) * 24), load_pt16<pt>(gen), test,
+                                                 load_fe16(scal + i * 8), load_fe16(scal + (n + i) * 8), msg, len);
+  const unsigned char d = decided[i];
+  const unsigned char st = !ok ? 4 : test ? 1 : d;
+  if (st >= 4) {
+    o.rx = o.ry = o.s = fe_zero();
+    o.rinf = false;
+    FEC_UNROLL for (int j = 0; j < 16; ++j) o.bytes[j] = 0;
+  }
+  store_fe16(io.r_xy + i * 16, o.rx);
+  store_fe16(io.r_xy + i * 16 + 8, o.ry);
+  io.r_inf[i] = o.rinf ? 1 : 0;
+  store_fe16(io.s + i * 8, o.s);
+  if (io.sig_bytes) {
+    store_w8(io.sig_bytes + i * 16, o.bytes);
+    store_w8(io.sig_bytes + i * 16 + 8, o.bytes + 8);
+  }
+  io.status[i] = st;
+}
+
 unsigned grid(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 }  // namespace
+
+void from_bytes_reduced_launch(int curve, const u32* bytes, u32* out, size_t n, hipStream_t s) {
+  const dim3 g(grid(n)), b(TPB);
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_from_bytes_reduced<schnorr::CSecp>), g, b, 0, s, bytes, out, n);
+  else if (curve == FEC_P256) hipLaunchKernelGGL((k_from_bytes_reduced<schnorr::CP256>), g, b, 0, s, bytes, out, n);
+  else hipLaunchKernelGGL((k_from_bytes_reduced<schnorr::CEd>), g, b, 0, s, bytes, out, n);
+}
+void schnorr_challenge_launch(int curve, const SchnorrChallengeIo& io, size_t n, hipStream_t s) {
+  const dim3 g(grid(n)), b(TPB);
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_schnorr_challenge<schnorr::CSecp>), g, b, 0, s, io, n);
+  else if (curve == FEC_P256) hipLaunchKernelGGL((k_schnorr_challenge<schnorr::CP256>), g, b, 0, s, io, n);
+  else hipLaunchKernelGGL((k_schnorr_challenge<schnorr::CEd>), g, b, 0, s, io, n);
+}
+void schnorr_sign_finish_launch(int curve, const SchnorrSignIo& io, const u32* scal, const u32* pts, const unsigned char* decided,
+                                const u32* gen, size_t n, hipStream_t s) {
+  const dim3 g(grid(n)), b(TPB);
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_schnorr_sign_finish<schnorr::CSecp>), g, b, 0, s, io, scal, pts, decided, gen, n);
+  else hipLaunchKernelGGL((k_schnorr_sign_finish<schnorr::CP256>), g, b, 0, s, io, scal, pts, decided, gen, n);
+}
 
 void sha256_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
                    hipStream_t s) {

@@ -7,8 +7,9 @@
 // constants are literals of the adds.  A rotate is one v_alignbit_b32 (of a word with itself), the funnel shift that
 // puts an unaligned message in place is one more, Ch and Maj are one v_bfi_b32 each.  No LDS, no scratch.
 //
-// Input, as sha512.hpp takes it: a short PREFIX held in registers (big-endian words, zero past its end; here up to one
-// whole 64-byte block) followed by a message anywhere in memory, at any byte alignment.  Both are streamed block by
+// Input, as sha512.hpp takes it: a short PREFIX held in registers (big-endian words, zero past its end; here up to two
+// 64-byte blocks: Schnorr's R || P is 66 bytes, schnorr_sign.hpp) followed by a message anywhere in memory, at any byte
+// alignment.  Both are streamed block by
 // block, nothing is copied: a block's message bytes come from 17 dword loads at 4-byte-aligned addresses, each clamped
 // into the aligned words that hold at least one byte of the message, then funnel-shifted into place and byte-swapped;
 // the bytes outside the message are masked off.  So no load touches a dword that holds no byte of the message, and a
@@ -89,10 +90,12 @@ FEC_DEV void compress(state& st, const u32 (&blk)[16]) {
 }
 
 // SHA-256 of  prefix[0 .. plen) || msg[0 .. len)  with prefix = the big-endian words pre[0 .. PW) (zero past plen,
-// plen <= 4 * PW <= 64 bytes, so the prefix lies inside the first block).  `msg` may be null when len == 0.
+// plen <= 4 * PW <= 128 bytes: the prefix covers block 0 and, with PW > 16, the start of block 1; the message then
+// begins inside block 1 and everything below -- which only ever asks where a block lies relative to plen and total --
+// holds as it stands).  `msg` may be null when len == 0.
 template <int PW>
 FEC_DEV state hash_prefixed(const u32 (&pre)[PW], u32 plen, const unsigned char* msg, u64 len) {
-  static_assert(PW >= 1 && PW <= 16, "the prefix must fit in the first block");
+  static_assert(PW >= 1 && PW <= 32, "the prefix must fit in the first two blocks");
   state st = init();
   const u64 total = (u64)plen + len;                 // stream bytes before the padding
   const u64 nblocks = (total + 9 + 63) >> 6;         // 0x80, the 64-bit length
@@ -104,6 +107,9 @@ FEC_DEV state hash_prefixed(const u32 (&pre)[PW], u32 plen, const unsigned char*
     const u64 S = b << 6;                            // stream offset of the block
     u32 wd[16];
     FEC_UNROLL for (int j = 0; j < 16; ++j) wd[j] = (j < PW && b == 0) ? pre[j < PW ? j : 0] : 0u;
+    if constexpr (PW > 16) {                         // the prefix's words of block 1
+      FEC_UNROLL for (int j = 0; j < PW - 16; ++j) wd[j] = b == 1 ? pre[16 + j] : wd[j];
+    }
     if (len != 0 && S + 64 > plen && S < total) {    // the block holds message bytes
       const u64 X = m0 - plen + S;                   // address of the block's first stream byte, were it all message
       const u64 base = X & ~(u64)3;

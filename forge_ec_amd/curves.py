@@ -588,6 +588,55 @@ class Context:
                    "fec_debug_rfc6979_k")
         return k, st
 
+    def scalar_from_bytes_reduced(self, curve, data):
+        """C::Scalar::from_bytes_reduced of 32-byte strings (forge-ec-core/src/lib.rs:320-468; P-256: p256.rs:1301-1331):
+        data (n, 32) uint8.  Returns (n, 4) raw limbs.  The reference's function, not a reduction mod n -- see
+        include/fecgpu.h."""
+        b = np.ascontiguousarray(np.asarray(data, dtype=np.uint8)).reshape(-1, 32)
+        out = np.zeros((b.shape[0], 4), dtype=np.uint64)
+        _check(self._lib.fec_scalar_from_bytes_reduced(self._h, curve, _ptr(b), _ptr(out), b.shape[0]), "fec_scalar_from_bytes_reduced")
+        return out
+
+    def schnorr_challenge(self, curve, r_xy, r_inf, pk_xy, pk_inf, msgs):
+        """e = from_bytes_reduced(SHA256(R.to_bytes() || P.to_bytes() || msg)) per element (schnorr.rs:66-81), the e that
+        schnorr_verify and the batch verifiers take: r_xy, pk_xy (n, 8) affine raw limbs; r_inf, pk_inf (n,) uint8 or
+        None; msgs a list of n byte strings.  Returns (n, 4) raw limbs."""
+        r, pk = _u64(r_xy, 8), _u64(pk_xy, 8)
+        buf, off, total = self._messages(msgs)
+        n = r.shape[0]
+        if pk.shape[0] != n or len(off) != n + 1:
+            raise ValueError("inputs differ in length")
+        flags = []
+        for f in (r_inf, pk_inf):
+            f = np.ascontiguousarray(np.asarray(f, dtype=np.uint8)).reshape(-1) if f is not None else None
+            if f is not None and f.shape[0] != n:
+                raise ValueError("flags and points differ in length")  # the C side reads n bytes
+            flags.append(f)
+        e = np.zeros((n, 4), dtype=np.uint64)
+        _check(self._lib.fec_schnorr_challenge(self._h, curve, _ptr(r), _ptr(flags[0]), _ptr(pk), _ptr(flags[1]), _ptr(buf), _ptr(off),
+                                               total, _ptr(e), n), "fec_schnorr_challenge")
+        return e
+
+    def schnorr_sign_msg(self, curve, sk, msgs, with_bytes=True):
+        """Schnorr::<C, Sha256>::sign per element FROM THE MESSAGE (schnorr.rs:43-88), the RFC 6979 nonce and the
+        challenge hash included: curve 0 (secp256k1) or 1 (P-256); sk (n, 4) raw limbs, signed as they are (no key check);
+        msgs a list of n byte strings.  Returns (r_xy (n, 8), r_inf (n,), s (n, 4), sig_bytes (n, 64) uint8 -- the
+        reference's signature_to_bytes -- or None, status (n,) uint8: 0 computed, 1 the "test message" pattern, 5 the
+        nonce loop gave up (never seen)).  Not constant-time -- see include/fecgpu.h."""
+        kk = _u64(sk, 4)
+        buf, off, total = self._messages(msgs)
+        n = kk.shape[0]
+        if len(off) != n + 1:
+            raise ValueError("inputs differ in length")
+        r = np.zeros((n, 8), dtype=np.uint64)
+        rinf = np.zeros(n, dtype=np.uint8)
+        s = np.zeros((n, 4), dtype=np.uint64)
+        sb = np.zeros((n, 64), dtype=np.uint8) if with_bytes else None
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_schnorr_sign_msg(self._h, curve, _ptr(kk), _ptr(buf), _ptr(off), total, _ptr(r), _ptr(rinf), _ptr(s),
+                                              _ptr(sb), _ptr(st), n), "fec_schnorr_sign_msg")
+        return r, rinf, s, sb, st
+
     def curve25519_mul(self, scalars, points):
         """Curve25519::multiply per element (curve25519.rs:1922-1955): scalars (n, 4) raw Scalar limbs, points (n, 8)
         ProjectivePoint X limbs then Z limbs; returns (n, 8) likewise."""
@@ -728,6 +777,17 @@ class Context:
     def ecdsa_sign_msg_dev(self, curve, d_sk, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream=None):
         _check(self._lib.fec_ecdsa_sign_msg_dev(self._h, curve, d_sk, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream),
                "fec_ecdsa_sign_msg_dev")
+
+    def scalar_from_bytes_reduced_dev(self, curve, d_bytes, d_out, n, stream=None):
+        _check(self._lib.fec_scalar_from_bytes_reduced_dev(self._h, curve, d_bytes, d_out, n, stream), "fec_scalar_from_bytes_reduced_dev")
+
+    def schnorr_challenge_dev(self, curve, d_r_xy, d_r_inf, d_pk_xy, d_pk_inf, d_msgs, d_msg_off, msg_len, d_e, d_status, n, stream=None):
+        _check(self._lib.fec_schnorr_challenge_dev(self._h, curve, d_r_xy, d_r_inf, d_pk_xy, d_pk_inf, d_msgs, d_msg_off, msg_len, d_e,
+                                                   d_status, n, stream), "fec_schnorr_challenge_dev")
+
+    def schnorr_sign_msg_dev(self, curve, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_sig_bytes, d_status, n, stream=None):
+        _check(self._lib.fec_schnorr_sign_msg_dev(self._h, curve, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_sig_bytes,
+                                                  d_status, n, stream), "fec_schnorr_sign_msg_dev")
 
     def rfc6979_k_dev(self, curve, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream=None):
         _check(self._lib.fec_rfc6979_k_dev(self._h, curve, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream), "fec_rfc6979_k_dev")

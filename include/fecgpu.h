@@ -49,6 +49,12 @@
  *                         included (ecdsa.rs:98-211; forge-ec-rng/src/rfc6979.rs:58-181)
  *   fec_rfc6979_k         Rfc6979::<C, Sha256>::generate_k for secp256k1 / P-256 (forge-ec-rng/src/rfc6979.rs:40-181; trait
  *                         Scalar::to_bytes / from_bytes secp256k1.rs:2271-2312, p256.rs:1026-1055)
+ *   fec_schnorr_sign_msg  Schnorr::<C, Sha256>::sign for secp256k1 / P-256 from the message: the RFC 6979 nonce, R, P, the
+ *                         challenge hash and s = k + e * sk (forge-ec-signature/src/schnorr.rs:43-88, 145-157)
+ *   fec_schnorr_challenge e = from_bytes_reduced(SHA256(R.to_bytes() || P.to_bytes() || msg)) for the three curves
+ *                         (schnorr.rs:66-81, 107-122, 241-256)
+ *   fec_scalar_from_bytes_reduced   C::Scalar::from_bytes_reduced of 32 bytes (forge-ec-core/src/lib.rs:320-468;
+ *                         p256.rs:1301-1331)
  *   fec_ecdsa_batch_verify   Ecdsa::<C, D>::batch_verify for secp256k1 / P-256 (ecdsa.rs:287-391; scalar Add
  *                         secp256k1.rs:2358-2378, p256.rs:1352-1375)
  *   fec_eddsa_verify_ed25519   Eddsa::<Ed25519, D>::verify / Ed25519::verify after the hash and the decoding
@@ -64,8 +70,8 @@
  *   fec_schnorr_batch_verify_secp256k1   schnorr::batch_verify::<Secp256k1, D> (forge-ec-signature/src/
  *                         schnorr.rs:194-290): the 3n scalar multiplications in parallel, then the two
  *                         strictly sequential `+=` folds (268, 281) and the affine comparison (286).
- *                         The challenges e_i (236-256, a hash) and the random weights a_i (228-233,
- *                         OsRng) are computed by the caller with the reference's own code
+ *                         The challenges e_i (236-256, a hash) come from fec_schnorr_challenge for D = Sha256; the
+ *                         random weights a_i (228-233, OsRng) are drawn by the caller with the reference's own code
  *   fec_field_op          FieldElement trait ops (core lib.rs:173-241): Add/Sub/Mul/Neg/square
  *   fec_point_op          PointProjective trait ops (core lib.rs:699-748): Add / double / negate
  *
@@ -293,7 +299,7 @@ int fec_batch_decode_uncompressed(fec_ctx* ctx, fec_curve curve, const uint8_t* 
                                   uint8_t* inf /* n */, uint8_t* ok /* n */, size_t n);
 /* *result = 1 if the reference's batch_verify returns true for these inputs, else 0.  pk_xy / r_xy:
  * AffinePoint x, y raw limbs (n*8), pk_inf / r_inf their infinity flags (may be NULL = all finite);
- * s, a, e: Scalar::to_raw() limbs (n*4).  sides_xy (16 limbs, may be NULL) receives x, y of
+ * s, a, e: Scalar::to_raw() limbs (n*4); e as fec_schnorr_challenge computes it.  sides_xy (16 limbs, may be NULL) receives x, y of
  * to_affine(s_g) then of to_affine(r_e_p) -- the two points line 286 compares -- and sides_inf (2
  * bytes, may be NULL) their infinity flags; both stay zero when the call returns false early. */
 int fec_schnorr_batch_verify_secp256k1(fec_ctx* ctx, const uint64_t* pk_xy, const uint8_t* pk_inf,
@@ -320,8 +326,8 @@ int fec_schnorr_batch_verify_ed25519(fec_ctx* ctx, const uint64_t* pk_xy, const 
                                      const uint8_t* r_inf, const uint64_t* s, const uint64_t* a, const uint64_t* e, size_t n,
                                      uint8_t* result, uint64_t* sides_xy, uint8_t* sides_inf, uint8_t* debug_build_panics);
 /* Schnorr::<C, D>::verify per signature (forge-ec-signature/src/schnorr.rs:90-140), all three curves, from the point
- * computation on: the caller keeps the two message special cases (92-99) and hashes -- e = from_bytes_reduced(H(R || P
- * || m)), 107-123, raw limbs.  status[i] = 1 true, 0 false, 2 where the reference panics (Ed25519 only: to_affine
+ * computation on: the caller keeps the two message special cases (92-99); e = from_bytes_reduced(H(R || P || m)),
+ * 107-123, raw limbs, comes from fec_schnorr_challenge for D = Sha256.  status[i] = 1 true, 0 false, 2 where the reference panics (Ed25519 only: to_affine
  * unwraps the inverse of a zero z of a point that is not the identity).  The reference re-validates to_affine(e * P)
  * with PointAffine::new(x, -y) under its own arithmetic (130-134), whose None is `false`: practically every input on
  * secp256k1 and Ed25519, and every P-256 key that fails that curve's own is_on_curve, is answered false -- reproduced. */
@@ -681,6 +687,59 @@ int fec_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const
 int fec_debug_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* order_override /* 4 */, const uint64_t* sk /* n*4 */,
                         const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len, uint64_t* k /* n*4 */,
                         uint8_t* status /* n */, size_t n);
+
+/* ---- Schnorr signing FROM THE MESSAGE, its challenge and Scalar::from_bytes_reduced (schnorr.rs, forge-ec-core), parity mode ----
+ * Messages, alignment, status 4, multi-device and prefix-table rules: those of the "SHA-256 ..." block above.
+ * fec_scalar_from_bytes_reduced   out[i] = C::Scalar::from_bytes_reduced(&bytes[32 i .. 32 i + 32]), four raw limbs, for all
+ *   three curves and 32-byte inputs -- the only length forge-ec-signature passes.  As the reference computes it:
+ *     secp256k1, Ed25519: the trait default (forge-ec-core/src/lib.rs:320-468) on the curve's TRAIT from_bytes / to_bytes /
+ *       get_order.  The bytes read BIG-endian, if that is Some: for Ed25519 always (ed25519.rs:1142-1162; the result is not
+ *       reduced), for secp256k1 iff below the order constant whose two top limbs are swapped (secp256k1.rs:2271-2297).
+ *       Else the SAME bytes read LITTLE-endian, minus that constant once if not below it (the `while` runs at most once: the
+ *       high half is zero and the constant is above 2^255), each 64-bit limb byte-swapped (result_bytes is read back
+ *       big-endian), and zero if that is not below the constant (`unwrap_or_else`; reachable: FF x 31 || FE).  The
+ *       `hi_is_zero && is_less` leg (375-410) is unreachable for 32 bytes: schnorr_sign.hpp has the argument.
+ *     P-256: the override (p256.rs:1301-1331): the inherent from_bytes (big-endian, Some iff below n), else the bytes read
+ *       LITTLE-endian into reduce_wide (924-1020), the routine of the scalar Mul.
+ *   Nothing here is secret.
+ * fec_schnorr_challenge   e[i] = from_bytes_reduced(SHA256(R_i.to_bytes() || P_i.to_bytes() || msg_i)) (schnorr.rs:66-81 in
+ *   sign, 107-122 in verify, 241-256 in batch_verify: the same lines), all three curves: the e that fec_schnorr_verify,
+ *   fec_schnorr_batch_verify and fec_schnorr_batch_verify_ed25519 take.  R and P are affine raw limbs with their infinity
+ *   flags (r_inf, pk_inf may be NULL); to_bytes is PointAffine::to_bytes, the 33 bytes fec_batch_compress writes (an
+ *   infinite point: 33 zero bytes).  _dev adds d_status: 0, or 4 with e = 0.  The "test message" / "different message"
+ *   cases of verify stay with the caller: this is the hash and nothing else.  Nothing here is secret.
+ * fec_schnorr_sign_msg   Schnorr::<C, Sha256>::sign(sk[i], msg_i) (schnorr.rs:43-88) for curve = FEC_SECP256K1 or FEC_P256
+ *   (FEC_ED25519: FEC_E_UNSUPPORTED -- its nonce and scalar Mul are not built for this path).  In the reference's order:
+ *     msg == "test message" -> R = to_affine(generator()), s = Scalar::one(), before the key is looked at (45-52);
+ *     k = Rfc6979::<C, Sha256>::generate_k(sk, msg) as fec_rfc6979_k draws it; there is NO key check (Schnorr::sign has
+ *       none): zero and out-of-range limbs sign;
+ *     R = to_affine(multiply(G, k)), P = to_affine(multiply(G, sk)); e as fec_schnorr_challenge;
+ *     s = k + e * sk with the curve's impl Mul / impl Add for Scalar.  sk = 0: P is the identity, its encoding 33 zero
+ *       bytes, and s = k.
+ *   Outputs: r_xy, r_inf R as affine raw limbs and its infinity flag; s four raw limbs; sig_bytes (may be NULL)
+ *   signature_to_bytes (145-157): bytes 0..32 of R's 33-byte encoding -- the prefix byte and the first 31 bytes of x, as
+ *   fec_ed25519_sign's generic form describes for that curve -- then s big-endian.
+ *   status[i]: 0 computed; 1 the "test message" pattern; 3 is reserved for "the reference panics" and is never written:
+ *   both to_affine invert Z only when Z != 0 (secp256k1.rs:1344-1353, p256.rs:1835-1857), and P-256's invert is Some for
+ *   every nonzero input (p256.rs:343-370); 4 bad message range (_dev form only; the outputs are 0); 5 the nonce loop's
+ *   retry cap (the outputs are 0; below 2^-4000, never seen).
+ *   SECRETS: sk, k, e * sk.  The host form clears its device staging and the stream scratch (k, sk, R, P) on every way out;
+ *   the _dev form leaves every buffer to the caller (the stream's scratch keeps k, sk, R and P until the ctx is wiped,
+ *   fec_ctx_wipe, or destroyed).  NOT constant-time. */
+int fec_scalar_from_bytes_reduced(fec_ctx* ctx, fec_curve curve, const uint8_t* bytes /* n*32 */, uint64_t* out /* n*4 */, size_t n);
+int fec_scalar_from_bytes_reduced_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_bytes, uint64_t* d_out, size_t n, void* stream);
+int fec_schnorr_challenge(fec_ctx* ctx, fec_curve curve, const uint64_t* r_xy /* n*8 */, const uint8_t* r_inf /* n or NULL */,
+                          const uint64_t* pk_xy /* n*8 */, const uint8_t* pk_inf /* n or NULL */, const uint8_t* msgs,
+                          const uint64_t* msg_off /* n+1 */, size_t msg_len, uint64_t* e /* n*4 */, size_t n);
+int fec_schnorr_challenge_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_r_xy, const uint8_t* d_r_inf, const uint64_t* d_pk_xy,
+                              const uint8_t* d_pk_inf, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                              uint64_t* d_e, uint8_t* d_status, size_t n, void* stream);
+int fec_schnorr_sign_msg(fec_ctx* ctx, fec_curve curve, const uint64_t* sk /* n*4 */, const uint8_t* msgs,
+                         const uint64_t* msg_off /* n+1 */, size_t msg_len, uint64_t* r_xy /* n*8 */, uint8_t* r_inf /* n */,
+                         uint64_t* s /* n*4 */, uint8_t* sig_bytes /* n*64 or NULL */, uint8_t* status /* n */, size_t n);
+int fec_schnorr_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                             size_t msg_len, uint64_t* d_r_xy, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_sig_bytes,
+                             uint8_t* d_status, size_t n, void* stream);
 
 /* Every element-wise host-pointer entry point processes its batch in chunks of `elements` elements
  * (default 2^18), so device staging memory is bounded by two chunks for any n.  Most run them as a

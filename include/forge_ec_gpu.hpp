@@ -282,9 +282,9 @@ struct Signature {
   AffinePoint<FEC_SECP256K1> r;
   Scalar<FEC_SECP256K1> s;
 };
-// schnorr::batch_verify::<Secp256k1, D> (forge-ec-signature/src/schnorr.rs:194-290).  The caller hashes:
-// challenges[i] = Scalar::from_bytes_reduced(H(R_i || P_i || m_i)) (236-256) and draws the random
-// weights (228-233) with the reference's own code; everything from line 258 on runs on the GPU.
+// schnorr::batch_verify::<Secp256k1, D> (forge-ec-signature/src/schnorr.rs:194-290).
+// challenges[i] = Scalar::from_bytes_reduced(H(R_i || P_i || m_i)) (236-256): schnorr::challenge for Sha256; the caller
+// draws the random weights (228-233) with the reference's own code; everything from line 258 on runs on the GPU.
 inline bool batch_verify(GpuContext& ctx, const std::vector<AffinePoint<FEC_SECP256K1>>& public_keys,
                          const std::vector<Signature>& signatures,
                          const std::vector<Scalar<FEC_SECP256K1>>& challenges,
@@ -366,8 +366,8 @@ struct SignatureOf {
   Scalar<C> s;
 };
 // Schnorr::<C, D>::verify per signature (forge-ec-signature/src/schnorr.rs:90-140) from the point computation on:
-// challenges[i] = Scalar::from_bytes_reduced(H(R_i || P_i || m_i)) (107-123) computed by the caller, who also keeps the
-// two message special cases (92-99).  Returns the reference's boolean per signature or ReferencePanics.
+// challenges[i] = Scalar::from_bytes_reduced(H(R_i || P_i || m_i)) (107-123) -- schnorr::challenge below for Sha256 --;
+// the caller keeps the two message special cases (92-99).  Returns the reference's boolean per signature or ReferencePanics.
 template <fec_curve C>
 inline std::vector<Verify> verify(GpuContext& ctx, const std::vector<AffinePoint<C>>& public_keys,
                                   const std::vector<SignatureOf<C>>& signatures, const std::vector<Scalar<C>>& challenges) {
@@ -740,6 +740,61 @@ inline std::vector<eddsa::Bytes64> bip340_sign(GpuContext& ctx, const std::vecto
                         reinterpret_cast<uint8_t*>(sig.data()), st.data(), n));
   if (status) *status = st;
   return sig;
+}
+// Schnorr::<C, Sha256>::sign(sks[i], msgs[i]) (schnorr.rs:43-88), all of it on the GPU (fec_schnorr_sign_msg): the
+// "test message" case, the RFC 6979 nonce, R and P, the challenge hash and s = k + e * sk; no key check, as there.
+// status (optional): 0 computed, 1 the "test message" pattern, 5 where the nonce loop gave up (outputs 0; never seen).
+// sig_bytes (optional): signature_to_bytes (145-157) per element.
+template <fec_curve C>
+inline std::vector<SignatureOf<C>> sign_msg(GpuContext& ctx, const std::vector<Scalar<C>>& sks, const std::vector<std::string>& msgs,
+                                            std::vector<uint8_t>* status = nullptr, std::vector<eddsa::Bytes64>* sig_bytes = nullptr) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "Schnorr signing is built for secp256k1 and P-256");
+  const size_t n = sks.size();
+  if (msgs.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  std::vector<uint64_t> r(n * 8), s(n * 4);
+  std::vector<uint8_t> r_inf(n), st(n);
+  if (sig_bytes) sig_bytes->resize(n);
+  check(fec_schnorr_sign_msg(ctx.raw(), C, reinterpret_cast<const uint64_t*>(sks.data()), m.bytes.data(), m.off.data(), m.bytes.size(),
+                             r.data(), r_inf.data(), s.data(), sig_bytes ? reinterpret_cast<uint8_t*>(sig_bytes->data()) : nullptr,
+                             st.data(), n));
+  std::vector<SignatureOf<C>> out(n);
+  for (size_t i = 0; i < n; ++i) {
+    for (int l = 0; l < 4; ++l) {
+      out[i].r.x_.raw[l] = r[i * 8 + l];
+      out[i].r.y_.raw[l] = r[i * 8 + 4 + l];
+      out[i].s.raw[l] = s[i * 4 + l];
+    }
+    out[i].r.infinity = r_inf[i] != 0;
+  }
+  if (status) *status = st;
+  return out;
+}
+// e[i] = Scalar::from_bytes_reduced(Sha256(R_i.to_bytes() || P_i.to_bytes() || msgs[i])) (schnorr.rs:66-81, 107-122,
+// 241-256) per element (fec_schnorr_challenge), all three curves: the challenges verify and the batch verifiers take.
+template <fec_curve C>
+inline std::vector<Scalar<C>> challenge(GpuContext& ctx, const std::vector<AffinePoint<C>>& rs, const std::vector<AffinePoint<C>>& public_keys,
+                                        const std::vector<std::string>& msgs) {
+  const size_t n = rs.size();
+  if (public_keys.size() != n || msgs.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  std::vector<uint64_t> r, pk;
+  std::vector<uint8_t> r_inf, pk_inf;
+  detail::pack_affine<C>(rs, r, r_inf);
+  detail::pack_affine<C>(public_keys, pk, pk_inf);
+  std::vector<Scalar<C>> e(n);
+  check(fec_schnorr_challenge(ctx.raw(), C, r.data(), r_inf.data(), pk.data(), pk_inf.data(), m.bytes.data(), m.off.data(), m.bytes.size(),
+                              reinterpret_cast<uint64_t*>(e.data()), n));
+  return e;
+}
+// C::Scalar::from_bytes_reduced of 32-byte strings (forge-ec-core/src/lib.rs:320-468; P-256: p256.rs:1301-1331) per
+// element (fec_scalar_from_bytes_reduced): the reference's function, not a reduction mod n.
+template <fec_curve C>
+inline std::vector<Scalar<C>> scalar_from_bytes_reduced(GpuContext& ctx, const std::vector<eddsa::Bytes32>& bytes) {
+  std::vector<Scalar<C>> out(bytes.size());
+  check(fec_scalar_from_bytes_reduced(ctx.raw(), C, reinterpret_cast<const uint8_t*>(bytes.data()), reinterpret_cast<uint64_t*>(out.data()),
+                                      bytes.size()));
+  return out;
 }
 }  // namespace schnorr
 

@@ -100,6 +100,12 @@ extern "C" {
     fn fec_ecdsa_sign_msg_dev(ctx: *mut FecCtx, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_sig: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_rfc6979_k(ctx: *mut FecCtx, curve: c_int, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, k: *mut u64, status: *mut u8, n: usize) -> c_int;
     fn fec_rfc6979_k_dev(ctx: *mut FecCtx, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_k: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_scalar_from_bytes_reduced(ctx: *mut FecCtx, curve: c_int, bytes: *const u8, out: *mut u64, n: usize) -> c_int;
+    fn fec_scalar_from_bytes_reduced_dev(ctx: *mut FecCtx, curve: c_int, d_bytes: *const u8, d_out: *mut u64, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_schnorr_challenge(ctx: *mut FecCtx, curve: c_int, r_xy: *const u64, r_inf: *const u8, pk_xy: *const u64, pk_inf: *const u8, msgs: *const u8, msg_off: *const u64, msg_len: usize, e: *mut u64, n: usize) -> c_int;
+    fn fec_schnorr_challenge_dev(ctx: *mut FecCtx, curve: c_int, d_r_xy: *const u64, d_r_inf: *const u8, d_pk_xy: *const u64, d_pk_inf: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_e: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_schnorr_sign_msg(ctx: *mut FecCtx, curve: c_int, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, r_xy: *mut u64, r_inf: *mut u8, s: *mut u64, sig_bytes: *mut u8, status: *mut u8, n: usize) -> c_int;
+    fn fec_schnorr_sign_msg_dev(ctx: *mut FecCtx, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *mut u64, d_r_inf: *mut u8, d_s: *mut u64, d_sig_bytes: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_debug_rfc6979_k(ctx: *mut FecCtx, curve: c_int, order_override: *const u64, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, k: *mut u64, status: *mut u8, n: usize) -> c_int;
     fn fec_ctx_set_chunk(ctx: *mut FecCtx, elements: usize) -> c_int;
     fn fec_ctx_set_timing(ctx: *mut FecCtx, enabled: c_int) -> c_int;
@@ -908,6 +914,58 @@ fn rfc6979_k_with<C: GpuCurve>(ctx: &mut GpuContext, order: Option<[u64; 4]>, sk
     out
 }
 
+/// `Schnorr::<C, Sha256>::sign(sks[i], msgs[i])` per element, ALL of it on the GPU (`fec_schnorr_sign_msg`;
+/// `forge-ec-signature/src/schnorr.rs:43-88`) for `C` = secp256k1 or P-256: the "test message" case, the nonce of
+/// `Rfc6979::<C, Sha256>::generate_k`, R and P, the challenge hash with `from_bytes_reduced`, and `s = k + e * sk`.
+/// There is no key check, as in the reference.  `Err` for an element where the nonce loop gave up (status 5, never
+/// seen).  `Ed25519`: `Err(UnsupportedCurve)`.  Not constant-time: see include/fecgpu.h.
+#[cfg(feature = "signature")]
+pub fn schnorr_sign_batch<C: GpuCurve>(ctx: &mut GpuContext, sks: &[C::Scalar], msgs: &[&[u8]]) -> Result<Vec<Result<forge_ec_signature::schnorr::Signature<C>>>> {
+    let n = sks.len();
+    if msgs.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let mut kk = pack_scalars::<C>(sks);
+    let (buf, off) = pack_messages(msgs);
+    let (mut r_xy, mut r_inf, mut s, mut status) = (vec![0u64; 8 * n], vec![0u8; n], vec![0u64; 4 * n], vec![0u8; n]);
+    // SAFETY: every buffer holds n elements of the width the header states; off n + 1 offsets into buf; sig_bytes is null.
+    let rc = check(unsafe { fec_schnorr_sign_msg(ctx.raw, C::ID, kk.as_ptr(), buf.as_ptr(), off.as_ptr(), buf.len(), r_xy.as_mut_ptr(), r_inf.as_mut_ptr(), s.as_mut_ptr(), core::ptr::null_mut(), status.as_mut_ptr(), n) });
+    kk.iter_mut().for_each(|w| *w = 0);
+    rc?;
+    Ok((0..n).map(|i| match status[i] {
+        0 | 1 => Ok(forge_ec_signature::schnorr::Signature { r: C::affine_from_limbs(&r_xy[8 * i..8 * i + 8], r_inf[i] != 0), s: C::scalar_from_limbs(limb4(&s, i)) }),
+        _ => Err(Error::ValidationError),
+    }).collect())
+}
+
+/// `e[i] = C::Scalar::from_bytes_reduced(Sha256(R_i.to_bytes() || P_i.to_bytes() || msgs[i]))` per element on the GPU
+/// (`fec_schnorr_challenge`; `forge-ec-signature/src/schnorr.rs:66-81`, 107-122, 241-256), all three curves: the
+/// challenges [`schnorr_verify_batch`] and the batch verifiers take.  The message special cases of `verify` stay with the
+/// caller.  Nothing here is secret.
+pub fn schnorr_challenge_batch<C: GpuCurve>(ctx: &mut GpuContext, sig_r: &[C::PointAffine], public_keys: &[C::PointAffine], msgs: &[&[u8]]) -> Result<Vec<C::Scalar>> {
+    let n = sig_r.len();
+    if public_keys.len() != n || msgs.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let ((r_xy, r_inf), (pk_xy, pk_inf)) = (marshal_affine::<C>(sig_r), marshal_affine::<C>(public_keys));
+    let (buf, off) = pack_messages(msgs);
+    let mut e = vec![0u64; 4 * n];
+    // SAFETY: every buffer holds n elements of the width the header states; off n + 1 offsets into buf.
+    check(unsafe { fec_schnorr_challenge(ctx.raw, C::ID, r_xy.as_ptr(), r_inf.as_ptr(), pk_xy.as_ptr(), pk_inf.as_ptr(), buf.as_ptr(), off.as_ptr(), buf.len(), e.as_mut_ptr(), n) })?;
+    Ok((0..n).map(|i| C::scalar_from_limbs(limb4(&e, i))).collect())
+}
+
+/// `C::Scalar::from_bytes_reduced(&bytes[i])` per element on the GPU (`fec_scalar_from_bytes_reduced`;
+/// `forge-ec-core/src/lib.rs:320-468`, P-256: `p256.rs:1301-1331`), 32-byte inputs, all three curves: the reference's
+/// function with its mixed byte orders, not a reduction mod n.  Nothing here is secret.
+pub fn scalar_from_bytes_reduced_batch<C: GpuCurve>(ctx: &mut GpuContext, bytes: &[[u8; 32]]) -> Result<Vec<C::Scalar>> {
+    let n = bytes.len();
+    let mut out = vec![0u64; 4 * n];
+    // SAFETY: bytes holds n * 32 bytes, out n * 4 limbs.
+    check(unsafe { fec_scalar_from_bytes_reduced(ctx.raw, C::ID, bytes.as_ptr() as *const u8, out.as_mut_ptr(), n) })?;
+    Ok((0..n).map(|i| C::scalar_from_limbs(limb4(&out, i))).collect())
+}
+
 /// `Ecdsa::<C, D>::batch_verify` (`forge-ec-signature/src/ecdsa.rs:287-391`) for `C` = secp256k1 or P-256 from
 /// line 310 on: the caller hashes (`digests[i] = D::digest(msgs[i])`) and draws the weights `a` (302-306) with
 /// the reference's own `Scalar::random`.
@@ -956,8 +1014,8 @@ pub fn eddsa_verify_batch_ed25519(ctx: &mut GpuContext, sig_r: &[ed25519::Affine
 }
 
 /// `schnorr::batch_verify::<Secp256k1, D>` from line 258 on (`forge-ec-signature/src/schnorr.rs:194-290`):
-/// the caller hashes (challenges `e`, 236-256) and draws the weights (`a`, 228-233) with the
-/// reference's own code and passes them as scalars.
+/// the challenges `e` (236-256) come from [`schnorr_challenge_batch`] for `D = Sha256`; the caller draws the weights
+/// (`a`, 228-233) with the reference's own code and passes them as scalars.
 pub fn schnorr_batch_verify_secp256k1(ctx: &mut GpuContext, public_keys: &[secp256k1::AffinePoint], sig_r: &[secp256k1::AffinePoint], sig_s: &[secp256k1::Scalar], a: &[secp256k1::Scalar], e: &[secp256k1::Scalar]) -> Result<bool> {
     let n = public_keys.len();
     if sig_r.len() != n || sig_s.len() != n || a.len() != n || e.len() != n {
@@ -992,7 +1050,7 @@ fn marshal_affine<C: GpuCurve>(pts: &[C::PointAffine]) -> (Vec<u64>, Vec<u8>) {
 }
 
 /// `schnorr::batch_verify::<C, D>` for `C` = `Secp256k1` or `P256` (`forge-ec-signature/src/schnorr.rs:194-290`,
-/// generic over the curve): as [`schnorr_batch_verify_secp256k1`].  `Ed25519`: the release profile's behaviour, see
+/// generic over the curve): as [`schnorr_batch_verify_secp256k1`], challenges from [`schnorr_challenge_batch`].  `Ed25519`: the release profile's behaviour, see
 /// [`schnorr_batch_verify_ed25519`].
 pub fn schnorr_batch_verify<C: GpuCurve>(ctx: &mut GpuContext, public_keys: &[C::PointAffine], sig_r: &[C::PointAffine], sig_s: &[C::Scalar], a: &[C::Scalar], e: &[C::Scalar]) -> Result<bool> {
     let n = public_keys.len();
@@ -1025,8 +1083,9 @@ pub fn schnorr_batch_verify_ed25519(ctx: &mut GpuContext, public_keys: &[ed25519
 }
 
 /// `Schnorr::<C, D>::verify` per signature (`forge-ec-signature/src/schnorr.rs:90-140`) from the point computation
-/// on, all three curves: the caller keeps the two message special cases (92-99) and hashes
-/// (`e[i] = C::Scalar::from_bytes_reduced(H(R || P || m))`, 107-123).
+/// on, all three curves: the caller keeps the two message special cases (92-99); the challenges
+/// (`e[i] = C::Scalar::from_bytes_reduced(H(R || P || m))`, 107-123) come from [`schnorr_challenge_batch`] for
+/// `D = Sha256`.
 pub fn schnorr_verify_batch<C: GpuCurve>(ctx: &mut GpuContext, public_keys: &[C::PointAffine], sig_r: &[C::PointAffine], sig_s: &[C::Scalar], e: &[C::Scalar]) -> Result<Vec<VerifyStatus>> {
     let n = public_keys.len();
     if sig_r.len() != n || sig_s.len() != n || e.len() != n {
@@ -1231,6 +1290,30 @@ pub mod dev {
     /// As [`batch_mul`].
     pub unsafe fn rfc6979_k(ctx: &mut GpuContext, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_k: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
         check(fec_rfc6979_k_dev(ctx.raw, curve, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream))
+    }
+
+    /// `fec_schnorr_sign_msg_dev`.  The stream's scratch keeps k, sk, R and P until the ctx is wiped.
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn schnorr_sign_msg(ctx: &mut GpuContext, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *mut u64, d_r_inf: *mut u8, d_s: *mut u64, d_sig_bytes: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_schnorr_sign_msg_dev(ctx.raw, curve, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_sig_bytes, d_status, n, stream))
+    }
+
+    /// `fec_schnorr_challenge_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn schnorr_challenge(ctx: &mut GpuContext, curve: c_int, d_r_xy: *const u64, d_r_inf: *const u8, d_pk_xy: *const u64, d_pk_inf: *const u8, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_e: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_schnorr_challenge_dev(ctx.raw, curve, d_r_xy, d_r_inf, d_pk_xy, d_pk_inf, d_msgs, d_msg_off, msg_len, d_e, d_status, n, stream))
+    }
+
+    /// `fec_scalar_from_bytes_reduced_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`].
+    pub unsafe fn scalar_from_bytes_reduced(ctx: &mut GpuContext, curve: c_int, d_bytes: *const u8, d_out: *mut u64, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_scalar_from_bytes_reduced_dev(ctx.raw, curve, d_bytes, d_out, n, stream))
     }
 
     /// `fec_schnorr_verify_dev`.
