@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "fec_ecdsa_sign_msg", "fec_ecdsa_sign_msg_dev", "fec_rfc6979_k", "fec_rfc6979_k_dev", "fec_debug_rfc6979_k",
     "fec_scalar_from_bytes_reduced", "fec_scalar_from_bytes_reduced_dev", "fec_schnorr_challenge", "fec_schnorr_challenge_dev",
     "fec_schnorr_sign_msg", "fec_schnorr_sign_msg_dev",
+    "fec_derive_key", "fec_derive_key_dev", "fec_ecdh_derive_key", "fec_ecdh_derive_key_dev", "fec_ecdh_exchange", "fec_ecdh_exchange_dev",
 ]
 # include/fecgpu_canon.h: the canonical-math mode (NOT reference parity)
 CANON_ABI_SYMBOLS = [
@@ -214,6 +215,15 @@ def lib():
     L.fec_schnorr_sign_msg_dev.argtypes = [vp, ci, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp]
     for n in ("fec_scalar_from_bytes_reduced", "fec_scalar_from_bytes_reduced_dev", "fec_schnorr_challenge", "fec_schnorr_challenge_dev",
               "fec_schnorr_sign_msg", "fec_schnorr_sign_msg_dev"):
+        getattr(L, n).restype = ci
+    L.fec_derive_key.argtypes = [vp, ci, vp, sz, vp, sz, sz, vp, sz]
+    L.fec_derive_key_dev.argtypes = [vp, ci, vp, sz, vp, sz, sz, vp, sz, vp]
+    L.fec_ecdh_derive_key.argtypes = [vp, ci, vp, vp, vp, vp, sz, sz, vp, vp, sz]
+    L.fec_ecdh_derive_key_dev.argtypes = [vp, ci, vp, vp, vp, vp, sz, sz, vp, vp, sz, vp]
+    L.fec_ecdh_exchange.argtypes = [vp, ci, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz]
+    L.fec_ecdh_exchange_dev.argtypes = [vp, ci, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]
+    for n in ("fec_derive_key", "fec_derive_key_dev", "fec_ecdh_derive_key", "fec_ecdh_derive_key_dev", "fec_ecdh_exchange",
+              "fec_ecdh_exchange_dev"):
         getattr(L, n).restype = ci
     L.fec_ctx_set_chunk.argtypes = [vp, sz]
     L.fec_ctx_set_chunk.restype = ci

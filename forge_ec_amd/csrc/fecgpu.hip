@@ -23,6 +23,7 @@
 #include "ed25519.hpp"
 #include "p256.hpp"
 #include "secp256k1.hpp"
+#include "hkdf.hpp"
 #include "host_ctx.hpp"
 #include "kernels.hpp"
 #include "cu_split.hpp"
@@ -1084,6 +1085,55 @@ int launch_ecdh(fec_ctx* ctx, int curve, const u64* dsk, const u64* dpk, const u
   return L.done();
 }
 
+// KeyExchange::derive_key per element (kernels_ecdh.hip; hkdf.hpp): one pass, no work area.  `p` travels with the launch.
+int launch_derive_key(fec_ctx* ctx, int curve, const unsigned char* dsecrets, const hkdf::Params& p, unsigned char* dkeys, size_t n,
+                      void* stream) {
+  if (n == 0 || p.out_len == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_derive_key");
+  derive_key_launch(curve, dsecrets, p, dkeys, n, L.s);
+  return L.done();
+}
+
+// derive_shared_secret followed by derive_key: launch_ecdh's pipeline on the same work area with k_ecdh_kdf_finish, which
+// keeps the x coordinate in registers -- no secret of this call is written anywhere but the shared points in the
+// stream's scratch and the keys.
+int launch_ecdh_kdf(fec_ctx* ctx, int curve, const u64* dsk, const u64* dpk, const unsigned char* dinf, const hkdf::Params& p,
+                    unsigned char* dkeys, unsigned char* dstatus, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  void* work;
+  WorkArea area;
+  area.add(work, ecdh_work_bytes(n));
+  const int rc = area.acquire(ctx, stream ? (hipStream_t)stream : ctx->stream);
+  if (rc != FEC_OK) return rc;
+  Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_ecdh_pre + k_secp_mul + k_ecdh_kdf_finish" : "k_ecdh_pre + k_p256_mul_sched + k_ecdh_kdf_finish");
+  const EcdhWork w = ecdh_pre_launch(curve, reinterpret_cast<const u32*>(dpk), dinf, work, n, L.s);
+  var_product(sched_env(ctx), curve, reinterpret_cast<const u32*>(dsk), w.q, w.t, n, L.s);
+  ecdh_kdf_finish_launch(curve, w.t, w.flags, p, dkeys, dstatus, n, L.s);
+  return L.done();
+}
+
+// KeyExchange::exchange with the caller's private key (lib.rs:1154-1174): multiply(generator(), sk) beside
+// multiply(from_affine(peer), sk) -- product_pair, under launch_mul's prefix-table policy -- then k_ecdh_exchange_finish.
+// The public points and the ECDH work area are regions of one request.
+int launch_ecdh_exchange(fec_ctx* ctx, int curve, const u64* dsk, const u64* dpeer, const unsigned char* dinf, const hkdf::Params& p,
+                         u64* dpub_xy, unsigned char* dpub_inf, unsigned char* dkeys, unsigned char* dstatus, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  u32* pub;
+  void* work;
+  WorkArea area;
+  area.add(pub, n * 96).add(work, ecdh_work_bytes(n));
+  int rc = area.acquire(ctx, st);
+  if (rc == FEC_OK) rc = prepare_generator(ctx, curve, st, n);
+  if (rc != FEC_OK) return rc;
+  Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_ecdh_pre + k_secp_mul x2 + k_ecdh_exchange_finish" : "k_ecdh_pre + k_p256_mul_sched x2 + k_ecdh_exchange_finish");
+  const u32* sk = reinterpret_cast<const u32*>(dsk);
+  const EcdhWork w = ecdh_pre_launch(curve, reinterpret_cast<const u32*>(dpeer), dinf, work, n, L.s);
+  product_pair(ctx, curve, n, L.s, SideStream::kSideStreamMax, kP256VarAffineMs, sk, pub, nullptr, sk, w.q, w.t);
+  ecdh_exchange_finish_launch(curve, pub, w.t, w.flags, p, reinterpret_cast<u32*>(dpub_xy), dpub_inf, dkeys, dstatus, n, L.s);
+  return L.done();
+}
+
 // Ecdsa::<C, D>::sign for secp256k1 / P-256 after the hash and the nonce (ecdsa.rs:98-211): R = multiply(G, k) by the
 // curve's fixed-base kernel into the stream's scratch -- from the ctx's prefix table under launch_mul's policy (the
 // host-pointer form may build one, a *_dev call only takes one that exists) -- then k_ecdsa_sign_finish (kernels_ecdsa.hip).
@@ -2057,6 +2107,99 @@ int fec_batch_ecdh(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys, 
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_ecdh(c, curve, (const u64*)d[0], (const u64*)d[1], (const unsigned char*)d[2], (unsigned char*)d[3],
                        (unsigned char*)d[4], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- ECDH key derivation (fecgpu.h; hkdf.hpp) ----
+// The checks every form shares: the curve picks the function, the lengths are bounded so that info travels with the
+// launch and the u8 block counter of the reference never overflows.
+static int kdf_args(fec_ctx* ctx, int curve, const uint8_t* info, size_t info_len, size_t secret_len, size_t out_len) {
+  if (!ctx || !curve_ok(curve) || (info_len && !info)) return FEC_E_ARG;
+  if (curve == FEC_ED25519) return FEC_E_UNSUPPORTED;   // Ed25519 has no KeyExchange impl
+  if (secret_len > hkdf::MAX_SECRET || info_len > hkdf::MAX_INFO || out_len > hkdf::MAX_OUT) return FEC_E_UNSUPPORTED;
+  return FEC_OK;
+}
+
+int fec_derive_key_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_secrets, size_t secret_len, const uint8_t* info, size_t info_len,
+                       size_t out_len, uint8_t* d_keys, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  const int rc = kdf_args(ctx, curve, info, info_len, secret_len, out_len);
+  if (rc != FEC_OK) return rc;
+  if (n && ((secret_len && !d_secrets) || (out_len && !d_keys))) return FEC_E_ARG;
+  if (!aligned16(d_secrets) || !aligned16(d_keys)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_derive_key(ctx, curve, d_secrets, hkdf::make_params(curve == FEC_P256, info, info_len, secret_len, out_len), d_keys, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_derive_key(fec_ctx* ctx, fec_curve curve, const uint8_t* secrets, size_t secret_len, const uint8_t* info, size_t info_len,
+                   size_t out_len, uint8_t* keys, size_t n) try {
+  const int rc = kdf_args(ctx, curve, info, info_len, secret_len, out_len);
+  if (rc != FEC_OK) return rc;
+  if (n && ((secret_len && !secrets) || (out_len && !keys))) return FEC_E_ARG;
+  if (out_len == 0) return FEC_OK;
+  const hkdf::Params p = hkdf::make_params(curve == FEC_P256, info, info_len, secret_len, out_len);
+  // (an absent array -- secret_len 0 -- reaches the body as null)
+  const HostArray a[] = {secret_input(secret_len ? secrets : nullptr, secret_len), secret_output(keys, out_len)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_derive_key(c, curve, (const unsigned char*)d[0], p, (unsigned char*)d[1], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_ecdh_derive_key_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_keys, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf,
+                            const uint8_t* info, size_t info_len, size_t out_len, uint8_t* d_keys, uint8_t* d_status, size_t n,
+                            void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  const int rc = kdf_args(ctx, curve, info, info_len, 32, out_len);
+  if (rc != FEC_OK) return rc;
+  if (n && (!d_private_keys || !d_pk_xy || !d_status || (out_len && !d_keys))) return FEC_E_ARG;
+  if (!aligned16(d_private_keys) || !aligned16(d_pk_xy) || !aligned16(d_keys)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_ecdh_kdf(ctx, curve, d_private_keys, d_pk_xy, d_pk_inf, hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len),
+                         d_keys, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_ecdh_derive_key(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys, const uint64_t* pk_xy, const uint8_t* pk_inf,
+                        const uint8_t* info, size_t info_len, size_t out_len, uint8_t* keys, uint8_t* status, size_t n) try {
+  const int rc = kdf_args(ctx, curve, info, info_len, 32, out_len);
+  if (rc != FEC_OK) return rc;
+  if (n && (!private_keys || !pk_xy || !status || (out_len && !keys))) return FEC_E_ARG;
+  const hkdf::Params p = hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len);
+  // (the shared points sit in the stream's scratch: cleared with the staging on every way out)
+  const HostArray a[] = {secret_input(private_keys, 32), input(pk_xy, 64), input(pk_inf, 1), secret_output(out_len ? keys : nullptr, out_len),
+                         output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_ecdh_kdf(c, curve, (const u64*)d[0], (const u64*)d[1], (const unsigned char*)d[2], p, (unsigned char*)d[3],
+                           (unsigned char*)d[4], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_ecdh_exchange_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_keys, const uint64_t* d_peer_xy, const uint8_t* d_peer_inf,
+                          const uint8_t* info, size_t info_len, size_t out_len, uint64_t* d_public_xy, uint8_t* d_public_inf,
+                          uint8_t* d_keys, uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  const int rc = kdf_args(ctx, curve, info, info_len, 32, out_len);
+  if (rc != FEC_OK) return rc;
+  if (n && (!d_private_keys || !d_peer_xy || !d_public_xy || !d_public_inf || !d_status || (out_len && !d_keys))) return FEC_E_ARG;
+  if (!aligned16(d_private_keys) || !aligned16(d_peer_xy) || !aligned16(d_public_xy) || !aligned16(d_keys)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_ecdh_exchange(ctx, curve, d_private_keys, d_peer_xy, d_peer_inf, hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len),
+                              d_public_xy, d_public_inf, d_keys, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_ecdh_exchange(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys, const uint64_t* peer_xy, const uint8_t* peer_inf,
+                      const uint8_t* info, size_t info_len, size_t out_len, uint64_t* public_xy, uint8_t* public_inf, uint8_t* keys,
+                      uint8_t* status, size_t n) try {
+  const int rc = kdf_args(ctx, curve, info, info_len, 32, out_len);
+  if (rc != FEC_OK) return rc;
+  if (n && (!private_keys || !peer_xy || !public_xy || !public_inf || !status || (out_len && !keys))) return FEC_E_ARG;
+  const hkdf::Params p = hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len);
+  // (both products sit in the stream's scratch: cleared with the staging on every way out; the public key of a failed
+  // exchange is never written, the one of a good exchange is public but staged beside the keys)
+  const HostArray a[] = {secret_input(private_keys, 32), input(peer_xy, 64), input(peer_inf, 1), secret_output(public_xy, 64),
+                         output(public_inf, 1), secret_output(out_len ? keys : nullptr, out_len), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_ecdh_exchange(c, curve, (const u64*)d[0], (const u64*)d[1], (const unsigned char*)d[2], p, (u64*)d[3],
+                                (unsigned char*)d[4], (unsigned char*)d[5], (unsigned char*)d[6], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 

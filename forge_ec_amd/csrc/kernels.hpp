@@ -265,6 +265,28 @@ void validate_launch(const SchedEnv& env, int curve, const u32* xy, const unsign
 size_t ecdh_work_bytes(size_t n);
 void ecdh_launch(const SchedEnv& env, int curve, const u32* sk, const u32* pk, const unsigned char* pk_inf, u32* out, unsigned char* status,
                  void* work, size_t n, hipStream_t s);
+// The regions of that work area, and its first pass alone: q = from_affine(pk) (24 words per element, the base of the
+// multiplication), t (24 words: where the caller puts multiply(q, sk)), one validation flag per element.
+struct EcdhWork {
+  u32 *q, *t;
+  unsigned char* flags;
+};
+EcdhWork ecdh_pre_launch(int curve, const u32* pk, const unsigned char* pk_inf, void* work, size_t n, hipStream_t s);
+
+// kernels_ecdh.hip: KeyExchange::derive_key and the finishing passes that end in it (hkdf.hpp: the readings and
+// hkdf::Params, the launch's uniform part -- info and the three lengths).  secrets: p.secret_len bytes per element;
+// keys: p.out_len bytes per element, packed, behind a 16-byte aligned base (may be null when out_len is 0).
+// ecdh_kdf_finish: ecdh_launch's finishing pass with derive_key on the x value; exchange_finish: the same with
+// pub = multiply(generator(), sk) brought to affine form beside it (public_xy 16 words, public_inf one byte).
+namespace hkdf {
+struct Params;
+}
+void derive_key_launch(int curve, const unsigned char* secrets, const hkdf::Params& p, unsigned char* keys, size_t n, hipStream_t s);
+void ecdh_kdf_finish_launch(int curve, const u32* t, const unsigned char* flags, const hkdf::Params& p, unsigned char* keys,
+                            unsigned char* status, size_t n, hipStream_t s);
+void ecdh_exchange_finish_launch(int curve, const u32* pub, const u32* t, const unsigned char* flags, const hkdf::Params& p,
+                                 u32* public_xy, unsigned char* public_inf, unsigned char* keys, unsigned char* status, size_t n,
+                                 hipStream_t s);
 
 // kernels_ecdsa.hip: Eddsa verify around the Ed25519 multiplications (eddsa.rs:174-211, 430-447).
 // eddsa_pre_launch: a[i] = from_affine(pk[i]) (32 words); eddsa_finish_launch: status from sg = multiply(G, s),

@@ -299,17 +299,19 @@ __global__ __launch_bounds__(TPB) void k_ecdh_finish(const u32* __restrict__ t, 
   status[i] = st;
 }
 using MulLauncher = void (*)(const SchedEnv&, bool, const u32*, const u32*, u32*, size_t, hipStream_t);
+// the work area of ecdh_work_bytes(n): q, t, flags
+EcdhWork ecdh_layout(void* work, size_t n) {
+  char* w = static_cast<char*>(work);
+  return EcdhWork{reinterpret_cast<u32*>(w), reinterpret_cast<u32*>(w + n * 96), reinterpret_cast<unsigned char*>(w + n * 192)};
+}
 template <class E>
 void run_ecdh(MulLauncher mul, const SchedEnv& env, const u32* sk, const u32* pk, const unsigned char* pk_inf, u32* out,
               unsigned char* status, void* work, size_t n, hipStream_t s) {
-  char* w = static_cast<char*>(work);
-  u32* q = reinterpret_cast<u32*>(w);
-  u32* t = reinterpret_cast<u32*>(w + n * 96);
-  unsigned char* flags = reinterpret_cast<unsigned char*>(w + n * 192);
+  const EcdhWork w = ecdh_layout(work, n);
   const dim3 g((unsigned)((n + TPB - 1) / TPB)), b(TPB);
-  hipLaunchKernelGGL((k_ecdh_pre<E>), g, b, 0, s, pk, pk_inf, q, flags, n);
-  mul(env, false, sk, q, t, n, s);
-  hipLaunchKernelGGL((k_ecdh_finish<E>), g, b, 0, s, (const u32*)t, (const unsigned char*)flags, out, status, n);
+  hipLaunchKernelGGL((k_ecdh_pre<E>), g, b, 0, s, pk, pk_inf, w.q, w.flags, n);
+  mul(env, false, sk, w.q, w.t, n, s);
+  hipLaunchKernelGGL((k_ecdh_finish<E>), g, b, 0, s, (const u32*)w.t, (const unsigned char*)w.flags, out, status, n);
 }
 
 // ---- Curve::validate_point ----
@@ -511,6 +513,13 @@ void ecdh_launch(const SchedEnv& env, int curve, const u32* sk, const u32* pk, c
                  unsigned char* status, void* work, size_t n, hipStream_t s) {
   if (curve == FEC_SECP256K1) run_ecdh<ESecp>(secp_launch_mul, env, sk, pk, pk_inf, out, status, work, n, s);
   else run_ecdh<EP256>(p256_launch_mul, env, sk, pk, pk_inf, out, status, work, n, s);
+}
+EcdhWork ecdh_pre_launch(int curve, const u32* pk, const unsigned char* pk_inf, void* work, size_t n, hipStream_t s) {
+  const EcdhWork w = ecdh_layout(work, n);
+  const dim3 g((unsigned)((n + TPB - 1) / TPB)), b(TPB);
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_ecdh_pre<ESecp>), g, b, 0, s, pk, pk_inf, w.q, w.flags, n);
+  else hipLaunchKernelGGL((k_ecdh_pre<EP256>), g, b, 0, s, pk, pk_inf, w.q, w.flags, n);
+  return w;
 }
 
 void ecdsa_pre_launch(int curve, const unsigned char* digests, const u32* r, const u32* s_, const u32* pk,

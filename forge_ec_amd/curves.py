@@ -216,6 +216,65 @@ class Context:
         _check(self._lib.fec_batch_ecdh(self._h, curve, _ptr(kk), _ptr(pk), _ptr(inf), _ptr(out), _ptr(st), n), "fec_batch_ecdh")
         return out, st
 
+    @staticmethod
+    def _info(info):
+        b = bytes(info) if info is not None else b""
+        return (ctypes.c_char_p(b) if b else None), len(b)
+
+    def derive_key(self, curve, secrets, info, out_len):
+        """KeyExchange::derive_key per element: curve 0 (secp256k1) HKDF-SHA-256 with a zero salt (secp256k1.rs:1846-1883),
+        curve 1 (P-256) the reference's XOR placeholder (p256.rs:2314-2344).  secrets (n, secret_len) uint8 with
+        secret_len <= 64, or a list of n equally long byte strings; info one byte string (<= 1024 bytes) or None;
+        out_len <= 8128.  Returns (n, out_len) uint8.  See include/fecgpu.h."""
+        if isinstance(secrets, (list, tuple)):
+            secrets = np.array([list(x) for x in secrets], dtype=np.uint8).reshape(len(secrets), -1)
+        sec = np.ascontiguousarray(np.asarray(secrets, dtype=np.uint8))
+        if sec.ndim != 2:
+            raise ValueError("secrets must be (n, secret_len)")
+        n, secret_len = sec.shape
+        ip, il = self._info(info)
+        keys = np.zeros((n, int(out_len)), dtype=np.uint8)
+        _check(self._lib.fec_derive_key(self._h, curve, _ptr(sec) if secret_len else None, secret_len, ip, il, int(out_len),
+                                        _ptr(keys) if out_len else None, n), "fec_derive_key")
+        return keys
+
+    def _ecdh_inputs(self, private_keys, pk_xy, pk_inf):
+        kk, pk = _u64(private_keys, 4), _u64(pk_xy, 8)
+        n = kk.shape[0]
+        if pk.shape[0] != n:
+            raise ValueError("inputs differ in length")
+        inf = np.ascontiguousarray(np.asarray(pk_inf, dtype=np.uint8)).reshape(-1) if pk_inf is not None else None
+        if inf is not None and inf.shape[0] != n:
+            raise ValueError("pk_inf and the keys differ in length")  # the C side reads n bytes
+        return kk, pk, inf, n
+
+    def ecdh_derive_key(self, curve, private_keys, pk_xy, pk_inf, info, out_len):
+        """derive_shared_secret followed by derive_key per element; the x coordinate never leaves the device.  Inputs as
+        batch_ecdh and derive_key.  Returns (keys (n, out_len) uint8, status (n,) uint8 as batch_ecdh); a key row is zero
+        where its status is not 0.  NOT FOR PRODUCTION SECRETS: see include/fecgpu.h."""
+        kk, pk, inf, n = self._ecdh_inputs(private_keys, pk_xy, pk_inf)
+        ip, il = self._info(info)
+        keys = np.zeros((n, int(out_len)), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_ecdh_derive_key(self._h, curve, _ptr(kk), _ptr(pk), _ptr(inf), ip, il, int(out_len),
+                                             _ptr(keys) if out_len else None, _ptr(st), n), "fec_ecdh_derive_key")
+        return keys, st
+
+    def ecdh_exchange(self, curve, private_keys, peer_xy, peer_inf, info, out_len):
+        """KeyExchange::exchange per element with the caller's private keys (forge-ec-core/src/lib.rs:1154-1174; draw them
+        with the reference's Scalar::random): the public key to_affine(multiply(generator(), sk)), then
+        derive_shared_secret and derive_key.  Returns (public_xy (n, 8), public_inf (n,), keys (n, out_len) uint8,
+        status (n,) uint8 as batch_ecdh); everything is zero where the status is not 0."""
+        kk, pk, inf, n = self._ecdh_inputs(private_keys, peer_xy, peer_inf)
+        ip, il = self._info(info)
+        pub = np.zeros((n, 8), dtype=np.uint64)
+        pinf = np.zeros(n, dtype=np.uint8)
+        keys = np.zeros((n, int(out_len)), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_ecdh_exchange(self._h, curve, _ptr(kk), _ptr(pk), _ptr(inf), ip, il, int(out_len), _ptr(pub), _ptr(pinf),
+                                           _ptr(keys) if out_len else None, _ptr(st), n), "fec_ecdh_exchange")
+        return pub, pinf, keys, st
+
     def ecdsa_sign(self, curve, sk, digests, k):
         """Ecdsa::<C, D>::sign per element (ecdsa.rs:98-211) for secp256k1 / P-256 after the hash and the nonce:
         sk (n,4), digests (n,32) uint8 (h_bytes), k (n,4) from Rfc6979::<C, D>::generate_k.  Returns (r (n,4),
@@ -732,6 +791,22 @@ class Context:
     def batch_ecdh_dev(self, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream=None):
         _check(self._lib.fec_batch_ecdh_dev(self._h, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream),
                "fec_batch_ecdh_dev")
+
+    def derive_key_dev(self, curve, d_secrets, secret_len, info, out_len, d_keys, n, stream=None):
+        """fec_derive_key_dev: `info` is a host byte string (or None), everything else raw device addresses."""
+        ip, il = self._info(info)
+        _check(self._lib.fec_derive_key_dev(self._h, curve, d_secrets, secret_len, ip, il, out_len, d_keys, n, stream), "fec_derive_key_dev")
+
+    def ecdh_derive_key_dev(self, curve, d_private_keys, d_pk_xy, d_pk_inf, info, out_len, d_keys, d_status, n, stream=None):
+        ip, il = self._info(info)
+        _check(self._lib.fec_ecdh_derive_key_dev(self._h, curve, d_private_keys, d_pk_xy, d_pk_inf, ip, il, out_len, d_keys, d_status, n,
+                                                 stream), "fec_ecdh_derive_key_dev")
+
+    def ecdh_exchange_dev(self, curve, d_private_keys, d_peer_xy, d_peer_inf, info, out_len, d_public_xy, d_public_inf, d_keys, d_status, n,
+                          stream=None):
+        ip, il = self._info(info)
+        _check(self._lib.fec_ecdh_exchange_dev(self._h, curve, d_private_keys, d_peer_xy, d_peer_inf, ip, il, out_len, d_public_xy,
+                                               d_public_inf, d_keys, d_status, n, stream), "fec_ecdh_exchange_dev")
 
     def x25519_dev(self, d_scalars, d_u, d_out, n, stream=None):
         _check(self._lib.fec_x25519_dev(self._h, d_scalars, d_u, d_out, n, stream), "fec_x25519_dev")

@@ -32,6 +32,10 @@
  *   fec_batch_validate_point   Curve::validate_point (secp256k1.rs:2722-2726, p256.rs:2187-2191, core lib.rs:905-925)
  *   fec_batch_ecdh        KeyExchange::derive_shared_secret for secp256k1 / P-256 (secp256k1.rs:1884-1904,
  *                         p256.rs:2281-2312)
+ *   fec_derive_key        KeyExchange::derive_key for secp256k1 (HKDF-SHA-256, zero salt: secp256k1.rs:1846-1883) / P-256
+ *                         (the XOR placeholder: p256.rs:2314-2344)
+ *   fec_ecdh_derive_key   derive_shared_secret followed by derive_key; the x coordinate never leaves the device
+ *   fec_ecdh_exchange     KeyExchange::exchange with the caller's private key (forge-ec-core/src/lib.rs:1154-1174)
  *   fec_ecdsa_sign        Ecdsa::<C, D>::sign for secp256k1 / P-256 after the hash and the RFC 6979 nonce
  *                         (ecdsa.rs:45-71, 98-211; scalar Sub secp256k1.rs:2380-2408, p256.rs:1377-1408)
  *   fec_ed25519_sign      Ed25519Signature::sign with SHA-512, hash included (forge-ec-signature/src/eddsa.rs:267-356)
@@ -740,6 +744,54 @@ int fec_schnorr_sign_msg(fec_ctx* ctx, fec_curve curve, const uint64_t* sk /* n*
 int fec_schnorr_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                              size_t msg_len, uint64_t* d_r_xy, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_sig_bytes,
                              uint8_t* d_status, size_t n, void* stream);
+
+/* ---- ECDH key derivation: KeyExchange::derive_key and exchange (forge-ec-core/src/lib.rs:998-1175), parity mode ----
+ * Alignment, multi-device and prefix-table rules: those of the "SHA-256 ..." block above (the _dev forms take 16-byte aligned
+ * arrays, return FEC_E_UNSUPPORTED on a multi-device ctx and never build a fixed-base prefix table; `stream` comes last).
+ * curve = FEC_SECP256K1 or FEC_P256; FEC_ED25519: FEC_E_UNSUPPORTED (it implements no KeyExchange).
+ * `info` is a HOST pointer in both forms, one string for the whole batch, info_len <= 1024 (above: FEC_E_UNSUPPORTED), and
+ * may be NULL when info_len == 0.  The bound exists so that the string travels with the launch, as a padded block template
+ * among the kernel arguments: no device buffer, no copy to wait for.
+ * out_len <= 8128 = 254 * 32 for both curves, FEC_E_UNSUPPORTED above it: the reference counts HKDF blocks in a u8 that it
+ * increments after every block, so beyond 254 blocks a debug build panics and a release build wraps -- there is no one
+ * behaviour to reproduce.  out_len == 0 is legal: `keys` may be NULL and the statuses are still produced.
+ * `keys` rows are packed at out_len bytes with no padding; nothing past n * out_len is written.
+ * fec_derive_key   keys[i] = C::derive_key(&secrets[i], info, out_len).unwrap(); secret_len <= 64, the same for the whole
+ *   call (above: FEC_E_UNSUPPORTED).  The curve selects the function:
+ *     secp256k1 (secp256k1.rs:1846-1883): PRK = HMAC-SHA-256(key = 32 zero bytes, secret); T(0) empty,
+ *       T(i) = HMAC(PRK, T(i-1) || info || byte(i)), i from 1; the first out_len bytes of T(1) || T(2) || ...  Always Ok:
+ *       new_from_slice never fails and there is no RFC 5869 length check.  RFC 5869 test case A.3 is this reading.
+ *     P-256 (p256.rs:2314-2344): keys[i][j] = (j < secret_len ? secret[j] : 0) ^ (j < info_len ? info[j] : 0).  Always Ok.
+ *       A placeholder, NOT a key derivation function.
+ * fec_ecdh_derive_key   derive_shared_secret(private_keys[i], pk[i]) as fec_batch_ecdh computes it, with its status -- 0 Ok,
+ *   1 Err(InvalidPublicKey) (P-256), 2 Err (identity product) -- followed by derive_key on the 32 bytes of x, in one
+ *   finishing kernel that holds x in registers: the shared secret is written nowhere.  The key row is zero where status != 0.
+ * fec_ecdh_exchange   exchange with the caller's private key in place of the reference's draw (Scalar::random; draw it with
+ *   the reference and pass the limbs, as for the weights of fec_ecdsa_batch_verify).  No key check: any four limbs are used
+ *   as they are.  public = to_affine(multiply(generator(), sk)) with the trait functions (public_xy raw affine limbs,
+ *   public_inf 0 or 1), then derive_shared_secret(sk, peer)?, then derive_key(&secret, info, out_len)?.  An Err returns no
+ *   public key: public_xy, public_inf and the key row are zero where status != 0.
+ * SECRETS: the private keys, the shared points, the x coordinate, PRK, every T(i) and the keys.  The host forms clear their
+ *   device staging (keys in, keys and public scratch out) and the stream scratch (the products) on every way out; the _dev
+ *   forms leave every buffer to the caller (the stream's scratch keeps the products until the ctx is wiped, fec_ctx_wipe,
+ *   or destroyed).  NOT constant-time (the P-256 scheduler), as for fec_batch_ecdh. */
+int fec_derive_key(fec_ctx* ctx, fec_curve curve, const uint8_t* secrets /* n*secret_len */, size_t secret_len, const uint8_t* info,
+                   size_t info_len, size_t out_len, uint8_t* keys /* n*out_len */, size_t n);
+int fec_derive_key_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_secrets, size_t secret_len, const uint8_t* info,
+                       size_t info_len, size_t out_len, uint8_t* d_keys, size_t n, void* stream);
+int fec_ecdh_derive_key(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys /* n*4 */, const uint64_t* pk_xy /* n*8 */,
+                        const uint8_t* pk_inf /* n or NULL */, const uint8_t* info, size_t info_len, size_t out_len,
+                        uint8_t* keys /* n*out_len */, uint8_t* status /* n */, size_t n);
+int fec_ecdh_derive_key_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_keys, const uint64_t* d_pk_xy,
+                            const uint8_t* d_pk_inf, const uint8_t* info, size_t info_len, size_t out_len, uint8_t* d_keys,
+                            uint8_t* d_status, size_t n, void* stream);
+int fec_ecdh_exchange(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys /* n*4 */, const uint64_t* peer_xy /* n*8 */,
+                      const uint8_t* peer_inf /* n or NULL */, const uint8_t* info, size_t info_len, size_t out_len,
+                      uint64_t* public_xy /* n*8 */, uint8_t* public_inf /* n */, uint8_t* keys /* n*out_len */,
+                      uint8_t* status /* n */, size_t n);
+int fec_ecdh_exchange_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_keys, const uint64_t* d_peer_xy,
+                          const uint8_t* d_peer_inf, const uint8_t* info, size_t info_len, size_t out_len, uint64_t* d_public_xy,
+                          uint8_t* d_public_inf, uint8_t* d_keys, uint8_t* d_status, size_t n, void* stream);
 
 /* Every element-wise host-pointer entry point processes its batch in chunks of `elements` elements
  * (default 2^18), so device staging memory is bounded by two chunks for any n.  Most run them as a

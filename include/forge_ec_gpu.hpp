@@ -489,6 +489,62 @@ inline std::vector<SharedSecret> derive_shared_secret(GpuContext& ctx, const std
   }
   return r;
 }
+
+// KeyExchange::derive_key(&secrets[i], info, output_len) per element (fec_derive_key): secp256k1 is HKDF-SHA-256 with a
+// zero salt (secp256k1.rs:1846-1883), P-256 the reference's XOR placeholder (p256.rs:2314-2344); always Ok.  Every
+// secret has the same length (<= 64); info <= 1024 bytes; output_len <= 8128 -- see fecgpu.h.
+template <fec_curve C>
+inline std::vector<std::vector<uint8_t>> derive_key(GpuContext& ctx, const std::vector<std::vector<uint8_t>>& secrets,
+                                                    const std::vector<uint8_t>& info, size_t output_len) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "KeyExchange is implemented for secp256k1 and P-256");
+  const size_t n = secrets.size(), secret_len = n ? secrets[0].size() : 0;
+  std::vector<uint8_t> packed, keys(n * output_len);
+  for (const auto& s : secrets) {
+    if (s.size() != secret_len) throw Error(FEC_E_ARG);
+    packed.insert(packed.end(), s.begin(), s.end());
+  }
+  check(fec_derive_key(ctx.raw(), C, packed.empty() ? nullptr : packed.data(), secret_len, info.empty() ? nullptr : info.data(),
+                       info.size(), output_len, keys.empty() ? nullptr : keys.data(), n));
+  std::vector<std::vector<uint8_t>> r(n);
+  for (size_t i = 0; i < n; ++i) r[i].assign(keys.begin() + i * output_len, keys.begin() + (i + 1) * output_len);
+  return r;
+}
+
+// KeyExchange::exchange(rng, &peers[i], info, output_len) per element (forge-ec-core/src/lib.rs:1154-1174) with the
+// private keys drawn by the caller (Scalar::random, the reference's own draw) and everything after the draw on the GPU
+// (fec_ecdh_exchange): public_key = to_affine(multiply(generator(), sk)), derive_shared_secret, derive_key.  No key
+// check, as in the reference.  An Err carries neither a public key nor a key: both are zero unless outcome is Ok.
+template <fec_curve C>
+struct Exchange {
+  Outcome outcome;
+  AffinePoint<C> public_key;
+  std::vector<uint8_t> key;
+};
+template <fec_curve C>
+inline std::vector<Exchange<C>> exchange(GpuContext& ctx, const std::vector<Scalar<C>>& private_keys,
+                                         const std::vector<AffinePoint<C>>& peers, const std::vector<uint8_t>& info,
+                                         size_t output_len) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "KeyExchange is implemented for secp256k1 and P-256");
+  const size_t n = private_keys.size();
+  if (peers.size() != n) throw Error(FEC_E_ARG);
+  std::vector<uint64_t> pk, pub(n * 8);
+  std::vector<uint8_t> inf, st(n), pub_inf(n), keys(n * output_len);
+  detail::pack_affine<C>(peers, pk, inf);
+  check(fec_ecdh_exchange(ctx.raw(), C, reinterpret_cast<const uint64_t*>(private_keys.data()), pk.data(), inf.data(),
+                          info.empty() ? nullptr : info.data(), info.size(), output_len, pub.data(), pub_inf.data(),
+                          keys.empty() ? nullptr : keys.data(), st.data(), n));
+  std::vector<Exchange<C>> r(n);
+  for (size_t i = 0; i < n; ++i) {
+    r[i].outcome = static_cast<Outcome>(st[i]);
+    for (int l = 0; l < 4; ++l) {
+      r[i].public_key.x_.raw[l] = pub[i * 8 + l];
+      r[i].public_key.y_.raw[l] = pub[i * 8 + 4 + l];
+    }
+    r[i].public_key.infinity = pub_inf[i] != 0;
+    r[i].key.assign(keys.begin() + i * output_len, keys.begin() + (i + 1) * output_len);
+  }
+  return r;
+}
 }  // namespace key_exchange
 
 namespace curve25519 {

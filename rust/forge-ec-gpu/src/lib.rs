@@ -107,6 +107,12 @@ extern "C" {
     fn fec_schnorr_sign_msg(ctx: *mut FecCtx, curve: c_int, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, r_xy: *mut u64, r_inf: *mut u8, s: *mut u64, sig_bytes: *mut u8, status: *mut u8, n: usize) -> c_int;
     fn fec_schnorr_sign_msg_dev(ctx: *mut FecCtx, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *mut u64, d_r_inf: *mut u8, d_s: *mut u64, d_sig_bytes: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_debug_rfc6979_k(ctx: *mut FecCtx, curve: c_int, order_override: *const u64, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, k: *mut u64, status: *mut u8, n: usize) -> c_int;
+    fn fec_derive_key(ctx: *mut FecCtx, curve: c_int, secrets: *const u8, secret_len: usize, info: *const u8, info_len: usize, out_len: usize, keys: *mut u8, n: usize) -> c_int;
+    fn fec_derive_key_dev(ctx: *mut FecCtx, curve: c_int, d_secrets: *const u8, secret_len: usize, info: *const u8, info_len: usize, out_len: usize, d_keys: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_ecdh_derive_key(ctx: *mut FecCtx, curve: c_int, private_keys: *const u64, pk_xy: *const u64, pk_inf: *const u8, info: *const u8, info_len: usize, out_len: usize, keys: *mut u8, status: *mut u8, n: usize) -> c_int;
+    fn fec_ecdh_derive_key_dev(ctx: *mut FecCtx, curve: c_int, d_private_keys: *const u64, d_pk_xy: *const u64, d_pk_inf: *const u8, info: *const u8, info_len: usize, out_len: usize, d_keys: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_ecdh_exchange(ctx: *mut FecCtx, curve: c_int, private_keys: *const u64, peer_xy: *const u64, peer_inf: *const u8, info: *const u8, info_len: usize, out_len: usize, public_xy: *mut u64, public_inf: *mut u8, keys: *mut u8, status: *mut u8, n: usize) -> c_int;
+    fn fec_ecdh_exchange_dev(ctx: *mut FecCtx, curve: c_int, d_private_keys: *const u64, d_peer_xy: *const u64, d_peer_inf: *const u8, info: *const u8, info_len: usize, out_len: usize, d_public_xy: *mut u64, d_public_inf: *mut u8, d_keys: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_ctx_set_chunk(ctx: *mut FecCtx, elements: usize) -> c_int;
     fn fec_ctx_set_timing(ctx: *mut FecCtx, enabled: c_int) -> c_int;
     fn fec_ctx_last_kernel_ms(ctx: *mut FecCtx, ms: *mut c_float, kernel_name: *mut *const c_char) -> c_int;
@@ -596,6 +602,78 @@ pub fn batch_derive_shared_secret<C: GpuCurve>(ctx: &mut GpuContext, private_key
         0 => { let mut s = [0u8; 32]; s.copy_from_slice(&secrets[32 * i..32 * i + 32]); Ok(s) }
         1 => Err(Error::InvalidPublicKey),
         _ => Err(if C::ID == 0 { Error::InvalidEncoding } else { Error::KeyExchangeError }),
+    }).collect())
+}
+
+/// The reference's error for an exchange status (`fec_batch_ecdh`'s): 1 is P-256's `InvalidPublicKey`, 2 the identity
+/// product (`InvalidEncoding` on secp256k1, `KeyExchangeError` on P-256).
+fn exchange_error<C: GpuCurve>(status: u8) -> Error {
+    match status {
+        1 => Error::InvalidPublicKey,
+        _ => if C::ID == 0 { Error::InvalidEncoding } else { Error::KeyExchangeError },
+    }
+}
+
+/// `KeyExchange::derive_key(&secrets[i], info, output_len)` per element on the GPU (`fec_derive_key`) for secp256k1
+/// (HKDF-SHA-256 with a zero salt, `secp256k1.rs:1846-1883`) and P-256 (the XOR placeholder, `p256.rs:2314-2344`): always
+/// `Ok` in the reference.  Every secret has the same length, at most 64 bytes; `info` at most 1024 bytes; `output_len`
+/// at most 8128 (the reference's `u8` block counter overflows beyond it): `Err(UnsupportedCurve)` otherwise, and for
+/// Ed25519, which implements no `KeyExchange`.
+pub fn derive_key_batch<C: GpuCurve>(ctx: &mut GpuContext, secrets: &[&[u8]], info: &[u8], output_len: usize) -> Result<Vec<Vec<u8>>> {
+    let n = secrets.len();
+    let secret_len = secrets.first().map_or(0, |s| s.len());
+    if secrets.iter().any(|s| s.len() != secret_len) {
+        return Err(Error::ValidationError);
+    }
+    let mut packed: Vec<u8> = secrets.iter().flat_map(|s| s.iter().copied()).collect();
+    let mut keys = vec![0u8; n * output_len];
+    // SAFETY: packed holds n * secret_len bytes, keys n * output_len; null stands for an empty array.
+    let rc = check(unsafe { fec_derive_key(ctx.raw, C::ID, if packed.is_empty() { core::ptr::null() } else { packed.as_ptr() }, secret_len, if info.is_empty() { core::ptr::null() } else { info.as_ptr() }, info.len(), output_len, if keys.is_empty() { core::ptr::null_mut() } else { keys.as_mut_ptr() }, n) });
+    packed.iter_mut().for_each(|b| *b = 0);
+    rc?;
+    Ok((0..n).map(|i| keys[i * output_len..(i + 1) * output_len].to_vec()).collect())
+}
+
+/// `derive_shared_secret(&private_keys[i], &public_keys[i])` followed by `derive_key(&secret, info, output_len)` per
+/// element (`fec_ecdh_derive_key`): the shared secret never leaves the GPU.  `Err` per element as
+/// [`batch_derive_shared_secret`].  Reproduces reference behaviour; not a hardened ECDH.
+pub fn ecdh_derive_key_batch<C: GpuCurve>(ctx: &mut GpuContext, private_keys: &[C::Scalar], public_keys: &[C::PointAffine], info: &[u8], output_len: usize) -> Result<Vec<Result<Vec<u8>>>> {
+    let n = private_keys.len();
+    if public_keys.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let mut kk = pack_scalars::<C>(private_keys);
+    let (xy, inf) = marshal_affine::<C>(public_keys);
+    let (mut keys, mut status) = (vec![0u8; n * output_len], vec![0u8; n]);
+    // SAFETY: every buffer holds n elements of the width the header states; null stands for an empty array.
+    let rc = check(unsafe { fec_ecdh_derive_key(ctx.raw, C::ID, kk.as_ptr(), xy.as_ptr(), inf.as_ptr(), if info.is_empty() { core::ptr::null() } else { info.as_ptr() }, info.len(), output_len, if keys.is_empty() { core::ptr::null_mut() } else { keys.as_mut_ptr() }, status.as_mut_ptr(), n) });
+    kk.iter_mut().for_each(|w| *w = 0);
+    rc?;
+    Ok((0..n).map(|i| match status[i] {
+        0 => Ok(keys[i * output_len..(i + 1) * output_len].to_vec()),
+        st => Err(exchange_error::<C>(st)),
+    }).collect())
+}
+
+/// `KeyExchange::exchange(rng, &peers[i], info, output_len)` per element (`forge-ec-core/src/lib.rs:1154-1174`) with the
+/// private keys drawn by the caller -- `C::Scalar::random(rng)`, the reference's own draw -- and everything after it on
+/// the GPU (`fec_ecdh_exchange`): the public key `to_affine(multiply(generator(), sk))`, `derive_shared_secret`,
+/// `derive_key`.  There is no key check, as in the reference.  An `Err` carries no public key.
+pub fn ecdh_exchange_batch<C: GpuCurve>(ctx: &mut GpuContext, private_keys: &[C::Scalar], peers: &[C::PointAffine], info: &[u8], output_len: usize) -> Result<Vec<Result<(C::PointAffine, Vec<u8>)>>> {
+    let n = private_keys.len();
+    if peers.len() != n {
+        return Err(Error::ValidationError);
+    }
+    let mut kk = pack_scalars::<C>(private_keys);
+    let (xy, inf) = marshal_affine::<C>(peers);
+    let (mut pub_xy, mut pub_inf, mut keys, mut status) = (vec![0u64; 8 * n], vec![0u8; n], vec![0u8; n * output_len], vec![0u8; n]);
+    // SAFETY: every buffer holds n elements of the width the header states; null stands for an empty array.
+    let rc = check(unsafe { fec_ecdh_exchange(ctx.raw, C::ID, kk.as_ptr(), xy.as_ptr(), inf.as_ptr(), if info.is_empty() { core::ptr::null() } else { info.as_ptr() }, info.len(), output_len, pub_xy.as_mut_ptr(), pub_inf.as_mut_ptr(), if keys.is_empty() { core::ptr::null_mut() } else { keys.as_mut_ptr() }, status.as_mut_ptr(), n) });
+    kk.iter_mut().for_each(|w| *w = 0);
+    rc?;
+    Ok((0..n).map(|i| match status[i] {
+        0 => Ok((C::affine_from_limbs(&pub_xy[8 * i..8 * i + 8], pub_inf[i] != 0), keys[i * output_len..(i + 1) * output_len].to_vec())),
+        st => Err(exchange_error::<C>(st)),
     }).collect())
 }
 
@@ -1177,6 +1255,30 @@ pub mod dev {
     /// As [`batch_mul`]; the caller owns and clears every buffer.
     pub unsafe fn batch_ecdh(ctx: &mut GpuContext, curve: c_int, d_private_keys: *const u64, d_pk_xy: *const u64, d_pk_inf: *const u8, d_secrets: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
         check(fec_batch_ecdh_dev(ctx.raw, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream))
+    }
+
+    /// `fec_derive_key_dev`.  `info` is a host slice.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn derive_key(ctx: &mut GpuContext, curve: c_int, d_secrets: *const u8, secret_len: usize, info: &[u8], out_len: usize, d_keys: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_derive_key_dev(ctx.raw, curve, d_secrets, secret_len, if info.is_empty() { core::ptr::null() } else { info.as_ptr() }, info.len(), out_len, d_keys, n, stream))
+    }
+
+    /// `fec_ecdh_derive_key_dev`.  `info` is a host slice.  The stream's scratch keeps the shared points until the ctx is wiped.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn ecdh_derive_key(ctx: &mut GpuContext, curve: c_int, d_private_keys: *const u64, d_pk_xy: *const u64, d_pk_inf: *const u8, info: &[u8], out_len: usize, d_keys: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_ecdh_derive_key_dev(ctx.raw, curve, d_private_keys, d_pk_xy, d_pk_inf, if info.is_empty() { core::ptr::null() } else { info.as_ptr() }, info.len(), out_len, d_keys, d_status, n, stream))
+    }
+
+    /// `fec_ecdh_exchange_dev`.  `info` is a host slice.  The stream's scratch keeps both products until the ctx is wiped.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn ecdh_exchange(ctx: &mut GpuContext, curve: c_int, d_private_keys: *const u64, d_peer_xy: *const u64, d_peer_inf: *const u8, info: &[u8], out_len: usize, d_public_xy: *mut u64, d_public_inf: *mut u8, d_keys: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_ecdh_exchange_dev(ctx.raw, curve, d_private_keys, d_peer_xy, d_peer_inf, if info.is_empty() { core::ptr::null() } else { info.as_ptr() }, info.len(), out_len, d_public_xy, d_public_inf, d_keys, d_status, n, stream))
     }
 
     /// `fec_x25519_dev`.
