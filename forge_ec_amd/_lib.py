@@ -22,6 +22,8 @@ ABI_SYMBOLS = [
     "fec_scalar_from_bytes_reduced", "fec_scalar_from_bytes_reduced_dev", "fec_schnorr_challenge", "fec_schnorr_challenge_dev",
     "fec_schnorr_sign_msg", "fec_schnorr_sign_msg_dev",
     "fec_derive_key", "fec_derive_key_dev", "fec_ecdh_derive_key", "fec_ecdh_derive_key_dev", "fec_ecdh_exchange", "fec_ecdh_exchange_dev",
+    "fec_expand_message_xmd", "fec_expand_message_xmd_dev", "fec_hash_to_field", "fec_hash_to_field_dev", "fec_map_to_curve",
+    "fec_map_to_curve_dev", "fec_hash_to_curve", "fec_hash_to_curve_dev", "fec_curve_hash_to_curve", "fec_curve_hash_to_curve_dev",
 ]
 # include/fecgpu_canon.h: the canonical-math mode (NOT reference parity)
 CANON_ABI_SYMBOLS = [
@@ -224,6 +226,19 @@ def lib():
     L.fec_ecdh_exchange_dev.argtypes = [vp, ci, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]
     for n in ("fec_derive_key", "fec_derive_key_dev", "fec_ecdh_derive_key", "fec_ecdh_derive_key_dev", "fec_ecdh_exchange",
               "fec_ecdh_exchange_dev"):
+        getattr(L, n).restype = ci
+    L.fec_expand_message_xmd.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, sz]
+    L.fec_expand_message_xmd_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp, vp, sz, vp]
+    L.fec_hash_to_field.argtypes = [vp, ci, vp, vp, sz, vp, sz, sz, vp, sz]
+    L.fec_hash_to_field_dev.argtypes = [vp, ci, vp, vp, sz, vp, sz, sz, vp, vp, sz, vp]
+    L.fec_map_to_curve.argtypes = [vp, ci, vp, vp, vp, vp, sz]
+    L.fec_map_to_curve_dev.argtypes = [vp, ci, vp, vp, vp, vp, sz, vp]
+    L.fec_hash_to_curve.argtypes = [vp, ci, ci, ci, vp, vp, sz, vp, sz, vp, vp, vp, sz]
+    L.fec_hash_to_curve_dev.argtypes = [vp, ci, ci, ci, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]
+    L.fec_curve_hash_to_curve.argtypes = [vp, ci, vp, vp, sz, vp, sz, vp, vp, sz]
+    L.fec_curve_hash_to_curve_dev.argtypes = [vp, ci, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp]
+    for n in ("fec_expand_message_xmd", "fec_expand_message_xmd_dev", "fec_hash_to_field", "fec_hash_to_field_dev", "fec_map_to_curve",
+              "fec_map_to_curve_dev", "fec_hash_to_curve", "fec_hash_to_curve_dev", "fec_curve_hash_to_curve", "fec_curve_hash_to_curve_dev"):
         getattr(L, n).restype = ci
     L.fec_ctx_set_chunk.argtypes = [vp, sz]
     L.fec_ctx_set_chunk.restype = ci

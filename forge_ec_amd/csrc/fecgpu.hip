@@ -24,6 +24,7 @@
 #include "p256.hpp"
 #include "secp256k1.hpp"
 #include "hkdf.hpp"
+#include "h2c.hpp"
 #include "host_ctx.hpp"
 #include "kernels.hpp"
 #include "cu_split.hpp"
@@ -1596,6 +1597,76 @@ int schnorr_challenge_call(fec_ctx* ctx, int curve, const uint64_t* r_xy, const 
     });
   });
 }
+
+// ---- HashToCurve (fecgpu.h; h2c.hpp; kernels_h2c.hip) ----
+// What one call computes: the expander alone, hash_to_field, or the fused kernel in one of its forms.
+enum { kH2cXmd, kH2cField, kH2cCurve };
+struct H2cCall {
+  int kind, curve, form;
+  h2c::Params p;
+};
+// One pass and no work area, except P-256's H2C_HASH (kernels_h2c.hip: split at the map boundary); the uniform part
+// travels with the launch.
+int launch_h2c(fec_ctx* ctx, const H2cCall& c, const H2cMessages& m, void* out, unsigned char* inf, void* cand, unsigned char* legs,
+               unsigned char* status, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  void* work = nullptr;
+  WorkArea area;   // (held until the launches are enqueued)
+  if (c.kind == kH2cCurve && h2c_work_bytes(c.curve, c.form, n) != 0) {
+    area.add(work, h2c_work_bytes(c.curve, c.form, n));
+    const int rc = area.acquire(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    if (rc != FEC_OK) return rc;
+  }
+  Launch L(ctx, stream, c.kind == kH2cXmd ? "k_xmd" : (c.kind == kH2cField ? "k_hash_to_field" : (work ? "k_h2c + k_h2c_add" : "k_h2c")));
+  if (c.kind == kH2cXmd) xmd_launch(m, c.p, static_cast<unsigned char*>(out), status, n, L.s);
+  else if (c.kind == kH2cField) hash_to_field_launch(c.curve, m, c.p, static_cast<u32*>(out), status, n, L.s);
+  else h2c_launch(c.curve, c.form, m, c.p, static_cast<u32*>(out), inf, static_cast<u32*>(cand), legs, status, work, n, L.s);
+  return L.done();
+}
+int launch_map_to_curve(fec_ctx* ctx, int curve, const u32* u, u32* xy, u32* cand, unsigned char* legs, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_map_to_curve");
+  map_to_curve_launch(curve, u, xy, cand, legs, n, L.s);
+  return L.done();
+}
+// The host forms: the engine as msg_call uses it, one lane, the chunk's messages in the same two slots.  The messages may
+// be secret (passwords), so every output is staged as one: the staging and the stream scratch are cleared on every way out.
+// A stride of 0 or a null pointer: the array is absent.
+int h2c_msg_call(fec_ctx* ctx, const H2cCall& c, const uint8_t* msgs, const uint64_t* off, size_t msg_len, void* out, size_t out_stride,
+                 uint8_t* inf, void* cand, size_t cand_stride, uint8_t* legs, size_t legs_stride, size_t n) {
+  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  const HostArray a[] = {ragged(off, 8), secret_output(out_stride ? out : nullptr, out_stride), secret_output(inf, 1),
+                         secret_output(cand_stride ? cand : nullptr, cand_stride), secret_output(legs_stride ? legs : nullptr, legs_stride)};
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[5], size_t cnt, size_t) {
+    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
+    return chunked(child, cnt, sa, 1, [&](fec_ctx* cc, void* const* d, size_t, size_t m, hipStream_t st) -> int {
+      H2cMessages hm{nullptr, nullptr, 0};
+      const int rc = stage_messages(cc, msgs, static_cast<const u64*>(d[0]), m, reb, st, hm.msgs, hm.off, hm.msg_len);
+      if (rc != FEC_OK) return rc;
+      return launch_h2c(cc, c, hm, d[1], static_cast<unsigned char*>(d[2]), d[3], static_cast<unsigned char*>(d[4]), nullptr, m, st);
+    });
+  });
+}
+// The checks every form shares.  The bounds exist because the reference writes dst.len() and the block counter into a u8.
+int h2c_args(fec_ctx* ctx, int curve, const uint8_t* dst, size_t dst_len) {
+  if (!ctx || !curve_ok(curve) || (dst_len && !dst)) return FEC_E_ARG;
+  if (curve == FEC_ED25519) return FEC_E_UNSUPPORTED;   // Ed25519 implements no HashToCurve
+  if (dst_len > h2c::MAX_DST) return FEC_E_UNSUPPORTED;
+  return FEC_OK;
+}
+int h2c_mode_args(fec_ctx* ctx, int curve, int mode, int method, const uint8_t* dst, size_t dst_len) {
+  const int rc = h2c_args(ctx, curve, dst, dst_len);
+  if (rc != FEC_OK) return rc;
+  if (mode != FEC_H2C_HASH && mode != FEC_H2C_ENCODE) return FEC_E_ARG;
+  if (method == FEC_H2C_ICART || method == FEC_H2C_ELLIGATOR2) return FEC_E_UNSUPPORTED;
+  if (method != FEC_H2C_SWU) return FEC_E_ARG;
+  return dst_len == 0 ? FEC_E_ARG : FEC_OK;   // Err(DomainSeparationFailure), before any element is looked at
+}
+int h2c_count_args(size_t count) { return count == 0 ? FEC_E_ARG : (count > h2c::MAX_COUNT ? FEC_E_UNSUPPORTED : FEC_OK); }
+// the _dev forms' pointer rules for the message arrays
+bool h2c_dev_msgs_ok(const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, size_t n) {
+  return !(n && !d_msg_off) && !(msg_len && !d_msgs) && (reinterpret_cast<uintptr_t>(d_msg_off) & 7u) == 0;
+}
 }  // namespace
 
 extern "C" {
@@ -2956,6 +3027,120 @@ int fec_schnorr_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk
   const SchnorrSignIo io{reinterpret_cast<const u32*>(d_sk), d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len,
                          reinterpret_cast<u32*>(d_r_xy), d_r_inf, reinterpret_cast<u32*>(d_s), reinterpret_cast<u32*>(d_sig_bytes), d_status};
   return launch_schnorr_sign(ctx, curve, io, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+// ---- HashToCurve (kernels_h2c.hip; helpers above the extern "C" block) ----
+
+int fec_expand_message_xmd(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* dst, size_t dst_len,
+                           size_t out_len, uint8_t* out, size_t n) try {
+  if (!ctx || (dst_len && !dst)) return FEC_E_ARG;
+  if (dst_len > h2c::MAX_DST || out_len > h2c::MAX_OUT) return FEC_E_UNSUPPORTED;
+  if (n && out_len && !out) return FEC_E_ARG;
+  const H2cCall c{kH2cXmd, 0, 0, h2c::make_params(dst, dst_len, out_len)};
+  return h2c_msg_call(ctx, c, msgs, msg_off, msg_len, out, out_len, nullptr, nullptr, 0, nullptr, 0, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_expand_message_xmd_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, const uint8_t* dst,
+                               size_t dst_len, size_t out_len, uint8_t* d_out, uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || (dst_len && !dst)) return FEC_E_ARG;
+  if (dst_len > h2c::MAX_DST || out_len > h2c::MAX_OUT) return FEC_E_UNSUPPORTED;
+  if (!h2c_dev_msgs_ok(d_msgs, d_msg_off, msg_len, n) || (n && out_len && !d_out) || !aligned16(d_out)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const H2cCall c{kH2cXmd, 0, 0, h2c::make_params(dst, dst_len, out_len)};
+  return launch_h2c(ctx, c, H2cMessages{d_msgs, d_msg_off, (u64)msg_len}, d_out, nullptr, nullptr, nullptr, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_hash_to_field(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* dst,
+                      size_t dst_len, size_t count, uint64_t* u, size_t n) try {
+  int rc = h2c_args(ctx, curve, dst, dst_len);
+  if (rc == FEC_OK) rc = h2c_count_args(count);
+  if (rc != FEC_OK) return rc;
+  if (n && !u) return FEC_E_ARG;
+  const H2cCall c{kH2cField, curve, 0, h2c::make_params(dst, dst_len, 32 * count)};
+  return h2c_msg_call(ctx, c, msgs, msg_off, msg_len, u, 32 * count, nullptr, nullptr, 0, nullptr, 0, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_hash_to_field_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                          const uint8_t* dst, size_t dst_len, size_t count, uint64_t* d_u, uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  int rc = h2c_args(ctx, curve, dst, dst_len);
+  if (rc == FEC_OK) rc = h2c_count_args(count);
+  if (rc != FEC_OK) return rc;
+  if (!h2c_dev_msgs_ok(d_msgs, d_msg_off, msg_len, n) || (n && !d_u) || !aligned16(d_u)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const H2cCall c{kH2cField, curve, 0, h2c::make_params(dst, dst_len, 32 * count)};
+  return launch_h2c(ctx, c, H2cMessages{d_msgs, d_msg_off, (u64)msg_len}, d_u, nullptr, nullptr, nullptr, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_map_to_curve(fec_ctx* ctx, fec_curve curve, const uint64_t* u, uint64_t* xy, uint64_t* cand, uint8_t* legs, size_t n) try {
+  if (!ctx || !curve_ok(curve) || (n && (!u || !xy))) return FEC_E_ARG;
+  if (curve == FEC_ED25519) return FEC_E_UNSUPPORTED;
+  const HostArray a[] = {secret_input(u, 32), secret_output(xy, 64), secret_output(cand, 64), secret_output(legs, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_map_to_curve(c, curve, static_cast<const u32*>(d[0]), static_cast<u32*>(d[1]), static_cast<u32*>(d[2]),
+                               static_cast<unsigned char*>(d[3]), m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_map_to_curve_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_u, uint64_t* d_xy, uint64_t* d_cand, uint8_t* d_legs, size_t n,
+                         void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  if (!ctx || !curve_ok(curve) || (n && (!d_u || !d_xy))) return FEC_E_ARG;
+  if (curve == FEC_ED25519) return FEC_E_UNSUPPORTED;
+  if (!aligned16(d_u) || !aligned16(d_xy) || !aligned16(d_cand)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_map_to_curve(ctx, curve, reinterpret_cast<const u32*>(d_u), reinterpret_cast<u32*>(d_xy), reinterpret_cast<u32*>(d_cand),
+                             d_legs, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_hash_to_curve(fec_ctx* ctx, fec_curve curve, int mode, int method, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                      const uint8_t* dst, size_t dst_len, uint64_t* out, uint64_t* cand, uint8_t* legs, size_t n) try {
+  const int rc = h2c_mode_args(ctx, curve, mode, method, dst, dst_len);
+  if (rc != FEC_OK) return rc;
+  if (n && !out) return FEC_E_ARG;
+  const size_t maps = mode == FEC_H2C_HASH ? 2 : 1;
+  const H2cCall c{kH2cCurve, curve, mode == FEC_H2C_HASH ? H2C_HASH : H2C_ENCODE, h2c::make_params(dst, dst_len, 32 * maps)};
+  return h2c_msg_call(ctx, c, msgs, msg_off, msg_len, out, 96, nullptr, cand, 64 * maps, legs, maps, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_hash_to_curve_dev(fec_ctx* ctx, fec_curve curve, int mode, int method, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                          size_t msg_len, const uint8_t* dst, size_t dst_len, uint64_t* d_out, uint64_t* d_cand, uint8_t* d_legs,
+                          uint8_t* d_status, size_t n, void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  const int rc = h2c_mode_args(ctx, curve, mode, method, dst, dst_len);
+  if (rc != FEC_OK) return rc;
+  if (!h2c_dev_msgs_ok(d_msgs, d_msg_off, msg_len, n) || (n && !d_out) || !aligned16(d_out) || !aligned16(d_cand)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const size_t maps = mode == FEC_H2C_HASH ? 2 : 1;
+  const H2cCall c{kH2cCurve, curve, mode == FEC_H2C_HASH ? H2C_HASH : H2C_ENCODE, h2c::make_params(dst, dst_len, 32 * maps)};
+  return launch_h2c(ctx, c, H2cMessages{d_msgs, d_msg_off, (u64)msg_len}, d_out, nullptr, d_cand, d_legs, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+// (secp256k1: 96 uniform bytes under dst_prime; P-256: the plain template, SHA-256(msg || dst))
+static h2c::Params curve_h2c_params(int curve, const uint8_t* dst, size_t dst_len) {
+  return curve == FEC_SECP256K1 ? h2c::make_params(dst, dst_len, 96) : h2c::make_params_plain(dst, dst_len);
+}
+
+int fec_curve_hash_to_curve(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                            const uint8_t* dst, size_t dst_len, uint64_t* xy, uint8_t* inf, size_t n) try {
+  const int rc = h2c_args(ctx, curve, dst, dst_len);
+  if (rc != FEC_OK) return rc;
+  if (n && (!xy || !inf)) return FEC_E_ARG;
+  const H2cCall c{kH2cCurve, curve, H2C_TRAIT, curve_h2c_params(curve, dst, dst_len)};
+  return h2c_msg_call(ctx, c, msgs, msg_off, msg_len, xy, 64, inf, nullptr, 0, nullptr, 0, n);
+} FEC_ABI_CATCH_STATUS
+
+int fec_curve_hash_to_curve_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                const uint8_t* dst, size_t dst_len, uint64_t* d_xy, uint8_t* d_inf, uint8_t* d_status, size_t n,
+                                void* stream) try {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
+  const int rc = h2c_args(ctx, curve, dst, dst_len);
+  if (rc != FEC_OK) return rc;
+  if (!h2c_dev_msgs_ok(d_msgs, d_msg_off, msg_len, n) || (n && (!d_xy || !d_inf)) || !aligned16(d_xy)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const H2cCall c{kH2cCurve, curve, H2C_TRAIT, curve_h2c_params(curve, dst, dst_len)};
+  return launch_h2c(ctx, c, H2cMessages{d_msgs, d_msg_off, (u64)msg_len}, d_xy, d_inf, nullptr, nullptr, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 // Debug hook: fec_rfc6979_k with the caller's comparison constant instead of the curve's.  At least 2^254, so that a

@@ -288,6 +288,31 @@ void ecdh_exchange_finish_launch(int curve, const u32* pub, const u32* t, const 
                                  u32* public_xy, unsigned char* public_inf, unsigned char* keys, unsigned char* status, size_t n,
                                  hipStream_t s);
 
+// kernels_h2c.hip: HashToCurve for secp256k1 / P-256 (h2c.hpp: the readings and h2c::Params, the launch's uniform part
+// -- dst as a padded block template and the lengths).  Messages as above; a bad range: status 4 (may be null) and zero
+// outputs.  xmd: p.out_len bytes per element, packed, behind a 16-byte aligned base (may be null when out_len is 0).
+// hash_to_field: p.out_len / 32 field elements of 8 words per element.  map_to_curve: u 8 words, xy 16 words, cand (may
+// be null) 16 words -- x then y2 -- and legs (may be null) one byte per element.  h2c: form H2C_HASH / H2C_ENCODE (equal
+// to FEC_H2C_HASH / FEC_H2C_ENCODE) write 24 words to out; H2C_TRAIT, the trait method with its to_affine, 16 words and
+// inf; cand and legs (may be null) hold one entry per map: two for H2C_HASH and for secp256k1's H2C_TRAIT, else one.
+// `work` holds h2c_work_bytes(curve, form, n) bytes: nonzero for the one form that is split at the map boundary, P-256's
+// H2C_HASH (two mapped points and a flag per element; secret).
+namespace h2c {
+struct Params;
+}
+struct H2cMessages {
+  const unsigned char* msgs;
+  const u64* off;
+  u64 msg_len;
+};
+constexpr int H2C_HASH = 0, H2C_ENCODE = 1, H2C_TRAIT = 2, H2C_MAPS = 3;   // (H2C_MAPS: inside kernels_h2c.hip only)
+void xmd_launch(const H2cMessages& m, const h2c::Params& p, unsigned char* out, unsigned char* status, size_t n, hipStream_t s);
+void hash_to_field_launch(int curve, const H2cMessages& m, const h2c::Params& p, u32* u, unsigned char* status, size_t n, hipStream_t s);
+void map_to_curve_launch(int curve, const u32* u, u32* xy, u32* cand, unsigned char* legs, size_t n, hipStream_t s);
+void h2c_launch(int curve, int form, const H2cMessages& m, const h2c::Params& p, u32* out, unsigned char* inf, u32* cand,
+                unsigned char* legs, unsigned char* status, void* work, size_t n, hipStream_t s);
+size_t h2c_work_bytes(int curve, int form, size_t n);
+
 // kernels_ecdsa.hip: Eddsa verify around the Ed25519 multiplications (eddsa.rs:174-211, 430-447).
 // eddsa_pre_launch: a[i] = from_affine(pk[i]) (32 words); eddsa_finish_launch: status from sg = multiply(G, s),
 // ka = multiply(A, k), R.

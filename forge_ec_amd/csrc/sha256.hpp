@@ -146,6 +146,78 @@ FEC_DEV state hash_prefixed(const u32 (&pre)[PW], u32 plen, const unsigned char*
   return st;
 }
 
+// The state after one block of 64 zero bytes (Z_pad of RFC 9380's expand_message_xmd, h2c.hpp): compress(init(), {0}).
+FEC_DEV state after_zero_block() {
+  state s;
+  s.h[0] = 0xda5698beu;
+  s.h[1] = 0x17b9b469u;
+  s.h[2] = 0x62335799u;
+  s.h[3] = 0x779fbecau;
+  s.h[4] = 0x8ce5d491u;
+  s.h[5] = 0xc0d26243u;
+  s.h[6] = 0xbafef9eau;
+  s.h[7] = 0x1837a9d8u;
+  return s;
+}
+
+// SHA-256 continued from `st`, which has absorbed `done` bytes (a multiple of 64), over  msg[0 .. len) || tail, which
+// hash_prefixed cannot express: the tail follows the message, so it sits at another byte offset on every lane.  The tail
+// is the same for the whole launch and comes as a TEMPLATE of big-endian words: tmpl[0] is zero, the tail's bytes start
+// at tmpl[1], the 0x80 of the padding follows its last byte (tlen counts the tail without it) and every word from there
+// to tmpl[TW - 1] is zero, with at least one zero word at the end.  A block that reaches past the message takes 17
+// consecutive template words from a per-lane index -- clamped into [0, TW - 1], so that both ends read zeros -- and
+// funnel-shifts them into place; the message's bytes are loaded as hash_prefixed loads them.
+template <int TW>
+FEC_DEV state hash_msg_tail(state st, u32 done, const unsigned char* msg, u64 len, const u32 (&tmpl)[TW], u32 tlen) {
+  const u64 total = len + tlen;                      // stream bytes of this call before the padding
+  const u64 nblocks = (total + 9 + 63) >> 6;
+  const u64 bits = ((u64)done + total) << 3;
+  const u64 m0 = (u64)(uintptr_t)msg;
+  const u64 first = m0 & ~(u64)3, last = len ? ((m0 + len - 1) & ~(u64)3) : first;
+#pragma unroll 1
+  for (u64 b = 0; b < nblocks; ++b) {
+    const u64 S = b << 6;
+    u32 wd[16];
+    FEC_UNROLL for (int j = 0; j < 16; ++j) wd[j] = 0u;
+    if (S < len) {                                   // the block holds message bytes
+      const u64 X = m0 + S;
+      const u64 base = X & ~(u64)3;
+      const u32 sh = (u32)(X & 3) * 8;
+      u32 d[17];
+      FEC_UNROLL for (int k = 0; k < 17; ++k) {
+        u64 a = base + 4 * (u64)k;
+        a = a < first ? first : (a > last ? last : a);
+        d[k] = *reinterpret_cast<const u32*>((uintptr_t)a);
+      }
+      const int tl = len - S > 64 ? 64 : (int)(len - S);
+      FEC_UNROLL for (int j = 0; j < 16; ++j) {
+        const u32 le = funnel(d[j + 1], d[j], sh);
+        int hi = tl - 4 * j;
+        hi = hi < 0 ? 0 : (hi > 4 ? 4 : hi);
+        wd[j] |= bswap(le) & (u32)~(0xFFFFFFFFull >> (8 * hi));
+      }
+    }
+    if (S + 64 > len) {                              // the block holds bytes of the tail or of its padding
+      const long long k0 = (long long)S - (long long)len;   // the tail byte at the block's first byte (below 0: message)
+      const long long q = k0 >> 2;
+      const u32 r = (u32)(k0 & 3);
+      u32 t[17];
+      FEC_UNROLL for (int k = 0; k < 17; ++k) {
+        long long ix = q + 1 + k;
+        ix = ix < 0 ? 0 : (ix > TW - 1 ? TW - 1 : ix);
+        t[k] = tmpl[ix];
+      }
+      FEC_UNROLL for (int j = 0; j < 16; ++j) wd[j] |= r == 0 ? t[j] : funnel(t[j], t[j + 1], 32 - 8 * r);
+    }
+    if (b + 1 == nblocks) {
+      wd[14] |= (u32)(bits >> 32);
+      wd[15] |= (u32)bits;
+    }
+    compress(st, wd);
+  }
+  return st;
+}
+
 // The 32 digest bytes as 8 little-endian memory words (digest byte 4k is the low byte of word k).
 FEC_DEV void digest_words(const state& st, u32 (&o)[8]) {
   FEC_UNROLL for (int i = 0; i < 8; ++i) o[i] = bswap(st.h[i]);

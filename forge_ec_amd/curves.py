@@ -275,6 +275,75 @@ class Context:
                                            _ptr(keys) if out_len else None, _ptr(st), n), "fec_ecdh_exchange")
         return pub, pinf, keys, st
 
+    # ---- HashToCurve (include/fecgpu.h: the readings, and the two facts about the reference's sqrt) ----
+    H2C_HASH, H2C_ENCODE = 0, 1
+    H2C_SWU, H2C_ICART, H2C_ELLIGATOR2 = 0, 1, 2
+
+    def expand_message_xmd(self, msgs, dst, out_len):
+        """expand_message_xmd::<Sha256>(msg, dst || len(dst), out_len) per message (hash_to_curve.rs:380-448; RFC 9380's):
+        msgs a list of n byte strings, dst one byte string (<= 255 bytes), out_len <= 8160.  Returns (n, out_len) uint8."""
+        buf, off, total = self._messages(msgs)
+        n = len(off) - 1
+        dp, dl = self._info(dst)
+        out = np.zeros((n, int(out_len)), dtype=np.uint8)
+        _check(self._lib.fec_expand_message_xmd(self._h, _ptr(buf), _ptr(off), total, dp, dl, int(out_len), _ptr(out) if out_len else None, n),
+               "fec_expand_message_xmd")
+        return out
+
+    def hash_to_field(self, curve, msgs, dst, count):
+        """HashToCurveSwu::hash_to_field(msg, dst, count) per message (hash_to_curve.rs:316-377): (n, count, 4) raw limbs."""
+        buf, off, total = self._messages(msgs)
+        n = len(off) - 1
+        dp, dl = self._info(dst)
+        u = np.zeros((n, max(int(count), 0), 4), dtype=np.uint64)
+        _check(self._lib.fec_hash_to_field(self._h, curve, _ptr(buf), _ptr(off), total, dp, dl, int(count), _ptr(u), n), "fec_hash_to_field")
+        return u
+
+    def map_to_curve(self, curve, u, with_cand=True, with_legs=True):
+        """C::map_to_curve on n x 4 raw limbs (secp256k1.rs:1587-1705, p256.rs:2215-2265).  Returns (xy (n, 8), cand (n, 8):
+        x then y^2 as computed, or None, legs (n,) uint8 or None)."""
+        uu = _u64(u, 4)
+        n = uu.shape[0]
+        xy = np.zeros((n, 8), dtype=np.uint64)
+        cand = np.zeros((n, 8), dtype=np.uint64) if with_cand else None
+        legs = np.zeros(n, dtype=np.uint8) if with_legs else None
+        _check(self._lib.fec_map_to_curve(self._h, curve, _ptr(uu), _ptr(xy), _ptr(cand), _ptr(legs), n), "fec_map_to_curve")
+        return xy, cand, legs
+
+    def _h2c(self, curve, mode, msgs, dst, with_cand, with_legs, method):
+        buf, off, total = self._messages(msgs)
+        n = len(off) - 1
+        maps = 2 if mode == self.H2C_HASH else 1
+        dp, dl = self._info(dst)
+        out = np.zeros((n, 12), dtype=np.uint64)
+        cand = np.zeros((n, maps, 8), dtype=np.uint64) if with_cand else None
+        legs = np.zeros((n, maps), dtype=np.uint8) if with_legs else None
+        _check(self._lib.fec_hash_to_curve(self._h, curve, mode, method, _ptr(buf), _ptr(off), total, dp, dl, _ptr(out), _ptr(cand),
+                                           _ptr(legs), n), "fec_hash_to_curve")
+        return out, cand, legs
+
+    def hash_to_curve(self, curve, msgs, dst, with_cand=True, with_legs=True, method=0):
+        """hash_to_curve::<C, Sha256>(msg, dst, SimplifiedSwu) per message (hash_to_curve.rs:254-312).  Returns (points
+        (n, 12) projective raw limbs, cand (n, 2, 8) or None, legs (n, 2) uint8 or None)."""
+        return self._h2c(curve, self.H2C_HASH, msgs, dst, with_cand, with_legs, method)
+
+    def encode_to_curve(self, curve, msgs, dst, with_cand=True, with_legs=True, method=0):
+        """encode_to_curve::<C, Sha256>(msg, dst, SimplifiedSwu) per message (hash_to_curve.rs:1030-1056).  Returns (points
+        (n, 12), cand (n, 1, 8) or None, legs (n, 1) uint8 or None)."""
+        return self._h2c(curve, self.H2C_ENCODE, msgs, dst, with_cand, with_legs, method)
+
+    def curve_hash_to_curve(self, curve, msgs, dst):
+        """The trait method C::hash_to_curve::<Sha256>(msg, &tag), dst = tag.as_bytes() = suite_id || dst
+        (secp256k1.rs:1712-1769; the default forge-ec-core/src/lib.rs:1550-1581 for P-256).  Returns (xy (n, 8), inf (n,))."""
+        buf, off, total = self._messages(msgs)
+        n = len(off) - 1
+        dp, dl = self._info(dst)
+        xy = np.zeros((n, 8), dtype=np.uint64)
+        inf = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_curve_hash_to_curve(self._h, curve, _ptr(buf), _ptr(off), total, dp, dl, _ptr(xy), _ptr(inf), n),
+               "fec_curve_hash_to_curve")
+        return xy, inf
+
     def ecdsa_sign(self, curve, sk, digests, k):
         """Ecdsa::<C, D>::sign per element (ecdsa.rs:98-211) for secp256k1 / P-256 after the hash and the nonce:
         sk (n,4), digests (n,32) uint8 (h_bytes), k (n,4) from Rfc6979::<C, D>::generate_k.  Returns (r (n,4),
@@ -807,6 +876,33 @@ class Context:
         ip, il = self._info(info)
         _check(self._lib.fec_ecdh_exchange_dev(self._h, curve, d_private_keys, d_peer_xy, d_peer_inf, ip, il, out_len, d_public_xy,
                                                d_public_inf, d_keys, d_status, n, stream), "fec_ecdh_exchange_dev")
+
+    def expand_message_xmd_dev(self, d_msgs, d_msg_off, msg_len, dst, out_len, d_out, d_status, n, stream=None):
+        """fec_expand_message_xmd_dev: `dst` is a host byte string (or None), everything else raw device addresses."""
+        dp, dl = self._info(dst)
+        _check(self._lib.fec_expand_message_xmd_dev(self._h, d_msgs, d_msg_off, msg_len, dp, dl, out_len, d_out, d_status, n, stream),
+               "fec_expand_message_xmd_dev")
+
+    def hash_to_field_dev(self, curve, d_msgs, d_msg_off, msg_len, dst, count, d_u, d_status, n, stream=None):
+        dp, dl = self._info(dst)
+        _check(self._lib.fec_hash_to_field_dev(self._h, curve, d_msgs, d_msg_off, msg_len, dp, dl, count, d_u, d_status, n, stream),
+               "fec_hash_to_field_dev")
+
+    def map_to_curve_dev(self, curve, d_u, d_xy, d_cand, d_legs, n, stream=None):
+        _check(self._lib.fec_map_to_curve_dev(self._h, curve, d_u, d_xy, d_cand, d_legs, n, stream), "fec_map_to_curve_dev")
+
+    def hash_to_curve_dev(self, curve, d_msgs, d_msg_off, msg_len, dst, d_out, d_cand, d_legs, d_status, n, stream=None, mode=0, method=0):
+        dp, dl = self._info(dst)
+        _check(self._lib.fec_hash_to_curve_dev(self._h, curve, mode, method, d_msgs, d_msg_off, msg_len, dp, dl, d_out, d_cand, d_legs,
+                                               d_status, n, stream), "fec_hash_to_curve_dev")
+
+    def encode_to_curve_dev(self, curve, d_msgs, d_msg_off, msg_len, dst, d_out, d_cand, d_legs, d_status, n, stream=None, method=0):
+        self.hash_to_curve_dev(curve, d_msgs, d_msg_off, msg_len, dst, d_out, d_cand, d_legs, d_status, n, stream, self.H2C_ENCODE, method)
+
+    def curve_hash_to_curve_dev(self, curve, d_msgs, d_msg_off, msg_len, dst, d_xy, d_inf, d_status, n, stream=None):
+        dp, dl = self._info(dst)
+        _check(self._lib.fec_curve_hash_to_curve_dev(self._h, curve, d_msgs, d_msg_off, msg_len, dp, dl, d_xy, d_inf, d_status, n, stream),
+               "fec_curve_hash_to_curve_dev")
 
     def x25519_dev(self, d_scalars, d_u, d_out, n, stream=None):
         _check(self._lib.fec_x25519_dev(self._h, d_scalars, d_u, d_out, n, stream), "fec_x25519_dev")

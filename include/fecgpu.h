@@ -36,6 +36,11 @@
  *                         (the XOR placeholder: p256.rs:2314-2344)
  *   fec_ecdh_derive_key   derive_shared_secret followed by derive_key; the x coordinate never leaves the device
  *   fec_ecdh_exchange     KeyExchange::exchange with the caller's private key (forge-ec-core/src/lib.rs:1154-1174)
+ *   fec_expand_message_xmd   expand_message_xmd::<Sha256> (forge-ec-hash/src/hash_to_curve.rs:380-448): RFC 9380's
+ *   fec_hash_to_field     HashToCurveSwu::hash_to_field with os2ip_mod_p (hash_to_curve.rs:316-377)
+ *   fec_map_to_curve      HashToCurve::map_to_curve for secp256k1 / P-256 (secp256k1.rs:1587-1705, p256.rs:2215-2265)
+ *   fec_hash_to_curve     hash_to_curve / encode_to_curve with SimplifiedSwu (hash_to_curve.rs:254-312, 1030-1056)
+ *   fec_curve_hash_to_curve   the trait method C::hash_to_curve::<Sha256> (secp256k1.rs:1712-1769; core lib.rs:1550-1581)
  *   fec_ecdsa_sign        Ecdsa::<C, D>::sign for secp256k1 / P-256 after the hash and the RFC 6979 nonce
  *                         (ecdsa.rs:45-71, 98-211; scalar Sub secp256k1.rs:2380-2408, p256.rs:1377-1408)
  *   fec_ed25519_sign      Ed25519Signature::sign with SHA-512, hash included (forge-ec-signature/src/eddsa.rs:267-356)
@@ -139,6 +144,11 @@ typedef enum {
   FEC_P_NEGATE = 2,
   FEC_P_DOUBLE_TRAIT = 3  /* secp256k1 only: trait PointProjective::double (secp256k1.rs:1375) */
 } fec_point_opcode;
+/* fec_hash_to_curve: which function, and which HashToCurveMethod (only SimplifiedSwu is offered) */
+typedef enum { FEC_H2C_HASH = 0, FEC_H2C_ENCODE = 1 } fec_h2c_mode;
+typedef enum { FEC_H2C_SWU = 0, FEC_H2C_ICART = 1, FEC_H2C_ELLIGATOR2 = 2 } fec_h2c_method;
+/* bits of the `legs` outputs of fec_map_to_curve and fec_hash_to_curve */
+enum { FEC_H2C_LEG_U_ZERO = 1, FEC_H2C_LEG_INV_ZERO = 2, FEC_H2C_LEG_SQRT_NONE = 4, FEC_H2C_LEG_NEGATE = 8, FEC_H2C_LEG_OS2IP = 16 };
 
 typedef struct fec_ctx fec_ctx;
 
@@ -792,6 +802,90 @@ int fec_ecdh_exchange(fec_ctx* ctx, fec_curve curve, const uint64_t* private_key
 int fec_ecdh_exchange_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_keys, const uint64_t* d_peer_xy,
                           const uint8_t* d_peer_inf, const uint8_t* info, size_t info_len, size_t out_len, uint64_t* d_public_xy,
                           uint8_t* d_public_inf, uint8_t* d_keys, uint8_t* d_status, size_t n, void* stream);
+
+/* ---- HashToCurve: expand_message_xmd, hash_to_field, map_to_curve, hash / encode (forge-ec-hash/src/hash_to_curve.rs =
+ * h2c below; the trait forge-ec-core/src/lib.rs:1450-1581), parity mode, D = Sha256 ----
+ * Messages: layout, alignment rules and status 4 are those of the "SHA-256 ..." block above (msgs, msg_off with n + 1 values,
+ * msg_len); in the _dev forms each element checks its own range, a bad range gets status 4 (d_status may be NULL) and zero
+ * outputs.  The _dev forms take 16-byte aligned arrays and an 8-byte aligned d_msg_off, have `stream` last, only enqueue, and
+ * return FEC_E_UNSUPPORTED on a multi-device ctx; the host forms chunk by fec_ctx_set_chunk and shard over a multi-device ctx.
+ * curve = FEC_SECP256K1 or FEC_P256; FEC_ED25519: FEC_E_UNSUPPORTED (it implements no HashToCurve).
+ * `dst` is a HOST pointer in both forms, one string for the whole batch, dst_len <= 255 (above: FEC_E_UNSUPPORTED -- the
+ * reference appends `dst.len() as u8`, which would wrap) and may be NULL when dst_len == 0.  It travels with the launch, as a
+ * padded block template among the kernel arguments.
+ *
+ * TWO FACTS ABOUT THE REFERENCE that decide what every result looks like:
+ *   - Its map_to_curve calls the INHERENT FieldElement::sqrt (secp256k1.rs:112-131, p256.rs:320-339), whose exponents are wrong;
+ *     in a trial over 80 hashed inputs per curve it returned None every time.  On secp256k1 the map therefore returns its
+ *     default_point (1681-1695: the generator's coordinates written as raw limbs with the most significant 64 bits in limb
+ *     0, reproduced literally), and FEC_H2C_HASH returns default + default for every input anyone can find.  On P-256 the
+ *     map returns (x, +-1) with an x that varies with the message.
+ *   - The whole computation runs all the same; `cand` and `legs` report it (below), so that a caller -- and the tests -- can
+ *     tell the computation from a constant.
+ *
+ * fec_expand_message_xmd   out[i] = the first out_len bytes of expand_message_xmd::<Sha256>(msg_i, dst || len(dst), out_len)
+ *   (h2c:380-448; the copy at secp256k1.rs:1774-1840 is identical).  This IS RFC 9380's function (its K.1 vectors are in
+ *   tests/golden/h2c_vectors.json).  out_len <= 8160 = 255 * 32, FEC_E_UNSUPPORTED above it: the block counter is `i as u8`.
+ *   out_len == 0 is legal (`out` may be NULL), dst_len == 0 too.  Rows are packed, nothing past n * out_len is written.
+ * fec_hash_to_field   u[i][j], j < count, four raw limbs each = HashToCurveSwu::hash_to_field(msg_i, dst, count) (316-348):
+ *   32 * count uniform bytes, so count = 1 and count = 2 do not share u[0].  1 <= count <= 255 (0: FEC_E_ARG; above:
+ *   FEC_E_UNSUPPORTED, the expander's bound).  Each element goes through os2ip_mod_p (355-377): the TRAIT
+ *   FieldElement::from_bytes, which forwards to the inherent form -- big-endian, None iff not below p; secp256k1's returns
+ *   the Montgomery form, P-256's the limbs as read -- and None gives one(), the raw limb 1 on both curves.
+ * fec_map_to_curve   xy[i] (affine raw limbs, never infinite) = C::map_to_curve(&FieldElement::from_raw(u[i])), on whatever
+ *   four limbs the caller passes.  Inherent methods win over trait methods: on secp256k1 `sqrt` and `to_bytes` are the
+ *   inherent forms, `invert`, `square`, `is_zero` the trait's; on P-256 `invert`, `sqrt`, `to_bytes` are inherent.
+ *   secp256k1 (1587-1705): a zero u is replaced by one; w.invert().unwrap_or(zero); sqrt.unwrap_or(zero); valid_point =
+ *   w != 0 && sqrt is Some, else the default point.  P-256 (2215-2265): tv2.invert().unwrap_or(one); x2 iff tv2 is zero;
+ *   sqrt().unwrap_or(one).  Two optional outputs, each may be NULL:
+ *     cand  n*8 limbs: x then y^2 as the reference computes them (1649 / 1654, 2251 / 2254), kept or not;
+ *     legs  n bytes: FEC_H2C_LEG_U_ZERO (u was zero and was replaced, secp256k1) | FEC_H2C_LEG_INV_ZERO (w / tv2 was zero) |
+ *           FEC_H2C_LEG_SQRT_NONE (sqrt was None) | FEC_H2C_LEG_NEGATE (the sign comparison asked for -y, as computed, used
+ *           or not).
+ * fec_hash_to_curve   mode FEC_H2C_HASH: out[i] (n*12 limbs, projective) = hash_to_curve::<C, Sha256>(msg_i, dst,
+ *   SimplifiedSwu) (254-278) = HashToCurveSwu::hash (292-312): two field elements, two maps, from_affine on each, the
+ *   curve's impl Add for ProjectivePoint, clear_cofactor (the identity function on both curves).  FEC_H2C_ENCODE:
+ *   encode_to_curve (1030-1056): one element (count = 1), one map, from_affine.  Another mode: FEC_E_ARG.  dst_len == 0:
+ *   FEC_E_ARG -- the reference's Err(DomainSeparationFailure), decided before any element is looked at.  method: only
+ *   FEC_H2C_SWU; FEC_H2C_ICART and FEC_H2C_ELLIGATOR2 return FEC_E_UNSUPPORTED: their generic bodies end in
+ *   PointAffine::new, which the reference's arithmetic answers None for practically every input (see fec_schnorr_verify).
+ *   cand: n*16 limbs (HASH) or n*8 (ENCODE); legs: n*2 bytes or n; both optional as above; legs also carries
+ *   FEC_H2C_LEG_OS2IP (os2ip_mod_p fell back to one()).  d_status: 0, or 4.
+ * fec_curve_hash_to_curve   (xy[i], inf[i]) = C::hash_to_curve::<Sha256>(msg_i, &tag) with dst = tag.as_bytes() = suite_id ||
+ *   dst.  secp256k1 has an override (1712-1769): 96 uniform bytes, the first 32 of each 48-byte half through the inherent
+ *   from_bytes, fallback from_raw([i + 1, 0, 0, 0]); two maps, add, to_affine.  P-256 keeps the trait default (core lib.rs:
+ *   1550-1581): ONE SHA-256 of msg || dst, from_bytes(..).unwrap_or(zero), one map, from_affine, to_affine.  Neither checks
+ *   for an empty dst, so dst_len == 0 is legal here.
+ * Legs no message is known to reach, forced on the CPU only (tests/test_h2c_host.py): the os2ip fallbacks (a hash not below
+ *   p: about 2^-32 on P-256, 2^-128 on secp256k1) and, on secp256k1, valid_point and w == 0 (a root of the reference's own
+ *   arithmetic).  fec_map_to_curve reaches u == 0 and every sign outcome on planted limbs.
+ * SECRETS: messages may be secret (passwords), and with them everything computed here.  The host forms clear their device
+ *   staging (messages in, every output) and the stream scratch on every way out, as fec_ed25519_sign does; the _dev forms
+ *   leave every buffer to the caller (P-256's FEC_H2C_HASH leaves its two mapped points in the stream's scratch until the
+ *   ctx is wiped, fec_ctx_wipe, or destroyed).  NOT constant-time: the message length decides the number of blocks. */
+int fec_expand_message_xmd(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len, const uint8_t* dst,
+                           size_t dst_len, size_t out_len, uint8_t* out /* n*out_len */, size_t n);
+int fec_expand_message_xmd_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, const uint8_t* dst,
+                               size_t dst_len, size_t out_len, uint8_t* d_out, uint8_t* d_status, size_t n, void* stream);
+int fec_hash_to_field(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                      const uint8_t* dst, size_t dst_len, size_t count, uint64_t* u /* n*count*4 */, size_t n);
+int fec_hash_to_field_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                          const uint8_t* dst, size_t dst_len, size_t count, uint64_t* d_u, uint8_t* d_status, size_t n, void* stream);
+int fec_map_to_curve(fec_ctx* ctx, fec_curve curve, const uint64_t* u /* n*4 */, uint64_t* xy /* n*8 */,
+                     uint64_t* cand /* n*8 or NULL */, uint8_t* legs /* n or NULL */, size_t n);
+int fec_map_to_curve_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_u, uint64_t* d_xy, uint64_t* d_cand, uint8_t* d_legs, size_t n,
+                         void* stream);
+int fec_hash_to_curve(fec_ctx* ctx, fec_curve curve, int mode, int method, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */,
+                      size_t msg_len, const uint8_t* dst, size_t dst_len, uint64_t* out /* n*12 */,
+                      uint64_t* cand /* n*16 | n*8, or NULL */, uint8_t* legs /* n*2 | n, or NULL */, size_t n);
+int fec_hash_to_curve_dev(fec_ctx* ctx, fec_curve curve, int mode, int method, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                          size_t msg_len, const uint8_t* dst, size_t dst_len, uint64_t* d_out, uint64_t* d_cand, uint8_t* d_legs,
+                          uint8_t* d_status, size_t n, void* stream);
+int fec_curve_hash_to_curve(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                            const uint8_t* dst, size_t dst_len, uint64_t* xy /* n*8 */, uint8_t* inf /* n */, size_t n);
+int fec_curve_hash_to_curve_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                const uint8_t* dst, size_t dst_len, uint64_t* d_xy, uint8_t* d_inf, uint8_t* d_status, size_t n,
+                                void* stream);
 
 /* Every element-wise host-pointer entry point processes its batch in chunks of `elements` elements
  * (default 2^18), so device staging memory is bounded by two chunks for any n.  Most run them as a

@@ -717,6 +717,117 @@ inline std::vector<eddsa::Bytes32> sha256(GpuContext& ctx, const std::vector<std
   return out;
 }
 }  // namespace sha2
+
+// ---- HashToCurve (fec_expand_message_xmd .. fec_curve_hash_to_curve): the reference's functions bit for bit, and so the
+// reference's results -- its map_to_curve calls an inherent sqrt that fails for every known input: secp256k1 returns ONE
+// constant point from hash_to_curve, P-256 a point (x, +-1).  NOT RFC 9380 points; see fecgpu.h.  Messages may be secret;
+// not constant-time.
+namespace hash_to_curve {
+// What map_to_curve did besides returning a point: the candidate x and y^2 as computed, kept or not, and FEC_H2C_LEG_* bits
+template <fec_curve C>
+struct MapTrace {
+  FieldElement<C> x, y2;
+  uint8_t legs = 0;
+};
+// expand_message_xmd::<Sha256>(msgs[i], dst || len(dst), out_len) (hash_to_curve.rs:380-448): RFC 9380's
+inline std::vector<std::vector<uint8_t>> expand_message_xmd(GpuContext& ctx, const std::vector<std::string>& msgs, const std::string& dst,
+                                                            size_t out_len) {
+  const eddsa::detail::Messages m(msgs);
+  const size_t n = msgs.size();
+  std::vector<uint8_t> out(n * out_len);
+  check(fec_expand_message_xmd(ctx.raw(), m.bytes.data(), m.off.data(), m.bytes.size(),
+                               dst.empty() ? nullptr : reinterpret_cast<const uint8_t*>(dst.data()), dst.size(), out_len,
+                               out.empty() ? nullptr : out.data(), n));
+  std::vector<std::vector<uint8_t>> r(n);
+  for (size_t i = 0; i < n; ++i) r[i].assign(out.begin() + i * out_len, out.begin() + (i + 1) * out_len);
+  return r;
+}
+// HashToCurveSwu::hash_to_field(msgs[i], dst, count) (316-377)
+template <fec_curve C>
+inline std::vector<std::vector<FieldElement<C>>> hash_to_field(GpuContext& ctx, const std::vector<std::string>& msgs, const std::string& dst,
+                                                               size_t count) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "HashToCurve is implemented for secp256k1 and P-256");
+  const eddsa::detail::Messages m(msgs);
+  const size_t n = msgs.size();
+  std::vector<uint64_t> u(n * count * 4);
+  check(fec_hash_to_field(ctx.raw(), C, m.bytes.data(), m.off.data(), m.bytes.size(),
+                          dst.empty() ? nullptr : reinterpret_cast<const uint8_t*>(dst.data()), dst.size(), count, u.data(), n));
+  std::vector<std::vector<FieldElement<C>>> r(n, std::vector<FieldElement<C>>(count));
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = 0; j < count; ++j)
+      for (int l = 0; l < 4; ++l) r[i][j].raw[l] = u[(i * count + j) * 4 + l];
+  return r;
+}
+// C::map_to_curve(&u[i]) (secp256k1.rs:1587-1705, p256.rs:2215-2265); trace (may be null) receives what each did
+template <fec_curve C>
+inline std::vector<AffinePoint<C>> map_to_curve(GpuContext& ctx, const std::vector<FieldElement<C>>& u,
+                                                std::vector<MapTrace<C>>* trace = nullptr) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "HashToCurve is implemented for secp256k1 and P-256");
+  const size_t n = u.size();
+  std::vector<uint64_t> xy(n * 8), cand(n * 8);
+  std::vector<uint8_t> legs(n);
+  check(fec_map_to_curve(ctx.raw(), C, reinterpret_cast<const uint64_t*>(u.data()), xy.data(), cand.data(), legs.data(), n));
+  std::vector<AffinePoint<C>> r(n);
+  if (trace) trace->resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    for (int l = 0; l < 4; ++l) {
+      r[i].x_.raw[l] = xy[i * 8 + l];
+      r[i].y_.raw[l] = xy[i * 8 + 4 + l];
+      if (trace) {
+        (*trace)[i].x.raw[l] = cand[i * 8 + l];
+        (*trace)[i].y2.raw[l] = cand[i * 8 + 4 + l];
+      }
+    }
+    if (trace) (*trace)[i].legs = legs[i];
+  }
+  return r;
+}
+namespace detail {
+template <fec_curve C>
+inline std::vector<ProjectivePoint<C>> call(GpuContext& ctx, int mode, const std::vector<std::string>& msgs, const std::string& dst) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "HashToCurve is implemented for secp256k1 and P-256");
+  const eddsa::detail::Messages m(msgs);
+  std::vector<ProjectivePoint<C>> r(msgs.size());
+  check(fec_hash_to_curve(ctx.raw(), C, mode, FEC_H2C_SWU, m.bytes.data(), m.off.data(), m.bytes.size(),
+                          dst.empty() ? nullptr : reinterpret_cast<const uint8_t*>(dst.data()), dst.size(),
+                          reinterpret_cast<uint64_t*>(r.data()), nullptr, nullptr, msgs.size()));
+  return r;
+}
+}  // namespace detail
+// hash_to_curve::<C, Sha256>(msgs[i], dst, SimplifiedSwu) (254-312); an empty dst throws Error(FEC_E_ARG), the reference's
+// Err(DomainSeparationFailure)
+template <fec_curve C>
+inline std::vector<ProjectivePoint<C>> hash(GpuContext& ctx, const std::vector<std::string>& msgs, const std::string& dst) {
+  return detail::call<C>(ctx, FEC_H2C_HASH, msgs, dst);
+}
+// encode_to_curve::<C, Sha256>(msgs[i], dst, SimplifiedSwu) (1030-1056)
+template <fec_curve C>
+inline std::vector<ProjectivePoint<C>> encode(GpuContext& ctx, const std::vector<std::string>& msgs, const std::string& dst) {
+  return detail::call<C>(ctx, FEC_H2C_ENCODE, msgs, dst);
+}
+// The trait method C::hash_to_curve::<Sha256>(msgs[i], &tag), tag_bytes = suite_id || dst (secp256k1.rs:1712-1769; the
+// default forge-ec-core/src/lib.rs:1550-1581 for P-256)
+template <fec_curve C>
+inline std::vector<AffinePoint<C>> curve_hash_to_curve(GpuContext& ctx, const std::vector<std::string>& msgs, const std::string& tag_bytes) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "HashToCurve is implemented for secp256k1 and P-256");
+  const eddsa::detail::Messages m(msgs);
+  const size_t n = msgs.size();
+  std::vector<uint64_t> xy(n * 8);
+  std::vector<uint8_t> inf(n);
+  check(fec_curve_hash_to_curve(ctx.raw(), C, m.bytes.data(), m.off.data(), m.bytes.size(),
+                                tag_bytes.empty() ? nullptr : reinterpret_cast<const uint8_t*>(tag_bytes.data()), tag_bytes.size(),
+                                xy.data(), inf.data(), n));
+  std::vector<AffinePoint<C>> r(n);
+  for (size_t i = 0; i < n; ++i) {
+    for (int l = 0; l < 4; ++l) {
+      r[i].x_.raw[l] = xy[i * 8 + l];
+      r[i].y_.raw[l] = xy[i * 8 + 4 + l];
+    }
+    r[i].infinity = inf[i] != 0;
+  }
+  return r;
+}
+}  // namespace hash_to_curve
 namespace ecdsa {
 // Ecdsa::<C, Sha256>::verify(public_keys[i], msgs[i], sigs[i]) (ecdsa.rs:213-281), C = Secp256k1 or P256, the hash on
 // the GPU as well (fec_ecdsa_verify_msg).  The function has no message special case.

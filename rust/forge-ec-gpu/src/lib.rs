@@ -113,6 +113,16 @@ extern "C" {
     fn fec_ecdh_derive_key_dev(ctx: *mut FecCtx, curve: c_int, d_private_keys: *const u64, d_pk_xy: *const u64, d_pk_inf: *const u8, info: *const u8, info_len: usize, out_len: usize, d_keys: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_ecdh_exchange(ctx: *mut FecCtx, curve: c_int, private_keys: *const u64, peer_xy: *const u64, peer_inf: *const u8, info: *const u8, info_len: usize, out_len: usize, public_xy: *mut u64, public_inf: *mut u8, keys: *mut u8, status: *mut u8, n: usize) -> c_int;
     fn fec_ecdh_exchange_dev(ctx: *mut FecCtx, curve: c_int, d_private_keys: *const u64, d_peer_xy: *const u64, d_peer_inf: *const u8, info: *const u8, info_len: usize, out_len: usize, d_public_xy: *mut u64, d_public_inf: *mut u8, d_keys: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_expand_message_xmd(ctx: *mut FecCtx, msgs: *const u8, msg_off: *const u64, msg_len: usize, dst: *const u8, dst_len: usize, out_len: usize, out: *mut u8, n: usize) -> c_int;
+    fn fec_expand_message_xmd_dev(ctx: *mut FecCtx, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, dst: *const u8, dst_len: usize, out_len: usize, d_out: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_hash_to_field(ctx: *mut FecCtx, curve: c_int, msgs: *const u8, msg_off: *const u64, msg_len: usize, dst: *const u8, dst_len: usize, count: usize, u: *mut u64, n: usize) -> c_int;
+    fn fec_hash_to_field_dev(ctx: *mut FecCtx, curve: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, dst: *const u8, dst_len: usize, count: usize, d_u: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_map_to_curve(ctx: *mut FecCtx, curve: c_int, u: *const u64, xy: *mut u64, cand: *mut u64, legs: *mut u8, n: usize) -> c_int;
+    fn fec_map_to_curve_dev(ctx: *mut FecCtx, curve: c_int, d_u: *const u64, d_xy: *mut u64, d_cand: *mut u64, d_legs: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_hash_to_curve(ctx: *mut FecCtx, curve: c_int, mode: c_int, method: c_int, msgs: *const u8, msg_off: *const u64, msg_len: usize, dst: *const u8, dst_len: usize, out: *mut u64, cand: *mut u64, legs: *mut u8, n: usize) -> c_int;
+    fn fec_hash_to_curve_dev(ctx: *mut FecCtx, curve: c_int, mode: c_int, method: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, dst: *const u8, dst_len: usize, d_out: *mut u64, d_cand: *mut u64, d_legs: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    fn fec_curve_hash_to_curve(ctx: *mut FecCtx, curve: c_int, msgs: *const u8, msg_off: *const u64, msg_len: usize, dst: *const u8, dst_len: usize, xy: *mut u64, inf: *mut u8, n: usize) -> c_int;
+    fn fec_curve_hash_to_curve_dev(ctx: *mut FecCtx, curve: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, dst: *const u8, dst_len: usize, d_xy: *mut u64, d_inf: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_ctx_set_chunk(ctx: *mut FecCtx, elements: usize) -> c_int;
     fn fec_ctx_set_timing(ctx: *mut FecCtx, enabled: c_int) -> c_int;
     fn fec_ctx_last_kernel_ms(ctx: *mut FecCtx, ms: *mut c_float, kernel_name: *mut *const c_char) -> c_int;
@@ -692,6 +702,88 @@ pub fn x25519_batch(ctx: &mut GpuContext, scalars: &[[u8; 32]], u: &[[u8; 32]]) 
 }
 
 /// The message layout of include/fecgpu.h: the concatenated bytes and the n + 1 offsets.
+fn ptr_or_null(b: &[u8]) -> *const u8 {
+    if b.is_empty() { core::ptr::null() } else { b.as_ptr() }
+}
+
+/// `expand_message_xmd::<Sha256>(msgs[i], dst || len(dst), out_len)` per message (`forge-ec-hash/src/hash_to_curve.rs:380-448`,
+/// RFC 9380's function) on the GPU (`fec_expand_message_xmd`).  `dst` at most 255 bytes, `out_len` at most 8160 -- the
+/// reference writes both counts into a `u8`: `Err(UnsupportedOperation)` beyond.
+pub fn expand_message_xmd_batch(ctx: &mut GpuContext, msgs: &[&[u8]], dst: &[u8], out_len: usize) -> Result<Vec<Vec<u8>>> {
+    let n = msgs.len();
+    let (buf, off) = pack_messages(msgs);
+    let mut out = vec![0u8; n * out_len];
+    // SAFETY: off holds n + 1 offsets into buf, out n * out_len bytes; null stands for an empty array.
+    check(unsafe { fec_expand_message_xmd(ctx.raw, buf.as_ptr(), off.as_ptr(), buf.len(), ptr_or_null(dst), dst.len(), out_len, if out.is_empty() { core::ptr::null_mut() } else { out.as_mut_ptr() }, n) })?;
+    Ok((0..n).map(|i| out[i * out_len..(i + 1) * out_len].to_vec()).collect())
+}
+
+/// `HashToCurveSwu::<C, Sha256>::hash_to_field(msgs[i], dst, count)` per message (`hash_to_curve.rs:316-377`): `count` raw
+/// limb quadruples each (`FieldElement::from_raw` rebuilds the element).  1 <= `count` <= 255.
+pub fn hash_to_field_batch<C: GpuCurve>(ctx: &mut GpuContext, msgs: &[&[u8]], dst: &[u8], count: usize) -> Result<Vec<Vec<[u64; 4]>>> {
+    let n = msgs.len();
+    let (buf, off) = pack_messages(msgs);
+    let mut u = vec![0u64; 4 * count * n];
+    // SAFETY: off holds n + 1 offsets into buf, u n * count * 4 limbs.
+    check(unsafe { fec_hash_to_field(ctx.raw, C::ID, buf.as_ptr(), off.as_ptr(), buf.len(), ptr_or_null(dst), dst.len(), count, u.as_mut_ptr(), n) })?;
+    Ok((0..n).map(|i| (0..count).map(|j| limb4(&u, i * count + j)).collect()).collect())
+}
+
+/// What `map_to_curve` did besides returning a point: the candidate x and y^2 as the reference computes them, kept or not,
+/// and the `FEC_H2C_LEG_*` bits (see `include/fecgpu.h`: the reference's inherent `sqrt` fails for every known input).
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct MapTrace {
+    pub x: [u64; 4],
+    pub y2: [u64; 4],
+    pub legs: u8,
+}
+
+/// `C::map_to_curve(&FieldElement::from_raw(u[i]))` per element (`secp256k1.rs:1587-1705`, `p256.rs:2215-2265`) with the
+/// trace of each computation (`fec_map_to_curve`).
+pub fn map_to_curve_batch<C: GpuCurve>(ctx: &mut GpuContext, u: &[[u64; 4]]) -> Result<Vec<(C::PointAffine, MapTrace)>> {
+    let n = u.len();
+    let flat: Vec<u64> = u.iter().flat_map(|l| l.iter().copied()).collect();
+    let (mut xy, mut cand, mut legs) = (vec![0u64; 8 * n], vec![0u64; 8 * n], vec![0u8; n]);
+    // SAFETY: every buffer holds n elements of the width the header states.
+    check(unsafe { fec_map_to_curve(ctx.raw, C::ID, flat.as_ptr(), xy.as_mut_ptr(), cand.as_mut_ptr(), legs.as_mut_ptr(), n) })?;
+    Ok((0..n).map(|i| (C::affine_from_limbs(&xy[8 * i..8 * i + 8], false), MapTrace { x: limb4(&cand, 2 * i), y2: limb4(&cand, 2 * i + 1), legs: legs[i] })).collect())
+}
+
+fn h2c_call<C: GpuCurve>(ctx: &mut GpuContext, mode: c_int, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<C::PointProjective>> {
+    if dst.is_empty() {
+        return Err(Error::DomainSeparationFailure);   // hash_to_curve.rs:264-266, before any element is looked at
+    }
+    let n = msgs.len();
+    let (buf, off) = pack_messages(msgs);
+    let mut out = vec![0u64; C::LIMBS * n];
+    // SAFETY: off holds n + 1 offsets into buf, out n * 12 limbs; the optional outputs are absent.
+    check(unsafe { fec_hash_to_curve(ctx.raw, C::ID, mode, 0, buf.as_ptr(), off.as_ptr(), buf.len(), dst.as_ptr(), dst.len(), out.as_mut_ptr(), core::ptr::null_mut(), core::ptr::null_mut(), n) })?;
+    Ok(unpack_points::<C>(&out))
+}
+
+/// `hash_to_curve::<C, Sha256>(msgs[i], dst, HashToCurveMethod::SimplifiedSwu)` per message (`hash_to_curve.rs:254-312`),
+/// bit for bit: on secp256k1 that is ONE constant point for every known input, on P-256 a point (x, +-1) -- the
+/// reference's results, not RFC 9380's.  The other methods are not offered.  Messages may be secret; NOT constant-time.
+pub fn hash_to_curve_batch<C: GpuCurve>(ctx: &mut GpuContext, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<C::PointProjective>> {
+    h2c_call::<C>(ctx, 0, msgs, dst)
+}
+
+/// `encode_to_curve::<C, Sha256>(msgs[i], dst, HashToCurveMethod::SimplifiedSwu)` per message (`hash_to_curve.rs:1030-1056`).
+pub fn encode_to_curve_batch<C: GpuCurve>(ctx: &mut GpuContext, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<C::PointProjective>> {
+    h2c_call::<C>(ctx, 1, msgs, dst)
+}
+
+/// The trait method `C::hash_to_curve::<Sha256>(msgs[i], &tag)` per message, `tag_bytes = tag.as_bytes()` (suite_id || dst):
+/// secp256k1's override (`secp256k1.rs:1712-1769`) or the trait default P-256 keeps (`forge-ec-core/src/lib.rs:1550-1581`).
+pub fn curve_hash_to_curve_batch<C: GpuCurve>(ctx: &mut GpuContext, msgs: &[&[u8]], tag_bytes: &[u8]) -> Result<Vec<C::PointAffine>> {
+    let n = msgs.len();
+    let (buf, off) = pack_messages(msgs);
+    let (mut xy, mut inf) = (vec![0u64; 8 * n], vec![0u8; n]);
+    // SAFETY: off holds n + 1 offsets into buf, xy n * 8 limbs, inf n bytes.
+    check(unsafe { fec_curve_hash_to_curve(ctx.raw, C::ID, buf.as_ptr(), off.as_ptr(), buf.len(), ptr_or_null(tag_bytes), tag_bytes.len(), xy.as_mut_ptr(), inf.as_mut_ptr(), n) })?;
+    Ok((0..n).map(|i| C::affine_from_limbs(&xy[8 * i..8 * i + 8], inf[i] != 0)).collect())
+}
+
 fn pack_messages(msgs: &[&[u8]]) -> (Vec<u8>, Vec<u64>) {
     let mut off = Vec::with_capacity(msgs.len() + 1);
     off.push(0u64);
@@ -1279,6 +1371,47 @@ pub mod dev {
     /// As [`batch_mul`]; the caller owns and clears every buffer.
     pub unsafe fn ecdh_exchange(ctx: &mut GpuContext, curve: c_int, d_private_keys: *const u64, d_peer_xy: *const u64, d_peer_inf: *const u8, info: &[u8], out_len: usize, d_public_xy: *mut u64, d_public_inf: *mut u8, d_keys: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
         check(fec_ecdh_exchange_dev(ctx.raw, curve, d_private_keys, d_peer_xy, d_peer_inf, if info.is_empty() { core::ptr::null() } else { info.as_ptr() }, info.len(), out_len, d_public_xy, d_public_inf, d_keys, d_status, n, stream))
+    }
+
+    /// `fec_expand_message_xmd_dev`.  `dst` is a host slice; `d_status` may be null.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn expand_message_xmd(ctx: &mut GpuContext, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, dst: &[u8], out_len: usize, d_out: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_expand_message_xmd_dev(ctx.raw, d_msgs, d_msg_off, msg_len, super::ptr_or_null(dst), dst.len(), out_len, d_out, d_status, n, stream))
+    }
+
+    /// `fec_hash_to_field_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn hash_to_field(ctx: &mut GpuContext, curve: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, dst: &[u8], count: usize, d_u: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_hash_to_field_dev(ctx.raw, curve, d_msgs, d_msg_off, msg_len, super::ptr_or_null(dst), dst.len(), count, d_u, d_status, n, stream))
+    }
+
+    /// `fec_map_to_curve_dev` (`d_cand`, `d_legs` may be null).
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn map_to_curve(ctx: &mut GpuContext, curve: c_int, d_u: *const u64, d_xy: *mut u64, d_cand: *mut u64, d_legs: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_map_to_curve_dev(ctx.raw, curve, d_u, d_xy, d_cand, d_legs, n, stream))
+    }
+
+    /// `fec_hash_to_curve_dev`: `mode` 0 hash, 1 encode; `method` 0 (SimplifiedSwu).  P-256's hash leaves its two mapped
+    /// points in the stream's scratch until the ctx is wiped.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn hash_to_curve(ctx: &mut GpuContext, curve: c_int, mode: c_int, method: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, dst: &[u8], d_out: *mut u64, d_cand: *mut u64, d_legs: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_hash_to_curve_dev(ctx.raw, curve, mode, method, d_msgs, d_msg_off, msg_len, super::ptr_or_null(dst), dst.len(), d_out, d_cand, d_legs, d_status, n, stream))
+    }
+
+    /// `fec_curve_hash_to_curve_dev`.
+    ///
+    /// # Safety
+    /// As [`batch_mul`]; the caller owns and clears every buffer.
+    pub unsafe fn curve_hash_to_curve(ctx: &mut GpuContext, curve: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, dst: &[u8], d_xy: *mut u64, d_inf: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+        check(fec_curve_hash_to_curve_dev(ctx.raw, curve, d_msgs, d_msg_off, msg_len, super::ptr_or_null(dst), dst.len(), d_xy, d_inf, d_status, n, stream))
     }
 
     /// `fec_x25519_dev`.
