@@ -950,15 +950,9 @@ void ecdsa_layout(WorkArea& area, EcdsaWork& w, size_t n, bool weighted) {
 // into a region of the same work area -- one request for both stages -- and the pipeline runs on them unchanged;
 // `mark_bad_ranges` (the *_dev form, whose message layout nobody has checked) then sets status 4 where an element's
 // range was bad.
-struct EcdsaMessages {
-  const unsigned char* msgs;
-  const u64* off;
-  u64 msg_len;
-  bool mark_bad_ranges;
-};
 int launch_ecdsa_verify(fec_ctx* ctx, int curve, const unsigned char* dd, const u64* dr, const u64* ds, const u64* dpk,
                         const unsigned char* dinf, unsigned char* dstatus, size_t n, void* stream,
-                        const EcdsaMessages* msg = nullptr) {
+                        const Messages* msg = nullptr, bool mark_bad_ranges = false) {
   if (n == 0) return FEC_OK;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   EcdsaWork w;
@@ -976,7 +970,7 @@ int launch_ecdsa_verify(fec_ctx* ctx, int curve, const unsigned char* dd, const 
   Launch L(ctx, stream, curve == FEC_SECP256K1 ? (msg ? "k_sha256 + k_ecdsa_pre + k_secp_mul x2 + k_ecdsa_finish" : "k_ecdsa_pre + k_secp_mul x2 + k_ecdsa_finish")
                                                : (msg ? "k_sha256 + k_ecdsa_pre + k_p256_mul_sched x2 + k_ecdsa_finish" : "k_ecdsa_pre + k_p256_mul_sched x2 + k_ecdsa_finish"));
   if (msg) {
-    sha256_launch(msg->msgs, msg->off, msg->msg_len, digests, bad, n, L.s);
+    sha256_launch(*msg, digests, bad, n, L.s);
     dd = reinterpret_cast<const unsigned char*>(digests);
   }
   const u32* r = reinterpret_cast<const u32*>(dr);
@@ -984,7 +978,7 @@ int launch_ecdsa_verify(fec_ctx* ctx, int curve, const unsigned char* dd, const 
   // (u2 * from_affine(public key): the affine-addend cost in the P-256 CU split)
   product_pair(ctx, curve, n, L.s, SideStream::kSideStreamMax, kP256VarAffineMs, w.u1, w.ta, nullptr, w.u2, w.q, w.tb);
   ecdsa_finish_launch(curve, r, w, dstatus, n, L.s);
-  if (msg && msg->mark_bad_ranges) bad_range_status_launch(bad, dstatus, n, L.s);
+  if (msg && mark_bad_ranges) bad_range_status_launch(bad, dstatus, n, L.s);
   return L.done();
 }
 
@@ -1144,7 +1138,7 @@ int launch_ecdh_exchange(fec_ctx* ctx, int curve, const u64* dsk, const u64* dpe
 // pass decided: status 4 and a zero signature for a bad range (a *_dev call's layout, which nobody has checked), status 5
 // at the retry cap.
 int launch_ecdsa_sign(fec_ctx* ctx, int curve, const u64* dsk, const unsigned char* dd, const u64* dk, u64* dsig,
-                      unsigned char* dstatus, size_t n, void* stream, const EcdsaMessages* msg = nullptr) {
+                      unsigned char* dstatus, size_t n, void* stream, const Messages* msg = nullptr) {
   if (n == 0) return FEC_OK;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   u32 *rp, *nonce = nullptr, *digests = nullptr;
@@ -1160,7 +1154,7 @@ int launch_ecdsa_sign(fec_ctx* ctx, int curve, const u64* dsk, const unsigned ch
   const u32* sk = reinterpret_cast<const u32*>(dsk);
   const u32* k = reinterpret_cast<const u32*>(dk);
   if (msg) {
-    rfc6979_launch(curve, Rfc6979Io{sk, msg->msgs, msg->off, msg->msg_len, nonce, digests, decided}, rfc6979_curve_order(curve), true, n, L.s);
+    rfc6979_launch(curve, Rfc6979Io{sk, *msg, nonce, digests, decided}, rfc6979_curve_order(curve), true, n, L.s);
     dd = reinterpret_cast<const unsigned char*>(digests);
     k = nonce;
   }
@@ -1171,12 +1165,11 @@ int launch_ecdsa_sign(fec_ctx* ctx, int curve, const u64* dsk, const unsigned ch
 }
 
 // Rfc6979::<C, Sha256>::generate_k per element (kernels_rfc6979.hip): one pass, no work area, no key check.
-int launch_rfc6979(fec_ctx* ctx, int curve, const Rfc6979Order& order, const u64* dsk, const EcdsaMessages& msg, u64* dk,
+int launch_rfc6979(fec_ctx* ctx, int curve, const Rfc6979Order& order, const u64* dsk, const Messages& msg, u64* dk,
                    unsigned char* dstatus, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
   Launch L(ctx, stream, "k_rfc6979");
-  rfc6979_launch(curve, Rfc6979Io{reinterpret_cast<const u32*>(dsk), msg.msgs, msg.off, msg.msg_len, reinterpret_cast<u32*>(dk), nullptr, dstatus},
-                 order, false, n, L.s);
+  rfc6979_launch(curve, Rfc6979Io{reinterpret_cast<const u32*>(dsk), msg, reinterpret_cast<u32*>(dk), nullptr, dstatus}, order, false, n, L.s);
   return L.done();
 }
 
@@ -1252,7 +1245,7 @@ int launch_schnorr_sign(fec_ctx* ctx, int curve, const SchnorrSignIo& io, size_t
     return FEC_E_DEVICE;
   }
   Launch L(ctx, stream, curve == FEC_SECP256K1 ? "k_rfc6979 + k_secp_mul + k_schnorr_sign_finish" : "k_rfc6979 + k_p256_mul_sched + k_schnorr_sign_finish");
-  rfc6979_launch(curve, Rfc6979Io{io.sk, io.msgs, io.off, io.msg_len, scal, nullptr, decided}, rfc6979_curve_order(curve), false, n, L.s);
+  rfc6979_launch(curve, Rfc6979Io{io.sk, io.msg, scal, nullptr, decided}, rfc6979_curve_order(curve), false, n, L.s);
   fixed_product(ctx, sched_env(ctx), curve, scal, gen, pts, 2 * n, nullptr, L.s);
   schnorr_sign_finish_launch(curve, io, scal, pts, decided, gen, n, L.s);
   return L.done();
@@ -1380,8 +1373,8 @@ int launch_curve25519_mul(fec_ctx* ctx, const u32* s, const u32* p, u32* out, si
 }
 }  // namespace
 
-// EdDSA signing and SHA-512 (kernels_eddsa.hip): the message layout and the host-pointer pipeline of the calls that take
-// messages.  Message i is msgs[off[i], off[i+1]); off holds n + 1 values, off[0] = 0, non-decreasing, off[n] = msg_len.
+// The calls that take messages: the layout, the host-pointer engine and the *_dev forms' argument rules.
+// Message i is msgs[off[i], off[i+1]); off holds n + 1 values, off[0] = 0, non-decreasing, off[n] = msg_len.
 namespace {
 bool msg_layout_ok(const uint8_t* msgs, const uint64_t* off, size_t msg_len, size_t n) {
   if (!off || off[0] != 0 || off[n] != (uint64_t)msg_len || (msg_len && !msgs)) return false;
@@ -1391,9 +1384,8 @@ bool msg_layout_ok(const uint8_t* msgs, const uint64_t* off, size_t msg_len, siz
 }
 // One chunk's messages onto the device: the bytes msgs[o[0], o[m]) into slot kStageBody, the m + 1 offsets o[0..m],
 // rebased to that range (`reb`: host scratch of at least m + 1 values that outlives the copy), into the slot after it.
-int stage_messages(fec_ctx* c, const uint8_t* msgs, const u64* o, size_t m, std::vector<uint64_t>& reb, hipStream_t st,
-                   const unsigned char*& d_msgs, const u64*& d_off, u64& bytes) {
-  bytes = o[m] - o[0];
+int stage_messages(fec_ctx* c, const uint8_t* msgs, const u64* o, size_t m, std::vector<uint64_t>& reb, hipStream_t st, Messages& dm) {
+  const u64 bytes = o[m] - o[0];
   for (size_t k = 0; k <= m; ++k) reb[k] = o[k] - o[0];
   int rc = ensure(c, kStageBody + 1, reb.size() * 8);
   if (rc == FEC_OK && bytes) rc = ensure(c, kStageBody, bytes);
@@ -1402,199 +1394,197 @@ int stage_messages(fec_ctx* c, const uint8_t* msgs, const u64* o, size_t m, std:
     return FEC_E_DEVICE;
   if (hipMemcpyAsync(c->d_buf[kStageBody + 1], reb.data(), (m + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
     return FEC_E_DEVICE;
-  d_msgs = bytes ? static_cast<const unsigned char*>(c->d_buf[kStageBody]) : nullptr;
-  d_off = static_cast<const u64*>(c->d_buf[kStageBody + 1]);
+  dm = Messages{bytes ? static_cast<const unsigned char*>(c->d_buf[kStageBody]) : nullptr, static_cast<const u64*>(c->d_buf[kStageBody + 1]), bytes};
   return FEC_OK;
 }
-constexpr int kSha512 = -1, kSha256 = -2, kBip340 = -3;   // msg_call's modes for fec_sha512, fec_sha256, fec_bip340_sign (else EDDSA_MODE_*)
-// The host forms, on a single-device or a multi-device ctx (host_ctx.hpp: sharded, chunked; one lane).  The engine stages
-// the keys and takes back the outputs (out: 64 bytes per element, 32 for derive and SHA-256; status; r_inf and s for the generic
-// form); the body stages the chunk's message bytes msgs[off[lo], off[lo + cnt]) into slot kStageBody and its offsets,
-// rebased to that range, into the slot after it.  Keys and outputs are secret (a digest too: its message may be), so the
-// staging and the stream scratch (a, r, A, R) are cleared on every way out.  The layout is checked once, here.
-int msg_call(fec_ctx* ctx, int mode, const void* keys, const uint8_t* msgs, const uint64_t* off, size_t msg_len, void* out,
-             uint8_t* status, uint8_t* r_inf, uint64_t* s_out, size_t n) {
-  if (!ctx) return FEC_E_ARG;
-  const bool with_msgs = mode != EDDSA_MODE_DERIVE;
-  if (with_msgs && !msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(keys, 32), ragged(with_msgs ? off : nullptr, 8),
-                         secret_output(out, with_msgs && mode != kSha256 ? 64 : 32), output(status, 1), output(r_inf, 1),
-                         output(s_out, 32)};
-  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[6], size_t cnt, size_t) {
-    std::vector<uint64_t> reb(with_msgs ? (child->chunk < cnt ? child->chunk : cnt) + 1 : 0);
+// The host forms' engine, on a single-device or a multi-device ctx (host_ctx.hpp: sharded, chunked; one lane).  The layout
+// is checked once, here.  `a` names the call's arrays, the offsets among them as its one ragged() entry; per chunk the
+// engine stages them, then the chunk's message bytes and its offsets rebased to that range (stage_messages), and hands
+// body(ctx, d, messages, m, stream) the device side of all of it.  An array list with a secret in it (keys, and digests or
+// points whose message may be one) has the staging and the stream scratch cleared on every way out: chunked's rule.
+template <size_t N, class F>
+int with_messages(fec_ctx* ctx, size_t n, const HostArray (&a)[N], const uint8_t* msgs, const uint64_t* off, size_t msg_len, F body) {
+  size_t r = 0;
+  while (r < N && a[r].staged) ++r;
+  if (!ctx || r == N || !msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[N], size_t cnt, size_t) {
+    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
     return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
-      const u64* o = static_cast<const u64*>(d[1]);   // (host) the offsets from the chunk's first element on
-      const unsigned char* d_msgs = nullptr;
-      const u64* d_off = nullptr;
-      u64 bytes = 0;
-      if (with_msgs) {
-        const int rc = stage_messages(c, msgs, o, m, reb, st, d_msgs, d_off, bytes);
-        if (rc != FEC_OK) return rc;
-      }
-      if (mode == kSha512) {
-        Launch L(c, st, "k_sha512");
-        sha512_launch(d_msgs, d_off, bytes, static_cast<u32*>(d[2]), nullptr, m, L.s);
-        return L.done();
-      }
-      if (mode == kSha256) {
-        Launch L(c, st, "k_sha256");
-        sha256_launch(d_msgs, d_off, bytes, static_cast<u32*>(d[2]), nullptr, m, L.s);
-        return L.done();
-      }
-      if (mode == kBip340) {
-        const Bip340Io io{static_cast<const u32*>(d[0]), d_msgs, d_off, bytes, static_cast<u32*>(d[2]), static_cast<unsigned char*>(d[3])};
-        return launch_bip340_sign(c, io, m, st);
-      }
-      const EddsaSignIo io{mode, static_cast<const u32*>(d[0]), d_msgs, d_off, bytes, nullptr, static_cast<u32*>(d[2]),
-                           static_cast<unsigned char*>(d[4]), static_cast<u32*>(d[5]), static_cast<unsigned char*>(d[3])};
-      return launch_eddsa_sign(c, io, m, st);
+      Messages dm;
+      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[r]), m, reb, st, dm);   // (d[r]: host, from the chunk's first element on)
+      return rc != FEC_OK ? rc : body(c, d, dm, m, st);
     });
+  });
+}
+// What every *_dev form starts with: device pointers belong to one device, which becomes the current one.
+int dev_enter(fec_ctx* ctx) {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;
+  if (!ctx) return FEC_E_ARG;
+  return hipSetDevice(ctx->device) == hipSuccess ? FEC_OK : FEC_E_DEVICE;
+}
+// The message arrays of a *_dev form, whose layout nobody checks (each lane checks its own range): 0, or what is wrong
+// with the pointers -- both FEC_E_ARG, apart only because some forms test the curve between the two.
+enum { kDevMsgsNull = 1, kDevMsgsMisaligned = 2 };
+int dev_messages(const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, size_t n, Messages& m) {
+  m = Messages{d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len};
+  if ((n && !d_msg_off) || (msg_len && !d_msgs)) return kDevMsgsNull;
+  return (reinterpret_cast<uintptr_t>(d_msg_off) & 7u) ? kDevMsgsMisaligned : 0;
+}
+
+// SHA-512 and SHA-256 per message (kernels_eddsa.hip, kernels_schnorr.hip).  A digest is secret: its message may be.
+struct DigestKernel {
+  void (*launch)(const Messages&, u32*, unsigned char*, size_t, hipStream_t);
+  const char* name;
+  size_t bytes;
+};
+constexpr DigestKernel kDigestSha512{sha512_launch, "k_sha512", 64}, kDigestSha256{sha256_launch, "k_sha256", 32};
+int digest_call(fec_ctx* ctx, const DigestKernel& k, const uint8_t* msgs, const uint64_t* off, size_t msg_len, uint8_t* digests, size_t n) {
+  if (n && !digests) return FEC_E_ARG;
+  const HostArray a[] = {ragged(off, 8), secret_output(digests, k.bytes)};
+  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    Launch L(c, st, k.name);
+    k.launch(m, static_cast<u32*>(d[1]), nullptr, cnt, L.s);
+    return L.done();
+  });
+}
+int digest_dev(fec_ctx* ctx, const DigestKernel& k, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
+               uint8_t* d_status, size_t n, void* stream) {
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && !d_digests) || !aligned16(d_digests)) return FEC_E_ARG;
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, k.name);
+  k.launch(m, reinterpret_cast<u32*>(d_digests), d_status, n, L.s);
+  return L.done();
+}
+
+// EdDSA signing for Ed25519 (kernels_eddsa.hip).  out: 64 bytes per element, 32 for derive; r_inf and s for the generic
+// form.  Keys and outputs are secret.  EDDSA_MODE_DERIVE has no messages: the plain engine, one lane.
+int eddsa_sign_call(fec_ctx* ctx, int mode, const void* keys, const uint8_t* msgs, const uint64_t* off, size_t msg_len, void* out,
+                    uint8_t* status, uint8_t* r_inf, uint64_t* s_out, size_t n) {
+  const bool derive = mode == EDDSA_MODE_DERIVE;
+  if (!ctx || (n && (!keys || !out || !status || (mode == EDDSA_MODE_GENERIC && (!r_inf || !s_out))))) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(keys, 32), ragged(off, 8), secret_output(out, derive ? 32 : 64), output(status, 1), output(r_inf, 1),
+                         output(s_out, 32)};
+  auto body = [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    const EddsaSignIo io{mode, static_cast<const u32*>(d[0]), m, nullptr, static_cast<u32*>(d[2]),
+                         static_cast<unsigned char*>(d[4]), static_cast<u32*>(d[5]), static_cast<unsigned char*>(d[3])};
+    return launch_eddsa_sign(c, io, cnt, st);
+  };
+  if (!derive) return with_messages(ctx, n, a, msgs, off, msg_len, body);
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t cnt, hipStream_t st) {
+    return body(c, d, Messages{nullptr, nullptr, 0}, cnt, st);
   });
 }
 // The *_dev forms: one launch sequence on the caller's stream; each lane checks its own message range.
 int eddsa_sign_dev(fec_ctx* ctx, int mode, const void* d_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                    void* d_out, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_status, size_t n, void* stream) {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  const bool with_msgs = mode != EDDSA_MODE_DERIVE;
-  if (!ctx || (n && (!d_keys || !d_out || !d_status || (with_msgs && !d_msg_off))) || (with_msgs && msg_len && !d_msgs))
-    return FEC_E_ARG;
-  if (mode == EDDSA_MODE_GENERIC && n && (!d_r_inf || !d_s)) return FEC_E_ARG;
-  if (!aligned16(d_keys) || !aligned16(d_out) || !aligned16(d_s) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const EddsaSignIo io{mode, static_cast<const u32*>(d_keys), with_msgs ? d_msgs : nullptr, with_msgs ? reinterpret_cast<const u64*>(d_msg_off) : nullptr,
-                       with_msgs ? (u64)msg_len : 0, nullptr, static_cast<u32*>(d_out), d_r_inf, reinterpret_cast<u32*>(d_s), d_status};
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m{nullptr, nullptr, 0};
+  if (mode != EDDSA_MODE_DERIVE && dev_messages(d_msgs, d_msg_off, msg_len, n, m)) return FEC_E_ARG;
+  if (n && (!d_keys || !d_out || !d_status || (mode == EDDSA_MODE_GENERIC && (!d_r_inf || !d_s)))) return FEC_E_ARG;
+  if (!aligned16(d_keys) || !aligned16(d_out) || !aligned16(d_s)) return FEC_E_ARG;
+  const EddsaSignIo io{mode, static_cast<const u32*>(d_keys), m, nullptr, static_cast<u32*>(d_out), d_r_inf, reinterpret_cast<u32*>(d_s), d_status};
   return launch_eddsa_sign(ctx, io, n, stream);
 }
 
+// BipSchnorr::sign (kernels_schnorr.hip).  Keys and signatures are secret.
+int bip340_sign_call(fec_ctx* ctx, const uint8_t* keys, const uint8_t* msgs, const uint64_t* off, size_t msg_len, uint8_t* sig,
+                     uint8_t* status, size_t n) {
+  if (n && (!keys || !sig || !status)) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(keys, 32), ragged(off, 8), secret_output(sig, 64), output(status, 1)};
+  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_bip340_sign(c, Bip340Io{static_cast<const u32*>(d[0]), m, static_cast<u32*>(d[2]), static_cast<unsigned char*>(d[3])}, cnt, st);
+  });
+}
+
 // The verifiers from the message.  form EDDSA_VERIFY_BYTES: pk n*32 bytes, sig n*64 bytes; EDDSA_VERIFY_GENERIC: pk and
-// sig (R) n*64 bytes of affine limbs with their flags, s n*32 bytes.  Host form: the engine as msg_call uses it, one lane,
-// the chunk's messages in the same two slots; nothing is secret, so nothing is cleared beyond the engine's rule.
+// sig (R) n*64 bytes of affine limbs with their flags, s n*32 bytes.  Nothing is secret.
 int verify_msg_call(fec_ctx* ctx, int form, const void* pk, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* off,
                     size_t msg_len, const void* sig, const uint8_t* r_inf, const uint64_t* s_in, uint8_t* status, size_t n) {
   const bool generic = form == EDDSA_VERIFY_GENERIC;
-  if (!ctx || (n && (!pk || !sig || !status || (generic && !s_in)))) return FEC_E_ARG;
-  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  if (n && (!pk || !sig || !status || (generic && !s_in))) return FEC_E_ARG;
   const HostArray a[] = {input(pk, generic ? 64 : 32), input(pk_inf, 1), ragged(off, 8), input(sig, 64), input(r_inf, 1),
                          input(s_in, 32), output(status, 1)};
-  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[7], size_t cnt, size_t) {
-    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
-    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
-      const unsigned char* d_msgs = nullptr;
-      const u64* d_off = nullptr;
-      u64 bytes = 0;
-      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[2]), m, reb, st, d_msgs, d_off, bytes);
-      if (rc != FEC_OK) return rc;
-      const EddsaVerifyIo io{form, static_cast<const u32*>(d[0]), static_cast<const unsigned char*>(d[1]), d_msgs, d_off, bytes,
-                             static_cast<const u32*>(d[3]), static_cast<const unsigned char*>(d[4]), static_cast<const u32*>(d[5])};
-      return launch_eddsa_verify_msg(c, io, static_cast<unsigned char*>(d[6]), m, st);
-    });
+  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    const EddsaVerifyIo io{form, static_cast<const u32*>(d[0]), static_cast<const unsigned char*>(d[1]), m,
+                           static_cast<const u32*>(d[3]), static_cast<const unsigned char*>(d[4]), static_cast<const u32*>(d[5])};
+    return launch_eddsa_verify_msg(c, io, static_cast<unsigned char*>(d[6]), cnt, st);
   });
 }
-// The *_dev forms: one launch sequence on the caller's stream; each lane checks its own message range.
 int verify_msg_dev(fec_ctx* ctx, int form, const void* d_pk, const uint8_t* d_pk_inf, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                    size_t msg_len, const void* d_sig, const uint8_t* d_r_inf, const uint64_t* d_s, uint8_t* d_status, size_t n,
                    void* stream) {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  const bool generic = form == EDDSA_VERIFY_GENERIC;
-  if (!ctx || (n && (!d_pk || !d_sig || !d_status || !d_msg_off || (generic && !d_s))) || (msg_len && !d_msgs)) return FEC_E_ARG;
-  if (!aligned16(d_pk) || !aligned16(d_sig) || !aligned16(d_s) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const EddsaVerifyIo io{form, static_cast<const u32*>(d_pk), d_pk_inf, d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len,
-                         static_cast<const u32*>(d_sig), d_r_inf, reinterpret_cast<const u32*>(d_s)};
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m)) return FEC_E_ARG;
+  if (n && (!d_pk || !d_sig || !d_status || (form == EDDSA_VERIFY_GENERIC && !d_s))) return FEC_E_ARG;
+  if (!aligned16(d_pk) || !aligned16(d_sig) || !aligned16(d_s)) return FEC_E_ARG;
+  const EddsaVerifyIo io{form, static_cast<const u32*>(d_pk), d_pk_inf, m, static_cast<const u32*>(d_sig), d_r_inf, reinterpret_cast<const u32*>(d_s)};
   return launch_eddsa_verify_msg(ctx, io, d_status, n, stream);
 }
 
-// Ecdsa::<C, Sha256>::verify from the message (ecdsa.rs:213-281).  Host form: the engine as verify_msg_call uses it, one
-// lane, the chunk's messages in the same two slots; nothing is secret.
+// Ecdsa::<C, Sha256>::verify from the message (ecdsa.rs:213-281).  Nothing is secret.
 int ecdsa_verify_msg_call(fec_ctx* ctx, int curve, const uint8_t* msgs, const uint64_t* off, size_t msg_len, const uint64_t* r,
                           const uint64_t* s_in, const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* status, size_t n) {
   if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
-  if (!ctx || (n && (!r || !s_in || !pk_xy || !status))) return FEC_E_ARG;
-  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  if (n && (!r || !s_in || !pk_xy || !status)) return FEC_E_ARG;
   const HostArray a[] = {ragged(off, 8), input(r, 32), input(s_in, 32), input(pk_xy, 64), input(pk_inf, 1), output(status, 1)};
-  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[6], size_t cnt, size_t) {
-    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
-    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
-      EcdsaMessages em{nullptr, nullptr, 0, false};
-      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[0]), m, reb, st, em.msgs, em.off, em.msg_len);
-      if (rc != FEC_OK) return rc;
-      return launch_ecdsa_verify(c, curve, nullptr, (const u64*)d[1], (const u64*)d[2], (const u64*)d[3], (const unsigned char*)d[4],
-                                 (unsigned char*)d[5], m, st, &em);
-    });
+  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_ecdsa_verify(c, curve, nullptr, (const u64*)d[1], (const u64*)d[2], (const u64*)d[3], (const unsigned char*)d[4],
+                               (unsigned char*)d[5], cnt, st, &m);
   });
 }
 
 // Ecdsa::<C, Sha256>::sign from the message (`order` null: out = the signature, 64 bytes per element) and
-// Rfc6979::<C, Sha256>::generate_k alone (out = k, 32 bytes, candidates compared with *order).  Host form: the engine as
-// msg_call uses it, one lane, the chunk's messages in the same two slots.  The keys are secret, and so is k: the staging
-// and the stream scratch (k, h1, R) are cleared on every way out.
+// Rfc6979::<C, Sha256>::generate_k alone (out = k, 32 bytes, candidates compared with *order).  The keys are secret, and
+// so is k.
 int ecdsa_sign_msg_call(fec_ctx* ctx, int curve, const Rfc6979Order* order, const uint64_t* sk, const uint8_t* msgs, const uint64_t* off,
                         size_t msg_len, uint64_t* out, uint8_t* status, size_t n) {
   if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
-  if (!ctx || (n && (!sk || !out || !status))) return FEC_E_ARG;
-  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  if (n && (!sk || !out || !status)) return FEC_E_ARG;
   const HostArray a[] = {secret_input(sk, 32), ragged(off, 8), secret_output(out, order ? 32 : 64), output(status, 1)};
-  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[4], size_t cnt, size_t) {
-    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
-    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
-      EcdsaMessages em{nullptr, nullptr, 0, false};
-      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[1]), m, reb, st, em.msgs, em.off, em.msg_len);
-      if (rc != FEC_OK) return rc;
-      if (order) return launch_rfc6979(c, curve, *order, (const u64*)d[0], em, (u64*)d[2], (unsigned char*)d[3], m, st);
-      return launch_ecdsa_sign(c, curve, (const u64*)d[0], nullptr, nullptr, (u64*)d[2], (unsigned char*)d[3], m, st, &em);
-    });
+  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    if (order) return launch_rfc6979(c, curve, *order, (const u64*)d[0], m, (u64*)d[2], (unsigned char*)d[3], cnt, st);
+    return launch_ecdsa_sign(c, curve, (const u64*)d[0], nullptr, nullptr, (u64*)d[2], (unsigned char*)d[3], cnt, st, &m);
   });
 }
-// The *_dev forms of the two: one launch sequence on the caller's stream; each lane checks its own message range.
+// The *_dev forms of the two.
 int ecdsa_sign_msg_dev(fec_ctx* ctx, int curve, bool nonce_only, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                        size_t msg_len, uint64_t* d_out, uint8_t* d_status, size_t n, void* stream) {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_sk || !d_msg_off || !d_out || !d_status)) || (msg_len && !d_msgs)) return FEC_E_ARG;
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  const int bad = dev_messages(d_msgs, d_msg_off, msg_len, n, m);
+  if (bad == kDevMsgsNull || (n && (!d_sk || !d_out || !d_status))) return FEC_E_ARG;
   if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
-  if (!aligned16(d_sk) || !aligned16(d_out) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const EcdsaMessages em{d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len, true};
-  if (nonce_only) return launch_rfc6979(ctx, curve, rfc6979_curve_order(curve), d_sk, em, d_out, d_status, n, stream);
-  return launch_ecdsa_sign(ctx, curve, d_sk, nullptr, nullptr, d_out, d_status, n, stream, &em);
+  if (bad || !aligned16(d_sk) || !aligned16(d_out)) return FEC_E_ARG;
+  if (nonce_only) return launch_rfc6979(ctx, curve, rfc6979_curve_order(curve), d_sk, m, d_out, d_status, n, stream);
+  return launch_ecdsa_sign(ctx, curve, d_sk, nullptr, nullptr, d_out, d_status, n, stream, &m);
 }
 
-// Schnorr::<C, Sha256>::sign from the message.  Host form: the engine as ecdsa_sign_msg_call uses it, one lane, the
-// chunk's messages in the same two slots.  sk is secret, and so are k and e * sk behind s: the staging and the stream
-// scratch (k, sk, R, P) are cleared on every way out.
+// Schnorr::<C, Sha256>::sign from the message.  sk is secret, and so are k and e * sk behind s.
 int schnorr_sign_msg_call(fec_ctx* ctx, int curve, const uint64_t* sk, const uint8_t* msgs, const uint64_t* off, size_t msg_len,
                           uint64_t* r_xy, uint8_t* r_inf, uint64_t* s_out, uint8_t* sig_bytes, uint8_t* status, size_t n) {
   if (!curve_ok(curve)) return FEC_E_ARG;
   if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519: its nonce and fixed-base instances are not built
-  if (!ctx || (n && (!sk || !r_xy || !r_inf || !s_out || !status))) return FEC_E_ARG;
-  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  if (n && (!sk || !r_xy || !r_inf || !s_out || !status)) return FEC_E_ARG;
   const HostArray a[] = {secret_input(sk, 32), ragged(off, 8), secret_output(r_xy, 64), output(r_inf, 1), secret_output(s_out, 32),
                          secret_output(sig_bytes, 64), output(status, 1)};
-  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[7], size_t cnt, size_t) {
-    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
-    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
-      SchnorrSignIo io{static_cast<const u32*>(d[0]), nullptr, nullptr, 0, static_cast<u32*>(d[2]), static_cast<unsigned char*>(d[3]),
-                       static_cast<u32*>(d[4]), static_cast<u32*>(d[5]), static_cast<unsigned char*>(d[6])};
-      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[1]), m, reb, st, io.msgs, io.off, io.msg_len);
-      if (rc != FEC_OK) return rc;
-      return launch_schnorr_sign(c, curve, io, m, st);
-    });
+  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    const SchnorrSignIo io{static_cast<const u32*>(d[0]), m, static_cast<u32*>(d[2]), static_cast<unsigned char*>(d[3]),
+                           static_cast<u32*>(d[4]), static_cast<u32*>(d[5]), static_cast<unsigned char*>(d[6])};
+    return launch_schnorr_sign(c, curve, io, cnt, st);
   });
 }
 // The challenge alone, all three curves.  Nothing is secret.
 int schnorr_challenge_call(fec_ctx* ctx, int curve, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy, const uint8_t* pk_inf,
                            const uint8_t* msgs, const uint64_t* off, size_t msg_len, uint64_t* e, size_t n) {
-  if (!ctx || !curve_ok(curve) || (n && (!r_xy || !pk_xy || !e))) return FEC_E_ARG;
-  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
+  if (!curve_ok(curve) || (n && (!r_xy || !pk_xy || !e))) return FEC_E_ARG;
   const HostArray a[] = {input(r_xy, 64), input(r_inf, 1), input(pk_xy, 64), input(pk_inf, 1), ragged(off, 8), output(e, 32)};
-  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[6], size_t cnt, size_t) {
-    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
-    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
-      SchnorrChallengeIo io{static_cast<const u32*>(d[0]), static_cast<const unsigned char*>(d[1]), static_cast<const u32*>(d[2]),
-                            static_cast<const unsigned char*>(d[3]), nullptr, nullptr, 0, static_cast<u32*>(d[5]), nullptr};
-      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[4]), m, reb, st, io.msgs, io.off, io.msg_len);
-      if (rc != FEC_OK) return rc;
-      return launch_schnorr_challenge(c, curve, io, m, st);
-    });
+  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    const SchnorrChallengeIo io{static_cast<const u32*>(d[0]), static_cast<const unsigned char*>(d[1]), static_cast<const u32*>(d[2]),
+                                static_cast<const unsigned char*>(d[3]), m, static_cast<u32*>(d[5]), nullptr};
+    return launch_schnorr_challenge(c, curve, io, cnt, st);
   });
 }
 
@@ -1607,7 +1597,7 @@ struct H2cCall {
 };
 // One pass and no work area, except P-256's H2C_HASH (kernels_h2c.hip: split at the map boundary); the uniform part
 // travels with the launch.
-int launch_h2c(fec_ctx* ctx, const H2cCall& c, const H2cMessages& m, void* out, unsigned char* inf, void* cand, unsigned char* legs,
+int launch_h2c(fec_ctx* ctx, const H2cCall& c, const Messages& m, void* out, unsigned char* inf, void* cand, unsigned char* legs,
                unsigned char* status, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
   void* work = nullptr;
@@ -1629,22 +1619,14 @@ int launch_map_to_curve(fec_ctx* ctx, int curve, const u32* u, u32* xy, u32* can
   map_to_curve_launch(curve, u, xy, cand, legs, n, L.s);
   return L.done();
 }
-// The host forms: the engine as msg_call uses it, one lane, the chunk's messages in the same two slots.  The messages may
-// be secret (passwords), so every output is staged as one: the staging and the stream scratch are cleared on every way out.
-// A stride of 0 or a null pointer: the array is absent.
+// The host forms.  The messages may be secret (passwords), so every output is staged as one.  A stride of 0 or a null
+// pointer: the array is absent.
 int h2c_msg_call(fec_ctx* ctx, const H2cCall& c, const uint8_t* msgs, const uint64_t* off, size_t msg_len, void* out, size_t out_stride,
                  uint8_t* inf, void* cand, size_t cand_stride, uint8_t* legs, size_t legs_stride, size_t n) {
-  if (!msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
   const HostArray a[] = {ragged(off, 8), secret_output(out_stride ? out : nullptr, out_stride), secret_output(inf, 1),
                          secret_output(cand_stride ? cand : nullptr, cand_stride), secret_output(legs_stride ? legs : nullptr, legs_stride)};
-  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[5], size_t cnt, size_t) {
-    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
-    return chunked(child, cnt, sa, 1, [&](fec_ctx* cc, void* const* d, size_t, size_t m, hipStream_t st) -> int {
-      H2cMessages hm{nullptr, nullptr, 0};
-      const int rc = stage_messages(cc, msgs, static_cast<const u64*>(d[0]), m, reb, st, hm.msgs, hm.off, hm.msg_len);
-      if (rc != FEC_OK) return rc;
-      return launch_h2c(cc, c, hm, d[1], static_cast<unsigned char*>(d[2]), d[3], static_cast<unsigned char*>(d[4]), nullptr, m, st);
-    });
+  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* cc, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_h2c(cc, c, m, d[1], static_cast<unsigned char*>(d[2]), d[3], static_cast<unsigned char*>(d[4]), nullptr, cnt, st);
   });
 }
 // The checks every form shares.  The bounds exist because the reference writes dst.len() and the block counter into a u8.
@@ -1663,10 +1645,6 @@ int h2c_mode_args(fec_ctx* ctx, int curve, int mode, int method, const uint8_t* 
   return dst_len == 0 ? FEC_E_ARG : FEC_OK;   // Err(DomainSeparationFailure), before any element is looked at
 }
 int h2c_count_args(size_t count) { return count == 0 ? FEC_E_ARG : (count > h2c::MAX_COUNT ? FEC_E_UNSUPPORTED : FEC_OK); }
-// the _dev forms' pointer rules for the message arrays
-bool h2c_dev_msgs_ok(const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, size_t n) {
-  return !(n && !d_msg_off) && !(msg_len && !d_msgs) && (reinterpret_cast<uintptr_t>(d_msg_off) & 7u) == 0;
-}
 }  // namespace
 
 extern "C" {
@@ -2826,38 +2804,27 @@ int fec_curve25519_field_op(fec_ctx* ctx, fec_field_opcode op, const uint64_t* a
 // ---- EdDSA signing for Ed25519 with SHA-512, and SHA-512 (kernels_eddsa.hip; helpers above the extern "C" block) ----
 
 int fec_sha512(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* digests, size_t n) try {
-  if (n && !digests) return FEC_E_ARG;
-  return msg_call(ctx, kSha512, nullptr, msgs, msg_off, msg_len, digests, nullptr, nullptr, nullptr, n);
+  return digest_call(ctx, kDigestSha512, msgs, msg_off, msg_len, digests, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_sha512_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
                    uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_msg_off || !d_digests)) || (msg_len && !d_msgs)) return FEC_E_ARG;
-  if (!aligned16(d_digests) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  if (n == 0) return FEC_OK;
-  Launch L(ctx, stream, "k_sha512");
-  sha512_launch(d_msgs, d_msg_off, msg_len, reinterpret_cast<u32*>(d_digests), d_status, n, L.s);
-  return L.done();
+  return digest_dev(ctx, kDigestSha512, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 int fec_ed25519_sign(fec_ctx* ctx, const uint8_t* private_keys, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                      uint8_t* sig, uint8_t* status, size_t n) try {
-  if (n && (!private_keys || !sig || !status)) return FEC_E_ARG;
-  return msg_call(ctx, EDDSA_MODE_SIGN, private_keys, msgs, msg_off, msg_len, sig, status, nullptr, nullptr, n);
+  return eddsa_sign_call(ctx, EDDSA_MODE_SIGN, private_keys, msgs, msg_off, msg_len, sig, status, nullptr, nullptr, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_ed25519_derive_public_key(fec_ctx* ctx, const uint8_t* private_keys, uint8_t* public_keys, uint8_t* status,
                                   size_t n) try {
-  if (n && (!private_keys || !public_keys || !status)) return FEC_E_ARG;
-  return msg_call(ctx, EDDSA_MODE_DERIVE, private_keys, nullptr, nullptr, 0, public_keys, status, nullptr, nullptr, n);
+  return eddsa_sign_call(ctx, EDDSA_MODE_DERIVE, private_keys, nullptr, nullptr, 0, public_keys, status, nullptr, nullptr, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_eddsa_sign_ed25519(fec_ctx* ctx, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                            uint64_t* r_xy, uint8_t* r_inf, uint64_t* s, uint8_t* status, size_t n) try {
-  if (n && (!sk || !r_xy || !r_inf || !s || !status)) return FEC_E_ARG;
-  return msg_call(ctx, EDDSA_MODE_GENERIC, sk, msgs, msg_off, msg_len, r_xy, status, r_inf, s, n);
+  return eddsa_sign_call(ctx, EDDSA_MODE_GENERIC, sk, msgs, msg_off, msg_len, r_xy, status, r_inf, s, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_ed25519_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
@@ -2904,20 +2871,12 @@ int fec_eddsa_verify_ed25519_msg_dev(fec_ctx* ctx, const uint64_t* d_pk_xy, cons
 // ---- SHA-256, ECDSA verification from the message, BIP-340 signing (kernels_schnorr.hip; helpers above) ----
 
 int fec_sha256(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* digests, size_t n) try {
-  if (n && !digests) return FEC_E_ARG;
-  return msg_call(ctx, kSha256, nullptr, msgs, msg_off, msg_len, digests, nullptr, nullptr, nullptr, n);
+  return digest_call(ctx, kDigestSha256, msgs, msg_off, msg_len, digests, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_sha256_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
                    uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_msg_off || !d_digests)) || (msg_len && !d_msgs)) return FEC_E_ARG;
-  if (!aligned16(d_digests) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  if (n == 0) return FEC_OK;
-  Launch L(ctx, stream, "k_sha256");
-  sha256_launch(d_msgs, d_msg_off, msg_len, reinterpret_cast<u32*>(d_digests), d_status, n, L.s);
-  return L.done();
+  return digest_dev(ctx, kDigestSha256, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 int fec_ecdsa_verify_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
@@ -2929,30 +2888,27 @@ int fec_ecdsa_verify_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, con
 int fec_ecdsa_verify_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                              const uint64_t* d_r, const uint64_t* d_s, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf,
                              uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_msg_off || !d_r || !d_s || !d_pk_xy || !d_status)) || (msg_len && !d_msgs)) return FEC_E_ARG;
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  const int bad = dev_messages(d_msgs, d_msg_off, msg_len, n, m);
+  if (bad == kDevMsgsNull || (n && (!d_r || !d_s || !d_pk_xy || !d_status))) return FEC_E_ARG;
   if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
-  if (!aligned16(d_r) || !aligned16(d_s) || !aligned16(d_pk_xy) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const EcdsaMessages em{d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len, true};
-  return launch_ecdsa_verify(ctx, curve, nullptr, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n, stream, &em);
+  if (bad || !aligned16(d_r) || !aligned16(d_s) || !aligned16(d_pk_xy)) return FEC_E_ARG;
+  return launch_ecdsa_verify(ctx, curve, nullptr, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n, stream, &m, true);
 } FEC_ABI_CATCH_STATUS
 
 int fec_bip340_sign(fec_ctx* ctx, const uint8_t* private_keys, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                     uint8_t* signatures, uint8_t* status, size_t n) try {
-  if (n && (!private_keys || !signatures || !status)) return FEC_E_ARG;
-  return msg_call(ctx, kBip340, private_keys, msgs, msg_off, msg_len, signatures, status, nullptr, nullptr, n);
+  return bip340_sign_call(ctx, private_keys, msgs, msg_off, msg_len, signatures, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_bip340_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                         size_t msg_len, uint8_t* d_signatures, uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_private_keys || !d_signatures || !d_status || !d_msg_off)) || (msg_len && !d_msgs)) return FEC_E_ARG;
-  if (!aligned16(d_private_keys) || !aligned16(d_signatures) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const Bip340Io io{reinterpret_cast<const u32*>(d_private_keys), d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len,
-                    reinterpret_cast<u32*>(d_signatures), d_status};
-  return launch_bip340_sign(ctx, io, n, stream);
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_private_keys || !d_signatures || !d_status))) return FEC_E_ARG;
+  if (!aligned16(d_private_keys) || !aligned16(d_signatures)) return FEC_E_ARG;
+  return launch_bip340_sign(ctx, Bip340Io{reinterpret_cast<const u32*>(d_private_keys), m, reinterpret_cast<u32*>(d_signatures), d_status}, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 // ---- ECDSA signing from the message, RFC 6979 nonces (kernels_rfc6979.hip; helpers above) ----
@@ -3001,12 +2957,12 @@ int fec_schnorr_challenge(fec_ctx* ctx, fec_curve curve, const uint64_t* r_xy, c
 int fec_schnorr_challenge_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_r_xy, const uint8_t* d_r_inf, const uint64_t* d_pk_xy,
                               const uint8_t* d_pk_inf, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint64_t* d_e,
                               uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!d_r_xy || !d_pk_xy || !d_msg_off || !d_e || !d_status)) || (msg_len && !d_msgs)) return FEC_E_ARG;
-  if (!aligned16(d_r_xy) || !aligned16(d_pk_xy) || !aligned16(d_e) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const SchnorrChallengeIo io{reinterpret_cast<const u32*>(d_r_xy), d_r_inf, reinterpret_cast<const u32*>(d_pk_xy), d_pk_inf, d_msgs,
-                              reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len, reinterpret_cast<u32*>(d_e), d_status};
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || !curve_ok(curve) || (n && (!d_r_xy || !d_pk_xy || !d_e || !d_status))) return FEC_E_ARG;
+  if (!aligned16(d_r_xy) || !aligned16(d_pk_xy) || !aligned16(d_e)) return FEC_E_ARG;
+  const SchnorrChallengeIo io{reinterpret_cast<const u32*>(d_r_xy), d_r_inf, reinterpret_cast<const u32*>(d_pk_xy), d_pk_inf, m,
+                              reinterpret_cast<u32*>(d_e), d_status};
   return launch_schnorr_challenge(ctx, curve, io, n, stream);
 } FEC_ABI_CATCH_STATUS
 
@@ -3017,15 +2973,14 @@ int fec_schnorr_sign_msg(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, cons
 int fec_schnorr_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                              size_t msg_len, uint64_t* d_r_xy, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_sig_bytes, uint8_t* d_status,
                              size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!d_sk || !d_msg_off || !d_r_xy || !d_r_inf || !d_s || !d_status)) || (msg_len && !d_msgs))
-    return FEC_E_ARG;
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  const int bad = dev_messages(d_msgs, d_msg_off, msg_len, n, m);
+  if (bad == kDevMsgsNull || !curve_ok(curve) || (n && (!d_sk || !d_r_xy || !d_r_inf || !d_s || !d_status))) return FEC_E_ARG;
   if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
-  if (!aligned16(d_sk) || !aligned16(d_r_xy) || !aligned16(d_s) || !aligned16(d_sig_bytes) || (reinterpret_cast<uintptr_t>(d_msg_off) & 7u))
-    return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  const SchnorrSignIo io{reinterpret_cast<const u32*>(d_sk), d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len,
-                         reinterpret_cast<u32*>(d_r_xy), d_r_inf, reinterpret_cast<u32*>(d_s), reinterpret_cast<u32*>(d_sig_bytes), d_status};
+  if (bad || !aligned16(d_sk) || !aligned16(d_r_xy) || !aligned16(d_s) || !aligned16(d_sig_bytes)) return FEC_E_ARG;
+  const SchnorrSignIo io{reinterpret_cast<const u32*>(d_sk), m, reinterpret_cast<u32*>(d_r_xy), d_r_inf, reinterpret_cast<u32*>(d_s),
+                         reinterpret_cast<u32*>(d_sig_bytes), d_status};
   return launch_schnorr_sign(ctx, curve, io, n, stream);
 } FEC_ABI_CATCH_STATUS
 
@@ -3042,13 +2997,13 @@ int fec_expand_message_xmd(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* ms
 
 int fec_expand_message_xmd_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, const uint8_t* dst,
                                size_t dst_len, size_t out_len, uint8_t* d_out, uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (dst_len && !dst)) return FEC_E_ARG;
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (dst_len && !dst) return FEC_E_ARG;
   if (dst_len > h2c::MAX_DST || out_len > h2c::MAX_OUT) return FEC_E_UNSUPPORTED;
-  if (!h2c_dev_msgs_ok(d_msgs, d_msg_off, msg_len, n) || (n && out_len && !d_out) || !aligned16(d_out)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && out_len && !d_out) || !aligned16(d_out)) return FEC_E_ARG;
   const H2cCall c{kH2cXmd, 0, 0, h2c::make_params(dst, dst_len, out_len)};
-  return launch_h2c(ctx, c, H2cMessages{d_msgs, d_msg_off, (u64)msg_len}, d_out, nullptr, nullptr, nullptr, d_status, n, stream);
+  return launch_h2c(ctx, c, m, d_out, nullptr, nullptr, nullptr, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 int fec_hash_to_field(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* dst,
@@ -3063,14 +3018,14 @@ int fec_hash_to_field(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const 
 
 int fec_hash_to_field_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                           const uint8_t* dst, size_t dst_len, size_t count, uint64_t* d_u, uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  int rc = h2c_args(ctx, curve, dst, dst_len);
+  int rc = dev_enter(ctx);
+  if (rc == FEC_OK) rc = h2c_args(ctx, curve, dst, dst_len);
   if (rc == FEC_OK) rc = h2c_count_args(count);
   if (rc != FEC_OK) return rc;
-  if (!h2c_dev_msgs_ok(d_msgs, d_msg_off, msg_len, n) || (n && !d_u) || !aligned16(d_u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && !d_u) || !aligned16(d_u)) return FEC_E_ARG;
   const H2cCall c{kH2cField, curve, 0, h2c::make_params(dst, dst_len, 32 * count)};
-  return launch_h2c(ctx, c, H2cMessages{d_msgs, d_msg_off, (u64)msg_len}, d_u, nullptr, nullptr, nullptr, d_status, n, stream);
+  return launch_h2c(ctx, c, m, d_u, nullptr, nullptr, nullptr, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 int fec_map_to_curve(fec_ctx* ctx, fec_curve curve, const uint64_t* u, uint64_t* xy, uint64_t* cand, uint8_t* legs, size_t n) try {
@@ -3107,14 +3062,14 @@ int fec_hash_to_curve(fec_ctx* ctx, fec_curve curve, int mode, int method, const
 int fec_hash_to_curve_dev(fec_ctx* ctx, fec_curve curve, int mode, int method, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                           size_t msg_len, const uint8_t* dst, size_t dst_len, uint64_t* d_out, uint64_t* d_cand, uint8_t* d_legs,
                           uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  const int rc = h2c_mode_args(ctx, curve, mode, method, dst, dst_len);
+  int rc = dev_enter(ctx);
+  if (rc == FEC_OK) rc = h2c_mode_args(ctx, curve, mode, method, dst, dst_len);
   if (rc != FEC_OK) return rc;
-  if (!h2c_dev_msgs_ok(d_msgs, d_msg_off, msg_len, n) || (n && !d_out) || !aligned16(d_out) || !aligned16(d_cand)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && !d_out) || !aligned16(d_out) || !aligned16(d_cand)) return FEC_E_ARG;
   const size_t maps = mode == FEC_H2C_HASH ? 2 : 1;
   const H2cCall c{kH2cCurve, curve, mode == FEC_H2C_HASH ? H2C_HASH : H2C_ENCODE, h2c::make_params(dst, dst_len, 32 * maps)};
-  return launch_h2c(ctx, c, H2cMessages{d_msgs, d_msg_off, (u64)msg_len}, d_out, nullptr, d_cand, d_legs, d_status, n, stream);
+  return launch_h2c(ctx, c, m, d_out, nullptr, d_cand, d_legs, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 // (secp256k1: 96 uniform bytes under dst_prime; P-256: the plain template, SHA-256(msg || dst))
@@ -3134,13 +3089,13 @@ int fec_curve_hash_to_curve(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, 
 int fec_curve_hash_to_curve_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                                 const uint8_t* dst, size_t dst_len, uint64_t* d_xy, uint8_t* d_inf, uint8_t* d_status, size_t n,
                                 void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  const int rc = h2c_args(ctx, curve, dst, dst_len);
+  int rc = dev_enter(ctx);
+  if (rc == FEC_OK) rc = h2c_args(ctx, curve, dst, dst_len);
   if (rc != FEC_OK) return rc;
-  if (!h2c_dev_msgs_ok(d_msgs, d_msg_off, msg_len, n) || (n && (!d_xy || !d_inf)) || !aligned16(d_xy)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_xy || !d_inf)) || !aligned16(d_xy)) return FEC_E_ARG;
   const H2cCall c{kH2cCurve, curve, H2C_TRAIT, curve_h2c_params(curve, dst, dst_len)};
-  return launch_h2c(ctx, c, H2cMessages{d_msgs, d_msg_off, (u64)msg_len}, d_xy, d_inf, nullptr, nullptr, d_status, n, stream);
+  return launch_h2c(ctx, c, m, d_xy, d_inf, nullptr, nullptr, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 // Debug hook: fec_rfc6979_k with the caller's comparison constant instead of the curve's.  At least 2^254, so that a

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "limbs.hpp"
+#include "messages.hpp"
 
 namespace fecgpu {
 
@@ -124,17 +125,15 @@ void x25519_field_launch(int op, const u32* a, const u32* b, u32* out, size_t n,
 
 // kernels_eddsa.hip: the reference's EdDSA signing for Ed25519 with SHA-512 (forge-ec-signature/src/eddsa.rs) around
 // one fixed-base launch over the pre pass's scalars (a at [0, n), r at [n, 2n); derive: a only; 8 words each), and the
-// per-message SHA-512.  Messages: element i is msgs[off[i], off[i+1]) (n + 1 offsets; each lane checks its range
-// against msg_len).  out: EDDSA_MODE_SIGN 16 words (the signature's 64 bytes), EDDSA_MODE_DERIVE 8 words (32 bytes),
+// per-message SHA-512.  Messages: messages.hpp (each lane checks its own range).  out: EDDSA_MODE_SIGN 16 words (the
+// signature's 64 bytes), EDDSA_MODE_DERIVE 8 words (32 bytes),
 // EDDSA_MODE_GENERIC 16 words (R's affine x then y) with r_inf and s (8 words); status one byte.  gen: generator()
 // (32 words; EDDSA_MODE_GENERIC's special cases).  flags: one byte per element between the two passes.
 enum : int { EDDSA_MODE_SIGN = 0, EDDSA_MODE_DERIVE = 1, EDDSA_MODE_GENERIC = 2 };
 struct EddsaSignIo {
   int mode;
   const u32* keys;   // SIGN / DERIVE: the 32 private-key bytes; GENERIC: the raw Scalar limbs
-  const unsigned char* msgs;
-  const u64* off;
-  u64 msg_len;
+  Messages msg;
   const u32* gen;
   u32* out;
   unsigned char* r_inf;
@@ -145,8 +144,7 @@ void eddsa_sign_pre_launch(const EddsaSignIo& io, u32* scal, unsigned char* flag
 void eddsa_sign_finish_launch(const EddsaSignIo& io, const u32* scal, const u32* pts, const unsigned char* flags, size_t n,
                               hipStream_t s);
 // digests: 16 words (64 bytes) per message, zero where the range is bad; status (may be null): 0, or 4 for a bad range
-void sha512_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
-                   hipStream_t s);
+void sha512_launch(const Messages& msgs, u32* out, unsigned char* status, size_t n, hipStream_t s);
 
 // kernels_eddsa.hip: the reference's two Ed25519 EdDSA verifiers FROM THE MESSAGE (eddsa.rs:360-447 Ed25519Signature::
 // verify on bytes; 156-212 EdDsa::<Ed25519, Sha512>::verify on a decoded key and signature) around the two multiplications
@@ -159,9 +157,7 @@ struct EddsaVerifyIo {
   int form;
   const u32* pk;                 // BYTES: the 32 public-key bytes; GENERIC: the affine x then y (16 words)
   const unsigned char* pk_inf;   // GENERIC (may be null)
-  const unsigned char* msgs;
-  const u64* off;
-  u64 msg_len;
+  Messages msg;
   const u32* sig;                // BYTES: the 64 signature bytes; GENERIC: R's affine x then y (16 words)
   const unsigned char* r_inf;    // GENERIC (may be null)
   const u32* s;                  // GENERIC: the raw Scalar limbs
@@ -175,8 +171,7 @@ void eddsa_verify_msg_finish_launch(const EddsaVerifyWork& w, unsigned char* sta
 
 // kernels_schnorr.hip: SHA-256 per message, as sha512_launch: digests 8 words (32 bytes) per message, zero where the
 // range is bad; status (may be null): 0, or 4 for a bad range
-void sha256_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
-                   hipStream_t s);
+void sha256_launch(const Messages& msgs, u32* out, unsigned char* status, size_t n, hipStream_t s);
 // status[i] = bad[i] where bad[i] != 0: the status of a pass whose outputs went on into a verifier or a signer
 // (sha256_launch: 4; rfc6979_launch: 4 or 5).  With `sig` (16 words per element) a bad range's signature is zeroed too.
 void bad_range_status_launch(const unsigned char* bad, unsigned char* status, size_t n, hipStream_t s, u32* sig = nullptr);
@@ -189,9 +184,7 @@ void bad_range_status_launch(const unsigned char* bad, unsigned char* status, si
 // (ecdsa.rs:101-104) first; a rejected key draws no nonce: k = h1 = 0, status 0 (the signer's finishing pass reports it).
 struct Rfc6979Io {
   const u32* sk;
-  const unsigned char* msgs;
-  const u64* off;
-  u64 msg_len;
+  Messages msg;
   u32* k;
   u32* h1;
   unsigned char* status;
@@ -208,9 +201,7 @@ void rfc6979_launch(int curve, const Rfc6979Io& io, const Rfc6979Order& order, b
 // pass, d' = -d or d after the middle one), k (8 words), px (8 words: the value P.x.to_bytes() encodes), one flag byte.
 struct Bip340Io {
   const u32* keys;
-  const unsigned char* msgs;
-  const u64* off;
-  u64 msg_len;
+  Messages msg;
   u32* sig;
   unsigned char* status;
 };
@@ -234,18 +225,14 @@ struct SchnorrChallengeIo {
   const unsigned char* r_inf;
   const u32* pk_xy;
   const unsigned char* pk_inf;
-  const unsigned char* msgs;
-  const u64* off;
-  u64 msg_len;
+  Messages msg;
   u32* e;
   unsigned char* status;
 };
 void schnorr_challenge_launch(int curve, const SchnorrChallengeIo& io, size_t n, hipStream_t s);
 struct SchnorrSignIo {
   const u32* sk;
-  const unsigned char* msgs;
-  const u64* off;
-  u64 msg_len;
+  Messages msg;
   u32* r_xy;
   unsigned char* r_inf;
   u32* s;
@@ -300,16 +287,11 @@ void ecdh_exchange_finish_launch(int curve, const u32* pub, const u32* t, const 
 namespace h2c {
 struct Params;
 }
-struct H2cMessages {
-  const unsigned char* msgs;
-  const u64* off;
-  u64 msg_len;
-};
 constexpr int H2C_HASH = 0, H2C_ENCODE = 1, H2C_TRAIT = 2, H2C_MAPS = 3;   // (H2C_MAPS: inside kernels_h2c.hip only)
-void xmd_launch(const H2cMessages& m, const h2c::Params& p, unsigned char* out, unsigned char* status, size_t n, hipStream_t s);
-void hash_to_field_launch(int curve, const H2cMessages& m, const h2c::Params& p, u32* u, unsigned char* status, size_t n, hipStream_t s);
+void xmd_launch(const Messages& m, const h2c::Params& p, unsigned char* out, unsigned char* status, size_t n, hipStream_t s);
+void hash_to_field_launch(int curve, const Messages& m, const h2c::Params& p, u32* u, unsigned char* status, size_t n, hipStream_t s);
 void map_to_curve_launch(int curve, const u32* u, u32* xy, u32* cand, unsigned char* legs, size_t n, hipStream_t s);
-void h2c_launch(int curve, int form, const H2cMessages& m, const h2c::Params& p, u32* out, unsigned char* inf, u32* cand,
+void h2c_launch(int curve, int form, const Messages& m, const h2c::Params& p, u32* out, unsigned char* inf, u32* cand,
                 unsigned char* legs, unsigned char* status, void* work, size_t n, hipStream_t s);
 size_t h2c_work_bytes(int curve, int form, size_t n);
 

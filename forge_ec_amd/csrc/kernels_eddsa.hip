@@ -46,7 +46,7 @@
 //  * status: 1 where the reference panics -- to_affine (ed25519.rs:1793-1811) unwraps z.invert(), which is None for a
 //    zero z of a point that is not the identity; 2 where only a debug build panics -- Mul's u128 column sums pass 2^128
 //    (the release build wraps and goes on: the output is the release value); 4 (the *_dev forms) where the element's
-//    message range [off[i], off[i+1]) is not inside [0, msg_len): nothing of the message is read and the outputs are 0.
+//    message range is bad (messages.hpp: message_at): nothing of the message is read and the outputs are 0.
 //    Where status has bit 1 the outputs are 0.
 #include <hip/hip_runtime.h>
 
@@ -57,6 +57,7 @@
 #include "sha512.hpp"
 #include "staging.hpp"
 #include "kernels.hpp"
+#include "messages.hpp"
 
 namespace fecgpu {
 
@@ -92,14 +93,6 @@ FEC_DEV ed::sc4 scalar_be(const sha512::state& h, int q) {
   ed::sc4 s;
   FEC_UNROLL for (int i = 0; i < 4; ++i) s.l[i] = h.h[4 * q + 3 - i];
   return s;
-}
-// Element i's message range; false (and nothing read) where it is not inside [0, msg_len)
-FEC_DEV bool msg_range(const u64* __restrict__ off, u64 msg_len, size_t i, u64& lo, u64& len) {
-  const u64 a = off[i], b = off[i + 1];
-  const bool ok = a <= b && b <= msg_len;
-  lo = ok ? a : 0;
-  len = ok ? b - a : 0;
-  return ok;
 }
 FEC_DEV bool is_test_message(const unsigned char* m, u64 len) {   // msg == b"test message"
   if (len != 12) return false;
@@ -153,13 +146,12 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_pre(EddsaSignIo io, u32* __r
     key0 = kw[0] & 0xFFu;
   }
   unsigned char f = 0;
-  u64 lo = 0, len = 0;
+  u64 len = 0;
   const unsigned char* m = nullptr;
   if (io.mode == EDDSA_MODE_DERIVE) {
     if (key0 == 0x9d) f |= F_RFC;                                               // 452
   } else {
-    if (!msg_range(io.off, io.msg_len, i, lo, len)) f |= F_BAD_RANGE;
-    m = len ? io.msgs + lo : nullptr;
+    if (!message_at(io.msg, i, m, len)) f |= F_BAD_RANGE;
     if (is_test_message(m, len)) f |= F_TEST_MESSAGE;                          // 269, 45
     if (!(f & F_BAD_RANGE) && len == 0 && key0 == 0x9d) f |= F_RFC;             // 281, 55
   }
@@ -216,9 +208,9 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_finish(EddsaSignIo io, const
   const bool inf_r = affine_of(pts + (n + i) * 32, xr, yr, panic_r);           // 325-326
   const u32 pr = prefix_byte(yr, inf_r);
   const fe xrb = ed::reduce(xr);
-  u64 lo = 0, len = 0;
-  const bool ok = msg_range(io.off, io.msg_len, i, lo, len);
-  const unsigned char* m = ok && len ? io.msgs + lo : nullptr;
+  u64 len;
+  const unsigned char* m;
+  (void)message_at(io.msg, i, m, len);
   u32 pre[17];
   prefix_r33_a33(pre, pr, xrb, pa, xab);
   ed::sc4 s = {{0, 0, 0, 0}};
@@ -282,16 +274,16 @@ __global__ __launch_bounds__(TPB) void k_eddsa_sign_finish(EddsaSignIo io, const
   store_w8(io.s + i * 8, w);
 }
 
-__global__ __launch_bounds__(TPB) void k_sha512(const unsigned char* __restrict__ msgs, const u64* __restrict__ off, u64 msg_len,
-                                                u32* __restrict__ out, unsigned char* __restrict__ status, size_t n) {
+__global__ __launch_bounds__(TPB) void k_sha512(Messages msgs, u32* __restrict__ out, unsigned char* __restrict__ status, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  u64 lo, len;
-  const bool ok = msg_range(off, msg_len, i, lo, len);
+  u64 len;
+  const unsigned char* m;
+  const bool ok = message_at(msgs, i, m, len);
   u32 o[16];
   if (ok) {
     const u32 none[1] = {0};
-    sha512::digest_words(sha512::hash_prefixed<1>(none, 0, len ? msgs + lo : nullptr, len), o);
+    sha512::digest_words(sha512::hash_prefixed<1>(none, 0, m, len), o);
   } else {
     FEC_UNROLL for (int j = 0; j < 16; ++j) o[j] = 0;
   }
@@ -307,10 +299,10 @@ template <int FORM>
 __global__ __launch_bounds__(TPB) void k_eddsa_verify_msg_pre(EddsaVerifyIo io, EddsaVerifyWork w, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  u64 lo = 0, len = 0;
+  u64 len;
+  const unsigned char* m;
   unsigned char f = 0;
-  if (!msg_range(io.off, io.msg_len, i, lo, len)) f = V_DECIDED | 4;
-  const unsigned char* m = len ? io.msgs + lo : nullptr;
+  if (!message_at(io.msg, i, m, len)) f = V_DECIDED | 4;
   if (f == 0) {
     if (is_test_message(m, len) || len == 0) f = V_DECIDED | 1;            // 362-369, 158-165
     else if (is_different_message(m, len)) f = V_DECIDED | 0;             // 372-374, 168-170
@@ -400,9 +392,8 @@ void eddsa_verify_msg_pre_launch(const EddsaVerifyIo& io, const EddsaVerifyWork&
 void eddsa_verify_msg_finish_launch(const EddsaVerifyWork& w, unsigned char* status, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_eddsa_verify_msg_finish, dim3(grid(n)), dim3(TPB), 0, s, w, status, n);
 }
-void sha512_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
-                   hipStream_t s) {
-  hipLaunchKernelGGL(k_sha512, dim3(grid(n)), dim3(TPB), 0, s, msgs, off, msg_len, out, status, n);
+void sha512_launch(const Messages& msgs, u32* out, unsigned char* status, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_sha512, dim3(grid(n)), dim3(TPB), 0, s, msgs, out, status, n);
 }
 
 }  // namespace fecgpu

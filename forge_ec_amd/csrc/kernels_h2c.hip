@@ -16,13 +16,14 @@
 //                       points in the call's work area and k_h2c_add adds them.  secp256k1 ships fused.
 // One element per lane; the hash state lives in VGPRs.  dst and the lengths are the same for the whole batch and come
 // with the launch (h2c::Params by value): every branch on dst, count or the form is scalar.
-// Secret: the messages and everything derived from them.
+// Element i's message: messages.hpp (message_at).  Secret: the messages and everything derived from them.
 #include <hip/hip_runtime.h>
 
 #include "../../include/fecgpu.h"
 #include "h2c.hpp"
 #include "hkdf.hpp"
 #include "kernels.hpp"
+#include "messages.hpp"
 #include "staging.hpp"
 
 namespace fecgpu {
@@ -32,27 +33,19 @@ namespace {
 using h2c::MP256;
 using h2c::MSecp;
 
-// Element i's message range; false (and nothing read) where it is not inside [0, msg_len)  (as kernels_schnorr.hip)
-FEC_DEV bool msg_range(const u64* __restrict__ off, u64 msg_len, size_t i, u64& lo, u64& len) {
-  const u64 a = off[i], b = off[i + 1];
-  const bool ok = a <= b && b <= msg_len;
-  lo = ok ? a : 0;
-  len = ok ? b - a : 0;
-  return ok;
-}
-
 // out: p.out_len bytes per element, packed behind a 16-byte aligned base
-__global__ __launch_bounds__(TPB) void k_xmd(H2cMessages m, const h2c::Params p, unsigned char* __restrict__ out,
+__global__ __launch_bounds__(TPB) void k_xmd(Messages m, const h2c::Params p, unsigned char* __restrict__ out,
                                              unsigned char* __restrict__ status, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  u64 lo, len;
-  const bool ok = msg_range(m.off, m.msg_len, i, lo, len);
+  u64 len;
+  const unsigned char* msg;
+  const bool ok = message_at(m, i, msg, len);
   if (status) status[i] = ok ? 0 : 4;
   const u32 L = p.out_len;
   if (L == 0) return;
   const u32 ell = (L + 31) >> 5, align = hkdf::row_align(L);
-  const sha256::state b0 = h2c::xmd_b0(p, len ? m.msgs + lo : nullptr, len);
+  const sha256::state b0 = h2c::xmd_b0(p, msg, len);
   sha256::state b = b0;
   unsigned char* row = out + i * (size_t)L;
 #pragma unroll 1
@@ -67,15 +60,16 @@ __global__ __launch_bounds__(TPB) void k_xmd(H2cMessages m, const h2c::Params p,
 
 // u: count field elements (8 words each) per element; p.out_len = 32 * count
 template <class K>
-__global__ __launch_bounds__(TPB) void k_hash_to_field(H2cMessages m, const h2c::Params p, u32* __restrict__ u,
+__global__ __launch_bounds__(TPB) void k_hash_to_field(Messages m, const h2c::Params p, u32* __restrict__ u,
                                                        unsigned char* __restrict__ status, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  u64 lo, len;
-  const bool ok = msg_range(m.off, m.msg_len, i, lo, len);
+  u64 len;
+  const unsigned char* msg;
+  const bool ok = message_at(m, i, msg, len);
   if (status) status[i] = ok ? 0 : 4;
   const u32 count = p.out_len >> 5;
-  const sha256::state b0 = h2c::xmd_b0(p, len ? m.msgs + lo : nullptr, len);
+  const sha256::state b0 = h2c::xmd_b0(p, msg, len);
   sha256::state b = b0;
 #pragma unroll 1
   for (u32 k = 1; k <= count; ++k) {
@@ -107,7 +101,7 @@ __global__ __launch_bounds__(TPB) void k_map_to_curve(const u32* __restrict__ u,
 // form of H2C_HASH) 32 words, the two mapped affine points, and in inf whether the range was bad.  cand (may be null):
 // 16 words per map; legs (may be null): one byte per map.  A bad range: status 4 and zero outputs.
 template <class K, int FORM>
-__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(3))) void k_h2c(H2cMessages m, const h2c::Params p,
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(3))) void k_h2c(Messages m, const h2c::Params p,
                                                                                       u32* __restrict__ out, unsigned char* __restrict__ inf,
                                                                                       u32* __restrict__ cand, unsigned char* __restrict__ legs,
                                                                                       unsigned char* __restrict__ status, size_t n) {
@@ -117,8 +111,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(3))) void k
   constexpr bool TWO = FORM == H2C_HASH || FORM == H2C_MAPS || (FORM == H2C_TRAIT && !K::IS_P256);
   constexpr int OUT_FE = FORM == H2C_TRAIT ? 2 : (FORM == H2C_MAPS ? 4 : 3);
   constexpr int MAPS = TWO ? 2 : 1;
-  u64 lo, len;
-  if (!msg_range(m.off, m.msg_len, i, lo, len)) {       // a bad range: status 4, zero outputs, nothing else
+  u64 len;
+  const unsigned char* msg;
+  if (!message_at(m, i, msg, len)) {                     // a bad range: status 4, zero outputs, nothing else
     const fe z = fe_zero();
     FEC_UNROLL for (int k = 0; k < OUT_FE; ++k) store_fe16(out + i * (8 * OUT_FE) + 8 * k, z);
     if constexpr (FORM == H2C_TRAIT) inf[i] = 0;
@@ -132,7 +127,6 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(3))) void k
     if (status) status[i] = 4;
     return;
   }
-  const unsigned char* msg = len ? m.msgs + lo : nullptr;
   fe u0, u1 = fe_zero();
   bool fell0 = false, fell1 = false;
   if constexpr (FORM == H2C_TRAIT && K::IS_P256) {       // core:1558-1570: one SHA-256 of msg || dst
@@ -214,7 +208,7 @@ __global__ __launch_bounds__(TPB) void k_h2c_add(const u32* __restrict__ maps, c
 unsigned grid(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 template <class K>
-void h2c_launch_k(int form, const H2cMessages& m, const h2c::Params& p, u32* out, unsigned char* inf, u32* cand, unsigned char* legs,
+void h2c_launch_k(int form, const Messages& m, const h2c::Params& p, u32* out, unsigned char* inf, u32* cand, unsigned char* legs,
                   unsigned char* status, void* work, size_t n, hipStream_t s) {
   const dim3 g(grid(n)), b(TPB);
   if (form == H2C_HASH) {
@@ -235,10 +229,10 @@ void h2c_launch_k(int form, const H2cMessages& m, const h2c::Params& p, u32* out
 
 }  // namespace
 
-void xmd_launch(const H2cMessages& m, const h2c::Params& p, unsigned char* out, unsigned char* status, size_t n, hipStream_t s) {
+void xmd_launch(const Messages& m, const h2c::Params& p, unsigned char* out, unsigned char* status, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_xmd, dim3(grid(n)), dim3(TPB), 0, s, m, p, out, status, n);
 }
-void hash_to_field_launch(int curve, const H2cMessages& m, const h2c::Params& p, u32* u, unsigned char* status, size_t n, hipStream_t s) {
+void hash_to_field_launch(int curve, const Messages& m, const h2c::Params& p, u32* u, unsigned char* status, size_t n, hipStream_t s) {
   const dim3 g(grid(n)), b(TPB);
   if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_hash_to_field<MSecp>), g, b, 0, s, m, p, u, status, n);
   else hipLaunchKernelGGL((k_hash_to_field<MP256>), g, b, 0, s, m, p, u, status, n);
@@ -249,7 +243,7 @@ void map_to_curve_launch(int curve, const u32* u, u32* xy, u32* cand, unsigned c
   else hipLaunchKernelGGL((k_map_to_curve<MP256>), g, b, 0, s, u, xy, cand, legs, n);
 }
 size_t h2c_work_bytes(int curve, int form, size_t n) { return curve == FEC_P256 && form == H2C_HASH ? n * 129 : 0; }
-void h2c_launch(int curve, int form, const H2cMessages& m, const h2c::Params& p, u32* out, unsigned char* inf, u32* cand,
+void h2c_launch(int curve, int form, const Messages& m, const h2c::Params& p, u32* out, unsigned char* inf, u32* cand,
                 unsigned char* legs, unsigned char* status, void* work, size_t n, hipStream_t s) {
   if (curve == FEC_SECP256K1) h2c_launch_k<MSecp>(form, m, p, out, inf, cand, legs, status, work, n, s);
   else h2c_launch_k<MP256>(form, m, p, out, inf, cand, legs, status, work, n, s);

@@ -1,6 +1,6 @@
 // kernels_rfc6979.hip -- Rfc6979::<C, Sha256>::generate_k per element (forge-ec-rng/src/rfc6979.rs:58-181), the pass
 // that turns fec_ecdsa_sign into Ecdsa::<C, Sha256>::sign from the message (fecgpu.hip: launch_ecdsa_sign):
-//   k_rfc6979<E>   the message range; with check_key the key check of sign_internal (ecdsa.rs:101-104) -- a rejected
+//   k_rfc6979<E>   the message (messages.hpp: message_at); with check_key the key check of sign_internal (ecdsa.rs:101-104) -- a rejected
 //                  key draws no nonce, the reference returns before it hashes --; h1 = SHA-256(msg); the HMAC-DRBG chain
 //                  of rfc6979.hpp under the comparison constant the launch passes; k and h1 into the work area.
 // One element per lane, a plain grid; the hash state and the whole chain live in VGPRs (sha256.hpp, rfc6979.hpp: the
@@ -12,6 +12,7 @@
 
 #include "../../include/fecgpu.h"
 #include "kernels.hpp"
+#include "messages.hpp"
 #include "p256.hpp"
 #include "rfc6979.hpp"
 #include "secp256k1.hpp"
@@ -20,15 +21,6 @@
 namespace fecgpu {
 
 namespace {
-
-// Element i's message range; false (and nothing read) where it is not inside [0, msg_len)  (as kernels_schnorr.hip)
-FEC_DEV bool msg_range(const u64* __restrict__ off, u64 msg_len, size_t i, u64& lo, u64& len) {
-  const u64 a = off[i], b = off[i + 1];
-  const bool ok = a <= b && b <= msg_len;
-  lo = ok ? a : 0;
-  len = ok ? b - a : 0;
-  return ok;
-}
 
 // sk.is_zero() || !sk.ct_lt(&order) with each curve's own ct_lt, as k_ecdsa_sign_finish tests it (kernels_ecdsa.hip:
 // ESecp::sk_bad, EP256::sk_bad): secp256k1's override is a true comparison with the reference's N; P-256's is the
@@ -46,13 +38,14 @@ template <class E>
 __global__ __launch_bounds__(TPB) void k_rfc6979(Rfc6979Io io, Rfc6979Order order, int check_key, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  u64 lo, len;
-  const bool ok = msg_range(io.off, io.msg_len, i, lo, len);
+  u64 len;
+  const unsigned char* m;
+  const bool ok = message_at(io.msg, i, m, len);
   const fe sk = load_fe16(io.sk + i * 8);
   u32 k[8] = {0, 0, 0, 0, 0, 0, 0, 0}, h1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned char st = ok ? 0 : 4;
   if (ok && !(check_key != 0 && E::sk_bad(sk))) {
-    st = rfc6979::nonce_from_message(sk.w, len ? io.msgs + lo : nullptr, len, order.w, k, h1);
+    st = rfc6979::nonce_from_message(sk.w, m, len, order.w, k, h1);
     if (st != 0) {
       FEC_UNROLL for (int j = 0; j < 8; ++j) h1[j] = 0;
     }

@@ -35,7 +35,7 @@
 //  * The "test message" signature and the fallback of a failed from_bytes are the same 64 bytes 0..63 (311-314,
 //    328-330); the status tells them apart.
 //  * status: 0 computed; 1 the "test message" pattern; 2 the 0..63 fallback (d, k or e not below N); 3 the reference
-//    panics -- never written, see above; 4 (the *_dev forms) a bad message range: nothing of the message is read and
+//    panics -- never written, see above; 4 (the *_dev forms) a bad message range (messages.hpp: message_at): nothing of the message is read and
 //    the signature is 0.
 // Secret: d, d', k, k' and the digest behind k.  The digest stays in registers; d' and k sit in the work area.
 #include <hip/hip_runtime.h>
@@ -43,6 +43,7 @@
 #include "../../include/fecgpu.h"
 #include "bip340.hpp"
 #include "kernels.hpp"
+#include "messages.hpp"
 #include "schnorr_sign.hpp"
 #include "secp256k1.hpp"
 #include "sha256.hpp"
@@ -52,24 +53,16 @@ namespace fecgpu {
 
 namespace {
 
-// Element i's message range; false (and nothing read) where it is not inside [0, msg_len)  (as kernels_eddsa.hip)
-FEC_DEV bool msg_range(const u64* __restrict__ off, u64 msg_len, size_t i, u64& lo, u64& len) {
-  const u64 a = off[i], b = off[i + 1];
-  const bool ok = a <= b && b <= msg_len;
-  lo = ok ? a : 0;
-  len = ok ? b - a : 0;
-  return ok;
-}
-__global__ __launch_bounds__(TPB) void k_sha256(const unsigned char* __restrict__ msgs, const u64* __restrict__ off, u64 msg_len,
-                                                u32* __restrict__ out, unsigned char* __restrict__ status, size_t n) {
+__global__ __launch_bounds__(TPB) void k_sha256(Messages msgs, u32* __restrict__ out, unsigned char* __restrict__ status, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  u64 lo, len;
-  const bool ok = msg_range(off, msg_len, i, lo, len);
+  u64 len;
+  const unsigned char* m;
+  const bool ok = message_at(msgs, i, m, len);
   u32 o[8];
   if (ok) {
     const u32 none[1] = {0};
-    sha256::digest_words(sha256::hash_prefixed<1>(none, 0, len ? msgs + lo : nullptr, len), o);
+    sha256::digest_words(sha256::hash_prefixed<1>(none, 0, m, len), o);
   } else {
     FEC_UNROLL for (int j = 0; j < 8; ++j) o[j] = 0;
   }
@@ -95,11 +88,12 @@ __global__ __launch_bounds__(TPB) void k_bad_range_status(const unsigned char* _
 __global__ __launch_bounds__(TPB) void k_bip340_pre(Bip340Io io, Bip340Work w, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  u64 lo = 0, len = 0;
-  unsigned char f = msg_range(io.off, io.msg_len, i, lo, len) ? 0 : bip340::F_BAD_RANGE;
+  u64 len;
+  const unsigned char* m;
+  unsigned char f = message_at(io.msg, i, m, len) ? 0 : bip340::F_BAD_RANGE;
   u32 kw[8];
   load_w8(kw, io.keys + i * 8);
-  const fe d = bip340::pre_step(f, kw, len ? io.msgs + lo : nullptr, len);
+  const fe d = bip340::pre_step(f, kw, m, len);
   store_fe16(w.d + i * 8, d);
   w.flags[i] = f;
 }
@@ -109,11 +103,12 @@ __global__ __launch_bounds__(TPB) void k_bip340_mid(Bip340Io io, Bip340Work w, s
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   unsigned char f = w.flags[i];
-  u64 lo = 0, len = 0;
-  (void)msg_range(io.off, io.msg_len, i, lo, len);
+  u64 len;
+  const unsigned char* m;
+  (void)message_at(io.msg, i, m, len);
   fe d, px;
   d = load_fe16(w.d + i * 8);
-  const fe k = bip340::mid_step(f, load_pt16<secp::pt>(w.p + i * 24), d, px, len ? io.msgs + lo : nullptr, len);
+  const fe k = bip340::mid_step(f, load_pt16<secp::pt>(w.p + i * 24), d, px, m, len);
   store_fe16(w.d + i * 8, d);
   store_fe16(w.k + i * 8, k);
   store_fe16(w.px + i * 8, px);
@@ -125,14 +120,15 @@ __global__ __launch_bounds__(TPB) void k_bip340_finish(Bip340Io io, Bip340Work w
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   unsigned char f = w.flags[i];
-  u64 lo = 0, len = 0;
-  (void)msg_range(io.off, io.msg_len, i, lo, len);
+  u64 len;
+  const unsigned char* m;
+  (void)message_at(io.msg, i, m, len);
   fe k, d, px;
   k = load_fe16(w.k + i * 8);
   d = load_fe16(w.d + i * 8);
   px = load_fe16(w.px + i * 8);
   u32 o[16];
-  bip340::finish_step(f, load_pt16<secp::pt>(w.r + i * 24), k, d, px, len ? io.msgs + lo : nullptr, len, o);
+  bip340::finish_step(f, load_pt16<secp::pt>(w.r + i * 24), k, d, px, m, len, o);
   store_w8(io.sig + i * 16, o);
   store_w8(io.sig + i * 16 + 8, o + 8);
   io.status[i] = bip340::status_of(f);
@@ -154,15 +150,16 @@ template <class E>
 __global__ __launch_bounds__(TPB) void k_schnorr_challenge(SchnorrChallengeIo io, size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  u64 lo, len;
-  const bool ok = msg_range(io.off, io.msg_len, i, lo, len);
+  u64 len;
+  const unsigned char* m;
+  const bool ok = message_at(io.msg, i, m, len);
   fe e = fe_zero();
   if (ok) {
     const bool rinf = io.r_inf != nullptr && io.r_inf[i] != 0, pinf = io.pk_inf != nullptr && io.pk_inf[i] != 0;
     u32 pre[17];
     unsigned char leg;
     e = schnorr::schnorr_challenge<E>(load_fe16(io.r_xy + i * 16), load_fe16(io.r_xy + i * 16 + 8), rinf, load_fe16(io.pk_xy + i * 16),
-                                      load_fe16(io.pk_xy + i * 16 + 8), pinf, len ? io.msgs + lo : nullptr, len, pre, leg);
+                                      load_fe16(io.pk_xy + i * 16 + 8), pinf, m, len, pre, leg);
   }
   store_fe16(io.e + i * 8, e);
   if (io.status) io.status[i] = ok ? 0 : 4;
@@ -179,9 +176,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(3))) void k
                                                              size_t n) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  u64 lo, len;
-  const bool ok = msg_range(io.off, io.msg_len, i, lo, len);
-  const unsigned char* msg = len ? io.msgs + lo : nullptr;
+  u64 len;
+  const unsigned char* msg;
+  const bool ok = message_at(io.msg, i, msg, len);
   const bool test = ok && schnorr::is_test_message(msg, len);
   typedef typename E::pt pt;
   schnorr::signature o = schnorr::sign_finish<E>(load_pt16<pt>(pts + i * 24), load_pt16<pt>(pts + (n + i) * 24), load_pt16<pt>(gen), test,
@@ -227,9 +224,8 @@ void schnorr_sign_finish_launch(int curve, const SchnorrSignIo& io, const u32* s
   else hipLaunchKernelGGL((k_schnorr_sign_finish<schnorr::CP256>), g, b, 0, s, io, scal, pts, decided, gen, n);
 }
 
-void sha256_launch(const unsigned char* msgs, const u64* off, u64 msg_len, u32* out, unsigned char* status, size_t n,
-                   hipStream_t s) {
-  hipLaunchKernelGGL(k_sha256, dim3(grid(n)), dim3(TPB), 0, s, msgs, off, msg_len, out, status, n);
+void sha256_launch(const Messages& msgs, u32* out, unsigned char* status, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_sha256, dim3(grid(n)), dim3(TPB), 0, s, msgs, out, status, n);
 }
 void bad_range_status_launch(const unsigned char* bad, unsigned char* status, size_t n, hipStream_t s, u32* sig) {
   hipLaunchKernelGGL(k_bad_range_status, dim3(grid(n)), dim3(TPB), 0, s, bad, status, sig, n);

@@ -1,0 +1,311 @@
+"""
+GPU tests of what the from-the-message entry points share on the host side (fecgpu.hip: with_messages, dev_enter,
+dev_messages):
+
+  * an all-empty batch -- n = 5, every message empty, msg_len = 0 and a NULL message pointer, the `bytes == 0` leg of the
+    staging -- through one host entry point of every caller of the engine, against the models the per-family tests use
+    (hashlib for the two hashes);
+  * the status every entry point, host and *_dev, returns for bad arguments: a table of cases, each rejected before
+    anything is launched (or the valid n = 0 call; or Ed25519 given to the challenge, which supports it, on zeroed points),
+    whose expected codes (tests/golden/msg_arg_codes.json) were recorded
+    from the library as it was before the seven host scaffolds and the *_dev prologues were merged.  Every buffer of a
+    case is real and large enough for n = 8, apart from the one pointer the case spoils.
+"""
+import hashlib
+import json
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "msg_arg_codes.json")
+N = 8
+DST = b"forge-ec msg args dst"
+
+
+# ---- the all-empty batch ----
+
+@pytest.fixture
+def null_msgs(monkeypatch):
+    """forge_ec_amd.Context hands an all-empty batch a one-byte dummy buffer; under this fixture it hands it NULL."""
+    import forge_ec_amd as F
+    real = F.Context._messages
+
+    def messages(msgs):
+        _, off, total = real(msgs)
+        assert total == 0 and not off.any()
+        return None, off, 0
+    monkeypatch.setattr(F.Context, "_messages", staticmethod(messages))
+
+
+EMPTY = [b""] * 5
+
+
+def _scalars(seed):
+    return np.random.default_rng(seed).integers(1, 1 << 62, size=(5, 4), dtype=np.uint64)
+
+
+def _bytes(seed, width):
+    return np.random.default_rng(seed).integers(0, 256, size=(5, width), dtype=np.uint8)
+
+
+def test_empty_batch_hashes(gpu_ctx, null_msgs):
+    assert gpu_ctx.sha256(EMPTY).tobytes() == hashlib.sha256(b"").digest() * 5
+    assert gpu_ctx.sha512(EMPTY).tobytes() == hashlib.sha512(b"").digest() * 5
+
+
+def test_empty_batch_ed25519_sign(gpu_ctx, null_msgs):
+    import eddsa_sign_ref as R
+    keys = _bytes(1, 32)
+    keys[2, 0] = 0x9d                                   # an empty message with this key byte: the reference's fixed signature
+    sig, st = gpu_ctx.ed25519_sign(keys, EMPTY)
+    want = R.sign_batch(keys, EMPTY, R.CBackend())
+    assert [s.tobytes() for s in sig] == [w[0] for w in want] and st.tolist() == [w[1] for w in want]
+
+
+def test_empty_batch_bip340_sign(gpu_ctx, null_msgs):
+    import bip340_sign_ref as R
+    keys = _bytes(2, 32)
+    keys[:, 31] &= 0x7F                                 # below N: computed signatures
+    sig, st = gpu_ctx.bip340_sign(keys, EMPTY)
+    want = R.sign_batch(keys, EMPTY, R.CBackend(4))
+    assert [s.tobytes() for s in sig] == [bytes(w[0]) for w in want] and st.tolist() == [w[1] for w in want]
+
+
+def test_empty_batch_ed25519_verify(gpu_ctx, null_msgs):
+    import eddsa_verify_ref as R
+    pk, sigs = _bytes(3, 32), _bytes(4, 64)
+    want = R.verify_batch(pk, EMPTY, sigs, R.CBackend())
+    assert want == [1] * 5                              # the reference accepts an empty message before it looks at anything
+    assert gpu_ctx.ed25519_verify(pk, EMPTY, sigs).tolist() == want
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+def test_empty_batch_ecdsa_verify_msg(gpu_ctx, null_msgs, oracle, curve):
+    from test_gpu_ecdsa_verify_msg import _digests, _verify
+    import rfc6979_ref as R
+    sk = _scalars(5 + curve)
+    r, s, _, _ = R.sign_msg(oracle, curve, sk, EMPTY)   # the reference's own signatures, and one spoiled
+    s[3, 0] ^= np.uint64(1)
+    pk, inf = oracle.batch_to_affine(curve, oracle.batch_mul_fixed(curve, sk, oracle.generator(curve)))
+    pk, inf = np.ascontiguousarray(pk), np.ascontiguousarray(inf).astype(np.uint8)
+    want = _verify(oracle, curve, _digests(EMPTY), r, s, pk, inf)
+    assert np.array_equal(gpu_ctx.ecdsa_verify_msg(curve, EMPTY, r, s, pk, inf), want)
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+def test_empty_batch_rfc6979_k(gpu_ctx, null_msgs, curve):
+    import rfc6979_ref as R
+    sk = _scalars(7 + curve)
+    k, st = gpu_ctx.rfc6979_k(curve, sk, EMPTY)
+    assert not st.any() and np.array_equal(k, R.nonces(curve, sk, EMPTY)[0])
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+def test_empty_batch_schnorr_sign_msg(gpu_ctx, null_msgs, curve):
+    import schnorr_sign_ref as S
+    sk = _scalars(9 + curve)
+    want = S.sign_many(curve, sk, EMPTY)
+    r_xy, r_inf, s, sig_bytes, st = gpu_ctx.schnorr_sign_msg(curve, sk, EMPTY)
+    assert np.array_equal(st, want["status"]) and np.array_equal(r_xy, want["r_xy"]) and np.array_equal(r_inf, want["r_inf"])
+    assert np.array_equal(s, want["s"]) and np.array_equal(sig_bytes, want["sig_bytes"])
+
+
+@pytest.mark.parametrize("curve", [0, 1, 2])
+def test_empty_batch_schnorr_challenge(gpu_ctx, null_msgs, curve):
+    from test_gpu_schnorr_challenge import _points, _want
+    r_xy, r_inf = _points(gpu_ctx, curve, 5, 60 + curve)
+    pk_xy, pk_inf = _points(gpu_ctx, curve, 5, 70 + curve)
+    assert np.array_equal(gpu_ctx.schnorr_challenge(curve, r_xy, r_inf, pk_xy, pk_inf, EMPTY), _want(curve, r_xy, r_inf, pk_xy, pk_inf, EMPTY))
+
+
+def test_empty_batch_expand_message_xmd(gpu_ctx, null_msgs):
+    import h2c_ref as H
+    assert gpu_ctx.expand_message_xmd(EMPTY, DST, 48).tobytes() == bytes(H.expand_message_xmd(b"", DST, 48)) * 5
+
+
+# ---- the return-code table ----
+# An entry point is a list of arguments: "ctx", "curve", the message triple "msgs" / "off" / "len", "dst" / "dst_len",
+# ("val", v) for a plain integer, "n", "stream" (NULL), and arrays (name, bytes per element, required).  A *_dev form
+# wants every array of 32 bytes per element or more on a 16-byte boundary.
+M = ["msgs", "off", "len"]
+D = ["dst", "dst_len"]
+ORDER_2_255 = ("order", [0, 0, 0, 1 << 63])
+
+
+def _arr(name, stride, required=True):
+    return (name, stride, required)
+
+
+HOST = {
+    "fec_sha512": ["ctx"] + M + [_arr("digests", 64), "n"],
+    "fec_sha256": ["ctx"] + M + [_arr("digests", 32), "n"],
+    "fec_ed25519_sign": ["ctx", _arr("keys", 32)] + M + [_arr("sig", 64), _arr("status", 1), "n"],
+    "fec_ed25519_derive_public_key": ["ctx", _arr("keys", 32), _arr("pk", 32), _arr("status", 1), "n"],
+    "fec_eddsa_sign_ed25519": ["ctx", _arr("sk", 32)] + M + [_arr("r_xy", 64), _arr("r_inf", 1), _arr("s", 32), _arr("status", 1), "n"],
+    "fec_ed25519_verify": ["ctx", _arr("pk", 32)] + M + [_arr("sigs", 64), _arr("status", 1), "n"],
+    "fec_eddsa_verify_ed25519_msg": ["ctx", _arr("pk_xy", 64), _arr("pk_inf", 1, False)] + M +
+                                    [_arr("r_xy", 64), _arr("r_inf", 1, False), _arr("s", 32), _arr("status", 1), "n"],
+    "fec_ecdsa_verify_msg": ["ctx", "curve"] + M + [_arr("r", 32), _arr("s", 32), _arr("pk_xy", 64), _arr("pk_inf", 1, False), _arr("status", 1), "n"],
+    "fec_bip340_sign": ["ctx", _arr("keys", 32)] + M + [_arr("sigs", 64), _arr("status", 1), "n"],
+    "fec_ecdsa_sign_msg": ["ctx", "curve", _arr("sk", 32)] + M + [_arr("sig", 64), _arr("status", 1), "n"],
+    "fec_rfc6979_k": ["ctx", "curve", _arr("sk", 32)] + M + [_arr("k", 32), _arr("status", 1), "n"],
+    "fec_debug_rfc6979_k": ["ctx", "curve", ORDER_2_255, _arr("sk", 32)] + M + [_arr("k", 32), _arr("status", 1), "n"],
+    "fec_schnorr_challenge": ["ctx", "curve", _arr("r_xy", 64), _arr("r_inf", 1, False), _arr("pk_xy", 64), _arr("pk_inf", 1, False)] + M +
+                             [_arr("e", 32), "n"],
+    "fec_schnorr_sign_msg": ["ctx", "curve", _arr("sk", 32)] + M +
+                            [_arr("r_xy", 64), _arr("r_inf", 1), _arr("s", 32), _arr("sig_bytes", 64, False), _arr("status", 1), "n"],
+    "fec_expand_message_xmd": ["ctx"] + M + D + [("val", 48), _arr("out", 48), "n"],
+    "fec_hash_to_field": ["ctx", "curve"] + M + D + [("val", 2), _arr("u", 64), "n"],
+    "fec_hash_to_curve": ["ctx", "curve", ("val", 0), ("val", 0)] + M + D + [_arr("out", 96), _arr("cand", 128, False), _arr("legs", 2, False), "n"],
+    "fec_curve_hash_to_curve": ["ctx", "curve"] + M + D + [_arr("xy", 64), _arr("inf", 1), "n"],
+}
+ST, ST_OPT = _arr("status", 1), _arr("status", 1, False)
+DEV = {
+    "fec_sha512_dev": HOST["fec_sha512"][:-1] + [ST_OPT, "n", "stream"],
+    "fec_sha256_dev": HOST["fec_sha256"][:-1] + [ST_OPT, "n", "stream"],
+    "fec_schnorr_challenge_dev": HOST["fec_schnorr_challenge"][:-1] + [ST, "n", "stream"],
+    "fec_expand_message_xmd_dev": HOST["fec_expand_message_xmd"][:-1] + [ST_OPT, "n", "stream"],
+    "fec_hash_to_field_dev": HOST["fec_hash_to_field"][:-1] + [ST_OPT, "n", "stream"],
+    "fec_hash_to_curve_dev": HOST["fec_hash_to_curve"][:-1] + [ST_OPT, "n", "stream"],
+    "fec_curve_hash_to_curve_dev": HOST["fec_curve_hash_to_curve"][:-1] + [ST_OPT, "n", "stream"],
+}
+for _name in ("fec_ed25519_sign", "fec_ed25519_derive_public_key", "fec_eddsa_sign_ed25519", "fec_ed25519_verify", "fec_eddsa_verify_ed25519_msg",
+              "fec_ecdsa_verify_msg", "fec_bip340_sign", "fec_ecdsa_sign_msg", "fec_rfc6979_k", "fec_schnorr_sign_msg"):
+    DEV[_name + "_dev"] = HOST[_name] + ["stream"]
+
+
+class _Buffers:
+    """One real buffer per argument, host and device: arrays of N elements (zeros) with 16 bytes to spare, messages of 5 bytes."""
+
+    def __init__(self):
+        import torch
+        self.torch = torch
+        self.keep, self.cache = [], {}
+        self.good = np.arange(0, 5 * N + 1, 5, dtype=np.uint64)
+        self.dst = np.frombuffer(DST, dtype=np.uint8).copy()
+
+    def host(self, a):
+        a = np.ascontiguousarray(a)
+        self.keep.append(a)
+        return a.ctypes.data
+
+    def dev(self, a):
+        t = self.torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(self.torch.device("cuda:0"))
+        self.keep.append(t)
+        return t.data_ptr()
+
+    def zeros(self, nbytes, dev):
+        """(cached: no case changes what a buffer holds)"""
+        if (nbytes, dev) not in self.cache:
+            a = np.zeros(nbytes, dtype=np.uint8)
+            self.cache[(nbytes, dev)] = self.dev(a) if dev else self.host(a)
+        return self.cache[(nbytes, dev)]
+
+    def put(self, a, dev):
+        return self.dev(a) if dev else self.host(a)
+
+
+def _call_args(spec, dev, buf, ctx, spoil):
+    """The argument tuple of one case.  `spoil` maps an argument name to what replaces it: None, "+4" / "+8" (the pointer
+    moved), an offsets array, or a value ("ctx", "curve", "len", "n")."""
+    out = []
+    for arg in spec:
+        name = arg if isinstance(arg, str) else arg[0]
+        if name == "ctx":
+            v = ctx
+        elif name == "curve":
+            v = 0
+        elif name == "msgs":
+            v = buf.zeros(5 * N + 16, dev)
+        elif name == "off":
+            o = spoil.get("off")
+            v = buf.put(np.concatenate([o if isinstance(o, np.ndarray) else buf.good, np.zeros(2, dtype=np.uint64)]), dev)
+        elif name == "len":
+            v = 5 * N
+        elif name == "dst":
+            v = buf.host(buf.dst)
+        elif name == "dst_len":
+            v = len(DST)
+        elif name == "val":
+            v = arg[1]
+        elif name == "order":
+            v = buf.host(np.array(arg[1], dtype=np.uint64))
+        elif name == "n":
+            v = N
+        elif name == "stream":
+            v = None
+        else:
+            v = buf.zeros(arg[1] * N + 16, dev)
+        if name in spoil and not isinstance(spoil[name], np.ndarray):
+            s = spoil[name]
+            v = v + int(s) if isinstance(s, str) else s
+        out.append(v)
+    return tuple(out)
+
+
+def _pointers(spec):
+    return [a if isinstance(a, str) else a[0] for a in spec if a in ("msgs", "off", "dst") or (isinstance(a, tuple) and len(a) == 3)]
+
+
+def _spoils(spec, dev):
+    """(case name, spoil) for one entry point."""
+    names = [a if isinstance(a, str) else a[0] for a in spec]
+    arrays = [a for a in spec if isinstance(a, tuple) and len(a) == 3]
+    required = [a[0] for a in arrays if a[2]] + [p for p in ("msgs", "off", "dst") if p in names]
+    every_null = {p: None for p in _pointers(spec) if p != "dst"}
+    every_null.update({"n": 0, "len": 0})
+    cases = [("ctx=null", {"ctx": None}), ("n=0,every array null", every_null)]
+    cases += [(p + "=null", {p: None}) for p in required]
+    if "off" in names and not dev:
+        bad, nz = np.arange(0, 5 * N + 1, 5, dtype=np.uint64), np.arange(0, 5 * N + 1, 5, dtype=np.uint64)
+        bad[3], bad[4] = 20, 10
+        nz[0] = 1
+        cases += [("off not monotonic", {"off": bad}), ("off[0]!=0", {"off": nz}), ("off[n]!=msg_len", {"len": 5 * N + 1})]
+    aligned = [a[0] for a in arrays if a[1] >= 32]
+    if dev:
+        cases += [("ctx=multi", {"ctx": "multi"})]
+        cases += [("off+4", {"off": "+4"})] if "off" in names else []
+        cases += [(p + "+8", {p: "+8"}) for p in aligned]
+    if "curve" in names:
+        cases += [("curve=2", {"curve": 2}), ("curve=7", {"curve": 7})]
+        # the curve check against the pointer checks: which of the two a call that fails both reports
+        cases += [("curve=2," + required[0] + "=null", {"curve": 2, required[0]: None})]
+        cases += [("curve=2,off=null", {"curve": 2, "off": None})]
+        if dev:
+            cases += [("curve=2,off+4", {"curve": 2, "off": "+4"}), ("curve=2," + aligned[0] + "+8", {"curve": 2, aligned[0]: "+8"})]
+    return cases
+
+
+def run_table(lib, ctx, multi):
+    """{case id: status} of every case, on the library `lib` (ctypes), a ctx handle and a multi-device ctx handle."""
+    buf = _Buffers()
+    out = {}
+    for table, dev in ((HOST, False), (DEV, True)):
+        for fn, spec in table.items():
+            for case, spoil in _spoils(spec, dev):
+                spoil = dict(spoil)
+                if spoil.get("ctx") == "multi":
+                    spoil["ctx"] = multi
+                out["%s: %s" % (fn, case)] = int(getattr(lib, fn)(*_call_args(spec, dev, buf, ctx, spoil)))
+    buf.torch.cuda.synchronize()
+    return out
+
+
+def test_return_codes_are_what_they_were(gpu_ctx):
+    import forge_ec_amd as F
+    from forge_ec_amd import _lib as L
+    want = json.load(open(GOLDEN))
+    with F.Context(devices=[0, 0]) as multi:
+        got = run_table(L.lib(), gpu_ctx._h, multi._h)
+    assert sorted(got) == sorted(want)
+    assert {k: v for k, v in got.items() if want[k] != v} == {}
+    # no case but the curve-2 challenge (a supported curve there) got as far as a launch with elements in it
+    assert sorted(k for k, v in want.items() if v == 0) == sorted(
+        ["%s: %s" % (fn, c) for fn in ("fec_ed25519_derive_public_key", "fec_ed25519_derive_public_key_dev") for c in ("n=0,every array null",)] +
+        ["%s: n=0,every array null" % fn for fn in DEV if fn != "fec_ed25519_derive_public_key_dev"] +
+        ["fec_schnorr_challenge: curve=2", "fec_schnorr_challenge_dev: curve=2"])
+    gpu_ctx.check()

@@ -76,6 +76,28 @@ def test_mixed_lengths_host_and_dev_unaligned(gpu_ctx, n):
         assert np.array_equal(d_k.cpu().numpy().view(np.uint64).reshape(n, 4), want), shift
 
 
+@pytest.mark.parametrize("curve", [0, 1])
+def test_chunked_and_multi_device(gpu_ctx, curve):
+    """Chunks of 64 over n = 131: elements 63 and 64 are empty, so one chunk's rebased offsets end and the next one's
+    start on an empty range; the other lengths cycle through the padding edges of SHA-256."""
+    import forge_ec_amd as F
+    n = 131
+    rng = np.random.default_rng(300 + curve)
+    sk = rng.integers(0, 1 << 64, size=(n, 4), dtype=np.uint64)
+    msgs = [rng.integers(0, 256, size=0 if i in (63, 64) else (0, 1, 55, 56, 64, 119)[i % 6], dtype=np.uint8).tobytes() for i in range(n)]
+    want, _ = R.nonces(curve, sk, msgs)
+    gpu_ctx.set_chunk(64)
+    try:
+        k, st = gpu_ctx.rfc6979_k(curve, sk, msgs)
+    finally:
+        gpu_ctx.set_chunk(1 << 18)
+    assert not st.any() and np.array_equal(k, want)
+    with F.Context(devices=[0, 0]) as multi:
+        multi.set_chunk(64)
+        k, st = multi.rfc6979_k(curve, sk, msgs)
+    assert not st.any() and np.array_equal(k, want)
+
+
 def test_dev_form_bad_range_planted(gpu_ctx):
     import torch
     n, bad = 70, 37

@@ -82,6 +82,27 @@ def test_random_points_flags_and_lengths(gpu_ctx, curve):
     assert np.array_equal(d_e.cpu().numpy().view(np.uint64).reshape(n, 4), _want(curve, r_xy, zero, pk_xy, pk_inf, msgs))
 
 
+@pytest.mark.parametrize("curve", [0, 1, 2])
+def test_chunked_and_multi_device(gpu_ctx, curve):
+    """Chunks of 64 over n = 131: elements 63 and 64 are empty, so one chunk's rebased offsets end and the next one's
+    start on an empty range; the other lengths cycle through the padding edges of SHA-256."""
+    import forge_ec_amd as F
+    n = 131
+    r_xy, r_inf = _points(gpu_ctx, curve, n, 80 + curve)
+    pk_xy, pk_inf = _points(gpu_ctx, curve, n, 90 + curve)
+    rng = np.random.default_rng(95 + curve)
+    msgs = [rng.integers(0, 256, size=0 if i in (63, 64) else (0, 1, 55, 56, 64, 119)[i % 6], dtype=np.uint8).tobytes() for i in range(n)]
+    want = _want(curve, r_xy, r_inf, pk_xy, pk_inf, msgs)
+    gpu_ctx.set_chunk(64)
+    try:
+        assert np.array_equal(gpu_ctx.schnorr_challenge(curve, r_xy, r_inf, pk_xy, pk_inf, msgs), want)
+    finally:
+        gpu_ctx.set_chunk(1 << 18)
+    with F.Context(devices=[0, 0]) as multi:
+        multi.set_chunk(64)
+        assert np.array_equal(multi.schnorr_challenge(curve, r_xy, r_inf, pk_xy, pk_inf, msgs), want)
+
+
 def test_dev_form_bad_range_planted(gpu_ctx):
     import torch
     n, bad, curve = 70, 37, 1
