@@ -8,7 +8,8 @@
  *    produces (fec_batch_mul_fixed), then Curve::to_affine and PointAffine::to_bytes on the GPU;
  *    then round 4's calls: the prefix-table policy, schnorr::batch_verify::<Ed25519>, the multi-GPU calls' refusal;
  * 2. canonical mode: the standard secp256k1 public keys of the same scalars (fec_canon_mul_base) --
- *    3*G.x is the BIP-340 test-vector-0 public key.
+ *    3*G.x is the BIP-340 test-vector-0 public key; that vector's signature is then verified from the message,
+ *    the 64 signature bytes and the 32 key bytes (fec_canon_bip340_verify_msg: hash and decoding on the GPU).
  * Prints one line per step and returns 0 when everything behaved.
  */
 #include <stdint.h>
@@ -58,6 +59,23 @@ int main(void) {
          (unsigned long long)pub[2][1], (unsigned long long)pub[2][0]);
   const uint64_t want[4] = {0x8601F113BCE036F9ULL, 0xB531C845836F99B0ULL, 0x49344F85F89D5229ULL, 0xF9308A019258C310ULL};
   int ok = memcmp(pub[2], want, sizeof want) == 0 && st[2] == FEC_CANON_FINITE;
+
+  /* from the message: BIP-340 test vector 0 (message 0^32) and the same signature over another message */
+  static const uint8_t sig0[64] = {
+      0xE9, 0x07, 0x83, 0x1F, 0x80, 0x84, 0x8D, 0x10, 0x69, 0xA5, 0x37, 0x1B, 0x40, 0x24, 0x10, 0x36, 0x4B, 0xDF, 0x1C, 0x5F, 0x83, 0x07,
+      0xB0, 0x08, 0x4C, 0x55, 0xF1, 0xCE, 0x2D, 0xCA, 0x82, 0x15, 0x25, 0xF6, 0x6A, 0x4A, 0x85, 0xEA, 0x8B, 0x71, 0xE4, 0x82, 0xA7, 0x4F,
+      0x38, 0x2D, 0x2C, 0xE5, 0xEB, 0xEE, 0xE8, 0xFD, 0xB2, 0x17, 0x2F, 0x47, 0x7D, 0xF4, 0x90, 0x0D, 0x31, 0x05, 0x36, 0xC0};
+  uint8_t msgs[32 + 5], sigs[2][64], pks[2][32], valid[2] = {9, 9};
+  const uint64_t msg_off[3] = {0, 32, 37};
+  memset(msgs, 0, 32);
+  memcpy(msgs + 32, "hello", 5);
+  for (int i = 0; i < 2; ++i) {
+    memcpy(sigs[i], sig0, 64);
+    for (int b = 0; b < 32; ++b) pks[i][b] = (uint8_t)(pub[2][3 - b / 8] >> (56 - 8 * (b % 8)));   /* 3*G.x, big-endian */
+  }
+  rc = fec_canon_bip340_verify_msg(ctx, msgs, msg_off, sizeof msgs, &sigs[0][0], &pks[0][0], valid, 2);
+  printf("canon   bip340_verify_msg(vector 0) rc=%d valid=%d, over another message valid=%d\n", rc, valid[0], valid[1]);
+  ok = ok && rc == FEC_OK && valid[0] == 1 && valid[1] == 0;
 
   /* ---- round 4's additions, as an FFI would call them ---- */
   /* the prefix-table policy: how much of the free memory a table may take, a table built at a point of the caller's

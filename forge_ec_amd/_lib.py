@@ -31,6 +31,8 @@ CANON_ABI_SYMBOLS = [
     "fec_canon_double_mul", "fec_canon_double_mul_dev", "fec_canon_ecdsa_verify", "fec_canon_ecdsa_verify_dev",
     "fec_canon_bip340_verify", "fec_canon_bip340_verify_dev", "fec_canon_eddsa_verify", "fec_canon_eddsa_verify_dev",
     "fec_canon_scalar_op",
+    "fec_canon_ecdsa_verify_msg", "fec_canon_ecdsa_verify_msg_dev", "fec_canon_bip340_verify_msg", "fec_canon_bip340_verify_msg_dev",
+    "fec_canon_ed25519_verify_msg", "fec_canon_ed25519_verify_msg_dev", "fec_canon_decompress", "fec_canon_decompress_dev",
 ]
 F_INV = 5
 
@@ -265,6 +267,13 @@ def lib():
     for name in ("fec_canon_bip340_verify", "fec_canon_eddsa_verify"):
         getattr(L, name).argtypes = [vp, vp, vp, vp, vp, vp, sz]
         getattr(L, name + "_dev").argtypes = [vp, vp, vp, vp, vp, vp, sz, vp]
+    L.fec_canon_ecdsa_verify_msg.argtypes = [vp, ci, vp, vp, sz, vp, vp, sz, vp, sz]
+    L.fec_canon_ecdsa_verify_msg_dev.argtypes = [vp, ci, vp, vp, sz, vp, vp, sz, vp, sz, vp]
+    for name in ("fec_canon_bip340_verify_msg", "fec_canon_ed25519_verify_msg"):
+        getattr(L, name).argtypes = [vp, vp, vp, sz, vp, vp, vp, sz]
+        getattr(L, name + "_dev").argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp]
+    L.fec_canon_decompress.argtypes = [vp, ci, vp, sz, vp, vp, sz]
+    L.fec_canon_decompress_dev.argtypes = [vp, ci, vp, sz, vp, vp, sz, vp]
     for n in CANON_ABI_SYMBOLS:
         getattr(L, n).restype = ci
     _lib = L

@@ -5,6 +5,8 @@ The real secp256k1 / P-256 / Ed25519 groups (standard public keys / ECDH points)
 other libraries agree with; forge-ec's own arithmetic does not produce them.
 Arrays are numpy uint64 little-endian limbs of the plain integers: scalars (n,4); affine points
 (n,8) = x then y; status (n,) uint8: 0 finite, 1 infinity (xy = 0), 2 input point rejected.
+The *_verify_msg calls take what arrives on a wire instead: a list of message byte strings, signatures (n,64) uint8
+and encoded keys (n,32 / 33 / 65) uint8 (or bytes objects); the hash and the decoding run on the GPU.
 GPU only, like the rest of the package.
 """
 import numpy as np
@@ -13,6 +15,30 @@ from . import _lib as L
 from .curves import Context, _check, _ptr, _u64
 
 FINITE, INFINITY, BAD_POINT = 0, 1, 2
+
+
+def _bytes_rows(a, width, what):
+    """bytes, a list of byte strings or an array -> contiguous (n, width) uint8."""
+    if isinstance(a, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(bytes(a), dtype=np.uint8)
+    elif isinstance(a, (list, tuple)) and a and isinstance(a[0], (bytes, bytearray)):
+        a = np.frombuffer(b"".join(a), dtype=np.uint8)
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.uint8))
+    if a.size % width:
+        raise ValueError("%s: not a whole number of %d-byte records" % (what, width))
+    return a.reshape(-1, width)
+
+
+def _verify_msg(lib_fn, h, msgs, sigs, pks, pk_len, what, lead=()):
+    sg, pk = _bytes_rows(sigs, 64, "sigs"), _bytes_rows(pks, pk_len, "pks")
+    buf, off, total = Context._messages(msgs)
+    n = sg.shape[0]
+    if not (pk.shape[0] == n and len(off) == n + 1):
+        raise ValueError("inputs differ in length")
+    out = np.zeros(n, dtype=np.uint8)
+    tail = (pk_len,) if lead else ()
+    _check(lib_fn(h, *lead, _ptr(buf), _ptr(off), total, _ptr(sg), _ptr(pk), *tail, _ptr(out), n), what)
+    return out
 
 
 class CanonCurve:
@@ -76,6 +102,29 @@ class CanonCurve:
     def ecdsa_verify_dev(self, d_z, d_r, d_s, d_pk_xy, d_result, n, stream=None):
         _check(self._lib.fec_canon_ecdsa_verify_dev(self._h, self.CURVE, d_z, d_r, d_s, d_pk_xy, d_result, n, stream),
                "fec_canon_ecdsa_verify_dev")
+
+    def ecdsa_verify_msg(self, msgs, sigs, pks, pk_len=33):
+        """ECDSA with SHA-256 from the message (secp256k1, P-256): msgs a list of n byte strings, sigs (n,64) r || s
+        big-endian, pks (n,pk_len) SEC 1 keys, pk_len 33 (compressed) or 65.  (n,) uint8, 1 = valid."""
+        return _verify_msg(self._lib.fec_canon_ecdsa_verify_msg, self._h, msgs, sigs, pks, pk_len,
+                           "fec_canon_ecdsa_verify_msg", lead=(self.CURVE,))
+
+    def ecdsa_verify_msg_dev(self, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, pk_len, d_result, n, stream=None):
+        _check(self._lib.fec_canon_ecdsa_verify_msg_dev(self._h, self.CURVE, d_msgs, d_msg_off, msg_len, d_sigs, d_pks,
+                                                        pk_len, d_result, n, stream), "fec_canon_ecdsa_verify_msg_dev")
+
+    def decompress(self, keys, pk_len=33):
+        """SEC 1 decoding (secp256k1, P-256): keys (n,pk_len) uint8 -> (xy (n,8), status (n,): 0, or 2 with zeros)."""
+        k = _bytes_rows(keys, pk_len, "keys")
+        n = k.shape[0]
+        xy = np.zeros((n, 8), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_decompress(self._h, self.CURVE, _ptr(k), pk_len, _ptr(xy), _ptr(st), n), "fec_canon_decompress")
+        return xy, st
+
+    def decompress_dev(self, d_in, pk_len, d_xy, d_status, n, stream=None):
+        _check(self._lib.fec_canon_decompress_dev(self._h, self.CURVE, d_in, pk_len, d_xy, d_status, n, stream),
+               "fec_canon_decompress_dev")
 
     def scalar_muladd(self, a, b, c):
         """a * b + c modulo the group order, element-wise, any 256-bit inputs."""
@@ -155,6 +204,15 @@ class CanonSecp256k1(CanonCurve):
         _check(self._lib.fec_canon_bip340_verify_dev(self._h, d_pk_x, d_r, d_s, d_e, d_result, n, stream),
                "fec_canon_bip340_verify_dev")
 
+    def bip340_verify_msg(self, msgs, sigs, pks):
+        """BIP-340 verification from the message: msgs a list of n byte strings (any length), sigs (n,64), pks (n,32)
+        x-only keys.  (n,) uint8, 1 = valid."""
+        return _verify_msg(self._lib.fec_canon_bip340_verify_msg, self._h, msgs, sigs, pks, 32, "fec_canon_bip340_verify_msg")
+
+    def bip340_verify_msg_dev(self, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, d_result, n, stream=None):
+        _check(self._lib.fec_canon_bip340_verify_msg_dev(self._h, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, d_result, n,
+                                                         stream), "fec_canon_bip340_verify_msg_dev")
+
 
 class CanonP256(CanonCurve):
     CURVE = L.P256
@@ -167,6 +225,15 @@ class CanonEd25519(CanonCurve):
     def eddsa_verify(self, a_enc, r_enc, s, h):
         """RFC 8032 verification; encodings as little-endian 256-bit integers, h = SHA-512(R||A||M) mod l."""
         return _four(self._lib.fec_canon_eddsa_verify, self._h, a_enc, r_enc, s, h, "fec_canon_eddsa_verify")
+
+    def ed25519_verify_msg(self, msgs, sigs, pks):
+        """RFC 8032 Ed25519 verification from the message: msgs a list of n byte strings, sigs (n,64) R || S, pks (n,32).
+        (n,) uint8, 1 = valid."""
+        return _verify_msg(self._lib.fec_canon_ed25519_verify_msg, self._h, msgs, sigs, pks, 32, "fec_canon_ed25519_verify_msg")
+
+    def ed25519_verify_msg_dev(self, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, d_result, n, stream=None):
+        _check(self._lib.fec_canon_ed25519_verify_msg_dev(self._h, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, d_result, n,
+                                                          stream), "fec_canon_ed25519_verify_msg_dev")
 
     def eddsa_sign_finish(self, h, a, r):
         """second half of RFC 8032 signing: S = h * a + r (mod l); the first half is R = mul_base(r).

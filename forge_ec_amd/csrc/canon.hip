@@ -5,6 +5,7 @@
 #include "../../include/fecgpu.h"
 #include "../../include/fecgpu_canon.h"
 #include "host_ctx.hpp"
+#include "host_messages.hpp"
 #include "canon_kernels.hpp"
 
 using namespace fecgpu;
@@ -141,11 +142,11 @@ int launch_canon_mul(fec_ctx* ctx, int curve, const u64* ds, const u64* dp, u64*
 
 // ECDSA verification: scalars -> u1*G + u2*Q -> compare.  d_work: u1, u2 (n*32 each), xy (n*64),
 // point status (n), range flags (n).
+inline size_t canon_ecdsa_work_bytes(size_t n) { return n * (32 + 32 + 64 + 1 + 1) + 64; }
 int launch_canon_ecdsa_verify(fec_ctx* ctx, int curve, const u64* dz, const u64* dr, const u64* ds, const u64* dpk,
                               unsigned char* dres, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  const size_t need = n * (32 + 32 + 64 + 1 + 1) + 64;
-  int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, need);
+  int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, canon_ecdsa_work_bytes(n));
   if (rc != FEC_OK) return rc;
   char* base = (char*)ctx->d_verify;
   u64* u1 = (u64*)base;
@@ -176,37 +177,122 @@ int launch_canon_ecdsa_verify(fec_ctx* ctx, int curve, const u64* dz, const u64*
 }
 
 // BIP-340 / EdDSA: prepare -> u1*G + u2*P -> final test.  Work area: P xy (n*64), expected R xy (n*64,
-// EdDSA only), u2 (n*32), result xy (n*64), point status (n), flags (n).
+// EdDSA only), u2 (n*32), result xy (n*64), point status (n), flags (n); the from-the-message forms add what their
+// prepare kernel parses out of the signature bytes -- s (n*32), r (n*32) -- and the message flags (n).
+struct SigWork {
+  u64 *pxy, *rxy, *u2, *xy;
+  unsigned char *pst, *ok;
+  u64 *s, *r;            // from the message only
+  unsigned char* flag;   // from the message only
+};
+int sig_work(fec_ctx* ctx, size_t n, bool from_msg, SigWork& w) {
+  const size_t after_hash = n * (64 + 64 + 32 + 64 + 1 + 1) + 64;
+  const size_t wire = (after_hash + 255) & ~(size_t)255;
+  const int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, from_msg ? wire + n * (32 + 32 + 1) : after_hash);
+  if (rc != FEC_OK) return rc;
+  char* base = (char*)ctx->d_verify;
+  w.pxy = (u64*)base;
+  w.rxy = (u64*)(base + n * 64);
+  w.u2 = (u64*)(base + n * 128);
+  w.xy = (u64*)(base + n * 160);
+  w.pst = (unsigned char*)(base + n * 224);
+  w.ok = w.pst + n;
+  w.s = (u64*)(base + wire);
+  w.r = (u64*)(base + wire + n * 32);
+  w.flag = (unsigned char*)(base + wire + n * 64);
+  return FEC_OK;
+}
+// Everything after the prepare step, which has filled w.pxy, w.u2, w.ok (and w.rxy for EdDSA): d_s = u1, d_r = the r the
+// BIP-340 finish compares with.  The after-the-hash and the from-the-message forms differ in their prepare kernel only.
+int launch_canon_sig_finish(fec_ctx* ctx, int curve, const SigWork& w, const u64* d_r, const u64* d_s, unsigned char* dres,
+                            size_t n, void* stream) {
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  dim3 g(grid_for(n)), b(TPB);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;   // the prepare kernel's launch
+  int rc = launch_canon_mul_base(ctx, curve, d_s, w.xy, w.pst, n, stream, false);   // u1 = s
+  if (rc == FEC_OK) rc = launch_canon_mul(ctx, curve, w.u2, w.pxy, w.xy, w.pst, n, stream, true);
+  if (rc != FEC_OK) return rc;
+  if (curve == FEC_SECP256K1)
+    hipLaunchKernelGGL(k_canon_bip340_finish, g, b, 0, s, (const u32*)w.xy, (const u32*)d_r, w.ok, w.pst, dres, n);
+  else
+    hipLaunchKernelGGL(k_ced_eddsa_finish, g, b, 0, s, (const u32*)w.xy, (const u32*)w.rxy, w.ok, w.pst, dres, n);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
 int launch_canon_sig_verify(fec_ctx* ctx, int curve, const u64* d_key, const u64* d_r, const u64* d_s, const u64* d_e,
                             unsigned char* dres, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  const size_t need = n * (64 + 64 + 32 + 64 + 1 + 1) + 64;
-  int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, need);
+  SigWork w;
+  const int rc = sig_work(ctx, n, false, w);
   if (rc != FEC_OK) return rc;
-  char* base = (char*)ctx->d_verify;
-  u64* pxy = (u64*)base;
-  u64* rxy = (u64*)(base + n * 64);
-  u64* u2 = (u64*)(base + n * 128);
-  u64* xy = (u64*)(base + n * 160);
-  unsigned char* pst = (unsigned char*)(base + n * 224);
-  unsigned char* ok = pst + n;
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   dim3 g(grid_for(n)), b(TPB);
   if (curve == FEC_SECP256K1)
     hipLaunchKernelGGL(k_canon_bip340_prepare, g, b, 0, s, (const u32*)d_key, (const u32*)d_r, (const u32*)d_s,
-                       (const u32*)d_e, (u32*)pxy, (u32*)u2, ok, n);
+                       (const u32*)d_e, (u32*)w.pxy, (u32*)w.u2, w.ok, n);
   else
     hipLaunchKernelGGL(k_ced_eddsa_prepare, g, b, 0, s, (const u32*)d_key, (const u32*)d_r, (const u32*)d_s,
-                       (const u32*)d_e, (u32*)pxy, (u32*)rxy, (u32*)u2, ok, n);
-  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
-  rc = launch_canon_mul_base(ctx, curve, d_s, xy, pst, n, stream, false);   // u1 = s
-  if (rc == FEC_OK) rc = launch_canon_mul(ctx, curve, u2, pxy, xy, pst, n, stream, true);
-  if (rc != FEC_OK) return rc;
-  if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL(k_canon_bip340_finish, g, b, 0, s, (const u32*)xy, (const u32*)d_r, ok, pst, dres, n);
-  else
-    hipLaunchKernelGGL(k_ced_eddsa_finish, g, b, 0, s, (const u32*)xy, (const u32*)rxy, ok, pst, dres, n);
+                       (const u32*)d_e, (u32*)w.pxy, (u32*)w.rxy, (u32*)w.u2, w.ok, n);
+  return launch_canon_sig_finish(ctx, curve, w, d_r, d_s, dres, n, stream);
+}
+int launch_canon_msg_fold(unsigned char* dres, const unsigned char* flag, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_canon_msg_fold, dim3(grid_for(n)), dim3(TPB), 0, s, dres, flag, n);
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+// ... from the message, the 64 signature bytes and the 32 key bytes (BIP-340: secp256k1; Ed25519)
+int launch_canon_sig_verify_msg(fec_ctx* ctx, int curve, const Messages& m, const uint8_t* d_sigs, const uint8_t* d_pks,
+                                unsigned char* dres, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  SigWork w;
+  int rc = sig_work(ctx, n, true, w);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // the work area is the ctx's
+  dim3 g(grid_for(n)), b(TPB);
+  if (curve == FEC_SECP256K1)
+    hipLaunchKernelGGL(k_canon_bip340_prepare_msg, g, b, 0, s, m, (const u32*)d_sigs, (const u32*)d_pks, (u32*)w.pxy,
+                       (u32*)w.u2, (u32*)w.r, (u32*)w.s, w.ok, w.flag, n);
+  else
+    hipLaunchKernelGGL(k_ced_eddsa_prepare_msg, g, b, 0, s, m, (const u32*)d_sigs, (const u32*)d_pks, (u32*)w.pxy,
+                       (u32*)w.rxy, (u32*)w.u2, (u32*)w.s, w.ok, w.flag, n);
+  rc = launch_canon_sig_finish(ctx, curve, w, w.r, w.s, dres, n, stream);
+  return rc != FEC_OK ? rc : launch_canon_msg_fold(dres, w.flag, n, s);
+}
+
+// ECDSA from the message: the prepare kernel writes z, r, s, the decoded key and the flags behind the area that
+// launch_canon_ecdsa_verify lays out for itself in d_verify (asked for here at the size of both, so it stays where it is).
+int launch_canon_ecdsa_verify_msg(fec_ctx* ctx, int curve, const Messages& m, const uint8_t* d_sigs, const uint8_t* d_pks,
+                                  size_t pk_len, unsigned char* dres, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  const size_t wire = (canon_ecdsa_work_bytes(n) + 255) & ~(size_t)255;
+  int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, wire + n * (32 + 32 + 32 + 64 + 1));
+  if (rc != FEC_OK) return rc;
+  char* base = (char*)ctx->d_verify + wire;
+  u64 *z = (u64*)base, *r = (u64*)(base + n * 32), *sv = (u64*)(base + n * 64), *pk = (u64*)(base + n * 96);
+  unsigned char* flag = (unsigned char*)(base + n * 160);
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // the work area is the ctx's
+  dim3 g(grid_for(n)), b(TPB);
+  const int unc = pk_len == 65;
+  if (curve == FEC_SECP256K1)
+    hipLaunchKernelGGL((k_canon_ecdsa_prepare_msg<canon::SecpParams>), g, b, 0, s, m, (const u32*)d_sigs, d_pks, unc,
+                       (u32*)z, (u32*)r, (u32*)sv, (u32*)pk, flag, n);
+  else
+    hipLaunchKernelGGL((k_canon_ecdsa_prepare_msg<canon::P256Params>), g, b, 0, s, m, (const u32*)d_sigs, d_pks, unc,
+                       (u32*)z, (u32*)r, (u32*)sv, (u32*)pk, flag, n);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  rc = launch_canon_ecdsa_verify(ctx, curve, z, r, sv, pk, dres, n, stream);
+  return rc != FEC_OK ? rc : launch_canon_msg_fold(dres, flag, n, s);
+}
+
+int launch_canon_decompress(fec_ctx* ctx, int curve, const uint8_t* d_in, size_t pk_len, u64* d_xy, unsigned char* d_st,
+                            size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_canon_decompress");
+  dim3 g(grid_for(n)), b(TPB);
+  const int unc = pk_len == 65;
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_decompress<canon::SecpParams>), g, b, 0, L.s, d_in, unc, (u32*)d_xy, d_st, n);
+  else hipLaunchKernelGGL((k_canon_decompress<canon::P256Params>), g, b, 0, L.s, d_in, unc, (u32*)d_xy, d_st, n);
+  return L.done();
 }
 
 }  // namespace
@@ -378,6 +464,89 @@ int fec_canon_field_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a,
     else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_field_op<cp256>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);
     else hipLaunchKernelGGL((k_canon_field_op<ced>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);
     return L.done();
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- verification from the message, the signature bytes and the encoded key ------------------------------------
+// Host forms: with_messages (host_messages.hpp) checks the layout, shards over a multi-device ctx, chunks and rebases
+// the offsets.  *_dev forms: one device, every lane checks its own message range (result 4).
+int fec_canon_ecdsa_verify_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                                   size_t msg_len, const uint8_t* d_sigs, const uint8_t* d_pks, size_t pk_len,
+                                   uint8_t* d_result, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_sigs || !d_pks || !d_result))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if ((pk_len != 33 && pk_len != 65) || !aligned16(d_sigs) || !aligned16(d_pks)) return FEC_E_ARG;
+  return launch_canon_ecdsa_verify_msg(ctx, curve, m, d_sigs, d_pks, pk_len, d_result, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ecdsa_verify_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                               const uint8_t* sigs, const uint8_t* pks, size_t pk_len, uint8_t* result, size_t n) try {
+  if (!ctx || (n && (!sigs || !pks || !result))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (pk_len != 33 && pk_len != 65) return FEC_E_ARG;
+  const HostArray a[] = {ragged(msg_off, 8), input(sigs, 64), input(pks, pk_len), output(result, 1)};
+  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_canon_ecdsa_verify_msg(c, curve, m, (const uint8_t*)d[1], (const uint8_t*)d[2], pk_len, (unsigned char*)d[3], cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_bip340_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                    const uint8_t* d_sigs, const uint8_t* d_pks, uint8_t* d_result, size_t n,
+                                    void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_sigs || !d_pks || !d_result))) return FEC_E_ARG;
+  if (!aligned16(d_sigs) || !aligned16(d_pks)) return FEC_E_ARG;
+  return launch_canon_sig_verify_msg(ctx, FEC_SECP256K1, m, d_sigs, d_pks, d_result, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_bip340_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                                const uint8_t* sigs, const uint8_t* pks, uint8_t* result, size_t n) try {
+  if (!ctx || (n && (!sigs || !pks || !result))) return FEC_E_ARG;
+  const HostArray a[] = {ragged(msg_off, 8), input(sigs, 64), input(pks, 32), output(result, 1)};
+  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_canon_sig_verify_msg(c, FEC_SECP256K1, m, (const uint8_t*)d[1], (const uint8_t*)d[2], (unsigned char*)d[3], cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ed25519_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                     const uint8_t* d_sigs, const uint8_t* d_pks, uint8_t* d_result, size_t n,
+                                     void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_sigs || !d_pks || !d_result))) return FEC_E_ARG;
+  if (!aligned16(d_sigs) || !aligned16(d_pks)) return FEC_E_ARG;
+  return launch_canon_sig_verify_msg(ctx, FEC_ED25519, m, d_sigs, d_pks, d_result, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ed25519_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                                 const uint8_t* sigs, const uint8_t* pks, uint8_t* result, size_t n) try {
+  if (!ctx || (n && (!sigs || !pks || !result))) return FEC_E_ARG;
+  const HostArray a[] = {ragged(msg_off, 8), input(sigs, 64), input(pks, 32), output(result, 1)};
+  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_canon_sig_verify_msg(c, FEC_ED25519, m, (const uint8_t*)d[1], (const uint8_t*)d[2], (unsigned char*)d[3], cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_decompress_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_in, size_t pk_len, uint64_t* d_xy,
+                             uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_in || !d_xy || !d_status)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if ((pk_len != 33 && pk_len != 65) || !aligned16(d_in) || !aligned16(d_xy)) return FEC_E_ARG;
+  return launch_canon_decompress(ctx, curve, d_in, pk_len, d_xy, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_decompress(fec_ctx* ctx, fec_curve curve, const uint8_t* in, size_t pk_len, uint64_t* xy, uint8_t* status,
+                         size_t n) try {
+  if (!ctx || (n && (!in || !xy || !status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (pk_len != 33 && pk_len != 65) return FEC_E_ARG;
+  const HostArray a[] = {input(in, pk_len), output(xy, 64), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_decompress(c, curve, (const uint8_t*)d[0], pk_len, (u64*)d[1], (unsigned char*)d[2], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 

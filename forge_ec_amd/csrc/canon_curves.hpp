@@ -1520,6 +1520,55 @@ FEC_DEV lmask eddsa_prepare(const fe& a_enc, const fe& r_enc, const fe& s, const
   return uniform_mask(a_ok & r_ok & s_lt & h_lt);
 }
 
+// ================================================================================================
+// From the wire: a 512-bit hash as a scalar, SEC 1 public keys (canon_msg.hpp)
+// ================================================================================================
+// (hi * 2^256 + lo) mod n for any hi, lo:  hi * R2 * R^-1 = hi R,  lo * R2 * R^-1 * 1 * R^-1 = lo  (mod n, R = 2^256);
+// every product is below n * 2^256, REDC's contract.  hi = 0 is the 256-bit case.
+template <class N>
+FEC_DEV fe reduce512(const fe& hi, const fe& lo) {
+  using F = Fn<N>;
+  return F::addn(F::mmul(hi, N::r2()), F::mmul(F::mmul(lo, N::r2()), fe_small(1)));
+}
+FEC_DEV fe p256_sqr_n(fe v, int n) {
+#pragma unroll 1
+  for (int i = 0; i < n; ++i) v = FpP256::sqr(v);
+  return v;
+}
+// a^((p+1)/4) for P-256, (p+1)/4 = (2^32 - 1) 2^222 + 2^190 + 2^94: the square root when one exists; 253 S + 7 M
+FEC_DEV fe p256_sqrt_candidate(const fe& a) {
+  using F = FpP256;
+  const fe x2 = F::mul(F::sqr(a), a);
+  const fe x4 = F::mul(p256_sqr_n(x2, 2), x2);
+  const fe x8 = F::mul(p256_sqr_n(x4, 4), x4);
+  const fe x16 = F::mul(p256_sqr_n(x8, 8), x8);
+  const fe x32 = F::mul(p256_sqr_n(x16, 16), x16);      // a^(2^32 - 1)
+  fe t = F::mul(p256_sqr_n(x32, 32), a);                // (2^32 - 1) 2^32 + 1
+  t = F::mul(p256_sqr_n(t, 96), a);                     // ... 2^96 + 1
+  return p256_sqr_n(t, 94);
+}
+// SEC 1 section 2.3.4 on the curve of P (SecpParams, P256Params), one form per call (`uncompressed` is wave-uniform).
+// Compressed: tag 2 or 3, x < p, x^3 + a x + b a square; y is the root with the tag's parity (the given y is ignored).
+// Uncompressed: tag 4, x, y < p, on the curve.  Every other tag -- 0 and the hybrid 6, 7 among them -- is rejected.
+template <class P>
+FEC_DEV lmask sec1_decode(u32 tag, const fe& x, const fe& y, bool uncompressed, aff& out) {
+  using W = wei<P>;
+  out.x = x;
+  if (uncompressed) {
+    out.y = y;
+    return uniform_mask(lanes_where(tag == 4u) & W::on_curve(out));
+  }
+  fe x2 = W::sqr(x);
+  if constexpr (!P::A_IS_ZERO) x2 = W::sub(x2, fe_small(3));
+  const fe c = W::add(W::mul(x2, x), P::b());
+  fe r;
+  if constexpr (P::A_IS_ZERO) r = secp_sqrt_candidate(c);
+  else r = p256_sqrt_candidate(c);
+  const lmask is_root = fe_eq(W::sqr(r), c);
+  out.y = fe_select(r, W::neg(r), lanes_where((r.w[0] & 1u) != (tag & 1u)));   // (c = 0: y = 0 for either tag)
+  return uniform_mask(lanes_where((tag | 1u) == 3u) & ~W::ge_p(x) & is_root);
+}
+
 }  // namespace canon
 using csecp = canon::wei<canon::SecpParams>;
 using cp256 = canon::wei<canon::P256Params>;

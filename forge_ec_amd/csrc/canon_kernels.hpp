@@ -4,6 +4,7 @@
 // per lane, 256-thread workgroups, coalesced 16-byte HBM<->LDS staging of word-major columns.
 #pragma once
 #include "canon_curves.hpp"
+#include "canon_msg.hpp"
 
 namespace fecgpu {
 
@@ -438,6 +439,102 @@ __global__ __launch_bounds__(TPB, 2) void k_canon_scalar_op(int op, const u32* _
   const fe y = b ? canon::ld8(b + i * 8) : fe_zero();
   const fe z = c ? canon::ld8(c + i * 8) : fe_zero();
   canon::st8(out + i * 8, canon::scalar_op<N>(op, x, y, z));
+}
+
+// ---- verification from the wire (canon_msg.hpp): message bytes, 64 signature bytes, encoded key -----------------
+// One element per lane, no LDS.  Each kernel hashes, then runs the after-the-hash prepare step unchanged and leaves what
+// the comb, the accumulate pass and the finish kernels read; `flag` (canon::MSG_*) goes to k_canon_msg_fold.  A lane whose
+// message range is bad (message_at) hashes the empty message and is marked MSG_BAD_RANGE.  `uncompressed` is uniform.
+__global__ __launch_bounds__(TPB, 2) void k_canon_bip340_prepare_msg(Messages m, const u32* __restrict__ sigs,
+                                                                     const u32* __restrict__ pks, u32* __restrict__ pxy,
+                                                                     u32* __restrict__ u2, u32* __restrict__ rs,
+                                                                     u32* __restrict__ ss, unsigned char* __restrict__ ok,
+                                                                     unsigned char* __restrict__ flag, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const unsigned char* msg;
+  u64 len;
+  const bool in_range = message_at(m, i, msg, len);
+  canon::aff P;
+  fe v, r, s;
+  const lmask good = canon::bip340_prepare_msg(sigs + i * 16, pks + i * 8, msg, len, P, v, r, s);
+  const bool mine = lane_of(good);
+  if (!mine) P = csecp::generator();  // keep the ladder on a valid point; the lane is rejected by `ok`
+  canon::st8(pxy + i * 16, P.x);
+  canon::st8(pxy + i * 16 + 8, P.y);
+  canon::st8(u2 + i * 8, v);
+  canon::st8(rs + i * 8, r);
+  canon::st8(ss + i * 8, s);
+  ok[i] = mine ? 1 : 0;
+  flag[i] = in_range ? canon::MSG_GO : canon::MSG_BAD_RANGE;
+}
+__global__ __launch_bounds__(TPB, 2) void k_ced_eddsa_prepare_msg(Messages m, const u32* __restrict__ sigs,
+                                                                  const u32* __restrict__ pks, u32* __restrict__ axy,
+                                                                  u32* __restrict__ rxy, u32* __restrict__ u2,
+                                                                  u32* __restrict__ ss, unsigned char* __restrict__ ok,
+                                                                  unsigned char* __restrict__ flag, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const unsigned char* msg;
+  u64 len;
+  const bool in_range = message_at(m, i, msg, len);
+  canon::aff A, R;
+  fe v, s;
+  const lmask good = canon::eddsa_prepare_msg(sigs + i * 16, pks + i * 8, msg, len, A, R, v, s);
+  const bool mine = lane_of(good);
+  if (!mine) A = ced::generator();
+  canon::st8(axy + i * 16, A.x);
+  canon::st8(axy + i * 16 + 8, A.y);
+  canon::st8(rxy + i * 16, R.x);
+  canon::st8(rxy + i * 16 + 8, R.y);
+  canon::st8(u2 + i * 8, v);
+  canon::st8(ss + i * 8, s);
+  ok[i] = mine ? 1 : 0;
+  flag[i] = in_range ? canon::MSG_GO : canon::MSG_BAD_RANGE;
+}
+// ECDSA: z, r, s and the decoded key for launch_canon_ecdsa_verify; a lane whose key failed hands it the generator
+template <class P>
+__global__ __launch_bounds__(TPB, 2) void k_canon_ecdsa_prepare_msg(Messages m, const u32* __restrict__ sigs,
+                                                                    const unsigned char* __restrict__ pks, int uncompressed,
+                                                                    u32* __restrict__ zs, u32* __restrict__ rs,
+                                                                    u32* __restrict__ ss, u32* __restrict__ pkxy,
+                                                                    unsigned char* __restrict__ flag, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const unsigned char* msg;
+  u64 len;
+  const bool in_range = message_at(m, i, msg, len);
+  fe z, r, s;
+  canon::aff Q;
+  const bool mine = lane_of(canon::ecdsa_prepare_msg<P>(sigs + i * 16, pks, i, uncompressed != 0, msg, len, z, r, s, Q));
+  if (!mine) Q = canon::wei<P>::generator();
+  canon::st8(zs + i * 8, z);
+  canon::st8(rs + i * 8, r);
+  canon::st8(ss + i * 8, s);
+  canon::st8(pkxy + i * 16, Q.x);
+  canon::st8(pkxy + i * 16 + 8, Q.y);
+  flag[i] = !in_range ? canon::MSG_BAD_RANGE : (mine ? canon::MSG_GO : canon::MSG_BAD_KEY);
+}
+// after the finish kernel: a lane the prepare kernel did not let through gets its own result
+__global__ __launch_bounds__(TPB) void k_canon_msg_fold(unsigned char* __restrict__ result,
+                                                        const unsigned char* __restrict__ flag, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const unsigned char f = flag[i];
+  if (f != canon::MSG_GO) result[i] = f == canon::MSG_BAD_RANGE ? 4 : 0;
+}
+// SEC 1 decoding on its own: status 0 and x, y, or CANON_BAD_POINT and zeros
+template <class P>
+__global__ __launch_bounds__(TPB, 2) void k_canon_decompress(const unsigned char* __restrict__ recs, int uncompressed,
+                                                             u32* __restrict__ xy, unsigned char* __restrict__ status,
+                                                             size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  canon::aff Q;
+  const bool mine = lane_of(canon::sec1_record<P>(recs, i, uncompressed != 0, Q));
+  canon::st8(xy + i * 16, mine ? Q.x : fe_zero());
+  canon::st8(xy + i * 16 + 8, mine ? Q.y : fe_zero());
+  status[i] = mine ? CANON_FINITE : CANON_BAD_POINT;
 }
 
 }  // namespace fecgpu

@@ -26,6 +26,7 @@
 #include "hkdf.hpp"
 #include "h2c.hpp"
 #include "host_ctx.hpp"
+#include "host_messages.hpp"
 #include "kernels.hpp"
 #include "cu_split.hpp"
 
@@ -1373,63 +1374,9 @@ int launch_curve25519_mul(fec_ctx* ctx, const u32* s, const u32* p, u32* out, si
 }
 }  // namespace
 
-// The calls that take messages: the layout, the host-pointer engine and the *_dev forms' argument rules.
-// Message i is msgs[off[i], off[i+1]); off holds n + 1 values, off[0] = 0, non-decreasing, off[n] = msg_len.
+// The calls that take messages: the layout, the host-pointer engine and the *_dev forms' argument rules are
+// host_messages.hpp's (with_messages, dev_enter, dev_messages), shared with canon.hip.
 namespace {
-bool msg_layout_ok(const uint8_t* msgs, const uint64_t* off, size_t msg_len, size_t n) {
-  if (!off || off[0] != 0 || off[n] != (uint64_t)msg_len || (msg_len && !msgs)) return false;
-  for (size_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return false;
-  return true;
-}
-// One chunk's messages onto the device: the bytes msgs[o[0], o[m]) into slot kStageBody, the m + 1 offsets o[0..m],
-// rebased to that range (`reb`: host scratch of at least m + 1 values that outlives the copy), into the slot after it.
-int stage_messages(fec_ctx* c, const uint8_t* msgs, const u64* o, size_t m, std::vector<uint64_t>& reb, hipStream_t st, Messages& dm) {
-  const u64 bytes = o[m] - o[0];
-  for (size_t k = 0; k <= m; ++k) reb[k] = o[k] - o[0];
-  int rc = ensure(c, kStageBody + 1, reb.size() * 8);
-  if (rc == FEC_OK && bytes) rc = ensure(c, kStageBody, bytes);
-  if (rc != FEC_OK) return rc;
-  if (bytes && hipMemcpyAsync(c->d_buf[kStageBody], msgs + o[0], bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-    return FEC_E_DEVICE;
-  if (hipMemcpyAsync(c->d_buf[kStageBody + 1], reb.data(), (m + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
-    return FEC_E_DEVICE;
-  dm = Messages{bytes ? static_cast<const unsigned char*>(c->d_buf[kStageBody]) : nullptr, static_cast<const u64*>(c->d_buf[kStageBody + 1]), bytes};
-  return FEC_OK;
-}
-// The host forms' engine, on a single-device or a multi-device ctx (host_ctx.hpp: sharded, chunked; one lane).  The layout
-// is checked once, here.  `a` names the call's arrays, the offsets among them as its one ragged() entry; per chunk the
-// engine stages them, then the chunk's message bytes and its offsets rebased to that range (stage_messages), and hands
-// body(ctx, d, messages, m, stream) the device side of all of it.  An array list with a secret in it (keys, and digests or
-// points whose message may be one) has the staging and the stream scratch cleared on every way out: chunked's rule.
-template <size_t N, class F>
-int with_messages(fec_ctx* ctx, size_t n, const HostArray (&a)[N], const uint8_t* msgs, const uint64_t* off, size_t msg_len, F body) {
-  size_t r = 0;
-  while (r < N && a[r].staged) ++r;
-  if (!ctx || r == N || !msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
-  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[N], size_t cnt, size_t) {
-    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
-    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
-      Messages dm;
-      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[r]), m, reb, st, dm);   // (d[r]: host, from the chunk's first element on)
-      return rc != FEC_OK ? rc : body(c, d, dm, m, st);
-    });
-  });
-}
-// What every *_dev form starts with: device pointers belong to one device, which becomes the current one.
-int dev_enter(fec_ctx* ctx) {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;
-  if (!ctx) return FEC_E_ARG;
-  return hipSetDevice(ctx->device) == hipSuccess ? FEC_OK : FEC_E_DEVICE;
-}
-// The message arrays of a *_dev form, whose layout nobody checks (each lane checks its own range): 0, or what is wrong
-// with the pointers -- both FEC_E_ARG, apart only because some forms test the curve between the two.
-enum { kDevMsgsNull = 1, kDevMsgsMisaligned = 2 };
-int dev_messages(const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, size_t n, Messages& m) {
-  m = Messages{d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len};
-  if ((n && !d_msg_off) || (msg_len && !d_msgs)) return kDevMsgsNull;
-  return (reinterpret_cast<uintptr_t>(d_msg_off) & 7u) ? kDevMsgsMisaligned : 0;
-}
 
 // SHA-512 and SHA-256 per message (kernels_eddsa.hip, kernels_schnorr.hip).  A digest is secret: its message may be.
 struct DigestKernel {

@@ -5,7 +5,7 @@
 namespace fecgpu {
 
 // Element i is bytes[off[i], off[i+1]): n + 1 offsets, `len` the length of `bytes`.  Passed to kernels by value.  The
-// host forms check the whole layout once (fecgpu.hip: with_messages); a *_dev caller's layout nobody has checked, so
+// host forms check the whole layout once (host_messages.hpp: with_messages); a *_dev caller's layout nobody has checked, so
 // each lane checks its own range.
 struct Messages {
   const unsigned char* bytes;

@@ -104,6 +104,61 @@ int fec_canon_eddsa_verify(fec_ctx* ctx, const uint64_t* a_enc /* n*4 */, const 
 int fec_canon_eddsa_verify_dev(fec_ctx* ctx, const uint64_t* d_a_enc, const uint64_t* d_r_enc, const uint64_t* d_s,
                                const uint64_t* d_h, uint8_t* d_result, size_t n, void* stream);
 
+/* ---- Verification from the message, the 64 signature bytes and the encoded public key --------------------------
+ * The three verifiers above begin after the hash and take limbs.  The calls below begin where a caller does: message i
+ * is msgs[msg_off[i], msg_off[i+1]) -- the layout of fecgpu.h's message calls: msg_off holds n + 1 values, msg_off[0] = 0,
+ * non-decreasing, msg_off[n] = msg_len -- signatures and keys are the bytes of their standards.  The hash, its reduction,
+ * the byte parsing and the key decoding run on the GPU; from the challenge on, each call runs exactly its after-the-hash
+ * counterpart above.  Nothing here is secret; work areas are not wiped beyond what every host call does.
+ * Host forms: FEC_E_ARG on a bad layout; chunked by fec_ctx_set_chunk and sharded over a multi-device ctx.
+ * *_dev forms: sigs, pks, in, xy 16-byte aligned, d_msg_off 8-byte aligned; every lane checks its own range and
+ * a bad one gets result 4; FEC_E_UNSUPPORTED on a multi-device ctx.
+ * result[i]: 1 valid, 0 invalid, 4 bad message range (*_dev only).
+ * Not offered: DER signatures, Ed25519ph / Ed25519ctx, ECDSA with another hash, batch (random linear combination)
+ * verification. */
+
+/* ECDSA with SHA-256 (FIPS 186-4 section 6.4 / SEC 1 section 4.1.4), FEC_SECP256K1 and FEC_P256 (FEC_ED25519:
+ * FEC_E_UNSUPPORTED).  z = the 32 bytes of SHA-256(msg_i) read big-endian (both orders have 256 bits: no truncation);
+ * sigs: r || s, 32 bytes each, big-endian; low-S is not enforced, as in fec_canon_ecdsa_verify (the twin (r, n - s)
+ * verifies).  pks: n SEC 1 keys of one form per call, pk_len = 33 (compressed) or 65 (uncompressed), else FEC_E_ARG.
+ * 33 bytes: byte 0 is 2 or 3, x < p, x^3 + a x + b has a root, and the root with the parity of byte 0 is taken.
+ * 65 bytes: byte 0 is 4, x, y < p, the point is on the curve.  Any other key -- byte 0 of 0, the hybrid forms 6 and 7
+ * among them -- gives result 0. */
+int fec_canon_ecdsa_verify_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */,
+                               size_t msg_len, const uint8_t* sigs /* n*64 */, const uint8_t* pks /* n*pk_len */,
+                               size_t pk_len, uint8_t* result /* n */, size_t n);
+int fec_canon_ecdsa_verify_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                                   size_t msg_len, const uint8_t* d_sigs, const uint8_t* d_pks, size_t pk_len,
+                                   uint8_t* d_result, size_t n, void* stream);
+
+/* BIP-340 (secp256k1).  sigs: r || s big-endian; pks: the 32-byte x-only keys.
+ * e = int(SHA-256(T || T || sig[0..32] || pk || msg_i)) mod n, T = SHA-256("BIP0340/challenge"); a message of any length.
+ * From e on: fec_canon_bip340_verify. */
+int fec_canon_bip340_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                                const uint8_t* sigs /* n*64 */, const uint8_t* pks /* n*32 */, uint8_t* result /* n */,
+                                size_t n);
+int fec_canon_bip340_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                    const uint8_t* d_sigs, const uint8_t* d_pks, uint8_t* d_result, size_t n,
+                                    void* stream);
+
+/* Ed25519 (RFC 8032 section 5.1.7).  sigs: R || S; pks: the 32-byte keys.
+ * h = SHA-512(sig[0..32] || pk || msg_i), the 64 bytes read little-endian and reduced mod l.  The bytes are hashed as
+ * given (a non-canonical encoding is rejected by the decoding, so that is unambiguous).  From h on:
+ * fec_canon_eddsa_verify -- canonical encodings only, S < l, the cofactorless equation S B - h A == R. */
+int fec_canon_ed25519_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                                 const uint8_t* sigs /* n*64 */, const uint8_t* pks /* n*32 */, uint8_t* result /* n */,
+                                 size_t n);
+int fec_canon_ed25519_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                     const uint8_t* d_sigs, const uint8_t* d_pks, uint8_t* d_result, size_t n,
+                                     void* stream);
+
+/* SEC 1 point decoding on its own, FEC_SECP256K1 and FEC_P256 (FEC_ED25519: FEC_E_UNSUPPORTED), by the rules of
+ * fec_canon_ecdsa_verify_msg.  status[i] = 0 with the x, y limbs in xy[i], or FEC_CANON_BAD_POINT with zeros. */
+int fec_canon_decompress(fec_ctx* ctx, fec_curve curve, const uint8_t* in /* n*pk_len */, size_t pk_len /* 33 or 65 */,
+                         uint64_t* xy /* n*8 */, uint8_t* status /* n */, size_t n);
+int fec_canon_decompress_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_in, size_t pk_len, uint64_t* d_xy,
+                             uint8_t* d_status, size_t n, void* stream);
+
 /* Arithmetic modulo the group order (n for secp256k1 / P-256, l for Ed25519) on any 256-bit inputs, results
  * in [0, order): op 0: out = a * b + c, op 1: out = a^-1 (0 for a = 0 mod order; b, c ignored).  With
  * fec_canon_mul_base this is the device side of signing, e.g. ECDSA  r = x(k G) mod n (a * 1 + 0),

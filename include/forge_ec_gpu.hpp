@@ -1064,6 +1064,53 @@ inline std::vector<uint8_t> ecdsa_verify(GpuContext& ctx, const std::vector<Limb
                                reinterpret_cast<const uint64_t*>(q.data()), ok.data(), n));
   return ok;
 }
+// ---- from the message, the 64 signature bytes and the encoded key: hash, parsing and key decoding on the GPU ----
+// valid[i]: 1 valid, 0 invalid.  Messages as eddsa::detail::Messages packs them.
+// ECDSA with SHA-256; keys: n SEC 1 keys of key_len = 33 (compressed) or 65 bytes each, one form per call
+template <fec_curve C>
+inline std::vector<uint8_t> ecdsa_verify_msg(GpuContext& ctx, const std::vector<std::string>& msgs, const std::vector<eddsa::Bytes64>& sigs,
+                                             const std::vector<uint8_t>& keys, size_t key_len) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "ECDSA is offered on secp256k1 and P-256");
+  const size_t n = sigs.size();
+  if (msgs.size() != n || keys.size() != n * key_len) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  std::vector<uint8_t> ok(n);
+  check(fec_canon_ecdsa_verify_msg(ctx.raw(), C, m.bytes.data(), m.off.data(), m.bytes.size(), reinterpret_cast<const uint8_t*>(sigs.data()),
+                                   keys.data(), key_len, ok.data(), n));
+  return ok;
+}
+// BIP-340; keys: the 32-byte x-only keys
+inline std::vector<uint8_t> bip340_verify_msg(GpuContext& ctx, const std::vector<std::string>& msgs, const std::vector<eddsa::Bytes64>& sigs,
+                                              const std::vector<eddsa::Bytes32>& keys) {
+  const size_t n = sigs.size();
+  if (msgs.size() != n || keys.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  std::vector<uint8_t> ok(n);
+  check(fec_canon_bip340_verify_msg(ctx.raw(), m.bytes.data(), m.off.data(), m.bytes.size(), reinterpret_cast<const uint8_t*>(sigs.data()),
+                                    reinterpret_cast<const uint8_t*>(keys.data()), ok.data(), n));
+  return ok;
+}
+// RFC 8032 Ed25519
+inline std::vector<uint8_t> ed25519_verify_msg(GpuContext& ctx, const std::vector<std::string>& msgs, const std::vector<eddsa::Bytes64>& sigs,
+                                               const std::vector<eddsa::Bytes32>& keys) {
+  const size_t n = sigs.size();
+  if (msgs.size() != n || keys.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  std::vector<uint8_t> ok(n);
+  check(fec_canon_ed25519_verify_msg(ctx.raw(), m.bytes.data(), m.off.data(), m.bytes.size(), reinterpret_cast<const uint8_t*>(sigs.data()),
+                                     reinterpret_cast<const uint8_t*>(keys.data()), ok.data(), n));
+  return ok;
+}
+// SEC 1 decoding on its own: status 0 and the point, or 2 (rejected) and zeros
+template <fec_curve C>
+inline PointResult decompress(GpuContext& ctx, const std::vector<uint8_t>& keys, size_t key_len) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "SEC 1 keys belong to secp256k1 and P-256");
+  if (key_len == 0 || keys.size() % key_len) throw Error(FEC_E_ARG);
+  const size_t n = keys.size() / key_len;
+  PointResult r{std::vector<Affine>(n), std::vector<uint8_t>(n)};
+  check(fec_canon_decompress(ctx.raw(), C, keys.data(), key_len, reinterpret_cast<uint64_t*>(r.points.data()), r.status.data(), n));
+  return r;
+}
 }  // namespace canon
 
 using Secp256k1 = Curve<FEC_SECP256K1>;

@@ -3,6 +3,18 @@ HIP events inside the library for secp256k1 key generation (k*G, comb) and ECDH 
 inputs resident in HBM.  One JSON line per workload.
 
     python tools/canon_perf.py [log2_n] [reps] [curve,...]
+
+From the message (fec_canon_*_verify_msg_dev) against the parts it replaces, one JSON line per row:
+
+    python tools/canon_perf.py msg [log2_n] [reps] [out.jsonl]
+
+The batch is resident on the device: n messages of 32 bytes, then of 256 bytes; keys are real (k*G from the comb,
+encoded on the host), signatures are random bytes -- every lane does the full work and is rejected at the end.  Per
+scheme, alternating in one process: the *_verify_msg_dev call; fec_sha256_dev / fec_sha512_dev over what a caller of
+the after-the-hash verifier has to hash (the bare message for ECDSA, T || T || r || pk || msg for BIP-340, R || A || msg
+for Ed25519) plus that verifier on limb arrays.  Wall clock around a device synchronise, median and spread (max - min) of
+`reps` samples; the whole set of rows is measured twice (pass 0, pass 1), so the run-to-run spread shows.  Then
+fec_canon_decompress_dev alone and the three host-pointer forms (32-byte messages, PCIe included).
 """
 import json
 import os
@@ -22,6 +34,136 @@ from forge_ec_amd.canon import CANON_CURVES  # noqa: E402
 # field multiplications per unit (each = 64 MAD32 for the 512-bit product + 8 for the fold)
 MULS = {"keygen": 64 * 11 + 274, "ecdh": 7 + 13 * 11 + 64 * (4 * 7 + 16) + 274 + 5}
 MAD_PER_MUL = 72
+
+
+def _timed(fn, reps):
+    """median and spread (max - min) in ms of `reps` runs after one warm-up, wall clock around a device synchronise"""
+    samples = []
+    for i in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        if i:
+            samples.append((time.perf_counter() - t0) * 1e3)
+    samples.sort()
+    return samples[len(samples) // 2], samples[-1] - samples[0]
+
+
+def _encoded_keys(ctx, n):
+    """real keys as bytes: {("secp256k1", 33): (n,33) uint8, ..., ("bip340", 32), ("ed25519", 32)}"""
+    out = {}
+    k = synth.scalars(n, 0, 51)
+    for cname in ("secp256k1", "p256", "ed25519"):
+        xy, st = CANON_CURVES[cname](ctx).mul_base(k)
+        assert not st.any()
+        x = xy[:, :4].copy().view(np.uint8).reshape(n, 32)
+        y = xy[:, 4:].copy().view(np.uint8).reshape(n, 32)
+        if cname == "ed25519":
+            enc = y.copy()
+            enc[:, 31] |= (x[:, 0] & 1) << 7
+            out[("ed25519", 32)] = enc
+            continue
+        xb, yb = x[:, ::-1], y[:, ::-1]   # big-endian
+        out[(cname, 33)] = np.ascontiguousarray(np.concatenate([(2 + (y[:, :1] & 1)).astype(np.uint8), xb], axis=1))
+        out[(cname, 65)] = np.ascontiguousarray(np.concatenate([np.full((n, 1), 4, dtype=np.uint8), xb, yb], axis=1))
+        if cname == "secp256k1":
+            out[("bip340", 32)] = np.ascontiguousarray(xb)
+    return out
+
+
+def main_msg():
+    logn = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    out_path = sys.argv[4] if len(sys.argv) > 4 else None
+    n = 1 << logn
+    ctx = F.Context(0)
+    lib, h = ctx._lib, ctx._h
+    rng = np.random.default_rng(16)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()  # noqa: E731
+    keys = _encoded_keys(ctx, n)
+    sigs_h = rng.integers(0, 256, size=(n, 64), dtype=np.uint8)
+    sigs_h[:, 0] &= 0x7F      # big-endian r and s below p and n; Ed25519's little-endian S below l
+    sigs_h[:, 32] &= 0x7F
+    sigs_h[:, 63] &= 0x0F
+    sigs = dev(sigs_h)
+    limbs = [torch.from_numpy(synth.scalars(n, 0, 60 + i).view(np.int64)).cuda() for i in range(4)]
+    pub = torch.from_numpy(CANON_CURVES["secp256k1"](ctx).mul_base(synth.scalars(n, 0, 51))[0].view(np.int64)).cuda()
+    pub_p256 = torch.from_numpy(CANON_CURVES["p256"](ctx).mul_base(synth.scalars(n, 0, 51))[0].view(np.int64)).cuda()
+    res = torch.empty(n, dtype=torch.uint8, device="cuda")
+    digests = torch.empty(n * 64, dtype=torch.uint8, device="cuda")
+    xy = torch.empty((n, 8), dtype=torch.int64, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    schemes = [("ecdsa-secp256k1-33", "secp256k1", ("secp256k1", 33), 0), ("ecdsa-secp256k1-65", "secp256k1", ("secp256k1", 65), 0),
+               ("ecdsa-p256-33", "p256", ("p256", 33), 0), ("bip340", "secp256k1", ("bip340", 32), 128), ("ed25519", "ed25519", ("ed25519", 32), 64)]
+    for npass in range(2):
+        for mlen in (32, 256):
+            msgs = dev(rng.integers(0, 256, size=n * mlen, dtype=np.uint8))
+            off = dev(np.arange(n + 1, dtype=np.uint64) * mlen)
+            for name, cname, kk, prefix in schemes:
+                c = CANON_CURVES[cname](ctx)
+                pk = dev(keys[kk])
+                # what the parts approach hashes: the message behind its prefix
+                pm = dev(rng.integers(0, 256, size=n * (prefix + mlen), dtype=np.uint8)) if prefix else msgs
+                poff = dev(np.arange(n + 1, dtype=np.uint64) * (prefix + mlen)) if prefix else off
+                if name.startswith("ecdsa"):
+                    whole = lambda: c.ecdsa_verify_msg_dev(msgs.data_ptr(), off.data_ptr(), n * mlen, sigs.data_ptr(), pk.data_ptr(), kk[1], res.data_ptr(), n, st)  # noqa: E731
+                    hash_ = lambda: ctx.sha256_dev(pm.data_ptr(), poff.data_ptr(), n * mlen, digests.data_ptr(), None, n, st)  # noqa: E731
+                    p = pub if cname == "secp256k1" else pub_p256
+                    verify = lambda: c.ecdsa_verify_dev(limbs[0].data_ptr(), limbs[1].data_ptr(), limbs[2].data_ptr(), p.data_ptr(), res.data_ptr(), n, st)  # noqa: E731
+                elif name == "bip340":
+                    whole = lambda: c.bip340_verify_msg_dev(msgs.data_ptr(), off.data_ptr(), n * mlen, sigs.data_ptr(), pk.data_ptr(), res.data_ptr(), n, st)  # noqa: E731
+                    hash_ = lambda: ctx.sha256_dev(pm.data_ptr(), poff.data_ptr(), n * (prefix + mlen), digests.data_ptr(), None, n, st)  # noqa: E731
+                    verify = lambda: c.bip340_verify_dev(pub.data_ptr(), limbs[1].data_ptr(), limbs[2].data_ptr(), limbs[3].data_ptr(), res.data_ptr(), n, st)  # noqa: E731
+                else:
+                    whole = lambda: c.ed25519_verify_msg_dev(msgs.data_ptr(), off.data_ptr(), n * mlen, sigs.data_ptr(), pk.data_ptr(), res.data_ptr(), n, st)  # noqa: E731
+                    hash_ = lambda: ctx.sha512_dev(pm.data_ptr(), poff.data_ptr(), n * (prefix + mlen), digests.data_ptr(), None, n, st)  # noqa: E731
+                    verify = lambda: c.eddsa_verify_dev(pk.data_ptr(), sigs.data_ptr(), limbs[2].data_ptr(), limbs[3].data_ptr(), res.data_ptr(), n, st)  # noqa: E731
+                ws, hs, vs = [], [], []
+                for _ in range(3):       # whole, parts, whole, parts, ...: alternating in one process
+                    ws.append(_timed(whole, reps))
+                    hs.append(_timed(hash_, reps))
+                    vs.append(_timed(verify, reps))
+                w, h_, v = (sorted(x)[1] for x in (ws, hs, vs))      # the middle round's (median, spread)
+                emit({"row": name, "msg_bytes": mlen, "pass": npass, "n": n, "reps": reps,
+                      "msg_dev_ms": round(w[0], 4), "msg_dev_spread_ms": round(max(x[1] for x in ws), 4),
+                      "hash_dev_ms": round(h_[0], 4), "verify_dev_ms": round(v[0], 4), "parts_ms": round(h_[0] + v[0], 4),
+                      "parts_spread_ms": round(max(x[1] for x in hs) + max(x[1] for x in vs), 4),
+                      "msg_over_parts": round(w[0] / (h_[0] + v[0]), 4), "M_per_s": round(n / w[0] / 1e3, 3)})
+        for cname, kl in (("secp256k1", 33), ("secp256k1", 65), ("p256", 33), ("p256", 65)):
+            c = CANON_CURVES[cname](ctx)
+            pk = dev(keys[(cname, kl)])
+            ms, spread = _timed(lambda: c.decompress_dev(pk.data_ptr(), kl, xy.data_ptr(), res.data_ptr(), n, st), reps)
+            emit({"row": "decompress-%s-%d" % (cname, kl), "pass": npass, "n": n, "reps": reps, "ms": round(ms, 4),
+                  "spread_ms": round(spread, 4), "M_per_s": round(n / ms / 1e3, 3)})
+    # host pointers: what a caller with arrays in host memory sees (PCIe: 64 + key + message bytes in, 1 byte out)
+    mlen = 32
+    msgs_h = rng.integers(0, 256, size=n * mlen, dtype=np.uint8)
+    off_h = np.arange(n + 1, dtype=np.uint64) * mlen
+    res_h = np.zeros(n, dtype=np.uint8)
+    p = lambda a: a.ctypes.data  # noqa: E731
+    for name, cid, kk in (("ecdsa-secp256k1-33", 0, ("secp256k1", 33)), ("bip340", None, ("bip340", 32)), ("ed25519", None, ("ed25519", 32))):
+        pk = keys[kk]
+        if cid is not None:
+            fn = lambda: lib.fec_canon_ecdsa_verify_msg(h, cid, p(msgs_h), p(off_h), n * mlen, p(sigs_h), p(pk), kk[1], p(res_h), n)  # noqa: E731
+        elif name == "bip340":
+            fn = lambda: lib.fec_canon_bip340_verify_msg(h, p(msgs_h), p(off_h), n * mlen, p(sigs_h), p(pk), p(res_h), n)  # noqa: E731
+        else:
+            fn = lambda: lib.fec_canon_ed25519_verify_msg(h, p(msgs_h), p(off_h), n * mlen, p(sigs_h), p(pk), p(res_h), n)  # noqa: E731
+        assert fn() == 0
+        ms, spread = _timed(fn, reps)
+        emit({"row": "host-" + name, "msg_bytes": mlen, "n": n, "reps": reps, "ms": round(ms, 4), "spread_ms": round(spread, 4),
+              "M_per_s": round(n / ms / 1e3, 3), "bytes_per_signature": 64 + kk[1] + mlen + 8 + 1})
+    if out_path:
+        with open(out_path, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
 
 
 def main():
@@ -79,4 +221,7 @@ def main():
                   flush=True)
 
 
-main()
+if len(sys.argv) > 1 and sys.argv[1] == "msg":
+    main_msg()
+else:
+    main()
