@@ -9,7 +9,9 @@
  *    then round 4's calls: the prefix-table policy, schnorr::batch_verify::<Ed25519>, the multi-GPU calls' refusal;
  * 2. canonical mode: the standard secp256k1 public keys of the same scalars (fec_canon_mul_base) --
  *    3*G.x is the BIP-340 test-vector-0 public key; that vector's signature is then verified from the message,
- *    the 64 signature bytes and the 32 key bytes (fec_canon_bip340_verify_msg: hash and decoding on the GPU).
+ *    the 64 signature bytes and the 32 key bytes (fec_canon_bip340_verify_msg: hash and decoding on the GPU);
+ *    then one message is signed and verified per scheme -- ECDSA (secp256k1, low S), BIP-340, Ed25519 -- with the keys
+ *    from fec_canon_public_key: the BIP-340 signature of key 3 over 0^32 with zero aux is test vector 0 again.
  * Prints one line per step and returns 0 when everything behaved.
  */
 #include <stdint.h>
@@ -76,6 +78,31 @@ int main(void) {
   rc = fec_canon_bip340_verify_msg(ctx, msgs, msg_off, sizeof msgs, &sigs[0][0], &pks[0][0], valid, 2);
   printf("canon   bip340_verify_msg(vector 0) rc=%d valid=%d, over another message valid=%d\n", rc, valid[0], valid[1]);
   ok = ok && rc == FEC_OK && valid[0] == 1 && valid[1] == 0;
+
+  /* sign, then verify, one message per scheme: everything from the key bytes to the signature bytes on the GPU */
+  uint8_t key3[32], aux0[32], sg[64], pk33[33], pk32[32], sst[1], pst[1], vv[1];
+  const uint64_t one_off[2] = {0, 32};
+  memset(key3, 0, 32);
+  key3[31] = 3;
+  memset(aux0, 0, 32);
+  rc = fec_canon_bip340_sign_msg(ctx, msgs, one_off, 32, key3, aux0, sg, sst, 1);
+  if (rc == FEC_OK) rc = fec_canon_public_key(ctx, FEC_CANON_SCHEME_BIP340, key3, pk32, 32, pst, 1);
+  if (rc == FEC_OK) rc = fec_canon_bip340_verify_msg(ctx, msgs, one_off, 32, sg, pk32, vv, 1);
+  printf("canon   bip340_sign_msg(key 3, 0^32, aux 0) rc=%d status=%d, is vector 0: %s, verifies: %d\n", rc, sst[0],
+         memcmp(sg, sig0, 64) == 0 ? "yes" : "NO", vv[0]);
+  ok = ok && rc == FEC_OK && sst[0] == 0 && pst[0] == 0 && memcmp(sg, sig0, 64) == 0 && vv[0] == 1;
+  rc = fec_canon_ecdsa_sign_msg(ctx, FEC_SECP256K1, msgs, one_off, 32, key3, FEC_CANON_SIGN_LOW_S, sg, sst, 1);
+  if (rc == FEC_OK) rc = fec_canon_public_key(ctx, FEC_SECP256K1, key3, pk33, 33, pst, 1);
+  if (rc == FEC_OK) rc = fec_canon_ecdsa_verify_msg(ctx, FEC_SECP256K1, msgs, one_off, 32, sg, pk33, 33, vv, 1);
+  printf("canon   ecdsa_sign_msg(secp256k1, low S) rc=%d status=%d, s starts %02x, verifies: %d\n", rc, sst[0], sg[32], vv[0]);
+  ok = ok && rc == FEC_OK && sst[0] == 0 && pst[0] == 0 && sg[32] < 0x80 && vv[0] == 1;
+  rc = fec_canon_ed25519_sign_msg(ctx, msgs, one_off, 32, key3, sg, pk32, sst, 1);
+  if (rc == FEC_OK) rc = fec_canon_ed25519_verify_msg(ctx, msgs, one_off, 32, sg, pk32, vv, 1);
+  printf("canon   ed25519_sign_msg rc=%d status=%d, verifies: %d\n", rc, sst[0], vv[0]);
+  ok = ok && rc == FEC_OK && sst[0] == 0 && vv[0] == 1;
+  memset(key3, 0, 32);   /* a zero key is refused: status FEC_CANON_BAD_KEY, a zero signature */
+  rc = fec_canon_ecdsa_sign_msg(ctx, FEC_SECP256K1, msgs, one_off, 32, key3, 0, sg, sst, 1);
+  ok = ok && rc == FEC_OK && sst[0] == FEC_CANON_BAD_KEY && sg[0] == 0 && sg[63] == 0;
 
   /* ---- round 4's additions, as an FFI would call them ---- */
   /* the prefix-table policy: how much of the free memory a table may take, a table built at a point of the caller's

@@ -33,7 +33,12 @@ CANON_ABI_SYMBOLS = [
     "fec_canon_scalar_op",
     "fec_canon_ecdsa_verify_msg", "fec_canon_ecdsa_verify_msg_dev", "fec_canon_bip340_verify_msg", "fec_canon_bip340_verify_msg_dev",
     "fec_canon_ed25519_verify_msg", "fec_canon_ed25519_verify_msg_dev", "fec_canon_decompress", "fec_canon_decompress_dev",
+    "fec_canon_mul_base_secret", "fec_canon_mul_base_secret_dev", "fec_canon_public_key", "fec_canon_public_key_dev",
+    "fec_canon_ecdsa_sign_digest", "fec_canon_ecdsa_sign_digest_dev", "fec_canon_ecdsa_sign_msg", "fec_canon_ecdsa_sign_msg_dev",
+    "fec_canon_rfc6979_k", "fec_canon_rfc6979_k_dev", "fec_canon_bip340_sign_msg", "fec_canon_bip340_sign_msg_dev",
+    "fec_canon_ed25519_sign_msg", "fec_canon_ed25519_sign_msg_dev",
 ]
+CANON_BAD_SCALAR, CANON_BAD_KEY, CANON_SIGN_LOW_S, CANON_SCHEME_BIP340 = 3, 6, 1, 3
 F_INV = 5
 
 
@@ -274,6 +279,21 @@ def lib():
         getattr(L, name + "_dev").argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp]
     L.fec_canon_decompress.argtypes = [vp, ci, vp, sz, vp, vp, sz]
     L.fec_canon_decompress_dev.argtypes = [vp, ci, vp, sz, vp, vp, sz, vp]
+    cu = ctypes.c_uint
+    L.fec_canon_mul_base_secret.argtypes = [vp, ci, vp, vp, vp, sz]
+    L.fec_canon_mul_base_secret_dev.argtypes = [vp, ci, vp, vp, vp, sz, vp]
+    L.fec_canon_public_key.argtypes = [vp, ci, vp, vp, sz, vp, sz]
+    L.fec_canon_public_key_dev.argtypes = [vp, ci, vp, vp, sz, vp, sz, vp]
+    L.fec_canon_ecdsa_sign_digest.argtypes = [vp, ci, vp, vp, cu, vp, vp, sz]
+    L.fec_canon_ecdsa_sign_digest_dev.argtypes = [vp, ci, vp, vp, cu, vp, vp, sz, vp]
+    L.fec_canon_ecdsa_sign_msg.argtypes = [vp, ci, vp, vp, sz, vp, cu, vp, vp, sz]
+    L.fec_canon_ecdsa_sign_msg_dev.argtypes = [vp, ci, vp, vp, sz, vp, cu, vp, vp, sz, vp]
+    L.fec_canon_rfc6979_k.argtypes = [vp, ci, vp, vp, vp, vp, sz]
+    L.fec_canon_rfc6979_k_dev.argtypes = [vp, ci, vp, vp, vp, vp, sz, vp]
+    L.fec_canon_bip340_sign_msg.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz]
+    L.fec_canon_bip340_sign_msg_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]
+    L.fec_canon_ed25519_sign_msg.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz]
+    L.fec_canon_ed25519_sign_msg_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]
     for n in CANON_ABI_SYMBOLS:
         getattr(L, n).restype = ci
     _lib = L

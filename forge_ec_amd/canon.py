@@ -41,8 +41,22 @@ def _verify_msg(lib_fn, h, msgs, sigs, pks, pk_len, what, lead=()):
     return out
 
 
+def _sign_msg(lib_fn, h, msgs, secrets, what, lead=(), mid=(), after=()):
+    """the *_sign_msg calls: (sigs (n,64), status (n,)); secrets = the 32-byte record arrays, in order."""
+    buf, off, total = Context._messages(msgs)
+    n = len(off) - 1
+    recs = [_bytes_rows(x, 32, "keys") for x in secrets]
+    if any(r.shape[0] != n for r in recs):
+        raise ValueError("inputs differ in length")
+    sigs = np.zeros((n, 64), dtype=np.uint8)
+    st = np.zeros(n, dtype=np.uint8)
+    _check(lib_fn(h, *lead, _ptr(buf), _ptr(off), total, *[_ptr(r) for r in recs], *mid, _ptr(sigs), *after, _ptr(st), n), what)
+    return sigs, st
+
+
 class CanonCurve:
     CURVE = None
+    SCHEME = None
 
     def __init__(self, ctx=None, device=0):
         self.ctx = ctx if ctx is not None else Context(device)
@@ -57,6 +71,77 @@ class CanonCurve:
         st = np.zeros(n, dtype=np.uint8)
         _check(self._lib.fec_canon_mul_base(self._h, self.CURVE, _ptr(k), _ptr(xy), _ptr(st), n), "fec_canon_mul_base")
         return xy, st
+
+    def mul_base_secret(self, scalars):
+        """mul_base for secret scalars: no table lookup indexed by a digit, no branch on one (include/fecgpu_canon.h, the
+        signing side).  Weierstrass: k outside [1, n) gets status 3 and zeros."""
+        k = _u64(scalars, 4)
+        n = k.shape[0]
+        xy = np.zeros((n, 8), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_mul_base_secret(self._h, self.CURVE, _ptr(k), _ptr(xy), _ptr(st), n), "fec_canon_mul_base_secret")
+        return xy, st
+
+    def mul_base_secret_dev(self, d_scalars, d_out_xy, d_status, n, stream=None):
+        _check(self._lib.fec_canon_mul_base_secret_dev(self._h, self.CURVE, d_scalars, d_out_xy, d_status, n, stream),
+               "fec_canon_mul_base_secret_dev")
+
+    def public_key(self, keys, out_len=None, scheme=None):
+        """(keys (n,out_len) uint8, status): ECDSA curves SEC 1 with out_len 33 (default) or 65; Ed25519 32 bytes from the
+        seed; scheme=L.CANON_SCHEME_BIP340 (secp256k1): 32 bytes x-only.  status 6: key 0 or >= n, zeros."""
+        scheme = self.SCHEME if scheme is None else scheme
+        out_len = (33 if scheme in (L.SECP256K1, L.P256) else 32) if out_len is None else out_len
+        k = _bytes_rows(keys, 32, "keys")
+        n = k.shape[0]
+        out = np.zeros((n, out_len), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_public_key(self._h, scheme, _ptr(k), _ptr(out), out_len, _ptr(st), n), "fec_canon_public_key")
+        return out, st
+
+    def public_key_dev(self, d_keys, d_out, out_len, d_status, n, stream=None, scheme=None):
+        _check(self._lib.fec_canon_public_key_dev(self._h, self.SCHEME if scheme is None else scheme, d_keys, d_out, out_len,
+                                                  d_status, n, stream), "fec_canon_public_key_dev")
+
+    def ecdsa_sign_digest(self, digests, keys, flags=0):
+        """ECDSA with RFC 6979 nonces over given 32-byte digests (secp256k1, P-256): (sigs (n,64) r || s big-endian, status).
+        keys (n,32) big-endian.  flags: L.CANON_SIGN_LOW_S.  status: 0, 6 (key 0 or >= n), 5 (unobservable)."""
+        dg, k = _bytes_rows(digests, 32, "digests"), _bytes_rows(keys, 32, "keys")
+        n = dg.shape[0]
+        if k.shape[0] != n:
+            raise ValueError("inputs differ in length")
+        sigs = np.zeros((n, 64), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_ecdsa_sign_digest(self._h, self.CURVE, _ptr(dg), _ptr(k), flags, _ptr(sigs), _ptr(st), n),
+               "fec_canon_ecdsa_sign_digest")
+        return sigs, st
+
+    def ecdsa_sign_digest_dev(self, d_digests, d_keys, flags, d_sigs, d_status, n, stream=None):
+        _check(self._lib.fec_canon_ecdsa_sign_digest_dev(self._h, self.CURVE, d_digests, d_keys, flags, d_sigs, d_status, n, stream),
+               "fec_canon_ecdsa_sign_digest_dev")
+
+    def ecdsa_sign_msg(self, msgs, keys, flags=0):
+        """ECDSA with SHA-256 and RFC 6979 nonces from the message: msgs a list of n byte strings -> (sigs, status)."""
+        return _sign_msg(self._lib.fec_canon_ecdsa_sign_msg, self._h, msgs, [keys], "fec_canon_ecdsa_sign_msg", lead=(self.CURVE,),
+                         mid=(flags,))
+
+    def ecdsa_sign_msg_dev(self, d_msgs, d_msg_off, msg_len, d_keys, flags, d_sigs, d_status, n, stream=None):
+        _check(self._lib.fec_canon_ecdsa_sign_msg_dev(self._h, self.CURVE, d_msgs, d_msg_off, msg_len, d_keys, flags, d_sigs,
+                                                      d_status, n, stream), "fec_canon_ecdsa_sign_msg_dev")
+
+    def rfc6979_k(self, digests, keys):
+        """The RFC 6979 nonces alone: (k (n,32) big-endian, status)."""
+        dg, k = _bytes_rows(digests, 32, "digests"), _bytes_rows(keys, 32, "keys")
+        n = dg.shape[0]
+        if k.shape[0] != n:
+            raise ValueError("inputs differ in length")
+        out = np.zeros((n, 32), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_rfc6979_k(self._h, self.CURVE, _ptr(dg), _ptr(k), _ptr(out), _ptr(st), n), "fec_canon_rfc6979_k")
+        return out, st
+
+    def rfc6979_k_dev(self, d_digests, d_keys, d_k_out, d_status, n, stream=None):
+        _check(self._lib.fec_canon_rfc6979_k_dev(self._h, self.CURVE, d_digests, d_keys, d_k_out, d_status, n, stream),
+               "fec_canon_rfc6979_k_dev")
 
     def mul(self, scalars, points_xy):
         """(xy, status) with xy[i] = scalars[i] * points_xy[i]; off-curve inputs get status 2."""
@@ -195,6 +280,15 @@ def _four(lib_fn, h, a, b, c, d, what):
 
 class CanonSecp256k1(CanonCurve):
     CURVE = L.SECP256K1
+    SCHEME = L.SECP256K1
+
+    def bip340_sign_msg(self, msgs, keys, aux):
+        """BIP-340 default signing: msgs a list of n byte strings (any length), keys (n,32), aux (n,32) -> (sigs, status)."""
+        return _sign_msg(self._lib.fec_canon_bip340_sign_msg, self._h, msgs, [keys, aux], "fec_canon_bip340_sign_msg")
+
+    def bip340_sign_msg_dev(self, d_msgs, d_msg_off, msg_len, d_keys, d_aux, d_sigs, d_status, n, stream=None):
+        _check(self._lib.fec_canon_bip340_sign_msg_dev(self._h, d_msgs, d_msg_off, msg_len, d_keys, d_aux, d_sigs, d_status, n,
+                                                       stream), "fec_canon_bip340_sign_msg_dev")
 
     def bip340_verify(self, pk_x, r, s, e):
         """BIP-340 Schnorr verification; e = int(tagged_hash("BIP0340/challenge", r || pk || m)).  (n,) uint8."""
@@ -216,11 +310,25 @@ class CanonSecp256k1(CanonCurve):
 
 class CanonP256(CanonCurve):
     CURVE = L.P256
+    SCHEME = L.P256
 
 
 class CanonEd25519(CanonCurve):
     """Ed25519 (RFC 8032): affine (x, y) of k*B / k*P; there is no point at infinity, status is 0 or 2."""
     CURVE = L.ED25519
+    SCHEME = L.ED25519
+
+    def ed25519_sign_msg(self, msgs, seeds, with_keys=True):
+        """RFC 8032 Ed25519 signing: msgs a list of n byte strings, seeds (n,32) -> (sigs (n,64), pks (n,32) or None, status)."""
+        n = len(msgs)
+        pks = np.zeros((n, 32), dtype=np.uint8) if with_keys else None
+        sigs, st = _sign_msg(self._lib.fec_canon_ed25519_sign_msg, self._h, msgs, [seeds], "fec_canon_ed25519_sign_msg",
+                             after=(_ptr(pks) if with_keys else None,))
+        return sigs, pks, st
+
+    def ed25519_sign_msg_dev(self, d_msgs, d_msg_off, msg_len, d_seeds, d_sigs, d_pks_out, d_status, n, stream=None):
+        _check(self._lib.fec_canon_ed25519_sign_msg_dev(self._h, d_msgs, d_msg_off, msg_len, d_seeds, d_sigs, d_pks_out, d_status,
+                                                        n, stream), "fec_canon_ed25519_sign_msg_dev")
 
     def eddsa_verify(self, a_enc, r_enc, s, h):
         """RFC 8032 verification; encodings as little-endian 256-bit integers, h = SHA-512(R||A||M) mod l."""

@@ -7,6 +7,7 @@
 #include "host_ctx.hpp"
 #include "host_messages.hpp"
 #include "canon_kernels.hpp"
+#include "canon_sign_kernels.hpp"
 
 using namespace fecgpu;
 using namespace fecgpu::host;
@@ -295,6 +296,203 @@ int launch_canon_decompress(fec_ctx* ctx, int curve, const uint8_t* d_in, size_t
   return L.done();
 }
 
+// ---- the signing side (canon_sign.hpp, canon_sign_kernels.hpp) ------------------------------------------------------
+// One launch's work area: a single region of the stream's scratch, carved on 256-byte boundaries.  Everything a signer
+// leaves between its kernels lives here -- key and nonce limbs, un-normalised points, Z -- and the whole area is cleared
+// behind the last kernel on every way out (the destructor queues the clear; the scratch stays held until then).
+inline size_t r256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct SignArea {
+  WorkArea wa;
+  char* base = nullptr;
+  size_t total = 0, used = 0;
+  hipStream_t s = nullptr;
+  int open(fec_ctx* ctx, hipStream_t st, size_t bytes) {
+    s = st;
+    total = bytes;
+    wa.add(base, bytes);
+    return wa.acquire(ctx, st);
+  }
+  template <class T>
+  T* take(size_t bytes) {
+    T* p = reinterpret_cast<T*>(base + used);
+    used += r256(bytes);
+    return p;
+  }
+  ~SignArea() {
+    if (base) (void)hipMemsetAsync(base, 0, total, s);
+  }
+};
+// what one secret comb pass over `cnt` scalars needs besides its output: Z, the point status, the refused flags, the flag word
+inline size_t comb_area_bytes(size_t cnt) { return r256(cnt * 32) + 2 * r256(cnt) + 256; }
+struct CombArea {
+  u32* z;
+  unsigned char *pst, *refused;
+  u32* flag;
+  void take(SignArea& a, size_t cnt) {
+    z = a.take<u32>(cnt * 32);
+    pst = a.take<unsigned char>(cnt);
+    refused = a.take<unsigned char>(cnt);
+    flag = a.take<u32>(256);
+  }
+};
+// affine xy[i] = scalars[i] * G for secret scalars: scan comb, then the batched normalisation.  The 4-bit table is built
+// on first use whatever FEC_CANON_COMB4 says.  c.flag must be zero on entry (launch_secret_report reads it).
+int launch_secret_comb(fec_ctx* ctx, int curve, const u32* scalars, u32* xy, const CombArea& c, size_t cnt, hipStream_t s) {
+  int rc = ensure_canon_comb(ctx, curve, s);
+  if (rc != FEC_OK) return rc;
+  dim3 g(grid_for(cnt)), b(TPB);
+  const u32* tab = ctx->d_canon_comb[curve];
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_mul_base_secret<canon::SecpParams>), g, b, 0, s, scalars, tab, xy, c.z, c.pst, c.refused, c.flag, cnt);
+  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_mul_base_secret<canon::P256Params>), g, b, 0, s, scalars, tab, xy, c.z, c.pst, c.refused, c.flag, cnt);
+  else hipLaunchKernelGGL(k_ced_mul_base_secret, g, b, 0, s, scalars, tab, xy, c.z, c.pst, c.refused, cnt);
+  const size_t lanes = (cnt + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
+  const size_t stride = (lanes + 63) / 64 * 64;
+  dim3 gn(grid_for(stride));
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_normalize<csecp>), gn, b, 0, s, xy, c.z, c.pst, cnt, stride);
+  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_normalize<cp256>), gn, b, 0, s, xy, c.z, c.pst, cnt, stride);
+  else hipLaunchKernelGGL((k_canon_normalize<ced>), gn, b, 0, s, xy, c.z, c.pst, cnt, stride);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+int launch_secret_report(fec_ctx* ctx, int curve, const CombArea& c, hipStream_t s) {
+  if (curve == FEC_ED25519 || !ctx->d_err) return FEC_OK;
+  hipLaunchKernelGGL(k_canon_secret_report, dim3(1), dim3(1), 0, s, c.flag, ctx->d_err);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+inline hipStream_t sign_stream(fec_ctx* ctx, void* stream) {
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);
+  return s;
+}
+
+int launch_canon_mul_base_secret(fec_ctx* ctx, int curve, const u64* dk, u64* dxy, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t s = sign_stream(ctx, stream);
+  SignArea a;
+  int rc = a.open(ctx, s, comb_area_bytes(n));
+  if (rc != FEC_OK) return rc;
+  CombArea c;
+  c.take(a, n);
+  c.pst = dst;   // the normalisation writes the caller's status from Z; a refused scalar is folded in behind it
+  if (hipMemsetAsync(c.flag, 0, 4, s) != hipSuccess) return FEC_E_DEVICE;
+  rc = launch_secret_comb(ctx, curve, (const u32*)dk, (u32*)dxy, c, n, s);
+  if (rc != FEC_OK) return rc;
+  hipLaunchKernelGGL(k_canon_secret_fold, dim3(grid_for(n)), dim3(TPB), 0, s, (u32*)dxy, dst, c.refused, n);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  return launch_secret_report(ctx, curve, c, s);
+}
+
+// scheme of fec_canon_public_key: the curve ids, and BIP-340
+enum { kSchemeBip340 = FEC_CANON_SCHEME_BIP340 };
+inline int scheme_curve(int scheme) { return scheme == kSchemeBip340 ? FEC_SECP256K1 : scheme; }
+inline bool key_len_ok(int scheme, size_t len) {
+  if (scheme == FEC_SECP256K1 || scheme == FEC_P256) return len == 33 || len == 65;
+  return len == 32;
+}
+int launch_canon_public_key(fec_ctx* ctx, int scheme, const uint8_t* dkeys, uint8_t* dout, size_t out_len, unsigned char* dst,
+                            size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  const int curve = scheme_curve(scheme);
+  hipStream_t s = sign_stream(ctx, stream);
+  SignArea a;
+  int rc = a.open(ctx, s, r256(n * 32) + r256(n * 64) + comb_area_bytes(n));
+  if (rc != FEC_OK) return rc;
+  u32* ds = a.take<u32>(n * 32);
+  u32* xy = a.take<u32>(n * 64);
+  CombArea c;
+  c.take(a, n);
+  if (hipMemsetAsync(c.flag, 0, 4, s) != hipSuccess) return FEC_E_DEVICE;
+  dim3 g(grid_for(n)), b(TPB);
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_key_limbs<canon::NSecp>), g, b, 0, s, (const u32*)dkeys, ds, dst, n);
+  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_key_limbs<canon::NP256>), g, b, 0, s, (const u32*)dkeys, ds, dst, n);
+  else hipLaunchKernelGGL(k_ced_sign_expand, g, b, 0, s, Messages{nullptr, nullptr, 0}, (const u32*)dkeys, ds, (u32*)nullptr, dst, n);
+  rc = launch_secret_comb(ctx, curve, ds, xy, c, n, s);
+  if (rc != FEC_OK) return rc;
+  const u32* cxy = xy;
+  const unsigned char* cst = dst;
+  if (curve == FEC_ED25519) hipLaunchKernelGGL(k_canon_encode_keys<0>, g, b, 0, s, cxy, cst, dout, n);
+  else if (out_len == 32) hipLaunchKernelGGL(k_canon_encode_keys<32>, g, b, 0, s, cxy, cst, dout, n);
+  else if (out_len == 33) hipLaunchKernelGGL(k_canon_encode_keys<33>, g, b, 0, s, cxy, cst, dout, n);
+  else hipLaunchKernelGGL(k_canon_encode_keys<65>, g, b, 0, s, cxy, cst, dout, n);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  return launch_secret_report(ctx, curve, c, s);
+}
+
+// ECDSA: nonce kernel -> secret comb -> finish.  d_digests != null: sign the digests; else hash the messages.
+// d_k_be != null (fec_canon_rfc6979_k): the nonce kernel alone.
+int launch_canon_ecdsa_sign(fec_ctx* ctx, int curve, const Messages& m, const uint8_t* d_digests, const uint8_t* d_keys,
+                            unsigned flags, uint8_t* d_sigs, uint8_t* d_k_be, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t s = sign_stream(ctx, stream);
+  SignArea a;
+  int rc = a.open(ctx, s, 3 * r256(n * 32) + r256(n * 64) + comb_area_bytes(n));
+  if (rc != FEC_OK) return rc;
+  u32 *ks = a.take<u32>(n * 32), *zs = a.take<u32>(n * 32), *ds = a.take<u32>(n * 32), *xy = a.take<u32>(n * 64);
+  CombArea c;
+  c.take(a, n);
+  if (hipMemsetAsync(c.flag, 0, 4, s) != hipSuccess) return FEC_E_DEVICE;
+  dim3 g(grid_for(n)), b(TPB);
+  if (curve == FEC_SECP256K1)
+    hipLaunchKernelGGL((k_canon_ecdsa_nonce<canon::NSecp>), g, b, 0, s, m, (const u32*)d_digests, (const u32*)d_keys, ks, zs, ds, (u32*)d_k_be, dst, n);
+  else
+    hipLaunchKernelGGL((k_canon_ecdsa_nonce<canon::NP256>), g, b, 0, s, m, (const u32*)d_digests, (const u32*)d_keys, ks, zs, ds, (u32*)d_k_be, dst, n);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  if (d_k_be) return FEC_OK;
+  rc = launch_secret_comb(ctx, curve, ks, xy, c, n, s);
+  if (rc != FEC_OK) return rc;
+  const size_t lanes = (n + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
+  const size_t stride = (lanes + 63) / 64 * 64;
+  dim3 gs(grid_for(stride));
+  if (curve == FEC_SECP256K1)
+    hipLaunchKernelGGL((k_canon_ecdsa_sign_finish<canon::NSecp>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, dst, n, stride);
+  else
+    hipLaunchKernelGGL((k_canon_ecdsa_sign_finish<canon::NP256>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, dst, n, stride);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  return launch_secret_report(ctx, curve, c, s);
+}
+
+// BIP-340: key -> P = d G -> nonce -> R = k' G -> finish; two comb passes, the nonce needs P
+int launch_canon_bip340_sign(fec_ctx* ctx, const Messages& m, const uint8_t* d_keys, const uint8_t* d_aux, uint8_t* d_sigs,
+                             unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t s = sign_stream(ctx, stream);
+  SignArea a;
+  int rc = a.open(ctx, s, 2 * r256(n * 32) + 2 * r256(n * 64) + comb_area_bytes(n));
+  if (rc != FEC_OK) return rc;
+  u32 *ds = a.take<u32>(n * 32), *ks = a.take<u32>(n * 32), *pxy = a.take<u32>(n * 64), *rxy = a.take<u32>(n * 64);
+  CombArea c;
+  c.take(a, n);
+  if (hipMemsetAsync(c.flag, 0, 4, s) != hipSuccess) return FEC_E_DEVICE;
+  dim3 g(grid_for(n)), b(TPB);
+  hipLaunchKernelGGL((k_canon_key_limbs<canon::NSecp>), g, b, 0, s, (const u32*)d_keys, ds, dst, n);
+  rc = launch_secret_comb(ctx, FEC_SECP256K1, ds, pxy, c, n, s);
+  if (rc != FEC_OK) return rc;
+  hipLaunchKernelGGL(k_canon_bip340_nonce, g, b, 0, s, m, (const u32*)d_aux, (const u32*)pxy, ds, ks, dst, n);
+  rc = launch_secret_comb(ctx, FEC_SECP256K1, ks, rxy, c, n, s);
+  if (rc != FEC_OK) return rc;
+  hipLaunchKernelGGL(k_canon_bip340_sign_finish, g, b, 0, s, m, (const u32*)ks, (const u32*)ds, (const u32*)pxy, (const u32*)rxy, (u32*)d_sigs, (const unsigned char*)dst, n);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  return launch_secret_report(ctx, FEC_SECP256K1, c, s);
+}
+
+// Ed25519: expand -> ONE comb pass over a_0 .. a_{n-1}, r_0 .. r_{n-1} -> finish
+int launch_canon_ed25519_sign(fec_ctx* ctx, const Messages& m, const uint8_t* d_seeds, uint8_t* d_sigs, uint8_t* d_pks,
+                              unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t s = sign_stream(ctx, stream);
+  SignArea a;
+  int rc = a.open(ctx, s, r256(2 * n * 32) + r256(2 * n * 64) + comb_area_bytes(2 * n));
+  if (rc != FEC_OK) return rc;
+  u32 *sc = a.take<u32>(2 * n * 32), *xy = a.take<u32>(2 * n * 64);
+  CombArea c;
+  c.take(a, 2 * n);
+  dim3 g(grid_for(n)), b(TPB);
+  hipLaunchKernelGGL(k_ced_sign_expand, g, b, 0, s, m, (const u32*)d_seeds, sc, sc + n * 8, dst, n);
+  rc = launch_secret_comb(ctx, FEC_ED25519, sc, xy, c, 2 * n, s);
+  if (rc != FEC_OK) return rc;
+  hipLaunchKernelGGL(k_ced_sign_finish, g, b, 0, s, m, (const u32*)xy, (const u32*)sc, (const u32*)(sc + n * 8), (u32*)d_sigs, (u32*)d_pks, (const unsigned char*)dst, n);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+
 }  // namespace
 
 extern "C" {
@@ -547,6 +745,146 @@ int fec_canon_decompress(fec_ctx* ctx, fec_curve curve, const uint8_t* in, size_
   const HostArray a[] = {input(in, pk_len), output(xy, 64), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_canon_decompress(c, curve, (const uint8_t*)d[0], pk_len, (u64*)d[1], (unsigned char*)d[2], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- the signing side: secrets in, signatures out (include/fecgpu_canon.h) ----------------------------------------
+int fec_canon_mul_base_secret_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, uint64_t* d_out_xy,
+                                  uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_scalars || !d_out_xy || !d_status)) return FEC_E_ARG;
+  if (!canon_curve_ok(curve)) return FEC_E_ARG;
+  if (!aligned16(d_scalars) || !aligned16(d_out_xy)) return FEC_E_ARG;
+  return launch_canon_mul_base_secret(ctx, curve, d_scalars, d_out_xy, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_mul_base_secret(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, uint64_t* out_xy, uint8_t* status,
+                              size_t n) try {
+  if (!ctx || (n && (!scalars || !out_xy || !status))) return FEC_E_ARG;
+  if (!canon_curve_ok(curve)) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(scalars, 32), secret_output(out_xy, 64), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_mul_base_secret(c, curve, (const u64*)d[0], (u64*)d[1], (unsigned char*)d[2], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_public_key_dev(fec_ctx* ctx, int scheme, const uint8_t* d_keys, uint8_t* d_out, size_t out_len,
+                             uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_keys || !d_out || !d_status)) return FEC_E_ARG;
+  if (scheme < 0 || scheme > kSchemeBip340 || !key_len_ok(scheme, out_len)) return FEC_E_ARG;
+  if (!aligned16(d_keys) || (out_len == 32 && !aligned16(d_out))) return FEC_E_ARG;
+  return launch_canon_public_key(ctx, scheme, d_keys, d_out, out_len, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_public_key(fec_ctx* ctx, int scheme, const uint8_t* keys, uint8_t* out, size_t out_len, uint8_t* status,
+                         size_t n) try {
+  if (!ctx || (n && (!keys || !out || !status))) return FEC_E_ARG;
+  if (scheme < 0 || scheme > kSchemeBip340 || !key_len_ok(scheme, out_len)) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(keys, 32), output(out, out_len), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_public_key(c, scheme, (const uint8_t*)d[0], (uint8_t*)d[1], out_len, (unsigned char*)d[2], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ecdsa_sign_digest_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_keys,
+                                    unsigned flags, uint8_t* d_sigs, uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_digests || !d_keys || !d_sigs || !d_status)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if ((flags & ~1u) || !aligned16(d_digests) || !aligned16(d_keys) || !aligned16(d_sigs)) return FEC_E_ARG;
+  return launch_canon_ecdsa_sign(ctx, curve, Messages{nullptr, nullptr, 0}, d_digests, d_keys, flags, d_sigs, nullptr, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ecdsa_sign_digest(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* keys, unsigned flags,
+                                uint8_t* sigs, uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!digests || !keys || !sigs || !status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (flags & ~1u) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(digests, 32), secret_input(keys, 32), secret_output(sigs, 64), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_ecdsa_sign(c, curve, Messages{nullptr, nullptr, 0}, (const uint8_t*)d[0], (const uint8_t*)d[1], flags,
+                                   (uint8_t*)d[2], nullptr, (unsigned char*)d[3], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ecdsa_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                                 size_t msg_len, const uint8_t* d_keys, unsigned flags, uint8_t* d_sigs, uint8_t* d_status,
+                                 size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_keys || !d_sigs || !d_status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if ((flags & ~1u) || !aligned16(d_keys) || !aligned16(d_sigs)) return FEC_E_ARG;
+  return launch_canon_ecdsa_sign(ctx, curve, m, nullptr, d_keys, flags, d_sigs, nullptr, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ecdsa_sign_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                             const uint8_t* keys, unsigned flags, uint8_t* sigs, uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!keys || !sigs || !status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (flags & ~1u) return FEC_E_ARG;
+  const HostArray a[] = {ragged(msg_off, 8), secret_input(keys, 32), secret_output(sigs, 64), output(status, 1)};
+  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_canon_ecdsa_sign(c, curve, m, nullptr, (const uint8_t*)d[1], flags, (uint8_t*)d[2], nullptr, (unsigned char*)d[3], cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_keys, uint8_t* d_k_out,
+                            uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_digests || !d_keys || !d_k_out || !d_status)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!aligned16(d_digests) || !aligned16(d_keys) || !aligned16(d_k_out)) return FEC_E_ARG;
+  return launch_canon_ecdsa_sign(ctx, curve, Messages{nullptr, nullptr, 0}, d_digests, d_keys, 0, nullptr, d_k_out, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* keys, uint8_t* k_out,
+                        uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!digests || !keys || !k_out || !status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  const HostArray a[] = {secret_input(digests, 32), secret_input(keys, 32), secret_output(k_out, 32), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_ecdsa_sign(c, curve, Messages{nullptr, nullptr, 0}, (const uint8_t*)d[0], (const uint8_t*)d[1], 0, nullptr,
+                                   (uint8_t*)d[2], (unsigned char*)d[3], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_bip340_sign_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                  const uint8_t* d_keys, const uint8_t* d_aux, uint8_t* d_sigs, uint8_t* d_status, size_t n,
+                                  void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_keys || !d_aux || !d_sigs || !d_status))) return FEC_E_ARG;
+  if (!aligned16(d_keys) || !aligned16(d_aux) || !aligned16(d_sigs)) return FEC_E_ARG;
+  return launch_canon_bip340_sign(ctx, m, d_keys, d_aux, d_sigs, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_bip340_sign_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* keys,
+                              const uint8_t* aux, uint8_t* sigs, uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!keys || !aux || !sigs || !status))) return FEC_E_ARG;
+  const HostArray a[] = {ragged(msg_off, 8), secret_input(keys, 32), secret_input(aux, 32), secret_output(sigs, 64), output(status, 1)};
+  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_canon_bip340_sign(c, m, (const uint8_t*)d[1], (const uint8_t*)d[2], (uint8_t*)d[3], (unsigned char*)d[4], cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ed25519_sign_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                   const uint8_t* d_seeds, uint8_t* d_sigs, uint8_t* d_pks_out, uint8_t* d_status, size_t n,
+                                   void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_seeds || !d_sigs || !d_status))) return FEC_E_ARG;
+  if (!aligned16(d_seeds) || !aligned16(d_sigs) || !aligned16(d_pks_out)) return FEC_E_ARG;
+  return launch_canon_ed25519_sign(ctx, m, d_seeds, d_sigs, d_pks_out, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ed25519_sign_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* seeds,
+                               uint8_t* sigs, uint8_t* pks_out, uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!seeds || !sigs || !status))) return FEC_E_ARG;
+  const HostArray a[] = {ragged(msg_off, 8), secret_input(seeds, 32), secret_output(sigs, 64), output(pks_out, 32), output(status, 1)};
+  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_canon_ed25519_sign(c, m, (const uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], (unsigned char*)d[4], cnt, st);
   });
 } FEC_ABI_CATCH_STATUS
 

@@ -162,7 +162,8 @@ int fec_canon_decompress_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_in,
 /* Arithmetic modulo the group order (n for secp256k1 / P-256, l for Ed25519) on any 256-bit inputs, results
  * in [0, order): op 0: out = a * b + c, op 1: out = a^-1 (0 for a = 0 mod order; b, c ignored).  With
  * fec_canon_mul_base this is the device side of signing, e.g. ECDSA  r = x(k G) mod n (a * 1 + 0),
- * s = k^-1 (z + r d);  EdDSA  S = h a + r (mod l).  Nonces and hashes are the caller's. */
+ * s = k^-1 (z + r d);  EdDSA  S = h a + r (mod l).  Nonces and hashes are the caller's: a vector-checking tool, not a
+ * signer.  The signers are at the end of this header. */
 int fec_canon_scalar_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a /* n*4 */,
                         const uint64_t* b /* n*4 */, const uint64_t* c /* n*4 */, uint64_t* out /* n*4 */, size_t n);
 
@@ -170,6 +171,90 @@ int fec_canon_scalar_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a
  * or FEC_F_INV; b is ignored for unary ops */
 int fec_canon_field_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a /* n*4 */,
                        const uint64_t* b /* n*4 */, uint64_t* out /* n*4 */, size_t n);
+
+/* ---- The signing side: a fixed-base multiplication for secret scalars, and signers from the message ----------------------
+ * Everything above takes public inputs (or accepts the warning at the top).  The calls below take keys, seeds and nonces.
+ * What they guarantee, stated by reading the code (canon_sign.hpp), not by a timing test: in every kernel on the signing
+ * path no load or store address, no branch and no trip count depends on a key, a seed, a nonce, a digit of one or an
+ * intermediate point, above the field layer.  The comb's table lookup reads every entry of a window and keeps the wanted one
+ * under a lane mask; the addition runs its general formula always and resolves an accumulator at infinity and a zero digit
+ * by selects; range tests are a comparison and a select.  Not removed: the field layer keeps its rare wave-uniform legs
+ * (secp256k1's mul sends a lane with a column word >= 2^32 - 4096, one multiplication in 2^17, down a general path; its
+ * add / sub and P-256's reduction have a wrapped-once-more leg; Ed25519's reduction finishes a lane that lands in
+ * [p, 2^255) separately), each of which is a data-dependent branch.  So the path is not called constant-time.
+ * The RFC 6979 chain draws again when a candidate is not below the order (probability below 2^-32), as the RFC itself does.
+ * Host forms stage keys and signatures as secrets: staging and every work-area region that held a key, a nonce or an
+ * un-normalised point is cleared on every way out; the *_dev forms clear their work area behind their last kernel.
+ * Host forms are chunked by fec_ctx_set_chunk and sharded over a multi-device ctx.  *_dev forms: every record array 16-byte
+ * aligned, d_msg_off 8-byte aligned, per-lane range check, FEC_E_UNSUPPORTED on a multi-device ctx. */
+
+#define FEC_CANON_BAD_SCALAR 3 /* fec_canon_mul_base_secret: a Weierstrass scalar outside [1, n); out_xy[i] = 0 */
+#define FEC_CANON_BAD_KEY 6    /* signers, fec_canon_public_key: key 0 or >= n; the outputs are zeros */
+#define FEC_CANON_SIGN_LOW_S 1u /* flags bit 0 of the ECDSA signers: s > n/2 is replaced by n - s */
+
+/* fec_canon_mul_base for secret scalars: the same limbs in, the same affine x, y out, identical results for every scalar
+ * both accept.  FEC_SECP256K1 / FEC_P256 accept k in [1, n), anything else gets FEC_CANON_BAD_SCALAR and zeros; FEC_ED25519
+ * accepts any 256-bit k.  4-bit comb held in LDS (built once per ctx and device, whatever FEC_CANON_COMB4 says): 64 scanned
+ * lookups and 64 additions.  Should the comb ever meet P == +-Q -- impossible for k in [1, n) -- the call (or the next
+ * fec_ctx_check) returns FEC_E_LAUNCH. */
+int fec_canon_mul_base_secret(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars /* n*4 */, uint64_t* out_xy /* n*8 */,
+                              uint8_t* status /* n */, size_t n);
+int fec_canon_mul_base_secret_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, uint64_t* d_out_xy,
+                                  uint8_t* d_status, size_t n, void* stream);
+
+/* Public keys through the secret comb.  scheme: FEC_SECP256K1 / FEC_P256 = ECDSA, SEC 1 encoding, out_len 33 or 65;
+ * FEC_CANON_SCHEME_BIP340 = 32 bytes x-only; FEC_ED25519 = 32 bytes from the seed (RFC 8032 5.1.5).  keys: 32 bytes each,
+ * big-endian (Ed25519: the seed).  status[i]: 0, or FEC_CANON_BAD_KEY with zeros.  Another out_len: FEC_E_ARG. */
+#define FEC_CANON_SCHEME_BIP340 3
+int fec_canon_public_key(fec_ctx* ctx, int scheme, const uint8_t* keys /* n*32 */, uint8_t* out /* n*out_len */,
+                         size_t out_len, uint8_t* status /* n */, size_t n);
+int fec_canon_public_key_dev(fec_ctx* ctx, int scheme, const uint8_t* d_keys, uint8_t* d_out, size_t out_len,
+                             uint8_t* d_status, size_t n, void* stream);
+
+/* Signers.  status[i]: 0 success; FEC_CANON_BAD_KEY; 4 bad message range (*_dev only); 5: the nonce chain hit its retry
+ * bound (128 draws), the BIP-340 nonce was 0, or r = 0 or s = 0 -- RFC 6979 section 3.2 step h.3 would draw again, this is
+ * reported instead, and it is unobservable (below 2^-128 per signature).  Every status but 0 comes with a zero signature.
+ * A refused key runs the pipeline on the key 1 and its results are dropped by select.
+ *
+ * ECDSA with SHA-256 and RFC 6979 nonces, FEC_SECP256K1 and FEC_P256 (FEC_ED25519: FEC_E_UNSUPPORTED).  keys: 32 bytes
+ * big-endian; sigs: r || s big-endian.  The nonce is the standard's: generate_k(int2octets(d), bits2octets(h1), n) with
+ * bits2octets(h1) = h1 mod n; z = h1 mod n, r = x(k G) mod n, s = k^-1 (z + r d).  _digest takes h1 as given (what a Bitcoin
+ * caller has), _msg computes h1 = SHA-256(msg_i).  flags: FEC_CANON_SIGN_LOW_S or 0 (other bits: FEC_E_ARG).
+ * fec_canon_rfc6979_k: the nonce alone, 32 bytes big-endian, for checking published nonces. */
+int fec_canon_ecdsa_sign_digest(fec_ctx* ctx, fec_curve curve, const uint8_t* digests /* n*32 */, const uint8_t* keys /* n*32 */,
+                                unsigned flags, uint8_t* sigs /* n*64 */, uint8_t* status /* n */, size_t n);
+int fec_canon_ecdsa_sign_digest_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_keys,
+                                    unsigned flags, uint8_t* d_sigs, uint8_t* d_status, size_t n, void* stream);
+int fec_canon_ecdsa_sign_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */,
+                             size_t msg_len, const uint8_t* keys /* n*32 */, unsigned flags, uint8_t* sigs /* n*64 */,
+                             uint8_t* status /* n */, size_t n);
+int fec_canon_ecdsa_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off,
+                                 size_t msg_len, const uint8_t* d_keys, unsigned flags, uint8_t* d_sigs, uint8_t* d_status,
+                                 size_t n, void* stream);
+int fec_canon_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint8_t* digests /* n*32 */, const uint8_t* keys /* n*32 */,
+                        uint8_t* k_out /* n*32 */, uint8_t* status /* n */, size_t n);
+int fec_canon_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_keys, uint8_t* d_k_out,
+                            uint8_t* d_status, size_t n, void* stream);
+
+/* BIP-340 default signing (secp256k1), a message of any length: P = d G, d negated on odd y; t = d xor H_aux(aux),
+ * k' = H_nonce(t || P.x || m) mod n, R = k' G, k negated on odd y; sig = R.x || (k + H_challenge(R.x || P.x || m) d) mod n.
+ * Two comb passes (the nonce needs P). */
+int fec_canon_bip340_sign_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                              const uint8_t* keys /* n*32 */, const uint8_t* aux /* n*32 */, uint8_t* sigs /* n*64 */,
+                              uint8_t* status /* n */, size_t n);
+int fec_canon_bip340_sign_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                  const uint8_t* d_keys, const uint8_t* d_aux, uint8_t* d_sigs, uint8_t* d_status, size_t n,
+                                  void* stream);
+
+/* Ed25519, pure (RFC 8032 section 5.1.6): h = SHA-512(seed), a = clamp(h[0..32)), r = SHA-512(h[32..64) || M) mod l; A = a B
+ * and R = r B go through one comb launch over 2n scalars; S = r + SHA-512(R || A || M) a mod l.  pks_out: the public keys,
+ * or NULL.  Every seed is a key: status is 0 (or 4). */
+int fec_canon_ed25519_sign_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                               const uint8_t* seeds /* n*32 */, uint8_t* sigs /* n*64 */, uint8_t* pks_out /* n*32 or NULL */,
+                               uint8_t* status /* n */, size_t n);
+int fec_canon_ed25519_sign_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                   const uint8_t* d_seeds, uint8_t* d_sigs, uint8_t* d_pks_out, uint8_t* d_status, size_t n,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "fecgpu.h"
@@ -1109,6 +1110,88 @@ inline PointResult decompress(GpuContext& ctx, const std::vector<uint8_t>& keys,
   const size_t n = keys.size() / key_len;
   PointResult r{std::vector<Affine>(n), std::vector<uint8_t>(n)};
   check(fec_canon_decompress(ctx.raw(), C, keys.data(), key_len, reinterpret_cast<uint64_t*>(r.points.data()), r.status.data(), n));
+  return r;
+}
+// ---- the signing side: secrets in, signatures out (see fecgpu_canon.h for what the secret path guarantees) ----
+struct SignResult {
+  std::vector<eddsa::Bytes64> sigs;
+  std::vector<uint8_t> status;   // 0, FEC_CANON_BAD_KEY, 5 (unobservable): see fecgpu_canon.h
+};
+// mul_base for secret scalars: no table lookup indexed by a digit of the scalar, no branch on one
+template <fec_curve C>
+inline PointResult mul_base_secret(GpuContext& ctx, const std::vector<Limbs>& scalars) {
+  PointResult r{std::vector<Affine>(scalars.size()), std::vector<uint8_t>(scalars.size())};
+  check(fec_canon_mul_base_secret(ctx.raw(), C, reinterpret_cast<const uint64_t*>(scalars.data()),
+                                  reinterpret_cast<uint64_t*>(r.points.data()), r.status.data(), scalars.size()));
+  return r;
+}
+// public keys: scheme = FEC_SECP256K1 / FEC_P256 (SEC 1, key_len 33 or 65), FEC_CANON_SCHEME_BIP340 (32, x-only) or
+// FEC_ED25519 (32, from the seed); {n * key_len bytes, status}
+inline std::pair<std::vector<uint8_t>, std::vector<uint8_t>> public_key(GpuContext& ctx, int scheme, const std::vector<eddsa::Bytes32>& keys,
+                                                                        size_t key_len) {
+  const size_t n = keys.size();
+  std::vector<uint8_t> out(n * key_len), st(n);
+  check(fec_canon_public_key(ctx.raw(), scheme, reinterpret_cast<const uint8_t*>(keys.data()), out.data(), key_len, st.data(), n));
+  return {std::move(out), std::move(st)};
+}
+// ECDSA with RFC 6979 nonces over given digests / from the message (SHA-256); flags: FEC_CANON_SIGN_LOW_S or 0
+template <fec_curve C>
+inline SignResult ecdsa_sign_digest(GpuContext& ctx, const std::vector<eddsa::Bytes32>& digests, const std::vector<eddsa::Bytes32>& keys,
+                                    unsigned flags = 0) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "ECDSA is offered on secp256k1 and P-256");
+  const size_t n = digests.size();
+  if (keys.size() != n) throw Error(FEC_E_ARG);
+  SignResult r{std::vector<eddsa::Bytes64>(n), std::vector<uint8_t>(n)};
+  check(fec_canon_ecdsa_sign_digest(ctx.raw(), C, reinterpret_cast<const uint8_t*>(digests.data()), reinterpret_cast<const uint8_t*>(keys.data()),
+                                    flags, reinterpret_cast<uint8_t*>(r.sigs.data()), r.status.data(), n));
+  return r;
+}
+template <fec_curve C>
+inline SignResult ecdsa_sign_msg(GpuContext& ctx, const std::vector<std::string>& msgs, const std::vector<eddsa::Bytes32>& keys,
+                                 unsigned flags = 0) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "ECDSA is offered on secp256k1 and P-256");
+  const size_t n = msgs.size();
+  if (keys.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  SignResult r{std::vector<eddsa::Bytes64>(n), std::vector<uint8_t>(n)};
+  check(fec_canon_ecdsa_sign_msg(ctx.raw(), C, m.bytes.data(), m.off.data(), m.bytes.size(), reinterpret_cast<const uint8_t*>(keys.data()), flags,
+                                 reinterpret_cast<uint8_t*>(r.sigs.data()), r.status.data(), n));
+  return r;
+}
+// the RFC 6979 nonces alone, 32 bytes big-endian each
+template <fec_curve C>
+inline std::pair<std::vector<eddsa::Bytes32>, std::vector<uint8_t>> rfc6979_k(GpuContext& ctx, const std::vector<eddsa::Bytes32>& digests,
+                                                                              const std::vector<eddsa::Bytes32>& keys) {
+  const size_t n = digests.size();
+  if (keys.size() != n) throw Error(FEC_E_ARG);
+  std::vector<eddsa::Bytes32> k(n);
+  std::vector<uint8_t> st(n);
+  check(fec_canon_rfc6979_k(ctx.raw(), C, reinterpret_cast<const uint8_t*>(digests.data()), reinterpret_cast<const uint8_t*>(keys.data()),
+                            reinterpret_cast<uint8_t*>(k.data()), st.data(), n));
+  return {std::move(k), std::move(st)};
+}
+// BIP-340 default signing
+inline SignResult bip340_sign_msg(GpuContext& ctx, const std::vector<std::string>& msgs, const std::vector<eddsa::Bytes32>& keys,
+                                  const std::vector<eddsa::Bytes32>& aux) {
+  const size_t n = msgs.size();
+  if (keys.size() != n || aux.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  SignResult r{std::vector<eddsa::Bytes64>(n), std::vector<uint8_t>(n)};
+  check(fec_canon_bip340_sign_msg(ctx.raw(), m.bytes.data(), m.off.data(), m.bytes.size(), reinterpret_cast<const uint8_t*>(keys.data()),
+                                  reinterpret_cast<const uint8_t*>(aux.data()), reinterpret_cast<uint8_t*>(r.sigs.data()), r.status.data(), n));
+  return r;
+}
+// RFC 8032 Ed25519 (pure); public_keys, when given, receives the n keys
+inline SignResult ed25519_sign_msg(GpuContext& ctx, const std::vector<std::string>& msgs, const std::vector<eddsa::Bytes32>& seeds,
+                                   std::vector<eddsa::Bytes32>* public_keys = nullptr) {
+  const size_t n = msgs.size();
+  if (seeds.size() != n) throw Error(FEC_E_ARG);
+  const eddsa::detail::Messages m(msgs);
+  SignResult r{std::vector<eddsa::Bytes64>(n), std::vector<uint8_t>(n)};
+  if (public_keys) public_keys->resize(n);
+  check(fec_canon_ed25519_sign_msg(ctx.raw(), m.bytes.data(), m.off.data(), m.bytes.size(), reinterpret_cast<const uint8_t*>(seeds.data()),
+                                   reinterpret_cast<uint8_t*>(r.sigs.data()), public_keys ? reinterpret_cast<uint8_t*>(public_keys->data()) : nullptr,
+                                   r.status.data(), n));
   return r;
 }
 }  // namespace canon

@@ -1655,3 +1655,194 @@ pub mod hooks {
         Ok((name, cus, khz))
     }
 }
+
+/// Canonical-math mode, the signing side (include/fecgpu_canon.h): the STANDARDS' signers -- ECDSA with SHA-256 and
+/// RFC 6979 nonces on secp256k1 and P-256, BIP-340, RFC 8032 Ed25519 -- and the public keys of each, from key, seed
+/// and message bytes to signature bytes on the GPU.  NOT reference parity: forge-ec's own signers are the calls above.
+/// The fixed-base multiplication under them reads every entry of a table window and keeps the wanted one by a select,
+/// and its addition has no exceptional-case branches: no secret-indexed memory access and no secret-dependent branch
+/// above the field layer (what that leaves is said in the header).  The library clears its device copies of keys, nonces
+/// and un-normalised points before a call returns.
+pub mod canon_sign {
+    use super::*;
+
+    /// `status[i]` of the signing calls.
+    #[derive(Clone, Copy, Debug, PartialEq, Eq)]
+    pub enum SignStatus {
+        /// a signature was made
+        Signed,
+        /// the key is 0 or not below the group order: a zero signature
+        BadKey,
+        /// the nonce chain hit its retry bound, or r = 0 or s = 0 (unobservable): a zero signature
+        Retry,
+        /// a `*_dev` caller's message range was bad
+        BadRange,
+    }
+    fn status_of(b: u8) -> SignStatus {
+        match b {
+            0 => SignStatus::Signed,
+            6 => SignStatus::BadKey,
+            4 => SignStatus::BadRange,
+            _ => SignStatus::Retry,
+        }
+    }
+    /// `flags` bit 0 of the ECDSA signers: s > n/2 is replaced by n - s.
+    pub const SIGN_LOW_S: c_uint = 1;
+    /// `scheme` of [`public_key_batch`] for 32-byte x-only BIP-340 keys (the other schemes are the curve ids).
+    pub const SCHEME_BIP340: c_int = 3;
+
+    // ---- include/fecgpu_canon.h, the signing side, symbol for symbol ----
+    #[link(name = "fecgpu")]
+    extern "C" {
+        fn fec_canon_mul_base_secret(ctx: *mut FecCtx, curve: c_int, scalars: *const u64, out_xy: *mut u64, status: *mut u8, n: usize) -> c_int;
+        fn fec_canon_mul_base_secret_dev(ctx: *mut FecCtx, curve: c_int, d_scalars: *const u64, d_out_xy: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+        fn fec_canon_public_key(ctx: *mut FecCtx, scheme: c_int, keys: *const u8, out: *mut u8, out_len: usize, status: *mut u8, n: usize) -> c_int;
+        fn fec_canon_public_key_dev(ctx: *mut FecCtx, scheme: c_int, d_keys: *const u8, d_out: *mut u8, out_len: usize, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+        fn fec_canon_ecdsa_sign_digest(ctx: *mut FecCtx, curve: c_int, digests: *const u8, keys: *const u8, flags: c_uint, sigs: *mut u8, status: *mut u8, n: usize) -> c_int;
+        fn fec_canon_ecdsa_sign_digest_dev(ctx: *mut FecCtx, curve: c_int, d_digests: *const u8, d_keys: *const u8, flags: c_uint, d_sigs: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+        fn fec_canon_ecdsa_sign_msg(ctx: *mut FecCtx, curve: c_int, msgs: *const u8, msg_off: *const u64, msg_len: usize, keys: *const u8, flags: c_uint, sigs: *mut u8, status: *mut u8, n: usize) -> c_int;
+        fn fec_canon_ecdsa_sign_msg_dev(ctx: *mut FecCtx, curve: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_keys: *const u8, flags: c_uint, d_sigs: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+        fn fec_canon_rfc6979_k(ctx: *mut FecCtx, curve: c_int, digests: *const u8, keys: *const u8, k_out: *mut u8, status: *mut u8, n: usize) -> c_int;
+        fn fec_canon_rfc6979_k_dev(ctx: *mut FecCtx, curve: c_int, d_digests: *const u8, d_keys: *const u8, d_k_out: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+        fn fec_canon_bip340_sign_msg(ctx: *mut FecCtx, msgs: *const u8, msg_off: *const u64, msg_len: usize, keys: *const u8, aux: *const u8, sigs: *mut u8, status: *mut u8, n: usize) -> c_int;
+        fn fec_canon_bip340_sign_msg_dev(ctx: *mut FecCtx, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_keys: *const u8, d_aux: *const u8, d_sigs: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+        fn fec_canon_ed25519_sign_msg(ctx: *mut FecCtx, msgs: *const u8, msg_off: *const u64, msg_len: usize, seeds: *const u8, sigs: *mut u8, pks_out: *mut u8, status: *mut u8, n: usize) -> c_int;
+        fn fec_canon_ed25519_sign_msg_dev(ctx: *mut FecCtx, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_seeds: *const u8, d_sigs: *mut u8, d_pks_out: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
+    }
+
+    fn signed(sig: Vec<[u8; 64]>, status: Vec<u8>) -> Vec<([u8; 64], SignStatus)> {
+        sig.into_iter().zip(status).map(|(s, b)| (s, status_of(b))).collect()
+    }
+
+    /// `scalars[i] * G` as affine `[x, y]` limbs of the real curve, for secret scalars; `None` where a Weierstrass scalar
+    /// is outside [1, n).  `curve`: 0 secp256k1, 1 P-256, 2 Ed25519.
+    pub fn mul_base_secret_batch(ctx: &mut GpuContext, curve: c_int, scalars: &[[u64; 4]]) -> Result<Vec<Option<[u64; 8]>>> {
+        let n = scalars.len();
+        let (mut xy, mut status) = (vec![[0u64; 8]; n], vec![0u8; n]);
+        // SAFETY: n scalars of 4 limbs, n points of 8 limbs, n status bytes.
+        check(unsafe { fec_canon_mul_base_secret(ctx.raw, curve, scalars.as_ptr().cast(), xy.as_mut_ptr().cast(), status.as_mut_ptr(), n) })?;
+        Ok((0..n).map(|i| if status[i] == 0 { Some(xy[i]) } else { None }).collect())
+    }
+
+    /// Public keys: `scheme` 0 / 1 = SEC 1 keys of secp256k1 / P-256 (`key_len` 33 or 65), [`SCHEME_BIP340`] = 32 bytes
+    /// x-only, 2 = Ed25519 from the seed (32).  `None` for a key that is 0 or not below the order.
+    pub fn public_key_batch(ctx: &mut GpuContext, scheme: c_int, keys: &[[u8; 32]], key_len: usize) -> Result<Vec<Option<Vec<u8>>>> {
+        let n = keys.len();
+        let (mut out, mut status) = (vec![0u8; n * key_len], vec![0u8; n]);
+        // SAFETY: n keys of 32 bytes, n * key_len output bytes, n status bytes.
+        check(unsafe { fec_canon_public_key(ctx.raw, scheme, keys.as_ptr().cast(), out.as_mut_ptr(), key_len, status.as_mut_ptr(), n) })?;
+        Ok((0..n).map(|i| if status[i] == 0 { Some(out[i * key_len..(i + 1) * key_len].to_vec()) } else { None }).collect())
+    }
+
+    /// ECDSA (RFC 6979 nonces) over given 32-byte digests: r || s big-endian.  `curve`: 0 secp256k1, 1 P-256.
+    pub fn ecdsa_sign_digest_batch(ctx: &mut GpuContext, curve: c_int, digests: &[[u8; 32]], keys: &[[u8; 32]], flags: c_uint) -> Result<Vec<([u8; 64], SignStatus)>> {
+        let n = digests.len();
+        if keys.len() != n {
+            return Err(Error::ValidationError);
+        }
+        let (mut sig, mut status) = (vec![[0u8; 64]; n], vec![0u8; n]);
+        // SAFETY: n digests and n keys of 32 bytes, n signatures of 64 bytes, n status bytes.
+        check(unsafe { fec_canon_ecdsa_sign_digest(ctx.raw, curve, digests.as_ptr().cast(), keys.as_ptr().cast(), flags, sig.as_mut_ptr().cast(), status.as_mut_ptr(), n) })?;
+        Ok(signed(sig, status))
+    }
+
+    /// ECDSA with SHA-256 (RFC 6979 nonces) from the message.
+    pub fn ecdsa_sign_msg_batch(ctx: &mut GpuContext, curve: c_int, msgs: &[&[u8]], keys: &[[u8; 32]], flags: c_uint) -> Result<Vec<([u8; 64], SignStatus)>> {
+        let n = msgs.len();
+        if keys.len() != n {
+            return Err(Error::ValidationError);
+        }
+        let (buf, off) = pack_messages(msgs);
+        let (mut sig, mut status) = (vec![[0u8; 64]; n], vec![0u8; n]);
+        // SAFETY: off holds n + 1 offsets into buf; n keys, n signatures, n status bytes.
+        check(unsafe { fec_canon_ecdsa_sign_msg(ctx.raw, curve, buf.as_ptr(), off.as_ptr(), buf.len(), keys.as_ptr().cast(), flags, sig.as_mut_ptr().cast(), status.as_mut_ptr(), n) })?;
+        Ok(signed(sig, status))
+    }
+
+    /// The RFC 6979 nonces alone, 32 bytes big-endian each (for checking published nonces).
+    pub fn rfc6979_k_batch(ctx: &mut GpuContext, curve: c_int, digests: &[[u8; 32]], keys: &[[u8; 32]]) -> Result<Vec<([u8; 32], SignStatus)>> {
+        let n = digests.len();
+        if keys.len() != n {
+            return Err(Error::ValidationError);
+        }
+        let (mut k, mut status) = (vec![[0u8; 32]; n], vec![0u8; n]);
+        // SAFETY: n records of 32 bytes behind every pointer, n status bytes.
+        check(unsafe { fec_canon_rfc6979_k(ctx.raw, curve, digests.as_ptr().cast(), keys.as_ptr().cast(), k.as_mut_ptr().cast(), status.as_mut_ptr(), n) })?;
+        Ok(k.into_iter().zip(status).map(|(x, b)| (x, status_of(b))).collect())
+    }
+
+    /// BIP-340 default signing with the caller's auxiliary randomness.
+    pub fn bip340_sign_msg_batch(ctx: &mut GpuContext, msgs: &[&[u8]], keys: &[[u8; 32]], aux: &[[u8; 32]]) -> Result<Vec<([u8; 64], SignStatus)>> {
+        let n = msgs.len();
+        if keys.len() != n || aux.len() != n {
+            return Err(Error::ValidationError);
+        }
+        let (buf, off) = pack_messages(msgs);
+        let (mut sig, mut status) = (vec![[0u8; 64]; n], vec![0u8; n]);
+        // SAFETY: off holds n + 1 offsets into buf; n keys, n aux records, n signatures, n status bytes.
+        check(unsafe { fec_canon_bip340_sign_msg(ctx.raw, buf.as_ptr(), off.as_ptr(), buf.len(), keys.as_ptr().cast(), aux.as_ptr().cast(), sig.as_mut_ptr().cast(), status.as_mut_ptr(), n) })?;
+        Ok(signed(sig, status))
+    }
+
+    /// RFC 8032 Ed25519 (pure): the signatures and the public keys of the seeds.
+    pub fn ed25519_sign_msg_batch(ctx: &mut GpuContext, msgs: &[&[u8]], seeds: &[[u8; 32]]) -> Result<Vec<([u8; 64], [u8; 32])>> {
+        let n = msgs.len();
+        if seeds.len() != n {
+            return Err(Error::ValidationError);
+        }
+        let (buf, off) = pack_messages(msgs);
+        let (mut sig, mut pk, mut status) = (vec![[0u8; 64]; n], vec![[0u8; 32]; n], vec![0u8; n]);
+        // SAFETY: off holds n + 1 offsets into buf; n seeds, n signatures, n keys, n status bytes.
+        check(unsafe { fec_canon_ed25519_sign_msg(ctx.raw, buf.as_ptr(), off.as_ptr(), buf.len(), seeds.as_ptr().cast(), sig.as_mut_ptr().cast(), pk.as_mut_ptr().cast(), status.as_mut_ptr(), n) })?;
+        Ok(sig.into_iter().zip(pk).collect())
+    }
+
+    /// The device-pointer forms: one device, the caller's stream, every record array 16-byte aligned, `d_msg_off`
+    /// 8-byte aligned; a lane with a bad message range gets status 4.  Results are ready once the stream has run.
+    pub mod dev {
+        use super::*;
+
+        /// `fec_canon_mul_base_secret_dev`.
+        /// # Safety
+        /// device pointers to n scalars (4 limbs), n points (8 limbs), n status bytes
+        pub unsafe fn mul_base_secret(ctx: &mut GpuContext, curve: c_int, d_scalars: *const u64, d_out_xy: *mut u64, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+            check(fec_canon_mul_base_secret_dev(ctx.raw, curve, d_scalars, d_out_xy, d_status, n, stream))
+        }
+        /// `fec_canon_public_key_dev`.
+        /// # Safety
+        /// device pointers to n keys (32 bytes), n * out_len output bytes, n status bytes
+        pub unsafe fn public_key(ctx: &mut GpuContext, scheme: c_int, d_keys: *const u8, d_out: *mut u8, out_len: usize, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+            check(fec_canon_public_key_dev(ctx.raw, scheme, d_keys, d_out, out_len, d_status, n, stream))
+        }
+        /// `fec_canon_ecdsa_sign_digest_dev`.
+        /// # Safety
+        /// device pointers to n digests and n keys (32 bytes), n signatures (64 bytes), n status bytes
+        pub unsafe fn ecdsa_sign_digest(ctx: &mut GpuContext, curve: c_int, d_digests: *const u8, d_keys: *const u8, flags: c_uint, d_sigs: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+            check(fec_canon_ecdsa_sign_digest_dev(ctx.raw, curve, d_digests, d_keys, flags, d_sigs, d_status, n, stream))
+        }
+        /// `fec_canon_ecdsa_sign_msg_dev`.
+        /// # Safety
+        /// device pointers: msg_len message bytes, n + 1 offsets, n keys, n signatures, n status bytes
+        pub unsafe fn ecdsa_sign_msg(ctx: &mut GpuContext, curve: c_int, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_keys: *const u8, flags: c_uint, d_sigs: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+            check(fec_canon_ecdsa_sign_msg_dev(ctx.raw, curve, d_msgs, d_msg_off, msg_len, d_keys, flags, d_sigs, d_status, n, stream))
+        }
+        /// `fec_canon_rfc6979_k_dev`.
+        /// # Safety
+        /// device pointers to n records of 32 bytes each, n status bytes
+        pub unsafe fn rfc6979_k(ctx: &mut GpuContext, curve: c_int, d_digests: *const u8, d_keys: *const u8, d_k_out: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+            check(fec_canon_rfc6979_k_dev(ctx.raw, curve, d_digests, d_keys, d_k_out, d_status, n, stream))
+        }
+        /// `fec_canon_bip340_sign_msg_dev`.
+        /// # Safety
+        /// device pointers: msg_len message bytes, n + 1 offsets, n keys, n aux records, n signatures, n status bytes
+        pub unsafe fn bip340_sign_msg(ctx: &mut GpuContext, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_keys: *const u8, d_aux: *const u8, d_sigs: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+            check(fec_canon_bip340_sign_msg_dev(ctx.raw, d_msgs, d_msg_off, msg_len, d_keys, d_aux, d_sigs, d_status, n, stream))
+        }
+        /// `fec_canon_ed25519_sign_msg_dev`; `d_pks_out` may be null.
+        /// # Safety
+        /// device pointers: msg_len message bytes, n + 1 offsets, n seeds, n signatures, n keys or null, n status bytes
+        pub unsafe fn ed25519_sign_msg(ctx: &mut GpuContext, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_seeds: *const u8, d_sigs: *mut u8, d_pks_out: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> Result<()> {
+            check(fec_canon_ed25519_sign_msg_dev(ctx.raw, d_msgs, d_msg_off, msg_len, d_seeds, d_sigs, d_pks_out, d_status, n, stream))
+        }
+    }
+}

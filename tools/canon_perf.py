@@ -15,6 +15,18 @@ the after-the-hash verifier has to hash (the bare message for ECDSA, T || T || r
 for Ed25519) plus that verifier on limb arrays.  Wall clock around a device synchronise, median and spread (max - min) of
 `reps` samples; the whole set of rows is measured twice (pass 0, pass 1), so the run-to-run spread shows.  Then
 fec_canon_decompress_dev alone and the three host-pointer forms (32-byte messages, PCIe included).
+
+The signing side (fec_canon_mul_base_secret_dev, the *_sign_*_dev calls), by the same method:
+
+    python tools/canon_perf.py sign [log2_n] [reps] [out.jsonl]
+
+"scan" rows: the secret comb against fec_canon_mul_base_dev on a ctx made with FEC_CANON_COMB4=1 (the same table, the same
+64 additions: the difference is the scan and the branch-free addition) and against the default 8-bit comb.  "sign" rows:
+each signer with 32- and 256-byte messages, alternating with its parts -- the secret comb pass(es) on as many scalars,
+fec_sha256_dev / fec_sha512_dev over the bytes the signer hashes, for ECDSA the parity-mode RFC 6979 kernel (the same chain;
+it hashes the message itself), and the fec_canon_scalar_op passes, which exist as host-pointer calls only and are reported
+apart (PCIe included).  "verify-valid" rows: fec_canon_*_verify_msg_dev over the signatures the signers just made, all
+of which must come out valid.  Last, one host-pointer row per signer.
 """
 import json
 import os
@@ -166,6 +178,138 @@ def main_msg():
                 f.write(json.dumps(r) + "\n")
 
 
+def main_sign():
+    logn = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    out_path = sys.argv[4] if len(sys.argv) > 4 else None
+    n = 1 << logn
+    ctx = F.Context(0)
+    os.environ["FEC_CANON_COMB4"] = "1"
+    ctx4 = F.Context(0)
+    del os.environ["FEC_CANON_COMB4"]
+    lib, h = ctx._lib, ctx._h
+    rng = np.random.default_rng(17)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()  # noqa: E731
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    def rounds(fns):
+        """each of fns three times, alternating; per fn the middle round's median and the largest spread"""
+        got = [[] for _ in fns]
+        for _ in range(3):
+            for g, fn in zip(got, fns):
+                g.append(_timed(fn, reps))
+        return [(sorted(g)[1][0], max(x[1] for x in g)) for g in got]
+
+    keys_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    keys_h[:, 0] &= 0x7F                     # big-endian keys below both orders, and not zero
+    keys_h[:, 31] |= 1
+    keys = dev(keys_h)
+    aux = dev(rng.integers(0, 256, size=(n, 32), dtype=np.uint8))
+    k_limbs = torch.from_numpy(synth.scalars(n, 0, 71).view(np.int64)).cuda()
+    k_limbs[:, 3] &= 0x0FFFFFFFFFFFFFFF      # below every order
+    k2 = torch.cat([k_limbs, k_limbs])
+    xy = torch.empty((2 * n, 8), dtype=torch.int64, device="cuda")
+    stat = torch.empty(2 * n, dtype=torch.uint8, device="cuda")
+    sigs = torch.empty((n, 64), dtype=torch.uint8, device="cuda")
+    digests = torch.empty(n * 64, dtype=torch.uint8, device="cuda")
+    res = torch.empty(n, dtype=torch.uint8, device="cuda")
+    pks = {33: torch.empty((n, 33), dtype=torch.uint8, device="cuda"), 32: torch.empty((n, 32), dtype=torch.uint8, device="cuda")}
+    knonce = torch.empty((n, 4), dtype=torch.int64, device="cuda")
+    for npass in range(2):
+        # ---- the price of the scan ----
+        for cname in ("secp256k1", "p256", "ed25519"):
+            c, c4 = CANON_CURVES[cname](ctx), CANON_CURVES[cname](ctx4)
+            sec, pub4, pub8 = rounds([
+                lambda: c.mul_base_secret_dev(k_limbs.data_ptr(), xy.data_ptr(), stat.data_ptr(), n, st),
+                lambda: c4.mul_base_dev(k_limbs.data_ptr(), xy.data_ptr(), stat.data_ptr(), n, st),
+                lambda: c.mul_base_dev(k_limbs.data_ptr(), xy.data_ptr(), stat.data_ptr(), n, st)])
+            emit({"row": "scan-" + cname, "pass": npass, "n": n, "reps": reps, "secret_ms": round(sec[0], 4), "secret_spread_ms": round(sec[1], 4),
+                  "comb4_ms": round(pub4[0], 4), "comb4_spread_ms": round(pub4[1], 4), "comb8_ms": round(pub8[0], 4),
+                  "comb8_spread_ms": round(pub8[1], 4), "secret_over_comb4": round(sec[0] / pub4[0], 4),
+                  "secret_over_comb8": round(sec[0] / pub8[0], 4), "M_per_s": round(n / sec[0] / 1e3, 3)})
+        # ---- each signer against its parts, then the verifier on what it made ----
+        for mlen in (32, 256):
+            msgs = dev(rng.integers(0, 256, size=n * mlen, dtype=np.uint8))
+            off = dev(np.arange(n + 1, dtype=np.uint64) * mlen)
+
+            def hashed(fn, prefix):
+                pm = dev(rng.integers(0, 256, size=n * (prefix + mlen), dtype=np.uint8))
+                po = dev(np.arange(n + 1, dtype=np.uint64) * (prefix + mlen))
+                return lambda: fn(pm.data_ptr(), po.data_ptr(), n * (prefix + mlen), digests.data_ptr(), None, n, st)
+
+            for name, cname in (("ecdsa-secp256k1", "secp256k1"), ("ecdsa-p256", "p256"), ("bip340", "secp256k1"), ("ed25519", "ed25519")):
+                c = CANON_CURVES[cname](ctx)
+                comb1 = lambda: c.mul_base_secret_dev(k_limbs.data_ptr(), xy.data_ptr(), stat.data_ptr(), n, st)  # noqa: E731
+                if name.startswith("ecdsa"):
+                    cid = 0 if cname == "secp256k1" else 1
+                    whole = lambda: c.ecdsa_sign_msg_dev(msgs.data_ptr(), off.data_ptr(), n * mlen, keys.data_ptr(), 1, sigs.data_ptr(), stat.data_ptr(), n, st)  # noqa: E731
+                    parts = [comb1, lambda: ctx.rfc6979_k_dev(cid, k_limbs.data_ptr(), msgs.data_ptr(), off.data_ptr(), n * mlen, knonce.data_ptr(),
+                                                              stat.data_ptr(), n, st)]
+                    scalar_passes = 4      # x mod n, k^-1, r d + z, the product
+                elif name == "bip340":
+                    whole = lambda: c.bip340_sign_msg_dev(msgs.data_ptr(), off.data_ptr(), n * mlen, keys.data_ptr(), aux.data_ptr(), sigs.data_ptr(), stat.data_ptr(), n, st)  # noqa: E731
+                    parts = [comb1, comb1, hashed(ctx.sha256_dev, 128), hashed(ctx.sha256_dev, 128)]    # nonce and challenge hashes (the 96-byte aux hash: not counted)
+                    scalar_passes = 1
+                else:
+                    whole = lambda: c.ed25519_sign_msg_dev(msgs.data_ptr(), off.data_ptr(), n * mlen, keys.data_ptr(), sigs.data_ptr(), pks[32].data_ptr(), stat.data_ptr(), n, st)  # noqa: E731
+                    parts = [lambda: c.mul_base_secret_dev(k2.data_ptr(), xy.data_ptr(), stat.data_ptr(), 2 * n, st),
+                             hashed(ctx.sha512_dev, 32), hashed(ctx.sha512_dev, 64)]
+                    scalar_passes = 1
+                got = rounds([whole] + parts)
+                w, ps = got[0], got[1:]
+                parts_ms, parts_spread = sum(p[0] for p in ps), sum(p[1] for p in ps)
+                emit({"row": "sign-" + name, "msg_bytes": mlen, "pass": npass, "n": n, "reps": reps, "sign_dev_ms": round(w[0], 4),
+                      "sign_dev_spread_ms": round(w[1], 4), "parts_ms": round(parts_ms, 4), "parts_spread_ms": round(parts_spread, 4),
+                      "parts_each_ms": [round(p[0], 4) for p in ps], "scalar_op_passes_not_included": scalar_passes,
+                      "sign_over_parts": round(w[0] / parts_ms, 4), "M_per_s": round(n / w[0] / 1e3, 3)})
+                # the verifier on these signatures: every one must be valid
+                torch.cuda.synchronize()
+                assert not bool(stat[:n].any()), name
+                if name.startswith("ecdsa"):
+                    c.public_key_dev(keys.data_ptr(), pks[33].data_ptr(), 33, stat.data_ptr(), n, st)
+                    ver = lambda: c.ecdsa_verify_msg_dev(msgs.data_ptr(), off.data_ptr(), n * mlen, sigs.data_ptr(), pks[33].data_ptr(), 33, res.data_ptr(), n, st)  # noqa: E731
+                elif name == "bip340":
+                    c.public_key_dev(keys.data_ptr(), pks[32].data_ptr(), 32, stat.data_ptr(), n, st, scheme=3)
+                    ver = lambda: c.bip340_verify_msg_dev(msgs.data_ptr(), off.data_ptr(), n * mlen, sigs.data_ptr(), pks[32].data_ptr(), res.data_ptr(), n, st)  # noqa: E731
+                else:
+                    ver = lambda: c.ed25519_verify_msg_dev(msgs.data_ptr(), off.data_ptr(), n * mlen, sigs.data_ptr(), pks[32].data_ptr(), res.data_ptr(), n, st)  # noqa: E731
+                ms, spread = _timed(ver, reps)
+                torch.cuda.synchronize()
+                assert int(res.sum()) == n, (name, int(res.sum()))
+                emit({"row": "verify-valid-" + name, "msg_bytes": mlen, "pass": npass, "n": n, "reps": reps, "ms": round(ms, 4),
+                      "spread_ms": round(spread, 4), "M_per_s": round(n / ms / 1e3, 3), "valid": n})
+    # ---- the scalar-field passes (host pointers only) and one host-pointer row per signer ----
+    a_h = synth.scalars(n, 0, 72)
+    for cname in ("secp256k1", "ed25519"):
+        c = CANON_CURVES[cname](ctx)
+        ms, spread = _timed(lambda: c.scalar_muladd(a_h, a_h, a_h), reps)
+        emit({"row": "scalar-op-muladd-host-" + cname, "n": n, "reps": reps, "ms": round(ms, 4), "spread_ms": round(spread, 4)})
+    ms, spread = _timed(lambda: CANON_CURVES["secp256k1"](ctx).scalar_inv(a_h), reps)
+    emit({"row": "scalar-op-inverse-host-secp256k1", "n": n, "reps": reps, "ms": round(ms, 4), "spread_ms": round(spread, 4)})
+    mlen = 32
+    msgs_h = rng.integers(0, 256, size=n * mlen, dtype=np.uint8)
+    off_h = np.arange(n + 1, dtype=np.uint64) * mlen
+    sig_h, st_h, pk_h = np.zeros((n, 64), np.uint8), np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8)
+    aux_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    p = lambda a: a.ctypes.data  # noqa: E731
+    for name, fn in (("ecdsa-secp256k1", lambda: lib.fec_canon_ecdsa_sign_msg(h, 0, p(msgs_h), p(off_h), n * mlen, p(keys_h), 1, p(sig_h), p(st_h), n)),
+                     ("bip340", lambda: lib.fec_canon_bip340_sign_msg(h, p(msgs_h), p(off_h), n * mlen, p(keys_h), p(aux_h), p(sig_h), p(st_h), n)),
+                     ("ed25519", lambda: lib.fec_canon_ed25519_sign_msg(h, p(msgs_h), p(off_h), n * mlen, p(keys_h), p(sig_h), p(pk_h), p(st_h), n))):
+        assert fn() == 0
+        ms, spread = _timed(fn, reps)
+        emit({"row": "host-sign-" + name, "msg_bytes": mlen, "n": n, "reps": reps, "ms": round(ms, 4), "spread_ms": round(spread, 4),
+              "M_per_s": round(n / ms / 1e3, 3)})
+    if out_path:
+        with open(out_path, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     logn = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -223,5 +367,7 @@ def main():
 
 if len(sys.argv) > 1 and sys.argv[1] == "msg":
     main_msg()
+elif len(sys.argv) > 1 and sys.argv[1] == "sign":
+    main_sign()
 else:
     main()
