@@ -1507,16 +1507,17 @@ FEC_DEV lmask ed_decode(const fe& enc, aff& out) {
   out.y = y;
   return uniform_mask(y_ok & (direct | twisted) & ~bad_sign);
 }
-// EdDSA verification, decoding half: A, R decoded; S < l; u2 = l - h (mod l)
+// EdDSA verification, decoding half: R decoded, A decoded and negated; S < l; u2 = h.  The verifier tests
+// S B + h (-A) == R, the cofactorless equation of RFC 8032.  The point is negated, not the scalar: A may carry a
+// component T of order 2, 4 or 8, and (l - h) T = (5 - h) T is not -h T.
 FEC_DEV lmask eddsa_prepare(const fe& a_enc, const fe& r_enc, const fe& s, const fe& h, aff& A, aff& R, fe& u2) {
   const fe l = edw::fe_words(0x5CF5D3EDu, 0x5812631Au, 0xA2F79CD6u, 0x14DEF9DEu, 0u, 0u, 0u, 0x10000000u);
   const lmask a_ok = ed_decode(a_enc, A), r_ok = ed_decode(r_enc, R);
+  A.x = FpEd::neg(A.x);
   fe t;
   const lmask s_lt = sub256(t, s, l);           // borrow  <=>  S < l
   const lmask h_lt = sub256(t, h, l);
-  fe neg;
-  sub256(neg, l, h);
-  u2 = fe_select(neg, fe_zero(), fe_is_zero(h));
+  u2 = h;
   return uniform_mask(a_ok & r_ok & s_lt & h_lt);
 }
 

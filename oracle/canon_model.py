@@ -236,7 +236,8 @@ def ed25519_decode(b):
 
 def eddsa_rfc8032_test1():
     """RFC 8032 section 7.1 TEST 1 (empty message): the signature test_standard_vectors.rs quotes.
-    S*B == R + h*A  <=>  S*B + (l - h)*A == R."""
+    S*B == R + h*A  <=>  S*B + h*(-A) == R  (the point is negated, not the scalar: (l - h)*A is -h*A only for A of
+    prime order)."""
     import hashlib
     E = ED25519
     _, pk = ED25519_RFC8032_TEST1
@@ -244,7 +245,7 @@ def eddsa_rfc8032_test1():
                         "5fb8821590a33bacc61e39701cf9b46bd25bf5f0595bbe24655141438e7a100b")
     A, Rp, S = ed25519_decode(pk), ed25519_decode(sig[:32]), int.from_bytes(sig[32:], "little")
     h = int.from_bytes(hashlib.sha512(sig[:32] + pk + b"").digest(), "little") % E.N
-    return E, S, (E.N - h) % E.N, A, lambda R: R == Rp
+    return E, S, h, E.neg(A), lambda R: R == Rp
 
 
 SIGNATURE_VECTORS = {"p256": ecdsa_p256_rfc6979_sample, "secp256k1": schnorr_bip340_vector0,

@@ -149,13 +149,14 @@ def ed25519_sign(seed, msg):
 
 
 def ed25519_verify(msg, sig, pk):
-    """Canonical encodings only, S < l, the cofactorless equation S B - h A == R."""
+    """Canonical encodings only, S < l, the cofactorless equation S B - h A == R.  -h A is h (-A): A may have a torsion
+    component, and (l - h) A is -h A only for A of prime order."""
     A, R = ed_decode(pk), ed_decode(sig[:32])
     S = int.from_bytes(sig[32:], "little")
     if A is None or R is None or S >= ED.N:
         return 0
     h = ed25519_challenge(sig[:32], pk, msg)
-    return 1 if ED.add(ED.mul(S, ED.G), ED.mul((ED.N - h) % ED.N, A)) == R else 0
+    return 1 if ED.add(ED.mul(S, ED.G), ED.mul(h, ED.neg(A))) == R else 0
 
 
 # ---- the published from-the-message vectors --------------------------------------------------------

@@ -565,7 +565,7 @@ def test_ed25519_decode_and_eddsa_prepare(emu):
         assert ok == (1 if want else 0), hex(enc)
         if want:
             assert (M.unlimbs(xy[:4]), M.unlimbs(xy[4:])) == want
-    # prepare: S < l, h < l, u2 = l - h
+    # prepare: S < l, h < l, u2 = h and the key negated: the verifier adds h (-A)
     axy, rxy, u2 = np.zeros(8, dtype=np.uint64), np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
     a_enc = int.from_bytes(E.encode(pts[3]), "little")
     r_enc = int.from_bytes(E.encode(pts[4]), "little")
@@ -573,8 +573,8 @@ def test_ed25519_decode_and_eddsa_prepare(emu):
         ok = emu.he_eddsa_prepare(_p(_arr(a_enc)), _p(_arr(r_enc)), _p(_arr(s)), _p(_arr(h)), _p(axy), _p(rxy), _p(u2))
         assert ok == want, (s, h)
         if want:
-            assert M.unlimbs(u2) == (-h) % E.N
-            assert (M.unlimbs(axy[:4]), M.unlimbs(axy[4:])) == pts[3] and (M.unlimbs(rxy[:4]), M.unlimbs(rxy[4:])) == pts[4]
+            assert M.unlimbs(u2) == h
+            assert (M.unlimbs(axy[:4]), M.unlimbs(axy[4:])) == E.neg(pts[3]) and (M.unlimbs(rxy[:4]), M.unlimbs(rxy[4:])) == pts[4]
 
 
 @pytest.mark.parametrize("name", ["secp256k1", "p256", "ed25519"])
