@@ -78,6 +78,7 @@ FEC_SDEV fe reduce512_general(const u32 t[16]) {
   fe r;
   lmask c3 = add256(r, w, addend);
   if (__builtin_expect(c3 != 0, 0)) {  // wrapped past 2^256 once more (probability ~2^-190): add c
+    FEC_RARE(CSECP_GENERAL_WRAP);
     fe r2;
     lmask t2;
     FEC_ADDK256(r2, r, t2, FEC_SECP_C);
@@ -95,7 +96,10 @@ FEC_SDEV fe reduce512_general(const u32 t[16]) {
 FEC_SDEV fe reduce512(const u32 t[16]) {
   u32 hmax = t[8];
   FEC_UNROLL for (int k = 9; k < 16; ++k) hmax = hmax > t[k] ? hmax : t[k];
-  if (__builtin_expect(lanes_where(hmax >= 0xFFFFF000u) != 0, 0)) return reduce512_general(t);
+  if (__builtin_expect(lanes_where(hmax >= 0xFFFFF000u) != 0, 0)) {
+    FEC_RARE(CSECP_GENERAL);
+    return reduce512_general(t);
+  }
   fe a, b;
   u32 top;
   {
@@ -114,6 +118,7 @@ FEC_SDEV fe reduce512(const u32 t[16]) {
   fe r2;
   lmask c2 = add_lohi256(r2, r, 0u, (u32)(q >> 32));
   if (__builtin_expect(c2 != 0, 0)) {  // wrapped past 2^256 (probability ~2^-190): add c once more
+    FEC_RARE(CSECP_FAST_WRAP);
     fe r3;
     lmask t2;
     FEC_ADDK256(r3, r2, t2, FEC_SECP_C);
@@ -192,6 +197,7 @@ struct FpP256 {
   }
   FEC_SDEV fe csub_p_unlikely(const fe& v) {  // v >= p needs w7 = 0xFFFFFFFF and w6 >= 1: ~2^-32
     if (__builtin_expect(lanes_where(v.w[7] == 0xFFFFFFFFu && v.w[6] != 0) != 0, 0)) {
+      FEC_RARE(CP256_CSUB_P);
       fe w;
       lmask ov;
       FEC_ADDK256(w, v, ov, FEC_P256_NEGP);
@@ -252,6 +258,7 @@ struct FpP256 {
     fe r;
     lmask c2 = add256(r, v, k);
     if (__builtin_expect(c2 != 0, 0)) {  // wrapped once more (probability ~ t / 2^32): add 2^256 - p again
+      FEC_RARE(CP256_WRAP);
       fe r2;
       lmask t2;
       FEC_ADDK256(r2, r, t2, FEC_P256_NEGP);
@@ -502,12 +509,14 @@ FEC_SDEV jac jadd_affine(const jac& p, const aff& q, lmask skip) {
   lmask pinf = fe_is_zero(p.z);
   lmask hzero = fe_is_zero(h) & ~pinf;
   if (__builtin_expect((pinf | hzero) != 0, 0)) {
+    FEC_RARE(CWEI_MADD_EXC);
     jac qa;
     qa.x = q.x;
     qa.y = q.y;
     qa.z = fe_small(1);
     o = jac_select(o, qa, pinf);
     if (hzero != 0) {  // same x: either P == Q (double) or P == -Q (infinity)
+      FEC_RARE(CWEI_MADD_SAME_X);
       lmask same = hzero & fe_is_zero(rr);
       jac d = jdouble(qa);
       o = jac_select(o, jac_infinity(), hzero & ~same);
@@ -560,8 +569,10 @@ FEC_SDEV jac jadd_window(const jac& p, const jac& q, lmask skip) {
   lmask pinf = fe_is_zero(p.z) & ~skip;
   lmask hzero = fe_is_zero(h) & ~pinf & ~skip;
   if (__builtin_expect((pinf | hzero) != 0, 0)) {
+    FEC_RARE(CWEI_WADD_EXC);
     o = jac_select(o, q, pinf);
     if (hzero != 0) {
+      FEC_RARE(CWEI_WADD_SAME_X);
       lmask same = hzero & fe_is_zero(rr);
       jac d = jdouble(q);
       o = jac_select(o, jac_infinity(), hzero & ~same);
@@ -784,7 +795,10 @@ struct FpEd {
     fe v;
     add_word256(v, r, fold);  // < 2^255 + 1520: no carry out
     u32 ones = v.w[1] & v.w[2] & v.w[3] & v.w[4] & v.w[5] & v.w[6] & (v.w[7] | 0x80000000u);
-    if (__builtin_expect(lanes_where(ones == 0xFFFFFFFFu || (v.w[7] >> 31) != 0) != 0, 0)) v = ed::reduce(v);
+    if (__builtin_expect(lanes_where(ones == 0xFFFFFFFFu || (v.w[7] >> 31) != 0) != 0, 0)) {
+      FEC_RARE(CED_FINISH);
+      v = ed::reduce(v);
+    }
     return v;
   }
   FEC_SDEV fe mul(const fe& a, const fe& b) {
@@ -1320,6 +1334,7 @@ struct glv_secp {
     {
       const u32 d1 = k1.w[4] & 15u, d2 = k2.w[4] & 15u;
       if (__builtin_expect(lanes_where((d1 | d2) != 0) != 0, 0)) {
+        FEC_RARE(CGLV_TOP_WINDOW);
         acc = W::jadd_window(acc, entry(table, d1, neg1, false), lanes_where(d1 == 0));
         acc = W::jadd_window(acc, entry(table, d2, neg2, true), lanes_where(d2 == 0));
       }

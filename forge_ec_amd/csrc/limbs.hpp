@@ -46,7 +46,10 @@
   X(P256_ADD_GENERAL) X(P256_SUB_TOP) X(P256_SUB_GE) X(P256_PRODUCT_TOP) X(P256_MULK_EXC)                         \
   X(P256_PDBL_ZLOW) X(P256_PADD_EARLY) X(P256_PADD_UEQ) X(P256_PADD_NONCANON)                                     \
   X(ED_REDUCE_CARRY) X(ED_REDUCE_TOP) X(ED_ADD_CARRY) X(ED_SUB_BORROW) X(ED_MUL_EXC)                              \
-  X(ED_PADD_EARLY) X(ED_PADD_OPPOSITE) X(ED_PDBL_MAYBE) X(ED_PDBL_OPPOSITE)
+  X(ED_PADD_EARLY) X(ED_PADD_OPPOSITE) X(ED_PDBL_MAYBE) X(ED_PDBL_OPPOSITE)                                       \
+  /* canonical mode (canon_curves.hpp) */                                                                         \
+  X(CSECP_GENERAL) X(CSECP_GENERAL_WRAP) X(CSECP_FAST_WRAP) X(CP256_WRAP) X(CP256_CSUB_P) X(CED_FINISH)           \
+  X(CWEI_MADD_EXC) X(CWEI_MADD_SAME_X) X(CWEI_WADD_EXC) X(CWEI_WADD_SAME_X) X(CGLV_TOP_WINDOW)
 #define FEC_RARE_ENUM(L) FEC_RL_##L,
 #define FEC_RARE_NAME(L) #L,
 namespace fecgpu {

@@ -454,7 +454,7 @@ def test_glv_constants_and_decomposition(emu):
     for k in ks:
         signs = emu.he_glv_decompose(_p(_arr(k)), _p(k1), _p(k2))
         a, b = M.unlimbs(k1), M.unlimbs(k2)
-        assert a < 2**129 and b < 2**129, hex(k)
+        assert a < 2**128 and b < 2**128, hex(k)   # the lattice bound: tests/test_canon_rare_legs.py::test_glv_top_window_is_out_of_reach
         sa = -a if signs & 1 else a
         sb = -b if signs & 2 else b
         assert (sa + sb * GLV_LAMBDA - k) % n == 0, hex(k)

@@ -5,7 +5,10 @@ what reaches them, without a GPU:
     the census test until the census says how it is reached (or why it is not);
   * the host build of the headers (tools/host_emul.cpp) counts each leg (limbs.hpp FEC_RARE_LEGS);
   * tests/golden/kernel_forcing_vectors.json (gen_kernel_forcing.py) holds (scalar, point) cases on which a named leg
-    fires in a kept operation of the multiplication; tests/test_gpu_kernel_forcing.py drives them through the kernels.
+    fires in a kept operation of the multiplication; tests/test_gpu_kernel_forcing.py drives them through the kernels;
+  * canonical mode (canon_curves.hpp) is in the same census, keyed canon_curves.hpp::Struct::function#ordinal, with the
+    families of tests/golden/canon_forcing_vectors.json (gen_canon_forcing.py); tests/test_canon_rare_legs.py checks them
+    on the host, tests/test_gpu_canon_forcing.py through the kernels.
 """
 import ctypes
 import json
@@ -26,6 +29,8 @@ OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "neg": 4}
 FILES = ["secp256k1.hpp", "p256.hpp", "ed25519.hpp", "kernels_secp.hip", "kernels_p256.hip", "kernels_ed.hip"]
 CENSUS = json.load(open(os.path.join(ROOT, "tests", "rare_legs.json")))
 FORCING = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_forcing_vectors.json")))
+CANON_FILE = "canon_curves.hpp"
+CANON = json.load(open(os.path.join(ROOT, "tests", "golden", "canon_forcing_vectors.json")))
 
 
 def rare_sites():
@@ -40,7 +45,35 @@ def rare_sites():
                 k = seen.get(fn, 0)
                 seen[fn] = k + 1
                 out.append("%s::%s#%d" % (f, fn, k))
+    return out + [key for key, _ in canon_sites()]
+
+
+def canon_sites():
+    """(canon_curves.hpp::Struct::function#ordinal, line index) of every __builtin_expect in canonical mode's header: its
+    functions are members (FEC_SDEV, indented) of structs that share names such as reduce512"""
+    out, struct, fn, seen = [], None, None, {}
+    for i, line in enumerate(open(os.path.join(CSRC, CANON_FILE))):
+        m = re.match(r"struct (\w+)", line)
+        if m:
+            struct = m.group(1)
+        elif line.startswith("};"):
+            struct = None
+        m = re.match(r"\s*FEC_S?DEV\b[^(]*?(\w+)\s*\(", line)
+        if m:
+            fn = "%s::%s" % (struct, m.group(1)) if struct else m.group(1)
+        for _ in re.finditer(r"__builtin_expect\(", line.split("//")[0]):
+            k = seen.get(fn, 0)
+            seen[fn] = k + 1
+            out.append(("%s::%s#%d" % (CANON_FILE, fn, k), i))
     return out
+
+
+def canon_families():
+    """family -> counters, for the three kinds of case in canon_forcing_vectors.json"""
+    fams = {name: set(f["legs"]) for name, f in CANON["families"].items()}
+    for c in CANON["points"] + CANON["edge_scalars"]:
+        fams.setdefault(c["family"], set()).update(c["legs"])
+    return fams
 
 
 @pytest.fixture(scope="module")
@@ -48,7 +81,7 @@ def emu():
     if not os.path.exists(CLANG):
         pytest.skip("ROCm clang++ not available")
     src = os.path.join(ROOT, "tools", "host_emul.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("limbs.hpp", "secp256k1.hpp", "p256.hpp", "ed25519.hpp")]
+    deps = [src] + [os.path.join(CSRC, f) for f in ("limbs.hpp", "secp256k1.hpp", "p256.hpp", "ed25519.hpp", CANON_FILE)]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call([CLANG, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO, src])
     return ctypes.CDLL(SO)
@@ -101,6 +134,8 @@ def test_census_counters_and_families(emu):
     fams = {}
     for c in FORCING["cases"]:
         fams.setdefault(c["family"], set()).update(c["legs"])
+    assert not set(fams) & set(canon_families())
+    fams.update(canon_families())
     for key, leg in CENSUS["legs"].items():
         assert leg["counter"] in names, (key, leg["counter"])
         if leg["status"] == "forced":
@@ -118,7 +153,7 @@ def test_census_counters_and_families(emu):
 
 def test_census_search_records():
     """A leg whose operand the generator searches for: forced legs have a hit, unreached legs none in the bound."""
-    searches = FORCING["searches"]
+    searches = FORCING["searches"] + [r for r in CANON["searches"] if "leg" in r]
     for key, leg in CENSUS["legs"].items():
         if not leg.get("search"):
             continue

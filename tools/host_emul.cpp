@@ -443,3 +443,47 @@ extern "C" int he_canon_scalar_general(int curve, int op, const uint64_t* a, con
   st(out, r);
   return 0;
 }
+// Bounded search for the GLV ladder's top window (glv_secp::mul_window, CGLV_TOP_WINDOW): `count` splitmix64 scalars
+// from `seed` over `threads` threads through cglv::decompose.  A hit is a scalar with |k1| or |k2| >= 2^128 (the leg's
+// own test is on bits 128..131, a subset); the one of lowest candidate index is written to `hit`.  max_top receives
+// the largest bits 96..159 of any |k1|, |k2| seen: how close the search came.
+extern "C" unsigned long he_search_glv_top(uint64_t seed, unsigned long count, int threads, uint64_t* hit, uint64_t* max_top) {
+  std::atomic<unsigned long> hits{0};
+  std::mutex m;
+  unsigned long first = ~0ul;
+  uint64_t top = 0;
+  std::vector<std::thread> pool;
+  for (int t = 0; t < threads; ++t)
+    pool.emplace_back([&, t] {
+      uint64_t st = seed ^ ((uint64_t)t << 48), mine = 0;
+      for (unsigned long i = t; i < count; i += threads) {
+        uint64_t w[4] = {splitmix(st), splitmix(st), splitmix(st), splitmix(st)};
+        fe a, b; lmask n1, n2;
+        cglv::decompose(ld(w), a, n1, b, n2);
+        const uint64_t ta = ((uint64_t)a.w[4] << 32) | a.w[3], tb = ((uint64_t)b.w[4] << 32) | b.w[3];
+        mine = ta > mine ? ta : mine;
+        mine = tb > mine ? tb : mine;
+        if (a.w[4] | a.w[5] | a.w[6] | a.w[7] | b.w[4] | b.w[5] | b.w[6] | b.w[7]) {
+          ++hits;
+          std::lock_guard<std::mutex> g(m);
+          if (i < first) {
+            first = i;
+            memcpy(hit, w, sizeof(w));
+          }
+        }
+      }
+      std::lock_guard<std::mutex> g(m);
+      top = mine > top ? mine : top;
+    });
+  for (auto& th : pool) th.join();
+  *max_top = top;
+  return hits;
+}
+// the on-curve test of the point routines alone (the first thing every kernel does with a caller's point): 1 = accepted
+extern "C" int he_canon_on_curve(int curve, const uint64_t* pxy) {
+  canon::aff q; q.x = ld(pxy); q.y = ld(pxy + 4);
+  if (curve == 2) return ced::on_curve(q) ? 1 : 0;
+#define CALL(W) (W::on_curve(q) ? 1 : 0)
+  return CANON_DISPATCH(curve, CALL);
+#undef CALL
+}
