@@ -355,4 +355,40 @@ class CanonEd25519(CanonCurve):
                "fec_canon_eddsa_verify_dev")
 
 
+class CanonX25519:
+    """X25519 (RFC 7748 section 5): byte strings in, byte strings out -- scalars, u-coordinates and results are (n,32) uint8,
+    little-endian, exactly what other libraries exchange.  Not a CanonCurve: there are no points here, only u."""
+
+    def __init__(self, ctx=None, device=0):
+        self.ctx = ctx if ctx is not None else Context(device)
+        self._lib = self.ctx._lib
+        self._h = self.ctx._h
+
+    def x25519(self, scalars, us):
+        """(out (n,32), status): out[i] = X25519(scalars[i], us[i]); status 7 (L.CANON_ZERO_SHARED): the output is all zero
+        (a low-order u), which RFC 7748 section 6.1 lets a caller refuse."""
+        k, u = _bytes_rows(scalars, 32, "scalars"), _bytes_rows(us, 32, "us")
+        n = k.shape[0]
+        if u.shape[0] != n:
+            raise ValueError("inputs differ in length")
+        out = np.zeros((n, 32), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_x25519(self._h, _ptr(k), _ptr(u), _ptr(out), _ptr(st), n), "fec_canon_x25519")
+        return out, st
+
+    def x25519_dev(self, d_scalars, d_us, d_out, d_status, n, stream=None):
+        _check(self._lib.fec_canon_x25519_dev(self._h, d_scalars, d_us, d_out, d_status, n, stream), "fec_canon_x25519_dev")
+
+    def x25519_base(self, scalars):
+        """(n,32): the public keys X25519(scalars[i], 9), through the Ed25519 secret comb and the birational map."""
+        k = _bytes_rows(scalars, 32, "scalars")
+        n = k.shape[0]
+        out = np.zeros((n, 32), dtype=np.uint8)
+        _check(self._lib.fec_canon_x25519_base(self._h, _ptr(k), _ptr(out), n), "fec_canon_x25519_base")
+        return out
+
+    def x25519_base_dev(self, d_scalars, d_out, n, stream=None):
+        _check(self._lib.fec_canon_x25519_base_dev(self._h, d_scalars, d_out, n, stream), "fec_canon_x25519_base_dev")
+
+
 CANON_CURVES = {"secp256k1": CanonSecp256k1, "p256": CanonP256, "ed25519": CanonEd25519}

@@ -8,6 +8,7 @@
 #include "host_messages.hpp"
 #include "canon_kernels.hpp"
 #include "canon_sign_kernels.hpp"
+#include "canon_x25519_kernels.hpp"
 
 using namespace fecgpu;
 using namespace fecgpu::host;
@@ -493,6 +494,35 @@ int launch_canon_ed25519_sign(fec_ctx* ctx, const Messages& m, const uint8_t* d_
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 
+// ---- X25519 (canon_x25519.hpp, canon_x25519_kernels.hpp) ---------------------------------------------------------------
+// The ladder keeps everything in registers and LDS: no work area.
+int launch_canon_x25519(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_us, uint8_t* d_out, unsigned char* dst,
+                        size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t s = sign_stream(ctx, stream);
+  hipLaunchKernelGGL(k_canon_x25519, dim3(grid_for(n)), dim3(TPB), 0, s, (const u32*)d_scalars, (const u32*)d_us, (u32*)d_out, dst, n);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+// Public keys: clamp -> the Ed25519 secret comb -> u = (Z + Y) / (Z - Y).  The clamped limbs and the comb's X, Y, Z share
+// one work area, cleared behind the last kernel on every way out.
+int launch_canon_x25519_base(fec_ctx* ctx, const uint8_t* d_scalars, uint8_t* d_out, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t s = sign_stream(ctx, stream);
+  int rc = ensure_canon_comb(ctx, FEC_ED25519, s);
+  if (rc != FEC_OK) return rc;
+  SignArea a;
+  rc = a.open(ctx, s, r256(n * 32) + r256(n * 64) + comb_area_bytes(n));
+  if (rc != FEC_OK) return rc;
+  u32 *ks = a.take<u32>(n * 32), *xy = a.take<u32>(n * 64);
+  CombArea c;
+  c.take(a, n);
+  dim3 g(grid_for(n)), b(TPB);
+  hipLaunchKernelGGL(k_canon_x25519_clamp, g, b, 0, s, (const u32*)d_scalars, ks, n);
+  hipLaunchKernelGGL(k_ced_mul_base_secret, g, b, 0, s, (const u32*)ks, (const u32*)ctx->d_canon_comb[FEC_ED25519], xy, c.z, c.pst, c.refused, n);
+  hipLaunchKernelGGL(k_canon_x25519_base_finish, g, b, 0, s, (const u32*)xy, (const u32*)c.z, (u32*)d_out, n);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+
 }  // namespace
 
 extern "C" {
@@ -885,6 +915,38 @@ int fec_canon_ed25519_sign_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t
   const HostArray a[] = {ragged(msg_off, 8), secret_input(seeds, 32), secret_output(sigs, 64), output(pks_out, 32), output(status, 1)};
   return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
     return launch_canon_ed25519_sign(c, m, (const uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], (unsigned char*)d[4], cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- X25519 (RFC 7748 section 5): 32 little-endian bytes each way ------------------------------------------------------
+int fec_canon_x25519_dev(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_us, uint8_t* d_out, uint8_t* d_status,
+                         size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_scalars || !d_us || !d_out || !d_status)) return FEC_E_ARG;
+  if (!aligned16(d_scalars) || !aligned16(d_us) || !aligned16(d_out)) return FEC_E_ARG;
+  return launch_canon_x25519(ctx, d_scalars, d_us, d_out, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_x25519(fec_ctx* ctx, const uint8_t* scalars, const uint8_t* us, uint8_t* out, uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!scalars || !us || !out || !status))) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(scalars, 32), input(us, 32), secret_output(out, 32), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_x25519(c, (const uint8_t*)d[0], (const uint8_t*)d[1], (uint8_t*)d[2], (unsigned char*)d[3], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_x25519_base_dev(fec_ctx* ctx, const uint8_t* d_scalars, uint8_t* d_out, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_scalars || !d_out)) return FEC_E_ARG;
+  if (!aligned16(d_scalars) || !aligned16(d_out)) return FEC_E_ARG;
+  return launch_canon_x25519_base(ctx, d_scalars, d_out, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_x25519_base(fec_ctx* ctx, const uint8_t* scalars, uint8_t* out, size_t n) try {
+  if (!ctx || (n && (!scalars || !out))) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(scalars, 32), output(out, 32)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_x25519_base(c, (const uint8_t*)d[0], (uint8_t*)d[1], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 

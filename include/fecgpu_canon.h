@@ -4,8 +4,8 @@
  * *** NOT REFERENCE PARITY. ***  Everything in fecgpu.h reproduces forge-ec's CPU arithmetic bit
  * for bit, and that arithmetic is not the secp256k1 group: its outputs are
  * not public keys any other library would accept.  The entry points below compute the REAL curves
- * -- secp256k1 (SEC 2), NIST P-256 (FIPS 186-4) and Ed25519 (RFC 8032) -- for callers that want
- * standard results at GPU speed.  They replace the same loops as fec_batch_mul_fixed /
+ * -- secp256k1 (SEC 2), NIST P-256 (FIPS 186-4), Ed25519 (RFC 8032) and X25519 (RFC 7748) -- for callers that want
+ * standard results at GPU speed. They replace the same loops as fec_batch_mul_fixed /
  * fec_batch_mul + fec_batch_to_affine (key generation forge-ec-examples/src/ecdh.rs:27-49,
  * forge-ec-signature/src/ecdsa.rs:111-112; ECDH ecdh.rs:51-70), but their results differ from the
  * reference's by design; they are validated against an independent big-integer model
@@ -255,6 +255,34 @@ int fec_canon_ed25519_sign_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t
 int fec_canon_ed25519_sign_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                                    const uint8_t* d_seeds, uint8_t* d_sigs, uint8_t* d_pks_out, uint8_t* d_status, size_t n,
                                    void* stream);
+
+/* ---- X25519 (RFC 7748 section 5) ---------------------------------------------------------------------------------------
+ * The key exchange other libraries compute; fec_x25519 in fecgpu.h is the reference's own curve25519.rs and agrees with
+ * none of them.  32 little-endian bytes each way, exactly the RFC's function: the scalar is clamped (k[0] &= 248,
+ * k[31] &= 127, k[31] |= 64), bit 255 of u is ignored, a non-canonical u in [p, 2^255) is accepted and reduced, the result
+ * is x2 * z2^(p-2) encoded canonically.  status[i]: 0, or FEC_CANON_ZERO_SHARED when the 32 output bytes are all zero -- the
+ * optional check of RFC 7748 section 6.1, which a low-order u fails; out[i] is the zeros, as the RFC's function gives them.
+ * One Montgomery ladder per lane, 255 steps, the inversion in the kernel.  The scalar is a secret and the signing side's
+ * guarantee above holds in its words: no load or store address, no branch and no trip count depends on the scalar, on u
+ * or on an intermediate, above the field layer (the step's scalar bit is read at a word index the step alone fixes, the
+ * conditional swap is an AND with a mask and two XORs); Ed25519's reduction and add / sub keep their rare wave-uniform legs,
+ * so the path is not called constant-time.
+ * fec_canon_x25519_base: out[i] = X25519(scalars[i], 9), the public key, computed another way -- the clamped scalar goes
+ * through the Ed25519 secret comb of fec_canon_mul_base_secret and the point maps to u = (Z + Y) / (Z - Y).
+ * Host forms stage scalars and shared secrets as secrets (public keys are plain outputs), are chunked by fec_ctx_set_chunk
+ * and sharded over a multi-device ctx.  *_dev forms: every array 16-byte aligned (else FEC_E_ARG), FEC_E_UNSUPPORTED on a
+ * multi-device ctx, the work area of _base_dev cleared behind its last kernel.
+ * Not offered: X448. */
+#define FEC_CANON_ZERO_SHARED 7 /* the X25519 output is all zero (RFC 7748 section 6.1's optional check); out[i] is the zeros */
+
+/* RFC 7748 section 5 X25519: 32 little-endian bytes each way. */
+int fec_canon_x25519(fec_ctx* ctx, const uint8_t* scalars /* n*32 */, const uint8_t* us /* n*32 */, uint8_t* out /* n*32 */,
+                     uint8_t* status /* n */, size_t n);
+int fec_canon_x25519_dev(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_us, uint8_t* d_out, uint8_t* d_status,
+                         size_t n, void* stream);
+/* X25519(k, 9): public keys. */
+int fec_canon_x25519_base(fec_ctx* ctx, const uint8_t* scalars /* n*32 */, uint8_t* out /* n*32 */, size_t n);
+int fec_canon_x25519_base_dev(fec_ctx* ctx, const uint8_t* d_scalars, uint8_t* d_out, size_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,15 @@ fec_sha256_dev / fec_sha512_dev over the bytes the signer hashes, for ECDSA the 
 it hashes the message itself), and the fec_canon_scalar_op passes, which exist as host-pointer calls only and are reported
 apart (PCIe included).  "verify-valid" rows: fec_canon_*_verify_msg_dev over the signatures the signers just made, all
 of which must come out valid.  Last, one host-pointer row per signer.
+
+X25519 (fec_canon_x25519_dev, fec_canon_x25519_base_dev), by the same method:
+
+    python tools/canon_perf.py x25519 [log2_n] [reps] [out.jsonl]
+
+"ladder" rows: fec_canon_x25519_dev on random u against fec_canon_mul_dev(FEC_ED25519) -- the same field, the windowed
+Edwards multiplication -- and against parity mode's fec_x25519_dev.  "base" rows: fec_canon_x25519_base_dev against
+fec_canon_mul_base_secret_dev(FEC_ED25519) (the difference is the clamp, the map's inversion and the encoding) and against
+fec_canon_x25519_dev at u = 9, whose outputs must equal the base path's.  Last, one host-pointer row each.
 """
 import json
 import os
@@ -310,6 +319,76 @@ def main_sign():
                 f.write(json.dumps(r) + "\n")
 
 
+def main_x25519():
+    from forge_ec_amd.canon import CanonX25519
+    logn = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    out_path = sys.argv[4] if len(sys.argv) > 4 else None
+    n = 1 << logn
+    ctx = F.Context(0)
+    lib, h = ctx._lib, ctx._h
+    rng = np.random.default_rng(20)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()  # noqa: E731
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    def rounds(fns):
+        """each of fns three times, alternating; per fn the middle round's median and the largest spread"""
+        got = [[] for _ in fns]
+        for _ in range(3):
+            for g, fn in zip(got, fns):
+                g.append(_timed(fn, reps))
+        return [(sorted(g)[1][0], max(x[1] for x in g)) for g in got]
+
+    x, ed = CanonX25519(ctx), CANON_CURVES["ed25519"](ctx)
+    ks_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    us_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    nine_h = np.zeros((n, 32), dtype=np.uint8)
+    nine_h[:, 0] = 9
+    ks, us, nine = dev(ks_h), dev(us_h), dev(nine_h)
+    out = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
+    out9 = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
+    stat = torch.empty(n, dtype=torch.uint8, device="cuda")
+    xy = torch.empty((n, 8), dtype=torch.int64, device="cuda")
+    pts = torch.from_numpy(ed.mul_base(synth.scalars(n, 0, 51))[0].view(np.int64)).cuda()     # points for the windowed multiplication
+    for npass in range(2):
+        lad, win, par = rounds([
+            lambda: x.x25519_dev(ks.data_ptr(), us.data_ptr(), out.data_ptr(), stat.data_ptr(), n, st),
+            lambda: ed.mul_dev(ks.data_ptr(), pts.data_ptr(), xy.data_ptr(), stat.data_ptr(), n, st),
+            lambda: ctx.x25519_dev(ks.data_ptr(), us.data_ptr(), out.data_ptr(), n, st)])
+        emit({"row": "ladder", "pass": npass, "n": n, "reps": reps, "x25519_dev_ms": round(lad[0], 4), "x25519_dev_spread_ms": round(lad[1], 4),
+              "canon_mul_ed25519_ms": round(win[0], 4), "canon_mul_ed25519_spread_ms": round(win[1], 4),
+              "parity_x25519_dev_ms": round(par[0], 4), "parity_x25519_dev_spread_ms": round(par[1], 4),
+              "ladder_over_windowed": round(lad[0] / win[0], 4), "ladder_over_parity": round(lad[0] / par[0], 4),
+              "M_per_s": round(n / lad[0] / 1e3, 3)})
+        base, comb, lad9 = rounds([
+            lambda: x.x25519_base_dev(ks.data_ptr(), out.data_ptr(), n, st),
+            lambda: ed.mul_base_secret_dev(ks.data_ptr(), xy.data_ptr(), stat.data_ptr(), n, st),
+            lambda: x.x25519_dev(ks.data_ptr(), nine.data_ptr(), out9.data_ptr(), stat.data_ptr(), n, st)])
+        torch.cuda.synchronize()
+        assert bool((out == out9).all()) and not bool(stat.any())
+        emit({"row": "base", "pass": npass, "n": n, "reps": reps, "x25519_base_dev_ms": round(base[0], 4), "x25519_base_dev_spread_ms": round(base[1], 4),
+              "mul_base_secret_ed25519_ms": round(comb[0], 4), "mul_base_secret_ed25519_spread_ms": round(comb[1], 4),
+              "x25519_dev_at_9_ms": round(lad9[0], 4), "x25519_dev_at_9_spread_ms": round(lad9[1], 4),
+              "base_over_secret_comb": round(base[0] / comb[0], 4), "base_over_ladder_at_9": round(base[0] / lad9[0], 4),
+              "M_per_s": round(n / base[0] / 1e3, 3)})
+    out_h, st_h = np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+    p = lambda a: a.ctypes.data  # noqa: E731
+    for name, fn in (("x25519", lambda: lib.fec_canon_x25519(h, p(ks_h), p(us_h), p(out_h), p(st_h), n)),
+                     ("x25519_base", lambda: lib.fec_canon_x25519_base(h, p(ks_h), p(out_h), n))):
+        assert fn() == 0
+        ms, spread = _timed(fn, reps)
+        emit({"row": "host-" + name, "n": n, "reps": reps, "ms": round(ms, 4), "spread_ms": round(spread, 4), "M_per_s": round(n / ms / 1e3, 3)})
+    if out_path:
+        with open(out_path, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     logn = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -369,5 +448,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "msg":
     main_msg()
 elif len(sys.argv) > 1 and sys.argv[1] == "sign":
     main_sign()
+elif len(sys.argv) > 1 and sys.argv[1] == "x25519":
+    main_x25519()
 else:
     main()
