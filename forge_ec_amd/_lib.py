@@ -38,7 +38,10 @@ CANON_ABI_SYMBOLS = [
     "fec_canon_rfc6979_k", "fec_canon_rfc6979_k_dev", "fec_canon_bip340_sign_msg", "fec_canon_bip340_sign_msg_dev",
     "fec_canon_ed25519_sign_msg", "fec_canon_ed25519_sign_msg_dev",
     "fec_canon_x25519", "fec_canon_x25519_dev", "fec_canon_x25519_base", "fec_canon_x25519_base_dev",
+    "fec_canon_keccak256", "fec_canon_keccak256_dev", "fec_canon_ecdsa_recover", "fec_canon_ecdsa_recover_dev",
+    "fec_canon_ecdsa_sign_recoverable_digest", "fec_canon_ecdsa_sign_recoverable_digest_dev",
 ]
+CANON_NO_KEY = 8
 CANON_BAD_SCALAR, CANON_BAD_KEY, CANON_SIGN_LOW_S, CANON_SCHEME_BIP340 = 3, 6, 1, 3
 CANON_ZERO_SHARED = 7
 F_INV = 5
@@ -300,6 +303,12 @@ def lib():
     L.fec_canon_x25519_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp]
     L.fec_canon_x25519_base.argtypes = [vp, vp, vp, sz]
     L.fec_canon_x25519_base_dev.argtypes = [vp, vp, vp, sz, vp]
+    L.fec_canon_keccak256.argtypes = [vp, vp, vp, sz, vp, sz]
+    L.fec_canon_keccak256_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+    L.fec_canon_ecdsa_recover.argtypes = [vp, ci, vp, vp, vp, vp, sz, vp, sz]
+    L.fec_canon_ecdsa_recover_dev.argtypes = [vp, ci, vp, vp, vp, vp, sz, vp, sz, vp]
+    L.fec_canon_ecdsa_sign_recoverable_digest.argtypes = [vp, ci, vp, vp, cu, vp, vp, vp, sz]
+    L.fec_canon_ecdsa_sign_recoverable_digest_dev.argtypes = [vp, ci, vp, vp, cu, vp, vp, vp, sz, vp]
     for n in CANON_ABI_SYMBOLS:
         getattr(L, n).restype = ci
     _lib = L

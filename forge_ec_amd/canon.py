@@ -119,6 +119,43 @@ class CanonCurve:
         _check(self._lib.fec_canon_ecdsa_sign_digest_dev(self._h, self.CURVE, d_digests, d_keys, flags, d_sigs, d_status, n, stream),
                "fec_canon_ecdsa_sign_digest_dev")
 
+    def ecdsa_sign_recoverable_digest(self, digests, keys, flags=0):
+        """ecdsa_sign_digest with the recovery ids: (sigs, recids (n,) uint8 in 0..3, status).  sigs and status are those of
+        ecdsa_sign_digest; recids[i] is what ecdsa_recover needs to find the key again, 0 where status is not 0."""
+        dg, k = _bytes_rows(digests, 32, "digests"), _bytes_rows(keys, 32, "keys")
+        n = dg.shape[0]
+        if k.shape[0] != n:
+            raise ValueError("inputs differ in length")
+        sigs = np.zeros((n, 64), dtype=np.uint8)
+        rec = np.zeros(n, dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_ecdsa_sign_recoverable_digest(self._h, self.CURVE, _ptr(dg), _ptr(k), flags, _ptr(sigs), _ptr(rec),
+                                                                 _ptr(st), n), "fec_canon_ecdsa_sign_recoverable_digest")
+        return sigs, rec, st
+
+    def ecdsa_sign_recoverable_digest_dev(self, d_digests, d_keys, flags, d_sigs, d_recids, d_status, n, stream=None):
+        _check(self._lib.fec_canon_ecdsa_sign_recoverable_digest_dev(self._h, self.CURVE, d_digests, d_keys, flags, d_sigs, d_recids,
+                                                                     d_status, n, stream), "fec_canon_ecdsa_sign_recoverable_digest_dev")
+
+    def ecdsa_recover(self, digests, sigs, recids, out_len=33):
+        """Public-key recovery (SEC 1 section 4.1.6; secp256k1, P-256): digests (n,32), sigs (n,64) r || s big-endian, recids
+        (n,) in 0..3 -> (out (n,out_len) uint8, status).  out_len 33 / 65: SEC 1; 64: x || y big-endian; 20 (secp256k1): the
+        Ethereum address.  status 8 (L.CANON_NO_KEY): no key, zeros."""
+        dg, sg = _bytes_rows(digests, 32, "digests"), _bytes_rows(sigs, 64, "sigs")
+        rc = np.ascontiguousarray(np.asarray(recids, dtype=np.uint8)).reshape(-1)
+        n = dg.shape[0]
+        if not (sg.shape[0] == rc.shape[0] == n):
+            raise ValueError("inputs differ in length")
+        out = np.zeros((n, out_len), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_ecdsa_recover(self._h, self.CURVE, _ptr(dg), _ptr(sg), _ptr(rc), _ptr(out), out_len, _ptr(st), n),
+               "fec_canon_ecdsa_recover")
+        return out, st
+
+    def ecdsa_recover_dev(self, d_digests, d_sigs, d_recids, d_out, out_len, d_status, n, stream=None):
+        _check(self._lib.fec_canon_ecdsa_recover_dev(self._h, self.CURVE, d_digests, d_sigs, d_recids, d_out, out_len, d_status, n,
+                                                     stream), "fec_canon_ecdsa_recover_dev")
+
     def ecdsa_sign_msg(self, msgs, keys, flags=0):
         """ECDSA with SHA-256 and RFC 6979 nonces from the message: msgs a list of n byte strings -> (sigs, status)."""
         return _sign_msg(self._lib.fec_canon_ecdsa_sign_msg, self._h, msgs, [keys], "fec_canon_ecdsa_sign_msg", lead=(self.CURVE,),
@@ -389,6 +426,27 @@ class CanonX25519:
 
     def x25519_base_dev(self, d_scalars, d_out, n, stream=None):
         _check(self._lib.fec_canon_x25519_base_dev(self._h, d_scalars, d_out, n, stream), "fec_canon_x25519_base_dev")
+
+
+class CanonKeccak:
+    """Keccak-256 as Ethereum uses it (padding 0x01, not SHA3-256's 0x06): a list of n byte strings -> (n,32) uint8."""
+
+    def __init__(self, ctx=None, device=0):
+        self.ctx = ctx if ctx is not None else Context(device)
+        self._lib = self.ctx._lib
+        self._h = self.ctx._h
+
+    def keccak256(self, msgs):
+        buf, off, total = Context._messages(msgs)
+        n = len(off) - 1
+        out = np.zeros((n, 32), dtype=np.uint8)
+        _check(self._lib.fec_canon_keccak256(self._h, _ptr(buf), _ptr(off), total, _ptr(out), n), "fec_canon_keccak256")
+        return out
+
+    def keccak256_dev(self, d_msgs, d_msg_off, msg_len, d_out, d_status, n, stream=None):
+        """d_status may be None; else 4 marks a bad range (zero digest)."""
+        _check(self._lib.fec_canon_keccak256_dev(self._h, d_msgs, d_msg_off, msg_len, d_out, d_status, n, stream),
+               "fec_canon_keccak256_dev")
 
 
 CANON_CURVES = {"secp256k1": CanonSecp256k1, "p256": CanonP256, "ed25519": CanonEd25519}

@@ -9,6 +9,7 @@
 #include "canon_kernels.hpp"
 #include "canon_sign_kernels.hpp"
 #include "canon_x25519_kernels.hpp"
+#include "canon_recover_kernels.hpp"
 
 using namespace fecgpu;
 using namespace fecgpu::host;
@@ -421,7 +422,8 @@ int launch_canon_public_key(fec_ctx* ctx, int scheme, const uint8_t* dkeys, uint
 // ECDSA: nonce kernel -> secret comb -> finish.  d_digests != null: sign the digests; else hash the messages.
 // d_k_be != null (fec_canon_rfc6979_k): the nonce kernel alone.
 int launch_canon_ecdsa_sign(fec_ctx* ctx, int curve, const Messages& m, const uint8_t* d_digests, const uint8_t* d_keys,
-                            unsigned flags, uint8_t* d_sigs, uint8_t* d_k_be, unsigned char* dst, size_t n, void* stream) {
+                            unsigned flags, uint8_t* d_sigs, uint8_t* d_k_be, unsigned char* dst, size_t n, void* stream,
+                            uint8_t* d_recids = nullptr) {
   if (n == 0) return FEC_OK;
   hipStream_t s = sign_stream(ctx, stream);
   SignArea a;
@@ -443,7 +445,11 @@ int launch_canon_ecdsa_sign(fec_ctx* ctx, int curve, const Messages& m, const ui
   const size_t lanes = (n + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
   const size_t stride = (lanes + 63) / 64 * 64;
   dim3 gs(grid_for(stride));
-  if (curve == FEC_SECP256K1)
+  if (d_recids && curve == FEC_SECP256K1)   // with the recovery ids: the same pass, a kernel of its own
+    hipLaunchKernelGGL((k_canon_ecdsa_sign_finish_rec<canon::NSecp>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, d_recids, dst, n, stride);
+  else if (d_recids)
+    hipLaunchKernelGGL((k_canon_ecdsa_sign_finish_rec<canon::NP256>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, d_recids, dst, n, stride);
+  else if (curve == FEC_SECP256K1)
     hipLaunchKernelGGL((k_canon_ecdsa_sign_finish<canon::NSecp>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, dst, n, stride);
   else
     hipLaunchKernelGGL((k_canon_ecdsa_sign_finish<canon::NP256>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, dst, n, stride);
@@ -520,6 +526,53 @@ int launch_canon_x25519_base(fec_ctx* ctx, const uint8_t* d_scalars, uint8_t* d_
   hipLaunchKernelGGL(k_canon_x25519_clamp, g, b, 0, s, (const u32*)d_scalars, ks, n);
   hipLaunchKernelGGL(k_ced_mul_base_secret, g, b, 0, s, (const u32*)ks, (const u32*)ctx->d_canon_comb[FEC_ED25519], xy, c.z, c.pst, c.refused, n);
   hipLaunchKernelGGL(k_canon_x25519_base_finish, g, b, 0, s, (const u32*)xy, (const u32*)c.z, (u32*)d_out, n);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+
+// ---- Keccak-256 and ECDSA recovery (keccak.hpp, canon_recover.hpp, canon_recover_kernels.hpp) -----------------------------
+int launch_canon_keccak256(fec_ctx* ctx, const Messages& m, uint8_t* d_out, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_canon_keccak256");
+  hipLaunchKernelGGL(k_canon_keccak256, dim3(grid_for(n)), dim3(TPB), 0, L.s, m, (u32*)d_out, dst, n);
+  return L.done();
+}
+// Recovery: prepare -> u1*G + u2*R -> finish, the verifier's pipeline with another first and last kernel.  Work area in
+// d_verify, laid out as launch_canon_ecdsa_verify lays out its own with R behind it: u1, u2 (n*32 each), xy (n*64), R (n*64),
+// point status (n), flags (n).
+inline bool recover_len_ok(int curve, size_t out_len) {
+  return out_len == 33 || out_len == 65 || out_len == 64 || (out_len == 20 && curve == FEC_SECP256K1);
+}
+int launch_canon_ecdsa_recover(fec_ctx* ctx, int curve, const uint8_t* d_digests, const uint8_t* d_sigs, const uint8_t* d_recids,
+                               uint8_t* d_out, size_t out_len, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, n * (32 + 32 + 64 + 64 + 1 + 1) + 64);
+  if (rc != FEC_OK) return rc;
+  char* base = (char*)ctx->d_verify;
+  u64 *u1 = (u64*)base, *u2 = (u64*)(base + n * 32), *xy = (u64*)(base + n * 64), *rxy = (u64*)(base + n * 128);
+  unsigned char* pst = (unsigned char*)(base + n * 192);
+  unsigned char* ok = pst + n;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // the work area is the ctx's
+  dim3 g(grid_for(n)), b(TPB);
+  const size_t lanes = (n + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
+  const size_t stride = (lanes + 63) / 64 * 64;
+  dim3 gs(grid_for(stride));
+  if (curve == FEC_SECP256K1)
+    hipLaunchKernelGGL((k_canon_recover_prepare<canon::SecpParams>), gs, b, 0, s, (const u32*)d_digests, (const u32*)d_sigs, d_recids,
+                       (u32*)u1, (u32*)u2, (u32*)rxy, ok, n, stride);
+  else
+    hipLaunchKernelGGL((k_canon_recover_prepare<canon::P256Params>), gs, b, 0, s, (const u32*)d_digests, (const u32*)d_sigs, d_recids,
+                       (u32*)u1, (u32*)u2, (u32*)rxy, ok, n, stride);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  rc = launch_canon_mul_base(ctx, curve, u1, xy, pst, n, stream, false);
+  if (rc == FEC_OK) rc = launch_canon_mul(ctx, curve, u2, rxy, xy, pst, n, stream, true);
+  if (rc != FEC_OK) return rc;
+  const u32* cxy = (const u32*)xy;
+  const unsigned char *cok = ok, *cpst = pst;
+  if (out_len == 20) hipLaunchKernelGGL(k_canon_recover_finish<20>, g, b, 0, s, cxy, cok, cpst, d_out, dst, n);
+  else if (out_len == 33) hipLaunchKernelGGL(k_canon_recover_finish<33>, g, b, 0, s, cxy, cok, cpst, d_out, dst, n);
+  else if (out_len == 64) hipLaunchKernelGGL(k_canon_recover_finish<64>, g, b, 0, s, cxy, cok, cpst, d_out, dst, n);
+  else hipLaunchKernelGGL(k_canon_recover_finish<65>, g, b, 0, s, cxy, cok, cpst, d_out, dst, n);
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 
@@ -947,6 +1000,71 @@ int fec_canon_x25519_base(fec_ctx* ctx, const uint8_t* scalars, uint8_t* out, si
   const HostArray a[] = {secret_input(scalars, 32), output(out, 32)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_canon_x25519_base(c, (const uint8_t*)d[0], (uint8_t*)d[1], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- Keccak-256 (the original submission, Ethereum's hash; not SHA3-256) ---------------------------------------------------
+int fec_canon_keccak256_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_out,
+                            uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && !d_out) || !aligned16(d_out)) return FEC_E_ARG;
+  return launch_canon_keccak256(ctx, m, d_out, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_keccak256(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* out, size_t n) try {
+  if (!ctx || (n && !out)) return FEC_E_ARG;
+  const HostArray a[] = {ragged(msg_off, 8), output(out, 32)};
+  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_canon_keccak256(c, m, (uint8_t*)d[1], nullptr, cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- ECDSA public-key recovery (SEC 1 section 4.1.6) ------------------------------------------------------------------------
+int fec_canon_ecdsa_recover_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_sigs,
+                                const uint8_t* d_recids, uint8_t* d_out, size_t out_len, uint8_t* d_status, size_t n,
+                                void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_digests || !d_sigs || !d_recids || !d_out || !d_status)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!recover_len_ok(curve, out_len) || !aligned16(d_digests) || !aligned16(d_sigs)) return FEC_E_ARG;
+  if ((out_len == 64 || out_len == 20) && !aligned16(d_out)) return FEC_E_ARG;
+  return launch_canon_ecdsa_recover(ctx, curve, d_digests, d_sigs, d_recids, d_out, out_len, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ecdsa_recover(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* sigs, const uint8_t* recids,
+                            uint8_t* out, size_t out_len, uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!digests || !sigs || !recids || !out || !status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!recover_len_ok(curve, out_len)) return FEC_E_ARG;
+  const HostArray a[] = {input(digests, 32), input(sigs, 64), input(recids, 1), output(out, out_len), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_ecdsa_recover(c, curve, (const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (uint8_t*)d[3],
+                                      out_len, (unsigned char*)d[4], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- recoverable ECDSA signing: fec_canon_ecdsa_sign_digest and the recovery id -------------------------------------------------
+int fec_canon_ecdsa_sign_recoverable_digest_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_keys,
+                                                unsigned flags, uint8_t* d_sigs, uint8_t* d_recids, uint8_t* d_status, size_t n,
+                                                void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_digests || !d_keys || !d_sigs || !d_recids || !d_status)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if ((flags & ~1u) || !aligned16(d_digests) || !aligned16(d_keys) || !aligned16(d_sigs)) return FEC_E_ARG;
+  return launch_canon_ecdsa_sign(ctx, curve, Messages{nullptr, nullptr, 0}, d_digests, d_keys, flags, d_sigs, nullptr, d_status, n, stream,
+                                 d_recids);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ecdsa_sign_recoverable_digest(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* keys,
+                                            unsigned flags, uint8_t* sigs, uint8_t* recids, uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!digests || !keys || !sigs || !recids || !status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (flags & ~1u) return FEC_E_ARG;
+  const HostArray a[] = {secret_input(digests, 32), secret_input(keys, 32), secret_output(sigs, 64), output(recids, 1), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_ecdsa_sign(c, curve, Messages{nullptr, nullptr, 0}, (const uint8_t*)d[0], (const uint8_t*)d[1], flags,
+                                   (uint8_t*)d[2], nullptr, (unsigned char*)d[4], m, s, (uint8_t*)d[3]);
   });
 } FEC_ABI_CATCH_STATUS
 

@@ -213,24 +213,40 @@ FEC_DEV fe half_order() {  // (n - 1) / 2
   return h;
 }
 // r = x mod n, s = kinv_m * (z + r d) with kinv_m = k^-1 in Montgomery form; low_s: s > n/2 becomes n - s.
-// Returns the lanes where r or s is zero.
+// Returns the lanes where r or s is zero.  x_ge_n: the lanes where x >= n (r = x - n); flipped: the lanes where low_s
+// replaced s -- the two facts besides y's parity that a recovery id is made of.
 template <class N>
-FEC_DEV lmask ecdsa_rs(const fe& x, const fe& kinv_m, const fe& z, const fe& d, bool low_s, fe& r, fe& s) {
+FEC_DEV lmask ecdsa_rs(const fe& x, const fe& kinv_m, const fe& z, const fe& d, bool low_s, fe& r, fe& s, lmask& x_ge_n,
+                       lmask& flipped) {
   using F = Fn<N>;
   fe t;
   sub256(t, x, N::n());
-  r = fe_select(x, t, F::ge_n(x));                                    // x < p < 2n
+  x_ge_n = F::ge_n(x);
+  r = fe_select(x, t, x_ge_n);                                        // x < p < 2n
   const fe rd = F::mmul(F::mmul(r, N::r2()), d);                      // (r R) d R^-1
   s = F::mmul(F::addn(rd, z), kinv_m);                                // plain * Montgomery = plain
   fe neg;
   sub256(neg, N::n(), s);
   const lmask high = sub256(t, half_order<N>(), s);                   // borrow  <=>  s > (n - 1) / 2
-  s = fe_select(s, neg, low_s ? high : (lmask)0);
+  flipped = low_s ? high : (lmask)0;
+  s = fe_select(s, neg, flipped);
   return fe_is_zero(r) | fe_is_zero(s);
+}
+template <class N>
+FEC_DEV lmask ecdsa_rs(const fe& x, const fe& kinv_m, const fe& z, const fe& d, bool low_s, fe& r, fe& s) {
+  lmask x_ge_n, flipped;
+  return ecdsa_rs<N>(x, kinv_m, z, d, low_s, r, s, x_ge_n, flipped);
+}
+// The recovery id of (r, s) (SEC 1 section 4.1.6): bit 0 = the parity of the y that recovery must lift -- y(kG)'s, turned
+// over when s was replaced by n - s, which is the signature of -kG -- and bit 1 = x(kG) >= n.  Selects only: y, the flip
+// and the comparison all derive from the nonce.
+FEC_DEV u32 ecdsa_recid(u32 y_low_word, lmask flipped, lmask x_ge_n) {
+  return ((y_low_word & 1u) ^ word_select(0u, 1u, flipped)) | word_select(0u, 2u, x_ge_n);
 }
 // NORM_GROUP signatures per lane with one inversion of their nonces (ecdsa_scalars_group's scheme): elements first,
 // first + stride, ...  ks, zs, ds: limbs from the nonce kernel; xy: affine k*G.  Writes r || s big-endian, zeros where
-// st[i] != 0 on entry or r = 0 or s = 0 (st[i] = SIGN_RETRY then).
+// st[i] != 0 on entry or r = 0 or s = 0 (st[i] = SIGN_RETRY then).  REC: also the recovery id to recids[i], 0 where the
+// signature is zeros.
 // (The prefix products are taken by a step instantiated per index, not by a loop: a loop the compiler declines to unroll
 // would index c[] dynamically, and that puts it in scratch memory.)
 template <class N, int J>
@@ -243,9 +259,9 @@ FEC_DEV void nonce_prefix_step(const u32* ks, size_t first, size_t stride, size_
   run = J == 0 ? km : F::mmul(run, km);
   c[J] = run;
 }
-template <class N>
+template <class N, bool REC = false>
 FEC_DEV void ecdsa_sign_group(const u32* ks, const u32* zs, const u32* ds, const u32* xy, bool low_s, u32* sigs,
-                              unsigned char* st, size_t first, size_t stride, size_t n) {
+                              unsigned char* st, size_t first, size_t stride, size_t n, unsigned char* recids = nullptr) {
   using F = Fn<N>;
   static_assert(NORM_GROUP == 8, "nonce_prefix_step is instantiated for eight elements");
   fe c[NORM_GROUP];
@@ -271,9 +287,11 @@ FEC_DEV void ecdsa_sign_group(const u32* ks, const u32* zs, const u32* ds, const
     u = F::mmul(u, F::mmul(k, N::r2()));
     if (live) {
       fe r, s;
-      const lmask zero = ecdsa_rs<N>(ld8(xy + i * 16), kinv_m, ld8(zs + i * 8), ld8(ds + i * 8), low_s, r, s);
+      lmask x_ge_n, flipped;
+      const lmask zero = ecdsa_rs<N>(ld8(xy + i * 16), kinv_m, ld8(zs + i * 8), ld8(ds + i * 8), low_s, r, s, x_ge_n, flipped);
       const u32 was = st[i];
       const lmask drop = zero | lanes_where(was != 0);
+      if constexpr (REC) recids[i] = (unsigned char)word_select(ecdsa_recid(xy[i * 16 + 8], flipped, x_ge_n), 0u, drop);
       st8(sigs + i * 16, zero_where(be_bytes(r), drop));
       st8(sigs + i * 16 + 8, zero_where(be_bytes(s), drop));
       st[i] = (unsigned char)word_select(word_select(was, (u32)SIGN_RETRY, zero), was, lanes_where(was != 0));

@@ -195,6 +195,17 @@ __global__ __launch_bounds__(TPB, 2) void k_canon_ecdsa_sign_finish(const u32* _
   const size_t g = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (g < stride) canon::ecdsa_sign_group<N>(ks, zs, ds, xy, (flags & 1u) != 0, sigs, st, g, stride, n);
 }
+// ... with the recovery ids (fec_canon_ecdsa_sign_recoverable_digest): a kernel of its own, so that the one above stays as
+// it is.  The id is made of selects on what the pass has in registers (canon::ecdsa_recid); its store address is the index.
+template <class N>
+__global__ __launch_bounds__(TPB, 2) void k_canon_ecdsa_sign_finish_rec(const u32* __restrict__ ks, const u32* __restrict__ zs,
+                                                                        const u32* __restrict__ ds, const u32* __restrict__ xy,
+                                                                        unsigned flags, u32* __restrict__ sigs,
+                                                                        unsigned char* __restrict__ recids,
+                                                                        unsigned char* __restrict__ st, size_t n, size_t stride) {
+  const size_t g = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (g < stride) canon::ecdsa_sign_group<N, true>(ks, zs, ds, xy, (flags & 1u) != 0, sigs, st, g, stride, n, recids);
+}
 
 // ---- BIP-340 --------------------------------------------------------------------------------------------------------
 // between the passes: ds = the key's limbs (negated here on odd y), pxy = d*G affine; leaves k' in ks

@@ -284,6 +284,57 @@ int fec_canon_x25519_dev(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* 
 int fec_canon_x25519_base(fec_ctx* ctx, const uint8_t* scalars /* n*32 */, uint8_t* out /* n*32 */, size_t n);
 int fec_canon_x25519_base_dev(fec_ctx* ctx, const uint8_t* d_scalars, uint8_t* d_out, size_t n, void* stream);
 
+/* ---- Keccak-256, ECDSA public-key recovery, recoverable signing ------------------------------------------------------------
+ * What a caller needs to go from a batch of (digest, signature, recovery id) to public keys or Ethereum addresses -- ecrecover,
+ * transaction-sender recovery, Bitcoin signed messages -- and to produce such signatures.  Validated against
+ * tests/canon_recover_ref.py (a Keccak model pinned by hashlib.sha3_256 and published digests; recovery pinned by sign-and-
+ * recover properties over oracle/canon_model.py and by the OpenSSL CLI), never against the reference, which has neither.
+ * Host forms: chunked by fec_ctx_set_chunk, sharded over a multi-device ctx, FEC_E_ARG on a bad message layout.
+ * *_dev forms: digests, sigs, keys 16-byte aligned (recids and status are byte arrays), d_msg_off 8-byte aligned,
+ * FEC_E_UNSUPPORTED on a multi-device ctx.
+ * Not offered: Ethereum's v encodings (27 / 28, EIP-155) -- the recovery id is the raw 0..3; DER and the compact 65-byte
+ * signature packing; SHA3-256 and other Keccak widths; EIP-55 checksummed hex. */
+
+/* Keccak-256 as submitted to the SHA-3 competition and used by Ethereum: rate 136 bytes, padding 0x01 ... 0x80.  NOT FIPS 202
+ * SHA3-256 (padding 0x06).  out[i] = the 32 digest bytes of message i (the layout of fec_sha256).  One message per lane, the
+ * state in registers.  _dev, as fec_sha256_dev: d_out 16-byte aligned; every lane checks its own range, a bad one gets a zero
+ * digest and, where d_status is not NULL, status 4 (0 otherwise). */
+int fec_canon_keccak256(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                        uint8_t* out /* n*32 */, size_t n);
+int fec_canon_keccak256_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_out,
+                            uint8_t* d_status /* n or NULL */, size_t n, void* stream);
+
+/* Public-key recovery (SEC 1 v2 section 4.1.6), FEC_SECP256K1 and FEC_P256 (FEC_ED25519: FEC_E_UNSUPPORTED).
+ * digests: 32 bytes each, z = the bytes read big-endian, reduced mod n (as fec_canon_ecdsa_verify_msg reads a SHA-256);
+ * sigs: r || s big-endian; low-S is not enforced.  recids[i]: bit 0 = the parity of y(R), bit 1 = x(R) is r + n.
+ * Q = r^-1 (s R - z G), computed as u1 G + u2 R by the verifier's comb and windowed accumulate, r^-1 by one inversion per
+ * eight elements.  status[i]: 0, or FEC_CANON_NO_KEY with an all-zero record when recid > 3; r or s is outside [1, n); bit 1
+ * is set and r + n >= p (the sum is taken as a 257-bit value: no wrap-around is accepted); x^3 + a x + b is not a square; or
+ * Q is the point at infinity.
+ * out_len: 33 or 65 = the SEC 1 encoding; 64 = x || y big-endian, the bytes Ethereum hashes; 20 = the last 20 bytes of
+ * Keccak-256(x || y), the Ethereum address (FEC_SECP256K1 only; FEC_P256: FEC_E_ARG).  Any other out_len: FEC_E_ARG.
+ * _dev: d_out 16-byte aligned for out_len 64 and 20. */
+#define FEC_CANON_NO_KEY 8 /* fec_canon_ecdsa_recover: no public key for this (digest, signature, recid); out[i] is zeros */
+int fec_canon_ecdsa_recover(fec_ctx* ctx, fec_curve curve, const uint8_t* digests /* n*32 */, const uint8_t* sigs /* n*64 */,
+                            const uint8_t* recids /* n */, uint8_t* out /* n*out_len */, size_t out_len, uint8_t* status /* n */,
+                            size_t n);
+int fec_canon_ecdsa_recover_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_sigs,
+                                const uint8_t* d_recids, uint8_t* d_out, size_t out_len, uint8_t* d_status, size_t n,
+                                void* stream);
+
+/* fec_canon_ecdsa_sign_digest with the recovery id: signatures and statuses are byte-identical to that call's for the same
+ * inputs; recids[i] = (y(k G) & 1) ^ flipped | (x(k G) >= n) << 1, flipped = 1 exactly where FEC_CANON_SIGN_LOW_S replaced s by
+ * n - s; 0 wherever status[i] is not 0.  The same kernels with one more store in the last: the id is formed by selects from
+ * what that pass holds in registers, and the signing side's guarantee above holds for it in its words.
+ * There is no message-taking form: an Ethereum-style caller chains fec_canon_keccak256_dev into this call's _dev form on the
+ * device, a SHA-256 caller has fec_sha256_dev. */
+int fec_canon_ecdsa_sign_recoverable_digest(fec_ctx* ctx, fec_curve curve, const uint8_t* digests /* n*32 */,
+                                            const uint8_t* keys /* n*32 */, unsigned flags, uint8_t* sigs /* n*64 */,
+                                            uint8_t* recids /* n */, uint8_t* status /* n */, size_t n);
+int fec_canon_ecdsa_sign_recoverable_digest_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_keys,
+                                                unsigned flags, uint8_t* d_sigs, uint8_t* d_recids, uint8_t* d_status, size_t n,
+                                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,17 @@ X25519 (fec_canon_x25519_dev, fec_canon_x25519_base_dev), by the same method:
 Edwards multiplication -- and against parity mode's fec_x25519_dev.  "base" rows: fec_canon_x25519_base_dev against
 fec_canon_mul_base_secret_dev(FEC_ED25519) (the difference is the clamp, the map's inversion and the encoding) and against
 fec_canon_x25519_dev at u = 9, whose outputs must equal the base path's.  Last, one host-pointer row each.
+
+Recovery, Keccak-256 and recoverable signing on secp256k1, by the same method:
+
+    python tools/canon_perf.py recover [log2_n] [reps] [out.jsonl]
+
+The signatures are real (fec_canon_ecdsa_sign_recoverable_digest_dev over random digests and keys) and every one must recover
+to its key.  "recover" rows: fec_canon_ecdsa_recover_dev (out_len 64) against fec_canon_ecdsa_verify_msg_dev with 33-byte
+keys and 32-byte messages -- one square root, one grouped inversion and u1 G + u2 Q each, the verifier with a SHA-256 on top.
+"address" rows: out_len 20 against out_len 64, the cost of the Keccak in the finish pass.  "keccak" rows:
+fec_canon_keccak256_dev against fec_sha256_dev on the same 64-byte messages.  "sign" rows: the recoverable signer against
+fec_canon_ecdsa_sign_digest_dev, whose signatures must be the same bytes.  Last, one host-pointer row each.
 """
 import json
 import os
@@ -389,6 +400,92 @@ def main_x25519():
                 f.write(json.dumps(r) + "\n")
 
 
+def main_recover():
+    from forge_ec_amd.canon import CanonKeccak
+    logn = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    out_path = sys.argv[4] if len(sys.argv) > 4 else None
+    n = 1 << logn
+    ctx = F.Context(0)
+    lib, h = ctx._lib, ctx._h
+    rng = np.random.default_rng(21)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()  # noqa: E731
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    def rounds(fns):
+        """each of fns three times, alternating; per fn the middle round's median and the largest spread"""
+        got = [[] for _ in fns]
+        for _ in range(3):
+            for g, fn in zip(got, fns):
+                g.append(_timed(fn, reps))
+        return [(sorted(g)[1][0], max(x[1] for x in g)) for g in got]
+
+    def pair(row, npass, names, fns, **extra):
+        a, b = rounds(fns)
+        emit(dict({"row": row, "pass": npass, "n": n, "reps": reps, names[0] + "_ms": round(a[0], 4), names[0] + "_spread_ms": round(a[1], 4),
+                   names[1] + "_ms": round(b[0], 4), names[1] + "_spread_ms": round(b[1], 4), "ratio": round(a[0] / b[0], 4),
+                   "M_per_s": round(n / a[0] / 1e3, 3)}, **extra))
+
+    cv, kk = CANON_CURVES["secp256k1"](ctx), CanonKeccak(ctx)
+    keys_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    keys_h[:, 0] &= 0x7F      # big-endian keys below n ...
+    keys_h[:, 31] |= 1        # ... and not zero
+    dg_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    msg64_h = rng.integers(0, 256, size=(n, 64), dtype=np.uint8)
+    keys, dg, msg64 = dev(keys_h), dev(dg_h), dev(msg64_h)
+    off32 = torch.arange(0, 32 * (n + 1), 32, dtype=torch.int64, device="cuda")
+    off64 = torch.arange(0, 64 * (n + 1), 64, dtype=torch.int64, device="cuda")
+    sigs, sigs2 = (torch.empty((n, 64), dtype=torch.uint8, device="cuda") for _ in range(2))
+    rec, stat, stat2, res = (torch.empty(n, dtype=torch.uint8, device="cuda") for _ in range(4))
+    pk33, out33 = (torch.empty((n, 33), dtype=torch.uint8, device="cuda") for _ in range(2))
+    out64 = torch.empty((n, 64), dtype=torch.uint8, device="cuda")
+    out20 = torch.empty((n, 20), dtype=torch.uint8, device="cuda")
+    hash_k, hash_s = (torch.empty((n, 32), dtype=torch.uint8, device="cuda") for _ in range(2))
+    # real signatures with their ids, and what they must recover to
+    cv.ecdsa_sign_recoverable_digest_dev(dg.data_ptr(), keys.data_ptr(), 1, sigs.data_ptr(), rec.data_ptr(), stat.data_ptr(), n, st)
+    cv.public_key_dev(keys.data_ptr(), pk33.data_ptr(), 33, stat2.data_ptr(), n, st)
+    cv.ecdsa_recover_dev(dg.data_ptr(), sigs.data_ptr(), rec.data_ptr(), out33.data_ptr(), 33, res.data_ptr(), n, st)
+    torch.cuda.synchronize()
+    assert not bool(stat.any()) and not bool(stat2.any()) and not bool(res.any()) and bool((out33 == pk33).all())
+    for npass in range(2):
+        pair("recover", npass, ("ecdsa_recover_dev_64", "ecdsa_verify_msg_dev_33"), [
+            lambda: cv.ecdsa_recover_dev(dg.data_ptr(), sigs.data_ptr(), rec.data_ptr(), out64.data_ptr(), 64, res.data_ptr(), n, st),
+            lambda: cv.ecdsa_verify_msg_dev(dg.data_ptr(), off32.data_ptr(), 32 * n, sigs.data_ptr(), pk33.data_ptr(), 33, stat2.data_ptr(), n, st)])
+        pair("address", npass, ("ecdsa_recover_dev_20", "ecdsa_recover_dev_64"), [
+            lambda: cv.ecdsa_recover_dev(dg.data_ptr(), sigs.data_ptr(), rec.data_ptr(), out20.data_ptr(), 20, res.data_ptr(), n, st),
+            lambda: cv.ecdsa_recover_dev(dg.data_ptr(), sigs.data_ptr(), rec.data_ptr(), out64.data_ptr(), 64, res.data_ptr(), n, st)])
+        pair("keccak", npass, ("keccak256_dev_64B", "sha256_dev_64B"), [
+            lambda: kk.keccak256_dev(msg64.data_ptr(), off64.data_ptr(), 64 * n, hash_k.data_ptr(), stat2.data_ptr(), n, st),
+            lambda: lib.fec_sha256_dev(h, msg64.data_ptr(), off64.data_ptr(), 64 * n, hash_s.data_ptr(), stat2.data_ptr(), n, st)])
+        pair("sign", npass, ("sign_recoverable_digest_dev", "sign_digest_dev"), [
+            lambda: cv.ecdsa_sign_recoverable_digest_dev(dg.data_ptr(), keys.data_ptr(), 1, sigs2.data_ptr(), rec.data_ptr(), stat.data_ptr(), n, st),
+            lambda: cv.ecdsa_sign_digest_dev(dg.data_ptr(), keys.data_ptr(), 1, sigs.data_ptr(), stat.data_ptr(), n, st)])
+        torch.cuda.synchronize()
+        assert bool((sigs == sigs2).all()) and not bool(res.any())
+    # the address is the hash of the raw key
+    kk.keccak256_dev(out64.data_ptr(), off64.data_ptr(), 64 * n, hash_k.data_ptr(), None, n, st)
+    torch.cuda.synchronize()
+    assert bool((hash_k[:, 12:] == out20).all())
+    p = lambda a: a.ctypes.data  # noqa: E731
+    sigs_h, rec_h = sigs.cpu().numpy(), rec.cpu().numpy()
+    out_h, st_h, dig_h = np.zeros((n, 20), np.uint8), np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8)
+    off_h = np.arange(0, 64 * (n + 1), 64, dtype=np.uint64)
+    for name, fn in (("ecdsa_recover_20", lambda: lib.fec_canon_ecdsa_recover(h, 0, p(dg_h), p(sigs_h), p(rec_h), p(out_h), 20, p(st_h), n)),
+                     ("keccak256_64B", lambda: lib.fec_canon_keccak256(h, p(msg64_h), p(off_h), 64 * n, p(dig_h), n))):
+        assert fn() == 0
+        ms, spread = _timed(fn, reps)
+        emit({"row": "host-" + name, "n": n, "reps": reps, "ms": round(ms, 4), "spread_ms": round(spread, 4), "M_per_s": round(n / ms / 1e3, 3)})
+    if out_path:
+        with open(out_path, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     logn = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -450,5 +547,7 @@ elif len(sys.argv) > 1 and sys.argv[1] == "sign":
     main_sign()
 elif len(sys.argv) > 1 and sys.argv[1] == "x25519":
     main_x25519()
+elif len(sys.argv) > 1 and sys.argv[1] == "recover":
+    main_recover()
 else:
     main()
