@@ -40,8 +40,11 @@ CANON_ABI_SYMBOLS = [
     "fec_canon_x25519", "fec_canon_x25519_dev", "fec_canon_x25519_base", "fec_canon_x25519_base_dev",
     "fec_canon_keccak256", "fec_canon_keccak256_dev", "fec_canon_ecdsa_recover", "fec_canon_ecdsa_recover_dev",
     "fec_canon_ecdsa_sign_recoverable_digest", "fec_canon_ecdsa_sign_recoverable_digest_dev",
+    "fec_canon_pubkey_tweak_add", "fec_canon_pubkey_tweak_add_dev", "fec_canon_seckey_tweak_add", "fec_canon_seckey_tweak_add_dev",
+    "fec_canon_bip32_derive_pub", "fec_canon_bip32_derive_pub_dev", "fec_canon_bip32_derive_priv", "fec_canon_bip32_derive_priv_dev",
 ]
 CANON_NO_KEY = 8
+CANON_BAD_POINT, CANON_BAD_INDEX, CANON_BIP32_INVALID, CANON_BIP32_NO_COMB = 2, 9, 10, 1
 CANON_BAD_SCALAR, CANON_BAD_KEY, CANON_SIGN_LOW_S, CANON_SCHEME_BIP340 = 3, 6, 1, 3
 CANON_ZERO_SHARED = 7
 F_INV = 5
@@ -309,6 +312,14 @@ def lib():
     L.fec_canon_ecdsa_recover_dev.argtypes = [vp, ci, vp, vp, vp, vp, sz, vp, sz, vp]
     L.fec_canon_ecdsa_sign_recoverable_digest.argtypes = [vp, ci, vp, vp, cu, vp, vp, vp, sz]
     L.fec_canon_ecdsa_sign_recoverable_digest_dev.argtypes = [vp, ci, vp, vp, cu, vp, vp, vp, sz, vp]
+    L.fec_canon_pubkey_tweak_add.argtypes = [vp, ci, vp, sz, vp, vp, sz, vp, sz]
+    L.fec_canon_pubkey_tweak_add_dev.argtypes = [vp, ci, vp, sz, vp, vp, sz, vp, sz, vp]
+    L.fec_canon_seckey_tweak_add.argtypes = [vp, ci, vp, vp, vp, vp, sz]
+    L.fec_canon_seckey_tweak_add_dev.argtypes = [vp, ci, vp, vp, vp, vp, sz, vp]
+    L.fec_canon_bip32_derive_pub.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz]
+    L.fec_canon_bip32_derive_pub_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]
+    L.fec_canon_bip32_derive_priv.argtypes = [vp, vp, vp, sz, vp, cu, vp, vp, vp, sz]
+    L.fec_canon_bip32_derive_priv_dev.argtypes = [vp, vp, vp, sz, vp, cu, vp, vp, vp, sz, vp]
     for n in CANON_ABI_SYMBOLS:
         getattr(L, n).restype = ci
     _lib = L

@@ -156,6 +156,42 @@ class CanonCurve:
         _check(self._lib.fec_canon_ecdsa_recover_dev(self._h, self.CURVE, d_digests, d_sigs, d_recids, d_out, out_len, d_status, n,
                                                      stream), "fec_canon_ecdsa_recover_dev")
 
+    def pubkey_tweak_add(self, pks, tweaks, pk_len=33, out_len=33):
+        """pks[i] + tweaks[i] * G on encoded keys (secp256k1, P-256): pks (n,pk_len) with pk_len 33 / 65 (SEC 1) or 32 (x-only,
+        even y; secp256k1), tweaks (n,32) big-endian -> (out (n,out_len) uint8, status); out_len 33, 65 or 32 (x alone;
+        secp256k1).  status: 0, 2 (the key does not decode), 3 (tweak >= n), 8 (the sum is the point at infinity), zeros then.
+        A tweak of 0 returns the key."""
+        pk, t = _bytes_rows(pks, pk_len, "pks"), _bytes_rows(tweaks, 32, "tweaks")
+        n = pk.shape[0]
+        if t.shape[0] != n:
+            raise ValueError("inputs differ in length")
+        out = np.zeros((n, out_len), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_pubkey_tweak_add(self._h, self.CURVE, _ptr(pk), pk_len, _ptr(t), _ptr(out), out_len, _ptr(st), n),
+               "fec_canon_pubkey_tweak_add")
+        return out, st
+
+    def pubkey_tweak_add_dev(self, d_pks, pk_len, d_tweaks, d_out, out_len, d_status, n, stream=None):
+        _check(self._lib.fec_canon_pubkey_tweak_add_dev(self._h, self.CURVE, d_pks, pk_len, d_tweaks, d_out, out_len, d_status, n,
+                                                        stream), "fec_canon_pubkey_tweak_add_dev")
+
+    def seckey_tweak_add(self, keys, tweaks):
+        """(keys[i] + tweaks[i]) mod n (secp256k1, P-256), (n,32) big-endian each -> (out (n,32), status).  status: 0, 6 (key 0
+        or >= n), 3 (tweak >= n), 8 (the result is 0), zeros then."""
+        k, t = _bytes_rows(keys, 32, "keys"), _bytes_rows(tweaks, 32, "tweaks")
+        n = k.shape[0]
+        if t.shape[0] != n:
+            raise ValueError("inputs differ in length")
+        out = np.zeros((n, 32), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_seckey_tweak_add(self._h, self.CURVE, _ptr(k), _ptr(t), _ptr(out), _ptr(st), n),
+               "fec_canon_seckey_tweak_add")
+        return out, st
+
+    def seckey_tweak_add_dev(self, d_keys, d_tweaks, d_out, d_status, n, stream=None):
+        _check(self._lib.fec_canon_seckey_tweak_add_dev(self._h, self.CURVE, d_keys, d_tweaks, d_out, d_status, n, stream),
+               "fec_canon_seckey_tweak_add_dev")
+
     def ecdsa_sign_msg(self, msgs, keys, flags=0):
         """ECDSA with SHA-256 and RFC 6979 nonces from the message: msgs a list of n byte strings -> (sigs, status)."""
         return _sign_msg(self._lib.fec_canon_ecdsa_sign_msg, self._h, msgs, [keys], "fec_canon_ecdsa_sign_msg", lead=(self.CURVE,),
@@ -447,6 +483,56 @@ class CanonKeccak:
         """d_status may be None; else 4 marks a bad range (zero digest)."""
         _check(self._lib.fec_canon_keccak256_dev(self._h, d_msgs, d_msg_off, msg_len, d_out, d_status, n, stream),
                "fec_canon_keccak256_dev")
+
+
+class CanonBip32:
+    """BIP-32 child key derivation on secp256k1: CKDpub and CKDpriv over batches of (parent, chain code, index).  Parents and
+    chain codes are (n,33) / (n,32) uint8 arrays, lists of byte strings or bytes; ONE parent -- given as bytes or as a (1,33) /
+    (1,32) array -- with n > 1 indices is the shared-parent case (one xpub, many children).  status: 0, 2 / 6 (bad parent
+    public / secret key), 9 (L.CANON_BAD_INDEX), 10 (L.CANON_BIP32_INVALID: take the next index; unobservable); zeros then."""
+
+    def __init__(self, ctx=None, device=0):
+        self.ctx = ctx if ctx is not None else Context(device)
+        self._lib = self.ctx._lib
+        self._h = self.ctx._h
+
+    @staticmethod
+    def _parents(keys, width, ccs, n):
+        k, c = _bytes_rows(keys, width, "parents"), _bytes_rows(ccs, 32, "chain codes")
+        if k.shape[0] != c.shape[0] or k.shape[0] not in (n, 1):
+            raise ValueError("parents and chain codes must number the indices, or one")
+        return k, c
+
+    def derive_pub(self, parent_pks, parent_ccs, indices):
+        """CKDpub: (child keys (n,33), child chain codes (n,32), status); an index >= 2^31 gets status 9."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32)).reshape(-1)
+        n = idx.shape[0]
+        pk, cc = self._parents(parent_pks, 33, parent_ccs, n)
+        out, occ = np.zeros((n, 33), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_bip32_derive_pub(self._h, _ptr(pk), _ptr(cc), pk.shape[0], _ptr(idx), _ptr(out), _ptr(occ), _ptr(st), n),
+               "fec_canon_bip32_derive_pub")
+        return out, occ, st
+
+    def derive_pub_dev(self, d_parent_pks, d_parent_ccs, n_par, d_indices, d_out_pks, d_out_ccs, d_status, n, stream=None):
+        _check(self._lib.fec_canon_bip32_derive_pub_dev(self._h, d_parent_pks, d_parent_ccs, n_par, d_indices, d_out_pks, d_out_ccs,
+                                                        d_status, n, stream), "fec_canon_bip32_derive_pub_dev")
+
+    def derive_priv(self, parent_keys, parent_ccs, indices, flags=0):
+        """CKDpriv, hardened and non-hardened indices mixed: (child keys (n,32), child chain codes (n,32), status).
+        flags = L.CANON_BIP32_NO_COMB: every index is hardened, the comb pass is skipped (a non-hardened one gets status 9)."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32)).reshape(-1)
+        n = idx.shape[0]
+        k, cc = self._parents(parent_keys, 32, parent_ccs, n)
+        out, occ = np.zeros((n, 32), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_bip32_derive_priv(self._h, _ptr(k), _ptr(cc), k.shape[0], _ptr(idx), flags, _ptr(out), _ptr(occ),
+                                                     _ptr(st), n), "fec_canon_bip32_derive_priv")
+        return out, occ, st
+
+    def derive_priv_dev(self, d_parent_keys, d_parent_ccs, n_par, d_indices, flags, d_out_keys, d_out_ccs, d_status, n, stream=None):
+        _check(self._lib.fec_canon_bip32_derive_priv_dev(self._h, d_parent_keys, d_parent_ccs, n_par, d_indices, flags, d_out_keys,
+                                                         d_out_ccs, d_status, n, stream), "fec_canon_bip32_derive_priv_dev")
 
 
 CANON_CURVES = {"secp256k1": CanonSecp256k1, "p256": CanonP256, "ed25519": CanonEd25519}

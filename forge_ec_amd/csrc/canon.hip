@@ -10,6 +10,7 @@
 #include "canon_sign_kernels.hpp"
 #include "canon_x25519_kernels.hpp"
 #include "canon_recover_kernels.hpp"
+#include "canon_bip32_kernels.hpp"
 
 using namespace fecgpu;
 using namespace fecgpu::host;
@@ -576,6 +577,126 @@ int launch_canon_ecdsa_recover(fec_ctx* ctx, int curve, const uint8_t* d_digests
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 
+// ---- tweak-add and BIP-32 derivation (canon_bip32.hpp, canon_bip32_kernels.hpp) ---------------------------------------------
+// The public side: prepare -> t*G by the comb (finish = false) -> k_canon_add_affine -> normalisation -> finish.  Work area in
+// d_verify: the shared parent's block (256 bytes), t (n*32), xy (n*64), the affine addend (n*64), point status (n), flags (n).
+struct TweakWork {
+  u32* shared;
+  u64 *t, *xy, *q;
+  unsigned char *pst, *flag;
+};
+int tweak_work(fec_ctx* ctx, size_t n, TweakWork& w) {
+  const int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, 256 + n * (32 + 64 + 64 + 1 + 1) + 64);
+  if (rc != FEC_OK) return rc;
+  char* base = (char*)ctx->d_verify;
+  w.shared = (u32*)base;
+  w.t = (u64*)(base + 256);
+  w.xy = (u64*)(base + 256 + n * 32);
+  w.q = (u64*)(base + 256 + n * 96);
+  w.pst = (unsigned char*)(base + 256 + n * 160);
+  w.flag = w.pst + n;
+  return FEC_OK;
+}
+inline bool tweak_len_ok(int curve, size_t len) { return len == 33 || len == 65 || (len == 32 && curve == FEC_SECP256K1); }
+// Everything after the prepare kernel, which has filled w.t, w.q and w.flag.  ccs: the child chain codes (BIP-32) or null.
+int launch_canon_tweak_tail(fec_ctx* ctx, int curve, const TweakWork& w, unsigned char at_infinity, uint8_t* d_out, size_t out_len,
+                            u32* ccs, unsigned char* dst, size_t n, void* stream) {
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;   // the prepare kernel's launch
+  int rc = launch_canon_mul_base(ctx, curve, w.t, w.xy, w.pst, n, stream, false);
+  if (rc != FEC_OK) return rc;
+  dim3 g(grid_for(n)), b(TPB);
+  u32* z = reinterpret_cast<u32*>(ctx->d_zbuf);
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_add_affine<csecp>), g, b, 0, s, (u32*)w.xy, z, (const u32*)w.q, w.pst, n);
+  else hipLaunchKernelGGL((k_canon_add_affine<cp256>), g, b, 0, s, (u32*)w.xy, z, (const u32*)w.q, w.pst, n);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  rc = launch_canon_normalize(ctx, curve, w.xy, w.pst, n, s);
+  if (rc != FEC_OK) return rc;
+  const u32* cxy = (const u32*)w.xy;
+  const unsigned char *cflag = w.flag, *cpst = w.pst;
+  if (out_len == 32) hipLaunchKernelGGL(k_canon_tweak_finish<32>, g, b, 0, s, cxy, cflag, cpst, at_infinity, d_out, ccs, dst, n);
+  else if (out_len == 33) hipLaunchKernelGGL(k_canon_tweak_finish<33>, g, b, 0, s, cxy, cflag, cpst, at_infinity, d_out, ccs, dst, n);
+  else hipLaunchKernelGGL(k_canon_tweak_finish<65>, g, b, 0, s, cxy, cflag, cpst, at_infinity, d_out, ccs, dst, n);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+int launch_canon_pubkey_tweak_add(fec_ctx* ctx, int curve, const uint8_t* d_pks, size_t pk_len, const uint8_t* d_tweaks, uint8_t* d_out,
+                                  size_t out_len, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  TweakWork w;
+  const int rc = tweak_work(ctx, n, w);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // the work area is the ctx's
+  dim3 g(grid_for(n)), b(TPB);
+  if (curve == FEC_SECP256K1)
+    hipLaunchKernelGGL((k_canon_tweak_prepare<canon::SecpParams>), g, b, 0, s, d_pks, (int)pk_len, (const u32*)d_tweaks, (u32*)w.t, (u32*)w.q, w.flag, n);
+  else
+    hipLaunchKernelGGL((k_canon_tweak_prepare<canon::P256Params>), g, b, 0, s, d_pks, (int)pk_len, (const u32*)d_tweaks, (u32*)w.t, (u32*)w.q, w.flag, n);
+  return launch_canon_tweak_tail(ctx, curve, w, canon::TWK_NO_KEY, d_out, out_len, nullptr, dst, n, stream);
+}
+// CKDpub (secp256k1).  shared: one parent and one chain code for the whole batch.
+int launch_canon_bip32_derive_pub(fec_ctx* ctx, const uint8_t* d_pks, const uint8_t* d_ccs, bool shared, const uint32_t* d_idx,
+                                  uint8_t* d_out_pks, uint8_t* d_out_ccs, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  using P = canon::SecpParams;
+  TweakWork w;
+  const int rc = tweak_work(ctx, n, w);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // the work area is the ctx's
+  dim3 g(grid_for(n)), b(TPB);
+  if (shared) {
+    hipLaunchKernelGGL((k_canon_bip32_parent<P>), dim3(1), dim3(64), 0, s, d_pks, (const u32*)d_ccs, w.shared);
+    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, true>), g, b, 0, s, d_pks, (const u32*)d_ccs, (const u32*)w.shared, d_idx, (u32*)w.t,
+                       (u32*)w.q, (u32*)d_out_ccs, w.flag, n);
+  } else {
+    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, false>), g, b, 0, s, d_pks, (const u32*)d_ccs, (const u32*)w.shared, d_idx, (u32*)w.t,
+                       (u32*)w.q, (u32*)d_out_ccs, w.flag, n);
+  }
+  return launch_canon_tweak_tail(ctx, FEC_SECP256K1, w, canon::BIP32_INVALID, d_out_pks, 33, (u32*)d_out_ccs, dst, n, stream);
+}
+int launch_canon_seckey_tweak_add(fec_ctx* ctx, int curve, const uint8_t* d_keys, const uint8_t* d_tweaks, uint8_t* d_out,
+                                  unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  hipStream_t s = sign_stream(ctx, stream);
+  dim3 g(grid_for(n)), b(TPB);
+  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_seckey_tweak_add<canon::NSecp>), g, b, 0, s, (const u32*)d_keys, (const u32*)d_tweaks, (u32*)d_out, dst, n);
+  else hipLaunchKernelGGL((k_canon_seckey_tweak_add<canon::NP256>), g, b, 0, s, (const u32*)d_keys, (const u32*)d_tweaks, (u32*)d_out, dst, n);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+// CKDpriv (secp256k1): key limbs -> the secret comb over the n_par parents (skipped under FEC_CANON_BIP32_NO_COMB) -> the
+// derivation kernel.  The parents' limbs, k*G and Z live in one SignArea, cleared behind the last kernel on every way out.
+int launch_canon_bip32_derive_priv(fec_ctx* ctx, const uint8_t* d_keys, const uint8_t* d_ccs, size_t n_par, const uint32_t* d_idx,
+                                   unsigned flags, uint8_t* d_out_keys, uint8_t* d_out_ccs, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  const bool comb = (flags & FEC_CANON_BIP32_NO_COMB) == 0;
+  hipStream_t s = sign_stream(ctx, stream);
+  SignArea a;
+  int rc = a.open(ctx, s, r256(n_par * 32) + r256(n_par * 64) + r256(n_par) + comb_area_bytes(n_par));
+  if (rc != FEC_OK) return rc;
+  u32 *ds = a.take<u32>(n_par * 32), *xy = a.take<u32>(n_par * 64);
+  unsigned char* kst = a.take<unsigned char>(n_par);
+  CombArea c;
+  c.take(a, n_par);
+  if (hipMemsetAsync(c.flag, 0, 4, s) != hipSuccess) return FEC_E_DEVICE;
+  hipLaunchKernelGGL((k_canon_key_limbs<canon::NSecp>), dim3(grid_for(n_par)), dim3(TPB), 0, s, (const u32*)d_keys, ds, kst, n_par);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  if (comb) {
+    rc = launch_secret_comb(ctx, FEC_SECP256K1, ds, xy, c, n_par, s);
+    if (rc != FEC_OK) return rc;
+  }
+  dim3 g(grid_for(n)), b(TPB);
+  const size_t per_elem = n_par == n ? 1 : 0;
+  if (comb)
+    hipLaunchKernelGGL(k_canon_bip32_priv<true>, g, b, 0, s, (const u32*)ds, (const unsigned char*)kst, (const u32*)xy, (const u32*)d_ccs, per_elem,
+                       d_idx, (u32*)d_out_keys, (u32*)d_out_ccs, dst, n);
+  else
+    hipLaunchKernelGGL(k_canon_bip32_priv<false>, g, b, 0, s, (const u32*)ds, (const unsigned char*)kst, (const u32*)xy, (const u32*)d_ccs, per_elem,
+                       d_idx, (u32*)d_out_keys, (u32*)d_out_ccs, dst, n);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  return comb ? launch_secret_report(ctx, FEC_SECP256K1, c, s) : FEC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1065,6 +1186,99 @@ int fec_canon_ecdsa_sign_recoverable_digest(fec_ctx* ctx, fec_curve curve, const
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_canon_ecdsa_sign(c, curve, Messages{nullptr, nullptr, 0}, (const uint8_t*)d[0], (const uint8_t*)d[1], flags,
                                    (uint8_t*)d[2], nullptr, (unsigned char*)d[4], m, s, (uint8_t*)d[3]);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- EC tweak-add: Q = P + t G on encoded keys, k' = k + t mod n ---------------------------------------------------------------
+int fec_canon_pubkey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_pks, size_t pk_len, const uint8_t* d_tweaks,
+                                   uint8_t* d_out, size_t out_len, uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_pks || !d_tweaks || !d_out || !d_status)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!tweak_len_ok(curve, pk_len) || !tweak_len_ok(curve, out_len) || !aligned16(d_tweaks)) return FEC_E_ARG;
+  if ((pk_len == 32 && !aligned16(d_pks)) || (out_len == 32 && !aligned16(d_out))) return FEC_E_ARG;
+  return launch_canon_pubkey_tweak_add(ctx, curve, d_pks, pk_len, d_tweaks, d_out, out_len, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_pubkey_tweak_add(fec_ctx* ctx, fec_curve curve, const uint8_t* pks, size_t pk_len, const uint8_t* tweaks, uint8_t* out,
+                               size_t out_len, uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!pks || !tweaks || !out || !status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!tweak_len_ok(curve, pk_len) || !tweak_len_ok(curve, out_len)) return FEC_E_ARG;
+  const HostArray a[] = {input(pks, pk_len), input(tweaks, 32), output(out, out_len), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_pubkey_tweak_add(c, curve, (const uint8_t*)d[0], pk_len, (const uint8_t*)d[1], (uint8_t*)d[2], out_len,
+                                         (unsigned char*)d[3], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_seckey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_keys, const uint8_t* d_tweaks, uint8_t* d_out,
+                                   uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n && (!d_keys || !d_tweaks || !d_out || !d_status)) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!aligned16(d_keys) || !aligned16(d_tweaks) || !aligned16(d_out)) return FEC_E_ARG;
+  return launch_canon_seckey_tweak_add(ctx, curve, d_keys, d_tweaks, d_out, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_seckey_tweak_add(fec_ctx* ctx, fec_curve curve, const uint8_t* keys, const uint8_t* tweaks, uint8_t* out, uint8_t* status,
+                               size_t n) try {
+  if (!ctx || (n && (!keys || !tweaks || !out || !status))) return FEC_E_ARG;
+  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  const HostArray a[] = {secret_input(keys, 32), secret_input(tweaks, 32), secret_output(out, 32), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_seckey_tweak_add(c, curve, (const uint8_t*)d[0], (const uint8_t*)d[1], (uint8_t*)d[2], (unsigned char*)d[3], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- BIP-32 child key derivation (secp256k1) -------------------------------------------------------------------------------------
+int fec_canon_bip32_derive_pub_dev(fec_ctx* ctx, const uint8_t* d_parent_pks, const uint8_t* d_parent_ccs, size_t n_par,
+                                   const uint32_t* d_indices, uint8_t* d_out_pks, uint8_t* d_out_ccs, uint8_t* d_status, size_t n,
+                                   void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n_par != n && n_par != 1) return FEC_E_ARG;
+  if (n && (!d_parent_pks || !d_parent_ccs || !d_indices || !d_out_pks || !d_out_ccs || !d_status)) return FEC_E_ARG;
+  if (!aligned16(d_parent_ccs) || !aligned16(d_out_ccs) || (reinterpret_cast<uintptr_t>(d_indices) & 3u)) return FEC_E_ARG;
+  return launch_canon_bip32_derive_pub(ctx, d_parent_pks, d_parent_ccs, n_par != n, d_indices, d_out_pks, d_out_ccs, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_bip32_derive_pub(fec_ctx* ctx, const uint8_t* parent_pks, const uint8_t* parent_ccs, size_t n_par, const uint32_t* indices,
+                               uint8_t* out_pks, uint8_t* out_ccs, uint8_t* status, size_t n) try {
+  if (!ctx || (n_par != n && n_par != 1)) return FEC_E_ARG;
+  if (n && (!parent_pks || !parent_ccs || !indices || !out_pks || !out_ccs || !status)) return FEC_E_ARG;
+  const bool shared = n_par != n;
+  const HostArray a[] = {shared ? shared_input(parent_pks, 33) : input(parent_pks, 33),
+                         shared ? shared_input(parent_ccs, 32) : input(parent_ccs, 32),
+                         input(indices, 4), output(out_pks, 33), output(out_ccs, 32), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_bip32_derive_pub(c, (const uint8_t*)d[0], (const uint8_t*)d[1], shared, (const uint32_t*)d[2], (uint8_t*)d[3],
+                                         (uint8_t*)d[4], (unsigned char*)d[5], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_bip32_derive_priv_dev(fec_ctx* ctx, const uint8_t* d_parent_keys, const uint8_t* d_parent_ccs, size_t n_par,
+                                    const uint32_t* d_indices, unsigned flags, uint8_t* d_out_keys, uint8_t* d_out_ccs, uint8_t* d_status,
+                                    size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if ((n_par != n && n_par != 1) || (flags & ~(unsigned)FEC_CANON_BIP32_NO_COMB)) return FEC_E_ARG;
+  if (n && (!d_parent_keys || !d_parent_ccs || !d_indices || !d_out_keys || !d_out_ccs || !d_status)) return FEC_E_ARG;
+  if (!aligned16(d_parent_keys) || !aligned16(d_parent_ccs) || !aligned16(d_out_keys) || !aligned16(d_out_ccs) ||
+      (reinterpret_cast<uintptr_t>(d_indices) & 3u))
+    return FEC_E_ARG;
+  return launch_canon_bip32_derive_priv(ctx, d_parent_keys, d_parent_ccs, n_par, d_indices, flags, d_out_keys, d_out_ccs, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_bip32_derive_priv(fec_ctx* ctx, const uint8_t* parent_keys, const uint8_t* parent_ccs, size_t n_par, const uint32_t* indices,
+                                unsigned flags, uint8_t* out_keys, uint8_t* out_ccs, uint8_t* status, size_t n) try {
+  if (!ctx || (n_par != n && n_par != 1) || (flags & ~(unsigned)FEC_CANON_BIP32_NO_COMB)) return FEC_E_ARG;
+  if (n && (!parent_keys || !parent_ccs || !indices || !out_keys || !out_ccs || !status)) return FEC_E_ARG;
+  const bool shared = n_par != n;
+  const HostArray shared_key = {parent_keys, 0, 32, false, true, true}, shared_cc = {parent_ccs, 0, 32, false, true, true};
+  const HostArray a[] = {shared ? shared_key : secret_input(parent_keys, 32), shared ? shared_cc : secret_input(parent_ccs, 32),
+                         input(indices, 4), secret_output(out_keys, 32), secret_output(out_ccs, 32), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_bip32_derive_priv(c, (const uint8_t*)d[0], (const uint8_t*)d[1], shared ? 1 : m, (const uint32_t*)d[2], flags,
+                                          (uint8_t*)d[3], (uint8_t*)d[4], (unsigned char*)d[5], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 

@@ -335,6 +335,75 @@ int fec_canon_ecdsa_sign_recoverable_digest_dev(fec_ctx* ctx, fec_curve curve, c
                                                 unsigned flags, uint8_t* d_sigs, uint8_t* d_recids, uint8_t* d_status, size_t n,
                                                 void* stream);
 
+/* ---- EC tweak-add and BIP-32 child key derivation --------------------------------------------------------------------------
+ * The keys the calls above work on: Q = P + t G on encoded public keys, k' = k + t mod n on secret keys, and BIP-32's CKDpub /
+ * CKDpriv built on them with t = IL of HMAC-SHA-512(chain code, ...) -- gap-limit scanning of xpubs, deposit addresses,
+ * re-deriving child keys; Taproot output keys (BIP-341), pay-to-contract and libsecp256k1's ec_pubkey_tweak_add /
+ * ec_seckey_tweak_add are the same two primitives.  Validated against tests/canon_bip32_ref.py (hmac / hashlib over
+ * oracle/canon_model.py, pinned by BIP-32 test vector 1), never against the reference, which has no derivation.
+ * The public calls: the comb computes t G without doublings, one mixed addition (all of its exceptional cases live: t = 0,
+ * P == t G, P == -t G) puts the key on it, the batched normalisation and an encoding kernel finish.  A refused element runs as
+ * t = 1, P = G and is dropped by its flag.
+ * The secret calls (fec_canon_seckey_tweak_add, fec_canon_bip32_derive_priv): the signing side's guarantee above holds for
+ * their kernels in its words -- no load or store address, no branch and no trip count depends on a key, on IL or on an
+ * intermediate, above the field layer: the HMAC is straight-line code on registers, the message of a hardened or a normal
+ * child is chosen by the index (public) and still by select, the child key is an addition and a select, every status a
+ * comparison and a select; the parent's public key comes from the secret comb.  The field layer keeps its rare wave-uniform
+ * legs, so the path is not called constant-time.  All work of fec_canon_bip32_derive_priv lives in one work area, cleared
+ * behind its last kernel on every way out; host forms stage keys, chain codes and child keys as secrets.
+ * Host forms: chunked by fec_ctx_set_chunk, sharded over a multi-device ctx.  *_dev forms: every 32- and 64-byte record array
+ * 16-byte aligned (33- and 65-byte records: any alignment), indices 4-byte aligned, FEC_E_UNSUPPORTED on a multi-device ctx.
+ * Every status but 0 comes with zero records.
+ * Not offered: xpub / xprv Base58Check serialisation and fingerprints (they need RIPEMD-160); master-key generation from a
+ * seed; SLIP-10 (the P-256 and Ed25519 variants); the TapTweak tagged hash (prepend the 64-byte tag prefix and use
+ * fec_sha256_dev); whole-path derivation in one call (chain the *_dev calls level by level). */
+#define FEC_CANON_BAD_INDEX 9       /* derive_pub: index >= 2^31; derive_priv under FEC_CANON_BIP32_NO_COMB: index < 2^31 */
+#define FEC_CANON_BIP32_INVALID 10  /* IL >= n, or the child is the point at infinity / the key 0: BIP-32 says to take the next
+                                       index; unobservable (below 2^-127) */
+#define FEC_CANON_BIP32_NO_COMB 1u  /* flags bit 0 of fec_canon_bip32_derive_priv: every index is hardened, skip the comb pass */
+
+/* out[i] = pks[i] + tweaks[i] G, FEC_SECP256K1 and FEC_P256 (FEC_ED25519: FEC_E_UNSUPPORTED).  pks: one form per call, pk_len 33
+ * or 65 (SEC 1, by the rules of fec_canon_ecdsa_verify_msg) or 32 (x-only: the point with even y; FEC_SECP256K1 only); tweaks: 32
+ * bytes big-endian; out_len 33, 65 or 32 (x alone, FEC_SECP256K1 only).  Another pk_len or out_len: FEC_E_ARG.
+ * status[i]: 0; FEC_CANON_BAD_POINT: the key does not decode; FEC_CANON_BAD_SCALAR: tweak >= n; FEC_CANON_NO_KEY: the sum is the
+ * point at infinity.  A tweak of 0 is accepted and returns the key. */
+int fec_canon_pubkey_tweak_add(fec_ctx* ctx, fec_curve curve, const uint8_t* pks /* n*pk_len */, size_t pk_len,
+                               const uint8_t* tweaks /* n*32 */, uint8_t* out /* n*out_len */, size_t out_len, uint8_t* status /* n */,
+                               size_t n);
+int fec_canon_pubkey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_pks, size_t pk_len, const uint8_t* d_tweaks,
+                                   uint8_t* d_out, size_t out_len, uint8_t* d_status, size_t n, void* stream);
+
+/* out[i] = (keys[i] + tweaks[i]) mod n, 32 bytes big-endian each.  status[i]: 0; FEC_CANON_BAD_KEY: key 0 or >= n;
+ * FEC_CANON_BAD_SCALAR: tweak >= n; FEC_CANON_NO_KEY: the result is 0. */
+int fec_canon_seckey_tweak_add(fec_ctx* ctx, fec_curve curve, const uint8_t* keys /* n*32 */, const uint8_t* tweaks /* n*32 */,
+                               uint8_t* out /* n*32 */, uint8_t* status /* n */, size_t n);
+int fec_canon_seckey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_keys, const uint8_t* d_tweaks, uint8_t* d_out,
+                                   uint8_t* d_status, size_t n, void* stream);
+
+/* BIP-32 CKDpub on secp256k1: I = HMAC-SHA-512(cc, serP(K) || ser32(i)), child key = IL G + K as 33 bytes, child chain code = IR.
+ * n_par = n: parent i and chain code i for element i; n_par = 1: one parent and chain code for all -- decoded once, the HMAC's
+ * two key blocks compressed once -- with results identical to the replicated form; another n_par: FEC_E_ARG.
+ * status[i]: 0; FEC_CANON_BAD_POINT: bad parent key; FEC_CANON_BAD_INDEX: index >= 2^31; FEC_CANON_BIP32_INVALID -- in that
+ * order. */
+int fec_canon_bip32_derive_pub(fec_ctx* ctx, const uint8_t* parent_pks /* n_par*33 */, const uint8_t* parent_ccs /* n_par*32 */,
+                               size_t n_par, const uint32_t* indices /* n */, uint8_t* out_pks /* n*33 */, uint8_t* out_ccs /* n*32 */,
+                               uint8_t* status /* n */, size_t n);
+int fec_canon_bip32_derive_pub_dev(fec_ctx* ctx, const uint8_t* d_parent_pks, const uint8_t* d_parent_ccs, size_t n_par,
+                                   const uint32_t* d_indices, uint8_t* d_out_pks, uint8_t* d_out_ccs, uint8_t* d_status, size_t n,
+                                   void* stream);
+
+/* BIP-32 CKDpriv on secp256k1, hardened and non-hardened indices mixed: I = HMAC-SHA-512(cc, serP(k G) || ser32(i)) for
+ * i < 2^31 (k G through the secret comb), HMAC-SHA-512(cc, 0x00 || ser256(k) || ser32(i)) otherwise; child key = IL + k mod n.
+ * flags: FEC_CANON_BIP32_NO_COMB or 0 (other bits: FEC_E_ARG); n_par as above (one comb pass over n_par keys).
+ * status[i]: 0; FEC_CANON_BAD_KEY: parent key 0 or >= n; FEC_CANON_BAD_INDEX: a non-hardened index under
+ * FEC_CANON_BIP32_NO_COMB; FEC_CANON_BIP32_INVALID: IL >= n or child key 0 -- in that order. */
+int fec_canon_bip32_derive_priv(fec_ctx* ctx, const uint8_t* parent_keys /* n_par*32 */, const uint8_t* parent_ccs /* n_par*32 */,
+                                size_t n_par, const uint32_t* indices /* n */, unsigned flags, uint8_t* out_keys /* n*32 */,
+                                uint8_t* out_ccs /* n*32 */, uint8_t* status /* n */, size_t n);
+int fec_canon_bip32_derive_priv_dev(fec_ctx* ctx, const uint8_t* d_parent_keys, const uint8_t* d_parent_ccs, size_t n_par,
+                                    const uint32_t* d_indices, unsigned flags, uint8_t* d_out_keys, uint8_t* d_out_ccs,
+                                    uint8_t* d_status, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

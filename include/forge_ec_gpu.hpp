@@ -1194,6 +1194,57 @@ inline SignResult ed25519_sign_msg(GpuContext& ctx, const std::vector<std::strin
                                    r.status.data(), n));
   return r;
 }
+// ---- EC tweak-add and BIP-32 child key derivation (see fecgpu_canon.h for the statuses) ----
+// keys[i] + tweaks[i] * G on encoded keys: key_len / out_len 33, 65 or (secp256k1) 32; {n * out_len bytes, status}
+template <fec_curve C>
+inline std::pair<std::vector<uint8_t>, std::vector<uint8_t>> pubkey_tweak_add(GpuContext& ctx, const std::vector<uint8_t>& keys, size_t key_len,
+                                                                              const std::vector<eddsa::Bytes32>& tweaks, size_t out_len) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "the tweak-add is offered on secp256k1 and P-256");
+  const size_t n = tweaks.size();
+  if (key_len == 0 || keys.size() != n * key_len) throw Error(FEC_E_ARG);
+  std::vector<uint8_t> out(n * out_len), st(n);
+  check(fec_canon_pubkey_tweak_add(ctx.raw(), C, keys.data(), key_len, reinterpret_cast<const uint8_t*>(tweaks.data()), out.data(), out_len,
+                                   st.data(), n));
+  return {std::move(out), std::move(st)};
+}
+// (keys[i] + tweaks[i]) mod n, 32 bytes big-endian each
+template <fec_curve C>
+inline std::pair<std::vector<eddsa::Bytes32>, std::vector<uint8_t>> seckey_tweak_add(GpuContext& ctx, const std::vector<eddsa::Bytes32>& keys,
+                                                                                     const std::vector<eddsa::Bytes32>& tweaks) {
+  static_assert(C == FEC_SECP256K1 || C == FEC_P256, "the tweak-add is offered on secp256k1 and P-256");
+  const size_t n = keys.size();
+  if (tweaks.size() != n) throw Error(FEC_E_ARG);
+  std::vector<eddsa::Bytes32> out(n);
+  std::vector<uint8_t> st(n);
+  check(fec_canon_seckey_tweak_add(ctx.raw(), C, reinterpret_cast<const uint8_t*>(keys.data()), reinterpret_cast<const uint8_t*>(tweaks.data()),
+                                   reinterpret_cast<uint8_t*>(out.data()), st.data(), n));
+  return {std::move(out), std::move(st)};
+}
+// BIP-32 on secp256k1.  parents: n of them (33 / 32 bytes each) with n chain codes, or one of each for all the indices.
+struct Bip32Result {
+  std::vector<uint8_t> keys;               // n * 33 (derive_pub) or n * 32 (derive_priv) bytes
+  std::vector<eddsa::Bytes32> chain_codes;
+  std::vector<uint8_t> status;             // 0, 2 / 6 (bad parent), FEC_CANON_BAD_INDEX, FEC_CANON_BIP32_INVALID
+};
+inline Bip32Result bip32_derive_pub(GpuContext& ctx, const std::vector<uint8_t>& parent_keys, const std::vector<eddsa::Bytes32>& parent_ccs,
+                                    const std::vector<uint32_t>& indices) {
+  const size_t n = indices.size(), n_par = parent_ccs.size();
+  if (parent_keys.size() != n_par * 33) throw Error(FEC_E_ARG);
+  Bip32Result r{std::vector<uint8_t>(n * 33), std::vector<eddsa::Bytes32>(n), std::vector<uint8_t>(n)};
+  check(fec_canon_bip32_derive_pub(ctx.raw(), parent_keys.data(), reinterpret_cast<const uint8_t*>(parent_ccs.data()), n_par, indices.data(),
+                                   r.keys.data(), reinterpret_cast<uint8_t*>(r.chain_codes.data()), r.status.data(), n));
+  return r;
+}
+// flags: FEC_CANON_BIP32_NO_COMB (every index is hardened) or 0
+inline Bip32Result bip32_derive_priv(GpuContext& ctx, const std::vector<eddsa::Bytes32>& parent_keys, const std::vector<eddsa::Bytes32>& parent_ccs,
+                                     const std::vector<uint32_t>& indices, unsigned flags = 0) {
+  const size_t n = indices.size(), n_par = parent_ccs.size();
+  if (parent_keys.size() != n_par) throw Error(FEC_E_ARG);
+  Bip32Result r{std::vector<uint8_t>(n * 32), std::vector<eddsa::Bytes32>(n), std::vector<uint8_t>(n)};
+  check(fec_canon_bip32_derive_priv(ctx.raw(), reinterpret_cast<const uint8_t*>(parent_keys.data()), reinterpret_cast<const uint8_t*>(parent_ccs.data()),
+                                    n_par, indices.data(), flags, r.keys.data(), reinterpret_cast<uint8_t*>(r.chain_codes.data()), r.status.data(), n));
+  return r;
+}
 }  // namespace canon
 
 using Secp256k1 = Curve<FEC_SECP256K1>;

@@ -47,6 +47,20 @@ keys and 32-byte messages -- one square root, one grouped inversion and u1 G + u
 "address" rows: out_len 20 against out_len 64, the cost of the Keccak in the finish pass.  "keccak" rows:
 fec_canon_keccak256_dev against fec_sha256_dev on the same 64-byte messages.  "sign" rows: the recoverable signer against
 fec_canon_ecdsa_sign_digest_dev, whose signatures must be the same bytes.  Last, one host-pointer row each.
+
+EC tweak-add and BIP-32 derivation on secp256k1, by the same method:
+
+    python tools/canon_perf.py bip32 [log2_n] [reps] [out.jsonl]
+
+Before anything is timed: derive_priv -> public_key must equal derive_pub, chain codes included, and pubkey_tweak_add must equal
+public_key(seckey_tweak_add).  "tweak" rows: fec_canon_pubkey_tweak_add_dev on 33-byte keys against fec_canon_decompress_dev(33)
+followed by fec_canon_mul_base_dev on the same batch (its square root and its comb, without the addition and the encoding).
+"tweak-emulation" rows: against the double_mul(t, 1, P) it replaces, with the decoding that emulation needs.  "derive-pub" rows:
+fec_canon_bip32_derive_pub_dev with n parents against the tweak-add (the difference is the four compressions);
+"derive-pub-shared": with one parent against fec_canon_mul_base_dev, the floor of that form.  "derive-priv":
+fec_canon_bip32_derive_priv_dev on non-hardened indices against fec_canon_public_key_dev, the same secret comb;
+"derive-priv-hardened": under FEC_CANON_BIP32_NO_COMB against fec_sha512_dev on 64-byte messages, four compressions against
+one.  Last, one host-pointer row each.
 """
 import json
 import os
@@ -486,6 +500,118 @@ def main_recover():
                 f.write(json.dumps(r) + "\n")
 
 
+def main_bip32():
+    from forge_ec_amd.canon import CanonBip32
+    from forge_ec_amd import _lib as L
+    logn = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    out_path = sys.argv[4] if len(sys.argv) > 4 else None
+    n = 1 << logn
+    ctx = F.Context(0)
+    lib, h = ctx._lib, ctx._h
+    rng = np.random.default_rng(22)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()  # noqa: E731
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    def rounds(fns):
+        """each of fns three times, alternating; per fn the middle round's median and the largest spread"""
+        got = [[] for _ in fns]
+        for _ in range(3):
+            for g, fn in zip(got, fns):
+                g.append(_timed(fn, reps))
+        return [(sorted(g)[1][0], max(x[1] for x in g)) for g in got]
+
+    def pair(row, npass, names, fns, **extra):
+        a, b = rounds(fns)
+        emit(dict({"row": row, "pass": npass, "n": n, "reps": reps, names[0] + "_ms": round(a[0], 4), names[0] + "_spread_ms": round(a[1], 4),
+                   names[1] + "_ms": round(b[0], 4), names[1] + "_spread_ms": round(b[1], 4), "ratio": round(a[0] / b[0], 4),
+                   "M_per_s": round(n / a[0] / 1e3, 3)}, **extra))
+
+    cv, hd = CANON_CURVES["secp256k1"](ctx), CanonBip32(ctx)
+    keys_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    keys_h[:, 0] &= 0x7F      # big-endian keys and tweaks below n ...
+    keys_h[:, 31] |= 1        # ... and not zero
+    tw_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    tw_h[:, 0] &= 0x7F
+    cc_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    idx_h = rng.integers(0, 1 << 31, size=n, dtype=np.uint32)
+    msg64_h = rng.integers(0, 256, size=(n, 64), dtype=np.uint8)
+    keys, tw, cc, idx, msg64 = dev(keys_h), dev(tw_h), dev(cc_h), dev(idx_h), dev(msg64_h)
+    hard = dev(idx_h | np.uint32(1 << 31))
+    tw_limbs = dev(np.ascontiguousarray(tw_h[:, ::-1]))          # the same tweaks as little-endian limbs
+    one = np.zeros((n, 4), dtype=np.uint64)
+    one[:, 0] = 1
+    one = dev(one)
+    off64 = torch.arange(0, 64 * (n + 1), 64, dtype=torch.int64, device="cuda")
+    pk33, out33, out33b, child33 = (torch.empty((n, 33), dtype=torch.uint8, device="cuda") for _ in range(4))
+    xy, xy2 = (torch.empty((n, 8), dtype=torch.int64, device="cuda") for _ in range(2))
+    ck, occ, occ2, tk = (torch.empty((n, 32), dtype=torch.uint8, device="cuda") for _ in range(4))
+    dg64 = torch.empty((n, 64), dtype=torch.uint8, device="cuda")
+    s1, s2, s3 = (torch.empty(n, dtype=torch.uint8, device="cuda") for _ in range(3))
+    P = lambda t: t.data_ptr()  # noqa: E731
+    # what the timed calls must agree on: derive_priv -> public_key == derive_pub; tweak-add == public_key(seckey_tweak_add)
+    cv.public_key_dev(P(keys), P(pk33), 33, P(s1), n, st)
+    hd.derive_priv_dev(P(keys), P(cc), n, P(idx), 0, P(ck), P(occ), P(s2), n, st)
+    cv.public_key_dev(P(ck), P(child33), 33, P(s3), n, st)
+    torch.cuda.synchronize()
+    assert not bool(s1.any()) and not bool(s2.any()) and not bool(s3.any())
+    hd.derive_pub_dev(P(pk33), P(cc), n, P(idx), P(out33), P(occ2), P(s1), n, st)
+    cv.seckey_tweak_add_dev(P(keys), P(tw), P(tk), P(s2), n, st)
+    cv.public_key_dev(P(tk), P(out33b), 33, P(s3), n, st)
+    torch.cuda.synchronize()
+    assert not bool(s1.any()) and bool((out33 == child33).all()) and bool((occ == occ2).all()) and not bool(s2.any()) and not bool(s3.any())
+    cv.pubkey_tweak_add_dev(P(pk33), 33, P(tw), P(out33), 33, P(s1), n, st)
+    torch.cuda.synchronize()
+    assert not bool(s1.any()) and bool((out33 == out33b).all())
+
+    def decompress_then(fn):
+        def run():
+            cv.decompress_dev(P(pk33), 33, P(xy), P(s2), n, st)
+            fn()
+        return run
+
+    for npass in range(2):
+        pair("tweak", npass, ("pubkey_tweak_add_dev_33", "decompress_dev_33+mul_base_dev"), [
+            lambda: cv.pubkey_tweak_add_dev(P(pk33), 33, P(tw), P(out33), 33, P(s1), n, st),
+            decompress_then(lambda: cv.mul_base_dev(P(tw_limbs), P(xy2), P(s3), n, st))])
+        pair("tweak-emulation", npass, ("pubkey_tweak_add_dev_33", "decompress_dev_33+double_mul_dev(t,1,P)"), [
+            lambda: cv.pubkey_tweak_add_dev(P(pk33), 33, P(tw), P(out33), 33, P(s1), n, st),
+            decompress_then(lambda: cv.double_mul_dev(P(tw_limbs), P(one), P(xy), P(xy2), P(s3), n, st))])
+        pair("derive-pub", npass, ("bip32_derive_pub_dev", "pubkey_tweak_add_dev_33"), [
+            lambda: hd.derive_pub_dev(P(pk33), P(cc), n, P(idx), P(out33), P(occ2), P(s1), n, st),
+            lambda: cv.pubkey_tweak_add_dev(P(pk33), 33, P(tw), P(out33b), 33, P(s3), n, st)])
+        pair("derive-pub-shared", npass, ("bip32_derive_pub_dev_n_par_1", "mul_base_dev"), [
+            lambda: hd.derive_pub_dev(P(pk33), P(cc), 1, P(idx), P(out33), P(occ2), P(s1), n, st),
+            lambda: cv.mul_base_dev(P(tw_limbs), P(xy2), P(s3), n, st)])
+        pair("derive-priv", npass, ("bip32_derive_priv_dev", "public_key_dev_33"), [
+            lambda: hd.derive_priv_dev(P(keys), P(cc), n, P(idx), 0, P(ck), P(occ), P(s1), n, st),
+            lambda: cv.public_key_dev(P(keys), P(out33b), 33, P(s3), n, st)])
+        pair("derive-priv-hardened", npass, ("bip32_derive_priv_dev_no_comb", "sha512_dev_64B"), [
+            lambda: hd.derive_priv_dev(P(keys), P(cc), n, P(hard), L.CANON_BIP32_NO_COMB, P(ck), P(occ), P(s1), n, st),
+            lambda: lib.fec_sha512_dev(h, P(msg64), P(off64), 64 * n, P(dg64), P(s3), n, st)], compressions=(4, 1))
+        torch.cuda.synchronize()
+        assert not bool(s1.any()) and not bool(s3.any())
+    p = lambda a: a.ctypes.data  # noqa: E731
+    pk_h = pk33.cpu().numpy()
+    o33, o32, occ_h, st_h = np.zeros((n, 33), np.uint8), np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+    for name, fn in (("pubkey_tweak_add_33", lambda: lib.fec_canon_pubkey_tweak_add(h, 0, p(pk_h), 33, p(tw_h), p(o33), 33, p(st_h), n)),
+                     ("bip32_derive_pub", lambda: lib.fec_canon_bip32_derive_pub(h, p(pk_h), p(cc_h), n, p(idx_h), p(o33), p(occ_h), p(st_h), n)),
+                     ("bip32_derive_pub_n_par_1", lambda: lib.fec_canon_bip32_derive_pub(h, p(pk_h), p(cc_h), 1, p(idx_h), p(o33), p(occ_h), p(st_h), n)),
+                     ("bip32_derive_priv", lambda: lib.fec_canon_bip32_derive_priv(h, p(keys_h), p(cc_h), n, p(idx_h), 0, p(o32), p(occ_h), p(st_h), n))):
+        assert fn() == 0
+        ms, spread = _timed(fn, reps)
+        emit({"row": "host-" + name, "n": n, "reps": reps, "ms": round(ms, 4), "spread_ms": round(spread, 4), "M_per_s": round(n / ms / 1e3, 3)})
+    if out_path:
+        with open(out_path, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     logn = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -549,5 +675,7 @@ elif len(sys.argv) > 1 and sys.argv[1] == "x25519":
     main_x25519()
 elif len(sys.argv) > 1 and sys.argv[1] == "recover":
     main_recover()
+elif len(sys.argv) > 1 and sys.argv[1] == "bip32":
+    main_bip32()
 else:
     main()
