@@ -159,6 +159,7 @@ int launch_canon_ecdsa_verify(fec_ctx* ctx, int curve, const u64* dz, const u64*
   unsigned char* pst = (unsigned char*)(base + n * 128);
   unsigned char* ok = pst + n;
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // the work area is the ctx's
   dim3 g(grid_for(n)), b(TPB);
   const size_t lanes = (n + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
   const size_t stride = (lanes + 63) / 64 * 64;
@@ -229,6 +230,7 @@ int launch_canon_sig_verify(fec_ctx* ctx, int curve, const u64* d_key, const u64
   const int rc = sig_work(ctx, n, false, w);
   if (rc != FEC_OK) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // the work area is the ctx's
   dim3 g(grid_for(n)), b(TPB);
   if (curve == FEC_SECP256K1)
     hipLaunchKernelGGL(k_canon_bip340_prepare, g, b, 0, s, (const u32*)d_key, (const u32*)d_r, (const u32*)d_s,
