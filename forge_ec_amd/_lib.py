@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "fec_derive_key", "fec_derive_key_dev", "fec_ecdh_derive_key", "fec_ecdh_derive_key_dev", "fec_ecdh_exchange", "fec_ecdh_exchange_dev",
     "fec_expand_message_xmd", "fec_expand_message_xmd_dev", "fec_hash_to_field", "fec_hash_to_field_dev", "fec_map_to_curve",
     "fec_map_to_curve_dev", "fec_hash_to_curve", "fec_hash_to_curve_dev", "fec_curve_hash_to_curve", "fec_curve_hash_to_curve_dev",
+    "fec_debug_work_area_count", "fec_debug_work_area_read",
 ]
 # include/fecgpu_canon.h: the canonical-math mode (NOT reference parity)
 CANON_ABI_SYMBOLS = [
@@ -96,6 +97,10 @@ def lib():
     L.fec_ctx_device_count.restype = ci
     L.fec_ctx_wipe.argtypes = [vp]
     L.fec_ctx_wipe.restype = ci
+    L.fec_debug_work_area_count.argtypes = [vp]
+    L.fec_debug_work_area_count.restype = ci
+    L.fec_debug_work_area_read.argtypes = [vp, ci, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_char_p)]
+    L.fec_debug_work_area_read.restype = ci
     L.fec_ctx_check.argtypes = [vp]
     L.fec_ctx_check.restype = ci
     L.fec_ctx_debug_force_fault.argtypes = [vp, ci]

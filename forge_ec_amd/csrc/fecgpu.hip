@@ -2517,12 +2517,7 @@ int fec_ctx_wipe(fec_ctx* ctx) try {
       ++failed;
     }
   };
-  for (int i = 0; i < 8; ++i) zero(ctx->d_buf[i], ctx->d_cap[i]);
-  for (auto& e : ctx->stream_scratch) zero(e.buf, e.cap);
-  zero(ctx->d_win_scratch, ctx->win_scratch_cap);
-  zero(ctx->d_zbuf, ctx->zbuf_cap);
-  zero(ctx->d_tbuf, ctx->tbuf_cap);
-  zero(ctx->d_verify, ctx->verify_cap);
+  for_each_work_buffer(ctx, [&](const char*, void* p, size_t bytes) { zero(p, bytes); });   // (host_ctx.hpp: THE list)
   if (hipStreamSynchronize(st) != hipSuccess) {
     (void)hipGetLastError();
     ++failed;
@@ -3056,6 +3051,46 @@ int fec_debug_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* order_ove
     order.w[2 * i + 1] = (u32)(order_override[i] >> 32);
   }
   return ecdsa_sign_msg_call(ctx, curve, &order, sk, msgs, msg_off, msg_len, k, status, n);
+} FEC_ABI_CATCH_STATUS
+
+// Debug hooks: the ctx's work buffers as for_each_work_buffer (host_ctx.hpp) names them -- the list fec_ctx_wipe clears --
+// counted, and read back one at a time.  Read-only: no kernel, no device allocation, no state of the ctx changes.
+int fec_debug_work_area_count(fec_ctx* ctx) try {
+  if (!ctx) return FEC_E_ARG;
+  int count = 0;
+  for_each_work_ctx(ctx, [&](fec_ctx* c) { for_each_work_buffer(c, [&](const char*, void*, size_t) { ++count; }); });
+  return count;
+} FEC_ABI_CATCH_STATUS
+
+int fec_debug_work_area_read(fec_ctx* ctx, int index, void* host_out, size_t cap, size_t* bytes, const char** name) try {
+  if (!ctx || index < 0 || !bytes) return FEC_E_ARG;
+  fec_ctx* owner = nullptr;
+  const char* found_name = nullptr;
+  void* found = nullptr;
+  size_t found_bytes = 0;
+  int at = 0;
+  for_each_work_ctx(ctx, [&](fec_ctx* c) {
+    for_each_work_buffer(c, [&](const char* nm, void* p, size_t b) {
+      if (at++ != index) return;
+      owner = c;
+      found_name = nm;
+      found = p;
+      found_bytes = p ? b : 0;
+    });
+  });
+  if (!owner) return FEC_E_ARG;
+  *bytes = found_bytes;
+  if (name) *name = found_name;
+  if (found_bytes == 0) return FEC_OK;
+  if (!host_out || cap < found_bytes) return FEC_E_ARG;   // (*bytes says how much room the buffer needs)
+  bool synced = true;
+  for_each_work_ctx(ctx, [&](fec_ctx* c) { synced = hipSetDevice(c->device) == hipSuccess && hipDeviceSynchronize() == hipSuccess && synced; });
+  if (hipSetDevice(owner->device) != hipSuccess) return FEC_E_DEVICE;
+  if (!synced || hipMemcpy(host_out, found, found_bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+    (void)hipGetLastError();
+    return FEC_E_DEVICE;
+  }
+  return FEC_OK;
 } FEC_ABI_CATCH_STATUS
 
 }  // extern "C"

@@ -117,6 +117,28 @@ inline bool curve_ok(int c) { return c == FEC_SECP256K1 || c == FEC_P256 || c ==
 inline int plimbs(int c) { return c == FEC_ED25519 ? 16 : 12; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// THE list of work buffers: every device buffer a (single-device) ctx owns that can hold per-call data -- the staging
+// slots, the scratch of every stream, the canonical-mode work buffers -- as visit(name, pointer, capacity), unallocated
+// ones included (null, 0).  fec_ctx_wipe clears what this names and fec_debug_work_area_read reads it back, so the two
+// agree by construction; a buffer that is not here must be a public table (tests/test_work_area_census.py keeps the
+// allocation sites of csrc/ to these two kinds).  A multi-device ctx: its children, in order (for_each_work_ctx).
+template <class V>
+inline void for_each_work_buffer(fec_ctx* ctx, V&& visit) {
+  static const char* const kStage[8] = {"d_buf[0]", "d_buf[1]", "d_buf[2]", "d_buf[3]", "d_buf[4]", "d_buf[5]", "d_buf[6]", "d_buf[7]"};
+  for (int i = 0; i < 8; ++i) visit(kStage[i], ctx->d_buf[i], ctx->d_cap[i]);
+  for (auto& e : ctx->stream_scratch) visit("stream_scratch", e.buf, e.cap);
+  visit("d_win_scratch", ctx->d_win_scratch, ctx->win_scratch_cap);
+  visit("d_zbuf", ctx->d_zbuf, ctx->zbuf_cap);
+  visit("d_tbuf", ctx->d_tbuf, ctx->tbuf_cap);
+  visit("d_verify", ctx->d_verify, ctx->verify_cap);
+}
+template <class F>
+inline void for_each_work_ctx(fec_ctx* ctx, F&& fn) {
+  if (ctx->children.empty()) fn(ctx);
+  else
+    for (fec_ctx* c : ctx->children) fn(c);
+}
+
 inline int ensure(fec_ctx* ctx, int slot, size_t bytes) {
   if (ctx->d_cap[slot] >= bytes) return FEC_OK;
   if (ctx->d_buf[slot]) {

@@ -58,6 +58,23 @@ class Context:
         """fec_ctx_wipe: zero every ctx-owned device buffer that can hold copies of caller data."""
         _check(self._lib.fec_ctx_wipe(self._h), "fec_ctx_wipe")
 
+    def debug_work_areas(self):
+        """fec_debug_work_area_count / _read: test hook, not part of the reference's surface -- the device buffers that
+        wipe() clears, read back: a list of (name, uint8 array of the buffer's whole capacity), every child of a
+        multi-device ctx in order; an unallocated buffer gives an empty array.  Synchronises; reads only."""
+        count = self._lib.fec_debug_work_area_count(self._h)
+        _check(min(count, 0), "fec_debug_work_area_count")
+        out = []
+        for i in range(count):
+            size, name = ctypes.c_size_t(0), ctypes.c_char_p()
+            rc = self._lib.fec_debug_work_area_read(self._h, i, None, 0, ctypes.byref(size), ctypes.byref(name))
+            buf = np.zeros(size.value, dtype=np.uint8)
+            if size.value:   # (the first call only asked for the size)
+                rc = self._lib.fec_debug_work_area_read(self._h, i, _ptr(buf), buf.size, ctypes.byref(size), ctypes.byref(name))
+            _check(rc, "fec_debug_work_area_read")
+            out.append((name.value.decode(), buf))
+        return out
+
     def check(self):
         """fec_ctx_check: synchronise, then raise FecError(FEC_E_LAUNCH) if a kernel launched through this ctx since
         the last check reported a fault (the outputs of those launches must not be used).  For the *_dev callers;

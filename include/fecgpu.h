@@ -430,8 +430,20 @@ int fec_multi_batch_double_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t
 
 /* Zeroes every device buffer the ctx owns that can hold copies of caller data (host-call staging, the
  * per-stream scratch of composed launches, the canonical-mode work areas).  Synchronises the device.
- * fec_ctx_destroy calls it; call it yourself after a batch whose inputs were sensitive. */
+ * fec_ctx_destroy calls it; call it yourself after a batch whose inputs were sensitive.  What "every" means is ONE
+ * list in the source (csrc/host_ctx.hpp: for_each_work_buffer): the eight staging slots, the scratch of every stream
+ * the ctx has launched on, and the canonical-mode work buffers (window tables, Z, T, the verifiers' area).  Not on it,
+ * and not cleared, are the public tables: the generators, the fixed-base and comb tables. */
 int fec_ctx_wipe(fec_ctx* ctx);
+/* fec_debug_work_area_count / fec_debug_work_area_read: test hooks, NOT part of the reference's surface -- the list that
+ * fec_ctx_wipe clears, read back, so that a test can see what a call left in device memory (tests/test_gpu_secret_residue.py).
+ * count: how many buffers the list names now (every child of a multi-device ctx in order; a stream's scratch appears
+ * with the first launch on that stream), or a negative status.  read: synchronises the ctx's device(s) and copies buffer
+ * `index` to host_out; *bytes = its capacity (0: not allocated, nothing is copied and host_out may be null), *name
+ * (optional) = a static string naming it.  FEC_E_ARG with *bytes set when cap is too small: ask with cap = 0 first.
+ * Reads only: no kernel is launched, nothing is allocated on the device and no state of the ctx changes. */
+int fec_debug_work_area_count(fec_ctx* ctx);
+int fec_debug_work_area_read(fec_ctx* ctx, int index, void* host_out, size_t cap, size_t* bytes, const char** name);
 
 /* The sticky device error state of the ctx, for callers of the *_dev entry points (those return once the work
  * is enqueued, so a fault reported by a kernel can only be seen afterwards; the host-pointer entry points do this

@@ -107,6 +107,8 @@ extern "C" {
     fn fec_schnorr_sign_msg(ctx: *mut FecCtx, curve: c_int, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, r_xy: *mut u64, r_inf: *mut u8, s: *mut u64, sig_bytes: *mut u8, status: *mut u8, n: usize) -> c_int;
     fn fec_schnorr_sign_msg_dev(ctx: *mut FecCtx, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *mut u64, d_r_inf: *mut u8, d_s: *mut u64, d_sig_bytes: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_debug_rfc6979_k(ctx: *mut FecCtx, curve: c_int, order_override: *const u64, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, k: *mut u64, status: *mut u8, n: usize) -> c_int;
+    fn fec_debug_work_area_count(ctx: *mut FecCtx) -> c_int;
+    fn fec_debug_work_area_read(ctx: *mut FecCtx, index: c_int, host_out: *mut c_void, cap: usize, bytes: *mut usize, name: *mut *const c_char) -> c_int;
     fn fec_derive_key(ctx: *mut FecCtx, curve: c_int, secrets: *const u8, secret_len: usize, info: *const u8, info_len: usize, out_len: usize, keys: *mut u8, n: usize) -> c_int;
     fn fec_derive_key_dev(ctx: *mut FecCtx, curve: c_int, d_secrets: *const u8, secret_len: usize, info: *const u8, info_len: usize, out_len: usize, d_keys: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_ecdh_derive_key(ctx: *mut FecCtx, curve: c_int, private_keys: *const u64, pk_xy: *const u64, pk_inf: *const u8, info: *const u8, info_len: usize, out_len: usize, keys: *mut u8, status: *mut u8, n: usize) -> c_int;
@@ -197,6 +199,33 @@ impl GpuContext {
     pub fn debug_force_fault(&mut self, enabled: bool) -> Result<()> {
         // SAFETY: self.raw is a live ctx.
         check(unsafe { fec_ctx_debug_force_fault(self.raw, enabled as c_int) })
+    }
+
+    /// Test hook (`fec_debug_work_area_count` / `fec_debug_work_area_read`), not part of the reference's surface: the
+    /// device buffers that `wipe` clears, read back as (name, bytes); an unallocated buffer gives no bytes.  Reads only.
+    pub fn debug_work_areas(&mut self) -> Result<Vec<(&'static str, Vec<u8>)>> {
+        // SAFETY: self.raw is a live ctx.
+        let count = unsafe { fec_debug_work_area_count(self.raw) };
+        if count < 0 {
+            check(count)?;
+        }
+        let mut out = Vec::with_capacity(count as usize);
+        for i in 0..count {
+            let (mut size, mut name): (usize, *const c_char) = (0, core::ptr::null());
+            // SAFETY: cap = 0 copies nothing; size and name are valid for writes.
+            let rc = unsafe { fec_debug_work_area_read(self.raw, i, core::ptr::null_mut(), 0, &mut size, &mut name) };
+            let mut buf = vec![0u8; size];
+            if size != 0 {
+                // SAFETY: buf holds `size` bytes, the capacity the library just reported for this buffer.
+                check(unsafe { fec_debug_work_area_read(self.raw, i, buf.as_mut_ptr() as *mut c_void, size, &mut size, &mut name) })?;
+            } else {
+                check(rc)?;
+            }
+            // SAFETY: the library returns a static NUL-terminated ASCII string.
+            let label = unsafe { core::ffi::CStr::from_ptr(name) }.to_str().unwrap_or("");
+            out.push((label, buf));
+        }
+        Ok(out)
     }
 
     /// Size of the generator's fixed-base prefix tables (`fec_ctx_set_fixed_prefix_bits`): 2^bits entries per curve,
