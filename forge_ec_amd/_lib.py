@@ -43,6 +43,9 @@ CANON_ABI_SYMBOLS = [
     "fec_canon_ecdsa_sign_recoverable_digest", "fec_canon_ecdsa_sign_recoverable_digest_dev",
     "fec_canon_pubkey_tweak_add", "fec_canon_pubkey_tweak_add_dev", "fec_canon_seckey_tweak_add", "fec_canon_seckey_tweak_add_dev",
     "fec_canon_bip32_derive_pub", "fec_canon_bip32_derive_pub_dev", "fec_canon_bip32_derive_priv", "fec_canon_bip32_derive_priv_dev",
+    "fec_canon_ripemd160", "fec_canon_ripemd160_dev", "fec_canon_hash160", "fec_canon_hash160_dev",
+    "fec_canon_pubkey_hash160", "fec_canon_pubkey_hash160_dev", "fec_canon_taproot_output_key", "fec_canon_taproot_output_key_dev",
+    "fec_canon_bip32_derive_pub_path", "fec_canon_bip32_derive_pub_path_dev",
 ]
 CANON_NO_KEY = 8
 CANON_BAD_POINT, CANON_BAD_INDEX, CANON_BIP32_INVALID, CANON_BIP32_NO_COMB = 2, 9, 10, 1
@@ -325,6 +328,16 @@ def lib():
     L.fec_canon_bip32_derive_pub_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]
     L.fec_canon_bip32_derive_priv.argtypes = [vp, vp, vp, sz, vp, cu, vp, vp, vp, sz]
     L.fec_canon_bip32_derive_priv_dev.argtypes = [vp, vp, vp, sz, vp, cu, vp, vp, vp, sz, vp]
+    L.fec_canon_ripemd160.argtypes = [vp, vp, vp, sz, vp, sz]
+    L.fec_canon_ripemd160_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+    L.fec_canon_hash160.argtypes = [vp, vp, vp, sz, vp, sz]
+    L.fec_canon_hash160_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+    L.fec_canon_pubkey_hash160.argtypes = [vp, vp, sz, vp, sz]
+    L.fec_canon_pubkey_hash160_dev.argtypes = [vp, vp, sz, vp, sz, vp]
+    L.fec_canon_taproot_output_key.argtypes = [vp, vp, sz, vp, vp, vp, vp, sz]
+    L.fec_canon_taproot_output_key_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, sz, vp]
+    L.fec_canon_bip32_derive_pub_path.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, sz]
+    L.fec_canon_bip32_derive_pub_path_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, sz, vp]
     for n in CANON_ABI_SYMBOLS:
         getattr(L, n).restype = ci
     _lib = L

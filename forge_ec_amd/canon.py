@@ -380,6 +380,26 @@ class CanonSecp256k1(CanonCurve):
         _check(self._lib.fec_canon_bip340_verify_msg_dev(self._h, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, d_result, n,
                                                          stream), "fec_canon_bip340_verify_msg_dev")
 
+    def taproot_output_key(self, pks, roots=None, pk_len=32):
+        """Taproot output keys (BIP-341): pks (n,pk_len), pk_len 32 (x-only) or 33 (tag 2 / 3, ignored); roots (n,32) Merkle
+        roots or None (no script tree, BIP-86) -> (output keys (n,32) x-only, parity of y (n,), status).  status: 0, 2 (the key
+        is refused), 3 / 8 (unobservable), zeros then."""
+        pk = _bytes_rows(pks, pk_len, "pks")
+        n = pk.shape[0]
+        rt = None if roots is None else _bytes_rows(roots, 32, "roots")
+        if rt is not None and rt.shape[0] != n:
+            raise ValueError("inputs differ in length")
+        out = np.zeros((n, 32), dtype=np.uint8)
+        par, st = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_taproot_output_key(self._h, _ptr(pk), pk_len, None if rt is None else _ptr(rt), _ptr(out), _ptr(par),
+                                                      _ptr(st), n), "fec_canon_taproot_output_key")
+        return out, par, st
+
+    def taproot_output_key_dev(self, d_pks, pk_len, d_roots, d_out_keys, d_out_parity, d_status, n, stream=None):
+        """d_roots: None for no script tree."""
+        _check(self._lib.fec_canon_taproot_output_key_dev(self._h, d_pks, pk_len, d_roots, d_out_keys, d_out_parity, d_status, n,
+                                                          stream), "fec_canon_taproot_output_key_dev")
+
 
 class CanonP256(CanonCurve):
     CURVE = L.P256
@@ -465,7 +485,8 @@ class CanonX25519:
 
 
 class CanonKeccak:
-    """Keccak-256 as Ethereum uses it (padding 0x01, not SHA3-256's 0x06): a list of n byte strings -> (n,32) uint8."""
+    """The curve-less hashes.  Keccak-256 as Ethereum uses it (padding 0x01, not SHA3-256's 0x06): a list of n byte strings ->
+    (n,32) uint8.  RIPEMD-160 and HASH160 = RIPEMD-160(SHA-256(.)), Bitcoin's key hash: -> (n,20) uint8."""
 
     def __init__(self, ctx=None, device=0):
         self.ctx = ctx if ctx is not None else Context(device)
@@ -483,6 +504,41 @@ class CanonKeccak:
         """d_status may be None; else 4 marks a bad range (zero digest)."""
         _check(self._lib.fec_canon_keccak256_dev(self._h, d_msgs, d_msg_off, msg_len, d_out, d_status, n, stream),
                "fec_canon_keccak256_dev")
+
+    def _digest20(self, fn, what, msgs):
+        buf, off, total = Context._messages(msgs)
+        n = len(off) - 1
+        out = np.zeros((n, 20), dtype=np.uint8)
+        _check(fn(self._h, _ptr(buf), _ptr(off), total, _ptr(out), n), what)
+        return out
+
+    def ripemd160(self, msgs):
+        """RIPEMD-160: a list of n byte strings -> (n,20) uint8."""
+        return self._digest20(self._lib.fec_canon_ripemd160, "fec_canon_ripemd160", msgs)
+
+    def ripemd160_dev(self, d_msgs, d_msg_off, msg_len, d_out, d_status, n, stream=None):
+        """d_out 4-byte aligned; d_status may be None; else 4 marks a bad range (zero digest)."""
+        _check(self._lib.fec_canon_ripemd160_dev(self._h, d_msgs, d_msg_off, msg_len, d_out, d_status, n, stream),
+               "fec_canon_ripemd160_dev")
+
+    def hash160(self, msgs):
+        """HASH160 = RIPEMD-160(SHA-256(.)): a list of n byte strings -> (n,20) uint8."""
+        return self._digest20(self._lib.fec_canon_hash160, "fec_canon_hash160", msgs)
+
+    def hash160_dev(self, d_msgs, d_msg_off, msg_len, d_out, d_status, n, stream=None):
+        _check(self._lib.fec_canon_hash160_dev(self._h, d_msgs, d_msg_off, msg_len, d_out, d_status, n, stream),
+               "fec_canon_hash160_dev")
+
+    def pubkey_hash160(self, pks, pk_len=33):
+        """HASH160 of (n,pk_len) records as their bytes lie, pk_len 33 or 65 -> (n,20) uint8: P2PKH / P2WPKH programs."""
+        pk = _bytes_rows(pks, pk_len, "pks")
+        n = pk.shape[0]
+        out = np.zeros((n, 20), dtype=np.uint8)
+        _check(self._lib.fec_canon_pubkey_hash160(self._h, _ptr(pk), pk_len, _ptr(out), n), "fec_canon_pubkey_hash160")
+        return out
+
+    def pubkey_hash160_dev(self, d_pks, pk_len, d_out, n, stream=None):
+        _check(self._lib.fec_canon_pubkey_hash160_dev(self._h, d_pks, pk_len, d_out, n, stream), "fec_canon_pubkey_hash160_dev")
 
 
 class CanonBip32:
@@ -517,6 +573,31 @@ class CanonBip32:
     def derive_pub_dev(self, d_parent_pks, d_parent_ccs, n_par, d_indices, d_out_pks, d_out_ccs, d_status, n, stream=None):
         _check(self._lib.fec_canon_bip32_derive_pub_dev(self._h, d_parent_pks, d_parent_ccs, n_par, d_indices, d_out_pks, d_out_ccs,
                                                         d_status, n, stream), "fec_canon_bip32_derive_pub_dev")
+
+    def derive_pub_path(self, parent_pks, parent_ccs, indices, fingerprints=True, hash160=True):
+        """CKDpub along a path: indices (n,depth), depth 1..255 -> (child keys (n,33), chain codes (n,32), fingerprints (n,4) or
+        None, HASH160 of the child keys (n,20) or None, status); the status is the first of the chain that is not 0.  The
+        fingerprint is that of the last level's parent, as the child's xpub record carries it."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32))
+        if idx.ndim != 2:
+            raise ValueError("indices: one row of the path's indices per element")
+        n, depth = idx.shape
+        pk, cc = self._parents(parent_pks, 33, parent_ccs, n)
+        out, occ = np.zeros((n, 33), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8)
+        fp = np.zeros((n, 4), dtype=np.uint8) if fingerprints else None
+        h160 = np.zeros((n, 20), dtype=np.uint8) if hash160 else None
+        st = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.fec_canon_bip32_derive_pub_path(self._h, _ptr(pk), _ptr(cc), pk.shape[0], _ptr(idx), depth, _ptr(out), _ptr(occ),
+                                                         _ptr(fp) if fingerprints else None, _ptr(h160) if hash160 else None,
+                                                         _ptr(st), n), "fec_canon_bip32_derive_pub_path")
+        return out, occ, fp, h160, st
+
+    def derive_pub_path_dev(self, d_parent_pks, d_parent_ccs, n_par, d_indices, depth, d_out_pks, d_out_ccs, d_out_fingerprints,
+                            d_out_hash160, d_status, n, stream=None):
+        """d_out_fingerprints, d_out_hash160: None where not wanted."""
+        _check(self._lib.fec_canon_bip32_derive_pub_path_dev(self._h, d_parent_pks, d_parent_ccs, n_par, d_indices, depth, d_out_pks,
+                                                             d_out_ccs, d_out_fingerprints, d_out_hash160, d_status, n, stream),
+               "fec_canon_bip32_derive_pub_path_dev")
 
     def derive_priv(self, parent_keys, parent_ccs, indices, flags=0):
         """CKDpriv, hardened and non-hardened indices mixed: (child keys (n,32), child chain codes (n,32), status).

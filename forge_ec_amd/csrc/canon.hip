@@ -11,6 +11,7 @@
 #include "canon_x25519_kernels.hpp"
 #include "canon_recover_kernels.hpp"
 #include "canon_bip32_kernels.hpp"
+#include "canon_wallet_kernels.hpp"
 
 using namespace fecgpu;
 using namespace fecgpu::host;
@@ -599,6 +600,7 @@ int tweak_work(fec_ctx* ctx, size_t n, TweakWork& w) {
   w.flag = w.pst + n;
   return FEC_OK;
 }
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 inline bool tweak_len_ok(int curve, size_t len) { return len == 33 || len == 65 || (len == 32 && curve == FEC_SECP256K1); }
 // Everything after the prepare kernel, which has filled w.t, w.q and w.flag.  ccs: the child chain codes (BIP-32) or null.
 int launch_canon_tweak_tail(fec_ctx* ctx, int curve, const TweakWork& w, unsigned char at_infinity, uint8_t* d_out, size_t out_len,
@@ -697,6 +699,91 @@ int launch_canon_bip32_derive_priv(fec_ctx* ctx, const uint8_t* d_keys, const ui
                        d_idx, (u32*)d_out_keys, (u32*)d_out_ccs, dst, n);
   if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
   return comb ? launch_secret_report(ctx, FEC_SECP256K1, c, s) : FEC_OK;
+}
+
+// ---- RIPEMD-160, HASH160, Taproot output keys, CKDpub along a path (ripemd160.hpp, canon_wallet.hpp, canon_wallet_kernels.hpp) ----
+int launch_canon_ripemd160(fec_ctx* ctx, bool sha_first, const Messages& m, uint8_t* d_out, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, sha_first ? "k_canon_hash160" : "k_canon_ripemd160");
+  if (sha_first) hipLaunchKernelGGL(k_canon_ripemd160<true>, dim3(grid_for(n)), dim3(TPB), 0, L.s, m, (u32*)d_out, dst, n);
+  else hipLaunchKernelGGL(k_canon_ripemd160<false>, dim3(grid_for(n)), dim3(TPB), 0, L.s, m, (u32*)d_out, dst, n);
+  return L.done();
+}
+int launch_canon_pubkey_hash160(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_len, uint8_t* d_out, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  Launch L(ctx, stream, "k_canon_pubkey_hash160");
+  hipLaunchKernelGGL(k_canon_pubkey_hash160, dim3(grid_for(n)), dim3(TPB), 0, L.s, d_pks, pk_len, (u32*)d_out, n);
+  return L.done();
+}
+// The middle of launch_canon_tweak_tail on secp256k1, for the callers that end with a kernel of their own: w.t * G by the comb
+// (finish = false), + w.q, the normalisation.  w.xy is affine behind it, w.pst says where the sum is at infinity.
+int wallet_sum(fec_ctx* ctx, const TweakWork& w, size_t n, void* stream) {
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // (the caller has: this keeps the function ordered when read alone)
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;   // the kernel before
+  int rc = launch_canon_mul_base(ctx, FEC_SECP256K1, w.t, w.xy, w.pst, n, stream, false);
+  if (rc != FEC_OK) return rc;
+  hipLaunchKernelGGL((k_canon_add_affine<csecp>), dim3(grid_for(n)), dim3(TPB), 0, s, (u32*)w.xy, reinterpret_cast<u32*>(ctx->d_zbuf),
+                     (const u32*)w.q, w.pst, n);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  return launch_canon_normalize(ctx, FEC_SECP256K1, w.xy, w.pst, n, s);
+}
+// Taproot: prepare -> the tweak-add's middle -> finish.  d_roots: null = no script tree (BIP-86).
+int launch_canon_taproot_output_key(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_len, const uint8_t* d_roots, uint8_t* d_out,
+                                    uint8_t* d_parity, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  TweakWork w;
+  int rc = tweak_work(ctx, n, w);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // the work area is the ctx's
+  dim3 g(grid_for(n)), b(TPB);
+  hipLaunchKernelGGL((k_canon_taproot_prepare<canon::SecpParams>), g, b, 0, s, d_pks, (int)pk_len, (const u32*)d_roots, (u32*)w.t, (u32*)w.q,
+                     w.flag, n);
+  rc = wallet_sum(ctx, w, n, stream);
+  if (rc != FEC_OK) return rc;
+  hipLaunchKernelGGL(k_canon_taproot_finish, g, b, 0, s, (const u32*)w.xy, (const unsigned char*)w.flag, (const unsigned char*)w.pst, d_out,
+                     d_parity, dst, n);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+// CKDpub along `depth` levels: the first level is launch_canon_bip32_derive_pub's prepare (its index column gathered into
+// w.xy, free until the comb writes it); every further level reads the affine child the normalisation left in w.xy.  The
+// running chain code lives in d_out_ccs.  d_fp, d_h160: null where not asked for.
+int launch_canon_bip32_derive_pub_path(fec_ctx* ctx, const uint8_t* d_pks, const uint8_t* d_ccs, bool shared, const uint32_t* d_idx,
+                                       size_t depth, uint8_t* d_out_pks, uint8_t* d_out_ccs, uint8_t* d_fp, uint8_t* d_h160,
+                                       unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  using P = canon::SecpParams;
+  TweakWork w;
+  int rc = tweak_work(ctx, n, w);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);   // the work area is the ctx's
+  dim3 g(grid_for(n)), b(TPB);
+  const u32* idx0 = d_idx;
+  if (depth > 1) {
+    hipLaunchKernelGGL(k_canon_path_indices, g, b, 0, s, (const u32*)d_idx, depth, (size_t)0, (u32*)w.xy, n);
+    idx0 = (const u32*)w.xy;
+  }
+  if (shared) {
+    hipLaunchKernelGGL((k_canon_bip32_parent<P>), dim3(1), dim3(64), 0, s, d_pks, (const u32*)d_ccs, w.shared);
+    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, true>), g, b, 0, s, d_pks, (const u32*)d_ccs, (const u32*)w.shared, idx0, (u32*)w.t,
+                       (u32*)w.q, (u32*)d_out_ccs, w.flag, n);
+  } else {
+    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, false>), g, b, 0, s, d_pks, (const u32*)d_ccs, (const u32*)w.shared, idx0, (u32*)w.t,
+                       (u32*)w.q, (u32*)d_out_ccs, w.flag, n);
+  }
+  if (d_fp && depth == 1) hipLaunchKernelGGL(k_canon_path_fingerprint, g, b, 0, s, (const u32*)w.q, (u32*)d_fp, n);
+  for (size_t level = 1;; ++level) {
+    rc = wallet_sum(ctx, w, n, stream);
+    if (rc != FEC_OK) return rc;
+    if (level == depth) break;
+    hipLaunchKernelGGL((k_canon_bip32_path_step<P>), g, b, 0, s, (const u32*)w.xy, (const unsigned char*)w.pst, (const u32*)d_idx, depth, level,
+                       (u32*)w.t, (u32*)w.q, (u32*)d_out_ccs, w.flag, level + 1 == depth ? (u32*)d_fp : nullptr, n);
+  }
+  hipLaunchKernelGGL(k_canon_bip32_path_finish, g, b, 0, s, (const u32*)w.xy, (const unsigned char*)w.flag, (const unsigned char*)w.pst, d_out_pks,
+                     (u32*)d_out_ccs, (u32*)d_fp, (u32*)d_h160, dst, n);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 
 }  // namespace
@@ -1281,6 +1368,108 @@ int fec_canon_bip32_derive_priv(fec_ctx* ctx, const uint8_t* parent_keys, const 
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_canon_bip32_derive_priv(c, (const uint8_t*)d[0], (const uint8_t*)d[1], shared ? 1 : m, (const uint32_t*)d[2], flags,
                                           (uint8_t*)d[3], (uint8_t*)d[4], (unsigned char*)d[5], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- RIPEMD-160 and HASH160 = RIPEMD-160(SHA-256(.)) ----------------------------------------------------------------------------
+int fec_canon_ripemd160_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_out,
+                            uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n == 0) return FEC_OK;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || !d_out || !aligned4(d_out)) return FEC_E_ARG;
+  return launch_canon_ripemd160(ctx, false, m, d_out, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_ripemd160(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* out, size_t n) try {
+  if (!ctx || (n && !out)) return FEC_E_ARG;
+  const HostArray a[] = {ragged(msg_off, 8), output(out, 20)};
+  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_canon_ripemd160(c, false, m, (uint8_t*)d[1], nullptr, cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_hash160_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_out,
+                          uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n == 0) return FEC_OK;
+  Messages m;
+  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || !d_out || !aligned4(d_out)) return FEC_E_ARG;
+  return launch_canon_ripemd160(ctx, true, m, d_out, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_hash160(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* out, size_t n) try {
+  if (!ctx || (n && !out)) return FEC_E_ARG;
+  const HostArray a[] = {ragged(msg_off, 8), output(out, 20)};
+  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
+    return launch_canon_ripemd160(c, true, m, (uint8_t*)d[1], nullptr, cnt, st);
+  });
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_pubkey_hash160_dev(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_len, uint8_t* d_out, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n == 0) return FEC_OK;
+  if (!d_pks || !d_out || (pk_len != 33 && pk_len != 65) || !aligned4(d_out)) return FEC_E_ARG;
+  return launch_canon_pubkey_hash160(ctx, d_pks, pk_len, d_out, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_pubkey_hash160(fec_ctx* ctx, const uint8_t* pks, size_t pk_len, uint8_t* out, size_t n) try {
+  if (!ctx || (n && (!pks || !out)) || (pk_len != 33 && pk_len != 65)) return FEC_E_ARG;
+  const HostArray a[] = {input(pks, pk_len), output(out, 20)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_pubkey_hash160(c, (const uint8_t*)d[0], pk_len, (uint8_t*)d[1], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- Taproot output keys (BIP-341, BIP-86) ---------------------------------------------------------------------------------------
+int fec_canon_taproot_output_key_dev(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_len, const uint8_t* d_roots, uint8_t* d_out_keys,
+                                     uint8_t* d_out_parity, uint8_t* d_status, size_t n, void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (n == 0) return FEC_OK;
+  if (!d_pks || !d_out_keys || !d_out_parity || !d_status || (pk_len != 32 && pk_len != 33)) return FEC_E_ARG;
+  if ((pk_len == 32 && !aligned16(d_pks)) || !aligned16(d_roots) || !aligned16(d_out_keys)) return FEC_E_ARG;
+  return launch_canon_taproot_output_key(ctx, d_pks, pk_len, d_roots, d_out_keys, d_out_parity, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_taproot_output_key(fec_ctx* ctx, const uint8_t* pks, size_t pk_len, const uint8_t* roots, uint8_t* out_keys,
+                                 uint8_t* out_parity, uint8_t* status, size_t n) try {
+  if (!ctx || (n && (!pks || !out_keys || !out_parity || !status)) || (pk_len != 32 && pk_len != 33)) return FEC_E_ARG;
+  const HostArray a[] = {input(pks, pk_len), input(roots, 32), output(out_keys, 32), output(out_parity, 1), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_taproot_output_key(c, (const uint8_t*)d[0], pk_len, (const uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3],
+                                           (unsigned char*)d[4], m, s);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// ---- BIP-32 CKDpub along a path ------------------------------------------------------------------------------------------------
+int fec_canon_bip32_derive_pub_path_dev(fec_ctx* ctx, const uint8_t* d_parent_pks, const uint8_t* d_parent_ccs, size_t n_par,
+                                        const uint32_t* d_indices, size_t depth, uint8_t* d_out_pks, uint8_t* d_out_ccs,
+                                        uint8_t* d_out_fingerprints, uint8_t* d_out_hash160, uint8_t* d_status, size_t n,
+                                        void* stream) try {
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (depth < 1 || depth > 255) return FEC_E_ARG;
+  if (n == 0) return FEC_OK;
+  if (n_par != n && n_par != 1) return FEC_E_ARG;
+  if (!d_parent_pks || !d_parent_ccs || !d_indices || !d_out_pks || !d_out_ccs || !d_status) return FEC_E_ARG;
+  if (!aligned16(d_parent_ccs) || !aligned16(d_out_ccs) || !aligned4(d_indices) || !aligned4(d_out_fingerprints) || !aligned4(d_out_hash160))
+    return FEC_E_ARG;
+  return launch_canon_bip32_derive_pub_path(ctx, d_parent_pks, d_parent_ccs, n_par != n, d_indices, depth, d_out_pks, d_out_ccs,
+                                            d_out_fingerprints, d_out_hash160, d_status, n, stream);
+} FEC_ABI_CATCH_STATUS
+
+int fec_canon_bip32_derive_pub_path(fec_ctx* ctx, const uint8_t* parent_pks, const uint8_t* parent_ccs, size_t n_par,
+                                    const uint32_t* indices, size_t depth, uint8_t* out_pks, uint8_t* out_ccs, uint8_t* out_fingerprints,
+                                    uint8_t* out_hash160, uint8_t* status, size_t n) try {
+  if (!ctx || depth < 1 || depth > 255 || (n_par != n && n_par != 1)) return FEC_E_ARG;
+  if (n && (!parent_pks || !parent_ccs || !indices || !out_pks || !out_ccs || !status)) return FEC_E_ARG;
+  const bool shared = n_par != n;
+  const HostArray a[] = {shared ? shared_input(parent_pks, 33) : input(parent_pks, 33),
+                         shared ? shared_input(parent_ccs, 32) : input(parent_ccs, 32),
+                         input(indices, 4 * depth), output(out_pks, 33), output(out_ccs, 32), output(out_fingerprints, 4),
+                         output(out_hash160, 20), output(status, 1)};
+  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+    return launch_canon_bip32_derive_pub_path(c, (const uint8_t*)d[0], (const uint8_t*)d[1], shared, (const uint32_t*)d[2], depth,
+                                              (uint8_t*)d[3], (uint8_t*)d[4], (uint8_t*)d[5], (uint8_t*)d[6], (unsigned char*)d[7], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 

@@ -354,9 +354,9 @@ int fec_canon_ecdsa_sign_recoverable_digest_dev(fec_ctx* ctx, fec_curve curve, c
  * Host forms: chunked by fec_ctx_set_chunk, sharded over a multi-device ctx.  *_dev forms: every 32- and 64-byte record array
  * 16-byte aligned (33- and 65-byte records: any alignment), indices 4-byte aligned, FEC_E_UNSUPPORTED on a multi-device ctx.
  * Every status but 0 comes with zero records.
- * Not offered: xpub / xprv Base58Check serialisation and fingerprints (they need RIPEMD-160); master-key generation from a
- * seed; SLIP-10 (the P-256 and Ed25519 variants); the TapTweak tagged hash (prepend the 64-byte tag prefix and use
- * fec_sha256_dev); whole-path derivation in one call (chain the *_dev calls level by level). */
+ * Not offered: xpub / xprv Base58Check serialisation (fingerprints and key hashes: the wallet block below); master-key
+ * generation from a seed; SLIP-10 (the P-256 and Ed25519 variants); whole-path CKDpriv and the Taproot secret-key tweak (the
+ * public halves, fec_canon_bip32_derive_pub_path and fec_canon_taproot_output_key, are below). */
 #define FEC_CANON_BAD_INDEX 9       /* derive_pub: index >= 2^31; derive_priv under FEC_CANON_BIP32_NO_COMB: index < 2^31 */
 #define FEC_CANON_BIP32_INVALID 10  /* IL >= n, or the child is the point at infinity / the key 0: BIP-32 says to take the next
                                        index; unobservable (below 2^-127) */
@@ -403,6 +403,70 @@ int fec_canon_bip32_derive_priv(fec_ctx* ctx, const uint8_t* parent_keys /* n_pa
 int fec_canon_bip32_derive_priv_dev(fec_ctx* ctx, const uint8_t* d_parent_keys, const uint8_t* d_parent_ccs, size_t n_par,
                                     const uint32_t* d_indices, unsigned flags, uint8_t* d_out_keys, uint8_t* d_out_ccs,
                                     uint8_t* d_status, size_t n, void* stream);
+
+/* ---- RIPEMD-160, HASH160, Taproot output keys, CKDpub along a path -------------------------------------------------------------
+ * What a watch-only scanner needs to get from an account xpub to the 20 or 32 bytes that stand in a scriptPubKey without
+ * leaving the device: key hashes (P2PKH / P2WPKH programs) and fingerprints, Taproot output keys (BIP-341, BIP-86), and BIP-32
+ * CKDpub over several levels in one call.  Every input is public: nothing here is staged as a secret or wiped.  Validated
+ * against tests/canon_wallet_ref.py (a RIPEMD-160 model pinned by the published digests, hashlib / hmac over
+ * tests/canon_bip32_ref.py; pinned by BIP-32 test vector 1 and BIP-86's first receive key), never against the reference, which
+ * has none of it.
+ * Host forms: chunked by fec_ctx_set_chunk, sharded over a multi-device ctx, FEC_E_ARG on a bad message layout.
+ * *_dev forms: FEC_E_UNSUPPORTED on a multi-device ctx; FEC_OK at n = 0 whatever the pointers; 33- and 65-byte record arrays
+ * need no alignment, 20-byte and 4-byte records (digests, fingerprints, indices) 4-byte alignment, 32-byte records (x-only
+ * keys, roots, chain codes) 16-byte alignment, d_msg_off 8-byte alignment -- else FEC_E_ARG.  Every status but 0 comes with
+ * zero records.
+ * Not offered: Base58Check, bech32 / bech32m and the 78-byte xpub record (text and packing: the caller has every field);
+ * script-tree Merkle roots (TapLeaf / TapBranch); P2SH-wrapped programs (chain fec_canon_hash160_dev); sharing a common path
+ * prefix across the batch (derive the account / change node with one n = 1 call and pass it as the shared parent); the
+ * secret side -- master key from a seed, whole-path CKDpriv, the Taproot secret-key tweak, SLIP-10; P-256 for any of it. */
+
+/* RIPEMD-160: out[i] = the 20 digest bytes of message i.  Arguments and per-lane range checking as fec_canon_keccak256(_dev):
+ * a bad range gets a zero digest and, where d_status is not NULL, status 4 (0 otherwise).  One message per lane, the state and
+ * the block in registers. */
+int fec_canon_ripemd160(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                        uint8_t* out /* n*20 */, size_t n);
+int fec_canon_ripemd160_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_out,
+                            uint8_t* d_status /* n or NULL */, size_t n, void* stream);
+/* HASH160: out[i] = RIPEMD-160(SHA-256(message i)); the SHA-256 digest goes from registers into the RIPEMD-160 block. */
+int fec_canon_hash160(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                      uint8_t* out /* n*20 */, size_t n);
+int fec_canon_hash160_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_out,
+                          uint8_t* d_status /* n or NULL */, size_t n, void* stream);
+/* HASH160 of fixed-length records as their bytes lie, pk_len 33 or 65 (another: FEC_E_ARG): the program of a P2PKH / P2WPKH
+ * output.  Nothing is decoded, there is no status. */
+int fec_canon_pubkey_hash160(fec_ctx* ctx, const uint8_t* pks /* n*pk_len */, size_t pk_len, uint8_t* out /* n*20 */, size_t n);
+int fec_canon_pubkey_hash160_dev(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_len, uint8_t* d_out, size_t n, void* stream);
+
+/* Taproot output keys (BIP-341) on secp256k1: P = lift_x(x), the point with even y; t = SHA-256(T || T || x || root) with
+ * T = SHA-256("TapTweak"); Q = P + t G; out_keys[i] = x(Q) big-endian, out_parity[i] = y(Q) & 1.  pk_len 32: x-only keys;
+ * 33: the tag must be 2 or 3 and is then ignored; another pk_len: FEC_E_ARG.  roots: 32 bytes each, or NULL for the whole call:
+ * no script tree, t = H(x) (BIP-86).  status[i]: 0; FEC_CANON_BAD_POINT: a bad tag, x >= p or x on no point;
+ * FEC_CANON_BAD_SCALAR: t >= n; FEC_CANON_NO_KEY: Q at infinity -- in that order, the last two unobservable.
+ * The tweak-add's pipeline with its own first and last kernel; the state behind T || T is a constant, so the tweak costs one
+ * compression without a root and two with one. */
+int fec_canon_taproot_output_key(fec_ctx* ctx, const uint8_t* pks /* n*pk_len */, size_t pk_len, const uint8_t* roots /* n*32 or NULL */,
+                                 uint8_t* out_keys /* n*32 */, uint8_t* out_parity /* n */, uint8_t* status /* n */, size_t n);
+int fec_canon_taproot_output_key_dev(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_len, const uint8_t* d_roots, uint8_t* d_out_keys,
+                                     uint8_t* d_out_parity, uint8_t* d_status, size_t n, void* stream);
+
+/* BIP-32 CKDpub along a path: element i walks `depth` levels (1..255, BIP-32's depth byte; another depth: FEC_E_ARG) from its
+ * parent with the indices of row i of `indices` (n rows of depth, row-major).  n_par as fec_canon_bip32_derive_pub.  The results
+ * are byte-identical to depth successive fec_canon_bip32_derive_pub calls along the row, status[i] is the first status of that
+ * chain that is not 0: FEC_CANON_BAD_POINT (the given parent), FEC_CANON_BAD_INDEX (an index >= 2^31 at any level),
+ * FEC_CANON_BIP32_INVALID (IL >= n or the child at infinity, at any level).
+ * out_fingerprints (or NULL): the first four bytes of HASH160(serP(the last level's parent)), the four bytes the child's xpub
+ * record carries; out_hash160 (or NULL): HASH160 of the 33-byte child key.
+ * Between the levels the child stays affine in the work area and goes into the next HMAC message from there: no SEC 1 record
+ * and no square root per level. */
+int fec_canon_bip32_derive_pub_path(fec_ctx* ctx, const uint8_t* parent_pks /* n_par*33 */, const uint8_t* parent_ccs /* n_par*32 */,
+                                    size_t n_par, const uint32_t* indices /* n*depth */, size_t depth, uint8_t* out_pks /* n*33 */,
+                                    uint8_t* out_ccs /* n*32 */, uint8_t* out_fingerprints /* n*4 or NULL */,
+                                    uint8_t* out_hash160 /* n*20 or NULL */, uint8_t* status /* n */, size_t n);
+int fec_canon_bip32_derive_pub_path_dev(fec_ctx* ctx, const uint8_t* d_parent_pks, const uint8_t* d_parent_ccs, size_t n_par,
+                                        const uint32_t* d_indices, size_t depth, uint8_t* d_out_pks, uint8_t* d_out_ccs,
+                                        uint8_t* d_out_fingerprints, uint8_t* d_out_hash160, uint8_t* d_status, size_t n,
+                                        void* stream);
 
 #ifdef __cplusplus
 }

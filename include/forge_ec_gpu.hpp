@@ -13,6 +13,7 @@
 // batches of one and exist so that tests can be written like the reference's unit tests.
 // Failures surface as forge_ec::Error (GenericError, like forge-ec-core's Error::GenericError).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <memory>
@@ -1243,6 +1244,60 @@ inline Bip32Result bip32_derive_priv(GpuContext& ctx, const std::vector<eddsa::B
   Bip32Result r{std::vector<uint8_t>(n * 32), std::vector<eddsa::Bytes32>(n), std::vector<uint8_t>(n)};
   check(fec_canon_bip32_derive_priv(ctx.raw(), reinterpret_cast<const uint8_t*>(parent_keys.data()), reinterpret_cast<const uint8_t*>(parent_ccs.data()),
                                     n_par, indices.data(), flags, r.keys.data(), reinterpret_cast<uint8_t*>(r.chain_codes.data()), r.status.data(), n));
+  return r;
+}
+// RIPEMD-160 (sha_first = false) or HASH160 = RIPEMD-160(SHA-256(.)) of each message: n * 20 bytes
+inline std::vector<uint8_t> ripemd160(GpuContext& ctx, const std::vector<std::vector<uint8_t>>& msgs, bool sha_first = false) {
+  const size_t n = msgs.size();
+  std::vector<uint64_t> off(n + 1, 0);
+  for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + msgs[i].size();
+  std::vector<uint8_t> flat(off[n]), out(n * 20);
+  for (size_t i = 0; i < n; ++i) std::copy(msgs[i].begin(), msgs[i].end(), flat.begin() + off[i]);
+  check((sha_first ? fec_canon_hash160 : fec_canon_ripemd160)(ctx.raw(), flat.data(), off.data(), flat.size(), out.data(), n));
+  return out;
+}
+inline std::vector<uint8_t> hash160(GpuContext& ctx, const std::vector<std::vector<uint8_t>>& msgs) { return ripemd160(ctx, msgs, true); }
+// HASH160 of 33- or 65-byte records as their bytes lie: n * 20 bytes, the programs of P2PKH / P2WPKH outputs
+inline std::vector<uint8_t> pubkey_hash160(GpuContext& ctx, const std::vector<uint8_t>& keys, size_t key_len) {
+  if (key_len == 0 || keys.size() % key_len) throw Error(FEC_E_ARG);
+  const size_t n = keys.size() / key_len;
+  std::vector<uint8_t> out(n * 20);
+  check(fec_canon_pubkey_hash160(ctx.raw(), keys.data(), key_len, out.data(), n));
+  return out;
+}
+// Taproot output keys (BIP-341): keys of key_len 32 (x-only) or 33 bytes; roots: one per key, or empty for no script tree (BIP-86)
+struct TaprootResult {
+  std::vector<eddsa::Bytes32> keys;   // x(Q)
+  std::vector<uint8_t> parity;        // y(Q) & 1
+  std::vector<uint8_t> status;        // 0, FEC_CANON_BAD_POINT (FEC_CANON_BAD_SCALAR, FEC_CANON_NO_KEY: unobservable)
+};
+inline TaprootResult taproot_output_key(GpuContext& ctx, const std::vector<uint8_t>& keys, size_t key_len, const std::vector<eddsa::Bytes32>& roots) {
+  if (key_len == 0 || keys.size() % key_len) throw Error(FEC_E_ARG);
+  const size_t n = keys.size() / key_len;
+  if (!roots.empty() && roots.size() != n) throw Error(FEC_E_ARG);
+  TaprootResult r{std::vector<eddsa::Bytes32>(n), std::vector<uint8_t>(n), std::vector<uint8_t>(n)};
+  check(fec_canon_taproot_output_key(ctx.raw(), keys.data(), key_len, roots.empty() ? nullptr : reinterpret_cast<const uint8_t*>(roots.data()),
+                                     reinterpret_cast<uint8_t*>(r.keys.data()), r.parity.data(), r.status.data(), n));
+  return r;
+}
+// BIP-32 CKDpub along a path: indices holds n rows of depth (1..255) indices; parents as bip32_derive_pub
+struct Bip32PathResult {
+  std::vector<uint8_t> keys;               // n * 33
+  std::vector<eddsa::Bytes32> chain_codes;
+  std::vector<uint8_t> fingerprints;       // n * 4: of the last level's parent
+  std::vector<uint8_t> hash160;            // n * 20: of the child key
+  std::vector<uint8_t> status;             // the first of the chain that is not 0
+};
+inline Bip32PathResult bip32_derive_pub_path(GpuContext& ctx, const std::vector<uint8_t>& parent_keys, const std::vector<eddsa::Bytes32>& parent_ccs,
+                                             const std::vector<uint32_t>& indices, size_t depth) {
+  const size_t n_par = parent_ccs.size();
+  if (depth == 0 || indices.size() % depth || parent_keys.size() != n_par * 33) throw Error(FEC_E_ARG);
+  const size_t n = indices.size() / depth;
+  Bip32PathResult r{std::vector<uint8_t>(n * 33), std::vector<eddsa::Bytes32>(n), std::vector<uint8_t>(n * 4), std::vector<uint8_t>(n * 20),
+                    std::vector<uint8_t>(n)};
+  check(fec_canon_bip32_derive_pub_path(ctx.raw(), parent_keys.data(), reinterpret_cast<const uint8_t*>(parent_ccs.data()), n_par, indices.data(),
+                                        depth, r.keys.data(), reinterpret_cast<uint8_t*>(r.chain_codes.data()), r.fingerprints.data(),
+                                        r.hash160.data(), r.status.data(), n));
   return r;
 }
 }  // namespace canon

@@ -61,7 +61,23 @@ fec_canon_bip32_derive_pub_dev with n parents against the tweak-add (the differe
 fec_canon_bip32_derive_priv_dev on non-hardened indices against fec_canon_public_key_dev, the same secret comb;
 "derive-priv-hardened": under FEC_CANON_BIP32_NO_COMB against fec_sha512_dev on 64-byte messages, four compressions against
 one.  Last, one host-pointer row each.
+
+RIPEMD-160 / HASH160, Taproot output keys and CKDpub along a path on secp256k1, by the same method:
+
+    [FEC_AB_LIB=<another build of libfecgpu.so>] python tools/canon_perf.py wallet [log2_n] [reps] [out.jsonl]
+
+Before anything is timed: the path call at depth 2 and 3 must equal as many chained fec_canon_bip32_derive_pub_dev calls, its
+fingerprints and HASH160 must equal fec_canon_pubkey_hash160_dev of the chain's keys, and the Taproot call must equal
+fec_canon_pubkey_tweak_add_dev fed tweaks that fec_sha256_dev computed from the tag prefix.  "path-depth2" / "path-depth3" rows:
+fec_canon_bip32_derive_pub_path_dev with both optional outputs NULL against the chain -- the chain runs in the library named by
+FEC_AB_LIB where that is set (the build of the parent commit, loaded beside this one with a ctx of its own: the same box, the
+same process, alternating) and in this library otherwise; the row says which.  "path-optional" rows: the depth-2 call with
+out_hash160, with out_fingerprints and with both against both NULL.  "hash" rows: fec_canon_ripemd160_dev and
+fec_canon_hash160_dev against fec_sha256_dev (FEC_AB_LIB's where set) on the same 64-byte messages.  "taproot" rows:
+fec_canon_taproot_output_key_dev with and without roots against fec_canon_pubkey_tweak_add_dev (pk_len 32, out_len 32) fed
+precomputed tweaks.  Last, one host-pointer row each.
 """
+import ctypes
 import json
 import os
 import sys
@@ -612,6 +628,156 @@ def main_bip32():
                 f.write(json.dumps(r) + "\n")
 
 
+def main_wallet():
+    from forge_ec_amd.canon import CanonBip32, CanonKeccak
+    logn = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    out_path = sys.argv[4] if len(sys.argv) > 4 else None
+    n = 1 << logn
+    ctx = F.Context(0)
+    lib, h = ctx._lib, ctx._h
+    rng = np.random.default_rng(23)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()  # noqa: E731
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+    # the comparator library: another build beside this one, with a ctx of its own
+    base_lib, base_h, base_name = lib, h, "this build"
+    if os.environ.get("FEC_AB_LIB"):
+        vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+        base_lib = ctypes.CDLL(os.path.abspath(os.environ["FEC_AB_LIB"]))
+        base_lib.fec_ctx_create.argtypes = [ctypes.POINTER(vp), ci]
+        base_lib.fec_ctx_destroy.argtypes = [vp]
+        base_lib.fec_ctx_destroy.restype = None
+        base_lib.fec_canon_bip32_derive_pub_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]
+        base_lib.fec_canon_pubkey_tweak_add_dev.argtypes = [vp, ci, vp, sz, vp, vp, sz, vp, sz, vp]
+        base_lib.fec_sha256_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+        hh = vp()
+        assert base_lib.fec_ctx_create(ctypes.byref(hh), 0) == 0
+        base_h, base_name = hh, os.path.basename(os.environ["FEC_AB_LIB"])
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    def rounds(fns):
+        """each of fns three times, alternating; per fn the middle round's median and the largest spread"""
+        got = [[] for _ in fns]
+        for _ in range(3):
+            for g, fn in zip(got, fns):
+                g.append(_timed(fn, reps))
+        return [(sorted(g)[1][0], max(x[1] for x in g)) for g in got]
+
+    def pair(row, npass, names, fns, **extra):
+        a, b = rounds(fns)
+        emit(dict({"row": row, "pass": npass, "n": n, "reps": reps, names[0] + "_ms": round(a[0], 4), names[0] + "_spread_ms": round(a[1], 4),
+                   names[1] + "_ms": round(b[0], 4), names[1] + "_spread_ms": round(b[1], 4), "ratio": round(a[0] / b[0], 4),
+                   "M_per_s": round(n / a[0] / 1e3, 3)}, **extra))
+
+    cv, hd, hs = CANON_CURVES["secp256k1"](ctx), CanonBip32(ctx), CanonKeccak(ctx)
+    keys_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    keys_h[:, 0] &= 0x7F
+    keys_h[:, 31] |= 1
+    cc_h = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    idx_h = rng.integers(0, 1 << 31, size=(n, 3), dtype=np.uint32)
+    msg64_h = rng.integers(0, 256, size=(n, 64), dtype=np.uint8)
+    keys, cc, msg64 = dev(keys_h), dev(cc_h), dev(msg64_h)
+    idx3, idx2 = dev(idx_h), dev(idx_h[:, :2])
+    col = [dev(idx_h[:, j]) for j in range(3)]
+    off64 = torch.arange(0, 64 * (n + 1), 64, dtype=torch.int64, device="cuda")
+    pk33, ka, kb, out33 = (torch.empty((n, 33), dtype=torch.uint8, device="cuda") for _ in range(4))
+    ca, cb, occ, x32, t32, q32, q32b, dg32 = (torch.empty((n, 32), dtype=torch.uint8, device="cuda") for _ in range(8))
+    fp, fpb = (torch.empty((n, 4), dtype=torch.uint8, device="cuda") for _ in range(2))
+    h20, h20b = (torch.empty((n, 20), dtype=torch.uint8, device="cuda") for _ in range(2))
+    s1, s2, par = (torch.empty(n, dtype=torch.uint8, device="cuda") for _ in range(3))
+    P = lambda t: t.data_ptr()  # noqa: E731
+    cv.public_key_dev(P(keys), P(pk33), 33, P(s1), n, st)
+    torch.cuda.synchronize()
+    assert not bool(s1.any())
+
+    def chain(depth, L=None, hh=None):
+        """depth chained derive_pub_dev calls: the last level's parent is left in ka or kb, the child in the other"""
+        L, hh = L or lib, hh or h
+        src, scc = (pk33, cc)
+        bufs = [(ka, ca), (kb, cb)]
+        for level in range(depth):
+            dk, dc = bufs[level & 1]
+            rc = L.fec_canon_bip32_derive_pub_dev(hh, P(src), P(scc), n, P(col[level]), P(dk), P(dc), P(s2), n, st)
+            assert rc == 0
+            src, scc = dk, dc
+        return src, scc
+
+    # what the timed calls must agree on
+    for depth, ix in ((2, idx2), (3, idx3)):
+        hd.derive_pub_path_dev(P(pk33), P(cc), n, P(ix), depth, P(out33), P(occ), P(fp), P(h20), P(s1), n, st)
+        child, ccc = chain(depth)
+        parent = kb if child is ka else ka
+        hs.pubkey_hash160_dev(P(child), 33, P(h20b), n, st)
+        torch.cuda.synchronize()
+        assert not bool(s1.any()) and not bool(s2.any()) and bool((out33 == child).all()) and bool((occ == ccc).all()) and bool((h20 == h20b).all())
+        hs.pubkey_hash160_dev(P(parent), 33, P(h20b), n, st)
+        torch.cuda.synchronize()
+        assert bool((fp == h20b[:, :4]).all())
+    x32.copy_(pk33[:, 1:])
+    tag = np.frombuffer(__import__("hashlib").sha256(b"TapTweak").digest() * 2, dtype=np.uint8)
+    pre96 = torch.cat([torch.from_numpy(tag.copy()).cuda().expand(n, 64), x32], dim=1).contiguous()
+    pre128 = torch.cat([pre96, cc.view(n, 32)], dim=1).contiguous()
+    off96 = torch.arange(0, 96 * (n + 1), 96, dtype=torch.int64, device="cuda")
+    off128 = torch.arange(0, 128 * (n + 1), 128, dtype=torch.int64, device="cuda")
+    for roots, pre, off, width in ((None, pre96, off96, 96), (cc, pre128, off128, 128)):
+        assert lib.fec_sha256_dev(h, P(pre), P(off), width * n, P(t32), P(s2), n, st) == 0
+        cv.pubkey_tweak_add_dev(P(x32), 32, P(t32), P(q32b), 32, P(s2), n, st)
+        cv.taproot_output_key_dev(P(x32), 32, P(roots) if roots is not None else None, P(q32), P(par), P(s1), n, st)
+        torch.cuda.synchronize()
+        assert not bool(s1.any()) and not bool(s2.any()) and bool((q32 == q32b).all())
+
+    for npass in range(2):
+        for depth, ix in ((2, idx2), (3, idx3)):
+            pair("path-depth%d" % depth, npass, ("bip32_derive_pub_path_dev", "%d_chained_bip32_derive_pub_dev" % depth), [
+                lambda: hd.derive_pub_path_dev(P(pk33), P(cc), n, P(ix), depth, P(out33), P(occ), None, None, P(s1), n, st),
+                lambda: chain(depth, base_lib, base_h)], chain_library=base_name)
+        both_null = lambda: hd.derive_pub_path_dev(P(pk33), P(cc), n, P(idx2), 2, P(out33), P(occ), None, None, P(s1), n, st)  # noqa: E731
+        pair("path-optional", npass, ("path_dev_depth2_hash160", "path_dev_depth2_both_null"), [
+            lambda: hd.derive_pub_path_dev(P(pk33), P(cc), n, P(idx2), 2, P(out33), P(occ), None, P(h20), P(s1), n, st), both_null])
+        pair("path-optional", npass, ("path_dev_depth2_fingerprints", "path_dev_depth2_both_null"), [
+            lambda: hd.derive_pub_path_dev(P(pk33), P(cc), n, P(idx2), 2, P(out33), P(occ), P(fp), None, P(s1), n, st), both_null])
+        pair("path-optional", npass, ("path_dev_depth2_both", "path_dev_depth2_both_null"), [
+            lambda: hd.derive_pub_path_dev(P(pk33), P(cc), n, P(idx2), 2, P(out33), P(occ), P(fp), P(h20), P(s1), n, st), both_null])
+        sha = lambda: base_lib.fec_sha256_dev(base_h, P(msg64), P(off64), 64 * n, P(dg32), P(s2), n, st)  # noqa: E731
+        pair("hash", npass, ("ripemd160_dev_64B", "sha256_dev_64B"), [
+            lambda: hs.ripemd160_dev(P(msg64), P(off64), 64 * n, P(h20), P(s1), n, st), sha], sha256_library=base_name)
+        pair("hash", npass, ("hash160_dev_64B", "sha256_dev_64B"), [
+            lambda: hs.hash160_dev(P(msg64), P(off64), 64 * n, P(h20), P(s1), n, st), sha], sha256_library=base_name)
+        pair("hash", npass, ("pubkey_hash160_dev_33", "sha256_dev_64B"), [
+            lambda: hs.pubkey_hash160_dev(P(pk33), 33, P(h20), n, st), sha], sha256_library=base_name)
+        tweak_add = lambda: base_lib.fec_canon_pubkey_tweak_add_dev(base_h, 0, P(x32), 32, P(t32), P(q32b), 32, P(s2), n, st)  # noqa: E731
+        pair("taproot", npass, ("taproot_output_key_dev_roots", "pubkey_tweak_add_dev_32_32"), [
+            lambda: cv.taproot_output_key_dev(P(x32), 32, P(cc), P(q32), P(par), P(s1), n, st), tweak_add], tweak_add_library=base_name)
+        pair("taproot", npass, ("taproot_output_key_dev_no_roots", "pubkey_tweak_add_dev_32_32"), [
+            lambda: cv.taproot_output_key_dev(P(x32), 32, None, P(q32), P(par), P(s1), n, st), tweak_add], tweak_add_library=base_name)
+        torch.cuda.synchronize()
+        assert not bool(s1.any()) and not bool(s2.any())
+    p = lambda a: a.ctypes.data  # noqa: E731
+    pk_h, x_h = pk33.cpu().numpy(), x32.cpu().numpy()
+    off_h = np.arange(0, 64 * (n + 1), 64, dtype=np.uint64)
+    o33, o32, o20, o4, st_h, par_h = (np.zeros((n, w), np.uint8) for w in (33, 32, 20, 4, 1, 1))
+    for name, fn in (("ripemd160_64B", lambda: lib.fec_canon_ripemd160(h, p(msg64_h), p(off_h), 64 * n, p(o20), n)),
+                     ("hash160_64B", lambda: lib.fec_canon_hash160(h, p(msg64_h), p(off_h), 64 * n, p(o20), n)),
+                     ("pubkey_hash160_33", lambda: lib.fec_canon_pubkey_hash160(h, p(pk_h), 33, p(o20), n)),
+                     ("taproot_output_key_roots", lambda: lib.fec_canon_taproot_output_key(h, p(x_h), 32, p(cc_h), p(o32), p(par_h), p(st_h), n)),
+                     ("bip32_derive_pub_path_depth3_all_outputs",
+                      lambda: lib.fec_canon_bip32_derive_pub_path(h, p(pk_h), p(cc_h), n, p(idx_h), 3, p(o33), p(o32), p(o4), p(o20), p(st_h), n))):
+        assert fn() == 0
+        ms, spread = _timed(fn, reps)
+        emit({"row": "host-" + name, "n": n, "reps": reps, "ms": round(ms, 4), "spread_ms": round(spread, 4), "M_per_s": round(n / ms / 1e3, 3)})
+    if base_lib is not lib:
+        torch.cuda.synchronize()
+        base_lib.fec_ctx_destroy(base_h)
+    if out_path:
+        with open(out_path, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     logn = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -677,5 +843,7 @@ elif len(sys.argv) > 1 and sys.argv[1] == "recover":
     main_recover()
 elif len(sys.argv) > 1 and sys.argv[1] == "bip32":
     main_bip32()
+elif len(sys.argv) > 1 and sys.argv[1] == "wallet":
+    main_wallet()
 else:
     main()
