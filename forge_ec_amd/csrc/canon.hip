@@ -19,8 +19,62 @@ using namespace fecgpu::host;
 namespace {
 
 // ---- canonical-math mode -------------------------------------------------------------------
-inline bool canon_curve_ok(int c) { return curve_ok(c); }
+// One per-curve dispatch of the kernel templates of this file: f(tag).  From the tag a generic lambda takes the parameters (P),
+// the curve of the point kernels (C) and the group order (N).  Ed25519 has no P; where its kernel has a name and an argument
+// list of its own, the launcher branches to it first and dispatches the other two through with_weierstrass.
+template <class Params>
+struct WeiTag {
+  using P = Params;
+  using C = canon::wei<P>;
+  using N = typename canon::order_of<P>::N;
+};
+struct EdTag {
+  using C = ced;
+  using N = canon::NEd;
+};
+template <class F>
+void with_curve(int curve, F&& f) {
+  switch (curve) {
+    case FEC_SECP256K1: f(WeiTag<canon::SecpParams>{}); break;
+    case FEC_P256: f(WeiTag<canon::P256Params>{}); break;
+    default: f(EdTag{}); break;
+  }
+}
+// ... of what has no Ed25519 form (a launcher whose entry point has turned Ed25519 away: weierstrass_only)
+template <class F>
+void with_weierstrass(int curve, F&& f) {
+  if (curve == FEC_SECP256K1) f(WeiTag<canon::SecpParams>{});
+  else f(WeiTag<canon::P256Params>{});
+}
+// FEC_OK on secp256k1 and P-256; Ed25519 is a curve, but none of the caller's
+inline int weierstrass_only(int curve) {
+  if (curve == FEC_SECP256K1 || curve == FEC_P256) return FEC_OK;
+  return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+}
 
+// The launch stream, ordered behind the ctx's previous launch: the work areas, the comb tables and the error word are the ctx's.
+inline hipStream_t ordered_stream(fec_ctx* ctx, void* stream) {
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  order_after_previous(ctx, s);
+  return s;
+}
+// lanes of the batched normalisation and of the kernels built like it: one per NORM_GROUP elements, in whole wavefronts
+inline size_t norm_stride(size_t n) {
+  const size_t lanes = (n + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
+  return (lanes + 63) / 64 * 64;
+}
+
+// The end of a comb table's build: the table is read by kernels on either pipeline stream, so it is finished before it is
+// published and nobody can race it.
+int publish_comb(hipStream_t s, bool& ready) {
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  if (hipStreamSynchronize(s) != hipSuccess) {
+    (void)hipGetLastError();
+    return FEC_E_LAUNCH;
+  }
+  ready = true;
+  return FEC_OK;
+}
 int ensure_canon_comb(fec_ctx* ctx, int curve, hipStream_t s) {
   if (ctx->canon_comb_ready[curve]) return FEC_OK;
   if (!ctx->d_canon_comb[curve] &&
@@ -29,19 +83,12 @@ int ensure_canon_comb(fec_ctx* ctx, int curve, hipStream_t s) {
     (void)hipGetLastError();
     return FEC_E_OOM;
   }
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_build_comb<csecp>), dim3(1), dim3(64), 0, s, ctx->d_canon_comb[curve]);
-  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_build_comb<cp256>), dim3(1), dim3(64), 0, s, ctx->d_canon_comb[curve]);
-  else hipLaunchKernelGGL(k_ced_build_comb, dim3(1), dim3(64), 0, s, ctx->d_canon_comb[curve]);
-  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
-  // the table is read by kernels on either pipeline stream: finish it before anyone can race
-  if (hipStreamSynchronize(s) != hipSuccess) {
-    (void)hipGetLastError();
-    return FEC_E_LAUNCH;
-  }
-  ctx->canon_comb_ready[curve] = true;
-  return FEC_OK;
+  if (curve == FEC_ED25519) hipLaunchKernelGGL(k_ced_build_comb, dim3(1), dim3(64), 0, s, ctx->d_canon_comb[curve]);
+  else with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_build_comb<typename decltype(t)::C>), dim3(1), dim3(64), 0, s, ctx->d_canon_comb[curve]);
+  });
+  return publish_comb(s, ctx->canon_comb_ready[curve]);
 }
-
 int ensure_canon_comb8(fec_ctx* ctx, int curve, hipStream_t s) {
   if (ctx->canon_comb8_ready[curve]) return FEC_OK;
   if (!ctx->d_canon_comb8[curve] &&
@@ -50,16 +97,11 @@ int ensure_canon_comb8(fec_ctx* ctx, int curve, hipStream_t s) {
     (void)hipGetLastError();
     return FEC_E_OOM;
   }
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_build_comb8<csecp>), dim3(canon::COMB8_WINDOWS), dim3(TPB), 0, s, ctx->d_canon_comb8[curve]);
-  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_build_comb8<cp256>), dim3(canon::COMB8_WINDOWS), dim3(TPB), 0, s, ctx->d_canon_comb8[curve]);
-  else hipLaunchKernelGGL(k_ced_build_comb8, dim3(canon::COMB8_WINDOWS + 1), dim3(TPB), 0, s, ctx->d_canon_comb8[curve]);
-  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
-  if (hipStreamSynchronize(s) != hipSuccess) {
-    (void)hipGetLastError();
-    return FEC_E_LAUNCH;
-  }
-  ctx->canon_comb8_ready[curve] = true;
-  return FEC_OK;
+  if (curve == FEC_ED25519) hipLaunchKernelGGL(k_ced_build_comb8, dim3(canon::COMB8_WINDOWS + 1), dim3(TPB), 0, s, ctx->d_canon_comb8[curve]);
+  else with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_build_comb8<typename decltype(t)::C>), dim3(canon::COMB8_WINDOWS), dim3(TPB), 0, s, ctx->d_canon_comb8[curve]);
+  });
+  return publish_comb(s, ctx->canon_comb8_ready[curve]);
 }
 
 // grow-only device buffer owned by the ctx (kernels of earlier calls may still use the old one)
@@ -77,14 +119,19 @@ int ensure_owned(void** buf, size_t* cap, size_t need) {
   return FEC_OK;
 }
 
-int launch_canon_normalize(fec_ctx* ctx, int curve, u64* dxy, unsigned char* dst, size_t n, hipStream_t s) {
-  const size_t lanes = (n + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
-  const size_t stride = (lanes + 63) / 64 * 64;
-  u32* xy = reinterpret_cast<u32*>(dxy);
-  const u32* z = reinterpret_cast<const u32*>(ctx->d_zbuf);
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_normalize<csecp>), dim3(grid_for(stride)), dim3(TPB), 0, s, xy, z, dst, n, stride);
-  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_normalize<cp256>), dim3(grid_for(stride)), dim3(TPB), 0, s, xy, z, dst, n, stride);
-  else hipLaunchKernelGGL((k_canon_normalize<ced>), dim3(grid_for(stride)), dim3(TPB), 0, s, xy, z, dst, n, stride);
+// A launcher's work area in the ctx's d_verify: the buffer grown to hold `area`, then the area's regions placed on it.
+int place_in_verify(fec_ctx* ctx, WorkArea& area) {
+  const int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, area.bytes());
+  if (rc == FEC_OK) area.place(ctx->d_verify);
+  return rc;
+}
+
+// the batched normalisation: xy / z -> affine xy, dst says where z was zero.  z: the ctx's d_zbuf, or a signer's own.
+int launch_canon_normalize(int curve, u32* xy, const u32* z, unsigned char* dst, size_t n, hipStream_t s) {
+  const size_t stride = norm_stride(n);
+  with_curve(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_normalize<typename decltype(t)::C>), dim3(grid_for(stride)), dim3(TPB), 0, s, xy, z, dst, n, stride);
+  });
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 
@@ -104,13 +151,16 @@ int launch_canon_mul_base(fec_ctx* ctx, int curve, const u64* ds, u64* dxy, unsi
   const u32* k = reinterpret_cast<const u32*>(ds);
   u32* xy = reinterpret_cast<u32*>(dxy);
   u32* z = reinterpret_cast<u32*>(ctx->d_zbuf);
-  if (comb8 && curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_mul_base8<csecp>), dim3(grid_for(n)), dim3(TPB), 0, L.s, k, ctx->d_canon_comb8[curve], xy, z, dst, n);
-  else if (comb8 && curve == FEC_P256) hipLaunchKernelGGL((k_canon_mul_base8<cp256>), dim3(grid_for(n)), dim3(TPB), 0, L.s, k, ctx->d_canon_comb8[curve], xy, z, dst, n);
-  else if (comb8) hipLaunchKernelGGL(k_ced_mul_base8, dim3(grid_for(n)), dim3(TPB), 0, L.s, k, ctx->d_canon_comb8[curve], xy, z, tb, dst, n);
-  else if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_mul_base<csecp>), dim3(grid_for(n)), dim3(TPB), 0, L.s, k, ctx->d_canon_comb[curve], xy, z, dst, n);
-  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_mul_base<cp256>), dim3(grid_for(n)), dim3(TPB), 0, L.s, k, ctx->d_canon_comb[curve], xy, z, dst, n);
-  else hipLaunchKernelGGL(k_ced_mul_base, dim3(grid_for(n)), dim3(TPB), 0, L.s, k, ctx->d_canon_comb[curve], xy, z, tb, dst, n);
-  rc = finish ? launch_canon_normalize(ctx, curve, dxy, dst, n, L.s) : FEC_OK;
+  const u32* tab = comb8 ? ctx->d_canon_comb8[curve] : ctx->d_canon_comb[curve];
+  dim3 g(grid_for(n)), b(TPB);
+  if (curve == FEC_ED25519 && comb8) hipLaunchKernelGGL(k_ced_mul_base8, g, b, 0, L.s, k, tab, xy, z, tb, dst, n);
+  else if (curve == FEC_ED25519) hipLaunchKernelGGL(k_ced_mul_base, g, b, 0, L.s, k, tab, xy, z, tb, dst, n);
+  else with_weierstrass(curve, [&](auto t) {
+    using C = typename decltype(t)::C;
+    if (comb8) hipLaunchKernelGGL((k_canon_mul_base8<C>), g, b, 0, L.s, k, tab, xy, z, dst, n);
+    else hipLaunchKernelGGL((k_canon_mul_base<C>), g, b, 0, L.s, k, tab, xy, z, dst, n);
+  });
+  rc = finish ? launch_canon_normalize(curve, xy, z, dst, n, L.s) : FEC_OK;
   int rc2 = L.done();
   return rc != FEC_OK ? rc : rc2;
 }
@@ -131,97 +181,96 @@ int launch_canon_mul(fec_ctx* ctx, int curve, const u64* ds, const u64* dp, u64*
   u32* xy = reinterpret_cast<u32*>(dxy);
   u32* z = reinterpret_cast<u32*>(ctx->d_zbuf);
   dim3 g(grid_for(n)), b(TPB);
-  if (curve == FEC_SECP256K1) {
-    if (accum) hipLaunchKernelGGL((k_canon_mul<csecp, true>), g, b, 0, L.s, k, p, scratch, xy, z, dst, n);
-    else hipLaunchKernelGGL((k_canon_mul<csecp, false>), g, b, 0, L.s, k, p, scratch, xy, z, dst, n);
-  } else if (curve == FEC_P256) {
-    if (accum) hipLaunchKernelGGL((k_canon_mul<cp256, true>), g, b, 0, L.s, k, p, scratch, xy, z, dst, n);
-    else hipLaunchKernelGGL((k_canon_mul<cp256, false>), g, b, 0, L.s, k, p, scratch, xy, z, dst, n);
-  } else {
-    hipLaunchKernelGGL(k_ced_mul, g, b, 0, L.s, k, p, scratch, xy, z, tb, dst, n);
-  }
-  rc = launch_canon_normalize(ctx, curve, dxy, dst, n, L.s);
+  if (curve == FEC_ED25519) hipLaunchKernelGGL(k_ced_mul, g, b, 0, L.s, k, p, scratch, xy, z, tb, dst, n);
+  else with_weierstrass(curve, [&](auto t) {
+    using C = typename decltype(t)::C;
+    if (accum) hipLaunchKernelGGL((k_canon_mul<C, true>), g, b, 0, L.s, k, p, scratch, xy, z, dst, n);
+    else hipLaunchKernelGGL((k_canon_mul<C, false>), g, b, 0, L.s, k, p, scratch, xy, z, dst, n);
+  });
+  rc = launch_canon_normalize(curve, xy, z, dst, n, L.s);
   int rc2 = L.done();
   return rc != FEC_OK ? rc : rc2;
 }
+// u1*G + u2*P into dxy, Z in the ctx's d_zbuf on the way: the comb leaves u1*G projective (finish = false), the ladder adds
+// u2*P onto it (accum = true) and normalises.
+int launch_canon_double_mul(fec_ctx* ctx, int curve, const u64* du1, const u64* du2, const u64* dp, u64* dxy, unsigned char* dst,
+                            size_t n, void* stream) {
+  const int rc = launch_canon_mul_base(ctx, curve, du1, dxy, dst, n, stream, false);
+  return rc != FEC_OK ? rc : launch_canon_mul(ctx, curve, du2, dp, dxy, dst, n, stream, true);
+}
 
-// ECDSA verification: scalars -> u1*G + u2*Q -> compare.  d_work: u1, u2 (n*32 each), xy (n*64),
-// point status (n), range flags (n).
-inline size_t canon_ecdsa_work_bytes(size_t n) { return n * (32 + 32 + 64 + 1 + 1) + 64; }
+// ECDSA verification and recovery: scalars -> u1*G + u2*Q -> compare or encode.  Work area: u1, u2 (n*32 each), the result xy
+// (n*64), point status (n), range flags (n); recovery adds R (n*64); verification from the message adds what its prepare
+// kernel parses and decodes -- z, r, s (n*32 each), the key (n*64) -- and the message flags (n).
+enum class EcdsaForm { kAfterHash, kFromMessage, kRecover };
+struct VerifyWork {
+  u32 *u1, *u2, *xy;
+  unsigned char *pst, *ok;
+  u32* rxy;                  // recovery only
+  u32 *z, *r, *s, *pk;       // from the message only
+  unsigned char* flag;       // from the message only
+};
+int verify_work(fec_ctx* ctx, size_t n, EcdsaForm form, VerifyWork& w) {
+  WorkArea area;
+  area.add(w.u1, n * 32).add(w.u2, n * 32).add(w.xy, n * 64).add(w.pst, n).add(w.ok, n);
+  if (form == EcdsaForm::kRecover) area.add(w.rxy, n * 64);
+  if (form == EcdsaForm::kFromMessage) area.add(w.z, n * 32).add(w.r, n * 32).add(w.s, n * 32).add(w.pk, n * 64).add(w.flag, n);
+  return place_in_verify(ctx, area);
+}
+// Everything behind the ordering of the after-the-hash form and behind the prepare kernel of the from-the-message form.
+int launch_canon_ecdsa_tail(fec_ctx* ctx, int curve, const VerifyWork& w, const u64* dz, const u64* dr, const u64* ds,
+                            const u64* dpk, unsigned char* dres, size_t n, hipStream_t s) {
+  dim3 g(grid_for(n)), b(TPB);
+  const size_t stride = norm_stride(n);
+  with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_ecdsa_scalars<typename decltype(t)::N>), dim3(grid_for(stride)), b, 0, s, (const u32*)dz, (const u32*)dr,
+                       (const u32*)ds, w.u1, w.u2, w.ok, n, stride);
+  });
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  const int rc = launch_canon_double_mul(ctx, curve, (const u64*)w.u1, (const u64*)w.u2, dpk, (u64*)w.xy, w.pst, n, s);
+  if (rc != FEC_OK) return rc;
+  with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_ecdsa_finish<typename decltype(t)::N>), g, b, 0, s, w.xy, (const u32*)dr, w.ok, w.pst, dres, n);
+  });
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
 int launch_canon_ecdsa_verify(fec_ctx* ctx, int curve, const u64* dz, const u64* dr, const u64* ds, const u64* dpk,
                               unsigned char* dres, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, canon_ecdsa_work_bytes(n));
+  VerifyWork w;
+  const int rc = verify_work(ctx, n, EcdsaForm::kAfterHash, w);
   if (rc != FEC_OK) return rc;
-  char* base = (char*)ctx->d_verify;
-  u64* u1 = (u64*)base;
-  u64* u2 = (u64*)(base + n * 32);
-  u64* xy = (u64*)(base + n * 64);
-  unsigned char* pst = (unsigned char*)(base + n * 128);
-  unsigned char* ok = pst + n;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // the work area is the ctx's
-  dim3 g(grid_for(n)), b(TPB);
-  const size_t lanes = (n + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
-  const size_t stride = (lanes + 63) / 64 * 64;
-  dim3 gs(grid_for(stride));
-  if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL((k_canon_ecdsa_scalars<canon::NSecp>), gs, b, 0, s, (const u32*)dz, (const u32*)dr, (const u32*)ds,
-                       (u32*)u1, (u32*)u2, ok, n, stride);
-  else
-    hipLaunchKernelGGL((k_canon_ecdsa_scalars<canon::NP256>), gs, b, 0, s, (const u32*)dz, (const u32*)dr, (const u32*)ds,
-                       (u32*)u1, (u32*)u2, ok, n, stride);
-  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
-  rc = launch_canon_mul_base(ctx, curve, u1, xy, pst, n, stream, false);
-  if (rc == FEC_OK) rc = launch_canon_mul(ctx, curve, u2, dpk, xy, pst, n, stream, true);
-  if (rc != FEC_OK) return rc;
-  if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL((k_canon_ecdsa_finish<canon::NSecp>), g, b, 0, s, (const u32*)xy, (const u32*)dr, ok, pst, dres, n);
-  else
-    hipLaunchKernelGGL((k_canon_ecdsa_finish<canon::NP256>), g, b, 0, s, (const u32*)xy, (const u32*)dr, ok, pst, dres, n);
-  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+  hipStream_t s = ordered_stream(ctx, stream);
+  return launch_canon_ecdsa_tail(ctx, curve, w, dz, dr, ds, dpk, dres, n, s);
 }
 
 // BIP-340 / EdDSA: prepare -> u1*G + u2*P -> final test.  Work area: P xy (n*64), expected R xy (n*64,
 // EdDSA only), u2 (n*32), result xy (n*64), point status (n), flags (n); the from-the-message forms add what their
 // prepare kernel parses out of the signature bytes -- s (n*32), r (n*32) -- and the message flags (n).
 struct SigWork {
-  u64 *pxy, *rxy, *u2, *xy;
+  u32 *pxy, *rxy, *u2, *xy;
   unsigned char *pst, *ok;
-  u64 *s, *r;            // from the message only
+  u32 *s, *r;            // from the message only
   unsigned char* flag;   // from the message only
 };
 int sig_work(fec_ctx* ctx, size_t n, bool from_msg, SigWork& w) {
-  const size_t after_hash = n * (64 + 64 + 32 + 64 + 1 + 1) + 64;
-  const size_t wire = (after_hash + 255) & ~(size_t)255;
-  const int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, from_msg ? wire + n * (32 + 32 + 1) : after_hash);
-  if (rc != FEC_OK) return rc;
-  char* base = (char*)ctx->d_verify;
-  w.pxy = (u64*)base;
-  w.rxy = (u64*)(base + n * 64);
-  w.u2 = (u64*)(base + n * 128);
-  w.xy = (u64*)(base + n * 160);
-  w.pst = (unsigned char*)(base + n * 224);
-  w.ok = w.pst + n;
-  w.s = (u64*)(base + wire);
-  w.r = (u64*)(base + wire + n * 32);
-  w.flag = (unsigned char*)(base + wire + n * 64);
-  return FEC_OK;
+  WorkArea area;
+  area.add(w.pxy, n * 64).add(w.rxy, n * 64).add(w.u2, n * 32).add(w.xy, n * 64).add(w.pst, n).add(w.ok, n);
+  if (from_msg) area.add(w.s, n * 32).add(w.r, n * 32).add(w.flag, n);
+  return place_in_verify(ctx, area);
 }
 // Everything after the prepare step, which has filled w.pxy, w.u2, w.ok (and w.rxy for EdDSA): d_s = u1, d_r = the r the
 // BIP-340 finish compares with.  The after-the-hash and the from-the-message forms differ in their prepare kernel only.
 int launch_canon_sig_finish(fec_ctx* ctx, int curve, const SigWork& w, const u64* d_r, const u64* d_s, unsigned char* dres,
-                            size_t n, void* stream) {
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+                            size_t n, hipStream_t s) {
   dim3 g(grid_for(n)), b(TPB);
   if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;   // the prepare kernel's launch
-  int rc = launch_canon_mul_base(ctx, curve, d_s, w.xy, w.pst, n, stream, false);   // u1 = s
-  if (rc == FEC_OK) rc = launch_canon_mul(ctx, curve, w.u2, w.pxy, w.xy, w.pst, n, stream, true);
+  const int rc = launch_canon_double_mul(ctx, curve, d_s, (const u64*)w.u2, (const u64*)w.pxy, (u64*)w.xy, w.pst, n, s);   // u1 = s
   if (rc != FEC_OK) return rc;
   if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL(k_canon_bip340_finish, g, b, 0, s, (const u32*)w.xy, (const u32*)d_r, w.ok, w.pst, dres, n);
+    hipLaunchKernelGGL(k_canon_bip340_finish, g, b, 0, s, w.xy, (const u32*)d_r, w.ok, w.pst, dres, n);
   else
-    hipLaunchKernelGGL(k_ced_eddsa_finish, g, b, 0, s, (const u32*)w.xy, (const u32*)w.rxy, w.ok, w.pst, dres, n);
+    hipLaunchKernelGGL(k_ced_eddsa_finish, g, b, 0, s, w.xy, w.rxy, w.ok, w.pst, dres, n);
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 int launch_canon_sig_verify(fec_ctx* ctx, int curve, const u64* d_key, const u64* d_r, const u64* d_s, const u64* d_e,
@@ -230,16 +279,15 @@ int launch_canon_sig_verify(fec_ctx* ctx, int curve, const u64* d_key, const u64
   SigWork w;
   const int rc = sig_work(ctx, n, false, w);
   if (rc != FEC_OK) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // the work area is the ctx's
+  hipStream_t s = ordered_stream(ctx, stream);
   dim3 g(grid_for(n)), b(TPB);
   if (curve == FEC_SECP256K1)
     hipLaunchKernelGGL(k_canon_bip340_prepare, g, b, 0, s, (const u32*)d_key, (const u32*)d_r, (const u32*)d_s,
-                       (const u32*)d_e, (u32*)w.pxy, (u32*)w.u2, w.ok, n);
+                       (const u32*)d_e, w.pxy, w.u2, w.ok, n);
   else
     hipLaunchKernelGGL(k_ced_eddsa_prepare, g, b, 0, s, (const u32*)d_key, (const u32*)d_r, (const u32*)d_s,
-                       (const u32*)d_e, (u32*)w.pxy, (u32*)w.rxy, (u32*)w.u2, w.ok, n);
-  return launch_canon_sig_finish(ctx, curve, w, d_r, d_s, dres, n, stream);
+                       (const u32*)d_e, w.pxy, w.rxy, w.u2, w.ok, n);
+  return launch_canon_sig_finish(ctx, curve, w, d_r, d_s, dres, n, s);
 }
 int launch_canon_msg_fold(unsigned char* dres, const unsigned char* flag, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_canon_msg_fold, dim3(grid_for(n)), dim3(TPB), 0, s, dres, flag, n);
@@ -252,53 +300,45 @@ int launch_canon_sig_verify_msg(fec_ctx* ctx, int curve, const Messages& m, cons
   SigWork w;
   int rc = sig_work(ctx, n, true, w);
   if (rc != FEC_OK) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // the work area is the ctx's
+  hipStream_t s = ordered_stream(ctx, stream);
   dim3 g(grid_for(n)), b(TPB);
   if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL(k_canon_bip340_prepare_msg, g, b, 0, s, m, (const u32*)d_sigs, (const u32*)d_pks, (u32*)w.pxy,
-                       (u32*)w.u2, (u32*)w.r, (u32*)w.s, w.ok, w.flag, n);
+    hipLaunchKernelGGL(k_canon_bip340_prepare_msg, g, b, 0, s, m, (const u32*)d_sigs, (const u32*)d_pks, w.pxy, w.u2, w.r, w.s, w.ok,
+                       w.flag, n);
   else
-    hipLaunchKernelGGL(k_ced_eddsa_prepare_msg, g, b, 0, s, m, (const u32*)d_sigs, (const u32*)d_pks, (u32*)w.pxy,
-                       (u32*)w.rxy, (u32*)w.u2, (u32*)w.s, w.ok, w.flag, n);
-  rc = launch_canon_sig_finish(ctx, curve, w, w.r, w.s, dres, n, stream);
+    hipLaunchKernelGGL(k_ced_eddsa_prepare_msg, g, b, 0, s, m, (const u32*)d_sigs, (const u32*)d_pks, w.pxy, w.rxy, w.u2, w.s, w.ok,
+                       w.flag, n);
+  rc = launch_canon_sig_finish(ctx, curve, w, (const u64*)w.r, (const u64*)w.s, dres, n, s);
   return rc != FEC_OK ? rc : launch_canon_msg_fold(dres, w.flag, n, s);
 }
 
-// ECDSA from the message: the prepare kernel writes z, r, s, the decoded key and the flags behind the area that
-// launch_canon_ecdsa_verify lays out for itself in d_verify (asked for here at the size of both, so it stays where it is).
+// ECDSA from the message: the prepare kernel writes z, r, s, the decoded key and the flags into regions of the same area,
+// and the after-the-hash pipeline runs on them.
 int launch_canon_ecdsa_verify_msg(fec_ctx* ctx, int curve, const Messages& m, const uint8_t* d_sigs, const uint8_t* d_pks,
                                   size_t pk_len, unsigned char* dres, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  const size_t wire = (canon_ecdsa_work_bytes(n) + 255) & ~(size_t)255;
-  int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, wire + n * (32 + 32 + 32 + 64 + 1));
+  VerifyWork w;
+  int rc = verify_work(ctx, n, EcdsaForm::kFromMessage, w);
   if (rc != FEC_OK) return rc;
-  char* base = (char*)ctx->d_verify + wire;
-  u64 *z = (u64*)base, *r = (u64*)(base + n * 32), *sv = (u64*)(base + n * 64), *pk = (u64*)(base + n * 96);
-  unsigned char* flag = (unsigned char*)(base + n * 160);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // the work area is the ctx's
-  dim3 g(grid_for(n)), b(TPB);
+  hipStream_t s = ordered_stream(ctx, stream);
   const int unc = pk_len == 65;
-  if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL((k_canon_ecdsa_prepare_msg<canon::SecpParams>), g, b, 0, s, m, (const u32*)d_sigs, d_pks, unc,
-                       (u32*)z, (u32*)r, (u32*)sv, (u32*)pk, flag, n);
-  else
-    hipLaunchKernelGGL((k_canon_ecdsa_prepare_msg<canon::P256Params>), g, b, 0, s, m, (const u32*)d_sigs, d_pks, unc,
-                       (u32*)z, (u32*)r, (u32*)sv, (u32*)pk, flag, n);
+  with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_ecdsa_prepare_msg<typename decltype(t)::P>), dim3(grid_for(n)), dim3(TPB), 0, s, m, (const u32*)d_sigs, d_pks,
+                       unc, w.z, w.r, w.s, w.pk, w.flag, n);
+  });
   if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
-  rc = launch_canon_ecdsa_verify(ctx, curve, z, r, sv, pk, dres, n, stream);
-  return rc != FEC_OK ? rc : launch_canon_msg_fold(dres, flag, n, s);
+  rc = launch_canon_ecdsa_tail(ctx, curve, w, (const u64*)w.z, (const u64*)w.r, (const u64*)w.s, (const u64*)w.pk, dres, n, s);
+  return rc != FEC_OK ? rc : launch_canon_msg_fold(dres, w.flag, n, s);
 }
 
 int launch_canon_decompress(fec_ctx* ctx, int curve, const uint8_t* d_in, size_t pk_len, u64* d_xy, unsigned char* d_st,
                             size_t n, void* stream) {
   if (n == 0) return FEC_OK;
   Launch L(ctx, stream, "k_canon_decompress");
-  dim3 g(grid_for(n)), b(TPB);
   const int unc = pk_len == 65;
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_decompress<canon::SecpParams>), g, b, 0, L.s, d_in, unc, (u32*)d_xy, d_st, n);
-  else hipLaunchKernelGGL((k_canon_decompress<canon::P256Params>), g, b, 0, L.s, d_in, unc, (u32*)d_xy, d_st, n);
+  with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_decompress<typename decltype(t)::P>), dim3(grid_for(n)), dim3(TPB), 0, L.s, d_in, unc, (u32*)d_xy, d_st, n);
+  });
   return L.done();
 }
 
@@ -348,31 +388,21 @@ int launch_secret_comb(fec_ctx* ctx, int curve, const u32* scalars, u32* xy, con
   if (rc != FEC_OK) return rc;
   dim3 g(grid_for(cnt)), b(TPB);
   const u32* tab = ctx->d_canon_comb[curve];
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_mul_base_secret<canon::SecpParams>), g, b, 0, s, scalars, tab, xy, c.z, c.pst, c.refused, c.flag, cnt);
-  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_mul_base_secret<canon::P256Params>), g, b, 0, s, scalars, tab, xy, c.z, c.pst, c.refused, c.flag, cnt);
-  else hipLaunchKernelGGL(k_ced_mul_base_secret, g, b, 0, s, scalars, tab, xy, c.z, c.pst, c.refused, cnt);
-  const size_t lanes = (cnt + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
-  const size_t stride = (lanes + 63) / 64 * 64;
-  dim3 gn(grid_for(stride));
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_normalize<csecp>), gn, b, 0, s, xy, c.z, c.pst, cnt, stride);
-  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_normalize<cp256>), gn, b, 0, s, xy, c.z, c.pst, cnt, stride);
-  else hipLaunchKernelGGL((k_canon_normalize<ced>), gn, b, 0, s, xy, c.z, c.pst, cnt, stride);
-  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+  if (curve == FEC_ED25519) hipLaunchKernelGGL(k_ced_mul_base_secret, g, b, 0, s, scalars, tab, xy, c.z, c.pst, c.refused, cnt);
+  else with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_mul_base_secret<typename decltype(t)::P>), g, b, 0, s, scalars, tab, xy, c.z, c.pst, c.refused, c.flag, cnt);
+  });
+  return launch_canon_normalize(curve, xy, c.z, c.pst, cnt, s);
 }
 int launch_secret_report(fec_ctx* ctx, int curve, const CombArea& c, hipStream_t s) {
   if (curve == FEC_ED25519 || !ctx->d_err) return FEC_OK;
   hipLaunchKernelGGL(k_canon_secret_report, dim3(1), dim3(1), 0, s, c.flag, ctx->d_err);
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
-inline hipStream_t sign_stream(fec_ctx* ctx, void* stream) {
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);
-  return s;
-}
 
 int launch_canon_mul_base_secret(fec_ctx* ctx, int curve, const u64* dk, u64* dxy, unsigned char* dst, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  hipStream_t s = sign_stream(ctx, stream);
+  hipStream_t s = ordered_stream(ctx, stream);
   SignArea a;
   int rc = a.open(ctx, s, comb_area_bytes(n));
   if (rc != FEC_OK) return rc;
@@ -398,7 +428,7 @@ int launch_canon_public_key(fec_ctx* ctx, int scheme, const uint8_t* dkeys, uint
                             size_t n, void* stream) {
   if (n == 0) return FEC_OK;
   const int curve = scheme_curve(scheme);
-  hipStream_t s = sign_stream(ctx, stream);
+  hipStream_t s = ordered_stream(ctx, stream);
   SignArea a;
   int rc = a.open(ctx, s, r256(n * 32) + r256(n * 64) + comb_area_bytes(n));
   if (rc != FEC_OK) return rc;
@@ -408,9 +438,10 @@ int launch_canon_public_key(fec_ctx* ctx, int scheme, const uint8_t* dkeys, uint
   c.take(a, n);
   if (hipMemsetAsync(c.flag, 0, 4, s) != hipSuccess) return FEC_E_DEVICE;
   dim3 g(grid_for(n)), b(TPB);
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_key_limbs<canon::NSecp>), g, b, 0, s, (const u32*)dkeys, ds, dst, n);
-  else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_key_limbs<canon::NP256>), g, b, 0, s, (const u32*)dkeys, ds, dst, n);
-  else hipLaunchKernelGGL(k_ced_sign_expand, g, b, 0, s, Messages{nullptr, nullptr, 0}, (const u32*)dkeys, ds, (u32*)nullptr, dst, n);
+  if (curve == FEC_ED25519) hipLaunchKernelGGL(k_ced_sign_expand, g, b, 0, s, Messages{nullptr, nullptr, 0}, (const u32*)dkeys, ds, (u32*)nullptr, dst, n);
+  else with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_key_limbs<typename decltype(t)::N>), g, b, 0, s, (const u32*)dkeys, ds, dst, n);
+  });
   rc = launch_secret_comb(ctx, curve, ds, xy, c, n, s);
   if (rc != FEC_OK) return rc;
   const u32* cxy = xy;
@@ -429,7 +460,7 @@ int launch_canon_ecdsa_sign(fec_ctx* ctx, int curve, const Messages& m, const ui
                             unsigned flags, uint8_t* d_sigs, uint8_t* d_k_be, unsigned char* dst, size_t n, void* stream,
                             uint8_t* d_recids = nullptr) {
   if (n == 0) return FEC_OK;
-  hipStream_t s = sign_stream(ctx, stream);
+  hipStream_t s = ordered_stream(ctx, stream);
   SignArea a;
   int rc = a.open(ctx, s, 3 * r256(n * 32) + r256(n * 64) + comb_area_bytes(n));
   if (rc != FEC_OK) return rc;
@@ -438,25 +469,22 @@ int launch_canon_ecdsa_sign(fec_ctx* ctx, int curve, const Messages& m, const ui
   c.take(a, n);
   if (hipMemsetAsync(c.flag, 0, 4, s) != hipSuccess) return FEC_E_DEVICE;
   dim3 g(grid_for(n)), b(TPB);
-  if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL((k_canon_ecdsa_nonce<canon::NSecp>), g, b, 0, s, m, (const u32*)d_digests, (const u32*)d_keys, ks, zs, ds, (u32*)d_k_be, dst, n);
-  else
-    hipLaunchKernelGGL((k_canon_ecdsa_nonce<canon::NP256>), g, b, 0, s, m, (const u32*)d_digests, (const u32*)d_keys, ks, zs, ds, (u32*)d_k_be, dst, n);
+  with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_ecdsa_nonce<typename decltype(t)::N>), g, b, 0, s, m, (const u32*)d_digests, (const u32*)d_keys, ks, zs, ds, (u32*)d_k_be, dst, n);
+  });
   if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
   if (d_k_be) return FEC_OK;
   rc = launch_secret_comb(ctx, curve, ks, xy, c, n, s);
   if (rc != FEC_OK) return rc;
-  const size_t lanes = (n + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
-  const size_t stride = (lanes + 63) / 64 * 64;
+  const size_t stride = norm_stride(n);
   dim3 gs(grid_for(stride));
-  if (d_recids && curve == FEC_SECP256K1)   // with the recovery ids: the same pass, a kernel of its own
-    hipLaunchKernelGGL((k_canon_ecdsa_sign_finish_rec<canon::NSecp>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, d_recids, dst, n, stride);
-  else if (d_recids)
-    hipLaunchKernelGGL((k_canon_ecdsa_sign_finish_rec<canon::NP256>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, d_recids, dst, n, stride);
-  else if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL((k_canon_ecdsa_sign_finish<canon::NSecp>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, dst, n, stride);
-  else
-    hipLaunchKernelGGL((k_canon_ecdsa_sign_finish<canon::NP256>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, dst, n, stride);
+  with_weierstrass(curve, [&](auto t) {
+    using N = typename decltype(t)::N;
+    if (d_recids)   // with the recovery ids: the same pass, a kernel of its own
+      hipLaunchKernelGGL((k_canon_ecdsa_sign_finish_rec<N>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, d_recids, dst, n, stride);
+    else
+      hipLaunchKernelGGL((k_canon_ecdsa_sign_finish<N>), gs, b, 0, s, (const u32*)ks, (const u32*)zs, (const u32*)ds, (const u32*)xy, flags, (u32*)d_sigs, dst, n, stride);
+  });
   if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
   return launch_secret_report(ctx, curve, c, s);
 }
@@ -465,7 +493,7 @@ int launch_canon_ecdsa_sign(fec_ctx* ctx, int curve, const Messages& m, const ui
 int launch_canon_bip340_sign(fec_ctx* ctx, const Messages& m, const uint8_t* d_keys, const uint8_t* d_aux, uint8_t* d_sigs,
                              unsigned char* dst, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  hipStream_t s = sign_stream(ctx, stream);
+  hipStream_t s = ordered_stream(ctx, stream);
   SignArea a;
   int rc = a.open(ctx, s, 2 * r256(n * 32) + 2 * r256(n * 64) + comb_area_bytes(n));
   if (rc != FEC_OK) return rc;
@@ -489,7 +517,7 @@ int launch_canon_bip340_sign(fec_ctx* ctx, const Messages& m, const uint8_t* d_k
 int launch_canon_ed25519_sign(fec_ctx* ctx, const Messages& m, const uint8_t* d_seeds, uint8_t* d_sigs, uint8_t* d_pks,
                               unsigned char* dst, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  hipStream_t s = sign_stream(ctx, stream);
+  hipStream_t s = ordered_stream(ctx, stream);
   SignArea a;
   int rc = a.open(ctx, s, r256(2 * n * 32) + r256(2 * n * 64) + comb_area_bytes(2 * n));
   if (rc != FEC_OK) return rc;
@@ -509,7 +537,7 @@ int launch_canon_ed25519_sign(fec_ctx* ctx, const Messages& m, const uint8_t* d_
 int launch_canon_x25519(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_us, uint8_t* d_out, unsigned char* dst,
                         size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  hipStream_t s = sign_stream(ctx, stream);
+  hipStream_t s = ordered_stream(ctx, stream);
   hipLaunchKernelGGL(k_canon_x25519, dim3(grid_for(n)), dim3(TPB), 0, s, (const u32*)d_scalars, (const u32*)d_us, (u32*)d_out, dst, n);
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
@@ -517,7 +545,7 @@ int launch_canon_x25519(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d
 // one work area, cleared behind the last kernel on every way out.
 int launch_canon_x25519_base(fec_ctx* ctx, const uint8_t* d_scalars, uint8_t* d_out, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  hipStream_t s = sign_stream(ctx, stream);
+  hipStream_t s = ordered_stream(ctx, stream);
   int rc = ensure_canon_comb(ctx, FEC_ED25519, s);
   if (rc != FEC_OK) return rc;
   SignArea a;
@@ -540,39 +568,29 @@ int launch_canon_keccak256(fec_ctx* ctx, const Messages& m, uint8_t* d_out, unsi
   hipLaunchKernelGGL(k_canon_keccak256, dim3(grid_for(n)), dim3(TPB), 0, L.s, m, (u32*)d_out, dst, n);
   return L.done();
 }
-// Recovery: prepare -> u1*G + u2*R -> finish, the verifier's pipeline with another first and last kernel.  Work area in
-// d_verify, laid out as launch_canon_ecdsa_verify lays out its own with R behind it: u1, u2 (n*32 each), xy (n*64), R (n*64),
-// point status (n), flags (n).
+// Recovery: prepare -> u1*G + u2*R -> finish, the verifier's pipeline with another first and last kernel, in the verifier's
+// work area with R behind it (verify_work).
 inline bool recover_len_ok(int curve, size_t out_len) {
   return out_len == 33 || out_len == 65 || out_len == 64 || (out_len == 20 && curve == FEC_SECP256K1);
 }
 int launch_canon_ecdsa_recover(fec_ctx* ctx, int curve, const uint8_t* d_digests, const uint8_t* d_sigs, const uint8_t* d_recids,
                                uint8_t* d_out, size_t out_len, unsigned char* dst, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, n * (32 + 32 + 64 + 64 + 1 + 1) + 64);
+  VerifyWork w;
+  int rc = verify_work(ctx, n, EcdsaForm::kRecover, w);
   if (rc != FEC_OK) return rc;
-  char* base = (char*)ctx->d_verify;
-  u64 *u1 = (u64*)base, *u2 = (u64*)(base + n * 32), *xy = (u64*)(base + n * 64), *rxy = (u64*)(base + n * 128);
-  unsigned char* pst = (unsigned char*)(base + n * 192);
-  unsigned char* ok = pst + n;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // the work area is the ctx's
+  hipStream_t s = ordered_stream(ctx, stream);
   dim3 g(grid_for(n)), b(TPB);
-  const size_t lanes = (n + canon::NORM_GROUP - 1) / canon::NORM_GROUP;
-  const size_t stride = (lanes + 63) / 64 * 64;
-  dim3 gs(grid_for(stride));
-  if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL((k_canon_recover_prepare<canon::SecpParams>), gs, b, 0, s, (const u32*)d_digests, (const u32*)d_sigs, d_recids,
-                       (u32*)u1, (u32*)u2, (u32*)rxy, ok, n, stride);
-  else
-    hipLaunchKernelGGL((k_canon_recover_prepare<canon::P256Params>), gs, b, 0, s, (const u32*)d_digests, (const u32*)d_sigs, d_recids,
-                       (u32*)u1, (u32*)u2, (u32*)rxy, ok, n, stride);
+  const size_t stride = norm_stride(n);
+  with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_recover_prepare<typename decltype(t)::P>), dim3(grid_for(stride)), b, 0, s, (const u32*)d_digests,
+                       (const u32*)d_sigs, d_recids, w.u1, w.u2, w.rxy, w.ok, n, stride);
+  });
   if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
-  rc = launch_canon_mul_base(ctx, curve, u1, xy, pst, n, stream, false);
-  if (rc == FEC_OK) rc = launch_canon_mul(ctx, curve, u2, rxy, xy, pst, n, stream, true);
+  rc = launch_canon_double_mul(ctx, curve, (const u64*)w.u1, (const u64*)w.u2, (const u64*)w.rxy, (u64*)w.xy, w.pst, n, s);
   if (rc != FEC_OK) return rc;
-  const u32* cxy = (const u32*)xy;
-  const unsigned char *cok = ok, *cpst = pst;
+  const u32* cxy = w.xy;
+  const unsigned char *cok = w.ok, *cpst = w.pst;
   if (out_len == 20) hipLaunchKernelGGL(k_canon_recover_finish<20>, g, b, 0, s, cxy, cok, cpst, d_out, dst, n);
   else if (out_len == 33) hipLaunchKernelGGL(k_canon_recover_finish<33>, g, b, 0, s, cxy, cok, cpst, d_out, dst, n);
   else if (out_len == 64) hipLaunchKernelGGL(k_canon_recover_finish<64>, g, b, 0, s, cxy, cok, cpst, d_out, dst, n);
@@ -584,39 +602,37 @@ int launch_canon_ecdsa_recover(fec_ctx* ctx, int curve, const uint8_t* d_digests
 // The public side: prepare -> t*G by the comb (finish = false) -> k_canon_add_affine -> normalisation -> finish.  Work area in
 // d_verify: the shared parent's block (256 bytes), t (n*32), xy (n*64), the affine addend (n*64), point status (n), flags (n).
 struct TweakWork {
-  u32* shared;
-  u64 *t, *xy, *q;
+  u32 *shared, *t, *xy, *q;
   unsigned char *pst, *flag;
 };
 int tweak_work(fec_ctx* ctx, size_t n, TweakWork& w) {
-  const int rc = ensure_owned(&ctx->d_verify, &ctx->verify_cap, 256 + n * (32 + 64 + 64 + 1 + 1) + 64);
-  if (rc != FEC_OK) return rc;
-  char* base = (char*)ctx->d_verify;
-  w.shared = (u32*)base;
-  w.t = (u64*)(base + 256);
-  w.xy = (u64*)(base + 256 + n * 32);
-  w.q = (u64*)(base + 256 + n * 96);
-  w.pst = (unsigned char*)(base + 256 + n * 160);
-  w.flag = w.pst + n;
-  return FEC_OK;
+  WorkArea area;
+  area.add(w.shared, 256).add(w.t, n * 32).add(w.xy, n * 64).add(w.q, n * 64).add(w.pst, n).add(w.flag, n);
+  return place_in_verify(ctx, area);
 }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 inline bool tweak_len_ok(int curve, size_t len) { return len == 33 || len == 65 || (len == 32 && curve == FEC_SECP256K1); }
-// Everything after the prepare kernel, which has filled w.t, w.q and w.flag.  ccs: the child chain codes (BIP-32) or null.
+// The sum, behind a kernel that has filled w.t and w.q: w.t * G by the comb (finish = false), + w.q, the normalisation.  w.xy is
+// affine behind it, w.pst says where the sum is at infinity.
+int launch_canon_tweak_sum(fec_ctx* ctx, int curve, const TweakWork& w, size_t n, hipStream_t s) {
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;   // the kernel before
+  const int rc = launch_canon_mul_base(ctx, curve, (const u64*)w.t, (u64*)w.xy, w.pst, n, s, false);
+  if (rc != FEC_OK) return rc;
+  u32* z = reinterpret_cast<u32*>(ctx->d_zbuf);
+  with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_add_affine<typename decltype(t)::C>), dim3(grid_for(n)), dim3(TPB), 0, s, w.xy, z, w.q, w.pst, n);
+  });
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  return launch_canon_normalize(curve, w.xy, z, w.pst, n, s);
+}
+// Everything after the prepare kernel, which has filled w.t, w.q and w.flag: the sum, then its finish kernel.  ccs: the child
+// chain codes (BIP-32) or null.
 int launch_canon_tweak_tail(fec_ctx* ctx, int curve, const TweakWork& w, unsigned char at_infinity, uint8_t* d_out, size_t out_len,
-                            u32* ccs, unsigned char* dst, size_t n, void* stream) {
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;   // the prepare kernel's launch
-  int rc = launch_canon_mul_base(ctx, curve, w.t, w.xy, w.pst, n, stream, false);
+                            u32* ccs, unsigned char* dst, size_t n, hipStream_t s) {
+  const int rc = launch_canon_tweak_sum(ctx, curve, w, n, s);
   if (rc != FEC_OK) return rc;
   dim3 g(grid_for(n)), b(TPB);
-  u32* z = reinterpret_cast<u32*>(ctx->d_zbuf);
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_add_affine<csecp>), g, b, 0, s, (u32*)w.xy, z, (const u32*)w.q, w.pst, n);
-  else hipLaunchKernelGGL((k_canon_add_affine<cp256>), g, b, 0, s, (u32*)w.xy, z, (const u32*)w.q, w.pst, n);
-  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
-  rc = launch_canon_normalize(ctx, curve, w.xy, w.pst, n, s);
-  if (rc != FEC_OK) return rc;
-  const u32* cxy = (const u32*)w.xy;
+  const u32* cxy = w.xy;
   const unsigned char *cflag = w.flag, *cpst = w.pst;
   if (out_len == 32) hipLaunchKernelGGL(k_canon_tweak_finish<32>, g, b, 0, s, cxy, cflag, cpst, at_infinity, d_out, ccs, dst, n);
   else if (out_len == 33) hipLaunchKernelGGL(k_canon_tweak_finish<33>, g, b, 0, s, cxy, cflag, cpst, at_infinity, d_out, ccs, dst, n);
@@ -629,43 +645,48 @@ int launch_canon_pubkey_tweak_add(fec_ctx* ctx, int curve, const uint8_t* d_pks,
   TweakWork w;
   const int rc = tweak_work(ctx, n, w);
   if (rc != FEC_OK) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // the work area is the ctx's
-  dim3 g(grid_for(n)), b(TPB);
-  if (curve == FEC_SECP256K1)
-    hipLaunchKernelGGL((k_canon_tweak_prepare<canon::SecpParams>), g, b, 0, s, d_pks, (int)pk_len, (const u32*)d_tweaks, (u32*)w.t, (u32*)w.q, w.flag, n);
-  else
-    hipLaunchKernelGGL((k_canon_tweak_prepare<canon::P256Params>), g, b, 0, s, d_pks, (int)pk_len, (const u32*)d_tweaks, (u32*)w.t, (u32*)w.q, w.flag, n);
-  return launch_canon_tweak_tail(ctx, curve, w, canon::TWK_NO_KEY, d_out, out_len, nullptr, dst, n, stream);
+  hipStream_t s = ordered_stream(ctx, stream);
+  with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_tweak_prepare<typename decltype(t)::P>), dim3(grid_for(n)), dim3(TPB), 0, s, d_pks, (int)pk_len,
+                       (const u32*)d_tweaks, w.t, w.q, w.flag, n);
+  });
+  return launch_canon_tweak_tail(ctx, curve, w, canon::TWK_NO_KEY, d_out, out_len, nullptr, dst, n, s);
 }
-// CKDpub (secp256k1).  shared: one parent and one chain code for the whole batch.
-int launch_canon_bip32_derive_pub(fec_ctx* ctx, const uint8_t* d_pks, const uint8_t* d_ccs, bool shared, const uint32_t* d_idx,
-                                  uint8_t* d_out_pks, uint8_t* d_out_ccs, unsigned char* dst, size_t n, void* stream) {
-  if (n == 0) return FEC_OK;
+// The first level of CKDpub (secp256k1): IL into w.t, the parent into w.q, the child chain codes, the flags.  shared: one
+// parent and one chain code for the whole batch, decoded once into w.shared.  (launch_canon_tweak_sum, which follows, reads
+// the launch status.)
+void launch_canon_bip32_pub_prepare(const TweakWork& w, const uint8_t* d_pks, const uint8_t* d_ccs, bool shared, const u32* d_idx,
+                                    uint8_t* d_out_ccs, size_t n, hipStream_t s) {
   using P = canon::SecpParams;
-  TweakWork w;
-  const int rc = tweak_work(ctx, n, w);
-  if (rc != FEC_OK) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // the work area is the ctx's
   dim3 g(grid_for(n)), b(TPB);
   if (shared) {
     hipLaunchKernelGGL((k_canon_bip32_parent<P>), dim3(1), dim3(64), 0, s, d_pks, (const u32*)d_ccs, w.shared);
-    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, true>), g, b, 0, s, d_pks, (const u32*)d_ccs, (const u32*)w.shared, d_idx, (u32*)w.t,
-                       (u32*)w.q, (u32*)d_out_ccs, w.flag, n);
+    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, true>), g, b, 0, s, d_pks, (const u32*)d_ccs, w.shared, d_idx, w.t, w.q,
+                       (u32*)d_out_ccs, w.flag, n);
   } else {
-    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, false>), g, b, 0, s, d_pks, (const u32*)d_ccs, (const u32*)w.shared, d_idx, (u32*)w.t,
-                       (u32*)w.q, (u32*)d_out_ccs, w.flag, n);
+    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, false>), g, b, 0, s, d_pks, (const u32*)d_ccs, w.shared, d_idx, w.t, w.q,
+                       (u32*)d_out_ccs, w.flag, n);
   }
-  return launch_canon_tweak_tail(ctx, FEC_SECP256K1, w, canon::BIP32_INVALID, d_out_pks, 33, (u32*)d_out_ccs, dst, n, stream);
+}
+// CKDpub (secp256k1)
+int launch_canon_bip32_derive_pub(fec_ctx* ctx, const uint8_t* d_pks, const uint8_t* d_ccs, bool shared, const uint32_t* d_idx,
+                                  uint8_t* d_out_pks, uint8_t* d_out_ccs, unsigned char* dst, size_t n, void* stream) {
+  if (n == 0) return FEC_OK;
+  TweakWork w;
+  const int rc = tweak_work(ctx, n, w);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = ordered_stream(ctx, stream);
+  launch_canon_bip32_pub_prepare(w, d_pks, d_ccs, shared, d_idx, d_out_ccs, n, s);
+  return launch_canon_tweak_tail(ctx, FEC_SECP256K1, w, canon::BIP32_INVALID, d_out_pks, 33, (u32*)d_out_ccs, dst, n, s);
 }
 int launch_canon_seckey_tweak_add(fec_ctx* ctx, int curve, const uint8_t* d_keys, const uint8_t* d_tweaks, uint8_t* d_out,
                                   unsigned char* dst, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  hipStream_t s = sign_stream(ctx, stream);
-  dim3 g(grid_for(n)), b(TPB);
-  if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_seckey_tweak_add<canon::NSecp>), g, b, 0, s, (const u32*)d_keys, (const u32*)d_tweaks, (u32*)d_out, dst, n);
-  else hipLaunchKernelGGL((k_canon_seckey_tweak_add<canon::NP256>), g, b, 0, s, (const u32*)d_keys, (const u32*)d_tweaks, (u32*)d_out, dst, n);
+  hipStream_t s = ordered_stream(ctx, stream);
+  with_weierstrass(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_seckey_tweak_add<typename decltype(t)::N>), dim3(grid_for(n)), dim3(TPB), 0, s, (const u32*)d_keys,
+                       (const u32*)d_tweaks, (u32*)d_out, dst, n);
+  });
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 // CKDpriv (secp256k1): key limbs -> the secret comb over the n_par parents (skipped under FEC_CANON_BIP32_NO_COMB) -> the
@@ -674,7 +695,7 @@ int launch_canon_bip32_derive_priv(fec_ctx* ctx, const uint8_t* d_keys, const ui
                                    unsigned flags, uint8_t* d_out_keys, uint8_t* d_out_ccs, unsigned char* dst, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
   const bool comb = (flags & FEC_CANON_BIP32_NO_COMB) == 0;
-  hipStream_t s = sign_stream(ctx, stream);
+  hipStream_t s = ordered_stream(ctx, stream);
   SignArea a;
   int rc = a.open(ctx, s, r256(n_par * 32) + r256(n_par * 64) + r256(n_par) + comb_area_bytes(n_par));
   if (rc != FEC_OK) return rc;
@@ -715,35 +736,19 @@ int launch_canon_pubkey_hash160(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_le
   hipLaunchKernelGGL(k_canon_pubkey_hash160, dim3(grid_for(n)), dim3(TPB), 0, L.s, d_pks, pk_len, (u32*)d_out, n);
   return L.done();
 }
-// The middle of launch_canon_tweak_tail on secp256k1, for the callers that end with a kernel of their own: w.t * G by the comb
-// (finish = false), + w.q, the normalisation.  w.xy is affine behind it, w.pst says where the sum is at infinity.
-int wallet_sum(fec_ctx* ctx, const TweakWork& w, size_t n, void* stream) {
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // (the caller has: this keeps the function ordered when read alone)
-  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;   // the kernel before
-  int rc = launch_canon_mul_base(ctx, FEC_SECP256K1, w.t, w.xy, w.pst, n, stream, false);
-  if (rc != FEC_OK) return rc;
-  hipLaunchKernelGGL((k_canon_add_affine<csecp>), dim3(grid_for(n)), dim3(TPB), 0, s, (u32*)w.xy, reinterpret_cast<u32*>(ctx->d_zbuf),
-                     (const u32*)w.q, w.pst, n);
-  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
-  return launch_canon_normalize(ctx, FEC_SECP256K1, w.xy, w.pst, n, s);
-}
-// Taproot: prepare -> the tweak-add's middle -> finish.  d_roots: null = no script tree (BIP-86).
+// Taproot: prepare -> the tweak-add's sum -> finish.  d_roots: null = no script tree (BIP-86).
 int launch_canon_taproot_output_key(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_len, const uint8_t* d_roots, uint8_t* d_out,
                                     uint8_t* d_parity, unsigned char* dst, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
   TweakWork w;
   int rc = tweak_work(ctx, n, w);
   if (rc != FEC_OK) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // the work area is the ctx's
+  hipStream_t s = ordered_stream(ctx, stream);
   dim3 g(grid_for(n)), b(TPB);
-  hipLaunchKernelGGL((k_canon_taproot_prepare<canon::SecpParams>), g, b, 0, s, d_pks, (int)pk_len, (const u32*)d_roots, (u32*)w.t, (u32*)w.q,
-                     w.flag, n);
-  rc = wallet_sum(ctx, w, n, stream);
+  hipLaunchKernelGGL((k_canon_taproot_prepare<canon::SecpParams>), g, b, 0, s, d_pks, (int)pk_len, (const u32*)d_roots, w.t, w.q, w.flag, n);
+  rc = launch_canon_tweak_sum(ctx, FEC_SECP256K1, w, n, s);
   if (rc != FEC_OK) return rc;
-  hipLaunchKernelGGL(k_canon_taproot_finish, g, b, 0, s, (const u32*)w.xy, (const unsigned char*)w.flag, (const unsigned char*)w.pst, d_out,
-                     d_parity, dst, n);
+  hipLaunchKernelGGL(k_canon_taproot_finish, g, b, 0, s, w.xy, w.flag, w.pst, d_out, d_parity, dst, n);
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 // CKDpub along `depth` levels: the first level is launch_canon_bip32_derive_pub's prepare (its index column gathered into
@@ -753,36 +758,26 @@ int launch_canon_bip32_derive_pub_path(fec_ctx* ctx, const uint8_t* d_pks, const
                                        size_t depth, uint8_t* d_out_pks, uint8_t* d_out_ccs, uint8_t* d_fp, uint8_t* d_h160,
                                        unsigned char* dst, size_t n, void* stream) {
   if (n == 0) return FEC_OK;
-  using P = canon::SecpParams;
   TweakWork w;
   int rc = tweak_work(ctx, n, w);
   if (rc != FEC_OK) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  order_after_previous(ctx, s);   // the work area is the ctx's
+  hipStream_t s = ordered_stream(ctx, stream);
   dim3 g(grid_for(n)), b(TPB);
   const u32* idx0 = d_idx;
   if (depth > 1) {
-    hipLaunchKernelGGL(k_canon_path_indices, g, b, 0, s, (const u32*)d_idx, depth, (size_t)0, (u32*)w.xy, n);
-    idx0 = (const u32*)w.xy;
+    hipLaunchKernelGGL(k_canon_path_indices, g, b, 0, s, (const u32*)d_idx, depth, (size_t)0, w.xy, n);
+    idx0 = w.xy;
   }
-  if (shared) {
-    hipLaunchKernelGGL((k_canon_bip32_parent<P>), dim3(1), dim3(64), 0, s, d_pks, (const u32*)d_ccs, w.shared);
-    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, true>), g, b, 0, s, d_pks, (const u32*)d_ccs, (const u32*)w.shared, idx0, (u32*)w.t,
-                       (u32*)w.q, (u32*)d_out_ccs, w.flag, n);
-  } else {
-    hipLaunchKernelGGL((k_canon_bip32_pub_prepare<P, false>), g, b, 0, s, d_pks, (const u32*)d_ccs, (const u32*)w.shared, idx0, (u32*)w.t,
-                       (u32*)w.q, (u32*)d_out_ccs, w.flag, n);
-  }
-  if (d_fp && depth == 1) hipLaunchKernelGGL(k_canon_path_fingerprint, g, b, 0, s, (const u32*)w.q, (u32*)d_fp, n);
+  launch_canon_bip32_pub_prepare(w, d_pks, d_ccs, shared, idx0, d_out_ccs, n, s);
+  if (d_fp && depth == 1) hipLaunchKernelGGL(k_canon_path_fingerprint, g, b, 0, s, w.q, (u32*)d_fp, n);
   for (size_t level = 1;; ++level) {
-    rc = wallet_sum(ctx, w, n, stream);
+    rc = launch_canon_tweak_sum(ctx, FEC_SECP256K1, w, n, s);
     if (rc != FEC_OK) return rc;
     if (level == depth) break;
-    hipLaunchKernelGGL((k_canon_bip32_path_step<P>), g, b, 0, s, (const u32*)w.xy, (const unsigned char*)w.pst, (const u32*)d_idx, depth, level,
-                       (u32*)w.t, (u32*)w.q, (u32*)d_out_ccs, w.flag, level + 1 == depth ? (u32*)d_fp : nullptr, n);
+    hipLaunchKernelGGL((k_canon_bip32_path_step<canon::SecpParams>), g, b, 0, s, w.xy, w.pst, (const u32*)d_idx, depth, level, w.t, w.q,
+                       (u32*)d_out_ccs, w.flag, level + 1 == depth ? (u32*)d_fp : nullptr, n);
   }
-  hipLaunchKernelGGL(k_canon_bip32_path_finish, g, b, 0, s, (const u32*)w.xy, (const unsigned char*)w.flag, (const unsigned char*)w.pst, d_out_pks,
-                     (u32*)d_out_ccs, (u32*)d_fp, (u32*)d_h160, dst, n);
+  hipLaunchKernelGGL(k_canon_bip32_path_finish, g, b, 0, s, w.xy, w.flag, w.pst, d_out_pks, (u32*)d_out_ccs, (u32*)d_fp, (u32*)d_h160, dst, n);
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 
@@ -795,7 +790,7 @@ int fec_canon_mul_base_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scal
                            uint8_t* d_status, size_t n, void* stream) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!d_scalars || !d_out_xy || !d_status))) return FEC_E_ARG;
-  if (!canon_curve_ok(curve)) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
   if (!aligned16(d_scalars) || !aligned16(d_out_xy)) return FEC_E_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
   return launch_canon_mul_base(ctx, curve, d_scalars, d_out_xy, d_status, n, stream);
@@ -805,7 +800,7 @@ int fec_canon_mul_base(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, u
                        size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!scalars || !out_xy || !status))) return FEC_E_ARG;
-  if (!canon_curve_ok(curve)) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
   const HostArray a[] = {input(scalars, 32), output(out_xy, 64), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_canon_mul_base(c, curve, (const u64*)d[0], (u64*)d[1], (unsigned char*)d[2], m, s);
@@ -816,7 +811,7 @@ int fec_canon_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, 
                       uint64_t* d_out_xy, uint8_t* d_status, size_t n, void* stream) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!d_scalars || !d_points_xy || !d_out_xy || !d_status))) return FEC_E_ARG;
-  if (!canon_curve_ok(curve)) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
   if (!aligned16(d_scalars) || !aligned16(d_points_xy) || !aligned16(d_out_xy)) return FEC_E_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
   return launch_canon_mul(ctx, curve, d_scalars, d_points_xy, d_out_xy, d_status, n, stream);
@@ -826,7 +821,7 @@ int fec_canon_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const 
                   uint64_t* out_xy, uint8_t* status, size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!scalars || !points_xy || !out_xy || !status))) return FEC_E_ARG;
-  if (!canon_curve_ok(curve)) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
   const HostArray a[] = {input(scalars, 32), input(points_xy, 64), output(out_xy, 64), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_canon_mul(c, curve, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], (unsigned char*)d[3], m, s);
@@ -838,24 +833,20 @@ int fec_canon_double_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_u1
                              void* stream) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!d_u1 || !d_u2 || !d_points_xy || !d_out_xy || !d_status))) return FEC_E_ARG;
-  if (!canon_curve_ok(curve)) return FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
   if (!aligned16(d_u1) || !aligned16(d_u2) || !aligned16(d_points_xy) || !aligned16(d_out_xy)) return FEC_E_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  int rc = launch_canon_mul_base(ctx, curve, d_u1, d_out_xy, d_status, n, stream, false);
-  if (rc != FEC_OK) return rc;
-  return launch_canon_mul(ctx, curve, d_u2, d_points_xy, d_out_xy, d_status, n, stream, true);
+  return launch_canon_double_mul(ctx, curve, d_u1, d_u2, d_points_xy, d_out_xy, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_double_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* u1, const uint64_t* u2,
                          const uint64_t* points_xy, uint64_t* out_xy, uint8_t* status, size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!u1 || !u2 || !points_xy || !out_xy || !status))) return FEC_E_ARG;
-  if (!canon_curve_ok(curve)) return FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
   const HostArray a[] = {input(u1, 32), input(u2, 32), input(points_xy, 64), output(out_xy, 64), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    int rc = launch_canon_mul_base(c, curve, (const u64*)d[0], (u64*)d[3], (unsigned char*)d[4], m, s, false);
-    if (rc != FEC_OK) return rc;
-    return launch_canon_mul(c, curve, (const u64*)d[1], (const u64*)d[2], (u64*)d[3], (unsigned char*)d[4], m, s, true);
+    return launch_canon_double_mul(c, curve, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (u64*)d[3], (unsigned char*)d[4], m, s);
   });
 } FEC_ABI_CATCH_STATUS
 
@@ -864,7 +855,7 @@ int fec_canon_ecdsa_verify_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_
                                void* stream) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!d_z || !d_r || !d_s || !d_pk_xy || !d_result))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (!aligned16(d_z) || !aligned16(d_r) || !aligned16(d_s) || !aligned16(d_pk_xy)) return FEC_E_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
   return launch_canon_ecdsa_verify(ctx, curve, d_z, d_r, d_s, d_pk_xy, d_result, n, stream);
@@ -874,7 +865,7 @@ int fec_canon_ecdsa_verify(fec_ctx* ctx, fec_curve curve, const uint64_t* z, con
                            const uint64_t* pk_xy, uint8_t* result, size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || (n && (!z || !r || !s || !pk_xy || !result))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   const HostArray a[] = {input(z, 32), input(r, 32), input(s, 32), input(pk_xy, 64), output(result, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
     return launch_canon_ecdsa_verify(c, curve, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
@@ -925,16 +916,16 @@ int fec_canon_eddsa_verify(fec_ctx* ctx, const uint64_t* a_enc, const uint64_t* 
 int fec_canon_scalar_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a, const uint64_t* b,
                         const uint64_t* c, uint64_t* out, size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || !canon_curve_ok(curve) || op < 0 || op > 1 || (n && (!a || !out))) return FEC_E_ARG;
+  if (!ctx || !curve_ok(curve) || op < 0 || op > 1 || (n && (!a || !out))) return FEC_E_ARG;
   if (op == 0 && n && (!b || !c)) return FEC_E_ARG;
   const HostArray arr[] = {input(a, 32), input(op == 0 ? b : nullptr, 32), input(op == 0 ? c : nullptr, 32), output(out, 32)};
   return host_call(ctx, n, arr, 1, [&](fec_ctx* cx, void* const* d, size_t, size_t m, hipStream_t s) {
     Launch L(cx, s, "k_canon_scalar_op");
     dim3 g(grid_for(m)), blk(TPB);
     const u32 *x = (const u32*)d[0], *y = (const u32*)d[1], *z = (const u32*)d[2];
-    if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_scalar_op<canon::NSecp>), g, blk, 0, L.s, op, x, y, z, (u32*)d[3], m);
-    else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_scalar_op<canon::NP256>), g, blk, 0, L.s, op, x, y, z, (u32*)d[3], m);
-    else hipLaunchKernelGGL((k_canon_scalar_op<canon::NEd>), g, blk, 0, L.s, op, x, y, z, (u32*)d[3], m);
+    with_curve(curve, [&](auto t) {
+      hipLaunchKernelGGL((k_canon_scalar_op<typename decltype(t)::N>), g, blk, 0, L.s, op, x, y, z, (u32*)d[3], m);
+    });
     return L.done();
   });
 } FEC_ABI_CATCH_STATUS
@@ -943,7 +934,7 @@ int fec_canon_field_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a,
                        size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
   if (!ctx || op < FEC_F_ADD || op > FEC_F_INV || (n && (!a || !out))) return FEC_E_ARG;
-  if (!canon_curve_ok(curve)) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
   const bool binary = op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL;
   if (binary && n && !b) return FEC_E_ARG;
   const HostArray arr[] = {input(a, 32), input(binary ? b : nullptr, 32), output(out, 32)};
@@ -951,9 +942,9 @@ int fec_canon_field_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a,
     const size_t n = m;
     void *x = d[0], *y = d[1], *o = d[2];
     Launch L(c, s, "k_canon_field_op");
-    if (curve == FEC_SECP256K1) hipLaunchKernelGGL((k_canon_field_op<csecp>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);
-    else if (curve == FEC_P256) hipLaunchKernelGGL((k_canon_field_op<cp256>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);
-    else hipLaunchKernelGGL((k_canon_field_op<ced>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);
+    with_curve(curve, [&](auto t) {
+      hipLaunchKernelGGL((k_canon_field_op<typename decltype(t)::C>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);
+    });
     return L.done();
   });
 } FEC_ABI_CATCH_STATUS
@@ -967,7 +958,7 @@ int fec_canon_ecdsa_verify_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t*
   if (const int rc = dev_enter(ctx)) return rc;
   Messages m;
   if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_sigs || !d_pks || !d_result))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if ((pk_len != 33 && pk_len != 65) || !aligned16(d_sigs) || !aligned16(d_pks)) return FEC_E_ARG;
   return launch_canon_ecdsa_verify_msg(ctx, curve, m, d_sigs, d_pks, pk_len, d_result, n, stream);
 } FEC_ABI_CATCH_STATUS
@@ -975,7 +966,7 @@ int fec_canon_ecdsa_verify_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t*
 int fec_canon_ecdsa_verify_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                                const uint8_t* sigs, const uint8_t* pks, size_t pk_len, uint8_t* result, size_t n) try {
   if (!ctx || (n && (!sigs || !pks || !result))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (pk_len != 33 && pk_len != 65) return FEC_E_ARG;
   const HostArray a[] = {ragged(msg_off, 8), input(sigs, 64), input(pks, pk_len), output(result, 1)};
   return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
@@ -1025,7 +1016,7 @@ int fec_canon_decompress_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_in,
                              uint8_t* d_status, size_t n, void* stream) try {
   if (const int rc = dev_enter(ctx)) return rc;
   if (n && (!d_in || !d_xy || !d_status)) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if ((pk_len != 33 && pk_len != 65) || !aligned16(d_in) || !aligned16(d_xy)) return FEC_E_ARG;
   return launch_canon_decompress(ctx, curve, d_in, pk_len, d_xy, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
@@ -1033,7 +1024,7 @@ int fec_canon_decompress_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_in,
 int fec_canon_decompress(fec_ctx* ctx, fec_curve curve, const uint8_t* in, size_t pk_len, uint64_t* xy, uint8_t* status,
                          size_t n) try {
   if (!ctx || (n && (!in || !xy || !status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (pk_len != 33 && pk_len != 65) return FEC_E_ARG;
   const HostArray a[] = {input(in, pk_len), output(xy, 64), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
@@ -1046,7 +1037,7 @@ int fec_canon_mul_base_secret_dev(fec_ctx* ctx, fec_curve curve, const uint64_t*
                                   uint8_t* d_status, size_t n, void* stream) try {
   if (const int rc = dev_enter(ctx)) return rc;
   if (n && (!d_scalars || !d_out_xy || !d_status)) return FEC_E_ARG;
-  if (!canon_curve_ok(curve)) return FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
   if (!aligned16(d_scalars) || !aligned16(d_out_xy)) return FEC_E_ARG;
   return launch_canon_mul_base_secret(ctx, curve, d_scalars, d_out_xy, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
@@ -1054,7 +1045,7 @@ int fec_canon_mul_base_secret_dev(fec_ctx* ctx, fec_curve curve, const uint64_t*
 int fec_canon_mul_base_secret(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, uint64_t* out_xy, uint8_t* status,
                               size_t n) try {
   if (!ctx || (n && (!scalars || !out_xy || !status))) return FEC_E_ARG;
-  if (!canon_curve_ok(curve)) return FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
   const HostArray a[] = {secret_input(scalars, 32), secret_output(out_xy, 64), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_canon_mul_base_secret(c, curve, (const u64*)d[0], (u64*)d[1], (unsigned char*)d[2], m, s);
@@ -1084,7 +1075,7 @@ int fec_canon_ecdsa_sign_digest_dev(fec_ctx* ctx, fec_curve curve, const uint8_t
                                     unsigned flags, uint8_t* d_sigs, uint8_t* d_status, size_t n, void* stream) try {
   if (const int rc = dev_enter(ctx)) return rc;
   if (n && (!d_digests || !d_keys || !d_sigs || !d_status)) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if ((flags & ~1u) || !aligned16(d_digests) || !aligned16(d_keys) || !aligned16(d_sigs)) return FEC_E_ARG;
   return launch_canon_ecdsa_sign(ctx, curve, Messages{nullptr, nullptr, 0}, d_digests, d_keys, flags, d_sigs, nullptr, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
@@ -1092,7 +1083,7 @@ int fec_canon_ecdsa_sign_digest_dev(fec_ctx* ctx, fec_curve curve, const uint8_t
 int fec_canon_ecdsa_sign_digest(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* keys, unsigned flags,
                                 uint8_t* sigs, uint8_t* status, size_t n) try {
   if (!ctx || (n && (!digests || !keys || !sigs || !status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (flags & ~1u) return FEC_E_ARG;
   const HostArray a[] = {secret_input(digests, 32), secret_input(keys, 32), secret_output(sigs, 64), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
@@ -1107,7 +1098,7 @@ int fec_canon_ecdsa_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d
   if (const int rc = dev_enter(ctx)) return rc;
   Messages m;
   if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_keys || !d_sigs || !d_status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if ((flags & ~1u) || !aligned16(d_keys) || !aligned16(d_sigs)) return FEC_E_ARG;
   return launch_canon_ecdsa_sign(ctx, curve, m, nullptr, d_keys, flags, d_sigs, nullptr, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
@@ -1115,7 +1106,7 @@ int fec_canon_ecdsa_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d
 int fec_canon_ecdsa_sign_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                              const uint8_t* keys, unsigned flags, uint8_t* sigs, uint8_t* status, size_t n) try {
   if (!ctx || (n && (!keys || !sigs || !status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (flags & ~1u) return FEC_E_ARG;
   const HostArray a[] = {ragged(msg_off, 8), secret_input(keys, 32), secret_output(sigs, 64), output(status, 1)};
   return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
@@ -1127,7 +1118,7 @@ int fec_canon_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_dige
                             uint8_t* d_status, size_t n, void* stream) try {
   if (const int rc = dev_enter(ctx)) return rc;
   if (n && (!d_digests || !d_keys || !d_k_out || !d_status)) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (!aligned16(d_digests) || !aligned16(d_keys) || !aligned16(d_k_out)) return FEC_E_ARG;
   return launch_canon_ecdsa_sign(ctx, curve, Messages{nullptr, nullptr, 0}, d_digests, d_keys, 0, nullptr, d_k_out, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
@@ -1135,7 +1126,7 @@ int fec_canon_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_dige
 int fec_canon_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* keys, uint8_t* k_out,
                         uint8_t* status, size_t n) try {
   if (!ctx || (n && (!digests || !keys || !k_out || !status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   const HostArray a[] = {secret_input(digests, 32), secret_input(keys, 32), secret_output(k_out, 32), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_canon_ecdsa_sign(c, curve, Messages{nullptr, nullptr, 0}, (const uint8_t*)d[0], (const uint8_t*)d[1], 0, nullptr,
@@ -1236,7 +1227,7 @@ int fec_canon_ecdsa_recover_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_
                                 void* stream) try {
   if (const int rc = dev_enter(ctx)) return rc;
   if (n && (!d_digests || !d_sigs || !d_recids || !d_out || !d_status)) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (!recover_len_ok(curve, out_len) || !aligned16(d_digests) || !aligned16(d_sigs)) return FEC_E_ARG;
   if ((out_len == 64 || out_len == 20) && !aligned16(d_out)) return FEC_E_ARG;
   return launch_canon_ecdsa_recover(ctx, curve, d_digests, d_sigs, d_recids, d_out, out_len, d_status, n, stream);
@@ -1245,7 +1236,7 @@ int fec_canon_ecdsa_recover_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_
 int fec_canon_ecdsa_recover(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* sigs, const uint8_t* recids,
                             uint8_t* out, size_t out_len, uint8_t* status, size_t n) try {
   if (!ctx || (n && (!digests || !sigs || !recids || !out || !status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (!recover_len_ok(curve, out_len)) return FEC_E_ARG;
   const HostArray a[] = {input(digests, 32), input(sigs, 64), input(recids, 1), output(out, out_len), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
@@ -1260,7 +1251,7 @@ int fec_canon_ecdsa_sign_recoverable_digest_dev(fec_ctx* ctx, fec_curve curve, c
                                                 void* stream) try {
   if (const int rc = dev_enter(ctx)) return rc;
   if (n && (!d_digests || !d_keys || !d_sigs || !d_recids || !d_status)) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if ((flags & ~1u) || !aligned16(d_digests) || !aligned16(d_keys) || !aligned16(d_sigs)) return FEC_E_ARG;
   return launch_canon_ecdsa_sign(ctx, curve, Messages{nullptr, nullptr, 0}, d_digests, d_keys, flags, d_sigs, nullptr, d_status, n, stream,
                                  d_recids);
@@ -1269,7 +1260,7 @@ int fec_canon_ecdsa_sign_recoverable_digest_dev(fec_ctx* ctx, fec_curve curve, c
 int fec_canon_ecdsa_sign_recoverable_digest(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* keys,
                                             unsigned flags, uint8_t* sigs, uint8_t* recids, uint8_t* status, size_t n) try {
   if (!ctx || (n && (!digests || !keys || !sigs || !recids || !status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (flags & ~1u) return FEC_E_ARG;
   const HostArray a[] = {secret_input(digests, 32), secret_input(keys, 32), secret_output(sigs, 64), output(recids, 1), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
@@ -1283,7 +1274,7 @@ int fec_canon_pubkey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t*
                                    uint8_t* d_out, size_t out_len, uint8_t* d_status, size_t n, void* stream) try {
   if (const int rc = dev_enter(ctx)) return rc;
   if (n && (!d_pks || !d_tweaks || !d_out || !d_status)) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (!tweak_len_ok(curve, pk_len) || !tweak_len_ok(curve, out_len) || !aligned16(d_tweaks)) return FEC_E_ARG;
   if ((pk_len == 32 && !aligned16(d_pks)) || (out_len == 32 && !aligned16(d_out))) return FEC_E_ARG;
   return launch_canon_pubkey_tweak_add(ctx, curve, d_pks, pk_len, d_tweaks, d_out, out_len, d_status, n, stream);
@@ -1292,7 +1283,7 @@ int fec_canon_pubkey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t*
 int fec_canon_pubkey_tweak_add(fec_ctx* ctx, fec_curve curve, const uint8_t* pks, size_t pk_len, const uint8_t* tweaks, uint8_t* out,
                                size_t out_len, uint8_t* status, size_t n) try {
   if (!ctx || (n && (!pks || !tweaks || !out || !status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (!tweak_len_ok(curve, pk_len) || !tweak_len_ok(curve, out_len)) return FEC_E_ARG;
   const HostArray a[] = {input(pks, pk_len), input(tweaks, 32), output(out, out_len), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
@@ -1305,7 +1296,7 @@ int fec_canon_seckey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t*
                                    uint8_t* d_status, size_t n, void* stream) try {
   if (const int rc = dev_enter(ctx)) return rc;
   if (n && (!d_keys || !d_tweaks || !d_out || !d_status)) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   if (!aligned16(d_keys) || !aligned16(d_tweaks) || !aligned16(d_out)) return FEC_E_ARG;
   return launch_canon_seckey_tweak_add(ctx, curve, d_keys, d_tweaks, d_out, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
@@ -1313,7 +1304,7 @@ int fec_canon_seckey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t*
 int fec_canon_seckey_tweak_add(fec_ctx* ctx, fec_curve curve, const uint8_t* keys, const uint8_t* tweaks, uint8_t* out, uint8_t* status,
                                size_t n) try {
   if (!ctx || (n && (!keys || !tweaks || !out || !status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return curve_ok(curve) ? FEC_E_UNSUPPORTED : FEC_E_ARG;
+  if (const int rc = weierstrass_only(curve)) return rc;
   const HostArray a[] = {secret_input(keys, 32), secret_input(tweaks, 32), secret_output(out, 32), output(status, 1)};
   return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
     return launch_canon_seckey_tweak_add(c, curve, (const uint8_t*)d[0], (const uint8_t*)d[1], (uint8_t*)d[2], (unsigned char*)d[3], m, s);

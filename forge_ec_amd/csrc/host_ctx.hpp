@@ -249,7 +249,7 @@ class WorkArea {
   }
 
  private:
-  static constexpr int kMaxRegions = 8;
+  static constexpr int kMaxRegions = 10;   // canonical ECDSA verification from the message has the most
   template <class T>
   static void assign(void* slot, char* at) {
     *static_cast<T**>(slot) = reinterpret_cast<T*>(at);

@@ -5,7 +5,7 @@ the ctx's previous launch before they enqueue anything.
 include/fecgpu.h promises that the launches of one ctx execute in call order whatever streams they name; the canonical work
 areas (d_verify, d_zbuf, d_tbuf, d_win_scratch), the comb tables and the device error word belong to the ctx, so the promise
 is what keeps two calls on two streams off each other's scratch and lets one call read what the previous one wrote.  A
-launcher keeps it by ordering its stream -- order_after_previous(ctx, s), sign_stream(ctx, stream) or a `Launch L(...)`,
+launcher keeps it by ordering its stream -- order_after_previous(ctx, s), ordered_stream(ctx, stream) or a `Launch L(...)`,
 whose constructor does it -- BEFORE its first kernel or memset.  The rules, on the text of canon.hip:
 
   * every function named launch_canon_* or launch_secret_* has one of the three ahead of its first hipLaunchKernelGGL /
@@ -23,16 +23,19 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CANON_HIP = os.path.join(ROOT, "forge_ec_amd", "csrc", "canon.hip")
 
-ORDERS = ("order_after_previous(", "sign_stream(", "Launch L(")
+ORDERS = ("order_after_previous(", "ordered_stream(", "Launch L(")
 ENQUEUES = ("hipLaunchKernelGGL", "hipMemsetAsync")
 
 # launchers that enqueue without ordering: each runs only behind a head that has ordered the same stream already
 TAILS = {
-    "launch_canon_normalize": "behind the ladder or comb of launch_canon_mul_base / launch_canon_mul (Launch L), and in launch_canon_tweak_tail",
+    "launch_canon_normalize": "behind the ladder or comb of launch_canon_mul_base / launch_canon_mul (Launch L), and last in launch_secret_comb / launch_canon_tweak_sum",
+    "launch_canon_ecdsa_tail": "behind the ordering of launch_canon_ecdsa_verify and the prepare kernel of launch_canon_ecdsa_verify_msg",
     "launch_canon_sig_finish": "behind the prepare kernel of launch_canon_sig_verify / launch_canon_sig_verify_msg",
     "launch_canon_msg_fold": "last kernel of launch_canon_sig_verify_msg / launch_canon_ecdsa_verify_msg",
-    "launch_secret_comb": "the comb pass of the signers, launch_canon_mul_base_secret, launch_canon_public_key, launch_canon_bip32_derive_priv (sign_stream)",
+    "launch_secret_comb": "the comb pass of the signers, launch_canon_mul_base_secret, launch_canon_public_key, launch_canon_bip32_derive_priv (ordered_stream)",
     "launch_secret_report": "last kernel of the same heads as launch_secret_comb",
+    "launch_canon_bip32_pub_prepare": "first level of launch_canon_bip32_derive_pub / launch_canon_bip32_derive_pub_path, behind their ordering",
+    "launch_canon_tweak_sum": "behind the prepare kernel of launch_canon_taproot_output_key, behind every level of launch_canon_bip32_derive_pub_path, first in launch_canon_tweak_tail",
     "launch_canon_tweak_tail": "behind the prepare kernel of launch_canon_pubkey_tweak_add / launch_canon_bip32_derive_pub",
 }
 
@@ -99,7 +102,9 @@ def test_the_parser_sees_the_launchers():
     for n in ("launch_canon_mul_base", "launch_canon_ecdsa_verify", "launch_canon_sig_verify", "launch_canon_x25519",
               "launch_canon_bip32_derive_priv", "fec_canon_mul_base_dev", "ensure_canon_comb"):
         assert n in fns, n
-    assert "hipLaunchKernelGGL" in fns["launch_canon_ecdsa_verify"] and "launch_canon_mul(" in fns["launch_canon_ecdsa_verify"]
+    assert "launch_canon_ecdsa_tail(" in fns["launch_canon_ecdsa_verify"]
+    assert "hipLaunchKernelGGL" in fns["launch_canon_ecdsa_tail"] and "launch_canon_double_mul(" in fns["launch_canon_ecdsa_tail"]
+    assert "launch_canon_mul_base(" in fns["launch_canon_double_mul"] and "launch_canon_mul(" in fns["launch_canon_double_mul"]
     assert "hipLaunchKernelGGL" not in fns["fec_canon_mul_base_dev"]
 
 
@@ -112,9 +117,10 @@ def test_the_rules_bite(tmp_path):
     a tail that is gone"""
     text = open(CANON_HIP).read()
     head = text.index("int launch_canon_ecdsa_recover(")
-    at = text.index("order_after_previous(ctx, s);", head)
+    at = text.index("ordered_stream(ctx, stream);", head)
+    assert at < text.index("\n}\n", head)                       # inside that head
     p = tmp_path / "unordered.hip"
-    p.write_text(text[:at] + text[at + len("order_after_previous(ctx, s);"):])
+    p.write_text(text[:at] + "(hipStream_t)stream;" + text[at + len("ordered_stream(ctx, stream);"):])
     assert violations(str(p)) == ["launch_canon_ecdsa_recover enqueues before it orders its stream"]
     p = tmp_path / "stray.hip"
     p.write_text(text + "\nint launch_canon_stray(fec_ctx* ctx, hipStream_t s) {\n  return launch_canon_msg_fold(nullptr, nullptr, 0, s);\n}\n")

@@ -4,7 +4,7 @@ GPU tests of canonical mode's call order across streams: pairs and chains of *_d
 model (oracle/canon_model.py and the canon_*_ref.py modules beside this file), never with another GPU run.
 
 include/fecgpu.h promises that the launches of one ctx execute in call order whatever streams they name: the verifiers,
-recovery, tweak-add and CKDpub share ctx->d_verify at the same offsets, every multiplication shares d_zbuf / d_tbuf /
+recovery, tweak-add and CKDpub lay their work areas out over the same ctx->d_verify, every multiplication shares d_zbuf / d_tbuf /
 d_win_scratch, the secret family shares the comb tables and the error word, and a caller may feed one call's output tensor
 to the next call on another stream.  tests/test_canon_launch_order.py holds the promise on the text of canon.hip; here two
 calls really are in flight.
