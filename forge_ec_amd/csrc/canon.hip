@@ -610,7 +610,6 @@ int tweak_work(fec_ctx* ctx, size_t n, TweakWork& w) {
   area.add(w.shared, 256).add(w.t, n * 32).add(w.xy, n * 64).add(w.q, n * 64).add(w.pst, n).add(w.flag, n);
   return place_in_verify(ctx, area);
 }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 inline bool tweak_len_ok(int curve, size_t len) { return len == 33 || len == 65 || (len == 32 && curve == FEC_SECP256K1); }
 // The sum, behind a kernel that has filled w.t and w.q: w.t * G by the comb (finish = false), + w.q, the normalisation.  w.xy is
 // affine behind it, w.pst says where the sum is at infinity.
@@ -781,6 +780,229 @@ int launch_canon_bip32_derive_pub_path(fec_ctx* ctx, const uint8_t* d_pks, const
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 
+// ---- the entry points (include/fecgpu_canon.h), one function per host / *_dev pair -------------------------------------------
+// Each names its value checks and its arrays once and hands them to host::call or host::message_call (host_ctx.hpp,
+// host_messages.hpp) with the body both forms share; `w` says which form is running.  The extern "C" wrappers below forward
+// to these, and keep the few checks whose place differs between the two forms of a pair.
+inline int arg_if(bool bad) { return bad ? FEC_E_ARG : FEC_OK; }
+inline int first_of(int a, int b) { return a != FEC_OK ? a : b; }
+inline bool n_par_ok(size_t n_par, size_t n) { return n_par == n || n_par == 1; }
+const Messages kNoMessages{nullptr, nullptr, 0};
+
+// (mul_base, mul, double_mul and the three verifiers on words are not sharded: a multi-device ctx runs them on devices[0])
+int canon_mul_base(fec_ctx* ctx, Where w, int curve, const uint64_t* scalars, uint64_t* out_xy, uint8_t* status, size_t n) {
+  FEC_FIRST_DEVICE(ctx);
+  return call(ctx, w, n, 1, arg_if(!curve_ok(curve)), arrays(input(scalars, 32).aligned(16), output(out_xy, 64).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_canon_mul_base(c, curve, p...); });
+}
+int canon_mul(fec_ctx* ctx, Where w, int curve, const uint64_t* scalars, const uint64_t* points_xy, uint64_t* out_xy, uint8_t* status, size_t n) {
+  FEC_FIRST_DEVICE(ctx);
+  return call(ctx, w, n, 1, arg_if(!curve_ok(curve)),
+              arrays(input(scalars, 32).aligned(16), input(points_xy, 64).aligned(16), output(out_xy, 64).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_canon_mul(c, curve, p...); });
+}
+int canon_double_mul(fec_ctx* ctx, Where w, int curve, const uint64_t* u1, const uint64_t* u2, const uint64_t* points_xy, uint64_t* out_xy,
+                     uint8_t* status, size_t n) {
+  FEC_FIRST_DEVICE(ctx);
+  return call(ctx, w, n, 1, arg_if(!curve_ok(curve)),
+              arrays(input(u1, 32).aligned(16), input(u2, 32).aligned(16), input(points_xy, 64).aligned(16), output(out_xy, 64).aligned(16),
+                     output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_canon_double_mul(c, curve, p...); });
+}
+int canon_ecdsa_verify(fec_ctx* ctx, Where w, int curve, const uint64_t* z, const uint64_t* r, const uint64_t* s, const uint64_t* pk_xy,
+                       uint8_t* result, size_t n) {
+  FEC_FIRST_DEVICE(ctx);
+  return call(ctx, w, n, 1, weierstrass_only(curve),
+              arrays(input(z, 32).aligned(16), input(r, 32).aligned(16), input(s, 32).aligned(16), input(pk_xy, 64).aligned(16), output(result, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_canon_ecdsa_verify(c, curve, p...); });
+}
+// BIP-340 (key: pk_x, challenge e) and Ed25519 (key: A's encoding, challenge h) on words
+int canon_sig_verify(fec_ctx* ctx, Where w, int curve, const uint64_t* key, const uint64_t* r, const uint64_t* s, const uint64_t* e, uint8_t* result,
+                     size_t n) {
+  FEC_FIRST_DEVICE(ctx);
+  return call(ctx, w, n, 1, FEC_OK,
+              arrays(input(key, 32).aligned(16), input(r, 32).aligned(16), input(s, 32).aligned(16), input(e, 32).aligned(16), output(result, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_canon_sig_verify(c, curve, p...); });
+}
+
+// ---- verification from the message, the signature bytes and the encoded key ------------------------------------
+// Host forms: with_messages (host_messages.hpp) checks the layout, shards over a multi-device ctx, chunks and rebases
+// the offsets.  *_dev forms: one device, every lane checks its own message range (result 4).
+int canon_ecdsa_verify_msg(fec_ctx* ctx, Where w, int curve, const MessageArgs& ma, const uint8_t* sigs, const uint8_t* pks, size_t pk_len,
+                           uint8_t* result, size_t n) {
+  return message_call(ctx, w, n, first_of(weierstrass_only(curve), arg_if(pk_len != 33 && pk_len != 65)), ma,
+                      arrays(input(sigs, 64).aligned(16), input(pks, pk_len).aligned(16), output(result, 1)),
+                      [&](fec_ctx* c, const Messages& m, const uint8_t* d_sigs, const uint8_t* d_pks, auto... p) {
+                        return launch_canon_ecdsa_verify_msg(c, curve, m, d_sigs, d_pks, pk_len, p...);
+                      });
+}
+int canon_sig_verify_msg(fec_ctx* ctx, Where w, int curve, const MessageArgs& ma, const uint8_t* sigs, const uint8_t* pks, uint8_t* result, size_t n) {
+  return message_call(ctx, w, n, FEC_OK, ma, arrays(input(sigs, 64).aligned(16), input(pks, 32).aligned(16), output(result, 1)),
+                      [&](fec_ctx* c, const Messages& m, auto... p) { return launch_canon_sig_verify_msg(c, curve, m, p...); });
+}
+int canon_decompress(fec_ctx* ctx, Where w, int curve, const uint8_t* in, size_t pk_len, uint64_t* xy, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, first_of(weierstrass_only(curve), arg_if(pk_len != 33 && pk_len != 65)),
+              arrays(input(in, pk_len).aligned(16), output(xy, 64).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_in, auto... p) { return launch_canon_decompress(c, curve, d_in, pk_len, p...); });
+}
+
+// ---- the signing side: secrets in, signatures out ------------------------------------------------------------------
+int canon_mul_base_secret(fec_ctx* ctx, Where w, int curve, const uint64_t* scalars, uint64_t* out_xy, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, arg_if(!curve_ok(curve)),
+              arrays(secret_input(scalars, 32).aligned(16), secret_output(out_xy, 64).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_canon_mul_base_secret(c, curve, p...); });
+}
+int canon_public_key(fec_ctx* ctx, Where w, int scheme, const uint8_t* keys, uint8_t* out, size_t out_len, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, arg_if(scheme < 0 || scheme > kSchemeBip340 || !key_len_ok(scheme, out_len)),
+              arrays(secret_input(keys, 32).aligned(16), output(out, out_len).aligned(out_len == 32 ? 16 : 0), output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_keys, uint8_t* d_out, auto... p) { return launch_canon_public_key(c, scheme, d_keys, d_out, out_len, p...); });
+}
+int canon_ecdsa_sign_digest(fec_ctx* ctx, Where w, int curve, const uint8_t* digests, const uint8_t* keys, unsigned flags, uint8_t* sigs,
+                            uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, first_of(weierstrass_only(curve), arg_if(flags & ~1u)),
+              arrays(secret_input(digests, 32).aligned(16), secret_input(keys, 32).aligned(16), secret_output(sigs, 64).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_digests, const uint8_t* d_keys, uint8_t* d_sigs, auto... p) {
+                return launch_canon_ecdsa_sign(c, curve, kNoMessages, d_digests, d_keys, flags, d_sigs, nullptr, p...);
+              });
+}
+int canon_ecdsa_sign_msg(fec_ctx* ctx, Where w, int curve, const MessageArgs& ma, const uint8_t* keys, unsigned flags, uint8_t* sigs, uint8_t* status,
+                         size_t n) {
+  return message_call(ctx, w, n, first_of(weierstrass_only(curve), arg_if(flags & ~1u)), ma,
+                      arrays(secret_input(keys, 32).aligned(16), secret_output(sigs, 64).aligned(16), output(status, 1)),
+                      [&](fec_ctx* c, const Messages& m, const uint8_t* d_keys, uint8_t* d_sigs, auto... p) {
+                        return launch_canon_ecdsa_sign(c, curve, m, nullptr, d_keys, flags, d_sigs, nullptr, p...);
+                      });
+}
+int canon_rfc6979_k(fec_ctx* ctx, Where w, int curve, const uint8_t* digests, const uint8_t* keys, uint8_t* k_out, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, weierstrass_only(curve),
+              arrays(secret_input(digests, 32).aligned(16), secret_input(keys, 32).aligned(16), secret_output(k_out, 32).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_digests, const uint8_t* d_keys, auto... p) {
+                return launch_canon_ecdsa_sign(c, curve, kNoMessages, d_digests, d_keys, 0, nullptr, p...);
+              });
+}
+int canon_bip340_sign_msg(fec_ctx* ctx, Where w, const MessageArgs& ma, const uint8_t* keys, const uint8_t* aux, uint8_t* sigs, uint8_t* status,
+                          size_t n) {
+  return message_call(ctx, w, n, FEC_OK, ma,
+                      arrays(secret_input(keys, 32).aligned(16), secret_input(aux, 32).aligned(16), secret_output(sigs, 64).aligned(16), output(status, 1)),
+                      [&](fec_ctx* c, auto... p) { return launch_canon_bip340_sign(c, p...); });
+}
+int canon_ed25519_sign_msg(fec_ctx* ctx, Where w, const MessageArgs& ma, const uint8_t* seeds, uint8_t* sigs, uint8_t* pks_out, uint8_t* status,
+                           size_t n) {
+  return message_call(ctx, w, n, FEC_OK, ma,
+                      arrays(secret_input(seeds, 32).aligned(16), secret_output(sigs, 64).aligned(16), output(pks_out, 32).aligned(16).opt(),
+                             output(status, 1)),
+                      [&](fec_ctx* c, auto... p) { return launch_canon_ed25519_sign(c, p...); });
+}
+
+// ---- X25519 (RFC 7748 section 5): 32 little-endian bytes each way ------------------------------------------------------
+int canon_x25519(fec_ctx* ctx, Where w, const uint8_t* scalars, const uint8_t* us, uint8_t* out, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, FEC_OK,
+              arrays(secret_input(scalars, 32).aligned(16), input(us, 32).aligned(16), secret_output(out, 32).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_canon_x25519(c, p...); });
+}
+int canon_x25519_base(fec_ctx* ctx, Where w, const uint8_t* scalars, uint8_t* out, size_t n) {
+  return call(ctx, w, n, 1, FEC_OK, arrays(secret_input(scalars, 32).aligned(16), output(out, 32).aligned(16)),
+              [&](fec_ctx* c, auto... p) { return launch_canon_x25519_base(c, p...); });
+}
+
+// ---- the hashes: Keccak-256 (the original submission, Ethereum's hash; not SHA3-256), RIPEMD-160, HASH160 = RIPEMD-160(SHA-256(.)) ----
+// (`status`: the *_dev forms' optional array; the host forms have none)
+enum { kHashKeccak256, kHashRipemd160, kHash160 };
+int canon_hash(fec_ctx* ctx, Where w, int hash, const MessageArgs& ma, uint8_t* out, uint8_t* status, size_t n) {
+  const bool keccak = hash == kHashKeccak256;
+  return message_call(ctx, w, n, FEC_OK, ma, arrays(output(out, keccak ? 32 : 20).aligned(keccak ? 16 : 4)),
+                      [&](fec_ctx* c, const Messages& m, uint8_t* d_out, size_t cnt, void* s) {
+                        return keccak ? launch_canon_keccak256(c, m, d_out, status, cnt, s)
+                                      : launch_canon_ripemd160(c, hash == kHash160, m, d_out, status, cnt, s);
+                      });
+}
+
+// ---- ECDSA public-key recovery (SEC 1 section 4.1.6), and recoverable signing: fec_canon_ecdsa_sign_digest and the recovery id ----
+int canon_ecdsa_recover(fec_ctx* ctx, Where w, int curve, const uint8_t* digests, const uint8_t* sigs, const uint8_t* recids, uint8_t* out,
+                        size_t out_len, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, first_of(weierstrass_only(curve), arg_if(!recover_len_ok(curve, out_len))),
+              arrays(input(digests, 32).aligned(16), input(sigs, 64).aligned(16), input(recids, 1),
+                     output(out, out_len).aligned(out_len == 64 || out_len == 20 ? 16 : 0), output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_digests, const uint8_t* d_sigs, const uint8_t* d_recids, uint8_t* d_out, auto... p) {
+                return launch_canon_ecdsa_recover(c, curve, d_digests, d_sigs, d_recids, d_out, out_len, p...);
+              });
+}
+int canon_ecdsa_sign_recoverable_digest(fec_ctx* ctx, Where w, int curve, const uint8_t* digests, const uint8_t* keys, unsigned flags, uint8_t* sigs,
+                                        uint8_t* recids, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, first_of(weierstrass_only(curve), arg_if(flags & ~1u)),
+              arrays(secret_input(digests, 32).aligned(16), secret_input(keys, 32).aligned(16), secret_output(sigs, 64).aligned(16), output(recids, 1),
+                     output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_digests, const uint8_t* d_keys, uint8_t* d_sigs, uint8_t* d_recids, uint8_t* d_status, size_t m, void* s) {
+                return launch_canon_ecdsa_sign(c, curve, kNoMessages, d_digests, d_keys, flags, d_sigs, nullptr, d_status, m, s, d_recids);
+              });
+}
+
+// ---- EC tweak-add: Q = P + t G on encoded keys, k' = k + t mod n ---------------------------------------------------------------
+int canon_pubkey_tweak_add(fec_ctx* ctx, Where w, int curve, const uint8_t* pks, size_t pk_len, const uint8_t* tweaks, uint8_t* out, size_t out_len,
+                           uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, first_of(weierstrass_only(curve), arg_if(!tweak_len_ok(curve, pk_len) || !tweak_len_ok(curve, out_len))),
+              arrays(input(pks, pk_len).aligned(pk_len == 32 ? 16 : 0), input(tweaks, 32).aligned(16), output(out, out_len).aligned(out_len == 32 ? 16 : 0),
+                     output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_pks, const uint8_t* d_tweaks, uint8_t* d_out, auto... p) {
+                return launch_canon_pubkey_tweak_add(c, curve, d_pks, pk_len, d_tweaks, d_out, out_len, p...);
+              });
+}
+int canon_seckey_tweak_add(fec_ctx* ctx, Where w, int curve, const uint8_t* keys, const uint8_t* tweaks, uint8_t* out, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, weierstrass_only(curve),
+              arrays(secret_input(keys, 32).aligned(16), secret_input(tweaks, 32).aligned(16), secret_output(out, 32).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_canon_seckey_tweak_add(c, curve, p...); });
+}
+
+// ---- BIP-32 child key derivation (secp256k1).  n_par = 1: one parent for the batch, copied once per lane ---------------------------
+int canon_bip32_derive_pub(fec_ctx* ctx, Where w, const uint8_t* parent_pks, const uint8_t* parent_ccs, size_t n_par, const uint32_t* indices,
+                           uint8_t* out_pks, uint8_t* out_ccs, uint8_t* status, size_t n) {
+  const bool shared = n_par != n;
+  return call(ctx, w, n, 1, arg_if(!n_par_ok(n_par, n)),
+              arrays(shared ? shared_input(parent_pks, 33) : input(parent_pks, 33),
+                     (shared ? shared_input(parent_ccs, 32) : input(parent_ccs, 32)).aligned(16), input(indices, 4).aligned(4), output(out_pks, 33),
+                     output(out_ccs, 32).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_pks, const uint8_t* d_ccs, auto... p) { return launch_canon_bip32_derive_pub(c, d_pks, d_ccs, shared, p...); });
+}
+int canon_bip32_derive_priv(fec_ctx* ctx, Where w, const uint8_t* parent_keys, const uint8_t* parent_ccs, size_t n_par, const uint32_t* indices,
+                            unsigned flags, uint8_t* out_keys, uint8_t* out_ccs, uint8_t* status, size_t n) {
+  const bool shared = n_par != n;
+  return call(ctx, w, n, 1, arg_if(!n_par_ok(n_par, n) || (flags & ~(unsigned)FEC_CANON_BIP32_NO_COMB)),
+              arrays((shared ? shared_secret_input(parent_keys, 32) : secret_input(parent_keys, 32)).aligned(16),
+                     (shared ? shared_secret_input(parent_ccs, 32) : secret_input(parent_ccs, 32)).aligned(16), input(indices, 4).aligned(4),
+                     secret_output(out_keys, 32).aligned(16), secret_output(out_ccs, 32).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_keys, const uint8_t* d_ccs, const uint32_t* d_idx, uint8_t* d_out_keys, uint8_t* d_out_ccs,
+                  uint8_t* d_status, size_t m, void* s) {
+                return launch_canon_bip32_derive_priv(c, d_keys, d_ccs, shared ? 1 : m, d_idx, flags, d_out_keys, d_out_ccs, d_status, m, s);
+              });
+}
+// CKDpub along a path of `depth` indices per element
+int canon_bip32_derive_pub_path(fec_ctx* ctx, Where w, const uint8_t* parent_pks, const uint8_t* parent_ccs, size_t n_par, const uint32_t* indices,
+                                size_t depth, uint8_t* out_pks, uint8_t* out_ccs, uint8_t* out_fingerprints, uint8_t* out_hash160, uint8_t* status,
+                                size_t n) {
+  const bool shared = n_par != n;
+  return call(ctx, w, n, 1, arg_if(depth < 1 || depth > 255 || !n_par_ok(n_par, n)),
+              arrays(shared ? shared_input(parent_pks, 33) : input(parent_pks, 33),
+                     (shared ? shared_input(parent_ccs, 32) : input(parent_ccs, 32)).aligned(16), input(indices, 4 * depth).aligned(4),
+                     output(out_pks, 33), output(out_ccs, 32).aligned(16), output(out_fingerprints, 4).aligned(4).opt(),
+                     output(out_hash160, 20).aligned(4).opt(), output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_pks, const uint8_t* d_ccs, const uint32_t* d_idx, auto... p) {
+                return launch_canon_bip32_derive_pub_path(c, d_pks, d_ccs, shared, d_idx, depth, p...);
+              });
+}
+
+// ---- wallet: HASH160 of encoded keys, Taproot output keys (BIP-341, BIP-86) ---------------------------------------------------------
+int canon_pubkey_hash160(fec_ctx* ctx, Where w, const uint8_t* pks, size_t pk_len, uint8_t* out, size_t n) {
+  return call(ctx, w, n, 1, arg_if(pk_len != 33 && pk_len != 65), arrays(input(pks, pk_len), output(out, 20).aligned(4)),
+              [&](fec_ctx* c, const uint8_t* d_pks, auto... p) { return launch_canon_pubkey_hash160(c, d_pks, pk_len, p...); });
+}
+int canon_taproot_output_key(fec_ctx* ctx, Where w, const uint8_t* pks, size_t pk_len, const uint8_t* roots, uint8_t* out_keys, uint8_t* out_parity,
+                             uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, arg_if(pk_len != 32 && pk_len != 33),
+              arrays(input(pks, pk_len).aligned(pk_len == 32 ? 16 : 0), input(roots, 32).aligned(16).opt(), output(out_keys, 32).aligned(16),
+                     output(out_parity, 1), output(status, 1)),
+              [&](fec_ctx* c, const uint8_t* d_pks, auto... p) { return launch_canon_taproot_output_key(c, d_pks, pk_len, p...); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -788,680 +1010,337 @@ extern "C" {
 // ---- canonical-math mode (include/fecgpu_canon.h): NOT reference parity ----------------------
 int fec_canon_mul_base_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, uint64_t* d_out_xy,
                            uint8_t* d_status, size_t n, void* stream) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!d_scalars || !d_out_xy || !d_status))) return FEC_E_ARG;
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  if (!aligned16(d_scalars) || !aligned16(d_out_xy)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_canon_mul_base(ctx, curve, d_scalars, d_out_xy, d_status, n, stream);
+  return canon_mul_base(ctx, on_device(stream), curve, d_scalars, d_out_xy, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_mul_base(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, uint64_t* out_xy, uint8_t* status,
                        size_t n) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!scalars || !out_xy || !status))) return FEC_E_ARG;
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  const HostArray a[] = {input(scalars, 32), output(out_xy, 64), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_mul_base(c, curve, (const u64*)d[0], (u64*)d[1], (unsigned char*)d[2], m, s);
-  });
+  return canon_mul_base(ctx, kOnHost, curve, scalars, out_xy, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, const uint64_t* d_points_xy,
                       uint64_t* d_out_xy, uint8_t* d_status, size_t n, void* stream) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!d_scalars || !d_points_xy || !d_out_xy || !d_status))) return FEC_E_ARG;
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  if (!aligned16(d_scalars) || !aligned16(d_points_xy) || !aligned16(d_out_xy)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_canon_mul(ctx, curve, d_scalars, d_points_xy, d_out_xy, d_status, n, stream);
+  return canon_mul(ctx, on_device(stream), curve, d_scalars, d_points_xy, d_out_xy, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* points_xy,
                   uint64_t* out_xy, uint8_t* status, size_t n) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!scalars || !points_xy || !out_xy || !status))) return FEC_E_ARG;
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  const HostArray a[] = {input(scalars, 32), input(points_xy, 64), output(out_xy, 64), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_mul(c, curve, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], (unsigned char*)d[3], m, s);
-  });
+  return canon_mul(ctx, kOnHost, curve, scalars, points_xy, out_xy, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_double_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_u1, const uint64_t* d_u2,
                              const uint64_t* d_points_xy, uint64_t* d_out_xy, uint8_t* d_status, size_t n,
                              void* stream) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!d_u1 || !d_u2 || !d_points_xy || !d_out_xy || !d_status))) return FEC_E_ARG;
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  if (!aligned16(d_u1) || !aligned16(d_u2) || !aligned16(d_points_xy) || !aligned16(d_out_xy)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_canon_double_mul(ctx, curve, d_u1, d_u2, d_points_xy, d_out_xy, d_status, n, stream);
+  return canon_double_mul(ctx, on_device(stream), curve, d_u1, d_u2, d_points_xy, d_out_xy, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_double_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* u1, const uint64_t* u2,
                          const uint64_t* points_xy, uint64_t* out_xy, uint8_t* status, size_t n) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!u1 || !u2 || !points_xy || !out_xy || !status))) return FEC_E_ARG;
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  const HostArray a[] = {input(u1, 32), input(u2, 32), input(points_xy, 64), output(out_xy, 64), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_double_mul(c, curve, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (u64*)d[3], (unsigned char*)d[4], m, s);
-  });
+  return canon_double_mul(ctx, kOnHost, curve, u1, u2, points_xy, out_xy, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_ecdsa_verify_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_z, const uint64_t* d_r,
                                const uint64_t* d_s, const uint64_t* d_pk_xy, uint8_t* d_result, size_t n,
                                void* stream) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!d_z || !d_r || !d_s || !d_pk_xy || !d_result))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (!aligned16(d_z) || !aligned16(d_r) || !aligned16(d_s) || !aligned16(d_pk_xy)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_canon_ecdsa_verify(ctx, curve, d_z, d_r, d_s, d_pk_xy, d_result, n, stream);
+  return canon_ecdsa_verify(ctx, on_device(stream), curve, d_z, d_r, d_s, d_pk_xy, d_result, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_ecdsa_verify(fec_ctx* ctx, fec_curve curve, const uint64_t* z, const uint64_t* r, const uint64_t* s,
                            const uint64_t* pk_xy, uint8_t* result, size_t n) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!z || !r || !s || !pk_xy || !result))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  const HostArray a[] = {input(z, 32), input(r, 32), input(s, 32), input(pk_xy, 64), output(result, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
-    return launch_canon_ecdsa_verify(c, curve, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
-                                     (unsigned char*)d[4], m, st);
-  });
+  return canon_ecdsa_verify(ctx, kOnHost, curve, z, r, s, pk_xy, result, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_bip340_verify_dev(fec_ctx* ctx, const uint64_t* d_pk_x, const uint64_t* d_r, const uint64_t* d_s,
                                 const uint64_t* d_e, uint8_t* d_result, size_t n, void* stream) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!d_pk_x || !d_r || !d_s || !d_e || !d_result))) return FEC_E_ARG;
-  if (!aligned16(d_pk_x) || !aligned16(d_r) || !aligned16(d_s) || !aligned16(d_e)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_canon_sig_verify(ctx, FEC_SECP256K1, d_pk_x, d_r, d_s, d_e, d_result, n, stream);
+  return canon_sig_verify(ctx, on_device(stream), FEC_SECP256K1, d_pk_x, d_r, d_s, d_e, d_result, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_bip340_verify(fec_ctx* ctx, const uint64_t* pk_x, const uint64_t* r, const uint64_t* s,
                             const uint64_t* e, uint8_t* result, size_t n) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!pk_x || !r || !s || !e || !result))) return FEC_E_ARG;
-  const HostArray arr[] = {input(pk_x, 32), input(r, 32), input(s, 32), input(e, 32), output(result, 1)};
-  return host_call(ctx, n, arr, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
-    return launch_canon_sig_verify(c, FEC_SECP256K1, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
-                                   (unsigned char*)d[4], m, st);
-  });
+  return canon_sig_verify(ctx, kOnHost, FEC_SECP256K1, pk_x, r, s, e, result, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_eddsa_verify_dev(fec_ctx* ctx, const uint64_t* d_a_enc, const uint64_t* d_r_enc, const uint64_t* d_s,
                                const uint64_t* d_h, uint8_t* d_result, size_t n, void* stream) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!d_a_enc || !d_r_enc || !d_s || !d_h || !d_result))) return FEC_E_ARG;
-  if (!aligned16(d_a_enc) || !aligned16(d_r_enc) || !aligned16(d_s) || !aligned16(d_h)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_canon_sig_verify(ctx, FEC_ED25519, d_a_enc, d_r_enc, d_s, d_h, d_result, n, stream);
+  return canon_sig_verify(ctx, on_device(stream), FEC_ED25519, d_a_enc, d_r_enc, d_s, d_h, d_result, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_eddsa_verify(fec_ctx* ctx, const uint64_t* a_enc, const uint64_t* r_enc, const uint64_t* s,
                            const uint64_t* h, uint8_t* result, size_t n) try {
-  FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || (n && (!a_enc || !r_enc || !s || !h || !result))) return FEC_E_ARG;
-  const HostArray arr[] = {input(a_enc, 32), input(r_enc, 32), input(s, 32), input(h, 32), output(result, 1)};
-  return host_call(ctx, n, arr, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
-    return launch_canon_sig_verify(c, FEC_ED25519, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
-                                   (unsigned char*)d[4], m, st);
-  });
+  return canon_sig_verify(ctx, kOnHost, FEC_ED25519, a_enc, r_enc, s, h, result, n);
 } FEC_ABI_CATCH_STATUS
 
+// (the two element-wise helpers have a host form only; b, and c, are arrays of the call only where the op reads them)
 int fec_canon_scalar_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a, const uint64_t* b,
                         const uint64_t* c, uint64_t* out, size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || !curve_ok(curve) || op < 0 || op > 1 || (n && (!a || !out))) return FEC_E_ARG;
-  if (op == 0 && n && (!b || !c)) return FEC_E_ARG;
-  const HostArray arr[] = {input(a, 32), input(op == 0 ? b : nullptr, 32), input(op == 0 ? c : nullptr, 32), output(out, 32)};
-  return host_call(ctx, n, arr, 1, [&](fec_ctx* cx, void* const* d, size_t, size_t m, hipStream_t s) {
-    Launch L(cx, s, "k_canon_scalar_op");
-    dim3 g(grid_for(m)), blk(TPB);
-    const u32 *x = (const u32*)d[0], *y = (const u32*)d[1], *z = (const u32*)d[2];
-    with_curve(curve, [&](auto t) {
-      hipLaunchKernelGGL((k_canon_scalar_op<typename decltype(t)::N>), g, blk, 0, L.s, op, x, y, z, (u32*)d[3], m);
-    });
-    return L.done();
-  });
+  return call(ctx, kOnHost, n, 1, arg_if(!curve_ok(curve) || op < 0 || op > 1),
+              arrays(input(a, 32), input(op == 0 ? b : nullptr, 32).opt(op != 0), input(op == 0 ? c : nullptr, 32).opt(op != 0), output(out, 32)),
+              [&](fec_ctx* cx, const uint64_t* x, const uint64_t* y, const uint64_t* z, uint64_t* o, size_t m, void* s) {
+                Launch L(cx, s, "k_canon_scalar_op");
+                with_curve(curve, [&](auto t) {
+                  hipLaunchKernelGGL((k_canon_scalar_op<typename decltype(t)::N>), dim3(grid_for(m)), dim3(TPB), 0, L.s, op,
+                                     reinterpret_cast<const u32*>(x), reinterpret_cast<const u32*>(y), reinterpret_cast<const u32*>(z),
+                                     reinterpret_cast<u32*>(o), m);
+                });
+                return L.done();
+              });
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_field_op(fec_ctx* ctx, fec_curve curve, int op, const uint64_t* a, const uint64_t* b, uint64_t* out,
                        size_t n) try {
   FEC_FIRST_DEVICE(ctx);  // canonical mode is not sharded: a multi-device ctx runs it on devices[0]
-  if (!ctx || op < FEC_F_ADD || op > FEC_F_INV || (n && (!a || !out))) return FEC_E_ARG;
-  if (!curve_ok(curve)) return FEC_E_ARG;
   const bool binary = op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL;
-  if (binary && n && !b) return FEC_E_ARG;
-  const HostArray arr[] = {input(a, 32), input(binary ? b : nullptr, 32), output(out, 32)};
-  return host_call(ctx, n, arr, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    const size_t n = m;
-    void *x = d[0], *y = d[1], *o = d[2];
-    Launch L(c, s, "k_canon_field_op");
-    with_curve(curve, [&](auto t) {
-      hipLaunchKernelGGL((k_canon_field_op<typename decltype(t)::C>), dim3(grid_for(n)), dim3(TPB), 0, L.s, op, (const u32*)x, (const u32*)y, (u32*)o, n);
-    });
-    return L.done();
-  });
+  return call(ctx, kOnHost, n, 1, arg_if(op < FEC_F_ADD || op > FEC_F_INV || !curve_ok(curve)),
+              arrays(input(a, 32), input(binary ? b : nullptr, 32).opt(!binary), output(out, 32)),
+              [&](fec_ctx* c, const uint64_t* x, const uint64_t* y, uint64_t* o, size_t m, void* s) {
+                Launch L(c, s, "k_canon_field_op");
+                with_curve(curve, [&](auto t) {
+                  hipLaunchKernelGGL((k_canon_field_op<typename decltype(t)::C>), dim3(grid_for(m)), dim3(TPB), 0, L.s, op,
+                                     reinterpret_cast<const u32*>(x), reinterpret_cast<const u32*>(y), reinterpret_cast<u32*>(o), m);
+                });
+                return L.done();
+              });
 } FEC_ABI_CATCH_STATUS
 
-// ---- verification from the message, the signature bytes and the encoded key ------------------------------------
-// Host forms: with_messages (host_messages.hpp) checks the layout, shards over a multi-device ctx, chunks and rebases
-// the offsets.  *_dev forms: one device, every lane checks its own message range (result 4).
+// (the *_dev forms of the two calls that take a curve and messages report misaligned offsets before the curve, the one
+// check message_call would make after it)
+static bool offsets_misaligned_first(fec_ctx* ctx, const uint64_t* d_msg_off) {
+  return ctx && !is_multi(ctx) && (reinterpret_cast<uintptr_t>(d_msg_off) & 7u);
+}
+
 int fec_canon_ecdsa_verify_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                                    size_t msg_len, const uint8_t* d_sigs, const uint8_t* d_pks, size_t pk_len,
                                    uint8_t* d_result, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_sigs || !d_pks || !d_result))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if ((pk_len != 33 && pk_len != 65) || !aligned16(d_sigs) || !aligned16(d_pks)) return FEC_E_ARG;
-  return launch_canon_ecdsa_verify_msg(ctx, curve, m, d_sigs, d_pks, pk_len, d_result, n, stream);
+  if (offsets_misaligned_first(ctx, d_msg_off)) return FEC_E_ARG;
+  return canon_ecdsa_verify_msg(ctx, on_device(stream), curve, {d_msgs, d_msg_off, msg_len}, d_sigs, d_pks, pk_len, d_result, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_ecdsa_verify_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                                const uint8_t* sigs, const uint8_t* pks, size_t pk_len, uint8_t* result, size_t n) try {
-  if (!ctx || (n && (!sigs || !pks || !result))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (pk_len != 33 && pk_len != 65) return FEC_E_ARG;
-  const HostArray a[] = {ragged(msg_off, 8), input(sigs, 64), input(pks, pk_len), output(result, 1)};
-  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_canon_ecdsa_verify_msg(c, curve, m, (const uint8_t*)d[1], (const uint8_t*)d[2], pk_len, (unsigned char*)d[3], cnt, st);
-  });
+  return canon_ecdsa_verify_msg(ctx, kOnHost, curve, {msgs, msg_off, msg_len}, sigs, pks, pk_len, result, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_bip340_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                                     const uint8_t* d_sigs, const uint8_t* d_pks, uint8_t* d_result, size_t n,
                                     void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_sigs || !d_pks || !d_result))) return FEC_E_ARG;
-  if (!aligned16(d_sigs) || !aligned16(d_pks)) return FEC_E_ARG;
-  return launch_canon_sig_verify_msg(ctx, FEC_SECP256K1, m, d_sigs, d_pks, d_result, n, stream);
+  return canon_sig_verify_msg(ctx, on_device(stream), FEC_SECP256K1, {d_msgs, d_msg_off, msg_len}, d_sigs, d_pks, d_result, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_bip340_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                                 const uint8_t* sigs, const uint8_t* pks, uint8_t* result, size_t n) try {
-  if (!ctx || (n && (!sigs || !pks || !result))) return FEC_E_ARG;
-  const HostArray a[] = {ragged(msg_off, 8), input(sigs, 64), input(pks, 32), output(result, 1)};
-  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_canon_sig_verify_msg(c, FEC_SECP256K1, m, (const uint8_t*)d[1], (const uint8_t*)d[2], (unsigned char*)d[3], cnt, st);
-  });
+  return canon_sig_verify_msg(ctx, kOnHost, FEC_SECP256K1, {msgs, msg_off, msg_len}, sigs, pks, result, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_ed25519_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                                      const uint8_t* d_sigs, const uint8_t* d_pks, uint8_t* d_result, size_t n,
                                      void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_sigs || !d_pks || !d_result))) return FEC_E_ARG;
-  if (!aligned16(d_sigs) || !aligned16(d_pks)) return FEC_E_ARG;
-  return launch_canon_sig_verify_msg(ctx, FEC_ED25519, m, d_sigs, d_pks, d_result, n, stream);
+  return canon_sig_verify_msg(ctx, on_device(stream), FEC_ED25519, {d_msgs, d_msg_off, msg_len}, d_sigs, d_pks, d_result, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_ed25519_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                                  const uint8_t* sigs, const uint8_t* pks, uint8_t* result, size_t n) try {
-  if (!ctx || (n && (!sigs || !pks || !result))) return FEC_E_ARG;
-  const HostArray a[] = {ragged(msg_off, 8), input(sigs, 64), input(pks, 32), output(result, 1)};
-  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_canon_sig_verify_msg(c, FEC_ED25519, m, (const uint8_t*)d[1], (const uint8_t*)d[2], (unsigned char*)d[3], cnt, st);
-  });
+  return canon_sig_verify_msg(ctx, kOnHost, FEC_ED25519, {msgs, msg_off, msg_len}, sigs, pks, result, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_decompress_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_in, size_t pk_len, uint64_t* d_xy,
                              uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_in || !d_xy || !d_status)) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if ((pk_len != 33 && pk_len != 65) || !aligned16(d_in) || !aligned16(d_xy)) return FEC_E_ARG;
-  return launch_canon_decompress(ctx, curve, d_in, pk_len, d_xy, d_status, n, stream);
+  return canon_decompress(ctx, on_device(stream), curve, d_in, pk_len, d_xy, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_decompress(fec_ctx* ctx, fec_curve curve, const uint8_t* in, size_t pk_len, uint64_t* xy, uint8_t* status,
                          size_t n) try {
-  if (!ctx || (n && (!in || !xy || !status))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (pk_len != 33 && pk_len != 65) return FEC_E_ARG;
-  const HostArray a[] = {input(in, pk_len), output(xy, 64), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_decompress(c, curve, (const uint8_t*)d[0], pk_len, (u64*)d[1], (unsigned char*)d[2], m, s);
-  });
+  return canon_decompress(ctx, kOnHost, curve, in, pk_len, xy, status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- the signing side: secrets in, signatures out (include/fecgpu_canon.h) ----------------------------------------
 int fec_canon_mul_base_secret_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, uint64_t* d_out_xy,
                                   uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_scalars || !d_out_xy || !d_status)) return FEC_E_ARG;
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  if (!aligned16(d_scalars) || !aligned16(d_out_xy)) return FEC_E_ARG;
-  return launch_canon_mul_base_secret(ctx, curve, d_scalars, d_out_xy, d_status, n, stream);
+  return canon_mul_base_secret(ctx, on_device(stream), curve, d_scalars, d_out_xy, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_mul_base_secret(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, uint64_t* out_xy, uint8_t* status,
                               size_t n) try {
-  if (!ctx || (n && (!scalars || !out_xy || !status))) return FEC_E_ARG;
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(scalars, 32), secret_output(out_xy, 64), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_mul_base_secret(c, curve, (const u64*)d[0], (u64*)d[1], (unsigned char*)d[2], m, s);
-  });
+  return canon_mul_base_secret(ctx, kOnHost, curve, scalars, out_xy, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_public_key_dev(fec_ctx* ctx, int scheme, const uint8_t* d_keys, uint8_t* d_out, size_t out_len,
                              uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_keys || !d_out || !d_status)) return FEC_E_ARG;
-  if (scheme < 0 || scheme > kSchemeBip340 || !key_len_ok(scheme, out_len)) return FEC_E_ARG;
-  if (!aligned16(d_keys) || (out_len == 32 && !aligned16(d_out))) return FEC_E_ARG;
-  return launch_canon_public_key(ctx, scheme, d_keys, d_out, out_len, d_status, n, stream);
+  return canon_public_key(ctx, on_device(stream), scheme, d_keys, d_out, out_len, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_public_key(fec_ctx* ctx, int scheme, const uint8_t* keys, uint8_t* out, size_t out_len, uint8_t* status,
                          size_t n) try {
-  if (!ctx || (n && (!keys || !out || !status))) return FEC_E_ARG;
-  if (scheme < 0 || scheme > kSchemeBip340 || !key_len_ok(scheme, out_len)) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(keys, 32), output(out, out_len), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_public_key(c, scheme, (const uint8_t*)d[0], (uint8_t*)d[1], out_len, (unsigned char*)d[2], m, s);
-  });
+  return canon_public_key(ctx, kOnHost, scheme, keys, out, out_len, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_ecdsa_sign_digest_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_keys,
                                     unsigned flags, uint8_t* d_sigs, uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_digests || !d_keys || !d_sigs || !d_status)) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if ((flags & ~1u) || !aligned16(d_digests) || !aligned16(d_keys) || !aligned16(d_sigs)) return FEC_E_ARG;
-  return launch_canon_ecdsa_sign(ctx, curve, Messages{nullptr, nullptr, 0}, d_digests, d_keys, flags, d_sigs, nullptr, d_status, n, stream);
+  return canon_ecdsa_sign_digest(ctx, on_device(stream), curve, d_digests, d_keys, flags, d_sigs, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_ecdsa_sign_digest(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* keys, unsigned flags,
                                 uint8_t* sigs, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!digests || !keys || !sigs || !status))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (flags & ~1u) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(digests, 32), secret_input(keys, 32), secret_output(sigs, 64), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_ecdsa_sign(c, curve, Messages{nullptr, nullptr, 0}, (const uint8_t*)d[0], (const uint8_t*)d[1], flags,
-                                   (uint8_t*)d[2], nullptr, (unsigned char*)d[3], m, s);
-  });
+  return canon_ecdsa_sign_digest(ctx, kOnHost, curve, digests, keys, flags, sigs, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_ecdsa_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                                  size_t msg_len, const uint8_t* d_keys, unsigned flags, uint8_t* d_sigs, uint8_t* d_status,
                                  size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_keys || !d_sigs || !d_status))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if ((flags & ~1u) || !aligned16(d_keys) || !aligned16(d_sigs)) return FEC_E_ARG;
-  return launch_canon_ecdsa_sign(ctx, curve, m, nullptr, d_keys, flags, d_sigs, nullptr, d_status, n, stream);
+  if (offsets_misaligned_first(ctx, d_msg_off)) return FEC_E_ARG;
+  return canon_ecdsa_sign_msg(ctx, on_device(stream), curve, {d_msgs, d_msg_off, msg_len}, d_keys, flags, d_sigs, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_ecdsa_sign_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                              const uint8_t* keys, unsigned flags, uint8_t* sigs, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!keys || !sigs || !status))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (flags & ~1u) return FEC_E_ARG;
-  const HostArray a[] = {ragged(msg_off, 8), secret_input(keys, 32), secret_output(sigs, 64), output(status, 1)};
-  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_canon_ecdsa_sign(c, curve, m, nullptr, (const uint8_t*)d[1], flags, (uint8_t*)d[2], nullptr, (unsigned char*)d[3], cnt, st);
-  });
+  return canon_ecdsa_sign_msg(ctx, kOnHost, curve, {msgs, msg_off, msg_len}, keys, flags, sigs, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_keys, uint8_t* d_k_out,
                             uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_digests || !d_keys || !d_k_out || !d_status)) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (!aligned16(d_digests) || !aligned16(d_keys) || !aligned16(d_k_out)) return FEC_E_ARG;
-  return launch_canon_ecdsa_sign(ctx, curve, Messages{nullptr, nullptr, 0}, d_digests, d_keys, 0, nullptr, d_k_out, d_status, n, stream);
+  return canon_rfc6979_k(ctx, on_device(stream), curve, d_digests, d_keys, d_k_out, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* keys, uint8_t* k_out,
                         uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!digests || !keys || !k_out || !status))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  const HostArray a[] = {secret_input(digests, 32), secret_input(keys, 32), secret_output(k_out, 32), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_ecdsa_sign(c, curve, Messages{nullptr, nullptr, 0}, (const uint8_t*)d[0], (const uint8_t*)d[1], 0, nullptr,
-                                   (uint8_t*)d[2], (unsigned char*)d[3], m, s);
-  });
+  return canon_rfc6979_k(ctx, kOnHost, curve, digests, keys, k_out, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_bip340_sign_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                                   const uint8_t* d_keys, const uint8_t* d_aux, uint8_t* d_sigs, uint8_t* d_status, size_t n,
                                   void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_keys || !d_aux || !d_sigs || !d_status))) return FEC_E_ARG;
-  if (!aligned16(d_keys) || !aligned16(d_aux) || !aligned16(d_sigs)) return FEC_E_ARG;
-  return launch_canon_bip340_sign(ctx, m, d_keys, d_aux, d_sigs, d_status, n, stream);
+  return canon_bip340_sign_msg(ctx, on_device(stream), {d_msgs, d_msg_off, msg_len}, d_keys, d_aux, d_sigs, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_bip340_sign_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* keys,
                               const uint8_t* aux, uint8_t* sigs, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!keys || !aux || !sigs || !status))) return FEC_E_ARG;
-  const HostArray a[] = {ragged(msg_off, 8), secret_input(keys, 32), secret_input(aux, 32), secret_output(sigs, 64), output(status, 1)};
-  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_canon_bip340_sign(c, m, (const uint8_t*)d[1], (const uint8_t*)d[2], (uint8_t*)d[3], (unsigned char*)d[4], cnt, st);
-  });
+  return canon_bip340_sign_msg(ctx, kOnHost, {msgs, msg_off, msg_len}, keys, aux, sigs, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_ed25519_sign_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                                    const uint8_t* d_seeds, uint8_t* d_sigs, uint8_t* d_pks_out, uint8_t* d_status, size_t n,
                                    void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_seeds || !d_sigs || !d_status))) return FEC_E_ARG;
-  if (!aligned16(d_seeds) || !aligned16(d_sigs) || !aligned16(d_pks_out)) return FEC_E_ARG;
-  return launch_canon_ed25519_sign(ctx, m, d_seeds, d_sigs, d_pks_out, d_status, n, stream);
+  return canon_ed25519_sign_msg(ctx, on_device(stream), {d_msgs, d_msg_off, msg_len}, d_seeds, d_sigs, d_pks_out, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_ed25519_sign_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* seeds,
                                uint8_t* sigs, uint8_t* pks_out, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!seeds || !sigs || !status))) return FEC_E_ARG;
-  const HostArray a[] = {ragged(msg_off, 8), secret_input(seeds, 32), secret_output(sigs, 64), output(pks_out, 32), output(status, 1)};
-  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_canon_ed25519_sign(c, m, (const uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], (unsigned char*)d[4], cnt, st);
-  });
+  return canon_ed25519_sign_msg(ctx, kOnHost, {msgs, msg_off, msg_len}, seeds, sigs, pks_out, status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- X25519 (RFC 7748 section 5): 32 little-endian bytes each way ------------------------------------------------------
 int fec_canon_x25519_dev(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_us, uint8_t* d_out, uint8_t* d_status,
                          size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_scalars || !d_us || !d_out || !d_status)) return FEC_E_ARG;
-  if (!aligned16(d_scalars) || !aligned16(d_us) || !aligned16(d_out)) return FEC_E_ARG;
-  return launch_canon_x25519(ctx, d_scalars, d_us, d_out, d_status, n, stream);
+  return canon_x25519(ctx, on_device(stream), d_scalars, d_us, d_out, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_x25519(fec_ctx* ctx, const uint8_t* scalars, const uint8_t* us, uint8_t* out, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!scalars || !us || !out || !status))) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(scalars, 32), input(us, 32), secret_output(out, 32), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_x25519(c, (const uint8_t*)d[0], (const uint8_t*)d[1], (uint8_t*)d[2], (unsigned char*)d[3], m, s);
-  });
+  return canon_x25519(ctx, kOnHost, scalars, us, out, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_x25519_base_dev(fec_ctx* ctx, const uint8_t* d_scalars, uint8_t* d_out, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_scalars || !d_out)) return FEC_E_ARG;
-  if (!aligned16(d_scalars) || !aligned16(d_out)) return FEC_E_ARG;
-  return launch_canon_x25519_base(ctx, d_scalars, d_out, n, stream);
+  return canon_x25519_base(ctx, on_device(stream), d_scalars, d_out, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_x25519_base(fec_ctx* ctx, const uint8_t* scalars, uint8_t* out, size_t n) try {
-  if (!ctx || (n && (!scalars || !out))) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(scalars, 32), output(out, 32)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_x25519_base(c, (const uint8_t*)d[0], (uint8_t*)d[1], m, s);
-  });
+  return canon_x25519_base(ctx, kOnHost, scalars, out, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- Keccak-256 (the original submission, Ethereum's hash; not SHA3-256) ---------------------------------------------------
 int fec_canon_keccak256_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_out,
                             uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && !d_out) || !aligned16(d_out)) return FEC_E_ARG;
-  return launch_canon_keccak256(ctx, m, d_out, d_status, n, stream);
+  return canon_hash(ctx, on_device(stream), kHashKeccak256, {d_msgs, d_msg_off, msg_len}, d_out, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_keccak256(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* out, size_t n) try {
-  if (!ctx || (n && !out)) return FEC_E_ARG;
-  const HostArray a[] = {ragged(msg_off, 8), output(out, 32)};
-  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_canon_keccak256(c, m, (uint8_t*)d[1], nullptr, cnt, st);
-  });
+  return canon_hash(ctx, kOnHost, kHashKeccak256, {msgs, msg_off, msg_len}, out, nullptr, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- ECDSA public-key recovery (SEC 1 section 4.1.6) ------------------------------------------------------------------------
 int fec_canon_ecdsa_recover_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_sigs,
                                 const uint8_t* d_recids, uint8_t* d_out, size_t out_len, uint8_t* d_status, size_t n,
                                 void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_digests || !d_sigs || !d_recids || !d_out || !d_status)) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (!recover_len_ok(curve, out_len) || !aligned16(d_digests) || !aligned16(d_sigs)) return FEC_E_ARG;
-  if ((out_len == 64 || out_len == 20) && !aligned16(d_out)) return FEC_E_ARG;
-  return launch_canon_ecdsa_recover(ctx, curve, d_digests, d_sigs, d_recids, d_out, out_len, d_status, n, stream);
+  return canon_ecdsa_recover(ctx, on_device(stream), curve, d_digests, d_sigs, d_recids, d_out, out_len, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_ecdsa_recover(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* sigs, const uint8_t* recids,
                             uint8_t* out, size_t out_len, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!digests || !sigs || !recids || !out || !status))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (!recover_len_ok(curve, out_len)) return FEC_E_ARG;
-  const HostArray a[] = {input(digests, 32), input(sigs, 64), input(recids, 1), output(out, out_len), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_ecdsa_recover(c, curve, (const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (uint8_t*)d[3],
-                                      out_len, (unsigned char*)d[4], m, s);
-  });
+  return canon_ecdsa_recover(ctx, kOnHost, curve, digests, sigs, recids, out, out_len, status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- recoverable ECDSA signing: fec_canon_ecdsa_sign_digest and the recovery id -------------------------------------------------
 int fec_canon_ecdsa_sign_recoverable_digest_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_digests, const uint8_t* d_keys,
                                                 unsigned flags, uint8_t* d_sigs, uint8_t* d_recids, uint8_t* d_status, size_t n,
                                                 void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_digests || !d_keys || !d_sigs || !d_recids || !d_status)) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if ((flags & ~1u) || !aligned16(d_digests) || !aligned16(d_keys) || !aligned16(d_sigs)) return FEC_E_ARG;
-  return launch_canon_ecdsa_sign(ctx, curve, Messages{nullptr, nullptr, 0}, d_digests, d_keys, flags, d_sigs, nullptr, d_status, n, stream,
-                                 d_recids);
+  return canon_ecdsa_sign_recoverable_digest(ctx, on_device(stream), curve, d_digests, d_keys, flags, d_sigs, d_recids, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_ecdsa_sign_recoverable_digest(fec_ctx* ctx, fec_curve curve, const uint8_t* digests, const uint8_t* keys,
                                             unsigned flags, uint8_t* sigs, uint8_t* recids, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!digests || !keys || !sigs || !recids || !status))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (flags & ~1u) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(digests, 32), secret_input(keys, 32), secret_output(sigs, 64), output(recids, 1), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_ecdsa_sign(c, curve, Messages{nullptr, nullptr, 0}, (const uint8_t*)d[0], (const uint8_t*)d[1], flags,
-                                   (uint8_t*)d[2], nullptr, (unsigned char*)d[4], m, s, (uint8_t*)d[3]);
-  });
+  return canon_ecdsa_sign_recoverable_digest(ctx, kOnHost, curve, digests, keys, flags, sigs, recids, status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- EC tweak-add: Q = P + t G on encoded keys, k' = k + t mod n ---------------------------------------------------------------
 int fec_canon_pubkey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_pks, size_t pk_len, const uint8_t* d_tweaks,
                                    uint8_t* d_out, size_t out_len, uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_pks || !d_tweaks || !d_out || !d_status)) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (!tweak_len_ok(curve, pk_len) || !tweak_len_ok(curve, out_len) || !aligned16(d_tweaks)) return FEC_E_ARG;
-  if ((pk_len == 32 && !aligned16(d_pks)) || (out_len == 32 && !aligned16(d_out))) return FEC_E_ARG;
-  return launch_canon_pubkey_tweak_add(ctx, curve, d_pks, pk_len, d_tweaks, d_out, out_len, d_status, n, stream);
+  return canon_pubkey_tweak_add(ctx, on_device(stream), curve, d_pks, pk_len, d_tweaks, d_out, out_len, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_pubkey_tweak_add(fec_ctx* ctx, fec_curve curve, const uint8_t* pks, size_t pk_len, const uint8_t* tweaks, uint8_t* out,
                                size_t out_len, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!pks || !tweaks || !out || !status))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (!tweak_len_ok(curve, pk_len) || !tweak_len_ok(curve, out_len)) return FEC_E_ARG;
-  const HostArray a[] = {input(pks, pk_len), input(tweaks, 32), output(out, out_len), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_pubkey_tweak_add(c, curve, (const uint8_t*)d[0], pk_len, (const uint8_t*)d[1], (uint8_t*)d[2], out_len,
-                                         (unsigned char*)d[3], m, s);
-  });
+  return canon_pubkey_tweak_add(ctx, kOnHost, curve, pks, pk_len, tweaks, out, out_len, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_seckey_tweak_add_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_keys, const uint8_t* d_tweaks, uint8_t* d_out,
                                    uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n && (!d_keys || !d_tweaks || !d_out || !d_status)) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  if (!aligned16(d_keys) || !aligned16(d_tweaks) || !aligned16(d_out)) return FEC_E_ARG;
-  return launch_canon_seckey_tweak_add(ctx, curve, d_keys, d_tweaks, d_out, d_status, n, stream);
+  return canon_seckey_tweak_add(ctx, on_device(stream), curve, d_keys, d_tweaks, d_out, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_seckey_tweak_add(fec_ctx* ctx, fec_curve curve, const uint8_t* keys, const uint8_t* tweaks, uint8_t* out, uint8_t* status,
                                size_t n) try {
-  if (!ctx || (n && (!keys || !tweaks || !out || !status))) return FEC_E_ARG;
-  if (const int rc = weierstrass_only(curve)) return rc;
-  const HostArray a[] = {secret_input(keys, 32), secret_input(tweaks, 32), secret_output(out, 32), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_seckey_tweak_add(c, curve, (const uint8_t*)d[0], (const uint8_t*)d[1], (uint8_t*)d[2], (unsigned char*)d[3], m, s);
-  });
+  return canon_seckey_tweak_add(ctx, kOnHost, curve, keys, tweaks, out, status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- BIP-32 child key derivation (secp256k1) -------------------------------------------------------------------------------------
 int fec_canon_bip32_derive_pub_dev(fec_ctx* ctx, const uint8_t* d_parent_pks, const uint8_t* d_parent_ccs, size_t n_par,
                                    const uint32_t* d_indices, uint8_t* d_out_pks, uint8_t* d_out_ccs, uint8_t* d_status, size_t n,
                                    void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n_par != n && n_par != 1) return FEC_E_ARG;
-  if (n && (!d_parent_pks || !d_parent_ccs || !d_indices || !d_out_pks || !d_out_ccs || !d_status)) return FEC_E_ARG;
-  if (!aligned16(d_parent_ccs) || !aligned16(d_out_ccs) || (reinterpret_cast<uintptr_t>(d_indices) & 3u)) return FEC_E_ARG;
-  return launch_canon_bip32_derive_pub(ctx, d_parent_pks, d_parent_ccs, n_par != n, d_indices, d_out_pks, d_out_ccs, d_status, n, stream);
+  return canon_bip32_derive_pub(ctx, on_device(stream), d_parent_pks, d_parent_ccs, n_par, d_indices, d_out_pks, d_out_ccs, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_bip32_derive_pub(fec_ctx* ctx, const uint8_t* parent_pks, const uint8_t* parent_ccs, size_t n_par, const uint32_t* indices,
                                uint8_t* out_pks, uint8_t* out_ccs, uint8_t* status, size_t n) try {
-  if (!ctx || (n_par != n && n_par != 1)) return FEC_E_ARG;
-  if (n && (!parent_pks || !parent_ccs || !indices || !out_pks || !out_ccs || !status)) return FEC_E_ARG;
-  const bool shared = n_par != n;
-  const HostArray a[] = {shared ? shared_input(parent_pks, 33) : input(parent_pks, 33),
-                         shared ? shared_input(parent_ccs, 32) : input(parent_ccs, 32),
-                         input(indices, 4), output(out_pks, 33), output(out_ccs, 32), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_bip32_derive_pub(c, (const uint8_t*)d[0], (const uint8_t*)d[1], shared, (const uint32_t*)d[2], (uint8_t*)d[3],
-                                         (uint8_t*)d[4], (unsigned char*)d[5], m, s);
-  });
+  return canon_bip32_derive_pub(ctx, kOnHost, parent_pks, parent_ccs, n_par, indices, out_pks, out_ccs, status, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_bip32_derive_priv_dev(fec_ctx* ctx, const uint8_t* d_parent_keys, const uint8_t* d_parent_ccs, size_t n_par,
                                     const uint32_t* d_indices, unsigned flags, uint8_t* d_out_keys, uint8_t* d_out_ccs, uint8_t* d_status,
                                     size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if ((n_par != n && n_par != 1) || (flags & ~(unsigned)FEC_CANON_BIP32_NO_COMB)) return FEC_E_ARG;
-  if (n && (!d_parent_keys || !d_parent_ccs || !d_indices || !d_out_keys || !d_out_ccs || !d_status)) return FEC_E_ARG;
-  if (!aligned16(d_parent_keys) || !aligned16(d_parent_ccs) || !aligned16(d_out_keys) || !aligned16(d_out_ccs) ||
-      (reinterpret_cast<uintptr_t>(d_indices) & 3u))
-    return FEC_E_ARG;
-  return launch_canon_bip32_derive_priv(ctx, d_parent_keys, d_parent_ccs, n_par, d_indices, flags, d_out_keys, d_out_ccs, d_status, n, stream);
+  return canon_bip32_derive_priv(ctx, on_device(stream), d_parent_keys, d_parent_ccs, n_par, d_indices, flags, d_out_keys, d_out_ccs, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_bip32_derive_priv(fec_ctx* ctx, const uint8_t* parent_keys, const uint8_t* parent_ccs, size_t n_par, const uint32_t* indices,
                                 unsigned flags, uint8_t* out_keys, uint8_t* out_ccs, uint8_t* status, size_t n) try {
-  if (!ctx || (n_par != n && n_par != 1) || (flags & ~(unsigned)FEC_CANON_BIP32_NO_COMB)) return FEC_E_ARG;
-  if (n && (!parent_keys || !parent_ccs || !indices || !out_keys || !out_ccs || !status)) return FEC_E_ARG;
-  const bool shared = n_par != n;
-  const HostArray shared_key = {parent_keys, 0, 32, false, true, true}, shared_cc = {parent_ccs, 0, 32, false, true, true};
-  const HostArray a[] = {shared ? shared_key : secret_input(parent_keys, 32), shared ? shared_cc : secret_input(parent_ccs, 32),
-                         input(indices, 4), secret_output(out_keys, 32), secret_output(out_ccs, 32), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_bip32_derive_priv(c, (const uint8_t*)d[0], (const uint8_t*)d[1], shared ? 1 : m, (const uint32_t*)d[2], flags,
-                                          (uint8_t*)d[3], (uint8_t*)d[4], (unsigned char*)d[5], m, s);
-  });
+  return canon_bip32_derive_priv(ctx, kOnHost, parent_keys, parent_ccs, n_par, indices, flags, out_keys, out_ccs, status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- RIPEMD-160 and HASH160 = RIPEMD-160(SHA-256(.)) ----------------------------------------------------------------------------
+// (the *_dev forms from here on return at n = 0 before they look at anything but the ctx -- the path form: and the depth)
 int fec_canon_ripemd160_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_out,
                             uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n == 0) return FEC_OK;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || !d_out || !aligned4(d_out)) return FEC_E_ARG;
-  return launch_canon_ripemd160(ctx, false, m, d_out, d_status, n, stream);
+  if (n == 0) return dev_enter(ctx);
+  return canon_hash(ctx, on_device(stream), kHashRipemd160, {d_msgs, d_msg_off, msg_len}, d_out, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_ripemd160(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* out, size_t n) try {
-  if (!ctx || (n && !out)) return FEC_E_ARG;
-  const HostArray a[] = {ragged(msg_off, 8), output(out, 20)};
-  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_canon_ripemd160(c, false, m, (uint8_t*)d[1], nullptr, cnt, st);
-  });
+  return canon_hash(ctx, kOnHost, kHashRipemd160, {msgs, msg_off, msg_len}, out, nullptr, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_hash160_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_out,
                           uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n == 0) return FEC_OK;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || !d_out || !aligned4(d_out)) return FEC_E_ARG;
-  return launch_canon_ripemd160(ctx, true, m, d_out, d_status, n, stream);
+  if (n == 0) return dev_enter(ctx);
+  return canon_hash(ctx, on_device(stream), kHash160, {d_msgs, d_msg_off, msg_len}, d_out, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_hash160(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* out, size_t n) try {
-  if (!ctx || (n && !out)) return FEC_E_ARG;
-  const HostArray a[] = {ragged(msg_off, 8), output(out, 20)};
-  return with_messages(ctx, n, a, msgs, msg_off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_canon_ripemd160(c, true, m, (uint8_t*)d[1], nullptr, cnt, st);
-  });
+  return canon_hash(ctx, kOnHost, kHash160, {msgs, msg_off, msg_len}, out, nullptr, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_canon_pubkey_hash160_dev(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_len, uint8_t* d_out, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n == 0) return FEC_OK;
-  if (!d_pks || !d_out || (pk_len != 33 && pk_len != 65) || !aligned4(d_out)) return FEC_E_ARG;
-  return launch_canon_pubkey_hash160(ctx, d_pks, pk_len, d_out, n, stream);
+  if (n == 0) return dev_enter(ctx);
+  return canon_pubkey_hash160(ctx, on_device(stream), d_pks, pk_len, d_out, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_pubkey_hash160(fec_ctx* ctx, const uint8_t* pks, size_t pk_len, uint8_t* out, size_t n) try {
-  if (!ctx || (n && (!pks || !out)) || (pk_len != 33 && pk_len != 65)) return FEC_E_ARG;
-  const HostArray a[] = {input(pks, pk_len), output(out, 20)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_pubkey_hash160(c, (const uint8_t*)d[0], pk_len, (uint8_t*)d[1], m, s);
-  });
+  return canon_pubkey_hash160(ctx, kOnHost, pks, pk_len, out, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- Taproot output keys (BIP-341, BIP-86) ---------------------------------------------------------------------------------------
 int fec_canon_taproot_output_key_dev(fec_ctx* ctx, const uint8_t* d_pks, size_t pk_len, const uint8_t* d_roots, uint8_t* d_out_keys,
                                      uint8_t* d_out_parity, uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (n == 0) return FEC_OK;
-  if (!d_pks || !d_out_keys || !d_out_parity || !d_status || (pk_len != 32 && pk_len != 33)) return FEC_E_ARG;
-  if ((pk_len == 32 && !aligned16(d_pks)) || !aligned16(d_roots) || !aligned16(d_out_keys)) return FEC_E_ARG;
-  return launch_canon_taproot_output_key(ctx, d_pks, pk_len, d_roots, d_out_keys, d_out_parity, d_status, n, stream);
+  if (n == 0) return dev_enter(ctx);
+  return canon_taproot_output_key(ctx, on_device(stream), d_pks, pk_len, d_roots, d_out_keys, d_out_parity, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_taproot_output_key(fec_ctx* ctx, const uint8_t* pks, size_t pk_len, const uint8_t* roots, uint8_t* out_keys,
                                  uint8_t* out_parity, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!pks || !out_keys || !out_parity || !status)) || (pk_len != 32 && pk_len != 33)) return FEC_E_ARG;
-  const HostArray a[] = {input(pks, pk_len), input(roots, 32), output(out_keys, 32), output(out_parity, 1), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_taproot_output_key(c, (const uint8_t*)d[0], pk_len, (const uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3],
-                                           (unsigned char*)d[4], m, s);
-  });
+  return canon_taproot_output_key(ctx, kOnHost, pks, pk_len, roots, out_keys, out_parity, status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- BIP-32 CKDpub along a path ------------------------------------------------------------------------------------------------
 int fec_canon_bip32_derive_pub_path_dev(fec_ctx* ctx, const uint8_t* d_parent_pks, const uint8_t* d_parent_ccs, size_t n_par,
                                         const uint32_t* d_indices, size_t depth, uint8_t* d_out_pks, uint8_t* d_out_ccs,
                                         uint8_t* d_out_fingerprints, uint8_t* d_out_hash160, uint8_t* d_status, size_t n,
                                         void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (depth < 1 || depth > 255) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  if (n_par != n && n_par != 1) return FEC_E_ARG;
-  if (!d_parent_pks || !d_parent_ccs || !d_indices || !d_out_pks || !d_out_ccs || !d_status) return FEC_E_ARG;
-  if (!aligned16(d_parent_ccs) || !aligned16(d_out_ccs) || !aligned4(d_indices) || !aligned4(d_out_fingerprints) || !aligned4(d_out_hash160))
-    return FEC_E_ARG;
-  return launch_canon_bip32_derive_pub_path(ctx, d_parent_pks, d_parent_ccs, n_par != n, d_indices, depth, d_out_pks, d_out_ccs,
-                                            d_out_fingerprints, d_out_hash160, d_status, n, stream);
+  if (n == 0 && depth >= 1 && depth <= 255) return dev_enter(ctx);
+  return canon_bip32_derive_pub_path(ctx, on_device(stream), d_parent_pks, d_parent_ccs, n_par, d_indices, depth, d_out_pks, d_out_ccs,
+                                     d_out_fingerprints, d_out_hash160, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_canon_bip32_derive_pub_path(fec_ctx* ctx, const uint8_t* parent_pks, const uint8_t* parent_ccs, size_t n_par,
                                     const uint32_t* indices, size_t depth, uint8_t* out_pks, uint8_t* out_ccs, uint8_t* out_fingerprints,
                                     uint8_t* out_hash160, uint8_t* status, size_t n) try {
-  if (!ctx || depth < 1 || depth > 255 || (n_par != n && n_par != 1)) return FEC_E_ARG;
-  if (n && (!parent_pks || !parent_ccs || !indices || !out_pks || !out_ccs || !status)) return FEC_E_ARG;
-  const bool shared = n_par != n;
-  const HostArray a[] = {shared ? shared_input(parent_pks, 33) : input(parent_pks, 33),
-                         shared ? shared_input(parent_ccs, 32) : input(parent_ccs, 32),
-                         input(indices, 4 * depth), output(out_pks, 33), output(out_ccs, 32), output(out_fingerprints, 4),
-                         output(out_hash160, 20), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_canon_bip32_derive_pub_path(c, (const uint8_t*)d[0], (const uint8_t*)d[1], shared, (const uint32_t*)d[2], depth,
-                                              (uint8_t*)d[3], (uint8_t*)d[4], (uint8_t*)d[5], (uint8_t*)d[6], (unsigned char*)d[7], m, s);
-  });
+  return canon_bip32_derive_pub_path(ctx, kOnHost, parent_pks, parent_ccs, n_par, indices, depth, out_pks, out_ccs, out_fingerprints, out_hash160,
+                                     status, n);
 } FEC_ABI_CATCH_STATUS
 
 }  // extern "C"

@@ -1671,15 +1671,15 @@ int fec_ctx_create(fec_ctx** out, int device) try {
   }
   {
     // every copy goes to the ctx stream: it is non-blocking, i.e. NOT ordered with NULL-stream work
-    bool ok = ensure(ctx, 0, 64) == FEC_OK && ensure(ctx, 1, 64) == FEC_OK;
-    ok = ok && hipMemcpyAsync(ctx->d_buf[0], SECP_GXY, 64, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(ctx->d_buf[1], SECP_R2X2, 64, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    bool ok = ensure(ctx, kStageIn, 64) == FEC_OK && ensure(ctx, kStageOut, 64) == FEC_OK;
+    ok = ok && hipMemcpyAsync(ctx->d_buf[kStageIn], SECP_GXY, 64, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(ctx->d_buf[kStageOut], SECP_R2X2, 64, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
     ok = ok && hipMemcpyAsync(ctx->d_gen[0] + 8, FE_ONE, 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
     ok = ok && hipMemcpyAsync(ctx->d_gen[1], GEN_P256, 96, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
     ok = ok && hipMemcpyAsync(ctx->d_gen[2], GEN_ED, 128, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
     // secp256k1: (gx, gy) * R_SQUARED;  Ed25519: t = x * y
-    ok = ok && launch_field(ctx, FEC_SECP256K1, FEC_F_MUL, (const u64*)ctx->d_buf[0],
-                            (const u64*)ctx->d_buf[1], ctx->d_gen[0], 2) == FEC_OK;
+    ok = ok && launch_field(ctx, FEC_SECP256K1, FEC_F_MUL, (const u64*)ctx->d_buf[kStageIn],
+                            (const u64*)ctx->d_buf[kStageOut], ctx->d_gen[0], 2) == FEC_OK;
     ok = ok && launch_field(ctx, FEC_ED25519, FEC_F_MUL, ctx->d_gen[2], ctx->d_gen[2] + 4,
                             ctx->d_gen[2] + 12, 1) == FEC_OK;
     ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;
@@ -1771,32 +1771,51 @@ void fec_ctx_destroy(fec_ctx* ctx) try {
   delete ctx;
 } FEC_ABI_CATCH_VOID
 
+// ---- the element-wise entry points, one function per host / *_dev pair: its value checks and its arrays, once, handed to
+// host::call (host_ctx.hpp) with the body both forms share; `w` says which form is running.  A wrapper keeps a check only
+// where its place differs between the two forms of the pair. ----
+static int arg_if(bool bad) { return bad ? FEC_E_ARG : FEC_OK; }
+static int first_of(int a, int b) { return a != FEC_OK ? a : b; }
+// secp256k1 and P-256 only; here any other value, a curve or not, is "unsupported"
+static int ecdsa_curves_only(int curve) { return curve == FEC_SECP256K1 || curve == FEC_P256 ? FEC_OK : FEC_E_UNSUPPORTED; }
+
+static int batch_mul(fec_ctx* ctx, Where w, int curve, const uint64_t* scalars, const uint64_t* points, uint64_t* out, size_t n) {
+  const size_t pb = (size_t)plimbs(curve) * 8;
+  return call(ctx, w, n, 2, arg_if(!curve_ok(curve)), arrays(input(scalars, 32).aligned(16), input(points, pb).aligned(16), output(out, pb).aligned(16)),
+              [&](fec_ctx* c, auto... p) { return launch_mul(c, curve, false, p...); });
+}
 int fec_batch_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* ds, const uint64_t* dp, uint64_t* dout,
                       size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!ds || !dp || !dout))) return FEC_E_ARG;
-  if (!aligned16(ds) || !aligned16(dp) || !aligned16(dout)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_mul(ctx, curve, false, ds, dp, dout, n, stream);
+  return batch_mul(ctx, on_device(stream), curve, ds, dp, dout, n);
+} FEC_ABI_CATCH_STATUS
+int fec_batch_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* points,
+                  uint64_t* out, size_t n) try {
+  return batch_mul(ctx, kOnHost, curve, scalars, points, out, n);
 } FEC_ABI_CATCH_STATUS
 
+// (fec_batch_mul_fixed stays two functions: its host form prepares every device before the chunks run, below)
 int fec_batch_mul_fixed_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* ds, const uint64_t* dbase,
                             uint64_t* dout, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!ds || !dbase || !dout))) return FEC_E_ARG;
+  if (const int rc = dev_enter(ctx)) return rc;
+  if (!curve_ok(curve) || (n && (!ds || !dbase || !dout))) return FEC_E_ARG;
   if (!aligned16(ds) || !aligned16(dbase) || !aligned16(dout)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
   // (Ed25519: the ctx's own generator (fec_generator_dev) is recognised by address, so its addend table is built once)
   return launch_mul(ctx, curve, true, ds, dbase, dout, n, stream, dbase == ctx->d_gen[FEC_ED25519] ? ctx->h_gen_ed : nullptr);
 } FEC_ABI_CATCH_STATUS
 
+static int batch_double_mul(fec_ctx* ctx, Where w, int curve, const uint64_t* u1, const uint64_t* u2, const uint64_t* q, uint64_t* out, size_t n) {
+  const size_t pb = (size_t)plimbs(curve) * 8;
+  return call(ctx, w, n, 2, arg_if(!curve_ok(curve)),
+              arrays(input(u1, 32).aligned(16), input(u2, 32).aligned(16), input(q, pb).aligned(16), output(out, pb).aligned(16)),
+              [&](fec_ctx* c, auto... p) { return launch_double_mul(c, curve, p...); });
+}
 int fec_batch_double_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d1, const uint64_t* d2,
                              const uint64_t* dq, uint64_t* dout, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!d1 || !d2 || !dq || !dout))) return FEC_E_ARG;
-  if (!aligned16(d1) || !aligned16(d2) || !aligned16(dq) || !aligned16(dout)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_double_mul(ctx, curve, d1, d2, dq, dout, n, stream);
+  return batch_double_mul(ctx, on_device(stream), curve, d1, d2, dq, dout, n);
+} FEC_ABI_CATCH_STATUS
+int fec_batch_double_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* u1, const uint64_t* u2,
+                         const uint64_t* q, uint64_t* out, size_t n) try {
+  return batch_double_mul(ctx, kOnHost, curve, u1, u2, q, out, n);
 } FEC_ABI_CATCH_STATUS
 
 // ---- device-resident shards of a multi-device ctx (include/fecgpu.h: fec_multi_batch_*_dev) ----
@@ -1860,16 +1879,6 @@ int fec_multi_batch_double_mul_dev(fec_ctx* ctx, fec_curve curve, const uint64_t
                        });
 } FEC_ABI_CATCH_STATUS
 
-int fec_batch_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* points,
-                  uint64_t* out, size_t n) try {
-  if (!ctx || !curve_ok(curve) || (n && (!scalars || !points || !out))) return FEC_E_ARG;
-  const size_t pb = (size_t)plimbs(curve) * 8;
-  const HostArray a[] = {input(scalars, 32), input(points, pb), output(out, pb)};
-  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_mul(c, curve, false, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], m, s);
-  });
-} FEC_ABI_CATCH_STATUS
-
 int fec_batch_mul_fixed(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* base,
                         uint64_t* out, size_t n) try {
   if (!ctx || !curve_ok(curve) || !base || (n && (!scalars || !out))) return FEC_E_ARG;
@@ -1899,16 +1908,6 @@ int fec_batch_mul_fixed(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, 
   });
 } FEC_ABI_CATCH_STATUS
 
-int fec_batch_double_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* u1, const uint64_t* u2,
-                         const uint64_t* q, uint64_t* out, size_t n) try {
-  if (!ctx || !curve_ok(curve) || (n && (!u1 || !u2 || !q || !out))) return FEC_E_ARG;
-  const size_t pb = (size_t)plimbs(curve) * 8;
-  const HostArray a[] = {input(u1, 32), input(u2, 32), input(q, pb), output(out, pb)};
-  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_double_mul(c, curve, (const u64*)d[0], (const u64*)d[1], (const u64*)d[2], (u64*)d[3], m, s);
-  });
-} FEC_ABI_CATCH_STATUS
-
 int fec_multi_scalar_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* points,
                          uint64_t* out, size_t n) try {
   FEC_FIRST_DEVICE(ctx);
@@ -1916,74 +1915,63 @@ int fec_multi_scalar_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars,
   if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
   const size_t pb = (size_t)plimbs(curve) * 8;
   return drained(ctx, [&]() -> int {
-  int rc = ensure(ctx, 6, (n ? n : 1) * pb);   // products stay on the device
-  if (rc == FEC_OK) rc = ensure(ctx, 7, pb);
+  u64* d_products;   // they stay on the device
+  u32* d_sum;
+  WorkArea work, record;
+  work.add(d_products, (n ? n : 1) * pb);
+  record.add(d_sum, pb);
+  int rc = ensure(ctx, kStageOut, work.bytes());
+  if (rc == FEC_OK) rc = ensure(ctx, kStageBody, record.bytes());
   if (rc != FEC_OK) return rc;
+  work.place(ctx->d_buf[kStageOut]);
+  record.place(ctx->d_buf[kStageBody]);
   const size_t msm_chunk = pipeline_chunk(ctx);
   for (size_t lo = 0; lo < n; lo += msm_chunk) {  // the independent products, chunked
     const size_t cnt = lo + msm_chunk <= n ? msm_chunk : n - lo;
-    rc = ensure(ctx, 0, cnt * 32);
-    if (rc == FEC_OK) rc = ensure(ctx, 1, cnt * pb);
-    if (rc != FEC_OK) return rc;
-    if (hipMemcpyAsync(ctx->d_buf[0], scalars + lo * 4, cnt * 32, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(ctx->d_buf[1], points + lo * (pb / 8), cnt * pb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      return FEC_E_DEVICE;
-    rc = launch_mul(ctx, curve, false, (const u64*)ctx->d_buf[0], (const u64*)ctx->d_buf[1],
-                    (u64*)((char*)ctx->d_buf[6] + lo * pb), cnt, nullptr);
+    const u64 *d_scalars, *d_points;
+    rc = upload(ctx, kStageIn, cnt, ctx->stream, arrays(input(scalars + lo * 4, 32), input(points + lo * (pb / 8), pb)), d_scalars, d_points);
+    if (rc == FEC_OK) rc = launch_mul(ctx, curve, false, d_scalars, d_points, d_products + lo * (pb / 8), cnt, nullptr);
     if (rc != FEC_OK) return rc;
   }
   {
     Launch L(ctx, nullptr, "k_fold_sum");
     with_curve(curve, [&](auto c) {
       using C = decltype(c);
-      hipLaunchKernelGGL((k_fold_sum<C>), dim3(1), dim3(64), 0, L.s, (const u32*)ctx->d_buf[6], (u32*)ctx->d_buf[7], n);
+      hipLaunchKernelGGL((k_fold_sum<C>), dim3(1), dim3(64), 0, L.s, reinterpret_cast<const u32*>(d_products), d_sum, n);
     });
     rc = L.done();
     if (rc != FEC_OK) return rc;
   }
-  if (hipMemcpyAsync(out, ctx->d_buf[7], pb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
+  if (hipMemcpyAsync(out, d_sum, pb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
   return sync_and_check(ctx, ctx->stream);
   });
 } FEC_ABI_CATCH_STATUS
 
-namespace {
-int ecdsa_verify_dev(fec_ctx* ctx, int curve, const uint8_t* d_digests, const uint64_t* d_r, const uint64_t* d_s,
-                     const uint64_t* d_pk_xy, const uint8_t* d_pk_inf, uint8_t* d_status, size_t n, void* stream) {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_digests || !d_r || !d_s || !d_pk_xy || !d_status))) return FEC_E_ARG;
-  if (!aligned16(d_digests) || !aligned16(d_r) || !aligned16(d_s) || !aligned16(d_pk_xy)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_ecdsa_verify(ctx, curve, d_digests, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n, stream);
+static int ecdsa_verify(fec_ctx* ctx, Where w, int curve, const uint8_t* digests, const uint64_t* r, const uint64_t* s, const uint64_t* pk_xy,
+                        const uint8_t* pk_inf, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 2, FEC_OK,
+              arrays(input(digests, 32).aligned(16), input(r, 32).aligned(16), input(s, 32).aligned(16), input(pk_xy, 64).aligned(16),
+                     input(pk_inf, 1).opt(), output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_ecdsa_verify(c, curve, p...); });
 }
-
-int ecdsa_verify_host(fec_ctx* ctx, int curve, const uint8_t* digests, const uint64_t* r, const uint64_t* s,
-                      const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* status, size_t n) {
-  if (!ctx || (n && (!digests || !r || !s || !pk_xy || !status))) return FEC_E_ARG;
-  const HostArray a[] = {input(digests, 32), input(r, 32), input(s, 32), input(pk_xy, 64), input(pk_inf, 1), output(status, 1)};
-  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
-    return launch_ecdsa_verify(c, curve, (const unsigned char*)d[0], (const u64*)d[1], (const u64*)d[2], (const u64*)d[3],
-                               (const unsigned char*)d[4], (unsigned char*)d[5], m, st);
-  });
-}
-}  // namespace
 
 int fec_ecdsa_verify_secp256k1_dev(fec_ctx* ctx, const uint8_t* d_digests, const uint64_t* d_r, const uint64_t* d_s,
                                    const uint64_t* d_pk_xy, const uint8_t* d_pk_inf, uint8_t* d_status, size_t n,
                                    void* stream) try {
-  return ecdsa_verify_dev(ctx, FEC_SECP256K1, d_digests, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n, stream);
+  return ecdsa_verify(ctx, on_device(stream), FEC_SECP256K1, d_digests, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n);
 } FEC_ABI_CATCH_STATUS
 int fec_ecdsa_verify_secp256k1(fec_ctx* ctx, const uint8_t* digests, const uint64_t* r, const uint64_t* s,
                                const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* status, size_t n) try {
-  return ecdsa_verify_host(ctx, FEC_SECP256K1, digests, r, s, pk_xy, pk_inf, status, n);
+  return ecdsa_verify(ctx, kOnHost, FEC_SECP256K1, digests, r, s, pk_xy, pk_inf, status, n);
 } FEC_ABI_CATCH_STATUS
 int fec_ecdsa_verify_p256_dev(fec_ctx* ctx, const uint8_t* d_digests, const uint64_t* d_r, const uint64_t* d_s,
                               const uint64_t* d_pk_xy, const uint8_t* d_pk_inf, uint8_t* d_status, size_t n,
                               void* stream) try {
-  return ecdsa_verify_dev(ctx, FEC_P256, d_digests, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n, stream);
+  return ecdsa_verify(ctx, on_device(stream), FEC_P256, d_digests, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n);
 } FEC_ABI_CATCH_STATUS
 int fec_ecdsa_verify_p256(fec_ctx* ctx, const uint8_t* digests, const uint64_t* r, const uint64_t* s,
                           const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* status, size_t n) try {
-  return ecdsa_verify_host(ctx, FEC_P256, digests, r, s, pk_xy, pk_inf, status, n);
+  return ecdsa_verify(ctx, kOnHost, FEC_P256, digests, r, s, pk_xy, pk_inf, status, n);
 } FEC_ABI_CATCH_STATUS
 
 // Ecdsa::<C, D>::batch_verify (forge-ec-signature/src/ecdsa.rs:287-391), C = Secp256k1 / P256, with the digests
@@ -2007,28 +1995,27 @@ int fec_ecdsa_batch_verify(fec_ctx* ctx, fec_curve curve, const uint8_t* digests
   unsigned char res = 0;
   uint64_t det[16];
   return drained(ctx, [&]() -> int {
-  // slots: 0 digests, 1 r, 2 s, 3 pk, 4 a, 5 pk_inf, 6 work area (ecdsa_layout), 7 r_sum + detail + result
-  const void* hin[6] = {digests, r, s, pk_xy, a, pk_inf};
-  const size_t bytes[6] = {n * 32, n * 32, n * 32, n * 64, n * 32, n};
+  // the inputs; the verifier's work area (ecdsa_layout); the result record: r_sum, detail, result
+  const uint8_t *d_digests, *d_pk_inf;
+  const uint64_t *d_r, *d_s, *d_pk, *d_a;
   EcdsaWork w;
-  WorkArea area;
-  ecdsa_layout(area, w, n, true);
-  int rc = FEC_OK;
-  for (int i = 0; i < 6 && rc == FEC_OK; ++i)
-    if (hin[i]) rc = ensure(ctx, i, bytes[i]);
-  if (rc == FEC_OK) rc = ensure(ctx, 6, area.bytes());
-  if (rc == FEC_OK) rc = ensure(ctx, 7, 96 + 128 + 16);
+  u32 *d_r_sum, *d_detail;
+  unsigned char* d_result;
+  WorkArea work, record;
+  ecdsa_layout(work, w, n, true);
+  record.add(d_r_sum, 96).add(d_detail, 128).add(d_result, 1);
+  int rc = upload(ctx, kStageIn, n, ctx->stream,
+                  arrays(input(digests, 32), input(r, 32), input(s, 32), input(pk_xy, 64), input(a, 32), input(pk_inf, 1)), d_digests, d_r, d_s, d_pk,
+                  d_a, d_pk_inf);
+  if (rc == FEC_OK) rc = ensure(ctx, kStageOut, work.bytes());
+  if (rc == FEC_OK) rc = ensure(ctx, kStageBody, record.bytes());
   if (rc != FEC_OK) return rc;
-  for (int i = 0; i < 6; ++i)
-    if (hin[i] && hipMemcpyAsync(ctx->d_buf[i], hin[i], bytes[i], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      return FEC_E_DEVICE;
-  area.place(ctx->d_buf[6]);
-  char* tail = static_cast<char*>(ctx->d_buf[7]);
+  work.place(ctx->d_buf[kStageOut]);
+  record.place(ctx->d_buf[kStageBody]);
   {
     Launch L(ctx, nullptr, "k_ecdsa_pre");
-    ecdsa_pre_launch(curve, (const unsigned char*)ctx->d_buf[0], (const u32*)ctx->d_buf[1], (const u32*)ctx->d_buf[2],
-                     (const u32*)ctx->d_buf[3], pk_inf ? (const unsigned char*)ctx->d_buf[5] : nullptr, (const u32*)ctx->d_buf[4],
-                     w, n, L.s);
+    ecdsa_pre_launch(curve, d_digests, reinterpret_cast<const u32*>(d_r), reinterpret_cast<const u32*>(d_s), reinterpret_cast<const u32*>(d_pk),
+                     d_pk_inf, reinterpret_cast<const u32*>(d_a), w, n, L.s);
     rc = L.done();
     if (rc != FEC_OK) return rc;
   }
@@ -2050,14 +2037,14 @@ int fec_ecdsa_batch_verify(fec_ctx* ctx, fec_curve curve, const uint8_t* digests
     with_curve(curve, [&](auto c) {   // r_i = r1 + r2 (355), then r_sum += r_i in index order (358)
       using C = decltype(c);
       hipLaunchKernelGGL((k_point_op<C>), dim3(grid_for(n)), dim3(TPB), 0, L.s, (int)FEC_P_ADD, (const u32*)w.ta, (const u32*)w.tb, w.ta, n);
-      hipLaunchKernelGGL((k_fold_sum<C>), dim3(1), dim3(64), 0, L.s, (const u32*)w.ta, (u32*)tail, n);
+      hipLaunchKernelGGL((k_fold_sum<C>), dim3(1), dim3(64), 0, L.s, (const u32*)w.ta, d_r_sum, n);
     });
-    ecdsa_batch_finish_launch(curve, (const u32*)tail, w.ar, n, (unsigned char*)(tail + 96 + 128), (u32*)(tail + 96), L.s);
+    ecdsa_batch_finish_launch(curve, d_r_sum, w.ar, n, d_result, d_detail, L.s);
     rc = L.done();
     if (rc != FEC_OK) return rc;
   }
-  if (hipMemcpyAsync(&res, tail + 96 + 128, 1, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(det, tail + 96, 128, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+  if (hipMemcpyAsync(&res, d_result, 1, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipMemcpyAsync(det, d_detail, 128, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
     return FEC_E_DEVICE;
   if (int rc_sync = sync_and_check(ctx, ctx->stream)) return rc_sync;
   *result = res;
@@ -2066,204 +2053,176 @@ int fec_ecdsa_batch_verify(fec_ctx* ctx, fec_curve curve, const uint8_t* digests
   });
 } FEC_ABI_CATCH_STATUS
 
+static int batch_validate_point(fec_ctx* ctx, Where w, int curve, const uint64_t* xy, const uint8_t* inf, uint8_t* ok, size_t n) {
+  return call(ctx, w, n, 2, arg_if(!curve_ok(curve)), arrays(input(xy, 64).aligned(16), input(inf, 1).opt(), output(ok, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_validate(c, curve, p...); });
+}
 int fec_batch_validate_point_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_xy, const uint8_t* d_inf, uint8_t* d_ok,
                                  size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!d_xy || !d_ok))) return FEC_E_ARG;
-  if (!aligned16(d_xy)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_validate(ctx, curve, d_xy, d_inf, d_ok, n, stream);
+  return batch_validate_point(ctx, on_device(stream), curve, d_xy, d_inf, d_ok, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_batch_validate_point(fec_ctx* ctx, fec_curve curve, const uint64_t* xy, const uint8_t* inf, uint8_t* ok, size_t n) try {
-  if (!ctx || !curve_ok(curve) || (n && (!xy || !ok))) return FEC_E_ARG;
-  const HostArray a[] = {input(xy, 64), input(inf, 1), output(ok, 1)};
-  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_validate(c, curve, (const u64*)d[0], (const unsigned char*)d[1], (unsigned char*)d[2], m, s);
-  });
+  return batch_validate_point(ctx, kOnHost, curve, xy, inf, ok, n);
 } FEC_ABI_CATCH_STATUS
 
+// (the shared points sit in the stream's scratch: cleared with the staging on every way out.  Ed25519 has no KeyExchange impl.)
+static int batch_ecdh(fec_ctx* ctx, Where w, int curve, const uint64_t* private_keys, const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* secrets,
+                      uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, ecdsa_curves_only(curve),
+              arrays(secret_input(private_keys, 32).aligned(16), input(pk_xy, 64).aligned(16), input(pk_inf, 1).opt(),
+                     secret_output(secrets, 32).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_ecdh(c, curve, p...); });
+}
 int fec_batch_ecdh_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_keys, const uint64_t* d_pk_xy,
                        const uint8_t* d_pk_inf, uint8_t* d_secrets, uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_private_keys || !d_pk_xy || !d_secrets || !d_status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no KeyExchange impl
-  if (!aligned16(d_private_keys) || !aligned16(d_pk_xy) || !aligned16(d_secrets)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_ecdh(ctx, curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n, stream);
+  return batch_ecdh(ctx, on_device(stream), curve, d_private_keys, d_pk_xy, d_pk_inf, d_secrets, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_batch_ecdh(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys, const uint64_t* pk_xy, const uint8_t* pk_inf,
                    uint8_t* secrets, uint8_t* status, size_t n) try {
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
-  if (!ctx || (n && (!private_keys || !pk_xy || !secrets || !status))) return FEC_E_ARG;
-  // (the shared points sit in the stream's scratch: cleared with the staging on every way out)
-  const HostArray a[] = {secret_input(private_keys, 32), input(pk_xy, 64), input(pk_inf, 1), secret_output(secrets, 32),
-                         output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_ecdh(c, curve, (const u64*)d[0], (const u64*)d[1], (const unsigned char*)d[2], (unsigned char*)d[3],
-                       (unsigned char*)d[4], m, s);
-  });
+  if (const int rc = ecdsa_curves_only(curve)) return rc;   // (the host form tests the curve before the ctx)
+  return batch_ecdh(ctx, kOnHost, curve, private_keys, pk_xy, pk_inf, secrets, status, n);
 } FEC_ABI_CATCH_STATUS
 
 // ---- ECDH key derivation (fecgpu.h; hkdf.hpp) ----
-// The checks every form shares: the curve picks the function, the lengths are bounded so that info travels with the
-// launch and the u8 block counter of the reference never overflows.
-static int kdf_args(fec_ctx* ctx, int curve, const uint8_t* info, size_t info_len, size_t secret_len, size_t out_len) {
+// The checks every form shares, made before the arrays are looked at (a *_dev form: after the multi-device ctx is turned
+// away): the curve picks the function, the lengths are bounded so that info travels with the launch and the u8 block
+// counter of the reference never overflows.
+static int kdf_args(fec_ctx* ctx, Where w, int curve, const uint8_t* info, size_t info_len, size_t secret_len, size_t out_len) {
+  if (w.dev && is_multi(ctx)) return FEC_E_UNSUPPORTED;
   if (!ctx || !curve_ok(curve) || (info_len && !info)) return FEC_E_ARG;
   if (curve == FEC_ED25519) return FEC_E_UNSUPPORTED;   // Ed25519 has no KeyExchange impl
   if (secret_len > hkdf::MAX_SECRET || info_len > hkdf::MAX_INFO || out_len > hkdf::MAX_OUT) return FEC_E_UNSUPPORTED;
   return FEC_OK;
 }
 
+// (an array of zero-byte elements -- secret_len 0, out_len 0 -- is optional, and absent on the host)
+static int derive_key(fec_ctx* ctx, Where w, int curve, const uint8_t* secrets, size_t secret_len, const uint8_t* info, size_t info_len, size_t out_len,
+                      uint8_t* keys, size_t n) {
+  if (const int rc = kdf_args(ctx, w, curve, info, info_len, secret_len, out_len)) return rc;
+  if (!w.dev && out_len == 0) return n && secret_len && !secrets ? FEC_E_ARG : FEC_OK;   // (the host form: nothing to write)
+  const hkdf::Params p = hkdf::make_params(curve == FEC_P256, info, info_len, secret_len, out_len);
+  return call(ctx, w, n, 1, FEC_OK,
+              arrays(secret_input(secrets, secret_len).aligned(16).opt(!secret_len), secret_output(keys, out_len).aligned(16).opt(!out_len)),
+              [&](fec_ctx* c, const uint8_t* d_secrets, auto... q) { return launch_derive_key(c, curve, d_secrets, p, q...); });
+}
 int fec_derive_key_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_secrets, size_t secret_len, const uint8_t* info, size_t info_len,
                        size_t out_len, uint8_t* d_keys, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  const int rc = kdf_args(ctx, curve, info, info_len, secret_len, out_len);
-  if (rc != FEC_OK) return rc;
-  if (n && ((secret_len && !d_secrets) || (out_len && !d_keys))) return FEC_E_ARG;
-  if (!aligned16(d_secrets) || !aligned16(d_keys)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_derive_key(ctx, curve, d_secrets, hkdf::make_params(curve == FEC_P256, info, info_len, secret_len, out_len), d_keys, n, stream);
+  return derive_key(ctx, on_device(stream), curve, d_secrets, secret_len, info, info_len, out_len, d_keys, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_derive_key(fec_ctx* ctx, fec_curve curve, const uint8_t* secrets, size_t secret_len, const uint8_t* info, size_t info_len,
                    size_t out_len, uint8_t* keys, size_t n) try {
-  const int rc = kdf_args(ctx, curve, info, info_len, secret_len, out_len);
-  if (rc != FEC_OK) return rc;
-  if (n && ((secret_len && !secrets) || (out_len && !keys))) return FEC_E_ARG;
-  if (out_len == 0) return FEC_OK;
-  const hkdf::Params p = hkdf::make_params(curve == FEC_P256, info, info_len, secret_len, out_len);
-  // (an absent array -- secret_len 0 -- reaches the body as null)
-  const HostArray a[] = {secret_input(secret_len ? secrets : nullptr, secret_len), secret_output(keys, out_len)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_derive_key(c, curve, (const unsigned char*)d[0], p, (unsigned char*)d[1], m, s);
-  });
+  return derive_key(ctx, kOnHost, curve, secrets, secret_len, info, info_len, out_len, keys, n);
 } FEC_ABI_CATCH_STATUS
 
+// (the shared points sit in the stream's scratch: cleared with the staging on every way out)
+static int ecdh_derive_key(fec_ctx* ctx, Where w, int curve, const uint64_t* private_keys, const uint64_t* pk_xy, const uint8_t* pk_inf,
+                           const uint8_t* info, size_t info_len, size_t out_len, uint8_t* keys, uint8_t* status, size_t n) {
+  if (const int rc = kdf_args(ctx, w, curve, info, info_len, 32, out_len)) return rc;
+  const hkdf::Params p = hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len);
+  return call(ctx, w, n, 1, FEC_OK,
+              arrays(secret_input(private_keys, 32).aligned(16), input(pk_xy, 64).aligned(16), input(pk_inf, 1).opt(),
+                     secret_output(keys, out_len).aligned(16).opt(!out_len), output(status, 1)),
+              [&](fec_ctx* c, const uint64_t* d_sk, const uint64_t* d_pk, const uint8_t* d_inf, auto... q) {
+                return launch_ecdh_kdf(c, curve, d_sk, d_pk, d_inf, p, q...);
+              });
+}
 int fec_ecdh_derive_key_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_keys, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf,
                             const uint8_t* info, size_t info_len, size_t out_len, uint8_t* d_keys, uint8_t* d_status, size_t n,
                             void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  const int rc = kdf_args(ctx, curve, info, info_len, 32, out_len);
-  if (rc != FEC_OK) return rc;
-  if (n && (!d_private_keys || !d_pk_xy || !d_status || (out_len && !d_keys))) return FEC_E_ARG;
-  if (!aligned16(d_private_keys) || !aligned16(d_pk_xy) || !aligned16(d_keys)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_ecdh_kdf(ctx, curve, d_private_keys, d_pk_xy, d_pk_inf, hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len),
-                         d_keys, d_status, n, stream);
+  return ecdh_derive_key(ctx, on_device(stream), curve, d_private_keys, d_pk_xy, d_pk_inf, info, info_len, out_len, d_keys, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_ecdh_derive_key(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys, const uint64_t* pk_xy, const uint8_t* pk_inf,
                         const uint8_t* info, size_t info_len, size_t out_len, uint8_t* keys, uint8_t* status, size_t n) try {
-  const int rc = kdf_args(ctx, curve, info, info_len, 32, out_len);
-  if (rc != FEC_OK) return rc;
-  if (n && (!private_keys || !pk_xy || !status || (out_len && !keys))) return FEC_E_ARG;
-  const hkdf::Params p = hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len);
-  // (the shared points sit in the stream's scratch: cleared with the staging on every way out)
-  const HostArray a[] = {secret_input(private_keys, 32), input(pk_xy, 64), input(pk_inf, 1), secret_output(out_len ? keys : nullptr, out_len),
-                         output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_ecdh_kdf(c, curve, (const u64*)d[0], (const u64*)d[1], (const unsigned char*)d[2], p, (unsigned char*)d[3],
-                           (unsigned char*)d[4], m, s);
-  });
+  return ecdh_derive_key(ctx, kOnHost, curve, private_keys, pk_xy, pk_inf, info, info_len, out_len, keys, status, n);
 } FEC_ABI_CATCH_STATUS
 
+// (both products sit in the stream's scratch: cleared with the staging on every way out; the public key of a failed
+// exchange is never written, the one of a good exchange is public but staged beside the keys)
+static int ecdh_exchange(fec_ctx* ctx, Where w, int curve, const uint64_t* private_keys, const uint64_t* peer_xy, const uint8_t* peer_inf,
+                         const uint8_t* info, size_t info_len, size_t out_len, uint64_t* public_xy, uint8_t* public_inf, uint8_t* keys,
+                         uint8_t* status, size_t n) {
+  if (const int rc = kdf_args(ctx, w, curve, info, info_len, 32, out_len)) return rc;
+  const hkdf::Params p = hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len);
+  return call(ctx, w, n, 1, FEC_OK,
+              arrays(secret_input(private_keys, 32).aligned(16), input(peer_xy, 64).aligned(16), input(peer_inf, 1).opt(),
+                     secret_output(public_xy, 64).aligned(16), output(public_inf, 1), secret_output(keys, out_len).aligned(16).opt(!out_len),
+                     output(status, 1)),
+              [&](fec_ctx* c, const uint64_t* d_sk, const uint64_t* d_peer, const uint8_t* d_inf, auto... q) {
+                return launch_ecdh_exchange(c, curve, d_sk, d_peer, d_inf, p, q...);
+              });
+}
 int fec_ecdh_exchange_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_private_keys, const uint64_t* d_peer_xy, const uint8_t* d_peer_inf,
                           const uint8_t* info, size_t info_len, size_t out_len, uint64_t* d_public_xy, uint8_t* d_public_inf,
                           uint8_t* d_keys, uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  const int rc = kdf_args(ctx, curve, info, info_len, 32, out_len);
-  if (rc != FEC_OK) return rc;
-  if (n && (!d_private_keys || !d_peer_xy || !d_public_xy || !d_public_inf || !d_status || (out_len && !d_keys))) return FEC_E_ARG;
-  if (!aligned16(d_private_keys) || !aligned16(d_peer_xy) || !aligned16(d_public_xy) || !aligned16(d_keys)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_ecdh_exchange(ctx, curve, d_private_keys, d_peer_xy, d_peer_inf, hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len),
-                              d_public_xy, d_public_inf, d_keys, d_status, n, stream);
+  return ecdh_exchange(ctx, on_device(stream), curve, d_private_keys, d_peer_xy, d_peer_inf, info, info_len, out_len, d_public_xy, d_public_inf,
+                       d_keys, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_ecdh_exchange(fec_ctx* ctx, fec_curve curve, const uint64_t* private_keys, const uint64_t* peer_xy, const uint8_t* peer_inf,
                       const uint8_t* info, size_t info_len, size_t out_len, uint64_t* public_xy, uint8_t* public_inf, uint8_t* keys,
                       uint8_t* status, size_t n) try {
-  const int rc = kdf_args(ctx, curve, info, info_len, 32, out_len);
-  if (rc != FEC_OK) return rc;
-  if (n && (!private_keys || !peer_xy || !public_xy || !public_inf || !status || (out_len && !keys))) return FEC_E_ARG;
-  const hkdf::Params p = hkdf::make_params(curve == FEC_P256, info, info_len, 32, out_len);
-  // (both products sit in the stream's scratch: cleared with the staging on every way out; the public key of a failed
-  // exchange is never written, the one of a good exchange is public but staged beside the keys)
-  const HostArray a[] = {secret_input(private_keys, 32), input(peer_xy, 64), input(peer_inf, 1), secret_output(public_xy, 64),
-                         output(public_inf, 1), secret_output(out_len ? keys : nullptr, out_len), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_ecdh_exchange(c, curve, (const u64*)d[0], (const u64*)d[1], (const unsigned char*)d[2], p, (u64*)d[3],
-                                (unsigned char*)d[4], (unsigned char*)d[5], (unsigned char*)d[6], m, s);
-  });
+  return ecdh_exchange(ctx, kOnHost, curve, private_keys, peer_xy, peer_inf, info, info_len, out_len, public_xy, public_inf, keys, status, n);
 } FEC_ABI_CATCH_STATUS
 
+// (R = k * G sits in the stream's scratch: cleared with the staging on every way out.  Ed25519 has no Ecdsa instance.)
+static int ecdsa_sign(fec_ctx* ctx, Where w, int curve, const uint64_t* sk, const uint8_t* digests, const uint64_t* k, uint64_t* sig, uint8_t* status,
+                      size_t n) {
+  return call(ctx, w, n, 1, ecdsa_curves_only(curve),
+              arrays(secret_input(sk, 32).aligned(16), input(digests, 32).aligned(16), secret_input(k, 32).aligned(16), output(sig, 64).aligned(16),
+                     output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_ecdsa_sign(c, curve, p...); });
+}
 int fec_ecdsa_sign_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_digests, const uint64_t* d_k,
                        uint64_t* d_sig, uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_sk || !d_digests || !d_k || !d_sig || !d_status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
-  if (!aligned16(d_sk) || !aligned16(d_digests) || !aligned16(d_k) || !aligned16(d_sig)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_ecdsa_sign(ctx, curve, d_sk, d_digests, d_k, d_sig, d_status, n, stream);
+  return ecdsa_sign(ctx, on_device(stream), curve, d_sk, d_digests, d_k, d_sig, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_ecdsa_sign(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8_t* digests, const uint64_t* k, uint64_t* sig,
                    uint8_t* status, size_t n) try {
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
-  if (!ctx || (n && (!sk || !digests || !k || !sig || !status))) return FEC_E_ARG;
-  // (R = k * G sits in the stream's scratch: cleared with the staging on every way out)
-  const HostArray a[] = {secret_input(sk, 32), input(digests, 32), secret_input(k, 32), output(sig, 64), output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_ecdsa_sign(c, curve, (const u64*)d[0], (const unsigned char*)d[1], (const u64*)d[2], (u64*)d[3],
-                             (unsigned char*)d[4], m, s);
-  });
+  if (const int rc = ecdsa_curves_only(curve)) return rc;   // (the host form tests the curve before the ctx)
+  return ecdsa_sign(ctx, kOnHost, curve, sk, digests, k, sig, status, n);
 } FEC_ABI_CATCH_STATUS
 
+static int eddsa_verify_ed25519(fec_ctx* ctx, Where w, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy, const uint8_t* pk_inf,
+                                const uint64_t* s, const uint64_t* k, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 2, FEC_OK,
+              arrays(input(r_xy, 64).aligned(16), input(r_inf, 1).opt(), input(pk_xy, 64).aligned(16), input(pk_inf, 1).opt(), input(s, 32).aligned(16),
+                     input(k, 32).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_eddsa_verify(c, p...); });
+}
 int fec_eddsa_verify_ed25519_dev(fec_ctx* ctx, const uint64_t* d_r_xy, const uint8_t* d_r_inf, const uint64_t* d_pk_xy,
                                  const uint8_t* d_pk_inf, const uint64_t* d_s, const uint64_t* d_k, uint8_t* d_status,
                                  size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_r_xy || !d_pk_xy || !d_s || !d_k || !d_status))) return FEC_E_ARG;
-  if (!aligned16(d_r_xy) || !aligned16(d_pk_xy) || !aligned16(d_s) || !aligned16(d_k)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_eddsa_verify(ctx, d_r_xy, d_r_inf, d_pk_xy, d_pk_inf, d_s, d_k, d_status, n, stream);
+  return eddsa_verify_ed25519(ctx, on_device(stream), d_r_xy, d_r_inf, d_pk_xy, d_pk_inf, d_s, d_k, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_eddsa_verify_ed25519(fec_ctx* ctx, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy,
                              const uint8_t* pk_inf, const uint64_t* s, const uint64_t* k, uint8_t* status, size_t n) try {
-  if (!ctx || (n && (!r_xy || !pk_xy || !s || !k || !status))) return FEC_E_ARG;
-  const HostArray a[] = {input(r_xy, 64), input(r_inf, 1), input(pk_xy, 64), input(pk_inf, 1), input(s, 32), input(k, 32),
-                         output(status, 1)};
-  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
-    return launch_eddsa_verify(c, (const u64*)d[0], (const unsigned char*)d[1], (const u64*)d[2], (const unsigned char*)d[3],
-                               (const u64*)d[4], (const u64*)d[5], (unsigned char*)d[6], m, st);
-  });
+  return eddsa_verify_ed25519(ctx, kOnHost, r_xy, r_inf, pk_xy, pk_inf, s, k, status, n);
 } FEC_ABI_CATCH_STATUS
 
+static int schnorr_verify(fec_ctx* ctx, Where w, int curve, const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* r_xy, const uint8_t* r_inf,
+                          const uint64_t* s, const uint64_t* e, uint8_t* status, size_t n) {
+  return call(ctx, w, n, 1, arg_if(!curve_ok(curve)),
+              arrays(input(pk_xy, 64).aligned(16), input(pk_inf, 1).opt(), input(r_xy, 64).aligned(16), input(r_inf, 1).opt(), input(s, 32).aligned(16),
+                     input(e, 32).aligned(16), output(status, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_schnorr_verify(c, curve, p...); });
+}
 int fec_schnorr_verify_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf,
                            const uint64_t* d_r_xy, const uint8_t* d_r_inf, const uint64_t* d_s, const uint64_t* d_e,
                            uint8_t* d_status, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!d_pk_xy || !d_r_xy || !d_s || !d_e || !d_status))) return FEC_E_ARG;
-  if (!aligned16(d_pk_xy) || !aligned16(d_r_xy) || !aligned16(d_s) || !aligned16(d_e)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_schnorr_verify(ctx, curve, d_pk_xy, d_pk_inf, d_r_xy, d_r_inf, d_s, d_e, d_status, n, stream);
+  return schnorr_verify(ctx, on_device(stream), curve, d_pk_xy, d_pk_inf, d_r_xy, d_r_inf, d_s, d_e, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_schnorr_verify(fec_ctx* ctx, fec_curve curve, const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* r_xy,
                        const uint8_t* r_inf, const uint64_t* s, const uint64_t* e, uint8_t* status, size_t n) try {
-  if (!ctx || !curve_ok(curve) || (n && (!pk_xy || !r_xy || !s || !e || !status))) return FEC_E_ARG;
-  const HostArray a[] = {input(pk_xy, 64), input(pk_inf, 1), input(r_xy, 64), input(r_inf, 1), input(s, 32), input(e, 32),
-                         output(status, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) {
-    return launch_schnorr_verify(c, curve, (const u64*)d[0], (const unsigned char*)d[1], (const u64*)d[2],
-                                 (const unsigned char*)d[3], (const u64*)d[4], (const u64*)d[5], (unsigned char*)d[6], m, st);
-  });
+  return schnorr_verify(ctx, kOnHost, curve, pk_xy, pk_inf, r_xy, r_inf, s, e, status, n);
 } FEC_ABI_CATCH_STATUS
 
 namespace {
+// The flags of schnorr_batch_verify's result record on the device, cleared before the launches.
+struct SchnorrBatchFlags {
+  unsigned char flags[8];   // k_schnorr_fold_compare: the result, then the two sides' infinity flags
+  unsigned int done;        // ... and its arrival counter
+  unsigned int unused;
+  unsigned char wrapped;    // Ed25519: some s_i * a_i wrapped a u128 sum (k_schnorr_pre)
+};
 // schnorr::batch_verify::<C, D> (forge-ec-signature/src/schnorr.rs:194-290) for C = Secp256k1 / P256 / Ed25519
 int schnorr_batch_verify(fec_ctx* ctx, int curve, const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* r_xy,
                          const uint8_t* r_inf, const uint64_t* s, const uint64_t* a, const uint64_t* e, size_t n,
@@ -2283,25 +2242,26 @@ int schnorr_batch_verify(fec_ctx* ctx, int curve, const uint64_t* pk_xy, const u
   unsigned char flags[8] = {0};  // (host targets of the last copies: outside the drained scope, see fec_ecdsa_batch_verify)
   uint64_t sides[16];
   return drained(ctx, [&]() -> int {
-  // slots: 0 pk, 1 r, 2 s, 3 a, 4 e, 5 A terms, 6 B terms, 7 sums + affine sides + flags + counter
-  const size_t bytes[5] = {n * 64, n * 64, n * 32, n * 32, n * 32};
-  const void* src[5] = {pk_xy, r_xy, s, a, e};
-  int rc = FEC_OK;
-  for (int i = 0; i < 5 && rc == FEC_OK; ++i) rc = ensure(ctx, i, bytes[i]);
-  if (rc == FEC_OK) rc = ensure(ctx, 5, n * pb);
-  if (rc == FEC_OK) rc = ensure(ctx, 6, n * pb);
-  if (rc == FEC_OK) rc = ensure(ctx, 7, 2 * pb + 128 + 32);
+  // the inputs; the A and B terms; the result record: the two sums, the affine sides, the flags
+  const u32 *d_pk, *d_r, *d_s, *d_a, *d_e;
+  u32 *d_a_terms, *d_b_terms, *d_sums, *d_sides;
+  SchnorrBatchFlags* d_rec;
+  WorkArea work, record;
+  work.add(d_a_terms, n * pb).add(d_b_terms, n * pb);
+  record.add(d_sums, 2 * pb).add(d_sides, 128).add(d_rec, sizeof(SchnorrBatchFlags));
+  const auto words = [](const uint64_t* p) { return reinterpret_cast<const u32*>(p); };
+  int rc = upload(ctx, kStageIn, n, ctx->stream,
+                  arrays(input(words(pk_xy), 64), input(words(r_xy), 64), input(words(s), 32), input(words(a), 32), input(words(e), 32)), d_pk, d_r,
+                  d_s, d_a, d_e);
+  if (rc == FEC_OK) rc = ensure(ctx, kStageOut, work.bytes());
+  if (rc == FEC_OK) rc = ensure(ctx, kStageBody, record.bytes());
   if (rc != FEC_OK) return rc;
-  for (int i = 0; i < 5; ++i)
-    if (hipMemcpyAsync(ctx->d_buf[i], src[i], bytes[i], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      return FEC_E_DEVICE;
-  char* tail = (char*)ctx->d_buf[7];
-  u32* d_sums = (u32*)tail;
-  u32* d_sides = (u32*)(tail + 2 * pb);
-  unsigned char* d_flags = (unsigned char*)(tail + 2 * pb + 128);
-  unsigned int* d_done = (unsigned int*)(tail + 2 * pb + 128 + 8);
-  unsigned char* d_wrapped = (unsigned char*)(tail + 2 * pb + 128 + 16);   // Ed25519: some s_i * a_i wrapped a u128 sum
-  if (hipMemsetAsync(tail + 2 * pb + 128, 0, 32, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
+  work.place(ctx->d_buf[kStageOut]);
+  record.place(ctx->d_buf[kStageBody]);
+  unsigned char* d_flags = d_rec->flags;
+  unsigned int* d_done = &d_rec->done;
+  unsigned char* d_wrapped = &d_rec->wrapped;
+  if (hipMemsetAsync(d_rec, 0, sizeof(SchnorrBatchFlags), ctx->stream) != hipSuccess) return FEC_E_DEVICE;
   {
     // work area: s*a (32 n), from_affine(P), e*P, R + e*P (one point each), and the popcount-sort area of the Ed25519 table
     // kernel (n >= 2^16)
@@ -2316,10 +2276,9 @@ int schnorr_batch_verify(fec_ctx* ctx, int curve, const uint64_t* pk_xy, const u
                            : (edw ? "k_schnorr_pre + k_ed_fixed_base + k_ed_mul_pers x2 + k_schnorr_mid"
                                   : "k_schnorr_pre + k_p256_mul_sched x3 + k_schnorr_mid"));
     const dim3 g(grid_for(n)), b(TPB);
-    auto d = [&](int slot) { return static_cast<const u32*>(ctx->d_buf[slot]); };
     with_curve(curve, [&](auto c) {
       using C = decltype(c);
-      hipLaunchKernelGGL((k_schnorr_pre<C>), g, b, 0, L.s, d(0), d(2), d(3), sa, pp, edw ? d_wrapped : (unsigned char*)nullptr, n);
+      hipLaunchKernelGGL((k_schnorr_pre<C>), g, b, 0, L.s, d_pk, d_s, d_a, sa, pp, edw ? d_wrapped : (unsigned char*)nullptr, n);
     });
     // the A terms do not depend on the B chain: for the Weierstrass curves they run on the ctx's second stream beside it
     // (at the moderate n this entry point is meant for, a launch fills a fraction of the chip and is bound by one ladder's
@@ -2327,22 +2286,22 @@ int schnorr_batch_verify(fec_ctx* ctx, int curve, const uint64_t* pk_xy, const u
     // batch_verify::<Ed25519, D>): the same products one after the other on the ctx stream.
     SideStream side(ctx, L.s, n, edw ? 0 : SideStream::kSideStreamMax);
     const ProductEnvs env = product_envs(ctx, curve, n, side.active, kP256VarAffineMs + kP256VarMs);
-    fixed_product(ctx, env.fixed, curve, sa, reinterpret_cast<const u32*>(ctx->d_gen[curve]), (u32*)ctx->d_buf[5], n, sort,
+    fixed_product(ctx, env.fixed, curve, sa, reinterpret_cast<const u32*>(ctx->d_gen[curve]), d_a_terms, n, sort,
                   side.s);                                                                             // A_i (266-268)
-    var_product(env.var, curve, d(4), pp, ep, n, L.s);                                                 // e_i P_i (276)
+    var_product(env.var, curve, d_e, pp, ep, n, L.s);                                                 // e_i P_i (276)
     with_curve(curve, [&](auto c) {
       using C = decltype(c);
-      hipLaunchKernelGGL((k_schnorr_mid<C>), g, b, 0, L.s, d(1), (const u32*)ep, qq, n);
+      hipLaunchKernelGGL((k_schnorr_mid<C>), g, b, 0, L.s, d_r, (const u32*)ep, qq, n);
     });
-    var_product(env.var, curve, d(3), qq, (u32*)ctx->d_buf[6], n, L.s);                                // B_i (282)
+    var_product(env.var, curve, d_a, qq, d_b_terms, n, L.s);                                // B_i (282)
     side.join();
     rc = L.done();
     if (rc != FEC_OK) return rc;
   }
   with_curve(curve, [&](auto c) {
     using C = decltype(c);
-    hipLaunchKernelGGL((k_schnorr_fold_compare<C>), dim3(2), dim3(64), 0, ctx->stream, (const u32*)ctx->d_buf[5],
-                       (const u32*)ctx->d_buf[6], d_sums, d_sides, d_flags, d_done, n);
+    hipLaunchKernelGGL((k_schnorr_fold_compare<C>), dim3(2), dim3(64), 0, ctx->stream, (const u32*)d_a_terms,
+                       (const u32*)d_b_terms, d_sums, d_sides, d_flags, d_done, n);
   });
   if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
   if (hipMemcpyAsync(flags + 4, d_wrapped, 1, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
@@ -2380,34 +2339,28 @@ int fec_schnorr_batch_verify_ed25519(fec_ctx* ctx, const uint64_t* pk_xy, const 
                               debug_build_panics);
 } FEC_ABI_CATCH_STATUS
 
+static int batch_compress(fec_ctx* ctx, Where w, int curve, const uint64_t* xy, const uint8_t* inf, uint8_t* out, size_t n) {
+  return call(ctx, w, n, 1, arg_if(!curve_ok(curve)), arrays(input(xy, 64).aligned(16), input(inf, 1).opt(), output(out, 33).aligned(4)),
+              [&](fec_ctx* c, auto... p) { return launch_compress(c, curve, p...); });
+}
 int fec_batch_compress_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_xy, const uint8_t* d_inf,
                            uint8_t* d_out, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!d_xy || !d_out))) return FEC_E_ARG;
-  if (!aligned16(d_xy) || (reinterpret_cast<uintptr_t>(d_out) & 3u)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_compress(ctx, curve, d_xy, d_inf, d_out, n, stream);
+  return batch_compress(ctx, on_device(stream), curve, d_xy, d_inf, d_out, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_batch_compress(fec_ctx* ctx, fec_curve curve, const uint64_t* xy, const uint8_t* inf, uint8_t* out,
                        size_t n) try {
-  if (!ctx || !curve_ok(curve) || (n && (!xy || !out))) return FEC_E_ARG;
-  const HostArray a[] = {input(xy, 64), input(inf, 1), output(out, 33)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_compress(c, curve, (const u64*)d[0], (const unsigned char*)d[1], (unsigned char*)d[2], m, s);
-  });
+  return batch_compress(ctx, kOnHost, curve, xy, inf, out, n);
 } FEC_ABI_CATCH_STATUS
 
-// decode entry points: in (33 or 65 bytes per element) -> (xy, inf, ok)
+// decode entry points (host forms only): in (33 or 65 bytes per element) -> (xy, inf, ok)
 static int decode_host(fec_ctx* ctx, int op, fec_curve curve, const uint8_t* in, size_t in_stride, uint64_t* xy,
                        uint8_t* inf, uint8_t* ok, size_t n) {
-  if (!ctx || !curve_ok(curve) || (n && (!in || !xy || !inf || !ok))) return FEC_E_ARG;
-  const HostArray a[] = {input(in, in_stride), output(xy, 64), output(inf, 1), output(ok, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    Launch L(c, s, op == 0 ? "k_decompress" : "k_decode_uncompressed");
-    codec_launch(op, curve, d[0], nullptr, d[1], (unsigned char*)d[2], (unsigned char*)d[3], m, L.s);
-    return L.done();
-  });
+  return call(ctx, kOnHost, n, 1, arg_if(!curve_ok(curve)), arrays(input(in, in_stride), output(xy, 64), output(inf, 1), output(ok, 1)),
+              [&](fec_ctx* c, const uint8_t* d_in, uint64_t* d_xy, uint8_t* d_inf, uint8_t* d_ok, size_t m, void* s) {
+                Launch L(c, s, op == 0 ? "k_decompress" : "k_decode_uncompressed");
+                codec_launch(op, curve, d_in, nullptr, d_xy, d_inf, d_ok, m, L.s);
+                return L.done();
+              });
 }
 
 int fec_batch_decompress(fec_ctx* ctx, fec_curve curve, const uint8_t* in, uint64_t* xy, uint8_t* inf, uint8_t* ok,
@@ -2422,55 +2375,45 @@ int fec_batch_decode_uncompressed(fec_ctx* ctx, fec_curve curve, const uint8_t* 
 
 int fec_batch_encode_uncompressed(fec_ctx* ctx, fec_curve curve, const uint64_t* xy, const uint8_t* inf, uint8_t* out,
                                   size_t n) try {
-  if (!ctx || !curve_ok(curve) || (n && (!xy || !out))) return FEC_E_ARG;
-  const HostArray a[] = {input(xy, 64), input(inf, 1), output(out, 65)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    Launch L(c, s, "k_encode_uncompressed");
-    codec_launch(2, curve, d[0], d[1], d[2], nullptr, nullptr, m, L.s);
-    return L.done();
-  });
+  return call(ctx, kOnHost, n, 1, arg_if(!curve_ok(curve)), arrays(input(xy, 64), input(inf, 1).opt(), output(out, 65)),
+              [&](fec_ctx* c, const uint64_t* d_xy, const uint8_t* d_inf, uint8_t* d_out, size_t m, void* s) {
+                Launch L(c, s, "k_encode_uncompressed");
+                codec_launch(2, curve, d_xy, d_inf, d_out, nullptr, nullptr, m, L.s);
+                return L.done();
+              });
 } FEC_ABI_CATCH_STATUS
 
+static int batch_to_affine(fec_ctx* ctx, Where w, int curve, const uint64_t* points, uint64_t* xy, uint8_t* inf, size_t n) {
+  return call(ctx, w, n, 2, arg_if(!curve_ok(curve)),
+              arrays(input(points, (size_t)plimbs(curve) * 8).aligned(16), output(xy, 64).aligned(16), output(inf, 1)),
+              [&](fec_ctx* c, auto... p) { return launch_to_affine(c, curve, p...); });
+}
 int fec_batch_to_affine_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_points, uint64_t* d_xy,
                             uint8_t* d_inf, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!d_points || !d_xy || !d_inf))) return FEC_E_ARG;
-  if (!aligned16(d_points) || !aligned16(d_xy)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_to_affine(ctx, curve, d_points, d_xy, d_inf, n, stream);
+  return batch_to_affine(ctx, on_device(stream), curve, d_points, d_xy, d_inf, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_batch_to_affine(fec_ctx* ctx, fec_curve curve, const uint64_t* points, uint64_t* xy, uint8_t* inf,
                         size_t n) try {
-  if (!ctx || !curve_ok(curve) || (n && (!points || !xy || !inf))) return FEC_E_ARG;
-  const HostArray a[] = {input(points, (size_t)plimbs(curve) * 8), output(xy, 64), output(inf, 1)};
-  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_to_affine(c, curve, (const u64*)d[0], (u64*)d[1], (unsigned char*)d[2], m, s);
-  });
+  return batch_to_affine(ctx, kOnHost, curve, points, xy, inf, n);
 } FEC_ABI_CATCH_STATUS
 
+// (the single-element helpers have a host form only; b, or q, is an array of the call only where the op reads it)
 int fec_field_op(fec_ctx* ctx, fec_curve curve, fec_field_opcode op, const uint64_t* a, const uint64_t* b,
                  uint64_t* out, size_t n) try {
-  if (!ctx || !curve_ok(curve) || op < FEC_F_ADD || op > FEC_F_NEG || (n && (!a || !out))) return FEC_E_ARG;
   const bool binary = op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL;
-  if (binary && n && !b) return FEC_E_ARG;
-  const HostArray arr[] = {input(a, 32), input(binary ? b : nullptr, 32), output(out, 32)};
-  return host_call(ctx, n, arr, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_field(c, curve, op, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], m, s);
-  });
+  return call(ctx, kOnHost, n, 2, arg_if(!curve_ok(curve) || op < FEC_F_ADD || op > FEC_F_NEG),
+              arrays(input(a, 32), input(binary ? b : nullptr, 32).opt(!binary), output(out, 32)),
+              [&](fec_ctx* c, auto... p) { return launch_field(c, curve, op, p...); });
 } FEC_ABI_CATCH_STATUS
 
 int fec_point_op(fec_ctx* ctx, fec_curve curve, fec_point_opcode op, const uint64_t* p, const uint64_t* q,
                  uint64_t* out, size_t n) try {
-  if (!ctx || !curve_ok(curve) || op < FEC_P_ADD || op > FEC_P_DOUBLE_TRAIT || (n && (!p || !out)))
-    return FEC_E_ARG;
-  if (op == FEC_P_DOUBLE_TRAIT && curve != FEC_SECP256K1) return FEC_E_UNSUPPORTED;
-  if (op == FEC_P_ADD && n && !q) return FEC_E_ARG;
   const size_t pb = (size_t)plimbs(curve) * 8;
-  const HostArray a[] = {input(p, pb), input(op == FEC_P_ADD ? q : nullptr, pb), output(out, pb)};
-  return host_call(ctx, n, a, 2, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_point(c, curve, op, (const u64*)d[0], (const u64*)d[1], (u64*)d[2], m, s);
-  });
+  return call(ctx, kOnHost, n, 2,
+              first_of(arg_if(!curve_ok(curve) || op < FEC_P_ADD || op > FEC_P_DOUBLE_TRAIT),
+                       op == FEC_P_DOUBLE_TRAIT && curve != FEC_SECP256K1 ? FEC_E_UNSUPPORTED : FEC_OK),
+              arrays(input(p, pb), input(op == FEC_P_ADD ? q : nullptr, pb).opt(op != FEC_P_ADD), output(out, pb)),
+              [&](fec_ctx* c, auto... a) { return launch_point(c, curve, op, a...); });
 } FEC_ABI_CATCH_STATUS
 
 int fec_generator(fec_ctx* ctx, fec_curve curve, uint64_t* out) try {
@@ -2667,9 +2610,9 @@ int fec_measure_peak_mad32(fec_ctx* ctx, double* mad32_per_sec) try {
   if (!ctx || !mad32_per_sec) return FEC_E_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
   const int blocks = ctx->prop.multiProcessorCount * 8;  // 8 wavefronts per SIMD
-  int rc = ensure(ctx, 3, (size_t)blocks * TPB * sizeof(u32));
+  int rc = ensure(ctx, kStageBody + 1, (size_t)blocks * TPB * sizeof(u32));
   if (rc != FEC_OK) return rc;
-  u32* out = (u32*)ctx->d_buf[3];
+  u32* out = (u32*)ctx->d_buf[kStageBody + 1];
   double best = 0;
   for (int rep = 0; rep < 4; ++rep) {  // first rep warms up
     (void)hipEventRecord(ctx->ev0, ctx->stream);
@@ -2698,49 +2641,42 @@ int fec_ctx_device_info(fec_ctx* ctx, char* name, size_t name_len, int* compute_
 
 // ---- Curve25519 (kernels_x25519.hip; helpers above the extern "C" block) ----
 
+static int x25519(fec_ctx* ctx, Where w, const uint8_t* scalars, const uint8_t* u, uint8_t* out, size_t n) {
+  return call(ctx, w, n, 1, FEC_OK, arrays(secret_input(scalars, 32).aligned(16), input(u, 32).aligned(16), secret_output(out, 32).aligned(16)),
+              [&](fec_ctx* c, const uint8_t* d_s, const uint8_t* d_u, uint8_t* d_out, size_t m, void* s) {
+                return launch_x25519(c, reinterpret_cast<const u32*>(d_s), reinterpret_cast<const u32*>(d_u), reinterpret_cast<u32*>(d_out), m, s);
+              });
+}
 int fec_x25519_dev(fec_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_u, uint8_t* d_out, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || (n && (!d_scalars || !d_u || !d_out))) return FEC_E_ARG;
-  if (!aligned16(d_scalars) || !aligned16(d_u) || !aligned16(d_out)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_x25519(ctx, (const u32*)d_scalars, (const u32*)d_u, (u32*)d_out, n, stream);
+  return x25519(ctx, on_device(stream), d_scalars, d_u, d_out, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_x25519(fec_ctx* ctx, const uint8_t* scalars, const uint8_t* u, uint8_t* out, size_t n) try {
-  if (!ctx || (n && (!scalars || !u || !out))) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(scalars, 32), input(u, 32), secret_output(out, 32)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_x25519(c, (const u32*)d[0], (const u32*)d[1], (u32*)d[2], m, s);
-  });
+  return x25519(ctx, kOnHost, scalars, u, out, n);
 } FEC_ABI_CATCH_STATUS
 
+static int curve25519_mul(fec_ctx* ctx, Where w, const uint64_t* scalars, const uint64_t* points, uint64_t* out, size_t n) {
+  return call(ctx, w, n, 1, FEC_OK, arrays(secret_input(scalars, 32).aligned(16), input(points, 64).aligned(16), secret_output(out, 64).aligned(16)),
+              [&](fec_ctx* c, const uint64_t* d_s, const uint64_t* d_p, uint64_t* d_out, size_t m, void* s) {
+                return launch_curve25519_mul(c, reinterpret_cast<const u32*>(d_s), reinterpret_cast<const u32*>(d_p), reinterpret_cast<u32*>(d_out), m, s);
+              });
+}
 int fec_curve25519_mul_dev(fec_ctx* ctx, const uint64_t* d_scalars, const uint64_t* d_points, uint64_t* d_out, size_t n,
                            void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;
-  if (!ctx || (n && (!d_scalars || !d_points || !d_out))) return FEC_E_ARG;
-  if (!aligned16(d_scalars) || !aligned16(d_points) || !aligned16(d_out)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_curve25519_mul(ctx, (const u32*)d_scalars, (const u32*)d_points, (u32*)d_out, n, stream);
+  return curve25519_mul(ctx, on_device(stream), d_scalars, d_points, d_out, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_curve25519_mul(fec_ctx* ctx, const uint64_t* scalars, const uint64_t* points, uint64_t* out, size_t n) try {
-  if (!ctx || (n && (!scalars || !points || !out))) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(scalars, 32), input(points, 64), secret_output(out, 64)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_curve25519_mul(c, (const u32*)d[0], (const u32*)d[1], (u32*)d[2], m, s);
-  });
+  return curve25519_mul(ctx, kOnHost, scalars, points, out, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_curve25519_field_op(fec_ctx* ctx, fec_field_opcode op, const uint64_t* a, const uint64_t* b, uint64_t* out,
                             size_t n) try {
   const bool binary = op == FEC_F_ADD || op == FEC_F_SUB || op == FEC_F_MUL;
-  if (!ctx || op < FEC_F_ADD || op > FEC_F_NEG || (n && (!a || !out || (binary && !b)))) return FEC_E_ARG;
-  const HostArray arr[] = {input(a, 32), input(binary ? b : nullptr, 32), output(out, 32)};
-  return host_call(ctx, n, arr, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    Launch L(c, s, "k_x25519_field_op");
-    x25519_field_launch((int)op, (const u32*)d[0], (const u32*)d[1], (u32*)d[2], m, L.s);
-    return L.done();
-  });
+  return call(ctx, kOnHost, n, 1, arg_if(op < FEC_F_ADD || op > FEC_F_NEG), arrays(input(a, 32), input(binary ? b : nullptr, 32).opt(!binary), output(out, 32)),
+              [&](fec_ctx* c, const uint64_t* x, const uint64_t* y, uint64_t* o, size_t m, void* s) {
+                Launch L(c, s, "k_x25519_field_op");
+                x25519_field_launch((int)op, reinterpret_cast<const u32*>(x), reinterpret_cast<const u32*>(y), reinterpret_cast<u32*>(o), m, L.s);
+                return L.done();
+              });
 } FEC_ABI_CATCH_STATUS
 
 // ---- EdDSA signing for Ed25519 with SHA-512, and SHA-512 (kernels_eddsa.hip; helpers above the extern "C" block) ----
@@ -2877,19 +2813,17 @@ int fec_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const
   return ecdsa_sign_msg_dev(ctx, curve, true, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
+static int scalar_from_bytes_reduced(fec_ctx* ctx, Where w, int curve, const uint8_t* bytes, uint64_t* out, size_t n) {
+  return call(ctx, w, n, 1, arg_if(!curve_ok(curve)), arrays(input(bytes, 32).aligned(16), output(out, 32).aligned(16)),
+              [&](fec_ctx* c, const uint8_t* d_bytes, uint64_t* d_out, size_t m, void* s) {
+                return launch_from_bytes_reduced(c, curve, reinterpret_cast<const u32*>(d_bytes), reinterpret_cast<u32*>(d_out), m, s);
+              });
+}
 int fec_scalar_from_bytes_reduced(fec_ctx* ctx, fec_curve curve, const uint8_t* bytes, uint64_t* out, size_t n) try {
-  if (!ctx || !curve_ok(curve) || (n && (!bytes || !out))) return FEC_E_ARG;
-  const HostArray a[] = {input(bytes, 32), output(out, 32)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_from_bytes_reduced(c, curve, static_cast<const u32*>(d[0]), static_cast<u32*>(d[1]), m, s);
-  });
+  return scalar_from_bytes_reduced(ctx, kOnHost, curve, bytes, out, n);
 } FEC_ABI_CATCH_STATUS
 int fec_scalar_from_bytes_reduced_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_bytes, uint64_t* d_out, size_t n, void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!d_bytes || !d_out))) return FEC_E_ARG;
-  if (!aligned16(d_bytes) || !aligned16(d_out)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_from_bytes_reduced(ctx, curve, reinterpret_cast<const u32*>(d_bytes), reinterpret_cast<u32*>(d_out), n, stream);
+  return scalar_from_bytes_reduced(ctx, on_device(stream), curve, d_bytes, d_out, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_schnorr_challenge(fec_ctx* ctx, fec_curve curve, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy,
@@ -2970,25 +2904,21 @@ int fec_hash_to_field_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, 
   return launch_h2c(ctx, c, m, d_u, nullptr, nullptr, nullptr, d_status, n, stream);
 } FEC_ABI_CATCH_STATUS
 
+static int map_to_curve(fec_ctx* ctx, Where w, int curve, const uint64_t* u, uint64_t* xy, uint64_t* cand, uint8_t* legs, size_t n) {
+  return call(ctx, w, n, 1, first_of(arg_if(!curve_ok(curve)), curve == FEC_ED25519 ? FEC_E_UNSUPPORTED : FEC_OK),
+              arrays(secret_input(u, 32).aligned(16), secret_output(xy, 64).aligned(16), secret_output(cand, 64).aligned(16).opt(),
+                     secret_output(legs, 1).opt()),
+              [&](fec_ctx* c, const uint64_t* d_u, uint64_t* d_xy, uint64_t* d_cand, uint8_t* d_legs, size_t m, void* s) {
+                return launch_map_to_curve(c, curve, reinterpret_cast<const u32*>(d_u), reinterpret_cast<u32*>(d_xy), reinterpret_cast<u32*>(d_cand),
+                                           d_legs, m, s);
+              });
+}
 int fec_map_to_curve(fec_ctx* ctx, fec_curve curve, const uint64_t* u, uint64_t* xy, uint64_t* cand, uint8_t* legs, size_t n) try {
-  if (!ctx || !curve_ok(curve) || (n && (!u || !xy))) return FEC_E_ARG;
-  if (curve == FEC_ED25519) return FEC_E_UNSUPPORTED;
-  const HostArray a[] = {secret_input(u, 32), secret_output(xy, 64), secret_output(cand, 64), secret_output(legs, 1)};
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
-    return launch_map_to_curve(c, curve, static_cast<const u32*>(d[0]), static_cast<u32*>(d[1]), static_cast<u32*>(d[2]),
-                               static_cast<unsigned char*>(d[3]), m, s);
-  });
+  return map_to_curve(ctx, kOnHost, curve, u, xy, cand, legs, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_map_to_curve_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_u, uint64_t* d_xy, uint64_t* d_cand, uint8_t* d_legs, size_t n,
                          void* stream) try {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;  // device pointers belong to one device
-  if (!ctx || !curve_ok(curve) || (n && (!d_u || !d_xy))) return FEC_E_ARG;
-  if (curve == FEC_ED25519) return FEC_E_UNSUPPORTED;
-  if (!aligned16(d_u) || !aligned16(d_xy) || !aligned16(d_cand)) return FEC_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
-  return launch_map_to_curve(ctx, curve, reinterpret_cast<const u32*>(d_u), reinterpret_cast<u32*>(d_xy), reinterpret_cast<u32*>(d_cand),
-                             d_legs, n, stream);
+  return map_to_curve(ctx, on_device(stream), curve, d_u, d_xy, d_cand, d_legs, n);
 } FEC_ABI_CATCH_STATUS
 
 int fec_hash_to_curve(fec_ctx* ctx, fec_curve curve, int mode, int method, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,

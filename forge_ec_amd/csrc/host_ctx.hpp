@@ -7,6 +7,8 @@
 #include <cstring>
 #include <functional>
 #include <new>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/fecgpu.h"
@@ -24,7 +26,8 @@ struct fec_ctx {
   // device staging for the host-pointer entry points (host::chunked): lane 0 packs a chunk's inputs into slot 0 and its
   // outputs into slot 1 (one region per array, each on a 256-byte boundary); slots 2 and 3 are the body's own, for
   // ragged data (the message calls: message bytes, rebased offsets); lane 1 (the second stream) uses slots 4 and 5.
-  // The calls that stage a whole batch at once (fec_multi_scalar_mul, the batch_verify calls) take slots as they need.
+  // The calls that stage a whole batch at once (fec_multi_scalar_mul, the batch_verify calls) use lane 0's slots: their inputs
+  // laid out on slot 0 (host::upload), their work on slot 1, the result record they read back on slot 2.
   void* d_buf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t d_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hipStream_t stream2 = nullptr;
@@ -393,12 +396,30 @@ struct HostArray {
   bool secret;
   bool staged;      // false: the body reads it from the host itself (ragged data), at the chunk's first element
 };
-inline HostArray input(const void* p, size_t stride) { return {p, stride, 0, false, false, true}; }
-inline HostArray secret_input(const void* p, size_t stride) { return {p, stride, 0, false, true, true}; }
-inline HostArray shared_input(const void* p, size_t bytes) { return {p, 0, bytes, false, false, true}; }
-inline HostArray output(void* p, size_t stride) { return {p, stride, 0, true, false, true}; }
-inline HostArray secret_output(void* p, size_t stride) { return {p, stride, 0, true, true, true}; }
-inline HostArray ragged(const void* p, size_t stride) { return {p, stride, 0, false, false, false}; }
+// One array of a call as its entry point names it: what the staging needs (HostArray), the static type of the pointer, and
+// what the *_dev form checks -- the boundary the device pointer must sit on (0: none; 4, 8, 16; may be a run-time value,
+// as in out_len == 32 ? 16 : 0) and whether the array may be absent (null) when n != 0.  An array of zero-byte elements is
+// absent on the host.
+template <class T>
+struct Array {
+  T* ptr;
+  size_t stride, bytes;
+  bool out, secret, staged;
+  unsigned align;
+  bool optional;
+  Array aligned(unsigned a) const { return {ptr, stride, bytes, out, secret, staged, a, optional}; }
+  Array opt(bool yes = true) const { return {ptr, stride, bytes, out, secret, staged, align, yes}; }
+  operator HostArray() const { return {stride || bytes ? ptr : nullptr, stride, bytes, out, secret, staged}; }
+  bool missing() const { return !ptr && !optional; }
+  bool misaligned() const { return align && (reinterpret_cast<uintptr_t>(ptr) & (align - 1u)); }
+};
+template <class T> Array<const T> input(const T* p, size_t stride) { return {p, stride, 0, false, false, true, 0, false}; }
+template <class T> Array<const T> secret_input(const T* p, size_t stride) { return {p, stride, 0, false, true, true, 0, false}; }
+template <class T> Array<const T> shared_input(const T* p, size_t bytes) { return {p, 0, bytes, false, false, true, 0, false}; }
+template <class T> Array<const T> shared_secret_input(const T* p, size_t bytes) { return {p, 0, bytes, false, true, true, 0, false}; }
+template <class T> Array<T> output(T* p, size_t stride) { return {p, stride, 0, true, false, true, 0, false}; }
+template <class T> Array<T> secret_output(T* p, size_t stride) { return {p, stride, 0, true, true, true, 0, false}; }
+template <class T> Array<const T> ragged(const T* p, size_t stride) { return {p, stride, 0, false, false, false, 0, false}; }
 inline const void* element(const HostArray& a, size_t i) {
   return a.ptr && a.stride ? static_cast<const char*>(a.ptr) + i * a.stride : a.ptr;
 }
@@ -517,6 +538,69 @@ int chunked(fec_ctx* ctx, size_t n, const HostArray (&a)[N], int lanes, F body) 
 template <size_t N, class F>
 int host_call(fec_ctx* ctx, size_t n, const HostArray (&a)[N], int lanes, F body) {
   return sharded(ctx, n, a, [&](fec_ctx* c, const HostArray (&s)[N], size_t cnt, size_t) { return chunked(c, cnt, s, lanes, body); });
+}
+
+// ---- one typed argument list per entry point, for its host form and its *_dev form ----
+//
+// What every *_dev form starts with: device pointers belong to one device, which becomes the current one.
+inline int dev_enter(fec_ctx* ctx) {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;
+  if (!ctx) return FEC_E_ARG;
+  return hipSetDevice(ctx->device) == hipSuccess ? FEC_OK : FEC_E_DEVICE;
+}
+// Where a call's arrays live: in host memory (the synchronous form), or on the ctx's device with the caller's stream (the
+// enqueue-only *_dev form).
+struct Where {
+  bool dev;
+  void* stream;
+};
+constexpr Where kOnHost{false, nullptr};
+inline Where on_device(void* stream) { return {true, stream}; }
+
+template <class... T>
+std::tuple<Array<T>...> arrays(const Array<T>&... a) { return std::tuple<Array<T>...>(a...); }
+
+// Whole arrays of n elements onto the device: one region each of staging slot `slot`, filled on stream s; dev... receive
+// the device pointers, in the arrays' types (null for an absent array).
+template <class... T>
+int upload(fec_ctx* ctx, int slot, size_t n, hipStream_t s, const std::tuple<Array<T>...>& list, T*&... dev) {
+  return std::apply([&](const Array<T>&... a) -> int {
+    WorkArea area;
+    (area.add(dev, a.ptr ? n * a.stride : 0), ...);
+    const int rc = ensure(ctx, slot, area.bytes());
+    if (rc != FEC_OK) return rc;
+    area.place(ctx->d_buf[slot]);
+    const bool ok = ((!a.ptr || hipMemcpyAsync(const_cast<void*>(static_cast<const void*>(dev)), a.ptr, n * a.stride, hipMemcpyHostToDevice, s) == hipSuccess) && ...);
+    return ok ? FEC_OK : FEC_E_DEVICE;
+  }, list);
+}
+
+template <class... T, class F, size_t... I>
+int typed_chunk(F& body, fec_ctx* c, void* const* d, size_t m, hipStream_t s, std::index_sequence<I...>) {
+  return body(c, static_cast<T*>(d[I])..., m, static_cast<void*>(s));
+}
+
+// An element-wise entry point, either form.  The checks, in this order: the ctx (*_dev: dev_enter); a required array that
+// is null while n != 0; `value_rc`, the status of the call's value checks (curve, lengths, flags: computed by the caller,
+// reported here); *_dev: the alignments, whatever n is.  Then body(ctx, pointers..., count, stream) with the pointers in
+// the types the descriptors were given: once with the caller's device pointers and stream, or per chunk with the staged
+// copies (host_call).  The *_dev path allocates nothing.
+template <class... T, class F>
+int call(fec_ctx* ctx, Where w, size_t n, int lanes, int value_rc, const std::tuple<Array<T>...>& list, F body) {
+  return std::apply([&](const Array<T>&... a) -> int {
+    if (w.dev) {
+      if (const int rc = dev_enter(ctx)) return rc;
+    } else if (!ctx) {
+      return FEC_E_ARG;
+    }
+    if (n && (a.missing() || ...)) return FEC_E_ARG;
+    if (value_rc != FEC_OK) return value_rc;
+    if (w.dev) return (a.misaligned() || ...) ? FEC_E_ARG : body(ctx, a.ptr..., n, w.stream);
+    const HostArray h[] = {a...};
+    return host_call(ctx, n, h, lanes, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t s) {
+      return typed_chunk<T...>(body, c, d, m, s, std::index_sequence_for<T...>{});
+    });
+  }, list);
 }
 
 }  // namespace host

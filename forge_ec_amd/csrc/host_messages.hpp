@@ -48,12 +48,6 @@ int with_messages(fec_ctx* ctx, size_t n, const HostArray (&a)[N], const uint8_t
     });
   });
 }
-// What every *_dev form starts with: device pointers belong to one device, which becomes the current one.
-inline int dev_enter(fec_ctx* ctx) {
-  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;
-  if (!ctx) return FEC_E_ARG;
-  return hipSetDevice(ctx->device) == hipSuccess ? FEC_OK : FEC_E_DEVICE;
-}
 // The message arrays of a *_dev form, whose layout nobody checks (each lane checks its own range): 0, or what is wrong
 // with the pointers -- both FEC_E_ARG, apart only because some forms test the curve between the two.
 enum { kDevMsgsNull = 1, kDevMsgsMisaligned = 2 };
@@ -61,6 +55,38 @@ inline int dev_messages(const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t
   m = Messages{d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len};
   if ((n && !d_msg_off) || (msg_len && !d_msgs)) return kDevMsgsNull;
   return (reinterpret_cast<uintptr_t>(d_msg_off) & 7u) ? kDevMsgsMisaligned : 0;
+}
+// The messages of a call as its entry point names them.
+struct MessageArgs {
+  const uint8_t* msgs;
+  const uint64_t* off;
+  size_t len;
+};
+template <class... T, class F, size_t... I>
+int typed_message_chunk(F& body, fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t s, std::index_sequence<I...>) {
+  return body(c, m, static_cast<T*>(d[I + 1])..., cnt, static_cast<void*>(s));
+}
+// host_ctx.hpp's call for an entry point that takes messages, either form: body(ctx, messages, pointers..., count, stream).
+// *_dev: null message pointers are reported with the null arrays, misaligned offsets with the misaligned arrays, so
+// `value_rc` sits between the two.  Host: with_messages checks the layout, after everything else.
+template <class... T, class F>
+int message_call(fec_ctx* ctx, Where w, size_t n, int value_rc, const MessageArgs& ma, const std::tuple<Array<T>...>& list, F body) {
+  return std::apply([&](const Array<T>&... a) -> int {
+    if (w.dev) {
+      if (const int rc = dev_enter(ctx)) return rc;
+      Messages m;
+      const int bad = dev_messages(ma.msgs, ma.off, ma.len, n, m);
+      if (bad == kDevMsgsNull || (n && (a.missing() || ...))) return FEC_E_ARG;
+      if (value_rc != FEC_OK) return value_rc;
+      return bad || (a.misaligned() || ...) ? FEC_E_ARG : body(ctx, m, a.ptr..., n, w.stream);
+    }
+    if (!ctx || (n && (a.missing() || ...))) return FEC_E_ARG;
+    if (value_rc != FEC_OK) return value_rc;
+    const HostArray h[] = {ragged(ma.off, 8), a...};
+    return with_messages(ctx, n, h, ma.msgs, ma.off, ma.len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t s) {
+      return typed_message_chunk<T...>(body, c, d, m, cnt, s, std::index_sequence_for<T...>{});
+    });
+  }, list);
 }
 
 }  // namespace host

@@ -18,12 +18,12 @@ import os
 import numpy as np
 import pytest
 
+from abi_arg_table import DST, arr as _arr, run_table
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "msg_arg_codes.json")
-N = 8
-DST = b"forge-ec msg args dst"
 
 
 # ---- the all-empty batch ----
@@ -128,16 +128,10 @@ def test_empty_batch_expand_message_xmd(gpu_ctx, null_msgs):
 
 
 # ---- the return-code table ----
-# An entry point is a list of arguments: "ctx", "curve", the message triple "msgs" / "off" / "len", "dst" / "dst_len",
-# ("val", v) for a plain integer, "n", "stream" (NULL), and arrays (name, bytes per element, required).  A *_dev form
-# wants every array of 32 bytes per element or more on a 16-byte boundary.
+# (abi_arg_table.py: what an entry point's argument list says, the cases made from it, run_table)
 M = ["msgs", "off", "len"]
 D = ["dst", "dst_len"]
 ORDER_2_255 = ("order", [0, 0, 0, 1 << 63])
-
-
-def _arr(name, stride, required=True):
-    return (name, stride, required)
 
 
 HOST = {
@@ -178,129 +172,12 @@ for _name in ("fec_ed25519_sign", "fec_ed25519_derive_public_key", "fec_eddsa_si
     DEV[_name + "_dev"] = HOST[_name] + ["stream"]
 
 
-class _Buffers:
-    """One real buffer per argument, host and device: arrays of N elements (zeros) with 16 bytes to spare, messages of 5 bytes."""
-
-    def __init__(self):
-        import torch
-        self.torch = torch
-        self.keep, self.cache = [], {}
-        self.good = np.arange(0, 5 * N + 1, 5, dtype=np.uint64)
-        self.dst = np.frombuffer(DST, dtype=np.uint8).copy()
-
-    def host(self, a):
-        a = np.ascontiguousarray(a)
-        self.keep.append(a)
-        return a.ctypes.data
-
-    def dev(self, a):
-        t = self.torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(self.torch.device("cuda:0"))
-        self.keep.append(t)
-        return t.data_ptr()
-
-    def zeros(self, nbytes, dev):
-        """(cached: no case changes what a buffer holds)"""
-        if (nbytes, dev) not in self.cache:
-            a = np.zeros(nbytes, dtype=np.uint8)
-            self.cache[(nbytes, dev)] = self.dev(a) if dev else self.host(a)
-        return self.cache[(nbytes, dev)]
-
-    def put(self, a, dev):
-        return self.dev(a) if dev else self.host(a)
-
-
-def _call_args(spec, dev, buf, ctx, spoil):
-    """The argument tuple of one case.  `spoil` maps an argument name to what replaces it: None, "+4" / "+8" (the pointer
-    moved), an offsets array, or a value ("ctx", "curve", "len", "n")."""
-    out = []
-    for arg in spec:
-        name = arg if isinstance(arg, str) else arg[0]
-        if name == "ctx":
-            v = ctx
-        elif name == "curve":
-            v = 0
-        elif name == "msgs":
-            v = buf.zeros(5 * N + 16, dev)
-        elif name == "off":
-            o = spoil.get("off")
-            v = buf.put(np.concatenate([o if isinstance(o, np.ndarray) else buf.good, np.zeros(2, dtype=np.uint64)]), dev)
-        elif name == "len":
-            v = 5 * N
-        elif name == "dst":
-            v = buf.host(buf.dst)
-        elif name == "dst_len":
-            v = len(DST)
-        elif name == "val":
-            v = arg[1]
-        elif name == "order":
-            v = buf.host(np.array(arg[1], dtype=np.uint64))
-        elif name == "n":
-            v = N
-        elif name == "stream":
-            v = None
-        else:
-            v = buf.zeros(arg[1] * N + 16, dev)
-        if name in spoil and not isinstance(spoil[name], np.ndarray):
-            s = spoil[name]
-            v = v + int(s) if isinstance(s, str) else s
-        out.append(v)
-    return tuple(out)
-
-
-def _pointers(spec):
-    return [a if isinstance(a, str) else a[0] for a in spec if a in ("msgs", "off", "dst") or (isinstance(a, tuple) and len(a) == 3)]
-
-
-def _spoils(spec, dev):
-    """(case name, spoil) for one entry point."""
-    names = [a if isinstance(a, str) else a[0] for a in spec]
-    arrays = [a for a in spec if isinstance(a, tuple) and len(a) == 3]
-    required = [a[0] for a in arrays if a[2]] + [p for p in ("msgs", "off", "dst") if p in names]
-    every_null = {p: None for p in _pointers(spec) if p != "dst"}
-    every_null.update({"n": 0, "len": 0})
-    cases = [("ctx=null", {"ctx": None}), ("n=0,every array null", every_null)]
-    cases += [(p + "=null", {p: None}) for p in required]
-    if "off" in names and not dev:
-        bad, nz = np.arange(0, 5 * N + 1, 5, dtype=np.uint64), np.arange(0, 5 * N + 1, 5, dtype=np.uint64)
-        bad[3], bad[4] = 20, 10
-        nz[0] = 1
-        cases += [("off not monotonic", {"off": bad}), ("off[0]!=0", {"off": nz}), ("off[n]!=msg_len", {"len": 5 * N + 1})]
-    aligned = [a[0] for a in arrays if a[1] >= 32]
-    if dev:
-        cases += [("ctx=multi", {"ctx": "multi"})]
-        cases += [("off+4", {"off": "+4"})] if "off" in names else []
-        cases += [(p + "+8", {p: "+8"}) for p in aligned]
-    if "curve" in names:
-        cases += [("curve=2", {"curve": 2}), ("curve=7", {"curve": 7})]
-        # the curve check against the pointer checks: which of the two a call that fails both reports
-        cases += [("curve=2," + required[0] + "=null", {"curve": 2, required[0]: None})]
-        cases += [("curve=2,off=null", {"curve": 2, "off": None})]
-        if dev:
-            cases += [("curve=2,off+4", {"curve": 2, "off": "+4"}), ("curve=2," + aligned[0] + "+8", {"curve": 2, aligned[0]: "+8"})]
-    return cases
-
-
-def run_table(lib, ctx, multi):
-    """{case id: status} of every case, on the library `lib` (ctypes), a ctx handle and a multi-device ctx handle."""
-    buf = _Buffers()
-    out = {}
-    for table, dev in ((HOST, False), (DEV, True)):
-        for fn, spec in table.items():
-            for case, spoil in _spoils(spec, dev):
-                spoil = dict(spoil)
-                if spoil.get("ctx") == "multi":
-                    spoil["ctx"] = multi
-                out["%s: %s" % (fn, case)] = int(getattr(lib, fn)(*_call_args(spec, dev, buf, ctx, spoil)))
-    buf.torch.cuda.synchronize()
-    return out
-
-
 def test_return_codes_are_what_they_were(gpu_ctx):
     import forge_ec_amd as F
     from forge_ec_amd import _lib as L
     want = json.load(open(GOLDEN))
     with F.Context(devices=[0, 0]) as multi:
-        got = run_table(L.lib(), gpu_ctx._h, multi._h)
+        got = run_table(L.lib(), gpu_ctx._h, multi._h, ((HOST, False), (DEV, True)))
     assert sorted(got) == sorted(want)
     assert {k: v for k, v in got.items() if want[k] != v} == {}
     # no case but the curve-2 challenge (a supported curve there) got as far as a launch with elements in it

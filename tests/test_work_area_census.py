@@ -7,9 +7,11 @@ forge_ec_amd/csrc.  tests/test_gpu_secret_residue.py reads that memory on the GP
     must target a buffer on that list or one of the public tables of PUBLIC below, each with its reason; so must every
     device-pointer member of struct fec_ctx.  A buffer added later fails here until it is placed in one of the two.
   * THE TABLES ARE COMPLETE.  The extern "C" functions that stage a secret array -- their body names secret_input( /
-    secret_output(, or calls a helper of the same file that does (digest_call, eddsa_sign_call, ...) -- are, as a set, the
-    functions of HOST_ROWS.  The canonical launchers that open a SignArea, with launch_canon_x25519 and
-    launch_canon_seckey_tweak_add (no work area: registers and LDS only), are the launchers of DEV_ROWS.
+    secret_output(, or calls a helper of the same file that does (digest_call, eddsa_sign_call, ..., and the one function a
+    host / *_dev pair of entry points shares), and it is not the *_dev form, which hands that function on_device(stream)
+    and stages nothing -- are, as a set, the functions of HOST_ROWS.  The canonical launchers that open a SignArea, with
+    launch_canon_x25519 and launch_canon_seckey_tweak_add (no work area: registers and LDS only), are the launchers of
+    DEV_ROWS.
 """
 import os
 import re
@@ -134,16 +136,29 @@ def _secret_entry_points(src):
     helpers = [n for n, b in fns.items() if not n.startswith("fec_") and any(s in b for s in names)]
     out = set()
     for n, b in fns.items():
-        if n.startswith("fec_") and (any(s in b for s in names) or any(re.search(r"\b%s\(" % h, b) for h in helpers)):
+        if n.startswith("fec_") and "on_device(stream)" not in b and (any(s in b for s in names) or any(re.search(r"\b%s\(" % h, b) for h in helpers)):
             out.add(n)
     return out, helpers
+
+
+def _with_pair_function(fns, name):
+    """the body of an entry point and of the function it shares with the other form of its pair"""
+    body = fns[name]
+    return body + "".join(b for n, b in fns.items() if not n.startswith(("fec_", "launch_")) and re.search(r"\b%s\(" % n, body))
 
 
 def test_host_rows_are_the_entry_points_that_stage_secrets():
     parity, helpers = _secret_entry_points("fecgpu.hip")
     canon, canon_helpers = _secret_entry_points("canon.hip")
-    assert set(helpers) == {"digest_call", "eddsa_sign_call", "bip340_sign_call", "ecdsa_sign_msg_call", "schnorr_sign_msg_call", "h2c_msg_call"}
-    assert canon_helpers == []
+    assert set(helpers) == {"digest_call", "eddsa_sign_call", "bip340_sign_call", "ecdsa_sign_msg_call", "schnorr_sign_msg_call", "h2c_msg_call",
+                            # one function per host / *_dev pair
+                            "batch_ecdh", "derive_key", "ecdh_derive_key", "ecdh_exchange", "ecdsa_sign", "x25519", "curve25519_mul", "map_to_curve"}
+    assert set(canon_helpers) == {"canon_" + c for c in (
+        "mul_base_secret", "public_key", "ecdsa_sign_digest", "ecdsa_sign_msg", "rfc6979_k", "bip340_sign_msg", "ed25519_sign_msg", "x25519",
+        "x25519_base", "ecdsa_sign_recoverable_digest", "seckey_tweak_add", "bip32_derive_priv")}
+    for n in set(helpers) | set(canon_helpers):   # a *_dev form is told apart by what it hands such a function
+        if not n.endswith("_call"):
+            assert "Where w" in functions(os.path.join(CSRC, "fecgpu.hip" if n in helpers else "canon.hip"))[n], n
     assert len(parity) >= 20 and len(canon) >= 12
     assert sorted(parity | canon) == T.HOST_FUNCTIONS, sorted((parity | canon) ^ set(T.HOST_FUNCTIONS))
 
@@ -158,5 +173,5 @@ def test_dev_rows_are_the_launchers_that_handle_secrets():
     for n in bare:   # "no work area": nothing of the ctx's but the stream
         assert not re.search(r"SignArea|WorkArea|ensure_owned|d_verify|d_zbuf|d_tbuf|d_win_scratch", fns[n]), n
     for row in T.DEV_ROWS + T.CANON_HOST_ROWS:   # each row's entry point runs the launcher the row names
-        assert re.search(r"\b%s\(" % row.launcher, fns[row.fn]), (row.id, row.fn, row.launcher)
+        assert re.search(r"\b%s\(" % row.launcher, _with_pair_function(fns, row.fn)), (row.id, row.fn, row.launcher)
     assert {r.fn for r in T.DEV_ROWS} == {r.fn + "_dev" for r in T.CANON_HOST_ROWS}
