@@ -1374,166 +1374,18 @@ int launch_curve25519_mul(fec_ctx* ctx, const u32* s, const u32* p, u32* out, si
 }
 }  // namespace
 
-// The calls that take messages: the layout, the host-pointer engine and the *_dev forms' argument rules are
-// host_messages.hpp's (with_messages, dev_enter, dev_messages), shared with canon.hip.
+// The calls that take messages: what their entry points (below, one function per host / *_dev pair) need besides the
+// launchers above.  The layout, the host-pointer engine and the *_dev forms' argument rules are host_messages.hpp's
+// message_call, shared with canon.hip.
 namespace {
 
-// SHA-512 and SHA-256 per message (kernels_eddsa.hip, kernels_schnorr.hip).  A digest is secret: its message may be.
+// SHA-512 and SHA-256 per message (kernels_eddsa.hip, kernels_schnorr.hip).
 struct DigestKernel {
   void (*launch)(const Messages&, u32*, unsigned char*, size_t, hipStream_t);
   const char* name;
   size_t bytes;
 };
 constexpr DigestKernel kDigestSha512{sha512_launch, "k_sha512", 64}, kDigestSha256{sha256_launch, "k_sha256", 32};
-int digest_call(fec_ctx* ctx, const DigestKernel& k, const uint8_t* msgs, const uint64_t* off, size_t msg_len, uint8_t* digests, size_t n) {
-  if (n && !digests) return FEC_E_ARG;
-  const HostArray a[] = {ragged(off, 8), secret_output(digests, k.bytes)};
-  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    Launch L(c, st, k.name);
-    k.launch(m, static_cast<u32*>(d[1]), nullptr, cnt, L.s);
-    return L.done();
-  });
-}
-int digest_dev(fec_ctx* ctx, const DigestKernel& k, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
-               uint8_t* d_status, size_t n, void* stream) {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && !d_digests) || !aligned16(d_digests)) return FEC_E_ARG;
-  if (n == 0) return FEC_OK;
-  Launch L(ctx, stream, k.name);
-  k.launch(m, reinterpret_cast<u32*>(d_digests), d_status, n, L.s);
-  return L.done();
-}
-
-// EdDSA signing for Ed25519 (kernels_eddsa.hip).  out: 64 bytes per element, 32 for derive; r_inf and s for the generic
-// form.  Keys and outputs are secret.  EDDSA_MODE_DERIVE has no messages: the plain engine, one lane.
-int eddsa_sign_call(fec_ctx* ctx, int mode, const void* keys, const uint8_t* msgs, const uint64_t* off, size_t msg_len, void* out,
-                    uint8_t* status, uint8_t* r_inf, uint64_t* s_out, size_t n) {
-  const bool derive = mode == EDDSA_MODE_DERIVE;
-  if (!ctx || (n && (!keys || !out || !status || (mode == EDDSA_MODE_GENERIC && (!r_inf || !s_out))))) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(keys, 32), ragged(off, 8), secret_output(out, derive ? 32 : 64), output(status, 1), output(r_inf, 1),
-                         output(s_out, 32)};
-  auto body = [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    const EddsaSignIo io{mode, static_cast<const u32*>(d[0]), m, nullptr, static_cast<u32*>(d[2]),
-                         static_cast<unsigned char*>(d[4]), static_cast<u32*>(d[5]), static_cast<unsigned char*>(d[3])};
-    return launch_eddsa_sign(c, io, cnt, st);
-  };
-  if (!derive) return with_messages(ctx, n, a, msgs, off, msg_len, body);
-  return host_call(ctx, n, a, 1, [&](fec_ctx* c, void* const* d, size_t, size_t cnt, hipStream_t st) {
-    return body(c, d, Messages{nullptr, nullptr, 0}, cnt, st);
-  });
-}
-// The *_dev forms: one launch sequence on the caller's stream; each lane checks its own message range.
-int eddsa_sign_dev(fec_ctx* ctx, int mode, const void* d_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
-                   void* d_out, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_status, size_t n, void* stream) {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m{nullptr, nullptr, 0};
-  if (mode != EDDSA_MODE_DERIVE && dev_messages(d_msgs, d_msg_off, msg_len, n, m)) return FEC_E_ARG;
-  if (n && (!d_keys || !d_out || !d_status || (mode == EDDSA_MODE_GENERIC && (!d_r_inf || !d_s)))) return FEC_E_ARG;
-  if (!aligned16(d_keys) || !aligned16(d_out) || !aligned16(d_s)) return FEC_E_ARG;
-  const EddsaSignIo io{mode, static_cast<const u32*>(d_keys), m, nullptr, static_cast<u32*>(d_out), d_r_inf, reinterpret_cast<u32*>(d_s), d_status};
-  return launch_eddsa_sign(ctx, io, n, stream);
-}
-
-// BipSchnorr::sign (kernels_schnorr.hip).  Keys and signatures are secret.
-int bip340_sign_call(fec_ctx* ctx, const uint8_t* keys, const uint8_t* msgs, const uint64_t* off, size_t msg_len, uint8_t* sig,
-                     uint8_t* status, size_t n) {
-  if (n && (!keys || !sig || !status)) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(keys, 32), ragged(off, 8), secret_output(sig, 64), output(status, 1)};
-  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_bip340_sign(c, Bip340Io{static_cast<const u32*>(d[0]), m, static_cast<u32*>(d[2]), static_cast<unsigned char*>(d[3])}, cnt, st);
-  });
-}
-
-// The verifiers from the message.  form EDDSA_VERIFY_BYTES: pk n*32 bytes, sig n*64 bytes; EDDSA_VERIFY_GENERIC: pk and
-// sig (R) n*64 bytes of affine limbs with their flags, s n*32 bytes.  Nothing is secret.
-int verify_msg_call(fec_ctx* ctx, int form, const void* pk, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* off,
-                    size_t msg_len, const void* sig, const uint8_t* r_inf, const uint64_t* s_in, uint8_t* status, size_t n) {
-  const bool generic = form == EDDSA_VERIFY_GENERIC;
-  if (n && (!pk || !sig || !status || (generic && !s_in))) return FEC_E_ARG;
-  const HostArray a[] = {input(pk, generic ? 64 : 32), input(pk_inf, 1), ragged(off, 8), input(sig, 64), input(r_inf, 1),
-                         input(s_in, 32), output(status, 1)};
-  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    const EddsaVerifyIo io{form, static_cast<const u32*>(d[0]), static_cast<const unsigned char*>(d[1]), m,
-                           static_cast<const u32*>(d[3]), static_cast<const unsigned char*>(d[4]), static_cast<const u32*>(d[5])};
-    return launch_eddsa_verify_msg(c, io, static_cast<unsigned char*>(d[6]), cnt, st);
-  });
-}
-int verify_msg_dev(fec_ctx* ctx, int form, const void* d_pk, const uint8_t* d_pk_inf, const uint8_t* d_msgs, const uint64_t* d_msg_off,
-                   size_t msg_len, const void* d_sig, const uint8_t* d_r_inf, const uint64_t* d_s, uint8_t* d_status, size_t n,
-                   void* stream) {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m)) return FEC_E_ARG;
-  if (n && (!d_pk || !d_sig || !d_status || (form == EDDSA_VERIFY_GENERIC && !d_s))) return FEC_E_ARG;
-  if (!aligned16(d_pk) || !aligned16(d_sig) || !aligned16(d_s)) return FEC_E_ARG;
-  const EddsaVerifyIo io{form, static_cast<const u32*>(d_pk), d_pk_inf, m, static_cast<const u32*>(d_sig), d_r_inf, reinterpret_cast<const u32*>(d_s)};
-  return launch_eddsa_verify_msg(ctx, io, d_status, n, stream);
-}
-
-// Ecdsa::<C, Sha256>::verify from the message (ecdsa.rs:213-281).  Nothing is secret.
-int ecdsa_verify_msg_call(fec_ctx* ctx, int curve, const uint8_t* msgs, const uint64_t* off, size_t msg_len, const uint64_t* r,
-                          const uint64_t* s_in, const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* status, size_t n) {
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
-  if (n && (!r || !s_in || !pk_xy || !status)) return FEC_E_ARG;
-  const HostArray a[] = {ragged(off, 8), input(r, 32), input(s_in, 32), input(pk_xy, 64), input(pk_inf, 1), output(status, 1)};
-  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_ecdsa_verify(c, curve, nullptr, (const u64*)d[1], (const u64*)d[2], (const u64*)d[3], (const unsigned char*)d[4],
-                               (unsigned char*)d[5], cnt, st, &m);
-  });
-}
-
-// Ecdsa::<C, Sha256>::sign from the message (`order` null: out = the signature, 64 bytes per element) and
-// Rfc6979::<C, Sha256>::generate_k alone (out = k, 32 bytes, candidates compared with *order).  The keys are secret, and
-// so is k.
-int ecdsa_sign_msg_call(fec_ctx* ctx, int curve, const Rfc6979Order* order, const uint64_t* sk, const uint8_t* msgs, const uint64_t* off,
-                        size_t msg_len, uint64_t* out, uint8_t* status, size_t n) {
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
-  if (n && (!sk || !out || !status)) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(sk, 32), ragged(off, 8), secret_output(out, order ? 32 : 64), output(status, 1)};
-  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    if (order) return launch_rfc6979(c, curve, *order, (const u64*)d[0], m, (u64*)d[2], (unsigned char*)d[3], cnt, st);
-    return launch_ecdsa_sign(c, curve, (const u64*)d[0], nullptr, nullptr, (u64*)d[2], (unsigned char*)d[3], cnt, st, &m);
-  });
-}
-// The *_dev forms of the two.
-int ecdsa_sign_msg_dev(fec_ctx* ctx, int curve, bool nonce_only, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
-                       size_t msg_len, uint64_t* d_out, uint8_t* d_status, size_t n, void* stream) {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  const int bad = dev_messages(d_msgs, d_msg_off, msg_len, n, m);
-  if (bad == kDevMsgsNull || (n && (!d_sk || !d_out || !d_status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519 has no Ecdsa instance
-  if (bad || !aligned16(d_sk) || !aligned16(d_out)) return FEC_E_ARG;
-  if (nonce_only) return launch_rfc6979(ctx, curve, rfc6979_curve_order(curve), d_sk, m, d_out, d_status, n, stream);
-  return launch_ecdsa_sign(ctx, curve, d_sk, nullptr, nullptr, d_out, d_status, n, stream, &m);
-}
-
-// Schnorr::<C, Sha256>::sign from the message.  sk is secret, and so are k and e * sk behind s.
-int schnorr_sign_msg_call(fec_ctx* ctx, int curve, const uint64_t* sk, const uint8_t* msgs, const uint64_t* off, size_t msg_len,
-                          uint64_t* r_xy, uint8_t* r_inf, uint64_t* s_out, uint8_t* sig_bytes, uint8_t* status, size_t n) {
-  if (!curve_ok(curve)) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;   // Ed25519: its nonce and fixed-base instances are not built
-  if (n && (!sk || !r_xy || !r_inf || !s_out || !status)) return FEC_E_ARG;
-  const HostArray a[] = {secret_input(sk, 32), ragged(off, 8), secret_output(r_xy, 64), output(r_inf, 1), secret_output(s_out, 32),
-                         secret_output(sig_bytes, 64), output(status, 1)};
-  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    const SchnorrSignIo io{static_cast<const u32*>(d[0]), m, static_cast<u32*>(d[2]), static_cast<unsigned char*>(d[3]),
-                           static_cast<u32*>(d[4]), static_cast<u32*>(d[5]), static_cast<unsigned char*>(d[6])};
-    return launch_schnorr_sign(c, curve, io, cnt, st);
-  });
-}
-// The challenge alone, all three curves.  Nothing is secret.
-int schnorr_challenge_call(fec_ctx* ctx, int curve, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy, const uint8_t* pk_inf,
-                           const uint8_t* msgs, const uint64_t* off, size_t msg_len, uint64_t* e, size_t n) {
-  if (!curve_ok(curve) || (n && (!r_xy || !pk_xy || !e))) return FEC_E_ARG;
-  const HostArray a[] = {input(r_xy, 64), input(r_inf, 1), input(pk_xy, 64), input(pk_inf, 1), ragged(off, 8), output(e, 32)};
-  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    const SchnorrChallengeIo io{static_cast<const u32*>(d[0]), static_cast<const unsigned char*>(d[1]), static_cast<const u32*>(d[2]),
-                                static_cast<const unsigned char*>(d[3]), m, static_cast<u32*>(d[5]), nullptr};
-    return launch_schnorr_challenge(c, curve, io, cnt, st);
-  });
-}
 
 // ---- HashToCurve (fecgpu.h; h2c.hpp; kernels_h2c.hip) ----
 // What one call computes: the expander alone, hash_to_field, or the fused kernel in one of its forms.
@@ -1566,25 +1418,17 @@ int launch_map_to_curve(fec_ctx* ctx, int curve, const u32* u, u32* xy, u32* can
   map_to_curve_launch(curve, u, xy, cand, legs, n, L.s);
   return L.done();
 }
-// The host forms.  The messages may be secret (passwords), so every output is staged as one.  A stride of 0 or a null
-// pointer: the array is absent.
-int h2c_msg_call(fec_ctx* ctx, const H2cCall& c, const uint8_t* msgs, const uint64_t* off, size_t msg_len, void* out, size_t out_stride,
-                 uint8_t* inf, void* cand, size_t cand_stride, uint8_t* legs, size_t legs_stride, size_t n) {
-  const HostArray a[] = {ragged(off, 8), secret_output(out_stride ? out : nullptr, out_stride), secret_output(inf, 1),
-                         secret_output(cand_stride ? cand : nullptr, cand_stride), secret_output(legs_stride ? legs : nullptr, legs_stride)};
-  return with_messages(ctx, n, a, msgs, off, msg_len, [&](fec_ctx* cc, void* const* d, const Messages& m, size_t cnt, hipStream_t st) {
-    return launch_h2c(cc, c, m, d[1], static_cast<unsigned char*>(d[2]), d[3], static_cast<unsigned char*>(d[4]), nullptr, cnt, st);
-  });
-}
-// The checks every form shares.  The bounds exist because the reference writes dst.len() and the block counter into a u8.
-int h2c_args(fec_ctx* ctx, int curve, const uint8_t* dst, size_t dst_len) {
+// The checks every form shares, made before an array is looked at (a *_dev form: after dev_enter).  The bounds exist
+// because the reference writes dst.len() and the block counter into a u8.
+int h2c_args(fec_ctx* ctx, Where w, int curve, const uint8_t* dst, size_t dst_len) {
+  if (const int rc = w.dev ? dev_enter(ctx) : FEC_OK) return rc;
   if (!ctx || !curve_ok(curve) || (dst_len && !dst)) return FEC_E_ARG;
   if (curve == FEC_ED25519) return FEC_E_UNSUPPORTED;   // Ed25519 implements no HashToCurve
   if (dst_len > h2c::MAX_DST) return FEC_E_UNSUPPORTED;
   return FEC_OK;
 }
-int h2c_mode_args(fec_ctx* ctx, int curve, int mode, int method, const uint8_t* dst, size_t dst_len) {
-  const int rc = h2c_args(ctx, curve, dst, dst_len);
+int h2c_mode_args(fec_ctx* ctx, Where w, int curve, int mode, int method, const uint8_t* dst, size_t dst_len) {
+  const int rc = h2c_args(ctx, w, curve, dst, dst_len);
   if (rc != FEC_OK) return rc;
   if (mode != FEC_H2C_HASH && mode != FEC_H2C_ENCODE) return FEC_E_ARG;
   if (method == FEC_H2C_ICART || method == FEC_H2C_ELLIGATOR2) return FEC_E_UNSUPPORTED;
@@ -2679,138 +2523,193 @@ int fec_curve25519_field_op(fec_ctx* ctx, fec_field_opcode op, const uint64_t* a
               });
 } FEC_ABI_CATCH_STATUS
 
-// ---- EdDSA signing for Ed25519 with SHA-512, and SHA-512 (kernels_eddsa.hip; helpers above the extern "C" block) ----
+// ---- the calls that take messages, one function per host / *_dev pair (host_messages.hpp: message_call) ----
+// The kernels read 32-bit words: an array goes into its descriptor in that type.
+static const u32* words(const void* p) { return static_cast<const u32*>(p); }
+static u32* words(void* p) { return static_cast<u32*>(p); }
+// Some host forms make a value check before they look at the ctx or at an array; their *_dev forms make it where the
+// engine does, after the null pointers.
+static int on_host_first(Where w, int value_rc) { return w.dev ? FEC_OK : value_rc; }
 
+// SHA-512 and SHA-256 per message (kernels_eddsa.hip, kernels_schnorr.hip).  A digest is secret: its message may be.
+// (`d_status`: the *_dev forms' optional array; the host forms have none)
+static int sha_digest(fec_ctx* ctx, Where w, const DigestKernel& k, const MessageArgs& ma, uint8_t* digests, uint8_t* d_status, size_t n) {
+  return message_call(ctx, w, n, FEC_OK, ma, arrays(secret_output(words(digests), k.bytes).aligned(16)),
+                      [&](fec_ctx* c, const Messages& m, u32* d_digests, size_t cnt, void* s) -> int {
+                        if (cnt == 0) return FEC_OK;
+                        Launch L(c, s, k.name);
+                        k.launch(m, d_digests, d_status, cnt, L.s);
+                        return L.done();
+                      });
+}
 int fec_sha512(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* digests, size_t n) try {
-  return digest_call(ctx, kDigestSha512, msgs, msg_off, msg_len, digests, n);
+  return sha_digest(ctx, kOnHost, kDigestSha512, {msgs, msg_off, msg_len}, digests, nullptr, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_sha512_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
                    uint8_t* d_status, size_t n, void* stream) try {
-  return digest_dev(ctx, kDigestSha512, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream);
+  return sha_digest(ctx, on_device(stream), kDigestSha512, {d_msgs, d_msg_off, msg_len}, d_digests, d_status, n);
+} FEC_ABI_CATCH_STATUS
+int fec_sha256(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* digests, size_t n) try {
+  return sha_digest(ctx, kOnHost, kDigestSha256, {msgs, msg_off, msg_len}, digests, nullptr, n);
+} FEC_ABI_CATCH_STATUS
+int fec_sha256_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
+                   uint8_t* d_status, size_t n, void* stream) try {
+  return sha_digest(ctx, on_device(stream), kDigestSha256, {d_msgs, d_msg_off, msg_len}, d_digests, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
+// EdDSA signing for Ed25519 (kernels_eddsa.hip).  out: 64 bytes per element, 32 for derive; r_inf and s: the generic form
+// only.  Keys and outputs are secret.  EDDSA_MODE_DERIVE has no messages: the plain engine, one lane.
+static int eddsa_sign(fec_ctx* ctx, Where w, int mode, const void* keys, const MessageArgs& ma, void* out, uint8_t* r_inf, uint64_t* s, uint8_t* status,
+                      size_t n) {
+  const bool derive = mode == EDDSA_MODE_DERIVE, generic = mode == EDDSA_MODE_GENERIC;
+  const auto list = arrays(secret_input(words(keys), 32).aligned(16), secret_output(words(out), derive ? 32 : 64).aligned(16),
+                           output(r_inf, 1).opt(!generic), output(words(s), 32).aligned(16).opt(!generic), output(status, 1));
+  auto body = [&](fec_ctx* c, const Messages& m, const u32* d_keys, u32* d_out, uint8_t* d_r_inf, u32* d_s, uint8_t* d_status, size_t cnt, void* st) {
+    return launch_eddsa_sign(c, EddsaSignIo{mode, d_keys, m, nullptr, d_out, d_r_inf, d_s, d_status}, cnt, st);
+  };
+  if (!derive) return message_call(ctx, w, n, FEC_OK, ma, list, body);
+  return call(ctx, w, n, 1, FEC_OK, list, [&](fec_ctx* c, auto... p) { return body(c, Messages{nullptr, nullptr, 0}, p...); });
+}
 int fec_ed25519_sign(fec_ctx* ctx, const uint8_t* private_keys, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                      uint8_t* sig, uint8_t* status, size_t n) try {
-  return eddsa_sign_call(ctx, EDDSA_MODE_SIGN, private_keys, msgs, msg_off, msg_len, sig, status, nullptr, nullptr, n);
+  return eddsa_sign(ctx, kOnHost, EDDSA_MODE_SIGN, private_keys, {msgs, msg_off, msg_len}, sig, nullptr, nullptr, status, n);
 } FEC_ABI_CATCH_STATUS
-
-int fec_ed25519_derive_public_key(fec_ctx* ctx, const uint8_t* private_keys, uint8_t* public_keys, uint8_t* status,
-                                  size_t n) try {
-  return eddsa_sign_call(ctx, EDDSA_MODE_DERIVE, private_keys, nullptr, nullptr, 0, public_keys, status, nullptr, nullptr, n);
-} FEC_ABI_CATCH_STATUS
-
-int fec_eddsa_sign_ed25519(fec_ctx* ctx, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
-                           uint64_t* r_xy, uint8_t* r_inf, uint64_t* s, uint8_t* status, size_t n) try {
-  return eddsa_sign_call(ctx, EDDSA_MODE_GENERIC, sk, msgs, msg_off, msg_len, r_xy, status, r_inf, s, n);
-} FEC_ABI_CATCH_STATUS
-
 int fec_ed25519_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                          size_t msg_len, uint8_t* d_sig, uint8_t* d_status, size_t n, void* stream) try {
-  return eddsa_sign_dev(ctx, EDDSA_MODE_SIGN, d_private_keys, d_msgs, d_msg_off, msg_len, d_sig, nullptr, nullptr, d_status, n, stream);
+  return eddsa_sign(ctx, on_device(stream), EDDSA_MODE_SIGN, d_private_keys, {d_msgs, d_msg_off, msg_len}, d_sig, nullptr, nullptr, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
+int fec_ed25519_derive_public_key(fec_ctx* ctx, const uint8_t* private_keys, uint8_t* public_keys, uint8_t* status,
+                                  size_t n) try {
+  return eddsa_sign(ctx, kOnHost, EDDSA_MODE_DERIVE, private_keys, {}, public_keys, nullptr, nullptr, status, n);
+} FEC_ABI_CATCH_STATUS
 int fec_ed25519_derive_public_key_dev(fec_ctx* ctx, const uint8_t* d_private_keys, uint8_t* d_public_keys, uint8_t* d_status,
                                       size_t n, void* stream) try {
-  return eddsa_sign_dev(ctx, EDDSA_MODE_DERIVE, d_private_keys, nullptr, nullptr, 0, d_public_keys, nullptr, nullptr, d_status, n, stream);
+  return eddsa_sign(ctx, on_device(stream), EDDSA_MODE_DERIVE, d_private_keys, {}, d_public_keys, nullptr, nullptr, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
+int fec_eddsa_sign_ed25519(fec_ctx* ctx, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                           uint64_t* r_xy, uint8_t* r_inf, uint64_t* s, uint8_t* status, size_t n) try {
+  return eddsa_sign(ctx, kOnHost, EDDSA_MODE_GENERIC, sk, {msgs, msg_off, msg_len}, r_xy, r_inf, s, status, n);
+} FEC_ABI_CATCH_STATUS
 int fec_eddsa_sign_ed25519_dev(fec_ctx* ctx, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                                uint64_t* d_r_xy, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_status, size_t n, void* stream) try {
-  return eddsa_sign_dev(ctx, EDDSA_MODE_GENERIC, d_sk, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status, n, stream);
+  return eddsa_sign(ctx, on_device(stream), EDDSA_MODE_GENERIC, d_sk, {d_msgs, d_msg_off, msg_len}, d_r_xy, d_r_inf, d_s, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- the Ed25519 EdDSA verifiers from the message (kernels_eddsa.hip; helpers above the extern "C" block) ----
-
+// The Ed25519 verifiers from the message (kernels_eddsa.hip).  form EDDSA_VERIFY_BYTES: pk n*32 bytes, sig n*64 bytes;
+// EDDSA_VERIFY_GENERIC: pk and sig (R) n*64 bytes of affine limbs with their flags, s n*32 bytes.  Nothing is secret.
+static int eddsa_verify_msg(fec_ctx* ctx, Where w, int form, const void* pk, const uint8_t* pk_inf, const MessageArgs& ma, const void* sig,
+                            const uint8_t* r_inf, const uint64_t* s, uint8_t* status, size_t n) {
+  const bool generic = form == EDDSA_VERIFY_GENERIC;
+  return message_call(ctx, w, n, FEC_OK, ma,
+                      arrays(input(words(pk), generic ? 64 : 32).aligned(16), input(pk_inf, 1).opt(), input(words(sig), 64).aligned(16),
+                             input(r_inf, 1).opt(), input(words(s), 32).aligned(16).opt(!generic), output(status, 1)),
+                      [&](fec_ctx* c, const Messages& m, const u32* d_pk, const uint8_t* d_pk_inf, const u32* d_sig, const uint8_t* d_r_inf,
+                          const u32* d_s, uint8_t* d_status, size_t cnt, void* st) {
+                        return launch_eddsa_verify_msg(c, EddsaVerifyIo{form, d_pk, d_pk_inf, m, d_sig, d_r_inf, d_s}, d_status, cnt, st);
+                      });
+}
 int fec_ed25519_verify(fec_ctx* ctx, const uint8_t* public_keys, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                        const uint8_t* sigs, uint8_t* status, size_t n) try {
-  return verify_msg_call(ctx, EDDSA_VERIFY_BYTES, public_keys, nullptr, msgs, msg_off, msg_len, sigs, nullptr, nullptr, status, n);
+  return eddsa_verify_msg(ctx, kOnHost, EDDSA_VERIFY_BYTES, public_keys, nullptr, {msgs, msg_off, msg_len}, sigs, nullptr, nullptr, status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_ed25519_verify_dev(fec_ctx* ctx, const uint8_t* d_public_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                            size_t msg_len, const uint8_t* d_sigs, uint8_t* d_status, size_t n, void* stream) try {
-  return verify_msg_dev(ctx, EDDSA_VERIFY_BYTES, d_public_keys, nullptr, d_msgs, d_msg_off, msg_len, d_sigs, nullptr, nullptr,
-                        d_status, n, stream);
+  return eddsa_verify_msg(ctx, on_device(stream), EDDSA_VERIFY_BYTES, d_public_keys, nullptr, {d_msgs, d_msg_off, msg_len}, d_sigs, nullptr, nullptr,
+                          d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_eddsa_verify_ed25519_msg(fec_ctx* ctx, const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs,
                                  const uint64_t* msg_off, size_t msg_len, const uint64_t* r_xy, const uint8_t* r_inf,
                                  const uint64_t* s, uint8_t* status, size_t n) try {
-  return verify_msg_call(ctx, EDDSA_VERIFY_GENERIC, pk_xy, pk_inf, msgs, msg_off, msg_len, r_xy, r_inf, s, status, n);
+  return eddsa_verify_msg(ctx, kOnHost, EDDSA_VERIFY_GENERIC, pk_xy, pk_inf, {msgs, msg_off, msg_len}, r_xy, r_inf, s, status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_eddsa_verify_ed25519_msg_dev(fec_ctx* ctx, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf, const uint8_t* d_msgs,
                                      const uint64_t* d_msg_off, size_t msg_len, const uint64_t* d_r_xy, const uint8_t* d_r_inf,
                                      const uint64_t* d_s, uint8_t* d_status, size_t n, void* stream) try {
-  return verify_msg_dev(ctx, EDDSA_VERIFY_GENERIC, d_pk_xy, d_pk_inf, d_msgs, d_msg_off, msg_len, d_r_xy, d_r_inf, d_s, d_status,
-                        n, stream);
+  return eddsa_verify_msg(ctx, on_device(stream), EDDSA_VERIFY_GENERIC, d_pk_xy, d_pk_inf, {d_msgs, d_msg_off, msg_len}, d_r_xy, d_r_inf, d_s,
+                          d_status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- SHA-256, ECDSA verification from the message, BIP-340 signing (kernels_schnorr.hip; helpers above) ----
-
-int fec_sha256(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint8_t* digests, size_t n) try {
-  return digest_call(ctx, kDigestSha256, msgs, msg_off, msg_len, digests, n);
-} FEC_ABI_CATCH_STATUS
-
-int fec_sha256_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint8_t* d_digests,
-                   uint8_t* d_status, size_t n, void* stream) try {
-  return digest_dev(ctx, kDigestSha256, d_msgs, d_msg_off, msg_len, d_digests, d_status, n, stream);
-} FEC_ABI_CATCH_STATUS
-
+// Ecdsa::<C, Sha256>::verify from the message (ecdsa.rs:213-281; kernels_schnorr.hip).  Nothing is secret.  Ed25519 has no
+// Ecdsa instance: the host form says so before anything else.  The *_dev form marks the elements whose range is bad.
+static int ecdsa_verify_msg(fec_ctx* ctx, Where w, int curve, const MessageArgs& ma, const uint64_t* r, const uint64_t* s, const uint64_t* pk_xy,
+                            const uint8_t* pk_inf, uint8_t* status, size_t n) {
+  if (const int rc = on_host_first(w, ecdsa_curves_only(curve))) return rc;
+  return message_call(ctx, w, n, ecdsa_curves_only(curve), ma,
+                      arrays(input(r, 32).aligned(16), input(s, 32).aligned(16), input(pk_xy, 64).aligned(16), input(pk_inf, 1).opt(), output(status, 1)),
+                      [&](fec_ctx* c, const Messages& m, const uint64_t* d_r, const uint64_t* d_s, const uint64_t* d_pk, const uint8_t* d_inf,
+                          uint8_t* d_status, size_t cnt, void* st) {
+                        return launch_ecdsa_verify(c, curve, nullptr, d_r, d_s, d_pk, d_inf, d_status, cnt, st, &m, w.dev);
+                      });
+}
 int fec_ecdsa_verify_msg(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                          const uint64_t* r, const uint64_t* s, const uint64_t* pk_xy, const uint8_t* pk_inf, uint8_t* status,
                          size_t n) try {
-  return ecdsa_verify_msg_call(ctx, curve, msgs, msg_off, msg_len, r, s, pk_xy, pk_inf, status, n);
+  return ecdsa_verify_msg(ctx, kOnHost, curve, {msgs, msg_off, msg_len}, r, s, pk_xy, pk_inf, status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_ecdsa_verify_msg_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                              const uint64_t* d_r, const uint64_t* d_s, const uint64_t* d_pk_xy, const uint8_t* d_pk_inf,
                              uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  const int bad = dev_messages(d_msgs, d_msg_off, msg_len, n, m);
-  if (bad == kDevMsgsNull || (n && (!d_r || !d_s || !d_pk_xy || !d_status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
-  if (bad || !aligned16(d_r) || !aligned16(d_s) || !aligned16(d_pk_xy)) return FEC_E_ARG;
-  return launch_ecdsa_verify(ctx, curve, nullptr, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n, stream, &m, true);
+  return ecdsa_verify_msg(ctx, on_device(stream), curve, {d_msgs, d_msg_off, msg_len}, d_r, d_s, d_pk_xy, d_pk_inf, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
+// BipSchnorr::sign (kernels_schnorr.hip).  Keys and signatures are secret.
+static int bip340_sign(fec_ctx* ctx, Where w, const uint8_t* keys, const MessageArgs& ma, uint8_t* sig, uint8_t* status, size_t n) {
+  return message_call(ctx, w, n, FEC_OK, ma, arrays(secret_input(words(keys), 32).aligned(16), secret_output(words(sig), 64).aligned(16), output(status, 1)),
+                      [&](fec_ctx* c, const Messages& m, const u32* d_keys, u32* d_sig, uint8_t* d_status, size_t cnt, void* st) {
+                        return launch_bip340_sign(c, Bip340Io{d_keys, m, d_sig, d_status}, cnt, st);
+                      });
+}
 int fec_bip340_sign(fec_ctx* ctx, const uint8_t* private_keys, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                     uint8_t* signatures, uint8_t* status, size_t n) try {
-  return bip340_sign_call(ctx, private_keys, msgs, msg_off, msg_len, signatures, status, n);
+  return bip340_sign(ctx, kOnHost, private_keys, {msgs, msg_off, msg_len}, signatures, status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_bip340_sign_dev(fec_ctx* ctx, const uint8_t* d_private_keys, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                         size_t msg_len, uint8_t* d_signatures, uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_private_keys || !d_signatures || !d_status))) return FEC_E_ARG;
-  if (!aligned16(d_private_keys) || !aligned16(d_signatures)) return FEC_E_ARG;
-  return launch_bip340_sign(ctx, Bip340Io{reinterpret_cast<const u32*>(d_private_keys), m, reinterpret_cast<u32*>(d_signatures), d_status}, n, stream);
+  return bip340_sign(ctx, on_device(stream), d_private_keys, {d_msgs, d_msg_off, msg_len}, d_signatures, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- ECDSA signing from the message, RFC 6979 nonces (kernels_rfc6979.hip; helpers above) ----
-
+// Ecdsa::<C, Sha256>::sign from the message (`order` null: out = the signature, 64 bytes per element) and
+// Rfc6979::<C, Sha256>::generate_k alone (out = k, 32 bytes, candidates compared with *order; kernels_rfc6979.hip).  The keys
+// are secret, and so is k.  Ed25519 has no Ecdsa instance: the host forms say so before anything else.
+static int ecdsa_sign_msg(fec_ctx* ctx, Where w, int curve, const Rfc6979Order* order, const uint64_t* sk, const MessageArgs& ma, uint64_t* out,
+                          uint8_t* status, size_t n) {
+  if (const int rc = on_host_first(w, ecdsa_curves_only(curve))) return rc;
+  return message_call(ctx, w, n, ecdsa_curves_only(curve), ma,
+                      arrays(secret_input(sk, 32).aligned(16), secret_output(out, order ? 32 : 64).aligned(16), output(status, 1)),
+                      [&](fec_ctx* c, const Messages& m, const uint64_t* d_sk, uint64_t* d_out, uint8_t* d_status, size_t cnt, void* st) {
+                        if (order) return launch_rfc6979(c, curve, *order, d_sk, m, d_out, d_status, cnt, st);
+                        return launch_ecdsa_sign(c, curve, d_sk, nullptr, nullptr, d_out, d_status, cnt, st, &m);
+                      });
+}
 int fec_ecdsa_sign_msg(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                        uint64_t* sig, uint8_t* status, size_t n) try {
-  return ecdsa_sign_msg_call(ctx, curve, nullptr, sk, msgs, msg_off, msg_len, sig, status, n);
+  return ecdsa_sign_msg(ctx, kOnHost, curve, nullptr, sk, {msgs, msg_off, msg_len}, sig, status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_ecdsa_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                            size_t msg_len, uint64_t* d_sig, uint8_t* d_status, size_t n, void* stream) try {
-  return ecdsa_sign_msg_dev(ctx, curve, false, d_sk, d_msgs, d_msg_off, msg_len, d_sig, d_status, n, stream);
+  return ecdsa_sign_msg(ctx, on_device(stream), curve, nullptr, d_sk, {d_msgs, d_msg_off, msg_len}, d_sig, d_status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                   uint64_t* k, uint8_t* status, size_t n) try {
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
   const Rfc6979Order order = rfc6979_curve_order(curve);
-  return ecdsa_sign_msg_call(ctx, curve, &order, sk, msgs, msg_off, msg_len, k, status, n);
+  return ecdsa_sign_msg(ctx, kOnHost, curve, &order, sk, {msgs, msg_off, msg_len}, k, status, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_rfc6979_k_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                       size_t msg_len, uint64_t* d_k, uint8_t* d_status, size_t n, void* stream) try {
-  return ecdsa_sign_msg_dev(ctx, curve, true, d_sk, d_msgs, d_msg_off, msg_len, d_k, d_status, n, stream);
+  const Rfc6979Order order = rfc6979_curve_order(curve);
+  return ecdsa_sign_msg(ctx, on_device(stream), curve, &order, d_sk, {d_msgs, d_msg_off, msg_len}, d_k, d_status, n);
+} FEC_ABI_CATCH_STATUS
+// Debug hook: fec_rfc6979_k with the caller's comparison constant instead of the curve's.  At least 2^254, so that a
+// candidate passes with probability 1/4 or more and the retry cap stays out of reach: tested before everything else.
+int fec_debug_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* order_override, const uint64_t* sk, const uint8_t* msgs,
+                        const uint64_t* msg_off, size_t msg_len, uint64_t* k, uint8_t* status, size_t n) try {
+  if (!order_override || (order_override[3] >> 62) == 0) return FEC_E_ARG;
+  Rfc6979Order order;
+  for (int i = 0; i < 4; ++i) {
+    order.w[2 * i] = (u32)order_override[i];
+    order.w[2 * i + 1] = (u32)(order_override[i] >> 32);
+  }
+  return ecdsa_sign_msg(ctx, kOnHost, curve, &order, sk, {msgs, msg_off, msg_len}, k, status, n);
 } FEC_ABI_CATCH_STATUS
 
 static int scalar_from_bytes_reduced(fec_ctx* ctx, Where w, int curve, const uint8_t* bytes, uint64_t* out, size_t n) {
@@ -2826,82 +2725,88 @@ int fec_scalar_from_bytes_reduced_dev(fec_ctx* ctx, fec_curve curve, const uint8
   return scalar_from_bytes_reduced(ctx, on_device(stream), curve, d_bytes, d_out, n);
 } FEC_ABI_CATCH_STATUS
 
+// The challenge alone, all three curves (kernels_schnorr.hip).  Nothing is secret.
+// (`d_status`: the *_dev form's array, required there; the host form has none)
+static int schnorr_challenge(fec_ctx* ctx, Where w, int curve, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy, const uint8_t* pk_inf,
+                             const MessageArgs& ma, uint64_t* e, uint8_t* d_status, size_t n) {
+  return message_call(ctx, w, n, arg_if(!curve_ok(curve) || (w.dev && n && !d_status)), ma,
+                      arrays(input(words(r_xy), 64).aligned(16), input(r_inf, 1).opt(), input(words(pk_xy), 64).aligned(16), input(pk_inf, 1).opt(),
+                             output(words(e), 32).aligned(16)),
+                      [&](fec_ctx* c, const Messages& m, const u32* d_r, const uint8_t* d_r_inf, const u32* d_pk, const uint8_t* d_pk_inf, u32* d_e,
+                          size_t cnt, void* st) {
+                        return launch_schnorr_challenge(c, curve, SchnorrChallengeIo{d_r, d_r_inf, d_pk, d_pk_inf, m, d_e, d_status}, cnt, st);
+                      });
+}
 int fec_schnorr_challenge(fec_ctx* ctx, fec_curve curve, const uint64_t* r_xy, const uint8_t* r_inf, const uint64_t* pk_xy,
                           const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, uint64_t* e, size_t n) try {
-  return schnorr_challenge_call(ctx, curve, r_xy, r_inf, pk_xy, pk_inf, msgs, msg_off, msg_len, e, n);
+  return schnorr_challenge(ctx, kOnHost, curve, r_xy, r_inf, pk_xy, pk_inf, {msgs, msg_off, msg_len}, e, nullptr, n);
 } FEC_ABI_CATCH_STATUS
 int fec_schnorr_challenge_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_r_xy, const uint8_t* d_r_inf, const uint64_t* d_pk_xy,
                               const uint8_t* d_pk_inf, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, uint64_t* d_e,
                               uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || !curve_ok(curve) || (n && (!d_r_xy || !d_pk_xy || !d_e || !d_status))) return FEC_E_ARG;
-  if (!aligned16(d_r_xy) || !aligned16(d_pk_xy) || !aligned16(d_e)) return FEC_E_ARG;
-  const SchnorrChallengeIo io{reinterpret_cast<const u32*>(d_r_xy), d_r_inf, reinterpret_cast<const u32*>(d_pk_xy), d_pk_inf, m,
-                              reinterpret_cast<u32*>(d_e), d_status};
-  return launch_schnorr_challenge(ctx, curve, io, n, stream);
+  return schnorr_challenge(ctx, on_device(stream), curve, d_r_xy, d_r_inf, d_pk_xy, d_pk_inf, {d_msgs, d_msg_off, msg_len}, d_e, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
+// Schnorr::<C, Sha256>::sign from the message.  sk is secret, and so are k and e * sk behind s.  A curve that does not
+// exist is FEC_E_ARG; Ed25519, whose nonce and fixed-base instances are not built, FEC_E_UNSUPPORTED: the host form says
+// either before anything else.
+static int schnorr_sign_msg(fec_ctx* ctx, Where w, int curve, const uint64_t* sk, const MessageArgs& ma, uint64_t* r_xy, uint8_t* r_inf, uint64_t* s,
+                            uint8_t* sig_bytes, uint8_t* status, size_t n) {
+  const int curve_rc = first_of(arg_if(!curve_ok(curve)), ecdsa_curves_only(curve));
+  if (const int rc = on_host_first(w, curve_rc)) return rc;
+  return message_call(ctx, w, n, curve_rc, ma,
+                      arrays(secret_input(words(sk), 32).aligned(16), secret_output(words(r_xy), 64).aligned(16), output(r_inf, 1),
+                             secret_output(words(s), 32).aligned(16), secret_output(words(sig_bytes), 64).aligned(16).opt(), output(status, 1)),
+                      [&](fec_ctx* c, const Messages& m, const u32* d_sk, u32* d_r, uint8_t* d_r_inf, u32* d_s, u32* d_sig, uint8_t* d_status, size_t cnt,
+                          void* st) { return launch_schnorr_sign(c, curve, SchnorrSignIo{d_sk, m, d_r, d_r_inf, d_s, d_sig, d_status}, cnt, st); });
+}
 int fec_schnorr_sign_msg(fec_ctx* ctx, fec_curve curve, const uint64_t* sk, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                          uint64_t* r_xy, uint8_t* r_inf, uint64_t* s, uint8_t* sig_bytes, uint8_t* status, size_t n) try {
-  return schnorr_sign_msg_call(ctx, curve, sk, msgs, msg_off, msg_len, r_xy, r_inf, s, sig_bytes, status, n);
+  return schnorr_sign_msg(ctx, kOnHost, curve, sk, {msgs, msg_off, msg_len}, r_xy, r_inf, s, sig_bytes, status, n);
 } FEC_ABI_CATCH_STATUS
 int fec_schnorr_sign_msg_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_sk, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                              size_t msg_len, uint64_t* d_r_xy, uint8_t* d_r_inf, uint64_t* d_s, uint8_t* d_sig_bytes, uint8_t* d_status,
                              size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  Messages m;
-  const int bad = dev_messages(d_msgs, d_msg_off, msg_len, n, m);
-  if (bad == kDevMsgsNull || !curve_ok(curve) || (n && (!d_sk || !d_r_xy || !d_r_inf || !d_s || !d_status))) return FEC_E_ARG;
-  if (curve != FEC_SECP256K1 && curve != FEC_P256) return FEC_E_UNSUPPORTED;
-  if (bad || !aligned16(d_sk) || !aligned16(d_r_xy) || !aligned16(d_s) || !aligned16(d_sig_bytes)) return FEC_E_ARG;
-  const SchnorrSignIo io{reinterpret_cast<const u32*>(d_sk), m, reinterpret_cast<u32*>(d_r_xy), d_r_inf, reinterpret_cast<u32*>(d_s),
-                         reinterpret_cast<u32*>(d_sig_bytes), d_status};
-  return launch_schnorr_sign(ctx, curve, io, n, stream);
+  return schnorr_sign_msg(ctx, on_device(stream), curve, d_sk, {d_msgs, d_msg_off, msg_len}, d_r_xy, d_r_inf, d_s, d_sig_bytes, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
-// ---- HashToCurve (kernels_h2c.hip; helpers above the extern "C" block) ----
-
+// ---- HashToCurve (kernels_h2c.hip; h2c_args and launch_h2c above the extern "C" block) ----
+// Each pair makes its value checks before it looks at an array (h2c_args: a *_dev form after dev_enter).  The messages may
+// be secret (passwords), so every output is one.  (`d_status`: the *_dev forms' optional array; the host forms have none)
+static int expand_message_xmd(fec_ctx* ctx, Where w, const MessageArgs& ma, const uint8_t* dst, size_t dst_len, size_t out_len, uint8_t* out,
+                              uint8_t* d_status, size_t n) {
+  if (const int rc = first_of(h2c_args(ctx, w, FEC_SECP256K1, dst, dst_len), out_len > h2c::MAX_OUT ? FEC_E_UNSUPPORTED : FEC_OK)) return rc;   // (no curve: any good one)
+  const H2cCall c{kH2cXmd, 0, 0, h2c::make_params(dst, dst_len, out_len)};
+  return message_call(ctx, w, n, FEC_OK, ma, arrays(secret_output(out, out_len).aligned(16).opt(!out_len)),
+                      [&](fec_ctx* cc, const Messages& m, uint8_t* d_out, size_t cnt, void* st) {
+                        return launch_h2c(cc, c, m, d_out, nullptr, nullptr, nullptr, d_status, cnt, st);
+                      });
+}
 int fec_expand_message_xmd(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* dst, size_t dst_len,
                            size_t out_len, uint8_t* out, size_t n) try {
-  if (!ctx || (dst_len && !dst)) return FEC_E_ARG;
-  if (dst_len > h2c::MAX_DST || out_len > h2c::MAX_OUT) return FEC_E_UNSUPPORTED;
-  if (n && out_len && !out) return FEC_E_ARG;
-  const H2cCall c{kH2cXmd, 0, 0, h2c::make_params(dst, dst_len, out_len)};
-  return h2c_msg_call(ctx, c, msgs, msg_off, msg_len, out, out_len, nullptr, nullptr, 0, nullptr, 0, n);
+  return expand_message_xmd(ctx, kOnHost, {msgs, msg_off, msg_len}, dst, dst_len, out_len, out, nullptr, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_expand_message_xmd_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, const uint8_t* dst,
                                size_t dst_len, size_t out_len, uint8_t* d_out, uint8_t* d_status, size_t n, void* stream) try {
-  if (const int rc = dev_enter(ctx)) return rc;
-  if (dst_len && !dst) return FEC_E_ARG;
-  if (dst_len > h2c::MAX_DST || out_len > h2c::MAX_OUT) return FEC_E_UNSUPPORTED;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && out_len && !d_out) || !aligned16(d_out)) return FEC_E_ARG;
-  const H2cCall c{kH2cXmd, 0, 0, h2c::make_params(dst, dst_len, out_len)};
-  return launch_h2c(ctx, c, m, d_out, nullptr, nullptr, nullptr, d_status, n, stream);
+  return expand_message_xmd(ctx, on_device(stream), {d_msgs, d_msg_off, msg_len}, dst, dst_len, out_len, d_out, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
+static int hash_to_field(fec_ctx* ctx, Where w, int curve, const MessageArgs& ma, const uint8_t* dst, size_t dst_len, size_t count, uint64_t* u,
+                         uint8_t* d_status, size_t n) {
+  if (const int rc = first_of(h2c_args(ctx, w, curve, dst, dst_len), h2c_count_args(count))) return rc;
+  const H2cCall c{kH2cField, curve, 0, h2c::make_params(dst, dst_len, 32 * count)};
+  return message_call(ctx, w, n, FEC_OK, ma, arrays(secret_output(u, 32 * count).aligned(16)),
+                      [&](fec_ctx* cc, const Messages& m, uint64_t* d_u, size_t cnt, void* st) {
+                        return launch_h2c(cc, c, m, d_u, nullptr, nullptr, nullptr, d_status, cnt, st);
+                      });
+}
 int fec_hash_to_field(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* dst,
                       size_t dst_len, size_t count, uint64_t* u, size_t n) try {
-  int rc = h2c_args(ctx, curve, dst, dst_len);
-  if (rc == FEC_OK) rc = h2c_count_args(count);
-  if (rc != FEC_OK) return rc;
-  if (n && !u) return FEC_E_ARG;
-  const H2cCall c{kH2cField, curve, 0, h2c::make_params(dst, dst_len, 32 * count)};
-  return h2c_msg_call(ctx, c, msgs, msg_off, msg_len, u, 32 * count, nullptr, nullptr, 0, nullptr, 0, n);
+  return hash_to_field(ctx, kOnHost, curve, {msgs, msg_off, msg_len}, dst, dst_len, count, u, nullptr, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_hash_to_field_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                           const uint8_t* dst, size_t dst_len, size_t count, uint64_t* d_u, uint8_t* d_status, size_t n, void* stream) try {
-  int rc = dev_enter(ctx);
-  if (rc == FEC_OK) rc = h2c_args(ctx, curve, dst, dst_len);
-  if (rc == FEC_OK) rc = h2c_count_args(count);
-  if (rc != FEC_OK) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && !d_u) || !aligned16(d_u)) return FEC_E_ARG;
-  const H2cCall c{kH2cField, curve, 0, h2c::make_params(dst, dst_len, 32 * count)};
-  return launch_h2c(ctx, c, m, d_u, nullptr, nullptr, nullptr, d_status, n, stream);
+  return hash_to_field(ctx, on_device(stream), curve, {d_msgs, d_msg_off, msg_len}, dst, dst_len, count, d_u, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
 static int map_to_curve(fec_ctx* ctx, Where w, int curve, const uint64_t* u, uint64_t* xy, uint64_t* cand, uint8_t* legs, size_t n) {
@@ -2921,66 +2826,46 @@ int fec_map_to_curve_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_u, uin
   return map_to_curve(ctx, on_device(stream), curve, d_u, d_xy, d_cand, d_legs, n);
 } FEC_ABI_CATCH_STATUS
 
-int fec_hash_to_curve(fec_ctx* ctx, fec_curve curve, int mode, int method, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
-                      const uint8_t* dst, size_t dst_len, uint64_t* out, uint64_t* cand, uint8_t* legs, size_t n) try {
-  const int rc = h2c_mode_args(ctx, curve, mode, method, dst, dst_len);
-  if (rc != FEC_OK) return rc;
-  if (n && !out) return FEC_E_ARG;
+// (cand: 64 bytes per map, legs: one; both optional)
+static int hash_to_curve(fec_ctx* ctx, Where w, int curve, int mode, int method, const MessageArgs& ma, const uint8_t* dst, size_t dst_len, uint64_t* out,
+                         uint64_t* cand, uint8_t* legs, uint8_t* d_status, size_t n) {
+  if (const int rc = h2c_mode_args(ctx, w, curve, mode, method, dst, dst_len)) return rc;
   const size_t maps = mode == FEC_H2C_HASH ? 2 : 1;
   const H2cCall c{kH2cCurve, curve, mode == FEC_H2C_HASH ? H2C_HASH : H2C_ENCODE, h2c::make_params(dst, dst_len, 32 * maps)};
-  return h2c_msg_call(ctx, c, msgs, msg_off, msg_len, out, 96, nullptr, cand, 64 * maps, legs, maps, n);
+  return message_call(ctx, w, n, FEC_OK, ma,
+                      arrays(secret_output(out, 96).aligned(16), secret_output(cand, 64 * maps).aligned(16).opt(), secret_output(legs, maps).opt()),
+                      [&](fec_ctx* cc, const Messages& m, uint64_t* d_out, uint64_t* d_cand, uint8_t* d_legs, size_t cnt, void* st) {
+                        return launch_h2c(cc, c, m, d_out, nullptr, d_cand, d_legs, d_status, cnt, st);
+                      });
+}
+int fec_hash_to_curve(fec_ctx* ctx, fec_curve curve, int mode, int method, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
+                      const uint8_t* dst, size_t dst_len, uint64_t* out, uint64_t* cand, uint8_t* legs, size_t n) try {
+  return hash_to_curve(ctx, kOnHost, curve, mode, method, {msgs, msg_off, msg_len}, dst, dst_len, out, cand, legs, nullptr, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_hash_to_curve_dev(fec_ctx* ctx, fec_curve curve, int mode, int method, const uint8_t* d_msgs, const uint64_t* d_msg_off,
                           size_t msg_len, const uint8_t* dst, size_t dst_len, uint64_t* d_out, uint64_t* d_cand, uint8_t* d_legs,
                           uint8_t* d_status, size_t n, void* stream) try {
-  int rc = dev_enter(ctx);
-  if (rc == FEC_OK) rc = h2c_mode_args(ctx, curve, mode, method, dst, dst_len);
-  if (rc != FEC_OK) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && !d_out) || !aligned16(d_out) || !aligned16(d_cand)) return FEC_E_ARG;
-  const size_t maps = mode == FEC_H2C_HASH ? 2 : 1;
-  const H2cCall c{kH2cCurve, curve, mode == FEC_H2C_HASH ? H2C_HASH : H2C_ENCODE, h2c::make_params(dst, dst_len, 32 * maps)};
-  return launch_h2c(ctx, c, m, d_out, nullptr, d_cand, d_legs, d_status, n, stream);
+  return hash_to_curve(ctx, on_device(stream), curve, mode, method, {d_msgs, d_msg_off, msg_len}, dst, dst_len, d_out, d_cand, d_legs, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
 // (secp256k1: 96 uniform bytes under dst_prime; P-256: the plain template, SHA-256(msg || dst))
-static h2c::Params curve_h2c_params(int curve, const uint8_t* dst, size_t dst_len) {
-  return curve == FEC_SECP256K1 ? h2c::make_params(dst, dst_len, 96) : h2c::make_params_plain(dst, dst_len);
+static int curve_hash_to_curve(fec_ctx* ctx, Where w, int curve, const MessageArgs& ma, const uint8_t* dst, size_t dst_len, uint64_t* xy, uint8_t* inf,
+                               uint8_t* d_status, size_t n) {
+  if (const int rc = h2c_args(ctx, w, curve, dst, dst_len)) return rc;
+  const H2cCall c{kH2cCurve, curve, H2C_TRAIT, curve == FEC_SECP256K1 ? h2c::make_params(dst, dst_len, 96) : h2c::make_params_plain(dst, dst_len)};
+  return message_call(ctx, w, n, FEC_OK, ma, arrays(secret_output(xy, 64).aligned(16), secret_output(inf, 1)),
+                      [&](fec_ctx* cc, const Messages& m, uint64_t* d_xy, uint8_t* d_inf, size_t cnt, void* st) {
+                        return launch_h2c(cc, c, m, d_xy, d_inf, nullptr, nullptr, d_status, cnt, st);
+                      });
 }
-
 int fec_curve_hash_to_curve(fec_ctx* ctx, fec_curve curve, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len,
                             const uint8_t* dst, size_t dst_len, uint64_t* xy, uint8_t* inf, size_t n) try {
-  const int rc = h2c_args(ctx, curve, dst, dst_len);
-  if (rc != FEC_OK) return rc;
-  if (n && (!xy || !inf)) return FEC_E_ARG;
-  const H2cCall c{kH2cCurve, curve, H2C_TRAIT, curve_h2c_params(curve, dst, dst_len)};
-  return h2c_msg_call(ctx, c, msgs, msg_off, msg_len, xy, 64, inf, nullptr, 0, nullptr, 0, n);
+  return curve_hash_to_curve(ctx, kOnHost, curve, {msgs, msg_off, msg_len}, dst, dst_len, xy, inf, nullptr, n);
 } FEC_ABI_CATCH_STATUS
-
 int fec_curve_hash_to_curve_dev(fec_ctx* ctx, fec_curve curve, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
                                 const uint8_t* dst, size_t dst_len, uint64_t* d_xy, uint8_t* d_inf, uint8_t* d_status, size_t n,
                                 void* stream) try {
-  int rc = dev_enter(ctx);
-  if (rc == FEC_OK) rc = h2c_args(ctx, curve, dst, dst_len);
-  if (rc != FEC_OK) return rc;
-  Messages m;
-  if (dev_messages(d_msgs, d_msg_off, msg_len, n, m) || (n && (!d_xy || !d_inf)) || !aligned16(d_xy)) return FEC_E_ARG;
-  const H2cCall c{kH2cCurve, curve, H2C_TRAIT, curve_h2c_params(curve, dst, dst_len)};
-  return launch_h2c(ctx, c, m, d_xy, d_inf, nullptr, nullptr, d_status, n, stream);
-} FEC_ABI_CATCH_STATUS
-
-// Debug hook: fec_rfc6979_k with the caller's comparison constant instead of the curve's.  At least 2^254, so that a
-// candidate passes with probability 1/4 or more and the retry cap stays out of reach.
-int fec_debug_rfc6979_k(fec_ctx* ctx, fec_curve curve, const uint64_t* order_override, const uint64_t* sk, const uint8_t* msgs,
-                        const uint64_t* msg_off, size_t msg_len, uint64_t* k, uint8_t* status, size_t n) try {
-  if (!order_override || (order_override[3] >> 62) == 0) return FEC_E_ARG;
-  Rfc6979Order order;
-  for (int i = 0; i < 4; ++i) {
-    order.w[2 * i] = (u32)order_override[i];
-    order.w[2 * i + 1] = (u32)(order_override[i] >> 32);
-  }
-  return ecdsa_sign_msg_call(ctx, curve, &order, sk, msgs, msg_off, msg_len, k, status, n);
+  return curve_hash_to_curve(ctx, on_device(stream), curve, {d_msgs, d_msg_off, msg_len}, dst, dst_len, d_xy, d_inf, d_status, n);
 } FEC_ABI_CATCH_STATUS
 
 // Debug hooks: the ctx's work buffers as for_each_work_buffer (host_ctx.hpp) names them -- the list fec_ctx_wipe clears --

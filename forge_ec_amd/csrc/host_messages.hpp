@@ -29,62 +29,49 @@ inline int stage_messages(fec_ctx* c, const uint8_t* msgs, const u64* o, size_t 
   dm = Messages{bytes ? static_cast<const unsigned char*>(c->d_buf[kStageBody]) : nullptr, static_cast<const u64*>(c->d_buf[kStageBody + 1]), bytes};
   return FEC_OK;
 }
-// The host forms' engine, on a single-device or a multi-device ctx (host_ctx.hpp: sharded, chunked; one lane).  The layout
-// is checked once, here.  `a` names the call's arrays, the offsets among them as its one ragged() entry; per chunk the
-// engine stages them, then the chunk's message bytes and its offsets rebased to that range (stage_messages), and hands
-// body(ctx, d, messages, m, stream) the device side of all of it.  An array list with a secret in it (keys, and digests or
-// points whose message may be one) has the staging and the stream scratch cleared on every way out: chunked's rule.
-template <size_t N, class F>
-int with_messages(fec_ctx* ctx, size_t n, const HostArray (&a)[N], const uint8_t* msgs, const uint64_t* off, size_t msg_len, F body) {
-  size_t r = 0;
-  while (r < N && a[r].staged) ++r;
-  if (!ctx || r == N || !msg_layout_ok(msgs, off, msg_len, n)) return FEC_E_ARG;
-  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[N], size_t cnt, size_t) {
-    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
-    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
-      Messages dm;
-      const int rc = stage_messages(c, msgs, static_cast<const u64*>(d[r]), m, reb, st, dm);   // (d[r]: host, from the chunk's first element on)
-      return rc != FEC_OK ? rc : body(c, d, dm, m, st);
-    });
-  });
-}
-// The message arrays of a *_dev form, whose layout nobody checks (each lane checks its own range): 0, or what is wrong
-// with the pointers -- both FEC_E_ARG, apart only because some forms test the curve between the two.
-enum { kDevMsgsNull = 1, kDevMsgsMisaligned = 2 };
-inline int dev_messages(const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, size_t n, Messages& m) {
-  m = Messages{d_msgs, reinterpret_cast<const u64*>(d_msg_off), (u64)msg_len};
-  if ((n && !d_msg_off) || (msg_len && !d_msgs)) return kDevMsgsNull;
-  return (reinterpret_cast<uintptr_t>(d_msg_off) & 7u) ? kDevMsgsMisaligned : 0;
-}
 // The messages of a call as its entry point names them.
 struct MessageArgs {
   const uint8_t* msgs;
   const uint64_t* off;
   size_t len;
 };
-template <class... T, class F, size_t... I>
-int typed_message_chunk(F& body, fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t s, std::index_sequence<I...>) {
-  return body(c, m, static_cast<T*>(d[I + 1])..., cnt, static_cast<void*>(s));
+// The host forms' engine, on a single-device or a multi-device ctx (host_ctx.hpp: sharded, chunked; one lane).  The layout
+// is checked once, here.  `a` names the call's arrays, a[0] the offsets (ragged); per chunk the engine stages them, then
+// the chunk's message bytes and its offsets rebased to that range (stage_messages), and hands body(ctx, d, messages, m,
+// stream) the device side of all of it.  An array list with a secret in it (keys, and digests or points whose message may
+// be one) has the staging and the stream scratch cleared on every way out: chunked's rule.
+template <size_t N, class F>
+int with_messages(fec_ctx* ctx, size_t n, const HostArray (&a)[N], const MessageArgs& ma, F body) {
+  if (!msg_layout_ok(ma.msgs, ma.off, ma.len, n)) return FEC_E_ARG;
+  return sharded(ctx, n, a, [&](fec_ctx* child, const HostArray (&sa)[N], size_t cnt, size_t) {
+    std::vector<uint64_t> reb((child->chunk < cnt ? child->chunk : cnt) + 1);
+    return chunked(child, cnt, sa, 1, [&](fec_ctx* c, void* const* d, size_t, size_t m, hipStream_t st) -> int {
+      Messages dm;
+      const int rc = stage_messages(c, ma.msgs, static_cast<const u64*>(d[0]), m, reb, st, dm);   // (d[0]: host, from the chunk's first element on)
+      return rc != FEC_OK ? rc : body(c, d, dm, m, st);
+    });
+  });
 }
 // host_ctx.hpp's call for an entry point that takes messages, either form: body(ctx, messages, pointers..., count, stream).
-// *_dev: null message pointers are reported with the null arrays, misaligned offsets with the misaligned arrays, so
-// `value_rc` sits between the two.  Host: with_messages checks the layout, after everything else.
+// *_dev: nobody checks the layout (each lane checks its own range); null message pointers are reported with the null
+// arrays, misaligned offsets with the misaligned arrays, so `value_rc` sits between the two.  Host: with_messages checks
+// the layout, after everything else.
 template <class... T, class F>
 int message_call(fec_ctx* ctx, Where w, size_t n, int value_rc, const MessageArgs& ma, const std::tuple<Array<T>...>& list, F body) {
   return std::apply([&](const Array<T>&... a) -> int {
     if (w.dev) {
       if (const int rc = dev_enter(ctx)) return rc;
-      Messages m;
-      const int bad = dev_messages(ma.msgs, ma.off, ma.len, n, m);
-      if (bad == kDevMsgsNull || (n && (a.missing() || ...))) return FEC_E_ARG;
+      if ((n && !ma.off) || (ma.len && !ma.msgs) || (n && (a.missing() || ...))) return FEC_E_ARG;
       if (value_rc != FEC_OK) return value_rc;
-      return bad || (a.misaligned() || ...) ? FEC_E_ARG : body(ctx, m, a.ptr..., n, w.stream);
+      if ((reinterpret_cast<uintptr_t>(ma.off) & 7u) || (a.misaligned() || ...)) return FEC_E_ARG;
+      return body(ctx, Messages{ma.msgs, reinterpret_cast<const u64*>(ma.off), (u64)ma.len}, a.ptr..., n, w.stream);
     }
     if (!ctx || (n && (a.missing() || ...))) return FEC_E_ARG;
     if (value_rc != FEC_OK) return value_rc;
     const HostArray h[] = {ragged(ma.off, 8), a...};
-    return with_messages(ctx, n, h, ma.msgs, ma.off, ma.len, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t s) {
-      return typed_message_chunk<T...>(body, c, d, m, cnt, s, std::index_sequence_for<T...>{});
+    return with_messages(ctx, n, h, ma, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t s) {
+      auto chunk = [&](fec_ctx* cc, auto... p) { return body(cc, m, p...); };
+      return typed_chunk<T...>(chunk, c, d + 1, cnt, s, std::index_sequence_for<T...>{});
     });
   }, list);
 }

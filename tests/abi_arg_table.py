@@ -3,7 +3,8 @@ The bad-argument tables of the C ABI (tests/test_gpu_msg_args.py, tests/test_gpu
 
 An entry point is a list of arguments: "ctx"; "curve" (Ed25519 is among the bad values) or "curve3" (all three curves are
 supported: only 7 is bad); the message triple "msgs" / "off" / "len"; the host byte strings "dst" / "dst_len" and "info";
-("val", v) for a plain integer; par(name, good, *bad) for a value parameter and its illegal values; ("order", words); "n";
+("val", v) or ("val", v, name) for a plain integer, which a case can spoil once it has a name; par(name, good, *bad) for a
+value parameter and its illegal values; ("order", words); "n";
 "stream" (NULL); and arrays arr(name, bytes per element, required, alignment a *_dev form asks for).  Every buffer of a
 case is real, zero-filled and large enough for n = 8 with 16 bytes to spare, apart from the one pointer the case spoils.
 """
@@ -32,7 +33,9 @@ def _is_par(a):
 
 
 def _name(a):
-    return a if isinstance(a, str) else (a[1] if _is_par(a) else a[0])
+    if isinstance(a, str):
+        return a
+    return a[1] if _is_par(a) else (a[2] if a[0] == "val" and len(a) == 3 else a[0])
 
 
 class Buffers:
@@ -68,7 +71,7 @@ class Buffers:
 
 def call_args(spec, dev, buf, ctx, spoil):
     """The argument tuple of one case.  `spoil` maps an argument name to what replaces it: None, "+2" / "+4" / "+8" (the
-    pointer moved), an offsets array, or a value ("ctx", "curve", "len", "n", a par)."""
+    pointer moved), an array (the offsets, the words of "order"), or a value ("ctx", "curve", "len", "n", a par, a named val)."""
     out = []
     for arg in spec:
         name = _name(arg)
@@ -87,12 +90,12 @@ def call_args(spec, dev, buf, ctx, spoil):
             v = buf.host(buf.dst)
         elif name == "dst_len":
             v = len(DST)
-        elif name == "val":
+        elif not isinstance(arg, str) and arg[0] == "val":
             v = arg[1]
         elif _is_par(arg):
             v = arg[2]
         elif name == "order":
-            v = buf.host(np.array(arg[1], dtype=np.uint64))
+            v = buf.host(np.array(spoil.get("order", arg[1]), dtype=np.uint64))
         elif name == "n":
             v = N
         elif name == "stream":

@@ -1,6 +1,5 @@
 """
-GPU tests of what the from-the-message entry points share on the host side (fecgpu.hip: with_messages, dev_enter,
-dev_messages):
+GPU tests of what the from-the-message entry points share on the host side (host_messages.hpp: message_call, with_messages):
 
   * an all-empty batch -- n = 5, every message empty, msg_len = 0 and a NULL message pointer, the `bytes == 0` leg of the
     staging -- through one host entry point of every caller of the engine, against the models the per-family tests use
@@ -9,7 +8,9 @@ dev_messages):
     anything is launched (or the valid n = 0 call; or Ed25519 given to the challenge, which supports it, on zeroed points),
     whose expected codes (tests/golden/msg_arg_codes.json) were recorded
     from the library as it was before the seven host scaffolds and the *_dev prologues were merged.  Every buffer of a
-    case is real and large enough for n = 8, apart from the one pointer the case spoils.
+    case is real and large enough for n = 8, apart from the one pointer the case spoils;
+  * a second table (tests/golden/msg_value_arg_codes.json): a bad value parameter of the hash-to-curve calls, or a bad
+    override of fec_debug_rfc6979_k, alone and beside a pointer fault -- which of the two is reported.
 """
 import hashlib
 import json
@@ -152,9 +153,9 @@ HOST = {
                              [_arr("e", 32), "n"],
     "fec_schnorr_sign_msg": ["ctx", "curve", _arr("sk", 32)] + M +
                             [_arr("r_xy", 64), _arr("r_inf", 1), _arr("s", 32), _arr("sig_bytes", 64, False), _arr("status", 1), "n"],
-    "fec_expand_message_xmd": ["ctx"] + M + D + [("val", 48), _arr("out", 48), "n"],
-    "fec_hash_to_field": ["ctx", "curve"] + M + D + [("val", 2), _arr("u", 64), "n"],
-    "fec_hash_to_curve": ["ctx", "curve", ("val", 0), ("val", 0)] + M + D + [_arr("out", 96), _arr("cand", 128, False), _arr("legs", 2, False), "n"],
+    "fec_expand_message_xmd": ["ctx"] + M + D + [("val", 48, "out_len"), _arr("out", 48), "n"],
+    "fec_hash_to_field": ["ctx", "curve"] + M + D + [("val", 2, "count"), _arr("u", 64), "n"],
+    "fec_hash_to_curve": ["ctx", "curve", ("val", 0, "mode"), ("val", 0, "method")] + M + D + [_arr("out", 96), _arr("cand", 128, False), _arr("legs", 2, False), "n"],
     "fec_curve_hash_to_curve": ["ctx", "curve"] + M + D + [_arr("xy", 64), _arr("inf", 1), "n"],
 }
 ST, ST_OPT = _arr("status", 1), _arr("status", 1, False)
@@ -185,4 +186,51 @@ def test_return_codes_are_what_they_were(gpu_ctx):
         ["%s: %s" % (fn, c) for fn in ("fec_ed25519_derive_public_key", "fec_ed25519_derive_public_key_dev") for c in ("n=0,every array null",)] +
         ["%s: n=0,every array null" % fn for fn in DEV if fn != "fec_ed25519_derive_public_key_dev"] +
         ["fec_schnorr_challenge: curve=2", "fec_schnorr_challenge_dev: curve=2"])
+    gpu_ctx.check()
+
+
+# ---- the value parameters against the pointer checks ----
+# A fault in a value parameter of the four hash-to-curve calls (h2c.hpp: MAX_DST 255, MAX_OUT 8160, MAX_COUNT 255) and in
+# fec_debug_rfc6979_k's override: alone, and with a pointer fault beside it -- which of the two the call reports.
+VALUE_GOLDEN = os.path.join(HERE, "golden", "msg_value_arg_codes.json")
+DST_FAULTS = [("dst_len=256", {"dst_len": 256}), ("dst=null,dst_len=5", {"dst": None, "dst_len": 5})]
+VALUE_FAULTS = {
+    "fec_expand_message_xmd": DST_FAULTS + [("out_len=8161", {"out_len": 8161})],
+    "fec_hash_to_field": DST_FAULTS + [("count=0", {"count": 0}), ("count=256", {"count": 256})],
+    "fec_hash_to_curve": DST_FAULTS + [("dst_len=0", {"dst_len": 0}), ("mode=2", {"mode": 2}), ("method=1", {"method": 1}), ("method=3", {"method": 3})],
+    "fec_curve_hash_to_curve": DST_FAULTS,
+    "fec_debug_rfc6979_k": [("order top two bits clear", {"order": np.array([0, 0, 0, 1 << 61], dtype=np.uint64)})],
+}
+
+
+def _value_cases(fn, spec, dev):
+    first = next(a for a in spec if isinstance(a, tuple) and len(a) == 4 and a[2])     # the first required array
+    aligned = next(a for a in spec if isinstance(a, tuple) and len(a) == 4 and a[3])   # the first aligned one: 16 bytes, every one here
+    beside = [("", {}), ("," + first[0] + "=null", {first[0]: None}), (",off=null", {"off": None})]
+    if dev:
+        beside += [(",off+4", {"off": "+4"}), (",%s+8" % aligned[0], {aligned[0]: "+8"}), (",ctx=multi", {"ctx": "multi"})]
+    return [(fault + name, dict(spoil, **more)) for fault, spoil in VALUE_FAULTS[fn] for name, more in beside]
+
+
+def value_fault_codes(gpu_ctx):
+    """{case id: status} of the cases above (the golden file is this, recorded from the library as it was before the
+    from-the-message pairs became one function each)"""
+    import forge_ec_amd as F
+    from forge_ec_amd import _lib as L
+    host = {fn: HOST[fn] for fn in VALUE_FAULTS}
+    dev = {fn + "_dev": DEV[fn + "_dev"] for fn in VALUE_FAULTS if fn + "_dev" in DEV}
+    extra = {fn: _value_cases(fn, spec, False) for fn, spec in host.items()}
+    extra.update({fn: _value_cases(fn[:-4], spec, True) for fn, spec in dev.items()})
+    with F.Context(devices=[0, 0]) as multi:
+        got = run_table(L.lib(), gpu_ctx._h, multi._h, ((host, False), (dev, True)), extra)
+    return {k: v for k, v in got.items() if k in {"%s: %s" % (fn, c) for fn, cases in extra.items() for c, _ in cases}}
+
+
+def test_value_faults_beside_pointer_faults_return_what_they_did(gpu_ctx):
+    want = json.load(open(VALUE_GOLDEN))
+    got = value_fault_codes(gpu_ctx)
+    assert len(got) ==3 * (3 + 4 + 6 + 2 + 1) + 6 * (3 + 4 + 6 + 2)
+    assert sorted(got) == sorted(want)
+    assert {k: v for k, v in got.items() if want[k] != v} == {}
+    assert 0 not in want.values()                       # every case is rejected: nothing was launched
     gpu_ctx.check()

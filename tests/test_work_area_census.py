@@ -150,15 +150,14 @@ def _with_pair_function(fns, name):
 def test_host_rows_are_the_entry_points_that_stage_secrets():
     parity, helpers = _secret_entry_points("fecgpu.hip")
     canon, canon_helpers = _secret_entry_points("canon.hip")
-    assert set(helpers) == {"digest_call", "eddsa_sign_call", "bip340_sign_call", "ecdsa_sign_msg_call", "schnorr_sign_msg_call", "h2c_msg_call",
-                            # one function per host / *_dev pair
-                            "batch_ecdh", "derive_key", "ecdh_derive_key", "ecdh_exchange", "ecdsa_sign", "x25519", "curve25519_mul", "map_to_curve"}
+    assert set(helpers) == {"sha_digest", "eddsa_sign", "bip340_sign", "ecdsa_sign_msg", "schnorr_sign_msg", "expand_message_xmd", "hash_to_field",
+                            "hash_to_curve", "curve_hash_to_curve", "batch_ecdh", "derive_key", "ecdh_derive_key", "ecdh_exchange", "ecdsa_sign",
+                            "x25519", "curve25519_mul", "map_to_curve"}
     assert set(canon_helpers) == {"canon_" + c for c in (
         "mul_base_secret", "public_key", "ecdsa_sign_digest", "ecdsa_sign_msg", "rfc6979_k", "bip340_sign_msg", "ed25519_sign_msg", "x25519",
         "x25519_base", "ecdsa_sign_recoverable_digest", "seckey_tweak_add", "bip32_derive_priv")}
-    for n in set(helpers) | set(canon_helpers):   # a *_dev form is told apart by what it hands such a function
-        if not n.endswith("_call"):
-            assert "Where w" in functions(os.path.join(CSRC, "fecgpu.hip" if n in helpers else "canon.hip"))[n], n
+    for n in set(helpers) | set(canon_helpers):   # one function per host / *_dev pair: a *_dev form is told apart by what it hands it
+        assert "Where w" in functions(os.path.join(CSRC, "fecgpu.hip" if n in helpers else "canon.hip"))[n], n
     assert len(parity) >= 20 and len(canon) >= 12
     assert sorted(parity | canon) == T.HOST_FUNCTIONS, sorted((parity | canon) ^ set(T.HOST_FUNCTIONS))
 
