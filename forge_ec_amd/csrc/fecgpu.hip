@@ -2348,6 +2348,20 @@ int fec_ctx_debug_force_fault(fec_ctx* ctx, int enabled) try {
   return FEC_OK;
 } FEC_ABI_CATCH_STATUS
 
+// Debug hook: the scheduler launches of this ctx (sched_env) are sized as if its device had `cus` compute units -- the
+// grids, per-workgroup ranges, slot-count choice and P-256 CU split of a smaller or partitioned chip, on whatever device
+// the ctx has.  0 restores the device's own count; a value above it is clamped to it (a launch never gets more
+// persistent workgroups than there are CUs).  Fewer workgroups than CUs is always safe: they do not depend on each other.
+int fec_ctx_debug_set_cus(fec_ctx* ctx, unsigned cus) try {
+  if (!ctx) return FEC_E_ARG;
+  if (is_multi(ctx)) {
+    for (fec_ctx* c : ctx->children) c->debug_cus = cus;
+    return FEC_OK;
+  }
+  ctx->debug_cus = cus;
+  return FEC_OK;
+} FEC_ABI_CATCH_STATUS
+
 int fec_ctx_fixed_prefix_bits(fec_ctx* ctx, fec_curve curve) try {
   FEC_FIRST_DEVICE(ctx);
   if (!ctx || !curve_ok(curve)) return FEC_E_ARG;

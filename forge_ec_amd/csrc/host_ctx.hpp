@@ -75,6 +75,7 @@ struct fec_ctx {
   unsigned* h_err = nullptr;       // host view
   unsigned* d_err = nullptr;       // device view of the same word
   unsigned debug_force_fault = 0;  // fec_ctx_debug_force_fault
+  unsigned debug_cus = 0;          // fec_ctx_debug_set_cus: the CU count the scheduler launches are sized for (0 = the device's own)
   // Fixed-base prefix tables of the reference's generator() (kernels.hpp: SchedEnv; fecgpu.hip: ensure_gen_prefix):
   // built by the fixed-base launch that takes the ctx past prefix_after multiplications, 2^prefix_bits entries; 0 = off.
   u32* d_gen_prefix[3] = {nullptr, nullptr, nullptr};
@@ -308,6 +309,7 @@ inline SchedEnv sched_env(const fec_ctx* ctx) {
   SchedEnv e;
   e.err = ctx->d_err;
   e.cus = ctx->prop.multiProcessorCount > 0 ? (unsigned)ctx->prop.multiProcessorCount : 256u;
+  if (ctx->debug_cus != 0 && ctx->debug_cus < e.cus) e.cus = ctx->debug_cus;   // (never more workgroups than CUs)
   e.force_fault = ctx->debug_force_fault;
   for (int c = 0; c < 3; ++c) {
     e.gen[c] = reinterpret_cast<const u32*>(ctx->d_gen[c]);

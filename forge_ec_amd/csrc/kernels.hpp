@@ -37,7 +37,8 @@ struct SchedGrid {
 inline SchedGrid sched_grid(const SchedEnv& env, size_t n, unsigned cu_divisor = 1) {
   const unsigned cus = env.cus ? env.cus : 256u;
   const unsigned cap = cu_divisor > 1 && cus >= cu_divisor ? cus / cu_divisor : cus;
-  size_t grid = (n + 63) / 64;
+  size_t grid = n / 64;   // (rounded down: rounded up, 65 elements went to two workgroups of 33 and 32)
+  if (grid < 1) grid = 1;
   if (grid > cap) grid = cap;
   const unsigned per_wg = (unsigned)((n + grid - 1) / grid);
   return {(unsigned)((n + per_wg - 1) / per_wg), per_wg};

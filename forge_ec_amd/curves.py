@@ -85,6 +85,11 @@ class Context:
         """fec_ctx_debug_force_fault: test hook -- scheduler kernels raise their fault word at once."""
         _check(self._lib.fec_ctx_debug_force_fault(self._h, 1 if enabled else 0), "fec_ctx_debug_force_fault")
 
+    def debug_set_cus(self, cus):
+        """fec_ctx_debug_set_cus: test hook -- scheduler launches are sized as for a device of `cus` compute units
+        (0 = the device's own count; larger values are clamped to it)."""
+        _check(self._lib.fec_ctx_debug_set_cus(self._h, int(cus)), "fec_ctx_debug_set_cus")
+
     def set_fixed_prefix_bits(self, bits):
         """fec_ctx_set_fixed_prefix_bits: size of the generator's fixed-base prefix tables (0 = off, default 24)."""
         _check(self._lib.fec_ctx_set_fixed_prefix_bits(self._h, int(bits)), "fec_ctx_set_fixed_prefix_bits")

@@ -172,7 +172,7 @@ int fec_ctx_create(fec_ctx** out, int device);
  * "gather" is the D2H copy of each shard, there is no device-to-device exchange.  Results are
  * identical to a single-device ctx.  Entry points that are not element-wise (fec_multi_scalar_mul,
  * fec_ecdsa_batch_verify, fec_schnorr_batch_verify*, fec_generator*, the measurement hooks)
- * run on devices[0]; fec_ctx_wipe, fec_ctx_check, fec_ctx_set_chunk, the fec_ctx_set_fixed_prefix_* calls, fec_ctx_build_fixed_prefix, fec_ctx_set_side_stream_max and fec_ctx_debug_force_fault apply
+ * run on devices[0]; fec_ctx_wipe, fec_ctx_check, fec_ctx_set_chunk, the fec_ctx_set_fixed_prefix_* calls, fec_ctx_build_fixed_prefix, fec_ctx_set_side_stream_max, fec_ctx_debug_force_fault and fec_ctx_debug_set_cus apply
  * to every shard worker;
  * the *_dev entry points take device pointers of ONE device and return FEC_E_UNSUPPORTED; shards that are already
  * RESIDENT in the devices' memory go through fec_multi_batch_*_dev (below), which also gathers the results onto one
@@ -455,6 +455,11 @@ int fec_ctx_check(fec_ctx* ctx);
  * multiplication, also inside the composed entry points) raises its fault word at once, exactly as its watchdog
  * would: outputs are zero-filled and the call (or fec_ctx_check) returns FEC_E_LAUNCH. */
 int fec_ctx_debug_force_fault(fec_ctx* ctx, int enabled);
+/* Debug / test hook: the scheduler-kernel launches of this ctx are sized as if its device had `cus` compute units --
+ * grid, elements per workgroup, slot-count choice and the P-256 CU split of a smaller (or partitioned) chip, whatever
+ * device the ctx is on.  0 restores the device's own count; a value above it is clamped to it, so a launch never has
+ * more persistent workgroups than the device has CUs.  Results do not depend on it. */
+int fec_ctx_debug_set_cus(fec_ctx* ctx, unsigned cus);
 
 /* Fixed-base prefix tables.  The state of Curve::multiply(generator(), k) after its first `bits` steps depends on the
  * first `bits` scalar bits alone, so it is computed once -- one step of the reference's loop per entry and level, with

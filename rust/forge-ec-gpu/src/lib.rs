@@ -28,6 +28,7 @@ extern "C" {
     fn fec_ctx_wipe(ctx: *mut FecCtx) -> c_int;
     fn fec_ctx_check(ctx: *mut FecCtx) -> c_int;
     fn fec_ctx_debug_force_fault(ctx: *mut FecCtx, enabled: c_int) -> c_int;
+    fn fec_ctx_debug_set_cus(ctx: *mut FecCtx, cus: c_uint) -> c_int;
     fn fec_ctx_set_fixed_prefix_bits(ctx: *mut FecCtx, bits: c_uint) -> c_int;
     fn fec_ctx_fixed_prefix_bits(ctx: *mut FecCtx, curve: c_int) -> c_int;
     fn fec_ctx_build_fixed_prefix(ctx: *mut FecCtx, curve: c_int) -> c_int;
@@ -199,6 +200,13 @@ impl GpuContext {
     pub fn debug_force_fault(&mut self, enabled: bool) -> Result<()> {
         // SAFETY: self.raw is a live ctx.
         check(unsafe { fec_ctx_debug_force_fault(self.raw, enabled as c_int) })
+    }
+
+    /// Test hook (`fec_ctx_debug_set_cus`): scheduler launches are sized for `cus` compute units (0 = the device's own
+    /// count; larger values are clamped to it).
+    pub fn debug_set_cus(&mut self, cus: u32) -> Result<()> {
+        // SAFETY: self.raw is a live ctx.
+        check(unsafe { fec_ctx_debug_set_cus(self.raw, cus as c_uint) })
     }
 
     /// Test hook (`fec_debug_work_area_count` / `fec_debug_work_area_read`), not part of the reference's surface: the

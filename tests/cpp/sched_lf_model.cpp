@@ -8,7 +8,9 @@
 // advances its elements' step counters and draws their next ring at random.  Checked: every element of the range is
 // claimed exactly once and advanced exactly `steps` times, no slot is ever in two batches at once, no ring entry is read
 // before it is written or overwritten unread, every thread terminates (a watchdog turns a stuck run into a failure), for
-// slot counts, ranges and step counts that cover the initial fill, steady state, the tail and the degenerate sizes.
+// slot counts, ranges and step counts that cover the initial fill, steady state, the tail and the degenerate sizes --
+// and ranges of 33 000 and 70 000 short elements, which take ring F (one entry per finished element) past position
+// 32 x RING, where its five-bit lap tag wraps (rings D and A wrap in every longer run).
 // Host threads are descheduled for long stretches at arbitrary points, which the wavefronts of a workgroup are not: the
 // first form of the protocol (entries tagged with a generation only, the producer writing without looking) survived the
 // whole GPU suite and soaks and was caught HERE -- a consumer that sleeps between its HEAD += and its read is lapped by the
@@ -222,7 +224,7 @@ void wavefront(Workgroup& w, int id, unsigned seed) {
   }
 }
 
-bool run(int slots, int range, int steps, unsigned seed) {
+bool run(int slots, int range, int steps, unsigned seed, uint32_t* f_positions = nullptr) {
   Workgroup w(slots, range, steps);
   std::vector<std::thread> t;
   for (int i = 0; i < kWaves; ++i) t.emplace_back(wavefront, std::ref(w), i, seed * 977u + (unsigned)i);
@@ -239,6 +241,13 @@ bool run(int slots, int range, int steps, unsigned seed) {
     std::fprintf(stderr, "FAIL: counters not back at rest (slots %d, range %d)\n", slots, range);
     return false;
   }
+  // ring F has taken the initial slots and one entry per finished element
+  const uint32_t live = (uint32_t)(range < slots ? range : slots);
+  if (w.res_f.load() != live + (uint32_t)range) {
+    std::fprintf(stderr, "FAIL: ring F at position %u, not %u (slots %d, range %d)\n", w.res_f.load(), live + (uint32_t)range, slots, range);
+    return false;
+  }
+  if (f_positions) *f_positions = w.res_f.load();
   return true;
 }
 
@@ -257,5 +266,20 @@ int main(int argc, char** argv) {
           ++runs;
         }
   std::printf("sched_lf model: %d runs, every element claimed once and stepped to the end, all queues back at rest\n", runs);
+  // Ring F past its lap wrap.  Once, not `rounds` times: a run moves 70 to 250 times the entries of the largest run
+  // above, and the interleavings that matter here are those around ONE position.
+  int wraps = 0;
+  for (int slots : {864, 1024})
+    for (int range : {33000, 70000})
+      for (int steps : {1, 3}) {
+        uint32_t f = 0;
+        if (!run(slots, range, steps, (unsigned)(slots * 31 + range * 3 + steps), &f)) return 1;
+        wraps += f > 32u * (slots < 1024 ? 1024u : 2048u);
+      }
+  if (wraps != 6) {   // (33 000 elements do not take the 2 048-position ring round 32 times)
+    std::fprintf(stderr, "FAIL: ring F passed its lap wrap in %d of the long runs, not 6\n", wraps);
+    return 1;
+  }
+  std::printf("sched_lf model: 8 long runs, ring F past its lap wrap in %d of them\n", wraps);
   return 0;
 }

@@ -3,34 +3,16 @@ The multiply-family kernels on inputs that force their rare legs (tests/golden/k
 tests/rare_legs.json): every case is a (scalar, point) pair on which a named leg fires in an operation whose result the
 kernel keeps.  Results are compared bit-exactly with the fixture (py_model) and with the threaded C oracle.
 """
-import json
-import os
-
 import numpy as np
 import pytest
 
+import sched_geometry
 import vectors as V
+from forcing_cases import FORCING, cases as _cases, mixed as _mixed
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FORCING = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_forcing_vectors.json")))
 THREADS = 16
 NAMES = {0: "secp256k1", 1: "P-256", 2: "Ed25519"}
 CHUNK = 1 << 12
-
-
-def _cases(curve, affine=False):
-    """the curve's cases, interleaved across families (case j of every family, then case j + 1): any run of as many
-    positions as there are families holds one case of each"""
-    cs = [c for c in FORCING["cases"] if c["curve"] == curve and (not affine or c["point"][8:12] == [1, 0, 0, 0])]
-    fams = list(dict.fromkeys(c["family"] for c in cs))
-    rank = {}
-    for c in cs:
-        rank[id(c)] = (sum(1 for d in cs[:cs.index(c)] if d["family"] == c["family"]), fams.index(c["family"]))
-    cs.sort(key=lambda c: rank[id(c)])
-    k = np.array([c["scalar"] for c in cs], dtype=np.uint64)
-    p = np.array([c["point"] for c in cs], dtype=np.uint64)
-    e = np.array([c["expect"] for c in cs], dtype=np.uint64)
-    return k, p, e, [c["family"] for c in cs]
 
 
 def _same(got, want, what):
@@ -39,27 +21,13 @@ def _same(got, want, what):
         raise AssertionError("%s: %d rows differ, first at %s" % (what, len(bad), list(bad[:8])))
 
 
-def _mixed(curve, n, at, stream):
-    """n random canonical (scalar, point) pairs with the crafted cases placed at the indices `at`, cycling over the
-    interleaved cases: every family sits at some index once `at` has as many entries as the curve has families"""
-    k, p, e, fam = _cases(curve)
-    at = sorted(set(at))
-    assert len(at) >= len(set(fam)), "too few positions to place every family"
-    ks, ps = V.scalars(n, curve, stream), V.points(n, curve, stream + 1)
-    idx = np.arange(len(at)) % k.shape[0]
-    ks[at], ps[at] = k[idx], p[idx]
-    return ks, ps, (np.asarray(at), e[idx])
-
-
 def _range_edges(n):
     """Element indices at the edges of the P-256 / Ed25519 schedulers' workgroup ranges (p256_launch_mul,
-    ed_launch_mul: grid = min(ceil(n / 64), CUs), per_wg = ceil(n / grid), workgroup w owns [w * per_wg, ...)) and of
+    ed_launch_mul; sched_geometry.sched_grid mirrors their rule: workgroup w owns [w * per_wg, ...)) and of
     the 64-element claims inside a range, including the last (partial) claim; plus wavefront edges 0 / 31 / 32 / 63."""
     import torch
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    grid = min((n + 63) // 64, cus)
-    per_wg = (n + grid - 1) // grid
-    grid = (n + per_wg - 1) // per_wg
+    grid, per_wg = sched_geometry.sched_grid(cus, n)
     at = {0, 31, 32, 63, n - 1}
     for w in (0, 1, grid // 2, grid - 2, grid - 1):
         lo, hi = w * per_wg, min(n, (w + 1) * per_wg)

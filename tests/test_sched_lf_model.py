@@ -2,7 +2,8 @@
 (tests/cpp/sched_lf_model.cpp): twelve threads as the twelve wavefronts of a scheduler workgroup, the same counters,
 atomics, entry format and batch policy; every element claimed once and stepped to its end, no slot in two batches, no
 entry overwritten unread, every thread terminates -- under the OS's arbitrary descheduling, which is how the first form
-of the protocol (no consumed flag) was caught.  Also checked: the constants the model restates are the header's."""
+of the protocol (no consumed flag) was caught; ring F, which takes one entry per finished element, goes past the
+position where its lap tag wraps.  Also checked: the constants the model restates are the header's."""
 import os
 import re
 import subprocess
@@ -33,3 +34,5 @@ def test_lock_free_queue_model_runs_clean():
     r = subprocess.run([EXE, "4"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "540 runs, every element claimed once" in r.stdout
+    # 33 000 and 70 000 elements of 1 and 3 steps: ring F's lap tag wraps (position 32 x 1 024, 32 x 2 048)
+    assert "8 long runs, ring F past its lap wrap in 6 of them" in r.stdout
