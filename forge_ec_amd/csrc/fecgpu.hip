@@ -1241,6 +1241,9 @@ int launch_schnorr_sign(fec_ctx* ctx, int curve, const SchnorrSignIo& io, size_t
   const u32* gen = reinterpret_cast<const u32*>(ctx->d_gen[curve]);
   // sk into scal[n, 2n) first: the one step here that can refuse, so it comes before anything is queued or timed.  The
   // region belongs to this stream's scratch, which `area` holds, and the copy is in stream order before its readers.
+  // The copy READS io.sk, which the ctx's previous launch on another stream may still be writing: the stream is ordered
+  // behind that launch here (prepare_generator orders only for Ed25519), and `Launch L` below then finds it ordered.
+  order_after_previous(ctx, st);
   if (hipMemcpyAsync(scal + n * 8, io.sk, n * 32, hipMemcpyDeviceToDevice, st) != hipSuccess) {
     (void)hipGetLastError();
     return FEC_E_DEVICE;

@@ -9,7 +9,8 @@ d_win_scratch, the secret family shares the comb tables and the error word, and 
 to the next call on another stream.  tests/test_canon_launch_order.py holds the promise on the text of canon.hip; here two
 calls really are in flight.
 
-The gate (_run) makes a missing ordering deterministic instead of hoped-for.  After a warm-up of the same calls on the same
+The gate (tests/stream_gate.py, shared with tests/test_gpu_parity_streams.py; _run here) makes a missing ordering
+deterministic instead of hoped-for.  After a warm-up of the same calls on the same
 streams (growth of a work area, the first build of a comb table and the first allocation of a stream's scratch all
 synchronise, and would hide a race), a chain of fp32 matmuls is queued on the stream of call A and event e_fill behind it;
 a trivial op and event e_probe go to the other stream and the host waits for e_probe.  Then A, B, ... are issued back to
@@ -23,8 +24,8 @@ before they ordered their stream ahead of their first kernel.
 Sizing, measured on an MI355X after warm-up (time.perf_counter round the issue loop, event timing round the filler; each
 run prints both under -s): the host issues a pair of calls in 0.03 - 0.11 ms and the longest chain here, four calls with
 the tensor unpacking between them, in 0.19 ms.  FILL_STEPS = 64 matmuls of 2048^2 in fp32 take 7.7 - 9.0 ms: forty times
-the longest issue (ten times would leave 2 ms, no more than one hiccup of the host), and the 133 gated runs of the module
-take about 7 s together.  The two event assertions check the sizing on every run.
+the longest issue (ten times would leave 2 ms, no more than one hiccup of the host; one such hiccup, an issue of 0.54 ms, is
+on record: still a fourteenth of the filler), and the 147 gated runs of the module take about 7 s together.  The two event assertions check the sizing on every run.
 
 The streams: HIP spreads a process's streams over a few hardware queues (four by default) by the
 number of users each queue has, and two streams that share a queue run one after the other -- two torch streams created
@@ -37,9 +38,7 @@ Inputs: n = 64 * 3 + 5 elements (three full wavefronts and a ragged one) cycling
 call A starts the cycle at record 0 and call B at record 3, so their inputs and expected outputs differ at every element.
 Verifier batches are all valid (the model says so), so a mix-up shows as rejects.  Outputs are pre-filled with a sentinel.
 """
-import hashlib
 import random
-import time
 
 import numpy as np
 import pytest
@@ -49,7 +48,9 @@ import canon_msg_ref as R
 import canon_recover_ref as RV
 import canon_sign_ref as S
 import canon_x25519_ref as X
+import canon_wallet_ref as W
 from oracle import canon_model as M
+from stream_gate import Call, Gate, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -57,14 +58,9 @@ N = 64 * 3 + 5
 NREC = 8
 ROT_A, ROT_B = 0, 3
 FILL_DIM, FILL_STEPS = 2048, 64
-STREAMS = 6      # candidates for the pair s1, s2 (gear)
 NAMES = ["secp256k1", "p256", "ed25519"]
 MODEL = dict(zip(NAMES, [M.SECP256K1, M.P256, M.ED25519]))
 LENGTHS = [1, 31, 55, 64, 135, 136, 137, 200]   # message lengths of the eight records: either side of the hashes' block edges
-
-_G = {}          # the two streams, the events and the filler's tensors: alive as long as the module (the ctx records an event on
-                 # the stream of its previous call, so a stream must outlive the next call of the session's ctx)
-TIMINGS = []     # (host issue seconds, filler milliseconds) of every gated run
 
 
 # ---- model records, computed once --------------------------------------------------------------------------------------
@@ -186,32 +182,6 @@ def out_bytes(width=None, fill=0xEE):
 
 def out_status():
     return out_bytes(None, 9)
-
-
-class Call:
-    """one *_dev call on tensors of its own: run(stream) issues it (stream: a torch stream, or None for the ctx's own);
-    outs: (tensor, sentinel) pairs; want: what the model says each holds afterwards, one row per element"""
-
-    def __init__(self, name, run, outs, want):
-        self.name, self.run, self.outs = name, run, outs
-        self.want = [np.ascontiguousarray(w).view(np.uint8).reshape(N, -1) for w in want]
-        assert len(outs) == len(want)
-
-    def reset(self):
-        for t, fill in self.outs:
-            t.fill_(fill)
-
-    def bad(self):
-        """elements of any output that differ from the model"""
-        wrong = set()
-        for (t, _), w in zip(self.outs, self.want):
-            got = t.cpu().numpy().view(np.uint8).reshape(N, -1)
-            wrong.update(int(i) for i in np.nonzero((got != w).any(axis=1))[0])
-        return sorted(wrong)
-
-
-def ptr(s):
-    return None if s is None else s.cuda_stream
 
 
 ZEROS, ONES = np.zeros(N, dtype=np.uint8), np.ones(N, dtype=np.uint8)
@@ -473,6 +443,69 @@ def c_decompress(ctx, rot, curve, pk_len):
                 [o, st_], [xy(cyc(curve, rot, lambda e: e["Q"])), ZEROS])
 
 
+_wallet = {}
+
+
+def wallet_recs():
+    """per secp256k1 record: a Merkle root and the Taproot output key of the x-only key; a depth-3 path and its CKDpub"""
+    if not _wallet:
+        rng = random.Random(0x57A7)
+        out = []
+        for e in recs("secp256k1"):
+            root = rng.randbytes(32)
+            path = [rng.randrange(B32.HARDENED) for _ in range(3)]
+            tap, child = W.taproot_output_key(e["bpk"], root), W.derive_pub_path(e["pk33"], e["cc"], path)
+            assert tap[2] == 0 and child[4] == 0
+            out.append(dict(root=root, path=path, tap=tap, child=child))
+        _wallet["recs"] = out
+    return _wallet["recs"]
+
+
+def wcyc(rot, f):
+    ws = wallet_recs()
+    return [f(ws[(i + rot) % NREC]) for i in range(N)]
+
+
+def c_taproot_output_key(ctx, rot):
+    dev = _canon(ctx, "secp256k1")
+    pk, rt = up(rows(cyc("secp256k1", rot, lambda e: e["bpk"]))), up(rows(wcyc(rot, lambda w: w["root"])))
+    out, par, st_ = out_bytes(32), out_status(), out_status()
+    return Call("taproot_output_key_dev",
+                lambda st: dev.taproot_output_key_dev(pk.data_ptr(), 32, rt.data_ptr(), out[0].data_ptr(), par[0].data_ptr(), st_[0].data_ptr(), N, ptr(st)),
+                [out, par, st_], [rows(wcyc(rot, lambda w: w["tap"][0])), np.array(wcyc(rot, lambda w: w["tap"][1]), dtype=np.uint8), ZEROS])
+
+
+def c_derive_pub_path(ctx, rot):
+    from forge_ec_amd.canon import CanonBip32
+    dev = CanonBip32(ctx)
+    pk, cc = up(rows(cyc("secp256k1", rot, lambda e: e["pk33"]))), up(rows(cyc("secp256k1", rot, lambda e: e["cc"])))
+    idx = up(np.array(wcyc(rot, lambda w: w["path"]), dtype=np.uint32))
+    out, occ, fp, h160, st_ = out_bytes(33), out_bytes(32), out_bytes(4), out_bytes(20), out_status()
+    return Call("derive_pub_path_dev depth 3",
+                lambda st: dev.derive_pub_path_dev(pk.data_ptr(), cc.data_ptr(), N, idx.data_ptr(), 3, out[0].data_ptr(), occ[0].data_ptr(),
+                                                   fp[0].data_ptr(), h160[0].data_ptr(), st_[0].data_ptr(), N, ptr(st)),
+                [out, occ, fp, h160, st_], [rows(wcyc(rot, lambda w, k=k: w["child"][k])) for k in range(4)] + [ZEROS])
+
+
+def c_digest20(ctx, rot, which):
+    from forge_ec_amd.canon import CanonKeccak
+    dev = CanonKeccak(ctx)
+    m, off, total = up_msgs(cyc("secp256k1", rot, lambda e: e["msg"]))
+    out, st_ = out_bytes(20), out_status()
+    fn, model = (dev.ripemd160_dev, W.ripemd160) if which == "ripemd160" else (dev.hash160_dev, W.hash160)
+    return Call(which + "_dev", lambda st: fn(m.data_ptr(), off.data_ptr(), total, out[0].data_ptr(), st_[0].data_ptr(), N, ptr(st)),
+                [out, st_], [rows(cyc("secp256k1", rot, lambda e: model(e["msg"]))), ZEROS])
+
+
+def c_pubkey_hash160(ctx, rot):
+    from forge_ec_amd.canon import CanonKeccak
+    dev = CanonKeccak(ctx)
+    pk = up(rows(cyc("secp256k1", rot, lambda e: e["pk33"])))
+    out = out_bytes(20)
+    return Call("pubkey_hash160_dev 33", lambda st: dev.pubkey_hash160_dev(pk.data_ptr(), 33, out[0].data_ptr(), N, ptr(st)),
+                [out], [rows(cyc("secp256k1", rot, lambda e: W.hash160(e["pk33"])))])
+
+
 # every user of ctx->d_verify, by the layout it gives the buffer
 VERIFY_USERS = {
     "ecdsa_verify secp256k1": (c_ecdsa_verify, ("secp256k1",), "ecdsa"),
@@ -492,6 +525,8 @@ VERIFY_USERS = {
     "pubkey_tweak_add p256": (c_pubkey_tweak_add, ("p256",), "tweak"),
     "derive_pub shared": (c_derive_pub, (True,), "tweak"),
     "derive_pub each": (c_derive_pub, (False,), "tweak"),
+    "taproot_output_key": (c_taproot_output_key, (), "tweak"),
+    "derive_pub_path depth 3": (c_derive_pub_path, (), "tweak"),
 }
 # the call that goes ahead of a user of each layout: a user of another one
 OTHER_LAYOUT = {"ecdsa": "bip340_verify_msg", "sig": "ecdsa_recover secp256k1 key", "recover": "derive_pub each", "tweak": "ecdsa_verify_msg p256 33"}
@@ -516,92 +551,15 @@ PER_STREAM = {
     "seckey_tweak_add secp256k1": (c_seckey_tweak_add, ("secp256k1",)),
     "keccak256": (c_keccak256, ()),
     "decompress p256 33": (c_decompress, ("p256", 33)),
+    "ripemd160": (c_digest20, ("ripemd160",)),
+    "hash160": (c_digest20, ("hash160",)),
+    "pubkey_hash160 33": (c_pubkey_hash160, ()),
 }
 
 
-# ---- the gate ----------------------------------------------------------------------------------------------------------
-def gear():
-    import torch
-    if not _G:
-        _G["pool"] = [torch.cuda.Stream() for _ in range(STREAMS)]
-        _G["s1"] = _G["pool"][0]
-        _G["w"] = torch.randn(FILL_DIM, FILL_DIM, device="cuda") / FILL_DIM ** 0.5
-        _G["x"] = {k: [torch.randn(FILL_DIM, FILL_DIM, device="cuda") for _ in range(2)] for k in ("s1", "s2")}
-        _G["probe"] = torch.zeros(64, device="cuda")
-        torch.cuda.synchronize()
-        for s in _G["pool"]:   # the matmul's own first-use work, on every stream
-            _G["s2"] = s
-            with torch.cuda.stream(s):
-                _fill("s2", 2)
-                _G["probe"].add_(1)
-            torch.cuda.synchronize()
-        # s2: the first stream after s1 that the device runs beside s1.  Streams are spread over a few hardware queues (four
-        # by default) by the number of users each queue has, so two streams created one after the other can share one, and
-        # then run one after the other; if none of them runs beside s1, every gated test fails on its first condition.
-        for s in _G["pool"][1:]:
-            _G["s2"] = s
-            e_fill, e_probe = torch.cuda.Event(), torch.cuda.Event()
-            with torch.cuda.stream(_G["s1"]):
-                _fill("s1", FILL_STEPS)
-                e_fill.record()
-            with torch.cuda.stream(s):
-                _G["probe"].add_(1)
-                e_probe.record()
-            e_probe.synchronize()
-            beside = not e_fill.query()
-            torch.cuda.synchronize()
-            if beside:
-                break
-        print("\ns2 is stream %d of %d" % (_G["pool"].index(_G["s2"]), STREAMS))
-    return _G
-
-
-def _fill(key, steps):
-    import torch
-    a, b = _G["x"][key]
-    for _ in range(steps // 2):
-        torch.mm(a, _G["w"], out=b)
-        torch.mm(b, _G["w"], out=a)
-
-
-def _run(calls, order):
-    """warm up, gate the first stream, issue the calls back to back on streams `order` ("s1", "s2" or None: the ctx's
-    own), synchronise once, then assert the gate's two conditions and every output"""
-    import torch
-    g = gear()
-    streams = [None if k is None else g[k] for k in order]
-    first = order[0]
-    other = g["s2" if first == "s1" else "s1"]
-    torch.cuda.synchronize()
-    for c, s in zip(calls, streams):
-        c.run(s)
-    torch.cuda.synchronize()
-    for c in calls:
-        c.reset()
-    torch.cuda.synchronize()
-    e0, e_fill, e_probe = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), torch.cuda.Event()
-    with torch.cuda.stream(g[first]):
-        e0.record()
-        _fill(first, FILL_STEPS)
-        e_fill.record()
-    with torch.cuda.stream(other):
-        g["probe"].add_(1)
-        e_probe.record()
-    e_probe.synchronize()
-    side_by_side = not e_fill.query()
-    t0 = time.perf_counter()
-    for c, s in zip(calls, streams):
-        c.run(s)
-    issue = time.perf_counter() - t0
-    held = not e_fill.query()
-    torch.cuda.synchronize()
-    TIMINGS.append((issue, e0.elapsed_time(e_fill)))
-    print("issue %.3f ms, filler %.1f ms: %s" % (issue * 1e3, TIMINGS[-1][1], " -> ".join(c.name for c in calls)))
-    assert side_by_side, "the probe on the second stream did not finish ahead of the filler: the streams do not run side by side"
-    assert held, "the filler was over before the last call was issued (%.3f ms): the gate held nothing back" % (issue * 1e3)
-    bad = [(c.name, k or "the ctx's stream", c.bad()) for c, k in zip(calls, order)]
-    bad = ["%s on %s: %d of %d elements differ from the model, the first at %s" % (name, k, len(b), N, b[:8]) for name, k, b in bad if b]
-    assert not bad, "\n".join(bad)
+# ---- the gate (tests/stream_gate.py), with this module's filler ------------------------------------------------------------
+GATE = Gate(FILL_DIM, FILL_STEPS)
+gear, _run, TIMINGS = GATE.gear, GATE.run, GATE.timings
 
 
 ASSIGN = {"A on s1, B on s2": ("s1", "s2"), "A on s2, B on s1": ("s2", "s1")}
@@ -612,13 +570,13 @@ def _leave_the_ctx_on_its_own_stream(gpu_ctx):
     """whatever subset of the module ran: the ctx's last launch names its own stream afterwards, and has finished"""
     yield
     import torch
-    if _G:
+    if GATE.geared:
         c = c_keccak256(gpu_ctx, ROT_A)
         c.run(None)
         torch.cuda.synchronize()
         assert not c.bad()
         if TIMINGS:
-            print("\ngated runs: %d; host issue max %.3f ms; filler min %.1f ms" % (len(TIMINGS), max(t[0] for t in TIMINGS) * 1e3, min(t[1] for t in TIMINGS)))
+            print("\n" + GATE.summary())
 
 
 # ---- 1. every user of d_verify behind another one ------------------------------------------------------------------------

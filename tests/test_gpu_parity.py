@@ -490,7 +490,12 @@ def test_dev_calls_on_two_streams_share_ctx_scratch_in_call_order(gpu_ctx, oracl
     """*_dev calls of ONE ctx issued back to back on two different streams with no host synchronisation
     in between: the Ed25519 fixed-base path rebuilds and reads the ctx-owned addend table, the P-256 /
     Ed25519 double-mul writes per-stream scratch.  The library orders a launch after the ctx's previous
-    launch when the stream changes, so every result must still be the oracle's."""
+    launch when the stream changes, so every result must still be the oracle's.
+
+    Nothing here makes the two calls overlap: two streams created one after the other can share a hardware queue and
+    then run one after the other, and the test passes with nothing in flight.  tests/test_gpu_parity_streams.py holds
+    the same promise for every parity *_dev entry point behind a gate that has both streams demonstrably running
+    (tests/stream_gate.py); this test stays for the batch of 20000, which that module does not reach."""
     import torch
     n = 20000
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
