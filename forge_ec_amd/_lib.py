@@ -46,6 +46,7 @@ CANON_ABI_SYMBOLS = [
     "fec_canon_ripemd160", "fec_canon_ripemd160_dev", "fec_canon_hash160", "fec_canon_hash160_dev",
     "fec_canon_pubkey_hash160", "fec_canon_pubkey_hash160_dev", "fec_canon_taproot_output_key", "fec_canon_taproot_output_key_dev",
     "fec_canon_bip32_derive_pub_path", "fec_canon_bip32_derive_pub_path_dev",
+    "fec_canon_msm", "fec_canon_msm_dev", "fec_ctx_set_canon_msm_window",
 ]
 CANON_NO_KEY = 8
 CANON_BAD_POINT, CANON_BAD_INDEX, CANON_BIP32_INVALID, CANON_BIP32_NO_COMB = 2, 9, 10, 1
@@ -340,6 +341,9 @@ def lib():
     L.fec_canon_taproot_output_key_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, sz, vp]
     L.fec_canon_bip32_derive_pub_path.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, sz]
     L.fec_canon_bip32_derive_pub_path_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, sz, vp]
+    L.fec_canon_msm.argtypes = [vp, ci, vp, vp, sz, vp, vp]
+    L.fec_canon_msm_dev.argtypes = [vp, ci, vp, vp, sz, vp, vp, vp]
+    L.fec_ctx_set_canon_msm_window.argtypes = [vp, ci]
     for n in CANON_ABI_SYMBOLS:
         getattr(L, n).restype = ci
     _lib = L

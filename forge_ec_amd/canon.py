@@ -228,6 +228,25 @@ class CanonCurve:
         _check(self._lib.fec_canon_mul(self._h, self.CURVE, _ptr(k), _ptr(p), _ptr(xy), _ptr(st), n), "fec_canon_mul")
         return xy, st
 
+    def msm(self, scalars, points_xy):
+        """(xy, status): the ONE point xy (8 limbs) = sum of scalars[i] * points_xy[i] by the bucket method.  status 0; 1: the sum
+        is the point at infinity (Weierstrass; n = 0 included), 2: some input point is off the curve -- zeros then."""
+        k = _u64(scalars, 4)
+        p = _u64(points_xy, 8)
+        if p.shape[0] != k.shape[0]:
+            raise ValueError("scalars and points differ in length")
+        xy = np.zeros(8, dtype=np.uint64)
+        st = np.zeros(1, dtype=np.uint8)
+        _check(self._lib.fec_canon_msm(self._h, self.CURVE, _ptr(k), _ptr(p), k.shape[0], _ptr(xy), _ptr(st)), "fec_canon_msm")
+        return xy, int(st[0])
+
+    def msm_dev(self, d_scalars, d_points_xy, n, d_out_xy, d_status, stream=None):
+        """Enqueue-only form of msm on device pointers: d_scalars (n*32 bytes), d_points_xy (n*64) and d_out_xy (64 bytes: the
+        one sum) 16-byte aligned, d_status one byte; d_out_xy and d_status are written whatever n is (n = 0: the identity).
+        Nothing is read back or synchronised; single-device ctx only."""
+        _check(self._lib.fec_canon_msm_dev(self._h, self.CURVE, d_scalars, d_points_xy, n, d_out_xy, d_status, stream),
+               "fec_canon_msm_dev")
+
     def double_mul(self, u1, u2, points_xy):
         """(xy, status) with xy[i] = u1[i] * G + u2[i] * points_xy[i]  (signature-verification point)."""
         a, b = _u64(u1, 4), _u64(u2, 4)

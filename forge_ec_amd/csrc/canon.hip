@@ -12,6 +12,7 @@
 #include "canon_recover_kernels.hpp"
 #include "canon_bip32_kernels.hpp"
 #include "canon_wallet_kernels.hpp"
+#include "canon_msm_kernels.hpp"
 
 using namespace fecgpu;
 using namespace fecgpu::host;
@@ -780,6 +781,166 @@ int launch_canon_bip32_derive_pub_path(fec_ctx* ctx, const uint8_t* d_pks, const
   return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
 }
 
+// ---- multi-scalar multiplication by the bucket method (canon_msm.hpp, canon_msm_kernels.hpp) ------------
+// One sum for the whole batch.  The batch goes through recode -> sort -> accumulate in slices of at most kMsmSlice elements;
+// the bucket accumulators persist in the work area from slice to slice, and reduce -> fold -> combine run once behind the
+// last slice.  Every pass is sized on the host from the slice length and the window width: nothing is read back.
+// Work area in d_verify: the flag word and the sum's Z (256 bytes); per slice the digits, the per-window histograms /
+// cursors, the sorted keys and entries; the buckets; the two partial-sum lists the accumulate levels alternate between;
+// the two halves the reduce and fold passes alternate between.
+constexpr size_t kMsmSlice = (size_t)1 << 18;
+struct MsmWork {
+  u32* misc;                              // word 0: bad-point flag; words 8..15: Z of the sum
+  u32 *dig, *hist, *skeys, *sent;         // per slice: W x cap digits, W x (B + 1) counters, W x cap sorted keys / entries
+  u32* bucket;                            // W x B accumulators
+  u32 *keys_a, *pts_a, *keys_b, *pts_b;   // partial-sum lists: W x la and W x lb entries
+  u32* red;                               // 2 x W x nseg accumulators
+  int c, W;
+  u32 B, nseg;
+  size_t cap, la, lb, words;
+};
+int msm_work(fec_ctx* ctx, int curve, int c, size_t cap, MsmWork& w) {
+  namespace M = canon::msm;
+  w.c = c;
+  w.W = M::windows(c);
+  w.B = M::buckets(c);
+  w.nseg = (u32)M::div_up(w.B, M::SEG);
+  w.cap = cap ? cap : 1;
+  w.la = 2 * M::div_up(w.cap, M::RUN);
+  w.lb = 2 * M::div_up(w.la, M::RUN);
+  w.words = curve == FEC_ED25519 ? M::ops<ced>::WORDS : M::ops<csecp>::WORDS;
+  const size_t W = (size_t)w.W, acc = w.words * sizeof(u32);
+  WorkArea area;
+  area.add(w.misc, 256).add(w.dig, W * w.cap * 4).add(w.hist, W * (w.B + 1) * 4).add(w.skeys, W * w.cap * 4).add(w.sent, W * w.cap * 4);
+  area.add(w.bucket, W * w.B * acc).add(w.keys_a, W * w.la * 4).add(w.pts_a, W * w.la * acc).add(w.keys_b, W * w.lb * 4).add(w.pts_b, W * w.lb * acc);
+  area.add(w.red, 2 * W * w.nseg * acc);
+  return place_in_verify(ctx, area);
+}
+// The window width: the ctx's forced one, else read from the forced-window sweeps at 2^18 and 2^20 (profiles/canon_msm.jsonl,
+// DESIGN.md section 30): from 2^18 elements on, 13 bits -- the fastest width on every curve at both sizes, by 10 % and more.
+// The sweeps are not smooth in c: 11, 12, 14, 15 and 16 bits cost up to twice what 10 and 13 do, in the recode and scatter
+// kernels (the counters' atomics), for a reason the kernel trace locates and does not explain.  Below 2^18, where no sweep
+// was taken and the time is the fixed tail's, the c that minimises the operation count W (n + 3 B) -- one mixed addition per
+// element and window, about two full additions per bucket and window at 1.5 times the cost -- among the widths the sweeps
+// showed fast: up to 10 bits, and 13.
+constexpr size_t kMsmSweptFrom = (size_t)1 << 18;
+constexpr int kMsmSweptWindow = 13;
+constexpr size_t kMsmReduceWeight = 3;
+inline bool msm_width_measured_fast(int c) { return c <= 10 || c == kMsmSweptWindow; }
+int msm_window(const fec_ctx* ctx, size_t n) {
+  namespace M = canon::msm;
+  if (ctx->canon_msm_window) return ctx->canon_msm_window;
+  if (n >= kMsmSweptFrom) return kMsmSweptWindow;
+  int best = M::MIN_WINDOW;
+  size_t best_cost = (size_t)-1;
+  for (int c = M::MIN_WINDOW; c <= M::MAX_WINDOW; ++c) {
+    const size_t cost = (size_t)M::windows(c) * (n + kMsmReduceWeight * M::buckets(c));
+    if (cost < best_cost && msm_width_measured_fast(c)) best = c, best_cost = cost;
+  }
+  return best;
+}
+int msm_begin(int curve, const MsmWork& w, hipStream_t s) {
+  const size_t count = (size_t)w.W * w.B;
+  with_curve(curve, [&](auto t) {
+    hipLaunchKernelGGL((k_canon_msm_init<typename decltype(t)::C>), dim3(grid_for(count)), dim3(TPB), 0, s, w.bucket, count, w.misc);
+  });
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+// one slice of m <= w.cap elements into the buckets
+int msm_slice(int curve, const MsmWork& w, const u64* ds, const u64* dp, size_t m, hipStream_t s) {
+  namespace M = canon::msm;
+  if (m == 0) return FEC_OK;
+  const u32 b1 = w.B + 1;
+  const unsigned W = (unsigned)w.W;
+  if (hipMemsetAsync(w.hist, 0, (size_t)W * b1 * 4, s) != hipSuccess) return FEC_E_DEVICE;
+  with_curve(curve, [&](auto t) {
+    using C = typename decltype(t)::C;
+    const u32* pts = reinterpret_cast<const u32*>(dp);
+    hipLaunchKernelGGL((k_canon_msm_recode<C>), dim3(grid_for(m)), dim3(TPB), 0, s, reinterpret_cast<const u32*>(ds), pts, w.dig, w.hist, w.misc, m, w.c);
+    hipLaunchKernelGGL(k_canon_msm_scan, dim3(W), dim3(TPB), 0, s, w.hist, b1);
+    hipLaunchKernelGGL(k_canon_msm_scatter, dim3(grid_for(m), W), dim3(TPB), 0, s, (const u32*)w.dig, w.hist, w.skeys, w.sent, m, b1);
+    size_t len = m, lanes = M::div_up(len, M::RUN);
+    hipLaunchKernelGGL((k_canon_msm_accumulate<C, true>), dim3(grid_for(lanes), W), dim3(TPB), 0, s, (const u32*)w.skeys, (const u32*)w.sent, pts, len,
+                       lanes, w.bucket, w.B, w.keys_a, w.pts_a);
+    u32 *ik = w.keys_a, *ip = w.pts_a, *ok = w.keys_b, *op = w.pts_b;
+    while (lanes > 1) {   // the partial sums of the buckets that crossed a run, RUN per lane again
+      len = 2 * lanes;
+      lanes = M::div_up(len, M::RUN);
+      hipLaunchKernelGGL((k_canon_msm_accumulate<C, false>), dim3(grid_for(lanes), W), dim3(TPB), 0, s, (const u32*)ik, (const u32*)ip, pts, len, lanes,
+                         w.bucket, w.B, ok, op);
+      std::swap(ik, ok);
+      std::swap(ip, op);
+    }
+  });
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+// behind the last slice: per window sum b B_b, the windows onto their places, their sum un-normalised into xy / Z
+int msm_finish(int curve, const MsmWork& w, u32* xy, unsigned char* dst, hipStream_t s) {
+  namespace M = canon::msm;
+  const unsigned W = (unsigned)w.W;
+  with_curve(curve, [&](auto t) {
+    using C = typename decltype(t)::C;
+    u32 *in = w.red, *out = w.red + (size_t)W * w.nseg * w.words;
+    hipLaunchKernelGGL((k_canon_msm_reduce<C>), dim3(grid_for(w.nseg), W), dim3(TPB), 0, s, (const u32*)w.bucket, w.B, w.nseg, in);
+    for (size_t cnt = w.nseg; cnt > 1;) {   // the segments of each window, as a tree
+      const size_t lanes = M::div_up(cnt, M::FOLD);
+      hipLaunchKernelGGL((k_canon_msm_fold<C>), dim3(grid_for(lanes), W), dim3(TPB), 0, s, (const u32*)in, cnt, lanes, out);
+      std::swap(in, out);
+      cnt = lanes;
+    }
+    hipLaunchKernelGGL((k_canon_msm_shift<C>), dim3(grid_for(W)), dim3(TPB), 0, s, (const u32*)in, out, w.W, w.c);
+    std::swap(in, out);
+    for (size_t cnt = W; cnt > 1;) {        // the windows
+      const size_t lanes = M::div_up(cnt, M::FOLD);
+      hipLaunchKernelGGL((k_canon_msm_fold<C>), dim3(grid_for(lanes), 1), dim3(TPB), 0, s, (const u32*)in, cnt, lanes, out);
+      std::swap(in, out);
+      cnt = lanes;
+    }
+    hipLaunchKernelGGL((k_canon_msm_emit<C>), dim3(1), dim3(64), 0, s, (const u32*)in, (const u32*)w.misc, xy, w.misc + 8, dst);
+  });
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+// the resident batch: enqueue only
+int launch_canon_msm(fec_ctx* ctx, int curve, const u64* ds, const u64* dp, size_t n, u64* dxy, unsigned char* dst, void* stream) {
+  MsmWork w;
+  const size_t cap = n < kMsmSlice ? n : kMsmSlice;
+  int rc = msm_work(ctx, curve, msm_window(ctx, n), cap, w);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = ordered_stream(ctx, stream);
+  rc = msm_begin(curve, w, s);
+  for (size_t lo = 0; lo < n && rc == FEC_OK; lo += cap) rc = msm_slice(curve, w, ds + lo * 4, dp + lo * 8, n - lo < cap ? n - lo : cap, s);
+  if (rc == FEC_OK) rc = msm_finish(curve, w, reinterpret_cast<u32*>(dxy), dst, s);
+  return rc != FEC_OK ? rc : launch_canon_normalize(curve, reinterpret_cast<u32*>(dxy), w.misc + 8, dst, 1, s);
+}
+// the batch in host memory: slice by slice through staging slot 0 on the ctx's stream, the 65 result bytes back from slot 1
+int launch_canon_msm_host(fec_ctx* ctx, int curve, const u64* scalars, const u64* points, size_t n, u64* out_xy, unsigned char* status) {
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return drained(ctx, [&]() -> int {
+    MsmWork w;
+    size_t cap = pipeline_chunk(ctx) < kMsmSlice ? pipeline_chunk(ctx) : kMsmSlice;
+    if (n < cap) cap = n;
+    int rc = msm_work(ctx, curve, msm_window(ctx, n), cap, w);
+    if (rc == FEC_OK) rc = ensure(ctx, kStageOut, 256);
+    if (rc != FEC_OK) return rc;
+    hipStream_t s = ordered_stream(ctx, nullptr);
+    rc = msm_begin(curve, w, s);
+    for (size_t lo = 0; lo < n && rc == FEC_OK; lo += cap) {
+      const size_t m = n - lo < cap ? n - lo : cap;
+      const u64 *d_s = nullptr, *d_p = nullptr;
+      rc = upload(ctx, kStageIn, m, s, arrays(input(scalars + lo * 4, 32), input(points + lo * 8, 64)), d_s, d_p);
+      if (rc == FEC_OK) rc = msm_slice(curve, w, d_s, d_p, m, s);
+    }
+    u32* d_xy = static_cast<u32*>(ctx->d_buf[kStageOut]);
+    unsigned char* d_st = static_cast<unsigned char*>(ctx->d_buf[kStageOut]) + 64;
+    if (rc == FEC_OK) rc = msm_finish(curve, w, d_xy, d_st, s);
+    if (rc == FEC_OK) rc = launch_canon_normalize(curve, d_xy, w.misc + 8, d_st, 1, s);
+    if (rc != FEC_OK) return rc;
+    if (hipMemcpyAsync(out_xy, d_xy, 64, hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(status, d_st, 1, hipMemcpyDeviceToHost, s) != hipSuccess)
+      return FEC_E_DEVICE;
+    return sync_and_check(ctx, s);
+  });
+}
+
 // ---- the entry points (include/fecgpu_canon.h), one function per host / *_dev pair -------------------------------------------
 // Each names its value checks and its arrays once and hands them to host::call or host::message_call (host_ctx.hpp,
 // host_messages.hpp) with the body both forms share; `w` says which form is running.  The extern "C" wrappers below forward
@@ -1001,6 +1162,19 @@ int canon_taproot_output_key(fec_ctx* ctx, Where w, const uint8_t* pks, size_t p
               arrays(input(pks, pk_len).aligned(pk_len == 32 ? 16 : 0), input(roots, 32).aligned(16).opt(), output(out_keys, 32).aligned(16),
                      output(out_parity, 1), output(status, 1)),
               [&](fec_ctx* c, const uint8_t* d_pks, auto... p) { return launch_canon_taproot_output_key(c, d_pks, pk_len, p...); });
+}
+
+// ---- multi-scalar multiplication: one sum, one status.  Neither form is element-wise, so the checks of host::call are spelt
+// out here in its order: the ctx, the required pointers (the result's whatever n is), the curve, the *_dev alignments.
+int canon_msm(fec_ctx* ctx, Where w, int curve, const uint64_t* scalars, const uint64_t* points_xy, size_t n, uint64_t* out_xy, uint8_t* status) {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;   // a sum across devices would be the first cross-device data dependency
+  if (!ctx) return FEC_E_ARG;
+  if (!out_xy || !status || (n && (!scalars || !points_xy))) return FEC_E_ARG;
+  if (!curve_ok(curve)) return FEC_E_ARG;
+  if (!w.dev) return launch_canon_msm_host(ctx, curve, scalars, points_xy, n, out_xy, status);
+  if (!aligned16(scalars) || !aligned16(points_xy) || !aligned16(out_xy)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_canon_msm(ctx, curve, scalars, points_xy, n, out_xy, status, w.stream);
 }
 
 }  // namespace
@@ -1341,6 +1515,21 @@ int fec_canon_bip32_derive_pub_path(fec_ctx* ctx, const uint8_t* parent_pks, con
                                     uint8_t* out_hash160, uint8_t* status, size_t n) try {
   return canon_bip32_derive_pub_path(ctx, kOnHost, parent_pks, parent_ccs, n_par, indices, depth, out_pks, out_ccs, out_fingerprints, out_hash160,
                                      status, n);
+} FEC_ABI_CATCH_STATUS
+
+// ---- multi-scalar multiplication (the bucket method) ---------------------------------------------------------------------------
+int fec_canon_msm_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, const uint64_t* d_points_xy, size_t n,
+                      uint64_t* d_out_xy, uint8_t* d_status, void* stream) try {
+  return canon_msm(ctx, on_device(stream), curve, d_scalars, d_points_xy, n, d_out_xy, d_status);
+} FEC_ABI_CATCH_STATUS
+int fec_canon_msm(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* points_xy, size_t n, uint64_t* out_xy,
+                  uint8_t* status) try {
+  return canon_msm(ctx, kOnHost, curve, scalars, points_xy, n, out_xy, status);
+} FEC_ABI_CATCH_STATUS
+int fec_ctx_set_canon_msm_window(fec_ctx* ctx, int bits) try {
+  if (!ctx || (bits != 0 && (bits < canon::msm::MIN_WINDOW || bits > canon::msm::MAX_WINDOW))) return FEC_E_ARG;
+  for_each_work_ctx(ctx, [&](fec_ctx* c) { c->canon_msm_window = bits; });
+  return FEC_OK;
 } FEC_ABI_CATCH_STATUS
 
 }  // extern "C"

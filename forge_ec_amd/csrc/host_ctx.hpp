@@ -52,6 +52,7 @@ struct fec_ctx {
   size_t verify_cap = 0;
   void* d_tbuf = nullptr;  // Ed25519 double-mul: T of the comb result until the accumulate pass
   size_t tbuf_cap = 0;
+  int canon_msm_window = 0;  // fec_ctx_set_canon_msm_window: 0 = chosen from n, 2..16 = forced
   hipDeviceProp_t prop;
   // multi-device ctx (fec_ctx_create_multi): the shard workers; empty for a single-device ctx
   std::vector<fec_ctx*> children;
@@ -253,7 +254,7 @@ class WorkArea {
   }
 
  private:
-  static constexpr int kMaxRegions = 10;   // canonical ECDSA verification from the message has the most
+  static constexpr int kMaxRegions = 12;   // the multi-scalar multiplication has the most (canon.hip: MsmWork)
   template <class T>
   static void assign(void* slot, char* at) {
     *static_cast<T**>(slot) = reinterpret_cast<T*>(at);

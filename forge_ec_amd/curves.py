@@ -1009,6 +1009,10 @@ class Context:
         """Elements per pipeline chunk of the host-pointer entry points (default 2^18)."""
         _check(self._lib.fec_ctx_set_chunk(self._h, int(elements)))
 
+    def set_canon_msm_window(self, bits):
+        """Window width of canonical mode's multi-scalar multiplication (CanonCurve.msm): 0 = chosen from n, 2..16 = forced."""
+        _check(self._lib.fec_ctx_set_canon_msm_window(self._h, int(bits)))
+
     # ---- measurement ----
     def set_timing(self, enabled=True):
         _check(self._lib.fec_ctx_set_timing(self._h, 1 if enabled else 0))

@@ -114,8 +114,8 @@ int fec_canon_eddsa_verify_dev(fec_ctx* ctx, const uint64_t* d_a_enc, const uint
  * *_dev forms: sigs, pks, in, xy 16-byte aligned, d_msg_off 8-byte aligned; every lane checks its own range and
  * a bad one gets result 4; FEC_E_UNSUPPORTED on a multi-device ctx.
  * result[i]: 1 valid, 0 invalid, 4 bad message range (*_dev only).
- * Not offered: DER signatures, Ed25519ph / Ed25519ctx, ECDSA with another hash, batch (random linear combination)
- * verification. */
+ * Not offered: DER signatures, Ed25519ph / Ed25519ctx, ECDSA with another hash; batch (random linear combination)
+ * verification -- the sum it needs is fec_canon_msm at the end of this header, the layer that draws the coefficients is not. */
 
 /* ECDSA with SHA-256 (FIPS 186-4 section 6.4 / SEC 1 section 4.1.4), FEC_SECP256K1 and FEC_P256 (FEC_ED25519:
  * FEC_E_UNSUPPORTED).  z = the 32 bytes of SHA-256(msg_i) read big-endian (both orders have 256 bits: no truncation);
@@ -467,6 +467,42 @@ int fec_canon_bip32_derive_pub_path_dev(fec_ctx* ctx, const uint8_t* d_parent_pk
                                         const uint32_t* d_indices, size_t depth, uint8_t* d_out_pks, uint8_t* d_out_ccs,
                                         uint8_t* d_out_fingerprints, uint8_t* d_out_hash160, uint8_t* d_status, size_t n,
                                         void* stream);
+
+/* ---- Multi-scalar multiplication: one sum over the batch -----------------------------------------------------------------------
+ * out_xy = sum over i < n of scalars[i] * points_xy[i] on the real curve: ONE affine point (8 limbs) and ONE status byte, by the
+ * bucket method (Pippenger): signed c-bit digits, a counting sort per window, a load-balanced bucket accumulation, a segmented
+ * bucket reduction and the window combination, all on the device; roughly one mixed addition per element per window instead of
+ * a ladder per element, and the sum never leaves the device.  The layout is this header's: four limbs per scalar and per
+ * coordinate, arrays of structs; all three curves.
+ * Scalars: any 256-bit value, k * P for k as given with no reduction modulo the group order (on Ed25519 a point with a torsion
+ * component tells k from k mod l; 2^256 - 1 is a legal scalar).  Points: every one is checked as fec_canon_mul checks it
+ * (coordinates < p, on the curve); if any element fails, status is FEC_CANON_BAD_POINT and out_xy is zero -- the failing element
+ * is left out of the arithmetic, which never runs on an off-curve value.  Otherwise status is 0 with the affine sum, or
+ * FEC_CANON_INFINITY with zero output when the sum is the point at infinity (secp256k1, P-256); Ed25519 has no infinity: its
+ * identity is (0, 1) with status 0, and (0, 1) and the seven other torsion points are legal inputs.  n = 0: the identity --
+ * FEC_CANON_INFINITY on secp256k1 and P-256, (0, 1) with status 0 on Ed25519 -- so out_xy and status are required whatever n is
+ * (FEC_E_ARG when null), scalars and points_xy only when n != 0.
+ * The result is a canonical affine point: bit-identical from run to run, for every window width and every slice size, whatever
+ * order the additions ran in.
+ * NOT constant-time, and nothing is wiped: bucket indices, memory addresses and trip counts depend on the scalars.  A call for
+ * public data, like the verifiers.
+ * fec_canon_msm_dev only enqueues: no readback, no stream synchronisation, every pass sized on the host from n and the window
+ * width; a batch above 2^18 elements walks through the same pipeline in internal slices, so the work area is bounded for any n
+ * (it grows on the first call that needs more, as the verifiers' does).  d_scalars, d_points_xy, d_out_xy 16-byte aligned
+ * (d_out_xy: 64 bytes), else FEC_E_ARG.  FEC_E_UNSUPPORTED on a multi-device ctx.
+ * fec_canon_msm streams the batch through the device in slices of fec_ctx_set_chunk elements (at most 2^18), so staging is
+ * bounded by one slice; the buckets persist on the device between slices.  On a multi-device ctx it, too, returns
+ * FEC_E_UNSUPPORTED: the multi-device path has never run across distinct devices, and a sum across devices would be
+ * its first cross-device data dependency.
+ * fec_ctx_set_canon_msm_window: the window width c of the bucket method, 0 = chosen from n (the default), 2..16 = forced;
+ * anything else FEC_E_ARG.  A tuning and testing knob: the result does not depend on it.
+ * Not offered: a segmented form (many sums per call); batch (random linear combination) verification, which is now a thin layer
+ * over this call -- where its coefficients come from is the open question. */
+int fec_canon_msm(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars /* n*4 */, const uint64_t* points_xy /* n*8 */,
+                  size_t n, uint64_t* out_xy /* 8 */, uint8_t* status /* 1 */);
+int fec_canon_msm_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, const uint64_t* d_points_xy, size_t n,
+                      uint64_t* d_out_xy, uint8_t* d_status, void* stream);
+int fec_ctx_set_canon_msm_window(fec_ctx* ctx, int bits);
 
 #ifdef __cplusplus
 }

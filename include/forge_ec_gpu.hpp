@@ -1300,6 +1300,20 @@ inline Bip32PathResult bip32_derive_pub_path(GpuContext& ctx, const std::vector<
                                         r.hash160.data(), r.status.data(), n));
   return r;
 }
+// the one point sum_i scalars[i] * points[i] by the bucket method (fec_canon_msm): status 0, 1 (the sum is the point at
+// infinity; zeros) or 2 (some input point is off the curve; zeros)
+struct SumResult {
+  Affine point;
+  uint8_t status = 0;
+};
+template <fec_curve C>
+inline SumResult msm(GpuContext& ctx, const std::vector<Limbs>& scalars, const std::vector<Affine>& points) {
+  if (scalars.size() != points.size()) throw Error(FEC_E_ARG);
+  SumResult r;
+  check(fec_canon_msm(ctx.raw(), C, reinterpret_cast<const uint64_t*>(scalars.data()), reinterpret_cast<const uint64_t*>(points.data()),
+                      scalars.size(), reinterpret_cast<uint64_t*>(&r.point), &r.status));
+  return r;
+}
 }  // namespace canon
 
 using Secp256k1 = Curve<FEC_SECP256K1>;

@@ -76,6 +76,16 @@ out_hash160, with out_fingerprints and with both against both NULL.  "hash" rows
 fec_canon_hash160_dev against fec_sha256_dev (FEC_AB_LIB's where set) on the same 64-byte messages.  "taproot" rows:
 fec_canon_taproot_output_key_dev with and without roots against fec_canon_pubkey_tweak_add_dev (pk_len 32, out_len 32) fed
 precomputed tweaks.  Last, one host-pointer row each.
+
+The bucket-method multi-scalar multiplication (fec_canon_msm_dev), by the same method:
+
+    python tools/canon_perf.py msm [max_log2_n] [reps] [out.jsonl]
+
+Inputs resident, wall clock around a device synchronise, median of `reps` (7); every MSM sample alternates in this process
+with one of its comparator, fec_canon_mul_dev on the same n pairs -- what a caller had to run before summing the n points on
+the CPU.  "size" rows: n = 2^10 .. 2^max in steps of 4x, random scalars, the automatic window.  "window" rows: n = 2^18 and 2^20 (or
+max), every forced window 8 .. 16 -- the sweep the automatic rule is read from.  "skew" rows at the same n: all scalars equal,
+and one point throughout, next to the random row.  Every row records the status byte the call left (0).
 """
 import ctypes
 import json
@@ -778,6 +788,83 @@ def main_wallet():
                 f.write(json.dumps(r) + "\n")
 
 
+def main_msm():
+    max_log = int(sys.argv[2]) if len(sys.argv) > 2 else 22
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    out_path = sys.argv[4] if len(sys.argv) > 4 else None
+    ctx = F.Context(0)
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+    nmax = 1 << max_log
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(28)
+    rand = lambda m: torch.randint(-2**63, 2**63 - 1, (m, 4), dtype=torch.int64, device="cuda", generator=gen)  # noqa: E731
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    def pair(c, k, p, n, window):
+        """(msm median ms, comparator median ms, status): the two calls alternate sample by sample"""
+        out1 = torch.empty(8, dtype=torch.int64, device="cuda")
+        st1 = torch.full((1,), 9, dtype=torch.uint8, device="cuda")
+        outn = torch.empty((n, 8), dtype=torch.int64, device="cuda")
+        stn = torch.empty(n, dtype=torch.uint8, device="cuda")
+        ctx.set_canon_msm_window(window)
+        fns = (lambda: c.msm_dev(k.data_ptr(), p.data_ptr(), n, out1.data_ptr(), st1.data_ptr(), st),
+               lambda: c.mul_dev(k.data_ptr(), p.data_ptr(), outn.data_ptr(), stn.data_ptr(), n, st))
+        samples = ([], [])
+        for i in range(reps + 1):
+            for smp, fn in zip(samples, fns):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if i:
+                    smp.append((time.perf_counter() - t0) * 1e3)
+        ctx.set_canon_msm_window(0)
+        med = [sorted(x)[len(x) // 2] for x in samples]
+        return med[0], med[1], int(st1.cpu()[0])
+
+    for cname in CANON_CURVES:
+        c = CANON_CURVES[cname](ctx)
+        k = rand(nmax)
+        p = torch.empty((nmax, 8), dtype=torch.int64, device="cuda")
+        stat = torch.empty(nmax, dtype=torch.uint8, device="cuda")
+        c.mul_base_dev(rand(nmax).data_ptr(), p.data_ptr(), stat.data_ptr(), nmax, st)
+        torch.cuda.synchronize()
+        for logn in range(10, max_log + 1, 2):
+            n = 1 << logn
+            m, cmp_, status = pair(c, k, p, n, 0)
+            emit({"row": "size", "curve": cname, "n": n, "window": 0, "reps": reps, "msm_ms": round(m, 4), "canon_mul_ms": round(cmp_, 4),
+                  "speedup": round(cmp_ / m, 3), "M_per_s": round(n / m / 1e3, 3), "status": status})
+        for sweep_log in sorted({min(18, max_log), min(20, max_log)}):
+            n = 1 << sweep_log
+            for window in range(8, 17):
+                m, cmp_, status = pair(c, k, p, n, window)
+                emit({"row": "window", "curve": cname, "n": n, "window": window, "reps": reps, "msm_ms": round(m, 4),
+                      "canon_mul_ms": round(cmp_, 4), "speedup": round(cmp_ / m, 3), "status": status})
+        rand_ms = None
+        m, cmp_, status = pair(c, k, p, n, 0)
+        rand_ms = m
+        emit({"row": "skew", "input": "random", "curve": cname, "n": n, "window": 0, "reps": reps, "msm_ms": round(m, 4), "canon_mul_ms": round(cmp_, 4),
+              "status": status})
+        keq = k[:1].repeat(n, 1).contiguous()
+        m, cmp_, status = pair(c, keq, p, n, 0)
+        emit({"row": "skew", "input": "all scalars equal", "curve": cname, "n": n, "window": 0, "reps": reps, "msm_ms": round(m, 4),
+              "canon_mul_ms": round(cmp_, 4), "over_random": round(m / rand_ms, 3), "status": status})
+        p1 = p[:1].repeat(n, 1).contiguous()
+        m, cmp_, status = pair(c, k, p1, n, 0)
+        emit({"row": "skew", "input": "one point", "curve": cname, "n": n, "window": 0, "reps": reps, "msm_ms": round(m, 4),
+              "canon_mul_ms": round(cmp_, 4), "over_random": round(m / rand_ms, 3), "status": status})
+        del k, p, stat, keq, p1
+        torch.cuda.empty_cache()
+    if out_path:
+        with open(out_path, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     logn = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -845,5 +932,7 @@ elif len(sys.argv) > 1 and sys.argv[1] == "bip32":
     main_bip32()
 elif len(sys.argv) > 1 and sys.argv[1] == "wallet":
     main_wallet()
+elif len(sys.argv) > 1 and sys.argv[1] == "msm":
+    main_msm()
 else:
     main()
