@@ -47,6 +47,8 @@ CANON_ABI_SYMBOLS = [
     "fec_canon_pubkey_hash160", "fec_canon_pubkey_hash160_dev", "fec_canon_taproot_output_key", "fec_canon_taproot_output_key_dev",
     "fec_canon_bip32_derive_pub_path", "fec_canon_bip32_derive_pub_path_dev",
     "fec_canon_msm", "fec_canon_msm_dev", "fec_ctx_set_canon_msm_window",
+    "fec_canon_bip340_batch_verify_msg", "fec_canon_bip340_batch_verify_msg_dev",
+    "fec_canon_ed25519_batch_verify_msg", "fec_canon_ed25519_batch_verify_msg_dev",
 ]
 CANON_NO_KEY = 8
 CANON_BAD_POINT, CANON_BAD_INDEX, CANON_BIP32_INVALID, CANON_BIP32_NO_COMB = 2, 9, 10, 1
@@ -344,6 +346,9 @@ def lib():
     L.fec_canon_msm.argtypes = [vp, ci, vp, vp, sz, vp, vp]
     L.fec_canon_msm_dev.argtypes = [vp, ci, vp, vp, sz, vp, vp, vp]
     L.fec_ctx_set_canon_msm_window.argtypes = [vp, ci]
+    for name in ("fec_canon_bip340_batch_verify_msg", "fec_canon_ed25519_batch_verify_msg"):
+        getattr(L, name).argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, sz]
+        getattr(L, name + "_dev").argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp]
     for n in CANON_ABI_SYMBOLS:
         getattr(L, n).restype = ci
     _lib = L

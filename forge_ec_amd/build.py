@@ -19,7 +19,7 @@ SO = os.path.join(HERE, "libfecgpu.so")
 STAMP = SO + ".sha256"
 SOURCES = ["fecgpu.hip", "canon.hip", "kernels_p256.hip", "kernels_ed.hip", "kernels_secp.hip", "kernels_codec.hip", "kernels_ecdsa.hip", "kernels_x25519.hip", "kernels_eddsa.hip", "kernels_schnorr.hip", "kernels_rfc6979.hip", "kernels_ecdh.hip", "kernels_h2c.hip"]
 HEADERS = ["coop.hpp", "sched_lf.hpp", "limbs.hpp", "point_io.hpp", "staging.hpp", "host_ctx.hpp", "host_messages.hpp", "secp256k1.hpp", "secp_step.hpp", "p256.hpp", "ed25519.hpp", "curve25519.hpp", "sha512.hpp", "sha256.hpp", "bip340.hpp", "rfc6979.hpp", "schnorr_sign.hpp", "hkdf.hpp", "h2c.hpp", "codec_bytes.hpp", "eddsa_verify.hpp",
-           "canon_curves.hpp", "canon_kernels.hpp", "canon_msg.hpp", "canon_sign.hpp", "canon_sign_kernels.hpp", "canon_x25519.hpp", "canon_x25519_kernels.hpp", "keccak.hpp", "canon_recover.hpp", "canon_recover_kernels.hpp", "canon_bip32.hpp", "canon_bip32_kernels.hpp", "ripemd160.hpp", "canon_wallet.hpp", "canon_wallet_kernels.hpp", "canon_msm.hpp", "canon_msm_kernels.hpp", "field_asm.inc", "kernels.hpp", "messages.hpp", "cu_split.hpp", os.path.join("..", "..", "include", "fecgpu.h"),
+           "canon_curves.hpp", "canon_kernels.hpp", "canon_msg.hpp", "canon_sign.hpp", "canon_sign_kernels.hpp", "canon_x25519.hpp", "canon_x25519_kernels.hpp", "keccak.hpp", "canon_recover.hpp", "canon_recover_kernels.hpp", "canon_bip32.hpp", "canon_bip32_kernels.hpp", "ripemd160.hpp", "canon_wallet.hpp", "canon_wallet_kernels.hpp", "canon_msm.hpp", "canon_msm_kernels.hpp", "canon_batch.hpp", "canon_batch_kernels.hpp", "field_asm.inc", "kernels.hpp", "messages.hpp", "cu_split.hpp", os.path.join("..", "..", "include", "fecgpu.h"),
            os.path.join("..", "..", "include", "fecgpu_canon.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 

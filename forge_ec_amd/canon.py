@@ -41,6 +41,31 @@ def _verify_msg(lib_fn, h, msgs, sigs, pks, pk_len, what, lead=()):
     return out
 
 
+def _batch_verify_msg(lib_fn, h, msgs, sigs, pks, seed, what):
+    """the *_batch_verify_msg calls: (ok, status (n,), verdict); seed: 32 bytes or None (drawn by the library)"""
+    sg, pk = _bytes_rows(sigs, 64, "sigs"), _bytes_rows(pks, 32, "pks")
+    buf, off, total = Context._messages(msgs)
+    n = sg.shape[0]
+    if not (pk.shape[0] == n and len(off) == n + 1):
+        raise ValueError("inputs differ in length")
+    sd = None if seed is None else _bytes_rows(seed, 32, "seed")
+    if sd is not None and sd.shape[0] != 1:
+        raise ValueError("seed: 32 bytes")
+    st, verdict = np.zeros(n, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+    _check(lib_fn(h, _ptr(buf), _ptr(off), total, _ptr(sg), _ptr(pk), None if sd is None else _ptr(sd), _ptr(st), _ptr(verdict), n), what)
+    return bool(verdict[0] == 1 and not st.any()), st, int(verdict[0])
+
+
+def _batch_seed(seed):
+    """(pointer or None, the array that keeps it alive)"""
+    if seed is None:
+        return None, None
+    sd = _bytes_rows(seed, 32, "seed")
+    if sd.shape[0] != 1:
+        raise ValueError("seed: 32 bytes")
+    return _ptr(sd), sd
+
+
 def _sign_msg(lib_fn, h, msgs, secrets, what, lead=(), mid=(), after=()):
     """the *_sign_msg calls: (sigs (n,64), status (n,)); secrets = the 32-byte record arrays, in order."""
     buf, off, total = Context._messages(msgs)
@@ -399,6 +424,20 @@ class CanonSecp256k1(CanonCurve):
         _check(self._lib.fec_canon_bip340_verify_msg_dev(self._h, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, d_result, n,
                                                          stream), "fec_canon_bip340_verify_msg_dev")
 
+    def bip340_batch_verify_msg(self, msgs, sigs, pks, seed=None):
+        """BIP-340 batch verification (one random linear combination over the batch): -> (ok, status (n,) uint8, verdict).
+        status[i]: 0 admitted, 2 the key or R does not decode, 3 s >= n; verdict: 1 iff the equation holds over the admitted
+        elements; ok = verdict == 1 and no status set = every signature is valid.  verdict 0 does not say which signature
+        is bad: bip340_verify_msg does.  seed: 32 bytes, unpredictable to whoever chose the signatures and fresh per call;
+        None draws them from the operating system.  A fixed seed is for tests."""
+        return _batch_verify_msg(self._lib.fec_canon_bip340_batch_verify_msg, self._h, msgs, sigs, pks, seed, "fec_canon_bip340_batch_verify_msg")
+
+    def bip340_batch_verify_msg_dev(self, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, seed, d_status, d_verdict, n, stream=None):
+        """seed: 32 bytes in host memory (bytes or an array) or None; only enqueues."""
+        p, _keep = _batch_seed(seed)
+        _check(self._lib.fec_canon_bip340_batch_verify_msg_dev(self._h, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, p, d_status, d_verdict, n,
+                                                               stream), "fec_canon_bip340_batch_verify_msg_dev")
+
     def taproot_output_key(self, pks, roots=None, pk_len=32):
         """Taproot output keys (BIP-341): pks (n,pk_len), pk_len 32 (x-only) or 33 (tag 2 / 3, ignored); roots (n,32) Merkle
         roots or None (no script tree, BIP-86) -> (output keys (n,32) x-only, parity of y (n,), status).  status: 0, 2 (the key
@@ -450,6 +489,18 @@ class CanonEd25519(CanonCurve):
         """RFC 8032 Ed25519 verification from the message: msgs a list of n byte strings, sigs (n,64) R || S, pks (n,32).
         (n,) uint8, 1 = valid."""
         return _verify_msg(self._lib.fec_canon_ed25519_verify_msg, self._h, msgs, sigs, pks, 32, "fec_canon_ed25519_verify_msg")
+
+    def ed25519_batch_verify_msg(self, msgs, sigs, pks, seed=None):
+        """Ed25519 batch verification by the COFACTORED equation: -> (ok, status (n,) uint8, verdict), as
+        CanonSecp256k1.bip340_batch_verify_msg (status 3: S >= l).  Everything ed25519_verify_msg accepts is accepted here; a
+        signature whose defect S B - h A - R is a non-zero torsion point is accepted here and refused there."""
+        return _batch_verify_msg(self._lib.fec_canon_ed25519_batch_verify_msg, self._h, msgs, sigs, pks, seed, "fec_canon_ed25519_batch_verify_msg")
+
+    def ed25519_batch_verify_msg_dev(self, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, seed, d_status, d_verdict, n, stream=None):
+        """seed: 32 bytes in host memory (bytes or an array) or None; only enqueues."""
+        p, _keep = _batch_seed(seed)
+        _check(self._lib.fec_canon_ed25519_batch_verify_msg_dev(self._h, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, p, d_status, d_verdict, n,
+                                                                stream), "fec_canon_ed25519_batch_verify_msg_dev")
 
     def ed25519_verify_msg_dev(self, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, d_result, n, stream=None):
         _check(self._lib.fec_canon_ed25519_verify_msg_dev(self._h, d_msgs, d_msg_off, msg_len, d_sigs, d_pks, d_result, n,

@@ -13,6 +13,12 @@
 #include "canon_bip32_kernels.hpp"
 #include "canon_wallet_kernels.hpp"
 #include "canon_msm_kernels.hpp"
+#include "canon_batch_kernels.hpp"
+
+#include <sys/random.h>
+#include <sys/types.h>
+
+#include <cerrno>
 
 using namespace fecgpu;
 using namespace fecgpu::host;
@@ -799,7 +805,16 @@ struct MsmWork {
   u32 B, nseg;
   size_t cap, la, lb, words;
 };
-int msm_work(fec_ctx* ctx, int curve, int c, size_t cap, MsmWork& w) {
+// What batch verification (below) keeps behind the sum's regions in the same area: the prepared scalars and points of one
+// slice of `sigs` signatures (2 * sigs entries; the sum's last pair uses entry 0), one partial sum of the a_i s_i per prepare
+// workgroup, the running sum (32 bytes), and what the sum's last kernel and the verdict kernel leave: X, Y (64 bytes), the
+// sum's status byte (at 64) and the verdict (at 65).
+struct BatchWork {
+  u32 *scal, *pts, *part, *acc;
+  unsigned char* out;
+  size_t sigs;
+};
+int msm_work(fec_ctx* ctx, int curve, int c, size_t cap, MsmWork& w, BatchWork* b = nullptr) {
   namespace M = canon::msm;
   w.c = c;
   w.W = M::windows(c);
@@ -814,6 +829,7 @@ int msm_work(fec_ctx* ctx, int curve, int c, size_t cap, MsmWork& w) {
   area.add(w.misc, 256).add(w.dig, W * w.cap * 4).add(w.hist, W * (w.B + 1) * 4).add(w.skeys, W * w.cap * 4).add(w.sent, W * w.cap * 4);
   area.add(w.bucket, W * w.B * acc).add(w.keys_a, W * w.la * 4).add(w.pts_a, W * w.la * acc).add(w.keys_b, W * w.lb * 4).add(w.pts_b, W * w.lb * acc);
   area.add(w.red, 2 * W * w.nseg * acc);
+  if (b) area.add(b->scal, 2 * b->sigs * 32).add(b->pts, 2 * b->sigs * 64).add(b->part, grid_for(b->sigs) * 32).add(b->acc, 32).add(b->out, 128);
   return place_in_verify(ctx, area);
 }
 // The window width: the ctx's forced one, else read from the forced-window sweeps at 2^18 and 2^20 (profiles/canon_msm.jsonl,
@@ -937,6 +953,115 @@ int launch_canon_msm_host(fec_ctx* ctx, int curve, const u64* scalars, const u64
     if (rc != FEC_OK) return rc;
     if (hipMemcpyAsync(out_xy, d_xy, 64, hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(status, d_st, 1, hipMemcpyDeviceToHost, s) != hipSuccess)
       return FEC_E_DEVICE;
+    return sync_and_check(ctx, s);
+  });
+}
+
+// ---- batch (random linear combination) verification of BIP-340 and Ed25519 signatures from the message (canon_batch.hpp,
+// canon_batch_kernels.hpp) ---------------------------------------------------------------------------------
+// One verdict for the whole batch.  The batch goes through prepare -> fold -> one slice of the sum's pipeline in slices of at most
+// kBatchSlice signatures (2 entries each); the buckets and the running sum of the a_i s_i persist in the work area from slice
+// to slice.  Behind the last slice the generator's pair goes in as a slice of one, msm_finish runs, and the verdict kernel
+// reads what it leaves.  Nothing is read back to size a pass.
+constexpr size_t kBatchSlice = kMsmSlice / 2;
+// the caller's seed, or 32 bytes of the kernel's generator, as the words the coefficient hash reads
+int batch_seed(const uint8_t* seed, canon::batch::seed_words& out) {
+  uint8_t drawn[32];
+  if (!seed) {
+    for (size_t got = 0; got < sizeof drawn;) {
+      const ssize_t r = getrandom(drawn + got, sizeof drawn - got, 0);
+      if (r < 0 && errno != EINTR) return FEC_E_DEVICE;
+      if (r > 0) got += (size_t)r;
+    }
+    seed = drawn;
+  }
+  for (int j = 0; j < 8; ++j) out.w[j] = (u32)seed[4 * j] << 24 | (u32)seed[4 * j + 1] << 16 | (u32)seed[4 * j + 2] << 8 | (u32)seed[4 * j + 3];
+  return FEC_OK;
+}
+int batch_work(fec_ctx* ctx, int curve, size_t n, size_t slice, MsmWork& w, BatchWork& b) {
+  b.sigs = slice ? slice : 1;
+  return msm_work(ctx, curve, msm_window(ctx, 2 * n + 1), 2 * b.sigs, w, &b);
+}
+int batch_begin(int curve, const MsmWork& w, const BatchWork& b, hipStream_t s) {
+  if (hipMemsetAsync(b.acc, 0, 32, s) != hipSuccess) return FEC_E_DEVICE;
+  return msm_begin(curve, w, s);
+}
+// one slice of cnt <= b.sigs signatures, `first` = the index of its element 0 in the whole batch
+int batch_slice(int curve, const MsmWork& w, const BatchWork& b, const Messages& m, const uint8_t* d_sigs, const uint8_t* d_pks,
+                const canon::batch::seed_words& seed, u64 first, unsigned char* d_status, size_t cnt, hipStream_t s) {
+  if (cnt == 0) return FEC_OK;
+  const dim3 g(grid_for(cnt)), blk(TPB);
+  if (curve == FEC_ED25519) {
+    hipLaunchKernelGGL((k_canon_batch_prepare<true>), g, blk, 0, s, m, (const u32*)d_sigs, (const u32*)d_pks, seed, first, b.scal, b.pts, d_status,
+                       b.part, cnt);
+    hipLaunchKernelGGL((k_canon_batch_fold<canon::NEd>), dim3(1), blk, 0, s, (const u32*)b.part, (size_t)g.x, b.acc);
+  } else {
+    hipLaunchKernelGGL((k_canon_batch_prepare<false>), g, blk, 0, s, m, (const u32*)d_sigs, (const u32*)d_pks, seed, first, b.scal, b.pts, d_status,
+                       b.part, cnt);
+    hipLaunchKernelGGL((k_canon_batch_fold<canon::NSecp>), dim3(1), blk, 0, s, (const u32*)b.part, (size_t)g.x, b.acc);
+  }
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  return msm_slice(curve, w, (const u64*)b.scal, (const u64*)b.pts, 2 * cnt, s);
+}
+// behind the last slice: the generator's pair, the sum's tail, the verdict
+int batch_finish(int curve, const MsmWork& w, const BatchWork& b, unsigned char* d_verdict, hipStream_t s) {
+  if (curve == FEC_ED25519) hipLaunchKernelGGL((k_canon_batch_generator<ced, canon::NEd, false>), dim3(1), dim3(64), 0, s, (const u32*)b.acc, b.scal, b.pts);
+  else hipLaunchKernelGGL((k_canon_batch_generator<csecp, canon::NSecp, true>), dim3(1), dim3(64), 0, s, (const u32*)b.acc, b.scal, b.pts);
+  if (hipGetLastError() != hipSuccess) return FEC_E_LAUNCH;
+  int rc = msm_slice(curve, w, (const u64*)b.scal, (const u64*)b.pts, 1, s);
+  if (rc == FEC_OK) rc = msm_finish(curve, w, reinterpret_cast<u32*>(b.out), b.out + 64, s);
+  if (rc != FEC_OK) return rc;
+  const u32* xy = reinterpret_cast<const u32*>(b.out);
+  if (curve == FEC_ED25519) hipLaunchKernelGGL((k_canon_batch_verdict<ced>), dim3(1), dim3(64), 0, s, xy, (const u32*)(w.misc + 8), (const u32*)w.misc, d_verdict);
+  else hipLaunchKernelGGL((k_canon_batch_verdict<csecp>), dim3(1), dim3(64), 0, s, xy, (const u32*)(w.misc + 8), (const u32*)w.misc, d_verdict);
+  return hipGetLastError() == hipSuccess ? FEC_OK : FEC_E_LAUNCH;
+}
+// the resident batch: enqueue only (the seed travels to the kernels by value)
+int launch_canon_batch_verify(fec_ctx* ctx, int curve, const Messages& m, const uint8_t* d_sigs, const uint8_t* d_pks,
+                              const canon::batch::seed_words& seed, unsigned char* d_status, unsigned char* d_verdict, size_t n, void* stream) {
+  MsmWork w;
+  BatchWork b;
+  const size_t slice = n < kBatchSlice ? n : kBatchSlice;
+  int rc = batch_work(ctx, curve, n, slice, w, b);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = ordered_stream(ctx, stream);
+  rc = batch_begin(curve, w, b, s);
+  for (size_t lo = 0; lo < n && rc == FEC_OK; lo += slice)
+    rc = batch_slice(curve, w, b, Messages{m.bytes, m.off + lo, m.len}, d_sigs + lo * 64, d_pks + lo * 32, seed, lo, d_status + lo,
+                     n - lo < slice ? n - lo : slice, s);
+  return rc != FEC_OK ? rc : batch_finish(curve, w, b, d_verdict, s);
+}
+// the batch in host memory: the message engine stages one chunk of fec_ctx_set_chunk signatures at a time (with_messages: the
+// ctx's stream, synchronised per chunk, the statuses copied back per chunk); a chunk larger than a slice is walked in slices
+int launch_canon_batch_verify_host(fec_ctx* ctx, int curve, const MessageArgs& ma, const uint8_t* sigs, const uint8_t* pks,
+                                   const canon::batch::seed_words& seed, uint8_t* status, uint8_t* verdict, size_t n) {
+  if (!msg_layout_ok(ma.msgs, ma.off, ma.len, n)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return drained(ctx, [&]() -> int {
+    MsmWork w;
+    BatchWork b;
+    size_t slice = pipeline_chunk(ctx) < kBatchSlice ? pipeline_chunk(ctx) : kBatchSlice;
+    if (n < slice) slice = n;
+    int rc = batch_work(ctx, curve, n, slice, w, b);
+    if (rc != FEC_OK) return rc;
+    hipStream_t s = ordered_stream(ctx, nullptr);
+    rc = batch_begin(curve, w, b, s);
+    if (rc != FEC_OK) return rc;
+    size_t done = 0;   // (the chunks come in order, on one lane)
+    const HostArray h[] = {ragged(ma.off, 8), input(sigs, 64), input(pks, 32), output(status, 1)};
+    rc = with_messages(ctx, n, h, ma, [&](fec_ctx* c, void* const* d, const Messages& m, size_t cnt, hipStream_t st) -> int {
+      int r = FEC_OK;
+      for (size_t lo = 0; lo < cnt && r == FEC_OK; lo += slice)
+        r = batch_slice(curve, w, b, Messages{m.bytes, m.off + lo, m.len}, static_cast<const uint8_t*>(d[1]) + lo * 64,
+                        static_cast<const uint8_t*>(d[2]) + lo * 32, seed, done + lo, static_cast<unsigned char*>(d[3]) + lo,
+                        cnt - lo < slice ? cnt - lo : slice, st);
+      done += cnt;
+      (void)c;
+      return r;
+    });
+    if (rc == FEC_OK) rc = batch_finish(curve, w, b, b.out + 65, s);
+    if (rc != FEC_OK) return rc;
+    if (hipMemcpyAsync(verdict, b.out + 65, 1, hipMemcpyDeviceToHost, s) != hipSuccess) return FEC_E_DEVICE;
     return sync_and_check(ctx, s);
   });
 }
@@ -1175,6 +1300,23 @@ int canon_msm(fec_ctx* ctx, Where w, int curve, const uint64_t* scalars, const u
   if (!aligned16(scalars) || !aligned16(points_xy) || !aligned16(out_xy)) return FEC_E_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
   return launch_canon_msm(ctx, curve, scalars, points_xy, n, out_xy, status, w.stream);
+}
+
+// ---- batch verification: one verdict, n statuses.  Like the sum it is built on it is not element-wise and runs on one device, so
+// the checks are spelt out in host::message_call's order: the ctx, the required pointers (status and verdict whatever n is), the
+// *_dev alignments; the host form's layout check is the launcher's first step.  `seed` is host memory in both forms.
+int canon_batch_verify_msg(fec_ctx* ctx, Where w, int curve, const MessageArgs& ma, const uint8_t* sigs, const uint8_t* pks, const uint8_t* seed,
+                           uint8_t* status, uint8_t* verdict, size_t n) {
+  if (is_multi(ctx)) return FEC_E_UNSUPPORTED;   // the sum is fec_canon_msm's: one device
+  if (!ctx) return FEC_E_ARG;
+  if (!status || !verdict || (n && (!ma.off || !sigs || !pks)) || (ma.len && !ma.msgs)) return FEC_E_ARG;
+  if (w.dev && ((reinterpret_cast<uintptr_t>(ma.off) & 7u) || !aligned16(sigs) || !aligned16(pks))) return FEC_E_ARG;
+  canon::batch::seed_words sw;
+  if (const int rc = batch_seed(seed, sw)) return rc;
+  if (!w.dev) return launch_canon_batch_verify_host(ctx, curve, ma, sigs, pks, sw, status, verdict, n);
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  return launch_canon_batch_verify(ctx, curve, Messages{ma.msgs, reinterpret_cast<const u64*>(ma.off), (u64)ma.len}, sigs, pks, sw, status, verdict, n,
+                                   w.stream);
 }
 
 }  // namespace
@@ -1525,6 +1667,25 @@ int fec_canon_msm_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, 
 int fec_canon_msm(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* points_xy, size_t n, uint64_t* out_xy,
                   uint8_t* status) try {
   return canon_msm(ctx, kOnHost, curve, scalars, points_xy, n, out_xy, status);
+} FEC_ABI_CATCH_STATUS
+// batch verification: BIP-340 (secp256k1) and Ed25519
+int fec_canon_bip340_batch_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, const uint8_t* d_sigs,
+                                          const uint8_t* d_pks, const uint8_t* seed, uint8_t* d_status, uint8_t* d_verdict, size_t n,
+                                          void* stream) try {
+  return canon_batch_verify_msg(ctx, on_device(stream), FEC_SECP256K1, {d_msgs, d_msg_off, msg_len}, d_sigs, d_pks, seed, d_status, d_verdict, n);
+} FEC_ABI_CATCH_STATUS
+int fec_canon_bip340_batch_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* sigs,
+                                      const uint8_t* pks, const uint8_t* seed, uint8_t* status, uint8_t* verdict, size_t n) try {
+  return canon_batch_verify_msg(ctx, kOnHost, FEC_SECP256K1, {msgs, msg_off, msg_len}, sigs, pks, seed, status, verdict, n);
+} FEC_ABI_CATCH_STATUS
+int fec_canon_ed25519_batch_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len, const uint8_t* d_sigs,
+                                           const uint8_t* d_pks, const uint8_t* seed, uint8_t* d_status, uint8_t* d_verdict, size_t n,
+                                           void* stream) try {
+  return canon_batch_verify_msg(ctx, on_device(stream), FEC_ED25519, {d_msgs, d_msg_off, msg_len}, d_sigs, d_pks, seed, d_status, d_verdict, n);
+} FEC_ABI_CATCH_STATUS
+int fec_canon_ed25519_batch_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off, size_t msg_len, const uint8_t* sigs,
+                                       const uint8_t* pks, const uint8_t* seed, uint8_t* status, uint8_t* verdict, size_t n) try {
+  return canon_batch_verify_msg(ctx, kOnHost, FEC_ED25519, {msgs, msg_off, msg_len}, sigs, pks, seed, status, verdict, n);
 } FEC_ABI_CATCH_STATUS
 int fec_ctx_set_canon_msm_window(fec_ctx* ctx, int bits) try {
   if (!ctx || (bits != 0 && (bits < canon::msm::MIN_WINDOW || bits > canon::msm::MAX_WINDOW))) return FEC_E_ARG;

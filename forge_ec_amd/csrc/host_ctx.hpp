@@ -254,7 +254,7 @@ class WorkArea {
   }
 
  private:
-  static constexpr int kMaxRegions = 12;   // the multi-scalar multiplication has the most (canon.hip: MsmWork)
+  static constexpr int kMaxRegions = 16;   // batch verification has the most (canon.hip: MsmWork plus BatchWork)
   template <class T>
   static void assign(void* slot, char* at) {
     *static_cast<T**>(slot) = reinterpret_cast<T*>(at);

@@ -114,8 +114,8 @@ int fec_canon_eddsa_verify_dev(fec_ctx* ctx, const uint64_t* d_a_enc, const uint
  * *_dev forms: sigs, pks, in, xy 16-byte aligned, d_msg_off 8-byte aligned; every lane checks its own range and
  * a bad one gets result 4; FEC_E_UNSUPPORTED on a multi-device ctx.
  * result[i]: 1 valid, 0 invalid, 4 bad message range (*_dev only).
- * Not offered: DER signatures, Ed25519ph / Ed25519ctx, ECDSA with another hash; batch (random linear combination)
- * verification -- the sum it needs is fec_canon_msm at the end of this header, the layer that draws the coefficients is not. */
+ * Not offered: DER signatures, Ed25519ph / Ed25519ctx, ECDSA with another hash.  Batch (random linear combination)
+ * verification of BIP-340 and Ed25519 signatures is fec_canon_*_batch_verify_msg at the end of this header. */
 
 /* ECDSA with SHA-256 (FIPS 186-4 section 6.4 / SEC 1 section 4.1.4), FEC_SECP256K1 and FEC_P256 (FEC_ED25519:
  * FEC_E_UNSUPPORTED).  z = the 32 bytes of SHA-256(msg_i) read big-endian (both orders have 256 bits: no truncation);
@@ -496,13 +496,63 @@ int fec_canon_bip32_derive_pub_path_dev(fec_ctx* ctx, const uint8_t* d_parent_pk
  * its first cross-device data dependency.
  * fec_ctx_set_canon_msm_window: the window width c of the bucket method, 0 = chosen from n (the default), 2..16 = forced;
  * anything else FEC_E_ARG.  A tuning and testing knob: the result does not depend on it.
- * Not offered: a segmented form (many sums per call); batch (random linear combination) verification, which is now a thin layer
- * over this call -- where its coefficients come from is the open question. */
+ * Not offered: a segmented form (many sums per call).  Batch (random linear combination) verification is the layer below, built
+ * on this sum's pipeline. */
 int fec_canon_msm(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars /* n*4 */, const uint64_t* points_xy /* n*8 */,
                   size_t n, uint64_t* out_xy /* 8 */, uint8_t* status /* 1 */);
 int fec_canon_msm_dev(fec_ctx* ctx, fec_curve curve, const uint64_t* d_scalars, const uint64_t* d_points_xy, size_t n,
                       uint64_t* d_out_xy, uint8_t* d_status, void* stream);
 int fec_ctx_set_canon_msm_window(fec_ctx* ctx, int bits);
+
+/* ---- Batch verification: one verdict for n BIP-340 or Ed25519 signatures ----------------------------------------------------------
+ * The random-linear-combination check (BIP-340 "Batch Verification"; the Ed25519 batch verifiers of other libraries) from the
+ * message: messages, signatures and keys are laid out exactly as for fec_canon_bip340_verify_msg / fec_canon_ed25519_verify_msg,
+ * with the same alignment rules for the *_dev forms (sigs, pks 16-byte aligned, d_msg_off 8-byte aligned).  The hashes, the
+ * decoding, the coefficients, the scalar products and the sum -- 2 n + 1 products through fec_canon_msm's pipeline -- run on
+ * the device; one verdict byte and n status bytes come back.
+ *   BIP-340:  sum a_i R_i + sum (a_i e_i mod n) P_i + (-sum a_i s_i mod n) G == infinity,  R_i = lift_x(r_i), P_i = lift_x(pk_i)
+ *   Ed25519:  8 (sum a_i (-R_i) + sum (a_i h_i mod l) (-A_i) + (sum a_i S_i mod l) B) == (0, 1)
+ * status[i] says whether element i was admitted to the sum: 0 admitted; 3 s >= n (S >= l); FEC_CANON_BAD_POINT (2) the key or
+ * R does not decode -- BIP-340: lift_x of the key or of r fails, r >= p among it; Ed25519: RFC 8032 5.1.3 fails for A or R,
+ * non-canonical encodings included: the per-signature verifiers' rules -- 4 bad message range (*_dev only).  Where more than
+ * one applies: 4, then 3, then 2.  A refused element enters the sum as 0 * G: the arithmetic never sees an off-curve value.
+ * verdict[0] = 1 iff the equation holds over the admitted elements, else 0.  So "every signature is valid" is verdict == 1 and
+ * no status set; verdict == 1 with statuses set names exactly the bad signatures, with no second pass; verdict == 0 says that
+ * at least one admitted signature is bad and not which: LOCATING IT IS THE CALLER'S JOB, by running the per-signature verifier
+ * over the batch (or over halves of it).  n = 0: verdict 1.  status and verdict are required whatever n is (FEC_E_ARG when null).
+ * Coefficients: a_i = the first 16 bytes, read big-endian, of SHA-256(T || T || seed || le64(i)), T =
+ * SHA-256("fecgpu/batch-coefficient"), i the element's index in the whole batch (neither fec_ctx_set_chunk nor the internal
+ * slices change a coefficient); a zero is replaced by 1.  A bad signature passes with probability about 2^-128 over the seed.
+ * seed: 32 bytes in HOST memory in both forms (the *_dev form passes it to its kernels by value and stays enqueue-only), or
+ * NULL: 32 bytes are then drawn from getrandom(2).  THE SEED CONTRACT: the seed must be unpredictable to whoever chose the
+ * signatures, and fresh for every call.  Someone who knows the seed before choosing the signatures can make invalid signatures
+ * cancel.  A fixed seed is for tests.  (A seed hashed from the whole batch is not offered.)
+ * Ed25519 is verified by the COFACTORED equation, the only one for which a random linear combination is sound (in a
+ * cofactorless sum a torsion defect cancels with probability 1/8).  fec_canon_ed25519_verify_msg is cofactorless.  The
+ * consequence: every signature the per-signature verifier accepts is accepted here; a signature whose defect S B - h A - R is
+ * a non-zero point of order 2, 4 or 8 is accepted here and refused there; nothing else differs.
+ * Speed (one MI355X, resident 32-byte messages): BELOW ABOUT 2^19 SIGNATURES THE PER-SIGNATURE VERIFIER
+ * (fec_canon_bip340_verify_msg_dev, fec_canon_ed25519_verify_msg_dev) IS THE FASTER CALL -- the sum has a fixed tail: 0.61 to
+ * 0.98 times its speed from 2^10 to 2^18; from 2^19 on this call is faster, 1.19 (BIP-340) and 1.13 (Ed25519) times at 2^20,
+ * 1.26 and 1.14 times at 2^22.  At any size it is the call that returns one verdict without n results crossing to the host.
+ * Both forms: FEC_E_UNSUPPORTED on a multi-device ctx, as fec_canon_msm.  Host form: FEC_E_ARG on a bad message layout; the
+ * batch is staged in slices of fec_ctx_set_chunk signatures (at most 2^17), the buckets and the running sum persist on the
+ * device between slices.  The *_dev form only enqueues.  NOT constant-time; nothing is wiped: a call for public data.
+ * Not offered: locating the bad signature (bisection); ECDSA (it has no R to sum); Ed25519ph / Ed25519ctx. */
+int fec_canon_bip340_batch_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                                      const uint8_t* sigs /* n*64 */, const uint8_t* pks /* n*32 */,
+                                      const uint8_t* seed /* 32 bytes, host memory, may be NULL */, uint8_t* status /* n */,
+                                      uint8_t* verdict /* 1 */, size_t n);
+int fec_canon_bip340_batch_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                          const uint8_t* d_sigs, const uint8_t* d_pks, const uint8_t* seed /* HOST pointer or NULL */,
+                                          uint8_t* d_status, uint8_t* d_verdict, size_t n, void* stream);
+int fec_canon_ed25519_batch_verify_msg(fec_ctx* ctx, const uint8_t* msgs, const uint64_t* msg_off /* n+1 */, size_t msg_len,
+                                       const uint8_t* sigs /* n*64 */, const uint8_t* pks /* n*32 */,
+                                       const uint8_t* seed /* 32 bytes, host memory, may be NULL */, uint8_t* status /* n */,
+                                       uint8_t* verdict /* 1 */, size_t n);
+int fec_canon_ed25519_batch_verify_msg_dev(fec_ctx* ctx, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t msg_len,
+                                           const uint8_t* d_sigs, const uint8_t* d_pks, const uint8_t* seed /* HOST pointer or NULL */,
+                                           uint8_t* d_status, uint8_t* d_verdict, size_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,15 @@ with one of its comparator, fec_canon_mul_dev on the same n pairs -- what a call
 the CPU.  "size" rows: n = 2^10 .. 2^max in steps of 4x, random scalars, the automatic window.  "window" rows: n = 2^18 and 2^20 (or
 max), every forced window 8 .. 16 -- the sweep the automatic rule is read from.  "skew" rows at the same n: all scalars equal,
 and one point throughout, next to the random row.  Every row records the status byte the call left (0).
+
+Batch signature verification (fec_canon_bip340_batch_verify_msg_dev, fec_canon_ed25519_batch_verify_msg_dev):
+
+    python tools/canon_perf.py batch [max_log2_n] [reps] [out.jsonl]
+
+Inputs resident -- 32-byte messages, signatures made by the library's own signers -- wall clock around a device synchronise,
+median of `reps` (7); every batch sample alternates in this process with one of fec_canon_bip340_verify_msg_dev /
+fec_canon_ed25519_verify_msg_dev over the same signatures.  "size" rows: n = 2^10 .. 2^20, and 2^max above that where the
+signatures fit.  "all-refused" row: every s out of range, so the sum is 2 n + 1 times 0 * G.
 """
 import ctypes
 import json
@@ -865,6 +874,91 @@ def main_msm():
                 f.write(json.dumps(r) + "\n")
 
 
+def main_batch():
+    max_log = int(sys.argv[2]) if len(sys.argv) > 2 else 22
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    out_path = sys.argv[4] if len(sys.argv) > 4 else None
+    ctx = F.Context(0)
+    st = torch.cuda.current_stream().cuda_stream
+    rows, mlen = [], 32
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(31)
+    seed = bytes(range(32))
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    for scheme, cname in (("bip340", "secp256k1"), ("ed25519", "ed25519")):
+        c = CANON_CURVES[cname](ctx)
+        batch = c.bip340_batch_verify_msg_dev if scheme == "bip340" else c.ed25519_batch_verify_msg_dev
+        single = c.bip340_verify_msg_dev if scheme == "bip340" else c.ed25519_verify_msg_dev
+        nmax = 1 << max_log
+        try:     # 2^22 only where the signatures fit
+            msgs = torch.randint(0, 256, (nmax * mlen,), dtype=torch.uint8, device="cuda", generator=gen)
+            off = (torch.arange(nmax + 1, dtype=torch.int64, device="cuda") * mlen)
+            keys = torch.randint(0, 256, (nmax, 32), dtype=torch.uint8, device="cuda", generator=gen)
+            keys[:, 0] &= 0x7F        # a BIP-340 key below n
+            keys[:, 31] |= 1          # ... and not zero
+            sigs = torch.empty((nmax, 64), dtype=torch.uint8, device="cuda")
+            pks = torch.empty((nmax, 32), dtype=torch.uint8, device="cuda")
+            stat = torch.empty(nmax, dtype=torch.uint8, device="cuda")
+            res = torch.empty(nmax, dtype=torch.uint8, device="cuda")
+            verdict = torch.full((1,), 9, dtype=torch.uint8, device="cuda")
+            if scheme == "bip340":
+                aux = torch.zeros((nmax, 32), dtype=torch.uint8, device="cuda")
+                c.bip340_sign_msg_dev(msgs.data_ptr(), off.data_ptr(), nmax * mlen, keys.data_ptr(), aux.data_ptr(), sigs.data_ptr(), stat.data_ptr(), nmax, st)
+                torch.cuda.synchronize()
+                assert int(stat.count_nonzero()) == 0
+                c.public_key_dev(keys.data_ptr(), pks.data_ptr(), 32, stat.data_ptr(), nmax, st, scheme=3)
+            else:
+                c.ed25519_sign_msg_dev(msgs.data_ptr(), off.data_ptr(), nmax * mlen, keys.data_ptr(), sigs.data_ptr(), pks.data_ptr(), stat.data_ptr(), nmax, st)
+            torch.cuda.synchronize()
+            assert int(stat.count_nonzero()) == 0
+        except torch.cuda.OutOfMemoryError:
+            emit({"row": "skipped", "scheme": scheme, "max_log": max_log, "why": "the signatures do not fit"})
+            continue
+
+        def pair(n, sg):
+            """(batch median ms, per-signature median ms, spreads): the two calls alternate sample by sample"""
+            fns = (lambda: batch(msgs.data_ptr(), off.data_ptr(), n * mlen, sg.data_ptr(), pks.data_ptr(), seed, stat.data_ptr(), verdict.data_ptr(), n, st),
+                   lambda: single(msgs.data_ptr(), off.data_ptr(), n * mlen, sg.data_ptr(), pks.data_ptr(), res.data_ptr(), n, st))
+            samples = ([], [])
+            for i in range(reps + 1):
+                for smp, fn in zip(samples, fns):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    if i:
+                        smp.append((time.perf_counter() - t0) * 1e3)
+            srt = [sorted(x) for x in samples]
+            return srt[0][len(srt[0]) // 2], srt[1][len(srt[1]) // 2], srt[0][-1] - srt[0][0], srt[1][-1] - srt[1][0]
+
+        sizes = list(range(10, min(max_log, 20) + 1)) + ([max_log] if max_log > 20 else [])
+        for logn in sizes:
+            n = 1 << logn
+            b, s, bs, ss = pair(n, sigs)
+            ok = int(verdict.cpu()[0]) == 1 and int(stat[:n].count_nonzero()) == 0 and int(res[:n].sum()) == n
+            emit({"row": "size", "scheme": scheme, "n": n, "msg_bytes": mlen, "reps": reps, "batch_ms": round(b, 4), "batch_spread_ms": round(bs, 4),
+                  "single_ms": round(s, 4), "single_spread_ms": round(ss, 4), "single_over_batch": round(s / b, 3),
+                  "batch_M_per_s": round(n / b / 1e3, 3), "single_M_per_s": round(n / s / 1e3, 3), "all_valid": ok})
+        # every element refused (s = 2^256 - 1): what the batch call costs when the sum is 2 n + 1 times 0 * G
+        n = 1 << min(max_log, 20)
+        bad = sigs[:n].clone()
+        bad[:, 32:] = 255
+        b, s, bs, ss = pair(n, bad)
+        emit({"row": "all-refused", "scheme": scheme, "n": n, "msg_bytes": mlen, "reps": reps, "batch_ms": round(b, 4), "batch_spread_ms": round(bs, 4),
+              "single_ms": round(s, 4), "single_over_batch": round(s / b, 3), "verdict": int(verdict.cpu()[0]),
+              "every_status_3": int((stat[:n] == 3).sum()) == n})
+        del msgs, off, keys, sigs, pks, stat, res, bad
+        torch.cuda.empty_cache()
+    if out_path:
+        with open(out_path, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     logn = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -934,5 +1028,7 @@ elif len(sys.argv) > 1 and sys.argv[1] == "wallet":
     main_wallet()
 elif len(sys.argv) > 1 and sys.argv[1] == "msm":
     main_msm()
+elif len(sys.argv) > 1 and sys.argv[1] == "batch":
+    main_batch()
 else:
     main()
