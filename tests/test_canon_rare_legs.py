@@ -3,7 +3,10 @@ The rare legs of canonical mode (canon_curves.hpp) on the host, without a GPU: t
 __builtin_expect site and the reach counter that sits in it, tests/golden/canon_forcing_vectors.json
 (gen_canon_forcing.py) holds operands and points on which those counters move.  Here every case goes through the
 host emulation with the counters watched and is compared with oracle/canon_model.py;
-tests/test_gpu_canon_forcing.py drives the same cases through the kernels.
+tests/test_gpu_canon_forcing.py drives the same cases through the kernels, tests/test_gpu_canon_forcing_points.py the points
+through the later kernels that decode or test a caller's point; the census says which kernels those are, and here every
+__global__ of csrc/canon*_kernels.hpp must have its place in it.  tests/golden/canon_forcing_keyed_vectors.json
+(gen_canon_forcing_keyed.py) holds forcing points with known logarithms.
 """
 import ctypes
 import os
@@ -177,6 +180,155 @@ def test_points_are_on_the_curve_and_light_their_legs(emu):  # noqa: F811
     for key in FIELD_LEGS:   # at least one point per forced field leg, and a BIP-340 key among secp256k1's
         assert per_leg.get(CANON_LEGS[key]["counter"]), key
     assert any("bip340" in c for c in CANON["points"])
+
+
+# ---- the kernels that decode or test a caller's point ------------------------------------------------------------------
+# the kernels tests/test_gpu_canon_forcing.py drives; every other kernel of a canonical field leg is one of
+# tests/test_gpu_canon_forcing_points.py's and must be a key of its DRIVES
+DRIVEN_BY_THE_FIRST_FILE = {"k_canon_field_op", "k_canon_mul", "k_canon_decompress", "k_canon_ecdsa_prepare_msg", "k_canon_normalize",
+                            "k_canon_bip340_prepare", "k_ced_mul", "k_ced_eddsa_prepare"}
+WITHOUT_POINTS = CENSUS["canon_kernels_without_caller_points"]
+
+
+def canon_kernels():
+    """name -> file of every __global__ kernel in csrc/canon*_kernels.hpp (a declaration may run over several lines)"""
+    out = {}
+    for f in sorted(os.listdir(CSRC)):
+        if re.fullmatch(r"canon\w*_kernels\.hpp", f):
+            text = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, f)).read())
+            for m in re.finditer(r"__global__\b(?:\s*__launch_bounds__\([^)]*\))?\s*void\s+(\w+)\s*\(", text):
+                assert m.group(1) not in out, m.group(1)
+                out[m.group(1)] = f
+            assert len(re.findall(r"__global__", text)) == sum(1 for v in out.values() if v == f), f
+    return out
+
+
+def census_kernels():
+    """kernel -> the census keys that name it, over the canonical legs and the borrowed ones"""
+    named = {}
+    for key, rec in list(CANON_LEGS.items()) + list(CENSUS["canon_borrowed"].items()):
+        for k in rec.get("kernels", ()):
+            named.setdefault(k, []).append(key)
+    return named
+
+
+def test_every_canon_kernel_is_in_a_leg_or_has_no_caller_point():
+    """A new __global__ in a canon*_kernels.hpp fails here until someone decides where it belongs: in the kernels list of the
+    legs it can reach with a caller's point, or in canon_kernels_without_caller_points with the reason.  And the census
+    names no kernel that the sources do not have."""
+    found, named = canon_kernels(), census_kernels()
+    assert len(found) >= 71 and len(set(found.values())) >= 8   # (the scan itself: 71 kernels in 8 files when this was written)
+    homeless = sorted(set(found) - set(named) - set(WITHOUT_POINTS))
+    assert not homeless, "kernels in neither a leg's list nor canon_kernels_without_caller_points: %s" % homeless
+    gone = sorted((set(named) | set(WITHOUT_POINTS)) - set(found))
+    assert not gone, "the census names kernels that are not in csrc/canon*_kernels.hpp: %s" % gone
+    assert not set(named) & set(WITHOUT_POINTS)
+    assert all(isinstance(r, str) and len(r) > 8 for r in WITHOUT_POINTS.values())
+    # a kernel that calls on_curve or one of the decoders cannot be filed under "no caller's point", and the legs' lists name
+    # no other kernel than those -- but the field kernel, the normalisation and the comb kernels of the point legs
+    calling = set()
+    for f in set(found.values()):
+        text = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, f)).read())
+        for body in re.split(r"__global__", text)[1:]:
+            name = re.search(r"void\s+(\w+)\s*\(", body).group(1)
+            if re.search(r"\bon_curve\(|sec1_record<|sec1_decode<|tweak_key<|taproot_key<|bip340_lift_x\(|canon::bip340_prepare(_msg)?\(|"
+                         r"canon::eddsa_prepare(_msg)?\(|ed_decode\(|ecdsa_prepare_msg<|recover_prepare_group<|bip340_element\(|ed25519_element\(", body):
+                assert name in named, name
+                calling.add(name)
+    assert calling == set(named) - {"k_canon_field_op", "k_canon_normalize", "k_canon_mul_base", "k_canon_mul_base8", "k_canon_build_comb",
+                                    "k_canon_build_comb8"}, calling ^ set(named)
+
+
+def test_drives_names_a_test_for_every_later_kernel():
+    """every kernel of a canonical field leg that tests/test_gpu_canon_forcing.py does not drive is a key of
+    test_gpu_canon_forcing_points.DRIVES, and every function DRIVES names is a test of that module (imported without a GPU)"""
+    import test_gpu_canon_forcing_points as G
+    later = {k for key in FIELD_LEGS for k in CANON_LEGS[key]["kernels"]} - DRIVEN_BY_THE_FIRST_FILE
+    assert len(later) >= 9 and later <= set(G.DRIVES), later - set(G.DRIVES)
+    assert set(G.DRIVES) <= set(census_kernels())
+    for kernel, tests in G.DRIVES.items():
+        assert tests and all(t.startswith("test_") and callable(getattr(G, t, None)) for t in tests), kernel
+    for key in FIELD_LEGS:   # each curve's later kernels are on each of its legs
+        curve = re.search(r"::Fp(\w+)::", key).group(1)
+        same = [k for k in FIELD_LEGS if "::Fp%s::" % curve in k]
+        assert all(CANON_LEGS[k]["kernels"] == CANON_LEGS[key]["kernels"] for k in same), key
+
+
+# the decoding functions the later kernels call, as the host emulation exports them: name -> (curves, call(cnt, cid, point
+# record, out) -> (ok, lit), the model's point for it)
+def _decoders(c, pt, xy):
+    cid = c["curve"]
+    if cid == 2:
+        enc = _arr(int.from_bytes(bytes.fromhex(c["ed"]), "little"))
+        other = _arr(int.from_bytes(M.ED25519.encode(M.ED25519.G), "little"))
+        s, h, a, u = _arr(1), _arr(2), np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+        neg = (M.ED25519.P - pt[0], pt[1])   # eddsa_prepare negates A
+        return {"ed_decode": (("he_ed_decode", enc, xy), pt),
+                "eddsa_prepare as A": (("he_eddsa_prepare", enc, other, s, h, xy, a, u), neg),
+                "eddsa_prepare as R": (("he_eddsa_prepare", other, enc, s, h, a, xy, u), pt)}
+    out = {"sec1_33": (("he_canon_sec1_decode", cid, 2 | (pt[1] & 1), _arr(pt[0]), None, 0, xy), pt),
+           "sec1_33 other tag": (("he_canon_sec1_decode", cid, 3 - (pt[1] & 1), _arr(pt[0]), None, 0, xy), CURVES[cid].neg(pt)),
+           "sec1_65": (("he_canon_sec1_decode", cid, 4, _arr(pt[0]), _arr(pt[1]), 1, xy), pt)}
+    if cid == 0:
+        even = pt if pt[1] % 2 == 0 else M.SECP256K1.neg(pt)
+        u = np.zeros(4, dtype=np.uint64)
+        out["lift_x"] = (("he_bip340_lift_x", _arr(pt[0]), xy), even)
+        out["bip340_prepare"] = (("he_bip340_prepare", _arr(pt[0]), _arr(1), _arr(1), _arr(1), xy, u), even)
+    return out
+
+
+def test_every_decoding_function_lights_the_points_legs(emu):  # noqa: F811
+    """The points are known to light their legs in he_canon_mul, he_canon_on_curve and he_ed_decode; the later kernels call
+    33-byte decompression, bip340_lift_x (which sees x alone) and the batch verifier's decoders.  Every fixture point through
+    each of them: the point's legs fire and the function returns the model's point.  A pairing in which a leg does not fire
+    belongs in test_gpu_canon_forcing_points.NOT_LIT, which the GPU tests skip; the counters find none."""
+    import test_gpu_canon_forcing_points as G
+    cnt = Counters(emu)
+    xy = np.zeros(8, dtype=np.uint64)
+    dark, seen = {}, set()
+    for i, c in enumerate(CANON["points"]):
+        pt = (_int(c["x"]), _int(c["y"]))
+        for name, (call, want) in _decoders(c, pt, xy).items():
+            ok, lit = _run(cnt, *call)
+            assert ok == 1 and (M.unlimbs(xy[:4]), M.unlimbs(xy[4:])) == want, (c["family"], name)
+            if not set(c["legs"]) <= lit:
+                dark[(i, name)] = sorted(lit)
+            seen.add(name)
+    assert seen == {"sec1_33", "sec1_33 other tag", "sec1_65", "lift_x", "bip340_prepare", "ed_decode", "eddsa_prepare as A", "eddsa_prepare as R"}
+    assert dark == G.NOT_LIT, dark
+
+
+def test_keyed_points_are_multiples_of_g_that_light_their_leg(emu):  # noqa: F811
+    """tests/golden/canon_forcing_keyed_vectors.json: every point is k G by the model, lights its legs in on_curve, and each
+    decoding function lights exactly what the fixture records for it; lift_x returns the point of the negated logarithm."""
+    import json
+    import test_gpu_canon_forcing_points as G
+    doc, C = G.KEYED, M.SECP256K1
+    cnt = Counters(emu)
+    xy = np.zeros(8, dtype=np.uint64)
+    start, count = _int(doc["start"]), doc["count"]
+    assert count in (1 << 19, 1 << 20) and doc["curve"] == 0
+    assert [(r["candidates"], r["hits"]) for r in doc["searches"]] and sum(r["hits"] for r in doc["searches"]) >= len(doc["points"])
+    assert all(r["candidates"] == count and r["leg"] in cnt.names for r in doc["searches"])
+    through = 0
+    for p in doc["points"]:
+        k, pt = _int(p["k"]), (_int(p["x"]), _int(p["y"]))
+        assert start <= k < start + count and C.mul(k, C.G) == pt
+        c = {"curve": 0}
+        calls = _decoders(c, pt, xy)
+        calls["on_curve"] = (("he_canon_on_curve", 0, _arr(*pt)), None)
+        for name in ("on_curve", "sec1_33", "sec1_65", "lift_x"):
+            call, want = calls[name]
+            ok, lit = _run(cnt, *call)
+            assert ok == 1 and sorted(lit) == p["lit"][name], (p["k"], name, lit)
+            assert want is None or (M.unlimbs(xy[:4]), M.unlimbs(xy[4:])) == want
+        assert p["legs"] == p["lit"]["on_curve"] and p["legs"]
+        assert p["through_x"] == bool(set(p["legs"]) & set(p["lit"]["lift_x"]))
+        d = _int(p["bip340_d"])
+        assert d in (k, C.N - k) and C.mul(d, C.G) == R.lift_x(pt[0])
+        through += p["through_x"]
+    assert through == doc["through_x"] and (through >= 4 or "SHORTFALL" in doc["note"])
+    assert json.dumps(doc, indent=1, sort_keys=True) + "\n" == open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "canon_forcing_keyed_vectors.json")).read()
 
 
 def test_edge_scalars_light_the_addition_legs(emu):  # noqa: F811

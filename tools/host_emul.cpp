@@ -421,6 +421,23 @@ extern "C" int he_bip340_prepare(const uint64_t* pkx, const uint64_t* r, const u
   st(pxy, P.x); st(pxy + 4, P.y); st(u2, v);
   return ok ? 1 : 0;
 }
+// BIP-340 lift_x alone (the batch verifier lifts r with it): 1 = x < p and a root exists; xy = the point with even y
+extern "C" int he_bip340_lift_x(const uint64_t* x, uint64_t* xy) {
+  canon::aff P;
+  lmask ok = canon::bip340_lift_x(ld(x), P);
+  st(xy, P.x); st(xy + 4, P.y);
+  return ok ? 1 : 0;
+}
+// SEC 1 decoding (curve 0 secp256k1, 1 P-256) of a tag and the big-endian integers behind it: uncompressed = 0 takes the
+// root of x with the tag's parity (y is ignored), 1 tests (x, y) with on_curve.  1 = accepted
+extern "C" int he_canon_sec1_decode(int curve, unsigned tag, const uint64_t* x, const uint64_t* y, int uncompressed, uint64_t* xy) {
+  canon::aff Q;
+  const fe yy = y ? ld(y) : fe_zero();
+  lmask ok = curve == 0 ? canon::sec1_decode<canon::SecpParams>(tag, ld(x), yy, uncompressed != 0, Q)
+                        : canon::sec1_decode<canon::P256Params>(tag, ld(x), yy, uncompressed != 0, Q);
+  st(xy, Q.x); st(xy + 4, Q.y);
+  return ok ? 1 : 0;
+}
 extern "C" int he_ed_decode(const uint64_t* enc, uint64_t* xy) {
   canon::aff a;
   lmask ok = canon::ed_decode(ld(enc), a);
