@@ -24,7 +24,7 @@ ABI_SYMBOLS = [
     "fec_derive_key", "fec_derive_key_dev", "fec_ecdh_derive_key", "fec_ecdh_derive_key_dev", "fec_ecdh_exchange", "fec_ecdh_exchange_dev",
     "fec_expand_message_xmd", "fec_expand_message_xmd_dev", "fec_hash_to_field", "fec_hash_to_field_dev", "fec_map_to_curve",
     "fec_map_to_curve_dev", "fec_hash_to_curve", "fec_hash_to_curve_dev", "fec_curve_hash_to_curve", "fec_curve_hash_to_curve_dev",
-    "fec_debug_work_area_count", "fec_debug_work_area_read",
+    "fec_debug_work_area_count", "fec_debug_work_area_read", "fec_debug_fold_terms",
 ]
 # include/fecgpu_canon.h: the canonical-math mode (NOT reference parity)
 CANON_ABI_SYMBOLS = [
@@ -147,6 +147,8 @@ def lib():
     L.fec_field_op.argtypes = [vp, ci, ci, vp, vp, vp, sz]
     L.fec_multi_scalar_mul.argtypes = [vp, ci, vp, vp, vp, sz]
     L.fec_multi_scalar_mul.restype = ci
+    L.fec_debug_fold_terms.argtypes = [vp, ci, vp, vp, sz]
+    L.fec_debug_fold_terms.restype = ci
     L.fec_ecdsa_verify_secp256k1.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz]
     L.fec_ecdsa_verify_secp256k1.restype = ci
     L.fec_ecdsa_verify_secp256k1_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp]

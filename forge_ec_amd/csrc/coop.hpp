@@ -14,7 +14,15 @@ namespace coopx {
 // a slot is 32 bytes, 16-byte aligned (the caller's array is): two ds_read_b128 / ds_write_b128
 FEC_DEV fe ld(const u32* sh, int slot) { return load_fe16(sh + slot * 8); }
 FEC_DEV void st(u32* sh, int slot, const fe& a) { store_fe16(sh + slot * 8, a); }
-#ifdef FEC_HOST_EMUL
+#if defined(FEC_HOST_EMUL) && defined(FEC_HOST_EMUL_WAVE)
+// The wavefront as host threads (tests/cpp/coop_wave.cpp, the only program that defines FEC_HOST_EMUL_WAVE): every
+// thread is one lane and runs the cooperative additions themselves; the program sets each thread's lane and the
+// barrier all of its lanes meet at.
+static thread_local int wave_lane = 0;
+static void (*wave_barrier)() = nullptr;
+FEC_DEV void sync() { wave_barrier(); }
+FEC_DEV int lane_id() { return wave_lane; }
+#elif defined(FEC_HOST_EMUL)
 FEC_DEV void sync() {}
 FEC_DEV int lane_id() { return 0; }
 #else

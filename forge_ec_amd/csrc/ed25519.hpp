@@ -270,7 +270,7 @@ FEC_DEV pt padd_coop(u32* sh) {
   using coopx::ld;
   using coopx::st;
   const pt p = {ld(sh, PX), ld(sh, PY), ld(sh, PZ), ld(sh, PT)}, q = {ld(sh, QX), ld(sh, QY), ld(sh, QZ), ld(sh, QT)};
-#ifdef FEC_HOST_EMUL
+#if defined(FEC_HOST_EMUL) && !defined(FEC_HOST_EMUL_WAVE)
   return padd(p, q);
 #else
   const int lane = coopx::lane_id();

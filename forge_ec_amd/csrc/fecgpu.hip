@@ -1755,6 +1755,17 @@ int fec_batch_mul_fixed(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, 
   });
 } FEC_ABI_CATCH_STATUS
 
+// The ordered fold of n points in device memory into d_sum: one wavefront of k_fold_sum<C> on the ctx's stream
+// (fec_multi_scalar_mul on its products, fec_debug_fold_terms on the caller's terms).
+static int launch_fold_sum(fec_ctx* ctx, int curve, const u64* d_terms, u32* d_sum, size_t n) {
+  Launch L(ctx, nullptr, "k_fold_sum");
+  with_curve(curve, [&](auto c) {
+    using C = decltype(c);
+    hipLaunchKernelGGL((k_fold_sum<C>), dim3(1), dim3(64), 0, L.s, reinterpret_cast<const u32*>(d_terms), d_sum, n);
+  });
+  return L.done();
+}
+
 int fec_multi_scalar_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars, const uint64_t* points,
                          uint64_t* out, size_t n) try {
   FEC_FIRST_DEVICE(ctx);
@@ -1780,15 +1791,30 @@ int fec_multi_scalar_mul(fec_ctx* ctx, fec_curve curve, const uint64_t* scalars,
     if (rc == FEC_OK) rc = launch_mul(ctx, curve, false, d_scalars, d_points, d_products + lo * (pb / 8), cnt, nullptr);
     if (rc != FEC_OK) return rc;
   }
-  {
-    Launch L(ctx, nullptr, "k_fold_sum");
-    with_curve(curve, [&](auto c) {
-      using C = decltype(c);
-      hipLaunchKernelGGL((k_fold_sum<C>), dim3(1), dim3(64), 0, L.s, reinterpret_cast<const u32*>(d_products), d_sum, n);
-    });
-    rc = L.done();
-    if (rc != FEC_OK) return rc;
-  }
+  rc = launch_fold_sum(ctx, curve, d_products, d_sum, n);
+  if (rc != FEC_OK) return rc;
+  if (hipMemcpyAsync(out, d_sum, pb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
+  return sync_and_check(ctx, ctx->stream);
+  });
+} FEC_ABI_CATCH_STATUS
+
+// Test hook (include/fecgpu.h): fec_multi_scalar_mul's fold on terms the caller supplies instead of products.
+int fec_debug_fold_terms(fec_ctx* ctx, fec_curve curve, const uint64_t* terms, uint64_t* out, size_t n) try {
+  FEC_FIRST_DEVICE(ctx);
+  if (!ctx || !curve_ok(curve) || !out || (n && !terms)) return FEC_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return FEC_E_DEVICE;
+  const size_t pb = (size_t)plimbs(curve) * 8;
+  return drained(ctx, [&]() -> int {
+  u32* d_sum;
+  WorkArea record;
+  record.add(d_sum, pb);
+  int rc = ensure(ctx, kStageBody, record.bytes());
+  if (rc != FEC_OK) return rc;
+  record.place(ctx->d_buf[kStageBody]);
+  const u64* d_terms = nullptr;   // n == 0: the kernel reads no term
+  if (n) rc = upload(ctx, kStageIn, n, ctx->stream, arrays(input(terms, pb)), d_terms);
+  if (rc == FEC_OK) rc = launch_fold_sum(ctx, curve, d_terms, d_sum, n);
+  if (rc != FEC_OK) return rc;
   if (hipMemcpyAsync(out, d_sum, pb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return FEC_E_DEVICE;
   return sync_and_check(ctx, ctx->stream);
   });

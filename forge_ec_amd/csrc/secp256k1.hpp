@@ -579,7 +579,7 @@ FEC_DEV void level(u32* sh, int n, int a0, int a1, int a2, int a3, int b0, int b
 // the caller, followed by coopx::sync()); slot ONE holds the constant 1.  Every lane returns the sum.
 FEC_DEV pt padd_coop(u32* sh) {
   using namespace coop;
-#ifdef FEC_HOST_EMUL
+#if defined(FEC_HOST_EMUL) && !defined(FEC_HOST_EMUL_WAVE)
   const pt p0 = {ld(sh, PX), ld(sh, PY), ld(sh, PZ)}, q0 = {ld(sh, QX), ld(sh, QY), ld(sh, QZ)};
   return padd(p0, q0);
 #else

@@ -185,6 +185,16 @@ class Context:
                "fec_multi_scalar_mul")
         return out
 
+    def debug_fold_terms(self, curve, terms):
+        """fec_debug_fold_terms: test hook, not part of the reference's surface -- multi_scalar_mul's ordered fold
+        (identity + terms[0] + terms[1] + ..., the reference's Add) on raw points the caller supplies."""
+        pl = L.POINT_LIMBS[curve]
+        t = _u64(terms, pl)
+        out = np.empty(pl, dtype=np.uint64)
+        _check(self._lib.fec_debug_fold_terms(self._h, curve, _ptr(t) if t.shape[0] else None, _ptr(out), t.shape[0]),
+               "fec_debug_fold_terms")
+        return out
+
     def _ecdsa_verify(self, fn, what, digests, r, s, pk_xy, pk_inf):
         d = np.ascontiguousarray(np.asarray(digests, dtype=np.uint8)).reshape(-1, 32)
         rr, ss, pk = _u64(r, 4), _u64(s, 4), _u64(pk_xy, 8)

@@ -444,6 +444,14 @@ int fec_ctx_wipe(fec_ctx* ctx);
  * Reads only: no kernel is launched, nothing is allocated on the device and no state of the ctx changes. */
 int fec_debug_work_area_count(fec_ctx* ctx);
 int fec_debug_work_area_read(fec_ctx* ctx, int index, void* host_out, size_t cap, size_t* bytes, const char** name);
+/* fec_debug_fold_terms: test hook, NOT part of the reference's surface -- the ordered fold of fec_multi_scalar_mul on
+ * terms the caller supplies instead of products: out (one point) = identity + terms[0] + terms[1] + ..., left to right
+ * with the reference's Add, by the launch fec_multi_scalar_mul ends with (the same kernel, launcher and error handling).
+ * The terms are raw projective (Ed25519: extended) limbs and need not be on the curve, so that a test can drive every
+ * early-out of the cooperative additions (tests/test_gpu_fold_legs.py): identity terms, a term equal to the running
+ * sum, a term that cancels it.  n == 0 gives the identity.  FEC_E_ARG, with nothing launched, for a null ctx or out,
+ * null terms with n != 0, or a bad curve.  A multi-device ctx runs it on devices[0], as fec_multi_scalar_mul. */
+int fec_debug_fold_terms(fec_ctx* ctx, fec_curve curve, const uint64_t* terms /* n*limbs */, uint64_t* out /* limbs */, size_t n);
 
 /* The sticky device error state of the ctx, for callers of the *_dev entry points (those return once the work
  * is enqueued, so a fault reported by a kernel can only be seen afterwards; the host-pointer entry points do this

@@ -108,6 +108,7 @@ extern "C" {
     fn fec_schnorr_sign_msg(ctx: *mut FecCtx, curve: c_int, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, r_xy: *mut u64, r_inf: *mut u8, s: *mut u64, sig_bytes: *mut u8, status: *mut u8, n: usize) -> c_int;
     fn fec_schnorr_sign_msg_dev(ctx: *mut FecCtx, curve: c_int, d_sk: *const u64, d_msgs: *const u8, d_msg_off: *const u64, msg_len: usize, d_r_xy: *mut u64, d_r_inf: *mut u8, d_s: *mut u64, d_sig_bytes: *mut u8, d_status: *mut u8, n: usize, stream: *mut c_void) -> c_int;
     fn fec_debug_rfc6979_k(ctx: *mut FecCtx, curve: c_int, order_override: *const u64, sk: *const u64, msgs: *const u8, msg_off: *const u64, msg_len: usize, k: *mut u64, status: *mut u8, n: usize) -> c_int;
+    fn fec_debug_fold_terms(ctx: *mut FecCtx, curve: c_int, terms: *const u64, out: *mut u64, n: usize) -> c_int;
     fn fec_debug_work_area_count(ctx: *mut FecCtx) -> c_int;
     fn fec_debug_work_area_read(ctx: *mut FecCtx, index: c_int, host_out: *mut c_void, cap: usize, bytes: *mut usize, name: *mut *const c_char) -> c_int;
     fn fec_derive_key(ctx: *mut FecCtx, curve: c_int, secrets: *const u8, secret_len: usize, info: *const u8, info_len: usize, out_len: usize, keys: *mut u8, n: usize) -> c_int;
@@ -556,6 +557,16 @@ pub fn multi_scalar_multiply<C: GpuCurve>(ctx: &mut GpuContext, points: &[C::Poi
     let mut out = vec![0u64; C::LIMBS];
     // SAFETY: as above; `out` holds one point.
     check(unsafe { fec_multi_scalar_mul(ctx.raw, C::ID, k.as_ptr(), p.as_ptr(), out.as_mut_ptr(), points.len()) })?;
+    Ok(C::point_from_limbs(&out))
+}
+
+/// Test hook (`fec_debug_fold_terms`), not part of the reference's surface: the ordered fold of
+/// `multi_scalar_multiply` on points the caller supplies instead of products.
+pub fn debug_fold_terms<C: GpuCurve>(ctx: &mut GpuContext, terms: &[C::PointProjective]) -> Result<C::PointProjective> {
+    let p = pack_points::<C>(terms);
+    let mut out = vec![0u64; C::LIMBS];
+    // SAFETY: `p` holds terms.len() points (the call reads none when it is empty); `out` holds one point.
+    check(unsafe { fec_debug_fold_terms(ctx.raw, C::ID, p.as_ptr(), out.as_mut_ptr(), terms.len()) })?;
     Ok(C::point_from_limbs(&out))
 }
 

@@ -105,7 +105,13 @@ PARITY = {
     "fec_map_to_curve": ["ctx", "curve"] + _s32("u") + [arr("xy", 64), arr("cand", 64, False), arr("legs", 1, False), "n"],
 }
 
-HOST = dict(list(CANON.items()) + list(CANON_HOST_ONLY.items()) + list(CANON_HASH.items()) + list(PARITY.items()))
+# the test hook that folds a caller's terms (host form only).  It is younger than the golden file's recording: its rows
+# there are the statuses include/fecgpu.h states -- FEC_E_ARG for a null ctx, terms or out and for a bad curve.
+HOOKS = {
+    "fec_debug_fold_terms": ["ctx", "curve3", arr("terms", PT), arr("out", PT), "n"],
+}
+
+HOST = dict(list(CANON.items()) + list(CANON_HOST_ONLY.items()) + list(CANON_HASH.items()) + list(PARITY.items()) + list(HOOKS.items()))
 DEV = {name + "_dev": spec + ["stream"] for name, spec in list(CANON.items()) + list(PARITY.items())}
 DEV.update({name + "_dev": spec[:-1] + [ST_OPT, "n", "stream"] for name, spec in CANON_HASH.items()})
 
@@ -122,6 +128,7 @@ TABLES = ((HOST, False), (DEV, True))
 N0 = "n=0,every array null"
 N0_REFUSED = {
     "fec_batch_mul_fixed",                                           # the host form wants the base whatever n is
+    "fec_debug_fold_terms",                                          # out receives the identity at n = 0: it may not be null
     "fec_canon_bip32_derive_pub", "fec_canon_bip32_derive_pub_dev",  # n_par = 8 is neither 1 nor n = 0 ...
     "fec_canon_bip32_derive_priv", "fec_canon_bip32_derive_priv_dev",
     "fec_canon_bip32_derive_pub_path",                               # ... (its *_dev form returns at n = 0 before it looks)
@@ -142,7 +149,8 @@ def record(path):
         got = run_table(L.lib(), ctx._h, multi._h, TABLES, EXTRA)
         ctx.check()
     got["_recorded"] = ("statuses of run_table (tests/test_gpu_abi_arg_codes.py) on a build of the commit before the host and *_dev "
-                        "forms of each entry point were merged into one function; not to be regenerated from a later library")
+                        "forms of each entry point were merged into one function; not to be regenerated from a later library "
+                        "(fec_debug_fold_terms, added later, has the statuses include/fecgpu.h states for it)")
     with open(path, "w") as f:
         json.dump(got, f, indent=0, sort_keys=True)
         f.write("\n")

@@ -129,6 +129,32 @@ def test_census_names_every_rare_leg():
         assert leg.get("reason") or leg["status"] == "forced", key
 
 
+def test_padd_coop_sub_legs_have_forcing_cases(oracle):
+    """The cooperative additions hold several early-outs inside one __builtin_expect branch: the census names each of them
+    (the legs of tests/fold_cases.py), and every one has cases of that table that take it at two indices or more, the
+    routes that reach it -- always the hook and the host wavefront -- and, where no public caller can, the reason."""
+    import fold_cases as FC
+    keys = {"secp256k1.hpp::padd_coop#0": FC.SECP, "p256.hpp::padd_coop#0": FC.P256, "ed25519.hpp::padd_coop#0": FC.ED}
+    assert {k for k in CENSUS["legs"] if "::padd_coop#" in k} == set(keys)
+    for key, curve in keys.items():
+        leg = CENSUS["legs"][key]
+        assert "not constructed" not in leg["reason"] and set(leg["kernels"]) == {"k_fold_sum", "k_schnorr_fold_compare"}
+        assert set(leg["sub_legs"]) == set(FC.LEGS[curve]), key
+        table = {c.name: c for c in FC.cases(oracle, curve)}
+        for name, sub in leg["sub_legs"].items():
+            assert sub["what"] and sub["cases"], (key, name, "a sub-leg without a forcing case")
+            where = set()
+            for case in sub["cases"]:
+                assert case in table, (key, name, case)
+                hits = [i for i, l in enumerate(table[case].legs) if l == name and (i > 0 or table[case].kinds[0] != "ord")]
+                assert hits, (key, name, case, "the case does not take the sub-leg")
+                where.update(hits)
+            assert len(where) >= 2, (key, name, where)
+            kinds = [r.split(" ", 1)[0] for r in sub["routes"]]
+            assert kinds in (["hook", "public", "host"], ["hook", "host"]), (key, name, kinds)
+            assert ("public" in kinds) != bool(sub.get("no_public_caller")), (key, name)
+
+
 def test_census_counters_and_families(emu):
     names = set(Counters(emu).names)
     fams = {}
