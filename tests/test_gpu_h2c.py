@@ -130,6 +130,7 @@ def test_expander_host_and_dev(gpu_ctx, dst_len):
         assert np.array_equal(gpu_ctx.expand_message_xmd(msgs, dst, out_len), want), out_len
         d_out = torch.full((n * out_len + GUARD,), 0xA5, dtype=torch.uint8, device=keep[0].device)
         d_st = torch.full((n,), 9, dtype=torch.uint8, device=keep[0].device)
+        torch.cuda.synchronize()   # the fills run on torch's stream, the call on the ctx's own (non-blocking): a late fill put the 9 back
         gpu_ctx.expand_message_xmd_dev(pm, po, total, dst, out_len, d_out.data_ptr() if out_len else None, d_st.data_ptr(), n)
         torch.cuda.synchronize()
         gpu_ctx.check()
@@ -160,6 +161,7 @@ def test_hash_to_field_host_and_dev(gpu_ctx, curve):
         n = len(msgs)
         keep, pm, po, total = _dev_msgs(torch, msgs, shift=3)
         d_u = torch.full((n * count * 32 + GUARD,), 0xA5, dtype=torch.uint8, device=keep[0].device)
+        torch.cuda.synchronize()   # (the fill, on torch's stream, ahead of the call on the ctx's own)
         gpu_ctx.hash_to_field_dev(curve, pm, po, total, dst, count, d_u.data_ptr(), None, n)
         torch.cuda.synchronize()
         got = d_u.cpu().numpy()
@@ -212,6 +214,7 @@ def test_hash_dev_form(gpu_ctx, curve, n):
         d_cand = torch.full((n * 128 + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
         d_legs = torch.full((n * 2 + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
         d_st = torch.full((n,), 9, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()   # (the fills, on torch's stream, ahead of the call on the ctx's own)
         gpu_ctx.hash_to_curve_dev(curve, pm, po, total, dst, d_out.data_ptr(), d_cand.data_ptr() if with_cand else None,
                                   d_legs.data_ptr() if with_legs else None, d_st.data_ptr(), n)
         torch.cuda.synchronize()
@@ -261,6 +264,7 @@ def test_encode_is_the_map_of_count_one(gpu_ctx, curve):
     d_out = torch.full((n * 96 + GUARD,), 0xA5, dtype=torch.uint8, device=keep[0].device)
     d_cand = torch.zeros(n * 64, dtype=torch.uint8, device=keep[0].device)
     d_legs = torch.full((n + GUARD,), 0xA5, dtype=torch.uint8, device=keep[0].device)
+    torch.cuda.synchronize()   # (the fills, on torch's stream, ahead of the call on the ctx's own)
     gpu_ctx.encode_to_curve_dev(curve, pm, po, total, dst, d_out.data_ptr(), d_cand.data_ptr(), d_legs.data_ptr(), None, n)
     torch.cuda.synchronize()
     o, lg = d_out.cpu().numpy(), d_legs.cpu().numpy()
@@ -295,6 +299,7 @@ def test_trait_method(gpu_ctx, curve):
         d_xy = torch.full((n * 64 + GUARD,), 0xA5, dtype=torch.uint8, device=keep[0].device)
         d_inf = torch.full((n + GUARD,), 0xA5, dtype=torch.uint8, device=keep[0].device)
         d_st = torch.full((n,), 9, dtype=torch.uint8, device=keep[0].device)
+        torch.cuda.synchronize()   # (the fills, on torch's stream, ahead of the call on the ctx's own)
         gpu_ctx.curve_hash_to_curve_dev(curve, pm, po, total, dst if dst_len else None, d_xy.data_ptr(), d_inf.data_ptr(), d_st.data_ptr(), n)
         torch.cuda.synchronize()
         o, fl = d_xy.cpu().numpy(), d_inf.cpu().numpy()
@@ -311,6 +316,7 @@ def test_map_to_curve_dev_on_planted_limbs(gpu_ctx, curve):
     d_xy = torch.full((n * 64 + GUARD,), 0xA5, dtype=torch.uint8, device=d_u.device)
     d_cand = torch.full((n * 64 + GUARD,), 0xA5, dtype=torch.uint8, device=d_u.device)
     d_legs = torch.full((n + GUARD,), 0xA5, dtype=torch.uint8, device=d_u.device)
+    torch.cuda.synchronize()   # (the fills, on torch's stream, ahead of the call on the ctx's own)
     gpu_ctx.map_to_curve_dev(curve, d_u.data_ptr(), d_xy.data_ptr(), d_cand.data_ptr(), d_legs.data_ptr(), n)
     torch.cuda.synchronize()
     xy, cand, legs = d_xy.cpu().numpy(), d_cand.cpu().numpy(), d_legs.cpu().numpy()
